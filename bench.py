@@ -14,6 +14,12 @@ the gather-free figure is reported beside it.
 Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line.  With N > 1 and no
 WORLD_SIZE in the environment this process starts the N ranks itself (before touching the GPU) and
 relays rank 0's line; under `torch.distributed.run` it is one of the ranks.
+
+A plain run does only what the headline needs: set-up, spin-up and warm-up, the K timed steps (and
+for N > 1 the gather), the result line.  `--full` adds every measurement reported beside the
+headline (K1 kernel leg and rooflines, the kernel K1 replaced, other sample rates, the record sanity
+check, host boundary, decode, CPU baseline, the N > 1 assembly check).  `--dump-outputs DIR` writes
+rank 0's records of the last timed step as float32 .npy files (see `record_arrays`).
 """
 import argparse
 import json
@@ -65,6 +71,42 @@ def chord(np, t0, t_count):
     return x.astype(np.float32).reshape(-1)
 
 
+DUMP_PAYLOAD_FRAMES = 3072  # payload rows in --dump-outputs: all 4096 would be exactly 64 MiB of float32
+
+
+def record_arrays(np, records, rec_bytes, channels, n_payload=None):
+    """The fixed-size frame records of include/glc.h as float32 arrays, every value exact and every
+    shape fixed by the frame count alone: is_raw [frames], scale and nnz [frames, ch], and for a
+    fixed, seeded sample of `n_payload` frames (all frames if None; their indices, ascending, in
+    payload_frames) payload [sample, ch, 2048] as a reader of the record takes it: a compressed
+    frame's dense quantised row in [0, 1024) and zeros after it, a raw frame's windowed i16 plane.
+    Bytes the encoder leaves undefined (header padding, payload[c][1024:] of a compressed frame) are
+    not read, so equal encodes give equal arrays."""
+    hdr = rec_bytes - 2 * 2 * HOP * channels
+    rec = np.ascontiguousarray(records, np.uint8).reshape(-1, rec_bytes)
+    nf = rec.shape[0]
+    frames = np.arange(nf)
+    if n_payload is not None and n_payload < nf:
+        frames = np.sort(np.random.RandomState(0).choice(nf, n_payload, replace=False))
+    is_raw = rec[:, 0:4].copy().view(np.uint32)[:, 0] != 0
+    head = rec[:, 8:8 + 8 * channels].copy()
+    payload = np.ascontiguousarray(rec[frames, hdr:]).view(np.int16).reshape(-1, channels, 2 * HOP)
+    payload[~is_raw[frames], :, HOP:] = 0
+    return {"is_raw": is_raw.astype(np.float32),
+            "scale": head.view(np.float32).reshape(-1, channels, 2)[:, :, 0].copy(),
+            "nnz": head.view(np.uint32).reshape(-1, channels, 2)[:, :, 1].astype(np.float32),
+            "payload_frames": frames.astype(np.float32),
+            "payload": payload.astype(np.float32)}
+
+
+def dump_outputs(np, out_dir, arrays):
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64_000_000, f"--dump-outputs: {total} bytes exceed the 64 MB budget"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 SPINUP_STEPS = 500  # untimed, before the --warmup steps
 DECODE_SPINUP_CALLS = 400  # untimed decode calls before the decode leg is timed
 
@@ -82,10 +124,14 @@ def launch_ranks(args):
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__),
            "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup),
            "--spinup", str(args.spinup)]
+    if args.full:
+        cmd.append("--full")
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
     if args.lean:
         cmd.append("--lean")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE)
     line = None
     for ln in p.stdout.decode("utf-8", "replace").splitlines():
@@ -104,12 +150,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also every measurement beside the headline (rooflines, other rates, decode, host boundary, CPU baseline, checks)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--lean", action="store_true",
-                    help="only the timed steps and the K1 leg (profiling runs: no other rates, decode, host boundary, CPU baseline, child process)")
+                    help="with --full: only the timed steps and the K1 leg (profiling runs: no other rates, decode, host boundary, CPU baseline, child process)")
     ap.add_argument("--spinup", type=int, default=SPINUP_STEPS,
                     help="untimed steps before --warmup that bring the device clock up after the idle set-up phase")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write rank 0's frame records of the last timed step to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.lean and not args.full:
+        ap.error("--lean narrows --full; pass both")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args)
     # The contract is ONE JSON line on stdout.  Native libraries write there too (RCCL prints a
@@ -208,11 +260,14 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed, t_steps = float(tt[0].item()), float(tt[1].item())
     barrier()
+    if args.dump_outputs and rank == 0:   # before any later leg writes d_rec again
+        dump_outputs(np, args.dump_outputs, record_arrays(np, d_rec.cpu().numpy(), rec_bytes, CH,
+                                                                  DUMP_PAYLOAD_FRAMES))
 
     samples_per_step = FRAMES_PER_GPU * HOP * CH * world
     value = samples_per_step * args.steps / elapsed / 1e6
 
-    # ---- the gathered blobs assemble into one valid stream (rank 0) ----------------------
+    # ---- the gather's sizes; with --full, the gathered blobs assemble into one valid stream (rank 0)
     gather = None
     if dist_on:
         gather = {"ms": round((elapsed - t_steps) * 1e3, 3),
@@ -226,6 +281,7 @@ def main():
             sizes = [int(b.numel()) for b in blobs]
             gather["bytes_to_root"] = int(sum(sizes[1:]))
             gather["dense_record_bytes_to_root"] = int(rec_bytes * FRAMES_PER_GPU * (world - 1))
+        if rank == 0 and args.full:
             ea = shard.assemble_frame_shards(blobs, SR, n_samples, CH)
             gather["assembled_frames"] = int(ea.info().n_frames)
             gather["assembled_raw_frames"] = int(ea.info().n_raw_frames)
@@ -240,6 +296,36 @@ def main():
                 gather["assembled_equals_single_rank"] = bool(single.to_bytes() == ea.to_bytes())
                 assert gather["assembled_equals_single_rank"], "gathered stream differs from the single-rank encode"
                 del whole, single
+
+    out = {
+        "metric": "Msamples/s encoded (48 kHz stereo batch) at 1/2/4/8 GPUs; % HBM roofline",
+        "value": round(value, 2),
+        "unit": "Msamples/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": "BASELINE configs[1]: batch-encode 4096 frames x 1024 samples, "
+                               "48 kHz stereo synthetic PCM (16-tone chord per channel) per GPU",
+                   "frames_per_gpu": FRAMES_PER_GPU, "channels": CH, "sample_rate": SR,
+                   "samples_per_step": samples_per_step,
+                   "sharding": f"frame-range x{world}" + (", one gather of the compact blobs at the end "
+                                                           "(inside the timed region)" if dist_on else ""),
+                   "spinup_steps": args.spinup},
+        "gather": gather,
+    }
+    if not args.full:
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(real_stdout, (json.dumps(out) + "\n").encode())
+        if dist_on:
+            dist.destroy_process_group()
+        return
 
     # ---- dominant kernel (K1, forward MDCT) timed alone with events on ITS stream -------
     k1_reps = max(10, min(args.steps, 50))
@@ -489,26 +575,8 @@ def main():
         dist.barrier()   # rank 0's single-rank legs (decode, host boundary, CPU baseline) are done
     if rank == 0:
         k1_peak_held = F32_PEAK_TFLOPS * k1_clock_ghz / 2.4 if k1_clock_ghz else None
-        out = {
-            "metric": "Msamples/s encoded (48 kHz stereo batch) at 1/2/4/8 GPUs; % HBM roofline",
-            "value": round(value, 2),
-            "unit": "Msamples/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": "BASELINE configs[1]: batch-encode 4096 frames x 1024 samples, "
-                                   "48 kHz stereo synthetic PCM (16-tone chord per channel) per GPU",
-                       "frames_per_gpu": FRAMES_PER_GPU, "channels": CH, "sample_rate": SR,
-                       "samples_per_step": samples_per_step,
-                       "sharding": f"frame-range x{world}" + (", one gather of the compact blobs at the end "
-                                                               "(inside the timed region)" if dist_on else ""),
-                       "spinup_steps": args.spinup, "decode_spinup_calls": DECODE_SPINUP_CALLS},
+        out["config"]["decode_spinup_calls"] = DECODE_SPINUP_CALLS
+        out.update({
             "roofline": {"bound": "valu", "kernel": K1_KERNEL, "achieved": round(k1_tflops, 3),
                          "peak": F32_PEAK_TFLOPS, "unit": "TFLOP/s",
                          "frac": round(k1_tflops / F32_PEAK_TFLOPS, 4),
@@ -539,9 +607,8 @@ def main():
             "other_sample_rates": other_rates,
             "host_boundary": host_boundary,
             "decode": decode,
-            "gather": gather,
             "encoded": encoded,
-        }
+        })
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
     if dist_on:

@@ -161,6 +161,45 @@ def test_record_assembly_reproduces_oracle_bytes(name, make, sr, ch):
         glc_amd.EncodedAudio.from_records(sr, x.size, ch, recs[:-glc_amd.lib.glc_record_bytes(ch)])
 
 
+@pytest.mark.parametrize("ch", [1, 2, 3])
+def test_bench_dump_reads_records_field_by_field(ch):
+    """bench.py --dump-outputs: record_arrays gives the oracle's taps for compressed and raw frames,
+    with shapes fixed by the frame count alone (never empty, whatever the raw/compressed mix), and
+    never reads the bytes the encoder leaves undefined (header padding, payload[c][1024:] of a
+    compressed frame), so two equal encodes dump equal arrays."""
+    import bench
+    x = np.concatenate([gen_tone("sine", 440.0, 48000, ch, 0.5), gen_noise(48000, ch, 0.25, 7)])
+    nf = O.num_frames(x.size, ch)
+    recs, taps = O.encode_range_records(x, 0, x.size // ch, x.size, 48000, ch, 0, nf, taps=True)
+    rb = glc_amd.lib.glc_record_bytes(ch)
+    raw = taps.is_raw.astype(bool)
+    assert raw.any() and not raw.all()
+    poisoned = recs.reshape(nf, rb).copy()
+    hdr = rb - 4096 * ch
+    poisoned[:, 8 + 8 * ch:hdr] = 0xAB
+    for c in range(ch):
+        poisoned[~raw, hdr + 4096 * c + 2048:hdr + 4096 * (c + 1)] = 0xAB
+    want = np.zeros((nf, ch, 2048), np.float32)
+    want[:, :, :1024] = taps.dense_q.reshape(nf, ch, 1024)
+    want[raw] = recs.reshape(nf, rb)[raw, hdr:].copy().view(np.int16).reshape(-1, ch, 2048)
+    for n_payload in (None, nf // 2):
+        n = nf if n_payload is None else n_payload
+        for r in (recs, poisoned):
+            a = bench.record_arrays(np, r, rb, ch, n_payload)
+            assert all(v.dtype == np.float32 and v.size > 0 for v in a.values())
+            assert np.array_equal(a["is_raw"], raw.astype(np.float32))
+            assert np.array_equal(a["scale"].view(np.uint32), taps.scales.reshape(nf, ch).view(np.uint32))
+            assert np.array_equal(a["nnz"], taps.nnz.reshape(nf, ch).astype(np.float32))
+            frames = a["payload_frames"].astype(np.int64)
+            assert frames.shape == (n,) and np.all(np.diff(frames) > 0) and frames[-1] < nf
+            assert np.array_equal(a["payload"], want[frames])
+    # an all-compressed stream dumps the same shapes (no array depends on the raw/compressed mix)
+    tonal, _ = O.encode_range_records(x[:nf // 2 * 1024 * ch], 0, nf // 2 * 1024, nf // 2 * 1024 * ch, 48000, ch,
+                                      0, O.num_frames(nf // 2 * 1024 * ch, ch))
+    a = bench.record_arrays(np, tonal, rb, ch, 4)
+    assert a["is_raw"].sum() == 0 and a["payload"].shape == (4, ch, 2048)
+
+
 def test_decoded_len():
     for data in _golden_bytes():
         enc = glc_amd.EncodedAudio.from_bytes(data)

@@ -1,7 +1,7 @@
 """Issue-side counters of the shipped forward transform (K1) at BASELINE config 2 -> profiles/<tag>_k1_pmc.txt.
 
 Separate `rocprofv3 --pmc` passes (a pass holds a handful of SQ counters; no tracing options beside
---pmc: the pool refuses that combination) over `python3 bench.py --steps 5 --warmup 1 --lean`, the
+--pmc: counters are collected in runs of their own) over `python3 bench.py --steps 5 --warmup 1 --full --lean`, the
 program itself right behind `--`.  Per pass the means over the second half of K1's dispatches, then the
 derived figures the roofline discussion needs:
     clock held            GRBM_GUI_ACTIVE / 8 XCDs / kernel duration
@@ -32,9 +32,9 @@ def main():
     ap.add_argument("--kernel-ms", type=float, default=None, help="K1 launch time of an un-profiled run (bench line), for the clock")
     args = ap.parse_args()
     scratch = os.path.join(ROOT, "gpurun_out", f"{args.tag}_k1_pmc")
-    bench = ["python3", os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "1", "--lean"]
+    bench = ["python3", os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "1", "--full", "--lean"]
     got = {}
-    lines = [f"# rocprofv3 --pmc ({len(PASSES)} separate passes) -- python3 bench.py --steps 5 --warmup 1 --lean",
+    lines = [f"# rocprofv3 --pmc ({len(PASSES)} separate passes) -- python3 bench.py --steps 5 --warmup 1 --full --lean",
              f"# kernel {K1} (the shipped instance for stereo), 8192 rows x 1024 coefficients (BASELINE config 2, chord input); second half of the dispatches",
              "# SQ_*_CYCLES / SQ_WAIT_* / SQ_ACTIVE_* in quad-cycles summed over all SIMDs; GRBM_GUI_ACTIVE, SQ_BUSY_CYCLES in cycles summed over 8 XCDs / 32 SEs",
              "# pass counter n mean"]

@@ -5,7 +5,7 @@ pass on gfx950 (MI355X_MICROARCH.md, PMC slots) - over
   1. build/fetch_calib: kernels that move exactly 512 MiB each with the access patterns K1 uses
      (128-byte PCM segments by buffer_load_dwordx4, table rows by global_load_lds_dwordx4) and two
      plain ones -> counter bytes per true byte for every pattern;
-  2. `python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline`: per-launch counter means of K1 / K2 / D1.
+  2. `python3 bench.py --steps 10 --warmup 2 --full --lean`: per-launch counter means of the encode kernels.
 and writes profiles/k1_traffic.json (what bench.py reports as roofline.traffic, with the commit it was
 taken at) plus the per-kernel CSV means under profiles/<tag>_pmc/.
 
@@ -62,7 +62,7 @@ def main():
     args = ap.parse_args()
     scratch = os.path.join(ROOT, "gpurun_out", f"{args.tag}_pmc")
     calib = [os.path.join(ROOT, "build", "fetch_calib")]
-    bench = ["python3", os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--lean"]
+    bench = ["python3", os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--full", "--lean"]
     true_kb = 512 * 1024.0
 
     cf = run_pass(["FETCH_SIZE"], calib, os.path.join(scratch, "calib_fetch"))

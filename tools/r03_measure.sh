@@ -7,9 +7,9 @@ O=${GLC_MEASURE_OUT:-gpurun_out/r3z}
 R=$(pwd)
 mkdir -p $O
 python tools/dump_d1_rows.py > $O/dump.txt 2>&1
-python bench.py --steps 20 --warmup 5 > $O/bench_a.json 2> $O/bench_a.err
-python bench.py --steps 20 --warmup 5 > $O/bench_b.json 2> $O/bench_b.err
-timeout -k 10 400 python bench.py --gpus 2 --steps 20 --warmup 5 > $O/bench_n2.json 2> $O/bench_n2.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_a.json 2> $O/bench_a.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_b.json 2> $O/bench_b.err
+timeout -k 10 400 python bench.py --full --gpus 2 --steps 20 --warmup 5 > $O/bench_n2.json 2> $O/bench_n2.err
 echo "bench done: $(date)"
 for f in chord random zero; do timeout -k 10 200 build/k1_tune 4096 2 40 $f > $O/k1_tune_$f.txt 2>&1; done
 timeout -k 10 120 build/k1_tune 4096 2 30 chord timeline > $O/k1_timeline.txt 2>&1
@@ -24,7 +24,7 @@ build/decode_breakdown > $O/decode_breakdown.txt 2>&1
 echo "tools done: $(date)"
 KMS=$(python3 -c "import json;print(json.loads(open('$O/bench_a.json').read().strip().splitlines()[-1])['roofline']['ms_per_launch'])")
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -- python3 $R/bench.py --steps 100 --warmup 5 --lean > $R/$O/prof_stdout.txt 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -- python3 $R/bench.py --steps 100 --warmup 5 --full --lean > $R/$O/prof_stdout.txt 2>&1
 echo "kernel trace done: $(date)"
 python3 $R/tools/pmc_k1.py --tag r03 --kernel-ms $KMS > $R/$O/pmc_k1_stdout.txt 2>&1
 echo "pmc k1 done: $(date)"
