@@ -418,20 +418,21 @@ int glc_ctx_tables(const glc_ctx *ctx, float *cos_table, float *window, float *n
 
 // ------------------------------------------------------------------------------ encode
 
-// glc_encode_range_device on a given stream with a given coefficient workspace (glc_encode runs
-// alternate rounds on two streams)
-static int encode_range_on(glc_ctx *ctx, hipStream_t stream, DevBuf &coef_ws, const float *d_pcm, uint64_t t0, uint64_t t_count,
-                           uint64_t n_samples, uint16_t channels, uint64_t frame_begin, uint64_t frame_end,
-                           void *d_records, float *d_coeffs, bool alternate_ok = false, bool beside = false) {
-  if (!ctx || !d_pcm || !d_records) return fail(ctx, GLC_EINVAL, "glc_encode_range_device: null argument");
+// Arguments of a frame-range encode (glc_encode_range_device, glc_debug_quantize_device): `fn` names the
+// entry point in the error message.  `whole_tap`: the range's rows go into one caller-supplied coefficient
+// buffer, so their count must fit one launch.
+static int check_encode_range(glc_ctx *ctx, const char *fn, const float *d_pcm, uint64_t t0, uint64_t t_count,
+                              uint64_t n_samples, uint16_t channels, uint64_t frame_begin, uint64_t frame_end,
+                              const void *d_records, bool whole_tap) {
+  const std::string f(fn);
+  if (!ctx || !d_pcm || !d_records) return fail(ctx, GLC_EINVAL, f + ": null argument");
   const glc_plan plan = glc::plan_encode(n_samples, channels);
   if (plan.n_frames == 0)
-    return fail(ctx, GLC_EINVAL, "glc_encode_range_device: the reference encoder panics on this input");
+    return fail(ctx, GLC_EINVAL, f + ": the reference encoder panics on this input");
   if (frame_begin > frame_end || frame_end > plan.n_frames)
-    return fail(ctx, GLC_EINVAL, "glc_encode_range_device: frame range out of bounds");
-  const uint32_t ch = channels;
-  if (d_coeffs && (frame_end - frame_begin) * ch > 0xFFFFFFFFull)
-    return fail(ctx, GLC_EINVAL, "glc_encode_range_device: range too large for one coefficient tap");
+    return fail(ctx, GLC_EINVAL, f + ": frame range out of bounds");
+  if (whole_tap && (frame_end - frame_begin) * channels > 0xFFFFFFFFull)
+    return fail(ctx, GLC_EINVAL, f + ": range too large for one coefficient tap");
   // The shard must hold every real sample the frame range reads:
   // per-channel t in [1024*f0 - 512, 1024*(f1-1) - 512 + 2048) clipped to the stream.
   if (frame_end > frame_begin) {
@@ -440,8 +441,32 @@ static int encode_range_on(glc_ctx *ctx, hipStream_t stream, DevBuf &coef_ws, co
     const int64_t need_hi = std::min<int64_t>(stream_len, static_cast<int64_t>(frame_end - 1) * glc::kHop - glc::kHop / 2 + glc::kFrame);
     if (need_hi > need_lo &&
         (static_cast<int64_t>(t0) > need_lo || static_cast<int64_t>(t0 + t_count) < need_hi))
-      return fail(ctx, GLC_EINVAL, "glc_encode_range_device: PCM shard does not cover the frame range (halo missing)");
+      return fail(ctx, GLC_EINVAL, f + ": PCM shard does not cover the frame range (halo missing)");
   }
+  return GLC_OK;
+}
+
+// K2, then K3 for the channel counts whose raw-vs-compressed decision K2 does not take itself, on the
+// coefficient rows of frames [frame_begin, frame_begin + n_frames) -> their records.
+static hipError_t launch_quantize_decide(glc_ctx *ctx, const float *coef, const glc::PcmView &view,
+                                         uint64_t frame_begin, uint64_t n_frames, uint8_t *records, hipStream_t st) {
+  bool decided = false;
+  hipError_t e = glc::launch_quantize(ctx->dev, coef, static_cast<uint32_t>(n_frames * view.ch), view.ch, view,
+                                      frame_begin, records, st, &decided);
+  if (e == hipSuccess && !decided)
+    e = glc::launch_decide_raw(ctx->dev, view, frame_begin, static_cast<uint32_t>(n_frames), records, st);
+  return e;
+}
+
+// glc_encode_range_device on a given stream with a given coefficient workspace (glc_encode runs
+// alternate rounds on two streams)
+static int encode_range_on(glc_ctx *ctx, hipStream_t stream, DevBuf &coef_ws, const float *d_pcm, uint64_t t0, uint64_t t_count,
+                           uint64_t n_samples, uint16_t channels, uint64_t frame_begin, uint64_t frame_end,
+                           void *d_records, float *d_coeffs, bool alternate_ok = false, bool beside = false) {
+  const int rc = check_encode_range(ctx, "glc_encode_range_device", d_pcm, t0, t_count, n_samples, channels,
+                                    frame_begin, frame_end, d_records, d_coeffs != nullptr);
+  if (rc != GLC_OK) return rc;
+  const uint32_t ch = channels;
   DeviceGuard guard(ctx->device);
   const uint64_t rec = glc::record_bytes(ch);
   glc::PcmView view{d_pcm, t0, t_count, n_samples, ch};
@@ -474,9 +499,7 @@ static int encode_range_on(glc_ctx *ctx, hipStream_t stream, DevBuf &coef_ws, co
     float *coef = d_coeffs ? d_coeffs + (f - frame_begin) * ch * glc::kHop : static_cast<float *>(odd ? ctx->coef_b.p : coef_ws.p);
     uint8_t *r = recs + (f - frame_begin) * rec;
     GLC_HIP(ctx, glc::launch_mdct_forward(ctx->dev, view, f, M, coef, st, ctx->k1_variant, beside));
-    bool decided = false;
-    GLC_HIP(ctx, glc::launch_quantize(ctx->dev, coef, M, ch, view, f, r, st, &decided));
-    if (!decided) GLC_HIP(ctx, glc::launch_decide_raw(ctx->dev, view, f, static_cast<uint32_t>(nf), r, st));
+    GLC_HIP(ctx, launch_quantize_decide(ctx, coef, view, f, nf, r, st));
   }
   if (alternate) {
     GLC_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->stream_b));
@@ -491,6 +514,21 @@ int glc_encode_range_device(glc_ctx *ctx, const float *d_pcm, uint64_t t0, uint6
   if (!ctx) return GLC_EINVAL;
   return encode_range_on(ctx, ctx->stream, ctx->coef, d_pcm, t0, t_count, n_samples, channels, frame_begin, frame_end,
                          d_records, d_coeffs, /*alternate_ok=*/true);
+}
+
+int glc_debug_quantize_device(glc_ctx *ctx, const float *d_coeffs, const float *d_pcm, uint64_t t0, uint64_t t_count,
+                              uint64_t n_samples, uint16_t channels, uint64_t frame_begin, uint64_t frame_end,
+                              void *d_records) {
+  if (!ctx) return GLC_EINVAL;
+  if (!d_coeffs) return fail(ctx, GLC_EINVAL, "glc_debug_quantize_device: null argument");
+  const int rc = check_encode_range(ctx, "glc_debug_quantize_device", d_pcm, t0, t_count, n_samples, channels,
+                                    frame_begin, frame_end, d_records, /*whole_tap=*/true);
+  if (rc != GLC_OK) return rc;
+  DeviceGuard guard(ctx->device);
+  const glc::PcmView view{d_pcm, t0, t_count, n_samples, channels};
+  GLC_HIP(ctx, launch_quantize_decide(ctx, d_coeffs, view, frame_begin, frame_end - frame_begin,
+                                      static_cast<uint8_t *>(d_records), ctx->stream));
+  return GLC_OK;
 }
 
 int glc_mdct_forward_device(glc_ctx *ctx, const float *d_pcm, uint64_t t0, uint64_t t_count,

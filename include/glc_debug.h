@@ -39,6 +39,16 @@ int glc_debug_set_imdct_variant(glc_ctx *ctx, int variant);
  * All of them produce the same bits (tests/test_gpu_parity.py). */
 int glc_debug_set_mdct_variant(glc_ctx *ctx, int variant);
 
+/* K2 (+ K3 where the channel count needs it) exactly as glc_encode_range_device runs them, on caller-supplied
+ * coefficients: d_coeffs holds (frame_end - frame_begin) * channels rows of 1024 floats, laid out as
+ * glc_mdct_forward_device writes them; d_pcm / t0 / t_count / n_samples are read only for raw planes.
+ * Arguments are checked as glc_encode_range_device checks them (halo included); the work is queued on
+ * the context's stream and nothing is synchronised.  tests/test_quantizer_edges.py drives the quantiser
+ * through this at its decision boundaries. */
+int glc_debug_quantize_device(glc_ctx *ctx, const float *d_coeffs, const float *d_pcm, uint64_t t0, uint64_t t_count,
+                              uint64_t n_samples, uint16_t channels, uint64_t frame_begin, uint64_t frame_end,
+                              void *d_records);
+
 /* The shader clock the device HOLDS under load (measurement only; bench.py's roofline.clock_ghz_held).
  * `begin` starts one sleeping wave on a stream of its own that runs for `window_us` microseconds beside
  * whatever the caller queues meanwhile and reads the shader-cycle counter against the constant 100 MHz

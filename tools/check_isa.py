@@ -6,8 +6,10 @@ reference accumulates with a separately rounded multiply and add.
   k_imdct_rows / k_imdct_plan   fused ops allowed only inside hipcc's correctly-rounded f32 division expansion
                 (v_div_scale ... v_div_fixup), which the raw-frame path `i16 / 32767.0` needs
 The quantiser / decision / overlap-add kernels are not scanned: their IEEE divide, sqrt and
-64-bit index division expand to FMA-based sequences by design; their arithmetic is pinned by the
-bit-exact parity tests instead."""
+64-bit index division expand to FMA-based sequences by design.  The arithmetic of the quantiser and the
+raw-or-compressed decision is pinned instead by tests/test_quantizer_edges.py, which drives them with
+coefficient rows sitting on every decision edge (thresholds, noise floor, peak gate, rounding, the raw
+flip point); the overlap-add by the bit-exact parity tests."""
 import os
 import re
 import subprocess
