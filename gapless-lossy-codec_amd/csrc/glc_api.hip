@@ -191,6 +191,11 @@ constexpr uint32_t kPlanGroups = 2048;  // (group, channel) units per D1 batch: 
 // (one std::string, two writers) - each helper points this at a string of its own for the duration of
 // its job, and the calling thread stores the winning message into ctx->err once, at the end.
 thread_local std::string *t_err_sink = nullptr;
+struct SinkGuard {
+  std::string *prev;
+  explicit SinkGuard(std::string *s) : prev(t_err_sink) { t_err_sink = s; }
+  ~SinkGuard() { t_err_sink = prev; }
+};
 
 int fail(glc_ctx *ctx, int code, const std::string &msg) {
   if (t_err_sink) {
@@ -433,14 +438,10 @@ static int check_encode_range(glc_ctx *ctx, const char *fn, const float *d_pcm, 
     return fail(ctx, GLC_EINVAL, f + ": frame range out of bounds");
   if (whole_tap && (frame_end - frame_begin) * channels > 0xFFFFFFFFull)
     return fail(ctx, GLC_EINVAL, f + ": range too large for one coefficient tap");
-  // The shard must hold every real sample the frame range reads:
-  // per-channel t in [1024*f0 - 512, 1024*(f1-1) - 512 + 2048) clipped to the stream.
+  // The shard must hold every real sample the frame range reads.
   if (frame_end > frame_begin) {
-    const int64_t need_lo = std::max<int64_t>(0, static_cast<int64_t>(frame_begin) * glc::kHop - glc::kHop / 2);
-    const int64_t stream_len = static_cast<int64_t>(plan.per_channel);
-    const int64_t need_hi = std::min<int64_t>(stream_len, static_cast<int64_t>(frame_end - 1) * glc::kHop - glc::kHop / 2 + glc::kFrame);
-    if (need_hi > need_lo &&
-        (static_cast<int64_t>(t0) > need_lo || static_cast<int64_t>(t0 + t_count) < need_hi))
+    const glc::SampleWindow need = glc::frame_sample_window(frame_begin, frame_end, plan.per_channel);
+    if (need.hi > need.lo && (t0 > need.lo || t0 + t_count < need.hi))
       return fail(ctx, GLC_EINVAL, f + ": PCM shard does not cover the frame range (halo missing)");
   }
   return GLC_OK;
@@ -594,12 +595,75 @@ int glc_compact_device_records(glc_ctx *ctx, const void *d_records, uint64_t n_f
   glc::CompactHeader h;
   GLC_HIP(ctx, hipMemcpyAsync(&h, d_blob, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
   GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (h.magic != glc::kCompactMagic || h.bytes > l.bound)
-    return fail(ctx, GLC_EHIP, "glc_compact_device_records: the device wrote an inconsistent header");
+  if (const char *bad = glc::compact_header_error(h, channels, n_frames, /*exact=*/true, l.bound))
+    return fail(ctx, GLC_EHIP, std::string("glc_compact_device_records: the device wrote an inconsistent header (") + bad + ")");
   info->n_frames = h.n_frames;
   info->n_pairs = h.n_pairs;
   info->n_raw_rows = h.n_raw_rows;
   info->bytes = h.bytes;
+  return GLC_OK;
+}
+
+// Compacts the records of frames [f_at, f_at + nf) into `d_blob` on `st` and lands the blob in F: its
+// pairs at p_at and raw planes at r_at of the pools (grown to fit), its index vectors from frame f_at on.
+// Only the bitstream's payload crosses PCIe, and it lands where it stays: the (u16, i16) pairs and the
+// raw planes are copied straight into the pools, the small per-frame / per-row metadata through the
+// pinned host_stage (which holds at least the metadata).  `drain(st)` blocks until `st` has drained (a
+// hooked encode hands out finished frames meanwhile).  `expect_pairs`: pairs the blob is expected to
+// hold; `reserve_scale` > 0: the pools are reserved for that many times this blob's payload first.
+// *n_pairs / *n_raw: what the blob added to the pools.  May throw std::bad_alloc.
+static int land_blob(glc_ctx *ctx, const char *who, glc_frames *F, const void *d_records, uint64_t nf, uint8_t *d_blob,
+                     uint64_t f_at, uint64_t p_at, uint64_t r_at, uint64_t expect_pairs, double reserve_scale, hipStream_t st,
+                     const std::function<hipError_t(hipStream_t)> &drain, uint64_t *n_pairs, uint64_t *n_raw) {
+  const uint32_t ch = F->channels;
+  const glc::CompactLayout l = glc::compact_layout(ch, nf);
+  uint8_t *hm = static_cast<uint8_t *>(ctx->host_stage.p);
+  const int crc = compact_launch(ctx, d_records, nf, ch, d_blob, st);
+  if (crc != GLC_OK) return crc;
+  // One copy fetches the metadata (header, raw flags, scale factors, list lengths: they say how
+  // long the payload is) AND as much of the pair section behind it as this round is expected to
+  // fill, into pinned memory; a round that holds more, or raw planes, fetches the rest straight into
+  // the pools once the header is known.  That is for short rounds, where the second round trip is
+  // what costs; a long round's payload (3.7 MB for 4096 stereo frames) goes straight into the pools -
+  // the host copy out of the pinned buffer would cost more than the round trip (one hour of stereo:
+  // 61 ms with it, 54 without).
+  // (Queueing the last round's compaction and download behind its quantiser on the round's own
+  // stream, to save the launch latency, measured 70 us SLOWER at config 2.)
+  if (expect_pairs * 4 > (size_t(3) << 19)) expect_pairs = 0;
+  const uint64_t first_bytes = std::min<uint64_t>({l.o_pairs + expect_pairs * 4, l.bound, ctx->host_stage.cap});
+  hipError_t e = hipMemcpyAsync(hm, d_blob, first_bytes, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = drain(st);
+  if (e != hipSuccess) return hip_fail(ctx, e, (std::string(who) + ": download").c_str());
+  glc::CompactHeader h;
+  std::memcpy(&h, hm, sizeof h);
+  if (const char *bad = glc::compact_header_error(h, ch, nf, /*exact=*/true, l.bound))
+    return fail(ctx, GLC_EHIP, std::string(who) + ": the device wrote an inconsistent compact header (" + bad + ")");
+  if (reserve_scale > 0) {
+    F->pairs.reserve(static_cast<size_t>(static_cast<double>(h.n_pairs) * reserve_scale) + 4096);
+    if (h.n_raw_rows) F->raw.reserve(static_cast<size_t>(static_cast<double>(h.n_raw_rows * glc::kFrame) * reserve_scale));
+  }
+  *n_pairs = h.n_pairs;
+  *n_raw = h.n_raw_rows * glc::kFrame;
+  if (F->pairs.size() < p_at + *n_pairs) F->pairs.resize(p_at + *n_pairs);
+  if (F->raw.size() < r_at + *n_raw) F->raw.resize(r_at + *n_raw);
+  const uint64_t have = std::min<uint64_t>(h.n_pairs, (first_bytes - l.o_pairs) / 4);  // pairs already on the host
+  if (h.n_pairs > have)
+    e = hipMemcpyAsync(F->pairs.data() + p_at + have, d_blob + l.o_pairs + have * 4, (h.n_pairs - have) * 4,
+                       hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && h.n_raw_rows)
+    e = hipMemcpyAsync(F->raw.data() + r_at, d_blob + glc::compact_raw_offset(l, h.n_pairs), *n_raw * 2,
+                       hipMemcpyDeviceToHost, st);
+  if (have) std::memcpy(F->pairs.data() + p_at, hm + l.o_pairs, have * 4);
+  bool canonical = true;
+  int rc = GLC_OK;
+  if (e == hipSuccess) rc = glc::index_compact_meta(F, ch, h, hm, f_at, p_at, r_at, /*trusted=*/true, &canonical);
+  // the pools may move when they grow next, and host_stage is reused: all of it has to have landed
+  if (h.n_pairs > have || h.n_raw_rows) {
+    const hipError_t e2 = drain(st);
+    if (e == hipSuccess) e = e2;
+  }
+  if (e != hipSuccess) return hip_fail(ctx, e, (std::string(who) + ": download").c_str());
+  if (rc != GLC_OK) return fail(ctx, rc, std::string(who) + ": " + glc_last_error(nullptr));
   return GLC_OK;
 }
 
@@ -613,56 +677,22 @@ int glc_frames_from_device_records(glc_ctx *ctx, const void *d_records, uint64_t
   DeviceGuard guard(ctx->device);
   const glc::CompactLayout l = glc::compact_layout(channels, n_frames);
   GLC_HIP(ctx, ctx->pack_blob.reserve(l.bound));
-  glc_compact_info info;
-  int rc = glc_compact_device_records(ctx, d_records, n_frames, channels, ctx->pack_blob.p, ctx->pack_blob.cap, &info);
-  if (rc != GLC_OK) return rc;
-  // Only the bitstream's payload crosses PCIe, and it lands where it stays: the (u16, i16) pairs
-  // and the raw planes are copied straight into the EncodedAudio's own pools, the small per-frame /
-  // per-row metadata through pinned staging.
-  const uint32_t ch = channels;
-  const uint64_t raw_off = glc::compact_raw_offset(l, info.n_pairs);
+  GLC_HIP(ctx, ctx->host_stage.reserve(l.o_pairs));
   std::unique_ptr<glc_frames> F(new (std::nothrow) glc_frames);
   if (!F) return fail(ctx, GLC_ENOMEM, "glc_frames_from_device_records: host allocation failed");
+  int rc;
   try {
-    F->sample_rate = ctx->sample_rate;
-    F->channels = channels;
-    F->total_samples = n_samples;           // src/codec.rs:423,555
-    F->encoder_delay = plan.encoder_delay;  // :547
-    F->padding = plan.padding;              // :546
-    F->original_length = n_samples;         // :562
-    F->n_frames = n_frames;
-    F->list_begin.assign(n_frames + 1, 0);
-    F->scale_begin.assign(n_frames + 1, 0);
-    F->raw_begin.assign(n_frames + 1, 0);
-    F->raw_tag.resize(n_frames);
-    F->pairs.resize(info.n_pairs);
-    F->raw.resize(info.n_raw_rows * glc::kFrame);
-    const uint64_t n_comp_rows = n_frames * ch - info.n_raw_rows;
-    F->list_off.reserve(n_comp_rows + 1);
-    F->list_off.push_back(0);
-    F->scales.reserve(n_comp_rows);
+    glc::init_frames(F.get(), ctx->sample_rate, n_samples, channels, plan);
+    uint64_t n_pairs, n_raw;
+    rc = land_blob(ctx, "glc_frames_from_device_records", F.get(), d_records, n_frames, static_cast<uint8_t *>(ctx->pack_blob.p),
+                   0, 0, 0, /*expect_pairs=*/0, /*reserve_scale=*/0, ctx->stream, hipStreamSynchronize, &n_pairs, &n_raw);
   } catch (const std::bad_alloc &) {
-    return fail(ctx, GLC_ENOMEM, "glc_frames_from_device_records: host allocation failed");
+    rc = fail(ctx, GLC_ENOMEM, "glc_frames_from_device_records: host allocation failed");
   }
-  GLC_HIP(ctx, ctx->host_stage.reserve(l.o_pairs));
-  const uint8_t *blob = static_cast<const uint8_t *>(ctx->pack_blob.p);
-  GLC_HIP(ctx, hipMemcpyAsync(ctx->host_stage.p, blob, l.o_pairs, hipMemcpyDeviceToHost, ctx->stream));
-  if (info.n_pairs)
-    GLC_HIP(ctx, hipMemcpyAsync(F->pairs.data(), blob + l.o_pairs, info.n_pairs * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (info.n_raw_rows)
-    GLC_HIP(ctx, hipMemcpyAsync(F->raw.data(), blob + raw_off, info.n_raw_rows * glc::kFrame * 2, hipMemcpyDeviceToHost,
-                                ctx->stream));
-  GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  glc::CompactHeader h;
-  std::memcpy(&h, ctx->host_stage.p, sizeof h);
-  bool canonical = true;
-  try {
-    rc = glc::index_compact_meta(F.get(), ch, h, static_cast<const uint8_t *>(ctx->host_stage.p), 0, 0, 0, /*trusted=*/true,
-                                 &canonical);
-  } catch (const std::bad_alloc &) {
-    return fail(ctx, GLC_ENOMEM, "glc_frames_from_device_records: host allocation failed");
+  if (rc != GLC_OK) {
+    (void)hipStreamSynchronize(ctx->stream);  // nothing may still be in flight into F's pools
+    return rc;
   }
-  if (rc != GLC_OK) return fail(ctx, rc, std::string("glc_frames_from_device_records: ") + glc_last_error(nullptr));
   F->lists_canonical = true;  // ballot-packed in ascending k
   *out = F.release();
   return GLC_OK;
@@ -730,28 +760,14 @@ int glc_encode_hooked(glc_ctx *ctx, const float *pcm, uint64_t n_samples, uint16
       // (Measured and dropped, round 3: cutting the END of a stream in halves - .. 2048, 1024, 512, 512 frames -
       // so that the last, unhidden transform is a short one: 1.045 ms against 1.02 at config 2; a round
       // costs the launcher and the collector more than the shorter tail returns.)
-      // frames [f, f+nf) read per-channel samples below 1024*(f+nf-1) - 512 + 2048
-      const uint64_t hi_t = std::min<uint64_t>(t_count, (f + nf - 1) * glc::kHop + glc::kFrame - glc::kHop / 2);
+      const uint64_t hi_t = glc::frame_sample_window(f, f + nf, plan.per_channel).hi;
       Round r{f, nf, blob_off, std::min<uint64_t>(n_samples, hi_t * ch), glc::compact_layout(ch, nf)};
       blob_off += align_up(r.l.bound, 256);
       max_nf = std::max(max_nf, nf);
       rounds.push_back(r);
     }
     F.reset(new glc_frames);
-    F->sample_rate = ctx->sample_rate;
-    F->channels = channels;
-    F->total_samples = n_samples;           // src/codec.rs:423,555
-    F->encoder_delay = plan.encoder_delay;  // :547
-    F->padding = plan.padding;              // :546
-    F->original_length = n_samples;         // :562
-    F->n_frames = plan.n_frames;
-    F->list_begin.assign(plan.n_frames + 1, 0);
-    F->scale_begin.assign(plan.n_frames + 1, 0);
-    F->raw_begin.assign(plan.n_frames + 1, 0);
-    F->raw_tag.resize(plan.n_frames);
-    F->list_off.reserve(plan.n_frames * ch + 1);  // never reallocated: a hook may be reading it while later rounds append
-    F->list_off.push_back(0);
-    F->scales.reserve(plan.n_frames * ch);
+    glc::init_frames(F.get(), ctx->sample_rate, n_samples, channels, plan);
   } catch (const std::bad_alloc &) {
     return fail(ctx, GLC_ENOMEM, "glc_encode: host allocation failed");
   }
@@ -783,7 +799,6 @@ int glc_encode_hooked(glc_ctx *ctx, const float *pcm, uint64_t n_samples, uint16
   GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // earlier work may still read the staging buffers
   float *d_pcm = static_cast<float *>(ctx->pcm.p);
   uint8_t *d_blob = static_cast<uint8_t *>(ctx->pack_blob.p);
-  uint8_t *h_meta = static_cast<uint8_t *>(ctx->host_stage.p);
   hipEvent_t *ev_rec = ctx->ev_round.data();
 
   // progress shared by the three threads; an error anywhere stops all of them
@@ -811,7 +826,7 @@ int glc_encode_hooked(glc_ctx *ctx, const float *pcm, uint64_t n_samples, uint16
     }
   } prog;
   auto hip_msg = [](const char *what, hipError_t e) { return std::string(what) + ": " + hipGetErrorString(e); };
-  std::atomic<double> pairs_per_frame{0.0};  // stored pairs per frame so far, + 25 % (sizes the next round's first copy)
+  double pairs_per_frame = 0.0;  // stored pairs per frame so far, + 25 % (sizes the next round's first copy)
 
   auto upload = [&] {  // stage 1
     DeviceGuard g(ctx->device);
@@ -832,11 +847,7 @@ int glc_encode_hooked(glc_ctx *ctx, const float *pcm, uint64_t n_samples, uint16
   };
   auto launch = [&] {  // stage 2
     std::string my_err;  // failures of this stage land here, not in ctx->err (another thread's to write)
-    struct SinkGuard {
-      std::string *prev;
-      explicit SinkGuard(std::string *s) : prev(t_err_sink) { t_err_sink = s; }
-      ~SinkGuard() { t_err_sink = prev; }
-    } sink(&my_err);
+    SinkGuard sink(&my_err);
     DeviceGuard g(ctx->device);
     for (size_t i = 0; i < n_rounds; ++i) {
       const Round &r = rounds[i];
@@ -876,27 +887,23 @@ int glc_encode_hooked(glc_ctx *ctx, const float *pcm, uint64_t n_samples, uint16
     return hrc == 0;
   };
   // block until `st` has drained - handing out finished frames meanwhile (hooked encodes)
-  auto drain = [&](hipStream_t st) -> hipError_t {
+  const std::function<hipError_t(hipStream_t)> drain = [&](hipStream_t st) {
     if (hook)
       while (delivered < complete && hipStreamQuery(st) == hipErrorNotReady)
         if (!deliver(std::min(complete, delivered + kHookSlice))) break;
     return hipStreamSynchronize(st);
   };
-  auto grow_pairs = [&](size_t want) {
-    if (F->pairs.size() < want) F->pairs.resize(want);
-  };
-  auto grow_raw = [&](size_t want) {
-    if (F->raw.size() < want) F->raw.resize(want);
-  };
   auto collect = [&] {  // stage 3
+    std::string my_err;  // land_blob reports here; the calling thread stores the winning message at the end
+    SinkGuard sink(&my_err);
     for (size_t i = 0; i < n_rounds; ++i) {
       const Round &r = rounds[i];
       if (i > 0) {
         // Growing a pool zero-fills it: do that for this round while its kernels still run, from the
-        // density of the stream so far (+ 25 %); a round that turns out denser grows again below.
+        // density of the stream so far (+ 25 %); a round that turns out denser grows again as it lands.
         const double per_frame = static_cast<double>(p_used) / static_cast<double>(r.f0) * 1.25;
         const uint64_t want = p_used + static_cast<uint64_t>(per_frame * static_cast<double>(r.nf)) + 1024;
-        grow_pairs(want);
+        if (F->pairs.size() < want) F->pairs.resize(want);
       }
       if (hook) {  // hand out finished frames while this round's records are not ready
         while (delivered < complete) {
@@ -913,63 +920,19 @@ int glc_encode_hooked(glc_ctx *ctx, const float *pcm, uint64_t n_samples, uint16
       if (!prog.wait_for(prog.queued, i)) return;
       hipError_t e = hipEventSynchronize(ev_rec[i]);  // the round's records are written: compact them now
       if (e != hipSuccess) return prog.set_error(GLC_EHIP, hip_msg("glc_encode: waiting for a round", e));
-      const uint8_t *blob = d_blob + r.blob_off;
-      uint8_t *hm = h_meta;
-      {
-        uint8_t *recs = static_cast<uint8_t *>(ctx->records.p) + r.f0 * rec;
-        const int crc = compact_launch(ctx, recs, r.nf, ch, d_blob + r.blob_off, ctx->down_stream);
-        if (crc != GLC_OK) return prog.set_error(crc, "glc_encode: compaction launch failed");
-      }
-      // One copy fetches the metadata (header, raw flags, scale factors, list lengths: they say how
-      // long the payload is) AND as much of the pair section behind it as this round is expected to
-      // fill, from the density of the stream so far (+ 25 %), into pinned memory; a round that holds
-      // more, or raw planes, fetches the rest straight into the pools once the header is known.
-      // (Queueing the last round's compaction and download behind its quantiser on the round's own
-      // stream, to save the launch latency, measured 70 us SLOWER at config 2.)
+      // pairs the round is expected to hold, from the density of the stream so far (+ 25 %)
       uint64_t guess_pairs = 0;
-      if (i > 0) guess_pairs = static_cast<uint64_t>(pairs_per_frame.load(std::memory_order_relaxed) * static_cast<double>(r.nf)) + 1024;
-      // ... for short rounds, where the second round trip is what costs; a long round's payload (3.7 MB
-      // for 4096 stereo frames) goes straight into the pools - the host copy out of the pinned buffer
-      // would cost more than the round trip (one hour of stereo: 61 ms with it, 54 without)
-      if (guess_pairs * 4 > (size_t(3) << 19)) guess_pairs = 0;
-      const uint64_t first_bytes = std::min<uint64_t>(r.l.o_pairs + guess_pairs * 4, std::min<uint64_t>(r.l.bound, stage_cap));
-      e = hipMemcpyAsync(hm, blob, first_bytes, hipMemcpyDeviceToHost, ctx->down_stream);
-      if (e == hipSuccess) e = drain(ctx->down_stream);
-      if (e != hipSuccess) return prog.set_error(GLC_EHIP, hip_msg("glc_encode: download", e));
-      glc::CompactHeader h;
-      std::memcpy(&h, hm, sizeof h);
-      if (h.magic != glc::kCompactMagic || h.n_frames != r.nf || h.channels != ch || h.bytes > r.l.bound ||
-          h.n_pairs > r.nf * ch * glc::kHop || h.n_raw_rows > r.nf * ch)
-        return prog.set_error(GLC_EHIP, "glc_encode: the device wrote an inconsistent compact header");
-      const uint64_t p_at = p_used, r_at = r_used;
-      if (i == 0 && n_rounds > 1) {  // reserve the pools once from the first round's density (+ 30 %)
-        const double scale = static_cast<double>(plan.n_frames) / static_cast<double>(r.nf) * 1.3;
-        F->pairs.reserve(static_cast<size_t>(static_cast<double>(h.n_pairs) * scale) + 4096);
-        if (h.n_raw_rows) F->raw.reserve(static_cast<size_t>(static_cast<double>(h.n_raw_rows * glc::kFrame) * scale));
-      }
-      grow_pairs(p_at + h.n_pairs);
-      grow_raw(r_at + h.n_raw_rows * glc::kFrame);
-      p_used += h.n_pairs;
-      r_used += h.n_raw_rows * glc::kFrame;
-      pairs_per_frame.store(static_cast<double>(p_used) / static_cast<double>(r.f0 + r.nf) * 1.25, std::memory_order_relaxed);
-      const uint64_t have = std::min<uint64_t>(h.n_pairs, (first_bytes - r.l.o_pairs) / 4);  // pairs already on the host
-      if (h.n_pairs > have)
-        e = hipMemcpyAsync(F->pairs.data() + p_at + have, blob + r.l.o_pairs + have * 4, (h.n_pairs - have) * 4, hipMemcpyDeviceToHost,
-                           ctx->down_stream);
-      if (e == hipSuccess && h.n_raw_rows)
-        e = hipMemcpyAsync(F->raw.data() + r_at, blob + glc::compact_raw_offset(r.l, h.n_pairs), h.n_raw_rows * glc::kFrame * 2,
-                           hipMemcpyDeviceToHost, ctx->down_stream);
-      if (have) std::memcpy(F->pairs.data() + p_at, hm + r.l.o_pairs, have * 4);
-      bool canonical = true;
-      int rc = GLC_OK;
-      if (e == hipSuccess) rc = glc::index_compact_meta(F.get(), ch, h, hm, r.f0, p_at, r_at, /*trusted=*/true, &canonical);
-      // the pools may move when the next round grows them, and h_meta is reused: all of it has to have landed
-      if (h.n_pairs > have || h.n_raw_rows) {
-        const hipError_t e2 = drain(ctx->down_stream);
-        if (e == hipSuccess) e = e2;
-      }
-      if (e != hipSuccess) return prog.set_error(GLC_EHIP, hip_msg("glc_encode: download", e));
-      if (rc != GLC_OK) return prog.set_error(rc, std::string("glc_encode: ") + glc_last_error(nullptr));
+      if (i > 0) guess_pairs = static_cast<uint64_t>(pairs_per_frame * static_cast<double>(r.nf)) + 1024;
+      // the first of several rounds reserves the pools for the stream from its density (+ 30 %)
+      const double reserve = i == 0 && n_rounds > 1 ? static_cast<double>(plan.n_frames) / static_cast<double>(r.nf) * 1.3 : 0.0;
+      uint64_t n_pairs = 0, n_raw = 0;
+      const int rc = land_blob(ctx, "glc_encode", F.get(), static_cast<uint8_t *>(ctx->records.p) + r.f0 * rec, r.nf,
+                               d_blob + r.blob_off, r.f0, p_used, r_used, guess_pairs, reserve, ctx->down_stream, drain,
+                               &n_pairs, &n_raw);
+      if (rc != GLC_OK) return prog.set_error(rc, my_err);
+      p_used += n_pairs;
+      r_used += n_raw;
+      pairs_per_frame = static_cast<double>(p_used) / static_cast<double>(r.f0 + r.nf) * 1.25;
       complete = r.f0 + r.nf;
     }
     if (hook && delivered < complete) (void)deliver(complete);
@@ -1225,6 +1188,24 @@ int launch_d1(glc_ctx *ctx, uint32_t row_begin, uint32_t M, float *blocks) {
   return GLC_OK;
 }
 
+// One decode round: D1 of frames [f0, f0 + n) into block slots 1.., the overlap-add of their hops
+// (+ `tail`: the bare overlap tail, hop n_frames) into dout, then, when another round follows
+// (`carry`), the last frame's block copied to slot 0 for that round's overlap-add.
+int decode_round(glc_ctx *ctx, uint64_t f0, uint64_t n, bool tail, bool carry, float *dout) {
+  const uint32_t ch = ctx->dec_ch;
+  const size_t slot = static_cast<size_t>(ch) * glc::kFrame;  // floats per frame
+  float *blocks = static_cast<float *>(ctx->blocks.p);
+  if (n) {
+    const int rc = launch_d1(ctx, static_cast<uint32_t>(f0 * ch), static_cast<uint32_t>(n * ch), blocks + slot);
+    if (rc != GLC_OK) return rc;
+  }
+  GLC_HIP(ctx, glc::launch_overlap_add(blocks, static_cast<int64_t>(f0) - 1, ctx->dec_frames, ch, f0, f0 + n + (tail ? 1 : 0),
+                                       dout, ctx->stream));
+  if (carry)
+    GLC_HIP(ctx, hipMemcpyAsync(blocks, blocks + n * slot, slot * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+  return GLC_OK;
+}
+
 // Queue the kernels of the next round of at most `round_frames` frames of the prepared session into
 // `dout` (hop dec_next at dout[0]) and mark their completion with `ev`.  A round that reaches the
 // last frame also produces the bare overlap tail (src/codec.rs:722-729); `flush_at_full` selects
@@ -1233,24 +1214,13 @@ int launch_d1(glc_ctx *ctx, uint32_t row_begin, uint32_t M, float *blocks) {
 // the previous round's last frame for the overlap-add.
 int round_launch(glc_ctx *ctx, uint64_t round_frames, bool flush_at_full, float *dout, hipEvent_t ev,
                  uint64_t *frames_out, bool *last_out) {
-  const uint32_t ch = ctx->dec_ch;
-  const uint64_t nf = ctx->dec_frames, f0 = ctx->dec_next;
-  const uint64_t left = nf - f0;
+  const uint64_t f0 = ctx->dec_next, left = ctx->dec_frames - f0;
   const bool last = flush_at_full ? left < round_frames : left <= round_frames;
   const uint64_t n = last ? left : round_frames;
-  const size_t slot = static_cast<size_t>(ch) * glc::kFrame;  // floats per frame
   DeviceGuard guard(ctx->device);
-  float *blocks = static_cast<float *>(ctx->blocks.p);
   // (overlap = 0.0 before the first frame, :601: the overlap-add never reads slot 0 for hop 0)
-  if (n) {
-    const int rc = launch_d1(ctx, static_cast<uint32_t>(f0 * ch), static_cast<uint32_t>(n * ch), blocks + slot);
-    if (rc != GLC_OK) return rc;
-  }
-  GLC_HIP(ctx, glc::launch_overlap_add(blocks, static_cast<int64_t>(f0) - 1, nf, ch, f0, f0 + n + (last ? 1 : 0), dout,
-                                       ctx->stream));
-  if (!last)
-    GLC_HIP(ctx, hipMemcpyAsync(blocks, blocks + n * slot, slot * sizeof(float), hipMemcpyDeviceToDevice,
-                                ctx->stream));
+  const int rc = decode_round(ctx, f0, n, /*tail=*/last, /*carry=*/!last, dout);
+  if (rc != GLC_OK) return rc;
   GLC_HIP(ctx, hipEventRecord(ev, ctx->stream));
   ctx->dec_next = f0 + n;
   *frames_out = n;
@@ -1285,21 +1255,14 @@ int decode_hops_prepared(glc_ctx *ctx, uint64_t hop_begin, uint64_t hop_end, flo
     const int rc = launch_d1(ctx, static_cast<uint32_t>((hop_begin - 1) * ch), ch, blocks);
     if (rc != GLC_OK) return rc;
   }
-  uint64_t f0 = hop_begin;
-  do {
+  for (uint64_t f0 = hop_begin; f0 < hop_end;) {
     const uint64_t nchunk = f0 < f_end ? std::min(chunk, f_end - f0) : 0;
     const bool tail = f0 + nchunk == nf && hop_end == nf + 1;  // this round also emits the bare overlap tail
-    if (nchunk) {
-      const int rc = launch_d1(ctx, static_cast<uint32_t>(f0 * ch), static_cast<uint32_t>(nchunk * ch), blocks + slot);
-      if (rc != GLC_OK) return rc;
-    }
-    GLC_HIP(ctx, glc::launch_overlap_add(blocks, static_cast<int64_t>(f0) - 1, nf, ch, f0, f0 + nchunk + (tail ? 1 : 0),
-                                         d_out + (f0 - hop_begin) * glc::kHop * ch, ctx->stream));
-    f0 += nchunk + (tail ? 1 : 0);
-    if (f0 < hop_end)
-      GLC_HIP(ctx, hipMemcpyAsync(blocks, blocks + nchunk * slot, slot * sizeof(float), hipMemcpyDeviceToDevice,
-                                  ctx->stream));
-  } while (f0 < hop_end);
+    const uint64_t next = f0 + nchunk + (tail ? 1 : 0);
+    const int rc = decode_round(ctx, f0, nchunk, tail, /*carry=*/next < hop_end, d_out + (f0 - hop_begin) * glc::kHop * ch);
+    if (rc != GLC_OK) return rc;
+    f0 = next;
+  }
   return GLC_OK;
 }
 
@@ -1309,14 +1272,8 @@ int decode_hops_prepared(glc_ctx *ctx, uint64_t hop_begin, uint64_t hop_end, flo
 static int decode_prepared_to_host(glc_ctx *ctx, float *pcm_out, uint64_t cap, uint64_t *n_out, const char *who) {
   const uint64_t n_frames = ctx->dec_frames;
   const uint32_t channels = ctx->dec_ch;
-  // gapless trim, src/codec.rs:756-765 (delay counted in INTERLEAVED samples, quirk Q3)
-  const uint64_t all = (n_frames + 1) * static_cast<uint64_t>(glc::kHop) * channels;
-  uint64_t start = 0, n = all;
-  if (n > ctx->dec_delay) {
-    start = ctx->dec_delay;
-    n -= ctx->dec_delay;
-  }
-  if (n > ctx->dec_orig_len) n = ctx->dec_orig_len;
+  const glc::Trim trim = glc::gapless_trim(n_frames, channels, ctx->dec_delay, ctx->dec_orig_len);
+  const uint64_t start = trim.start, n = trim.n;
   if (n_out) *n_out = n;
   if (cap < n) return fail(ctx, GLC_EINVAL, std::string(who) + ": output buffer too small");
   ctx->dec_next = 0;
@@ -1387,17 +1344,11 @@ int glc_decode_device(glc_ctx *ctx, const glc_frames *in, float *d_all, uint64_t
                       uint64_t *n_out) {
   if (!ctx || !in || !d_all) return fail(ctx, GLC_EINVAL, "glc_decode_device: null argument");
   ctx->stream_open = false;
-  const uint32_t ch = in->channels;
-  const uint64_t all = (in->n_frames + 1) * static_cast<uint64_t>(glc::kHop) * ch;
-  if (cap_all < all) return fail(ctx, GLC_EINVAL, "glc_decode_device: output buffer too small");
-  uint64_t s0 = 0, n = all;
-  if (n > in->encoder_delay) {
-    s0 = in->encoder_delay;
-    n -= in->encoder_delay;
-  }
-  if (n > in->original_length) n = in->original_length;
-  if (start) *start = s0;
-  if (n_out) *n_out = n;
+  if (cap_all < (in->n_frames + 1) * static_cast<uint64_t>(glc::kHop) * in->channels)
+    return fail(ctx, GLC_EINVAL, "glc_decode_device: output buffer too small");
+  const glc::Trim trim = glc::gapless_trim(in->n_frames, in->channels, in->encoder_delay, in->original_length);
+  if (start) *start = trim.start;
+  if (n_out) *n_out = trim.n;
   int rc = decode_prepare(ctx, in);
   if (rc != GLC_OK) return rc;
   return decode_hops_prepared(ctx, 0, in->n_frames + 1, d_all);

@@ -42,6 +42,32 @@ void build_host_tables(uint32_t sample_rate, HostTables &t);
 // Padding arithmetic of Encoder::encode, src/codec.rs:433-455.
 glc_plan plan_encode(uint64_t n_samples, uint16_t channels);
 
+// Per-channel samples [lo, hi) that frames [f0, f1) read (f1 > f0), clipped to a stream of `per_channel`:
+// [hop*f0 - hop/2, hop*(f1-1) - hop/2 + frame), src/codec.rs:449-474.
+struct SampleWindow {
+  uint64_t lo, hi;
+};
+inline SampleWindow frame_sample_window(uint64_t f0, uint64_t f1, uint64_t per_channel) {
+  const uint64_t lo = f0 * kHop > kHop / 2 ? f0 * kHop - kHop / 2 : 0;
+  const uint64_t hi = (f1 - 1) * kHop + kFrame - kHop / 2;
+  return {lo, hi < per_channel ? hi : per_channel};
+}
+
+// Gapless trim of a decoded stream, src/codec.rs:756-765: the interleaved samples [start, start + n) of
+// the (n_frames + 1) hops.  The delay counts INTERLEAVED samples (quirk Q3).
+struct Trim {
+  uint64_t start, n;
+};
+inline Trim gapless_trim(uint64_t n_frames, uint32_t ch, uint64_t encoder_delay, uint64_t original_length) {
+  Trim t{0, (n_frames + 1) * static_cast<uint64_t>(kHop) * ch};
+  if (t.n > encoder_delay) {
+    t.start = encoder_delay;
+    t.n -= encoder_delay;
+  }
+  if (t.n > original_length) t.n = original_length;
+  return t;
+}
+
 // Fixed-size device record (see include/glc.h glc_record_bytes).
 inline uint64_t record_header_bytes(uint32_t ch) { return ((8ull + 8ull * ch) + 15ull) & ~15ull; }
 inline uint64_t record_bytes(uint32_t ch) {
@@ -84,7 +110,16 @@ inline CompactLayout compact_layout(uint32_t ch, uint64_t n_frames) {
 }
 inline uint64_t compact_raw_offset(const CompactLayout &l, uint64_t n_pairs) { return align64(l.o_pairs + 4 * n_pairs); }
 
+// A compact header from the device or a caller: magic, channel count, a frame count of at most (or,
+// `exact`, exactly) `n_frames`, pair and raw-row counts its rows can hold, and a `bytes` that is exactly
+// its sections and fits the `avail` bytes the blob arrived in.  nullptr, or what is wrong.
+const char *compact_header_error(const CompactHeader &h, uint32_t ch, uint64_t n_frames, bool exact, uint64_t avail);
+
 void set_global_error(const std::string &msg);
+
+// EncodedAudio of a stream planned by plan_encode (src/codec.rs:546-562): the header, zeroed per-frame
+// index vectors, list_off = {0} and room for one list and one scale per row.  May throw std::bad_alloc.
+void init_frames(glc_frames *F, uint32_t sample_rate, uint64_t n_samples, uint16_t channels, const glc_plan &plan);
 
 // Host assembly of EncodedAudio from compact blobs in frame order (glc_frames_from_compact).
 // `trusted`: the blobs were produced by this process's own pack kernels (lists known canonical).

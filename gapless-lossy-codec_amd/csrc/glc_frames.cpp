@@ -67,6 +67,39 @@ uint64_t next_frames_uid() {
   return (counter.fetch_add(1, std::memory_order_relaxed) + 1) | (1ull << 63);
 }
 
+// Zeroed per-frame index vectors of n_frames frames
+static void zero_index(glc_frames *F, uint64_t n_frames) {
+  F->n_frames = n_frames;
+  F->list_begin.assign(n_frames + 1, 0);
+  F->scale_begin.assign(n_frames + 1, 0);
+  F->raw_begin.assign(n_frames + 1, 0);
+  F->raw_tag.assign(n_frames, 0);
+}
+
+void init_frames(glc_frames *F, uint32_t sample_rate, uint64_t n_samples, uint16_t channels, const glc_plan &plan) {
+  F->sample_rate = sample_rate;
+  F->channels = channels;
+  F->total_samples = n_samples;           // src/codec.rs:423,555
+  F->encoder_delay = plan.encoder_delay;  // :547
+  F->padding = plan.padding;              // :546
+  F->original_length = n_samples;         // :562
+  zero_index(F, plan.n_frames);
+  // never reallocated while lists are appended: glc_encode_hooked's hook may be reading them
+  F->list_off.reserve(plan.n_frames * channels + 1);
+  F->list_off.assign(1, 0);
+  F->scales.reserve(plan.n_frames * channels);
+}
+
+const char *compact_header_error(const CompactHeader &h, uint32_t ch, uint64_t n_frames, bool exact, uint64_t avail) {
+  if (h.magic != kCompactMagic || h.channels != ch || h.n_frames > n_frames || (exact && h.n_frames != n_frames))
+    return "bad magic, channel count or frame count";
+  const uint64_t M = h.n_frames * ch;
+  if (h.n_pairs > M * kHop || h.n_raw_rows > M || h.n_raw_rows % ch != 0) return "corrupt blob (pair / raw-row counts)";
+  const uint64_t need = compact_raw_offset(compact_layout(ch, h.n_frames), h.n_pairs) + h.n_raw_rows * kFrame * 2;
+  if (h.bytes != need || avail < need) return "blob size does not match its header";
+  return nullptr;
+}
+
 // Index vectors of EncodedAudio for the frames of ONE compact blob whose payload (pairs, raw planes)
 // already sits in F->pairs / F->raw at p_at / r_at: per-frame raw tags, list offsets, scales.  Appends
 // to F->list_off (which starts as {0}: every list adds its end offset, so the vector is complete after
@@ -149,19 +182,8 @@ int frames_from_compact(uint32_t sample_rate, uint64_t n_samples, uint16_t chann
     }
     CompactHeader &h = hdrs[b];
     std::memcpy(&h, blobs[b], sizeof h);
-    if (h.magic != kCompactMagic || h.channels != ch || h.n_frames > plan.n_frames) {
-      set_global_error("glc_frames_from_compact: bad magic, channel count or frame count");
-      return GLC_EFORMAT;
-    }
-    const CompactLayout l = compact_layout(ch, h.n_frames);
-    const uint64_t M = h.n_frames * ch;
-    if (h.n_pairs > M * kHop || h.n_raw_rows > M || h.n_raw_rows % ch != 0) {
-      set_global_error("glc_frames_from_compact: corrupt blob (pair / raw-row counts)");
-      return GLC_EFORMAT;
-    }
-    const uint64_t need = compact_raw_offset(l, h.n_pairs) + h.n_raw_rows * kFrame * 2;
-    if (h.bytes != need || blob_bytes[b] < need) {
-      set_global_error("glc_frames_from_compact: blob size does not match its header");
+    if (const char *bad = compact_header_error(h, ch, plan.n_frames, /*exact=*/false, blob_bytes[b])) {
+      set_global_error(std::string("glc_frames_from_compact: ") + bad);
       return GLC_EFORMAT;
     }
     n_frames += h.n_frames;
@@ -174,27 +196,11 @@ int frames_from_compact(uint32_t sample_rate, uint64_t n_samples, uint16_t chann
   }
   std::unique_ptr<glc_frames> F(new (std::nothrow) glc_frames);
   if (!F) return GLC_ENOMEM;
-  F->sample_rate = sample_rate;
-  F->channels = channels;
-  F->total_samples = n_samples;           // src/codec.rs:423,555
-  F->encoder_delay = plan.encoder_delay;  // :547
-  F->padding = plan.padding;              // :546
-  F->original_length = n_samples;         // :562
-  F->n_frames = n_frames;
   bool canonical = true;
   try {
-    F->list_begin.assign(n_frames + 1, 0);
-    F->scale_begin.assign(n_frames + 1, 0);
-    F->raw_begin.assign(n_frames + 1, 0);
-    F->raw_tag.resize(n_frames);
+    init_frames(F.get(), sample_rate, n_samples, channels, plan);
     F->pairs.resize(n_pairs);
     F->raw.resize(n_raw_rows * kFrame);
-    const uint64_t n_comp_rows = n_frames * ch - n_raw_rows;
-    F->list_off.clear();
-    F->list_off.reserve(n_comp_rows + 1);
-    F->list_off.push_back(0);
-    F->scales.clear();
-    F->scales.reserve(n_comp_rows);
     uint64_t f_at = 0, p_at = 0, r_at = 0;  // frames / pairs / raw samples placed so far
     for (uint32_t b = 0; b < n_blobs; ++b) {
       const CompactHeader &h = hdrs[b];
@@ -321,18 +327,8 @@ int glc_frames_from_records(uint32_t sample_rate, uint64_t n_samples, uint16_t c
   if (!F) return GLC_ENOMEM;
   const uint32_t ch = channels;
   const uint64_t rec = glc::record_bytes(ch), hdr = glc::record_header_bytes(ch);
-  F->sample_rate = sample_rate;
-  F->channels = channels;
-  F->total_samples = n_samples;           // src/codec.rs:423,555
-  F->encoder_delay = plan.encoder_delay;  // :547
-  F->padding = plan.padding;              // :546
-  F->original_length = n_samples;         // :562
-  F->n_frames = n_frames;
   try {
-    F->list_begin.assign(n_frames + 1, 0);
-    F->scale_begin.assign(n_frames + 1, 0);
-    F->raw_begin.assign(n_frames + 1, 0);
-    F->raw_tag.assign(n_frames, 0);
+    glc::init_frames(F.get(), sample_rate, n_samples, channels, plan);
     // pass 1: sizes
     uint64_t n_lists = 0, n_pairs = 0, n_scales = 0, n_raw = 0;
     const uint8_t *base = static_cast<const uint8_t *>(records);
@@ -645,6 +641,11 @@ int glc_frames_get_view(const glc_frames *f, glc_frames_view *out) {
 
 namespace {
 
+// Largest counts a caller-built stream may claim (glc_frames_from_parts / _gather): every count, and every
+// byte size derived from one, is addressable and far from wrapping
+constexpr uint64_t kMaxFrames = 1ull << 40, kMaxLists = 1ull << 44, kMaxPairs = 1ull << 46, kMaxScales = 1ull << 44,
+                   kMaxRaw = 1ull << 46;
+
 // offsets[0 .. n] must start at 0, never decrease and end at `total`
 bool offsets_ok(const uint64_t *off, uint64_t n, uint64_t total) {
   if (!off || off[0] != 0 || off[n] != total) return false;
@@ -669,8 +670,7 @@ int glc_frames_from_parts(const glc_frames_view *p, uint64_t stream_id, glc_fram
   *out = nullptr;
   const uint64_t nf = p->n_frames;
   // every count must be addressable before anything is read through it
-  if (nf > (1ull << 40) || p->n_lists > (1ull << 44) || p->n_pairs > (1ull << 46) || p->n_scales > (1ull << 44) ||
-      p->n_raw > (1ull << 46)) {
+  if (nf > kMaxFrames || p->n_lists > kMaxLists || p->n_pairs > kMaxPairs || p->n_scales > kMaxScales || p->n_raw > kMaxRaw) {
     glc::set_global_error("glc_frames_from_parts: absurd counts");
     return GLC_EFORMAT;
   }
@@ -709,7 +709,7 @@ int glc_frames_from_parts(const glc_frames_view *p, uint64_t stream_id, glc_fram
     F->raw_tag.assign(p->raw_tag, p->raw_tag + nf);
     F->raw_begin.assign(p->raw_begin, p->raw_begin + nf + 1);
     F->raw.assign(p->raw, p->raw + p->n_raw);
-  } catch (const std::bad_alloc &) {
+  } catch (const std::exception &) {  // nothing may cross the C ABI
     return GLC_ENOMEM;
   }
   F->lists_canonical = false;  // checked at decode
@@ -721,13 +721,43 @@ int glc_frames_from_gather(const glc_frames_gather *g, uint64_t stream_id, glc_f
   if (!g || !out) return GLC_EINVAL;
   *out = nullptr;
   const uint64_t nf = g->n_frames;
-  if (nf > (1ull << 40)) {
+  if (nf > kMaxFrames) {
     glc::set_global_error("glc_frames_from_gather: absurd frame count");
     return GLC_EFORMAT;
   }
   if (nf && (!g->lists_per_frame || !g->scales_per_frame || !g->scale_ptr || !g->raw_ptr || !g->raw_len)) {
     glc::set_global_error("glc_frames_from_gather: null array");
     return GLC_EINVAL;
+  }
+  // pass 1: sizes, bounded like glc_frames_from_parts' counts before anything is allocated (a u32 adds
+  // at most 2^32 to a sum kept below 2^46; a raw length is checked against the room left)
+  uint64_t n_lists = 0, n_pairs = 0, n_scales = 0, n_raw = 0;
+  for (uint64_t f = 0; f < nf; ++f) {
+    const uint32_t nl = g->lists_per_frame[f];
+    if (nl && (!g->list_ptr || !g->list_len)) {
+      glc::set_global_error("glc_frames_from_gather: null list array");
+      return GLC_EINVAL;
+    }
+    for (uint32_t l = 0; l < nl; ++l) {
+      if (g->list_len[n_lists + l] && !g->list_ptr[n_lists + l]) {
+        glc::set_global_error("glc_frames_from_gather: null list pointer with a non-zero length");
+        return GLC_EINVAL;
+      }
+      n_pairs += g->list_len[n_lists + l];
+      if (n_pairs > kMaxPairs) break;
+    }
+    if (g->scales_per_frame[f] && !g->scale_ptr[f]) {
+      glc::set_global_error("glc_frames_from_gather: null scale pointer with a non-zero length");
+      return GLC_EINVAL;
+    }
+    n_lists += nl;
+    n_scales += g->scales_per_frame[f];
+    const uint64_t nr = g->raw_ptr[f] ? g->raw_len[f] : 0;
+    if (n_lists > kMaxLists || n_pairs > kMaxPairs || n_scales > kMaxScales || nr > kMaxRaw - n_raw) {
+      glc::set_global_error("glc_frames_from_gather: absurd counts");
+      return GLC_EFORMAT;
+    }
+    n_raw += nr;
   }
   std::unique_ptr<glc_frames> F(new (std::nothrow) glc_frames);
   if (!F) return GLC_ENOMEM;
@@ -740,46 +770,13 @@ int glc_frames_from_gather(const glc_frames_gather *g, uint64_t stream_id, glc_f
     F->encoder_delay = g->encoder_delay;
     F->padding = g->padding;
     F->original_length = g->original_length;
-    F->n_frames = nf;
-    F->list_begin.assign(nf + 1, 0);
-    F->scale_begin.assign(nf + 1, 0);
-    F->raw_begin.assign(nf + 1, 0);
-    F->raw_tag.assign(nf, 0);
-    // pass 1: sizes
-    uint64_t n_lists = 0, n_pairs = 0, n_scales = 0, n_raw = 0;
-    for (uint64_t f = 0; f < nf; ++f) {
-      const uint32_t nl = g->lists_per_frame[f];
-      if (nl && (!g->list_ptr || !g->list_len)) {
-        glc::set_global_error("glc_frames_from_gather: null list array");
-        return GLC_EINVAL;
-      }
-      for (uint32_t l = 0; l < nl; ++l) {
-        if (g->list_len[n_lists + l] && !g->list_ptr[n_lists + l]) {
-          glc::set_global_error("glc_frames_from_gather: null list pointer with a non-zero length");
-          return GLC_EINVAL;
-        }
-        n_pairs += g->list_len[n_lists + l];
-      }
-      n_lists += nl;
-      if (g->scales_per_frame[f] && !g->scale_ptr[f]) {
-        glc::set_global_error("glc_frames_from_gather: null scale pointer with a non-zero length");
-        return GLC_EINVAL;
-      }
-      n_scales += g->scales_per_frame[f];
-      if (g->raw_ptr[f]) {
-        F->raw_tag[f] = 1;
-        n_raw += g->raw_len[f];
-      }
-      F->list_begin[f + 1] = n_lists;
-      F->scale_begin[f + 1] = n_scales;
-      F->raw_begin[f + 1] = n_raw;
-    }
+    glc::zero_index(F.get(), nf);
     F->list_off.resize(n_lists + 1);
     F->pairs.resize(n_pairs);
     F->scales.resize(n_scales);
     F->raw.resize(n_raw);
-    // pass 2: payload, one copy per vector
-    uint64_t li = 0, pi = 0;
+    // pass 2: index vectors and payload, one copy per vector
+    uint64_t li = 0, pi = 0, si = 0, ri = 0;
     for (uint64_t f = 0; f < nf; ++f) {
       const uint32_t nl = g->lists_per_frame[f];
       for (uint32_t l = 0; l < nl; ++l, ++li) {
@@ -789,12 +786,19 @@ int glc_frames_from_gather(const glc_frames_gather *g, uint64_t stream_id, glc_f
         pi += n;
       }
       const uint32_t ns = g->scales_per_frame[f];
-      if (ns) std::memcpy(F->scales.data() + F->scale_begin[f], g->scale_ptr[f], static_cast<size_t>(ns) * 4);
-      if (g->raw_ptr[f] && g->raw_len[f])
-        std::memcpy(F->raw.data() + F->raw_begin[f], g->raw_ptr[f], g->raw_len[f] * 2);
+      if (ns) std::memcpy(F->scales.data() + si, g->scale_ptr[f], static_cast<size_t>(ns) * 4);
+      si += ns;
+      if (g->raw_ptr[f]) {
+        F->raw_tag[f] = 1;
+        if (g->raw_len[f]) std::memcpy(F->raw.data() + ri, g->raw_ptr[f], g->raw_len[f] * 2);
+        ri += g->raw_len[f];
+      }
+      F->list_begin[f + 1] = li;
+      F->scale_begin[f + 1] = si;
+      F->raw_begin[f + 1] = ri;
     }
     F->list_off[n_lists] = pi;
-  } catch (const std::bad_alloc &) {
+  } catch (const std::exception &) {  // nothing may cross the C ABI
     return GLC_ENOMEM;
   }
   F->lists_canonical = false;  // checked at decode
@@ -805,12 +809,7 @@ int glc_frames_from_gather(const glc_frames_gather *g, uint64_t stream_id, glc_f
 uint64_t glc_frames_stream_id(const glc_frames *f) { return f ? f->uid : 0; }
 
 uint64_t glc_decoded_len(const glc_frames *f) {
-  if (!f) return 0;
-  // src/codec.rs:756-765
-  uint64_t all = (f->n_frames + 1) * static_cast<uint64_t>(glc::kHop) * f->channels;
-  if (all > f->encoder_delay) all -= f->encoder_delay;
-  if (all > f->original_length) all = f->original_length;
-  return all;
+  return f ? glc::gapless_trim(f->n_frames, f->channels, f->encoder_delay, f->original_length).n : 0;
 }
 
 const char *glc_version(void) { return "glc-mi355x 0.1 (reference gapless-lossy-codec 0.5.0)"; }

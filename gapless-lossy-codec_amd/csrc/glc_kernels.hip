@@ -13,6 +13,7 @@
 //   K3 k_decide_raw    :496-502 (raw plane) + :505-540 (size estimate, decision)
 //   D1 k_imdct_rows    :626-644 (raw frames), :651-665 (dequant), :377-390 (imdct), :672-675
 //   D2 k_overlap_add   :688-705 (overlap-add + interleave), :722-729 (tail)
+#include "glc_common.h"
 #include "glc_kernels.h"
 #include "glc_mdct_fwd.hpp"
 
@@ -1078,8 +1079,7 @@ hipError_t launch_quantize(const DeviceTables &t, const float *coef, uint32_t M,
                            uint64_t frame_begin, uint8_t *records, hipStream_t s, bool *decided) {
   *decided = ch == 1 || ch == 2 || ch == 4;  // a frame's rows sit in one wave: K2 decides raw-vs-compressed itself
   if (M == 0) return hipSuccess;
-  const unsigned long long hdr = ((8ull + 8ull * ch) + 15ull) & ~15ull;
-  const unsigned long long rec = hdr + 2ull * kFrameI * ch;
+  const unsigned long long hdr = record_header_bytes(ch), rec = record_bytes(ch);
   const dim3 grid((M + 4 * kQRows - 1) / (4 * kQRows));
   if (*decided)
     hipLaunchKernelGGL(k_quantize<true>, grid, dim3(256), 0, s, t, coef, M, ch, rec, hdr, pcm,
@@ -1093,8 +1093,7 @@ hipError_t launch_quantize(const DeviceTables &t, const float *coef, uint32_t M,
 hipError_t launch_decide_raw(const DeviceTables &t, const PcmView &pcm, uint64_t frame_begin,
                              uint32_t n_frames, uint8_t *records, hipStream_t s) {
   if (n_frames == 0) return hipSuccess;
-  const unsigned long long hdr = ((8ull + 8ull * pcm.ch) + 15ull) & ~15ull;
-  const unsigned long long rec = hdr + 2ull * kFrameI * pcm.ch;
+  const unsigned long long hdr = record_header_bytes(pcm.ch), rec = record_bytes(pcm.ch);
   hipLaunchKernelGGL(k_decide_raw, dim3(n_frames), dim3(256), 0, s, t, pcm,
                      static_cast<long long>(frame_begin), n_frames, rec, hdr, records);
   return hipGetLastError();
@@ -1109,8 +1108,7 @@ hipError_t launch_compact(const uint8_t *records, uint32_t M, uint32_t ch, uint6
                        reinterpret_cast<unsigned long long *>(blk_raw), 0u, t, ch, 0ull, static_cast<unsigned long long>(o_pairs), blob);
     return hipGetLastError();
   }
-  const unsigned long long hdr = ((8ull + 8ull * ch) + 15ull) & ~15ull;
-  const unsigned long long rec = hdr + 2ull * kFrameI * ch;
+  const unsigned long long hdr = record_header_bytes(ch), rec = record_bytes(ch);
   const unsigned nblk = (M + 1023) / 1024;
   auto *b = reinterpret_cast<unsigned long long *>(blk);
   auto *br = reinterpret_cast<unsigned long long *>(blk_raw);

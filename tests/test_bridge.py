@@ -115,6 +115,54 @@ def test_from_parts_rejects_inconsistent_arrays():
     assert glc_amd.lib.glc_frames_from_parts(None, 0, C.byref(out)) == -1
 
 
+GATHER_PAST_THE_BOUNDS = r"""
+import ctypes as C, sys
+sys.path.insert(0, %r)
+import glc_amd
+from glc_amd._lib import GlcFramesGather
+
+keep = []
+def arr(t, v):
+    a = (t * max(len(v), 1))(*v)
+    keep.append(a)
+    return C.cast(a, C.c_void_p)
+
+def gather(lists_per_frame, list_len, raw_len):
+    dummy = (C.c_int16 * 4)()
+    keep.append(dummy)
+    nf = len(lists_per_frame)
+    g = GlcFramesGather()
+    g.channels, g.n_frames = 1, nf
+    g.lists_per_frame = arr(C.c_uint32, lists_per_frame)
+    g.list_ptr = arr(C.c_void_p, [C.addressof(dummy)] * len(list_len))
+    g.list_len = arr(C.c_uint32, list_len)
+    g.scales_per_frame = arr(C.c_uint32, [0] * nf)
+    g.scale_ptr = arr(C.c_void_p, [None] * nf)
+    g.raw_ptr = arr(C.c_void_p, [C.addressof(dummy) if r is not None else None for r in raw_len])
+    g.raw_len = arr(C.c_uint64, [r or 0 for r in raw_len])
+    out = C.c_void_p()
+    print(glc_amd.lib.glc_frames_from_gather(C.byref(g), 0, C.byref(out)), flush=True)
+
+gather([0], [], [1 << 63])                       # one raw vector longer than a vector can be
+gather([0, 0], [], [1 << 63, 1 << 63])           # two whose total wraps to 0
+gather([16385], [0xFFFFFFFF] * 16385, [None])    # list lengths totalling past 2^46 pairs
+"""
+
+
+def test_gather_rejects_counts_past_the_bounds():
+    """glc_frames_from_gather bounds its running totals like glc_frames_from_parts bounds its counts,
+    before it allocates: a raw length above what a vector can hold, raw lengths whose total wraps, and
+    list lengths that total more than any pool holds are GLC_EFORMAT.  (u32 list lengths cannot wrap a
+    64-bit total without 2^32 of them; the bound is reached first.)  In a child process: without the
+    bounds the first terminates the process and the second builds a stream whose raw offsets point far
+    outside its empty raw pool."""
+    import sys
+    r = subprocess.run([sys.executable, "-c", GATHER_PAST_THE_BOUNDS % ROOT], cwd=ROOT, capture_output=True,
+                       text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.split() == [str(glc_amd._lib.GLC_EFORMAT)] * 3, r.stdout + r.stderr
+
+
 def test_gather_accepts_general_streams():
     """Any well-formed EncodedAudio: more lists than channels, empty lists, Some(vec![]), no scales."""
     hdr = glc_amd.AudioHeader(44100, 2, 12345)
