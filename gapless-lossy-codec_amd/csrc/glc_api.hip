@@ -1380,6 +1380,31 @@ int glc_imdct_device(glc_ctx *ctx, const glc_frames *in, uint64_t frame_begin, u
   return launch_d1(ctx, static_cast<uint32_t>(frame_begin * ch), static_cast<uint32_t>((frame_end - frame_begin) * ch), d_blocks);
 }
 
+int glc_debug_overlap_add_device(glc_ctx *ctx, const float *d_blocks, int64_t blk_frame0, uint64_t n_block_frames,
+                                 uint64_t n_frames, uint16_t channels, uint64_t hop_begin, uint64_t hop_end, float *d_out,
+                                 uint64_t cap) {
+  if (!ctx) return GLC_EINVAL;
+  if (!d_blocks || !d_out) return fail(ctx, GLC_EINVAL, "glc_debug_overlap_add_device: null argument");
+  if (channels == 0) return fail(ctx, GLC_EINVAL, "glc_debug_overlap_add_device: channels == 0");
+  if (hop_begin > hop_end || hop_end > n_frames + 1 || n_frames > 0xFFFFFFFFull)
+    return fail(ctx, GLC_EINVAL, "glc_debug_overlap_add_device: hop range out of bounds");
+  if (cap < (hop_end - hop_begin) * glc::kHop * channels)
+    return fail(ctx, GLC_EINVAL, "glc_debug_overlap_add_device: output buffer too small");
+  if (hop_begin < hop_end) {
+    // frames the hops read: hop h takes frame h - 1 (h >= 1) and frame h (h < n_frames)
+    const uint64_t first = hop_begin ? hop_begin - 1 : 0;
+    const uint64_t last = std::min(hop_end, n_frames);  // one past the last frame read
+    // d_blocks holds frames [blk_frame0, blk_frame0 + n_block_frames); -1 is the decode rounds' ring (slot 0 = carried frame)
+    const int64_t held_end = blk_frame0 + static_cast<int64_t>(n_block_frames);
+    if (blk_frame0 < -1 || n_block_frames > 0xFFFFFFFFull ||
+        (first < last && (static_cast<int64_t>(first) < blk_frame0 || static_cast<int64_t>(last) > held_end)))
+      return fail(ctx, GLC_EINVAL, "glc_debug_overlap_add_device: the hops read frames outside d_blocks");
+  }
+  DeviceGuard guard(ctx->device);
+  GLC_HIP(ctx, glc::launch_overlap_add(d_blocks, blk_frame0, n_frames, channels, hop_begin, hop_end, d_out, ctx->stream));
+  return GLC_OK;
+}
+
 int glc_debug_set_imdct_variant(glc_ctx *ctx, int variant) {
   if (!ctx || variant < 0 || variant > 6) return fail(ctx, GLC_EINVAL, "glc_debug_set_imdct_variant: variant must be 0..6");
   if (variant != ctx->d1_variant) ctx->plan_uid = 0;  // variants 5 / 6 deal the units differently: the kept order is not theirs

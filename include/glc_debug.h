@@ -1,7 +1,8 @@
 /*
  * glc_debug.h - cross-check hooks of libglc_hip.so.  NOT part of the drop-in boundary (that is
  * include/glc.h): these entry points exist so that soak tools and tests can run one stream through
- * two independent implementations of the same arithmetic and demand identical bits.
+ * two independent implementations of the same arithmetic and demand identical bits, or drive one kernel
+ * stage on inputs built for the purpose (tests/test_quantizer_edges.py, tests/test_decode_edges.py).
  */
 #ifndef GLC_DEBUG_H
 #define GLC_DEBUG_H
@@ -48,6 +49,18 @@ int glc_debug_set_mdct_variant(glc_ctx *ctx, int variant);
 int glc_debug_quantize_device(glc_ctx *ctx, const float *d_coeffs, const float *d_pcm, uint64_t t0, uint64_t t_count,
                               uint64_t n_samples, uint16_t channels, uint64_t frame_begin, uint64_t frame_end,
                               void *d_records);
+
+/* D2 (k_overlap_add) exactly as the decode rounds launch it, on caller-supplied blocks: d_blocks holds the
+ * frames [blk_frame0, blk_frame0 + n_block_frames) of a stream of n_frames frames as [frame][channel][2048]
+ * (blk_frame0 = -1: slot 0 is the carried frame in front of frame 0, which hop 0 never reads); hops
+ * [hop_begin, hop_end) go to d_out (cap floats; any 4-byte aligned device pointer), hop n_frames being the bare
+ * tail.  Arguments are checked (hop range, the frames the hops read lie inside d_blocks, cap); the work is
+ * queued on the context's stream and nothing is synchronised.  tests/test_decode_edges.py drives the
+ * overlap-add through this with -0.0 / inf / NaN operands and launches of more than 32768 hops, which no
+ * decode entry point can feed it. */
+int glc_debug_overlap_add_device(glc_ctx *ctx, const float *d_blocks, int64_t blk_frame0, uint64_t n_block_frames,
+                                 uint64_t n_frames, uint16_t channels, uint64_t hop_begin, uint64_t hop_end, float *d_out,
+                                 uint64_t cap);
 
 /* The shader clock the device HOLDS under load (measurement only; bench.py's roofline.clock_ghz_held).
  * `begin` starts one sleeping wave on a stream of its own that runs for `window_us` microseconds beside

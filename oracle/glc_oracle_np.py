@@ -260,7 +260,7 @@ def decode(glc: bytes) -> np.ndarray:
         else:
             co = np.zeros((ch, HOP), F32)
             for c in range(ch):
-                s = max(F32(scales[c]), F32(1e-12))
+                s = np.fmax(F32(scales[c]), F32(1e-12))  # f32::max (:653) ignores a NaN scale
                 qs = lists[c][:, 1].copy().view(np.int16)
                 for index, qv in zip(lists[c][:, 0].tolist(), qs.tolist()):
                     if index < HOP:

@@ -1,4 +1,4 @@
-"""Soak of the decode kernels: random sparse streams (random list lengths 0..400, a random share of
+"""Soak of the decode kernels: random sparse streams (random list lengths 0..1024, a random share of
 common indices, random raw frames, 1..3 channels) are decoded three ways - the shipped plan + apply
 kernels (absent row pairs skipped), the same without the skip, and the
 one-row kernel (include/glc_debug.h) - and all outputs must be bit-identical.
@@ -28,7 +28,7 @@ for r in range(rounds):
     M = nf * ch
     rec = glc_amd.lib.glc_record_bytes(ch)
     hdr = rec - 4096 * ch
-    nnz = rng.integers(0, 401, M)
+    nnz = rng.integers(0, 1025, M)
     nnz[rng.random(M) < 0.05] = 0
     order = np.argsort(rng.random((M, 1024)), axis=1)                 # a random permutation of the bins per row
     common = rng.permutation(1024)
