@@ -9,6 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libglc_hip.so")
 
 GLC_OK, GLC_EINVAL, GLC_EHIP, GLC_ENOMEM, GLC_EFORMAT, GLC_ENODEV, GLC_EIO = 0, -1, -2, -3, -4, -5, -6
+GLC_PCM_S16, GLC_PCM_S32, GLC_PCM_F32 = 1, 2, 3  # glc_pcm_format
 
 
 class GlcInfo(C.Structure):
@@ -164,6 +165,17 @@ SIGNATURES = {
                                 C.POINTER(C.c_uint16)]),
     "glc_flac_decode": (C.c_int, [_vp, C.c_uint64, C.POINTER(_vp), C.POINTER(C.c_uint64),
                                   C.POINTER(C.c_uint32), C.POINTER(C.c_uint16)]),
+    "glc_pcm_widen_device": (C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.c_uint64, _vp]),
+    "glc_encode_int": (C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.c_uint64, C.c_uint16, C.POINTER(_vp)]),
+    "glc_decode_i16": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "glc_decode_range_device_i16": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, C.c_uint64]),
+    "glc_decode_stream_next_i16": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "glc_audio_load_pcm": (C.c_int, [C.c_char_p, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(C.c_uint32),
+                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint16)]),
+    "glc_wav_save16_i16": (C.c_int, [C.c_char_p, _vp, C.c_uint64, C.c_uint32, C.c_uint16]),
+    "glc_flac_encode_i16": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint16, C.c_uint8, C.POINTER(_vp),
+                                      C.POINTER(C.c_uint64)]),
+    "glc_flac_save_i16": (C.c_int, [C.c_char_p, _vp, C.c_uint64, C.c_uint32, C.c_uint16, C.c_uint8]),
     "glc_version": (C.c_char_p, []),
 }
 

@@ -21,8 +21,8 @@ from typing import Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import (FRAMES_HOOK, GLC_EINVAL, GlcCompactInfo, GlcError, GlcFramesGather, GlcFramesView, GlcInfo, GlcPlan,
-                   check, lib)
+from ._lib import (FRAMES_HOOK, GLC_EINVAL, GLC_PCM_F32, GLC_PCM_S16, GLC_PCM_S32, GlcCompactInfo, GlcError,
+                   GlcFramesGather, GlcFramesView, GlcInfo, GlcPlan, check, lib)
 
 FRAME_SIZE = 2048        # src/codec.rs:15
 HOP_SIZE = 1024          # src/codec.rs:16
@@ -297,6 +297,31 @@ def plan_encode(n_samples: int, channels: int) -> GlcPlan:
     return p
 
 
+_PCM_FORMATS = {np.dtype(np.int16): (GLC_PCM_S16, 16), np.dtype(np.int32): (GLC_PCM_S32, 32),
+                np.dtype(np.float32): (GLC_PCM_F32, 32)}
+_PCM_DTYPES = {GLC_PCM_S16: np.int16, GLC_PCM_S32: np.int32, GLC_PCM_F32: np.float32}
+
+
+def pcm_format(samples, bits: Optional[int] = None):
+    """(flat C-contiguous array, glc_pcm_format, bits) of samples handed to an encoder: float32, or
+    int16 / int32 holding `bits`-bit values (default: the container's width).  An array of any other
+    dtype raises TypeError - nothing is cast silently; a plain sequence is taken as float32."""
+    dt = getattr(samples, "dtype", None)
+    if dt is None:
+        samples, dt = np.asarray(samples, np.float32), np.dtype(np.float32)
+    if np.dtype(dt) not in _PCM_FORMATS:
+        raise TypeError(f"samples must be float32, int16 or int32, not {dt}")
+    fmt, width = _PCM_FORMATS[np.dtype(dt)]
+    if fmt == GLC_PCM_F32:
+        if bits is not None:
+            raise TypeError("bits applies to integer samples only")
+    else:
+        bits = width if bits is None else int(bits)
+        if not 1 <= bits <= width:
+            raise GlcError(GLC_EINVAL, f"bits must be 1..{width} for {np.dtype(dt)} samples")
+    return np.ascontiguousarray(samples).reshape(-1), fmt, bits or 32
+
+
 class _Ctx:
     def __init__(self, sample_rate: int, device: int):
         h = C.c_void_p()
@@ -358,13 +383,27 @@ class Encoder(_Ctx):
     def __init__(self, sample_rate: int, device: int = 0):
         super().__init__(sample_rate, device)
 
-    def encode(self, samples, channels: int) -> EncodedAudio:
-        """Encoder::encode(&mut self, samples: &[f32], channels: u16) — src/codec.rs:421."""
-        pcm = np.ascontiguousarray(samples, np.float32).reshape(-1)
+    def encode(self, samples, channels: int, bits: Optional[int] = None) -> EncodedAudio:
+        """Encoder::encode(&mut self, samples: &[f32], channels: u16) — src/codec.rs:421.  int16 /
+        int32 samples (of `bits` bits, default the container's width) are encoded as the reference
+        encodes what its loaders make of them, s / 2^(bits-1) - widened on the device (glc_encode_int)."""
+        pcm, fmt, bits = pcm_format(samples, bits)
         out = C.c_void_p()
-        check(lib.glc_encode(self._h, pcm.ctypes.data_as(C.c_void_p), pcm.size, channels, C.byref(out)),
-              self._h)
+        if fmt == GLC_PCM_F32:
+            check(lib.glc_encode(self._h, pcm.ctypes.data_as(C.c_void_p), pcm.size, channels, C.byref(out)),
+                  self._h)
+        else:
+            check(lib.glc_encode_int(self._h, pcm.ctypes.data_as(C.c_void_p), fmt, bits, pcm.size, channels,
+                                     C.byref(out)), self._h)
         return EncodedAudio(out.value)
+
+    def widen_device(self, d_in: int, dtype, bits: int, n: int, d_out: int) -> None:
+        """glc_pcm_widen_device: n int16 / int32 samples of `bits` bits at device address d_in ->
+        float32 at d_out, s / 2^(bits-1).  Queued on the context's stream, not synchronised."""
+        if np.dtype(dtype) not in _PCM_FORMATS:
+            raise TypeError(f"samples must be float32, int16 or int32, not {np.dtype(dtype)}")
+        check(lib.glc_pcm_widen_device(self._h, C.c_void_p(d_in), _PCM_FORMATS[np.dtype(dtype)][0], bits, n,
+                                       C.c_void_p(d_out)), self._h)
 
     def encode_hooked(self, samples, channels: int, hook) -> EncodedAudio:
         """glc_encode_hooked: `hook(parts, frame_begin, frame_end)` is called each time a range of frames
@@ -432,25 +471,36 @@ class Decoder(_Ctx):
         if sender is not None:
             sender(kind, value)
 
-    def decode(self, encoded: EncodedAudio, progress_sender=None, out: Optional[np.ndarray] = None) -> np.ndarray:
+    @staticmethod
+    def _out_dtype(dtype) -> np.dtype:
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.int16)):
+            raise TypeError(f"decoded samples are float32 or int16, not {dt}")
+        return dt
+
+    def decode(self, encoded: EncodedAudio, progress_sender=None, out: Optional[np.ndarray] = None,
+               dtype=np.float32) -> np.ndarray:
         """Decoder::decode — src/codec.rs:744-768 (overlap-add, gapless trim).  `out` (optional, not
-        in the reference): a float32 array of at least total_samples to decode into, for callers
-        that reuse a buffer - pages that were touched before take the D2H copies much faster."""
+        in the reference): an array of `dtype` of at least total_samples to decode into, for callers
+        that reuse a buffer - pages that were touched before take the D2H copies much faster.
+        dtype=np.int16: the samples as the reference's 16-bit writers narrow them,
+        (s * 32767).clamp(-32768, 32767) as i16, narrowed on the device (glc_decode_i16)."""
+        dt = self._out_dtype(dtype)
         if progress_sender is not None:  # the reference decodes through decode_streaming (:747)
-            chunks = [c.samples for c in self.decode_streaming(encoded, progress_sender)]
-            allv = np.concatenate(chunks) if chunks else np.empty(0, np.float32)
+            chunks = [c.samples for c in self.decode_streaming(encoded, progress_sender, dtype=dt)]
+            allv = np.concatenate(chunks) if chunks else np.empty(0, dt)
             g = encoded.gapless_info
             if allv.size > g.encoder_delay:
                 allv = allv[g.encoder_delay:]
             return allv[:g.original_length].copy()
         n = lib.glc_decoded_len(encoded._h)
         if out is None:
-            out = np.empty(n, np.float32)
-        elif out.dtype != np.float32 or not out.flags.c_contiguous or out.size < n:
-            raise GlcError(GLC_EINVAL, "out must be a C-contiguous float32 array of at least total_samples")
+            out = np.empty(n, dt)
+        elif out.dtype != dt or not out.flags.c_contiguous or out.size < n:
+            raise GlcError(GLC_EINVAL, f"out must be a C-contiguous {dt} array of at least total_samples")
         got = C.c_uint64()
-        check(lib.glc_decode(self._h, encoded._h, out.ctypes.data_as(C.c_void_p), n, C.byref(got)),
-              self._h)
+        fn = lib.glc_decode if dt == np.float32 else lib.glc_decode_i16
+        check(fn(self._h, encoded._h, out.ctypes.data_as(C.c_void_p), n, C.byref(got)), self._h)
         return out[:got.value]
 
     def resident_stream(self) -> int:
@@ -478,14 +528,22 @@ class Decoder(_Ctx):
         memory at address d_out (glc_decode_range_device).  Queued, not synchronised."""
         check(lib.glc_decode_range_device(self._h, encoded._h, hop_begin, hop_end, C.c_void_p(d_out), cap), self._h)
 
+    def decode_range_device_i16(self, encoded: EncodedAudio, hop_begin: int, hop_end: int, d_out: int, cap: int) -> None:
+        """decode_range_device writing int16 samples, narrowed as Decoder.decode(dtype=np.int16) does
+        (glc_decode_range_device_i16).  Queued, not synchronised."""
+        check(lib.glc_decode_range_device_i16(self._h, encoded._h, hop_begin, hop_end, C.c_void_p(d_out), cap), self._h)
+
     def imdct_device(self, encoded: EncodedAudio, frame_begin: int, frame_end: int, d_blocks: int) -> None:
         """Dequant + imdct_block + window (src/codec.rs:651-675) alone for a frame range:
         d_blocks[(frame - frame_begin) * ch + c][2048] on the device (glc_imdct_device)."""
         check(lib.glc_imdct_device(self._h, encoded._h, frame_begin, frame_end, C.c_void_p(d_blocks)), self._h)
 
-    def decode_streaming(self, encoded: EncodedAudio, progress_sender=None) -> Iterator[AudioChunk]:
-        """Decoder::decode_streaming — src/codec.rs:595-741: yields AudioChunk until is_last."""
+    def decode_streaming(self, encoded: EncodedAudio, progress_sender=None, dtype=np.float32) -> Iterator[AudioChunk]:
+        """Decoder::decode_streaming — src/codec.rs:595-741: yields AudioChunk until is_last
+        (dtype=np.int16: chunks of narrowed samples, glc_decode_stream_next_i16)."""
         import time as _time
+        dt = self._out_dtype(dtype)
+        nxt = lib.glc_decode_stream_next if dt == np.float32 else lib.glc_decode_stream_next_i16
         t0 = _time.perf_counter()
         total_frames = encoded.info().n_frames
         self._progress(progress_sender, "Status", f"Starting streaming decode of {total_frames} frames")
@@ -494,11 +552,10 @@ class Decoder(_Ctx):
         cap = FRAMES_PER_CHUNK * HOP_SIZE * ch  # the last chunk is < 500 frames + the tail hop
         done = 0
         while True:
-            buf = np.empty(cap, np.float32)
+            buf = np.empty(cap, dt)
             n = C.c_uint64()
             last = C.c_int()
-            check(lib.glc_decode_stream_next(self._h, buf.ctypes.data_as(C.c_void_p), cap, C.byref(n),
-                                             C.byref(last)), self._h)
+            check(nxt(self._h, buf.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(last)), self._h)
             done += FRAMES_PER_CHUNK
             if not last.value and total_frames:
                 self._progress(progress_sender, "Decoding", min(done, total_frames) / total_frames * 100.0)
@@ -536,10 +593,18 @@ def load_wav(path):
     return out, sr.value, ch.value
 
 
+def _f32_or_i16(samples):
+    """Samples for a 16-bit writer: an int16 array is written as it is, anything else as float32."""
+    if getattr(samples, "dtype", None) == np.int16:
+        return np.ascontiguousarray(samples).reshape(-1), True
+    return np.ascontiguousarray(samples, np.float32).reshape(-1), False
+
+
 def export_to_wav(path, samples, sample_rate: int, channels: int) -> None:
-    """audio::export_to_wav (src/audio.rs:100-132): 16-bit PCM."""
-    s = np.ascontiguousarray(samples, np.float32).reshape(-1)
-    check(lib.glc_wav_save16(str(path).encode(), s.ctypes.data_as(C.c_void_p), s.size, sample_rate, channels))
+    """audio::export_to_wav (src/audio.rs:100-132): 16-bit PCM (int16 samples: already narrowed)."""
+    s, narrowed = _f32_or_i16(samples)
+    fn = lib.glc_wav_save16_i16 if narrowed else lib.glc_wav_save16
+    check(fn(str(path).encode(), s.ctypes.data_as(C.c_void_p), s.size, sample_rate, channels))
 
 
 def _take_f32(ptr, n):
@@ -551,14 +616,15 @@ def _take_f32(ptr, n):
 
 
 def encode_flac_with_level(samples, sample_rate: int, channels: int, compression_level: int) -> bytes:
-    """flac::encode_flac_with_level (src/flac.rs:947-1053): the reference's own FLAC encoder."""
-    s = np.ascontiguousarray(samples, np.float32).reshape(-1)
+    """flac::encode_flac_with_level (src/flac.rs:947-1053): the reference's own FLAC encoder
+    (int16 samples: already narrowed)."""
+    s, narrowed = _f32_or_i16(samples)
     if not 0 <= int(compression_level) <= 255 or not 0 <= int(channels) <= 0xFFFF:
         raise GlcError(-1, "compression_level is a u8 and channels a u16 in the reference")
     ptr = C.c_void_p()
     n = C.c_uint64()
-    check(lib.glc_flac_encode(s.ctypes.data_as(C.c_void_p), s.size, sample_rate, channels, compression_level,
-                              C.byref(ptr), C.byref(n)))
+    fn = lib.glc_flac_encode_i16 if narrowed else lib.glc_flac_encode
+    check(fn(s.ctypes.data_as(C.c_void_p), s.size, sample_rate, channels, compression_level, C.byref(ptr), C.byref(n)))
     try:
         return C.string_at(ptr, n.value)
     finally:
@@ -572,9 +638,9 @@ def encode_flac(samples, sample_rate: int, channels: int) -> bytes:
 
 def export_to_flac_with_level(path, samples, sample_rate: int, channels: int, compression_level: int) -> None:
     """flac::export_to_flac_with_level (src/flac.rs:1066-1077)."""
-    s = np.ascontiguousarray(samples, np.float32).reshape(-1)
-    check(lib.glc_flac_save(str(path).encode(), s.ctypes.data_as(C.c_void_p), s.size, sample_rate, channels,
-                            compression_level))
+    s, narrowed = _f32_or_i16(samples)
+    fn = lib.glc_flac_save_i16 if narrowed else lib.glc_flac_save
+    check(fn(str(path).encode(), s.ctypes.data_as(C.c_void_p), s.size, sample_rate, channels, compression_level))
 
 
 def export_to_flac(path, samples, sample_rate: int, channels: int) -> None:
@@ -615,3 +681,23 @@ def load_audio_file_lossless(path):
     if ext == "flac":
         return load_flac(path)
     raise GlcError(-1, f"Unsupported file format: {ext}")
+
+
+def load_audio_file_pcm(path):
+    """load_audio_file_lossless before the widening (glc_audio_load_pcm) -> (samples, bits,
+    sample_rate, channels): int16 for integer sources of at most 16 bits, int32 for wider ones,
+    float32 for float WAV - what Encoder.encode(samples, channels, bits=bits) takes."""
+    ptr = C.c_void_p()
+    fmt = C.c_int()
+    bits = C.c_uint32()
+    n = C.c_uint64()
+    sr = C.c_uint32()
+    ch = C.c_uint16()
+    check(lib.glc_audio_load_pcm(str(path).encode(), C.byref(ptr), C.byref(fmt), C.byref(bits), C.byref(n),
+                                 C.byref(sr), C.byref(ch)))
+    try:
+        dt = np.dtype(_PCM_DTYPES[fmt.value])
+        out = np.frombuffer(C.string_at(ptr, n.value * dt.itemsize), dt).copy() if n.value else np.empty(0, dt)
+    finally:
+        lib.glc_free(ptr)
+    return out, bits.value, sr.value, ch.value

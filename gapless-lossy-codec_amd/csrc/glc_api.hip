@@ -142,6 +142,7 @@ struct glc_ctx {
   DevBuf tables;     // all constant tables in one allocation
   DevBuf coef;       // MDCT coefficient workspace [rows][1024]
   DevBuf pcm;        // staging for host-boundary encode / decode output
+  DevBuf pcm_int;    // glc_encode_int: the integer samples as uploaded, widened into `pcm` on the device
   DevBuf records;    // staging for host-boundary encode
   DevBuf blocks;     // decode: windowed IMDCT blocks [(chunk+1)][ch][2048]
   DevBuf dec_meta;   // decode: pairs / offsets / scales / raw pool
@@ -169,6 +170,7 @@ struct glc_ctx {
   uint32_t dec_ch = 0;
   uint64_t dec_frames = 0, dec_next = 0;
   bool stream_open = false;  // glc_decode_stream_begin called, last chunk not yet delivered
+  int stream_elem = 0;       // bytes per sample of the chunks handed out so far (4: float, 2: int16_t; 0: none yet)
   // streaming session: chunk i is copied to the host while chunk i+1 is already being decoded
   DevBuf stream_out;                           // two chunk-sized output buffers
   hipEvent_t ev_dec[2] = {nullptr, nullptr};   // "kernels of the chunk in buffer b are done"
@@ -362,6 +364,7 @@ void glc_ctx_destroy(glc_ctx *ctx) {
   ctx->tables.release();
   ctx->coef.release();
   ctx->pcm.release();
+  ctx->pcm_int.release();
   ctx->records.release();
   ctx->blocks.release();
   ctx->dec_meta.release();
@@ -704,9 +707,52 @@ int glc_encode(glc_ctx *ctx, const float *pcm, uint64_t n_samples, uint16_t chan
   return glc_encode_hooked(ctx, pcm, n_samples, channels, nullptr, nullptr, out);
 }
 
+// The host-boundary encode of glc_encode / glc_encode_hooked (fmt == GLC_PCM_F32: `pcm` are floats) and
+// of glc_encode_int (int16_t / int32_t samples of `bits` bits, widened on the device as they arrive).
+static int encode_pipeline(glc_ctx *ctx, const void *pcm_any, glc_pcm_format fmt, uint32_t bits, uint64_t n_samples,
+                           uint16_t channels, glc_frames_hook hook, void *hook_user, glc_frames **out);
+
 int glc_encode_hooked(glc_ctx *ctx, const float *pcm, uint64_t n_samples, uint16_t channels,
                       glc_frames_hook hook, void *hook_user, glc_frames **out) {
-  if (!ctx || !pcm || (!out && !hook)) return fail(ctx, GLC_EINVAL, "glc_encode: null argument");
+  return encode_pipeline(ctx, pcm, GLC_PCM_F32, 32, n_samples, channels, hook, hook_user, out);
+}
+
+int glc_encode_int(glc_ctx *ctx, const void *pcm, glc_pcm_format fmt, uint32_t bits, uint64_t n_samples,
+                   uint16_t channels, glc_frames **out) {
+  if (!ctx || !pcm || !out) return fail(ctx, GLC_EINVAL, "glc_encode_int: null argument");
+  *out = nullptr;
+  if (fmt == GLC_PCM_F32) return glc_encode(ctx, static_cast<const float *>(pcm), n_samples, channels, out);
+  if (fmt != GLC_PCM_S16 && fmt != GLC_PCM_S32) return fail(ctx, GLC_EINVAL, "glc_encode_int: unknown sample format");
+  if (bits == 0 || bits > (fmt == GLC_PCM_S16 ? 16u : 32u))
+    return fail(ctx, GLC_EINVAL, "glc_encode_int: bits must be 1..16 for 16-bit samples, 1..32 for 32-bit ones");
+  return encode_pipeline(ctx, pcm, fmt, bits, n_samples, channels, nullptr, nullptr, out);
+}
+
+int glc_pcm_widen_device(glc_ctx *ctx, const void *d_in, glc_pcm_format fmt, uint32_t bits, uint64_t n, float *d_out) {
+  if (!ctx || ((!d_in || !d_out) && n)) return fail(ctx, GLC_EINVAL, "glc_pcm_widen_device: null argument");
+  if (fmt != GLC_PCM_S16 && fmt != GLC_PCM_S32 && fmt != GLC_PCM_F32)
+    return fail(ctx, GLC_EINVAL, "glc_pcm_widen_device: unknown sample format");
+  if (fmt != GLC_PCM_F32 && (bits == 0 || bits > (fmt == GLC_PCM_S16 ? 16u : 32u)))
+    return fail(ctx, GLC_EINVAL, "glc_pcm_widen_device: bits must be 1..16 for 16-bit samples, 1..32 for 32-bit ones");
+  const uintptr_t mis = (reinterpret_cast<uintptr_t>(d_in) & (fmt == GLC_PCM_S16 ? 1u : 3u)) | (reinterpret_cast<uintptr_t>(d_out) & 3u);
+  if (n && mis) return fail(ctx, GLC_EINVAL, "glc_pcm_widen_device: a pointer is not aligned to its sample size");
+  if (n == 0) return GLC_OK;
+  DeviceGuard guard(ctx->device);
+  if (fmt == GLC_PCM_F32) {
+    if (d_in != d_out) GLC_HIP(ctx, hipMemcpyAsync(d_out, d_in, n * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    return GLC_OK;
+  }
+  GLC_HIP(ctx, glc::launch_pcm_widen(d_in, fmt == GLC_PCM_S32, bits, n, d_out, ctx->stream));
+  return GLC_OK;
+}
+
+static int encode_pipeline(glc_ctx *ctx, const void *pcm_any, glc_pcm_format fmt, uint32_t bits, uint64_t n_samples,
+                           uint16_t channels, glc_frames_hook hook, void *hook_user, glc_frames **out) {
+  if (!ctx || !pcm_any || (!out && !hook)) return fail(ctx, GLC_EINVAL, "glc_encode: null argument");
+  const float *pcm = static_cast<const float *>(pcm_any);          // GLC_PCM_F32
+  const uint8_t *pcm_int = static_cast<const uint8_t *>(pcm_any);  // the integer formats
+  const bool is_int = fmt != GLC_PCM_F32;
+  const size_t elem = fmt == GLC_PCM_S16 ? 2 : 4;
   if (out) *out = nullptr;
   const glc_plan plan = glc::plan_encode(n_samples, channels);
   if (plan.n_frames == 0)
@@ -776,6 +822,7 @@ int glc_encode_hooked(glc_ctx *ctx, const float *pcm, uint64_t n_samples, uint16
   const size_t stage_cap = std::max<size_t>(std::min<size_t>(align_up(glc::compact_layout(ch, max_nf).bound, 256), size_t(64) << 20),
                                             align_up(glc::compact_layout(ch, max_nf).o_pairs, 256));
   GLC_HIP(ctx, ctx->pcm.reserve(static_cast<size_t>(t_count) * ch * sizeof(float)));
+  if (is_int) GLC_HIP(ctx, ctx->pcm_int.reserve(static_cast<size_t>(t_count) * ch * elem));
   GLC_HIP(ctx, ctx->records.reserve(static_cast<size_t>(plan.n_frames) * rec));
   GLC_HIP(ctx, ctx->pack_blob.reserve(rounds.back().blob_off + align_up(rounds.back().l.bound, 256)));
   GLC_HIP(ctx, ctx->host_stage.reserve(stage_cap));
@@ -828,18 +875,29 @@ int glc_encode_hooked(glc_ctx *ctx, const float *pcm, uint64_t n_samples, uint16
   auto hip_msg = [](const char *what, hipError_t e) { return std::string(what) + ": " + hipGetErrorString(e); };
   double pairs_per_frame = 0.0;  // stored pairs per frame so far, + 25 % (sizes the next round's first copy)
 
+  // Integer samples go up as they are, 2 or 4 bytes each, and the round's increment is widened into
+  // d_pcm behind its copy: the launcher finds the same floats as after a float upload.  A stream of a
+  // single round has nothing to run ahead of: its copy and its widening are queued on the stream the
+  // round's kernels follow on, and nobody waits for them on the host.
+  uint8_t *d_int = static_cast<uint8_t *>(ctx->pcm_int.p);
+  hipStream_t up_stream = is_int && n_rounds == 1 ? ctx->stream : ctx->copy_stream;
   auto upload = [&] {  // stage 1
     DeviceGuard g(ctx->device);
     uint64_t copied = 0;
     for (size_t i = 0; i < n_rounds; ++i) {
       const Round &r = rounds[i];
       hipError_t e = hipSuccess;
-      if (r.hi > copied)
+      if (r.hi > copied && !is_int)
         e = hipMemcpyAsync(d_pcm + copied, pcm + copied, (r.hi - copied) * sizeof(float), hipMemcpyHostToDevice, ctx->copy_stream);
+      if (r.hi > copied && is_int) {
+        e = hipMemcpyAsync(d_int + copied * elem, pcm_int + copied * elem, (r.hi - copied) * elem, hipMemcpyHostToDevice, up_stream);
+        if (e == hipSuccess)
+          e = glc::launch_pcm_widen(d_int + copied * elem, fmt == GLC_PCM_S32, bits, r.hi - copied, d_pcm + copied, up_stream);
+      }
       copied = std::max(copied, r.hi);
       // a copy from pageable memory has completed when the call returns; should the runtime ever
       // queue it instead, this is where it is waited for (the launcher queues nothing behind it)
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->copy_stream);
+      if (e == hipSuccess && up_stream == ctx->copy_stream) e = hipStreamSynchronize(ctx->copy_stream);
       if (e != hipSuccess) return prog.set_error(e == hipErrorOutOfMemory ? GLC_ENOMEM : GLC_EHIP, hip_msg("glc_encode: upload", e));
       prog.advance(prog.uploaded);
       { std::lock_guard<std::mutex> lk(prog.mu); if (prog.rc != GLC_OK) return; }
@@ -1009,6 +1067,7 @@ int glc_encode_hooked(glc_ctx *ctx, const float *pcm, uint64_t n_samples, uint16
 
 // ------------------------------------------------------------------------------ decode
 
+extern "C++" {  // templates over the output sample type
 namespace {
 
 // Upload the sparse representation of `in` and reset the overlap state: after this the stream
@@ -1188,10 +1247,22 @@ int launch_d1(glc_ctx *ctx, uint32_t row_begin, uint32_t M, float *blocks) {
   return GLC_OK;
 }
 
+// D2 by output type: float samples, or int16_t ones narrowed as the reference's 16-bit writers do
+inline hipError_t launch_d2(const float *blocks, int64_t blk_frame0, uint64_t n_frames, uint32_t ch, uint64_t hop_begin,
+                            uint64_t hop_end, float *out, hipStream_t s) {
+  return glc::launch_overlap_add(blocks, blk_frame0, n_frames, ch, hop_begin, hop_end, out, s);
+}
+inline hipError_t launch_d2(const float *blocks, int64_t blk_frame0, uint64_t n_frames, uint32_t ch, uint64_t hop_begin,
+                            uint64_t hop_end, int16_t *out, hipStream_t s) {
+  return glc::launch_overlap_add_i16(blocks, blk_frame0, n_frames, ch, hop_begin, hop_end, out, s);
+}
+
 // One decode round: D1 of frames [f0, f0 + n) into block slots 1.., the overlap-add of their hops
 // (+ `tail`: the bare overlap tail, hop n_frames) into dout, then, when another round follows
 // (`carry`), the last frame's block copied to slot 0 for that round's overlap-add.
-int decode_round(glc_ctx *ctx, uint64_t f0, uint64_t n, bool tail, bool carry, float *dout) {
+// T (here and below): the sample type of the output, float or int16_t.
+template <typename T>
+int decode_round(glc_ctx *ctx, uint64_t f0, uint64_t n, bool tail, bool carry, T *dout) {
   const uint32_t ch = ctx->dec_ch;
   const size_t slot = static_cast<size_t>(ch) * glc::kFrame;  // floats per frame
   float *blocks = static_cast<float *>(ctx->blocks.p);
@@ -1199,8 +1270,8 @@ int decode_round(glc_ctx *ctx, uint64_t f0, uint64_t n, bool tail, bool carry, f
     const int rc = launch_d1(ctx, static_cast<uint32_t>(f0 * ch), static_cast<uint32_t>(n * ch), blocks + slot);
     if (rc != GLC_OK) return rc;
   }
-  GLC_HIP(ctx, glc::launch_overlap_add(blocks, static_cast<int64_t>(f0) - 1, ctx->dec_frames, ch, f0, f0 + n + (tail ? 1 : 0),
-                                       dout, ctx->stream));
+  GLC_HIP(ctx, launch_d2(blocks, static_cast<int64_t>(f0) - 1, ctx->dec_frames, ch, f0, f0 + n + (tail ? 1 : 0), dout,
+                         ctx->stream));
   if (carry)
     GLC_HIP(ctx, hipMemcpyAsync(blocks, blocks + n * slot, slot * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
   return GLC_OK;
@@ -1212,7 +1283,8 @@ int decode_round(glc_ctx *ctx, uint64_t f0, uint64_t n, bool tail, bool carry, f
 // the reference's streaming rule (a chunk is flushed once it holds >= 500 frames, :708-717, so a
 // stream of exactly k*500 frames ends with a tail-only chunk).  Slot 0 of the block ring carries
 // the previous round's last frame for the overlap-add.
-int round_launch(glc_ctx *ctx, uint64_t round_frames, bool flush_at_full, float *dout, hipEvent_t ev,
+template <typename T>
+int round_launch(glc_ctx *ctx, uint64_t round_frames, bool flush_at_full, T *dout, hipEvent_t ev,
                  uint64_t *frames_out, bool *last_out) {
   const uint64_t f0 = ctx->dec_next, left = ctx->dec_frames - f0;
   const bool last = flush_at_full ? left < round_frames : left <= round_frames;
@@ -1241,7 +1313,8 @@ int ensure_copy_objects(glc_ctx *ctx) {
 // decode_prepare.  A range that does not start at 0 recomputes frame hop_begin-1 as its halo: the
 // only state the overlap-add carries (src/codec.rs:701-705), which is what lets GPUs decode
 // disjoint hop ranges of one stream independently.
-int decode_hops_prepared(glc_ctx *ctx, uint64_t hop_begin, uint64_t hop_end, float *d_out) {
+template <typename T>
+int decode_hops_prepared(glc_ctx *ctx, uint64_t hop_begin, uint64_t hop_end, T *d_out) {
   if (hop_end <= hop_begin) return GLC_OK;
   const uint32_t ch = ctx->dec_ch;
   const uint64_t nf = ctx->dec_frames;
@@ -1266,10 +1339,9 @@ int decode_hops_prepared(glc_ctx *ctx, uint64_t hop_begin, uint64_t hop_end, flo
   return GLC_OK;
 }
 
-}  // namespace
-
 // Decoder::decode of the prepared session into host memory (src/codec.rs:744-768).
-static int decode_prepared_to_host(glc_ctx *ctx, float *pcm_out, uint64_t cap, uint64_t *n_out, const char *who) {
+template <typename T>
+int decode_prepared_to_host(glc_ctx *ctx, T *pcm_out, uint64_t cap, uint64_t *n_out, const char *who) {
   const uint64_t n_frames = ctx->dec_frames;
   const uint32_t channels = ctx->dec_ch;
   const glc::Trim trim = glc::gapless_trim(n_frames, channels, ctx->dec_delay, ctx->dec_orig_len);
@@ -1282,16 +1354,16 @@ static int decode_prepared_to_host(glc_ctx *ctx, float *pcm_out, uint64_t cap, u
   // one round overlaps the decode of the next.  The block ring is sized once: slot 0 carries state.
   const uint64_t round = std::max<uint64_t>(1, std::min<uint64_t>(kDecodeChunkFrames, n_frames));
   const uint64_t per_hop = static_cast<uint64_t>(glc::kHop) * channels;
-  const size_t bufcap = static_cast<size_t>(round + 1) * per_hop;  // floats per output buffer
+  const size_t bufcap = static_cast<size_t>(round + 1) * per_hop;  // samples per output buffer
   {
     DeviceGuard guard(ctx->device);
     GLC_HIP(ctx, ctx->blocks.reserve((round + 1) * static_cast<size_t>(channels) * glc::kFrame * sizeof(float)));
-    GLC_HIP(ctx, ctx->pcm.reserve(2 * bufcap * sizeof(float)));
+    GLC_HIP(ctx, ctx->pcm.reserve(2 * bufcap * sizeof(T)));
   }
   int rc = ensure_copy_objects(ctx);
   if (rc != GLC_OK) return rc;
   DeviceGuard guard(ctx->device);
-  float *stage = static_cast<float *>(ctx->pcm.p);
+  T *stage = static_cast<T *>(ctx->pcm.p);
   int buf = 0;
   uint64_t f0 = 0, frames = 0;
   bool last = false;
@@ -1312,7 +1384,7 @@ static int decode_prepared_to_host(glc_ctx *ctx, float *pcm_out, uint64_t cap, u
     if (cs != ctx->stream) GLC_HIP(ctx, hipStreamWaitEvent(cs, ctx->ev_dec[buf], 0));
     if (hi > lo)
       GLC_HIP(ctx, hipMemcpyAsync(pcm_out + (lo - start), stage + static_cast<size_t>(buf) * bufcap + (lo - c_lo),
-                                  (hi - lo) * sizeof(float), hipMemcpyDeviceToHost, cs));
+                                  (hi - lo) * sizeof(T), hipMemcpyDeviceToHost, cs));
     GLC_HIP(ctx, hipStreamSynchronize(cs));
     if (cur_last) break;
     buf ^= 1;
@@ -1320,14 +1392,90 @@ static int decode_prepared_to_host(glc_ctx *ctx, float *pcm_out, uint64_t cap, u
   return GLC_OK;
 }
 
-int glc_decode(glc_ctx *ctx, const glc_frames *in, float *pcm_out, uint64_t cap, uint64_t *n_out) {
-  if (!ctx || !in || (!pcm_out && cap)) return fail(ctx, GLC_EINVAL, "glc_decode: null argument");
+// glc_decode / glc_decode_i16
+template <typename T>
+int decode_to_host(glc_ctx *ctx, const glc_frames *in, T *pcm_out, uint64_t cap, uint64_t *n_out, const char *who) {
+  if (!ctx || !in || (!pcm_out && cap)) return fail(ctx, GLC_EINVAL, std::string(who) + ": null argument");
   ctx->stream_open = false;
   if (n_out) *n_out = glc_decoded_len(in);
-  if (cap < glc_decoded_len(in)) return fail(ctx, GLC_EINVAL, "glc_decode: output buffer too small");
+  if (cap < glc_decoded_len(in)) return fail(ctx, GLC_EINVAL, std::string(who) + ": output buffer too small");
   const int rc = decode_prepare(ctx, in);
   if (rc != GLC_OK) return rc;
-  return decode_prepared_to_host(ctx, pcm_out, cap, n_out, "glc_decode");
+  return decode_prepared_to_host(ctx, pcm_out, cap, n_out, who);
+}
+
+// glc_decode_range_device / glc_decode_range_device_i16
+template <typename T>
+int decode_range_device(glc_ctx *ctx, const glc_frames *in, uint64_t hop_begin, uint64_t hop_end, T *d_out, uint64_t cap,
+                        const char *who) {
+  if (!ctx || !in || !d_out) return fail(ctx, GLC_EINVAL, std::string(who) + ": null argument");
+  ctx->stream_open = false;
+  if (hop_begin > hop_end || hop_end > in->n_frames + 1)
+    return fail(ctx, GLC_EINVAL, std::string(who) + ": hop range out of bounds");
+  if (cap < (hop_end - hop_begin) * glc::kHop * in->channels)
+    return fail(ctx, GLC_EINVAL, std::string(who) + ": output buffer too small");
+  if (reinterpret_cast<uintptr_t>(d_out) % sizeof(T))
+    return fail(ctx, GLC_EINVAL, std::string(who) + ": output pointer not aligned to its sample size");
+  int rc = decode_prepare(ctx, in);
+  if (rc != GLC_OK) return rc;
+  return decode_hops_prepared(ctx, hop_begin, hop_end, d_out);
+}
+
+// glc_decode_stream_next / glc_decode_stream_next_i16.  glc_decode_stream_begin cannot know which of
+// the two will read the stream and queues the first chunk as floats; a stream read as int16_t queues
+// that one chunk again (its plan records are still in place) before it goes on as the float one does.
+template <typename T>
+int decode_stream_next(glc_ctx *ctx, T *chunk, uint64_t cap, uint64_t *n_out, int *is_last) {
+  if (!ctx || !n_out || !is_last) return fail(ctx, GLC_EINVAL, "glc_decode_stream_next: null argument");
+  if (!ctx->stream_open) return fail(ctx, GLC_EINVAL, "glc_decode_stream_next: no stream open");
+  if (ctx->stream_elem != 0 && ctx->stream_elem != static_cast<int>(sizeof(T)))
+    return fail(ctx, GLC_EINVAL, "glc_decode_stream_next: this stream is being read in the other sample format");
+  const int buf = ctx->stream_buf;
+  const size_t bufcap = (static_cast<size_t>(GLC_FRAMES_PER_CHUNK) + 1) * glc::kHop * ctx->dec_ch;
+  T *stage = static_cast<T *>(ctx->stream_out.p);
+  if (ctx->stream_elem == 0 && sizeof(T) != sizeof(float)) {
+    ctx->dec_next = 0;
+    const int rc = round_launch(ctx, GLC_FRAMES_PER_CHUNK, true, stage + static_cast<size_t>(buf) * bufcap, ctx->ev_dec[buf],
+                                &ctx->stream_frames, &ctx->stream_last);
+    if (rc != GLC_OK) {
+      ctx->stream_open = false;
+      return rc;
+    }
+  }
+  const bool last = ctx->stream_last;
+  const uint64_t per_hop = static_cast<uint64_t>(glc::kHop) * ctx->dec_ch;
+  const uint64_t n = (ctx->stream_frames + (last ? 1 : 0)) * per_hop;
+  *n_out = n;
+  *is_last = last ? 1 : 0;
+  ctx->stream_elem = static_cast<int>(sizeof(T));
+  if (cap < n || (!chunk && n)) return fail(ctx, GLC_EINVAL, "glc_decode_stream_next: chunk buffer too small");
+  DeviceGuard guard(ctx->device);
+  // double buffering: the kernels of the following chunk are queued first, then this chunk is
+  // copied out on the copy stream as soon as its own kernels have finished
+  if (!last) {
+    const int rc = round_launch(ctx, GLC_FRAMES_PER_CHUNK, true, stage + static_cast<size_t>(buf ^ 1) * bufcap,
+                                ctx->ev_dec[buf ^ 1], &ctx->stream_frames, &ctx->stream_last);
+    if (rc != GLC_OK) return rc;
+  }
+  GLC_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_dec[buf], 0));
+  if (n)
+    GLC_HIP(ctx, hipMemcpyAsync(chunk, stage + static_cast<size_t>(buf) * bufcap, n * sizeof(T), hipMemcpyDeviceToHost,
+                                ctx->copy_stream));
+  GLC_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
+  ctx->stream_buf = buf ^ 1;
+  if (last) ctx->stream_open = false;
+  return GLC_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int glc_decode(glc_ctx *ctx, const glc_frames *in, float *pcm_out, uint64_t cap, uint64_t *n_out) {
+  return decode_to_host(ctx, in, pcm_out, cap, n_out, "glc_decode");
+}
+
+int glc_decode_i16(glc_ctx *ctx, const glc_frames *in, int16_t *pcm_out, uint64_t cap, uint64_t *n_out) {
+  return decode_to_host(ctx, in, pcm_out, cap, n_out, "glc_decode_i16");
 }
 
 uint64_t glc_ctx_resident_stream(const glc_ctx *ctx) { return ctx ? ctx->dec_uid : 0; }
@@ -1356,15 +1504,12 @@ int glc_decode_device(glc_ctx *ctx, const glc_frames *in, float *d_all, uint64_t
 
 int glc_decode_range_device(glc_ctx *ctx, const glc_frames *in, uint64_t hop_begin, uint64_t hop_end,
                             float *d_out, uint64_t cap) {
-  if (!ctx || !in || !d_out) return fail(ctx, GLC_EINVAL, "glc_decode_range_device: null argument");
-  ctx->stream_open = false;
-  if (hop_begin > hop_end || hop_end > in->n_frames + 1)
-    return fail(ctx, GLC_EINVAL, "glc_decode_range_device: hop range out of bounds");
-  if (cap < (hop_end - hop_begin) * glc::kHop * in->channels)
-    return fail(ctx, GLC_EINVAL, "glc_decode_range_device: output buffer too small");
-  int rc = decode_prepare(ctx, in);
-  if (rc != GLC_OK) return rc;
-  return decode_hops_prepared(ctx, hop_begin, hop_end, d_out);
+  return decode_range_device(ctx, in, hop_begin, hop_end, d_out, cap, "glc_decode_range_device");
+}
+
+int glc_decode_range_device_i16(glc_ctx *ctx, const glc_frames *in, uint64_t hop_begin, uint64_t hop_end,
+                                int16_t *d_out, uint64_t cap) {
+  return decode_range_device(ctx, in, hop_begin, hop_end, d_out, cap, "glc_decode_range_device_i16");
 }
 
 int glc_imdct_device(glc_ctx *ctx, const glc_frames *in, uint64_t frame_begin, uint64_t frame_end,
@@ -1453,6 +1598,7 @@ int glc_decode_stream_begin(glc_ctx *ctx, const glc_frames *in) {
   rc = ensure_copy_objects(ctx);
   if (rc != GLC_OK) return rc;
   ctx->stream_buf = 0;
+  ctx->stream_elem = 0;
   // the first chunk is on its way before the caller asks for it
   rc = round_launch(ctx, GLC_FRAMES_PER_CHUNK, true, static_cast<float *>(ctx->stream_out.p), ctx->ev_dec[0],
                     &ctx->stream_frames, &ctx->stream_last);
@@ -1462,33 +1608,11 @@ int glc_decode_stream_begin(glc_ctx *ctx, const glc_frames *in) {
 }
 
 int glc_decode_stream_next(glc_ctx *ctx, float *chunk, uint64_t cap, uint64_t *n_out, int *is_last) {
-  if (!ctx || !n_out || !is_last) return fail(ctx, GLC_EINVAL, "glc_decode_stream_next: null argument");
-  if (!ctx->stream_open) return fail(ctx, GLC_EINVAL, "glc_decode_stream_next: no stream open");
-  const int buf = ctx->stream_buf;
-  const bool last = ctx->stream_last;
-  const uint64_t per_hop = static_cast<uint64_t>(glc::kHop) * ctx->dec_ch;
-  const uint64_t n = (ctx->stream_frames + (last ? 1 : 0)) * per_hop;
-  *n_out = n;
-  *is_last = last ? 1 : 0;
-  if (cap < n || (!chunk && n)) return fail(ctx, GLC_EINVAL, "glc_decode_stream_next: chunk buffer too small");
-  const size_t bufcap = (static_cast<size_t>(GLC_FRAMES_PER_CHUNK) + 1) * per_hop;
-  DeviceGuard guard(ctx->device);
-  // double buffering: the kernels of the following chunk are queued first, then this chunk is
-  // copied out on the copy stream as soon as its own kernels have finished
-  if (!last) {
-    const int rc = round_launch(ctx, GLC_FRAMES_PER_CHUNK, true,
-                                static_cast<float *>(ctx->stream_out.p) + static_cast<size_t>(buf ^ 1) * bufcap,
-                                ctx->ev_dec[buf ^ 1], &ctx->stream_frames, &ctx->stream_last);
-    if (rc != GLC_OK) return rc;
-  }
-  GLC_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_dec[buf], 0));
-  if (n)
-    GLC_HIP(ctx, hipMemcpyAsync(chunk, static_cast<const float *>(ctx->stream_out.p) + static_cast<size_t>(buf) * bufcap,
-                                n * sizeof(float), hipMemcpyDeviceToHost, ctx->copy_stream));
-  GLC_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
-  ctx->stream_buf = buf ^ 1;
-  if (last) ctx->stream_open = false;
-  return GLC_OK;
+  return decode_stream_next(ctx, chunk, cap, n_out, is_last);
+}
+
+int glc_decode_stream_next_i16(glc_ctx *ctx, int16_t *chunk, uint64_t cap, uint64_t *n_out, int *is_last) {
+  return decode_stream_next(ctx, chunk, cap, n_out, is_last);
 }
 
 }  // extern "C"

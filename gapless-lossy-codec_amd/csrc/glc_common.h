@@ -132,6 +132,27 @@ int frames_from_compact(uint32_t sample_rate, uint64_t n_samples, uint16_t chann
 
 namespace glc {
 uint64_t next_frames_uid();  // never 0
+
+// Audio files as the integers they hold (glc_audio_load_pcm): the one parser per format, which the
+// float loaders widen.  *samples is malloc'd.  A FLAC stream of at most 16 bits whose decoded values
+// leave the 16-bit range (only a malformed one does) keeps them in GLC_PCM_S32.
+int wav_load_pcm(const char *path, void **samples, glc_pcm_format *fmt, uint32_t *bits, uint64_t *n_samples,
+                 uint32_t *sample_rate, uint16_t *channels);
+int flac_decode_pcm(const uint8_t *buf, uint64_t len, void **samples, glc_pcm_format *fmt, uint32_t *bits,
+                    uint64_t *n_samples, uint32_t *sample_rate, uint16_t *channels);
+int flac_load_pcm(const char *path, void **samples, glc_pcm_format *fmt, uint32_t *bits, uint64_t *n_samples,
+                  uint32_t *sample_rate, uint16_t *channels);
+// `s as f32 / (1 << (bits - 1)) as f32` over what the calls above return (src/audio.rs:58, :79): takes
+// `pcm` over (frees it, or hands a GLC_PCM_F32 buffer through).  nullptr: out of memory.
+float *widen_take(void *pcm, glc_pcm_format fmt, uint32_t bits, uint64_t n);
+// convert_f32_to_i16, src/audio.rs:11-16 = src/flac.rs:955-958
+inline int16_t narrow_i16(float s) {
+  float v = s * 32767.0f;
+  if (v != v) return 0;  // NaN passes through clamp and casts to 0
+  if (v < -32768.0f) v = -32768.0f;
+  if (v > 32767.0f) v = 32767.0f;
+  return static_cast<int16_t>(v);
+}
 }
 
 // EncodedAudio (src/codec.rs:31-69) in a flat, general form: every Vec of the schema keeps its

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "glc_common.h"
@@ -329,17 +330,13 @@ void put_frame(BitOut &w, const int16_t *pcm, size_t block, unsigned ch, uint32_
   w.put(crc16(w.bytes.data() + start, w.len - start), 16);
 }
 
-int16_t to_i16(float s) {  // (s * 32767.0).clamp(-32768.0, 32767.0) as i16, flac.rs:955-958
-  float v = s * 32767.0f;
-  if (v != v) return 0;  // NaN passes through clamp and casts to 0
-  if (v < -32768.0f) v = -32768.0f;
-  if (v > 32767.0f) v = 32767.0f;
-  return static_cast<int16_t>(v);
-}
-
 // -> the stream as consecutive pieces (STREAMINFO, then one run of frames per worker)
-int flac_encode(const float *samples, uint64_t n, uint32_t sample_rate, uint16_t channels, unsigned level,
+// `samples`: float (narrowed here by convert_f32_to_i16, flac.rs:955-958, fanned out like the frames) or
+// 16-bit already
+template <typename T>
+int flac_encode(const T *samples, uint64_t n, uint32_t sample_rate, uint16_t channels, unsigned level,
                 std::vector<BitOut> &parts) {
+  constexpr bool kNarrow = std::is_same<T, float>::value;
   if (channels == 0) {
     glc::set_global_error("glc_flac_encode: channels == 0 (the reference divides by zero here)");
     return GLC_EINVAL;
@@ -355,14 +352,18 @@ int flac_encode(const float *samples, uint64_t n, uint32_t sample_rate, uint16_t
   }
   const size_t block = static_cast<size_t>(std::max<uint64_t>(std::min<uint64_t>(level <= 2 ? 1152 : 4096, total), 16));
   const uint64_t n_frames = (total + block - 1) / block;
-  std::vector<int16_t> pcm(n);
+  std::vector<int16_t> narrowed(kNarrow ? n : 0);
+  const int16_t *pcm;
+  if constexpr (kNarrow) pcm = narrowed.data();
+  else pcm = samples;
 
   unsigned hw = std::thread::hardware_concurrency();
   const unsigned n_thr = static_cast<unsigned>(std::max<uint64_t>(1, std::min<uint64_t>({hw ? hw : 1u, 32u, n_frames / 8 + 1})));
   // f32 -> i16 over all n samples (a trailing partial sample-frame is hashed but not framed,
   // flac.rs:960, :1021-1030), fanned out like the frames below
   auto convert = [&](uint64_t a, uint64_t b) {
-    for (uint64_t i = a; i < b; ++i) pcm[i] = to_i16(samples[i]);
+    if constexpr (kNarrow)
+      for (uint64_t i = a; i < b; ++i) narrowed[i] = glc::narrow_i16(samples[i]);
   };
   parts.assign(n_thr, BitOut());
   auto frames = [&](unsigned t) {
@@ -373,11 +374,11 @@ int flac_encode(const float *samples, uint64_t n, uint32_t sample_rate, uint16_t
     for (uint64_t f = f0; f < f1; ++f) {
       const uint64_t first = f * block;
       const size_t cur = static_cast<size_t>(std::min<uint64_t>(block, total - first));
-      put_frame(w, pcm.data() + first * channels, cur, channels, sample_rate, static_cast<uint32_t>(f), level, plane, res);
+      put_frame(w, pcm + first * channels, cur, channels, sample_rate, static_cast<uint32_t>(f), level, plane, res);
     }
     w.align();
   };
-  {
+  if (kNarrow) {
     std::vector<std::thread> pool;
     for (unsigned t = 1; t < n_thr; ++t) pool.emplace_back(convert, n * t / n_thr, n * (t + 1) / n_thr);
     convert(0, n / n_thr);
@@ -388,7 +389,7 @@ int flac_encode(const float *samples, uint64_t n, uint32_t sample_rate, uint16_t
     std::vector<std::thread> pool;
     for (unsigned t = 0; t < n_thr; ++t) pool.emplace_back(frames, t);
     Md5 h;  // serial by nature; runs on the calling thread beside the frame workers
-    h.update(reinterpret_cast<const uint8_t *>(pcm.data()), static_cast<size_t>(n) * 2);
+    h.update(reinterpret_cast<const uint8_t *>(pcm), static_cast<size_t>(n) * 2);
     h.finish(md5);
     for (auto &th : pool) th.join();
   }
@@ -560,7 +561,8 @@ struct Span {
   uint8_t operator[](size_t i) const { return p[i]; }
 };
 
-int flac_decode(const Span f, std::vector<float> &out, uint32_t &sample_rate, uint16_t &channels) {
+// -> the samples as the integers the stream holds (`as i32` of the decoded value, audio.rs:79)
+int flac_decode(const Span f, std::vector<int32_t> &out, unsigned &bits, uint32_t &sample_rate, uint16_t &channels) {
   auto fail = [](const std::string &m) {
     glc::set_global_error("glc_flac_load: " + m);
     return GLC_EFORMAT;
@@ -594,10 +596,7 @@ int flac_decode(const Span f, std::vector<float> &out, uint32_t &sample_rate, ui
   if (info_bps < 4) return fail("unsupported sample size");
   sample_rate = info_rate;
   channels = static_cast<uint16_t>(info_ch);
-  // `(1 << (bits_per_sample - 1)) as f32`, audio.rs:72
-  // `(1 << (info.bits_per_sample - 1)) as f32`, audio.rs:72, on an i32 literal: 32-bit streams divide by
-  // i32::MIN = -2147483648.0 (polarity inverted, quirk Q11, kept)
-  const float scale = info_bps == 32 ? -2147483648.0f : static_cast<float>(1ull << (info_bps - 1));
+  bits = info_bps;
   out.clear();
   // STREAMINFO's sample count is a hint from the file, not a promise: reserve no more than the
   // remaining bytes could plausibly hold (the vector still grows if constant frames beat that)
@@ -665,7 +664,7 @@ int flac_decode(const Span f, std::vector<float> &out, uint32_t &sample_rate, ui
     out.resize(base + block * nch);
     for (size_t i = 0; i < block; ++i)
       for (unsigned c = 0; c < nch; ++c)
-        out[base + i * nch + c] = static_cast<float>(static_cast<int32_t>(plane[c * block + i])) / scale;  // audio.rs:79
+        out[base + i * nch + c] = static_cast<int32_t>(plane[c * block + i]);
     pos += r.pos >> 3;
   }
   return GLC_OK;
@@ -683,10 +682,10 @@ bool read_file(const char *path, std::vector<uint8_t> &buf) {
 
 }  // namespace
 
-extern "C" {
-
-int glc_flac_encode(const float *samples, uint64_t n_samples, uint32_t sample_rate, uint16_t channels,
-                    uint8_t level, uint8_t **out, uint64_t *out_len) {
+namespace {
+template <typename T>
+int flac_encode_buf(const T *samples, uint64_t n_samples, uint32_t sample_rate, uint16_t channels, uint8_t level,
+                    uint8_t **out, uint64_t *out_len) {
   if ((!samples && n_samples) || !out || !out_len) return GLC_EINVAL;
   try {  // no C++ exception may cross the C ABI
     std::vector<BitOut> parts;
@@ -709,8 +708,9 @@ int glc_flac_encode(const float *samples, uint64_t n_samples, uint32_t sample_ra
   }
 }
 
-int glc_flac_save(const char *path, const float *samples, uint64_t n_samples, uint32_t sample_rate,
-                  uint16_t channels, uint8_t level) {
+template <typename T>
+int flac_save(const char *path, const T *samples, uint64_t n_samples, uint32_t sample_rate, uint16_t channels,
+              uint8_t level) {
   if (!path || (!samples && n_samples)) return GLC_EINVAL;
   try {
     std::vector<BitOut> parts;
@@ -732,19 +732,30 @@ int glc_flac_save(const char *path, const float *samples, uint64_t n_samples, ui
     return GLC_EINVAL;
   }
 }
+}  // namespace
 
-int glc_flac_decode(const uint8_t *buf, uint64_t len, float **samples, uint64_t *n_samples, uint32_t *sample_rate,
-                    uint16_t *channels) {
-  if (!buf || !samples || !n_samples || !sample_rate || !channels) return GLC_EINVAL;
+namespace glc {
+
+int flac_decode_pcm(const uint8_t *buf, uint64_t len, void **samples, glc_pcm_format *fmt, uint32_t *bits,
+                    uint64_t *n_samples, uint32_t *sample_rate, uint16_t *channels) {
   try {
-    std::vector<float> pcm;
-    const int rc = flac_decode(Span{buf, static_cast<size_t>(len)}, pcm, *sample_rate, *channels);
+    std::vector<int32_t> pcm;
+    unsigned bps = 0;
+    const int rc = flac_decode(Span{buf, static_cast<size_t>(len)}, pcm, bps, *sample_rate, *channels);
     if (rc != GLC_OK) return rc;
-    float *o = static_cast<float *>(std::malloc((pcm.size() ? pcm.size() : 1) * sizeof(float)));
+    const size_t n = pcm.size();
+    bool fits = bps <= 16;  // a well-formed stream of <= 16 bits holds nothing wider; a malformed one keeps its values
+    for (size_t i = 0; fits && i < n; ++i) fits = pcm[i] == static_cast<int16_t>(pcm[i]);
+    void *o = std::malloc((n ? n : 1) * (fits ? 2 : 4));
     if (!o) return GLC_ENOMEM;
-    if (!pcm.empty()) std::memcpy(o, pcm.data(), pcm.size() * sizeof(float));
+    if (fits)
+      for (size_t i = 0; i < n; ++i) static_cast<int16_t *>(o)[i] = static_cast<int16_t>(pcm[i]);
+    else if (n)
+      std::memcpy(o, pcm.data(), n * 4);
     *samples = o;
-    *n_samples = pcm.size();
+    *fmt = fits ? GLC_PCM_S16 : GLC_PCM_S32;
+    *bits = bps;
+    *n_samples = n;
     return GLC_OK;
   } catch (const std::bad_alloc &) {
     return GLC_ENOMEM;
@@ -754,8 +765,8 @@ int glc_flac_decode(const uint8_t *buf, uint64_t len, float **samples, uint64_t 
   }
 }
 
-int glc_flac_load(const char *path, float **samples, uint64_t *n_samples, uint32_t *sample_rate, uint16_t *channels) {
-  if (!path) return GLC_EINVAL;
+int flac_load_pcm(const char *path, void **samples, glc_pcm_format *fmt, uint32_t *bits, uint64_t *n_samples,
+                  uint32_t *sample_rate, uint16_t *channels) {
   std::vector<uint8_t> f;
   bool opened = false;
   try {
@@ -767,7 +778,52 @@ int glc_flac_load(const char *path, float **samples, uint64_t *n_samples, uint32
     glc::set_global_error(std::string("glc_flac_load: cannot open ") + path);
     return GLC_EIO;
   }
-  return glc_flac_decode(f.data(), f.size(), samples, n_samples, sample_rate, channels);
+  return flac_decode_pcm(f.data(), f.size(), samples, fmt, bits, n_samples, sample_rate, channels);
+}
+
+}  // namespace glc
+
+extern "C" {
+
+int glc_flac_encode(const float *samples, uint64_t n_samples, uint32_t sample_rate, uint16_t channels,
+                    uint8_t level, uint8_t **out, uint64_t *out_len) {
+  return flac_encode_buf(samples, n_samples, sample_rate, channels, level, out, out_len);
+}
+int glc_flac_encode_i16(const int16_t *samples, uint64_t n_samples, uint32_t sample_rate, uint16_t channels,
+                        uint8_t level, uint8_t **out, uint64_t *out_len) {
+  return flac_encode_buf(samples, n_samples, sample_rate, channels, level, out, out_len);
+}
+
+int glc_flac_save(const char *path, const float *samples, uint64_t n_samples, uint32_t sample_rate,
+                  uint16_t channels, uint8_t level) {
+  return flac_save(path, samples, n_samples, sample_rate, channels, level);
+}
+int glc_flac_save_i16(const char *path, const int16_t *samples, uint64_t n_samples, uint32_t sample_rate,
+                      uint16_t channels, uint8_t level) {
+  return flac_save(path, samples, n_samples, sample_rate, channels, level);
+}
+
+int glc_flac_decode(const uint8_t *buf, uint64_t len, float **samples, uint64_t *n_samples, uint32_t *sample_rate,
+                    uint16_t *channels) {
+  if (!buf || !samples || !n_samples || !sample_rate || !channels) return GLC_EINVAL;
+  void *pcm = nullptr;
+  glc_pcm_format fmt;
+  uint32_t bits = 0;
+  const int rc = glc::flac_decode_pcm(buf, len, &pcm, &fmt, &bits, n_samples, sample_rate, channels);
+  if (rc != GLC_OK) return rc;
+  *samples = glc::widen_take(pcm, fmt, bits, *n_samples);
+  return *samples ? GLC_OK : GLC_ENOMEM;
+}
+
+int glc_flac_load(const char *path, float **samples, uint64_t *n_samples, uint32_t *sample_rate, uint16_t *channels) {
+  if (!path || !samples || !n_samples || !sample_rate || !channels) return GLC_EINVAL;
+  void *pcm = nullptr;
+  glc_pcm_format fmt;
+  uint32_t bits = 0;
+  const int rc = glc::flac_load_pcm(path, &pcm, &fmt, &bits, n_samples, sample_rate, channels);
+  if (rc != GLC_OK) return rc;
+  *samples = glc::widen_take(pcm, fmt, bits, *n_samples);
+  return *samples ? GLC_OK : GLC_ENOMEM;
 }
 
 }  // extern "C"

@@ -81,6 +81,16 @@ hipError_t launch_overlap_add(const float *blocks, int64_t blk_frame0, uint64_t 
                               uint32_t ch, uint64_t hop_begin, uint64_t hop_end, float *out,
                               hipStream_t s);
 
+// D2 with the narrowing of the reference's 16-bit writers on the way out: the same sums, then
+// `(v * 32767.0).clamp(-32768.0, 32767.0) as i16` (NaN -> 0, truncation) - `out` is any 2-byte aligned pointer.
+hipError_t launch_overlap_add_i16(const float *blocks, int64_t blk_frame0, uint64_t n_frames,
+                                  uint32_t ch, uint64_t hop_begin, uint64_t hop_end, int16_t *out,
+                                  hipStream_t s);
+// W1: interleaved integer PCM -> f32 as the reference's loaders widen it: out[i] = (float)in[i] / max,
+// max = 2^(bits-1), -2^31 for bits == 32.  `wide`: int32_t samples (bits 1..32), else int16_t
+// (bits 1..16); `in` aligned to its sample size, `out` to 4 bytes.
+hipError_t launch_pcm_widen(const void *in, bool wide, uint32_t bits, uint64_t n, float *out, hipStream_t s);
+
 // Measurement only (include/glc_debug.h): one sleeping wave that reports {shader cycles, 100 MHz ticks}
 // over a window of `ticks_100mhz` reference ticks, beside whatever runs on the device meanwhile.
 hipError_t launch_clock_probe(uint64_t ticks_100mhz, uint64_t *out, hipStream_t s);

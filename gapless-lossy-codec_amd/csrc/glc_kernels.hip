@@ -828,6 +828,81 @@ __global__ __launch_bounds__(256) void k_overlap_add(const float *__restrict__ b
   }
 }
 
+// D2 writing 16-bit PCM: the same sums, then convert_f32_to_i16 of the reference's writers
+// (`(s * 32767.0).clamp(-32768.0, 32767.0) as i16`, src/audio.rs:11-16) on the way out, so that the
+// host boundary of a decode moves 2 bytes per sample.  Four samples per thread as in k_overlap_add,
+// stored as one 8-byte word (VEC) or four 2-byte ones (a destination that is only 2-byte aligned).
+template <int CH, bool VEC>
+__global__ __launch_bounds__(256) void k_overlap_add_i16(const float *__restrict__ blocks, long long blk_frame0,
+                                                          unsigned long long n_frames, unsigned ch,
+                                                          unsigned long long hop_begin, short *__restrict__ out) {
+  const unsigned per_hop = static_cast<unsigned>(kHopI) * ch;
+  const unsigned o0 = (blockIdx.x * 256u + threadIdx.x) * 4u;  // first of this thread's 4 outputs inside the hop
+  if (o0 >= per_hop) return;
+  const unsigned long long h = hop_begin + blockIdx.y;
+  const bool has_prev = h >= 1, has_cur = h < n_frames;
+  const float *prev = blocks + (static_cast<size_t>(static_cast<long long>(h) - 1 - blk_frame0) * ch) * kFrameI + kHopI;
+  const float *cur = blocks + (static_cast<size_t>(static_cast<long long>(h) - blk_frame0) * ch) * kFrameI;
+  short q[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const unsigned o = o0 + e;
+    unsigned i, c;
+    if constexpr (CH == 1) i = o, c = 0;
+    else if constexpr (CH == 2) i = o >> 1, c = o & 1u;
+    else if constexpr (CH == 4) i = o >> 2, c = o & 3u;
+    else if constexpr (CH == 8) i = o >> 3, c = o & 7u;
+    else i = o / ch, c = o - i * ch;
+    const size_t at = static_cast<size_t>(c) * kFrameI + i;
+    const float p = has_prev ? prev[at] : 0.0f;              // overlap starts as +0.0, :601
+    const float v = has_cur ? add_rn(p, cur[at]) : p;        // :695 / the bare tail, :727
+    q[e] = sat_i16(mul_rn(v, 32767.0f));                     // src/audio.rs:13-14
+  }
+  short *dst = out + static_cast<size_t>(blockIdx.y) * per_hop + o0;
+  if constexpr (VEC) {
+    *reinterpret_cast<short4 *>(dst) = short4{q[0], q[1], q[2], q[3]};
+  } else {
+    dst[0] = q[0], dst[1] = q[1], dst[2] = q[2], dst[3] = q[3];
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// W1: integer PCM -> f32, what the reference's loaders do on the host (`s as f32 / (1 << (bits-1))
+// as f32`, src/audio.rs:58, :79).  `(float)s` rounds to nearest even beyond 24 bits like `as f32`;
+// the divisor is +-2^k, so the quotient is the product with `inv` = 1/divisor, which is exact too
+// (no result is subnormal: |s| >= 1 gives at least 2^-31) - same bits, no division.
+// Memory-bound: 6 (i16) or 8 (i32) bytes per sample.  The body starts where the DESTINATION is
+// 16-byte aligned: a float4 store per thread from four samples, loaded as one 8- / 16-byte word
+// when the source is aligned there too (VEC), else one by one.  The at most 3 + 3 samples in front
+// of and behind the body are converted by the threads after the body's.
+// ------------------------------------------------------------------------------------------
+template <typename S, bool VEC>
+__global__ __launch_bounds__(256) void k_pcm_widen(const S *__restrict__ in, float *__restrict__ out,
+                                                    unsigned long long n, unsigned head, float inv) {
+  const unsigned long long g = static_cast<unsigned long long>(blockIdx.x) * 256u + threadIdx.x;
+  const unsigned long long n4 = (n - head) / 4u;  // float4s of the body (head <= n)
+  if (g < n4) {
+    const unsigned long long at = head + g * 4u;
+    float4 v;
+    if constexpr (VEC && sizeof(S) == 2) {
+      const short4 s = *reinterpret_cast<const short4 *>(in + at);
+      v = float4{static_cast<float>(s.x), static_cast<float>(s.y), static_cast<float>(s.z), static_cast<float>(s.w)};
+    } else if constexpr (VEC) {
+      const int4 s = *reinterpret_cast<const int4 *>(in + at);
+      v = float4{static_cast<float>(s.x), static_cast<float>(s.y), static_cast<float>(s.z), static_cast<float>(s.w)};
+    } else {
+      v = float4{static_cast<float>(in[at]), static_cast<float>(in[at + 1]), static_cast<float>(in[at + 2]),
+                 static_cast<float>(in[at + 3])};
+    }
+    v.x = mul_rn(v.x, inv), v.y = mul_rn(v.y, inv), v.z = mul_rn(v.z, inv), v.w = mul_rn(v.w, inv);
+    *reinterpret_cast<float4 *>(out + at) = v;
+    return;
+  }
+  const unsigned long long e = g - n4;  // 0 .. head-1: the head; then the tail behind the body
+  const unsigned long long at = e < head ? e : 4u * n4 + e;
+  if (at < n) out[at] = mul_rn(static_cast<float>(in[at]), inv);
+}
+
 // ------------------------------------------------------------------------------------------
 // P1-P3: device-side compaction of frame records into the compact blob (glc_common.h
 // CompactLayout), so that the host boundary and the multi-GPU gather move (u16 idx, i16 q) pairs
@@ -1198,6 +1273,62 @@ hipError_t launch_overlap_add(const float *blocks, int64_t blk_frame0, uint64_t 
     }
   }
   return hipGetLastError();
+}
+
+hipError_t launch_overlap_add_i16(const float *blocks, int64_t blk_frame0, uint64_t n_frames, uint32_t ch,
+                                  uint64_t hop_begin, uint64_t hop_end, int16_t *out, hipStream_t s) {
+  if (hop_end <= hop_begin) return hipSuccess;
+  const unsigned per_hop = 1024u * ch;
+  const unsigned bx = (per_hop / 4u + 255u) / 256u;
+  for (uint64_t h0 = hop_begin; h0 < hop_end; h0 += 32768) {  // slabs: blockIdx.y is 16 bits wide
+    const unsigned nh = static_cast<unsigned>(hop_end - h0 < 32768 ? hop_end - h0 : 32768);
+    const dim3 grid(bx, nh);
+    short *o = out + (h0 - hop_begin) * per_hop;
+    const long long f0 = static_cast<long long>(blk_frame0);
+    const unsigned long long nf = n_frames, hb = h0;
+    if (reinterpret_cast<uintptr_t>(o) & 7u) {
+      hipLaunchKernelGGL((k_overlap_add_i16<0, false>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o);
+      continue;
+    }
+    switch (ch) {
+      case 1: hipLaunchKernelGGL((k_overlap_add_i16<1, true>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o); break;
+      case 2: hipLaunchKernelGGL((k_overlap_add_i16<2, true>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o); break;
+      case 4: hipLaunchKernelGGL((k_overlap_add_i16<4, true>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o); break;
+      case 8: hipLaunchKernelGGL((k_overlap_add_i16<8, true>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o); break;
+      default: hipLaunchKernelGGL((k_overlap_add_i16<0, true>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o); break;
+    }
+  }
+  return hipGetLastError();
+}
+
+namespace {
+template <typename S>
+hipError_t widen_typed(const S *in, uint64_t n, float inv, float *out, hipStream_t s) {
+  // body from the first 16-byte aligned destination element; the source is vector-loaded if it is
+  // aligned to four of its samples there
+  const unsigned long long head = std::min<uint64_t>(n, (16u - (reinterpret_cast<uintptr_t>(out) & 15u)) / 4u % 4u);
+  const bool vec = (reinterpret_cast<uintptr_t>(in + head) & (4u * sizeof(S) - 1u)) == 0;
+  const uint64_t threads = (n - head) / 4u + head + (n - head) % 4u;  // n <= 2^30 (launch_pcm_widen)
+  const dim3 grid(static_cast<unsigned>((threads + 255u) / 256u));
+  if (vec) hipLaunchKernelGGL((k_pcm_widen<S, true>), grid, dim3(256), 0, s, in, out, n, static_cast<unsigned>(head), inv);
+  else hipLaunchKernelGGL((k_pcm_widen<S, false>), grid, dim3(256), 0, s, in, out, n, static_cast<unsigned>(head), inv);
+  return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_pcm_widen(const void *in, bool wide, uint32_t bits, uint64_t n, float *out, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  // `(1 << (bits - 1)) as f32` on an i32 literal: 32 bits shift into the sign (quirk Q11, glc_wav.cpp)
+  const float max = bits == 32 ? -2147483648.0f : static_cast<float>(1u << (bits - 1));
+  const float inv = 1.0f / max;  // a power of two: exact
+  constexpr uint64_t kPiece = uint64_t{1} << 30;  // samples per launch: the grid stays far below its limit
+  for (uint64_t at = 0; at < n; at += kPiece) {
+    const uint64_t m = std::min(kPiece, n - at);
+    const hipError_t e = wide ? widen_typed(static_cast<const int32_t *>(in) + at, m, inv, out + at, s)
+                              : widen_typed(static_cast<const int16_t *>(in) + at, m, inv, out + at, s);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 }  // namespace glc

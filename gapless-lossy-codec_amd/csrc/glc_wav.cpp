@@ -1,5 +1,6 @@
 // glc_wav.cpp — WAV reader / 16-bit WAV writer: the file-I/O twin of the reference's
 // src/audio.rs (load_wav :39-64 via hound, export_to_wav :100-132).  Host only.
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -24,13 +25,10 @@ uint16_t le16(const uint8_t *p) { return static_cast<uint16_t>(p[0] | (p[1] << 8
 
 }  // namespace
 
-extern "C" {
+namespace glc {
 
-void glc_free(void *p) { std::free(p); }
-
-int glc_wav_load(const char *path, float **samples, uint64_t *n_samples, uint32_t *sample_rate,
-                 uint16_t *channels) {
-  if (!path || !samples || !n_samples || !sample_rate || !channels) return GLC_EINVAL;
+int wav_load_pcm(const char *path, void **samples, glc_pcm_format *fmt_out, uint32_t *bits_out, uint64_t *n_samples,
+                 uint32_t *sample_rate, uint16_t *channels) {
   std::vector<uint8_t> f;
   bool opened = false;
   try {  // no C++ exception may cross the C ABI
@@ -77,34 +75,96 @@ int glc_wav_load(const char *path, float **samples, uint64_t *n_samples, uint32_
   }
   const uint32_t bps = bits / 8;
   const uint64_t n = data_len / bps;
-  float *out = static_cast<float *>(std::malloc((n ? n : 1) * sizeof(float)));
+  const glc_pcm_format pf = is_float ? GLC_PCM_F32 : bits <= 16 ? GLC_PCM_S16 : GLC_PCM_S32;
+  void *out = std::malloc((n ? n : 1) * (pf == GLC_PCM_S16 ? 2 : 4));
   if (!out) return GLC_ENOMEM;
-  // `(1 << (bits - 1)) as f32`, audio.rs:55: the literal is an i32, so for 32-bit samples the shift
-  // lands on the sign bit and the divisor is i32::MIN = -2147483648.0 - the reference inverts the
-  // polarity of 32-bit integer WAV files (quirk Q11, kept)
-  const float max = bits == 32 ? -2147483648.0f : static_cast<float>(1u << (bits - 1));
-  for (uint64_t i = 0; i < n; ++i) {
-    const uint8_t *p = data + i * bps;
-    if (is_float) {
-      std::memcpy(&out[i], p, 4);
-    } else {
-      int32_t s;
-      if (bits == 8) s = static_cast<int32_t>(p[0]) - 128;  // WAV 8-bit is unsigned
-      else if (bits == 16) s = static_cast<int16_t>(le16(p));
-      else if (bits == 24) s = (static_cast<int32_t>((p[0] | (p[1] << 8) | (static_cast<uint32_t>(p[2]) << 16)) << 8)) >> 8;
-      else s = static_cast<int32_t>(le32(p));
-      out[i] = static_cast<float>(s) / max;  // `s? as f32 / max`, audio.rs:58
+  if (is_float) {
+    std::memcpy(out, data, n * 4);
+  } else if (pf == GLC_PCM_S16) {
+    int16_t *o = static_cast<int16_t *>(out);
+    for (uint64_t i = 0; i < n; ++i)
+      o[i] = bits == 8 ? static_cast<int16_t>(static_cast<int32_t>(data[i]) - 128)  // WAV 8-bit is unsigned
+                       : static_cast<int16_t>(le16(data + 2 * i));
+  } else {
+    int32_t *o = static_cast<int32_t *>(out);
+    for (uint64_t i = 0; i < n; ++i) {
+      const uint8_t *p = data + i * bps;
+      o[i] = bits == 24 ? (static_cast<int32_t>((p[0] | (p[1] << 8) | (static_cast<uint32_t>(p[2]) << 16)) << 8)) >> 8
+                        : static_cast<int32_t>(le32(p));
     }
   }
   *samples = out;
+  *fmt_out = pf;
+  *bits_out = bits;
   *n_samples = n;
   *sample_rate = sr;
   *channels = ch;
   return GLC_OK;
 }
 
-int glc_wav_save16(const char *path, const float *samples, uint64_t n_samples, uint32_t sample_rate,
-                   uint16_t channels) {
+float *widen_take(void *pcm, glc_pcm_format fmt, uint32_t bits, uint64_t n) {
+  if (fmt == GLC_PCM_F32) return static_cast<float *>(pcm);
+  float *out = static_cast<float *>(std::malloc((n ? n : 1) * sizeof(float)));
+  if (out) {
+    // `(1 << (bits - 1)) as f32`, audio.rs:55: the literal is an i32, so for 32-bit samples the shift
+    // lands on the sign bit and the divisor is i32::MIN = -2147483648.0 - the reference inverts the
+    // polarity of 32-bit integer WAV files (quirk Q11, kept)
+    const float max = bits == 32 ? -2147483648.0f : static_cast<float>(1u << (bits - 1));
+    // `s? as f32 / max`, audio.rs:58
+    if (fmt == GLC_PCM_S16)
+      for (uint64_t i = 0; i < n; ++i) out[i] = static_cast<float>(static_cast<const int16_t *>(pcm)[i]) / max;
+    else
+      for (uint64_t i = 0; i < n; ++i) out[i] = static_cast<float>(static_cast<const int32_t *>(pcm)[i]) / max;
+  }
+  std::free(pcm);
+  return out;
+}
+
+}  // namespace glc
+
+extern "C" {
+
+void glc_free(void *p) { std::free(p); }
+
+int glc_wav_load(const char *path, float **samples, uint64_t *n_samples, uint32_t *sample_rate,
+                 uint16_t *channels) {
+  if (!path || !samples || !n_samples || !sample_rate || !channels) return GLC_EINVAL;
+  void *pcm = nullptr;
+  glc_pcm_format fmt;
+  uint32_t bits = 0;
+  const int rc = glc::wav_load_pcm(path, &pcm, &fmt, &bits, n_samples, sample_rate, channels);
+  if (rc != GLC_OK) return rc;
+  *samples = glc::widen_take(pcm, fmt, bits, *n_samples);
+  return *samples ? GLC_OK : GLC_ENOMEM;
+}
+
+int glc_audio_load_pcm(const char *path, void **samples, glc_pcm_format *fmt, uint32_t *bits, uint64_t *n_samples,
+                       uint32_t *sample_rate, uint16_t *channels) {
+  if (!path || !samples || !fmt || !bits || !n_samples || !sample_rate || !channels) return GLC_EINVAL;
+  // load_audio_file_lossless, src/audio.rs:19-36: by lower-cased extension
+  const char *slash = std::strrchr(path, '/'), *dot = std::strrchr(path, '.');
+  if (!dot || (slash && dot < slash)) {
+    glc::set_global_error("No file extension");
+    return GLC_EINVAL;
+  }
+  std::string ext;
+  try {
+    ext = dot + 1;
+  } catch (const std::bad_alloc &) {
+    return GLC_ENOMEM;
+  }
+  for (char &c : ext) c = static_cast<char>(std::tolower(static_cast<unsigned char>(c)));
+  if (ext == "wav") return glc::wav_load_pcm(path, samples, fmt, bits, n_samples, sample_rate, channels);
+  if (ext == "flac") return glc::flac_load_pcm(path, samples, fmt, bits, n_samples, sample_rate, channels);
+  try {
+    glc::set_global_error("Unsupported file format: " + ext);
+  } catch (const std::bad_alloc &) {
+  }
+  return GLC_EINVAL;
+}
+
+int glc_wav_save16_i16(const char *path, const int16_t *samples, uint64_t n_samples, uint32_t sample_rate,
+                       uint16_t channels) {
   if (!path || (!samples && n_samples) || channels == 0) return GLC_EINVAL;
   const uint64_t data_bytes = n_samples * 2;
   if (data_bytes > 0xFFFFFFFFull - 36) {
@@ -131,17 +191,7 @@ int glc_wav_save16(const char *path, const float *samples, uint64_t n_samples, u
   put16(34, 16);
   std::memcpy(&buf[36], "data", 4);
   put32(40, static_cast<uint32_t>(data_bytes));
-  for (uint64_t i = 0; i < n_samples; ++i) {
-    float v = samples[i] * 32767.0f;  // convert_f32_to_i16, audio.rs:11-16
-    int16_t q;
-    if (v != v) q = 0;
-    else {
-      if (v < -32768.0f) v = -32768.0f;
-      if (v > 32767.0f) v = 32767.0f;
-      q = static_cast<int16_t>(v);
-    }
-    put16(44 + 2 * i, static_cast<uint16_t>(q));
-  }
+  for (uint64_t i = 0; i < n_samples; ++i) put16(44 + 2 * i, static_cast<uint16_t>(samples[i]));
   FILE *fp = std::fopen(path, "wb");
   if (!fp) {
     glc::set_global_error(std::string("glc_wav_save16: cannot open ") + path);
@@ -153,6 +203,23 @@ int glc_wav_save16(const char *path, const float *samples, uint64_t n_samples, u
     return GLC_EIO;
   }
   return GLC_OK;
+}
+
+int glc_wav_save16(const char *path, const float *samples, uint64_t n_samples, uint32_t sample_rate,
+                   uint16_t channels) {
+  if (!path || (!samples && n_samples) || channels == 0) return GLC_EINVAL;
+  if (n_samples * 2 > 0xFFFFFFFFull - 36) {
+    glc::set_global_error("glc_wav_save16: stream too long for a RIFF file");
+    return GLC_EINVAL;
+  }
+  std::vector<int16_t> q;
+  try {
+    q.resize(n_samples);
+  } catch (const std::bad_alloc &) {
+    return GLC_ENOMEM;
+  }
+  for (uint64_t i = 0; i < n_samples; ++i) q[i] = glc::narrow_i16(samples[i]);  // convert_f32_to_i16, audio.rs:11-16
+  return glc_wav_save16_i16(path, q.data(), n_samples, sample_rate, channels);
 }
 
 }  // extern "C"

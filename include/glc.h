@@ -370,6 +370,52 @@ int glc_flac_load(const char *path, float **samples, uint64_t *n_samples, uint32
 int glc_flac_decode(const uint8_t *buf, uint64_t len, float **samples, uint64_t *n_samples,
                     uint32_t *sample_rate, uint16_t *channels);
 
+/* ---- integer PCM at the host boundary -------------------------------------------------------- */
+
+/* The reference's program only ever feeds its encoder samples widened from an integer file
+ * (load_wav / load_flac: `s as f32 / (1 << (bits-1)) as f32`, src/audio.rs:52-60, :72-81) and narrows
+ * what its decoder returns to 16 bits straight away (convert_f32_to_i16, src/audio.rs:11-16,
+ * src/flac.rs:955-958).  The entry points below do both conversions on the device, bit for bit, so
+ * that 2 bytes per sample cross PCIe instead of 4 and the host never walks the audio. */
+typedef enum glc_pcm_format {
+  GLC_PCM_S16 = 1, /* int16_t samples, bits 1..16 */
+  GLC_PCM_S32 = 2, /* int32_t samples, bits 1..32, the value sign-extended in the container */
+  GLC_PCM_F32 = 3  /* float samples, already widened (`bits` is ignored) */
+} glc_pcm_format;
+
+/* out[i] = (float)in[i] / max, max = 2^(bits-1) - and -2^31 for bits == 32: the reference shifts an
+ * i32 literal into its sign bit and so inverts 32-bit files (quirk Q11, kept).  d_in: n samples in
+ * device memory, aligned to their size; d_out: n floats.  GLC_PCM_F32 is a device-to-device copy.
+ * Queued on glc_ctx_stream(ctx), not synchronised. */
+int glc_pcm_widen_device(glc_ctx *ctx, const void *d_in, glc_pcm_format fmt, uint32_t bits, uint64_t n,
+                         float *d_out);
+/* glc_encode of the samples load_wav / load_flac would have produced from these integers - the same
+ * frames - without the float copy: the integers are uploaded and widened on the device. */
+int glc_encode_int(glc_ctx *ctx, const void *pcm, glc_pcm_format fmt, uint32_t bits, uint64_t n_samples,
+                   uint16_t channels, glc_frames **out);
+/* convert_f32_to_i16(Decoder::decode(..)): what glc_decode returns, narrowed by
+ * `(s * 32767.0).clamp(-32768.0, 32767.0) as i16` (NaN gives 0) on the device. */
+int glc_decode_i16(glc_ctx *ctx, const glc_frames *in, int16_t *pcm_out, uint64_t cap, uint64_t *n_out);
+/* glc_decode_range_device with the same narrowing; d_out is any 2-byte aligned device pointer. */
+int glc_decode_range_device_i16(glc_ctx *ctx, const glc_frames *in, uint64_t hop_begin, uint64_t hop_end,
+                                int16_t *d_out, uint64_t cap);
+/* glc_decode_stream_next with the same narrowing, after the same glc_decode_stream_begin.  A stream
+ * is read through one of the two calls from its first chunk to its last: mixing them is GLC_EINVAL. */
+int glc_decode_stream_next_i16(glc_ctx *ctx, int16_t *chunk, uint64_t cap, uint64_t *n_out, int *is_last);
+
+/* load_audio_file_lossless (src/audio.rs:19-36: .wav or .flac by lower-cased extension) before the
+ * widening: integer sources of at most 16 bits come back as GLC_PCM_S16 (8-bit WAV made signed), wider
+ * ones as GLC_PCM_S32, float WAV as GLC_PCM_F32 (*bits = 32).  *samples is malloc'd (glc_free). */
+int glc_audio_load_pcm(const char *path, void **samples, glc_pcm_format *fmt, uint32_t *bits,
+                       uint64_t *n_samples, uint32_t *sample_rate, uint16_t *channels);
+/* glc_wav_save16 / glc_flac_encode / glc_flac_save of samples that are 16-bit already. */
+int glc_wav_save16_i16(const char *path, const int16_t *samples, uint64_t n_samples, uint32_t sample_rate,
+                       uint16_t channels);
+int glc_flac_encode_i16(const int16_t *samples, uint64_t n_samples, uint32_t sample_rate, uint16_t channels,
+                        uint8_t level, uint8_t **out, uint64_t *out_len);
+int glc_flac_save_i16(const char *path, const int16_t *samples, uint64_t n_samples, uint32_t sample_rate,
+                      uint16_t channels, uint8_t level);
+
 /* ---- tables (for inspection / parity tests) ---------------------------------------------- */
 
 /* Copies of the host tables of a context: MdctTables.cos_table [1024*2048] (row k), window

@@ -206,6 +206,24 @@ class Encoder {
   EncodedAudio encode(const std::vector<float> &samples, uint16_t channels) {
     return encode(samples.data(), samples.size(), channels);
   }
+  // encode of what load_wav / load_flac make of integer samples, s / 2^(bits-1) (src/audio.rs:58, :79),
+  // without the float copy: the integers go up and are widened on the device (glc_encode_int)
+  EncodedAudio encode(const int16_t *samples, uint64_t n_samples, uint16_t channels, uint32_t bits = 16) {
+    glc_frames *h = nullptr;
+    detail::check(glc_encode_int(ctx_, samples, GLC_PCM_S16, bits, n_samples, channels, &h), ctx_);
+    return EncodedAudio(h);
+  }
+  EncodedAudio encode(const int32_t *samples, uint32_t bits, uint64_t n_samples, uint16_t channels) {
+    glc_frames *h = nullptr;
+    detail::check(glc_encode_int(ctx_, samples, GLC_PCM_S32, bits, n_samples, channels, &h), ctx_);
+    return EncodedAudio(h);
+  }
+  EncodedAudio encode(const std::vector<int16_t> &samples, uint16_t channels, uint32_t bits = 16) {
+    return encode(samples.data(), samples.size(), channels, bits);
+  }
+  EncodedAudio encode(const std::vector<int32_t> &samples, uint32_t bits, uint16_t channels) {
+    return encode(samples.data(), bits, samples.size(), channels);
+  }
   // The same call handing the frames out as they arrive on the host, while the device still works on later
   // ones (glc_encode_hooked): `on_frames(first_frame, frames)` is called on this thread with ascending,
   // contiguous ranges - where an application fills its own Vec<EncodedFrame> under the encode instead of after it.
@@ -273,6 +291,14 @@ class Decoder {
     out.resize(n);
     return out;
   }
+  // convert_f32_to_i16(decode(..)) (src/audio.rs:11-16), narrowed on the device: what the 16-bit writers take
+  std::vector<int16_t> decode_i16(const EncodedAudio &encoded) {
+    std::vector<int16_t> out(glc_decoded_len(encoded.handle()));
+    uint64_t n = 0;
+    detail::check(glc_decode_i16(ctx_, encoded.handle(), out.data(), out.size(), &n), ctx_);
+    out.resize(n);
+    return out;
+  }
   // The stream whose sparse rows this Decoder still holds on the device (0: none), and its decode without
   // an EncodedAudio (glc.h glc_decode_resident): for callers that recognise a stream by the id they gave it
   uint64_t resident_stream() const { return glc_ctx_resident_stream(ctx_); }
@@ -302,6 +328,20 @@ class Decoder {
       c.samples.resize(n);
       c.is_last = last != 0;
       on_chunk(std::move(c));
+      if (last) return;
+    }
+  }
+  // decode_streaming with every chunk narrowed to 16 bits on the device: on_chunk(samples, is_last)
+  void decode_streaming_i16(const EncodedAudio &encoded, const std::function<void(std::vector<int16_t> &&, bool)> &on_chunk) {
+    detail::check(glc_decode_stream_begin(ctx_, encoded.handle()), ctx_);
+    const uint64_t cap = static_cast<uint64_t>(FRAMES_PER_CHUNK) * HOP_SIZE * encoded.header().channels;
+    for (;;) {
+      std::vector<int16_t> c(cap);
+      uint64_t n = 0;
+      int last = 0;
+      detail::check(glc_decode_stream_next_i16(ctx_, c.data(), cap, &n, &last), ctx_);
+      c.resize(n);
+      on_chunk(std::move(c), last != 0);
       if (last) return;
     }
   }
@@ -352,11 +392,60 @@ inline LoadedAudio load_audio_file_lossless(const std::string &path) {
   else throw Error(GLC_EINVAL, "Unsupported file format: " + ext);
   return detail::take(p, n, sr, ch);
 }
+// load_audio_file_lossless before the widening (glc_audio_load_pcm): the integers the file holds, in exactly one
+// of the three vectors - what Encoder::encode takes together with `bits`
+struct LoadedPcm {
+  glc_pcm_format format;
+  uint32_t bits;
+  std::vector<int16_t> s16;
+  std::vector<int32_t> s32;
+  std::vector<float> f32;
+  uint32_t sample_rate;
+  uint16_t channels;
+};
+inline LoadedPcm load_audio_file_pcm(const std::string &path) {
+  void *p = nullptr;
+  LoadedPcm a{};
+  uint64_t n = 0;
+  detail::check(glc_audio_load_pcm(path.c_str(), &p, &a.format, &a.bits, &n, &a.sample_rate, &a.channels));
+  try {
+    if (a.format == GLC_PCM_S16) a.s16.assign(static_cast<int16_t *>(p), static_cast<int16_t *>(p) + n);
+    else if (a.format == GLC_PCM_S32) a.s32.assign(static_cast<int32_t *>(p), static_cast<int32_t *>(p) + n);
+    else a.f32.assign(static_cast<float *>(p), static_cast<float *>(p) + n);
+  } catch (...) {
+    glc_free(p);
+    throw;
+  }
+  glc_free(p);
+  return a;
+}
 // export_to_wav — src/audio.rs:100-132
 inline void export_to_wav(const std::string &path, const std::vector<float> &s, uint32_t sample_rate, uint16_t channels) {
   detail::check(glc_wav_save16(path.c_str(), s.data(), s.size(), sample_rate, channels));
 }
-// encode_flac_with_level / encode_flac — src/flac.rs:947-1063
+inline void export_to_wav(const std::string &path, const std::vector<int16_t> &s, uint32_t sample_rate, uint16_t channels) {
+  detail::check(glc_wav_save16_i16(path.c_str(), s.data(), s.size(), sample_rate, channels));
+}
+// encode_flac_with_level / encode_flac — src/flac.rs:947-1063 (int16_t samples: narrowed already)
+inline std::vector<uint8_t> encode_flac_with_level(const std::vector<int16_t> &s, uint32_t sample_rate, uint16_t channels,
+                                                   uint8_t compression_level) {
+  uint8_t *p = nullptr;
+  uint64_t n = 0;
+  detail::check(glc_flac_encode_i16(s.data(), s.size(), sample_rate, channels, compression_level, &p, &n));
+  std::vector<uint8_t> out(p, p + n);
+  glc_free(p);
+  return out;
+}
+inline std::vector<uint8_t> encode_flac(const std::vector<int16_t> &s, uint32_t sample_rate, uint16_t channels) {
+  return encode_flac_with_level(s, sample_rate, channels, 5);
+}
+inline void export_to_flac_with_level(const std::string &path, const std::vector<int16_t> &s, uint32_t sample_rate,
+                                      uint16_t channels, uint8_t compression_level) {
+  detail::check(glc_flac_save_i16(path.c_str(), s.data(), s.size(), sample_rate, channels, compression_level));
+}
+inline void export_to_flac(const std::string &path, const std::vector<int16_t> &s, uint32_t sample_rate, uint16_t channels) {
+  export_to_flac_with_level(path, s, sample_rate, channels, 5);
+}
 inline std::vector<uint8_t> encode_flac_with_level(const std::vector<float> &s, uint32_t sample_rate, uint16_t channels,
                                                    uint8_t compression_level) {
   uint8_t *p = nullptr;

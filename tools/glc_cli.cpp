@@ -52,13 +52,14 @@ static long file_size(const std::string &p) {
 
 static int encode_file(const std::string &in) {
   std::printf("Loading: \"%s\"\n", file_name(in).c_str());
-  float *pcm = nullptr;
+  void *pcm = nullptr;
+  glc_pcm_format fmt = GLC_PCM_F32;
   uint64_t n = 0;
-  uint32_t sr = 0;
+  uint32_t sr = 0, bits = 0;
   uint16_t ch = 0;
-  // load_audio_file_lossless, src/audio.rs:19-36: by lower-cased extension
-  const int lrc = lower_ext(in) == "flac" ? glc_flac_load(in.c_str(), &pcm, &n, &sr, &ch)
-                                          : glc_wav_load(in.c_str(), &pcm, &n, &sr, &ch);
+  // load_audio_file_lossless, src/audio.rs:19-36 (by lower-cased extension), as the integers the file
+  // holds: they are widened to the loader's floats on the device (glc_encode_int)
+  const int lrc = glc_audio_load_pcm(in.c_str(), &pcm, &fmt, &bits, &n, &sr, &ch);
   if (lrc != GLC_OK) {
     std::fprintf(stderr, "Error encoding file: %s\n", glc_last_error(nullptr));
     return 1;
@@ -67,7 +68,7 @@ static int encode_file(const std::string &in) {
   glc_ctx *ctx = nullptr;
   glc_frames *fr = nullptr;
   int rc = glc_ctx_create(0, sr, &ctx);
-  if (rc == GLC_OK) rc = glc_encode(ctx, pcm, n, ch, &fr);
+  if (rc == GLC_OK) rc = glc_encode_int(ctx, pcm, fmt, bits, n, ch, &fr);
   glc_free(pcm);
   if (rc != GLC_OK) {
     std::fprintf(stderr, "Error encoding file: %s\n", glc_last_error(ctx));
@@ -99,9 +100,10 @@ static int decode_file(const std::string &in, bool wav, unsigned flac_level) {
   std::printf("Decoding: %u Hz, %u channels\n", info.sample_rate, info.channels);
   glc_ctx *ctx = nullptr;
   int rc = glc_ctx_create(0, info.sample_rate, &ctx);
-  std::vector<float> pcm(glc_decoded_len(fr));
+  // both outputs are 16-bit (convert_f32_to_i16, src/audio.rs:11-16, src/flac.rs:955-958): narrowed on the device
+  std::vector<int16_t> pcm(glc_decoded_len(fr));
   uint64_t n = 0;
-  if (rc == GLC_OK) rc = glc_decode(ctx, fr, pcm.data(), pcm.size(), &n);
+  if (rc == GLC_OK) rc = glc_decode_i16(ctx, fr, pcm.data(), pcm.size(), &n);
   glc_frames_free(fr);
   if (rc != GLC_OK) {
     std::fprintf(stderr, "Error decoding file: %s\n", glc_last_error(ctx));
@@ -111,8 +113,8 @@ static int decode_file(const std::string &in, bool wav, unsigned flac_level) {
   glc_ctx_destroy(ctx);
   std::printf("Decoded %llu samples\n", static_cast<unsigned long long>(n));
   const std::string out = with_ext(in, wav ? "wav" : "flac");
-  rc = wav ? glc_wav_save16(out.c_str(), pcm.data(), n, info.sample_rate, info.channels)
-           : glc_flac_save(out.c_str(), pcm.data(), n, info.sample_rate, info.channels, static_cast<uint8_t>(flac_level));
+  rc = wav ? glc_wav_save16_i16(out.c_str(), pcm.data(), n, info.sample_rate, info.channels)
+           : glc_flac_save_i16(out.c_str(), pcm.data(), n, info.sample_rate, info.channels, static_cast<uint8_t>(flac_level));
   if (rc != GLC_OK) {
     std::fprintf(stderr, "Error decoding file: %s\n", glc_last_error(nullptr));
     return 1;
