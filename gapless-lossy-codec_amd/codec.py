@@ -397,6 +397,18 @@ class Encoder(_Ctx):
                                      C.byref(out)), self._h)
         return EncodedAudio(out.value)
 
+    def encode_batch(self, clips, channels: int) -> list:
+        """glc_encode_batch: Encoder::encode of every clip of `clips` (a sequence of float32 arrays, each an
+        independent stream of `channels` channels) in one call; the i-th EncodedAudio holds the bytes
+        `encode(clips[i], channels)` gives.  Short clips share launch chains, uploads and downloads."""
+        pcm = [np.ascontiguousarray(c, np.float32).reshape(-1) for c in clips]
+        n = len(pcm)
+        ptrs = (C.c_void_p * max(n, 1))(*[p.ctypes.data for p in pcm])
+        lens = (C.c_uint64 * max(n, 1))(*[p.size for p in pcm])
+        outs = (C.c_void_p * max(n, 1))()
+        check(lib.glc_encode_batch(self._h, ptrs, lens, n, channels, outs), self._h)
+        return [EncodedAudio(outs[i]) for i in range(n)]
+
     def widen_device(self, d_in: int, dtype, bits: int, n: int, d_out: int) -> None:
         """glc_pcm_widen_device: n int16 / int32 samples of `bits` bits at device address d_in ->
         float32 at d_out, s / 2^(bits-1).  Queued on the context's stream, not synchronised."""
@@ -502,6 +514,22 @@ class Decoder(_Ctx):
         fn = lib.glc_decode if dt == np.float32 else lib.glc_decode_i16
         check(fn(self._h, encoded._h, out.ctypes.data_as(C.c_void_p), n, C.byref(got)), self._h)
         return out[:got.value]
+
+    def decode_batch(self, encoded_list, out: Optional[np.ndarray] = None) -> list:
+        """glc_decode_batch: Decoder::decode of every stream of `encoded_list` (all of one channel count)
+        in one call.  Returns one float32 array per stream, views into ONE packed array - `out` when
+        given (C-contiguous float32, at least the sum of the streams' total_samples), as in decode."""
+        encs = list(encoded_list)
+        n = len(encs)
+        handles = (C.c_void_p * max(n, 1))(*[e._h for e in encs])
+        offsets = (C.c_uint64 * (n + 1))()
+        total = sum(int(lib.glc_decoded_len(e._h)) for e in encs)
+        if out is None:
+            out = np.empty(total, np.float32)
+        elif out.dtype != np.float32 or not out.flags.c_contiguous or out.size < total:
+            raise GlcError(GLC_EINVAL, "out must be a C-contiguous float32 array of at least the streams' total_samples")
+        check(lib.glc_decode_batch(self._h, handles, n, out.ctypes.data_as(C.c_void_p), out.size, offsets), self._h)
+        return [out[offsets[i]:offsets[i + 1]] for i in range(n)]
 
     def resident_stream(self) -> int:
         """Identity of the stream whose sparse rows this context holds on the device (0: none)."""

@@ -155,6 +155,7 @@ struct glc_ctx {
   DevBuf pack_meta;  // compaction scratch: loc, blk, blk_raw, totals
   DevBuf pack_blob;  // compaction: the compact blob of glc_encode / glc_frames_from_device_records
   HostBuf host_stage;  // pinned: the blob on its way to the host
+  HostBuf batch_stage;  // pinned: a round of glc_encode_batch's short clips going up, then its payload coming down / of glc_decode_batch's rows going up
   std::string err;
   // decode session (decode_prepare / round_launch): device-resident sparse rows + position
   glc::DecodeRows dec_rows{};
@@ -372,6 +373,7 @@ void glc_ctx_destroy(glc_ctx *ctx) {
   ctx->pack_meta.release();
   ctx->pack_blob.release();
   ctx->host_stage.release();
+  ctx->batch_stage.release();
   delete ctx;
 }
 
@@ -1065,6 +1067,230 @@ static int encode_pipeline(glc_ctx *ctx, const void *pcm_any, glc_pcm_format fmt
   return GLC_OK;
 }
 
+// ------------------------------------------------------------------------------ encode, many clips
+
+namespace {
+
+struct BatchClip {
+  uint64_t index;  // in the caller's arrays
+  glc_plan plan;
+};
+
+// One round of glc_encode_batch: the clips `clips` (together at most encode_chunk_frames(ch) virtual
+// frames) through K1 / K2 / K3 as ONE virtual stream, one segment-aware compaction, two downloads.
+// Layout of the virtual stream: clip i of nf_i frames owns the (nf_i + 1) * 1024
+// per-channel samples from 1024 * slot_i on, its samples first, +0.0 behind them - the reference's own
+// padding (src/codec.rs:433-447), here in memory because the next clip follows.  Frame f of the clip
+// is virtual frame slot_i + f and reads nothing outside the clip's slot and the zeros in front of it;
+// virtual frame slot_i + nf_i straddles two clips and is junk: computed, in no frame map, never sent.
+int encode_batch_round(glc_ctx *ctx, const std::vector<BatchClip> &clips, const float *const *pcm, const uint64_t *n_samples,
+                       uint16_t channels, std::vector<std::unique_ptr<glc_frames>> &result) {
+  const uint32_t ch = channels;
+  const uint64_t n = clips.size();
+  uint64_t V = 0, n_real = 0;  // frames of the virtual stream / of the clips
+  for (const BatchClip &c : clips) V += c.plan.n_frames + 1, n_real += c.plan.n_frames;
+  const uint64_t T = V * glc::kHop, n_virtual = T * ch, M = n_real * ch;
+  const uint64_t rec = glc::record_bytes(ch);
+  // the round's blob: header | clip directory | raw flags | scales | counts | pairs | raw planes
+  const uint64_t o_dir = sizeof(glc::CompactHeader), o_israw = o_dir + glc::align64(16 * n),
+                 o_scale = o_israw + glc::align64(n_real), o_cnt = o_scale + glc::align64(4 * M),
+                 o_pairs = o_cnt + glc::align64(4 * M), bound = o_pairs + 4096ull * M + 64ull;
+  const size_t scratch = compact_scratch_bytes(M), o_fmap_h = align_up(o_pairs, 256);
+  GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // earlier work may still read the staging buffers
+  GLC_HIP(ctx, ctx->pcm.reserve(static_cast<size_t>(n_virtual) * sizeof(float)));
+  GLC_HIP(ctx, ctx->records.reserve(static_cast<size_t>(V) * rec));
+  GLC_HIP(ctx, ctx->pack_blob.reserve(bound));
+  GLC_HIP(ctx, ctx->pack_meta.reserve(scratch + align_up(n_real * sizeof(glc::FrameMap), 256)));
+  GLC_HIP(ctx, ctx->host_stage.reserve(o_fmap_h + n_real * sizeof(glc::FrameMap)));
+  float *d_pcm = static_cast<float *>(ctx->pcm.p);
+  uint8_t *hm = static_cast<uint8_t *>(ctx->host_stage.p);
+  uint8_t *mb = static_cast<uint8_t *>(ctx->pack_meta.p);
+  uint8_t *d_blob = static_cast<uint8_t *>(ctx->pack_blob.p);
+  hipStream_t st = ctx->stream;
+
+  // Staging: zeros everywhere (a recycled buffer holds old samples), then every clip into its slot.  A copy
+  // from pageable memory costs 11 us before it moves a byte, a host memcpy into pinned memory runs at half
+  // the speed of the DMA (tools/h2d_probe.cpp `clips`: 64 x 689 KiB take 1.49 ms with a copy each against 2.07 packed,
+  // 512 x 86 KiB 5.84 against 2.26): clips of at most kPackClipBytes are packed, slot by slot with their zeros, into
+  // a pinned image that goes up in runs of kPackRunBytes (the next run is packed while one is in flight);
+  // longer clips go up on their own, straight from the caller's memory.
+  constexpr uint64_t kPackClipBytes = 256u << 10, kPackRunBytes = 4u << 20;
+  auto slot_bytes = [&](const BatchClip &c) { return (c.plan.n_frames + 1) * glc::kHop * ch * sizeof(float); };
+  uint64_t packed = 0;
+  for (const BatchClip &c : clips)
+    if (n_samples[c.index] * sizeof(float) <= kPackClipBytes) packed += slot_bytes(c);
+  if (packed) GLC_HIP(ctx, ctx->batch_stage.reserve(packed));
+  uint8_t *pin = static_cast<uint8_t *>(ctx->batch_stage.p);
+  uint64_t pin_at = 0, run_begin = 0, run_dev = 0;  // bytes packed / where the open run starts in `pin` / in d_pcm (floats)
+  auto send_run = [&]() -> hipError_t {
+    hipError_t e = hipSuccess;
+    if (pin_at > run_begin)
+      e = hipMemcpyAsync(d_pcm + run_dev, pin + run_begin, pin_at - run_begin, hipMemcpyHostToDevice, st);
+    run_begin = pin_at;
+    return e;
+  };
+  GLC_HIP(ctx, hipMemsetAsync(d_pcm, 0, static_cast<size_t>(n_virtual) * sizeof(float), st));
+  glc::FrameMap *fmap = reinterpret_cast<glc::FrameMap *>(hm + o_fmap_h);
+  uint64_t slot = 0, real = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    const BatchClip &c = clips[i];
+    const uint64_t bytes = n_samples[c.index] * sizeof(float), at = slot * glc::kHop * ch;
+    if (bytes <= kPackClipBytes) {
+      if (pin_at == run_begin) run_dev = at;  // a run starts with this clip; consecutive clips have consecutive slots
+      std::memcpy(pin + pin_at, pcm[c.index], bytes);
+      std::memset(pin + pin_at + bytes, 0, slot_bytes(c) - bytes);
+      pin_at += slot_bytes(c);
+      if (pin_at - run_begin >= kPackRunBytes) GLC_HIP(ctx, send_run());
+    } else {
+      GLC_HIP(ctx, send_run());
+      GLC_HIP(ctx, hipMemcpyAsync(d_pcm + at, pcm[c.index], bytes, hipMemcpyHostToDevice, st));
+    }
+    for (uint64_t f = 0; f < c.plan.n_frames; ++f)
+      fmap[real + f] = glc::FrameMap{static_cast<uint32_t>(slot + f), f == 0 ? static_cast<uint32_t>(i) : 0xFFFFFFFFu};
+    slot += c.plan.n_frames + 1;
+    real += c.plan.n_frames;
+  }
+  GLC_HIP(ctx, send_run());
+  glc::FrameMap *d_fmap = reinterpret_cast<glc::FrameMap *>(mb + scratch);
+  GLC_HIP(ctx, hipMemcpyAsync(d_fmap, fmap, n_real * sizeof(glc::FrameMap), hipMemcpyHostToDevice, st));
+
+  int rc = encode_range_on(ctx, st, ctx->coef, d_pcm, 0, T, n_virtual, channels, 0, V, ctx->records.p, nullptr);
+  if (rc != GLC_OK) return rc;
+
+  {  // the scratch of compact_launch, the frame map behind it
+    const size_t nblk = (static_cast<size_t>(M) + 1023) / 1024;
+    const size_t o_loc = 0, o_blk = align_up(static_cast<size_t>(M) * 4, 256), o_blkr = o_blk + align_up(nblk * 8, 256),
+                 o_tot = o_blkr + align_up(nblk * 8, 256);
+    GLC_HIP(ctx, hipMemsetAsync(d_blob, 0, o_pairs, st));  // header + section padding: deterministic bytes
+    GLC_HIP(ctx, glc::launch_compact_batch(static_cast<const uint8_t *>(ctx->records.p), static_cast<uint32_t>(M), ch, n_real,
+                                           d_fmap, reinterpret_cast<uint64_t *>(d_blob + o_dir),
+                                           reinterpret_cast<uint32_t *>(mb + o_loc), reinterpret_cast<uint64_t *>(mb + o_blk),
+                                           reinterpret_cast<uint64_t *>(mb + o_blkr), reinterpret_cast<uint64_t *>(mb + o_tot),
+                                           d_blob, o_israw, o_scale, o_cnt, o_pairs, st));
+  }
+  // download 1: header, directory and the per-frame / per-row sections - they say how long the payload is
+  GLC_HIP(ctx, hipMemcpyAsync(hm, d_blob, o_pairs, hipMemcpyDeviceToHost, st));
+  GLC_HIP(ctx, hipStreamSynchronize(st));
+  glc::CompactHeader h;
+  std::memcpy(&h, hm, sizeof h);
+  const uint64_t raw_off = glc::align64(o_pairs + 4 * h.n_pairs);
+  if (h.magic != glc::kCompactMagic || h.channels != ch || h.n_frames != n_real || h.n_pairs > M * glc::kHop ||
+      h.n_raw_rows > M || h.bytes != raw_off + h.n_raw_rows * glc::kFrame * 2 || h.bytes > bound)
+    return fail(ctx, GLC_EHIP, "glc_encode_batch: the device wrote an inconsistent compact header");
+  // download 2: the payload of all clips in one copy, cut per clip on the host below
+  const uint64_t payload = h.bytes - o_pairs;
+  GLC_HIP(ctx, ctx->batch_stage.reserve(std::max<uint64_t>(payload, 64)));
+  const uint8_t *pay = static_cast<const uint8_t *>(ctx->batch_stage.p);
+  if (payload) GLC_HIP(ctx, hipMemcpyAsync(ctx->batch_stage.p, d_blob + o_pairs, payload, hipMemcpyDeviceToHost, st));
+  // ... and while it is on its way, the index vectors of every clip
+  const uint64_t *dir = reinterpret_cast<const uint64_t *>(hm + o_dir);
+  const uint8_t *israw = hm + o_israw;
+  const float *scale = reinterpret_cast<const float *>(hm + o_scale);
+  const uint32_t *cnt = reinterpret_cast<const uint32_t *>(hm + o_cnt);
+  std::vector<std::unique_ptr<glc_frames>> made(n);
+  real = 0;
+  for (uint64_t i = 0; i < n && rc == GLC_OK; ++i) {
+    const BatchClip &c = clips[i];
+    const uint64_t p0 = dir[2 * i], q0 = dir[2 * i + 1];
+    const uint64_t p1 = i + 1 < n ? dir[2 * i + 2] : h.n_pairs, q1 = i + 1 < n ? dir[2 * i + 3] : h.n_raw_rows;
+    if (p0 > p1 || p1 > h.n_pairs || q0 > q1 || q1 > h.n_raw_rows) {
+      rc = fail(ctx, GLC_EHIP, "glc_encode_batch: the device wrote an inconsistent clip directory");
+      break;
+    }
+    made[i].reset(new glc_frames);
+    glc_frames *F = made[i].get();
+    glc::init_frames(F, ctx->sample_rate, n_samples[c.index], channels, c.plan);
+    F->pairs.resize(p1 - p0);
+    F->raw.resize((q1 - q0) * glc::kFrame);
+    bool canonical = true;
+    const int irc = glc::index_compact_rows(F, ch, c.plan.n_frames, p1 - p0, q1 - q0, israw + real, scale + real * ch,
+                                            cnt + real * ch, 0, 0, 0, /*trusted=*/true, &canonical);
+    if (irc != GLC_OK) rc = fail(ctx, irc, std::string("glc_encode_batch: ") + glc_last_error(nullptr));
+    F->lists_canonical = true;  // ballot-packed in ascending k
+    real += c.plan.n_frames;
+  }
+  const hipError_t e = hipStreamSynchronize(st);
+  if (rc != GLC_OK) return rc;
+  if (e != hipSuccess) return hip_fail(ctx, e, "glc_encode_batch: download");
+  const uint32_t *pairs = reinterpret_cast<const uint32_t *>(pay);
+  const int16_t *raw = reinterpret_cast<const int16_t *>(pay + (raw_off - o_pairs));
+  for (uint64_t i = 0; i < n; ++i) {
+    glc_frames *F = made[i].get();
+    if (!F->pairs.empty()) std::memcpy(F->pairs.data(), pairs + dir[2 * i], F->pairs.size() * 4);
+    if (!F->raw.empty()) std::memcpy(F->raw.data(), raw + dir[2 * i + 1] * glc::kFrame, F->raw.size() * 2);
+    result[clips[i].index] = std::move(made[i]);
+  }
+  return GLC_OK;
+}
+
+int encode_batch_impl(glc_ctx *ctx, const float *const *pcm, const uint64_t *n_samples, uint64_t n_clips, uint16_t channels,
+                      glc_frames **out) {
+  std::vector<BatchClip> all(n_clips);
+  for (uint64_t i = 0; i < n_clips; ++i) {
+    all[i] = BatchClip{i, glc::plan_encode(n_samples[i], channels)};
+    if (all[i].plan.n_frames == 0)
+      return fail(ctx, GLC_EINVAL,
+                  "glc_encode_batch: clip " + std::to_string(i) +
+                      ": the reference encoder panics on this input (channels == 0, <= 512 samples per channel, or "
+                      "ragged channels)");
+    if (!pcm[i]) return fail(ctx, GLC_EINVAL, "glc_encode_batch: clip " + std::to_string(i) + ": null pointer");
+  }
+  DeviceGuard guard(ctx->device);
+  std::vector<std::unique_ptr<glc_frames>> result(n_clips);
+  const uint64_t budget = encode_chunk_frames(channels);  // virtual frames per round: the workspaces stay round-sized
+  std::vector<BatchClip> round;
+  uint64_t used = 0;
+  int rc = GLC_OK;
+  auto alone = [&](uint64_t i) {  // the single-stream pipeline (uploads, kernels and downloads of one stream overlapped)
+    glc_frames *f = nullptr;
+    rc = encode_pipeline(ctx, pcm[i], GLC_PCM_F32, 32, n_samples[i], channels, nullptr, nullptr, &f);
+    result[i].reset(f);
+  };
+  auto flush = [&] {
+    if (round.size() == 1 && rc == GLC_OK)  // a clip with a round to itself shares nothing
+      alone(round[0].index);
+    else if (!round.empty() && rc == GLC_OK)
+      rc = encode_batch_round(ctx, round, pcm, n_samples, channels, result);
+    round.clear();
+    used = 0;
+  };
+  for (uint64_t i = 0; i < n_clips && rc == GLC_OK; ++i) {
+    const uint64_t v = all[i].plan.n_frames + 1;
+    if (v > budget) {  // longer than a round: nothing to gain from packing
+      flush();
+      if (rc == GLC_OK) alone(i);
+      continue;
+    }
+    if (used + v > budget) flush();
+    round.push_back(all[i]);
+    used += v;
+  }
+  flush();
+  if (rc != GLC_OK) {
+    (void)hipStreamSynchronize(ctx->stream);  // nothing may still be in flight out of the caller's memory
+    return rc;
+  }
+  for (uint64_t i = 0; i < n_clips; ++i) out[i] = result[i].release();
+  return GLC_OK;
+}
+
+}  // namespace
+
+int glc_encode_batch(glc_ctx *ctx, const float *const *pcm, const uint64_t *n_samples, uint64_t n_clips, uint16_t channels,
+                     glc_frames **out) {
+  if (!ctx) return fail(ctx, GLC_EINVAL, "glc_encode_batch: null argument");
+  if (n_clips == 0) return GLC_OK;
+  if (!pcm || !n_samples || !out) return fail(ctx, GLC_EINVAL, "glc_encode_batch: null argument");
+  for (uint64_t i = 0; i < n_clips; ++i) out[i] = nullptr;
+  if (channels == 0) return fail(ctx, GLC_EINVAL, "glc_encode_batch: channels == 0");
+  try {  // no C++ exception may cross the C ABI
+    return encode_batch_impl(ctx, pcm, n_samples, n_clips, channels, out);
+  } catch (const std::bad_alloc &) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return fail(ctx, GLC_ENOMEM, "glc_encode_batch: host allocation failed");
+  }
+}
+
 // ------------------------------------------------------------------------------ decode
 
 extern "C++" {  // templates over the output sample type
@@ -1085,25 +1311,129 @@ int decode_prepare(glc_ctx *ctx, const glc_frames *in) {
   }
 }
 
+// D1's plan workspace for a launch of `nf` frames: its (8-frame group, channel) units, at most kPlanGroups
+// per batch (66 KB per unit: a 12-frame clip needs 4 units, not the 135 MB of a full batch)
+int reserve_d1_plan(glc_ctx *ctx, uint64_t nf, uint32_t ch) {
+  if (ctx->d1_variant == 1) return GLC_OK;
+  DeviceGuard guard_plan(ctx->device);
+  const uint64_t units = ((nf + 7) / 8) * ch;
+  const uint32_t want = static_cast<uint32_t>(std::max<uint64_t>(ch, std::min<uint64_t>(std::max<uint32_t>(kPlanGroups, ch), units)));
+  if (want > ctx->dec_plan_groups) {
+    GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // queued launches may still read the old workspace
+    GLC_HIP(ctx, ctx->dec_plan.reserve(glc::imdct_plan_bytes(want)));
+    ctx->dec_plan_groups = want;
+    ctx->plan_uid = 0;
+  }
+  return GLC_OK;
+}
+
+// The row tables D1 reads, for ONE stream (decode_prepare_impl) or for the streams of a round of
+// glc_decode_batch laid end to end: rows in stream order, the stored pairs of all streams back to back
+// (a row's pair range rebased by what the streams before it hold), then the canonicalised copies of
+// non-canonical lists; raw vectors likewise in one pool.
+// The five per-row arrays are built in ONE host block in the layout they have on the device, so that
+// they go up in one copy (each copy from pageable memory costs ~20 us before it moves a byte: eight
+// of them were a third of what a context spends on a stream it has not seen).
+struct RowTable {
+  size_t h_begin = 0, h_cnt = 0, h_scale = 0, h_raw = 0, h_rawlen = 0, h_end = 0;  // byte offsets inside `block`
+  std::vector<uint64_t> block;  // 8-byte aligned storage
+  std::vector<uint32_t> extra;  // canonicalised copies of non-canonical lists
+  uint64_t n_stored = 0, n_raw = 0;  // stored pairs / raw samples of all the streams
+  uint32_t any_raw = 0;
+};
+
+// `M`: rows of all the streams (each of `ch` channels).  `who`: the entry point for the error message, which
+// names the stream when there are several.
+int build_row_table(glc_ctx *ctx, const char *who, const glc_frames *const *streams, uint64_t n_streams, uint32_t ch,
+                    uint64_t M, RowTable &t) {
+  const size_t Mr = std::max<size_t>(M, 1);
+  t.h_begin = 0, t.h_cnt = align_up(t.h_begin + Mr * 8, 256), t.h_scale = align_up(t.h_cnt + Mr * 4, 256),
+  t.h_raw = align_up(t.h_scale + Mr * 4, 256), t.h_rawlen = align_up(t.h_raw + Mr * 8, 256),
+  t.h_end = align_up(t.h_rawlen + Mr * 8, 256);
+  t.block.assign(t.h_end / 8, 0);
+  uint8_t *hb = reinterpret_cast<uint8_t *>(t.block.data());
+  uint64_t *row_begin = reinterpret_cast<uint64_t *>(hb + t.h_begin);
+  uint32_t *row_cnt = reinterpret_cast<uint32_t *>(hb + t.h_cnt);
+  float *row_scale = reinterpret_cast<float *>(hb + t.h_scale);
+  int64_t *row_raw = reinterpret_cast<int64_t *>(hb + t.h_raw);
+  uint64_t *row_raw_len = reinterpret_cast<uint64_t *>(hb + t.h_rawlen);
+  for (uint64_t m = 0; m < M; ++m) row_raw[m] = -1;
+  t.any_raw = 0;
+  t.extra.clear();
+  t.n_stored = t.n_raw = 0;
+  for (uint64_t s = 0; s < n_streams; ++s) t.n_stored += streams[s]->pairs.size(), t.n_raw += streams[s]->raw.size();
+  std::vector<int32_t> dense;
+  uint64_t row0 = 0, pair0 = 0, raw0 = 0;  // what the streams in front of this one hold
+  for (uint64_t s = 0; s < n_streams; ++s) {
+    const glc_frames *in = streams[s];
+    const uint64_t nf = in->n_frames;
+    for (uint64_t f = 0; f < nf; ++f) {
+      if (in->raw_tag[f]) {
+        t.any_raw = 1;
+        for (uint32_t c = 0; c < ch; ++c) {
+          row_raw[row0 + f * ch + c] = static_cast<int64_t>(raw0 + in->raw_begin[f]);
+          row_raw_len[row0 + f * ch + c] = in->raw_begin[f + 1] - in->raw_begin[f];
+        }
+        continue;
+      }
+      const uint64_t l0 = in->list_begin[f], nl = in->list_begin[f + 1] - l0;
+      const uint64_t s0 = in->scale_begin[f], ns = in->scale_begin[f + 1] - s0;
+      if (nl < ch || ns < ch)  // the reference indexes [ch] out of bounds and panics, :652-653
+        return fail(ctx, GLC_EFORMAT,
+                    std::string(who) + (n_streams > 1 ? ": stream " + std::to_string(s) : std::string()) +
+                        ": frame has fewer channel vectors than header.channels");
+      for (uint32_t c = 0; c < ch; ++c) {
+        const uint64_t a = in->list_off[l0 + c], b = in->list_off[l0 + c + 1];
+        bool canonical = true;
+        if (!in->lists_canonical && b > a) {
+          // strictly ascending indices below 1024: branch-free over the whole list, so that the compiler
+          // vectorises it (streams built by glc_frames_from_parts / _gather / glc_deserialize come through
+          // here on their first decode: 0.9 M pairs at config 2)
+          const uint32_t *pp = in->pairs.data() + a;
+          const uint64_t n_p = b - a;
+          uint32_t bad = (pp[0] & 0xFFFFu) >= glc::kHop ? 1u : 0u;
+          for (uint64_t j = 1; j < n_p; ++j) {
+            const uint32_t k = pp[j] & 0xFFFFu, kp = pp[j - 1] & 0xFFFFu;
+            bad |= (k <= kp ? 1u : 0u) | (k >= glc::kHop ? 1u : 0u);
+          }
+          canonical = bad == 0;
+        }
+        const uint64_t m = row0 + f * ch + c;
+        if (canonical) {
+          row_begin[m] = pair0 + a;
+          row_cnt[m] = static_cast<uint32_t>(b - a);
+        } else {
+          dense.assign(glc::kHop, INT32_MIN);
+          for (uint64_t j = a; j < b; ++j) {
+            const uint32_t k = in->pairs[j] & 0xFFFFu;
+            if (k < glc::kHop) dense[k] = static_cast<int16_t>(in->pairs[j] >> 16);
+          }
+          row_begin[m] = t.n_stored + t.extra.size();
+          // stored zeros stay: 0 * scale is NaN when the scale is infinite (src/codec.rs:663), and
+          // the result must not depend on whether the list happened to be in canonical order
+          for (uint32_t k = 0; k < glc::kHop; ++k)
+            if (dense[k] != INT32_MIN)
+              t.extra.push_back(k | (static_cast<uint32_t>(static_cast<uint16_t>(dense[k])) << 16));
+          row_cnt[m] = static_cast<uint32_t>(t.n_stored + t.extra.size() - row_begin[m]);
+        }
+        row_scale[m] = in->scales[s0 + c];
+      }
+    }
+    row0 += nf * ch;
+    pair0 += in->pairs.size();
+    raw0 += in->raw.size();
+  }
+  return GLC_OK;
+}
+
 int decode_prepare_impl(glc_ctx *ctx, const glc_frames *in) {
   const uint32_t ch = in->channels;
   if (ch == 0) return fail(ctx, GLC_EINVAL, "glc_decode: header.channels == 0");
   const uint64_t nf = in->n_frames;
   const uint64_t M = nf * ch;
   if (M > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, "glc_decode: stream too long");
-  if (ctx->d1_variant != 1) {
-    // D1's plan workspace: one launch of this stream's (8-frame group, channel) units, at most kPlanGroups
-    // per batch (66 KB per unit: a 12-frame clip needs 4 units, not the 135 MB of a full batch)
-    DeviceGuard guard_plan(ctx->device);
-    const uint64_t units = ((nf + 7) / 8) * ch;
-    const uint32_t want = static_cast<uint32_t>(std::max<uint64_t>(ch, std::min<uint64_t>(std::max<uint32_t>(kPlanGroups, ch), units)));
-    if (want > ctx->dec_plan_groups) {
-      GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // queued launches may still read the old workspace
-      GLC_HIP(ctx, ctx->dec_plan.reserve(glc::imdct_plan_bytes(want)));
-      ctx->dec_plan_groups = want;
-      ctx->plan_uid = 0;
-    }
-  }
+  int rc = reserve_d1_plan(ctx, nf, ch);
+  if (rc != GLC_OK) return rc;
   // The sparse rows of this stream are still on the device from an earlier call (a glc_frames is
   // immutable and its uid is unique in the process, or a caller-supplied identity of the content;
   // the pool sizes are compared as well, so that a recycled id does not silently decode old rows).
@@ -1116,75 +1446,9 @@ int decode_prepare_impl(glc_ctx *ctx, const glc_frames *in) {
   ctx->dec_uid = 0;
   ctx->plan_uid = 0;
 
-  // The five per-row arrays are built in ONE host block in the layout they have on the device, so that
-  // they go up in one copy (each copy from pageable memory costs ~20 us before it moves a byte: eight
-  // of them were a third of what a context spends on a stream it has not seen).
-  const size_t Mr = std::max<size_t>(M, 1);
-  const size_t h_begin = 0, h_cnt = align_up(h_begin + Mr * 8, 256), h_scale = align_up(h_cnt + Mr * 4, 256),
-               h_raw = align_up(h_scale + Mr * 4, 256), h_rawlen = align_up(h_raw + Mr * 8, 256),
-               h_end = align_up(h_rawlen + Mr * 8, 256);
-  std::vector<uint64_t> host_rows(h_end / 8, 0);  // 8-byte aligned storage
-  uint8_t *hb = reinterpret_cast<uint8_t *>(host_rows.data());
-  uint64_t *row_begin = reinterpret_cast<uint64_t *>(hb + h_begin);
-  uint32_t *row_cnt = reinterpret_cast<uint32_t *>(hb + h_cnt);
-  float *row_scale = reinterpret_cast<float *>(hb + h_scale);
-  int64_t *row_raw = reinterpret_cast<int64_t *>(hb + h_raw);
-  uint64_t *row_raw_len = reinterpret_cast<uint64_t *>(hb + h_rawlen);
-  for (uint64_t m = 0; m < M; ++m) row_raw[m] = -1;
-  uint32_t any_raw = 0;
-  std::vector<uint32_t> extra;  // canonicalised copies of non-canonical lists
-  std::vector<int32_t> dense;
-  const uint64_t n_stored = in->pairs.size();
-  for (uint64_t f = 0; f < nf; ++f) {
-    if (in->raw_tag[f]) {
-      any_raw = 1;
-      for (uint32_t c = 0; c < ch; ++c) {
-        row_raw[f * ch + c] = static_cast<int64_t>(in->raw_begin[f]);
-        row_raw_len[f * ch + c] = in->raw_begin[f + 1] - in->raw_begin[f];
-      }
-      continue;
-    }
-    const uint64_t l0 = in->list_begin[f], nl = in->list_begin[f + 1] - l0;
-    const uint64_t s0 = in->scale_begin[f], ns = in->scale_begin[f + 1] - s0;
-    if (nl < ch || ns < ch)  // the reference indexes [ch] out of bounds and panics, :652-653
-      return fail(ctx, GLC_EFORMAT, "glc_decode: frame has fewer channel vectors than header.channels");
-    for (uint32_t c = 0; c < ch; ++c) {
-      const uint64_t a = in->list_off[l0 + c], b = in->list_off[l0 + c + 1];
-      bool canonical = true;
-      if (!in->lists_canonical && b > a) {
-        // strictly ascending indices below 1024: branch-free over the whole list, so that the compiler
-        // vectorises it (streams built by glc_frames_from_parts / _gather / glc_deserialize come through
-        // here on their first decode: 0.9 M pairs at config 2)
-        const uint32_t *pp = in->pairs.data() + a;
-        const uint64_t n_p = b - a;
-        uint32_t bad = (pp[0] & 0xFFFFu) >= glc::kHop ? 1u : 0u;
-        for (uint64_t j = 1; j < n_p; ++j) {
-          const uint32_t k = pp[j] & 0xFFFFu, kp = pp[j - 1] & 0xFFFFu;
-          bad |= (k <= kp ? 1u : 0u) | (k >= glc::kHop ? 1u : 0u);
-        }
-        canonical = bad == 0;
-      }
-      const uint64_t m = f * ch + c;
-      if (canonical) {
-        row_begin[m] = a;
-        row_cnt[m] = static_cast<uint32_t>(b - a);
-      } else {
-        dense.assign(glc::kHop, INT32_MIN);
-        for (uint64_t j = a; j < b; ++j) {
-          const uint32_t k = in->pairs[j] & 0xFFFFu;
-          if (k < glc::kHop) dense[k] = static_cast<int16_t>(in->pairs[j] >> 16);
-        }
-        row_begin[m] = n_stored + extra.size();
-        // stored zeros stay: 0 * scale is NaN when the scale is infinite (src/codec.rs:663), and
-        // the result must not depend on whether the list happened to be in canonical order
-        for (uint32_t k = 0; k < glc::kHop; ++k)
-          if (dense[k] != INT32_MIN)
-            extra.push_back(k | (static_cast<uint32_t>(static_cast<uint16_t>(dense[k])) << 16));
-        row_cnt[m] = static_cast<uint32_t>(n_stored + extra.size() - row_begin[m]);
-      }
-      row_scale[m] = in->scales[s0 + c];
-    }
-  }
+  RowTable t;
+  rc = build_row_table(ctx, "glc_decode", &in, 1, ch, M, t);
+  if (rc != GLC_OK) return rc;
 
   DeviceGuard guard(ctx->device);
   size_t off = 0;
@@ -1193,10 +1457,8 @@ int decode_prepare_impl(glc_ctx *ctx, const glc_frames *in) {
     off = align_up(off + bytes, 256);
     return at;
   };
-  const size_t o_pairs = place(std::max<size_t>(n_stored + extra.size(), 1) * 4);
-  const size_t o_rows = place(h_end);  // the block above, as it is
-  const size_t o_begin = o_rows + h_begin, o_cnt = o_rows + h_cnt, o_scale = o_rows + h_scale, o_raw = o_rows + h_raw,
-               o_rawlen = o_rows + h_rawlen;
+  const size_t o_pairs = place(std::max<size_t>(t.n_stored + t.extra.size(), 1) * 4);
+  const size_t o_rows = place(t.h_end);  // the row block, as it is
   const size_t o_pool = place(std::max<size_t>(in->raw.size(), 1) * 2);
   GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // a previous session may still read dec_meta
   GLC_HIP(ctx, ctx->dec_meta.reserve(off));
@@ -1205,18 +1467,18 @@ int decode_prepare_impl(glc_ctx *ctx, const glc_frames *in) {
     if (!bytes) return hipSuccess;
     return hipMemcpyAsync(mb + o, src, bytes, hipMemcpyHostToDevice, ctx->stream);
   };
-  GLC_HIP(ctx, up(o_pairs, in->pairs.data(), n_stored * 4));
-  GLC_HIP(ctx, up(o_pairs + n_stored * 4, extra.data(), extra.size() * 4));
-  GLC_HIP(ctx, up(o_rows, hb, h_end));
+  GLC_HIP(ctx, up(o_pairs, in->pairs.data(), t.n_stored * 4));
+  GLC_HIP(ctx, up(o_pairs + t.n_stored * 4, t.extra.data(), t.extra.size() * 4));
+  GLC_HIP(ctx, up(o_rows, t.block.data(), t.h_end));
   GLC_HIP(ctx, up(o_pool, in->raw.data(), in->raw.size() * 2));
   GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the host vectors above go out of scope
   ctx->dec_rows = glc::DecodeRows{reinterpret_cast<const uint32_t *>(mb + o_pairs),
-                                  reinterpret_cast<const uint64_t *>(mb + o_begin),
-                                  reinterpret_cast<const uint32_t *>(mb + o_cnt),
-                                  reinterpret_cast<const float *>(mb + o_scale),
-                                  reinterpret_cast<const int64_t *>(mb + o_raw),
-                                  reinterpret_cast<const uint64_t *>(mb + o_rawlen),
-                                  reinterpret_cast<const int16_t *>(mb + o_pool), any_raw};
+                                  reinterpret_cast<const uint64_t *>(mb + o_rows + t.h_begin),
+                                  reinterpret_cast<const uint32_t *>(mb + o_rows + t.h_cnt),
+                                  reinterpret_cast<const float *>(mb + o_rows + t.h_scale),
+                                  reinterpret_cast<const int64_t *>(mb + o_rows + t.h_raw),
+                                  reinterpret_cast<const uint64_t *>(mb + o_rows + t.h_rawlen),
+                                  reinterpret_cast<const int16_t *>(mb + o_pool), t.any_raw};
   ctx->dec_ch = ch;
   ctx->dec_frames = nf;
   ctx->dec_next = 0;
@@ -1392,6 +1654,135 @@ int decode_prepared_to_host(glc_ctx *ctx, T *pcm_out, uint64_t cap, uint64_t *n_
   return GLC_OK;
 }
 
+// One round of glc_decode_batch: streams[0 .. n) (all of `ch` channels, together at most a round's frames)
+// through D1 as one row table, then the segment-aware overlap-add, which writes every stream's TRIMMED
+// samples back to back, and one copy of them to pcm_out.  lens[i]: glc_decoded_len of stream i.
+int decode_batch_round(glc_ctx *ctx, const glc_frames *const *streams, uint64_t n, uint32_t ch, const uint64_t *lens,
+                       float *pcm_out) {
+  uint64_t frames = 0, n_out = 0;
+  for (uint64_t i = 0; i < n; ++i) frames += streams[i]->n_frames, n_out += lens[i];
+  const uint64_t M = frames * ch;
+  int rc = reserve_d1_plan(ctx, frames, ch);
+  if (rc != GLC_OK) return rc;
+  RowTable t;
+  rc = build_row_table(ctx, "glc_decode_batch", streams, n, ch, M, t);
+  if (rc != GLC_OK) return rc;
+  // a descriptor per output hop that the stream's gapless trim keeps something of
+  std::vector<glc::HopDesc> desc;
+  const uint64_t per_hop = static_cast<uint64_t>(glc::kHop) * ch;
+  uint64_t slot0 = 0, dst0 = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    const glc_frames *in = streams[i];
+    const glc::Trim trim = glc::gapless_trim(in->n_frames, ch, in->encoder_delay, in->original_length);
+    if (trim.n) {
+      const uint64_t h_lo = trim.start / per_hop, h_hi = (trim.start + trim.n - 1) / per_hop;
+      for (uint64_t h = h_lo; h <= h_hi; ++h) {
+        const uint64_t lo = std::max(trim.start, h * per_hop), hi = std::min(trim.start + trim.n, (h + 1) * per_hop);
+        desc.push_back(glc::HopDesc{h >= 1 ? static_cast<int32_t>(slot0 + h - 1) : -1,
+                                    h < in->n_frames ? static_cast<int32_t>(slot0 + h) : -1,
+                                    static_cast<uint32_t>(dst0 + (lo - trim.start)), static_cast<uint32_t>(lo - h * per_hop),
+                                    static_cast<uint32_t>(hi - lo), 0u});
+      }
+    }
+    slot0 += in->n_frames;
+    dst0 += trim.n;
+  }
+  // everything D1 and D2 read, as ONE image in pinned memory and one copy: the pairs of all streams, the
+  // canonicalised lists, the row arrays, the raw pool, the hop descriptors
+  size_t off = 0;
+  auto place = [&](size_t bytes) {
+    size_t at = off;
+    off = align_up(off + bytes, 256);
+    return at;
+  };
+  const size_t o_pairs = place(std::max<size_t>(t.n_stored + t.extra.size(), 1) * 4);
+  const size_t o_rows = place(t.h_end);
+  const size_t o_pool = place(std::max<size_t>(t.n_raw, 1) * 2);
+  const size_t o_desc = place(std::max<size_t>(desc.size(), 1) * sizeof(glc::HopDesc));
+  DeviceGuard guard(ctx->device);
+  const size_t slot = static_cast<size_t>(ch) * glc::kFrame;
+  GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // a previous session may still read dec_meta
+  GLC_HIP(ctx, ctx->dec_meta.reserve(off));
+  GLC_HIP(ctx, ctx->batch_stage.reserve(off));
+  GLC_HIP(ctx, ctx->blocks.reserve(std::max<size_t>(frames, 1) * slot * sizeof(float)));
+  GLC_HIP(ctx, ctx->pcm.reserve(std::max<size_t>(n_out, 1) * sizeof(float)));
+  uint8_t *img = static_cast<uint8_t *>(ctx->batch_stage.p);
+  {
+    uint8_t *p = img + o_pairs;
+    int16_t *r = reinterpret_cast<int16_t *>(img + o_pool);
+    for (uint64_t i = 0; i < n; ++i) {
+      const glc_frames *in = streams[i];
+      if (!in->pairs.empty()) std::memcpy(p, in->pairs.data(), in->pairs.size() * 4);
+      p += in->pairs.size() * 4;
+      if (!in->raw.empty()) std::memcpy(r, in->raw.data(), in->raw.size() * 2);
+      r += in->raw.size();
+    }
+    if (!t.extra.empty()) std::memcpy(p, t.extra.data(), t.extra.size() * 4);
+    std::memcpy(img + o_rows, t.block.data(), t.h_end);
+    if (!desc.empty()) std::memcpy(img + o_desc, desc.data(), desc.size() * sizeof(glc::HopDesc));
+  }
+  uint8_t *mb = static_cast<uint8_t *>(ctx->dec_meta.p);
+  GLC_HIP(ctx, hipMemcpyAsync(mb, img, off, hipMemcpyHostToDevice, ctx->stream));
+  const glc::DecodeRows rows{reinterpret_cast<const uint32_t *>(mb + o_pairs),
+                             reinterpret_cast<const uint64_t *>(mb + o_rows + t.h_begin),
+                             reinterpret_cast<const uint32_t *>(mb + o_rows + t.h_cnt),
+                             reinterpret_cast<const float *>(mb + o_rows + t.h_scale),
+                             reinterpret_cast<const int64_t *>(mb + o_rows + t.h_raw),
+                             reinterpret_cast<const uint64_t *>(mb + o_rows + t.h_rawlen),
+                             reinterpret_cast<const int16_t *>(mb + o_pool), t.any_raw};
+  float *blocks = static_cast<float *>(ctx->blocks.p);
+  float *stage = static_cast<float *>(ctx->pcm.p);
+  // (D1's 8-frame units may span two streams: that only widens a union)
+  GLC_HIP(ctx, glc::launch_imdct_rows(ctx->dev, rows, 0, static_cast<uint32_t>(M), ch, blocks, ctx->stream, ctx->d1_variant,
+                                      ctx->dec_plan.p, ctx->dec_plan.p ? ctx->dec_plan_groups : 0, false));
+  GLC_HIP(ctx, glc::launch_overlap_add_batch(blocks, reinterpret_cast<const glc::HopDesc *>(mb + o_desc),
+                                             static_cast<uint32_t>(desc.size()), ch, stage, ctx->stream));
+  if (n_out) GLC_HIP(ctx, hipMemcpyAsync(pcm_out, stage, n_out * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return GLC_OK;
+}
+
+int decode_batch_impl(glc_ctx *ctx, const glc_frames *const *in, uint64_t n_streams, float *pcm_out, const uint64_t *offsets) {
+  const uint32_t ch = in[0]->channels;
+  const uint64_t per_hop = static_cast<uint64_t>(glc::kHop) * ch;
+  // a round: whole streams of together at most kDecodeChunkFrames frames (+ one tail hop each), its output
+  // addressed in 32 bits
+  const uint64_t hop_budget = std::min<uint64_t>(kDecodeChunkFrames + 1, 0x7FFFFFFFull / per_hop);
+  uint64_t first = 0, hops = 0;
+  int rc = GLC_OK;
+  auto alone = [&](uint64_t i) {  // the single-stream driver, straight into the stream's span
+    rc = decode_prepare(ctx, in[i]);
+    if (rc == GLC_OK)
+      rc = decode_prepared_to_host(ctx, pcm_out + offsets[i], offsets[i + 1] - offsets[i], nullptr, "glc_decode_batch");
+    ctx->dec_uid = 0;  // a batch decode leaves no stream resident
+    ctx->plan_uid = 0;
+  };
+  auto flush = [&](uint64_t end) {
+    if (end == first + 1 && rc == GLC_OK) {  // a stream with a round to itself shares nothing
+      alone(first);
+    } else if (end > first && rc == GLC_OK) {
+      std::vector<uint64_t> lens(end - first);
+      for (uint64_t i = first; i < end; ++i) lens[i - first] = offsets[i + 1] - offsets[i];
+      rc = decode_batch_round(ctx, in + first, end - first, ch, lens.data(), pcm_out + offsets[first]);
+    }
+    first = end;
+    hops = 0;
+  };
+  for (uint64_t i = 0; i < n_streams && rc == GLC_OK; ++i) {
+    const uint64_t v = in[i]->n_frames + 1;
+    if (v > hop_budget) {  // longer than a round
+      flush(i);
+      if (rc == GLC_OK) alone(i);
+      first = i + 1;
+      continue;
+    }
+    if (hops + v > hop_budget) flush(i);
+    hops += v;
+  }
+  flush(n_streams);
+  return rc;
+}
+
 // glc_decode / glc_decode_i16
 template <typename T>
 int decode_to_host(glc_ctx *ctx, const glc_frames *in, T *pcm_out, uint64_t cap, uint64_t *n_out, const char *who) {
@@ -1476,6 +1867,43 @@ int glc_decode(glc_ctx *ctx, const glc_frames *in, float *pcm_out, uint64_t cap,
 
 int glc_decode_i16(glc_ctx *ctx, const glc_frames *in, int16_t *pcm_out, uint64_t cap, uint64_t *n_out) {
   return decode_to_host(ctx, in, pcm_out, cap, n_out, "glc_decode_i16");
+}
+
+int glc_decode_batch(glc_ctx *ctx, const glc_frames *const *in, uint64_t n_streams, float *pcm_out, uint64_t cap,
+                     uint64_t *offsets) {
+  if (!ctx) return fail(ctx, GLC_EINVAL, "glc_decode_batch: null argument");
+  if (n_streams == 0) {
+    if (offsets) offsets[0] = 0;
+    return GLC_OK;
+  }
+  if (!in || !offsets || (!pcm_out && cap)) return fail(ctx, GLC_EINVAL, "glc_decode_batch: null argument");
+  offsets[0] = 0;
+  for (uint64_t i = 0; i < n_streams; ++i) {
+    if (!in[i]) return fail(ctx, GLC_EINVAL, "glc_decode_batch: stream " + std::to_string(i) + ": null pointer");
+    offsets[i + 1] = offsets[i] + glc_decoded_len(in[i]);
+  }
+  if (in[0]->channels == 0) return fail(ctx, GLC_EINVAL, "glc_decode_batch: header.channels == 0");
+  for (uint64_t i = 1; i < n_streams; ++i)
+    if (in[i]->channels != in[0]->channels)
+      return fail(ctx, GLC_EINVAL,
+                  "glc_decode_batch: stream " + std::to_string(i) + " has " + std::to_string(in[i]->channels) +
+                      " channels, stream 0 has " + std::to_string(in[0]->channels));
+  if (cap < offsets[n_streams]) return fail(ctx, GLC_EINVAL, "glc_decode_batch: output buffer too small");
+  // no stream is resident afterwards: the row tables on the device are a round's, not a stream's
+  ctx->stream_open = false;
+  ctx->dec_uid = 0;
+  ctx->plan_uid = 0;
+  int rc;
+  try {  // no C++ exception may cross the C ABI
+    rc = decode_batch_impl(ctx, in, n_streams, pcm_out, offsets);
+  } catch (const std::bad_alloc &) {
+    rc = fail(ctx, GLC_ENOMEM, "glc_decode_batch: host allocation failed");
+  }
+  if (rc != GLC_OK) {
+    DeviceGuard guard(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);  // nothing may still be in flight into the caller's memory
+  }
+  return rc;
 }
 
 uint64_t glc_ctx_resident_stream(const glc_ctx *ctx) { return ctx ? ctx->dec_uid : 0; }

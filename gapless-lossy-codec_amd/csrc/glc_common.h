@@ -125,6 +125,9 @@ void init_frames(glc_frames *F, uint32_t sample_rate, uint64_t n_samples, uint16
 // `trusted`: the blobs were produced by this process's own pack kernels (lists known canonical).
 int index_compact_meta(glc_frames *F, uint32_t ch, const CompactHeader &h, const uint8_t *meta, uint64_t f_at,
                        uint64_t p_at, uint64_t r_at, bool trusted, bool *canonical);
+int index_compact_rows(glc_frames *F, uint32_t ch, uint64_t n_frames, uint64_t n_pairs, uint64_t n_raw_rows,
+                       const uint8_t *israw, const float *scale, const uint32_t *cnt, uint64_t f_at, uint64_t p_at,
+                       uint64_t r_at, bool trusted, bool *canonical);
 int frames_from_compact(uint32_t sample_rate, uint64_t n_samples, uint16_t channels, const void *const *blobs,
                         const uint64_t *blob_bytes, uint32_t n_blobs, bool trusted, glc_frames **out);
 

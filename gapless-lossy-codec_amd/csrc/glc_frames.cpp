@@ -109,12 +109,19 @@ const char *compact_header_error(const CompactHeader &h, uint32_t ch, uint64_t n
 int index_compact_meta(glc_frames *F, uint32_t ch, const CompactHeader &h, const uint8_t *meta, uint64_t f_at,
                        uint64_t p_at, uint64_t r_at, bool trusted, bool *canonical) {
   const CompactLayout l = compact_layout(ch, h.n_frames);
-  const uint8_t *israw = meta + l.o_israw;
-  const float *scale = reinterpret_cast<const float *>(meta + l.o_scale);
-  const uint32_t *cnt = reinterpret_cast<const uint32_t *>(meta + l.o_cnt);
+  return index_compact_rows(F, ch, h.n_frames, h.n_pairs, h.n_raw_rows, meta + l.o_israw,
+                            reinterpret_cast<const float *>(meta + l.o_scale),
+                            reinterpret_cast<const uint32_t *>(meta + l.o_cnt), f_at, p_at, r_at, trusted, canonical);
+}
+
+// ... from the three per-frame / per-row sections themselves: `n_frames` frames that hold `n_pairs` pairs
+// and `n_raw_rows` raw rows (a whole blob, or one clip's frames inside the blob of a batch round)
+int index_compact_rows(glc_frames *F, uint32_t ch, uint64_t n_frames, uint64_t n_pairs, uint64_t n_raw_rows,
+                       const uint8_t *israw, const float *scale, const uint32_t *cnt, uint64_t f_at, uint64_t p_at,
+                       uint64_t r_at, bool trusted, bool *canonical) {
   const uint32_t *pairs = F->pairs.data() + p_at;
   uint64_t p_in = 0, raw_rows_in = 0;
-  for (uint64_t f = 0; f < h.n_frames; ++f) {
+  for (uint64_t f = 0; f < n_frames; ++f) {
     const uint64_t fo = f_at + f;
     F->raw_tag[fo] = israw[f] ? 1 : 0;
     if (israw[f]) {
@@ -127,7 +134,7 @@ int index_compact_meta(glc_frames *F, uint32_t ch, const CompactHeader &h, const
     } else {
       for (uint32_t c = 0; c < ch; ++c) {
         const uint32_t n = cnt[f * ch + c];
-        if (n > kHop || p_in + n > h.n_pairs) {
+        if (n > kHop || p_in + n > n_pairs) {
           set_global_error("glc_frames_from_compact: corrupt blob (row counts exceed the pair pool)");
           return GLC_EFORMAT;
         }
@@ -151,7 +158,7 @@ int index_compact_meta(glc_frames *F, uint32_t ch, const CompactHeader &h, const
     F->scale_begin[fo + 1] = F->scales.size();
     F->raw_begin[fo + 1] = r_at + raw_rows_in * kFrame;
   }
-  if (p_in != h.n_pairs || raw_rows_in != h.n_raw_rows) {
+  if (p_in != n_pairs || raw_rows_in != n_raw_rows) {
     set_global_error("glc_frames_from_compact: corrupt blob (section totals disagree with the header)");
     return GLC_EFORMAT;
   }

@@ -50,6 +50,20 @@ hipError_t launch_compact(const uint8_t *records, uint32_t M, uint32_t ch, uint6
                           uint64_t *blk, uint64_t *blk_raw, uint64_t *totals, uint8_t *blob, uint64_t o_israw,
                           uint64_t o_scale, uint64_t o_cnt, uint64_t o_pairs, hipStream_t s);
 
+// P1-P3 over the real frames of a round of glc_encode_batch: row m is channel m % ch of real frame
+// m / ch, whose record is number fmap[m / ch].slot among `records` (the virtual stream's frames, junk
+// ones included - those are in no map and nothing of them reaches the blob).  Same sections at the
+// caller's offsets as launch_compact; dir[2 * i], dir[2 * i + 1]: pairs and raw rows the blob holds in
+// front of clip i, for every clip named in a FrameMap::clip.
+struct FrameMap {
+  uint32_t slot;  // record index of this real frame
+  uint32_t clip;  // the clip whose first frame this is, or 0xFFFFFFFF
+};
+hipError_t launch_compact_batch(const uint8_t *records, uint32_t M, uint32_t ch, uint64_t n_frames, const FrameMap *fmap,
+                                uint64_t *dir, uint32_t *loc, uint64_t *blk, uint64_t *blk_raw, uint64_t *totals,
+                                uint8_t *blob, uint64_t o_israw, uint64_t o_scale, uint64_t o_cnt, uint64_t o_pairs,
+                                hipStream_t s);
+
 // D1: sparse dequant + inverse MDCT + window -> blocks[row][2048].
 //   pairs: packed (u16 idx | i16 q << 16), canonical (ascending, unique, idx < 1024)
 //   row_begin[M] / row_cnt[M]: pair range of a row; row_scale[M]; row_raw[M]: -1 or offset (in
@@ -80,6 +94,17 @@ hipError_t launch_imdct_rows(const DeviceTables &t, const DecodeRows &rows, uint
 hipError_t launch_overlap_add(const float *blocks, int64_t blk_frame0, uint64_t n_frames,
                               uint32_t ch, uint64_t hop_begin, uint64_t hop_end, float *out,
                               hipStream_t s);
+
+// D2 of a batch of streams whose frames sit back to back in `blocks`: one descriptor per kept output
+// hop.  out[dst .. dst + cnt) = interleaved samples [first, first + cnt) of the hop made of the second
+// half of block slot `prev` (-1: +0.0, a stream's first hop) and the first half of slot `cur` (-1: none,
+// the bare tail).  `out` is 16-byte aligned, dst is not bound to any alignment.
+struct HopDesc {
+  int32_t prev, cur;
+  uint32_t dst, first, cnt, pad;
+};
+hipError_t launch_overlap_add_batch(const float *blocks, const HopDesc *desc, uint32_t n_desc, uint32_t ch, float *out,
+                                    hipStream_t s);
 
 // D2 with the narrowing of the reference's 16-bit writers on the way out: the same sums, then
 // `(v * 32767.0).clamp(-32768.0, 32767.0) as i16` (NaN -> 0, truncation) - `out` is any 2-byte aligned pointer.

@@ -828,6 +828,55 @@ __global__ __launch_bounds__(256) void k_overlap_add(const float *__restrict__ b
   }
 }
 
+// D2 of a batch of streams (glc_decode_batch): one workgroup row per KEPT output hop, described by a
+// HopDesc - the block slots of the frame before (second half) and of the frame itself (first half),
+// either of which may be absent (-1: the first hop of a stream starts from +0.0, its last hop is the
+// bare tail), and the span [first, first + cnt) of the hop's interleaved samples that survives the
+// stream's gapless trim, which lands at out[dst ..).  dst is any sample index, so the threads are laid
+// over the DESTINATION: chunk k of a hop is the four floats at (dst & ~3) + 4k, 16-byte aligned when `out`
+// is, and goes out as one float4; only the first and the last chunk of a cut span can be partial, and
+// those store float by float.  Same sums as k_overlap_add.
+template <int CH>
+__global__ __launch_bounds__(256) void k_overlap_add_batch(const float *__restrict__ blocks,
+                                                            const HopDesc *__restrict__ desc, unsigned ch,
+                                                            float *__restrict__ out) {
+  const HopDesc d = desc[blockIdx.y];
+  const unsigned lead = d.dst & 3u;
+  const unsigned n_chunks = (lead + d.cnt + 3u) >> 2;
+  const bool has_prev = d.prev >= 0, has_cur = d.cur >= 0;
+  const float *prev = blocks + (static_cast<size_t>(has_prev ? d.prev : 0) * ch) * kFrameI + kHopI;
+  const float *cur = blocks + (static_cast<size_t>(has_cur ? d.cur : 0) * ch) * kFrameI;
+  float *base = out + (d.dst - lead);
+  for (unsigned k = blockIdx.x * 256u + threadIdx.x; k < n_chunks; k += gridDim.x * 256u) {
+    const int j0 = static_cast<int>(4u * k) - static_cast<int>(lead);  // first of the chunk, counted from the span's start
+    float v[4];
+    bool keep[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int j = j0 + e;
+      keep[e] = j >= 0 && static_cast<unsigned>(j) < d.cnt;
+      const unsigned o = d.first + static_cast<unsigned>(keep[e] ? j : 0);
+      unsigned i, c;
+      if constexpr (CH == 1) i = o, c = 0;
+      else if constexpr (CH == 2) i = o >> 1, c = o & 1u;
+      else if constexpr (CH == 4) i = o >> 2, c = o & 3u;
+      else if constexpr (CH == 8) i = o >> 3, c = o & 7u;
+      else i = o / ch, c = o - i * ch;
+      const size_t at = static_cast<size_t>(c) * kFrameI + i;
+      const float p = has_prev ? prev[at] : 0.0f;  // overlap starts as +0.0, :601
+      v[e] = has_cur ? add_rn(p, cur[at]) : p;      // :695 / the bare tail, :727
+    }
+    float *dst = base + 4u * static_cast<size_t>(k);
+    if (keep[0] && keep[3]) {
+      *reinterpret_cast<float4 *>(dst) = float4{v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (keep[e]) dst[e] = v[e];
+    }
+  }
+}
+
 // D2 writing 16-bit PCM: the same sums, then convert_f32_to_i16 of the reference's writers
 // (`(s * 32767.0).clamp(-32768.0, 32767.0) as i16`, src/audio.rs:11-16) on the way out, so that the
 // host boundary of a decode moves 2 bytes per sample.  Four samples per thread as in k_overlap_add,
@@ -914,13 +963,19 @@ __global__ __launch_bounds__(256) void k_pcm_widen(const S *__restrict__ in, flo
 //   P3  one wave per row: ballot + popcount prefix keeps ascending k (src/codec.rs:303-306);
 //       planes of raw-frame rows go to the raw section, which starts behind the pairs
 // ------------------------------------------------------------------------------------------
+// SEG (glc_encode_batch): row m belongs to frame m / ch of the round's REAL frames, whose record is number
+// fmap[frame].x of the virtual stream's records - the junk frame behind every clip is in no one's map,
+// so nothing of it is counted, packed or sent.  fmap[frame].y is the clip that starts at this frame
+// (~0u: none): P3 leaves that clip's first pair and first raw row in dir[2 * clip], dir[2 * clip + 1].
+template <bool SEG>
 __global__ __launch_bounds__(256) void k_pack_scan_rows(const unsigned char *__restrict__ records, unsigned M,
                                                          unsigned ch, unsigned long long rec_bytes,
                                                          unsigned *__restrict__ loc,
                                                          unsigned long long *__restrict__ blk,
                                                          unsigned long long *__restrict__ blk_raw,
                                                          float *__restrict__ scales, unsigned *__restrict__ cnt,
-                                                         unsigned char *__restrict__ is_raw) {
+                                                         unsigned char *__restrict__ is_raw,
+                                                         const uint2 *__restrict__ fmap) {
   // one 32-bit word scans both counts: low 21 bits = pairs (<= 1024*1024 per block), high 11 =
   // rows of raw frames (<= 1024 per block)
   __shared__ unsigned s_part[256];
@@ -932,7 +987,8 @@ __global__ __launch_bounds__(256) void k_pack_scan_rows(const unsigned char *__r
     unsigned n = 0;
     if (m < M) {
       const unsigned frame = m / ch, c = m % ch;
-      const unsigned char *rec = records + static_cast<size_t>(frame) * rec_bytes;
+      const unsigned slot = SEG ? fmap[frame].x : frame;
+      const unsigned char *rec = records + static_cast<size_t>(slot) * rec_bytes;
       const unsigned raw = *reinterpret_cast<const unsigned *>(rec);
       const unsigned nnz = min(*reinterpret_cast<const unsigned *>(rec + 8 + 8 * c + 4), static_cast<unsigned>(kHopI));
       n = raw ? (1u << 21) : nnz;
@@ -1009,6 +1065,7 @@ __global__ __launch_bounds__(1024) void k_pack_scan_blocks(unsigned long long *_
   if (threadIdx.x < 64 && pairs_end + threadIdx.x < raw_off) blob[pairs_end + threadIdx.x] = 0;  // deterministic padding
 }
 
+template <bool SEG>
 __global__ __launch_bounds__(256) void k_pack_rows(const unsigned char *__restrict__ records, unsigned M,
                                                     unsigned ch, unsigned long long rec_bytes,
                                                     unsigned long long hdr_bytes, const unsigned *__restrict__ loc,
@@ -1016,14 +1073,24 @@ __global__ __launch_bounds__(256) void k_pack_rows(const unsigned char *__restri
                                                     const unsigned long long *__restrict__ blk_raw,
                                                     const unsigned long long *__restrict__ totals,
                                                     const unsigned *__restrict__ cnt, unsigned long long o_pairs,
-                                                    unsigned char *__restrict__ blob) {
+                                                    unsigned char *__restrict__ blob, const uint2 *__restrict__ fmap,
+                                                    unsigned long long *__restrict__ dir) {
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const unsigned m = blockIdx.x * 4 + w;
   if (m >= M) return;
   const unsigned l = loc[m];
   const unsigned long long off = blk[m >> 10] + (l & 0x1FFFFFu);
   const unsigned frame = m / ch, c = m % ch;
-  const unsigned char *rec = records + static_cast<size_t>(frame) * rec_bytes;
+  unsigned slot = frame;
+  if constexpr (SEG) {
+    const uint2 fm = fmap[frame];
+    slot = fm.x;
+    if (c == 0 && lane == 0 && fm.y != ~0u) {  // a clip starts here: what the round holds in front of it
+      dir[2ull * fm.y] = off;
+      dir[2ull * fm.y + 1] = blk_raw[m >> 10] + (l >> 21);
+    }
+  }
+  const unsigned char *rec = records + static_cast<size_t>(slot) * rec_bytes;
   const short *qrow = reinterpret_cast<const short *>(rec + hdr_bytes) + static_cast<size_t>(c) * kFrameI;
   if (*reinterpret_cast<const unsigned *>(rec)) {
     // row of a raw frame: its 2048-sample plane goes to the raw section (planar order == row order, Q1)
@@ -1174,9 +1241,12 @@ hipError_t launch_decide_raw(const DeviceTables &t, const PcmView &pcm, uint64_t
   return hipGetLastError();
 }
 
-hipError_t launch_compact(const uint8_t *records, uint32_t M, uint32_t ch, uint64_t n_frames, uint32_t *loc,
-                          uint64_t *blk, uint64_t *blk_raw, uint64_t *totals, uint8_t *blob, uint64_t o_israw,
-                          uint64_t o_scale, uint64_t o_cnt, uint64_t o_pairs, hipStream_t s) {
+namespace {
+// P1-P3 of M rows; fmap / dir: the segment-aware form (launch_compact_batch), else nullptr
+hipError_t compact_rows(const uint8_t *records, uint32_t M, uint32_t ch, uint64_t n_frames, uint32_t *loc,
+                        uint64_t *blk, uint64_t *blk_raw, uint64_t *totals, uint8_t *blob, uint64_t o_israw,
+                        uint64_t o_scale, uint64_t o_cnt, uint64_t o_pairs, const uint2 *fmap, unsigned long long *dir,
+                        hipStream_t s) {
   auto *t = reinterpret_cast<unsigned long long *>(totals);
   if (M == 0) {  // an empty range: the scans are over nothing, the header says so
     hipLaunchKernelGGL(k_pack_scan_blocks, dim3(1), dim3(1024), 0, s, reinterpret_cast<unsigned long long *>(blk),
@@ -1187,14 +1257,41 @@ hipError_t launch_compact(const uint8_t *records, uint32_t M, uint32_t ch, uint6
   const unsigned nblk = (M + 1023) / 1024;
   auto *b = reinterpret_cast<unsigned long long *>(blk);
   auto *br = reinterpret_cast<unsigned long long *>(blk_raw);
-  hipLaunchKernelGGL(k_pack_scan_rows, dim3(nblk), dim3(256), 0, s, records, M, ch, rec, loc, b, br,
-                     reinterpret_cast<float *>(blob + o_scale), reinterpret_cast<unsigned *>(blob + o_cnt),
-                     blob + o_israw);
+  float *scales = reinterpret_cast<float *>(blob + o_scale);
+  unsigned *cnt = reinterpret_cast<unsigned *>(blob + o_cnt);
+  if (fmap)
+    hipLaunchKernelGGL(k_pack_scan_rows<true>, dim3(nblk), dim3(256), 0, s, records, M, ch, rec, loc, b, br, scales, cnt,
+                       blob + o_israw, fmap);
+  else
+    hipLaunchKernelGGL(k_pack_scan_rows<false>, dim3(nblk), dim3(256), 0, s, records, M, ch, rec, loc, b, br, scales, cnt,
+                       blob + o_israw, fmap);
   hipLaunchKernelGGL(k_pack_scan_blocks, dim3(1), dim3(1024), 0, s, b, br, nblk, t, ch, static_cast<unsigned long long>(n_frames),
                      static_cast<unsigned long long>(o_pairs), blob);
-  hipLaunchKernelGGL(k_pack_rows, dim3((M + 3) / 4), dim3(256), 0, s, records, M, ch, rec, hdr, loc, b, br, t,
-                     reinterpret_cast<const unsigned *>(blob + o_cnt), static_cast<unsigned long long>(o_pairs), blob);
+  if (fmap)
+    hipLaunchKernelGGL(k_pack_rows<true>, dim3((M + 3) / 4), dim3(256), 0, s, records, M, ch, rec, hdr, loc, b, br, t, cnt,
+                       static_cast<unsigned long long>(o_pairs), blob, fmap, dir);
+  else
+    hipLaunchKernelGGL(k_pack_rows<false>, dim3((M + 3) / 4), dim3(256), 0, s, records, M, ch, rec, hdr, loc, b, br, t, cnt,
+                       static_cast<unsigned long long>(o_pairs), blob, fmap, dir);
   return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_compact(const uint8_t *records, uint32_t M, uint32_t ch, uint64_t n_frames, uint32_t *loc,
+                          uint64_t *blk, uint64_t *blk_raw, uint64_t *totals, uint8_t *blob, uint64_t o_israw,
+                          uint64_t o_scale, uint64_t o_cnt, uint64_t o_pairs, hipStream_t s) {
+  return compact_rows(records, M, ch, n_frames, loc, blk, blk_raw, totals, blob, o_israw, o_scale, o_cnt, o_pairs, nullptr,
+                      nullptr, s);
+}
+
+hipError_t launch_compact_batch(const uint8_t *records, uint32_t M, uint32_t ch, uint64_t n_frames, const FrameMap *fmap,
+                                uint64_t *dir, uint32_t *loc, uint64_t *blk, uint64_t *blk_raw, uint64_t *totals,
+                                uint8_t *blob, uint64_t o_israw, uint64_t o_scale, uint64_t o_cnt, uint64_t o_pairs,
+                                hipStream_t s) {
+  if (!fmap || !dir) return hipErrorInvalidValue;
+  static_assert(sizeof(FrameMap) == sizeof(uint2), "FrameMap is read as a uint2");
+  return compact_rows(records, M, ch, n_frames, loc, blk, blk_raw, totals, blob, o_israw, o_scale, o_cnt, o_pairs,
+                      reinterpret_cast<const uint2 *>(fmap), reinterpret_cast<unsigned long long *>(dir), s);
 }
 
 uint64_t imdct_plan_bytes(uint32_t groups) {
@@ -1270,6 +1367,27 @@ hipError_t launch_overlap_add(const float *blocks, int64_t blk_frame0, uint64_t 
       case 4: hipLaunchKernelGGL((k_overlap_add<4, true>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o); break;
       case 8: hipLaunchKernelGGL((k_overlap_add<8, true>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o); break;
       default: hipLaunchKernelGGL((k_overlap_add<0, true>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o); break;
+    }
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_overlap_add_batch(const float *blocks, const HopDesc *desc, uint32_t n_desc, uint32_t ch, float *out,
+                                    hipStream_t s) {
+  if (n_desc == 0) return hipSuccess;
+  if (reinterpret_cast<uintptr_t>(out) & 15u) return hipErrorInvalidValue;  // the float4 chunks are laid over `out`
+  const unsigned per_hop = 1024u * ch;
+  const unsigned bx = (per_hop / 4u + 255u) / 256u;  // a span that starts off a 16-byte boundary has one chunk more: the stride loop's
+  for (uint32_t d0 = 0; d0 < n_desc; d0 += 32768) {  // slabs: blockIdx.y is 16 bits wide
+    const unsigned nd = n_desc - d0 < 32768 ? n_desc - d0 : 32768;
+    const dim3 grid(bx, nd);
+    const HopDesc *d = desc + d0;
+    switch (ch) {
+      case 1: hipLaunchKernelGGL(k_overlap_add_batch<1>, grid, dim3(256), 0, s, blocks, d, ch, out); break;
+      case 2: hipLaunchKernelGGL(k_overlap_add_batch<2>, grid, dim3(256), 0, s, blocks, d, ch, out); break;
+      case 4: hipLaunchKernelGGL(k_overlap_add_batch<4>, grid, dim3(256), 0, s, blocks, d, ch, out); break;
+      case 8: hipLaunchKernelGGL(k_overlap_add_batch<8>, grid, dim3(256), 0, s, blocks, d, ch, out); break;
+      default: hipLaunchKernelGGL(k_overlap_add_batch<0>, grid, dim3(256), 0, s, blocks, d, ch, out); break;
     }
   }
   return hipGetLastError();

@@ -416,6 +416,28 @@ int glc_flac_encode_i16(const int16_t *samples, uint64_t n_samples, uint32_t sam
 int glc_flac_save_i16(const char *path, const int16_t *samples, uint64_t n_samples, uint32_t sample_rate,
                       uint16_t channels, uint8_t level);
 
+/* ---- batches of short clips ------------------------------------------------------------ */
+
+/* Encoder::encode of n_clips independent streams of `channels` channels at the context's sample rate
+ * in one call: whole clips are packed into rounds of one launch chain each, instead of one chain, one
+ * upload and one download per clip.  out[i] receives an owned glc_frames, byte-identical
+ * (glc_serialize) to what glc_encode returns for clip i alone.  n_clips == 0 is GLC_OK.  A clip that
+ * glc_encode refuses (glc_plan_encode gives it 0 frames; a null pointer) or channels == 0 fails the
+ * whole call with GLC_EINVAL - the message names the clip - and leaves every out[i] NULL. */
+int glc_encode_batch(glc_ctx *ctx, const float *const *pcm, const uint64_t *n_samples, uint64_t n_clips,
+                     uint16_t channels, glc_frames **out);
+
+/* Decoder::decode of n_streams streams into ONE packed buffer: stream i's trimmed samples are
+ * pcm_out[offsets[i] .. offsets[i+1]), bit-identical to glc_decode of it alone; offsets has
+ * n_streams + 1 entries, offsets[0] == 0, and is filled whenever the arguments are non-null (the
+ * running sums of glc_decoded_len), so cap == 0 sizes the buffer: GLC_EINVAL "output buffer too small".
+ * Nothing behind offsets[n_streams] is written.  All streams must have the same header.channels
+ * (GLC_EINVAL); their sample rates may differ.  A malformed stream fails the whole call (GLC_EFORMAT).
+ * Afterwards no stream is resident on the context (glc_ctx_resident_stream is 0) and an open
+ * glc_decode_stream_* session is closed.  n_streams == 0 is GLC_OK. */
+int glc_decode_batch(glc_ctx *ctx, const glc_frames *const *in, uint64_t n_streams, float *pcm_out, uint64_t cap,
+                     uint64_t *offsets);
+
 /* ---- tables (for inspection / parity tests) ---------------------------------------------- */
 
 /* Copies of the host tables of a context: MdctTables.cos_table [1024*2048] (row k), window

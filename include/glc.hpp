@@ -203,6 +203,18 @@ class Encoder {
     detail::check(glc_encode(ctx_, samples, n_samples, channels, &h), ctx_);
     return EncodedAudio(h);
   }
+  // glc_encode_batch: every clip an independent stream of `channels` channels, one call for all of them
+  std::vector<EncodedAudio> encode_batch(const std::vector<std::vector<float>> &clips, uint16_t channels) {
+    std::vector<const float *> pcm(clips.size());
+    std::vector<uint64_t> n(clips.size());
+    for (size_t i = 0; i < clips.size(); ++i) pcm[i] = clips[i].data(), n[i] = clips[i].size();
+    std::vector<glc_frames *> h(clips.size(), nullptr);
+    detail::check(glc_encode_batch(ctx_, pcm.data(), n.data(), clips.size(), channels, h.data()), ctx_);
+    std::vector<EncodedAudio> out;
+    out.reserve(h.size());
+    for (glc_frames *f : h) out.emplace_back(f);
+    return out;
+  }
   EncodedAudio encode(const std::vector<float> &samples, uint16_t channels) {
     return encode(samples.data(), samples.size(), channels);
   }
@@ -284,6 +296,16 @@ class Decoder {
   Decoder(const Decoder &) = delete;
   Decoder &operator=(const Decoder &) = delete;
   // decode(&mut self, &EncodedAudio, _) -> Result<Vec<f32>> — src/codec.rs:744
+  // glc_decode_batch: stream i's samples are packed[offsets[i] .. offsets[i + 1])
+  std::vector<float> decode_batch(const std::vector<const EncodedAudio *> &encoded, std::vector<uint64_t> &offsets) {
+    std::vector<const glc_frames *> h(encoded.size());
+    uint64_t total = 0;
+    for (size_t i = 0; i < encoded.size(); ++i) h[i] = encoded[i]->handle(), total += glc_decoded_len(h[i]);
+    offsets.assign(encoded.size() + 1, 0);
+    std::vector<float> packed(total);
+    detail::check(glc_decode_batch(ctx_, h.data(), h.size(), packed.data(), packed.size(), offsets.data()), ctx_);
+    return packed;
+  }
   std::vector<float> decode(const EncodedAudio &encoded) {
     std::vector<float> out(glc_decoded_len(encoded.handle()));
     uint64_t n = 0;

@@ -1,0 +1,165 @@
+// batch_bench.cpp — what one call for many clips saves: glc_encode_batch / glc_decode_batch against what a
+// caller does without them, a loop of glc_encode / glc_decode over the same clips on the same context.
+// Shapes: 64 clips like BASELINE config 1 (2 s, 44.1 kHz stereo, a tone per clip), 512 clips of 0.25 s,
+// and 4 clips of 60 s at 48 kHz (the case that must not get worse).  One process, one context per
+// direction, the arms interleaved A B A' B after a warm-up, so that clocks, buffers and neighbours on the
+// host are the same for both; A' is the loop again and the difference of the two loop medians is the
+// run's own A/A spread.  Every batch result is compared with the loop's before anything is timed.
+// C ABI only.  Build: make -C gapless-lossy-codec_amd/csrc tools
+// Usage: build/batch_bench [reps = 30]                          the three shapes
+//        build/batch_bench reps n_clips seconds sample_rate     one shape of the caller's
+//        build/batch_bench trace n_clips seconds                10 encode + 10 decode batch calls and nothing
+//                                                               else after the warm-up (for a kernel trace)
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "glc.h"
+
+static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+struct Stat {
+  double med, p10, p90;
+};
+static Stat stat(std::vector<double> v) {
+  std::sort(v.begin(), v.end());
+  return {v[v.size() / 2], v[v.size() / 10], v[v.size() * 9 / 10]};
+}
+
+#define CHECK(call)                                                                     \
+  do {                                                                                  \
+    if ((call) != GLC_OK) {                                                             \
+      std::printf("%s failed: %s\n", #call, glc_last_error(nullptr));                   \
+      return 1;                                                                         \
+    }                                                                                   \
+  } while (0)
+
+static int serialize(const glc_frames *F, std::vector<uint8_t> &out) {
+  out.resize(glc_serialized_size(F));
+  uint64_t w = 0;
+  return glc_serialize(F, out.data(), out.size(), &w);
+}
+
+static int run(const char *name, uint32_t sr, uint64_t n_clips, double seconds, int reps, bool trace) {
+  const uint16_t ch = 2;
+  const uint64_t per_ch = static_cast<uint64_t>(seconds * sr), n = per_ch * ch;
+  std::vector<std::vector<float>> clips(n_clips, std::vector<float>(n));
+  for (uint64_t k = 0; k < n_clips; ++k) {  // a different tone per clip, a fifth apart between the channels
+    const double f0 = 110.0 * std::pow(2.0, static_cast<double>(k % 48) / 12.0);
+    for (uint64_t t = 0; t < per_ch; ++t) {
+      clips[k][t * 2] = static_cast<float>(0.5 * std::sin(2 * M_PI * f0 * t / sr));
+      clips[k][t * 2 + 1] = static_cast<float>(0.4 * std::sin(2 * M_PI * 1.5 * f0 * t / sr + 0.3));
+    }
+  }
+  std::vector<const float *> pcm(n_clips);
+  std::vector<uint64_t> lens(n_clips, n);
+  for (uint64_t k = 0; k < n_clips; ++k) pcm[k] = clips[k].data();
+
+  glc_ctx *enc = nullptr, *dec = nullptr;
+  CHECK(glc_ctx_create(0, sr, &enc));
+  CHECK(glc_ctx_create(0, sr, &dec));
+  std::vector<glc_frames *> one(n_clips, nullptr), all(n_clips, nullptr);
+  auto free_all = [&](std::vector<glc_frames *> &v) {
+    for (glc_frames *&f : v) glc_frames_free(f), f = nullptr;
+  };
+  auto enc_loop = [&] {
+    for (uint64_t k = 0; k < n_clips; ++k)
+      if (const int rc = glc_encode(enc, pcm[k], n, ch, &one[k])) return rc;
+    return 0;
+  };
+  auto enc_batch = [&] { return glc_encode_batch(enc, pcm.data(), lens.data(), n_clips, ch, all.data()); };
+  if (!trace) CHECK(enc_loop());
+  CHECK(enc_batch());
+  if (trace) one.swap(all);  // nothing but batch calls in a trace: the decode arm reads the batch's own streams
+  std::vector<uint8_t> ba, bb;
+  for (uint64_t k = 0; k < n_clips && !trace; ++k) {
+    CHECK(serialize(one[k], ba));
+    CHECK(serialize(all[k], bb));
+    if (ba != bb) return std::printf("%s: clip %llu: glc_encode_batch and glc_encode give different streams\n", name, (unsigned long long)k), 1;
+  }
+  free_all(all);
+  // decode: the streams of the loop's encode, into one packed buffer either way
+  std::vector<uint64_t> off(n_clips + 1, 0), off_b(n_clips + 1, 0);
+  for (uint64_t k = 0; k < n_clips; ++k) off[k + 1] = off[k] + glc_decoded_len(one[k]);
+  std::vector<float> da(off[n_clips]), db(off[n_clips]);
+  auto dec_loop = [&] {
+    uint64_t got = 0;
+    for (uint64_t k = 0; k < n_clips; ++k)
+      if (const int rc = glc_decode(dec, one[k], da.data() + off[k], off[k + 1] - off[k], &got)) return rc;
+    return 0;
+  };
+  auto dec_batch = [&] { return glc_decode_batch(dec, one.data(), n_clips, db.data(), db.size(), off_b.data()); };
+  if (!trace) CHECK(dec_loop());
+  CHECK(dec_batch());
+  if (!trace && (off != off_b || std::memcmp(da.data(), db.data(), da.size() * sizeof(float))))
+    return std::printf("%s: glc_decode_batch differs from the loop of glc_decode\n", name), 1;
+
+  std::vector<glc_frames *> keep;  // the decode arms read these
+  keep.swap(one);
+  one.assign(n_clips, nullptr);
+  auto enc_a = [&] { const int rc = enc_loop(); free_all(one); return rc; };
+  auto enc_b = [&] { const int rc = enc_batch(); free_all(all); return rc; };
+  auto dec_a = [&] {
+    uint64_t got = 0;
+    for (uint64_t k = 0; k < n_clips; ++k)
+      if (const int rc = glc_decode(dec, keep[k], da.data() + off[k], off[k + 1] - off[k], &got)) return rc;
+    return 0;
+  };
+  auto dec_b = [&] { return glc_decode_batch(dec, keep.data(), n_clips, db.data(), db.size(), off_b.data()); };
+  auto timed = [&](auto &&fn, std::vector<double> &into) {
+    const double t0 = now_ms();
+    const int rc = fn();
+    into.push_back(now_ms() - t0);
+    return rc;
+  };
+  const int warm = trace ? 3 : std::max(3, reps / 5);
+  for (int i = 0; i < warm; ++i) {  // warm: clocks, staging buffers, helper threads, both code paths
+    if (!trace) { CHECK(enc_a()); CHECK(dec_a()); }
+    CHECK(enc_b()); CHECK(dec_b());
+  }
+  if (trace) {
+    for (int i = 0; i < 10; ++i) { CHECK(enc_b()); CHECK(dec_b()); }
+    std::printf("%s: 1 + %d warm-up + 10 batch calls each way, %llu clips of %llu samples x %u ch\n", name, warm,
+                (unsigned long long)n_clips, (unsigned long long)per_ch, ch);
+  } else {
+    std::vector<double> ea, eb, ea2, da1, db1, da2;
+    for (int i = 0; i < reps; ++i) {
+      CHECK(timed(enc_a, ea)); CHECK(timed(enc_b, eb)); CHECK(timed(enc_a, ea2)); CHECK(timed(enc_b, eb));
+    }
+    for (int i = 0; i < reps; ++i) {
+      CHECK(timed(dec_a, da1)); CHECK(timed(dec_b, db1)); CHECK(timed(dec_a, da2)); CHECK(timed(dec_b, db1));
+    }
+    const Stat A = stat(ea), B = stat(eb), A2 = stat(ea2), D = stat(da1), E = stat(db1), D2 = stat(da2);
+    const double es = std::fabs(A.med - A2.med), ds = std::fabs(D.med - D2.med);
+    auto verdict = [](double batch, double a, double a2, double spread) {
+      return batch < std::min(a, a2) - spread ? "FASTER" : batch <= std::max(a, a2) + spread ? "not slower" : "SLOWER";
+    };
+    std::printf("%s: %llu clips of %llu samples x %u ch, %d interleaved reps (ms per batch: median [p10 .. p90])\n", name,
+                (unsigned long long)n_clips, (unsigned long long)per_ch, ch, reps);
+    std::printf("  loop of glc_encode   %.4f [%.4f .. %.4f]   again %.4f   A/A spread %.4f\n", A.med, A.p10, A.p90, A2.med, es);
+    std::printf("  glc_encode_batch     %.4f [%.4f .. %.4f]   batch - loop %+.4f   loop / batch %.2f  -> %s\n", B.med, B.p10, B.p90,
+                B.med - std::min(A.med, A2.med), std::min(A.med, A2.med) / B.med, verdict(B.med, A.med, A2.med, es));
+    std::printf("  loop of glc_decode   %.4f [%.4f .. %.4f]   again %.4f   A/A spread %.4f\n", D.med, D.p10, D.p90, D2.med, ds);
+    std::printf("  glc_decode_batch     %.4f [%.4f .. %.4f]   batch - loop %+.4f   loop / batch %.2f  -> %s\n", E.med, E.p10, E.p90,
+                E.med - std::min(D.med, D2.med), std::min(D.med, D2.med) / E.med, verdict(E.med, D.med, D2.med, ds));
+  }
+  free_all(keep);
+  glc_ctx_destroy(enc);
+  glc_ctx_destroy(dec);
+  return 0;
+}
+
+int main(int argc, char **argv) {
+  if (argc > 3 && !std::strcmp(argv[1], "trace"))
+    return run("trace", 44100, std::strtoull(argv[2], nullptr, 10), std::atof(argv[3]), 0, true);
+  const int reps = argc > 1 ? std::max(5, std::atoi(argv[1])) : 30;
+  if (argc > 4) return run("custom", std::atoi(argv[4]), std::strtoull(argv[2], nullptr, 10), std::atof(argv[3]), reps, false);
+  if (run("64 clips like config 1 (2 s, 44.1 kHz stereo)", 44100, 64, 2.0, reps, false)) return 1;
+  if (run("512 clips of 0.25 s (44.1 kHz stereo)", 44100, 512, 0.25, reps, false)) return 1;
+  if (run("4 clips of 60 s (48 kHz stereo)", 48000, 4, 60.0, std::max(5, reps / 3), false)) return 1;
+  return 0;
+}

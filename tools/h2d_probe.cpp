@@ -2,6 +2,8 @@
 // Decides the staging strategy of glc_encode / glc_decode: plain hipMemcpy from pageable
 // memory, hipHostRegister + async copy + unregister, or a copy through a pinned ring.
 // Build: hipcc -O2 tools/h2d_probe.cpp -o build/h2d_probe        Usage: build/h2d_probe [MiB = 32]
+//        build/h2d_probe clips N KiB    the staging of glc_encode_batch: N pageable clips of KiB each, one copy per
+//                                       clip straight into its slot against packing them on the host + one copy
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,7 +27,47 @@ static double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+// N clips of `bytes` each, every one a buffer of its own (as a caller's files are), to N slots of one
+// device buffer: per-clip copies from pageable memory, or memcpy into one pinned image and one copy.
+static int clips_mode(size_t n_clips, size_t bytes) {
+  const size_t slot = (bytes + 4095) / 4096 * 4096 + 4096, total = n_clips * slot;
+  void *d = nullptr, *pin = nullptr;
+  OK(hipMalloc(&d, total));
+  OK(hipHostMalloc(&pin, total, hipHostMallocDefault));
+  std::memset(pin, 0, total);
+  std::vector<std::vector<char>> clips(n_clips);
+  for (size_t i = 0; i < n_clips; ++i) clips[i].assign(bytes, static_cast<char>(i + 1));
+  hipStream_t s;
+  OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  auto median = [&](const char *name, auto fn) {
+    std::vector<double> t;
+    for (int i = 0; i < 15; ++i) {
+      const double t0 = now_ms();
+      fn();
+      t.push_back(now_ms() - t0);
+    }
+    std::sort(t.begin(), t.end());
+    std::printf("%-62s %8.3f ms [%.3f .. %.3f]\n", name, t[7], t[1], t[13]);
+  };
+  std::printf("%zu clips of %zu KiB (%.1f MB)\n", n_clips, bytes >> 10, n_clips * bytes / 1e6);
+  for (int rep = 0; rep < 2; ++rep) {  // twice: the second pass shows what order and warm pages do to the pair
+    median("one hipMemcpyAsync per clip from pageable + memset + sync", [&] {
+      OK(hipMemsetAsync(d, 0, total, s));
+      for (size_t i = 0; i < n_clips; ++i)
+        OK(hipMemcpyAsync(static_cast<char *>(d) + i * slot, clips[i].data(), bytes, hipMemcpyHostToDevice, s));
+      OK(hipStreamSynchronize(s));
+    });
+    median("memcpy per clip into a pinned image + one copy + sync", [&] {
+      for (size_t i = 0; i < n_clips; ++i) std::memcpy(static_cast<char *>(pin) + i * slot, clips[i].data(), bytes);
+      OK(hipMemcpyAsync(d, pin, total, hipMemcpyHostToDevice, s));
+      OK(hipStreamSynchronize(s));
+    });
+  }
+  return 0;
+}
+
 int main(int argc, char **argv) {
+  if (argc > 3 && !std::strcmp(argv[1], "clips")) return clips_mode(std::atoi(argv[2]), static_cast<size_t>(std::atoi(argv[3])) << 10);
   const size_t mib = argc > 1 ? std::atoi(argv[1]) : 32;
   const size_t n = mib << 20;
   void *d = nullptr;
