@@ -178,6 +178,9 @@ SIGNATURES = {
     "glc_flac_save_i16": (C.c_int, [C.c_char_p, _vp, C.c_uint64, C.c_uint32, C.c_uint16, C.c_uint8]),
     "glc_encode_batch": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64), C.c_uint64, C.c_uint16, C.POINTER(_vp)]),
     "glc_decode_batch": (C.c_int, [_vp, C.POINTER(_vp), C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "glc_encode_batch_int": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint16,
+                                       C.POINTER(_vp)]),
+    "glc_decode_batch_i16": (C.c_int, [_vp, C.POINTER(_vp), C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "glc_version": (C.c_char_p, []),
 }
 

@@ -397,16 +397,32 @@ class Encoder(_Ctx):
                                      C.byref(out)), self._h)
         return EncodedAudio(out.value)
 
-    def encode_batch(self, clips, channels: int) -> list:
+    def encode_batch(self, clips, channels: int, bits: Optional[int] = None) -> list:
         """glc_encode_batch: Encoder::encode of every clip of `clips` (a sequence of float32 arrays, each an
         independent stream of `channels` channels) in one call; the i-th EncodedAudio holds the bytes
-        `encode(clips[i], channels)` gives.  Short clips share launch chains, uploads and downloads."""
-        pcm = [np.ascontiguousarray(c, np.float32).reshape(-1) for c in clips]
+        `encode(clips[i], channels)` gives.  Short clips share launch chains, uploads and downloads.
+        A sequence of int16 or of int32 arrays (of `bits` bits, as in encode) goes through
+        glc_encode_batch_int: the integers are uploaded and widened on the device.  One call has one sample
+        format: a sequence that mixes dtypes raises GlcError(GLC_EINVAL) before any device work."""
+        clips = list(clips)
+        int_dt = {np.dtype(c.dtype) for c in clips if getattr(c, "dtype", None) in (np.int16, np.int32)}
+        if not int_dt:
+            if bits is not None:
+                raise TypeError("bits applies to integer samples only")
+            pcm, fmt = [np.ascontiguousarray(c, np.float32).reshape(-1) for c in clips], GLC_PCM_F32
+        else:
+            got = [pcm_format(c, bits) for c in clips]  # TypeError for a dtype that is no PCM format at all
+            if len({f for _, f, _ in got}) != 1:
+                raise GlcError(GLC_EINVAL, "encode_batch: the clips of one call have one dtype (int16, int32 or float32)")
+            pcm, fmt, bits = [p for p, _, _ in got], got[0][1], got[0][2]
         n = len(pcm)
         ptrs = (C.c_void_p * max(n, 1))(*[p.ctypes.data for p in pcm])
         lens = (C.c_uint64 * max(n, 1))(*[p.size for p in pcm])
         outs = (C.c_void_p * max(n, 1))()
-        check(lib.glc_encode_batch(self._h, ptrs, lens, n, channels, outs), self._h)
+        if fmt == GLC_PCM_F32:
+            check(lib.glc_encode_batch(self._h, ptrs, lens, n, channels, outs), self._h)
+        else:
+            check(lib.glc_encode_batch_int(self._h, ptrs, fmt, bits, lens, n, channels, outs), self._h)
         return [EncodedAudio(outs[i]) for i in range(n)]
 
     def widen_device(self, d_in: int, dtype, bits: int, n: int, d_out: int) -> None:
@@ -515,20 +531,23 @@ class Decoder(_Ctx):
         check(fn(self._h, encoded._h, out.ctypes.data_as(C.c_void_p), n, C.byref(got)), self._h)
         return out[:got.value]
 
-    def decode_batch(self, encoded_list, out: Optional[np.ndarray] = None) -> list:
+    def decode_batch(self, encoded_list, out: Optional[np.ndarray] = None, dtype=np.float32) -> list:
         """glc_decode_batch: Decoder::decode of every stream of `encoded_list` (all of one channel count)
-        in one call.  Returns one float32 array per stream, views into ONE packed array - `out` when
-        given (C-contiguous float32, at least the sum of the streams' total_samples), as in decode."""
+        in one call.  Returns one array of `dtype` per stream, views into ONE packed array - `out` when
+        given (C-contiguous, of `dtype`, at least the sum of the streams' total_samples), as in decode.
+        dtype=np.int16: narrowed on the device as in decode (glc_decode_batch_i16)."""
+        dt = self._out_dtype(dtype)
         encs = list(encoded_list)
         n = len(encs)
         handles = (C.c_void_p * max(n, 1))(*[e._h for e in encs])
         offsets = (C.c_uint64 * (n + 1))()
         total = sum(int(lib.glc_decoded_len(e._h)) for e in encs)
         if out is None:
-            out = np.empty(total, np.float32)
-        elif out.dtype != np.float32 or not out.flags.c_contiguous or out.size < total:
-            raise GlcError(GLC_EINVAL, "out must be a C-contiguous float32 array of at least the streams' total_samples")
-        check(lib.glc_decode_batch(self._h, handles, n, out.ctypes.data_as(C.c_void_p), out.size, offsets), self._h)
+            out = np.empty(total, dt)
+        elif out.dtype != dt or not out.flags.c_contiguous or out.size < total:
+            raise GlcError(GLC_EINVAL, f"out must be a C-contiguous {dt} array of at least the streams' total_samples")
+        fn = lib.glc_decode_batch if dt == np.float32 else lib.glc_decode_batch_i16
+        check(fn(self._h, handles, n, out.ctypes.data_as(C.c_void_p), out.size, offsets), self._h)
         return [out[offsets[i]:offsets[i + 1]] for i in range(n)]
 
     def resident_stream(self) -> int:

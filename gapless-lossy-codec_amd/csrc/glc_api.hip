@@ -142,7 +142,7 @@ struct glc_ctx {
   DevBuf tables;     // all constant tables in one allocation
   DevBuf coef;       // MDCT coefficient workspace [rows][1024]
   DevBuf pcm;        // staging for host-boundary encode / decode output
-  DevBuf pcm_int;    // glc_encode_int: the integer samples as uploaded, widened into `pcm` on the device
+  DevBuf pcm_int;    // glc_encode_int / glc_encode_batch_int: the integer samples as uploaded, widened into `pcm` on the device
   DevBuf records;    // staging for host-boundary encode
   DevBuf blocks;     // decode: windowed IMDCT blocks [(chunk+1)][ch][2048]
   DevBuf dec_meta;   // decode: pairs / offsets / scales / raw pool
@@ -1083,9 +1083,16 @@ struct BatchClip {
 // padding (src/codec.rs:433-447), here in memory because the next clip follows.  Frame f of the clip
 // is virtual frame slot_i + f and reads nothing outside the clip's slot and the zeros in front of it;
 // virtual frame slot_i + nf_i straddles two clips and is junk: computed, in no frame map, never sent.
-int encode_batch_round(glc_ctx *ctx, const std::vector<BatchClip> &clips, const float *const *pcm, const uint64_t *n_samples,
-                       uint16_t channels, std::vector<std::unique_ptr<glc_frames>> &result) {
+// Integer clips (glc_encode_batch_int, fmt != GLC_PCM_F32): the same image in the clips' own element width -
+// memset, pinned image, uploads all hold the INTEGERS, in ctx->pcm_int - and ONE widening of the whole
+// virtual stream into ctx->pcm behind them.  Slots are whole multiples of 1024 * ch elements, so a slot
+// starts at the same element index in either width.
+int encode_batch_round(glc_ctx *ctx, const std::vector<BatchClip> &clips, const void *const *pcm, glc_pcm_format fmt,
+                       uint32_t bits, const uint64_t *n_samples, uint16_t channels,
+                       std::vector<std::unique_ptr<glc_frames>> &result) {
   const uint32_t ch = channels;
+  const bool is_int = fmt != GLC_PCM_F32;
+  const uint64_t elem = fmt == GLC_PCM_S16 ? 2 : 4;  // bytes per sample as uploaded
   const uint64_t n = clips.size();
   uint64_t V = 0, n_real = 0;  // frames of the virtual stream / of the clips
   for (const BatchClip &c : clips) V += c.plan.n_frames + 1, n_real += c.plan.n_frames;
@@ -1098,11 +1105,13 @@ int encode_batch_round(glc_ctx *ctx, const std::vector<BatchClip> &clips, const 
   const size_t scratch = compact_scratch_bytes(M), o_fmap_h = align_up(o_pairs, 256);
   GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // earlier work may still read the staging buffers
   GLC_HIP(ctx, ctx->pcm.reserve(static_cast<size_t>(n_virtual) * sizeof(float)));
+  if (is_int) GLC_HIP(ctx, ctx->pcm_int.reserve(static_cast<size_t>(n_virtual) * elem));
   GLC_HIP(ctx, ctx->records.reserve(static_cast<size_t>(V) * rec));
   GLC_HIP(ctx, ctx->pack_blob.reserve(bound));
   GLC_HIP(ctx, ctx->pack_meta.reserve(scratch + align_up(n_real * sizeof(glc::FrameMap), 256)));
   GLC_HIP(ctx, ctx->host_stage.reserve(o_fmap_h + n_real * sizeof(glc::FrameMap)));
   float *d_pcm = static_cast<float *>(ctx->pcm.p);
+  uint8_t *d_up = static_cast<uint8_t *>(is_int ? ctx->pcm_int.p : ctx->pcm.p);  // where the uploads land
   uint8_t *hm = static_cast<uint8_t *>(ctx->host_stage.p);
   uint8_t *mb = static_cast<uint8_t *>(ctx->pack_meta.p);
   uint8_t *d_blob = static_cast<uint8_t *>(ctx->pack_blob.p);
@@ -1113,28 +1122,29 @@ int encode_batch_round(glc_ctx *ctx, const std::vector<BatchClip> &clips, const 
   // the speed of the DMA (tools/h2d_probe.cpp `clips`: 64 x 689 KiB take 1.49 ms with a copy each against 2.07 packed,
   // 512 x 86 KiB 5.84 against 2.26): clips of at most kPackClipBytes are packed, slot by slot with their zeros, into
   // a pinned image that goes up in runs of kPackRunBytes (the next run is packed while one is in flight);
-  // longer clips go up on their own, straight from the caller's memory.
+  // longer clips go up on their own, straight from the caller's memory.  Both limits are bytes as they travel:
+  // a 16-bit clip is packed up to twice the samples of a float one.
   constexpr uint64_t kPackClipBytes = 256u << 10, kPackRunBytes = 4u << 20;
-  auto slot_bytes = [&](const BatchClip &c) { return (c.plan.n_frames + 1) * glc::kHop * ch * sizeof(float); };
+  auto slot_bytes = [&](const BatchClip &c) { return (c.plan.n_frames + 1) * glc::kHop * ch * elem; };
   uint64_t packed = 0;
   for (const BatchClip &c : clips)
-    if (n_samples[c.index] * sizeof(float) <= kPackClipBytes) packed += slot_bytes(c);
+    if (n_samples[c.index] * elem <= kPackClipBytes) packed += slot_bytes(c);
   if (packed) GLC_HIP(ctx, ctx->batch_stage.reserve(packed));
   uint8_t *pin = static_cast<uint8_t *>(ctx->batch_stage.p);
-  uint64_t pin_at = 0, run_begin = 0, run_dev = 0;  // bytes packed / where the open run starts in `pin` / in d_pcm (floats)
+  uint64_t pin_at = 0, run_begin = 0, run_dev = 0;  // bytes packed / where the open run starts in `pin` / in d_up (samples)
   auto send_run = [&]() -> hipError_t {
     hipError_t e = hipSuccess;
     if (pin_at > run_begin)
-      e = hipMemcpyAsync(d_pcm + run_dev, pin + run_begin, pin_at - run_begin, hipMemcpyHostToDevice, st);
+      e = hipMemcpyAsync(d_up + run_dev * elem, pin + run_begin, pin_at - run_begin, hipMemcpyHostToDevice, st);
     run_begin = pin_at;
     return e;
   };
-  GLC_HIP(ctx, hipMemsetAsync(d_pcm, 0, static_cast<size_t>(n_virtual) * sizeof(float), st));
+  GLC_HIP(ctx, hipMemsetAsync(d_up, 0, static_cast<size_t>(n_virtual) * elem, st));
   glc::FrameMap *fmap = reinterpret_cast<glc::FrameMap *>(hm + o_fmap_h);
   uint64_t slot = 0, real = 0;
   for (uint64_t i = 0; i < n; ++i) {
     const BatchClip &c = clips[i];
-    const uint64_t bytes = n_samples[c.index] * sizeof(float), at = slot * glc::kHop * ch;
+    const uint64_t bytes = n_samples[c.index] * elem, at = slot * glc::kHop * ch;
     if (bytes <= kPackClipBytes) {
       if (pin_at == run_begin) run_dev = at;  // a run starts with this clip; consecutive clips have consecutive slots
       std::memcpy(pin + pin_at, pcm[c.index], bytes);
@@ -1143,7 +1153,7 @@ int encode_batch_round(glc_ctx *ctx, const std::vector<BatchClip> &clips, const 
       if (pin_at - run_begin >= kPackRunBytes) GLC_HIP(ctx, send_run());
     } else {
       GLC_HIP(ctx, send_run());
-      GLC_HIP(ctx, hipMemcpyAsync(d_pcm + at, pcm[c.index], bytes, hipMemcpyHostToDevice, st));
+      GLC_HIP(ctx, hipMemcpyAsync(d_up + at * elem, pcm[c.index], bytes, hipMemcpyHostToDevice, st));
     }
     for (uint64_t f = 0; f < c.plan.n_frames; ++f)
       fmap[real + f] = glc::FrameMap{static_cast<uint32_t>(slot + f), f == 0 ? static_cast<uint32_t>(i) : 0xFFFFFFFFu};
@@ -1151,6 +1161,12 @@ int encode_batch_round(glc_ctx *ctx, const std::vector<BatchClip> &clips, const 
     real += c.plan.n_frames;
   }
   GLC_HIP(ctx, send_run());
+  // One widening for the round, whatever the number of clips: every element of the virtual stream, the zeros
+  // between and behind the clips included (d_pcm needs no memset of its own).  A zero widens to +0.0 - except
+  // with bits == 32, whose divisor is -2^31 (quirk Q11): there it, like a zero SAMPLE of glc_encode_int, becomes
+  // -0.0 where the reference pads with +0.0.  No output tells the two apart: a transform sum starts from +0.0
+  // and +0.0 + -0.0 = +0.0, the raw planes narrow both to 0.
+  if (is_int) GLC_HIP(ctx, glc::launch_pcm_widen(d_up, fmt == GLC_PCM_S32, bits, n_virtual, d_pcm, st));
   glc::FrameMap *d_fmap = reinterpret_cast<glc::FrameMap *>(mb + scratch);
   GLC_HIP(ctx, hipMemcpyAsync(d_fmap, fmap, n_real * sizeof(glc::FrameMap), hipMemcpyHostToDevice, st));
 
@@ -1223,17 +1239,17 @@ int encode_batch_round(glc_ctx *ctx, const std::vector<BatchClip> &clips, const 
   return GLC_OK;
 }
 
-int encode_batch_impl(glc_ctx *ctx, const float *const *pcm, const uint64_t *n_samples, uint64_t n_clips, uint16_t channels,
-                      glc_frames **out) {
+int encode_batch_impl(glc_ctx *ctx, const char *who, const void *const *pcm, glc_pcm_format fmt, uint32_t bits,
+                      const uint64_t *n_samples, uint64_t n_clips, uint16_t channels, glc_frames **out) {
   std::vector<BatchClip> all(n_clips);
   for (uint64_t i = 0; i < n_clips; ++i) {
     all[i] = BatchClip{i, glc::plan_encode(n_samples[i], channels)};
     if (all[i].plan.n_frames == 0)
       return fail(ctx, GLC_EINVAL,
-                  "glc_encode_batch: clip " + std::to_string(i) +
+                  std::string(who) + ": clip " + std::to_string(i) +
                       ": the reference encoder panics on this input (channels == 0, <= 512 samples per channel, or "
                       "ragged channels)");
-    if (!pcm[i]) return fail(ctx, GLC_EINVAL, "glc_encode_batch: clip " + std::to_string(i) + ": null pointer");
+    if (!pcm[i]) return fail(ctx, GLC_EINVAL, std::string(who) + ": clip " + std::to_string(i) + ": null pointer");
   }
   DeviceGuard guard(ctx->device);
   std::vector<std::unique_ptr<glc_frames>> result(n_clips);
@@ -1243,14 +1259,14 @@ int encode_batch_impl(glc_ctx *ctx, const float *const *pcm, const uint64_t *n_s
   int rc = GLC_OK;
   auto alone = [&](uint64_t i) {  // the single-stream pipeline (uploads, kernels and downloads of one stream overlapped)
     glc_frames *f = nullptr;
-    rc = encode_pipeline(ctx, pcm[i], GLC_PCM_F32, 32, n_samples[i], channels, nullptr, nullptr, &f);
+    rc = encode_pipeline(ctx, pcm[i], fmt, bits, n_samples[i], channels, nullptr, nullptr, &f);
     result[i].reset(f);
   };
   auto flush = [&] {
     if (round.size() == 1 && rc == GLC_OK)  // a clip with a round to itself shares nothing
       alone(round[0].index);
     else if (!round.empty() && rc == GLC_OK)
-      rc = encode_batch_round(ctx, round, pcm, n_samples, channels, result);
+      rc = encode_batch_round(ctx, round, pcm, fmt, bits, n_samples, channels, result);
     round.clear();
     used = 0;
   };
@@ -1276,19 +1292,40 @@ int encode_batch_impl(glc_ctx *ctx, const float *const *pcm, const uint64_t *n_s
 
 }  // namespace
 
-int glc_encode_batch(glc_ctx *ctx, const float *const *pcm, const uint64_t *n_samples, uint64_t n_clips, uint16_t channels,
-                     glc_frames **out) {
-  if (!ctx) return fail(ctx, GLC_EINVAL, "glc_encode_batch: null argument");
+// glc_encode_batch / glc_encode_batch_int behind their argument checks
+static int encode_batch_checked(glc_ctx *ctx, const char *who, const void *const *pcm, glc_pcm_format fmt, uint32_t bits,
+                                const uint64_t *n_samples, uint64_t n_clips, uint16_t channels, glc_frames **out) {
+  const std::string w(who);
+  if (!ctx) return fail(ctx, GLC_EINVAL, w + ": null argument");
   if (n_clips == 0) return GLC_OK;
-  if (!pcm || !n_samples || !out) return fail(ctx, GLC_EINVAL, "glc_encode_batch: null argument");
+  if (!pcm || !n_samples || !out) return fail(ctx, GLC_EINVAL, w + ": null argument");
   for (uint64_t i = 0; i < n_clips; ++i) out[i] = nullptr;
-  if (channels == 0) return fail(ctx, GLC_EINVAL, "glc_encode_batch: channels == 0");
+  if (channels == 0) return fail(ctx, GLC_EINVAL, w + ": channels == 0");
   try {  // no C++ exception may cross the C ABI
-    return encode_batch_impl(ctx, pcm, n_samples, n_clips, channels, out);
+    return encode_batch_impl(ctx, who, pcm, fmt, bits, n_samples, n_clips, channels, out);
   } catch (const std::bad_alloc &) {
     (void)hipStreamSynchronize(ctx->stream);
-    return fail(ctx, GLC_ENOMEM, "glc_encode_batch: host allocation failed");
+    return fail(ctx, GLC_ENOMEM, w + ": host allocation failed");
   }
+}
+
+int glc_encode_batch(glc_ctx *ctx, const float *const *pcm, const uint64_t *n_samples, uint64_t n_clips, uint16_t channels,
+                     glc_frames **out) {
+  return encode_batch_checked(ctx, "glc_encode_batch", reinterpret_cast<const void *const *>(pcm), GLC_PCM_F32, 32, n_samples,
+                              n_clips, channels, out);
+}
+
+int glc_encode_batch_int(glc_ctx *ctx, const void *const *pcm, glc_pcm_format fmt, uint32_t bits, const uint64_t *n_samples,
+                         uint64_t n_clips, uint16_t channels, glc_frames **out) {
+  if (!ctx) return fail(ctx, GLC_EINVAL, "glc_encode_batch_int: null argument");
+  if (fmt == GLC_PCM_F32)
+    return glc_encode_batch(ctx, reinterpret_cast<const float *const *>(pcm), n_samples, n_clips, channels, out);
+  if (out)
+    for (uint64_t i = 0; i < n_clips; ++i) out[i] = nullptr;
+  if (fmt != GLC_PCM_S16 && fmt != GLC_PCM_S32) return fail(ctx, GLC_EINVAL, "glc_encode_batch_int: unknown sample format");
+  if (bits == 0 || bits > (fmt == GLC_PCM_S16 ? 16u : 32u))
+    return fail(ctx, GLC_EINVAL, "glc_encode_batch_int: bits must be 1..16 for 16-bit samples, 1..32 for 32-bit ones");
+  return encode_batch_checked(ctx, "glc_encode_batch_int", pcm, fmt, bits, n_samples, n_clips, channels, out);
 }
 
 // ------------------------------------------------------------------------------ decode
@@ -1657,8 +1694,10 @@ int decode_prepared_to_host(glc_ctx *ctx, T *pcm_out, uint64_t cap, uint64_t *n_
 // One round of glc_decode_batch: streams[0 .. n) (all of `ch` channels, together at most a round's frames)
 // through D1 as one row table, then the segment-aware overlap-add, which writes every stream's TRIMMED
 // samples back to back, and one copy of them to pcm_out.  lens[i]: glc_decoded_len of stream i.
+// T: float (glc_decode_batch) or int16_t (glc_decode_batch_i16: narrowed by the overlap-add itself).
+template <typename T>
 int decode_batch_round(glc_ctx *ctx, const glc_frames *const *streams, uint64_t n, uint32_t ch, const uint64_t *lens,
-                       float *pcm_out) {
+                       T *pcm_out) {
   uint64_t frames = 0, n_out = 0;
   for (uint64_t i = 0; i < n; ++i) frames += streams[i]->n_frames, n_out += lens[i];
   const uint64_t M = frames * ch;
@@ -1705,7 +1744,7 @@ int decode_batch_round(glc_ctx *ctx, const glc_frames *const *streams, uint64_t 
   GLC_HIP(ctx, ctx->dec_meta.reserve(off));
   GLC_HIP(ctx, ctx->batch_stage.reserve(off));
   GLC_HIP(ctx, ctx->blocks.reserve(std::max<size_t>(frames, 1) * slot * sizeof(float)));
-  GLC_HIP(ctx, ctx->pcm.reserve(std::max<size_t>(n_out, 1) * sizeof(float)));
+  GLC_HIP(ctx, ctx->pcm.reserve(std::max<size_t>(n_out, 1) * sizeof(T)));
   uint8_t *img = static_cast<uint8_t *>(ctx->batch_stage.p);
   {
     uint8_t *p = img + o_pairs;
@@ -1731,18 +1770,20 @@ int decode_batch_round(glc_ctx *ctx, const glc_frames *const *streams, uint64_t 
                              reinterpret_cast<const uint64_t *>(mb + o_rows + t.h_rawlen),
                              reinterpret_cast<const int16_t *>(mb + o_pool), t.any_raw};
   float *blocks = static_cast<float *>(ctx->blocks.p);
-  float *stage = static_cast<float *>(ctx->pcm.p);
+  T *stage = static_cast<T *>(ctx->pcm.p);
   // (D1's 8-frame units may span two streams: that only widens a union)
   GLC_HIP(ctx, glc::launch_imdct_rows(ctx->dev, rows, 0, static_cast<uint32_t>(M), ch, blocks, ctx->stream, ctx->d1_variant,
                                       ctx->dec_plan.p, ctx->dec_plan.p ? ctx->dec_plan_groups : 0, false));
   GLC_HIP(ctx, glc::launch_overlap_add_batch(blocks, reinterpret_cast<const glc::HopDesc *>(mb + o_desc),
                                              static_cast<uint32_t>(desc.size()), ch, stage, ctx->stream));
-  if (n_out) GLC_HIP(ctx, hipMemcpyAsync(pcm_out, stage, n_out * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  if (n_out) GLC_HIP(ctx, hipMemcpyAsync(pcm_out, stage, n_out * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
   GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return GLC_OK;
 }
 
-int decode_batch_impl(glc_ctx *ctx, const glc_frames *const *in, uint64_t n_streams, float *pcm_out, const uint64_t *offsets) {
+template <typename T>
+int decode_batch_impl(glc_ctx *ctx, const char *who, const glc_frames *const *in, uint64_t n_streams, T *pcm_out,
+                      const uint64_t *offsets) {
   const uint32_t ch = in[0]->channels;
   const uint64_t per_hop = static_cast<uint64_t>(glc::kHop) * ch;
   // a round: whole streams of together at most kDecodeChunkFrames frames (+ one tail hop each), its output
@@ -1753,7 +1794,7 @@ int decode_batch_impl(glc_ctx *ctx, const glc_frames *const *in, uint64_t n_stre
   auto alone = [&](uint64_t i) {  // the single-stream driver, straight into the stream's span
     rc = decode_prepare(ctx, in[i]);
     if (rc == GLC_OK)
-      rc = decode_prepared_to_host(ctx, pcm_out + offsets[i], offsets[i + 1] - offsets[i], nullptr, "glc_decode_batch");
+      rc = decode_prepared_to_host(ctx, pcm_out + offsets[i], offsets[i + 1] - offsets[i], nullptr, who);
     ctx->dec_uid = 0;  // a batch decode leaves no stream resident
     ctx->plan_uid = 0;
   };
@@ -1869,41 +1910,58 @@ int glc_decode_i16(glc_ctx *ctx, const glc_frames *in, int16_t *pcm_out, uint64_
   return decode_to_host(ctx, in, pcm_out, cap, n_out, "glc_decode_i16");
 }
 
-int glc_decode_batch(glc_ctx *ctx, const glc_frames *const *in, uint64_t n_streams, float *pcm_out, uint64_t cap,
-                     uint64_t *offsets) {
-  if (!ctx) return fail(ctx, GLC_EINVAL, "glc_decode_batch: null argument");
+extern "C++" {
+namespace {
+// glc_decode_batch / glc_decode_batch_i16
+template <typename T>
+int decode_batch_to_host(glc_ctx *ctx, const char *who, const glc_frames *const *in, uint64_t n_streams, T *pcm_out, uint64_t cap,
+                         uint64_t *offsets) {
+  const std::string w(who);
+  if (!ctx) return fail(ctx, GLC_EINVAL, w + ": null argument");
   if (n_streams == 0) {
     if (offsets) offsets[0] = 0;
     return GLC_OK;
   }
-  if (!in || !offsets || (!pcm_out && cap)) return fail(ctx, GLC_EINVAL, "glc_decode_batch: null argument");
+  if (!in || !offsets || (!pcm_out && cap)) return fail(ctx, GLC_EINVAL, w + ": null argument");
   offsets[0] = 0;
   for (uint64_t i = 0; i < n_streams; ++i) {
-    if (!in[i]) return fail(ctx, GLC_EINVAL, "glc_decode_batch: stream " + std::to_string(i) + ": null pointer");
+    if (!in[i]) return fail(ctx, GLC_EINVAL, w + ": stream " + std::to_string(i) + ": null pointer");
     offsets[i + 1] = offsets[i] + glc_decoded_len(in[i]);
   }
-  if (in[0]->channels == 0) return fail(ctx, GLC_EINVAL, "glc_decode_batch: header.channels == 0");
+  if (in[0]->channels == 0) return fail(ctx, GLC_EINVAL, w + ": header.channels == 0");
   for (uint64_t i = 1; i < n_streams; ++i)
     if (in[i]->channels != in[0]->channels)
       return fail(ctx, GLC_EINVAL,
-                  "glc_decode_batch: stream " + std::to_string(i) + " has " + std::to_string(in[i]->channels) +
+                  w + ": stream " + std::to_string(i) + " has " + std::to_string(in[i]->channels) +
                       " channels, stream 0 has " + std::to_string(in[0]->channels));
-  if (cap < offsets[n_streams]) return fail(ctx, GLC_EINVAL, "glc_decode_batch: output buffer too small");
+  if (cap < offsets[n_streams]) return fail(ctx, GLC_EINVAL, w + ": output buffer too small");
   // no stream is resident afterwards: the row tables on the device are a round's, not a stream's
   ctx->stream_open = false;
   ctx->dec_uid = 0;
   ctx->plan_uid = 0;
   int rc;
   try {  // no C++ exception may cross the C ABI
-    rc = decode_batch_impl(ctx, in, n_streams, pcm_out, offsets);
+    rc = decode_batch_impl(ctx, who, in, n_streams, pcm_out, offsets);
   } catch (const std::bad_alloc &) {
-    rc = fail(ctx, GLC_ENOMEM, "glc_decode_batch: host allocation failed");
+    rc = fail(ctx, GLC_ENOMEM, w + ": host allocation failed");
   }
   if (rc != GLC_OK) {
     DeviceGuard guard(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);  // nothing may still be in flight into the caller's memory
   }
   return rc;
+}
+}  // namespace
+}  // extern "C++"
+
+int glc_decode_batch(glc_ctx *ctx, const glc_frames *const *in, uint64_t n_streams, float *pcm_out, uint64_t cap,
+                     uint64_t *offsets) {
+  return decode_batch_to_host(ctx, "glc_decode_batch", in, n_streams, pcm_out, cap, offsets);
+}
+
+int glc_decode_batch_i16(glc_ctx *ctx, const glc_frames *const *in, uint64_t n_streams, int16_t *pcm_out, uint64_t cap,
+                         uint64_t *offsets) {
+  return decode_batch_to_host(ctx, "glc_decode_batch_i16", in, n_streams, pcm_out, cap, offsets);
 }
 
 uint64_t glc_ctx_resident_stream(const glc_ctx *ctx) { return ctx ? ctx->dec_uid : 0; }

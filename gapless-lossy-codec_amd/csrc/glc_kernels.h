@@ -105,6 +105,10 @@ struct HopDesc {
 };
 hipError_t launch_overlap_add_batch(const float *blocks, const HopDesc *desc, uint32_t n_desc, uint32_t ch, float *out,
                                     hipStream_t s);
+// ... narrowed to 16-bit PCM as launch_overlap_add_i16 narrows (glc_decode_batch_i16): `out` is 8-byte aligned,
+// dst an index of 2-byte elements.
+hipError_t launch_overlap_add_batch(const float *blocks, const HopDesc *desc, uint32_t n_desc, uint32_t ch, int16_t *out,
+                                    hipStream_t s);
 
 // D2 with the narrowing of the reference's 16-bit writers on the way out: the same sums, then
 // `(v * 32767.0).clamp(-32768.0, 32767.0) as i16` (NaN -> 0, truncation) - `out` is any 2-byte aligned pointer.

@@ -13,6 +13,8 @@
 //   K3 k_decide_raw    :496-502 (raw plane) + :505-540 (size estimate, decision)
 //   D1 k_imdct_rows    :626-644 (raw frames), :651-665 (dequant), :377-390 (imdct), :672-675
 //   D2 k_overlap_add   :688-705 (overlap-add + interleave), :722-729 (tail)
+#include <type_traits>
+
 #include "glc_common.h"
 #include "glc_kernels.h"
 #include "glc_mdct_fwd.hpp"
@@ -836,17 +838,21 @@ __global__ __launch_bounds__(256) void k_overlap_add(const float *__restrict__ b
 // over the DESTINATION: chunk k of a hop is the four floats at (dst & ~3) + 4k, 16-byte aligned when `out`
 // is, and goes out as one float4; only the first and the last chunk of a cut span can be partial, and
 // those store float by float.  Same sums as k_overlap_add.
-template <int CH>
+// T = short (glc_decode_batch_i16): the same rows and sums, narrowed as k_overlap_add_i16 narrows them
+// (`sat_i16(mul_rn(v, 32767.0f))`, src/audio.rs:11-16); `dst & 3` is then the lead in 2-byte elements, a whole
+// chunk one aligned short4 (8 bytes), the partial first and last chunk of a cut span go out short by short.
+template <int CH, typename T>
 __global__ __launch_bounds__(256) void k_overlap_add_batch(const float *__restrict__ blocks,
                                                             const HopDesc *__restrict__ desc, unsigned ch,
-                                                            float *__restrict__ out) {
+                                                            T *__restrict__ out) {
+  static_assert(std::is_same<T, float>::value || std::is_same<T, short>::value, "float or 16-bit PCM");
   const HopDesc d = desc[blockIdx.y];
   const unsigned lead = d.dst & 3u;
   const unsigned n_chunks = (lead + d.cnt + 3u) >> 2;
   const bool has_prev = d.prev >= 0, has_cur = d.cur >= 0;
   const float *prev = blocks + (static_cast<size_t>(has_prev ? d.prev : 0) * ch) * kFrameI + kHopI;
   const float *cur = blocks + (static_cast<size_t>(has_cur ? d.cur : 0) * ch) * kFrameI;
-  float *base = out + (d.dst - lead);
+  T *base = out + (d.dst - lead);
   for (unsigned k = blockIdx.x * 256u + threadIdx.x; k < n_chunks; k += gridDim.x * 256u) {
     const int j0 = static_cast<int>(4u * k) - static_cast<int>(lead);  // first of the chunk, counted from the span's start
     float v[4];
@@ -866,13 +872,26 @@ __global__ __launch_bounds__(256) void k_overlap_add_batch(const float *__restri
       const float p = has_prev ? prev[at] : 0.0f;  // overlap starts as +0.0, :601
       v[e] = has_cur ? add_rn(p, cur[at]) : p;      // :695 / the bare tail, :727
     }
-    float *dst = base + 4u * static_cast<size_t>(k);
-    if (keep[0] && keep[3]) {
-      *reinterpret_cast<float4 *>(dst) = float4{v[0], v[1], v[2], v[3]};
-    } else {
+    T *dst = base + 4u * static_cast<size_t>(k);
+    if constexpr (std::is_same<T, float>::value) {
+      if (keep[0] && keep[3]) {
+        *reinterpret_cast<float4 *>(dst) = float4{v[0], v[1], v[2], v[3]};
+      } else {
 #pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (keep[e]) dst[e] = v[e];
+        for (int e = 0; e < 4; ++e)
+          if (keep[e]) dst[e] = v[e];
+      }
+    } else {
+      short q[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) q[e] = sat_i16(mul_rn(v[e], 32767.0f));  // src/audio.rs:13-14
+      if (keep[0] && keep[3]) {
+        *reinterpret_cast<short4 *>(dst) = short4{q[0], q[1], q[2], q[3]};
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (keep[e]) dst[e] = q[e];
+      }
     }
   }
 }
@@ -1372,25 +1391,38 @@ hipError_t launch_overlap_add(const float *blocks, int64_t blk_frame0, uint64_t 
   return hipGetLastError();
 }
 
-hipError_t launch_overlap_add_batch(const float *blocks, const HopDesc *desc, uint32_t n_desc, uint32_t ch, float *out,
-                                    hipStream_t s) {
+namespace {
+template <typename T>
+hipError_t overlap_add_batch_typed(const float *blocks, const HopDesc *desc, uint32_t n_desc, uint32_t ch, T *out,
+                                   hipStream_t s) {
   if (n_desc == 0) return hipSuccess;
-  if (reinterpret_cast<uintptr_t>(out) & 15u) return hipErrorInvalidValue;  // the float4 chunks are laid over `out`
+  if (reinterpret_cast<uintptr_t>(out) & (4u * sizeof(T) - 1u)) return hipErrorInvalidValue;  // the float4 / short4 chunks are laid over `out`
   const unsigned per_hop = 1024u * ch;
-  const unsigned bx = (per_hop / 4u + 255u) / 256u;  // a span that starts off a 16-byte boundary has one chunk more: the stride loop's
+  const unsigned bx = (per_hop / 4u + 255u) / 256u;  // a span that starts off a chunk boundary has one chunk more: the stride loop's
   for (uint32_t d0 = 0; d0 < n_desc; d0 += 32768) {  // slabs: blockIdx.y is 16 bits wide
     const unsigned nd = n_desc - d0 < 32768 ? n_desc - d0 : 32768;
     const dim3 grid(bx, nd);
     const HopDesc *d = desc + d0;
     switch (ch) {
-      case 1: hipLaunchKernelGGL(k_overlap_add_batch<1>, grid, dim3(256), 0, s, blocks, d, ch, out); break;
-      case 2: hipLaunchKernelGGL(k_overlap_add_batch<2>, grid, dim3(256), 0, s, blocks, d, ch, out); break;
-      case 4: hipLaunchKernelGGL(k_overlap_add_batch<4>, grid, dim3(256), 0, s, blocks, d, ch, out); break;
-      case 8: hipLaunchKernelGGL(k_overlap_add_batch<8>, grid, dim3(256), 0, s, blocks, d, ch, out); break;
-      default: hipLaunchKernelGGL(k_overlap_add_batch<0>, grid, dim3(256), 0, s, blocks, d, ch, out); break;
+      case 1: hipLaunchKernelGGL((k_overlap_add_batch<1, T>), grid, dim3(256), 0, s, blocks, d, ch, out); break;
+      case 2: hipLaunchKernelGGL((k_overlap_add_batch<2, T>), grid, dim3(256), 0, s, blocks, d, ch, out); break;
+      case 4: hipLaunchKernelGGL((k_overlap_add_batch<4, T>), grid, dim3(256), 0, s, blocks, d, ch, out); break;
+      case 8: hipLaunchKernelGGL((k_overlap_add_batch<8, T>), grid, dim3(256), 0, s, blocks, d, ch, out); break;
+      default: hipLaunchKernelGGL((k_overlap_add_batch<0, T>), grid, dim3(256), 0, s, blocks, d, ch, out); break;
     }
   }
   return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_overlap_add_batch(const float *blocks, const HopDesc *desc, uint32_t n_desc, uint32_t ch, float *out,
+                                    hipStream_t s) {
+  return overlap_add_batch_typed(blocks, desc, n_desc, ch, out, s);
+}
+
+hipError_t launch_overlap_add_batch(const float *blocks, const HopDesc *desc, uint32_t n_desc, uint32_t ch, int16_t *out,
+                                    hipStream_t s) {
+  return overlap_add_batch_typed(blocks, desc, n_desc, ch, reinterpret_cast<short *>(out), s);
 }
 
 hipError_t launch_overlap_add_i16(const float *blocks, int64_t blk_frame0, uint64_t n_frames, uint32_t ch,

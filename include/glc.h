@@ -438,6 +438,21 @@ int glc_encode_batch(glc_ctx *ctx, const float *const *pcm, const uint64_t *n_sa
 int glc_decode_batch(glc_ctx *ctx, const glc_frames *const *in, uint64_t n_streams, float *pcm_out, uint64_t cap,
                      uint64_t *offsets);
 
+/* glc_encode_batch of integer clips: one `fmt` and one `bits` for the whole call (as `channels` is one for
+ * the whole call; callers group).  out[i] is byte-identical to glc_encode_int(ctx, pcm[i], fmt, bits,
+ * n_samples[i], channels) - and so to glc_encode / glc_encode_batch of the widened floats.  The integers are
+ * what is staged and uploaded; the device widens a whole round in one pass.  pcm[i] is aligned to its sample
+ * size.  GLC_PCM_F32 forwards to glc_encode_batch; fmt / bits are validated as glc_encode_int validates them
+ * (GLC_EINVAL).  Every rule of glc_encode_batch holds unchanged. */
+int glc_encode_batch_int(glc_ctx *ctx, const void *const *pcm, glc_pcm_format fmt, uint32_t bits,
+                         const uint64_t *n_samples, uint64_t n_clips, uint16_t channels, glc_frames **out);
+
+/* glc_decode_batch writing 16-bit PCM: the same contract with int16_t elements (offsets in samples), stream
+ * i's span equal to glc_decode_i16 of it alone - narrowed on the device by the batch overlap-add itself.
+ * pcm_out is any 2-byte aligned host pointer. */
+int glc_decode_batch_i16(glc_ctx *ctx, const glc_frames *const *in, uint64_t n_streams, int16_t *pcm_out,
+                         uint64_t cap, uint64_t *offsets);
+
 /* ---- tables (for inspection / parity tests) ---------------------------------------------- */
 
 /* Copies of the host tables of a context: MdctTables.cos_table [1024*2048] (row k), window

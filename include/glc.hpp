@@ -218,6 +218,14 @@ class Encoder {
   EncodedAudio encode(const std::vector<float> &samples, uint16_t channels) {
     return encode(samples.data(), samples.size(), channels);
   }
+  // glc_encode_batch_int: clips of 16-bit / of `bits`-bit samples in 32-bit containers, one width for the call
+  // (argument order as in the integer `encode` overloads below)
+  std::vector<EncodedAudio> encode_batch(const std::vector<std::vector<int16_t>> &clips, uint16_t channels, uint32_t bits = 16) {
+    return encode_batch_int(clips, GLC_PCM_S16, bits, channels);
+  }
+  std::vector<EncodedAudio> encode_batch(const std::vector<std::vector<int32_t>> &clips, uint32_t bits, uint16_t channels) {
+    return encode_batch_int(clips, GLC_PCM_S32, bits, channels);
+  }
   // encode of what load_wav / load_flac make of integer samples, s / 2^(bits-1) (src/audio.rs:58, :79),
   // without the float copy: the integers go up and are widened on the device (glc_encode_int)
   EncodedAudio encode(const int16_t *samples, uint64_t n_samples, uint16_t channels, uint32_t bits = 16) {
@@ -282,6 +290,19 @@ class Encoder {
   glc_ctx *ctx() { return ctx_; }
 
  private:
+  template <typename S>
+  std::vector<EncodedAudio> encode_batch_int(const std::vector<std::vector<S>> &clips, glc_pcm_format fmt, uint32_t bits,
+                                             uint16_t channels) {
+    std::vector<const void *> pcm(clips.size());
+    std::vector<uint64_t> n(clips.size());
+    for (size_t i = 0; i < clips.size(); ++i) pcm[i] = clips[i].data(), n[i] = clips[i].size();
+    std::vector<glc_frames *> h(clips.size(), nullptr);
+    detail::check(glc_encode_batch_int(ctx_, pcm.data(), fmt, bits, n.data(), clips.size(), channels, h.data()), ctx_);
+    std::vector<EncodedAudio> out;
+    out.reserve(h.size());
+    for (glc_frames *f : h) out.emplace_back(f);
+    return out;
+  }
   glc_ctx *ctx_ = nullptr;
 };
 
@@ -320,6 +341,16 @@ class Decoder {
     detail::check(glc_decode_i16(ctx_, encoded.handle(), out.data(), out.size(), &n), ctx_);
     out.resize(n);
     return out;
+  }
+  // glc_decode_batch_i16: decode_batch with the narrowing of decode_i16, offsets in samples
+  std::vector<int16_t> decode_batch_i16(const std::vector<const EncodedAudio *> &encoded, std::vector<uint64_t> &offsets) {
+    std::vector<const glc_frames *> h(encoded.size());
+    uint64_t total = 0;
+    for (size_t i = 0; i < encoded.size(); ++i) h[i] = encoded[i]->handle(), total += glc_decoded_len(h[i]);
+    offsets.assign(encoded.size() + 1, 0);
+    std::vector<int16_t> packed(total);
+    detail::check(glc_decode_batch_i16(ctx_, h.data(), h.size(), packed.data(), packed.size(), offsets.data()), ctx_);
+    return packed;
   }
   // The stream whose sparse rows this Decoder still holds on the device (0: none), and its decode without
   // an EncodedAudio (glc.h glc_decode_resident): for callers that recognise a stream by the id they gave it

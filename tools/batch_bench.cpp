@@ -10,6 +10,13 @@
 //        build/batch_bench reps n_clips seconds sample_rate     one shape of the caller's
 //        build/batch_bench trace n_clips seconds                10 encode + 10 decode batch calls and nothing
 //                                                               else after the warm-up (for a kernel trace)
+// The integer arms, same method: glc_encode_batch on floats (A, A') against glc_encode_batch_int on the 16-bit
+// samples those floats were widened from (B), glc_decode_batch (A, A') against glc_decode_batch_i16 (B), and
+// what a caller of the float call does to get 16-bit samples: the float batch decode followed by the
+// narrowing on one host thread (C, for the record).
+//        build/batch_bench int [reps = 30]                      the three shapes
+//        build/batch_bench int reps n_clips seconds sample_rate one shape of the caller's
+//        build/batch_bench trace-int n_clips seconds            as `trace`, the integer calls
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -153,7 +160,128 @@ static int run(const char *name, uint32_t sr, uint64_t n_clips, double seconds, 
   return 0;
 }
 
+static int16_t narrow(float s) {  // convert_f32_to_i16
+  float v = s * 32767.0f;
+  if (v != v) return 0;
+  v = std::min(std::max(v, -32768.0f), 32767.0f);
+  return static_cast<int16_t>(v);
+}
+
+static int run_int(const char *name, uint32_t sr, uint64_t n_clips, double seconds, int reps, bool trace) {
+  const uint16_t ch = 2;
+  const uint64_t per_ch = static_cast<uint64_t>(seconds * sr), n = per_ch * ch;
+  std::vector<std::vector<int16_t>> s16(n_clips, std::vector<int16_t>(n));
+  std::vector<std::vector<float>> f32(n_clips, std::vector<float>(n));
+  for (uint64_t k = 0; k < n_clips; ++k) {  // the tones of run(), as a 16-bit file holds them and as load_wav widens them
+    const double f0 = 110.0 * std::pow(2.0, static_cast<double>(k % 48) / 12.0);
+    for (uint64_t t = 0; t < per_ch; ++t) {
+      s16[k][t * 2] = narrow(static_cast<float>(0.5 * std::sin(2 * M_PI * f0 * t / sr)));
+      s16[k][t * 2 + 1] = narrow(static_cast<float>(0.4 * std::sin(2 * M_PI * 1.5 * f0 * t / sr + 0.3)));
+    }
+    for (uint64_t i = 0; i < n; ++i) f32[k][i] = static_cast<float>(s16[k][i]) / 32768.0f;
+  }
+  std::vector<const float *> pf(n_clips);
+  std::vector<const void *> pi(n_clips);
+  std::vector<uint64_t> lens(n_clips, n);
+  for (uint64_t k = 0; k < n_clips; ++k) pf[k] = f32[k].data(), pi[k] = s16[k].data();
+
+  glc_ctx *enc = nullptr, *dec = nullptr;
+  CHECK(glc_ctx_create(0, sr, &enc));
+  CHECK(glc_ctx_create(0, sr, &dec));
+  std::vector<glc_frames *> ff(n_clips, nullptr), fi(n_clips, nullptr);
+  auto free_all = [&](std::vector<glc_frames *> &v) {
+    for (glc_frames *&f : v) glc_frames_free(f), f = nullptr;
+  };
+  auto enc_f = [&] { return glc_encode_batch(enc, pf.data(), lens.data(), n_clips, ch, ff.data()); };
+  auto enc_i = [&] { return glc_encode_batch_int(enc, pi.data(), GLC_PCM_S16, 16, lens.data(), n_clips, ch, fi.data()); };
+  if (!trace) CHECK(enc_f());
+  CHECK(enc_i());
+  std::vector<uint8_t> ba, bb;
+  for (uint64_t k = 0; k < n_clips && !trace; ++k) {
+    CHECK(serialize(ff[k], ba));
+    CHECK(serialize(fi[k], bb));
+    if (ba != bb) return std::printf("%s: clip %llu: glc_encode_batch_int and glc_encode_batch give different streams\n", name, (unsigned long long)k), 1;
+  }
+  free_all(ff);
+  std::vector<glc_frames *> keep;  // the decode arms read these
+  keep.swap(fi);
+  fi.assign(n_clips, nullptr);
+  std::vector<uint64_t> off_f(n_clips + 1, 0), off_i(n_clips + 1, 0);
+  uint64_t total = 0;
+  for (uint64_t k = 0; k < n_clips; ++k) total += glc_decoded_len(keep[k]);
+  std::vector<float> df(total);
+  std::vector<int16_t> di(total), want(total);
+  auto dec_f = [&] { return glc_decode_batch(dec, keep.data(), n_clips, df.data(), df.size(), off_f.data()); };
+  auto dec_i = [&] { return glc_decode_batch_i16(dec, keep.data(), n_clips, di.data(), di.size(), off_i.data()); };
+  auto dec_fn = [&] {  // what a caller of the float call does today
+    const int rc = dec_f();
+    for (uint64_t i = 0; i < total; ++i) want[i] = narrow(df[i]);
+    return rc;
+  };
+  if (!trace) CHECK(dec_fn());
+  CHECK(dec_i());
+  if (!trace && (off_f != off_i || std::memcmp(want.data(), di.data(), total * 2)))
+    return std::printf("%s: glc_decode_batch_i16 differs from the narrowed glc_decode_batch\n", name), 1;
+
+  auto enc_a = [&] { const int rc = enc_f(); free_all(ff); return rc; };
+  auto enc_b = [&] { const int rc = enc_i(); free_all(fi); return rc; };
+  auto timed = [&](auto &&fn, std::vector<double> &into) {
+    const double t0 = now_ms();
+    const int rc = fn();
+    into.push_back(now_ms() - t0);
+    return rc;
+  };
+  const int warm = trace ? 3 : std::max(3, reps / 5);
+  for (int i = 0; i < warm; ++i) {
+    if (!trace) { CHECK(enc_a()); CHECK(dec_fn()); }
+    CHECK(enc_b()); CHECK(dec_i());
+  }
+  if (trace) {
+    for (int i = 0; i < 10; ++i) { CHECK(enc_b()); CHECK(dec_i()); }
+    std::printf("%s: 1 + %d warm-up + 10 integer batch calls each way, %llu clips of %llu samples x %u ch\n", name, warm,
+                (unsigned long long)n_clips, (unsigned long long)per_ch, ch);
+  } else {
+    std::vector<double> ea, eb, ea2, da1, db1, da2, dn;
+    for (int i = 0; i < reps; ++i) {
+      CHECK(timed(enc_a, ea)); CHECK(timed(enc_b, eb)); CHECK(timed(enc_a, ea2)); CHECK(timed(enc_b, eb));
+    }
+    for (int i = 0; i < reps; ++i) {
+      CHECK(timed(dec_f, da1)); CHECK(timed(dec_i, db1)); CHECK(timed(dec_f, da2)); CHECK(timed(dec_i, db1));
+      CHECK(timed(dec_fn, dn));
+    }
+    const Stat A = stat(ea), B = stat(eb), A2 = stat(ea2), D = stat(da1), E = stat(db1), D2 = stat(da2), N = stat(dn);
+    const double es = std::fabs(A.med - A2.med), ds = std::fabs(D.med - D2.med);
+    auto verdict = [](double b, double a, double a2, double spread) {
+      return b < std::min(a, a2) - spread ? "FASTER" : b <= std::max(a, a2) + spread ? "not slower" : "SLOWER";
+    };
+    std::printf("%s: %llu clips of %llu samples x %u ch, %d interleaved reps (ms per batch: median [p10 .. p90])\n", name,
+                (unsigned long long)n_clips, (unsigned long long)per_ch, ch, reps);
+    std::printf("  glc_encode_batch (f32)      %.4f [%.4f .. %.4f]   again %.4f   A/A spread %.4f\n", A.med, A.p10, A.p90, A2.med, es);
+    std::printf("  glc_encode_batch_int (s16)  %.4f [%.4f .. %.4f]   int - float %+.4f   float / int %.2f  -> %s\n", B.med, B.p10, B.p90,
+                B.med - std::min(A.med, A2.med), std::min(A.med, A2.med) / B.med, verdict(B.med, A.med, A2.med, es));
+    std::printf("  glc_decode_batch (f32)      %.4f [%.4f .. %.4f]   again %.4f   A/A spread %.4f\n", D.med, D.p10, D.p90, D2.med, ds);
+    std::printf("  glc_decode_batch_i16        %.4f [%.4f .. %.4f]   int - float %+.4f   float / int %.2f  -> %s\n", E.med, E.p10, E.p90,
+                E.med - std::min(D.med, D2.med), std::min(D.med, D2.med) / E.med, verdict(E.med, D.med, D2.med, ds));
+    std::printf("  glc_decode_batch + host narrowing (one thread)  %.4f [%.4f .. %.4f]   / glc_decode_batch_i16 %.2f\n", N.med, N.p10,
+                N.p90, N.med / E.med);
+  }
+  free_all(keep);
+  glc_ctx_destroy(enc);
+  glc_ctx_destroy(dec);
+  return 0;
+}
+
 int main(int argc, char **argv) {
+  if (argc > 3 && !std::strcmp(argv[1], "trace-int"))
+    return run_int("trace-int", 44100, std::strtoull(argv[2], nullptr, 10), std::atof(argv[3]), 0, true);
+  if (argc > 1 && !std::strcmp(argv[1], "int")) {
+    const int reps = argc > 2 ? std::max(5, std::atoi(argv[2])) : 30;
+    if (argc > 5) return run_int("custom", std::atoi(argv[5]), std::strtoull(argv[3], nullptr, 10), std::atof(argv[4]), reps, false);
+    if (run_int("64 clips like config 1 (2 s, 44.1 kHz stereo)", 44100, 64, 2.0, reps, false)) return 1;
+    if (run_int("512 clips of 0.25 s (44.1 kHz stereo)", 44100, 512, 0.25, reps, false)) return 1;
+    if (run_int("4 clips of 60 s (48 kHz stereo)", 48000, 4, 60.0, std::max(5, reps / 3), false)) return 1;
+    return 0;
+  }
   if (argc > 3 && !std::strcmp(argv[1], "trace"))
     return run("trace", 44100, std::strtoull(argv[2], nullptr, 10), std::atof(argv[3]), 0, true);
   const int reps = argc > 1 ? std::max(5, std::atoi(argv[1])) : 30;

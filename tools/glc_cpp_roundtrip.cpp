@@ -95,6 +95,30 @@ int main(int argc, char **argv) {
       } catch (const std::runtime_error &) {
       }
     }
+    // the integer batch calls through the C++ mirror: the decode narrowed to 16 bits and its first half as two
+    // clips of one call - the bytes of the single integer encode, and of the same values in 24-bit containers;
+    // decode_batch_i16 gives each stream the samples decode_i16 gives it alone
+    if (whole.size() / 2 / ch > 512) {
+      const std::vector<int16_t> q = decoder.decode_i16(loaded);
+      const std::vector<std::vector<int16_t>> clips{q, std::vector<int16_t>(q.begin(), q.begin() + q.size() / 2 / ch * ch)};
+      std::vector<std::vector<int32_t>> clips24(clips.size());
+      for (size_t i = 0; i < clips.size(); ++i)
+        for (int16_t v : clips[i]) clips24[i].push_back(static_cast<int32_t>(v) * 256);
+      const std::vector<glc::EncodedAudio> b16 = encoder.encode_batch(clips, ch), b24 = encoder.encode_batch(clips24, 24, ch);
+      std::vector<const glc::EncodedAudio *> ptrs;
+      for (size_t i = 0; i < clips.size(); ++i) {
+        if (b16[i].to_bytes() != encoder.encode(clips[i], ch).to_bytes() || b24[i].to_bytes() != b16[i].to_bytes())
+          return std::fprintf(stderr, "integer encode_batch: clip %zu differs from the single encode\n", i), 1;
+        ptrs.push_back(&b16[i]);
+      }
+      std::vector<uint64_t> off;
+      const std::vector<int16_t> packed = decoder.decode_batch_i16(ptrs, off);
+      for (size_t i = 0; i < ptrs.size(); ++i) {
+        const std::vector<int16_t> one = decoder.decode_i16(b16[i]);
+        if (off[i + 1] - off[i] != one.size() || std::memcmp(packed.data() + off[i], one.data(), one.size() * 2) != 0)
+          return std::fprintf(stderr, "decode_batch_i16: stream %zu differs from decode_i16\n", i), 1;
+      }
+    }
     // src/audio.rs + src/flac.rs twins through the C++ mirror: export the decoded samples to FLAC and
     // WAV next to the output file and read both back (tests/test_export.rs)
     const std::string flac_path = std::string(argv[5]) + ".flac", wav_path = std::string(argv[5]) + ".wav";
