@@ -36,6 +36,15 @@ class GlcCompactInfo(C.Structure):
     ]
 
 
+class GlcRoundtripInfo(C.Structure):
+    _fields_ = [
+        ("n_frames", C.c_uint64),
+        ("n_raw_frames", C.c_uint64),
+        ("total_nnz", C.c_uint64),
+        ("serialized_bytes", C.c_uint64),
+    ]
+
+
 class GlcFramesView(C.Structure):
     """glc_frames_view (include/glc.h): EncodedAudio as flat arrays."""
     _fields_ = [
@@ -181,6 +190,11 @@ SIGNATURES = {
     "glc_encode_batch_int": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint16,
                                        C.POINTER(_vp)]),
     "glc_decode_batch_i16": (C.c_int, [_vp, C.POINTER(_vp), C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "glc_decode_device_records": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint16, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "glc_roundtrip_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint16, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "glc_roundtrip": (C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.c_uint64, C.c_uint16, _vp, C.c_int, C.c_uint64,
+                                C.POINTER(C.c_uint64)]),
+    "glc_roundtrip_last_info": (C.c_int, [_vp, C.POINTER(GlcRoundtripInfo)]),
     "glc_version": (C.c_char_p, []),
 }
 

@@ -22,7 +22,7 @@ from typing import Iterator, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ._lib import (FRAMES_HOOK, GLC_EINVAL, GLC_PCM_F32, GLC_PCM_S16, GLC_PCM_S32, GlcCompactInfo, GlcError,
-                   GlcFramesGather, GlcFramesView, GlcInfo, GlcPlan, check, lib)
+                   GlcFramesGather, GlcFramesView, GlcInfo, GlcPlan, GlcRoundtripInfo, check, lib)
 
 FRAME_SIZE = 2048        # src/codec.rs:15
 HOP_SIZE = 1024          # src/codec.rs:16
@@ -580,6 +580,16 @@ class Decoder(_Ctx):
         (glc_decode_range_device_i16).  Queued, not synchronised."""
         check(lib.glc_decode_range_device_i16(self._h, encoded._h, hop_begin, hop_end, C.c_void_p(d_out), cap), self._h)
 
+    def decode_device_records(self, d_records: int, n_frames: int, n_samples: int, channels: int, d_out: int, cap: int) -> int:
+        """glc_decode_device_records: Decoder::decode of the stream that n_frames frame records at device
+        address d_records describe (as Encoder.encode_range_device left them) into device memory at d_out,
+        gapless-trimmed; returns the number of samples.  The decoder's row tables are built on the device:
+        nothing crosses to the host.  Queued on the context's stream, not synchronised."""
+        n = C.c_uint64()
+        check(lib.glc_decode_device_records(self._h, C.c_void_p(d_records), n_frames, n_samples, channels,
+                                            C.c_void_p(d_out), cap, C.byref(n)), self._h)
+        return n.value
+
     def imdct_device(self, encoded: EncodedAudio, frame_begin: int, frame_end: int, d_blocks: int) -> None:
         """Dequant + imdct_block + window (src/codec.rs:651-675) alone for a frame range:
         d_blocks[(frame - frame_begin) * ch + c][2048] on the device (glc_imdct_device)."""
@@ -611,6 +621,88 @@ class Decoder(_Ctx):
                 self._progress(progress_sender, "Complete",
                                f"Decoded {total_frames} frames in {_time.perf_counter() - t0:.2f}s")
                 return
+
+
+@dataclass
+class RoundTripInfo:
+    """What a round trip encoded: the counts EncodedAudio.info() gives for Encoder.encode of the same samples,
+    and len(EncodedAudio.to_bytes()) of it."""
+    n_frames: int
+    n_raw_frames: int
+    total_nnz: int
+    serialized_bytes: int
+
+
+class RoundTrip(_Ctx):
+    """Encoder::encode followed by Decoder::decode as one call (glc_roundtrip, glc_roundtrip_device): what the
+    codec does to audio - the reference's own "encode, decode, compare" tests, or a degradation stage in
+    front of a model.  The samples are those of Decoder.decode(Encoder.encode(x)), bit for bit; no stream is
+    assembled on the host, the decoder reads the encoder's frame records where they are on the device."""
+
+    def __init__(self, sample_rate: int, device: int = 0):
+        super().__init__(sample_rate, device)
+
+    def apply(self, samples, channels: int, bits: Optional[int] = None, dtype=np.float32,
+              out: Optional[np.ndarray] = None) -> np.ndarray:
+        """Decoder.decode(Encoder.encode(samples, channels, bits), dtype=dtype) of a numpy array (float32, or
+        int16 / int32 of `bits` bits as in Encoder.encode): one upload, one download.  `out`: as in
+        Decoder.decode."""
+        dt = Decoder._out_dtype(dtype)
+        pcm, fmt, bits = pcm_format(samples, bits)
+        if out is None:
+            out = np.empty(pcm.size, dt)
+        elif out.dtype != dt or not out.flags.c_contiguous or out.size < pcm.size:
+            raise GlcError(GLC_EINVAL, f"out must be a C-contiguous {dt} array of at least as many samples as the input")
+        got = C.c_uint64()
+        check(lib.glc_roundtrip(self._h, pcm.ctypes.data_as(C.c_void_p), fmt, bits, pcm.size, channels,
+                                out.ctypes.data_as(C.c_void_p), GLC_PCM_F32 if dt == np.float32 else GLC_PCM_S16,
+                                out.size, C.byref(got)), self._h)
+        return out[:got.value]
+
+    def apply_device(self, d_pcm: int, n_samples: int, channels: int, d_out: int, cap: int) -> int:
+        """glc_roundtrip_device on raw device addresses (interleaved float32 in, float32 out); returns the
+        number of samples written.  Queued on the context's stream, not synchronised."""
+        n = C.c_uint64()
+        check(lib.glc_roundtrip_device(self._h, C.c_void_p(d_pcm), n_samples, channels, C.c_void_p(d_out), cap,
+                                       C.byref(n)), self._h)
+        return n.value
+
+    def apply_tensor(self, x, channels: int):
+        """The round trip of a contiguous float32 CUDA torch.Tensor - interleaved 1-D, or of shape (frames,
+        channels) - into a new tensor of the same shape on the same device.  The work is queued on torch's
+        current stream (set_stream) behind whatever fills `x` there, and the result is ready for torch ops on
+        that stream: no torch.cuda.synchronize() is needed on either side.  The context's private stream is
+        restored before the call returns, which waits for the queued work (glc_ctx_set_stream).  Raises
+        GlcError where set_stream does (two HIP runtimes mapped)."""
+        import torch
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous():
+            raise TypeError("apply_tensor takes a contiguous float32 CUDA tensor")
+        if x.device.index != self.device:
+            raise GlcError(GLC_EINVAL, f"the tensor is on {x.device}, this context on device {self.device}")
+        if x.dim() == 2:
+            if x.shape[1] != channels:
+                raise GlcError(GLC_EINVAL, f"a 2-D tensor is (frames, channels): got {tuple(x.shape)} for {channels} channels")
+        elif x.dim() != 1:
+            raise GlcError(GLC_EINVAL, "the tensor is interleaved 1-D or of shape (frames, channels)")
+        out = torch.empty_like(x)
+        self.set_stream(torch.cuda.current_stream(x.device).cuda_stream)
+        try:
+            n = self.apply_device(x.data_ptr(), x.numel(), channels, out.data_ptr(), out.numel())
+        finally:
+            self.set_stream(0)
+        assert n == x.numel()
+        return out
+
+    def resident_stream(self) -> int:
+        """0 after every apply* call: a round trip leaves no stream resident on its context."""
+        return int(lib.glc_ctx_resident_stream(self._h))
+
+    def last_info(self) -> RoundTripInfo:
+        """glc_roundtrip_last_info: counts and serialized size of the stream the last apply* call encoded
+        (synchronises)."""
+        i = GlcRoundtripInfo()
+        check(lib.glc_roundtrip_last_info(self._h, C.byref(i)), self._h)
+        return RoundTripInfo(i.n_frames, i.n_raw_frames, i.total_nnz, i.serialized_bytes)
 
 
 def save_encoded(encoded: EncodedAudio, path) -> None:

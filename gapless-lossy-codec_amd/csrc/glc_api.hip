@@ -155,6 +155,14 @@ struct glc_ctx {
   DevBuf pack_meta;  // compaction scratch: loc, blk, blk_raw, totals
   DevBuf pack_blob;  // compaction: the compact blob of glc_encode / glc_frames_from_device_records
   HostBuf host_stage;  // pinned: the blob on its way to the host
+  // round trip (glc_decode_device_records, glc_roundtrip_*): everything is sized by the round
+  DevBuf rt_records;  // the round's frame records
+  DevBuf rt_rows;     // the row tables R1 builds from them (glc_kernels.h rows_from_records_bytes)
+  DevBuf rt_edge;     // two hops: the output hops the gapless trim cuts, before their kept part is copied on
+  DevBuf rt_stats;    // counters of the stream the last round trip encoded (glc_kernels.h launch_rows_from_records)
+  DevBuf rt_out;      // glc_roundtrip: the trimmed output on its way to the host
+  uint64_t rt_info_frames = 0;  // frames of that stream (0: no round trip has completed)
+  uint32_t rt_info_ch = 0;
   HostBuf batch_stage;  // pinned: a round of glc_encode_batch's short clips going up, then its payload coming down / of glc_decode_batch's rows going up
   std::string err;
   // decode session (decode_prepare / round_launch): device-resident sparse rows + position
@@ -371,6 +379,11 @@ void glc_ctx_destroy(glc_ctx *ctx) {
   ctx->dec_meta.release();
   ctx->dec_plan.release();
   ctx->pack_meta.release();
+  ctx->rt_records.release();
+  ctx->rt_rows.release();
+  ctx->rt_edge.release();
+  ctx->rt_stats.release();
+  ctx->rt_out.release();
   ctx->pack_blob.release();
   ctx->host_stage.release();
   ctx->batch_stage.release();
@@ -1962,6 +1975,356 @@ int glc_decode_batch(glc_ctx *ctx, const glc_frames *const *in, uint64_t n_strea
 int glc_decode_batch_i16(glc_ctx *ctx, const glc_frames *const *in, uint64_t n_streams, int16_t *pcm_out, uint64_t cap,
                          uint64_t *offsets) {
   return decode_batch_to_host(ctx, "glc_decode_batch_i16", in, n_streams, pcm_out, cap, offsets);
+}
+
+// ------------------------------------------------------------------------------ round trip
+
+extern "C++" {
+namespace {
+
+// Grow a workspace of the round trip.  Work queued earlier may still use the old allocation: the stream is
+// drained first - only when the buffer has to grow, so that a repeated call of the same size only queues.
+int rt_reserve(glc_ctx *ctx, DevBuf &b, size_t bytes) {
+  if (bytes <= b.cap) return GLC_OK;
+  GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  GLC_HIP(ctx, b.reserve(bytes));
+  return GLC_OK;
+}
+
+// A decode of `n_frames` frames of `ch` channels from records on the device, in rounds of `round` frames, into
+// the samples `trim` keeps.
+struct RtGeom {
+  uint32_t ch;
+  uint64_t n_frames, round, per_hop;
+  glc::Trim trim;
+};
+
+// Every call of the family: no decode session survives it, no stream is resident afterwards.
+void rt_forget_streams(glc_ctx *ctx) {
+  ctx->stream_open = false;
+  ctx->dec_uid = 0;
+  ctx->plan_uid = 0;
+}
+
+// Workspaces of the decode half of a round.
+int rt_prepare(glc_ctx *ctx, const RtGeom &g) {
+  const size_t slot = static_cast<size_t>(g.ch) * glc::kFrame;
+  int rc = rt_reserve(ctx, ctx->blocks, (g.round + 1) * slot * sizeof(float));
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rt_rows, glc::rows_from_records_bytes(static_cast<uint32_t>(g.round * g.ch)));
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rt_edge, 2 * g.per_hop * sizeof(float));
+  if (rc == GLC_OK) rc = reserve_d1_plan(ctx, g.round, g.ch);
+  return rc;
+}
+
+// Hops [h0, h1) of the un-trimmed stream, whose frames are in the block ring (frame h0 - 1 in slot 0), into
+// the TRIMMED output: hops that lie inside the kept window [trim.start, trim.start + trim.n) are
+// overlap-added straight to their place in d_out; the at most two hops the window cuts go through a
+// hop-sized buffer, and only their kept part is copied on.  Nothing outside d_out[0 .. trim.n) is written.
+template <typename T>
+int rt_emit_hops(glc_ctx *ctx, const RtGeom &g, uint64_t h0, uint64_t h1, T *d_out) {
+  const float *blocks = static_cast<const float *>(ctx->blocks.p);
+  const int64_t blk0 = static_cast<int64_t>(h0) - 1;
+  const uint64_t lo = g.trim.start, hi = g.trim.start + g.trim.n;
+  if (g.trim.n == 0) return GLC_OK;
+  const uint64_t full_lo = std::max(h0, (lo + g.per_hop - 1) / g.per_hop), full_hi = std::min(h1, hi / g.per_hop);
+  if (full_hi > full_lo)
+    GLC_HIP(ctx, launch_d2(blocks, blk0, g.n_frames, g.ch, full_lo, full_hi, d_out + (full_lo * g.per_hop - lo), ctx->stream));
+  const uint64_t cut[2] = {lo / g.per_hop, hi / g.per_hop};  // the hops that hold the window's two ends
+  for (int i = 0; i < 2; ++i) {
+    const uint64_t h = cut[i];
+    if (h < h0 || h >= h1 || (i == 1 && cut[1] == cut[0])) continue;
+    if (h >= full_lo && h < full_hi) continue;  // an end on a hop boundary cuts nothing
+    const uint64_t a = std::max(lo, h * g.per_hop), b = std::min(hi, (h + 1) * g.per_hop);
+    if (b <= a) continue;
+    T *edge = static_cast<T *>(ctx->rt_edge.p) + static_cast<size_t>(i) * g.per_hop;
+    GLC_HIP(ctx, launch_d2(blocks, blk0, g.n_frames, g.ch, h, h + 1, edge, ctx->stream));
+    GLC_HIP(ctx, hipMemcpyAsync(d_out + (a - lo), edge + (a - h * g.per_hop), (b - a) * sizeof(T), hipMemcpyDeviceToDevice,
+                                ctx->stream));
+  }
+  return GLC_OK;
+}
+
+// One round: the records of frames [f0, f0 + nf) at `recs` -> row tables (R1) -> D1 into block slots 1.. ->
+// the round's hops (+ the bare tail behind the last frame) into the trimmed output -> the last block to
+// slot 0 for the next round.  `stats`: device counters of glc_roundtrip_last_info, or null.
+template <typename T>
+int rt_decode_round(glc_ctx *ctx, const RtGeom &g, const uint8_t *recs, uint64_t f0, uint64_t nf, uint64_t *stats, T *d_out) {
+  const size_t slot = static_cast<size_t>(g.ch) * glc::kFrame;
+  float *blocks = static_cast<float *>(ctx->blocks.p);
+  const uint32_t M = static_cast<uint32_t>(nf * g.ch);
+  glc::DecodeRows rows{};
+  GLC_HIP(ctx, glc::launch_rows_from_records(recs, M, g.ch, ctx->rt_rows.p, stats, ctx->stream, &rows));
+  GLC_HIP(ctx, glc::launch_imdct_rows(ctx->dev, rows, 0, M, g.ch, blocks + slot, ctx->stream, ctx->d1_variant, ctx->dec_plan.p,
+                                      ctx->dec_plan.p ? ctx->dec_plan_groups : 0, false));
+  const bool last = f0 + nf == g.n_frames;
+  const int rc = rt_emit_hops(ctx, g, f0, f0 + nf + (last ? 1 : 0), d_out);
+  if (rc != GLC_OK) return rc;
+  if (!last)
+    GLC_HIP(ctx, hipMemcpyAsync(blocks, blocks + nf * slot, slot * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+  return GLC_OK;
+}
+
+RtGeom rt_geom(uint64_t n_frames, uint32_t ch, const glc_plan &plan, uint64_t n_samples) {
+  RtGeom g;
+  g.ch = ch;
+  g.n_frames = n_frames;
+  g.round = std::max<uint64_t>(1, std::min<uint64_t>(kDecodeChunkFrames, n_frames));
+  g.per_hop = static_cast<uint64_t>(glc::kHop) * ch;
+  g.trim = glc::gapless_trim(n_frames, ch, plan.encoder_delay, n_samples);
+  return g;
+}
+
+// Arguments every call of the family checks the same way.  *n_out is filled before the capacity is judged.
+int rt_check(glc_ctx *ctx, const char *who, uint64_t n_samples, uint16_t channels, const void *out, size_t out_align,
+             uint64_t cap, uint64_t *n_out, glc_plan *plan, RtGeom *g) {
+  const std::string w(who);
+  if (channels == 0) return fail(ctx, GLC_EINVAL, w + ": channels == 0");
+  *plan = glc::plan_encode(n_samples, channels);
+  if (plan->n_frames == 0)
+    return fail(ctx, GLC_EINVAL, w + ": the reference encoder panics on this input (<= 512 samples per channel, or ragged channels)");
+  if (plan->n_frames * channels > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, w + ": stream too long");
+  *g = rt_geom(plan->n_frames, channels, *plan, n_samples);
+  if (n_out) *n_out = g->trim.n;
+  if (cap < g->trim.n) return fail(ctx, GLC_EINVAL, w + ": output buffer too small");
+  if (!out) return fail(ctx, GLC_EINVAL, w + ": null argument");
+  if (reinterpret_cast<uintptr_t>(out) % out_align) return fail(ctx, GLC_EINVAL, w + ": output pointer not aligned to its sample size");
+  return GLC_OK;
+}
+
+// Encode + decode of the frames [f0, f0 + nf) of device-resident PCM: K1, K2 (K3) into the round's record
+// buffer, then rt_decode_round of it.
+template <typename T>
+int rt_roundtrip_round(glc_ctx *ctx, const RtGeom &g, const float *d_pcm, uint64_t n_samples, uint64_t f0, uint64_t nf, T *d_out) {
+  const uint64_t t_count = (n_samples + g.ch - 1) / g.ch;
+  int rc = encode_range_on(ctx, ctx->stream, ctx->coef, d_pcm, 0, t_count, n_samples, static_cast<uint16_t>(g.ch), f0, f0 + nf,
+                           ctx->rt_records.p, nullptr);
+  if (rc != GLC_OK) return rc;
+  return rt_decode_round(ctx, g, static_cast<const uint8_t *>(ctx->rt_records.p), f0, nf, static_cast<uint64_t *>(ctx->rt_stats.p),
+                         d_out);
+}
+
+constexpr size_t kRtStatBytes = size_t(glc::kRowStatSlots) * glc::kRowStatStride * sizeof(uint64_t);
+
+// Workspaces of the encode half and the counters; the counters are zeroed in stream order.
+int rt_roundtrip_begin(glc_ctx *ctx, const RtGeom &g) {
+  ctx->rt_info_frames = 0;
+  int rc = rt_prepare(ctx, g);
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rt_records, g.round * glc::record_bytes(g.ch));
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->coef, g.round * g.ch * glc::kHop * sizeof(float));
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rt_stats, kRtStatBytes);
+  if (rc != GLC_OK) return rc;
+  GLC_HIP(ctx, hipMemsetAsync(ctx->rt_stats.p, 0, kRtStatBytes, ctx->stream));
+  return GLC_OK;
+}
+
+void rt_roundtrip_end(glc_ctx *ctx, const RtGeom &g) {
+  ctx->rt_info_frames = g.n_frames;
+  ctx->rt_info_ch = g.ch;
+}
+
+// glc_roundtrip behind its argument checks.  T: sample type of the output.
+template <typename T>
+int rt_roundtrip_host(glc_ctx *ctx, const void *pcm, glc_pcm_format fmt, uint32_t bits, uint64_t n_samples, const RtGeom &g,
+                      const glc_plan &plan, T *pcm_out) {
+  const bool is_int = fmt != GLC_PCM_F32;
+  const size_t elem = fmt == GLC_PCM_S16 ? 2 : 4;
+  int rc = rt_roundtrip_begin(ctx, g);
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->pcm, static_cast<size_t>(n_samples) * sizeof(float));
+  if (rc == GLC_OK && is_int) rc = rt_reserve(ctx, ctx->pcm_int, static_cast<size_t>(n_samples) * elem);
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rt_out, std::max<size_t>(g.trim.n, 1) * sizeof(T));
+  if (rc == GLC_OK) rc = ensure_copy_objects(ctx);
+  if (rc != GLC_OK) return rc;
+  if (!ctx->down_stream) GLC_HIP(ctx, hipStreamCreateWithFlags(&ctx->down_stream, hipStreamNonBlocking));
+  // the staging buffers are shared with the other host-boundary calls, some of which work on streams of their own
+  GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  float *d_pcm = static_cast<float *>(ctx->pcm.p);
+  uint8_t *d_int = static_cast<uint8_t *>(ctx->pcm_int.p);
+  T *d_out = static_cast<T *>(ctx->rt_out.p);
+  const uint8_t *src = static_cast<const uint8_t *>(pcm);
+  const uint64_t n_rounds = (g.n_frames + g.round - 1) / g.round;
+  // Three stages, as in glc_encode: round i + 1's samples go up (copy stream; a helper thread when there is more
+  // than one round, because a copy from pageable memory blocks its caller), round i's kernels run, round i - 1's
+  // output comes down (download stream, this thread) - PCIe carries both directions at once.  A stage waits on
+  // the HOST for what it depends on and only then queues (nothing is queued behind an unfinished dependency);
+  // copies from and to pageable memory have completed when they return.
+  struct Progress {
+    std::mutex mu;
+    std::condition_variable cv;
+    uint64_t uploaded = 0;
+    hipError_t err = hipSuccess;
+    bool stop = false;
+  } prog;
+  auto upload_all = [&] {
+    DeviceGuard dg(ctx->device);
+    uint64_t copied = 0;
+    for (uint64_t i = 0; i < n_rounds; ++i) {
+      const uint64_t f0 = i * g.round, nf = std::min(g.round, g.n_frames - f0);
+      const uint64_t hi = std::min<uint64_t>(n_samples, glc::frame_sample_window(f0, f0 + nf, plan.per_channel).hi * g.ch);
+      hipError_t e = hipSuccess;
+      if (hi > copied) {
+        if (!is_int) {
+          e = hipMemcpyAsync(d_pcm + copied, src + copied * 4, (hi - copied) * 4, hipMemcpyHostToDevice, ctx->copy_stream);
+        } else {
+          e = hipMemcpyAsync(d_int + copied * elem, src + copied * elem, (hi - copied) * elem, hipMemcpyHostToDevice, ctx->copy_stream);
+          if (e == hipSuccess)
+            e = glc::launch_pcm_widen(d_int + copied * elem, fmt == GLC_PCM_S32, bits, hi - copied, d_pcm + copied, ctx->copy_stream);
+        }
+        copied = hi;
+      }
+      if (e == hipSuccess) e = hipStreamSynchronize(ctx->copy_stream);
+      std::lock_guard<std::mutex> lk(prog.mu);
+      if (e != hipSuccess) prog.err = e;
+      else ++prog.uploaded;
+      prog.cv.notify_all();
+      if (e != hipSuccess || prog.stop) return;
+    }
+  };
+  auto download = [&](uint64_t i) -> hipError_t {  // the trimmed samples round i wrote
+    const uint64_t f0 = i * g.round, nf = std::min(g.round, g.n_frames - f0);
+    const bool last = f0 + nf == g.n_frames;
+    const uint64_t lo = std::max(g.trim.start, f0 * g.per_hop);
+    const uint64_t hi = std::min(g.trim.start + g.trim.n, (f0 + nf + (last ? 1 : 0)) * g.per_hop);
+    hipError_t e = hipEventSynchronize(ctx->ev_dec[i & 1]);
+    if (e == hipSuccess && hi > lo)
+      e = hipMemcpyAsync(pcm_out + (lo - g.trim.start), d_out + (lo - g.trim.start), (hi - lo) * sizeof(T), hipMemcpyDeviceToHost,
+                         ctx->down_stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->down_stream);
+    return e;
+  };
+  auto rounds = [&]() -> int {
+    for (uint64_t i = 0; i < n_rounds; ++i) {
+      {
+        std::unique_lock<std::mutex> lk(prog.mu);
+        prog.cv.wait(lk, [&] { return prog.uploaded > i || prog.err != hipSuccess; });
+        if (prog.err != hipSuccess) return hip_fail(ctx, prog.err, "glc_roundtrip: upload");
+      }
+      const uint64_t f0 = i * g.round, nf = std::min(g.round, g.n_frames - f0);
+      const int rrc = rt_roundtrip_round(ctx, g, d_pcm, n_samples, f0, nf, d_out);
+      if (rrc != GLC_OK) return rrc;
+      GLC_HIP(ctx, hipEventRecord(ctx->ev_dec[i & 1], ctx->stream));
+      if (i > 0) GLC_HIP(ctx, download(i - 1));
+    }
+    GLC_HIP(ctx, download(n_rounds - 1));
+    return GLC_OK;
+  };
+  if (n_rounds == 1) {
+    upload_all();
+    rc = rounds();
+  } else {
+    try {
+      if (!ctx->enc_up) ctx->enc_up.reset(new Worker);
+      ctx->enc_up->submit(upload_all);
+    } catch (...) {  // std::system_error / std::bad_alloc from starting the helper: nothing has been started
+      return fail(ctx, GLC_ENOMEM, "glc_roundtrip: cannot start a helper thread");
+    }
+    rc = rounds();
+    {
+      std::lock_guard<std::mutex> lk(prog.mu);
+      prog.stop = true;
+    }
+    ctx->enc_up->wait();  // it reads this frame's variables
+  }
+  if (rc != GLC_OK) return rc;
+  rt_roundtrip_end(ctx, g);
+  return GLC_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int glc_decode_device_records(glc_ctx *ctx, const void *d_records, uint64_t n_frames, uint64_t n_samples, uint16_t channels,
+                              float *d_out, uint64_t cap, uint64_t *n_out) {
+  if (!ctx) return GLC_EINVAL;
+  if (n_out) *n_out = 0;
+  if (!d_records) return fail(ctx, GLC_EINVAL, "glc_decode_device_records: null argument");
+  if (reinterpret_cast<uintptr_t>(d_records) & 15u)
+    return fail(ctx, GLC_EINVAL, "glc_decode_device_records: the records are not 16-byte aligned");
+  glc_plan plan;
+  RtGeom g;
+  int rc = rt_check(ctx, "glc_decode_device_records", n_samples, channels, d_out, sizeof(float), cap, n_out, &plan, &g);
+  if (rc == GLC_OK && plan.n_frames != n_frames) {
+    if (n_out) *n_out = 0;
+    rc = fail(ctx, GLC_EINVAL, "glc_decode_device_records: record count does not match the stream length");
+  }
+  if (rc != GLC_OK) return rc;
+  DeviceGuard guard(ctx->device);
+  rt_forget_streams(ctx);
+  rc = rt_prepare(ctx, g);
+  const uint64_t rec = glc::record_bytes(channels);
+  for (uint64_t f0 = 0; f0 < n_frames && rc == GLC_OK; f0 += g.round)
+    rc = rt_decode_round(ctx, g, static_cast<const uint8_t *>(d_records) + f0 * rec, f0, std::min(g.round, n_frames - f0), nullptr,
+                         d_out);
+  return rc;
+}
+
+int glc_roundtrip_device(glc_ctx *ctx, const float *d_pcm, uint64_t n_samples, uint16_t channels, float *d_out, uint64_t cap,
+                         uint64_t *n_out) {
+  if (!ctx) return GLC_EINVAL;
+  if (n_out) *n_out = 0;
+  if (!d_pcm) return fail(ctx, GLC_EINVAL, "glc_roundtrip_device: null argument");
+  glc_plan plan;
+  RtGeom g;
+  int rc = rt_check(ctx, "glc_roundtrip_device", n_samples, channels, d_out, sizeof(float), cap, n_out, &plan, &g);
+  if (rc != GLC_OK) return rc;
+  DeviceGuard guard(ctx->device);
+  rt_forget_streams(ctx);
+  rc = rt_roundtrip_begin(ctx, g);
+  for (uint64_t f0 = 0; f0 < g.n_frames && rc == GLC_OK; f0 += g.round)
+    rc = rt_roundtrip_round(ctx, g, d_pcm, n_samples, f0, std::min(g.round, g.n_frames - f0), d_out);
+  if (rc == GLC_OK) rt_roundtrip_end(ctx, g);
+  return rc;
+}
+
+int glc_roundtrip(glc_ctx *ctx, const void *pcm, glc_pcm_format fmt, uint32_t bits, uint64_t n_samples, uint16_t channels,
+                  void *pcm_out, glc_pcm_format out_fmt, uint64_t cap, uint64_t *n_out) {
+  if (!ctx) return GLC_EINVAL;
+  if (n_out) *n_out = 0;
+  if (!pcm) return fail(ctx, GLC_EINVAL, "glc_roundtrip: null argument");
+  if (fmt != GLC_PCM_S16 && fmt != GLC_PCM_S32 && fmt != GLC_PCM_F32) return fail(ctx, GLC_EINVAL, "glc_roundtrip: unknown sample format");
+  if (fmt != GLC_PCM_F32 && (bits == 0 || bits > (fmt == GLC_PCM_S16 ? 16u : 32u)))
+    return fail(ctx, GLC_EINVAL, "glc_roundtrip: bits must be 1..16 for 16-bit samples, 1..32 for 32-bit ones");
+  if (out_fmt != GLC_PCM_F32 && out_fmt != GLC_PCM_S16)
+    return fail(ctx, GLC_EINVAL, "glc_roundtrip: the output is GLC_PCM_F32 or GLC_PCM_S16");
+  glc_plan plan;
+  RtGeom g;
+  const size_t out_elem = out_fmt == GLC_PCM_S16 ? 2 : 4;
+  int rc = rt_check(ctx, "glc_roundtrip", n_samples, channels, pcm_out, out_elem, cap, n_out, &plan, &g);
+  if (rc != GLC_OK) return rc;
+  // At the host boundary a round is what the copies are cut into, and the first upload and the last download
+  // are hidden by nothing: rounds of 4096 ROWS - the smallest launch the large transform kernel takes
+  // (launch_mdct_forward), half a device round for stereo.
+  g.round = std::max<uint64_t>(1, std::min<uint64_t>(g.round, 4096 / channels));
+  DeviceGuard guard(ctx->device);
+  rt_forget_streams(ctx);
+  rc = out_fmt == GLC_PCM_S16 ? rt_roundtrip_host(ctx, pcm, fmt, bits, n_samples, g, plan, static_cast<int16_t *>(pcm_out))
+                              : rt_roundtrip_host(ctx, pcm, fmt, bits, n_samples, g, plan, static_cast<float *>(pcm_out));
+  if (rc != GLC_OK) {  // nothing may still be in flight out of or into the caller's memory
+    (void)hipStreamSynchronize(ctx->stream);
+    if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
+    if (ctx->down_stream) (void)hipStreamSynchronize(ctx->down_stream);
+  }
+  return rc;
+}
+
+int glc_roundtrip_last_info(glc_ctx *ctx, glc_roundtrip_info *out) {
+  if (!ctx || !out) return fail(ctx, GLC_EINVAL, "glc_roundtrip_last_info: null argument");
+  if (ctx->rt_info_frames == 0 || !ctx->rt_stats.p)
+    return fail(ctx, GLC_EINVAL, "glc_roundtrip_last_info: no round trip has completed on this context");
+  DeviceGuard guard(ctx->device);
+  uint64_t slots[glc::kRowStatSlots * glc::kRowStatStride];
+  GLC_HIP(ctx, hipMemcpyAsync(slots, ctx->rt_stats.p, sizeof slots, hipMemcpyDeviceToHost, ctx->stream));
+  GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  uint64_t s[2] = {0, 0};
+  for (uint32_t i = 0; i < glc::kRowStatSlots; ++i) s[0] += slots[i * glc::kRowStatStride], s[1] += slots[i * glc::kRowStatStride + 1];
+  const uint64_t nf = ctx->rt_info_frames, ch = ctx->rt_info_ch, n_raw = s[1], lists = (nf - n_raw) * ch;
+  out->n_frames = nf;
+  out->n_raw_frames = n_raw;
+  out->total_nnz = s[0];
+  // glc_serialized_size: header, per frame {two Vec lengths, Option tag}, per list its length, the pairs and
+  // scale factors of compressed frames, {length, planar i16 block} of raw ones, gapless info
+  out->serialized_bytes = (4 + 2 + 8 + 8) + nf * (8 + 8 + 1) + lists * 8 + s[0] * 4 + lists * 4 +
+                          n_raw * (8 + 2ull * glc::kFrame * ch) + (4 + 4 + 8);
+  return GLC_OK;
 }
 
 uint64_t glc_ctx_resident_stream(const glc_ctx *ctx) { return ctx ? ctx->dec_uid : 0; }

@@ -78,6 +78,19 @@ struct DecodeRows {
   const int16_t *raw_pool;
   uint32_t any_raw;  // the stream has rows of raw frames (their blocks are written by a kernel of their own)
 };
+// R1: the DecodeRows of M = n_frames * ch rows of frame records that are on the device, built there:
+// the ascending (k | q << 16) lists of the rows of compressed frames at a fixed stride (row_begin[m] =
+// 1024 m), row_scale from the record, rows of raw frames pointing at their frame's planar i16 block
+// inside `records` (raw_pool = records, 16-byte aligned), row_raw = -1 for the others.  `workspace`:
+// rows_from_records_bytes(M) bytes that stay untouched for as long as *rows is in use.  `stats`: null,
+// or kRowStatSlots pairs of device counters, kRowStatStride uint64_t apart, that are ADDED to: the sums over
+// the slots of [0] and of [1] are {list entries, raw frames}.  One launch, no synchronisation:
+// *rows may be handed to launch_imdct_rows on the same stream at once (any_raw is set: the host does
+// not know).
+constexpr uint32_t kRowStatSlots = 64, kRowStatStride = 16;  // a 128-byte line per slot
+uint64_t rows_from_records_bytes(uint32_t M);
+hipError_t launch_rows_from_records(const uint8_t *records, uint32_t M, uint32_t ch, void *workspace, uint64_t *stats,
+                                    hipStream_t s, DecodeRows *rows);
 // variant (include/glc_debug.h): 0 = shipped (k_imdct_plan + k_imdct_apply, absent row pairs skipped
 // by scalar branches); 1 = one row per workgroup (the cross-check kernel); 2 = plan + apply without
 // the skip; 3 = without the issue-priority schedule; 4 = skipping in row pairs only.  All but 1 need a workspace `plan` of imdct_plan_bytes(plan_groups) bytes,

@@ -1139,6 +1139,91 @@ __global__ __launch_bounds__(256) void k_pack_rows(const unsigned char *__restri
 }
 
 // ------------------------------------------------------------------------------------------
+// R1: frame records -> the row tables D1 reads (DecodeRows), without the host: what
+// glc_frames_from_device_records + build_row_table + an upload give for the same records, for a decode
+// queued right behind the encode that wrote them (glc_decode_device_records, glc_roundtrip_*).
+// One wave per row.  Row m owns pairs [1024 m, 1024 m + 1024): a fixed stride instead of a scan over the
+// rows, so nothing here waits for another workgroup (4 KiB of workspace per row, of which a tonal row
+// touches a few hundred bytes).  Lane l owns the 16 bins 16 l .. 16 l + 15 of the dense row (two 16-byte
+// loads); an inclusive shuffle scan of the lanes' non-zero counts gives every lane the place of its
+// first pair, and since a lane's bins are contiguous and the lanes ascend, the list is in ascending k
+// (src/codec.rs:303-306) with no sorting.  A record whose nnz field disagrees with its row is read as
+// k_pack_rows reads it: the first min(nnz, 1024) non-zeros; where the row holds fewer, k_pack_rows pads
+// its slot with entries every reader ignores (idx 0xFFFF) - here the list is simply that much shorter.
+// Rows of raw frames point into the records themselves (the frame's planar i16 block is its raw_pcm,
+// Q1): no copy.  stats (optional): {sum of min(nnz, 1024) over rows of compressed frames, raw frames},
+// added to - one pair of atomics per workgroup, spread over kRowStatSlots counter pairs a cache line apart
+// (2048 workgroups adding to ONE address took 21 us of the kernel's 30: same-address atomics queue up in L2).
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_rows_from_records(const unsigned char *__restrict__ records, unsigned M,
+                                                            unsigned ch, unsigned long long rec_bytes,
+                                                            unsigned long long hdr_bytes, unsigned *__restrict__ pairs,
+                                                            unsigned long long *__restrict__ row_begin,
+                                                            unsigned *__restrict__ row_cnt, float *__restrict__ row_scale,
+                                                            long long *__restrict__ row_raw,
+                                                            unsigned long long *__restrict__ row_raw_len,
+                                                            unsigned long long *__restrict__ stats) {
+  __shared__ unsigned s_nnz[4], s_rawf[4];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const unsigned m = blockIdx.x * 4 + w;
+  unsigned stat_nnz = 0, stat_raw = 0;
+  if (m < M) {
+    const unsigned frame = m / ch, c = m - frame * ch;
+    const unsigned char *rec = records + static_cast<size_t>(frame) * rec_bytes;
+    const unsigned raw = *reinterpret_cast<const unsigned *>(rec);
+    const float scale = *reinterpret_cast<const float *>(rec + 8 + 8 * c);
+    const unsigned room = min(*reinterpret_cast<const unsigned *>(rec + 8 + 8 * c + 4), static_cast<unsigned>(kHopI));
+    unsigned n_row = 0;
+    if (raw) {
+      stat_raw = c == 0 ? 1u : 0u;
+    } else {
+      stat_nnz = room;
+      const uint4 *src = reinterpret_cast<const uint4 *>(rec + hdr_bytes + static_cast<size_t>(c) * (kFrameI * 2) + lane * 32);
+      const uint4 a = src[0], b = src[1];
+      const unsigned wd[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};  // bins 16 lane + 2 j (low half), + 2 j + 1 (high half)
+      unsigned cnt = 0;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) cnt += ((wd[j] & 0xFFFFu) ? 1u : 0u) + ((wd[j] >> 16) ? 1u : 0u);
+      unsigned incl = cnt;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const unsigned v = __shfl_up(incl, off);
+        if (lane >= off) incl += v;
+      }
+      n_row = min(static_cast<unsigned>(__shfl(incl, 63)), room);
+      unsigned pos = incl - cnt;
+      unsigned *dst = pairs + static_cast<size_t>(m) * kHopI;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const unsigned q = (j & 1) ? wd[j >> 1] >> 16 : wd[j >> 1] & 0xFFFFu;
+        if (q != 0) {
+          if (pos < room) dst[pos] = static_cast<unsigned>(lane * 16 + j) | (q << 16);
+          ++pos;
+        }
+      }
+    }
+    if (lane == 0) {
+      row_begin[m] = static_cast<unsigned long long>(m) * kHopI;
+      row_cnt[m] = n_row;
+      row_scale[m] = scale;
+      // offset, in i16, of the frame's payload from `records` (the raw pool): header sizes are multiples of 16
+      row_raw[m] = raw ? static_cast<long long>((static_cast<unsigned long long>(frame) * rec_bytes + hdr_bytes) >> 1) : -1ll;
+      row_raw_len[m] = raw ? static_cast<unsigned long long>(kFrameI) * ch : 0ull;
+    }
+  }
+  if (stats) {  // kernel argument: uniform
+    if (lane == 0) s_nnz[w] = stat_nnz, s_rawf[w] = stat_raw;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const unsigned n = s_nnz[0] + s_nnz[1] + s_nnz[2] + s_nnz[3], r = s_rawf[0] + s_rawf[1] + s_rawf[2] + s_rawf[3];
+      unsigned long long *slot = stats + static_cast<size_t>(blockIdx.x % kRowStatSlots) * kRowStatStride;
+      if (n) atomicAdd(&slot[0], static_cast<unsigned long long>(n));
+      if (r) atomicAdd(&slot[1], static_cast<unsigned long long>(r));
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // Clock probe (include/glc_debug.h, measurement only): ONE wave that sleeps beside whatever else runs
 // on the device and reads the shader-clock counter (s_memtime) against the constant 100 MHz counter
 // (s_memrealtime) over `ticks_100mhz`: shader cycles / reference ticks x 100 MHz = the clock the chip
@@ -1311,6 +1396,44 @@ hipError_t launch_compact_batch(const uint8_t *records, uint32_t M, uint32_t ch,
   static_assert(sizeof(FrameMap) == sizeof(uint2), "FrameMap is read as a uint2");
   return compact_rows(records, M, ch, n_frames, loc, blk, blk_raw, totals, blob, o_israw, o_scale, o_cnt, o_pairs,
                       reinterpret_cast<const uint2 *>(fmap), reinterpret_cast<unsigned long long *>(dir), s);
+}
+
+namespace {
+inline uint64_t align256(uint64_t v) { return (v + 255ull) & ~255ull; }
+}  // namespace
+
+uint64_t rows_from_records_bytes(uint32_t M) {
+  const uint64_t m = M ? M : 1;
+  // pairs | row_begin | row_cnt | row_scale | row_raw | row_raw_len, each 256-byte aligned
+  return align256(m * kHopI * 4ull) + 3 * align256(m * 8ull) + 2 * align256(m * 4ull);
+}
+
+hipError_t launch_rows_from_records(const uint8_t *records, uint32_t M, uint32_t ch, void *workspace, uint64_t *stats,
+                                    hipStream_t s, DecodeRows *rows) {
+  if (!records || !workspace || !rows || ch == 0 || (reinterpret_cast<uintptr_t>(records) & 15u)) return hipErrorInvalidValue;
+  const uint64_t m = M ? M : 1;
+  uint8_t *p = static_cast<uint8_t *>(workspace);
+  auto take = [&](uint64_t bytes) {
+    uint8_t *at = p;
+    p += align256(bytes);
+    return at;
+  };
+  auto *pairs = reinterpret_cast<unsigned *>(take(m * kHopI * 4ull));
+  auto *row_begin = reinterpret_cast<unsigned long long *>(take(m * 8ull));
+  auto *row_cnt = reinterpret_cast<unsigned *>(take(m * 4ull));
+  auto *row_scale = reinterpret_cast<float *>(take(m * 4ull));
+  auto *row_raw = reinterpret_cast<long long *>(take(m * 8ull));
+  auto *row_raw_len = reinterpret_cast<unsigned long long *>(take(m * 8ull));
+  // any_raw: the host does not know, so the raw-row kernel is always launched (it returns at once for
+  // the rows of compressed frames)
+  *rows = DecodeRows{pairs, reinterpret_cast<const uint64_t *>(row_begin), row_cnt, row_scale,
+                     reinterpret_cast<const int64_t *>(row_raw), reinterpret_cast<const uint64_t *>(row_raw_len),
+                     reinterpret_cast<const int16_t *>(records), 1u};
+  if (M == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_rows_from_records, dim3((M + 3) / 4), dim3(256), 0, s, records, M, ch,
+                     static_cast<unsigned long long>(record_bytes(ch)), static_cast<unsigned long long>(record_header_bytes(ch)),
+                     pairs, row_begin, row_cnt, row_scale, row_raw, row_raw_len, reinterpret_cast<unsigned long long *>(stats));
+  return hipGetLastError();
 }
 
 uint64_t imdct_plan_bytes(uint32_t groups) {

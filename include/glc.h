@@ -453,6 +453,60 @@ int glc_encode_batch_int(glc_ctx *ctx, const void *const *pcm, glc_pcm_format fm
 int glc_decode_batch_i16(glc_ctx *ctx, const glc_frames *const *in, uint64_t n_streams, int16_t *pcm_out,
                          uint64_t cap, uint64_t *offsets);
 
+/* ---- round trip: what the codec does to audio, without a stream on the host ---------------- */
+
+/* The reference's own tests are "encode, decode, compare" (tests/test_codec.rs), and a lossy codec is a
+ * degradation stage for whoever trains on audio: PCM in, degraded PCM out.  After an encode the frame
+ * records are in device memory and hold everything the decoder reads, so the calls below build the
+ * decoder's row tables from them ON THE DEVICE (one small kernel per round of 4096 frames) instead of
+ * compacting, downloading, assembling an EncodedAudio, walking it and uploading its rows again.  Their
+ * samples are bit for bit those of glc_decode(glc_encode(..)).
+ * All of them leave no stream resident on the context (glc_ctx_resident_stream is 0) and close an open
+ * glc_decode_stream_* session - the rule of glc_decode_batch.  Workspaces are sized by the round, not by
+ * the stream; a call that has to grow one synchronises the stream for that, a call that finds them
+ * large enough only queues. */
+
+/* Decoder::decode of the stream that `n_frames` records at d_records describe (device memory of this
+ * context's device, 16-byte aligned, layout: glc_record_bytes; n_samples gives original_length as in
+ * glc_frames_from_device_records, whose EncodedAudio this decodes - where a record's nnz field and its
+ * dense row disagree, the first min(nnz, 1024) non-zeros count, as there).  The gapless-trimmed samples
+ * go to device memory at d_out[0 .. *n_out) (any 4-byte aligned pointer); nothing behind them is
+ * written.  *n_out is arithmetic: min(original_length, (n_frames + 1) * 1024 * channels - delay).
+ * Queued on glc_ctx_stream(ctx) and NOT synchronised; nothing is copied to the host.
+ * GLC_EINVAL: a null or misaligned pointer, a record count that does not match the stream length,
+ * cap < *n_out ("output buffer too small", *n_out filled). */
+int glc_decode_device_records(glc_ctx *ctx, const void *d_records, uint64_t n_frames, uint64_t n_samples,
+                              uint16_t channels, float *d_out, uint64_t cap, uint64_t *n_out);
+
+/* Encoder::encode + Decoder::decode of device-resident interleaved PCM into device-resident PCM:
+ * d_out[0 .. *n_out) = glc_decode(glc_encode(d_pcm[0 .. n_samples))), *n_out == n_samples for every
+ * input the encoder accepts.  Rounds of at most 4096 frames - transform, quantiser, row tables, inverse
+ * transform, overlap-add - with the overlap carried from round to round as the streaming decode
+ * carries it.  Entirely queued on glc_ctx_stream(ctx), NOT synchronised, no copy to the host.  d_pcm and
+ * d_out must not overlap.  Errors as glc_encode and as above. */
+int glc_roundtrip_device(glc_ctx *ctx, const float *d_pcm, uint64_t n_samples, uint16_t channels, float *d_out,
+                         uint64_t cap, uint64_t *n_out);
+
+/* The same at the host boundary: the samples go up once and come down once (round by round, beside the
+ * kernels of the neighbouring rounds).  fmt / bits: as glc_encode_int (GLC_PCM_F32: plain floats).
+ * out_fmt: GLC_PCM_F32 (pcm_out holds floats: what glc_decode returns) or GLC_PCM_S16 (int16_t: what
+ * glc_decode_i16 returns, narrowed on the device by the overlap-add); anything else is GLC_EINVAL.
+ * cap counts samples of the output format.  Synchronises before it returns. */
+int glc_roundtrip(glc_ctx *ctx, const void *pcm, glc_pcm_format fmt, uint32_t bits, uint64_t n_samples,
+                  uint16_t channels, void *pcm_out, glc_pcm_format out_fmt, uint64_t cap, uint64_t *n_out);
+
+/* What the last glc_roundtrip_device / glc_roundtrip on this context encoded, from a device reduction
+ * over the record headers: the counts glc_frames_info gives for glc_encode of the same samples, and
+ * serialized_bytes == glc_serialized_size of it - the bitrate without the stream.  Synchronises the
+ * context's stream.  GLC_EINVAL when no round trip has completed on this context. */
+typedef struct glc_roundtrip_info {
+  uint64_t n_frames;
+  uint64_t n_raw_frames;
+  uint64_t total_nnz;
+  uint64_t serialized_bytes;
+} glc_roundtrip_info;
+int glc_roundtrip_last_info(glc_ctx *ctx, glc_roundtrip_info *out);
+
 /* ---- tables (for inspection / parity tests) ---------------------------------------------- */
 
 /* Copies of the host tables of a context: MdctTables.cos_table [1024*2048] (row k), window

@@ -403,6 +403,63 @@ class Decoder {
   glc_ctx *ctx_ = nullptr;
 };
 
+// Encoder::encode followed by Decoder::decode as one call (glc.h glc_roundtrip): the samples of
+// decode(encode(x)), bit for bit, with no EncodedAudio assembled on the host - the decoder reads the
+// encoder's frame records where they are on the device.
+class RoundTrip {
+ public:
+  explicit RoundTrip(uint32_t sample_rate, int device = 0) { detail::check(glc_ctx_create(device, sample_rate, &ctx_)); }
+  ~RoundTrip() { glc_ctx_destroy(ctx_); }
+  RoundTrip(const RoundTrip &) = delete;
+  RoundTrip &operator=(const RoundTrip &) = delete;
+  // float samples out (what Decoder::decode returns) ...
+  std::vector<float> roundtrip(const std::vector<float> &samples, uint16_t channels) {
+    return run<float>(samples.data(), GLC_PCM_F32, 32, samples.size(), channels, GLC_PCM_F32);
+  }
+  std::vector<float> roundtrip(const std::vector<int16_t> &samples, uint16_t channels, uint32_t bits = 16) {
+    return run<float>(samples.data(), GLC_PCM_S16, bits, samples.size(), channels, GLC_PCM_F32);
+  }
+  std::vector<float> roundtrip(const std::vector<int32_t> &samples, uint32_t bits, uint16_t channels) {
+    return run<float>(samples.data(), GLC_PCM_S32, bits, samples.size(), channels, GLC_PCM_F32);
+  }
+  // ... or narrowed to 16 bits on the device (what Decoder::decode_i16 returns)
+  std::vector<int16_t> roundtrip_i16(const std::vector<float> &samples, uint16_t channels) {
+    return run<int16_t>(samples.data(), GLC_PCM_F32, 32, samples.size(), channels, GLC_PCM_S16);
+  }
+  std::vector<int16_t> roundtrip_i16(const std::vector<int16_t> &samples, uint16_t channels, uint32_t bits = 16) {
+    return run<int16_t>(samples.data(), GLC_PCM_S16, bits, samples.size(), channels, GLC_PCM_S16);
+  }
+  std::vector<int16_t> roundtrip_i16(const std::vector<int32_t> &samples, uint32_t bits, uint16_t channels) {
+    return run<int16_t>(samples.data(), GLC_PCM_S32, bits, samples.size(), channels, GLC_PCM_S16);
+  }
+  // device-resident interleaved floats in and out, queued on the context's stream and not synchronised
+  uint64_t roundtrip_device(const float *d_pcm, uint64_t n_samples, uint16_t channels, float *d_out, uint64_t cap) {
+    uint64_t n = 0;
+    detail::check(glc_roundtrip_device(ctx_, d_pcm, n_samples, channels, d_out, cap, &n), ctx_);
+    return n;
+  }
+  // counts and serialized size of the stream the last call encoded (synchronises)
+  glc_roundtrip_info last_info() {
+    glc_roundtrip_info i{};
+    detail::check(glc_roundtrip_last_info(ctx_, &i), ctx_);
+    return i;
+  }
+  void synchronize() { detail::check(glc_ctx_synchronize(ctx_), ctx_); }
+  glc_ctx *ctx() { return ctx_; }
+
+ private:
+  template <typename T>
+  std::vector<T> run(const void *pcm, glc_pcm_format fmt, uint32_t bits, uint64_t n_samples, uint16_t channels,
+                     glc_pcm_format out_fmt) {
+    std::vector<T> out(n_samples);
+    uint64_t n = 0;
+    detail::check(glc_roundtrip(ctx_, pcm, fmt, bits, n_samples, channels, out.data(), out_fmt, out.size(), &n), ctx_);
+    out.resize(n);
+    return out;
+  }
+  glc_ctx *ctx_ = nullptr;
+};
+
 // save_encoded / load_encoded — src/codec.rs:774-786
 inline void save_encoded(const EncodedAudio &e, const std::string &path) { detail::check(glc_save(e.handle(), path.c_str())); }
 inline EncodedAudio load_encoded(const std::string &path) {

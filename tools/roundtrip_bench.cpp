@@ -1,0 +1,197 @@
+// roundtrip_bench.cpp — what the device round trip saves: glc_roundtrip_device / glc_roundtrip against what a
+// caller does without them, on the same context in the same process.
+//   device-resident pair   A: glc_encode_range_device + glc_frames_from_device_records + glc_decode_device
+//                          B: glc_roundtrip_device                      (both end in glc_ctx_synchronize)
+//   host-boundary pair     A: glc_encode + glc_decode                   B: glc_roundtrip
+// Shapes: BASELINE config 2 (48 kHz stereo, 4096 frames), a 2 s clip, 10 minutes of stereo.  The arms are
+// interleaved A B A' B after a warm-up, so that clocks, buffers and neighbours on the host are the same for
+// both; A' is the parent path again, and the difference of its two medians is the run's own A/A spread.
+// Every new result is compared with the parent path's, bit for bit, before anything is timed.
+// Build: make -C gapless-lossy-codec_amd/csrc tools
+// Usage: build/roundtrip_bench [reps = 20]                 the three shapes
+//        build/roundtrip_bench reps seconds               one shape of the caller's (48 kHz stereo)
+//        build/roundtrip_bench trace tone|noise samples   3 warm-up + 10 glc_roundtrip_device calls of that many samples
+//                                                         per channel and nothing else (for a kernel + memory-copy
+//                                                         trace; no counters in that run)
+//        build/roundtrip_bench trace-records tone|noise samples   one encode, then 13 glc_decode_device_records calls
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "glc.h"
+
+static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+struct Stat {
+  double med, p10, p90;
+};
+static Stat stat(std::vector<double> v) {
+  std::sort(v.begin(), v.end());
+  return {v[v.size() / 2], v[v.size() / 10], v[v.size() * 9 / 10]};
+}
+
+#define CHECK(call)                                                                     \
+  do {                                                                                  \
+    if ((call) != GLC_OK) {                                                             \
+      std::printf("%s failed: %s\n", #call, glc_last_error(nullptr));                   \
+      return 1;                                                                         \
+    }                                                                                   \
+  } while (0)
+#define HIPCHECK(call)                                                                  \
+  do {                                                                                  \
+    const hipError_t e__ = (call);                                                      \
+    if (e__ != hipSuccess) {                                                            \
+      std::printf("%s failed: %s\n", #call, hipGetErrorString(e__));                    \
+      return 1;                                                                         \
+    }                                                                                   \
+  } while (0)
+
+// eight partials per channel (tonal: compressed frames), or uniform noise from an LCG (raw frames)
+static std::vector<float> signal(uint32_t sr, uint16_t ch, uint64_t per_ch, bool noise) {
+  std::vector<float> x(per_ch * ch);
+  if (noise) {
+    uint32_t s = 12345u;
+    for (float &v : x) {
+      s = 1664525u * s + 1013904223u;
+      v = static_cast<float>(0.5 * (s / 2147483648.0 - 1.0));
+    }
+    return x;
+  }
+  const uint64_t period = std::min<uint64_t>(per_ch, 10ull * sr);  // a 10 s segment, tiled
+  for (uint16_t c = 0; c < ch; ++c)
+    for (uint64_t t = 0; t < period; ++t) {
+      double v = 0;
+      for (int p = 0; p < 8; ++p) v += 0.05 * std::sin(2 * M_PI * (110.0 * (p + 1) * (1.0 + 0.37 * c) + 3.1 * p) * t / sr + 0.5 * p);
+      x[t * ch + c] = static_cast<float>(v);
+    }
+  for (uint64_t i = period * ch; i < x.size(); ++i) x[i] = x[i - period * ch];
+  return x;
+}
+
+static const char *verdict(double b, double a, double a2, double spread) {
+  return b < std::min(a, a2) - spread ? "FASTER" : b <= std::max(a, a2) + spread ? "not slower" : "SLOWER";
+}
+
+static int run(const char *name, uint64_t per_ch, int reps, bool trace, bool noise, bool records_only = false) {
+  const uint32_t sr = 48000;
+  const uint16_t ch = 2;
+  const uint64_t n = per_ch * ch;
+  const std::vector<float> x = signal(sr, ch, per_ch, noise);
+  glc_plan plan;
+  CHECK(glc_plan_encode(n, ch, &plan));
+  glc_ctx *ctx = nullptr;
+  CHECK(glc_ctx_create(0, sr, &ctx));
+  float *d_pcm = nullptr, *d_out = nullptr, *d_all = nullptr;
+  void *d_rec = nullptr;
+  const uint64_t cap_all = (plan.n_frames + 1) * 1024ull * ch;
+  HIPCHECK(hipMalloc(&d_pcm, n * sizeof(float)));
+  HIPCHECK(hipMalloc(&d_out, n * sizeof(float)));
+  HIPCHECK(hipMemcpy(d_pcm, x.data(), n * sizeof(float), hipMemcpyHostToDevice));
+  uint64_t got = 0, start = 0;
+  auto dev_new = [&] {
+    if (const int rc = glc_roundtrip_device(ctx, d_pcm, n, ch, d_out, n, &got)) return rc;
+    return glc_ctx_synchronize(ctx);
+  };
+  if (trace && records_only) {  // one encode, then the decode of its records alone
+    HIPCHECK(hipMalloc(&d_rec, plan.n_frames * glc_record_bytes(ch)));
+    CHECK(glc_encode_range_device(ctx, d_pcm, 0, per_ch, n, ch, 0, plan.n_frames, d_rec, nullptr));
+    for (int i = 0; i < 13; ++i) {
+      CHECK(glc_decode_device_records(ctx, d_rec, plan.n_frames, n, ch, d_out, n, &got));
+      CHECK(glc_ctx_synchronize(ctx));
+    }
+    std::printf("trace-records (%s): one encode, 3 warm-up + 10 glc_decode_device_records calls, %llu frames x %u ch\n",
+                noise ? "noise" : "tone", (unsigned long long)plan.n_frames, ch);
+    (void)hipFree(d_pcm), (void)hipFree(d_out), (void)hipFree(d_rec);
+    glc_ctx_destroy(ctx);
+    return 0;
+  }
+  if (trace) {
+    for (int i = 0; i < 13; ++i) CHECK(dev_new());
+    // (no glc_roundtrip_last_info here: its 16-byte download would be the only device-to-host copy of the run)
+    std::printf("trace (%s): 3 warm-up + 10 glc_roundtrip_device calls, %llu frames x %u ch\n", noise ? "noise" : "tone",
+                (unsigned long long)plan.n_frames, ch);
+    (void)hipFree(d_pcm), (void)hipFree(d_out);
+    glc_ctx_destroy(ctx);
+    return 0;
+  }
+  HIPCHECK(hipMalloc(&d_all, cap_all * sizeof(float)));
+  HIPCHECK(hipMalloc(&d_rec, plan.n_frames * glc_record_bytes(ch)));
+  auto dev_old = [&] {
+    glc_frames *F = nullptr;
+    int rc = glc_encode_range_device(ctx, d_pcm, 0, per_ch, n, ch, 0, plan.n_frames, d_rec, nullptr);
+    if (!rc) rc = glc_frames_from_device_records(ctx, d_rec, plan.n_frames, n, ch, &F);
+    if (!rc) rc = glc_decode_device(ctx, F, d_all, cap_all, &start, &got);
+    if (!rc) rc = glc_ctx_synchronize(ctx);
+    glc_frames_free(F);
+    return rc;
+  };
+  std::vector<float> ya(n), yb(n), yc(n);
+  auto host_old = [&] {
+    glc_frames *F = nullptr;
+    int rc = glc_encode(ctx, x.data(), n, ch, &F);
+    if (!rc) rc = glc_decode(ctx, F, ya.data(), n, &got);
+    glc_frames_free(F);
+    return rc;
+  };
+  auto host_new = [&] { return glc_roundtrip(ctx, x.data(), GLC_PCM_F32, 32, n, ch, yb.data(), GLC_PCM_F32, n, &got); };
+  // the same bits, before anything is timed
+  CHECK(host_old());
+  CHECK(host_new());
+  if (got != n || std::memcmp(ya.data(), yb.data(), n * sizeof(float))) return std::printf("%s: glc_roundtrip differs from glc_encode + glc_decode\n", name), 1;
+  CHECK(dev_new());
+  HIPCHECK(hipMemcpy(yc.data(), d_out, n * sizeof(float), hipMemcpyDeviceToHost));
+  if (got != n || std::memcmp(ya.data(), yc.data(), n * sizeof(float))) return std::printf("%s: glc_roundtrip_device differs from glc_encode + glc_decode\n", name), 1;
+  CHECK(dev_old());
+  HIPCHECK(hipMemcpy(yc.data(), d_all + start, got * sizeof(float), hipMemcpyDeviceToHost));
+  if (got != n || std::memcmp(ya.data(), yc.data(), n * sizeof(float))) return std::printf("%s: the device-resident parent path differs from glc_encode + glc_decode\n", name), 1;
+  glc_roundtrip_info info;
+  CHECK(dev_new());
+  CHECK(glc_roundtrip_last_info(ctx, &info));
+
+  auto timed = [&](auto &&fn, std::vector<double> &into) {
+    const double t0 = now_ms();
+    const int rc = fn();
+    into.push_back(now_ms() - t0);
+    return rc;
+  };
+  const int warm = std::max(3, reps / 5);
+  for (int i = 0; i < warm; ++i) { CHECK(dev_old()); CHECK(dev_new()); CHECK(host_old()); CHECK(host_new()); }
+  std::vector<double> da, db, da2, ha, hb, ha2;
+  for (int i = 0; i < reps; ++i) { CHECK(timed(dev_old, da)); CHECK(timed(dev_new, db)); CHECK(timed(dev_old, da2)); CHECK(timed(dev_new, db)); }
+  for (int i = 0; i < reps; ++i) { CHECK(timed(host_old, ha)); CHECK(timed(host_new, hb)); CHECK(timed(host_old, ha2)); CHECK(timed(host_new, hb)); }
+  const Stat A = stat(da), B = stat(db), A2 = stat(da2), H = stat(ha), N = stat(hb), H2 = stat(ha2);
+  const double ds = std::fabs(A.med - A2.med), hs = std::fabs(H.med - H2.med);
+  std::printf("%s: %llu samples x %u ch at %u Hz, %llu frames (%llu raw), %llu bytes as a stream, %d interleaved reps "
+              "(ms per call: median [p10 .. p90])\n", name, (unsigned long long)per_ch, ch, sr, (unsigned long long)info.n_frames,
+              (unsigned long long)info.n_raw_frames, (unsigned long long)info.serialized_bytes, reps);
+  std::printf("  encode_range_device + frames_from_device_records + decode_device  %.4f [%.4f .. %.4f]   again %.4f   A/A spread %.4f\n",
+              A.med, A.p10, A.p90, A2.med, ds);
+  std::printf("  glc_roundtrip_device                                              %.4f [%.4f .. %.4f]   new - parent %+.4f   parent / new %.2f  -> %s\n",
+              B.med, B.p10, B.p90, B.med - std::min(A.med, A2.med), std::min(A.med, A2.med) / B.med, verdict(B.med, A.med, A2.med, ds));
+  std::printf("  glc_encode + glc_decode                                           %.4f [%.4f .. %.4f]   again %.4f   A/A spread %.4f\n",
+              H.med, H.p10, H.p90, H2.med, hs);
+  std::printf("  glc_roundtrip                                                     %.4f [%.4f .. %.4f]   new - parent %+.4f   parent / new %.2f  -> %s\n",
+              N.med, N.p10, N.p90, N.med - std::min(H.med, H2.med), std::min(H.med, H2.med) / N.med, verdict(N.med, H.med, H2.med, hs));
+  (void)hipFree(d_pcm), (void)hipFree(d_out), (void)hipFree(d_all), (void)hipFree(d_rec);
+  glc_ctx_destroy(ctx);
+  return 0;
+}
+
+int main(int argc, char **argv) {
+  if (argc > 3 && !std::strcmp(argv[1], "trace"))
+    return run("trace", std::strtoull(argv[3], nullptr, 10), 0, true, !std::strcmp(argv[2], "noise"));
+  if (argc > 3 && !std::strcmp(argv[1], "trace-records"))
+    return run("trace-records", std::strtoull(argv[3], nullptr, 10), 0, true, !std::strcmp(argv[2], "noise"), true);
+  const int reps = argc > 1 ? std::max(5, std::atoi(argv[1])) : 20;
+  if (argc > 2) return run("custom", static_cast<uint64_t>(std::atof(argv[2]) * 48000), reps, false, false);
+  if (run("config 2 (4096 frames)", 4096ull * 1024, reps, false, false)) return 1;
+  if (run("2 s clip", 2ull * 48000, reps, false, false)) return 1;
+  if (run("10 minutes", 600ull * 48000, std::max(5, reps / 4), false, false)) return 1;
+  return 0;
+}
