@@ -45,6 +45,19 @@ class GlcRoundtripInfo(C.Structure):
     ]
 
 
+class GlcClipLayout(C.Structure):
+    """glc_clip_layout (include/glc.h): where the clips of a batch lie in one device buffer."""
+    _fields_ = [
+        ("n_clips", C.c_uint64),
+        ("channels", C.c_uint16),
+        ("planar", C.c_int),
+        ("clip_stride", C.c_uint64),
+        ("channel_stride", C.c_uint64),
+        ("length", C.c_uint64),
+        ("lengths", C.POINTER(C.c_uint64)),
+    ]
+
+
 class GlcFramesView(C.Structure):
     """glc_frames_view (include/glc.h): EncodedAudio as flat arrays."""
     _fields_ = [
@@ -195,6 +208,8 @@ SIGNATURES = {
     "glc_roundtrip": (C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.c_uint64, C.c_uint16, _vp, C.c_int, C.c_uint64,
                                 C.POINTER(C.c_uint64)]),
     "glc_roundtrip_last_info": (C.c_int, [_vp, C.POINTER(GlcRoundtripInfo)]),
+    "glc_roundtrip_batch_device": (C.c_int, [_vp, _vp, C.POINTER(GlcClipLayout), _vp, C.POINTER(GlcClipLayout)]),
+    "glc_roundtrip_batch_last_info": (C.c_int, [_vp, C.POINTER(GlcRoundtripInfo), C.c_uint64]),
     "glc_version": (C.c_char_p, []),
 }
 

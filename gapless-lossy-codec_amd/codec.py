@@ -21,7 +21,7 @@ from typing import Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import (FRAMES_HOOK, GLC_EINVAL, GLC_PCM_F32, GLC_PCM_S16, GLC_PCM_S32, GlcCompactInfo, GlcError,
+from ._lib import (FRAMES_HOOK, GLC_EINVAL, GLC_PCM_F32, GLC_PCM_S16, GLC_PCM_S32, GlcClipLayout, GlcCompactInfo, GlcError,
                    GlcFramesGather, GlcFramesView, GlcInfo, GlcPlan, GlcRoundtripInfo, check, lib)
 
 FRAME_SIZE = 2048        # src/codec.rs:15
@@ -692,6 +692,77 @@ class RoundTrip(_Ctx):
             self.set_stream(0)
         assert n == x.numel()
         return out
+
+    def apply_batch_tensor(self, x, lengths=None, planar: bool = True, out=None, out_planar: Optional[bool] = None):
+        """The round trip of every clip of a padded batch in one call (glc_roundtrip_batch_device).  `x`: a float32
+        CUDA tensor of shape (B, C, T) (planar) or (B, T, C), innermost stride 1; the other strides are taken from
+        the tensor, so a slice of something bigger works without a copy.  lengths: per clip its true number of
+        samples per channel (B integers, a sequence or a tensor; default: T for all).  In the output the first
+        lengths[i] samples of clip i are Decoder.decode(Encoder.encode(them)), bit for bit what apply_tensor gives
+        for that clip alone; no other element of it is written.
+        out: None - a new tensor like x, zero-filled, so the padding behind short clips is zero; x itself - in
+        place; or a float32 CUDA tensor of its own, whose layout is out_planar (default: as `planar`) and which
+        must not overlap x.  Queued on torch's current stream as apply_tensor queues; returns the output."""
+        import torch
+        out_planar = planar if out_planar is None else bool(out_planar)
+
+        def layout(t, is_planar, what):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+                raise TypeError(f"{what} must be a float32 CUDA tensor")
+            if t.dim() != 3:
+                raise TypeError(f"{what} must have shape (B, C, T) or (B, T, C)")
+            if t.shape[2] > 1 and t.stride(2) != 1:
+                raise TypeError(f"{what}: the innermost stride must be 1")
+            if t.device.index != self.device:
+                raise GlcError(GLC_EINVAL, f"{what} is on {t.device}, this context on device {self.device}")
+            b, c, n = (t.shape[0], t.shape[1], t.shape[2]) if is_planar else (t.shape[0], t.shape[2], t.shape[1])
+            if not 0 < c <= 0xFFFF:
+                raise GlcError(GLC_EINVAL, f"{what}: {c} channels")
+            if min(t.stride(0), t.stride(1)) < 0:
+                raise TypeError(f"{what}: negative strides")
+            lay = GlcClipLayout(b, c, 1 if is_planar else 0, t.stride(0), t.stride(1) if is_planar else 0, n, None)
+            if not is_planar and b and n > 1 and t.stride(1) != c:
+                raise TypeError(f"{what}: an interleaved clip must be dense (stride {c} between samples)")
+            return lay, n
+
+        lin, n = layout(x, planar, "x")
+        b = x.shape[0]
+        if lengths is not None:
+            lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+            if len(lens) != b or any(v < 0 or v > n for v in lens):
+                raise GlcError(GLC_EINVAL, f"lengths must hold {b} values in [0, {n}]")
+            arr = (C.c_uint64 * max(b, 1))(*lens)
+            lin.lengths = C.cast(arr, C.POINTER(C.c_uint64))
+        if out is None:
+            out = torch.zeros_like(x) if planar == out_planar else torch.zeros_like(x.transpose(1, 2), memory_format=torch.contiguous_format)
+        want = tuple(x.shape) if planar == out_planar else (x.shape[0], x.shape[2], x.shape[1])
+        lout, _ = layout(out, out_planar, "out")
+        if tuple(out.shape) != want:
+            raise GlcError(GLC_EINVAL, f"out has shape {tuple(out.shape)}, expected {want}")
+        lout.lengths = lin.lengths
+        self.set_stream(torch.cuda.current_stream(x.device).cuda_stream)
+        try:
+            check(lib.glc_roundtrip_batch_device(self._h, C.c_void_p(x.data_ptr()), C.byref(lin), C.c_void_p(out.data_ptr()),
+                                                 C.byref(lout)), self._h)
+        finally:
+            self.set_stream(0)
+        self._batch_clips = b
+        return out
+
+    def apply_batch_device(self, d_pcm: int, layout_in: "GlcClipLayout", d_out: int, layout_out: "GlcClipLayout") -> None:
+        """glc_roundtrip_batch_device on raw device addresses and glc_clip_layout structures (_lib.GlcClipLayout).
+        Queued on the context's stream, not synchronised."""
+        check(lib.glc_roundtrip_batch_device(self._h, C.c_void_p(d_pcm), C.byref(layout_in), C.c_void_p(d_out),
+                                             C.byref(layout_out)), self._h)
+        self._batch_clips = int(layout_in.n_clips)
+
+    def last_batch_info(self):
+        """glc_roundtrip_batch_last_info: per clip of the last apply_batch_* call the RoundTripInfo that last_info()
+        gives after a round trip of that clip alone (synchronises)."""
+        n = getattr(self, "_batch_clips", 0)
+        arr = (GlcRoundtripInfo * max(n, 1))()
+        check(lib.glc_roundtrip_batch_last_info(self._h, arr, n), self._h)
+        return [RoundTripInfo(i.n_frames, i.n_raw_frames, i.total_nnz, i.serialized_bytes) for i in arr[:n]]
 
     def resident_stream(self) -> int:
         """0 after every apply* call: a round trip leaves no stream resident on its context."""

@@ -163,6 +163,19 @@ struct glc_ctx {
   DevBuf rt_out;      // glc_roundtrip: the trimmed output on its way to the host
   uint64_t rt_info_frames = 0;  // frames of that stream (0: no round trip has completed)
   uint32_t rt_info_ch = 0;
+  // glc_roundtrip_batch_device
+  DevBuf rtb_vs;       // the virtual stream of a round / a clip longer than a round, staged whole
+  DevBuf rtb_tab;      // the call's tables: per round the clip table, the frame map and the hop descriptors
+  DevBuf rtb_stats;    // per-clip counters of the last batch call
+  HostBuf rtb_stage;   // pinned image of rtb_tab on its way up ...
+  hipEvent_t rtb_ev = nullptr;  // ... recorded behind that copy: the next call waits for it before it rewrites the image
+  bool rtb_ev_pending = false;
+  struct RtbClipInfo {
+    uint64_t n_frames, stat_off;  // stat_off: the clip's first counter pair in rtb_stats, in uint64_t
+    uint32_t stat_slots;
+  };
+  std::vector<RtbClipInfo> rtb_info;  // the clips of the last completed batch call (empty: none)
+  uint32_t rtb_info_ch = 0;
   HostBuf batch_stage;  // pinned: a round of glc_encode_batch's short clips going up, then its payload coming down / of glc_decode_batch's rows going up
   std::string err;
   // decode session (decode_prepare / round_launch): device-resident sparse rows + position
@@ -384,6 +397,11 @@ void glc_ctx_destroy(glc_ctx *ctx) {
   ctx->rt_edge.release();
   ctx->rt_stats.release();
   ctx->rt_out.release();
+  ctx->rtb_vs.release();
+  ctx->rtb_tab.release();
+  ctx->rtb_stats.release();
+  ctx->rtb_stage.release();
+  if (ctx->rtb_ev) (void)hipEventDestroy(ctx->rtb_ev);
   ctx->pack_blob.release();
   ctx->host_stage.release();
   ctx->batch_stage.release();
@@ -2047,8 +2065,17 @@ int rt_emit_hops(glc_ctx *ctx, const RtGeom &g, uint64_t h0, uint64_t h1, T *d_o
 // One round: the records of frames [f0, f0 + nf) at `recs` -> row tables (R1) -> D1 into block slots 1.. ->
 // the round's hops (+ the bare tail behind the last frame) into the trimmed output -> the last block to
 // slot 0 for the next round.  `stats`: device counters of glc_roundtrip_last_info, or null.
+// `sink` (glc_roundtrip_batch_device, a clip longer than a round): the round's hops go through the strided
+// overlap-add by these descriptors (block slots counted in the ring) instead of into a contiguous d_out.
+struct RtStridedSink {
+  const glc::HopDescStrided *desc;
+  uint32_t n_desc;
+  bool planar;
+  float *out;
+};
 template <typename T>
-int rt_decode_round(glc_ctx *ctx, const RtGeom &g, const uint8_t *recs, uint64_t f0, uint64_t nf, uint64_t *stats, T *d_out) {
+int rt_decode_round(glc_ctx *ctx, const RtGeom &g, const uint8_t *recs, uint64_t f0, uint64_t nf, uint64_t *stats, T *d_out,
+                    const RtStridedSink *sink = nullptr) {
   const size_t slot = static_cast<size_t>(g.ch) * glc::kFrame;
   float *blocks = static_cast<float *>(ctx->blocks.p);
   const uint32_t M = static_cast<uint32_t>(nf * g.ch);
@@ -2057,8 +2084,12 @@ int rt_decode_round(glc_ctx *ctx, const RtGeom &g, const uint8_t *recs, uint64_t
   GLC_HIP(ctx, glc::launch_imdct_rows(ctx->dev, rows, 0, M, g.ch, blocks + slot, ctx->stream, ctx->d1_variant, ctx->dec_plan.p,
                                       ctx->dec_plan.p ? ctx->dec_plan_groups : 0, false));
   const bool last = f0 + nf == g.n_frames;
-  const int rc = rt_emit_hops(ctx, g, f0, f0 + nf + (last ? 1 : 0), d_out);
-  if (rc != GLC_OK) return rc;
+  if (sink) {
+    GLC_HIP(ctx, glc::launch_overlap_add_strided(blocks, sink->desc, sink->n_desc, g.ch, sink->planar, sink->out, ctx->stream));
+  } else {
+    const int rc = rt_emit_hops(ctx, g, f0, f0 + nf + (last ? 1 : 0), d_out);
+    if (rc != GLC_OK) return rc;
+  }
   if (!last)
     GLC_HIP(ctx, hipMemcpyAsync(blocks, blocks + nf * slot, slot * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
   return GLC_OK;
@@ -2094,13 +2125,13 @@ int rt_check(glc_ctx *ctx, const char *who, uint64_t n_samples, uint16_t channel
 // Encode + decode of the frames [f0, f0 + nf) of device-resident PCM: K1, K2 (K3) into the round's record
 // buffer, then rt_decode_round of it.
 template <typename T>
-int rt_roundtrip_round(glc_ctx *ctx, const RtGeom &g, const float *d_pcm, uint64_t n_samples, uint64_t f0, uint64_t nf, T *d_out) {
+int rt_roundtrip_round(glc_ctx *ctx, const RtGeom &g, const float *d_pcm, uint64_t n_samples, uint64_t f0, uint64_t nf, T *d_out,
+                       uint64_t *stats, const RtStridedSink *sink = nullptr) {
   const uint64_t t_count = (n_samples + g.ch - 1) / g.ch;
   int rc = encode_range_on(ctx, ctx->stream, ctx->coef, d_pcm, 0, t_count, n_samples, static_cast<uint16_t>(g.ch), f0, f0 + nf,
                            ctx->rt_records.p, nullptr);
   if (rc != GLC_OK) return rc;
-  return rt_decode_round(ctx, g, static_cast<const uint8_t *>(ctx->rt_records.p), f0, nf, static_cast<uint64_t *>(ctx->rt_stats.p),
-                         d_out);
+  return rt_decode_round(ctx, g, static_cast<const uint8_t *>(ctx->rt_records.p), f0, nf, stats, d_out, sink);
 }
 
 constexpr size_t kRtStatBytes = size_t(glc::kRowStatSlots) * glc::kRowStatStride * sizeof(uint64_t);
@@ -2199,7 +2230,7 @@ int rt_roundtrip_host(glc_ctx *ctx, const void *pcm, glc_pcm_format fmt, uint32_
         if (prog.err != hipSuccess) return hip_fail(ctx, prog.err, "glc_roundtrip: upload");
       }
       const uint64_t f0 = i * g.round, nf = std::min(g.round, g.n_frames - f0);
-      const int rrc = rt_roundtrip_round(ctx, g, d_pcm, n_samples, f0, nf, d_out);
+      const int rrc = rt_roundtrip_round(ctx, g, d_pcm, n_samples, f0, nf, d_out, static_cast<uint64_t *>(ctx->rt_stats.p));
       if (rrc != GLC_OK) return rrc;
       GLC_HIP(ctx, hipEventRecord(ctx->ev_dec[i & 1], ctx->stream));
       if (i > 0) GLC_HIP(ctx, download(i - 1));
@@ -2231,6 +2262,18 @@ int rt_roundtrip_host(glc_ctx *ctx, const void *pcm, glc_pcm_format fmt, uint32_
 
 }  // namespace
 }  // extern "C++"
+
+// glc_roundtrip_info of a stream of `nf` frames of `ch` channels from its two device counters
+static void rt_fill_info(glc_roundtrip_info *out, uint64_t nf, uint64_t ch, uint64_t nnz, uint64_t n_raw) {
+  const uint64_t lists = (nf - n_raw) * ch;
+  out->n_frames = nf;
+  out->n_raw_frames = n_raw;
+  out->total_nnz = nnz;
+  // glc_serialized_size: header, per frame {two Vec lengths, Option tag}, per list its length, the pairs and
+  // scale factors of compressed frames, {length, planar i16 block} of raw ones, gapless info
+  out->serialized_bytes = (4 + 2 + 8 + 8) + nf * (8 + 8 + 1) + lists * 8 + nnz * 4 + lists * 4 +
+                          n_raw * (8 + 2ull * glc::kFrame * ch) + (4 + 4 + 8);
+}
 
 int glc_decode_device_records(glc_ctx *ctx, const void *d_records, uint64_t n_frames, uint64_t n_samples, uint16_t channels,
                               float *d_out, uint64_t cap, uint64_t *n_out) {
@@ -2270,7 +2313,8 @@ int glc_roundtrip_device(glc_ctx *ctx, const float *d_pcm, uint64_t n_samples, u
   rt_forget_streams(ctx);
   rc = rt_roundtrip_begin(ctx, g);
   for (uint64_t f0 = 0; f0 < g.n_frames && rc == GLC_OK; f0 += g.round)
-    rc = rt_roundtrip_round(ctx, g, d_pcm, n_samples, f0, std::min(g.round, g.n_frames - f0), d_out);
+    rc = rt_roundtrip_round(ctx, g, d_pcm, n_samples, f0, std::min(g.round, g.n_frames - f0), d_out,
+                            static_cast<uint64_t *>(ctx->rt_stats.p));
   if (rc == GLC_OK) rt_roundtrip_end(ctx, g);
   return rc;
 }
@@ -2316,14 +2360,294 @@ int glc_roundtrip_last_info(glc_ctx *ctx, glc_roundtrip_info *out) {
   GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   uint64_t s[2] = {0, 0};
   for (uint32_t i = 0; i < glc::kRowStatSlots; ++i) s[0] += slots[i * glc::kRowStatStride], s[1] += slots[i * glc::kRowStatStride + 1];
-  const uint64_t nf = ctx->rt_info_frames, ch = ctx->rt_info_ch, n_raw = s[1], lists = (nf - n_raw) * ch;
-  out->n_frames = nf;
-  out->n_raw_frames = n_raw;
-  out->total_nnz = s[0];
-  // glc_serialized_size: header, per frame {two Vec lengths, Option tag}, per list its length, the pairs and
-  // scale factors of compressed frames, {length, planar i16 block} of raw ones, gapless info
-  out->serialized_bytes = (4 + 2 + 8 + 8) + nf * (8 + 8 + 1) + lists * 8 + s[0] * 4 + lists * 4 +
-                          n_raw * (8 + 2ull * glc::kFrame * ch) + (4 + 4 + 8);
+  rt_fill_info(out, ctx->rt_info_frames, ctx->rt_info_ch, s[0], s[1]);
+  return GLC_OK;
+}
+
+// ------------------------------------------------------------------------------ round trip, many clips
+
+extern "C++" {
+namespace {
+
+// Where clip i of a glc_clip_layout starts, what it occupies, and the extent of the whole layout, in elements.
+struct RtbLayout {
+  const glc_clip_layout *l;
+  uint64_t len(uint64_t i) const { return l->lengths ? l->lengths[i] : l->length; }
+  uint64_t at(uint64_t i) const { return i * l->clip_stride; }
+  bool planes() const { return l->planar && l->channels > 1; }
+  uint64_t occupies(uint64_t i) const {
+    return planes() ? (l->channels - 1ull) * l->channel_stride + len(i) : len(i) * l->channels;
+  }
+  // The extent is that of the padded batch: every clip slot counts with the length of the LONGEST clip, so the padding
+  // behind a short last clip belongs to the batch too and no second buffer may begin inside it.
+  uint64_t extent() const {
+    uint64_t longest = 0;
+    for (uint64_t i = 0; i < l->n_clips; ++i) longest = std::max(longest, len(i));
+    const uint64_t occ = planes() ? (l->channels - 1ull) * l->channel_stride + longest : longest * l->channels;
+    return at(l->n_clips - 1) + occ;
+  }
+  bool same_as(const RtbLayout &o) const {
+    return planes() == o.planes() && (l->n_clips <= 1 || l->clip_stride == o.l->clip_stride) &&
+           (!planes() || l->channel_stride == o.l->channel_stride);
+  }
+};
+
+// A round of the batch round trip: clips [first, first + n) packed into one virtual stream, or (lng) ONE clip
+// longer than a round, staged whole and sent through rounds with the carried overlap.
+struct RtbRound {
+  uint64_t first = 0, n = 0, V = 0, n_real = 0;
+  bool lng = false;
+  size_t o_clips = 0, o_fmap = 0, o_desc = 0;  // in the call's table image
+  uint64_t n_desc = 0;
+  uint64_t stat_off = 0;  // lng: the clip's kRowStatSlots counter pairs
+};
+
+// Kept hops of a clip: 512 interleaved samples of delay in front (hop 0 is cut), len * ch kept.
+inline uint64_t rtb_hops_kept(uint64_t len, uint32_t ch) { return (glc::kHop / 2 + len * ch - 1) / (uint64_t(glc::kHop) * ch) + 1; }
+
+// The descriptors of hops [h0, h1) of a clip of `nf` frames whose frame f is block slot base + f.
+glc::HopDescStrided *rtb_write_hops(glc::HopDescStrided *d, uint64_t nf, uint32_t ch, const glc::Trim &trim, uint64_t h0,
+                                    uint64_t h1, int64_t base, uint64_t dst, bool planes, uint64_t cstride) {
+  const uint64_t per_hop = uint64_t(glc::kHop) * ch, lo_all = trim.start, hi_all = trim.start + trim.n;
+  for (uint64_t h = h0; h < h1; ++h) {
+    const uint64_t lo = std::max(lo_all, h * per_hop), hi = std::min(hi_all, (h + 1) * per_hop);
+    if (hi <= lo) continue;
+    const uint64_t j0 = lo - trim.start;
+    *d++ = glc::HopDescStrided{h >= 1 ? static_cast<int32_t>(base + static_cast<int64_t>(h) - 1) : -1,
+                               h < nf ? static_cast<int32_t>(base + static_cast<int64_t>(h)) : -1,
+                               static_cast<uint32_t>(lo - h * per_hop),
+                               static_cast<uint32_t>(hi - lo),
+                               planes ? dst : dst + j0,
+                               planes ? cstride : 0ull,
+                               j0};
+  }
+  return d;
+}
+
+int rtb_impl(glc_ctx *ctx, const float *d_pcm, const RtbLayout &in, float *d_out, const RtbLayout &out) {
+  const uint64_t n = in.l->n_clips;
+  const uint32_t ch = in.l->channels;
+  const uint64_t per_hop = uint64_t(glc::kHop) * ch, rec = glc::record_bytes(ch);
+  const size_t slot = static_cast<size_t>(ch) * glc::kFrame;
+  std::vector<glc_plan> plans(n);
+  for (uint64_t i = 0; i < n; ++i) plans[i] = glc::plan_encode(in.len(i) * ch, static_cast<uint16_t>(ch));
+
+  // rounds as in encode_batch_impl: whole clips, at most encode_chunk_frames(ch) virtual frames together
+  const uint64_t budget = encode_chunk_frames(ch);
+  std::vector<RtbRound> rounds;
+  {
+    RtbRound cur;
+    auto flush = [&](uint64_t next) {
+      if (cur.n) rounds.push_back(cur);
+      cur = RtbRound{};
+      cur.first = next;
+    };
+    for (uint64_t i = 0; i < n; ++i) {
+      const uint64_t v = plans[i].n_frames + 1;
+      if (v > budget) {
+        flush(i);
+        cur.n = 1, cur.lng = true, cur.V = v, cur.n_real = plans[i].n_frames;
+        flush(i + 1);
+        continue;
+      }
+      if (cur.V + v > budget) flush(i);
+      cur.n += 1, cur.V += v, cur.n_real += plans[i].n_frames;
+    }
+    flush(n);
+  }
+  // the call's tables, and what the workspaces have to hold
+  size_t tab = 0;
+  auto place = [&](size_t bytes) {
+    const size_t at = tab;
+    tab = align_up(tab + bytes, 256);
+    return at;
+  };
+  const uint64_t clip_stat = uint64_t(glc::kClipStatSlots) * glc::kRowStatStride;  // uint64_t per clip
+  uint64_t stat_words = n * clip_stat;
+  uint64_t max_vs = 0, max_recs = 0, max_rows = 0, max_blocks = 0, max_frames = 0, max_coef_rows = 0;
+  for (RtbRound &r : rounds) {
+    r.o_clips = place(r.n * sizeof(glc::StageClip));
+    for (uint64_t i = r.first; i < r.first + r.n; ++i) r.n_desc += rtb_hops_kept(in.len(i), ch);
+    r.o_desc = place(r.n_desc * sizeof(glc::HopDescStrided));
+    max_vs = std::max(max_vs, r.V * per_hop);
+    if (r.lng) {
+      const uint64_t rf = std::min<uint64_t>(kDecodeChunkFrames, r.n_real);
+      r.stat_off = stat_words;
+      stat_words += kRtStatBytes / sizeof(uint64_t);
+      max_recs = std::max(max_recs, rf), max_rows = std::max(max_rows, rf * ch), max_blocks = std::max(max_blocks, rf + 1);
+      max_frames = std::max(max_frames, rf), max_coef_rows = std::max(max_coef_rows, rf * ch);
+    } else {
+      r.o_fmap = place(r.n_real * sizeof(glc::FrameMap));
+      max_recs = std::max(max_recs, r.V), max_rows = std::max(max_rows, r.n_real * ch), max_blocks = std::max(max_blocks, r.n_real);
+      max_frames = std::max(max_frames, r.n_real), max_coef_rows = std::max(max_coef_rows, r.V * ch);
+    }
+  }
+  rt_forget_streams(ctx);
+  ctx->rtb_info.clear();
+  int rc = rt_reserve(ctx, ctx->rtb_vs, max_vs * sizeof(float));
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rt_records, max_recs * rec);
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->coef, max_coef_rows * glc::kHop * sizeof(float));
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rt_rows, glc::rows_from_records_bytes(static_cast<uint32_t>(max_rows)));
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->blocks, max_blocks * slot * sizeof(float));
+  if (rc == GLC_OK) rc = reserve_d1_plan(ctx, max_frames, ch);
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rtb_tab, tab);
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rtb_stats, stat_words * sizeof(uint64_t));
+  if (rc != GLC_OK) return rc;
+  if (!ctx->rtb_ev) GLC_HIP(ctx, hipEventCreateWithFlags(&ctx->rtb_ev, hipEventDisableTiming));
+  // the pinned image may still be on its way up for the call before: wait for that copy (not for any kernel
+  // of that call - they are queued behind it)
+  if (ctx->rtb_ev_pending) GLC_HIP(ctx, hipEventSynchronize(ctx->rtb_ev));
+  ctx->rtb_ev_pending = false;
+  GLC_HIP(ctx, ctx->rtb_stage.reserve(tab));
+  uint8_t *img = static_cast<uint8_t *>(ctx->rtb_stage.p);
+  uint8_t *d_tab = static_cast<uint8_t *>(ctx->rtb_tab.p);
+  const bool out_planes = out.planes();
+  for (const RtbRound &r : rounds) {
+    auto *clips = reinterpret_cast<glc::StageClip *>(img + r.o_clips);
+    auto *desc = reinterpret_cast<glc::HopDescStrided *>(img + r.o_desc);
+    auto *fmap = reinterpret_cast<glc::FrameMap *>(img + r.o_fmap);
+    uint64_t vslot = 0, real = 0;
+    for (uint64_t k = 0; k < r.n; ++k) {
+      const uint64_t i = r.first + k, nf = plans[i].n_frames;
+      clips[k] = glc::StageClip{in.at(i), in.len(i), static_cast<uint32_t>(vslot), {0u, 0u, 0u}};
+      const glc::Trim trim = glc::gapless_trim(nf, ch, plans[i].encoder_delay, in.len(i) * ch);
+      if (r.lng) {  // round by round, block slots counted in the ring (frame f0 - 1 of a round in slot 0)
+        for (uint64_t f0 = 0; f0 < nf; f0 += kDecodeChunkFrames) {
+          const uint64_t f1 = std::min(nf, f0 + kDecodeChunkFrames);
+          desc = rtb_write_hops(desc, nf, ch, trim, f0, f1 + (f1 == nf ? 1 : 0), 1 - static_cast<int64_t>(f0), out.at(i),
+                                out_planes, out.l->channel_stride);
+        }
+      } else {
+        desc = rtb_write_hops(desc, nf, ch, trim, 0, nf + 1, static_cast<int64_t>(real), out.at(i), out_planes,
+                              out.l->channel_stride);
+        for (uint64_t f = 0; f < nf; ++f)
+          fmap[real + f] = glc::FrameMap{static_cast<uint32_t>(vslot + f), static_cast<uint32_t>(i)};
+      }
+      vslot += nf + 1;
+      real += nf;
+    }
+    if (static_cast<uint64_t>(desc - reinterpret_cast<glc::HopDescStrided *>(img + r.o_desc)) != r.n_desc)
+      return fail(ctx, GLC_EHIP, "glc_roundtrip_batch_device: hop count arithmetic is inconsistent");
+  }
+  hipStream_t st = ctx->stream;
+  GLC_HIP(ctx, hipMemcpyAsync(d_tab, img, tab, hipMemcpyHostToDevice, st));
+  GLC_HIP(ctx, hipEventRecord(ctx->rtb_ev, st));
+  ctx->rtb_ev_pending = true;
+  uint64_t *d_stats = static_cast<uint64_t *>(ctx->rtb_stats.p);
+  GLC_HIP(ctx, hipMemsetAsync(d_stats, 0, stat_words * sizeof(uint64_t), st));
+
+  float *vs = static_cast<float *>(ctx->rtb_vs.p);
+  float *blocks = static_cast<float *>(ctx->blocks.p);
+  const uint8_t *recs = static_cast<const uint8_t *>(ctx->rt_records.p);
+  for (const RtbRound &r : rounds) {
+    const auto *clips = reinterpret_cast<const glc::StageClip *>(d_tab + r.o_clips);
+    const auto *desc = reinterpret_cast<const glc::HopDescStrided *>(d_tab + r.o_desc);
+    GLC_HIP(ctx, glc::launch_stage_clips(d_pcm, clips, static_cast<uint32_t>(r.n), ch, in.planes(), in.l->channel_stride,
+                                         static_cast<uint32_t>(r.V), vs, st));
+    if (r.lng) {
+      const uint64_t i = r.first, n_samples = in.len(i) * ch;
+      const RtGeom g = rt_geom(r.n_real, ch, plans[i], n_samples);
+      for (uint64_t f0 = 0; f0 < g.n_frames; f0 += g.round) {
+        const uint64_t nf = std::min(g.round, g.n_frames - f0), f1 = f0 + nf;
+        // the round's descriptors: those of hops [f0, f1 (+ 1)) that keep anything - all but none, since only the
+        // tail hop can lie wholly behind the kept samples
+        uint64_t nd = 0;
+        for (uint64_t h = f0; h < f1 + (f1 == g.n_frames ? 1 : 0); ++h)
+          if (std::min(g.trim.start + g.trim.n, (h + 1) * per_hop) > std::max(g.trim.start, h * per_hop)) ++nd;
+        const RtStridedSink sink{desc, static_cast<uint32_t>(nd), out_planes, d_out};
+        rc = rt_roundtrip_round<float>(ctx, g, vs, n_samples, f0, nf, nullptr, d_stats + r.stat_off, &sink);
+        if (rc != GLC_OK) return rc;
+        desc += nd;
+      }
+      continue;
+    }
+    const uint64_t T = r.V * glc::kHop;
+    rc = encode_range_on(ctx, st, ctx->coef, vs, 0, T, T * ch, static_cast<uint16_t>(ch), 0, r.V, ctx->rt_records.p, nullptr);
+    if (rc != GLC_OK) return rc;
+    const uint32_t M = static_cast<uint32_t>(r.n_real * ch);
+    glc::DecodeRows rows{};
+    GLC_HIP(ctx, glc::launch_rows_from_records_batch(recs, M, ch, reinterpret_cast<const glc::FrameMap *>(d_tab + r.o_fmap),
+                                                     ctx->rt_rows.p, d_stats, st, &rows));
+    // (D1's 8-frame units may span two clips: that only widens a union)
+    GLC_HIP(ctx, glc::launch_imdct_rows(ctx->dev, rows, 0, M, ch, blocks, st, ctx->d1_variant, ctx->dec_plan.p,
+                                        ctx->dec_plan.p ? ctx->dec_plan_groups : 0, false));
+    GLC_HIP(ctx, glc::launch_overlap_add_strided(blocks, desc, static_cast<uint32_t>(r.n_desc), ch, out_planes, d_out, st));
+  }
+  ctx->rtb_info.resize(n);
+  for (uint64_t i = 0; i < n; ++i) ctx->rtb_info[i] = glc_ctx::RtbClipInfo{plans[i].n_frames, i * clip_stat, glc::kClipStatSlots};
+  for (const RtbRound &r : rounds)
+    if (r.lng) ctx->rtb_info[r.first] = glc_ctx::RtbClipInfo{r.n_real, r.stat_off, glc::kRowStatSlots};
+  ctx->rtb_info_ch = ch;
+  return GLC_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int glc_roundtrip_batch_device(glc_ctx *ctx, const float *d_pcm, const glc_clip_layout *in, float *d_out,
+                               const glc_clip_layout *out) {
+  const char *who = "glc_roundtrip_batch_device";
+  const std::string w(who);
+  if (!ctx) return GLC_EINVAL;
+  if (!in || !out) return fail(ctx, GLC_EINVAL, w + ": null argument");
+  if (in->n_clips != out->n_clips || in->channels != out->channels)
+    return fail(ctx, GLC_EINVAL, w + ": the two layouts differ in the number of clips or channels");
+  if (in->n_clips == 0) return GLC_OK;
+  if (!d_pcm || !d_out) return fail(ctx, GLC_EINVAL, w + ": null argument");
+  if (in->channels == 0) return fail(ctx, GLC_EINVAL, w + ": channels == 0");
+  if ((reinterpret_cast<uintptr_t>(d_pcm) | reinterpret_cast<uintptr_t>(d_out)) & 3u)
+    return fail(ctx, GLC_EINVAL, w + ": a pointer is not aligned to its sample size");
+  const RtbLayout li{in}, lo{out};
+  const uint64_t n = in->n_clips, ch = in->channels;
+  for (uint64_t i = 0; i < n; ++i) {
+    const std::string clip = w + ": clip " + std::to_string(i);
+    if (li.len(i) != lo.len(i)) return fail(ctx, GLC_EINVAL, clip + ": the two layouts differ in its length");
+    const glc_plan plan = glc::plan_encode(li.len(i) * ch, in->channels);
+    if (plan.n_frames == 0)
+      return fail(ctx, GLC_EINVAL, clip + ": the reference encoder panics on this input (<= 512 samples per channel)");
+    if (plan.n_frames * ch > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, clip + ": stream too long");
+    for (const RtbLayout *l : {&li, &lo}) {
+      if (l->planes() && l->l->channel_stride < l->len(i))
+        return fail(ctx, GLC_EINVAL, clip + ": channel_stride is smaller than a plane");
+      if (n > 1 && l->l->clip_stride < l->occupies(i)) return fail(ctx, GLC_EINVAL, clip + ": clip_stride is smaller than the clip");
+    }
+  }
+  {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_pcm), a1 = a0 + li.extent() * sizeof(float);
+    const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_out), b1 = b0 + lo.extent() * sizeof(float);
+    if (a0 < b1 && b0 < a1 && !(a0 == b0 && li.same_as(lo)))
+      return fail(ctx, GLC_EINVAL, w + ": input and output overlap (in place needs the same pointer and the same layout)");
+  }
+  DeviceGuard guard(ctx->device);
+  try {  // no C++ exception may cross the C ABI
+    return rtb_impl(ctx, d_pcm, li, d_out, lo);
+  } catch (const std::bad_alloc &) {
+    return fail(ctx, GLC_ENOMEM, w + ": host allocation failed");
+  }
+}
+
+int glc_roundtrip_batch_last_info(glc_ctx *ctx, glc_roundtrip_info *infos, uint64_t n_clips) {
+  if (!ctx || !infos) return fail(ctx, GLC_EINVAL, "glc_roundtrip_batch_last_info: null argument");
+  if (ctx->rtb_info.empty() || !ctx->rtb_stats.p)
+    return fail(ctx, GLC_EINVAL, "glc_roundtrip_batch_last_info: no batch round trip has completed on this context");
+  if (n_clips != ctx->rtb_info.size())
+    return fail(ctx, GLC_EINVAL, "glc_roundtrip_batch_last_info: the last batch had another number of clips");
+  DeviceGuard guard(ctx->device);
+  uint64_t words = 0;
+  for (const glc_ctx::RtbClipInfo &c : ctx->rtb_info) words = std::max(words, c.stat_off + uint64_t(c.stat_slots) * glc::kRowStatStride);
+  try {
+    std::vector<uint64_t> h(words);
+    GLC_HIP(ctx, hipMemcpyAsync(h.data(), ctx->rtb_stats.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint64_t i = 0; i < n_clips; ++i) {
+      const glc_ctx::RtbClipInfo &c = ctx->rtb_info[i];
+      uint64_t s0 = 0, s1 = 0;
+      for (uint32_t k = 0; k < c.stat_slots; ++k) s0 += h[c.stat_off + k * glc::kRowStatStride], s1 += h[c.stat_off + k * glc::kRowStatStride + 1];
+      rt_fill_info(&infos[i], c.n_frames, ctx->rtb_info_ch, s0, s1);
+    }
+  } catch (const std::bad_alloc &) {
+    return fail(ctx, GLC_ENOMEM, "glc_roundtrip_batch_last_info: host allocation failed");
+  }
   return GLC_OK;
 }
 

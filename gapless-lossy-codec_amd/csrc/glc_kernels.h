@@ -91,6 +91,14 @@ constexpr uint32_t kRowStatSlots = 64, kRowStatStride = 16;  // a 128-byte line 
 uint64_t rows_from_records_bytes(uint32_t M);
 hipError_t launch_rows_from_records(const uint8_t *records, uint32_t M, uint32_t ch, void *workspace, uint64_t *stats,
                                     hipStream_t s, DecodeRows *rows);
+// R1 over the real frames of a round of glc_roundtrip_batch_device: row m is channel m % ch of real frame
+// m / ch, whose record is number fmap[m / ch].slot among `records` (the virtual stream's frames; the junk ones
+// are in no map and get no row).  Here fmap[r].clip names the clip of EVERY real frame.  clip_stats:
+// per clip kClipStatSlots pairs of counters, kRowStatStride uint64_t apart (clip i's first at clip_stats +
+// i * kClipStatSlots * kRowStatStride), ADDED to as launch_rows_from_records adds to its one set.
+constexpr uint32_t kClipStatSlots = 4;
+hipError_t launch_rows_from_records_batch(const uint8_t *records, uint32_t M, uint32_t ch, const FrameMap *fmap, void *workspace,
+                                          uint64_t *clip_stats, hipStream_t s, DecodeRows *rows);
 // variant (include/glc_debug.h): 0 = shipped (k_imdct_plan + k_imdct_apply, absent row pairs skipped
 // by scalar branches); 1 = one row per workgroup (the cross-check kernel); 2 = plan + apply without
 // the skip; 3 = without the issue-priority schedule; 4 = skipping in row pairs only.  All but 1 need a workspace `plan` of imdct_plan_bytes(plan_groups) bytes,
@@ -122,6 +130,31 @@ hipError_t launch_overlap_add_batch(const float *blocks, const HopDesc *desc, ui
 // dst an index of 2-byte elements.
 hipError_t launch_overlap_add_batch(const float *blocks, const HopDesc *desc, uint32_t n_desc, uint32_t ch, int16_t *out,
                                     hipStream_t s);
+
+// S1: the interleaved virtual stream of a round of glc_roundtrip_batch_device, gathered from strided device
+// audio.  clips[k] (ascending `slot`, clips[0].slot == 0): the clip's first sample is element `src` of the
+// source, it has `len` samples per channel and owns the virtual frame slots [slot, clips[k + 1].slot).
+// Interleaved source: sample t of channel c at src + t * ch + c; planar: at src + c * channel_stride + t.
+// vstream[(1024 v + i) * ch + c] for v < n_virtual_frames: the clip's sample 1024 (v - slot) + i, +0.0 from
+// `len` on - EVERY element of the stream is written.  vstream is 16-byte aligned, the source 4-byte.
+struct StageClip {
+  uint64_t src, len;
+  uint32_t slot, pad[3];
+};
+hipError_t launch_stage_clips(const float *src, const StageClip *clips, uint32_t n_clips, uint32_t ch, bool planar,
+                              uint64_t channel_stride, uint32_t n_virtual_frames, float *vstream, hipStream_t s);
+
+// D2 into strided clips: launch_overlap_add_batch with a 64-bit destination that is bound to no alignment
+// beyond 4 bytes.  Interleaved (cstride == 0 in every descriptor): out[dst .. dst + cnt) = samples [first,
+// first + cnt) of the hop.  `planar`: the span is the clip's interleaved samples [j0, j0 + cnt), sample j going
+// to out[dst + (j % ch) * cstride + j / ch] - dst is the clip's first element.
+struct HopDescStrided {
+  int32_t prev, cur;
+  uint32_t first, cnt;
+  uint64_t dst, cstride, j0;
+};
+hipError_t launch_overlap_add_strided(const float *blocks, const HopDescStrided *desc, uint32_t n_desc, uint32_t ch, bool planar,
+                                      float *out, hipStream_t s);
 
 // D2 with the narrowing of the reference's 16-bit writers on the way out: the same sums, then
 // `(v * 32767.0).clamp(-32768.0, 32767.0) as i16` (NaN -> 0, truncation) - `out` is any 2-byte aligned pointer.

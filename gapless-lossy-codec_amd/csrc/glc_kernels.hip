@@ -1155,6 +1155,13 @@ __global__ __launch_bounds__(256) void k_pack_rows(const unsigned char *__restri
 // added to - one pair of atomics per workgroup, spread over kRowStatSlots counter pairs a cache line apart
 // (2048 workgroups adding to ONE address took 21 us of the kernel's 30: same-address atomics queue up in L2).
 // ------------------------------------------------------------------------------------------
+// SEG (a round of glc_roundtrip_batch_device): row m is channel m % ch of REAL frame m / ch of a virtual stream
+// of many clips, whose record is number fmap[m / ch].x among `records` and which belongs to clip fmap[m / ch].y
+// (here EVERY frame names its clip, not only a clip's first); the junk frames between the clips are in no map
+// and get no row.  row_raw points at the record's place in `records`.  stats is then per clip: kClipStatSlots
+// counter pairs, kRowStatStride uint64_t apart, from stats + clip * kClipStatSlots * kRowStatStride on; a
+// workgroup's four rows ascend through at most four clips and add once per clip they touch.
+template <bool SEG>
 __global__ __launch_bounds__(256) void k_rows_from_records(const unsigned char *__restrict__ records, unsigned M,
                                                             unsigned ch, unsigned long long rec_bytes,
                                                             unsigned long long hdr_bytes, unsigned *__restrict__ pairs,
@@ -1162,13 +1169,20 @@ __global__ __launch_bounds__(256) void k_rows_from_records(const unsigned char *
                                                             unsigned *__restrict__ row_cnt, float *__restrict__ row_scale,
                                                             long long *__restrict__ row_raw,
                                                             unsigned long long *__restrict__ row_raw_len,
-                                                            unsigned long long *__restrict__ stats) {
-  __shared__ unsigned s_nnz[4], s_rawf[4];
+                                                            unsigned long long *__restrict__ stats,
+                                                            const uint2 *__restrict__ fmap) {
+  __shared__ unsigned s_nnz[4], s_rawf[4], s_clip[4];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const unsigned m = blockIdx.x * 4 + w;
-  unsigned stat_nnz = 0, stat_raw = 0;
+  unsigned stat_nnz = 0, stat_raw = 0, stat_clip = ~0u;
   if (m < M) {
-    const unsigned frame = m / ch, c = m - frame * ch;
+    unsigned frame = m / ch;
+    const unsigned c = m - frame * ch;
+    if constexpr (SEG) {
+      const uint2 fm = fmap[frame];
+      frame = fm.x;
+      stat_clip = fm.y;
+    }
     const unsigned char *rec = records + static_cast<size_t>(frame) * rec_bytes;
     const unsigned raw = *reinterpret_cast<const unsigned *>(rec);
     const float scale = *reinterpret_cast<const float *>(rec + 8 + 8 * c);
@@ -1211,7 +1225,26 @@ __global__ __launch_bounds__(256) void k_rows_from_records(const unsigned char *
       row_raw_len[m] = raw ? static_cast<unsigned long long>(kFrameI) * ch : 0ull;
     }
   }
-  if (stats) {  // kernel argument: uniform
+  if constexpr (SEG) {
+    if (lane == 0) s_nnz[w] = stat_nnz, s_rawf[w] = stat_raw, s_clip[w] = stat_clip;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned cur = s_clip[0], n = 0, r = 0;
+      for (int i = 0; i <= 4; ++i) {
+        if (i == 4 || s_clip[i] != cur) {  // the rows of `cur` in this workgroup end here
+          if (cur != ~0u) {
+            unsigned long long *slot =
+                stats + (static_cast<size_t>(cur) * kClipStatSlots + blockIdx.x % kClipStatSlots) * kRowStatStride;
+            if (n) atomicAdd(&slot[0], static_cast<unsigned long long>(n));
+            if (r) atomicAdd(&slot[1], static_cast<unsigned long long>(r));
+          }
+          if (i == 4) break;
+          cur = s_clip[i], n = 0, r = 0;
+        }
+        n += s_nnz[i], r += s_rawf[i];
+      }
+    }
+  } else if (stats) {  // kernel argument: uniform
     if (lane == 0) s_nnz[w] = stat_nnz, s_rawf[w] = stat_raw;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1219,6 +1252,196 @@ __global__ __launch_bounds__(256) void k_rows_from_records(const unsigned char *
       unsigned long long *slot = stats + static_cast<size_t>(blockIdx.x % kRowStatSlots) * kRowStatStride;
       if (n) atomicAdd(&slot[0], static_cast<unsigned long long>(n));
       if (r) atomicAdd(&slot[1], static_cast<unsigned long long>(r));
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// S1: the virtual stream of a round of glc_roundtrip_batch_device, gathered from clips that lie strided
+// (and, `planar`, one plane per channel) in the caller's memory.  Workgroup row blockIdx.x is virtual frame
+// slot v: the 1024 * ch interleaved samples [1024 v, 1024 v + 1024) of the stream.  Its clip is the last one
+// whose `slot` is <= v - a binary search per WORKGROUP (block-uniform, scalar loads), not per element.
+// Everything at or behind the clip's `len` samples is written as +0.0 in the same pass: the zeros behind
+// a clip and its junk frame need no memset.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ StageClip stage_find_clip(const StageClip *__restrict__ clips, unsigned n_clips, unsigned v) {
+  unsigned lo = 0, hi = n_clips;  // clips[lo].slot <= v < clips[hi].slot
+  while (hi - lo > 1) {
+    const unsigned mid = (lo + hi) >> 1;
+    if (clips[mid].slot <= v) lo = mid;
+    else hi = mid;
+  }
+  return clips[lo];
+}
+
+// Elements [t, t + 4) of a run of `len` floats (+0.0 past its end).  A run that starts off a 16-byte
+// boundary is read as the two aligned float4 around the four - both inside the run, so nothing outside
+// the caller's samples is touched; only where one of them would cross the run's first or last element
+// (its edges) do the four come one by one.  t advances by 4 per thread, so the case is wave-uniform.
+__device__ __forceinline__ float4 stage_load4(const float *__restrict__ run, unsigned long long t, unsigned long long len) {
+  const float *p = run + t;
+  const unsigned mis = static_cast<unsigned>(reinterpret_cast<uintptr_t>(p) >> 2) & 3u;
+  if (mis == 0 && t + 4 <= len) return *reinterpret_cast<const float4 *>(p);
+  if (mis != 0 && t >= mis && t - mis + 8 <= len) {
+    const float4 a = *reinterpret_cast<const float4 *>(p - mis), b = *reinterpret_cast<const float4 *>(p - mis + 4);
+    if (mis == 1) return float4{a.y, a.z, a.w, b.x};
+    if (mis == 2) return float4{a.z, a.w, b.x, b.y};
+    return float4{a.w, b.x, b.y, b.z};
+  }
+  float4 r;
+  r.x = t < len ? p[0] : 0.0f;
+  r.y = t + 1 < len ? p[1] : 0.0f;
+  r.z = t + 2 < len ? p[2] : 0.0f;
+  r.w = t + 3 < len ? p[3] : 0.0f;
+  return r;
+}
+
+// Interleaved clips (and mono planar ones, which are the same thing): a clip is ONE run of len * ch floats,
+// a thread copies a float4 of it.  grid (V, ch).
+__global__ __launch_bounds__(256) void k_stage_clips(const float *__restrict__ src, const StageClip *__restrict__ clips,
+                                                      unsigned n_clips, unsigned ch, float *__restrict__ vs) {
+  const unsigned v = blockIdx.x;
+  const StageClip cl = stage_find_clip(clips, n_clips, v);
+  const unsigned per_hop = static_cast<unsigned>(kHopI) * ch;
+  const unsigned o = (blockIdx.y * 256u + threadIdx.x) * 4u;
+  if (o >= per_hop) return;
+  const unsigned long long t = static_cast<unsigned long long>(v - cl.slot) * per_hop + o;
+  *reinterpret_cast<float4 *>(vs + static_cast<size_t>(v) * per_hop + o) = stage_load4(src + cl.src, t, cl.len * ch);
+}
+
+// Planar clips of 2 / 4 / 8 channels: a thread takes the same four samples of every plane (CH coalesced
+// 16-byte loads, one plane each) and stores them interleaved as CH float4.  grid (V).
+template <int CH>
+__global__ __launch_bounds__(256) void k_stage_clips_planar(const float *__restrict__ src, const StageClip *__restrict__ clips,
+                                                             unsigned n_clips, unsigned long long cstride,
+                                                             float *__restrict__ vs) {
+  const unsigned v = blockIdx.x;
+  const StageClip cl = stage_find_clip(clips, n_clips, v);
+  const unsigned i0 = threadIdx.x * 4u;
+  const unsigned long long t = static_cast<unsigned long long>(v - cl.slot) * kHopI + i0;
+  float q[4 * CH];  // [sample][channel]
+#pragma unroll
+  for (int c = 0; c < CH; ++c) {
+    const float4 p = stage_load4(src + cl.src + c * cstride, t, cl.len);
+    q[c] = p.x, q[CH + c] = p.y, q[2 * CH + c] = p.z, q[3 * CH + c] = p.w;
+  }
+  float4 *dst = reinterpret_cast<float4 *>(vs + (static_cast<size_t>(v) * kHopI + i0) * CH);
+#pragma unroll
+  for (int j = 0; j < CH; ++j) dst[j] = float4{q[4 * j], q[4 * j + 1], q[4 * j + 2], q[4 * j + 3]};
+}
+
+// Planar clips of any other channel count: a thread owns a float4 of the interleaved OUTPUT and fetches its
+// four samples one by one (a division each).  grid (V, ch).
+__global__ __launch_bounds__(256) void k_stage_clips_planar_any(const float *__restrict__ src,
+                                                                 const StageClip *__restrict__ clips, unsigned n_clips,
+                                                                 unsigned ch, unsigned long long cstride,
+                                                                 float *__restrict__ vs) {
+  const unsigned v = blockIdx.x;
+  const StageClip cl = stage_find_clip(clips, n_clips, v);
+  const unsigned per_hop = static_cast<unsigned>(kHopI) * ch;
+  const unsigned o = (blockIdx.y * 256u + threadIdx.x) * 4u;
+  if (o >= per_hop) return;
+  const unsigned long long t0 = static_cast<unsigned long long>(v - cl.slot) * kHopI;
+  float q[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const unsigned i = (o + e) / ch, c = (o + e) - i * ch;
+    q[e] = t0 + i < cl.len ? src[cl.src + c * cstride + t0 + i] : 0.0f;
+  }
+  *reinterpret_cast<float4 *>(vs + static_cast<size_t>(v) * per_hop + o) = float4{q[0], q[1], q[2], q[3]};
+}
+
+// ------------------------------------------------------------------------------------------
+// D2 into strided clips (glc_roundtrip_batch_device): k_overlap_add_batch with a 64-bit destination, which
+// may be 4 bytes off any boundary (the chunks are laid over the ADDRESS, not over an index), and a planar
+// form.  Same sums as k_overlap_add.
+// ------------------------------------------------------------------------------------------
+template <int CH>
+__global__ __launch_bounds__(256) void k_overlap_add_strided(const float *__restrict__ blocks,
+                                                              const HopDescStrided *__restrict__ desc, unsigned ch,
+                                                              float *__restrict__ out) {
+  const HopDescStrided d = desc[blockIdx.y];
+  float *span = out + d.dst;
+  const unsigned lead = static_cast<unsigned>(reinterpret_cast<uintptr_t>(span) >> 2) & 3u;
+  const unsigned n_chunks = (lead + d.cnt + 3u) >> 2;
+  const bool has_prev = d.prev >= 0, has_cur = d.cur >= 0;
+  const float *prev = blocks + (static_cast<size_t>(has_prev ? d.prev : 0) * ch) * kFrameI + kHopI;
+  const float *cur = blocks + (static_cast<size_t>(has_cur ? d.cur : 0) * ch) * kFrameI;
+  float *base = span - lead;
+  for (unsigned k = blockIdx.x * 256u + threadIdx.x; k < n_chunks; k += gridDim.x * 256u) {
+    const int j0 = static_cast<int>(4u * k) - static_cast<int>(lead);
+    float v[4];
+    bool keep[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int j = j0 + e;
+      keep[e] = j >= 0 && static_cast<unsigned>(j) < d.cnt;
+      const unsigned o = d.first + static_cast<unsigned>(keep[e] ? j : 0);
+      unsigned i, c;
+      if constexpr (CH == 1) i = o, c = 0;
+      else if constexpr (CH == 2) i = o >> 1, c = o & 1u;
+      else if constexpr (CH == 4) i = o >> 2, c = o & 3u;
+      else if constexpr (CH == 8) i = o >> 3, c = o & 7u;
+      else i = o / ch, c = o - i * ch;
+      const size_t at = static_cast<size_t>(c) * kFrameI + i;
+      const float p = has_prev ? prev[at] : 0.0f;
+      v[e] = has_cur ? add_rn(p, cur[at]) : p;
+    }
+    float *dst = base + 4u * static_cast<size_t>(k);
+    if (keep[0] && keep[3]) {
+      *reinterpret_cast<float4 *>(dst) = float4{v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (keep[e]) dst[e] = v[e];
+    }
+  }
+}
+
+// Planar: workgroup (blockIdx.x = plane c, blockIdx.y = hop).  The hop keeps the clip's interleaved samples
+// [j0, j0 + cnt) (sample j is time j / ch of plane j % ch - the trim is counted in interleaved samples, so with 3 or
+// 6 channels a hop's span starts at a different time in different planes); plane c gets the times t with
+// j0 <= t * ch + c < j0 + cnt, at most 1025 of them, consecutive in memory.  A thread owns an aligned float4 of
+// the plane: four consecutive times, whose samples are four consecutive entries of ONE block plane - position
+// i0 + (t - t_lo) of block channel cc, one division per thread.  Only the first and the last chunk of a span
+// can be partial; they store float by float.
+__global__ __launch_bounds__(256) void k_overlap_add_planar(const float *__restrict__ blocks,
+                                                             const HopDescStrided *__restrict__ desc, unsigned ch,
+                                                             float *__restrict__ out) {
+  const HopDescStrided d = desc[blockIdx.y];
+  const unsigned c = blockIdx.x;
+  const unsigned long long j1 = d.j0 + d.cnt;
+  const unsigned long long t_lo = d.j0 > c ? (d.j0 - c + ch - 1) / ch : 0ull, t_hi = j1 > c ? (j1 - c + ch - 1) / ch : 0ull;
+  if (t_hi <= t_lo) return;
+  const unsigned n = static_cast<unsigned>(t_hi - t_lo);
+  const unsigned o0 = d.first + static_cast<unsigned>(t_lo * ch + c - d.j0);  // the hop's interleaved index of (t_lo, c)
+  const unsigned i0 = o0 / ch, cc = o0 - i0 * ch;
+  const bool has_prev = d.prev >= 0, has_cur = d.cur >= 0;
+  const float *prev = blocks + (static_cast<size_t>(has_prev ? d.prev : 0) * ch + cc) * kFrameI + kHopI + i0;
+  const float *cur = blocks + (static_cast<size_t>(has_cur ? d.cur : 0) * ch + cc) * kFrameI + i0;
+  float *span = out + d.dst + c * d.cstride + t_lo;
+  const unsigned lead = static_cast<unsigned>(reinterpret_cast<uintptr_t>(span) >> 2) & 3u;
+  const unsigned n_chunks = (lead + n + 3u) >> 2;
+  float *base = span - lead;
+  for (unsigned k = threadIdx.x; k < n_chunks; k += 256u) {
+    const int j0 = static_cast<int>(4u * k) - static_cast<int>(lead);
+    float v[4];
+    bool keep[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int j = j0 + e;
+      keep[e] = j >= 0 && static_cast<unsigned>(j) < n;
+      const unsigned at = static_cast<unsigned>(keep[e] ? j : 0);
+      const float p = has_prev ? prev[at] : 0.0f;
+      v[e] = has_cur ? add_rn(p, cur[at]) : p;
+    }
+    float *dst = base + 4u * static_cast<size_t>(k);
+    if (keep[0] && keep[3]) {
+      *reinterpret_cast<float4 *>(dst) = float4{v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (keep[e]) dst[e] = v[e];
     }
   }
 }
@@ -1408,8 +1631,9 @@ uint64_t rows_from_records_bytes(uint32_t M) {
   return align256(m * kHopI * 4ull) + 3 * align256(m * 8ull) + 2 * align256(m * 4ull);
 }
 
-hipError_t launch_rows_from_records(const uint8_t *records, uint32_t M, uint32_t ch, void *workspace, uint64_t *stats,
-                                    hipStream_t s, DecodeRows *rows) {
+namespace {
+hipError_t rows_from_records(const uint8_t *records, uint32_t M, uint32_t ch, const FrameMap *fmap, void *workspace,
+                             uint64_t *stats, hipStream_t s, DecodeRows *rows) {
   if (!records || !workspace || !rows || ch == 0 || (reinterpret_cast<uintptr_t>(records) & 15u)) return hipErrorInvalidValue;
   const uint64_t m = M ? M : 1;
   uint8_t *p = static_cast<uint8_t *>(workspace);
@@ -1430,10 +1654,27 @@ hipError_t launch_rows_from_records(const uint8_t *records, uint32_t M, uint32_t
                      reinterpret_cast<const int64_t *>(row_raw), reinterpret_cast<const uint64_t *>(row_raw_len),
                      reinterpret_cast<const int16_t *>(records), 1u};
   if (M == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_rows_from_records, dim3((M + 3) / 4), dim3(256), 0, s, records, M, ch,
-                     static_cast<unsigned long long>(record_bytes(ch)), static_cast<unsigned long long>(record_header_bytes(ch)),
-                     pairs, row_begin, row_cnt, row_scale, row_raw, row_raw_len, reinterpret_cast<unsigned long long *>(stats));
+  const unsigned long long rec = record_bytes(ch), hdr = record_header_bytes(ch);
+  auto *st = reinterpret_cast<unsigned long long *>(stats);
+  if (fmap)
+    hipLaunchKernelGGL(k_rows_from_records<true>, dim3((M + 3) / 4), dim3(256), 0, s, records, M, ch, rec, hdr, pairs, row_begin,
+                       row_cnt, row_scale, row_raw, row_raw_len, st, reinterpret_cast<const uint2 *>(fmap));
+  else
+    hipLaunchKernelGGL(k_rows_from_records<false>, dim3((M + 3) / 4), dim3(256), 0, s, records, M, ch, rec, hdr, pairs, row_begin,
+                       row_cnt, row_scale, row_raw, row_raw_len, st, static_cast<const uint2 *>(nullptr));
   return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_rows_from_records(const uint8_t *records, uint32_t M, uint32_t ch, void *workspace, uint64_t *stats,
+                                    hipStream_t s, DecodeRows *rows) {
+  return rows_from_records(records, M, ch, nullptr, workspace, stats, s, rows);
+}
+
+hipError_t launch_rows_from_records_batch(const uint8_t *records, uint32_t M, uint32_t ch, const FrameMap *fmap, void *workspace,
+                                          uint64_t *clip_stats, hipStream_t s, DecodeRows *rows) {
+  if (!fmap || !clip_stats) return hipErrorInvalidValue;
+  return rows_from_records(records, M, ch, fmap, workspace, clip_stats, s, rows);
 }
 
 uint64_t imdct_plan_bytes(uint32_t groups) {
@@ -1546,6 +1787,51 @@ hipError_t launch_overlap_add_batch(const float *blocks, const HopDesc *desc, ui
 hipError_t launch_overlap_add_batch(const float *blocks, const HopDesc *desc, uint32_t n_desc, uint32_t ch, int16_t *out,
                                     hipStream_t s) {
   return overlap_add_batch_typed(blocks, desc, n_desc, ch, reinterpret_cast<short *>(out), s);
+}
+
+hipError_t launch_stage_clips(const float *src, const StageClip *clips, uint32_t n_clips, uint32_t ch, bool planar,
+                              uint64_t channel_stride, uint32_t n_virtual_frames, float *vstream, hipStream_t s) {
+  if (!src || !clips || !vstream || n_clips == 0 || ch == 0 || (reinterpret_cast<uintptr_t>(vstream) & 15u)) return hipErrorInvalidValue;
+  if (n_virtual_frames == 0) return hipSuccess;
+  const unsigned long long cs = channel_stride;
+  const dim3 wide(n_virtual_frames, ch), one(n_virtual_frames);  // 1024 * ch / 4 float4 over 256 threads: ch workgroups per slot
+  if (ch > 65535u) return hipErrorInvalidValue;
+  if (!planar || ch == 1) {
+    hipLaunchKernelGGL(k_stage_clips, wide, dim3(256), 0, s, src, clips, n_clips, ch, vstream);
+  } else {
+    switch (ch) {
+      case 2: hipLaunchKernelGGL(k_stage_clips_planar<2>, one, dim3(256), 0, s, src, clips, n_clips, cs, vstream); break;
+      case 4: hipLaunchKernelGGL(k_stage_clips_planar<4>, one, dim3(256), 0, s, src, clips, n_clips, cs, vstream); break;
+      case 8: hipLaunchKernelGGL(k_stage_clips_planar<8>, one, dim3(256), 0, s, src, clips, n_clips, cs, vstream); break;
+      default: hipLaunchKernelGGL(k_stage_clips_planar_any, wide, dim3(256), 0, s, src, clips, n_clips, ch, cs, vstream); break;
+    }
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_overlap_add_strided(const float *blocks, const HopDescStrided *desc, uint32_t n_desc, uint32_t ch, bool planar,
+                                      float *out, hipStream_t s) {
+  if (n_desc == 0) return hipSuccess;
+  if (!blocks || !desc || !out || ch == 0 || (reinterpret_cast<uintptr_t>(out) & 3u)) return hipErrorInvalidValue;
+  const unsigned per_hop = 1024u * ch;
+  const unsigned bx = (per_hop / 4u + 255u) / 256u;
+  for (uint32_t d0 = 0; d0 < n_desc; d0 += 32768) {  // slabs: blockIdx.y is 16 bits wide
+    const unsigned nd = n_desc - d0 < 32768 ? n_desc - d0 : 32768;
+    const HopDescStrided *d = desc + d0;
+    if (planar && ch > 1) {
+      hipLaunchKernelGGL(k_overlap_add_planar, dim3(ch, nd), dim3(256), 0, s, blocks, d, ch, out);
+      continue;
+    }
+    const dim3 grid(bx, nd);
+    switch (ch) {
+      case 1: hipLaunchKernelGGL(k_overlap_add_strided<1>, grid, dim3(256), 0, s, blocks, d, ch, out); break;
+      case 2: hipLaunchKernelGGL(k_overlap_add_strided<2>, grid, dim3(256), 0, s, blocks, d, ch, out); break;
+      case 4: hipLaunchKernelGGL(k_overlap_add_strided<4>, grid, dim3(256), 0, s, blocks, d, ch, out); break;
+      case 8: hipLaunchKernelGGL(k_overlap_add_strided<8>, grid, dim3(256), 0, s, blocks, d, ch, out); break;
+      default: hipLaunchKernelGGL(k_overlap_add_strided<0>, grid, dim3(256), 0, s, blocks, d, ch, out); break;
+    }
+  }
+  return hipGetLastError();
 }
 
 hipError_t launch_overlap_add_i16(const float *blocks, int64_t blk_frame0, uint64_t n_frames, uint32_t ch,

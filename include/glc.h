@@ -507,6 +507,48 @@ typedef struct glc_roundtrip_info {
 } glc_roundtrip_info;
 int glc_roundtrip_last_info(glc_ctx *ctx, glc_roundtrip_info *out);
 
+/* ---- round trip of a batch of device-resident clips, any layout --------------------------- */
+
+/* Where the clips of a batch lie in ONE device buffer, in elements (floats) from its start: clip i begins
+ * at i * clip_stride.  Interleaved (planar == 0): sample t of channel c of a clip at t * channels + c.
+ * Planar: at c * channel_stride + t - a (B, C, T) tensor, or any slice of one whose innermost stride is 1.
+ * Clip i has lengths[i] samples per channel (`length` each when lengths == NULL); what lies behind them,
+ * between the planes and between the clips belongs to the caller and is neither read nor written. */
+typedef struct glc_clip_layout {
+  uint64_t n_clips;
+  uint16_t channels;
+  int      planar;          /* 0: a clip is [t][c] interleaved; 1: [c][t], one plane per channel */
+  uint64_t clip_stride;     /* elements from clip i to clip i+1 */
+  uint64_t channel_stride;  /* planar: elements from plane c to plane c+1 of a clip; ignored otherwise */
+  uint64_t length;          /* per-channel samples of every clip when lengths == NULL */
+  const uint64_t *lengths;  /* host array [n_clips] of per-channel samples, or NULL */
+} glc_clip_layout;
+
+/* glc_roundtrip_device of every clip of a batch in one call: for every clip i the lengths[i] * channels
+ * samples of clip i in `out` are bit for bit glc_decode(glc_encode(clip i of `in`)), and NO other element of
+ * d_out is written.  `out` may differ from `in` in `planar` and in the strides; n_clips, channels and the
+ * lengths must agree.  d_out == d_pcm with the same layout runs in place; any other overlap of the two
+ * extents is GLC_EINVAL (the extent of a layout is that of the padded batch: (n_clips - 1) * clip_stride plus
+ * what a clip of the longest length occupies, so the padding behind a short last clip is part of it).  Offsets are 64-bit: a layout may span more than 2^32 elements.
+ * Whole clips are packed into rounds of at most 4096 frames (8192 for mono) - one gather, one transform,
+ * one quantiser, one row-table, one inverse-transform and one overlap-add launch chain per ROUND, whatever
+ * the number of clips; a clip longer than a round is staged whole and goes through the rounds of
+ * glc_roundtrip_device.  Queued on glc_ctx_stream(ctx), NOT synchronised, nothing is copied to the host.
+ * The call blocks on the host only where a workspace has to grow (the rule above) and until the small
+ * table upload of the previous batch call has left its pinned staging memory; it waits for no kernel of
+ * that call.  Afterwards no stream is resident and an open decode session is closed.
+ * GLC_EINVAL, checked before anything is queued: a null pointer, channels == 0, a clip the encoder refuses
+ * (<= 512 samples per channel; the message names the clip), a stride smaller than what a clip or plane
+ * occupies, layouts that do not match.  n_clips == 0 is GLC_OK. */
+int glc_roundtrip_batch_device(glc_ctx *ctx, const float *d_pcm, const glc_clip_layout *in, float *d_out,
+                               const glc_clip_layout *out);
+
+/* glc_roundtrip_last_info for every clip of the last glc_roundtrip_batch_device on this context:
+ * infos[i] is what glc_roundtrip_last_info gives after glc_roundtrip_device of clip i alone, from per-clip
+ * device counters.  Synchronises the context's stream.  GLC_EINVAL when no batch round trip has completed
+ * on this context or n_clips is not that call's. */
+int glc_roundtrip_batch_last_info(glc_ctx *ctx, glc_roundtrip_info *infos, uint64_t n_clips);
+
 /* ---- tables (for inspection / parity tests) ---------------------------------------------- */
 
 /* Copies of the host tables of a context: MdctTables.cos_table [1024*2048] (row k), window

@@ -444,6 +444,17 @@ class RoundTrip {
     detail::check(glc_roundtrip_last_info(ctx_, &i), ctx_);
     return i;
   }
+  // glc_roundtrip_batch_device: every clip of a strided (interleaved or planar) device batch in one call, in place
+  // when d_out == d_pcm and the layouts agree; queued, not synchronised
+  void apply_batch_device(const float *d_pcm, const glc_clip_layout &in, float *d_out, const glc_clip_layout &out) {
+    detail::check(glc_roundtrip_batch_device(ctx_, d_pcm, &in, d_out, &out), ctx_);
+  }
+  // per clip of the last apply_batch_device what last_info gives for that clip alone (synchronises)
+  std::vector<glc_roundtrip_info> last_batch_info(uint64_t n_clips) {
+    std::vector<glc_roundtrip_info> v(n_clips);
+    detail::check(glc_roundtrip_batch_last_info(ctx_, v.data(), n_clips), ctx_);
+    return v;
+  }
   void synchronize() { detail::check(glc_ctx_synchronize(ctx_), ctx_); }
   glc_ctx *ctx() { return ctx_; }
 

@@ -14,6 +14,12 @@
 //                                                         per channel and nothing else (for a kernel + memory-copy
 //                                                         trace; no counters in that run)
 //        build/roundtrip_bench trace-records tone|noise samples   one encode, then 13 glc_decode_device_records calls
+//        build/roundtrip_bench batch [reps = 20]          a loop of glc_roundtrip_device per clip against ONE
+//                                                         glc_roundtrip_batch_device, device-resident on both sides:
+//                                                         64 x 2 s, 512 x 0.25 s, 4 x 60 s (48 kHz stereo); the batch arm
+//                                                         interleaved and planar, the planar loop arm with the two
+//                                                         transposes a caller needs without the call
+//        build/roundtrip_bench trace-batch clips seconds [planar]   3 warm-up + 10 glc_roundtrip_batch_device calls
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -183,7 +189,125 @@ static int run(const char *name, uint64_t per_ch, int reps, bool trace, bool noi
   return 0;
 }
 
+// [B][T][C] <-> [B][C][T], one launch for the whole batch: what x.transpose(1, 2).contiguous() costs a caller
+__global__ void k_swap_layout(const float *__restrict__ in, float *__restrict__ out, unsigned long long n_per_clip, unsigned T,
+                              unsigned ch, bool to_planar) {
+  const unsigned long long i = blockIdx.x * 256ull + threadIdx.x, clip = blockIdx.y;
+  if (i >= n_per_clip) return;
+  const unsigned t = static_cast<unsigned>(i / ch), c = static_cast<unsigned>(i % ch);
+  const unsigned long long a = clip * n_per_clip + i, b = clip * n_per_clip + static_cast<unsigned long long>(c) * T + t;
+  if (to_planar) out[b] = in[a];
+  else out[a] = in[b];
+}
+
+static int run_batch(uint64_t n_clips, double seconds, int reps, bool trace, bool trace_planar) {
+  const uint32_t sr = 48000;
+  const uint16_t ch = 2;
+  const uint64_t T = static_cast<uint64_t>(seconds * sr), per_clip = T * ch, n = n_clips * per_clip;
+  // every clip a different cut of one tonal signal, every fourth one noise (raw frames)
+  const std::vector<float> tone = signal(sr, ch, T + 997 * n_clips, false), noise = signal(sr, ch, T, true);
+  std::vector<float> x(n), xp(n);
+  for (uint64_t b = 0; b < n_clips; ++b) {
+    const float *src = b % 4 == 3 ? noise.data() : tone.data() + 997 * b * ch;
+    std::memcpy(&x[b * per_clip], src, per_clip * sizeof(float));
+    for (uint64_t t = 0; t < T; ++t)
+      for (uint16_t c = 0; c < ch; ++c) xp[b * per_clip + c * T + t] = src[t * ch + c];
+  }
+  glc_ctx *ctx = nullptr;
+  CHECK(glc_ctx_create(0, sr, &ctx));
+  hipStream_t st = static_cast<hipStream_t>(glc_ctx_stream(ctx));
+  float *d_x = nullptr, *d_xp = nullptr, *d_y = nullptr, *d_tmp = nullptr, *d_tmp2 = nullptr;
+  for (float **p : {&d_x, &d_xp, &d_y, &d_tmp, &d_tmp2}) HIPCHECK(hipMalloc(p, n * sizeof(float)));
+  HIPCHECK(hipMemcpy(d_x, x.data(), n * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(d_xp, xp.data(), n * sizeof(float), hipMemcpyHostToDevice));
+  const glc_clip_layout li{n_clips, ch, 0, per_clip, 0, T, nullptr}, lp{n_clips, ch, 1, per_clip, T, T, nullptr};
+  uint64_t got = 0;
+  auto loop = [&](const float *in, float *out) {
+    for (uint64_t b = 0; b < n_clips; ++b)
+      if (const int rc = glc_roundtrip_device(ctx, in + b * per_clip, per_clip, ch, out + b * per_clip, per_clip, &got)) return rc;
+    return 0;
+  };
+  const dim3 grid(static_cast<unsigned>((per_clip + 255) / 256), static_cast<unsigned>(n_clips));
+  auto loop_il = [&] {
+    if (const int rc = loop(d_x, d_y)) return rc;
+    return glc_ctx_synchronize(ctx);
+  };
+  auto loop_pl = [&] {  // planar in, planar out: transpose, loop, transpose back
+    hipLaunchKernelGGL(k_swap_layout, grid, dim3(256), 0, st, d_xp, d_tmp, per_clip, static_cast<unsigned>(T), ch, false);
+    if (const int rc = loop(d_tmp, d_tmp2)) return rc;
+    hipLaunchKernelGGL(k_swap_layout, grid, dim3(256), 0, st, d_tmp2, d_y, per_clip, static_cast<unsigned>(T), ch, true);
+    return glc_ctx_synchronize(ctx);
+  };
+  auto batch_il = [&] {
+    if (const int rc = glc_roundtrip_batch_device(ctx, d_x, &li, d_y, &li)) return rc;
+    return glc_ctx_synchronize(ctx);
+  };
+  auto batch_pl = [&] {
+    if (const int rc = glc_roundtrip_batch_device(ctx, d_xp, &lp, d_y, &lp)) return rc;
+    return glc_ctx_synchronize(ctx);
+  };
+  if (trace) {
+    for (int i = 0; i < 13; ++i) CHECK(trace_planar ? batch_pl() : batch_il());
+    std::printf("trace-batch (%s): 3 warm-up + 10 glc_roundtrip_batch_device calls, %llu clips x %llu samples x %u ch\n",
+                trace_planar ? "planar" : "interleaved", (unsigned long long)n_clips, (unsigned long long)T, ch);
+  } else {
+    // the same bits, before anything is timed
+    std::vector<float> ya(n), yb(n);
+    CHECK(loop_il());
+    HIPCHECK(hipMemcpy(ya.data(), d_y, n * sizeof(float), hipMemcpyDeviceToHost));
+    CHECK(batch_il());
+    HIPCHECK(hipMemcpy(yb.data(), d_y, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (std::memcmp(ya.data(), yb.data(), n * sizeof(float))) return std::printf("the interleaved batch differs from the loop\n"), 1;
+    CHECK(loop_pl());
+    HIPCHECK(hipMemcpy(ya.data(), d_y, n * sizeof(float), hipMemcpyDeviceToHost));
+    CHECK(batch_pl());
+    HIPCHECK(hipMemcpy(yb.data(), d_y, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (std::memcmp(ya.data(), yb.data(), n * sizeof(float))) return std::printf("the planar batch differs from the loop\n"), 1;
+    std::vector<glc_roundtrip_info> infos(n_clips);
+    CHECK(glc_roundtrip_batch_last_info(ctx, infos.data(), n_clips));
+    uint64_t frames = 0, raw = 0;
+    for (const glc_roundtrip_info &i : infos) frames += i.n_frames, raw += i.n_raw_frames;
+    auto timed = [&](auto &&fn, std::vector<double> &into) {
+      const double t0 = now_ms();
+      const int rc = fn();
+      into.push_back(now_ms() - t0);
+      return rc;
+    };
+    const int warm = std::max(3, reps / 5);
+    for (int i = 0; i < warm; ++i) { CHECK(loop_il()); CHECK(batch_il()); CHECK(loop_pl()); CHECK(batch_pl()); }
+    std::vector<double> la, la2, bi, lpl, lpl2, bp;
+    for (int i = 0; i < reps; ++i) {
+      CHECK(timed(loop_il, la)); CHECK(timed(batch_il, bi)); CHECK(timed(loop_il, la2)); CHECK(timed(batch_il, bi));
+      CHECK(timed(loop_pl, lpl)); CHECK(timed(batch_pl, bp)); CHECK(timed(loop_pl, lpl2)); CHECK(timed(batch_pl, bp));
+    }
+    const Stat A = stat(la), A2 = stat(la2), B = stat(bi), P = stat(lpl), P2 = stat(lpl2), Q = stat(bp);
+    const double si = std::fabs(A.med - A2.med), sp = std::fabs(P.med - P2.med);
+    std::printf("%llu clips x %.2f s x %u ch at %u Hz: %llu frames (%llu raw), %d interleaved reps (ms per batch: median [p10 .. p90])\n",
+                (unsigned long long)n_clips, seconds, ch, sr, (unsigned long long)frames, (unsigned long long)raw, reps);
+    std::printf("  interleaved  loop of glc_roundtrip_device              %.4f [%.4f .. %.4f]   again %.4f   A/A spread %.4f\n", A.med, A.p10,
+                A.p90, A2.med, si);
+    std::printf("  interleaved  glc_roundtrip_batch_device                %.4f [%.4f .. %.4f]   new - loop %+.4f   loop / new %.2f  -> %s\n", B.med,
+                B.p10, B.p90, B.med - std::min(A.med, A2.med), std::min(A.med, A2.med) / B.med, verdict(B.med, A.med, A2.med, si));
+    std::printf("  planar       transpose + loop + transpose              %.4f [%.4f .. %.4f]   again %.4f   A/A spread %.4f\n", P.med, P.p10,
+                P.p90, P2.med, sp);
+    std::printf("  planar       glc_roundtrip_batch_device                %.4f [%.4f .. %.4f]   new - loop %+.4f   loop / new %.2f  -> %s\n", Q.med,
+                Q.p10, Q.p90, Q.med - std::min(P.med, P2.med), std::min(P.med, P2.med) / Q.med, verdict(Q.med, P.med, P2.med, sp));
+  }
+  for (float *p : {d_x, d_xp, d_y, d_tmp, d_tmp2}) (void)hipFree(p);
+  glc_ctx_destroy(ctx);
+  return 0;
+}
+
 int main(int argc, char **argv) {
+  if (argc > 3 && !std::strcmp(argv[1], "trace-batch"))
+    return run_batch(std::strtoull(argv[2], nullptr, 10), std::atof(argv[3]), 0, true, argc > 4 && !std::strcmp(argv[4], "planar"));
+  if (argc > 1 && !std::strcmp(argv[1], "batch")) {
+    const int reps = argc > 2 ? std::max(5, std::atoi(argv[2])) : 20;
+    if (run_batch(64, 2.0, reps, false, false)) return 1;
+    if (run_batch(512, 0.25, reps, false, false)) return 1;
+    if (run_batch(4, 60.0, std::max(5, reps / 2), false, false)) return 1;
+    return 0;
+  }
   if (argc > 3 && !std::strcmp(argv[1], "trace"))
     return run("trace", std::strtoull(argv[3], nullptr, 10), 0, true, !std::strcmp(argv[2], "noise"));
   if (argc > 3 && !std::strcmp(argv[1], "trace-records"))
