@@ -623,6 +623,9 @@ int glc_compact_device_records(glc_ctx *ctx, const void *d_records, uint64_t n_f
                                void *d_blob, uint64_t cap, glc_compact_info *info) {
   if (!ctx || !d_blob || !info || (!d_records && n_frames)) return fail(ctx, GLC_EINVAL, "glc_compact_device_records: null argument");
   if (channels == 0) return fail(ctx, GLC_EINVAL, "glc_compact_device_records: channels == 0");
+  // the kernels read rows as short4 and write the header as 64-bit words (include/glc.h)
+  if (reinterpret_cast<uintptr_t>(d_records) % 8 != 0 || reinterpret_cast<uintptr_t>(d_blob) % 8 != 0)
+    return fail(ctx, GLC_EINVAL, "glc_compact_device_records: d_records and d_blob must be 8-byte aligned");
   const glc::CompactLayout l = glc::compact_layout(channels, n_frames);
   if (cap < l.bound) return fail(ctx, GLC_EINVAL, "glc_compact_device_records: blob buffer smaller than glc_compact_bound()");
   DeviceGuard guard(ctx->device);
@@ -1102,6 +1105,60 @@ static int encode_pipeline(glc_ctx *ctx, const void *pcm_any, glc_pcm_format fmt
 
 namespace {
 
+// The blob of a batch round (glc_encode_batch): header | clip directory u64[2 n_clips] |
+// raw flags | scales | counts | pairs | raw planes, over the n_real REAL frames of the round's clips (M rows).
+struct BatchBlobLayout {
+  uint64_t n_real, M, V;  // frames of the clips / their rows / records of the virtual stream (a junk one behind every clip)
+  uint64_t o_dir, o_israw, o_scale, o_cnt, o_pairs, bound;
+};
+BatchBlobLayout batch_blob_layout(uint32_t ch, const uint64_t *clip_frames, uint64_t n_clips) {
+  BatchBlobLayout l{};
+  for (uint64_t i = 0; i < n_clips; ++i) l.n_real += clip_frames[i], l.V += clip_frames[i] + 1;
+  l.M = l.n_real * ch;
+  l.o_dir = sizeof(glc::CompactHeader);
+  l.o_israw = l.o_dir + glc::align64(16 * n_clips);
+  l.o_scale = l.o_israw + glc::align64(l.n_real);
+  l.o_cnt = l.o_scale + glc::align64(4 * l.M);
+  l.o_pairs = l.o_cnt + glc::align64(4 * l.M);
+  l.bound = l.o_pairs + 4096ull * l.M + 64ull;
+  return l;
+}
+
+// Queues the segment-aware compaction of a batch round on `st`: clip i of clip_frames[i] frames owns the records
+// slot_i .. slot_i + clip_frames[i] - 1 of `d_records`, record slot_i + clip_frames[i] is junk and slot_{i+1} comes
+// behind it.  The frame map (pinned in host_stage behind the blob's first o_pairs bytes, on the device behind the
+// scratch of compact_launch in pack_meta), the zeroed header / directory / section padding, then P1-P3 into
+// `d_blob` (l.bound bytes).  Nothing is synchronised.
+int compact_batch_launch(glc_ctx *ctx, const void *d_records, const uint64_t *clip_frames, uint64_t n_clips, uint32_t ch,
+                         const BatchBlobLayout &l, uint8_t *d_blob, hipStream_t st) {
+  if (l.M > 0xFFFFFFFFull || l.V > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, "batch compaction: frame range too long");
+  const size_t scratch = compact_scratch_bytes(l.M), o_fmap_h = align_up(l.o_pairs, 256);
+  GLC_HIP(ctx, ctx->pack_meta.reserve(scratch + align_up(l.n_real * sizeof(glc::FrameMap), 256)));
+  GLC_HIP(ctx, ctx->host_stage.reserve(o_fmap_h + l.n_real * sizeof(glc::FrameMap)));
+  uint8_t *mb = static_cast<uint8_t *>(ctx->pack_meta.p);
+  glc::FrameMap *fmap = reinterpret_cast<glc::FrameMap *>(static_cast<uint8_t *>(ctx->host_stage.p) + o_fmap_h);
+  uint64_t slot = 0, real = 0;
+  for (uint64_t i = 0; i < n_clips; ++i) {
+    for (uint64_t f = 0; f < clip_frames[i]; ++f)
+      fmap[real + f] = glc::FrameMap{static_cast<uint32_t>(slot + f), f == 0 ? static_cast<uint32_t>(i) : 0xFFFFFFFFu};
+    slot += clip_frames[i] + 1;
+    real += clip_frames[i];
+  }
+  glc::FrameMap *d_fmap = reinterpret_cast<glc::FrameMap *>(mb + scratch);
+  GLC_HIP(ctx, hipMemcpyAsync(d_fmap, fmap, l.n_real * sizeof(glc::FrameMap), hipMemcpyHostToDevice, st));
+  // the scratch of compact_launch, the frame map behind it
+  const size_t nblk = (static_cast<size_t>(l.M) + 1023) / 1024;
+  const size_t o_loc = 0, o_blk = align_up(static_cast<size_t>(l.M) * 4, 256), o_blkr = o_blk + align_up(nblk * 8, 256),
+               o_tot = o_blkr + align_up(nblk * 8, 256);
+  GLC_HIP(ctx, hipMemsetAsync(d_blob, 0, l.o_pairs, st));  // header + directory + section padding: deterministic bytes
+  GLC_HIP(ctx, glc::launch_compact_batch(static_cast<const uint8_t *>(d_records), static_cast<uint32_t>(l.M), ch, l.n_real, d_fmap,
+                                         reinterpret_cast<uint64_t *>(d_blob + l.o_dir), reinterpret_cast<uint32_t *>(mb + o_loc),
+                                         reinterpret_cast<uint64_t *>(mb + o_blk), reinterpret_cast<uint64_t *>(mb + o_blkr),
+                                         reinterpret_cast<uint64_t *>(mb + o_tot), d_blob, l.o_israw, l.o_scale, l.o_cnt,
+                                         l.o_pairs, st));
+  return GLC_OK;
+}
+
 struct BatchClip {
   uint64_t index;  // in the caller's arrays
   glc_plan plan;
@@ -1125,26 +1182,21 @@ int encode_batch_round(glc_ctx *ctx, const std::vector<BatchClip> &clips, const 
   const bool is_int = fmt != GLC_PCM_F32;
   const uint64_t elem = fmt == GLC_PCM_S16 ? 2 : 4;  // bytes per sample as uploaded
   const uint64_t n = clips.size();
-  uint64_t V = 0, n_real = 0;  // frames of the virtual stream / of the clips
-  for (const BatchClip &c : clips) V += c.plan.n_frames + 1, n_real += c.plan.n_frames;
-  const uint64_t T = V * glc::kHop, n_virtual = T * ch, M = n_real * ch;
+  std::vector<uint64_t> clip_frames(n);
+  for (uint64_t i = 0; i < n; ++i) clip_frames[i] = clips[i].plan.n_frames;
+  const BatchBlobLayout bl = batch_blob_layout(ch, clip_frames.data(), n);  // the round's blob
+  const uint64_t V = bl.V, n_real = bl.n_real, M = bl.M;  // frames of the virtual stream / of the clips; rows of the clips
+  const uint64_t T = V * glc::kHop, n_virtual = T * ch;
   const uint64_t rec = glc::record_bytes(ch);
-  // the round's blob: header | clip directory | raw flags | scales | counts | pairs | raw planes
-  const uint64_t o_dir = sizeof(glc::CompactHeader), o_israw = o_dir + glc::align64(16 * n),
-                 o_scale = o_israw + glc::align64(n_real), o_cnt = o_scale + glc::align64(4 * M),
-                 o_pairs = o_cnt + glc::align64(4 * M), bound = o_pairs + 4096ull * M + 64ull;
-  const size_t scratch = compact_scratch_bytes(M), o_fmap_h = align_up(o_pairs, 256);
+  const uint64_t o_dir = bl.o_dir, o_israw = bl.o_israw, o_scale = bl.o_scale, o_cnt = bl.o_cnt, o_pairs = bl.o_pairs,
+                 bound = bl.bound;
   GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // earlier work may still read the staging buffers
   GLC_HIP(ctx, ctx->pcm.reserve(static_cast<size_t>(n_virtual) * sizeof(float)));
   if (is_int) GLC_HIP(ctx, ctx->pcm_int.reserve(static_cast<size_t>(n_virtual) * elem));
   GLC_HIP(ctx, ctx->records.reserve(static_cast<size_t>(V) * rec));
   GLC_HIP(ctx, ctx->pack_blob.reserve(bound));
-  GLC_HIP(ctx, ctx->pack_meta.reserve(scratch + align_up(n_real * sizeof(glc::FrameMap), 256)));
-  GLC_HIP(ctx, ctx->host_stage.reserve(o_fmap_h + n_real * sizeof(glc::FrameMap)));
   float *d_pcm = static_cast<float *>(ctx->pcm.p);
   uint8_t *d_up = static_cast<uint8_t *>(is_int ? ctx->pcm_int.p : ctx->pcm.p);  // where the uploads land
-  uint8_t *hm = static_cast<uint8_t *>(ctx->host_stage.p);
-  uint8_t *mb = static_cast<uint8_t *>(ctx->pack_meta.p);
   uint8_t *d_blob = static_cast<uint8_t *>(ctx->pack_blob.p);
   hipStream_t st = ctx->stream;
 
@@ -1171,8 +1223,7 @@ int encode_batch_round(glc_ctx *ctx, const std::vector<BatchClip> &clips, const 
     return e;
   };
   GLC_HIP(ctx, hipMemsetAsync(d_up, 0, static_cast<size_t>(n_virtual) * elem, st));
-  glc::FrameMap *fmap = reinterpret_cast<glc::FrameMap *>(hm + o_fmap_h);
-  uint64_t slot = 0, real = 0;
+  uint64_t slot = 0;
   for (uint64_t i = 0; i < n; ++i) {
     const BatchClip &c = clips[i];
     const uint64_t bytes = n_samples[c.index] * elem, at = slot * glc::kHop * ch;
@@ -1186,10 +1237,7 @@ int encode_batch_round(glc_ctx *ctx, const std::vector<BatchClip> &clips, const 
       GLC_HIP(ctx, send_run());
       GLC_HIP(ctx, hipMemcpyAsync(d_up + at * elem, pcm[c.index], bytes, hipMemcpyHostToDevice, st));
     }
-    for (uint64_t f = 0; f < c.plan.n_frames; ++f)
-      fmap[real + f] = glc::FrameMap{static_cast<uint32_t>(slot + f), f == 0 ? static_cast<uint32_t>(i) : 0xFFFFFFFFu};
     slot += c.plan.n_frames + 1;
-    real += c.plan.n_frames;
   }
   GLC_HIP(ctx, send_run());
   // One widening for the round, whatever the number of clips: every element of the virtual stream, the zeros
@@ -1198,23 +1246,13 @@ int encode_batch_round(glc_ctx *ctx, const std::vector<BatchClip> &clips, const 
   // -0.0 where the reference pads with +0.0.  No output tells the two apart: a transform sum starts from +0.0
   // and +0.0 + -0.0 = +0.0, the raw planes narrow both to 0.
   if (is_int) GLC_HIP(ctx, glc::launch_pcm_widen(d_up, fmt == GLC_PCM_S32, bits, n_virtual, d_pcm, st));
-  glc::FrameMap *d_fmap = reinterpret_cast<glc::FrameMap *>(mb + scratch);
-  GLC_HIP(ctx, hipMemcpyAsync(d_fmap, fmap, n_real * sizeof(glc::FrameMap), hipMemcpyHostToDevice, st));
 
   int rc = encode_range_on(ctx, st, ctx->coef, d_pcm, 0, T, n_virtual, channels, 0, V, ctx->records.p, nullptr);
   if (rc != GLC_OK) return rc;
 
-  {  // the scratch of compact_launch, the frame map behind it
-    const size_t nblk = (static_cast<size_t>(M) + 1023) / 1024;
-    const size_t o_loc = 0, o_blk = align_up(static_cast<size_t>(M) * 4, 256), o_blkr = o_blk + align_up(nblk * 8, 256),
-                 o_tot = o_blkr + align_up(nblk * 8, 256);
-    GLC_HIP(ctx, hipMemsetAsync(d_blob, 0, o_pairs, st));  // header + section padding: deterministic bytes
-    GLC_HIP(ctx, glc::launch_compact_batch(static_cast<const uint8_t *>(ctx->records.p), static_cast<uint32_t>(M), ch, n_real,
-                                           d_fmap, reinterpret_cast<uint64_t *>(d_blob + o_dir),
-                                           reinterpret_cast<uint32_t *>(mb + o_loc), reinterpret_cast<uint64_t *>(mb + o_blk),
-                                           reinterpret_cast<uint64_t *>(mb + o_blkr), reinterpret_cast<uint64_t *>(mb + o_tot),
-                                           d_blob, o_israw, o_scale, o_cnt, o_pairs, st));
-  }
+  rc = compact_batch_launch(ctx, ctx->records.p, clip_frames.data(), n, ch, bl, d_blob, st);
+  if (rc != GLC_OK) return rc;
+  uint8_t *hm = static_cast<uint8_t *>(ctx->host_stage.p);  // reserved by compact_batch_launch: o_pairs bytes and the frame map
   // download 1: header, directory and the per-frame / per-row sections - they say how long the payload is
   GLC_HIP(ctx, hipMemcpyAsync(hm, d_blob, o_pairs, hipMemcpyDeviceToHost, st));
   GLC_HIP(ctx, hipStreamSynchronize(st));
@@ -1235,7 +1273,7 @@ int encode_batch_round(glc_ctx *ctx, const std::vector<BatchClip> &clips, const 
   const float *scale = reinterpret_cast<const float *>(hm + o_scale);
   const uint32_t *cnt = reinterpret_cast<const uint32_t *>(hm + o_cnt);
   std::vector<std::unique_ptr<glc_frames>> made(n);
-  real = 0;
+  uint64_t real = 0;
   for (uint64_t i = 0; i < n && rc == GLC_OK; ++i) {
     const BatchClip &c = clips[i];
     const uint64_t p0 = dir[2 * i], q0 = dir[2 * i + 1];
@@ -2720,6 +2758,33 @@ int glc_debug_overlap_add_device(glc_ctx *ctx, const float *d_blocks, int64_t bl
   }
   DeviceGuard guard(ctx->device);
   GLC_HIP(ctx, glc::launch_overlap_add(d_blocks, blk_frame0, n_frames, channels, hop_begin, hop_end, d_out, ctx->stream));
+  return GLC_OK;
+}
+
+int glc_debug_compact_batch_device(glc_ctx *ctx, const void *d_records, const uint64_t *clip_frames, uint64_t n_clips,
+                                   uint16_t channels, void *d_blob, uint64_t cap, glc_compact_info *info) {
+  if (!ctx || !d_records || !clip_frames || !d_blob || !info)
+    return fail(ctx, GLC_EINVAL, "glc_debug_compact_batch_device: null argument");
+  if (channels == 0 || n_clips == 0) return fail(ctx, GLC_EINVAL, "glc_debug_compact_batch_device: no channels or no clips");
+  for (uint64_t i = 0; i < n_clips; ++i)
+    if (clip_frames[i] == 0 || clip_frames[i] > 0xFFFFFFFFull)
+      return fail(ctx, GLC_EINVAL, "glc_debug_compact_batch_device: a clip of no frames, or of too many");
+  if (n_clips > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, "glc_debug_compact_batch_device: too many clips");
+  if (reinterpret_cast<uintptr_t>(d_records) % 8 != 0 || reinterpret_cast<uintptr_t>(d_blob) % 8 != 0)
+    return fail(ctx, GLC_EINVAL, "glc_debug_compact_batch_device: d_records and d_blob must be 8-byte aligned");
+  const BatchBlobLayout l = batch_blob_layout(channels, clip_frames, n_clips);
+  if (cap < l.bound) return fail(ctx, GLC_EINVAL, "glc_debug_compact_batch_device: blob buffer too small");
+  DeviceGuard guard(ctx->device);
+  GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // earlier work may still read the pinned frame map
+  const int rc = compact_batch_launch(ctx, d_records, clip_frames, n_clips, channels, l, static_cast<uint8_t *>(d_blob), ctx->stream);
+  if (rc != GLC_OK) return rc;
+  glc::CompactHeader h;
+  GLC_HIP(ctx, hipMemcpyAsync(&h, d_blob, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+  GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  info->n_frames = h.n_frames;
+  info->n_pairs = h.n_pairs;
+  info->n_raw_rows = h.n_raw_rows;
+  info->bytes = h.bytes;
   return GLC_OK;
 }
 

@@ -163,7 +163,10 @@ typedef struct glc_compact_info {
 uint64_t glc_compact_bound(uint16_t channels, uint64_t n_frames);
 /* Device-side compaction (scan + ballot pack, ascending k) of `n_frames` records at d_records into
  * the device buffer d_blob (cap >= glc_compact_bound).  Runs on the context's stream and
- * synchronises it (the sizes come back through `info`).  n_frames may be 0 (an empty shard). */
+ * synchronises it (the sizes come back through `info`).  n_frames may be 0 (an empty shard).
+ * d_records and d_blob must both be 8-byte aligned (the kernels read rows as 8-byte vectors and write the
+ * header as 64-bit words; glc_record_bytes is a multiple of 16, so any frame of an aligned record array
+ * is a valid start); a misaligned pointer is refused with GLC_EINVAL before any device work. */
 int glc_compact_device_records(glc_ctx *ctx, const void *d_records, uint64_t n_frames, uint16_t channels,
                                void *d_blob, uint64_t cap, glc_compact_info *info);
 /* Host twin of the same packing, for records that are already in host memory. */

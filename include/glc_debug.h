@@ -2,7 +2,8 @@
  * glc_debug.h - cross-check hooks of libglc_hip.so.  NOT part of the drop-in boundary (that is
  * include/glc.h): these entry points exist so that soak tools and tests can run one stream through
  * two independent implementations of the same arithmetic and demand identical bits, or drive one kernel
- * stage on inputs built for the purpose (tests/test_quantizer_edges.py, tests/test_decode_edges.py).
+ * stage on inputs built for the purpose (tests/test_quantizer_edges.py, tests/test_decode_edges.py,
+ * tests/test_compact_edges.py).
  */
 #ifndef GLC_DEBUG_H
 #define GLC_DEBUG_H
@@ -61,6 +62,19 @@ int glc_debug_quantize_device(glc_ctx *ctx, const float *d_coeffs, const float *
 int glc_debug_overlap_add_device(glc_ctx *ctx, const float *d_blocks, int64_t blk_frame0, uint64_t n_block_frames,
                                  uint64_t n_frames, uint16_t channels, uint64_t hop_begin, uint64_t hop_end, float *d_out,
                                  uint64_t cap);
+
+/* The segment-aware compaction (P1-P3, k_pack_*<true>) exactly as a round of glc_encode_batch runs it - frame map,
+ * blob layout, memset and launch are the round's own code - on caller-supplied records of a virtual stream: clip i
+ * of clip_frames[i] >= 1 frames owns the records slot_i .. slot_i + clip_frames[i] - 1 of d_records, the record
+ * behind them is the junk frame between two clips (d_records holds sum(clip_frames[i] + 1) records) and slot_{i+1}
+ * follows it.  d_blob (cap bytes) receives header (64 B) | clip directory u64[2 n_clips] (pairs and raw rows in front
+ * of clip i) | the sections of glc_compact_device_records over the real frames, every section 64-byte aligned; cap
+ * must be at least 64 + align64(16 n_clips) + align64(n_real) + 2 align64(4 M) + 4096 M + 64 for n_real real frames
+ * of M rows.  d_records and d_blob must be 8-byte aligned.  Synchronises; the sizes come back through `info`.
+ * tests/test_compact_edges.py drives the batch compaction through this with junk records that hold dense rows
+ * and raw flags, which no encode leaves there in a chosen place. */
+int glc_debug_compact_batch_device(glc_ctx *ctx, const void *d_records, const uint64_t *clip_frames, uint64_t n_clips,
+                                   uint16_t channels, void *d_blob, uint64_t cap, glc_compact_info *info);
 
 /* The shader clock the device HOLDS under load (measurement only; bench.py's roofline.clock_ghz_held).
  * `begin` starts one sleeping wave on a stream of its own that runs for `window_us` microseconds beside
