@@ -45,6 +45,16 @@ class GlcRoundtripInfo(C.Structure):
     ]
 
 
+class GlcCompactStatus(C.Structure):
+    """glc_compact_status (include/glc.h): what the device check of a compact blob found."""
+    _fields_ = [
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("n_bad_rows", C.c_uint64),
+        ("first_bad_row", C.c_uint64),
+    ]
+
+
 class GlcClipLayout(C.Structure):
     """glc_clip_layout (include/glc.h): where the clips of a batch lie in one device buffer."""
     _fields_ = [
@@ -210,6 +220,11 @@ SIGNATURES = {
     "glc_roundtrip_last_info": (C.c_int, [_vp, C.POINTER(GlcRoundtripInfo)]),
     "glc_roundtrip_batch_device": (C.c_int, [_vp, _vp, C.POINTER(GlcClipLayout), _vp, C.POINTER(GlcClipLayout)]),
     "glc_roundtrip_batch_last_info": (C.c_int, [_vp, C.POINTER(GlcRoundtripInfo), C.c_uint64]),
+    "glc_decode_device_compact": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint16, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "glc_decode_batch_device_compact": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _vp,
+                                                  C.POINTER(GlcClipLayout)]),
+    "glc_decode_compact_last_status": (C.c_int, [_vp, C.POINTER(GlcCompactStatus), C.c_uint64]),
+    "glc_frames_to_compact": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(GlcCompactInfo)]),
     "glc_version": (C.c_char_p, []),
 }
 

@@ -21,7 +21,7 @@ from typing import Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import (FRAMES_HOOK, GLC_EINVAL, GLC_PCM_F32, GLC_PCM_S16, GLC_PCM_S32, GlcClipLayout, GlcCompactInfo, GlcError,
+from ._lib import (FRAMES_HOOK, GLC_EINVAL, GLC_PCM_F32, GLC_PCM_S16, GLC_PCM_S32, GlcClipLayout, GlcCompactInfo, GlcCompactStatus, GlcError,
                    GlcFramesGather, GlcFramesView, GlcInfo, GlcPlan, GlcRoundtripInfo, check, lib)
 
 FRAME_SIZE = 2048        # src/codec.rs:15
@@ -290,6 +290,28 @@ def compact_records(records: np.ndarray, channels: int) -> np.ndarray:
     return blob[:info.bytes].copy()
 
 
+def frames_to_compact(encoded: "EncodedAudio") -> bytes:
+    """The compact blob of a whole stream (glc_frames_to_compact): the inverse of EncodedAudio.from_compact, the
+    bytes compact_records gives for the stream's records.  One upload puts it into a device store that
+    Decoder.decode_compact_tensor / decode_compact_batch_tensor decode in place.  GlcError (GLC_EINVAL) for a
+    stream a blob cannot hold (non-canonical lists, frames with another number of vectors than channels)."""
+    info = GlcCompactInfo()
+    rc = lib.glc_frames_to_compact(encoded._h, None, 0, C.byref(info))  # sizes the blob, or says why there is none
+    if rc != GLC_EINVAL or info.bytes == 0:
+        check(rc)
+    blob = np.empty(info.bytes, np.uint8)
+    check(lib.glc_frames_to_compact(encoded._h, blob.ctypes.data_as(C.c_void_p), blob.size, C.byref(info)))
+    return blob[:info.bytes].tobytes()
+
+
+@dataclass
+class CompactStatus:
+    """glc_compact_status: what the device check of one compact blob found (include/glc.h GLC_COMPACT_*)."""
+    flags: int
+    n_bad_rows: int
+    first_bad_row: int
+
+
 def plan_encode(n_samples: int, channels: int) -> GlcPlan:
     """Frame count / padding of Encoder::encode (src/codec.rs:433-455); raises where it panics."""
     p = GlcPlan()
@@ -365,6 +387,16 @@ class _Ctx:
 
     def synchronize(self) -> None:
         check(lib.glc_ctx_synchronize(self._h), self._h)
+
+    def _enter_torch_stream(self, device) -> None:
+        """Queue on torch's current stream of `device`.  The legacy default stream has no handle to hand over (0
+        means the private stream, which does not order itself against it): what torch has queued there - the fill
+        of a fresh output, whatever produced the input - is waited for instead."""
+        import torch
+        s = torch.cuda.current_stream(device)
+        if s.cuda_stream == 0:
+            s.synchronize()
+        self.set_stream(s.cuda_stream)
 
     def timer_begin(self) -> None:
         """Record a HIP event on the context's stream (device-side stopwatch)."""
@@ -476,6 +508,30 @@ class Encoder(_Ctx):
         check(lib.glc_compact_device_records(self._h, C.c_void_p(d_records) if d_records else None, n_frames, channels,
                                              C.c_void_p(d_blob), cap, C.byref(info)), self._h)
         return info
+
+    def encode_compact_tensor(self, x, channels: int):
+        """Encode a contiguous float32 CUDA tensor of interleaved samples (1-D, or (frames, channels)) into its
+        compact blob ON THE DEVICE: glc_encode_range_device + glc_compact_device_records into a uint8 CUDA tensor
+        of glc_compact_bound bytes, returned sliced to info.bytes (its storage is 64-byte aligned, as the compact
+        decode wants it) together with the GlcCompactInfo.  Runs on torch's current stream; synchronises (the
+        sizes come back)."""
+        import torch
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous():
+            raise TypeError("encode_compact_tensor takes a contiguous float32 CUDA tensor")
+        if x.device.index != self.device:
+            raise GlcError(GLC_EINVAL, f"the tensor is on {x.device}, this context on device {self.device}")
+        n = x.numel()
+        plan = plan_encode(n, channels)
+        nf = plan.n_frames
+        records = torch.empty(nf * int(lib.glc_record_bytes(channels)), dtype=torch.uint8, device=x.device)
+        blob = torch.empty(compact_bound(channels, nf), dtype=torch.uint8, device=x.device)
+        self._enter_torch_stream(x.device)
+        try:
+            self.encode_range_device(x.data_ptr(), 0, plan.per_channel, n, channels, 0, nf, records.data_ptr())
+            info = self.compact_device_records(records.data_ptr(), nf, channels, blob.data_ptr(), blob.numel())
+        finally:
+            self.set_stream(0)
+        return blob[:info.bytes], info
 
     def mdct_forward_device(self, d_pcm: int, t0: int, t_count: int, n_samples: int, channels: int,
                             frame_begin: int, frame_end: int, d_coeffs: int) -> None:
@@ -589,6 +645,104 @@ class Decoder(_Ctx):
         check(lib.glc_decode_device_records(self._h, C.c_void_p(d_records), n_frames, n_samples, channels,
                                             C.c_void_p(d_out), cap, C.byref(n)), self._h)
         return n.value
+
+    @staticmethod
+    def _blob_tensor(t, what: str, device: int):
+        import torch
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
+            raise TypeError(f"{what} must be a contiguous 1-D uint8 CUDA tensor")
+        if t.device.index != device:
+            raise GlcError(GLC_EINVAL, f"{what} is on {t.device}, this context on device {device}")
+        return t
+
+    def decode_device_compact(self, d_blob: int, blob_bytes: int, n_samples: int, channels: int, d_out: int, cap: int) -> int:
+        """glc_decode_device_compact on raw device addresses; returns the number of samples written.  Queued on the
+        context's stream, not synchronised."""
+        n = C.c_uint64()
+        check(lib.glc_decode_device_compact(self._h, C.c_void_p(d_blob), blob_bytes, n_samples, channels, C.c_void_p(d_out),
+                                            cap, C.byref(n)), self._h)
+        self._compact_clips = 1
+        return n.value
+
+    def decode_compact_tensor(self, blob, n_samples: int, out=None):
+        """Decode ONE compact blob where it lies in device memory (glc_decode_device_compact): `blob` a 1-D uint8
+        CUDA tensor whose first byte is 64-byte aligned, n_samples the stream's interleaved length, the channel
+        count the decoder was made with.  Returns the n_samples decoded samples as a float32 CUDA tensor (`out`,
+        when given: 1-D contiguous float32, at least n_samples long; its first n_samples elements are returned).
+        Queued on torch's current stream as RoundTrip.apply_tensor queues; nothing touches the host."""
+        import torch
+        blob = self._blob_tensor(blob, "blob", self.device)
+        if out is None:
+            out = torch.empty(n_samples, dtype=torch.float32, device=blob.device)
+        elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32 or out.dim() != 1 \
+                or not out.is_contiguous():
+            raise TypeError("out must be a contiguous 1-D float32 CUDA tensor")
+        self._enter_torch_stream(blob.device)
+        try:
+            n = self.decode_device_compact(blob.data_ptr(), blob.numel(), n_samples, self.channels, out.data_ptr(), out.numel())
+        finally:
+            self.set_stream(0)
+        return out[:n]
+
+    def decode_compact_batch_tensor(self, blobs, n_samples, lengths=None, planar: bool = True, out=None):
+        """Decode one compact blob per clip into ONE padded batch tensor (glc_decode_batch_device_compact).  blobs: B
+        1-D uint8 CUDA tensors (64-byte aligned, anywhere in device memory); n_samples: per clip its interleaved
+        length; lengths: per clip its samples per channel (default n_samples[i] // channels).  out: a float32 CUDA
+        tensor (B, C, T) (planar) or (B, T, C) with innermost stride 1 - a slice of something bigger works - or
+        None: a new zero-filled one with T = max(lengths).  The first lengths[i] samples of clip i are what
+        decode_compact_tensor gives for that blob; no other element is written.  One launch chain per round
+        whatever B.  Queued on torch's current stream; returns the output."""
+        import torch
+        b = len(blobs)
+        ch = self.channels
+        ns = [int(v) for v in (n_samples.tolist() if hasattr(n_samples, "tolist") else n_samples)]
+        lens = [v // ch for v in ns] if lengths is None else \
+            [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+        if len(ns) != b or len(lens) != b:
+            raise GlcError(GLC_EINVAL, f"n_samples and lengths must hold {b} values")
+        blobs = [self._blob_tensor(t, f"blobs[{i}]", self.device) for i, t in enumerate(blobs)]
+        if out is None:
+            t_max = max(lens, default=0)
+            dev = blobs[0].device if b else torch.device("cuda", self.device)
+            out = torch.zeros((b, ch, t_max) if planar else (b, t_max, ch), dtype=torch.float32, device=dev)
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32 or out.dim() != 3:
+            raise TypeError("out must be a float32 CUDA tensor of shape (B, C, T) or (B, T, C)")
+        if out.device.index != self.device:
+            raise GlcError(GLC_EINVAL, f"out is on {out.device}, this context on device {self.device}")
+        if out.shape[2] > 1 and out.stride(2) != 1:
+            raise TypeError("out: the innermost stride must be 1")
+        if min(out.stride(0), out.stride(1)) < 0:
+            raise TypeError("out: negative strides")
+        ob, oc, ot = (out.shape[0], out.shape[1], out.shape[2]) if planar else (out.shape[0], out.shape[2], out.shape[1])
+        if ob != b or oc != ch:
+            raise GlcError(GLC_EINVAL, f"out has shape {tuple(out.shape)} for {b} clips of {ch} channels")
+        if not planar and ot > 1 and out.stride(1) != ch:
+            raise TypeError(f"out: an interleaved clip must be dense (stride {ch} between samples)")
+        if any(v < 0 or v > ot for v in lens):
+            raise GlcError(GLC_EINVAL, f"lengths must lie in [0, {ot}]")
+        lens_arr = (C.c_uint64 * max(b, 1))(*lens)
+        lay = GlcClipLayout(b, ch, 1 if planar else 0, out.stride(0), out.stride(1) if planar else 0, ot,
+                            C.cast(lens_arr, C.POINTER(C.c_uint64)))
+        ptrs = (C.c_void_p * max(b, 1))(*[t.data_ptr() for t in blobs])
+        sizes = (C.c_uint64 * max(b, 1))(*[t.numel() for t in blobs])
+        ns_arr = (C.c_uint64 * max(b, 1))(*ns)
+        self._enter_torch_stream(out.device)
+        try:
+            check(lib.glc_decode_batch_device_compact(self._h, ptrs, sizes, ns_arr, C.c_void_p(out.data_ptr()), C.byref(lay)),
+                  self._h)
+        finally:
+            self.set_stream(0)
+        self._compact_clips = b
+        return out
+
+    def last_compact_status(self):
+        """glc_decode_compact_last_status: per blob of the last decode_compact_* call a CompactStatus (flags 0 and
+        no bad rows for a blob that passed every check).  Synchronises."""
+        n = getattr(self, "_compact_clips", 0)
+        arr = (GlcCompactStatus * max(n, 1))()
+        if n:
+            check(lib.glc_decode_compact_last_status(self._h, arr, n), self._h)
+        return [CompactStatus(int(a.flags), int(a.n_bad_rows), int(a.first_bad_row)) for a in arr[:n]]
 
     def imdct_device(self, encoded: EncodedAudio, frame_begin: int, frame_end: int, d_blocks: int) -> None:
         """Dequant + imdct_block + window (src/codec.rs:651-675) alone for a frame range:

@@ -176,6 +176,9 @@ struct glc_ctx {
   };
   std::vector<RtbClipInfo> rtb_info;  // the clips of the last completed batch call (empty: none)
   uint32_t rtb_info_ch = 0;
+  // glc_decode_device_compact / glc_decode_batch_device_compact
+  DevBuf cd_status;         // one glc::CompactStatus per blob of the last call: what R2 found
+  uint64_t cd_status_n = 0; // blobs of that call (0: none has completed)
   HostBuf batch_stage;  // pinned: a round of glc_encode_batch's short clips going up, then its payload coming down / of glc_decode_batch's rows going up
   std::string err;
   // decode session (decode_prepare / round_launch): device-resident sparse rows + position
@@ -400,6 +403,7 @@ void glc_ctx_destroy(glc_ctx *ctx) {
   ctx->rtb_vs.release();
   ctx->rtb_tab.release();
   ctx->rtb_stats.release();
+  ctx->cd_status.release();
   ctx->rtb_stage.release();
   if (ctx->rtb_ev) (void)hipEventDestroy(ctx->rtb_ev);
   ctx->pack_blob.release();
@@ -2111,15 +2115,14 @@ struct RtStridedSink {
   bool planar;
   float *out;
 };
+// ... from row `row0` on of row tables that are on the device (R1 of the round's records, or R2 of a whole blob)
 template <typename T>
-int rt_decode_round(glc_ctx *ctx, const RtGeom &g, const uint8_t *recs, uint64_t f0, uint64_t nf, uint64_t *stats, T *d_out,
-                    const RtStridedSink *sink = nullptr) {
+int rt_decode_round_rows(glc_ctx *ctx, const RtGeom &g, const glc::DecodeRows &rows, uint32_t row0, uint64_t f0, uint64_t nf,
+                         T *d_out, const RtStridedSink *sink) {
   const size_t slot = static_cast<size_t>(g.ch) * glc::kFrame;
   float *blocks = static_cast<float *>(ctx->blocks.p);
   const uint32_t M = static_cast<uint32_t>(nf * g.ch);
-  glc::DecodeRows rows{};
-  GLC_HIP(ctx, glc::launch_rows_from_records(recs, M, g.ch, ctx->rt_rows.p, stats, ctx->stream, &rows));
-  GLC_HIP(ctx, glc::launch_imdct_rows(ctx->dev, rows, 0, M, g.ch, blocks + slot, ctx->stream, ctx->d1_variant, ctx->dec_plan.p,
+  GLC_HIP(ctx, glc::launch_imdct_rows(ctx->dev, rows, row0, M, g.ch, blocks + slot, ctx->stream, ctx->d1_variant, ctx->dec_plan.p,
                                       ctx->dec_plan.p ? ctx->dec_plan_groups : 0, false));
   const bool last = f0 + nf == g.n_frames;
   if (sink) {
@@ -2131,6 +2134,13 @@ int rt_decode_round(glc_ctx *ctx, const RtGeom &g, const uint8_t *recs, uint64_t
   if (!last)
     GLC_HIP(ctx, hipMemcpyAsync(blocks, blocks + nf * slot, slot * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
   return GLC_OK;
+}
+template <typename T>
+int rt_decode_round(glc_ctx *ctx, const RtGeom &g, const uint8_t *recs, uint64_t f0, uint64_t nf, uint64_t *stats, T *d_out,
+                    const RtStridedSink *sink = nullptr) {
+  glc::DecodeRows rows{};
+  GLC_HIP(ctx, glc::launch_rows_from_records(recs, static_cast<uint32_t>(nf * g.ch), g.ch, ctx->rt_rows.p, stats, ctx->stream, &rows));
+  return rt_decode_round_rows(ctx, g, rows, 0, f0, nf, d_out, sink);
 }
 
 RtGeom rt_geom(uint64_t n_frames, uint32_t ch, const glc_plan &plan, uint64_t n_samples) {
@@ -2689,6 +2699,262 @@ int glc_roundtrip_batch_last_info(glc_ctx *ctx, glc_roundtrip_info *infos, uint6
   return GLC_OK;
 }
 
+// ------------------------------------------------------------------------------ decode of compact blobs in HBM
+
+extern "C++" {
+namespace {
+
+// What both calls check of one blob before anything is queued.  `who` already names the clip.
+int cd_check_blob(glc_ctx *ctx, const std::string &who, const void *d_blob, uint64_t blob_bytes, uint32_t ch, uint64_t n_frames) {
+  if (!d_blob) return fail(ctx, GLC_EINVAL, who + ": null argument");
+  if (reinterpret_cast<uintptr_t>(d_blob) & 63u) return fail(ctx, GLC_EINVAL, who + ": the blob is not 64-byte aligned");
+  if (blob_bytes < glc::compact_layout(ch, n_frames).o_pairs)
+    return fail(ctx, GLC_EINVAL, who + ": blob_bytes is smaller than the fixed sections of a blob of that many frames");
+  return GLC_OK;
+}
+
+// A blob of `nf` frames through R2 (one pass over all its rows, tables in rt_rows) and the rounds of the family.
+int cd_decode_one(glc_ctx *ctx, const RtGeom &g, const void *d_blob, uint64_t blob_bytes, glc::CompactStatus *d_status,
+                  float *d_out, const glc::HopDescStrided *desc, bool planar, float *sink_out) {
+  const uint32_t M = static_cast<uint32_t>(g.n_frames * g.ch);
+  const size_t slot = static_cast<size_t>(g.ch) * glc::kFrame;
+  int rc = rt_reserve(ctx, ctx->blocks, (g.round + 1) * slot * sizeof(float));
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rt_rows, glc::rows_from_compact_bytes(M));  // 32 B per row of the STREAM
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rt_edge, 2 * g.per_hop * sizeof(float));
+  if (rc == GLC_OK) rc = reserve_d1_plan(ctx, g.round, g.ch);
+  if (rc != GLC_OK) return rc;
+  const glc::CompactBlob one{reinterpret_cast<uintptr_t>(d_blob), blob_bytes, 0u, M, {0u, 0u}};
+  glc::DecodeRows rows{};
+  GLC_HIP(ctx, glc::launch_rows_from_compact(nullptr, one, 1, M, g.ch, d_blob, ctx->rt_rows.p, d_status, ctx->stream, &rows));
+  for (uint64_t f0 = 0; f0 < g.n_frames; f0 += g.round) {
+    const uint64_t nf = std::min(g.round, g.n_frames - f0), f1 = f0 + nf;
+    RtStridedSink sink{desc, 0u, planar, sink_out};
+    if (desc) {  // the round's descriptors: those of hops [f0, f1 (+ 1)) that keep anything (rtb_impl)
+      for (uint64_t h = f0; h < f1 + (f1 == g.n_frames ? 1 : 0); ++h)
+        if (std::min(g.trim.start + g.trim.n, (h + 1) * g.per_hop) > std::max(g.trim.start, h * g.per_hop)) ++sink.n_desc;
+      desc += sink.n_desc;
+    }
+    rc = rt_decode_round_rows<float>(ctx, g, rows, static_cast<uint32_t>(f0 * g.ch), f0, nf, d_out, desc ? &sink : nullptr);
+    if (rc != GLC_OK) return rc;
+  }
+  return GLC_OK;
+}
+
+// A round of glc_decode_batch_device_compact: blobs [first, first + n) with together n_real frames, or (lng) ONE
+// blob of more frames than a round.
+struct CdRound {
+  uint64_t first = 0, n = 0, n_real = 0;
+  bool lng = false;
+  size_t o_dir = 0, o_desc = 0;  // in the call's table image
+  uint64_t n_desc = 0;
+};
+
+int cdb_impl(glc_ctx *ctx, const void *const *d_blobs, const uint64_t *blob_bytes, float *d_out, const RtbLayout &out,
+             const std::vector<glc_plan> &plans) {
+  const uint64_t n = out.l->n_clips;
+  const uint32_t ch = out.l->channels;
+  const size_t slot = static_cast<size_t>(ch) * glc::kFrame;
+  // rounds as glc_decode_batch packs them: whole clips of together at most kDecodeChunkFrames frames (+ a tail hop each)
+  const uint64_t hop_budget = kDecodeChunkFrames + 1;
+  std::vector<CdRound> rounds;
+  {
+    CdRound cur;
+    uint64_t hops = 0;
+    auto flush = [&](uint64_t next) {
+      if (cur.n) rounds.push_back(cur);
+      cur = CdRound{};
+      cur.first = next;
+      hops = 0;
+    };
+    for (uint64_t i = 0; i < n; ++i) {
+      const uint64_t v = plans[i].n_frames + 1;
+      if (v > hop_budget) {
+        flush(i);
+        cur.n = 1, cur.lng = true, cur.n_real = plans[i].n_frames;
+        flush(i + 1);
+        continue;
+      }
+      if (hops + v > hop_budget) flush(i);
+      cur.n += 1, cur.n_real += plans[i].n_frames, hops += v;
+    }
+    flush(n);
+  }
+  size_t tab = 0;
+  auto place = [&](size_t bytes) {
+    const size_t at = tab;
+    tab = align_up(tab + bytes, 256);
+    return at;
+  };
+  uint64_t max_rows = 0, max_blocks = 0, max_frames = 0;
+  for (CdRound &r : rounds) {
+    if (!r.lng) r.o_dir = place(r.n * sizeof(glc::CompactBlob));
+    for (uint64_t i = r.first; i < r.first + r.n; ++i) r.n_desc += rtb_hops_kept(out.len(i), ch);
+    r.o_desc = place(r.n_desc * sizeof(glc::HopDescStrided));
+    const uint64_t rf = r.lng ? std::min<uint64_t>(kDecodeChunkFrames, r.n_real) : r.n_real;
+    max_rows = std::max(max_rows, r.n_real * ch);  // R2 takes a long clip's rows in one pass
+    max_blocks = std::max(max_blocks, rf + (r.lng ? 1 : 0));
+    max_frames = std::max(max_frames, rf);
+  }
+  rt_forget_streams(ctx);
+  ctx->cd_status_n = 0;
+  int rc = rt_reserve(ctx, ctx->rt_rows, glc::rows_from_compact_bytes(static_cast<uint32_t>(max_rows)));
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->blocks, max_blocks * slot * sizeof(float));
+  if (rc == GLC_OK) rc = reserve_d1_plan(ctx, max_frames, ch);
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rtb_tab, tab);
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->cd_status, n * sizeof(glc::CompactStatus));
+  if (rc != GLC_OK) return rc;
+  if (!ctx->rtb_ev) GLC_HIP(ctx, hipEventCreateWithFlags(&ctx->rtb_ev, hipEventDisableTiming));
+  // the pinned image is shared with glc_roundtrip_batch_device: wait until the last upload has left it
+  if (ctx->rtb_ev_pending) GLC_HIP(ctx, hipEventSynchronize(ctx->rtb_ev));
+  ctx->rtb_ev_pending = false;
+  GLC_HIP(ctx, ctx->rtb_stage.reserve(tab));
+  uint8_t *img = static_cast<uint8_t *>(ctx->rtb_stage.p);
+  uint8_t *d_tab = static_cast<uint8_t *>(ctx->rtb_tab.p);
+  const bool out_planes = out.planes();
+  for (const CdRound &r : rounds) {
+    auto *dir = reinterpret_cast<glc::CompactBlob *>(img + r.o_dir);
+    auto *desc = reinterpret_cast<glc::HopDescStrided *>(img + r.o_desc);
+    uint64_t real = 0;
+    for (uint64_t k = 0; k < r.n; ++k) {
+      const uint64_t i = r.first + k, nf = plans[i].n_frames;
+      const glc::Trim trim = glc::gapless_trim(nf, ch, plans[i].encoder_delay, out.len(i) * ch);
+      if (r.lng) {  // round by round, block slots counted in the ring (frame f0 - 1 of a round in slot 0)
+        for (uint64_t f0 = 0; f0 < nf; f0 += kDecodeChunkFrames) {
+          const uint64_t f1 = std::min(nf, f0 + kDecodeChunkFrames);
+          desc = rtb_write_hops(desc, nf, ch, trim, f0, f1 + (f1 == nf ? 1 : 0), 1 - static_cast<int64_t>(f0), out.at(i),
+                                out_planes, out.l->channel_stride);
+        }
+      } else {
+        dir[k] = glc::CompactBlob{reinterpret_cast<uintptr_t>(d_blobs[i]), blob_bytes[i], static_cast<uint32_t>(real * ch),
+                                  static_cast<uint32_t>(nf * ch), {0u, 0u}};
+        desc = rtb_write_hops(desc, nf, ch, trim, 0, nf + 1, static_cast<int64_t>(real), out.at(i), out_planes,
+                              out.l->channel_stride);
+      }
+      real += nf;
+    }
+    if (static_cast<uint64_t>(desc - reinterpret_cast<glc::HopDescStrided *>(img + r.o_desc)) != r.n_desc)
+      return fail(ctx, GLC_EHIP, "glc_decode_batch_device_compact: hop count arithmetic is inconsistent");
+  }
+  hipStream_t st = ctx->stream;
+  GLC_HIP(ctx, hipMemcpyAsync(d_tab, img, tab, hipMemcpyHostToDevice, st));
+  GLC_HIP(ctx, hipEventRecord(ctx->rtb_ev, st));
+  ctx->rtb_ev_pending = true;
+  auto *d_status = static_cast<glc::CompactStatus *>(ctx->cd_status.p);
+  float *blocks = static_cast<float *>(ctx->blocks.p);
+  for (const CdRound &r : rounds) {
+    const auto *desc = reinterpret_cast<const glc::HopDescStrided *>(d_tab + r.o_desc);
+    if (r.lng) {
+      const uint64_t i = r.first;
+      const RtGeom g = rt_geom(r.n_real, ch, plans[i], out.len(i) * ch);
+      rc = cd_decode_one(ctx, g, d_blobs[i], blob_bytes[i], d_status + i, nullptr, desc, out_planes, d_out);
+      if (rc != GLC_OK) return rc;
+      continue;
+    }
+    // pairs and raw planes are addressed from ONE base: the round's lowest blob (offsets are exact, every blob
+    // is 64-byte aligned)
+    uintptr_t base = reinterpret_cast<uintptr_t>(d_blobs[r.first]);
+    for (uint64_t i = r.first; i < r.first + r.n; ++i) base = std::min(base, reinterpret_cast<uintptr_t>(d_blobs[i]));
+    const uint32_t M = static_cast<uint32_t>(r.n_real * ch);
+    glc::DecodeRows rows{};
+    GLC_HIP(ctx, glc::launch_rows_from_compact(reinterpret_cast<const glc::CompactBlob *>(d_tab + r.o_dir), glc::CompactBlob{},
+                                               static_cast<uint32_t>(r.n), M, ch, reinterpret_cast<const void *>(base),
+                                               ctx->rt_rows.p, d_status + r.first, st, &rows));
+    // (D1's 8-frame units may span two clips: that only widens a union)
+    GLC_HIP(ctx, glc::launch_imdct_rows(ctx->dev, rows, 0, M, ch, blocks, st, ctx->d1_variant, ctx->dec_plan.p,
+                                        ctx->dec_plan.p ? ctx->dec_plan_groups : 0, false));
+    GLC_HIP(ctx, glc::launch_overlap_add_strided(blocks, desc, static_cast<uint32_t>(r.n_desc), ch, out_planes, d_out, st));
+  }
+  ctx->cd_status_n = n;
+  return GLC_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int glc_decode_device_compact(glc_ctx *ctx, const void *d_blob, uint64_t blob_bytes, uint64_t n_samples, uint16_t channels,
+                              float *d_out, uint64_t cap, uint64_t *n_out) {
+  const std::string w("glc_decode_device_compact");
+  if (!ctx) return GLC_EINVAL;
+  if (n_out) *n_out = 0;
+  glc_plan plan;
+  RtGeom g;
+  int rc = rt_check(ctx, w.c_str(), n_samples, channels, d_out, sizeof(float), cap, n_out, &plan, &g);
+  if (rc != GLC_OK) return rc;
+  rc = cd_check_blob(ctx, w, d_blob, blob_bytes, channels, plan.n_frames);
+  if (rc == GLC_OK) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_blob), a1 = a0 + blob_bytes;
+    const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_out), b1 = b0 + g.trim.n * sizeof(float);
+    if (a0 < b1 && b0 < a1) rc = fail(ctx, GLC_EINVAL, w + ": the output overlaps the blob");
+  }
+  if (rc != GLC_OK) {
+    if (n_out) *n_out = 0;
+    return rc;
+  }
+  DeviceGuard guard(ctx->device);
+  rt_forget_streams(ctx);
+  ctx->cd_status_n = 0;
+  rc = rt_reserve(ctx, ctx->cd_status, sizeof(glc::CompactStatus));
+  if (rc == GLC_OK)
+    rc = cd_decode_one(ctx, g, d_blob, blob_bytes, static_cast<glc::CompactStatus *>(ctx->cd_status.p), d_out, nullptr, false, nullptr);
+  if (rc == GLC_OK) ctx->cd_status_n = 1;
+  return rc;
+}
+
+int glc_decode_batch_device_compact(glc_ctx *ctx, const void *const *d_blobs, const uint64_t *blob_bytes, const uint64_t *n_samples,
+                                    float *d_out, const glc_clip_layout *out) {
+  const std::string w("glc_decode_batch_device_compact");
+  if (!ctx) return GLC_EINVAL;
+  if (!out) return fail(ctx, GLC_EINVAL, w + ": null argument");
+  if (out->n_clips == 0) return GLC_OK;
+  if (!d_blobs || !blob_bytes || !n_samples || !d_out) return fail(ctx, GLC_EINVAL, w + ": null argument");
+  if (out->channels == 0) return fail(ctx, GLC_EINVAL, w + ": channels == 0");
+  if (reinterpret_cast<uintptr_t>(d_out) & 3u) return fail(ctx, GLC_EINVAL, w + ": output pointer not aligned to its sample size");
+  const RtbLayout lo{out};
+  const uint64_t n = out->n_clips, ch = out->channels;
+  try {  // no C++ exception may cross the C ABI
+    std::vector<glc_plan> plans(n);
+    for (uint64_t i = 0; i < n; ++i) {
+      const std::string clip = w + ": clip " + std::to_string(i);
+      plans[i] = glc::plan_encode(n_samples[i], out->channels);
+      if (plans[i].n_frames == 0)
+        return fail(ctx, GLC_EINVAL, clip + ": the reference encoder panics on this input (<= 512 samples per channel, or ragged channels)");
+      if (plans[i].n_frames * ch > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, clip + ": stream too long");
+      if (lo.len(i) * ch != n_samples[i]) return fail(ctx, GLC_EINVAL, clip + ": the layout's length is not the decoded length");
+      if (lo.planes() && out->channel_stride < lo.len(i)) return fail(ctx, GLC_EINVAL, clip + ": channel_stride is smaller than a plane");
+      if (n > 1 && out->clip_stride < lo.occupies(i)) return fail(ctx, GLC_EINVAL, clip + ": clip_stride is smaller than the clip");
+      const int rc = cd_check_blob(ctx, clip, d_blobs[i], blob_bytes[i], out->channels, plans[i].n_frames);
+      if (rc != GLC_OK) return rc;
+    }
+    const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_out), b1 = b0 + lo.extent() * sizeof(float);
+    for (uint64_t i = 0; i < n; ++i) {
+      const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_blobs[i]), a1 = a0 + blob_bytes[i];
+      if (a0 < b1 && b0 < a1) return fail(ctx, GLC_EINVAL, w + ": clip " + std::to_string(i) + ": the output extent overlaps the blob");
+    }
+    DeviceGuard guard(ctx->device);
+    return cdb_impl(ctx, d_blobs, blob_bytes, d_out, lo, plans);
+  } catch (const std::bad_alloc &) {
+    return fail(ctx, GLC_ENOMEM, w + ": host allocation failed");
+  }
+}
+
+int glc_decode_compact_last_status(glc_ctx *ctx, glc_compact_status *status, uint64_t n_clips) {
+  if (!ctx || !status) return fail(ctx, GLC_EINVAL, "glc_decode_compact_last_status: null argument");
+  if (ctx->cd_status_n == 0 || !ctx->cd_status.p)
+    return fail(ctx, GLC_EINVAL, "glc_decode_compact_last_status: no compact decode has completed on this context");
+  if (n_clips != ctx->cd_status_n) return fail(ctx, GLC_EINVAL, "glc_decode_compact_last_status: the last call had another number of clips");
+  DeviceGuard guard(ctx->device);
+  try {
+    std::vector<glc::CompactStatus> h(n_clips);
+    GLC_HIP(ctx, hipMemcpyAsync(h.data(), ctx->cd_status.p, n_clips * sizeof(glc::CompactStatus), hipMemcpyDeviceToHost, ctx->stream));
+    GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint64_t i = 0; i < n_clips; ++i)
+      status[i] = glc_compact_status{h[i].flags, 0u, h[i].n_bad_rows, h[i].n_bad_rows ? h[i].first_bad_row : 0ull};
+  } catch (const std::bad_alloc &) {
+    return fail(ctx, GLC_ENOMEM, "glc_decode_compact_last_status: host allocation failed");
+  }
+  return GLC_OK;
+}
+
 uint64_t glc_ctx_resident_stream(const glc_ctx *ctx) { return ctx ? ctx->dec_uid : 0; }
 
 int glc_decode_resident(glc_ctx *ctx, uint64_t stream_id, float *pcm_out, uint64_t cap, uint64_t *n_out) {
@@ -2786,6 +3052,35 @@ int glc_debug_compact_batch_device(glc_ctx *ctx, const void *d_records, const ui
   info->n_raw_rows = h.n_raw_rows;
   info->bytes = h.bytes;
   return GLC_OK;
+}
+
+int glc_debug_rows_from_compact(glc_ctx *ctx, const void *d_blob, uint64_t blob_bytes, uint64_t n_frames, uint16_t channels,
+                                uint64_t *row_begin, uint32_t *row_cnt, float *row_scale, int64_t *row_raw,
+                                uint64_t *row_raw_len, glc_compact_status *status) {
+  const std::string w("glc_debug_rows_from_compact");
+  if (!ctx) return GLC_EINVAL;
+  if (channels == 0 || n_frames == 0 || n_frames * channels > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, w + ": bad shape");
+  int rc = cd_check_blob(ctx, w, d_blob, blob_bytes, channels, n_frames);
+  if (rc != GLC_OK) return rc;
+  DeviceGuard guard(ctx->device);
+  const uint32_t M = static_cast<uint32_t>(n_frames * channels);
+  rt_forget_streams(ctx);
+  ctx->cd_status_n = 0;
+  rc = rt_reserve(ctx, ctx->rt_rows, glc::rows_from_compact_bytes(M));
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->cd_status, sizeof(glc::CompactStatus));
+  if (rc != GLC_OK) return rc;
+  const glc::CompactBlob one{reinterpret_cast<uintptr_t>(d_blob), blob_bytes, 0u, M, {0u, 0u}};
+  glc::DecodeRows rows{};
+  GLC_HIP(ctx, glc::launch_rows_from_compact(nullptr, one, 1, M, channels, d_blob, ctx->rt_rows.p,
+                                             static_cast<glc::CompactStatus *>(ctx->cd_status.p), ctx->stream, &rows));
+  GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (row_begin) GLC_HIP(ctx, hipMemcpy(row_begin, rows.row_begin, M * 8ull, hipMemcpyDeviceToHost));
+  if (row_cnt) GLC_HIP(ctx, hipMemcpy(row_cnt, rows.row_cnt, M * 4ull, hipMemcpyDeviceToHost));
+  if (row_scale) GLC_HIP(ctx, hipMemcpy(row_scale, rows.row_scale, M * 4ull, hipMemcpyDeviceToHost));
+  if (row_raw) GLC_HIP(ctx, hipMemcpy(row_raw, rows.row_raw, M * 8ull, hipMemcpyDeviceToHost));
+  if (row_raw_len) GLC_HIP(ctx, hipMemcpy(row_raw_len, rows.row_raw_len, M * 8ull, hipMemcpyDeviceToHost));
+  ctx->cd_status_n = 1;
+  return status ? glc_decode_compact_last_status(ctx, status, 1) : GLC_OK;
 }
 
 int glc_debug_set_imdct_variant(glc_ctx *ctx, int variant) {

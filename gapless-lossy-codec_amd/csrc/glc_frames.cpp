@@ -309,6 +309,101 @@ int glc_frames_from_compact(uint32_t sample_rate, uint64_t n_samples, uint16_t c
   return glc::frames_from_compact(sample_rate, n_samples, channels, blobs, blob_bytes, n_blobs, false, out);
 }
 
+int glc_frames_to_compact(const glc_frames *f, void *blob, uint64_t cap, glc_compact_info *info) {
+  const char *who = "glc_frames_to_compact: ";
+  if (!f || !info || (!blob && cap)) return GLC_EINVAL;
+  *info = glc_compact_info{0, 0, 0, 0};
+  const uint32_t ch = f->channels;
+  const uint64_t nf = f->n_frames;
+  auto refuse = [&](uint64_t frame, const char *what) {
+    glc::set_global_error(std::string(who) + "frame " + std::to_string(frame) + ": " + what);
+    return GLC_EINVAL;
+  };
+  if (ch == 0) {
+    glc::set_global_error(std::string(who) + "header.channels == 0");
+    return GLC_EINVAL;
+  }
+  if (reinterpret_cast<uintptr_t>(blob) % 8 != 0) {
+    glc::set_global_error(std::string(who) + "blob must be 8-byte aligned");
+    return GLC_EINVAL;
+  }
+  // pass 1: what a blob can hold, and its size.  (The index vectors of a glc_frames are consistent with its
+  // pools: every constructor checks them.)
+  uint64_t n_pairs = 0, n_raw_rows = 0;
+  for (uint64_t fr = 0; fr < nf; ++fr) {
+    const uint64_t l0 = f->list_begin[fr], nl = f->list_begin[fr + 1] - l0;
+    const uint64_t ns = f->scale_begin[fr + 1] - f->scale_begin[fr];
+    const uint64_t nr = f->raw_begin[fr + 1] - f->raw_begin[fr];
+    if (f->raw_tag[fr]) {
+      // the blob keeps no lists or scales of a raw frame (no decoder reads them): a frame that has some would not
+      // come back from glc_frames_from_compact as it went in
+      if (nl != 0 || ns != 0) return refuse(fr, "a raw frame that carries sparse lists or scale factors");
+      if (nr != static_cast<uint64_t>(glc::kFrame) * ch) return refuse(fr, "a raw frame that is not 2048 * channels samples");
+      n_raw_rows += ch;
+      continue;
+    }
+    if (nl != ch || ns != ch) return refuse(fr, "not exactly `channels` sparse lists and `channels` scale factors");
+    if (nr != 0) return refuse(fr, "a compressed frame that carries raw samples");
+    for (uint32_t c = 0; c < ch; ++c) {
+      const uint64_t a = f->list_off[l0 + c], b = f->list_off[l0 + c + 1];
+      if (b - a > glc::kHop) return refuse(fr, "a sparse list that is not strictly ascending below 1024");
+      int32_t last = -1;
+      for (uint64_t j = a; j < b; ++j) {
+        const int32_t k = static_cast<int32_t>(f->pairs[j] & 0xFFFFu);
+        if (k <= last || k >= static_cast<int32_t>(glc::kHop))
+          return refuse(fr, "a sparse list that is not strictly ascending below 1024");
+        last = k;
+      }
+      n_pairs += b - a;
+    }
+  }
+  const glc::CompactLayout l = glc::compact_layout(ch, nf);
+  const uint64_t raw_off = glc::compact_raw_offset(l, n_pairs);
+  info->n_frames = nf;
+  info->n_pairs = n_pairs;
+  info->n_raw_rows = n_raw_rows;
+  info->bytes = raw_off + n_raw_rows * glc::kFrame * 2;
+  if (cap < info->bytes) {
+    glc::set_global_error(std::string(who) + "blob buffer smaller than the blob (info->bytes)");
+    return GLC_EINVAL;
+  }
+  // pass 2: the sections, as glc_compact_records writes them
+  uint8_t *out = static_cast<uint8_t *>(blob);
+  std::memset(out, 0, l.o_pairs);
+  uint8_t *israw = out + l.o_israw;
+  float *scale = reinterpret_cast<float *>(out + l.o_scale);
+  uint32_t *cnt = reinterpret_cast<uint32_t *>(out + l.o_cnt);
+  uint32_t *pairs = reinterpret_cast<uint32_t *>(out + l.o_pairs);
+  std::memset(out + l.o_pairs + 4 * n_pairs, 0, raw_off - (l.o_pairs + 4 * n_pairs));
+  int16_t *rawp = reinterpret_cast<int16_t *>(out + raw_off);
+  uint64_t p_at = 0, r_at = 0;
+  for (uint64_t fr = 0; fr < nf; ++fr) {
+    if (f->raw_tag[fr]) {  // scale 0.0f, cnt 0 on its rows
+      israw[fr] = 1;
+      std::memcpy(rawp + r_at, f->raw.data() + f->raw_begin[fr], sizeof(int16_t) * glc::kFrame * ch);
+      r_at += static_cast<uint64_t>(glc::kFrame) * ch;
+      continue;
+    }
+    const uint64_t l0 = f->list_begin[fr], s0 = f->scale_begin[fr];
+    for (uint32_t c = 0; c < ch; ++c) {
+      const uint64_t a = f->list_off[l0 + c], b = f->list_off[l0 + c + 1];
+      scale[fr * ch + c] = f->scales[s0 + c];
+      cnt[fr * ch + c] = static_cast<uint32_t>(b - a);
+      if (b > a) std::memcpy(pairs + p_at, f->pairs.data() + a, (b - a) * 4);
+      p_at += b - a;
+    }
+  }
+  glc::CompactHeader h{};
+  h.magic = glc::kCompactMagic;
+  h.channels = ch;
+  h.n_frames = nf;
+  h.n_pairs = n_pairs;
+  h.n_raw_rows = n_raw_rows;
+  h.bytes = info->bytes;
+  std::memcpy(out, &h, sizeof h);
+  return GLC_OK;
+}
+
 uint64_t glc_record_bytes(uint16_t channels) { return glc::record_bytes(channels); }
 
 int glc_plan_encode(uint64_t n_samples, uint16_t channels, glc_plan *out) {

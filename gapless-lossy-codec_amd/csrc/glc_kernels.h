@@ -99,6 +99,43 @@ hipError_t launch_rows_from_records(const uint8_t *records, uint32_t M, uint32_t
 constexpr uint32_t kClipStatSlots = 4;
 hipError_t launch_rows_from_records_batch(const uint8_t *records, uint32_t M, uint32_t ch, const FrameMap *fmap, void *workspace,
                                           uint64_t *clip_stats, hipStream_t s, DecodeRows *rows);
+// R2: the DecodeRows of the M rows of one or several COMPACT BLOBS (glc_common.h CompactLayout) that are on the
+// device, built there.  Nothing of the payload is copied: rows->pairs and rows->raw_pool are ONE common base (the
+// lowest blob address, every blob 64-byte aligned) from which row_begin counts in u32 and row_raw in i16, so
+// the lists and raw planes are read where they lie inside the blobs.  Blob i of `n_blobs` is described by
+// CompactBlob {address, capacity in bytes the caller vouches for, first row, rows}; first_row ascends from 0, rows
+// = frames * ch of the stream the host expects, and their sum is M.  `dir` is that table on the device, or
+// null with n_blobs == 1, when `one` travels as a kernel argument.  status[n_blobs] (device, kept by the caller
+// for as long as it wants to read it; written here, no need to zero it): what the checks found.
+//   header (k_r2_headers, one thread per blob): compact_header_error's check - magic, ch, exactly rows / ch frames,
+//   n_pairs <= 1024 rows, n_raw_rows <= rows and a multiple of ch, bytes == the sum of the sections <= capacity.
+//   A blob that fails is read no further: its rows are empty lists of scale 0.0f with no raw plane.
+//   scans (k_r2_scan_rows, k_r2_scan_blocks): row_begin = exclusive 64-bit sum of cnt over the blob's rows in
+//   front (rows of raw frames count 0 whatever their cnt says), raw plane = rows of raw frames in front: sums
+//   inside blocks of 1024 rows, one workgroup scans the block sums in chunks of 1024 and takes each blob's
+//   own origin out of the running sums.  No workgroup waits for another.
+//   rows (k_r2_rows, one wave per row): a compressed row is kept when cnt <= 1024, row_begin + cnt <= n_pairs and
+//   its bins ascend strictly below 1024; the rows of a raw frame when the frame's planes lie below n_raw_rows
+//   and inside `bytes`.  A row that is not kept becomes the empty list with its stored scale and no raw plane.
+//   No load leaves [address, address + capacity).
+// workspace: rows_from_compact_bytes(M) bytes (32 B per row + the block sums) that stay untouched while *rows
+// is in use.  Four launches whatever n_blobs, no synchronisation; any_raw is set (the host does not know).
+struct CompactBlob {
+  uint64_t addr, cap;
+  uint32_t first_row, rows, pad[2];
+};
+constexpr uint32_t kCompactBadHeader = 1u, kCompactRowBounds = 2u, kCompactNotCanonical = 4u, kCompactRawRange = 8u,
+                   kCompactPairSum = 16u, kCompactRawSum = 32u;
+struct CompactStatus {  // 64 bytes per blob
+  uint32_t flags, header_ok;
+  uint64_t n_bad_rows, first_bad_row;  // first_bad_row: ~0 while no row has been rejected
+  uint64_t n_pairs, n_raw_rows, bytes;  // of a header that passed
+  uint64_t pairs_before, raw_before;    // running sums of the launch at the blob's first row
+};
+uint64_t rows_from_compact_bytes(uint32_t M);
+hipError_t launch_rows_from_compact(const CompactBlob *dir, const CompactBlob &one, uint32_t n_blobs, uint32_t M, uint32_t ch,
+                                    const void *base, void *workspace, CompactStatus *status, hipStream_t s,
+                                    DecodeRows *rows);
 // variant (include/glc_debug.h): 0 = shipped (k_imdct_plan + k_imdct_apply, absent row pairs skipped
 // by scalar branches); 1 = one row per workgroup (the cross-check kernel); 2 = plan + apply without
 // the skip; 3 = without the issue-priority schedule; 4 = skipping in row pairs only.  All but 1 need a workspace `plan` of imdct_plan_bytes(plan_groups) bytes,

@@ -1257,6 +1257,251 @@ __global__ __launch_bounds__(256) void k_rows_from_records(const unsigned char *
 }
 
 // ------------------------------------------------------------------------------------------
+// R2: compact blobs -> the row tables D1 reads, without the host and without moving the payload (glc_kernels.h
+// launch_rows_from_compact has the rules).  The blob is almost the table already: cnt is row_cnt, scale is
+// row_scale, the pairs are the rows' lists back to back - what is missing are the two exclusive scans (pairs and
+// raw rows in front of a row) and the checks build_row_table makes on the host, because D1 trusts its rows.
+//   k_r2_headers      one thread per blob: the header check; fills the blob's CompactStatus
+//   k_r2_scan_rows    P1's shape: a workgroup scans 1024 rows (4 per thread, Hillis-Steele over the 256 thread
+//                     sums).  One 64-bit word carries both counts: pairs in the low 53 bits (a block holds
+//                     at most 1024 * (2^32 - 1) of them), rows of raw frames in the high 11 (< 1024 in front of a row
+//                     of the block).  The row's word waits in its row_raw_len slot for k_r2_rows.
+//   k_r2_scan_blocks  P2's shape: ONE workgroup, exclusive scans of the block sums in chunks of 1024, then per
+//                     blob the running sums at its first row (its rows' origin) and the two totals the header
+//                     promised (reported, they reject nothing)
+//   k_r2_rows         one wave per row: bounds, then the list in strides of 64 - lane l compares its bin with
+//                     lane l - 1's (shuffle; lane 0 takes the previous stride's last) - and the row's arrays
+// Rows of several blobs follow each other (glc_decode_batch_device_compact): a row finds its blob by a binary
+// search over the directory's first rows, and the scans simply run across the blobs - a blob's origin is
+// subtracted again.  The sums of a blob whose header failed are taken over nothing.
+// ------------------------------------------------------------------------------------------
+constexpr unsigned long long kR2PairMask = (1ull << 53) - 1ull;
+
+__device__ __forceinline__ unsigned r2_find_blob(const CompactBlob *__restrict__ dir, unsigned n_blobs, unsigned m) {
+  unsigned lo = 0, hi = n_blobs;  // the last blob whose first_row <= m (first_row ascends from 0)
+  while (hi - lo > 1) {
+    const unsigned mid = (lo + hi) >> 1;
+    if (dir[mid].first_row <= m) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// offsets of the fixed sections of a blob of `nf` frames of `ch` channels (glc_common.h compact_layout)
+__device__ __forceinline__ unsigned long long r2_align64(unsigned long long v) { return (v + 63ull) & ~63ull; }
+__device__ __forceinline__ unsigned long long r2_o_scale(unsigned long long nf) { return 64ull + r2_align64(nf); }
+__device__ __forceinline__ unsigned long long r2_o_cnt(unsigned long long nf, unsigned long long rows) {
+  return r2_o_scale(nf) + r2_align64(4ull * rows);
+}
+__device__ __forceinline__ unsigned long long r2_o_pairs(unsigned long long nf, unsigned long long rows) {
+  return r2_o_cnt(nf, rows) + r2_align64(4ull * rows);
+}
+
+__global__ __launch_bounds__(256) void k_r2_headers(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned n_blobs,
+                                                     unsigned ch, CompactStatus *__restrict__ status) {
+  const unsigned b = blockIdx.x * 256u + threadIdx.x;
+  if (b >= n_blobs) return;
+  const CompactBlob e = dir ? dir[b] : one;
+  const unsigned long long nf = e.rows / ch, rows = e.rows;
+  CompactStatus st{};
+  st.first_bad_row = ~0ull;
+  bool ok = e.cap >= r2_o_pairs(nf, rows);  // the host has checked this: the fixed sections lie inside the capacity
+  if (ok) {
+    const unsigned long long *h = reinterpret_cast<const unsigned long long *>(e.addr);
+    const unsigned long long h0 = h[0], h_nf = h[1], h_np = h[2], h_nr = h[3], h_bytes = h[4];
+    ok = h0 == (0x42434C47ull | (static_cast<unsigned long long>(ch) << 32)) && h_nf == nf;
+    ok = ok && h_np <= rows * 1024ull && h_nr <= rows && h_nr % ch == 0;
+    if (ok) {  // counts are bounded: the arithmetic below cannot wrap
+      const unsigned long long need = r2_align64(r2_o_pairs(nf, rows) + 4ull * h_np) + h_nr * 4096ull;
+      ok = h_bytes == need && need <= e.cap;
+    }
+    if (ok) st.n_pairs = h_np, st.n_raw_rows = h_nr, st.bytes = h_bytes;
+  }
+  st.header_ok = ok ? 1u : 0u;
+  if (!ok) {  // every row is rejected
+    st.flags = kCompactBadHeader;
+    st.n_bad_rows = rows;
+    st.first_bad_row = 0;
+  }
+  status[b] = st;
+}
+
+__global__ __launch_bounds__(256) void k_r2_scan_rows(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned n_blobs,
+                                                       unsigned M, unsigned ch, const CompactStatus *__restrict__ status,
+                                                       unsigned long long *__restrict__ loc,
+                                                       unsigned long long *__restrict__ blk,
+                                                       unsigned long long *__restrict__ blk_raw) {
+  __shared__ unsigned long long s_part[256];
+  const unsigned base = blockIdx.x * 1024u + threadIdx.x * 4u;
+  unsigned long long v[4], sum = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const unsigned m = base + j;
+    unsigned long long n = 0;
+    if (m < M) {
+      const unsigned b = dir ? r2_find_blob(dir, n_blobs, m) : 0u;
+      const CompactBlob e = dir ? dir[b] : one;
+      if (status[b].header_ok) {
+        const unsigned lm = m - e.first_row;
+        const unsigned long long nf = e.rows / ch;
+        const unsigned char *blob = reinterpret_cast<const unsigned char *>(e.addr);
+        const unsigned raw = blob[64ull + lm / ch];
+        n = raw ? (1ull << 53) : reinterpret_cast<const unsigned *>(blob + r2_o_cnt(nf, e.rows))[lm];
+      }
+    }
+    v[j] = sum;  // exclusive within the thread
+    sum += n;
+  }
+  s_part[threadIdx.x] = sum;
+  __syncthreads();
+  for (int off = 1; off < 256; off <<= 1) {  // Hillis-Steele inclusive scan of the 256 thread sums
+    const unsigned long long t = threadIdx.x >= static_cast<unsigned>(off) ? s_part[threadIdx.x - off] : 0ull;
+    __syncthreads();
+    s_part[threadIdx.x] += t;
+    __syncthreads();
+  }
+  const unsigned long long before = threadIdx.x ? s_part[threadIdx.x - 1] : 0ull;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (base + j < M) loc[base + j] = before + v[j];
+  if (threadIdx.x == 255) {
+    blk[blockIdx.x] = s_part[255] & kR2PairMask;
+    blk_raw[blockIdx.x] = s_part[255] >> 53;
+  }
+}
+
+__global__ __launch_bounds__(1024) void k_r2_scan_blocks(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned n_blobs,
+                                                          unsigned M, unsigned long long *__restrict__ blk,
+                                                          unsigned long long *__restrict__ blk_raw, unsigned n,
+                                                          const unsigned long long *__restrict__ loc,
+                                                          CompactStatus *__restrict__ status) {
+  __shared__ unsigned long long s[1024];
+  unsigned long long sums[2];
+#pragma unroll 1
+  for (int which = 0; which < 2; ++which) {
+    unsigned long long *v = which ? blk_raw : blk;
+    unsigned long long carry = 0;
+    for (unsigned b0 = 0; b0 < n; b0 += 1024) {
+      const unsigned i = b0 + threadIdx.x;
+      const unsigned long long mine = i < n ? v[i] : 0ull;
+      s[threadIdx.x] = mine;
+      __syncthreads();
+      for (int off = 1; off < 1024; off <<= 1) {
+        const unsigned long long t = threadIdx.x >= static_cast<unsigned>(off) ? s[threadIdx.x - off] : 0ull;
+        __syncthreads();
+        s[threadIdx.x] += t;
+        __syncthreads();
+      }
+      if (i < n) v[i] = carry + s[threadIdx.x] - mine;  // exclusive
+      const unsigned long long chunk_total = s[1023];
+      __syncthreads();
+      carry += chunk_total;
+    }
+    sums[which] = carry;
+  }
+  __syncthreads();  // this workgroup's own stores to blk / blk_raw are read below
+  // per blob: the running sums at its first row and behind its last one
+  for (unsigned b = threadIdx.x; b < n_blobs; b += 1024) {
+    const CompactBlob e = dir ? dir[b] : one;
+    const unsigned long long r0 = e.first_row, r1 = r0 + e.rows;
+    unsigned long long p0 = sums[0], q0 = sums[1], p1 = sums[0], q1 = sums[1];
+    if (r0 < M) {
+      const unsigned long long l = loc[r0];
+      p0 = blk[r0 >> 10] + (l & kR2PairMask), q0 = blk_raw[r0 >> 10] + (l >> 53);
+    }
+    if (r1 < M) {
+      const unsigned long long l = loc[r1];
+      p1 = blk[r1 >> 10] + (l & kR2PairMask), q1 = blk_raw[r1 >> 10] + (l >> 53);
+    }
+    CompactStatus *st = status + b;
+    st->pairs_before = p0;
+    st->raw_before = q0;
+    if (st->header_ok) {
+      unsigned f = st->flags;
+      if (p1 - p0 != st->n_pairs) f |= kCompactPairSum;
+      if (q1 - q0 != st->n_raw_rows) f |= kCompactRawSum;
+      st->flags = f;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_r2_rows(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned n_blobs,
+                                                  unsigned M, unsigned ch, unsigned long long base_addr,
+                                                  const unsigned long long *__restrict__ blk,
+                                                  const unsigned long long *__restrict__ blk_raw,
+                                                  CompactStatus *__restrict__ status,
+                                                  unsigned long long *__restrict__ row_begin, unsigned *__restrict__ row_cnt,
+                                                  float *__restrict__ row_scale, long long *__restrict__ row_raw,
+                                                  unsigned long long *__restrict__ row_raw_len) {
+  const int lane = threadIdx.x & 63;
+  const unsigned long long m64 = static_cast<unsigned long long>(blockIdx.x) * 4ull + (threadIdx.x >> 6);
+  if (m64 >= M) return;
+  const unsigned m = static_cast<unsigned>(m64);
+  const unsigned b = dir ? r2_find_blob(dir, n_blobs, m) : 0u;
+  const CompactBlob e = dir ? dir[b] : one;
+  CompactStatus *st = status + b;
+  unsigned long long begin = 0, raw_len = 0;
+  long long raw_at = -1;
+  unsigned cnt = 0, bad = 0;
+  float scale = 0.0f;
+  const unsigned lm = m - e.first_row;
+  if (st->header_ok) {
+    const unsigned long long nf = e.rows / ch, o_pairs = r2_o_pairs(nf, e.rows);
+    const unsigned long long n_pairs = st->n_pairs, n_raw_rows = st->n_raw_rows;
+    const unsigned char *blob = reinterpret_cast<const unsigned char *>(e.addr);
+    const unsigned c = lm % ch;
+    const unsigned long long l = row_raw_len[m];  // k_r2_scan_rows left the row's word here
+    const unsigned long long p = blk[m >> 10] + (l & kR2PairMask) - st->pairs_before;
+    const unsigned long long r = blk_raw[m >> 10] + (l >> 53) - st->raw_before;
+    scale = reinterpret_cast<const float *>(blob + r2_o_scale(nf))[lm];
+    if (blob[64ull + lm / ch]) {
+      // the frame's ch planes are its raw_pcm as it stands (Q1): they start at plane r - c
+      const unsigned long long raw_off = r2_align64(o_pairs + 4ull * n_pairs), first = r - c;
+      if (r >= c && first + ch <= n_raw_rows && raw_off + (first + ch) * 4096ull <= st->bytes) {
+        raw_at = static_cast<long long>((e.addr - base_addr + raw_off) / 2ull + first * 2048ull);
+        raw_len = 2048ull * ch;
+      } else {
+        bad = kCompactRawRange;
+      }
+    } else {
+      const unsigned n = reinterpret_cast<const unsigned *>(blob + r2_o_cnt(nf, e.rows))[lm];
+      if (n > 1024u || p > n_pairs || n > n_pairs - p) {
+        bad = kCompactRowBounds;
+      } else {
+        const unsigned *list = reinterpret_cast<const unsigned *>(blob + o_pairs) + p;
+        unsigned last = 0, wrong = 0;  // `last`: the bin at the end of the stride before
+        for (unsigned j0 = 0; j0 < n; j0 += 64) {
+          const unsigned j = j0 + lane;
+          const unsigned k = j < n ? list[j] & 0xFFFFu : 0xFFFFFFFFu;
+          unsigned prev = __shfl_up(k, 1);
+          if (lane == 0) prev = last;
+          if (j < n && (k >= 1024u || (j > 0 && k <= prev))) wrong = 1;
+          last = __shfl(k, 63);
+        }
+        if (__any(wrong)) {
+          bad = kCompactNotCanonical;
+        } else {
+          begin = (e.addr - base_addr + o_pairs) / 4ull + p;
+          cnt = n;
+        }
+      }
+    }
+  }
+  if (lane == 0) {
+    row_begin[m] = begin;
+    row_cnt[m] = cnt;
+    row_scale[m] = scale;
+    row_raw[m] = raw_at;
+    row_raw_len[m] = raw_len;
+    if (bad) {
+      atomicOr(&st->flags, bad);
+      atomicAdd(reinterpret_cast<unsigned long long *>(&st->n_bad_rows), 1ull);
+      atomicMin(reinterpret_cast<unsigned long long *>(&st->first_bad_row), static_cast<unsigned long long>(lm));
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // S1: the virtual stream of a round of glc_roundtrip_batch_device, gathered from clips that lie strided
 // (and, `planar`, one plane per channel) in the caller's memory.  Workgroup row blockIdx.x is virtual frame
 // slot v: the 1024 * ch interleaved samples [1024 v, 1024 v + 1024) of the stream.  Its clip is the last one
@@ -1675,6 +1920,48 @@ hipError_t launch_rows_from_records_batch(const uint8_t *records, uint32_t M, ui
                                           uint64_t *clip_stats, hipStream_t s, DecodeRows *rows) {
   if (!fmap || !clip_stats) return hipErrorInvalidValue;
   return rows_from_records(records, M, ch, fmap, workspace, clip_stats, s, rows);
+}
+
+uint64_t rows_from_compact_bytes(uint32_t M) {
+  const uint64_t m = M ? M : 1;
+  // row_begin | row_cnt | row_scale | row_raw | row_raw_len | blk | blk_raw, each 256-byte aligned
+  return 3 * align256(m * 8ull) + 2 * align256(m * 4ull) + 2 * align256((m + 1023) / 1024 * 8ull);
+}
+
+hipError_t launch_rows_from_compact(const CompactBlob *dir, const CompactBlob &one, uint32_t n_blobs, uint32_t M, uint32_t ch,
+                                    const void *base, void *workspace, CompactStatus *status, hipStream_t s,
+                                    DecodeRows *rows) {
+  static_assert(sizeof(CompactBlob) == 32 && sizeof(CompactStatus) == 64, "read and written by the kernels as laid out here");
+  if (!workspace || !status || !rows || !base || ch == 0 || n_blobs == 0 || (!dir && n_blobs != 1)) return hipErrorInvalidValue;
+  if (!dir && ((one.addr & 63u) || one.first_row != 0 || one.rows != M || one.addr < reinterpret_cast<uintptr_t>(base)))
+    return hipErrorInvalidValue;
+  if (reinterpret_cast<uintptr_t>(base) & 63u) return hipErrorInvalidValue;
+  const uint64_t m = M ? M : 1;
+  uint8_t *p = static_cast<uint8_t *>(workspace);
+  auto take = [&](uint64_t bytes) {
+    uint8_t *at = p;
+    p += align256(bytes);
+    return at;
+  };
+  auto *row_begin = reinterpret_cast<unsigned long long *>(take(m * 8ull));
+  auto *row_cnt = reinterpret_cast<unsigned *>(take(m * 4ull));
+  auto *row_scale = reinterpret_cast<float *>(take(m * 4ull));
+  auto *row_raw = reinterpret_cast<long long *>(take(m * 8ull));
+  auto *row_raw_len = reinterpret_cast<unsigned long long *>(take(m * 8ull));
+  const unsigned nblk = static_cast<unsigned>((m + 1023) / 1024);
+  auto *blk = reinterpret_cast<unsigned long long *>(take(nblk * 8ull));
+  auto *blk_raw = reinterpret_cast<unsigned long long *>(take(nblk * 8ull));
+  *rows = DecodeRows{static_cast<const uint32_t *>(base), reinterpret_cast<const uint64_t *>(row_begin), row_cnt, row_scale,
+                     reinterpret_cast<const int64_t *>(row_raw), reinterpret_cast<const uint64_t *>(row_raw_len),
+                     static_cast<const int16_t *>(base), 1u};
+  hipLaunchKernelGGL(k_r2_headers, dim3((n_blobs + 255) / 256), dim3(256), 0, s, dir, one, n_blobs, ch, status);
+  if (M == 0) return hipGetLastError();
+  hipLaunchKernelGGL(k_r2_scan_rows, dim3(nblk), dim3(256), 0, s, dir, one, n_blobs, M, ch, status, row_raw_len, blk, blk_raw);
+  hipLaunchKernelGGL(k_r2_scan_blocks, dim3(1), dim3(1024), 0, s, dir, one, n_blobs, M, blk, blk_raw, nblk, row_raw_len, status);
+  hipLaunchKernelGGL(k_r2_rows, dim3(static_cast<unsigned>((static_cast<uint64_t>(M) + 3) / 4)), dim3(256), 0, s, dir, one, n_blobs,
+                     M, ch, static_cast<unsigned long long>(reinterpret_cast<uintptr_t>(base)), blk, blk_raw, status, row_begin,
+                     row_cnt, row_scale, row_raw, row_raw_len);
+  return hipGetLastError();
 }
 
 uint64_t imdct_plan_bytes(uint32_t groups) {

@@ -552,6 +552,67 @@ int glc_roundtrip_batch_device(glc_ctx *ctx, const float *d_pcm, const glc_clip_
  * on this context or n_clips is not that call's. */
 int glc_roundtrip_batch_last_info(glc_ctx *ctx, glc_roundtrip_info *infos, uint64_t n_clips);
 
+/* ---- decode of compact blobs that are in device memory: a compressed clip store in HBM ------ */
+
+/* The compact blob (glc_compact_device_records, glc_compact_records, glc_frames_to_compact) is the form of a
+ * stream that is as small as the bitstream, and it is almost the decoder's row table already.  The calls below
+ * decode blobs where they lie: one small device pass (R2: the header check, two scans, one wave per row that
+ * checks the row's bounds and that its list ascends strictly below 1024) builds the row tables around the
+ * payload, which is not copied.  A corpus of clips can so be kept in device memory at bitstream size and any
+ * selection of it decoded into a (B, C, T) tensor with no host in the loop.
+ * A blob is untrusted: a header that does not pass glc_frames_from_compact's check (magic, channels, exactly
+ * the frame count n_samples gives, counts its rows can hold, `bytes` exactly the sum of the sections and
+ * <= blob_bytes) decodes as silence and is read no further; a row whose list leaves the pair pool, is longer
+ * than 1024 or is not strictly ascending below 1024, and the rows of a raw frame whose planes the blob does
+ * not hold, decode as an empty list.  No load leaves [blob, blob + blob_bytes).  glc_decode_compact_last_status
+ * says what was found; the calls themselves return GLC_OK (nothing comes back to the host).
+ * d_blob must be 64-byte aligned (every section then keeps the alignment it has inside the blob), blob_bytes
+ * at least the fixed sections of a blob of that many frames.  The family's rules hold: no stream is resident
+ * afterwards, an open decode session is closed, a call synchronises only where a workspace has to grow. */
+
+/* Decoder::decode of the stream ONE compact blob in device memory holds (all its frames, in order): the samples
+ * of glc_decode(glc_frames_from_compact(sample_rate, n_samples, channels, blob)) bit for bit, gapless-trimmed,
+ * at d_out[0 .. *n_out); nothing behind them is written.  n_samples gives the header as in
+ * glc_frames_from_compact.  Queued on glc_ctx_stream(ctx), NOT synchronised, nothing is copied to the host.
+ * The row tables take 32 bytes per row of the stream.
+ * GLC_EINVAL, before anything is queued: a null or misaligned pointer, channels == 0, an n_samples the encoder
+ * refuses, blob_bytes too small, cap < *n_out (*n_out filled), an output that overlaps the blob. */
+int glc_decode_device_compact(glc_ctx *ctx, const void *d_blob, uint64_t blob_bytes, uint64_t n_samples,
+                              uint16_t channels, float *d_out, uint64_t cap, uint64_t *n_out);
+
+/* The same for n_clips blobs, one per clip, into ONE strided device buffer described by a glc_clip_layout
+ * (out->lengths[i] * channels must be n_samples[i], the decoded length of clip i): whole clips packed into rounds
+ * as glc_decode_batch packs them, one R2, one inverse-transform and one strided overlap-add launch chain per ROUND
+ * whatever the number of clips; a clip longer than a round goes through the rounds of the single call.
+ * No element of d_out outside the clips' true samples is written.  The blobs may lie anywhere in device memory.
+ * GLC_EINVAL as above, and for a layout whose strides are too small or whose extent overlaps a blob.
+ * n_clips == 0 is GLC_OK. */
+int glc_decode_batch_device_compact(glc_ctx *ctx, const void *const *d_blobs, const uint64_t *blob_bytes,
+                                    const uint64_t *n_samples, float *d_out, const glc_clip_layout *out);
+
+/* What R2 found in the last of the two calls above: per clip the flag word, the number of rejected rows and
+ * the first of them (row = frame * channels + channel; 0 when none was rejected).  A bad header rejects every
+ * row.  The two SUM flags are reported only: they reject nothing.  Synchronises the context's stream.
+ * GLC_EINVAL when no such call has completed on this context or n_clips is not that call's. */
+#define GLC_COMPACT_BAD_HEADER    1u  /* the header check failed: the clip is silence */
+#define GLC_COMPACT_ROW_BOUNDS    2u  /* a row longer than 1024 or reaching behind n_pairs */
+#define GLC_COMPACT_NOT_CANONICAL 4u  /* a list that is not strictly ascending below 1024 */
+#define GLC_COMPACT_RAW_RANGE     8u  /* a raw frame whose planes the blob does not hold */
+#define GLC_COMPACT_PAIR_SUM     16u  /* the rows' counts do not add up to n_pairs */
+#define GLC_COMPACT_RAW_SUM      32u  /* the rows of raw frames are not n_raw_rows */
+typedef struct glc_compact_status { uint32_t flags; uint32_t reserved; uint64_t n_bad_rows; uint64_t first_bad_row; } glc_compact_status;
+int glc_decode_compact_last_status(glc_ctx *ctx, glc_compact_status *status, uint64_t n_clips);
+
+/* Host only: the compact blob of a whole stream, the inverse of glc_frames_from_compact - the bytes
+ * glc_compact_records gives for the records of that stream (padding zeroed), so that a .glc file can be put into
+ * a device store with one upload.  cap >= info->bytes is enough (glc_compact_bound is always enough); blob must be
+ * 8-byte aligned.  Rows of raw frames get scale 0.0f and cnt 0: EncodedAudio holds neither for them and no decoder
+ * reads them (a blob packed from the ENCODER's records keeps the quantiser's scale there - the only bytes in which
+ * the two can differ).  GLC_EINVAL (glc_last_error(NULL) says why) for a stream a blob cannot hold - a frame whose vectors
+ * are not exactly `channels` lists and `channels` scales, a raw frame that is not 2048 * channels samples, a list
+ * that is not strictly ascending below 1024 - and when cap is too small, with info->bytes filled. */
+int glc_frames_to_compact(const glc_frames *f, void *blob, uint64_t cap, glc_compact_info *info);
+
 /* ---- tables (for inspection / parity tests) ---------------------------------------------- */
 
 /* Copies of the host tables of a context: MdctTables.cos_table [1024*2048] (row k), window

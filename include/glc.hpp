@@ -399,9 +399,43 @@ class Decoder {
     }
   }
 
+  // Compact blobs decoded where they lie in device memory (glc.h glc_decode_device_compact): raw device pointers,
+  // queued on the context's stream, nothing copied to the host.  Returns the number of samples written to d_out.
+  uint64_t decode_device_compact(const void *d_blob, uint64_t blob_bytes, uint64_t n_samples, uint16_t channels, float *d_out,
+                                 uint64_t cap) {
+    uint64_t n = 0;
+    detail::check(glc_decode_device_compact(ctx_, d_blob, blob_bytes, n_samples, channels, d_out, cap, &n), ctx_);
+    return n;
+  }
+  // ... one blob per clip into a strided (interleaved or planar) device batch, one launch chain per round
+  void decode_batch_device_compact(const std::vector<const void *> &d_blobs, const std::vector<uint64_t> &blob_bytes,
+                                   const std::vector<uint64_t> &n_samples, float *d_out, const glc_clip_layout &out) {
+    if (d_blobs.size() != out.n_clips || blob_bytes.size() != out.n_clips || n_samples.size() != out.n_clips)
+      throw Error(GLC_EINVAL, "decode_batch_device_compact: one blob, size and length per clip of the layout");
+    detail::check(glc_decode_batch_device_compact(ctx_, d_blobs.data(), blob_bytes.data(), n_samples.data(), d_out, &out), ctx_);
+  }
+  // what the device check found in the blobs of the last of the two calls (synchronises)
+  std::vector<glc_compact_status> last_compact_status(uint64_t n_clips = 1) {
+    std::vector<glc_compact_status> v(n_clips);
+    if (n_clips) detail::check(glc_decode_compact_last_status(ctx_, v.data(), n_clips), ctx_);
+    return v;
+  }
+
  private:
   glc_ctx *ctx_ = nullptr;
 };
+
+// The compact blob of a whole stream (glc.h glc_frames_to_compact): upload it once, decode it on the device with
+// Decoder::decode_device_compact.  The vector is 8-byte aligned storage of exactly the blob's bytes.
+inline std::vector<uint64_t> to_compact(const EncodedAudio &encoded, glc_compact_info *info_out = nullptr) {
+  glc_compact_info info{};
+  const int sized = glc_frames_to_compact(encoded.handle(), nullptr, 0, &info);
+  if (sized != GLC_EINVAL || info.bytes == 0) detail::check(sized);  // a stream no blob can hold: the library says why
+  std::vector<uint64_t> blob((info.bytes + 7) / 8);
+  detail::check(glc_frames_to_compact(encoded.handle(), blob.data(), info.bytes, &info));
+  if (info_out) *info_out = info;
+  return blob;
+}
 
 // Encoder::encode followed by Decoder::decode as one call (glc.h glc_roundtrip): the samples of
 // decode(encode(x)), bit for bit, with no EncodedAudio assembled on the host - the decoder reads the

@@ -76,6 +76,16 @@ int glc_debug_overlap_add_device(glc_ctx *ctx, const float *d_blocks, int64_t bl
 int glc_debug_compact_batch_device(glc_ctx *ctx, const void *d_records, const uint64_t *clip_frames, uint64_t n_clips,
                                    uint16_t channels, void *d_blob, uint64_t cap, glc_compact_info *info);
 
+/* R2 (launch_rows_from_compact) alone, exactly as glc_decode_device_compact launches it for ONE blob of `n_frames`
+ * frames at d_blob (64-byte aligned, blob_bytes >= the fixed sections): the row tables it builds come back to
+ * the host - M = n_frames * channels entries each, any pointer may be NULL - with the status words.  row_begin
+ * counts u32 and row_raw i16 from d_blob (-1: no raw plane).  Synchronises.  tests/test_compact_decode.py holds
+ * the tables of a blob of more than 1024 * 1024 rows (the second chunk of the block-sum scan) to a model
+ * through this: decoding that many frames would take the test minutes. */
+int glc_debug_rows_from_compact(glc_ctx *ctx, const void *d_blob, uint64_t blob_bytes, uint64_t n_frames, uint16_t channels,
+                                uint64_t *row_begin, uint32_t *row_cnt, float *row_scale, int64_t *row_raw,
+                                uint64_t *row_raw_len, glc_compact_status *status);
+
 /* The shader clock the device HOLDS under load (measurement only; bench.py's roofline.clock_ghz_held).
  * `begin` starts one sleeping wave on a stream of its own that runs for `window_us` microseconds beside
  * whatever the caller queues meanwhile and reads the shader-cycle counter against the constant 100 MHz

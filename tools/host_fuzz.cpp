@@ -1,5 +1,5 @@
 // host_fuzz.cpp — AddressSanitizer + UBSan harness for the host-side parsers and writers of the
-// library (no device code): the .glc container and the structured bridge (glc_frames.cpp), the WAV twin
+// library (no device code): the .glc container, the structured bridge and the compact-blob writer (glc_frames.cpp), the WAV twin
 // (glc_wav.cpp) and the FLAC twin (glc_flac.cpp).  GPU sanitizers are not available on the pool, host ones are, and
 // these are the functions that read files a user did not write.
 //
@@ -144,6 +144,60 @@ static void fuzz_glc(const std::string &tmp) {
     } else {
       REQUIRE(fr == nullptr && (rc == GLC_EFORMAT || rc == GLC_ENOMEM || rc == GLC_EINVAL));
     }
+  }
+}
+
+// ---- glc_frames_to_compact: a stream into the compact blob and back ---------------------------------
+// The blob buffer is a heap block of exactly the size the function asked for: a byte written behind it is a finding.
+static void to_compact_checked(const glc_frames *fr, bool must_pass, const std::vector<uint8_t> *glc) {
+  glc_info fi;
+  REQUIRE(glc_frames_info(fr, &fi) == GLC_OK);
+  glc_compact_info info;
+  const int sized = glc_frames_to_compact(fr, nullptr, 0, &info);
+  if (sized == GLC_EINVAL && info.bytes == 0) {  // a stream no blob can hold
+    REQUIRE(!must_pass);
+    return;
+  }
+  REQUIRE(sized == GLC_EINVAL && info.bytes >= 64 && info.bytes % 64 == 0);
+  std::vector<uint64_t> blob(info.bytes / 8, 0xABABABABABABABABull);
+  const uint64_t want = info.bytes;
+  REQUIRE(glc_frames_to_compact(fr, blob.data(), want - 1, &info) == GLC_EINVAL && info.bytes == want);
+  REQUIRE(glc_frames_to_compact(fr, blob.data(), want, &info) == GLC_OK && info.bytes == want && info.n_frames == fi.n_frames);
+  uint64_t hdr_bytes;
+  std::memcpy(&hdr_bytes, reinterpret_cast<const uint8_t *>(blob.data()) + 32, 8);
+  REQUIRE(hdr_bytes == want);
+  // back: the stream's own length and channel count describe it when its header is the encoder's
+  const void *ptrs[1] = {blob.data()};
+  glc_frames *back = nullptr;
+  const int rc = glc_frames_from_compact(fi.sample_rate, fi.original_length, fi.channels, ptrs, &want, 1, &back);
+  if (must_pass) REQUIRE(rc == GLC_OK);
+  if (rc == GLC_OK) {
+    std::vector<uint8_t> again(glc_serialized_size(back));
+    uint64_t w = 0;
+    REQUIRE(glc_serialize(back, again.data(), again.size(), &w) == GLC_OK);
+    if (glc) REQUIRE(again == *glc);
+    std::vector<uint64_t> blob2(want / 8);
+    REQUIRE(glc_frames_to_compact(back, blob2.data(), want, &info) == GLC_OK && blob2 == blob);
+    glc_frames_free(back);
+  } else {
+    REQUIRE(back == nullptr);
+  }
+}
+
+static void fuzz_to_compact() {
+  std::vector<uint8_t> good = make_glc(1 + static_cast<unsigned>(below(3)), 1 + static_cast<unsigned>(below(6)));
+  if (good.empty()) return;
+  glc_frames *fr = nullptr;
+  REQUIRE(glc_deserialize(good.data(), good.size(), &fr) == GLC_OK);
+  to_compact_checked(fr, true, &good);
+  glc_frames_free(fr);
+  for (int round = 0; round < 40; ++round) {  // whatever still parses is packed or refused, never trusted
+    std::vector<uint8_t> bad = good;
+    for (uint64_t m = 1 + below(3); m; --m) mutate(bad);
+    fr = nullptr;
+    if (glc_deserialize(bad.data(), bad.size(), &fr) != GLC_OK) continue;
+    to_compact_checked(fr, false, nullptr);
+    glc_frames_free(fr);
   }
 }
 
@@ -374,6 +428,7 @@ int main(int argc, char **argv) {
   while (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() < seconds) {
     fuzz_glc(tmp);
     fuzz_bridge();
+    fuzz_to_compact();
     fuzz_wav(tmp);
     fuzz_flac();
     ++rounds;
