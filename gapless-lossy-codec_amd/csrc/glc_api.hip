@@ -190,6 +190,18 @@ struct glc_ctx {
   uint64_t dec_orig_len = 0, dec_n_pairs = 0, dec_n_raw = 0;
   int d1_variant = 0;    // include/glc_debug.h: which inverse-transform kernel / path to launch
   int k1_variant = 0;    // include/glc_debug.h: which forward-transform kernel takes launches of >= 4096 rows
+  // The screened encode (glc_kernels.h launch_encode_screened).  Slot 0 goes with `coef`, slot 1 with `coef_b`:
+  // a workspace of hf planes and flags, and 8 host-mapped words the repair launch leaves its count in.
+  int screen_mode = 0;          // include/glc_debug.h glc_debug_set_encode_screen
+  bool screen_usable = false;   // the rate's last band starts where a screen pays (encode_screen_shape)
+  glc::ScreenShape screen_shape{};
+  DevBuf screen_ws[2];
+  HostBuf screen_stat;          // [2][8] uint32_t
+  uint32_t screen_seq[2] = {0, 0}, screen_judged[2] = {0, 0};  // launches queued / whose count the guard has read
+  uint32_t screen_backoff = 0;  // launches the guard still sends down today's path
+  bool screen_held = false;     // the last count read was a bad one: one probe at a time
+  bool screen_judged_any = false;  // a count has been read since the context was created (or the mode set)
+  uint64_t rows_screened = 0;
   hipStream_t probe_stream = nullptr;  // include/glc_debug.h clock probe
   HostBuf probe_out;
   uint32_t dec_ch = 0;
@@ -359,6 +371,7 @@ int glc_ctx_create(int device, uint32_t sample_rate, glc_ctx **out) {
   d.norm = h.norm;
   d.cf = h.cf;
   d.noise_floor = h.noise_floor;
+  ctx->screen_usable = glc::encode_screen_shape(h.edges.data(), static_cast<uint32_t>(nb), &ctx->screen_shape);
   *out = ctx.release();
   return GLC_OK;
 }
@@ -383,6 +396,9 @@ void glc_ctx_destroy(glc_ctx *ctx) {
   if (ctx->probe_stream) (void)hipStreamDestroy(ctx->probe_stream);
   ctx->probe_out.release();
   ctx->coef_b.release();
+  ctx->screen_ws[0].release();
+  ctx->screen_ws[1].release();
+  ctx->screen_stat.release();
   if (ctx->down_stream) (void)hipStreamDestroy(ctx->down_stream);
   if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -499,6 +515,68 @@ static hipError_t launch_quantize_decide(glc_ctx *ctx, const float *coef, const 
   return e;
 }
 
+// Whether a launch of M rows may take the screened path at all (the mode and the launch's shape; the guard aside).
+static bool screen_may(const glc_ctx *ctx, uint32_t M, uint32_t ch) {
+  if (!ctx->screen_usable || ctx->screen_mode == 1) return false;
+  if (ctx->screen_mode == 2) return M >= 256;
+  return glc::mdct_forward_is_st16(M, ch, ctx->k1_variant);
+}
+
+// Whether a launch of M rows takes the screened path.  Automatic mode: where launch_mdct_forward would pick the
+// 16-wave kernel, unless the guard holds it off.  The guard: content that fails the screen everywhere (noise)
+// pays the fast pass AND a slow repair, so when a count a repair launch left shows more than 1 row in
+// kScreenGuardDen failed, the path is held off: the next kScreenGuardBackoff launches take today's kernels, then
+// ONE launch probes again, and until its count has come back - the host may be many launches ahead of the
+// device - nothing else is screened.  A launch that passes opens the path again.  A context that has read no count
+// yet is treated the same way: its first screened launch is its probe, and the launches queued behind it before
+// its count is back take today's kernels (a burst of noise on a fresh context pays the repair once).  What the
+// guard cannot shorten: when content turns from passing to failing, the launches queued before the first bad
+// count is back are screened and repaired - as many as the caller queues without waiting.
+// The count is a heuristic's input and nothing more: the device leaves {failed, rows, seq} as three plain
+// stores in no order, and this reads them without synchronising - it may see a launch's seq beside the counts
+// of the one before, or judge a launch late.  Either only moves the decision by a launch; the records are the
+// same whichever path a launch takes.
+constexpr uint32_t kScreenGuardDen = 8, kScreenGuardBackoff = 32;
+static bool screen_takes(glc_ctx *ctx, uint32_t M, uint32_t ch) {
+  if (!screen_may(ctx, M, ch)) return false;
+  if (ctx->screen_mode == 2) return true;
+  bool pending = false;  // a screened launch whose count has not come back
+  for (int s = 0; s < 2; ++s) {
+    const volatile uint32_t *hs = static_cast<const volatile uint32_t *>(ctx->screen_stat.p) + 8 * s;
+    const uint32_t seq = hs[2], failed = hs[0], rows = hs[1];
+    if (seq != ctx->screen_judged[s]) {
+      ctx->screen_judged[s] = seq;
+      const bool bad = rows && static_cast<uint64_t>(failed) * kScreenGuardDen > rows;
+      if (bad) ctx->screen_backoff = kScreenGuardBackoff;
+      ctx->screen_held = bad;
+      ctx->screen_judged_any = true;
+    }
+    pending = pending || seq != ctx->screen_seq[s];
+  }
+  if (ctx->screen_backoff) {
+    --ctx->screen_backoff;
+    return false;
+  }
+  return !((ctx->screen_held || !ctx->screen_judged_any) && pending);
+}
+
+// The screened path's workspace of a coefficient workspace (slot 0 with `coef`, 1 with `coef_b`), reserved where
+// that one is: for the largest launch of a range of `frames` frames in chunks of `chunk` that may take the path.
+static hipError_t screen_reserve(glc_ctx *ctx, int slot, uint32_t ch, uint64_t frames, uint64_t chunk) {
+  const uint32_t m_full = static_cast<uint32_t>(std::min(chunk, frames) * ch);
+  const uint32_t m_last = frames > chunk ? static_cast<uint32_t>(frames % chunk * ch) : 0u;
+  uint64_t need = 0;
+  if (screen_may(ctx, m_full, ch)) need = glc::encode_screen_bytes(m_full, ctx->screen_shape);
+  if (m_last && screen_may(ctx, m_last, ch)) need = std::max(need, glc::encode_screen_bytes(m_last, ctx->screen_shape));
+  if (!need) return hipSuccess;
+  if (!ctx->screen_stat.p) {
+    const hipError_t e = ctx->screen_stat.reserve(2 * 8 * sizeof(uint32_t));
+    if (e != hipSuccess) return e;
+    std::memset(ctx->screen_stat.p, 0, 2 * 8 * sizeof(uint32_t));
+  }
+  return ctx->screen_ws[slot].reserve(need);
+}
+
 // glc_encode_range_device on a given stream with a given coefficient workspace (glc_encode runs
 // alternate rounds on two streams)
 static int encode_range_on(glc_ctx *ctx, hipStream_t stream, DevBuf &coef_ws, const float *d_pcm, uint64_t t0, uint64_t t_count,
@@ -516,6 +594,7 @@ static int encode_range_on(glc_ctx *ctx, hipStream_t stream, DevBuf &coef_ws, co
   if (!d_coeffs) {
     const uint64_t rows = std::min<uint64_t>(chunk, frame_end - frame_begin) * ch;
     GLC_HIP(ctx, coef_ws.reserve(std::max<size_t>(rows, 1) * glc::kHop * sizeof(float)));
+    GLC_HIP(ctx, screen_reserve(ctx, &coef_ws == &ctx->coef_b ? 1 : 0, ch, frame_end - frame_begin, chunk));
   }
   // A range of several chunks alternates between the caller's stream and a second one (its own
   // coefficient workspace): chunk c's quantiser then runs beside chunk c+1's transform instead of in
@@ -528,6 +607,7 @@ static int encode_range_on(glc_ctx *ctx, hipStream_t stream, DevBuf &coef_ws, co
     if (!ctx->ev_fork) GLC_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
     if (!ctx->ev_join) GLC_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
     GLC_HIP(ctx, ctx->coef_b.reserve(static_cast<size_t>(chunk) * ch * glc::kHop * sizeof(float)));
+    GLC_HIP(ctx, screen_reserve(ctx, 1, ch, frame_end - frame_begin, chunk));
     GLC_HIP(ctx, hipEventRecord(ctx->ev_fork, stream));
     GLC_HIP(ctx, hipStreamWaitEvent(ctx->stream_b, ctx->ev_fork, 0));
   }
@@ -539,6 +619,18 @@ static int encode_range_on(glc_ctx *ctx, hipStream_t stream, DevBuf &coef_ws, co
     hipStream_t st = odd ? ctx->stream_b : stream;
     float *coef = d_coeffs ? d_coeffs + (f - frame_begin) * ch * glc::kHop : static_cast<float *>(odd ? ctx->coef_b.p : coef_ws.p);
     uint8_t *r = recs + (f - frame_begin) * rec;
+    const int slot = (odd || &coef_ws == &ctx->coef_b) ? 1 : 0;
+    if (!d_coeffs && screen_takes(ctx, M, ch)) {
+      if (ctx->screen_ws[slot].cap < glc::encode_screen_bytes(M, ctx->screen_shape))
+        return fail(ctx, GLC_EINVAL, "glc_encode_range_device: the screen's workspace was not reserved for this launch");
+      bool decided = false;
+      GLC_HIP(ctx, glc::launch_encode_screened(ctx->dev, ctx->screen_shape, view, f, M, coef, ctx->screen_ws[slot].p,
+                                               static_cast<uint32_t *>(ctx->screen_stat.p) + 8 * slot, ++ctx->screen_seq[slot],
+                                               r, st, &decided));
+      if (!decided) GLC_HIP(ctx, glc::launch_decide_raw(ctx->dev, view, f, static_cast<uint32_t>(nf), r, st));
+      ctx->rows_screened += M;
+      continue;
+    }
     GLC_HIP(ctx, glc::launch_mdct_forward(ctx->dev, view, f, M, coef, st, ctx->k1_variant, beside));
     GLC_HIP(ctx, launch_quantize_decide(ctx, coef, view, f, nf, r, st));
   }
@@ -3093,6 +3185,29 @@ int glc_debug_set_imdct_variant(glc_ctx *ctx, int variant) {
 int glc_debug_set_mdct_variant(glc_ctx *ctx, int variant) {
   if (!ctx || variant < 0 || variant > 4) return fail(ctx, GLC_EINVAL, "glc_debug_set_mdct_variant: variant must be 0..4");
   ctx->k1_variant = variant;
+  return GLC_OK;
+}
+
+int glc_debug_set_encode_screen(glc_ctx *ctx, int mode) {
+  if (!ctx || mode < 0 || mode > 2) return fail(ctx, GLC_EINVAL, "glc_debug_set_encode_screen: mode must be 0..2");
+  ctx->screen_mode = mode;
+  ctx->screen_backoff = 0;
+  ctx->screen_held = false;
+  ctx->screen_judged_any = false;
+  return GLC_OK;
+}
+
+int glc_debug_encode_screen_stats(glc_ctx *ctx, uint64_t *rows_screened, uint64_t *rows_repaired) {
+  if (!ctx || !rows_screened || !rows_repaired) return fail(ctx, GLC_EINVAL, "glc_debug_encode_screen_stats: null argument");
+  DeviceGuard guard(ctx->device);
+  GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (ctx->stream_b) GLC_HIP(ctx, hipStreamSynchronize(ctx->stream_b));
+  *rows_screened = ctx->rows_screened;
+  *rows_repaired = 0;
+  if (ctx->screen_stat.p) {
+    const volatile uint64_t *hs = static_cast<const volatile uint64_t *>(ctx->screen_stat.p);
+    *rows_repaired = hs[2] + hs[4 + 2];
+  }
   return GLC_OK;
 }
 

@@ -37,6 +37,23 @@ hipError_t launch_mdct_forward(const DeviceTables &t, const PcmView &pcm, uint64
 // frames (*decided = true: do not launch K3); `pcm` / `frame_begin` are what that needs.
 hipError_t launch_quantize(const DeviceTables &t, const float *coef, uint32_t M, uint32_t ch, const PcmView &pcm,
                            uint64_t frame_begin, uint8_t *records, hipStream_t s, bool *decided);
+// K1 + K2 of a launch whose records, row by row, provably do not depend on the last band (the screen, DESIGN
+// section 2): the mixed-role transform (exact below C0, a fused-multiply-add bound above), the quantiser on the
+// rows that pass, then the repair - exact columns C0.. and today's quantiser for the rows that failed.  Same
+// record bytes as launch_mdct_forward + launch_quantize for every input; *decided as launch_quantize.
+struct ScreenShape {
+  uint32_t l0, c0, ne, n_oct;  // start of the last band, l0 rounded up to 64, c0 / 64, octets of columns >= c0
+};
+bool encode_screen_shape(const uint32_t *edges, uint32_t n_bands, ScreenShape *sh);  // false: c0 / 64 outside 1..15
+// true where launch_mdct_forward gives the launch to the 16-wave k_mdct_fwd_st, the form the mixed-role kernel has
+bool mdct_forward_is_st16(uint32_t M, uint32_t ch, int variant);
+bool mdct_forward_has_segment_loader(uint32_t ch);
+uint64_t encode_screen_bytes(uint32_t M, const ScreenShape &sh);
+// workspace: encode_screen_bytes(M) bytes, 16-byte aligned, nothing in it needs initialising.  host_stat: 8
+// device-visible host words {failed rows, rows, seq, -, u64 failed rows so far, ...} the last launch writes.
+hipError_t launch_encode_screened(const DeviceTables &t, const ScreenShape &sh, const PcmView &pcm, uint64_t frame_begin,
+                                  uint32_t M, float *coef, void *workspace, uint32_t *host_stat, uint32_t seq,
+                                  uint8_t *records, hipStream_t s, bool *decided);
 // K3: per-frame raw-vs-compressed decision and raw fallback plane (channel counts K2 does not decide).
 hipError_t launch_decide_raw(const DeviceTables &t, const PcmView &pcm, uint64_t frame_begin,
                              uint32_t n_frames, uint8_t *records, hipStream_t s);

@@ -5,7 +5,9 @@
 // multiply and f32 add per term (rustc never fuses).  Every kernel below keeps that order and
 // never lets the compiler contract a*b+c: the file is compiled with -ffp-contract=off and the
 // accumulation is additionally written with __fmul_rn/__fadd_rn.  No v_fma/v_fmac/v_pk_fma may
-// appear in the MDCT kernels (checked at build time by tools/check_isa.py).
+// appear in the MDCT kernels (checked at build time by tools/check_isa.py) - with one exception that
+// never produces a value of the stream: the bound waves of k_mdct_mix_st accumulate an UPPER BOUND of
+// last-band magnitudes with v_pk_fma_f32 (the screen, above k_quantize).
 //
 // Reference loops replaced (file:line into /root/reference):
 //   K1 k_mdct_fwd      src/codec.rs:476-481 (window) + :359-374 (mdct_block)
@@ -66,15 +68,73 @@ __device__ __forceinline__ short sat_i16(float x) {
 // ------------------------------------------------------------------------------------------
 constexpr int kQRows = 4;  // rows per wave
 
-template <bool FUSED>
-__global__ __launch_bounds__(256) void k_quantize(DeviceTables tb, const float *__restrict__ coef,
-                                                   unsigned M, unsigned ch, unsigned long long rec_bytes,
-                                                   unsigned long long hdr_bytes, PcmView pcm, long long frame_begin,
-                                                   unsigned char *__restrict__ records) {
+// The screen.  With L = edges[n_bands - 1] the start of the last band and C0 = L rounded up to
+// 64, the mixed-role K1 leaves exact coefficients only below C0; of a column k >= C0 it leaves e_k, the same sum
+// with fused multiply-adds, as max |e| per octet of columns, and A = sum_i |fl(x_i w_i)|.  The stream's value is
+// c_k = fl(s_k norm) with s_k the ascending f32 sum of the rounded products.  Both s_k and e_k differ from the
+// real sum of xw_i T_ki by at most gamma_2048 sum_i |xw_i| |T_ki| (2048 roundings each at most: product and add
+// per term there, one fused rounding per term here; gamma_n = n u / (1 - n u), u = 2^-24), and |T| <= 1, so
+//     |c_k| <= (max_octets |e| + 2 gamma_2048 A) norm (1 + u),          2 gamma_2048 = 2.4417e-4 < kScreenCErr.
+// kScreenSlack covers that (1 + u), the roundings of the bound's own five operations and those of the 2048 adds
+// behind A (relative gamma_2048 = 1.3e-4, on a term that only adds); kScreenTiny the products that underflow
+// (4096 operations, each off by less than 2^-126 even where subnormals are flushed: < 5e-35).
+// A row PASSES iff (a) no exact bin in [L, C0) exceeds nfl = noise_floor * scale and (b) B <= nfl, B finite, with
+// scale taken over [0, C0) alone.  Then every |c_k|, k >= L, is <= nfl < scale: the scale IS the row's (or both are
+// the 1e-10 floor), every bin of the last band quantises to 0 whatever its threshold, and the band's ordered
+// energy sum is never needed.  A NaN or an infinity anywhere in the row's samples makes A, hence B, non-finite:
+// the row fails.  A row that fails is left to the repair (exact columns C0.., then this kernel's MODE 2).
+constexpr float kScreenCErr = 2.45e-4f, kScreenSlack = 1.001f, kScreenTiny = 1e-33f;
+
+struct ScreenArgs {
+  const float *hf;        // [n_oct + 1][stride]: per octet of columns >= C0 max |e|, then A
+  unsigned *row_flag;     // [M] 1 = the row's frame failed the screen (MODE 1 writes every entry, MODE 2 reads)
+  unsigned *wave_fail;    // [waves of the MODE 1 launch] failed rows of each wave (every entry written)
+  unsigned *host_stat;    // host-mapped {failed rows, rows, seq, -, u64 failed rows so far}: MODE 2 leaves the count
+  unsigned long long stride;
+  unsigned c0, l0, n_oct, seq;
+};
+
+// MODE 0: every row of the launch from exact coefficients.  1: the screened form - rows that pass, from the
+// columns below C0; rows that fail are flagged and left alone.  2: the repair - MODE 0 on the flagged rows only.
+template <bool FUSED, int MODE>
+__device__ __forceinline__ void quantize_body(const DeviceTables &tb, const float *__restrict__ coef, unsigned M,
+                                              unsigned ch, unsigned long long rec_bytes, unsigned long long hdr_bytes,
+                                              const PcmView &pcm, long long frame_begin,
+                                              unsigned char *__restrict__ records, const ScreenArgs &sa) {
   __shared__ __attribute__((aligned(16))) float ssq[4][kQRows][kHopI];  // 64 KiB
   __shared__ float sbase[4][kQRows][64];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const unsigned m0 = (blockIdx.x * 4 + w) * kQRows;
+  unsigned on = 0;  // MODE 1 / 2: bit r = row m0 + r is this launch's to write
+  if constexpr (MODE == 2) {
+    if (blockIdx.x == 0 && w == 0) {  // the count of the screened launch, for the host's guard and statistics
+      const unsigned n_w = (M + 15) / 16 * 4;
+      unsigned cnt = 0;
+      for (unsigned i = lane; i < n_w; i += 64) cnt += sa.wave_fail[i];
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
+      if (lane == 0) {
+        // plain stores, in no order the host can rely on: it reads them unsynchronised, for a heuristic (the guard,
+        // glc_api.hip screen_takes); the statistics call reads them after the stream has been waited for
+        volatile unsigned *hs = sa.host_stat;
+        volatile unsigned long long *tot = reinterpret_cast<volatile unsigned long long *>(sa.host_stat + 4);
+        *tot = *tot + cnt;
+        hs[0] = cnt;
+        hs[1] = M;
+        hs[2] = sa.seq;
+      }
+    }
+    // every wave reads the 16 flags of the workgroup's rows: the whole workgroup leaves, or none of it
+    const unsigned fr = blockIdx.x * 16 + lane;
+    const bool flagged = lane < 16 && fr < M && sa.row_flag[fr] != 0u;
+    const unsigned blk_on = static_cast<unsigned>(__ballot(flagged));
+    if (blk_on == 0u) return;
+    on = (blk_on >> (4 * w)) & 0xFu;
+  }
+  auto row_on = [&](int r) -> bool {
+    if constexpr (MODE == 0) return m0 + r < M;
+    else return (on >> r) & 1u;
+  };
 
   // per-lane constants of the 16 bins this lane owns (the same bins in every row)
   float4 indiv4[4];
@@ -93,10 +153,16 @@ __global__ __launch_bounds__(256) void k_quantize(DeviceTables tb, const float *
   for (int r = 0; r < kQRows; ++r) {
     const unsigned m = m0 + r;
     float amax = 0.0f;
-    if (m < M) {
+    if (MODE == 1 ? m < M : row_on(r)) {
       const float4 *src = reinterpret_cast<const float4 *>(coef + static_cast<size_t>(m) * kHopI);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
+        if constexpr (MODE == 1) {  // columns >= C0 (a multiple of 64) were not computed: they count as 0
+          if ((lane + 64 * j) * 4 >= static_cast<int>(sa.c0)) {
+            c4[r][j] = float4{0.f, 0.f, 0.f, 0.f};
+            continue;
+          }
+        }
         const float4 v = src[lane + 64 * j];
         c4[r][j] = v;
         amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
@@ -112,13 +178,67 @@ __global__ __launch_bounds__(256) void k_quantize(DeviceTables tb, const float *
     for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
     scale[r] = fmaxf(amax, 1e-10f);  // :488 (and global_max at :198, :278)
   }
+  if constexpr (MODE == 1) {
+    // the screen: rows m0 .. m0 + 3 are one float4 of every hf plane
+    float hfm[4] = {0.f, 0.f, 0.f, 0.f};
+    for (unsigned o = lane; o < sa.n_oct; o += 64) {
+      const float4 h = *reinterpret_cast<const float4 *>(sa.hf + o * sa.stride + m0);
+      hfm[0] = fmaxf(hfm[0], h.x); hfm[1] = fmaxf(hfm[1], h.y); hfm[2] = fmaxf(hfm[2], h.z); hfm[3] = fmaxf(hfm[3], h.w);
+    }
+    const float4 a4 = *reinterpret_cast<const float4 *>(sa.hf + sa.n_oct * sa.stride + m0);
+    const float asum[4] = {a4.x, a4.y, a4.z, a4.w};
+    unsigned fail = 0;
+#pragma unroll
+    for (int r = 0; r < kQRows; ++r) {
+      float h = hfm[r];
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) h = fmaxf(h, __shfl_xor(h, off));
+      const float nfl = mul_rn(tb.noise_floor, scale[r]);
+      bool hit = false;  // (a) an exact bin of the last band above the floor
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float cv[4] = {c4[r][j].x, c4[r][j].y, c4[r][j].z, c4[r][j].w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const unsigned k = (lane + 64 * j) * 4 + e;
+          hit = hit || (k >= sa.l0 && k < sa.c0 && fabsf(cv[e]) > nfl);
+        }
+      }
+      const float bound = add_rn(mul_rn(mul_rn(add_rn(h, mul_rn(kScreenCErr, asum[r])), tb.norm), kScreenSlack), kScreenTiny);
+      const bool pass = __ballot(hit) == 0ull && bound <= nfl && bound < __builtin_inff();  // a NaN bound fails
+      if (!pass) fail |= 1u << r;
+    }
+    unsigned valid = 0;
+#pragma unroll
+    for (int r = 0; r < kQRows; ++r)
+      if (m0 + r < M) valid |= 1u << r;
+    fail &= valid;
+    if (FUSED) {  // a frame's rows are consecutive rows of this wave: one failing row fails its frame
+      unsigned ff = 0;
+#pragma unroll
+      for (int r = 0; r < kQRows; ++r)
+#pragma unroll
+        for (int q = 0; q < kQRows; ++q)
+          if (static_cast<unsigned>(q) / ch == static_cast<unsigned>(r) / ch && ((fail >> q) & 1u)) ff |= 1u << r;
+      fail = ff & valid;
+    }
+    on = valid & ~fail;
+    if (lane < kQRows && m0 + lane < M) sa.row_flag[m0 + lane] = (fail >> lane) & 1u;
+    if (lane == 0) sa.wave_fail[blockIdx.x * 4 + w] = __builtin_popcount(fail);
+  }
   __syncthreads();
 
   {
     const int r = lane >> 4;
-    if (m0 + r < M) {
+    if (row_on(r)) {
       const float *sq = ssq[w][r];
       for (unsigned b = lane & 15; b < tb.n_bands; b += 16) {
+        if constexpr (MODE == 1) {
+          if (b == tb.n_bands - 1) {  // every bin of the last band is known to quantise to 0
+            sbase[w][r][b] = 0.0f;
+            continue;
+          }
+        }
         const unsigned lo = tb.edges[b], hi = tb.edges[b + 1];
         float ss = 0.0f;
         unsigned i = lo;
@@ -160,7 +280,10 @@ __global__ __launch_bounds__(256) void k_quantize(DeviceTables tb, const float *
   for (int r = 0; r < kQRows; ++r) {
     const unsigned m = m0 + r;
     nnz[r] = 0;
-    if (m >= M) break;
+    if (!row_on(r)) {
+      if constexpr (MODE == 0) break;
+      else continue;
+    }
     const float sc = scale[r];
     const float nfl = mul_rn(tb.noise_floor, sc);  // :277
     const float peak_gate = mul_rn(sc, 0.3f);      // global_max * 0.3, :232
@@ -212,7 +335,10 @@ __global__ __launch_bounds__(256) void k_quantize(DeviceTables tb, const float *
 #pragma unroll
   for (int r = 0; r < kQRows; ++r) {
     const unsigned m = m0 + r;
-    if (m >= M) break;
+    if (!row_on(r)) {
+      if constexpr (MODE == 0) break;
+      else continue;
+    }
     const unsigned frame = m / ch, c = m % ch;
     unsigned char *rec = records + static_cast<size_t>(frame) * rec_bytes;
     bool use_raw = false;
@@ -241,6 +367,22 @@ __global__ __launch_bounds__(256) void k_quantize(DeviceTables tb, const float *
       }
     }
   }
+}
+
+template <bool FUSED>
+__global__ __launch_bounds__(256) void k_quantize(DeviceTables tb, const float *__restrict__ coef,
+                                                   unsigned M, unsigned ch, unsigned long long rec_bytes,
+                                                   unsigned long long hdr_bytes, PcmView pcm, long long frame_begin,
+                                                   unsigned char *__restrict__ records) {
+  quantize_body<FUSED, 0>(tb, coef, M, ch, rec_bytes, hdr_bytes, pcm, frame_begin, records, ScreenArgs{});
+}
+
+template <bool FUSED, int MODE>
+__global__ __launch_bounds__(256) void k_quantize_screen(DeviceTables tb, const float *__restrict__ coef,
+                                                          unsigned M, unsigned ch, unsigned long long rec_bytes,
+                                                          unsigned long long hdr_bytes, PcmView pcm, long long frame_begin,
+                                                          unsigned char *__restrict__ records, ScreenArgs sa) {
+  quantize_body<FUSED, MODE>(tb, coef, M, ch, rec_bytes, hdr_bytes, pcm, frame_begin, records, sa);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1730,6 +1872,8 @@ hipError_t launch_clock_probe(uint64_t ticks_100mhz, uint64_t *out, hipStream_t 
 // The 16-wave form is 2 % faster on full rounds (its staging and barrier cost nothing: k1_tune [abl]) and
 // worse on a last round that is half empty - so it takes the launches whose last round of 32 row tiles is
 // full or more than half full, the 8-wave form the rest (profiles/r03_k1_tune_st_*.txt).
+bool mdct_forward_has_segment_loader(uint32_t ch) { return ch == 1 || ch == 2 || ch == 4 || ch == 8; }
+
 namespace {
 template <int NW>
 hipError_t launch_st_ch(const DeviceTables &t, const PcmView &pcm, uint64_t frame_begin, uint32_t M, float *coef,
@@ -1772,7 +1916,7 @@ hipError_t launch_mdct_forward(const DeviceTables &t, const PcmView &pcm, uint64
   // the channel count has a segment loader; with one dword per (row, sample) only at 4096.  (Rounds 1-3 used a
   // 64 x 128 kernel for 1793..4095 rows: 0.22 ms at 2048 rows, 0.34 at 3072 - slower than both neighbours when
   // a launch has the chip to itself; it keeps one job, below.)
-  const bool seg = pcm.ch == 1 || pcm.ch == 2 || pcm.ch == 4 || pcm.ch == 8;
+  const bool seg = mdct_forward_has_segment_loader(pcm.ch);
   if (M <= 640) return k1::launch_small<2>(t, pcm, frame_begin, M, coef, s);
   // beside: an opening round of glc_encode (2048 rows), which runs beside its neighbours' kernels on a second
   // stream.  Alone the 2 x 4 kernel is faster there (0.198 against 0.221 ms), but its 1024 workgroups fill every
@@ -1784,9 +1928,71 @@ hipError_t launch_mdct_forward(const DeviceTables &t, const PcmView &pcm, uint64
   if (variant == 1) return launch_dma_ch(t, pcm, frame_begin, M, coef, s);
   if (variant == 2) return launch_st_ch<8>(t, pcm, frame_begin, M, coef, s);
   if (variant == 3) return launch_st_ch<16>(t, pcm, frame_begin, M, coef, s);
-  const unsigned last_round = ((M + 255) / 256) % 32;  // row tiles in the last round of 32
-  if (last_round == 0 || last_round > 16) return launch_st_ch<16>(t, pcm, frame_begin, M, coef, s);
+  if (mdct_forward_is_st16(M, pcm.ch, variant)) return launch_st_ch<16>(t, pcm, frame_begin, M, coef, s);
   return launch_st_ch<8>(t, pcm, frame_begin, M, coef, s);
+}
+
+bool mdct_forward_is_st16(uint32_t M, uint32_t ch, int variant) {
+  if (M < (mdct_forward_has_segment_loader(ch) ? 3584u : 4096u) || variant == 1 || variant == 2) return false;
+  if (variant == 3) return true;
+  const unsigned last_round = ((M + 255) / 256) % 32;  // row tiles in the last round of 32
+  return last_round == 0 || last_round > 16;
+}
+
+bool encode_screen_shape(const uint32_t *edges, uint32_t n_bands, ScreenShape *sh) {
+  if (!edges || n_bands == 0 || n_bands > 64) return false;
+  sh->l0 = edges[n_bands - 1];
+  sh->c0 = (sh->l0 + 63u) / 64u * 64u;
+  sh->ne = sh->c0 / 64u;
+  if (sh->ne < 1 || sh->ne > 15) return false;
+  sh->n_oct = 8u * (16u - sh->ne);
+  return true;
+}
+
+namespace {
+inline uint64_t screen_stride(uint32_t M) { return (static_cast<uint64_t>(M) + 255ull) / 256ull * 256ull; }
+}  // namespace
+
+uint64_t encode_screen_bytes(uint32_t M, const ScreenShape &sh) {
+  // hf planes | row flags | failed rows per quantiser wave (a quarter of a plane is more than it needs)
+  return ((sh.n_oct + 1ull) * screen_stride(M) + screen_stride(M) + screen_stride(M) / 4) * 4ull;
+}
+
+hipError_t launch_encode_screened(const DeviceTables &t, const ScreenShape &sh, const PcmView &pcm, uint64_t frame_begin,
+                                  uint32_t M, float *coef, void *workspace, uint32_t *host_stat, uint32_t seq,
+                                  uint8_t *records, hipStream_t s, bool *decided) {
+  *decided = pcm.ch == 1 || pcm.ch == 2 || pcm.ch == 4;
+  if (M == 0) return hipSuccess;
+  const uint64_t stride = screen_stride(M);
+  float *hf = static_cast<float *>(workspace);
+  unsigned *row_flag = reinterpret_cast<unsigned *>(hf + (sh.n_oct + 1ull) * stride);
+  unsigned *wave_fail = row_flag + stride;
+  hipError_t e;
+  switch (pcm.ch) {
+    case 1: e = k1::launch_mix_st<1>(t, pcm, frame_begin, M, coef, sh.ne, hf, stride, s); break;
+    case 2: e = k1::launch_mix_st<2>(t, pcm, frame_begin, M, coef, sh.ne, hf, stride, s); break;
+    case 4: e = k1::launch_mix_st<4>(t, pcm, frame_begin, M, coef, sh.ne, hf, stride, s); break;
+    case 8: e = k1::launch_mix_st<8>(t, pcm, frame_begin, M, coef, sh.ne, hf, stride, s); break;
+    default: e = k1::launch_mix_st<0>(t, pcm, frame_begin, M, coef, sh.ne, hf, stride, s); break;
+  }
+  if (e != hipSuccess) return e;
+  const ScreenArgs sa{hf, row_flag, wave_fail, host_stat, stride, sh.c0, sh.l0, sh.n_oct, seq};
+  const unsigned long long hdr = record_header_bytes(pcm.ch), rec = record_bytes(pcm.ch);
+  const dim3 grid((M + 4 * kQRows - 1) / (4 * kQRows));
+  const long long fb = static_cast<long long>(frame_begin);
+  if (*decided)
+    hipLaunchKernelGGL((k_quantize_screen<true, 1>), grid, dim3(256), 0, s, t, coef, M, pcm.ch, rec, hdr, pcm, fb, records, sa);
+  else
+    hipLaunchKernelGGL((k_quantize_screen<false, 1>), grid, dim3(256), 0, s, t, coef, M, pcm.ch, rec, hdr, pcm, fb, records, sa);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  // the repair: exact columns C0.. of the row tiles that hold a failed row, then those rows' records from all
+  // 1024 exact coefficients.  Both launches leave at once where nothing failed.
+  if ((e = k1::launch_small_cols<2>(t, pcm, frame_begin, M, coef, row_flag, sh.c0, s)) != hipSuccess) return e;
+  if (*decided)
+    hipLaunchKernelGGL((k_quantize_screen<true, 2>), grid, dim3(256), 0, s, t, coef, M, pcm.ch, rec, hdr, pcm, fb, records, sa);
+  else
+    hipLaunchKernelGGL((k_quantize_screen<false, 2>), grid, dim3(256), 0, s, t, coef, M, pcm.ch, rec, hdr, pcm, fb, records, sa);
+  return hipGetLastError();
 }
 
 hipError_t launch_quantize(const DeviceTables &t, const float *coef, uint32_t M, uint32_t ch, const PcmView &pcm,

@@ -18,6 +18,11 @@
 //                      256x64 / 512 (two per CU, priority by quarter of the i loop), chosen per launch by
 //                      the fill of its last round of tiles; PCM tile by dwordx4 segments when the stream has
 //                      1 / 2 / 4 / 8 channels (CH), one dword per (row, sample) otherwise (CH = 0).
+//   k_mdct_mix_st      the 16-wave k_mdct_fwd_st in mixed-role form, for glc_encode_range_device without a coefficient
+//                      tap: exact waves on the columns below the last band, bound waves (one v_pk_fma_f32 per packed
+//                      multiply-add, no coefficients stored) on the rest - the screen of DESIGN section 2.  With
+//                      k_mdct_fwd_small_cols, the 2 x 2 short-clip kernel over a column range and only the row tiles
+//                      that hold a flagged row: the exact columns of the rows that failed the screen.
 //   k_mdct_fwd_dma     the kernel of rounds 2 / 3 for the same launches, now behind
 //                      glc_debug_set_mdct_variant(ctx, 1): 128x128 tile, 512 threads, 4x8 outputs per lane
 //                      with lanes <-> columns, both operands from LDS (table tile by LDS-DMA two stages
@@ -880,16 +885,71 @@ __device__ __forceinline__ void st_mac(f32x2 (&acc)[4][4], const StOps<D> &o) {
   }
 }
 
+// Bound waves of the mixed-role kernel (k_mdct_mix_st): the same operands, ONE v_pk_fma_f32 per packed
+// multiply-add.  What they accumulate is not a coefficient of the stream - it only feeds the upper bound of
+// the screen - so neither the fused rounding nor the order matters.
+__device__ __forceinline__ void mac2rows_fma(f32x2 (&c0)[4], f32x2 (&c1)[4], f32x2 a, u32x2 b0, u32x2 b1, u32x2 b2,
+                                             u32x2 b3) {
+  asm volatile(
+      "v_pk_fma_f32 %0, %8, %9, %0 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %1, %8, %10, %1 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %2, %8, %11, %2 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %3, %8, %12, %3 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %4, %8, %9, %4 op_sel:[1,0,0]\n\t"
+      "v_pk_fma_f32 %5, %8, %10, %5 op_sel:[1,0,0]\n\t"
+      "v_pk_fma_f32 %6, %8, %11, %6 op_sel:[1,0,0]\n\t"
+      "v_pk_fma_f32 %7, %8, %12, %7 op_sel:[1,0,0]"
+      : "+v"(c0[0]), "+v"(c0[1]), "+v"(c0[2]), "+v"(c0[3]), "+v"(c1[0]), "+v"(c1[1]), "+v"(c1[2]), "+v"(c1[3])
+      : "v"(a), "s"(b0), "s"(b1), "s"(b2), "s"(b3));
+}
+
+// ROLE of a wave: 0 = exact (st_mac: the stream's arithmetic), 1 = bound (fused), 2 = bound, and the wave
+// also sums |x w| of its lanes' 4 rows over the whole i loop (asum: the A of the screen's error term)
+template <int ROLE, int D>
+__device__ __forceinline__ void st_mac_role(f32x2 (&acc)[4][4], float (&asum)[4], const StOps<D> &o) {
+  if constexpr (ROLE == 0) {
+    st_mac(acc, o);
+  } else {
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      mac2rows_fma(acc[0], acc[1], o.a[d].xy, o.b[d].s01, o.b[d].s23, o.b[d].s45, o.b[d].s67);
+      mac2rows_fma(acc[2], acc[3], o.a[d].zw, o.b[d].s01, o.b[d].s23, o.b[d].s45, o.b[d].s67);
+      if constexpr (ROLE == 2) {
+        asum[0] = add_rn(asum[0], __builtin_fabsf(o.a[d].x));
+        asum[1] = add_rn(asum[1], __builtin_fabsf(o.a[d].y));
+        asum[2] = add_rn(asum[2], __builtin_fabsf(o.a[d].z));
+        asum[3] = add_rn(asum[3], __builtin_fabsf(o.a[d].w));
+      }
+    }
+  }
+}
+template <int V>
+struct RoleTag {
+  static constexpr int value = V;
+};
+
 // NW waves per workgroup (8: 256 x 64 tile, two workgroups per CU;  16: 256 x 128, one), BK i-steps per
 // LDS stage, D i-steps per operand fetch.
 // PRIO 1: priority by quarter of the i loop (between the two workgroups of a CU, as k_mdct_fwd_dma);
 // PRIO 2: by distance from the last barrier (inside a workgroup: whoever is behind goes first).
 // ABL (tuning only, wrong results): 1 = the table address does not advance, 2 = no staging and no barrier.
 // STAMP (tuning only): workgroup timeline into `stamps` - entry, loop start, the quarter points, loop end, stores drained.
-template <int MINW, int CH = 0, int PRIO = 0, int D = 2, int NW = 8, int BK = 16, int ABL = 0, bool STAMP = false>
-__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MINW, MINW)))
-void k_mdct_fwd_st(DeviceTables tb, PcmView pcm, long long frame_begin, unsigned M, float *__restrict__ coef,
-                   unsigned long long *__restrict__ stamps) {
+//
+// MIX (k_mdct_mix_st, 16 waves): the mixed-role form for launches whose records can only depend on the columns
+// below C0 = 64 ne when a row passes the screen.  Tile, staging, ring and barriers are the
+// same; what changes is which columns a wave owns and what it does with them.  Waves [0, ne) are EXACT: workgroup
+// n_tile = j owns columns [8 ne j, 8 ne (j + 1)), its exact waves run st_mac and store coefficients.  Waves
+// [ne, 16) are BOUND waves on columns C0 + 8 (16 - ne) j ...: fused multiply-adds (half the issue slots), no
+// coefficients; per row the largest |sum| of the wave's 8 columns goes to hf[octet][row] (octet = (16 - ne) j +
+// wave - ne; plain coalesced stores, every slot of the launch is written), and wave ne of workgroup j = 0 - the sum
+// does not depend on the columns - adds the row's sum of |x w| at hf[8 (16 - ne)][row].  Waves sit on SIMD wave % 4, so `wave < ne` spreads the exact ones as evenly
+// as ne allows (2, 2, 1, 1 for ne = 6) and wave ne, which has 4 more adds per i-step, never joins a fullest SIMD.
+// The role branch is wave-uniform and outside the i loop; every role runs the same barriers.
+template <int CH, int PRIO, int D, int NW, int BK, int ABL, bool STAMP, bool MIX>
+__device__ __forceinline__ void st_body(const DeviceTables &tb, const PcmView &pcm, long long frame_begin, unsigned M,
+                                        float *__restrict__ coef, unsigned long long *__restrict__ stamps, unsigned ne,
+                                        float *__restrict__ hf, unsigned long long hf_stride) {
+  static_assert(!MIX || NW == 16, "the mixed-role form is the 16-wave one");
   if constexpr (STAMP) {
     if (threadIdx.x == 0) stamps[static_cast<size_t>(blockIdx.x) * 8] = __builtin_amdgcn_s_memrealtime();
   }
@@ -1035,23 +1095,40 @@ void k_mdct_fwd_st(DeviceTables tb, PcmView pcm, long long frame_begin, unsigned
     for (int c = 0; c < 4; ++c) acc[r][c] = f32x2{0.0f, 0.0f};
 
   constexpr int kStages = kFrameI / BK;
-  // prologue: stage 0 complete in slot 0, PCM of stage 1 in registers
+  // prologue: stage 0 complete in slot 0 (the PCM of stage 1 is fetched where the i loop starts)
   __syncthreads();  // Ws
   issue_a(0);
   wait_staged();
   store_a(0, 0);
-  issue_a(BK);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
 
   const unsigned a_lds0 = static_cast<unsigned>(reinterpret_cast<uintptr_t>(&As[0][lane * 4]));
   // this wave's 8 columns of table row 0 (wave-uniform: the scalar loads' base)
-  const unsigned *b_base = reinterpret_cast<const unsigned *>(tb.cos_t) + n0 + 8 * wave;
+  int col0 = n0 + 8 * wave, role = 0;
+  if constexpr (MIX) {
+    const int nb = 16 - static_cast<int>(ne);  // bound waves per workgroup
+    if (wave < static_cast<int>(ne)) {
+      col0 = 8 * static_cast<int>(ne) * n_tile + 8 * wave;
+    } else {
+      col0 = 64 * static_cast<int>(ne) + 8 * nb * n_tile + 8 * (wave - static_cast<int>(ne));
+      role = wave == static_cast<int>(ne) && n_tile == 0 ? 2 : 1;  // A does not depend on the columns: one workgroup of a row tile forms it
+    }
+  }
+  const unsigned *b_base = reinterpret_cast<const unsigned *>(tb.cos_t) + col0;
 
   // Stage hand-off in the middle of a stage, as in k_mdct_fwd_dma: the samples of stage s+1 are
   // published by a barrier after the first BK / 2 i-steps, the stage's last fetch takes the first operands
   // of stage s+1, and the PCM loads of stage s+2 are issued behind the barrier.  Slot use: stage s reads
   // slot s % 3; As[(s+1) % 3] is written before the barrier of stage s (last read in stage s-2).
+  float asum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  // The i loop, once per role of the mixed form (one of them runs).  Every load an asm statement issues and a
+  // LATER one waits for - PCM registers, operands - is issued and retired INSIDE it: the compiler does not know such
+  // a load is in flight, and where the roles branch or join it may copy the destination registers, or reuse them,
+  // before the data has landed.
+  auto i_loop = [&](auto role_tag) {
+  constexpr int ROLE = decltype(role_tag)::value;
+  issue_a(BK);  // PCM of stage 1 into registers
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __syncthreads();
   StOps<D> X, Y;
   st_fetch<0, kAS>(X, a_lds0, b_base);
   st_wait(X);
@@ -1096,7 +1173,7 @@ void k_mdct_fwd_st(DeviceTables tb, PcmView pcm, long long frame_begin, unsigned
   do {                                                                                    \
     if constexpr ((II) + D < BK) st_fetch<((II) + D) % BK, kAS>(NXT, a_addr, brow);        \
     else st_fetch<0, kAS>(NXT, a_next, brow_next);                                        \
-    st_mac(acc, CUR);                                                                     \
+    st_mac_role<ROLE>(acc, asum, CUR);                                                    \
     if constexpr ((II) + D == BK / 2 && !(ABL & 2)) GLC_ST_HANDOFF(NXT);                  \
     else st_wait(NXT);                                                                    \
   } while (0)
@@ -1126,15 +1203,46 @@ void k_mdct_fwd_st(DeviceTables tb, PcmView pcm, long long frame_begin, unsigned
 #undef GLC_ST_HANDOFF
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the wrap-around prefetch
+  };  // i_loop
+  if constexpr (MIX) {
+    if (role == 0) i_loop(RoleTag<0>{});
+    else if (role == 1) i_loop(RoleTag<1>{});
+    else i_loop(RoleTag<2>{});
+  } else {
+    i_loop(RoleTag<0>{});
+  }
   if constexpr (STAMP) {
     if (tid == 0) stamps[static_cast<size_t>(blockIdx.x) * 8 + 5] = __builtin_amdgcn_s_memrealtime();
   }
 
+  if constexpr (MIX) {
+    if (role != 0) {
+      // rows m0 + 4 lane .. + 3 of the launch's padded row range (hf_stride = rows rounded up to whole tiles:
+      // rows >= M were staged as zeros and store 0)
+      const unsigned nb = 16u - ne;
+      f32x4 mx;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float m = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) m = fmaxf(m, fmaxf(__builtin_fabsf(acc[r][c].x), __builtin_fabsf(acc[r][c].y)));
+        mx[r] = m;
+      }
+      const size_t at = static_cast<size_t>(m0) + static_cast<size_t>(lane) * 4;
+      const unsigned octet = nb * static_cast<unsigned>(n_tile) + static_cast<unsigned>(wave) - ne;
+      *reinterpret_cast<f32x4 *>(hf + octet * hf_stride + at) = mx;
+      if (role == 2) {
+        const f32x4 av = {asum[0], asum[1], asum[2], asum[3]};
+        *reinterpret_cast<f32x4 *>(hf + 8u * nb * hf_stride + at) = av;
+      }
+      return;
+    }
+  }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const unsigned row = m0 + lane * 4 + r;
     if (row >= M) continue;
-    float *dst = coef + static_cast<size_t>(row) * kHopI + n0 + 8 * wave;
+    float *dst = coef + static_cast<size_t>(row) * kHopI + col0;
     float4 o;
     o.x = mul_rn(acc[r][0].x, tb.norm); o.y = mul_rn(acc[r][0].y, tb.norm);
     o.z = mul_rn(acc[r][1].x, tb.norm); o.w = mul_rn(acc[r][1].y, tb.norm);
@@ -1147,6 +1255,33 @@ void k_mdct_fwd_st(DeviceTables tb, PcmView pcm, long long frame_begin, unsigned
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (tid == 0) stamps[static_cast<size_t>(blockIdx.x) * 8 + 6] = __builtin_amdgcn_s_memrealtime();
   }
+}
+
+template <int MINW, int CH = 0, int PRIO = 0, int D = 2, int NW = 8, int BK = 16, int ABL = 0, bool STAMP = false>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(MINW, MINW)))
+void k_mdct_fwd_st(DeviceTables tb, PcmView pcm, long long frame_begin, unsigned M, float *__restrict__ coef,
+                   unsigned long long *__restrict__ stamps) {
+  st_body<CH, PRIO, D, NW, BK, ABL, STAMP, false>(tb, pcm, frame_begin, M, coef, stamps, 0u, nullptr, 0ull);
+}
+
+// the mixed-role form (see st_body): ne exact waves, hf = [8 (16 - ne) + 1][hf_stride] floats
+template <int MINW, int CH = 0>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(MINW, MINW)))
+void k_mdct_mix_st(DeviceTables tb, PcmView pcm, long long frame_begin, unsigned M, float *__restrict__ coef,
+                   unsigned ne, float *__restrict__ hf, unsigned long long hf_stride) {
+  st_body<CH, 2, 4, 16, 16, 0, false, true>(tb, pcm, frame_begin, M, coef, nullptr, ne, hf, hf_stride);
+}
+
+template <int CH>
+inline hipError_t launch_mix_st(const DeviceTables &t, const PcmView &pcm, uint64_t frame_begin, uint32_t M, float *coef,
+                                uint32_t ne, float *hf, uint64_t hf_stride, hipStream_t s) {
+  if (M == 0) return hipSuccess;
+  if (CH != 0 && pcm.ch != static_cast<uint32_t>(CH)) return hipErrorInvalidValue;
+  if (ne < 1 || ne > 15 || hf_stride < M || hf_stride % 256) return hipErrorInvalidValue;
+  const unsigned m_tiles = (M + 255) / 256;
+  hipLaunchKernelGGL((k_mdct_mix_st<4, CH>), dim3(m_tiles * 8), dim3(1024), 0, s, t, pcm,
+                     static_cast<long long>(frame_begin), M, coef, ne, hf, static_cast<unsigned long long>(hf_stride));
+  return hipGetLastError();
 }
 
 template <int MINW, int CH = 0, int PRIO = 0, int D = 2, int NW = 8, int BK = 16, int ABL = 0, bool STAMP = false>
@@ -1274,9 +1409,14 @@ __device__ __forceinline__ void small_steps(f32x2 (&acc)[2][TN / 2], SmallOps<TN
   }
 }
 
-template <int TN>
-__global__ __launch_bounds__(256) void k_mdct_fwd_small(DeviceTables tb, PcmView pcm, long long frame_begin, unsigned M,
-                                                         float *__restrict__ coef) {
+// REPAIR (k_mdct_fwd_small_cols): only the coefficient tiles [n_tile0, n_tile0 + n_cnt) of the launch's rows, and
+// of those only the row tiles that hold a flagged row (row_flag[M], written by the screened quantiser): the exact
+// columns C0.. of the rows that failed the screen.  Every wave reads the tile's 32 flags itself, so the whole
+// workgroup leaves together, before its first barrier.
+template <int TN, bool REPAIR>
+__device__ __forceinline__ void small_body(const DeviceTables &tb, const PcmView &pcm, long long frame_begin, unsigned M,
+                                           float *__restrict__ coef, const unsigned *__restrict__ row_flag,
+                                           unsigned n_tile0, unsigned n_cnt) {
   // D: i-steps of operands in flight (an LDS read takes ~250 cycles under no load, a 2 x 2 step 16 of VALU:
   // the ring is as deep as the 4-bit lgkmcnt allows - 7 x 2 or 5 x 3 younger reads)
   constexpr int BM = 32, BN = 16 * TN, BK = GLC_SMALL_BK, D = TN == 2 ? 8 : 6;
@@ -1288,9 +1428,15 @@ __global__ __launch_bounds__(256) void k_mdct_fwd_small(DeviceTables tb, PcmView
   __shared__ __attribute__((aligned(16))) float Bs[2][BK * BN];
 
   const int tid = threadIdx.x;
-  const int n_tile = blockIdx.x % kNTiles, m_tile = blockIdx.x / kNTiles;
+  const int n_tile = REPAIR ? static_cast<int>(n_tile0 + blockIdx.x % n_cnt) : static_cast<int>(blockIdx.x % kNTiles);
+  const int m_tile = REPAIR ? static_cast<int>(blockIdx.x / n_cnt) : static_cast<int>(blockIdx.x / kNTiles);
   const int m0 = m_tile * BM, n0 = n_tile * BN;
   const int tx = tid % 16, ty = tid / 16;
+  if constexpr (REPAIR) {
+    const unsigned fr = static_cast<unsigned>(m0) + (tid & 31);
+    const bool flagged = fr < M && row_flag[fr] != 0u;
+    if (__ballot(flagged) == 0ull) return;
+  }
 
   // A operand through a buffer descriptor whose range check is the encoder's zero padding (see k_mdct_fwd)
   const long long ch = pcm.ch;
@@ -1391,6 +1537,32 @@ __global__ __launch_bounds__(256) void k_mdct_fwd_small(DeviceTables tb, PcmView
       *reinterpret_cast<float4 *>(dst) = o;
     }
   }
+}
+
+template <int TN>
+__global__ __launch_bounds__(256) void k_mdct_fwd_small(DeviceTables tb, PcmView pcm, long long frame_begin, unsigned M,
+                                                         float *__restrict__ coef) {
+  small_body<TN, false>(tb, pcm, frame_begin, M, coef, nullptr, 0u, 0u);
+}
+
+template <int TN>
+__global__ __launch_bounds__(256) void k_mdct_fwd_small_cols(DeviceTables tb, PcmView pcm, long long frame_begin, unsigned M,
+                                                              float *__restrict__ coef, const unsigned *__restrict__ row_flag,
+                                                              unsigned n_tile0, unsigned n_cnt) {
+  small_body<TN, true>(tb, pcm, frame_begin, M, coef, row_flag, n_tile0, n_cnt);
+}
+
+// columns [col0, 1024) (col0 a multiple of the tile width) of the flagged rows' tiles
+template <int TN>
+inline hipError_t launch_small_cols(const DeviceTables &t, const PcmView &pcm, uint64_t frame_begin, uint32_t M, float *coef,
+                                    const unsigned *row_flag, uint32_t col0, hipStream_t s) {
+  constexpr unsigned BN = 16 * TN;
+  if (M == 0 || col0 >= static_cast<uint32_t>(kHopI)) return hipSuccess;
+  if (col0 % BN || !row_flag) return hipErrorInvalidValue;
+  const unsigned m_tiles = (M + 31) / 32, n_cnt = (kHopI - col0) / BN;
+  hipLaunchKernelGGL((k_mdct_fwd_small_cols<TN>), dim3(m_tiles * n_cnt), dim3(256), 0, s, t, pcm,
+                     static_cast<long long>(frame_begin), M, coef, row_flag, col0 / BN, n_cnt);
+  return hipGetLastError();
 }
 
 template <int TN>

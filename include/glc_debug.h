@@ -41,6 +41,22 @@ int glc_debug_set_imdct_variant(glc_ctx *ctx, int variant);
  * All of them produce the same bits (tests/test_gpu_parity.py). */
 int glc_debug_set_mdct_variant(glc_ctx *ctx, int variant);
 
+/* Whether the encode launches of `ctx` take the screened path (exact transform only for the
+ * columns below the last band; the last band by a fused-multiply-add upper bound, and exactly - the repair - for
+ * the rows whose bound does not stay under the noise floor):
+ *   0  automatic: the launches glc_debug_set_mdct_variant's variant 0 gives to the 16-wave k_mdct_fwd_st, at rates
+ *      whose last band starts at 64..960 (rounded up to 64), unless the guard holds the path off: after a launch in
+ *      which more than one row in eight failed the screen, 32 launches take today's kernels, then one probes, and
+ *      no other is screened until the probe's count is back; a context's first screened launch counts as a probe
+ *   1  off: today's kernels for every launch
+ *   2  on for every launch of 256 rows or more, guard ignored (tests reach the path with a few hundred rows)
+ * A launch with a coefficient tap (d_coeffs) and glc_mdct_forward_device never take it.  All modes produce the
+ * same record bytes (tests/test_encode_screen.py). */
+int glc_debug_set_encode_screen(glc_ctx *ctx, int mode);
+/* Rows the screened path has transformed since the context was created, and how many of them failed the screen
+ * and were repaired.  Waits for the context's encode streams. */
+int glc_debug_encode_screen_stats(glc_ctx *ctx, uint64_t *rows_screened, uint64_t *rows_repaired);
+
 /* K2 (+ K3 where the channel count needs it) exactly as glc_encode_range_device runs them, on caller-supplied
  * coefficients: d_coeffs holds (frame_end - frame_begin) * channels rows of 1024 floats, laid out as
  * glc_mdct_forward_device writes them; d_pcm / t0 / t_count / n_samples are read only for raw planes.

@@ -5,6 +5,13 @@ reference accumulates with a separately rounded multiply and add.
   k_mdct_fwd_sched / k_mdct_fwd_dma / k_mdct_fwd_st / k_mdct_fwd_small / k_imdct_apply  strict: no fused op at all (no division or sqrt inside)
   k_imdct_rows / k_imdct_plan   fused ops allowed only inside hipcc's correctly-rounded f32 division expansion
                 (v_div_scale ... v_div_fixup), which the raw-frame path `i16 / 32767.0` needs
+  k_mdct_mix_st (the mixed-role form of k_mdct_fwd_st)   v_pk_fma_f32 alone is allowed: its bound waves
+                accumulate an upper bound with it, never a coefficient; its exact waves run k_mdct_fwd_st's own multiply /
+                add block.  The i loop exists once per role (exact, bound, bound + A), each copy BK = 16 i-steps of
+                16 packed multiply-adds (a lane's 4 rows x 8 columns / 2): every instantiation may hold at most
+                2 x 256 v_pk_fma_f32 - the two bound copies - and must hold the exact copy's 256 v_pk_mul_f32 and
+                256 v_pk_add_f32, so a fused op in the exact role shows here as well as in the bit-exact parity of
+                tests/test_encode_screen.py
 The quantiser / decision / overlap-add kernels are not scanned: their IEEE divide, sqrt and
 64-bit index division expand to FMA-based sequences by design.  The arithmetic of the quantiser and the
 raw-or-compressed decision is pinned instead by tests/test_quantizer_edges.py, which drives them with
@@ -19,18 +26,22 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gapless-lossy-codec_amd", "csrc")
 ISA = os.path.join(ROOT, "build", "isa", "glc_kernels-hip-amdgcn-amd-amdhsa-gfx950.s")
 FORBIDDEN = re.compile(r"^\s+(v_fma\w*|v_fmac\w*|v_pk_fma\w*|v_mad_\w*f32|v_mac\w*|v_dot\w*|v_mfma\w*)\b")
-KERNELS = ("k_mdct_fwd_sched", "k_mdct_fwd_dma", "k_mdct_fwd_st", "k_mdct_fwd_small", "k_imdct_rows", "k_imdct_plan", "k_imdct_apply")
+KERNELS = ("k_mdct_fwd_sched", "k_mdct_fwd_dma", "k_mdct_fwd_st", "k_mdct_mix_st", "k_mdct_fwd_small", "k_imdct_rows", "k_imdct_plan", "k_imdct_apply")
 DIV_WINDOW = {"k_imdct_rows", "k_imdct_plan"}
+BOUND_FMA = re.compile(r"^\s+v_pk_fma_f32\b")  # the one fused op of k_mdct_mix_st's bound waves
+MIX_LOOP_MACS = 16 * 16  # packed multiply-adds in one copy of k_mdct_mix_st's i loop: BK i-steps x (4 rows x 8 columns / 2)
 
 
 def main() -> int:
     subprocess.check_call(["make", "-C", CSRC, "-s", "isa"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     cur, bad, seen, in_div = None, [], set(), False
     first_ds = {}   # kernel -> True once its first ds_read has been seen
+    mix = {}        # instantiation of k_mdct_mix_st -> [v_pk_fma_f32, v_pk_mul_f32, v_pk_add_f32] counts
     for line in open(ISA):
         m = re.match(r"^(_Z\w+):", line)
         if m:
             cur = next((k for k in KERNELS if k in m.group(1)), None)
+            cur_mix = mix.setdefault(m.group(1), [0, 0, 0]) if cur == "k_mdct_mix_st" else None
             in_div = False
             first_ds = {}
             if cur:
@@ -39,7 +50,7 @@ def main() -> int:
             in_div = True
         elif cur and "v_div_fixup_f32" in line:
             in_div = False
-        elif cur and FORBIDDEN.match(line) and not in_div:
+        elif cur and FORBIDDEN.match(line) and not in_div and not (cur == "k_mdct_mix_st" and BOUND_FMA.match(line)):
             bad.append((cur, line.strip()))
         # k_mdct_fwd_small waits for its LDS operands with COUNTED lgkmcnt (LDS returns in order): a scalar
         # load in flight at the same time would make those counts meaningless (SMEM returns out of order)
@@ -48,7 +59,7 @@ def main() -> int:
                 first_ds[cur] = True
             elif first_ds.get(cur) and re.match(r"^\s+(s_load|s_buffer_load)", line):
                 bad.append((cur, "scalar load beside counted LDS waits: " + line.strip()))
-        asm_async = cur and (cur.startswith("k_mdct_fwd") or cur == "k_imdct_apply")  # loads issued and waited for in separate asm statements
+        asm_async = cur and (cur.startswith("k_mdct_") or cur == "k_imdct_apply")  # loads issued and waited for in separate asm statements
         if asm_async and re.match(r"^\s+(scratch_|buffer_store.*offen.*s\[0:3\]|buffer_load.*off.*s\[0:3\])", line):
             bad.append((cur, "register spill: " + line.strip()))
         # k_mdct_fwd_st / k_imdct_apply keep table values / records in SGPRs that an asm statement loads and a LATER
@@ -56,12 +67,20 @@ def main() -> int:
         # variant: wrong results and a memory fault), besides putting v_writelane / v_readlane into the inner loop
         if asm_async and re.match(r"^\s+(v_writelane|v_readlane)", line):
             bad.append((cur, "scalar register spill: " + line.strip()))
+        if cur == "k_mdct_mix_st":
+            pk = re.match(r"^\s+v_pk_(fma|mul|add)_f32\b", line)
+            if pk:
+                cur_mix[("fma", "mul", "add").index(pk.group(1))] += 1
         if "s_endpgm" in line:
             cur = None
     missing = set(KERNELS) - seen
     if missing:
         print("check_isa: kernels not found in ISA:", sorted(missing))
         return 1
+    for name, (n_fma, n_mul, n_add) in mix.items():
+        if n_fma > 2 * MIX_LOOP_MACS or n_mul < MIX_LOOP_MACS or n_add < MIX_LOOP_MACS:
+            bad.append(("k_mdct_mix_st", f"{name}: {n_fma} v_pk_fma_f32 (at most {2 * MIX_LOOP_MACS}: the two bound copies), "
+                                         f"{n_mul} v_pk_mul_f32 / {n_add} v_pk_add_f32 (at least {MIX_LOOP_MACS} each: the exact copy)"))
     if bad:
         for k, l in bad:
             print(f"check_isa: fused op in {k}: {l}")
