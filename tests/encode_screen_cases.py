@@ -6,6 +6,8 @@ that says, from the oracle's coefficients, which rows MUST pass, which MUST fail
 The model is not the code under test: the exact columns of the device are the oracle's bit for bit, so condition (a)
 is evaluated on the oracle's coefficients; the bound waves' fused sums e_k are only known to lie within
 2 gamma_2048 A of the oracle's unnormalised sums, which brackets B from both sides."""
+import ctypes as C
+
 import numpy as np
 
 from oracle import oracle as O
@@ -229,3 +231,66 @@ def bound_per_bin(e, A):
     with np.errstate(all="ignore"):
         _, _, norm = O.tables()
         return ((np.abs(e) + (C_ERR * A)[:, None]) * F32(norm)) * SLACK + TINY
+
+
+def assert_bound(xw, what):
+    """|c| of the oracle never exceeds the kernel's bound formed from the emulated fused sums, for the rows `xw` over
+    the columns 128..1023 (S at 192 kHz: the widest) -> the largest |c| / B seen."""
+    T, _, norm = O.tables()
+    cols = np.arange(128, 1024)
+    e = fma_sums(xw, T, cols)
+    with np.errstate(all="ignore"):
+        A = np.cumsum(np.abs(xw), axis=1, dtype=F32)[:, -1]       # ascending f32 sum, as the wave forms it
+        B = bound_per_bin(e, A)
+        c = np.stack([np.abs(O.mdct_block(r))[cols] for r in xw])
+        ok = (c <= B) | ~np.isfinite(B)                # a non-finite bound fails the row: nothing is claimed
+    assert ok.all(), f"{what}: |c| exceeds the bound at (row, k) {np.argwhere(~ok)[:4].tolist()}"
+    with np.errstate(all="ignore"):
+        return float(np.nanmax(np.where(np.isfinite(B) & (B > 0), c / B, 0.0)))
+
+
+# ---------------------------------------------------------------------------------------------------- GPU helpers
+
+def bind(glc_amd):
+    """The two debug hooks of include/glc_debug.h the screen's suites drive."""
+    f = glc_amd.lib.glc_debug_set_encode_screen
+    f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_int]
+    g = glc_amd.lib.glc_debug_encode_screen_stats
+    g.restype, g.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+
+
+def stats(glc_amd, ctx):
+    """(rows screened, rows repaired) of a context so far."""
+    a, b = C.c_uint64(), C.c_uint64()
+    assert glc_amd.lib.glc_debug_encode_screen_stats(ctx._h, C.byref(a), C.byref(b)) == 0
+    return a.value, b.value
+
+
+def records(torch, glc_amd, enc, c, mode):
+    """One glc_encode_range_device of the case with the screen in `mode` (None: as the context stands, which is the
+    automatic mode) -> (record bytes, rows screened, rows repaired)."""
+    sh, t0, tc = c.shard()
+    d_pcm = torch.from_numpy(sh.view(np.int32).copy()).cuda()     # as words: NaN payloads travel untouched
+    rb = glc_amd.lib.glc_record_bytes(c.ch) * (c.f1 - c.f0)
+    d_rec = torch.full((rb + 8192,), 0xA5, dtype=torch.uint8, device="cuda")
+    d_rec[4096:4096 + rb] = 0     # zeroed, as the oracle's are: header padding and the upper half of a compressed row are nobody's
+    torch.cuda.synchronize()
+    s0 = stats(glc_amd, enc)
+    if mode is not None:      # (setting a mode, the automatic one too, clears the guard's state: None leaves it alone)
+        assert glc_amd.lib.glc_debug_set_encode_screen(enc._h, mode) == 0
+    try:
+        enc.encode_range_device(d_pcm.data_ptr(), t0, tc, c.n_samples, c.ch, c.f0, c.f1, d_rec.data_ptr() + 4096)
+        enc.synchronize()
+    finally:
+        if mode is not None:
+            assert glc_amd.lib.glc_debug_set_encode_screen(enc._h, 0) == 0
+    s1 = stats(glc_amd, enc)
+    r = d_rec.cpu().numpy()
+    assert (r[:4096] == 0xA5).all() and (r[4096 + rb:] == 0xA5).all(), f"{c.name}: bytes around the records were written"
+    return r[4096:4096 + rb], s1[0] - s0[0], s1[1] - s0[1]
+
+
+def explain(got, exp, ch):
+    bad = np.flatnonzero(got != exp)
+    rec = O.record_bytes(ch)
+    return f"{bad.size} record bytes differ in frames {np.unique(bad // rec)[:8].tolist()}, first at byte {bad[0] % rec} of its record"

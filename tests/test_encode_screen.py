@@ -8,7 +8,6 @@ cases' design (each outcome is really reached, by a margin), and the condition o
 GPU: every case through glc_debug_set_encode_screen mode 2 (forced on) and mode 1 (off) at 256..301 rows: record
 bytes against oracle.encode_range_records and against each other, and the counts of screened / repaired rows
 against the model - so a path that is silently off, or one that repairs everything, does not pass."""
-import ctypes as C
 import os
 import sys
 
@@ -103,18 +102,7 @@ def test_above_c0_the_screen_fails_before_the_truth_crosses(cases):
     assert early < 40 and first_open <= first_truth, (early, first_open, first_truth)
 
 
-def _assert_bound(xw, what):
-    T, _, norm = O.tables()
-    cols = np.arange(128, 1024)                       # S at 192 kHz: the widest
-    e = S.fma_sums(xw, T, cols)
-    with np.errstate(all="ignore"):
-        A = np.cumsum(np.abs(xw), axis=1, dtype=F32)[:, -1]       # ascending f32 sum, as the wave forms it
-        B = S.bound_per_bin(e, A)
-        c = np.stack([np.abs(O.mdct_block(r))[cols] for r in xw])
-        ok = (c <= B) | ~np.isfinite(B)                # a non-finite bound fails the row: nothing is claimed
-    assert ok.all(), f"{what}: |c| exceeds the bound at (row, k) {np.argwhere(~ok)[:4].tolist()}"
-    with np.errstate(all="ignore"):
-        return float(np.nanmax(np.where(np.isfinite(B) & (B > 0), c / B, 0.0)))
+_assert_bound = S.assert_bound
 
 
 def test_bound_holds_for_adversarial_sign_patterns():
@@ -163,10 +151,7 @@ def gpu():
     import torch
     assert torch.cuda.is_available(), "-m gpu tests need a GPU (no CPU fallback exists)"
     import glc_amd
-    f = glc_amd.lib.glc_debug_set_encode_screen
-    f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_int]
-    g = glc_amd.lib.glc_debug_encode_screen_stats
-    g.restype, g.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    S.bind(glc_amd)
     encoders = {}
 
     def encoder(sr):
@@ -178,41 +163,12 @@ def gpu():
         e.close()
 
 
-def _stats(glc_amd, enc):
-    a, b = C.c_uint64(), C.c_uint64()
-    assert glc_amd.lib.glc_debug_encode_screen_stats(enc._h, C.byref(a), C.byref(b)) == 0
-    return a.value, b.value
+_stats, _explain = S.stats, S.explain
 
 
 def _records(gpu, enc, c, mode):
-    """One glc_encode_range_device of the case with the screen in `mode` (None: as the context stands, which is the
-    automatic mode) -> (record bytes, rows screened, rows repaired)."""
-    torch, glc_amd, _ = gpu
-    sh, t0, tc = c.shard()
-    d_pcm = torch.from_numpy(sh.view(np.int32).copy()).cuda()     # as words: NaN payloads travel untouched
-    rb = glc_amd.lib.glc_record_bytes(c.ch) * (c.f1 - c.f0)
-    d_rec = torch.full((rb + 8192,), 0xA5, dtype=torch.uint8, device="cuda")
-    d_rec[4096:4096 + rb] = 0     # zeroed, as the oracle's are: header padding and the upper half of a compressed row are nobody's
-    torch.cuda.synchronize()
-    s0 = _stats(glc_amd, enc)
-    if mode is not None:      # (setting a mode, the automatic one too, clears the guard's state: None leaves it alone)
-        assert glc_amd.lib.glc_debug_set_encode_screen(enc._h, mode) == 0
-    try:
-        enc.encode_range_device(d_pcm.data_ptr(), t0, tc, c.n_samples, c.ch, c.f0, c.f1, d_rec.data_ptr() + 4096)
-        enc.synchronize()
-    finally:
-        if mode is not None:
-            assert glc_amd.lib.glc_debug_set_encode_screen(enc._h, 0) == 0
-    s1 = _stats(glc_amd, enc)
-    r = d_rec.cpu().numpy()
-    assert (r[:4096] == 0xA5).all() and (r[4096 + rb:] == 0xA5).all(), f"{c.name}: bytes around the records were written"
-    return r[4096:4096 + rb], s1[0] - s0[0], s1[1] - s0[1]
-
-
-def _explain(got, exp, ch):
-    bad = np.flatnonzero(got != exp)
-    rec = O.record_bytes(ch)
-    return f"{bad.size} record bytes differ in frames {np.unique(bad // rec)[:8].tolist()}, first at byte {bad[0] % rec} of its record"
+    """encode_screen_cases.records on the fixture's torch and library."""
+    return S.records(gpu[0], gpu[1], enc, c, mode)
 
 
 @pytest.mark.gpu
