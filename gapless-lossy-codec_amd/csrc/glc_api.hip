@@ -1711,16 +1711,6 @@ int launch_d1(glc_ctx *ctx, uint32_t row_begin, uint32_t M, float *blocks) {
   return GLC_OK;
 }
 
-// D2 by output type: float samples, or int16_t ones narrowed as the reference's 16-bit writers do
-inline hipError_t launch_d2(const float *blocks, int64_t blk_frame0, uint64_t n_frames, uint32_t ch, uint64_t hop_begin,
-                            uint64_t hop_end, float *out, hipStream_t s) {
-  return glc::launch_overlap_add(blocks, blk_frame0, n_frames, ch, hop_begin, hop_end, out, s);
-}
-inline hipError_t launch_d2(const float *blocks, int64_t blk_frame0, uint64_t n_frames, uint32_t ch, uint64_t hop_begin,
-                            uint64_t hop_end, int16_t *out, hipStream_t s) {
-  return glc::launch_overlap_add_i16(blocks, blk_frame0, n_frames, ch, hop_begin, hop_end, out, s);
-}
-
 // One decode round: D1 of frames [f0, f0 + n) into block slots 1.., the overlap-add of their hops
 // (+ `tail`: the bare overlap tail, hop n_frames) into dout, then, when another round follows
 // (`carry`), the last frame's block copied to slot 0 for that round's overlap-add.
@@ -1734,8 +1724,8 @@ int decode_round(glc_ctx *ctx, uint64_t f0, uint64_t n, bool tail, bool carry, T
     const int rc = launch_d1(ctx, static_cast<uint32_t>(f0 * ch), static_cast<uint32_t>(n * ch), blocks + slot);
     if (rc != GLC_OK) return rc;
   }
-  GLC_HIP(ctx, launch_d2(blocks, static_cast<int64_t>(f0) - 1, ctx->dec_frames, ch, f0, f0 + n + (tail ? 1 : 0), dout,
-                         ctx->stream));
+  GLC_HIP(ctx, glc::launch_overlap_add(blocks, static_cast<int64_t>(f0) - 1, ctx->dec_frames, ch, f0, f0 + n + (tail ? 1 : 0), dout,
+                                       ctx->stream));
   if (carry)
     GLC_HIP(ctx, hipMemcpyAsync(blocks, blocks + n * slot, slot * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
   return GLC_OK;
@@ -1856,6 +1846,50 @@ int decode_prepared_to_host(glc_ctx *ctx, T *pcm_out, uint64_t cap, uint64_t *n_
   return GLC_OK;
 }
 
+// ---- the hop descriptors of the descriptor overlap-add (glc::HopDescStrided), as every batch driver writes them
+
+// The descriptors of hops [h0, h1) of a clip of `nf` frames whose frame f is block slot base + f: one per hop that
+// the clip's trim keeps something of, in hop order.  The kept samples land from element `dst` on, interleaved, or
+// (planes) in planes `cstride` apart.
+glc::HopDescStrided *write_hop_descs(glc::HopDescStrided *d, uint64_t nf, uint32_t ch, const glc::Trim &trim, uint64_t h0,
+                                     uint64_t h1, int64_t base, uint64_t dst, bool planes, uint64_t cstride) {
+  const uint64_t per_hop = uint64_t(glc::kHop) * ch, lo_all = trim.start, hi_all = trim.start + trim.n;
+  for (uint64_t h = h0; h < h1; ++h) {
+    const uint64_t lo = std::max(lo_all, h * per_hop), hi = std::min(hi_all, (h + 1) * per_hop);
+    if (hi <= lo) continue;
+    const uint64_t j0 = lo - trim.start;
+    *d++ = glc::HopDescStrided{h >= 1 ? static_cast<int32_t>(base + static_cast<int64_t>(h) - 1) : -1,
+                               h < nf ? static_cast<int32_t>(base + static_cast<int64_t>(h)) : -1,
+                               static_cast<uint32_t>(lo - h * per_hop),
+                               static_cast<uint32_t>(hi - lo),
+                               planes ? dst : dst + j0,
+                               planes ? cstride : 0ull,
+                               j0};
+  }
+  return d;
+}
+
+// How many descriptors write_hop_descs makes of hops [h0, h1): a hop keeps something exactly when it lies from the
+// hop of the first kept sample to the hop of the last one.
+inline uint64_t count_hop_descs(const glc::Trim &trim, uint64_t per_hop, uint64_t h0, uint64_t h1) {
+  if (trim.n == 0) return 0;
+  const uint64_t lo = std::max(h0, trim.start / per_hop), hi = std::min(h1, (trim.start + trim.n - 1) / per_hop + 1);
+  return hi > lo ? hi - lo : 0;
+}
+
+// All descriptors of one clip of a batch round.  `lng` (the one clip of a round of its own, longer than a decode
+// round): round by round, block slots counted in the ring (frame f0 - 1 of a round in slot 0); otherwise flat, the
+// clip's frame 0 in block slot `real`.
+glc::HopDescStrided *write_clip_descs(glc::HopDescStrided *d, bool lng, uint64_t nf, uint32_t ch, const glc::Trim &trim,
+                                      uint64_t real, uint64_t dst, bool planes, uint64_t cstride) {
+  if (!lng) return write_hop_descs(d, nf, ch, trim, 0, nf + 1, static_cast<int64_t>(real), dst, planes, cstride);
+  for (uint64_t f0 = 0; f0 < nf; f0 += kDecodeChunkFrames) {
+    const uint64_t f1 = std::min(nf, f0 + kDecodeChunkFrames);
+    d = write_hop_descs(d, nf, ch, trim, f0, f1 + (f1 == nf ? 1 : 0), 1 - static_cast<int64_t>(f0), dst, planes, cstride);
+  }
+  return d;
+}
+
 // One round of glc_decode_batch: streams[0 .. n) (all of `ch` channels, together at most a round's frames)
 // through D1 as one row table, then the segment-aware overlap-add, which writes every stream's TRIMMED
 // samples back to back, and one copy of them to pcm_out.  lens[i]: glc_decoded_len of stream i.
@@ -1873,23 +1907,20 @@ int decode_batch_round(glc_ctx *ctx, const glc_frames *const *streams, uint64_t 
   if (rc != GLC_OK) return rc;
   // a descriptor per output hop that the stream's gapless trim keeps something of
   std::vector<glc::HopDesc> desc;
-  const uint64_t per_hop = static_cast<uint64_t>(glc::kHop) * ch;
-  uint64_t slot0 = 0, dst0 = 0;
-  for (uint64_t i = 0; i < n; ++i) {
-    const glc_frames *in = streams[i];
-    const glc::Trim trim = glc::gapless_trim(in->n_frames, ch, in->encoder_delay, in->original_length);
-    if (trim.n) {
-      const uint64_t h_lo = trim.start / per_hop, h_hi = (trim.start + trim.n - 1) / per_hop;
-      for (uint64_t h = h_lo; h <= h_hi; ++h) {
-        const uint64_t lo = std::max(trim.start, h * per_hop), hi = std::min(trim.start + trim.n, (h + 1) * per_hop);
-        desc.push_back(glc::HopDesc{h >= 1 ? static_cast<int32_t>(slot0 + h - 1) : -1,
-                                    h < in->n_frames ? static_cast<int32_t>(slot0 + h) : -1,
-                                    static_cast<uint32_t>(dst0 + (lo - trim.start)), static_cast<uint32_t>(lo - h * per_hop),
-                                    static_cast<uint32_t>(hi - lo), 0u});
-      }
+  {
+    std::vector<glc::HopDescStrided> wide(frames + n);  // at most a hop per frame and a tail per stream
+    glc::HopDescStrided *d = wide.data();
+    uint64_t slot0 = 0, dst0 = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+      const glc_frames *in = streams[i];
+      const glc::Trim trim = glc::gapless_trim(in->n_frames, ch, in->encoder_delay, in->original_length);
+      d = write_hop_descs(d, in->n_frames, ch, trim, 0, in->n_frames + 1, static_cast<int64_t>(slot0), dst0, false, 0);
+      slot0 += in->n_frames;
+      dst0 += trim.n;
     }
-    slot0 += in->n_frames;
-    dst0 += trim.n;
+    // uploaded in the 24-byte form: a round's output is addressed in 31 bits (decode_batch_impl's hop_budget)
+    for (const glc::HopDescStrided *w = wide.data(); w != d; ++w)
+      desc.push_back(glc::HopDesc{w->prev, w->cur, static_cast<uint32_t>(w->dst), w->first, w->cnt, 0u});
   }
   // everything D1 and D2 read, as ONE image in pinned memory and one copy: the pairs of all streams, the
   // canonicalised lists, the row arrays, the raw pool, the hop descriptors
@@ -1939,8 +1970,8 @@ int decode_batch_round(glc_ctx *ctx, const glc_frames *const *streams, uint64_t 
   // (D1's 8-frame units may span two streams: that only widens a union)
   GLC_HIP(ctx, glc::launch_imdct_rows(ctx->dev, rows, 0, static_cast<uint32_t>(M), ch, blocks, ctx->stream, ctx->d1_variant,
                                       ctx->dec_plan.p, ctx->dec_plan.p ? ctx->dec_plan_groups : 0, false));
-  GLC_HIP(ctx, glc::launch_overlap_add_batch(blocks, reinterpret_cast<const glc::HopDesc *>(mb + o_desc),
-                                             static_cast<uint32_t>(desc.size()), ch, stage, ctx->stream));
+  GLC_HIP(ctx, glc::launch_overlap_add_strided(blocks, reinterpret_cast<const glc::HopDesc *>(mb + o_desc),
+                                               static_cast<uint32_t>(desc.size()), ch, stage, ctx->stream));
   if (n_out) GLC_HIP(ctx, hipMemcpyAsync(pcm_out, stage, n_out * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
   GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return GLC_OK;
@@ -2180,7 +2211,8 @@ int rt_emit_hops(glc_ctx *ctx, const RtGeom &g, uint64_t h0, uint64_t h1, T *d_o
   if (g.trim.n == 0) return GLC_OK;
   const uint64_t full_lo = std::max(h0, (lo + g.per_hop - 1) / g.per_hop), full_hi = std::min(h1, hi / g.per_hop);
   if (full_hi > full_lo)
-    GLC_HIP(ctx, launch_d2(blocks, blk0, g.n_frames, g.ch, full_lo, full_hi, d_out + (full_lo * g.per_hop - lo), ctx->stream));
+    GLC_HIP(ctx, glc::launch_overlap_add(blocks, blk0, g.n_frames, g.ch, full_lo, full_hi, d_out + (full_lo * g.per_hop - lo),
+                                         ctx->stream));
   const uint64_t cut[2] = {lo / g.per_hop, hi / g.per_hop};  // the hops that hold the window's two ends
   for (int i = 0; i < 2; ++i) {
     const uint64_t h = cut[i];
@@ -2189,7 +2221,7 @@ int rt_emit_hops(glc_ctx *ctx, const RtGeom &g, uint64_t h0, uint64_t h1, T *d_o
     const uint64_t a = std::max(lo, h * g.per_hop), b = std::min(hi, (h + 1) * g.per_hop);
     if (b <= a) continue;
     T *edge = static_cast<T *>(ctx->rt_edge.p) + static_cast<size_t>(i) * g.per_hop;
-    GLC_HIP(ctx, launch_d2(blocks, blk0, g.n_frames, g.ch, h, h + 1, edge, ctx->stream));
+    GLC_HIP(ctx, glc::launch_overlap_add(blocks, blk0, g.n_frames, g.ch, h, h + 1, edge, ctx->stream));
     GLC_HIP(ctx, hipMemcpyAsync(d_out + (a - lo), edge + (a - h * g.per_hop), (b - a) * sizeof(T), hipMemcpyDeviceToDevice,
                                 ctx->stream));
   }
@@ -2545,25 +2577,6 @@ struct RtbRound {
 // Kept hops of a clip: 512 interleaved samples of delay in front (hop 0 is cut), len * ch kept.
 inline uint64_t rtb_hops_kept(uint64_t len, uint32_t ch) { return (glc::kHop / 2 + len * ch - 1) / (uint64_t(glc::kHop) * ch) + 1; }
 
-// The descriptors of hops [h0, h1) of a clip of `nf` frames whose frame f is block slot base + f.
-glc::HopDescStrided *rtb_write_hops(glc::HopDescStrided *d, uint64_t nf, uint32_t ch, const glc::Trim &trim, uint64_t h0,
-                                    uint64_t h1, int64_t base, uint64_t dst, bool planes, uint64_t cstride) {
-  const uint64_t per_hop = uint64_t(glc::kHop) * ch, lo_all = trim.start, hi_all = trim.start + trim.n;
-  for (uint64_t h = h0; h < h1; ++h) {
-    const uint64_t lo = std::max(lo_all, h * per_hop), hi = std::min(hi_all, (h + 1) * per_hop);
-    if (hi <= lo) continue;
-    const uint64_t j0 = lo - trim.start;
-    *d++ = glc::HopDescStrided{h >= 1 ? static_cast<int32_t>(base + static_cast<int64_t>(h) - 1) : -1,
-                               h < nf ? static_cast<int32_t>(base + static_cast<int64_t>(h)) : -1,
-                               static_cast<uint32_t>(lo - h * per_hop),
-                               static_cast<uint32_t>(hi - lo),
-                               planes ? dst : dst + j0,
-                               planes ? cstride : 0ull,
-                               j0};
-  }
-  return d;
-}
-
 int rtb_impl(glc_ctx *ctx, const float *d_pcm, const RtbLayout &in, float *d_out, const RtbLayout &out) {
   const uint64_t n = in.l->n_clips;
   const uint32_t ch = in.l->channels;
@@ -2651,18 +2664,10 @@ int rtb_impl(glc_ctx *ctx, const float *d_pcm, const RtbLayout &in, float *d_out
       const uint64_t i = r.first + k, nf = plans[i].n_frames;
       clips[k] = glc::StageClip{in.at(i), in.len(i), static_cast<uint32_t>(vslot), {0u, 0u, 0u}};
       const glc::Trim trim = glc::gapless_trim(nf, ch, plans[i].encoder_delay, in.len(i) * ch);
-      if (r.lng) {  // round by round, block slots counted in the ring (frame f0 - 1 of a round in slot 0)
-        for (uint64_t f0 = 0; f0 < nf; f0 += kDecodeChunkFrames) {
-          const uint64_t f1 = std::min(nf, f0 + kDecodeChunkFrames);
-          desc = rtb_write_hops(desc, nf, ch, trim, f0, f1 + (f1 == nf ? 1 : 0), 1 - static_cast<int64_t>(f0), out.at(i),
-                                out_planes, out.l->channel_stride);
-        }
-      } else {
-        desc = rtb_write_hops(desc, nf, ch, trim, 0, nf + 1, static_cast<int64_t>(real), out.at(i), out_planes,
-                              out.l->channel_stride);
+      desc = write_clip_descs(desc, r.lng, nf, ch, trim, real, out.at(i), out_planes, out.l->channel_stride);
+      if (!r.lng)
         for (uint64_t f = 0; f < nf; ++f)
           fmap[real + f] = glc::FrameMap{static_cast<uint32_t>(vslot + f), static_cast<uint32_t>(i)};
-      }
       vslot += nf + 1;
       real += nf;
     }
@@ -2691,9 +2696,7 @@ int rtb_impl(glc_ctx *ctx, const float *d_pcm, const RtbLayout &in, float *d_out
         const uint64_t nf = std::min(g.round, g.n_frames - f0), f1 = f0 + nf;
         // the round's descriptors: those of hops [f0, f1 (+ 1)) that keep anything - all but none, since only the
         // tail hop can lie wholly behind the kept samples
-        uint64_t nd = 0;
-        for (uint64_t h = f0; h < f1 + (f1 == g.n_frames ? 1 : 0); ++h)
-          if (std::min(g.trim.start + g.trim.n, (h + 1) * per_hop) > std::max(g.trim.start, h * per_hop)) ++nd;
+        const uint64_t nd = count_hop_descs(g.trim, per_hop, f0, f1 + (f1 == g.n_frames ? 1 : 0));
         const RtStridedSink sink{desc, static_cast<uint32_t>(nd), out_planes, d_out};
         rc = rt_roundtrip_round<float>(ctx, g, vs, n_samples, f0, nf, nullptr, d_stats + r.stat_off, &sink);
         if (rc != GLC_OK) return rc;
@@ -2820,12 +2823,10 @@ int cd_decode_one(glc_ctx *ctx, const RtGeom &g, const void *d_blob, uint64_t bl
   GLC_HIP(ctx, glc::launch_rows_from_compact(nullptr, one, 1, M, g.ch, d_blob, ctx->rt_rows.p, d_status, ctx->stream, &rows));
   for (uint64_t f0 = 0; f0 < g.n_frames; f0 += g.round) {
     const uint64_t nf = std::min(g.round, g.n_frames - f0), f1 = f0 + nf;
-    RtStridedSink sink{desc, 0u, planar, sink_out};
-    if (desc) {  // the round's descriptors: those of hops [f0, f1 (+ 1)) that keep anything (rtb_impl)
-      for (uint64_t h = f0; h < f1 + (f1 == g.n_frames ? 1 : 0); ++h)
-        if (std::min(g.trim.start + g.trim.n, (h + 1) * g.per_hop) > std::max(g.trim.start, h * g.per_hop)) ++sink.n_desc;
-      desc += sink.n_desc;
-    }
+    // the round's descriptors: those of hops [f0, f1 (+ 1)) that keep anything (rtb_impl)
+    const uint64_t nd = desc ? count_hop_descs(g.trim, g.per_hop, f0, f1 + (f1 == g.n_frames ? 1 : 0)) : 0;
+    const RtStridedSink sink{desc, static_cast<uint32_t>(nd), planar, sink_out};
+    if (desc) desc += nd;
     rc = rt_decode_round_rows<float>(ctx, g, rows, static_cast<uint32_t>(f0 * g.ch), f0, nf, d_out, desc ? &sink : nullptr);
     if (rc != GLC_OK) return rc;
   }
@@ -2910,18 +2911,10 @@ int cdb_impl(glc_ctx *ctx, const void *const *d_blobs, const uint64_t *blob_byte
     for (uint64_t k = 0; k < r.n; ++k) {
       const uint64_t i = r.first + k, nf = plans[i].n_frames;
       const glc::Trim trim = glc::gapless_trim(nf, ch, plans[i].encoder_delay, out.len(i) * ch);
-      if (r.lng) {  // round by round, block slots counted in the ring (frame f0 - 1 of a round in slot 0)
-        for (uint64_t f0 = 0; f0 < nf; f0 += kDecodeChunkFrames) {
-          const uint64_t f1 = std::min(nf, f0 + kDecodeChunkFrames);
-          desc = rtb_write_hops(desc, nf, ch, trim, f0, f1 + (f1 == nf ? 1 : 0), 1 - static_cast<int64_t>(f0), out.at(i),
-                                out_planes, out.l->channel_stride);
-        }
-      } else {
+      if (!r.lng)
         dir[k] = glc::CompactBlob{reinterpret_cast<uintptr_t>(d_blobs[i]), blob_bytes[i], static_cast<uint32_t>(real * ch),
                                   static_cast<uint32_t>(nf * ch), {0u, 0u}};
-        desc = rtb_write_hops(desc, nf, ch, trim, 0, nf + 1, static_cast<int64_t>(real), out.at(i), out_planes,
-                              out.l->channel_stride);
-      }
+      desc = write_clip_descs(desc, r.lng, nf, ch, trim, real, out.at(i), out_planes, out.l->channel_stride);
       real += nf;
     }
     if (static_cast<uint64_t>(desc - reinterpret_cast<glc::HopDescStrided *>(img + r.o_desc)) != r.n_desc)

@@ -169,21 +169,11 @@ hipError_t launch_imdct_rows(const DeviceTables &t, const DecodeRows &rows, uint
 hipError_t launch_overlap_add(const float *blocks, int64_t blk_frame0, uint64_t n_frames,
                               uint32_t ch, uint64_t hop_begin, uint64_t hop_end, float *out,
                               hipStream_t s);
-
-// D2 of a batch of streams whose frames sit back to back in `blocks`: one descriptor per kept output
-// hop.  out[dst .. dst + cnt) = interleaved samples [first, first + cnt) of the hop made of the second
-// half of block slot `prev` (-1: +0.0, a stream's first hop) and the first half of slot `cur` (-1: none,
-// the bare tail).  `out` is 16-byte aligned, dst is not bound to any alignment.
-struct HopDesc {
-  int32_t prev, cur;
-  uint32_t dst, first, cnt, pad;
-};
-hipError_t launch_overlap_add_batch(const float *blocks, const HopDesc *desc, uint32_t n_desc, uint32_t ch, float *out,
-                                    hipStream_t s);
-// ... narrowed to 16-bit PCM as launch_overlap_add_i16 narrows (glc_decode_batch_i16): `out` is 8-byte aligned,
-// dst an index of 2-byte elements.
-hipError_t launch_overlap_add_batch(const float *blocks, const HopDesc *desc, uint32_t n_desc, uint32_t ch, int16_t *out,
-                                    hipStream_t s);
+// ... with the narrowing of the reference's 16-bit writers on the way out: the same sums, then
+// `(v * 32767.0).clamp(-32768.0, 32767.0) as i16` (NaN -> 0, truncation) - `out` is any 2-byte aligned pointer.
+hipError_t launch_overlap_add(const float *blocks, int64_t blk_frame0, uint64_t n_frames,
+                              uint32_t ch, uint64_t hop_begin, uint64_t hop_end, int16_t *out,
+                              hipStream_t s);
 
 // S1: the interleaved virtual stream of a round of glc_roundtrip_batch_device, gathered from strided device
 // audio.  clips[k] (ascending `slot`, clips[0].slot == 0): the clip's first sample is element `src` of the
@@ -198,8 +188,10 @@ struct StageClip {
 hipError_t launch_stage_clips(const float *src, const StageClip *clips, uint32_t n_clips, uint32_t ch, bool planar,
                               uint64_t channel_stride, uint32_t n_virtual_frames, float *vstream, hipStream_t s);
 
-// D2 into strided clips: launch_overlap_add_batch with a 64-bit destination that is bound to no alignment
-// beyond 4 bytes.  Interleaved (cstride == 0 in every descriptor): out[dst .. dst + cnt) = samples [first,
+// D2 by descriptor, one per kept output hop (the batch drivers): the hop is made of the second half of block slot
+// `prev` (-1: +0.0, a stream's first hop) and the first half of slot `cur` (-1: none, the bare tail).  The
+// destination is a 64-bit element index bound to no alignment beyond that of `out`, which is aligned to its
+// element.  Interleaved (cstride == 0 in every descriptor): out[dst .. dst + cnt) = samples [first,
 // first + cnt) of the hop.  `planar`: the span is the clip's interleaved samples [j0, j0 + cnt), sample j going
 // to out[dst + (j % ch) * cstride + j / ch] - dst is the clip's first element.
 struct HopDescStrided {
@@ -209,12 +201,19 @@ struct HopDescStrided {
 };
 hipError_t launch_overlap_add_strided(const float *blocks, const HopDescStrided *desc, uint32_t n_desc, uint32_t ch, bool planar,
                                       float *out, hipStream_t s);
+// The interleaved descriptor with a 32-bit destination, 24 bytes instead of 40: what glc_decode_batch uploads per
+// kept hop (its rounds address their output in 31 bits).  Same kernel, same chunks; kept beside HopDescStrided
+// because that driver measured slower, per launch and per call, with the wide form.
+struct HopDesc {
+  int32_t prev, cur;
+  uint32_t dst, first, cnt, pad;
+};
+hipError_t launch_overlap_add_strided(const float *blocks, const HopDesc *desc, uint32_t n_desc, uint32_t ch, float *out,
+                                      hipStream_t s);
+// ... narrowed to 16-bit PCM as launch_overlap_add narrows (glc_decode_batch_i16): dst an index of 2-byte elements.
+hipError_t launch_overlap_add_strided(const float *blocks, const HopDesc *desc, uint32_t n_desc, uint32_t ch, int16_t *out,
+                                      hipStream_t s);
 
-// D2 with the narrowing of the reference's 16-bit writers on the way out: the same sums, then
-// `(v * 32767.0).clamp(-32768.0, 32767.0) as i16` (NaN -> 0, truncation) - `out` is any 2-byte aligned pointer.
-hipError_t launch_overlap_add_i16(const float *blocks, int64_t blk_frame0, uint64_t n_frames,
-                                  uint32_t ch, uint64_t hop_begin, uint64_t hop_end, int16_t *out,
-                                  hipStream_t s);
 // W1: interleaved integer PCM -> f32 as the reference's loaders widen it: out[i] = (float)in[i] / max,
 // max = 2^(bits-1), -2^31 for bits == 32.  `wide`: int32_t samples (bits 1..32), else int16_t
 // (bits 1..16); `in` aligned to its sample size, `out` to 4 bytes.

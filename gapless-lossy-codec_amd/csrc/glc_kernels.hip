@@ -932,16 +932,62 @@ void k_imdct_apply(DeviceTables tb, const unsigned *__restrict__ plan_hdr, const
 // D2: overlap-add + interleave.  blocks holds frames [blk_frame0, ...) as [frame][ch][2048];
 // hop h = second half of frame h-1 (+0.0 before the first frame) + first half of frame h; the
 // hop after the last frame is the bare overlap tail (no add, src/codec.rs:722-729).
+// Three kernels - whole hops of one stream (k_overlap_add), kept spans of many streams by descriptor
+// (k_overlap_add_strided) and its planar form (k_overlap_add_planar) - over ONE sum and ONE store.
 // ------------------------------------------------------------------------------------------
-// One workgroup row (blockIdx.y) per hop, a float4 of interleaved output per thread: 32-bit index
-// arithmetic (CH = 1 / 2 / 4 / 8: shifts; CH = 0: one 32-bit division per sample), coalesced 16-byte
-// stores, each block plane read in runs of consecutive samples.  (Round 2's kernel walked the output
+// The sample at position `at` of the two half blocks: prev = second half of the frame before, cur = first half
+// of the frame itself, either of which may be absent.
+__device__ __forceinline__ float d2_sum(const float *prev, const float *cur, bool has_prev, bool has_cur, size_t at) {
+  const float p = has_prev ? prev[at] : 0.0f;  // overlap starts as +0.0, :601
+  return has_cur ? add_rn(p, cur[at]) : p;      // :695 / the bare tail, :727
+}
+
+// ... at interleaved index o of the hop ([ch][2048] blocks): 32-bit index arithmetic, shifts for CH = 1 / 2 / 4 / 8,
+// one 32-bit division per sample for CH = 0 (any channel count).
+template <int CH>
+__device__ __forceinline__ float d2_sample(const float *prev, const float *cur, bool has_prev, bool has_cur, unsigned ch,
+                                           unsigned o) {
+  unsigned i, c;
+  if constexpr (CH == 1) i = o, c = 0;
+  else if constexpr (CH == 2) i = o >> 1, c = o & 1u;
+  else if constexpr (CH == 4) i = o >> 2, c = o & 3u;
+  else if constexpr (CH == 8) i = o >> 3, c = o & 7u;
+  else i = o / ch, c = o - i * ch;
+  return d2_sum(prev, cur, has_prev, has_cur, static_cast<size_t>(c) * kFrameI + i);
+}
+
+// Four consecutive output samples to dst: as one float4 / short4 when all four are kept and dst is aligned to
+// the vector (ALIGNED), else the kept ones element by element.  T = short narrows as the reference's 16-bit
+// writers do (convert_f32_to_i16: `(s * 32767.0).clamp(-32768.0, 32767.0) as i16`, src/audio.rs:11-16).
+template <bool ALIGNED, typename T>
+__device__ __forceinline__ void d2_store(const float (&v)[4], T *dst, const bool (&keep)[4]) {
+  static_assert(std::is_same<T, float>::value || std::is_same<T, short>::value, "float or 16-bit PCM");
+  using T4 = typename std::conditional<std::is_same<T, float>::value, float4, short4>::type;
+  T q[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if constexpr (std::is_same<T, float>::value) q[e] = v[e];
+    else q[e] = sat_i16(mul_rn(v[e], 32767.0f));  // src/audio.rs:13-14
+  }
+  if (ALIGNED && keep[0] && keep[3]) {
+    *reinterpret_cast<T4 *>(dst) = T4{q[0], q[1], q[2], q[3]};
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (keep[e]) dst[e] = q[e];
+  }
+}
+
+// One workgroup row (blockIdx.y) per hop, four interleaved output samples per thread: coalesced 16-byte
+// stores (8-byte ones of 16-bit PCM, so that the host boundary of a decode moves 2 bytes per sample), each
+// block plane read in runs of consecutive samples.  (Round 2's kernel walked the output
 // with a 64-bit grid-stride index: two 64-bit divisions per sample - 20 us at config 2, as long as the
 // 100 MB it moves take at Infinity-Cache speed.)
-template <int CH, bool VEC>
+// VEC = false: a destination that is only element-aligned (glc_decode_range_device takes any device pointer).
+template <int CH, bool VEC, typename T>
 __global__ __launch_bounds__(256) void k_overlap_add(const float *__restrict__ blocks, long long blk_frame0,
                                                       unsigned long long n_frames, unsigned ch,
-                                                      unsigned long long hop_begin, float *__restrict__ out) {
+                                                      unsigned long long hop_begin, T *__restrict__ out) {
   const unsigned per_hop = static_cast<unsigned>(kHopI) * ch;
   const unsigned o0 = (blockIdx.x * 256u + threadIdx.x) * 4u;  // first of this thread's 4 outputs inside the hop
   if (o0 >= per_hop) return;
@@ -952,49 +998,31 @@ __global__ __launch_bounds__(256) void k_overlap_add(const float *__restrict__ b
   const float *cur = blocks + (static_cast<size_t>(static_cast<long long>(h) - blk_frame0) * ch) * kFrameI;
   float v[4];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const unsigned o = o0 + e;
-    unsigned i, c;
-    if constexpr (CH == 1) i = o, c = 0;
-    else if constexpr (CH == 2) i = o >> 1, c = o & 1u;
-    else if constexpr (CH == 4) i = o >> 2, c = o & 3u;
-    else if constexpr (CH == 8) i = o >> 3, c = o & 7u;
-    else i = o / ch, c = o - i * ch;
-    const size_t at = static_cast<size_t>(c) * kFrameI + i;
-    const float p = has_prev ? prev[at] : 0.0f;  // overlap starts as +0.0, :601
-    v[e] = has_cur ? add_rn(p, cur[at]) : p;      // :695 / the bare tail, :727
-  }
-  float *dst = out + static_cast<size_t>(blockIdx.y) * per_hop + o0;
-  if constexpr (VEC) {
-    *reinterpret_cast<float4 *>(dst) = float4{v[0], v[1], v[2], v[3]};
-  } else {  // a destination that is only 4-byte aligned (glc_decode_range_device takes any device pointer)
-    dst[0] = v[0], dst[1] = v[1], dst[2] = v[2], dst[3] = v[3];
-  }
+  for (int e = 0; e < 4; ++e) v[e] = d2_sample<CH>(prev, cur, has_prev, has_cur, ch, o0 + e);
+  constexpr bool all[4] = {true, true, true, true};
+  d2_store<VEC>(v, out + static_cast<size_t>(blockIdx.y) * per_hop + o0, all);
 }
 
-// D2 of a batch of streams (glc_decode_batch): one workgroup row per KEPT output hop, described by a
-// HopDesc - the block slots of the frame before (second half) and of the frame itself (first half),
-// either of which may be absent (-1: the first hop of a stream starts from +0.0, its last hop is the
-// bare tail), and the span [first, first + cnt) of the hop's interleaved samples that survives the
-// stream's gapless trim, which lands at out[dst ..).  dst is any sample index, so the threads are laid
-// over the DESTINATION: chunk k of a hop is the four floats at (dst & ~3) + 4k, 16-byte aligned when `out`
-// is, and goes out as one float4; only the first and the last chunk of a cut span can be partial, and
-// those store float by float.  Same sums as k_overlap_add.
-// T = short (glc_decode_batch_i16): the same rows and sums, narrowed as k_overlap_add_i16 narrows them
-// (`sat_i16(mul_rn(v, 32767.0f))`, src/audio.rs:11-16); `dst & 3` is then the lead in 2-byte elements, a whole
-// chunk one aligned short4 (8 bytes), the partial first and last chunk of a cut span go out short by short.
-template <int CH, typename T>
-__global__ __launch_bounds__(256) void k_overlap_add_batch(const float *__restrict__ blocks,
-                                                            const HopDesc *__restrict__ desc, unsigned ch,
-                                                            T *__restrict__ out) {
-  static_assert(std::is_same<T, float>::value || std::is_same<T, short>::value, "float or 16-bit PCM");
-  const HopDesc d = desc[blockIdx.y];
-  const unsigned lead = d.dst & 3u;
+// D2 by descriptor (the batch drivers): one workgroup row per KEPT output hop, described by a HopDescStrided (or a
+// HopDesc, D: the same with a 32-bit destination) -
+// the block slots of the frame before (second half) and of the frame itself (first half), either of which may
+// be absent (-1: the first hop of a stream starts from +0.0, its last hop is the bare tail), and the span
+// [first, first + cnt) of the hop's interleaved samples that survives the stream's gapless trim, which lands at
+// out[dst ..).  dst is any element index and `out` any element-aligned pointer, so the threads are laid over the
+// destination ADDRESS: chunk k of a hop is the four elements from the vector boundary at or below out + dst on,
+// and goes out as one float4 / short4; only the first and the last chunk of a cut span can be partial, and those
+// store element by element.  Same sums as k_overlap_add; T = short (glc_decode_batch_i16) narrows as it does.
+template <int CH, typename T, typename D>
+__global__ __launch_bounds__(256) void k_overlap_add_strided(const float *__restrict__ blocks, const D *__restrict__ desc,
+                                                              unsigned ch, T *__restrict__ out) {
+  const D d = desc[blockIdx.y];
+  T *span = out + d.dst;
+  const unsigned lead = static_cast<unsigned>(reinterpret_cast<uintptr_t>(span) / sizeof(T)) & 3u;
   const unsigned n_chunks = (lead + d.cnt + 3u) >> 2;
   const bool has_prev = d.prev >= 0, has_cur = d.cur >= 0;
   const float *prev = blocks + (static_cast<size_t>(has_prev ? d.prev : 0) * ch) * kFrameI + kHopI;
   const float *cur = blocks + (static_cast<size_t>(has_cur ? d.cur : 0) * ch) * kFrameI;
-  T *base = out + (d.dst - lead);
+  T *base = span - lead;
   for (unsigned k = blockIdx.x * 256u + threadIdx.x; k < n_chunks; k += gridDim.x * 256u) {
     const int j0 = static_cast<int>(4u * k) - static_cast<int>(lead);  // first of the chunk, counted from the span's start
     float v[4];
@@ -1003,76 +1031,48 @@ __global__ __launch_bounds__(256) void k_overlap_add_batch(const float *__restri
     for (int e = 0; e < 4; ++e) {
       const int j = j0 + e;
       keep[e] = j >= 0 && static_cast<unsigned>(j) < d.cnt;
-      const unsigned o = d.first + static_cast<unsigned>(keep[e] ? j : 0);
-      unsigned i, c;
-      if constexpr (CH == 1) i = o, c = 0;
-      else if constexpr (CH == 2) i = o >> 1, c = o & 1u;
-      else if constexpr (CH == 4) i = o >> 2, c = o & 3u;
-      else if constexpr (CH == 8) i = o >> 3, c = o & 7u;
-      else i = o / ch, c = o - i * ch;
-      const size_t at = static_cast<size_t>(c) * kFrameI + i;
-      const float p = has_prev ? prev[at] : 0.0f;  // overlap starts as +0.0, :601
-      v[e] = has_cur ? add_rn(p, cur[at]) : p;      // :695 / the bare tail, :727
+      v[e] = d2_sample<CH>(prev, cur, has_prev, has_cur, ch, d.first + static_cast<unsigned>(keep[e] ? j : 0));
     }
-    T *dst = base + 4u * static_cast<size_t>(k);
-    if constexpr (std::is_same<T, float>::value) {
-      if (keep[0] && keep[3]) {
-        *reinterpret_cast<float4 *>(dst) = float4{v[0], v[1], v[2], v[3]};
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (keep[e]) dst[e] = v[e];
-      }
-    } else {
-      short q[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) q[e] = sat_i16(mul_rn(v[e], 32767.0f));  // src/audio.rs:13-14
-      if (keep[0] && keep[3]) {
-        *reinterpret_cast<short4 *>(dst) = short4{q[0], q[1], q[2], q[3]};
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (keep[e]) dst[e] = q[e];
-      }
-    }
+    d2_store<true>(v, base + 4u * static_cast<size_t>(k), keep);
   }
 }
 
-// D2 writing 16-bit PCM: the same sums, then convert_f32_to_i16 of the reference's writers
-// (`(s * 32767.0).clamp(-32768.0, 32767.0) as i16`, src/audio.rs:11-16) on the way out, so that the
-// host boundary of a decode moves 2 bytes per sample.  Four samples per thread as in k_overlap_add,
-// stored as one 8-byte word (VEC) or four 2-byte ones (a destination that is only 2-byte aligned).
-template <int CH, bool VEC>
-__global__ __launch_bounds__(256) void k_overlap_add_i16(const float *__restrict__ blocks, long long blk_frame0,
-                                                          unsigned long long n_frames, unsigned ch,
-                                                          unsigned long long hop_begin, short *__restrict__ out) {
-  const unsigned per_hop = static_cast<unsigned>(kHopI) * ch;
-  const unsigned o0 = (blockIdx.x * 256u + threadIdx.x) * 4u;  // first of this thread's 4 outputs inside the hop
-  if (o0 >= per_hop) return;
-  const unsigned long long h = hop_begin + blockIdx.y;
-  const bool has_prev = h >= 1, has_cur = h < n_frames;
-  const float *prev = blocks + (static_cast<size_t>(static_cast<long long>(h) - 1 - blk_frame0) * ch) * kFrameI + kHopI;
-  const float *cur = blocks + (static_cast<size_t>(static_cast<long long>(h) - blk_frame0) * ch) * kFrameI;
-  short q[4];
+// Planar: workgroup (blockIdx.x = plane c, blockIdx.y = hop).  The hop keeps the clip's interleaved samples
+// [j0, j0 + cnt) (sample j is time j / ch of plane j % ch - the trim is counted in interleaved samples, so with 3 or
+// 6 channels a hop's span starts at a different time in different planes); plane c gets the times t with
+// j0 <= t * ch + c < j0 + cnt, at most 1025 of them, consecutive in memory.  A thread owns an aligned float4 of
+// the plane: four consecutive times, whose samples are four consecutive entries of ONE block plane - position
+// i0 + (t - t_lo) of block channel cc, one division per thread.  Only the first and the last chunk of a span
+// can be partial; they store float by float.
+__global__ __launch_bounds__(256) void k_overlap_add_planar(const float *__restrict__ blocks,
+                                                             const HopDescStrided *__restrict__ desc, unsigned ch,
+                                                             float *__restrict__ out) {
+  const HopDescStrided d = desc[blockIdx.y];
+  const unsigned c = blockIdx.x;
+  const unsigned long long j1 = d.j0 + d.cnt;
+  const unsigned long long t_lo = d.j0 > c ? (d.j0 - c + ch - 1) / ch : 0ull, t_hi = j1 > c ? (j1 - c + ch - 1) / ch : 0ull;
+  if (t_hi <= t_lo) return;
+  const unsigned n = static_cast<unsigned>(t_hi - t_lo);
+  const unsigned o0 = d.first + static_cast<unsigned>(t_lo * ch + c - d.j0);  // the hop's interleaved index of (t_lo, c)
+  const unsigned i0 = o0 / ch, cc = o0 - i0 * ch;
+  const bool has_prev = d.prev >= 0, has_cur = d.cur >= 0;
+  const float *prev = blocks + (static_cast<size_t>(has_prev ? d.prev : 0) * ch + cc) * kFrameI + kHopI + i0;
+  const float *cur = blocks + (static_cast<size_t>(has_cur ? d.cur : 0) * ch + cc) * kFrameI + i0;
+  float *span = out + d.dst + c * d.cstride + t_lo;
+  const unsigned lead = static_cast<unsigned>(reinterpret_cast<uintptr_t>(span) >> 2) & 3u;
+  const unsigned n_chunks = (lead + n + 3u) >> 2;
+  float *base = span - lead;
+  for (unsigned k = threadIdx.x; k < n_chunks; k += 256u) {
+    const int j0 = static_cast<int>(4u * k) - static_cast<int>(lead);
+    float v[4];
+    bool keep[4];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const unsigned o = o0 + e;
-    unsigned i, c;
-    if constexpr (CH == 1) i = o, c = 0;
-    else if constexpr (CH == 2) i = o >> 1, c = o & 1u;
-    else if constexpr (CH == 4) i = o >> 2, c = o & 3u;
-    else if constexpr (CH == 8) i = o >> 3, c = o & 7u;
-    else i = o / ch, c = o - i * ch;
-    const size_t at = static_cast<size_t>(c) * kFrameI + i;
-    const float p = has_prev ? prev[at] : 0.0f;              // overlap starts as +0.0, :601
-    const float v = has_cur ? add_rn(p, cur[at]) : p;        // :695 / the bare tail, :727
-    q[e] = sat_i16(mul_rn(v, 32767.0f));                     // src/audio.rs:13-14
-  }
-  short *dst = out + static_cast<size_t>(blockIdx.y) * per_hop + o0;
-  if constexpr (VEC) {
-    *reinterpret_cast<short4 *>(dst) = short4{q[0], q[1], q[2], q[3]};
-  } else {
-    dst[0] = q[0], dst[1] = q[1], dst[2] = q[2], dst[3] = q[3];
+    for (int e = 0; e < 4; ++e) {
+      const int j = j0 + e;
+      keep[e] = j >= 0 && static_cast<unsigned>(j) < n;
+      v[e] = d2_sum(prev, cur, has_prev, has_cur, static_cast<unsigned>(keep[e] ? j : 0));
+    }
+    d2_store<true>(v, base + 4u * static_cast<size_t>(k), keep);
   }
 }
 
@@ -1739,101 +1739,6 @@ __global__ __launch_bounds__(256) void k_stage_clips_planar_any(const float *__r
 }
 
 // ------------------------------------------------------------------------------------------
-// D2 into strided clips (glc_roundtrip_batch_device): k_overlap_add_batch with a 64-bit destination, which
-// may be 4 bytes off any boundary (the chunks are laid over the ADDRESS, not over an index), and a planar
-// form.  Same sums as k_overlap_add.
-// ------------------------------------------------------------------------------------------
-template <int CH>
-__global__ __launch_bounds__(256) void k_overlap_add_strided(const float *__restrict__ blocks,
-                                                              const HopDescStrided *__restrict__ desc, unsigned ch,
-                                                              float *__restrict__ out) {
-  const HopDescStrided d = desc[blockIdx.y];
-  float *span = out + d.dst;
-  const unsigned lead = static_cast<unsigned>(reinterpret_cast<uintptr_t>(span) >> 2) & 3u;
-  const unsigned n_chunks = (lead + d.cnt + 3u) >> 2;
-  const bool has_prev = d.prev >= 0, has_cur = d.cur >= 0;
-  const float *prev = blocks + (static_cast<size_t>(has_prev ? d.prev : 0) * ch) * kFrameI + kHopI;
-  const float *cur = blocks + (static_cast<size_t>(has_cur ? d.cur : 0) * ch) * kFrameI;
-  float *base = span - lead;
-  for (unsigned k = blockIdx.x * 256u + threadIdx.x; k < n_chunks; k += gridDim.x * 256u) {
-    const int j0 = static_cast<int>(4u * k) - static_cast<int>(lead);
-    float v[4];
-    bool keep[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int j = j0 + e;
-      keep[e] = j >= 0 && static_cast<unsigned>(j) < d.cnt;
-      const unsigned o = d.first + static_cast<unsigned>(keep[e] ? j : 0);
-      unsigned i, c;
-      if constexpr (CH == 1) i = o, c = 0;
-      else if constexpr (CH == 2) i = o >> 1, c = o & 1u;
-      else if constexpr (CH == 4) i = o >> 2, c = o & 3u;
-      else if constexpr (CH == 8) i = o >> 3, c = o & 7u;
-      else i = o / ch, c = o - i * ch;
-      const size_t at = static_cast<size_t>(c) * kFrameI + i;
-      const float p = has_prev ? prev[at] : 0.0f;
-      v[e] = has_cur ? add_rn(p, cur[at]) : p;
-    }
-    float *dst = base + 4u * static_cast<size_t>(k);
-    if (keep[0] && keep[3]) {
-      *reinterpret_cast<float4 *>(dst) = float4{v[0], v[1], v[2], v[3]};
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (keep[e]) dst[e] = v[e];
-    }
-  }
-}
-
-// Planar: workgroup (blockIdx.x = plane c, blockIdx.y = hop).  The hop keeps the clip's interleaved samples
-// [j0, j0 + cnt) (sample j is time j / ch of plane j % ch - the trim is counted in interleaved samples, so with 3 or
-// 6 channels a hop's span starts at a different time in different planes); plane c gets the times t with
-// j0 <= t * ch + c < j0 + cnt, at most 1025 of them, consecutive in memory.  A thread owns an aligned float4 of
-// the plane: four consecutive times, whose samples are four consecutive entries of ONE block plane - position
-// i0 + (t - t_lo) of block channel cc, one division per thread.  Only the first and the last chunk of a span
-// can be partial; they store float by float.
-__global__ __launch_bounds__(256) void k_overlap_add_planar(const float *__restrict__ blocks,
-                                                             const HopDescStrided *__restrict__ desc, unsigned ch,
-                                                             float *__restrict__ out) {
-  const HopDescStrided d = desc[blockIdx.y];
-  const unsigned c = blockIdx.x;
-  const unsigned long long j1 = d.j0 + d.cnt;
-  const unsigned long long t_lo = d.j0 > c ? (d.j0 - c + ch - 1) / ch : 0ull, t_hi = j1 > c ? (j1 - c + ch - 1) / ch : 0ull;
-  if (t_hi <= t_lo) return;
-  const unsigned n = static_cast<unsigned>(t_hi - t_lo);
-  const unsigned o0 = d.first + static_cast<unsigned>(t_lo * ch + c - d.j0);  // the hop's interleaved index of (t_lo, c)
-  const unsigned i0 = o0 / ch, cc = o0 - i0 * ch;
-  const bool has_prev = d.prev >= 0, has_cur = d.cur >= 0;
-  const float *prev = blocks + (static_cast<size_t>(has_prev ? d.prev : 0) * ch + cc) * kFrameI + kHopI + i0;
-  const float *cur = blocks + (static_cast<size_t>(has_cur ? d.cur : 0) * ch + cc) * kFrameI + i0;
-  float *span = out + d.dst + c * d.cstride + t_lo;
-  const unsigned lead = static_cast<unsigned>(reinterpret_cast<uintptr_t>(span) >> 2) & 3u;
-  const unsigned n_chunks = (lead + n + 3u) >> 2;
-  float *base = span - lead;
-  for (unsigned k = threadIdx.x; k < n_chunks; k += 256u) {
-    const int j0 = static_cast<int>(4u * k) - static_cast<int>(lead);
-    float v[4];
-    bool keep[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int j = j0 + e;
-      keep[e] = j >= 0 && static_cast<unsigned>(j) < n;
-      const unsigned at = static_cast<unsigned>(keep[e] ? j : 0);
-      const float p = has_prev ? prev[at] : 0.0f;
-      v[e] = has_cur ? add_rn(p, cur[at]) : p;
-    }
-    float *dst = base + 4u * static_cast<size_t>(k);
-    if (keep[0] && keep[3]) {
-      *reinterpret_cast<float4 *>(dst) = float4{v[0], v[1], v[2], v[3]};
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (keep[e]) dst[e] = v[e];
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------
 // Clock probe (include/glc_debug.h, measurement only): ONE wave that sleeps beside whatever else runs
 // on the device and reads the shader-clock counter (s_memtime) against the constant 100 MHz counter
 // (s_memrealtime) over `ticks_100mhz`: shader cycles / reference ticks x 100 MHz = the clock the chip
@@ -2221,65 +2126,56 @@ hipError_t launch_imdct_rows(const DeviceTables &t, const DecodeRows &rows, uint
   return hipGetLastError();
 }
 
-hipError_t launch_overlap_add(const float *blocks, int64_t blk_frame0, uint64_t n_frames, uint32_t ch,
-                              uint64_t hop_begin, uint64_t hop_end, float *out, hipStream_t s) {
+namespace {
+// What the D2 launchers share.  blockIdx.y is 16 bits wide: rows (hops or descriptors) [0, n) go out in slabs
+// of 32768, launch(first row, rows).  (Every decode driver stays far below: rounds of <= 4097 hops.)
+template <typename F>
+void d2_slabs(uint64_t n, F &&launch) {
+  for (uint64_t r0 = 0; r0 < n; r0 += 32768) launch(r0, static_cast<unsigned>(std::min<uint64_t>(n - r0, 32768)));
+}
+// ... and the instantiation by channel count: launch(CH) with CH = ch for 1 / 2 / 4 / 8, else 0 (any count)
+template <typename F>
+void d2_by_channels(uint32_t ch, F &&launch) {
+  switch (ch) {
+    case 1: launch(std::integral_constant<int, 1>{}); break;
+    case 2: launch(std::integral_constant<int, 2>{}); break;
+    case 4: launch(std::integral_constant<int, 4>{}); break;
+    case 8: launch(std::integral_constant<int, 8>{}); break;
+    default: launch(std::integral_constant<int, 0>{}); break;
+  }
+}
+inline unsigned d2_blocks_x(uint32_t ch) { return (1024u * ch / 4u + 255u) / 256u; }  // 4-sample chunks of a hop over 256 threads
+
+template <typename T>
+hipError_t overlap_add_typed(const float *blocks, int64_t blk_frame0, uint64_t n_frames, uint32_t ch, uint64_t hop_begin,
+                             uint64_t hop_end, T *out, hipStream_t s) {
   if (hop_end <= hop_begin) return hipSuccess;
   const unsigned per_hop = 1024u * ch;
-  const unsigned bx = (per_hop / 4u + 255u) / 256u;  // float4s per hop over 256 threads
-  // blockIdx.y is 16 bits wide: hops in slabs of 32768 (every caller stays far below: rounds of <= 4097 hops)
-  for (uint64_t h0 = hop_begin; h0 < hop_end; h0 += 32768) {
-    const unsigned nh = static_cast<unsigned>(hop_end - h0 < 32768 ? hop_end - h0 : 32768);
-    const dim3 grid(bx, nh);
-    float *o = out + (h0 - hop_begin) * per_hop;
+  d2_slabs(hop_end - hop_begin, [&](uint64_t r0, unsigned nh) {
+    const dim3 grid(d2_blocks_x(ch), nh);
+    T *o = out + r0 * per_hop;
     const long long f0 = static_cast<long long>(blk_frame0);
-    const unsigned long long nf = n_frames, hb = h0;
-    if (reinterpret_cast<uintptr_t>(o) & 15u) {
-      hipLaunchKernelGGL((k_overlap_add<0, false>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o);
-      continue;
+    const unsigned long long nf = n_frames, hb = hop_begin + r0;
+    if (reinterpret_cast<uintptr_t>(o) & (4u * sizeof(T) - 1u)) {  // not aligned to a float4 / short4
+      hipLaunchKernelGGL((k_overlap_add<0, false, T>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o);
+      return;
     }
-    switch (ch) {
-      case 1: hipLaunchKernelGGL((k_overlap_add<1, true>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o); break;
-      case 2: hipLaunchKernelGGL((k_overlap_add<2, true>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o); break;
-      case 4: hipLaunchKernelGGL((k_overlap_add<4, true>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o); break;
-      case 8: hipLaunchKernelGGL((k_overlap_add<8, true>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o); break;
-      default: hipLaunchKernelGGL((k_overlap_add<0, true>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o); break;
-    }
-  }
-  return hipGetLastError();
-}
-
-namespace {
-template <typename T>
-hipError_t overlap_add_batch_typed(const float *blocks, const HopDesc *desc, uint32_t n_desc, uint32_t ch, T *out,
-                                   hipStream_t s) {
-  if (n_desc == 0) return hipSuccess;
-  if (reinterpret_cast<uintptr_t>(out) & (4u * sizeof(T) - 1u)) return hipErrorInvalidValue;  // the float4 / short4 chunks are laid over `out`
-  const unsigned per_hop = 1024u * ch;
-  const unsigned bx = (per_hop / 4u + 255u) / 256u;  // a span that starts off a chunk boundary has one chunk more: the stride loop's
-  for (uint32_t d0 = 0; d0 < n_desc; d0 += 32768) {  // slabs: blockIdx.y is 16 bits wide
-    const unsigned nd = n_desc - d0 < 32768 ? n_desc - d0 : 32768;
-    const dim3 grid(bx, nd);
-    const HopDesc *d = desc + d0;
-    switch (ch) {
-      case 1: hipLaunchKernelGGL((k_overlap_add_batch<1, T>), grid, dim3(256), 0, s, blocks, d, ch, out); break;
-      case 2: hipLaunchKernelGGL((k_overlap_add_batch<2, T>), grid, dim3(256), 0, s, blocks, d, ch, out); break;
-      case 4: hipLaunchKernelGGL((k_overlap_add_batch<4, T>), grid, dim3(256), 0, s, blocks, d, ch, out); break;
-      case 8: hipLaunchKernelGGL((k_overlap_add_batch<8, T>), grid, dim3(256), 0, s, blocks, d, ch, out); break;
-      default: hipLaunchKernelGGL((k_overlap_add_batch<0, T>), grid, dim3(256), 0, s, blocks, d, ch, out); break;
-    }
-  }
+    d2_by_channels(ch, [&](auto CH) {
+      hipLaunchKernelGGL((k_overlap_add<decltype(CH)::value, true, T>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o);
+    });
+  });
   return hipGetLastError();
 }
 }  // namespace
 
-hipError_t launch_overlap_add_batch(const float *blocks, const HopDesc *desc, uint32_t n_desc, uint32_t ch, float *out,
-                                    hipStream_t s) {
-  return overlap_add_batch_typed(blocks, desc, n_desc, ch, out, s);
+hipError_t launch_overlap_add(const float *blocks, int64_t blk_frame0, uint64_t n_frames, uint32_t ch,
+                              uint64_t hop_begin, uint64_t hop_end, float *out, hipStream_t s) {
+  return overlap_add_typed(blocks, blk_frame0, n_frames, ch, hop_begin, hop_end, out, s);
 }
 
-hipError_t launch_overlap_add_batch(const float *blocks, const HopDesc *desc, uint32_t n_desc, uint32_t ch, int16_t *out,
-                                    hipStream_t s) {
-  return overlap_add_batch_typed(blocks, desc, n_desc, ch, reinterpret_cast<short *>(out), s);
+hipError_t launch_overlap_add(const float *blocks, int64_t blk_frame0, uint64_t n_frames, uint32_t ch,
+                              uint64_t hop_begin, uint64_t hop_end, int16_t *out, hipStream_t s) {
+  return overlap_add_typed(blocks, blk_frame0, n_frames, ch, hop_begin, hop_end, reinterpret_cast<short *>(out), s);
 }
 
 hipError_t launch_stage_clips(const float *src, const StageClip *clips, uint32_t n_clips, uint32_t ch, bool planar,
@@ -2302,55 +2198,43 @@ hipError_t launch_stage_clips(const float *src, const StageClip *clips, uint32_t
   return hipGetLastError();
 }
 
-hipError_t launch_overlap_add_strided(const float *blocks, const HopDescStrided *desc, uint32_t n_desc, uint32_t ch, bool planar,
-                                      float *out, hipStream_t s) {
+namespace {
+template <typename T, typename D>
+hipError_t overlap_add_strided_typed(const float *blocks, const D *desc, uint32_t n_desc, uint32_t ch, bool planar, T *out,
+                                     hipStream_t s) {
   if (n_desc == 0) return hipSuccess;
-  if (!blocks || !desc || !out || ch == 0 || (reinterpret_cast<uintptr_t>(out) & 3u)) return hipErrorInvalidValue;
-  const unsigned per_hop = 1024u * ch;
-  const unsigned bx = (per_hop / 4u + 255u) / 256u;
-  for (uint32_t d0 = 0; d0 < n_desc; d0 += 32768) {  // slabs: blockIdx.y is 16 bits wide
-    const unsigned nd = n_desc - d0 < 32768 ? n_desc - d0 : 32768;
-    const HopDescStrided *d = desc + d0;
-    if (planar && ch > 1) {
-      hipLaunchKernelGGL(k_overlap_add_planar, dim3(ch, nd), dim3(256), 0, s, blocks, d, ch, out);
-      continue;
+  if (!blocks || !desc || !out || ch == 0 || (reinterpret_cast<uintptr_t>(out) & (sizeof(T) - 1u))) return hipErrorInvalidValue;
+  d2_slabs(n_desc, [&](uint64_t d0, unsigned nd) {
+    const D *d = desc + d0;
+    if constexpr (std::is_same<D, HopDescStrided>::value) {  // (a HopDesc has no planes)
+      if (planar && ch > 1) {
+        hipLaunchKernelGGL(k_overlap_add_planar, dim3(ch, nd), dim3(256), 0, s, blocks, d, ch, out);
+        return;
+      }
     }
-    const dim3 grid(bx, nd);
-    switch (ch) {
-      case 1: hipLaunchKernelGGL(k_overlap_add_strided<1>, grid, dim3(256), 0, s, blocks, d, ch, out); break;
-      case 2: hipLaunchKernelGGL(k_overlap_add_strided<2>, grid, dim3(256), 0, s, blocks, d, ch, out); break;
-      case 4: hipLaunchKernelGGL(k_overlap_add_strided<4>, grid, dim3(256), 0, s, blocks, d, ch, out); break;
-      case 8: hipLaunchKernelGGL(k_overlap_add_strided<8>, grid, dim3(256), 0, s, blocks, d, ch, out); break;
-      default: hipLaunchKernelGGL(k_overlap_add_strided<0>, grid, dim3(256), 0, s, blocks, d, ch, out); break;
-    }
-  }
+    // (a span that starts off a chunk boundary has one chunk more: the kernel's stride loop takes it)
+    const dim3 grid(d2_blocks_x(ch), nd);
+    d2_by_channels(ch, [&](auto CH) {
+      hipLaunchKernelGGL((k_overlap_add_strided<decltype(CH)::value, T, D>), grid, dim3(256), 0, s, blocks, d, ch, out);
+    });
+  });
   return hipGetLastError();
 }
+}  // namespace
 
-hipError_t launch_overlap_add_i16(const float *blocks, int64_t blk_frame0, uint64_t n_frames, uint32_t ch,
-                                  uint64_t hop_begin, uint64_t hop_end, int16_t *out, hipStream_t s) {
-  if (hop_end <= hop_begin) return hipSuccess;
-  const unsigned per_hop = 1024u * ch;
-  const unsigned bx = (per_hop / 4u + 255u) / 256u;
-  for (uint64_t h0 = hop_begin; h0 < hop_end; h0 += 32768) {  // slabs: blockIdx.y is 16 bits wide
-    const unsigned nh = static_cast<unsigned>(hop_end - h0 < 32768 ? hop_end - h0 : 32768);
-    const dim3 grid(bx, nh);
-    short *o = out + (h0 - hop_begin) * per_hop;
-    const long long f0 = static_cast<long long>(blk_frame0);
-    const unsigned long long nf = n_frames, hb = h0;
-    if (reinterpret_cast<uintptr_t>(o) & 7u) {
-      hipLaunchKernelGGL((k_overlap_add_i16<0, false>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o);
-      continue;
-    }
-    switch (ch) {
-      case 1: hipLaunchKernelGGL((k_overlap_add_i16<1, true>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o); break;
-      case 2: hipLaunchKernelGGL((k_overlap_add_i16<2, true>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o); break;
-      case 4: hipLaunchKernelGGL((k_overlap_add_i16<4, true>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o); break;
-      case 8: hipLaunchKernelGGL((k_overlap_add_i16<8, true>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o); break;
-      default: hipLaunchKernelGGL((k_overlap_add_i16<0, true>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o); break;
-    }
-  }
-  return hipGetLastError();
+hipError_t launch_overlap_add_strided(const float *blocks, const HopDescStrided *desc, uint32_t n_desc, uint32_t ch, bool planar,
+                                      float *out, hipStream_t s) {
+  return overlap_add_strided_typed(blocks, desc, n_desc, ch, planar, out, s);
+}
+
+hipError_t launch_overlap_add_strided(const float *blocks, const HopDesc *desc, uint32_t n_desc, uint32_t ch, float *out,
+                                      hipStream_t s) {
+  return overlap_add_strided_typed(blocks, desc, n_desc, ch, false, out, s);
+}
+
+hipError_t launch_overlap_add_strided(const float *blocks, const HopDesc *desc, uint32_t n_desc, uint32_t ch, int16_t *out,
+                                      hipStream_t s) {
+  return overlap_add_strided_typed(blocks, desc, n_desc, ch, false, reinterpret_cast<short *>(out), s);
 }
 
 namespace {

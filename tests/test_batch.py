@@ -334,6 +334,25 @@ def test_decode_small_batches(glc_amd, ch):
 
 
 @pytest.mark.parametrize("ch", CHANNELS)
+def test_decode_edge_batch(glc_amd, ch):
+    """The float output of the descriptor overlap-add on the batch that test_batch_int decodes to 16 bits: 39 streams
+    of 1-3 frames whose kept spans start at every residue of dst mod 4 with every residue of cnt mod 4."""
+    import test_batch_int as TI                  # it imports this module: not at the top
+    assert TI.all_sixteen(ch)
+    streams = TI.edge_streams(ch)
+    wants = [TI.oracle_pcm(g) for _, g in streams]
+    dec = glc_amd.Decoder(ch, SR)
+    rc, offsets, buf, lens = _decode_batch_raw(glc_amd, dec, [glc_amd.EncodedAudio.from_bytes(g) for _, g in streams], 4)
+    assert rc == 0, glc_amd.lib.glc_last_error(dec._h)
+    assert offsets == [0] + list(np.cumsum(lens)) and lens == [w.size for w in wants]
+    for i, ((name, _), want) in enumerate(zip(streams, wants)):
+        got = buf[offsets[i]:offsets[i + 1]]
+        bad = np.flatnonzero(bits(got) != bits(want))
+        assert bad.size == 0, f"{name}: {bad.size} samples differ, first at {bad[0]}"
+    assert (bits(buf[offsets[-1]:]) == DE.SENTINEL_BITS).all(), "written past offsets[n]"
+
+
+@pytest.mark.parametrize("ch", CHANNELS)
 def test_decode_state(glc_amd, ch):
     streams = [s for s in batch_streams(glc_amd, ch) if s[0] in ("config1-sine", "noise", "raw")]
     (_, a, want_a), (_, b, want_b), (_, c, want_c) = streams
