@@ -682,36 +682,16 @@ int glc_mdct_forward_device(glc_ctx *ctx, const float *d_pcm, uint64_t t0, uint6
 
 // Queue the compaction of `n_frames` records into `d_blob` (capacity checked by the caller) on
 // the context's stream; nothing is synchronised.
-// scratch of one compaction of M rows: loc[M] | blk[nblk] | blk_raw[nblk] | totals, each 256-byte aligned
-static size_t compact_scratch_bytes(uint64_t M) {
-  const size_t nblk = (static_cast<size_t>(M) + 1023) / 1024;
-  return align_up(static_cast<size_t>(M) * 4, 256) + 2 * align_up(nblk * 8, 256) + 256;
-}
-
 static int compact_launch(glc_ctx *ctx, const void *d_records, uint64_t n_frames, uint32_t ch, void *d_blob,
                           hipStream_t stream) {
-  DevBuf &pm = ctx->pack_meta;
-  const uint64_t M64 = n_frames * ch;
-  if (M64 > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, "compaction: frame range too long");
-  const uint32_t M = static_cast<uint32_t>(M64);
+  const uint64_t M = n_frames * ch;
+  if (M > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, "compaction: frame range too long");
   const glc::CompactLayout l = glc::compact_layout(ch, n_frames);
-  const size_t nblk = (static_cast<size_t>(M) + 1023) / 1024;
-  size_t off = 0;
-  auto place = [&](size_t bytes) {
-    size_t at = off;
-    off = align_up(off + bytes, 256);
-    return at;
-  };
-  const size_t o_loc = place(static_cast<size_t>(M) * 4), o_blk = place(nblk * 8), o_blkr = place(nblk * 8);
-  const size_t o_tot = place(16);
-  GLC_HIP(ctx, pm.reserve(std::max<size_t>(off, compact_scratch_bytes(M))));
-  uint8_t *mb = static_cast<uint8_t *>(pm.p);
+  GLC_HIP(ctx, ctx->pack_meta.reserve(glc::compact_scratch_bytes(M)));
   uint8_t *blob = static_cast<uint8_t *>(d_blob);
   GLC_HIP(ctx, hipMemsetAsync(blob, 0, l.o_pairs, stream));  // header + section padding: deterministic bytes
-  GLC_HIP(ctx, glc::launch_compact(static_cast<const uint8_t *>(d_records), M, ch, n_frames,
-                                   reinterpret_cast<uint32_t *>(mb + o_loc), reinterpret_cast<uint64_t *>(mb + o_blk),
-                                   reinterpret_cast<uint64_t *>(mb + o_blkr), reinterpret_cast<uint64_t *>(mb + o_tot),
-                                   blob, l.o_israw, l.o_scale, l.o_cnt, l.o_pairs, stream));
+  GLC_HIP(ctx, glc::launch_compact(static_cast<const uint8_t *>(d_records), static_cast<uint32_t>(M), ch, n_frames,
+                                   ctx->pack_meta.p, blob, l, nullptr, nullptr, stream));
   return GLC_OK;
 }
 
@@ -961,7 +941,7 @@ static int encode_pipeline(glc_ctx *ctx, const void *pcm_any, glc_pcm_format fmt
   // the per-round workspaces at their largest now: growing one mid-pipeline would free it under queued work
   GLC_HIP(ctx, ctx->coef.reserve(static_cast<size_t>(max_nf) * ch * glc::kHop * sizeof(float)));
   if (n_rounds > 1) GLC_HIP(ctx, ctx->coef_b.reserve(static_cast<size_t>(max_nf) * ch * glc::kHop * sizeof(float)));
-  GLC_HIP(ctx, ctx->pack_meta.reserve(compact_scratch_bytes(max_nf * ch)));
+  GLC_HIP(ctx, ctx->pack_meta.reserve(glc::compact_scratch_bytes(max_nf * ch)));
   if (!ctx->stream_b) GLC_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream_b, hipStreamNonBlocking));
   if (!ctx->copy_stream) GLC_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
   if (!ctx->down_stream) GLC_HIP(ctx, hipStreamCreateWithFlags(&ctx->down_stream, hipStreamNonBlocking));
@@ -1204,20 +1184,15 @@ namespace {
 // The blob of a batch round (glc_encode_batch): header | clip directory u64[2 n_clips] |
 // raw flags | scales | counts | pairs | raw planes, over the n_real REAL frames of the round's clips (M rows).
 struct BatchBlobLayout {
+  glc::CompactLayout at;  // the sections, behind a directory of dir_bytes
   uint64_t n_real, M, V;  // frames of the clips / their rows / records of the virtual stream (a junk one behind every clip)
-  uint64_t o_dir, o_israw, o_scale, o_cnt, o_pairs, bound;
+  uint64_t o_dir, dir_bytes;
 };
 BatchBlobLayout batch_blob_layout(uint32_t ch, const uint64_t *clip_frames, uint64_t n_clips) {
-  BatchBlobLayout l{};
-  for (uint64_t i = 0; i < n_clips; ++i) l.n_real += clip_frames[i], l.V += clip_frames[i] + 1;
-  l.M = l.n_real * ch;
-  l.o_dir = sizeof(glc::CompactHeader);
-  l.o_israw = l.o_dir + glc::align64(16 * n_clips);
-  l.o_scale = l.o_israw + glc::align64(l.n_real);
-  l.o_cnt = l.o_scale + glc::align64(4 * l.M);
-  l.o_pairs = l.o_cnt + glc::align64(4 * l.M);
-  l.bound = l.o_pairs + 4096ull * l.M + 64ull;
-  return l;
+  uint64_t n_real = 0, V = 0;
+  for (uint64_t i = 0; i < n_clips; ++i) n_real += clip_frames[i], V += clip_frames[i] + 1;
+  return BatchBlobLayout{glc::compact_layout(ch, n_real, 16 * n_clips), n_real, n_real * ch, V, sizeof(glc::CompactHeader),
+                         16 * n_clips};
 }
 
 // Queues the segment-aware compaction of a batch round on `st`: clip i of clip_frames[i] frames owns the records
@@ -1228,10 +1203,9 @@ BatchBlobLayout batch_blob_layout(uint32_t ch, const uint64_t *clip_frames, uint
 int compact_batch_launch(glc_ctx *ctx, const void *d_records, const uint64_t *clip_frames, uint64_t n_clips, uint32_t ch,
                          const BatchBlobLayout &l, uint8_t *d_blob, hipStream_t st) {
   if (l.M > 0xFFFFFFFFull || l.V > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, "batch compaction: frame range too long");
-  const size_t scratch = compact_scratch_bytes(l.M), o_fmap_h = align_up(l.o_pairs, 256);
+  const size_t scratch = glc::compact_scratch_bytes(l.M), o_fmap_h = align_up(l.at.o_pairs, 256);
   GLC_HIP(ctx, ctx->pack_meta.reserve(scratch + align_up(l.n_real * sizeof(glc::FrameMap), 256)));
   GLC_HIP(ctx, ctx->host_stage.reserve(o_fmap_h + l.n_real * sizeof(glc::FrameMap)));
-  uint8_t *mb = static_cast<uint8_t *>(ctx->pack_meta.p);
   glc::FrameMap *fmap = reinterpret_cast<glc::FrameMap *>(static_cast<uint8_t *>(ctx->host_stage.p) + o_fmap_h);
   uint64_t slot = 0, real = 0;
   for (uint64_t i = 0; i < n_clips; ++i) {
@@ -1240,18 +1214,11 @@ int compact_batch_launch(glc_ctx *ctx, const void *d_records, const uint64_t *cl
     slot += clip_frames[i] + 1;
     real += clip_frames[i];
   }
-  glc::FrameMap *d_fmap = reinterpret_cast<glc::FrameMap *>(mb + scratch);
+  glc::FrameMap *d_fmap = reinterpret_cast<glc::FrameMap *>(static_cast<uint8_t *>(ctx->pack_meta.p) + scratch);
   GLC_HIP(ctx, hipMemcpyAsync(d_fmap, fmap, l.n_real * sizeof(glc::FrameMap), hipMemcpyHostToDevice, st));
-  // the scratch of compact_launch, the frame map behind it
-  const size_t nblk = (static_cast<size_t>(l.M) + 1023) / 1024;
-  const size_t o_loc = 0, o_blk = align_up(static_cast<size_t>(l.M) * 4, 256), o_blkr = o_blk + align_up(nblk * 8, 256),
-               o_tot = o_blkr + align_up(nblk * 8, 256);
-  GLC_HIP(ctx, hipMemsetAsync(d_blob, 0, l.o_pairs, st));  // header + directory + section padding: deterministic bytes
-  GLC_HIP(ctx, glc::launch_compact_batch(static_cast<const uint8_t *>(d_records), static_cast<uint32_t>(l.M), ch, l.n_real, d_fmap,
-                                         reinterpret_cast<uint64_t *>(d_blob + l.o_dir), reinterpret_cast<uint32_t *>(mb + o_loc),
-                                         reinterpret_cast<uint64_t *>(mb + o_blk), reinterpret_cast<uint64_t *>(mb + o_blkr),
-                                         reinterpret_cast<uint64_t *>(mb + o_tot), d_blob, l.o_israw, l.o_scale, l.o_cnt,
-                                         l.o_pairs, st));
+  GLC_HIP(ctx, hipMemsetAsync(d_blob, 0, l.at.o_pairs, st));  // header + directory + section padding: deterministic bytes
+  GLC_HIP(ctx, glc::launch_compact(static_cast<const uint8_t *>(d_records), static_cast<uint32_t>(l.M), ch, l.n_real, ctx->pack_meta.p,
+                                   d_blob, l.at, d_fmap, reinterpret_cast<uint64_t *>(d_blob + l.o_dir), st));
   return GLC_OK;
 }
 
@@ -1281,11 +1248,11 @@ int encode_batch_round(glc_ctx *ctx, const std::vector<BatchClip> &clips, const 
   std::vector<uint64_t> clip_frames(n);
   for (uint64_t i = 0; i < n; ++i) clip_frames[i] = clips[i].plan.n_frames;
   const BatchBlobLayout bl = batch_blob_layout(ch, clip_frames.data(), n);  // the round's blob
-  const uint64_t V = bl.V, n_real = bl.n_real, M = bl.M;  // frames of the virtual stream / of the clips; rows of the clips
+  const uint64_t V = bl.V, n_real = bl.n_real;  // frames of the virtual stream / of the clips
   const uint64_t T = V * glc::kHop, n_virtual = T * ch;
   const uint64_t rec = glc::record_bytes(ch);
-  const uint64_t o_dir = bl.o_dir, o_israw = bl.o_israw, o_scale = bl.o_scale, o_cnt = bl.o_cnt, o_pairs = bl.o_pairs,
-                 bound = bl.bound;
+  const uint64_t o_dir = bl.o_dir, o_israw = bl.at.o_israw, o_scale = bl.at.o_scale, o_cnt = bl.at.o_cnt, o_pairs = bl.at.o_pairs,
+                 bound = bl.at.bound;
   GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // earlier work may still read the staging buffers
   GLC_HIP(ctx, ctx->pcm.reserve(static_cast<size_t>(n_virtual) * sizeof(float)));
   if (is_int) GLC_HIP(ctx, ctx->pcm_int.reserve(static_cast<size_t>(n_virtual) * elem));
@@ -1354,10 +1321,9 @@ int encode_batch_round(glc_ctx *ctx, const std::vector<BatchClip> &clips, const 
   GLC_HIP(ctx, hipStreamSynchronize(st));
   glc::CompactHeader h;
   std::memcpy(&h, hm, sizeof h);
-  const uint64_t raw_off = glc::align64(o_pairs + 4 * h.n_pairs);
-  if (h.magic != glc::kCompactMagic || h.channels != ch || h.n_frames != n_real || h.n_pairs > M * glc::kHop ||
-      h.n_raw_rows > M || h.bytes != raw_off + h.n_raw_rows * glc::kFrame * 2 || h.bytes > bound)
+  if (glc::compact_header_fault(h, ch, n_real, bl.dir_bytes, /*exact=*/true, bound) != glc::HeaderFault::kNone)
     return fail(ctx, GLC_EHIP, "glc_encode_batch: the device wrote an inconsistent compact header");
+  const uint64_t raw_off = glc::compact_raw_offset(bl.at, h.n_pairs);
   // download 2: the payload of all clips in one copy, cut per clip on the host below
   const uint64_t payload = h.bytes - o_pairs;
   GLC_HIP(ctx, ctx->batch_stage.reserve(std::max<uint64_t>(payload, 64)));
@@ -3124,7 +3090,7 @@ int glc_debug_compact_batch_device(glc_ctx *ctx, const void *d_records, const ui
   if (reinterpret_cast<uintptr_t>(d_records) % 8 != 0 || reinterpret_cast<uintptr_t>(d_blob) % 8 != 0)
     return fail(ctx, GLC_EINVAL, "glc_debug_compact_batch_device: d_records and d_blob must be 8-byte aligned");
   const BatchBlobLayout l = batch_blob_layout(channels, clip_frames, n_clips);
-  if (cap < l.bound) return fail(ctx, GLC_EINVAL, "glc_debug_compact_batch_device: blob buffer too small");
+  if (cap < l.at.bound) return fail(ctx, GLC_EINVAL, "glc_debug_compact_batch_device: blob buffer too small");
   DeviceGuard guard(ctx->device);
   GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // earlier work may still read the pinned frame map
   const int rc = compact_batch_launch(ctx, d_records, clip_frames, n_clips, channels, l, static_cast<uint8_t *>(d_blob), ctx->stream);

@@ -1,4 +1,4 @@
-// glc_common.h — shared host-side definitions for the MI355X codec hot path.
+// glc_common.h — definitions shared by the host sources and, where marked GLC_HD, the device code of the MI355X codec hot path.
 // Constants mirror /root/reference/src/codec.rs:15-29.
 #pragma once
 #include <cstdint>
@@ -92,15 +92,23 @@ struct CompactHeader {
   uint64_t reserved[3];
 };
 static_assert(sizeof(CompactHeader) == 64, "compact header is 64 bytes");
-inline uint64_t align64(uint64_t v) { return (v + 63ull) & ~63ull; }
+// The layout and the header rule below are the only statement of either: the host drivers and the device
+// kernels (P1-P3 write a blob, R2 reads one) call the same functions.
+#if defined(__HIP__) || defined(__HIPCC__)
+#define GLC_HD __host__ __device__
+#else
+#define GLC_HD
+#endif
+GLC_HD inline uint64_t align64(uint64_t v) { return (v + 63ull) & ~63ull; }
 struct CompactLayout {
   uint64_t o_israw, o_scale, o_cnt, o_pairs;  // byte offsets of the fixed sections
   uint64_t bound;                             // worst-case blob size for this range
 };
-inline CompactLayout compact_layout(uint32_t ch, uint64_t n_frames) {
-  const uint64_t M = n_frames * ch;
+// The sections of a blob of n_frames frames that are M = n_frames * ch rows.  dir_bytes: a directory between the
+// header and the raw flags (the blob of a batch round keeps its clips' there)
+GLC_HD inline CompactLayout compact_sections(uint64_t n_frames, uint64_t M, uint64_t dir_bytes = 0) {
   CompactLayout l;
-  l.o_israw = sizeof(CompactHeader);
+  l.o_israw = sizeof(CompactHeader) + align64(dir_bytes);
   l.o_scale = l.o_israw + align64(n_frames);
   l.o_cnt = l.o_scale + align64(4 * M);
   l.o_pairs = l.o_cnt + align64(4 * M);
@@ -108,11 +116,26 @@ inline CompactLayout compact_layout(uint32_t ch, uint64_t n_frames) {
   l.bound = l.o_pairs + 4096ull * M + 64ull;
   return l;
 }
-inline uint64_t compact_raw_offset(const CompactLayout &l, uint64_t n_pairs) { return align64(l.o_pairs + 4 * n_pairs); }
+GLC_HD inline CompactLayout compact_layout(uint32_t ch, uint64_t n_frames, uint64_t dir_bytes = 0) {
+  return compact_sections(n_frames, n_frames * ch, dir_bytes);
+}
+GLC_HD inline uint64_t compact_raw_offset(const CompactLayout &l, uint64_t n_pairs) { return align64(l.o_pairs + 4 * n_pairs); }
 
 // A compact header from the device or a caller: magic, channel count, a frame count of at most (or,
-// `exact`, exactly) `n_frames`, pair and raw-row counts its rows can hold, and a `bytes` that is exactly
-// its sections and fits the `avail` bytes the blob arrived in.  nullptr, or what is wrong.
+// `exact`, exactly) `n_frames`, pair and raw-row counts its rows can hold (a raw frame is raw in every channel),
+// and a `bytes` that is exactly its sections and fits the `avail` bytes the blob arrived in.  The first rule
+// that fails; the counts are bounded before the sizes are formed from them, so nothing wraps.
+enum class HeaderFault { kNone, kIdentity, kCounts, kBytes };
+GLC_HD inline HeaderFault compact_header_fault(const CompactHeader &h, uint32_t ch, uint64_t n_frames, uint64_t dir_bytes,
+                                               bool exact, uint64_t avail) {
+  if (h.magic != kCompactMagic || h.channels != ch || h.n_frames > n_frames || (exact && h.n_frames != n_frames))
+    return HeaderFault::kIdentity;
+  const uint64_t M = h.n_frames * ch;
+  if (h.n_pairs > M * kHop || h.n_raw_rows > M || h.n_raw_rows % ch != 0) return HeaderFault::kCounts;
+  const uint64_t need = compact_raw_offset(compact_sections(h.n_frames, M, dir_bytes), h.n_pairs) + h.n_raw_rows * kFrame * 2;
+  return h.bytes != need || avail < need ? HeaderFault::kBytes : HeaderFault::kNone;
+}
+// ... as text: nullptr, or what is wrong
 const char *compact_header_error(const CompactHeader &h, uint32_t ch, uint64_t n_frames, bool exact, uint64_t avail);
 
 void set_global_error(const std::string &msg);

@@ -91,13 +91,13 @@ void init_frames(glc_frames *F, uint32_t sample_rate, uint64_t n_samples, uint16
 }
 
 const char *compact_header_error(const CompactHeader &h, uint32_t ch, uint64_t n_frames, bool exact, uint64_t avail) {
-  if (h.magic != kCompactMagic || h.channels != ch || h.n_frames > n_frames || (exact && h.n_frames != n_frames))
-    return "bad magic, channel count or frame count";
-  const uint64_t M = h.n_frames * ch;
-  if (h.n_pairs > M * kHop || h.n_raw_rows > M || h.n_raw_rows % ch != 0) return "corrupt blob (pair / raw-row counts)";
-  const uint64_t need = compact_raw_offset(compact_layout(ch, h.n_frames), h.n_pairs) + h.n_raw_rows * kFrame * 2;
-  if (h.bytes != need || avail < need) return "blob size does not match its header";
-  return nullptr;
+  switch (compact_header_fault(h, ch, n_frames, 0, exact, avail)) {
+    case HeaderFault::kNone: return nullptr;
+    case HeaderFault::kIdentity: return "bad magic, channel count or frame count";
+    case HeaderFault::kCounts: return "corrupt blob (pair / raw-row counts)";
+    case HeaderFault::kBytes: break;
+  }
+  return "blob size does not match its header";
 }
 
 // Index vectors of EncodedAudio for the frames of ONE compact blob whose payload (pairs, raw planes)

@@ -4,6 +4,8 @@
 
 #include <cstdint>
 
+#include "glc_common.h"
+
 namespace glc {
 
 // Device-resident constant tables of one context.
@@ -58,28 +60,24 @@ hipError_t launch_encode_screened(const DeviceTables &t, const ScreenShape &sh, 
 hipError_t launch_decide_raw(const DeviceTables &t, const PcmView &pcm, uint64_t frame_begin,
                              uint32_t n_frames, uint8_t *records, hipStream_t s);
 
-// P1-P3: compact blob (glc_common.h CompactLayout) of M = n_frames*ch rows of records, written to
-// `blob` on the device: header, per-frame raw flags, per-row scale and pair count, the ascending
+// P1-P3: compact blob of M = n_frames*ch rows of records, written to `blob` on the device at the sections of
+// `l` (glc_common.h compact_layout): header, per-frame raw flags, per-row scale and pair count, the ascending
 // (u16 idx | i16 q << 16) pairs of every compressed row back to back, then the 2048-sample planes of
-// raw-frame rows.  loc[M], blk[ceil(M/1024)], blk_raw[same], totals[2] are scratch.  The alignment
-// padding of the fixed sections is NOT written here (the caller zeroes [0, o_pairs) first).
-hipError_t launch_compact(const uint8_t *records, uint32_t M, uint32_t ch, uint64_t n_frames, uint32_t *loc,
-                          uint64_t *blk, uint64_t *blk_raw, uint64_t *totals, uint8_t *blob, uint64_t o_israw,
-                          uint64_t o_scale, uint64_t o_cnt, uint64_t o_pairs, hipStream_t s);
-
-// P1-P3 over the real frames of a round of glc_encode_batch: row m is channel m % ch of real frame
-// m / ch, whose record is number fmap[m / ch].slot among `records` (the virtual stream's frames, junk
-// ones included - those are in no map and nothing of them reaches the blob).  Same sections at the
-// caller's offsets as launch_compact; dir[2 * i], dir[2 * i + 1]: pairs and raw rows the blob holds in
-// front of clip i, for every clip named in a FrameMap::clip.
+// raw-frame rows.  `scratch`: compact_scratch_bytes(M) bytes, 256-byte aligned, nothing in it needs
+// initialising.  The alignment padding of the fixed sections is NOT written here (the caller zeroes
+// [0, l.o_pairs) first).
+// frame_map / clip_dir (both or neither; a round of glc_encode_batch): row m is channel m % ch of real frame
+// m / ch, whose record is number frame_map[m / ch].slot among `records` (the virtual stream's frames, junk
+// ones included - those are in no map and nothing of them reaches the blob).  clip_dir[2 * i],
+// clip_dir[2 * i + 1]: pairs and raw rows the blob holds in front of clip i, for every clip named in a
+// FrameMap::clip.
 struct FrameMap {
   uint32_t slot;  // record index of this real frame
   uint32_t clip;  // the clip whose first frame this is, or 0xFFFFFFFF
 };
-hipError_t launch_compact_batch(const uint8_t *records, uint32_t M, uint32_t ch, uint64_t n_frames, const FrameMap *fmap,
-                                uint64_t *dir, uint32_t *loc, uint64_t *blk, uint64_t *blk_raw, uint64_t *totals,
-                                uint8_t *blob, uint64_t o_israw, uint64_t o_scale, uint64_t o_cnt, uint64_t o_pairs,
-                                hipStream_t s);
+uint64_t compact_scratch_bytes(uint64_t M);
+hipError_t launch_compact(const uint8_t *records, uint32_t M, uint32_t ch, uint64_t n_frames, void *scratch, uint8_t *blob,
+                          const CompactLayout &l, const FrameMap *frame_map, uint64_t *clip_dir, hipStream_t s);
 
 // D1: sparse dequant + inverse MDCT + window -> blocks[row][2048].
 //   pairs: packed (u16 idx | i16 q << 16), canonical (ascending, unique, idx < 1024)
@@ -121,10 +119,11 @@ hipError_t launch_rows_from_records_batch(const uint8_t *records, uint32_t M, ui
 // lowest blob address, every blob 64-byte aligned) from which row_begin counts in u32 and row_raw in i16, so
 // the lists and raw planes are read where they lie inside the blobs.  Blob i of `n_blobs` is described by
 // CompactBlob {address, capacity in bytes the caller vouches for, first row, rows}; first_row ascends from 0, rows
-// = frames * ch of the stream the host expects, and their sum is M.  `dir` is that table on the device, or
+// = frames * ch of the stream the host expects (whole frames: an M that is no multiple of ch is refused), and their
+// sum is M.  `dir` is that table on the device, or
 // null with n_blobs == 1, when `one` travels as a kernel argument.  status[n_blobs] (device, kept by the caller
 // for as long as it wants to read it; written here, no need to zero it): what the checks found.
-//   header (k_r2_headers, one thread per blob): compact_header_error's check - magic, ch, exactly rows / ch frames,
+//   header (k_r2_headers, one thread per blob): glc_common.h compact_header_fault - magic, ch, exactly rows / ch frames,
 //   n_pairs <= 1024 rows, n_raw_rows <= rows and a multiple of ch, bytes == the sum of the sections <= capacity.
 //   A blob that fails is read no further: its rows are empty lists of scale 0.0f with no raw plane.
 //   scans (k_r2_scan_rows, k_r2_scan_blocks): row_begin = exclusive 64-bit sum of cnt over the blob's rows in

@@ -1114,13 +1114,97 @@ __global__ __launch_bounds__(256) void k_pcm_widen(const S *__restrict__ in, flo
 }
 
 // ------------------------------------------------------------------------------------------
+// The two-level exclusive scan of P1 / P2 and of R2: how many pairs, and how many rows of raw frames, lie in
+// front of row m.  A row contributes ONE packed word - its pair count in the low RAW_SHIFT bits, or
+// 1 << RAW_SHIFT for a row of a raw frame (the high 11 bits: fewer than 1024 such rows in front of a row of its
+// block) - so one scan carries both counts.
+//   scan_rows_1024   a workgroup of 256 threads scans 1024 rows: 4 per thread, Hillis-Steele over the 256 thread
+//                    sums in LDS; loc[m] = the sum in front of row m inside its block, and the block's two
+//                    sums go to blk / blk_raw.  count(m) is the word of row m < M (and whatever per-row
+//                    stores its kernel wants made on the way).
+//   scan_block_sums  ONE workgroup of 1024 threads: blk and blk_raw become their own exclusive scans, in
+//                    chunks of 1024 with a carry; sums[] = the two totals.  No workgroup waits for another.
+//   rows_before      (loc word, blk, blk_raw, m) -> {pairs, rows of raw frames} in front of row m
+// P1 scans unsigned words (<= 1024 * 1024 pairs in a block: 21 bits; a wider word would double loc), R2 unsigned
+// long long ones (cnt is what a blob claims: <= 1024 * (2^32 - 1), 53 bits).
+// ------------------------------------------------------------------------------------------
+constexpr int kP1RawShift = 21, kR2RawShift = 53;
+
+template <typename W, int RAW_SHIFT, typename F>
+__device__ __forceinline__ void scan_rows_1024(F count, unsigned M, W *__restrict__ loc, unsigned long long *__restrict__ blk,
+                                               unsigned long long *__restrict__ blk_raw) {
+  static_assert(RAW_SHIFT + 11 == 8 * sizeof(W), "pairs | 11 bits of raw rows fill the word");
+  __shared__ W s_part[256];
+  const unsigned base = blockIdx.x * 1024u + threadIdx.x * 4u;
+  W v[4], sum = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const W n = base + j < M ? count(base + j) : W(0);
+    v[j] = sum;  // exclusive within the thread
+    sum += n;
+  }
+  s_part[threadIdx.x] = sum;
+  __syncthreads();
+  for (int off = 1; off < 256; off <<= 1) {  // Hillis-Steele inclusive scan of the 256 thread sums
+    const W t = threadIdx.x >= static_cast<unsigned>(off) ? s_part[threadIdx.x - off] : W(0);
+    __syncthreads();
+    s_part[threadIdx.x] += t;
+    __syncthreads();
+  }
+  const W before = threadIdx.x ? s_part[threadIdx.x - 1] : W(0);
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (base + j < M) loc[base + j] = before + v[j];
+  if (threadIdx.x == 255) {
+    blk[blockIdx.x] = s_part[255] & ((W(1) << RAW_SHIFT) - 1);
+    blk_raw[blockIdx.x] = s_part[255] >> RAW_SHIFT;
+  }
+}
+
+__device__ __forceinline__ void scan_block_sums(unsigned long long *__restrict__ blk, unsigned long long *__restrict__ blk_raw,
+                                                unsigned n, unsigned long long *s /* LDS, [1024] */,
+                                                unsigned long long sums[2]) {
+#pragma unroll 1
+  for (int which = 0; which < 2; ++which) {
+    unsigned long long *v = which ? blk_raw : blk;
+    unsigned long long carry = 0;
+    for (unsigned b0 = 0; b0 < n; b0 += 1024) {
+      const unsigned i = b0 + threadIdx.x;
+      const unsigned long long mine = i < n ? v[i] : 0ull;
+      s[threadIdx.x] = mine;
+      __syncthreads();
+      for (int off = 1; off < 1024; off <<= 1) {
+        const unsigned long long t = threadIdx.x >= static_cast<unsigned>(off) ? s[threadIdx.x - off] : 0ull;
+        __syncthreads();
+        s[threadIdx.x] += t;
+        __syncthreads();
+      }
+      if (i < n) v[i] = carry + s[threadIdx.x] - mine;  // exclusive
+      const unsigned long long chunk_total = s[1023];
+      __syncthreads();
+      carry += chunk_total;
+    }
+    sums[which] = carry;
+  }
+}
+
+struct RowsBefore {
+  unsigned long long pairs, raw;
+};
+template <int RAW_SHIFT, typename W>
+__device__ __forceinline__ RowsBefore rows_before(W l, const unsigned long long *__restrict__ blk,
+                                                  const unsigned long long *__restrict__ blk_raw, unsigned long long m) {
+  return {blk[m >> 10] + (l & ((W(1) << RAW_SHIFT) - 1)), blk_raw[m >> 10] + (l >> RAW_SHIFT)};
+}
+
+// ------------------------------------------------------------------------------------------
 // P1-P3: device-side compaction of frame records into the compact blob (glc_common.h
-// CompactLayout), so that the host boundary and the multi-GPU gather move (u16 idx, i16 q) pairs
-// instead of dense 1024-bin rows.
-//   P1  per row: pairs it contributes (nnz, 0 for rows of raw frames); exclusive scan inside
-//       blocks of 1024 rows; per-row scale and count, per-frame raw flag into the blob
-//   P2  one workgroup: exclusive scans of the block totals (pairs, raw rows), then the blob header
-//       they determine and the zeroed alignment gap in front of the raw section
+// CompactLayout `l`: every kernel takes the blob and its layout, none an offset of its own), so that the host
+// boundary and the multi-GPU gather move (u16 idx, i16 q) pairs instead of dense 1024-bin rows.
+//   P1  scan_rows_1024 over the pairs a row contributes (nnz, 0 for rows of raw frames); on the way the
+//       per-row scale and count and the per-frame raw flag into the blob
+//   P2  scan_block_sums, then the blob header the totals determine and the zeroed alignment gap in front
+//       of the raw section
 //   P3  one wave per row: ballot + popcount prefix keeps ascending k (src/codec.rs:303-306);
 //       planes of raw-frame rows go to the raw section, which starts behind the pairs
 // ------------------------------------------------------------------------------------------
@@ -1133,90 +1217,42 @@ __global__ __launch_bounds__(256) void k_pack_scan_rows(const unsigned char *__r
                                                          unsigned ch, unsigned long long rec_bytes,
                                                          unsigned *__restrict__ loc,
                                                          unsigned long long *__restrict__ blk,
-                                                         unsigned long long *__restrict__ blk_raw,
-                                                         float *__restrict__ scales, unsigned *__restrict__ cnt,
-                                                         unsigned char *__restrict__ is_raw,
+                                                         unsigned long long *__restrict__ blk_raw, CompactLayout l,
+                                                         unsigned char *__restrict__ blob,
                                                          const uint2 *__restrict__ fmap) {
-  // one 32-bit word scans both counts: low 21 bits = pairs (<= 1024*1024 per block), high 11 =
-  // rows of raw frames (<= 1024 per block)
-  __shared__ unsigned s_part[256];
-  const unsigned base = blockIdx.x * 1024u + threadIdx.x * 4u;
-  unsigned v[4], sum = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const unsigned m = base + j;
-    unsigned n = 0;
-    if (m < M) {
-      const unsigned frame = m / ch, c = m % ch;
-      const unsigned slot = SEG ? fmap[frame].x : frame;
-      const unsigned char *rec = records + static_cast<size_t>(slot) * rec_bytes;
-      const unsigned raw = *reinterpret_cast<const unsigned *>(rec);
-      const unsigned nnz = min(*reinterpret_cast<const unsigned *>(rec + 8 + 8 * c + 4), static_cast<unsigned>(kHopI));
-      n = raw ? (1u << 21) : nnz;
-      scales[m] = *reinterpret_cast<const float *>(rec + 8 + 8 * c);
-      cnt[m] = raw ? 0u : nnz;
-      if (c == 0) is_raw[frame] = raw ? 1 : 0;
-    }
-    v[j] = sum;  // exclusive within the thread
-    sum += n;
-  }
-  s_part[threadIdx.x] = sum;
-  __syncthreads();
-  for (int off = 1; off < 256; off <<= 1) {  // Hillis-Steele inclusive scan of the 256 thread sums
-    unsigned t = threadIdx.x >= static_cast<unsigned>(off) ? s_part[threadIdx.x - off] : 0u;
-    __syncthreads();
-    s_part[threadIdx.x] += t;
-    __syncthreads();
-  }
-  const unsigned before = threadIdx.x ? s_part[threadIdx.x - 1] : 0u;
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (base + j < M) loc[base + j] = before + v[j];
-  if (threadIdx.x == 255) {
-    blk[blockIdx.x] = s_part[255] & 0x1FFFFFu;
-    blk_raw[blockIdx.x] = s_part[255] >> 21;
-  }
+  float *scales = reinterpret_cast<float *>(blob + l.o_scale);
+  unsigned *cnt = reinterpret_cast<unsigned *>(blob + l.o_cnt);
+  unsigned char *is_raw = blob + l.o_israw;
+  scan_rows_1024<unsigned, kP1RawShift>(
+      [&](unsigned m) {
+        const unsigned frame = m / ch, c = m % ch;
+        const unsigned slot = SEG ? fmap[frame].x : frame;
+        const unsigned char *rec = records + static_cast<size_t>(slot) * rec_bytes;
+        const unsigned raw = *reinterpret_cast<const unsigned *>(rec);
+        const unsigned nnz = min(*reinterpret_cast<const unsigned *>(rec + 8 + 8 * c + 4), static_cast<unsigned>(kHopI));
+        scales[m] = *reinterpret_cast<const float *>(rec + 8 + 8 * c);
+        cnt[m] = raw ? 0u : nnz;
+        if (c == 0) is_raw[frame] = raw ? 1 : 0;
+        return raw ? (1u << kP1RawShift) : nnz;
+      },
+      M, loc, blk, blk_raw);
 }
 
-// One workgroup: exclusive scans of the per-block pair counts and raw-row counts, their totals, and
-// the blob header they determine (three dependent launches of a few microseconds each before).
 __global__ __launch_bounds__(1024) void k_pack_scan_blocks(unsigned long long *__restrict__ blk,
                                                             unsigned long long *__restrict__ blk_raw, unsigned n,
                                                             unsigned long long *__restrict__ totals, unsigned ch,
-                                                            unsigned long long n_frames, unsigned long long o_pairs,
+                                                            unsigned long long n_frames, CompactLayout l,
                                                             unsigned char *__restrict__ blob) {
   __shared__ unsigned long long s[1024];
   unsigned long long sums[2];
-#pragma unroll 1
-  for (int which = 0; which < 2; ++which) {
-    unsigned long long *v = which ? blk_raw : blk;
-    unsigned long long carry = 0;
-    for (unsigned b0 = 0; b0 < n; b0 += 1024) {
-      const unsigned i = b0 + threadIdx.x;
-      const unsigned long long mine = i < n ? v[i] : 0ull;
-      s[threadIdx.x] = mine;
-      __syncthreads();
-      for (int off = 1; off < 1024; off <<= 1) {
-        unsigned long long t = threadIdx.x >= static_cast<unsigned>(off) ? s[threadIdx.x - off] : 0ull;
-        __syncthreads();
-        s[threadIdx.x] += t;
-        __syncthreads();
-      }
-      if (i < n) v[i] = carry + s[threadIdx.x] - mine;  // exclusive
-      const unsigned long long chunk_total = s[1023];
-      __syncthreads();
-      carry += chunk_total;
-    }
-    sums[which] = carry;
-  }
+  scan_block_sums(blk, blk_raw, n, s, sums);
   const unsigned long long n_pairs = sums[0], n_raw_rows = sums[1];
-  const unsigned long long pairs_end = o_pairs + 4ull * n_pairs;
-  const unsigned long long raw_off = (pairs_end + 63ull) & ~63ull;
+  const unsigned long long pairs_end = l.o_pairs + 4ull * n_pairs, raw_off = compact_raw_offset(l, n_pairs);
   if (threadIdx.x == 0) {
     totals[0] = n_pairs;
     totals[1] = n_raw_rows;
     unsigned long long *h = reinterpret_cast<unsigned long long *>(blob);
-    h[0] = 0x42434C47ull | (static_cast<unsigned long long>(ch) << 32);  // magic, channels
+    h[0] = kCompactMagic | (static_cast<unsigned long long>(ch) << 32);  // magic, channels
     h[1] = n_frames;
     h[2] = n_pairs;
     h[3] = n_raw_rows;
@@ -1232,38 +1268,34 @@ __global__ __launch_bounds__(256) void k_pack_rows(const unsigned char *__restri
                                                     unsigned long long hdr_bytes, const unsigned *__restrict__ loc,
                                                     const unsigned long long *__restrict__ blk,
                                                     const unsigned long long *__restrict__ blk_raw,
-                                                    const unsigned long long *__restrict__ totals,
-                                                    const unsigned *__restrict__ cnt, unsigned long long o_pairs,
+                                                    const unsigned long long *__restrict__ totals, CompactLayout l,
                                                     unsigned char *__restrict__ blob, const uint2 *__restrict__ fmap,
                                                     unsigned long long *__restrict__ dir) {
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const unsigned m = blockIdx.x * 4 + w;
   if (m >= M) return;
-  const unsigned l = loc[m];
-  const unsigned long long off = blk[m >> 10] + (l & 0x1FFFFFu);
+  const RowsBefore at = rows_before<kP1RawShift>(loc[m], blk, blk_raw, m);
   const unsigned frame = m / ch, c = m % ch;
   unsigned slot = frame;
   if constexpr (SEG) {
     const uint2 fm = fmap[frame];
     slot = fm.x;
     if (c == 0 && lane == 0 && fm.y != ~0u) {  // a clip starts here: what the round holds in front of it
-      dir[2ull * fm.y] = off;
-      dir[2ull * fm.y + 1] = blk_raw[m >> 10] + (l >> 21);
+      dir[2ull * fm.y] = at.pairs;
+      dir[2ull * fm.y + 1] = at.raw;
     }
   }
   const unsigned char *rec = records + static_cast<size_t>(slot) * rec_bytes;
   const short *qrow = reinterpret_cast<const short *>(rec + hdr_bytes) + static_cast<size_t>(c) * kFrameI;
   if (*reinterpret_cast<const unsigned *>(rec)) {
     // row of a raw frame: its 2048-sample plane goes to the raw section (planar order == row order, Q1)
-    const unsigned long long raw_off = (o_pairs + 4ull * totals[0] + 63ull) & ~63ull;
-    const unsigned long long rrow = blk_raw[m >> 10] + (l >> 21);
     const short4 *src = reinterpret_cast<const short4 *>(qrow);
-    short4 *dst = reinterpret_cast<short4 *>(blob + raw_off + rrow * (kFrameI * 2ull));
+    short4 *dst = reinterpret_cast<short4 *>(blob + compact_raw_offset(l, totals[0]) + at.raw * (kFrameI * 2ull));
     for (int i = lane; i < kFrameI / 4; i += 64) dst[i] = src[i];
     return;
   }
-  unsigned *dst = reinterpret_cast<unsigned *>(blob + o_pairs) + off;
-  const unsigned room = cnt[m];  // a record whose nnz field disagrees with its row cannot write past its slot
+  unsigned *dst = reinterpret_cast<unsigned *>(blob + l.o_pairs) + at.pairs;
+  const unsigned room = reinterpret_cast<const unsigned *>(blob + l.o_cnt)[m];  // P1's: a record whose nnz field disagrees with its row cannot write past its slot
   unsigned done = 0;
   for (int k0 = 0; k0 < kHopI; k0 += 64) {
     const short q = qrow[k0 + lane];
@@ -1402,23 +1434,20 @@ __global__ __launch_bounds__(256) void k_rows_from_records(const unsigned char *
 // R2: compact blobs -> the row tables D1 reads, without the host and without moving the payload (glc_kernels.h
 // launch_rows_from_compact has the rules).  The blob is almost the table already: cnt is row_cnt, scale is
 // row_scale, the pairs are the rows' lists back to back - what is missing are the two exclusive scans (pairs and
-// raw rows in front of a row) and the checks build_row_table makes on the host, because D1 trusts its rows.
-//   k_r2_headers      one thread per blob: the header check; fills the blob's CompactStatus
-//   k_r2_scan_rows    P1's shape: a workgroup scans 1024 rows (4 per thread, Hillis-Steele over the 256 thread
-//                     sums).  One 64-bit word carries both counts: pairs in the low 53 bits (a block holds
-//                     at most 1024 * (2^32 - 1) of them), rows of raw frames in the high 11 (< 1024 in front of a row
-//                     of the block).  The row's word waits in its row_raw_len slot for k_r2_rows.
-//   k_r2_scan_blocks  P2's shape: ONE workgroup, exclusive scans of the block sums in chunks of 1024, then per
-//                     blob the running sums at its first row (its rows' origin) and the two totals the header
-//                     promised (reported, they reject nothing)
+// raw rows in front of a row; the shared scan above P1) and the checks build_row_table makes on the host, because
+// D1 trusts its rows.  Sections are found with glc_common.h compact_sections, as the host finds them.
+//   k_r2_headers      one thread per blob: glc_common.h compact_header_fault behind a capacity pre-check; fills
+//                     the blob's CompactStatus
+//   k_r2_scan_rows    scan_rows_1024 over the blob's own cnt (nothing for a blob whose header failed).  The
+//                     row's word waits in its row_raw_len slot for k_r2_rows.
+//   k_r2_scan_blocks  scan_block_sums, then per blob the running sums at its first row (its rows' origin) and
+//                     the two totals the header promised (reported, they reject nothing)
 //   k_r2_rows         one wave per row: bounds, then the list in strides of 64 - lane l compares its bin with
 //                     lane l - 1's (shuffle; lane 0 takes the previous stride's last) - and the row's arrays
 // Rows of several blobs follow each other (glc_decode_batch_device_compact): a row finds its blob by a binary
 // search over the directory's first rows, and the scans simply run across the blobs - a blob's origin is
 // subtracted again.  The sums of a blob whose header failed are taken over nothing.
 // ------------------------------------------------------------------------------------------
-constexpr unsigned long long kR2PairMask = (1ull << 53) - 1ull;
-
 __device__ __forceinline__ unsigned r2_find_blob(const CompactBlob *__restrict__ dir, unsigned n_blobs, unsigned m) {
   unsigned lo = 0, hi = n_blobs;  // the last blob whose first_row <= m (first_row ascends from 0)
   while (hi - lo > 1) {
@@ -1429,40 +1458,25 @@ __device__ __forceinline__ unsigned r2_find_blob(const CompactBlob *__restrict__
   return lo;
 }
 
-// offsets of the fixed sections of a blob of `nf` frames of `ch` channels (glc_common.h compact_layout)
-__device__ __forceinline__ unsigned long long r2_align64(unsigned long long v) { return (v + 63ull) & ~63ull; }
-__device__ __forceinline__ unsigned long long r2_o_scale(unsigned long long nf) { return 64ull + r2_align64(nf); }
-__device__ __forceinline__ unsigned long long r2_o_cnt(unsigned long long nf, unsigned long long rows) {
-  return r2_o_scale(nf) + r2_align64(4ull * rows);
-}
-__device__ __forceinline__ unsigned long long r2_o_pairs(unsigned long long nf, unsigned long long rows) {
-  return r2_o_cnt(nf, rows) + r2_align64(4ull * rows);
-}
-
 __global__ __launch_bounds__(256) void k_r2_headers(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned n_blobs,
                                                      unsigned ch, CompactStatus *__restrict__ status) {
   const unsigned b = blockIdx.x * 256u + threadIdx.x;
   if (b >= n_blobs) return;
   const CompactBlob e = dir ? dir[b] : one;
-  const unsigned long long nf = e.rows / ch, rows = e.rows;
+  const unsigned long long nf = e.rows / ch;
   CompactStatus st{};
   st.first_bad_row = ~0ull;
-  bool ok = e.cap >= r2_o_pairs(nf, rows);  // the host has checked this: the fixed sections lie inside the capacity
+  bool ok = e.cap >= compact_sections(nf, e.rows).o_pairs;  // the host has checked this: the fixed sections lie inside the capacity
   if (ok) {
-    const unsigned long long *h = reinterpret_cast<const unsigned long long *>(e.addr);
-    const unsigned long long h0 = h[0], h_nf = h[1], h_np = h[2], h_nr = h[3], h_bytes = h[4];
-    ok = h0 == (0x42434C47ull | (static_cast<unsigned long long>(ch) << 32)) && h_nf == nf;
-    ok = ok && h_np <= rows * 1024ull && h_nr <= rows && h_nr % ch == 0;
-    if (ok) {  // counts are bounded: the arithmetic below cannot wrap
-      const unsigned long long need = r2_align64(r2_o_pairs(nf, rows) + 4ull * h_np) + h_nr * 4096ull;
-      ok = h_bytes == need && need <= e.cap;
-    }
-    if (ok) st.n_pairs = h_np, st.n_raw_rows = h_nr, st.bytes = h_bytes;
+    // a copy: one round of loads, and what is checked is what goes into the status (the blob is not trusted to stay put)
+    const CompactHeader h = *reinterpret_cast<const CompactHeader *>(e.addr);
+    ok = compact_header_fault(h, ch, nf, 0, /*exact=*/true, e.cap) == HeaderFault::kNone;
+    if (ok) st.n_pairs = h.n_pairs, st.n_raw_rows = h.n_raw_rows, st.bytes = h.bytes;
   }
   st.header_ok = ok ? 1u : 0u;
   if (!ok) {  // every row is rejected
     st.flags = kCompactBadHeader;
-    st.n_bad_rows = rows;
+    st.n_bad_rows = e.rows;
     st.first_bad_row = 0;
   }
   status[b] = st;
@@ -1473,43 +1487,17 @@ __global__ __launch_bounds__(256) void k_r2_scan_rows(const CompactBlob *__restr
                                                        unsigned long long *__restrict__ loc,
                                                        unsigned long long *__restrict__ blk,
                                                        unsigned long long *__restrict__ blk_raw) {
-  __shared__ unsigned long long s_part[256];
-  const unsigned base = blockIdx.x * 1024u + threadIdx.x * 4u;
-  unsigned long long v[4], sum = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const unsigned m = base + j;
-    unsigned long long n = 0;
-    if (m < M) {
-      const unsigned b = dir ? r2_find_blob(dir, n_blobs, m) : 0u;
-      const CompactBlob e = dir ? dir[b] : one;
-      if (status[b].header_ok) {
+  scan_rows_1024<unsigned long long, kR2RawShift>(
+      [&](unsigned m) -> unsigned long long {
+        const unsigned b = dir ? r2_find_blob(dir, n_blobs, m) : 0u;
+        const CompactBlob e = dir ? dir[b] : one;
+        if (!status[b].header_ok) return 0ull;
         const unsigned lm = m - e.first_row;
-        const unsigned long long nf = e.rows / ch;
+        const CompactLayout l = compact_sections(e.rows / ch, e.rows);
         const unsigned char *blob = reinterpret_cast<const unsigned char *>(e.addr);
-        const unsigned raw = blob[64ull + lm / ch];
-        n = raw ? (1ull << 53) : reinterpret_cast<const unsigned *>(blob + r2_o_cnt(nf, e.rows))[lm];
-      }
-    }
-    v[j] = sum;  // exclusive within the thread
-    sum += n;
-  }
-  s_part[threadIdx.x] = sum;
-  __syncthreads();
-  for (int off = 1; off < 256; off <<= 1) {  // Hillis-Steele inclusive scan of the 256 thread sums
-    const unsigned long long t = threadIdx.x >= static_cast<unsigned>(off) ? s_part[threadIdx.x - off] : 0ull;
-    __syncthreads();
-    s_part[threadIdx.x] += t;
-    __syncthreads();
-  }
-  const unsigned long long before = threadIdx.x ? s_part[threadIdx.x - 1] : 0ull;
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (base + j < M) loc[base + j] = before + v[j];
-  if (threadIdx.x == 255) {
-    blk[blockIdx.x] = s_part[255] & kR2PairMask;
-    blk_raw[blockIdx.x] = s_part[255] >> 53;
-  }
+        return blob[l.o_israw + lm / ch] ? (1ull << kR2RawShift) : reinterpret_cast<const unsigned *>(blob + l.o_cnt)[lm];
+      },
+      M, loc, blk, blk_raw);
 }
 
 __global__ __launch_bounds__(1024) void k_r2_scan_blocks(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned n_blobs,
@@ -1519,49 +1507,22 @@ __global__ __launch_bounds__(1024) void k_r2_scan_blocks(const CompactBlob *__re
                                                           CompactStatus *__restrict__ status) {
   __shared__ unsigned long long s[1024];
   unsigned long long sums[2];
-#pragma unroll 1
-  for (int which = 0; which < 2; ++which) {
-    unsigned long long *v = which ? blk_raw : blk;
-    unsigned long long carry = 0;
-    for (unsigned b0 = 0; b0 < n; b0 += 1024) {
-      const unsigned i = b0 + threadIdx.x;
-      const unsigned long long mine = i < n ? v[i] : 0ull;
-      s[threadIdx.x] = mine;
-      __syncthreads();
-      for (int off = 1; off < 1024; off <<= 1) {
-        const unsigned long long t = threadIdx.x >= static_cast<unsigned>(off) ? s[threadIdx.x - off] : 0ull;
-        __syncthreads();
-        s[threadIdx.x] += t;
-        __syncthreads();
-      }
-      if (i < n) v[i] = carry + s[threadIdx.x] - mine;  // exclusive
-      const unsigned long long chunk_total = s[1023];
-      __syncthreads();
-      carry += chunk_total;
-    }
-    sums[which] = carry;
-  }
+  scan_block_sums(blk, blk_raw, n, s, sums);
   __syncthreads();  // this workgroup's own stores to blk / blk_raw are read below
   // per blob: the running sums at its first row and behind its last one
   for (unsigned b = threadIdx.x; b < n_blobs; b += 1024) {
     const CompactBlob e = dir ? dir[b] : one;
     const unsigned long long r0 = e.first_row, r1 = r0 + e.rows;
-    unsigned long long p0 = sums[0], q0 = sums[1], p1 = sums[0], q1 = sums[1];
-    if (r0 < M) {
-      const unsigned long long l = loc[r0];
-      p0 = blk[r0 >> 10] + (l & kR2PairMask), q0 = blk_raw[r0 >> 10] + (l >> 53);
-    }
-    if (r1 < M) {
-      const unsigned long long l = loc[r1];
-      p1 = blk[r1 >> 10] + (l & kR2PairMask), q1 = blk_raw[r1 >> 10] + (l >> 53);
-    }
+    RowsBefore at0{sums[0], sums[1]}, at1 = at0;
+    if (r0 < M) at0 = rows_before<kR2RawShift>(loc[r0], blk, blk_raw, r0);
+    if (r1 < M) at1 = rows_before<kR2RawShift>(loc[r1], blk, blk_raw, r1);
     CompactStatus *st = status + b;
-    st->pairs_before = p0;
-    st->raw_before = q0;
+    st->pairs_before = at0.pairs;
+    st->raw_before = at0.raw;
     if (st->header_ok) {
       unsigned f = st->flags;
-      if (p1 - p0 != st->n_pairs) f |= kCompactPairSum;
-      if (q1 - q0 != st->n_raw_rows) f |= kCompactRawSum;
+      if (at1.pairs - at0.pairs != st->n_pairs) f |= kCompactPairSum;
+      if (at1.raw - at0.raw != st->n_raw_rows) f |= kCompactRawSum;
       st->flags = f;
     }
   }
@@ -1588,17 +1549,16 @@ __global__ __launch_bounds__(256) void k_r2_rows(const CompactBlob *__restrict__
   float scale = 0.0f;
   const unsigned lm = m - e.first_row;
   if (st->header_ok) {
-    const unsigned long long nf = e.rows / ch, o_pairs = r2_o_pairs(nf, e.rows);
+    const CompactLayout l = compact_sections(e.rows / ch, e.rows);
     const unsigned long long n_pairs = st->n_pairs, n_raw_rows = st->n_raw_rows;
     const unsigned char *blob = reinterpret_cast<const unsigned char *>(e.addr);
     const unsigned c = lm % ch;
-    const unsigned long long l = row_raw_len[m];  // k_r2_scan_rows left the row's word here
-    const unsigned long long p = blk[m >> 10] + (l & kR2PairMask) - st->pairs_before;
-    const unsigned long long r = blk_raw[m >> 10] + (l >> 53) - st->raw_before;
-    scale = reinterpret_cast<const float *>(blob + r2_o_scale(nf))[lm];
-    if (blob[64ull + lm / ch]) {
+    const RowsBefore at = rows_before<kR2RawShift>(row_raw_len[m], blk, blk_raw, m);  // k_r2_scan_rows left the row's word there
+    const unsigned long long p = at.pairs - st->pairs_before, r = at.raw - st->raw_before;
+    scale = reinterpret_cast<const float *>(blob + l.o_scale)[lm];
+    if (blob[l.o_israw + lm / ch]) {
       // the frame's ch planes are its raw_pcm as it stands (Q1): they start at plane r - c
-      const unsigned long long raw_off = r2_align64(o_pairs + 4ull * n_pairs), first = r - c;
+      const unsigned long long raw_off = compact_raw_offset(l, n_pairs), first = r - c;
       if (r >= c && first + ch <= n_raw_rows && raw_off + (first + ch) * 4096ull <= st->bytes) {
         raw_at = static_cast<long long>((e.addr - base_addr + raw_off) / 2ull + first * 2048ull);
         raw_len = 2048ull * ch;
@@ -1606,11 +1566,11 @@ __global__ __launch_bounds__(256) void k_r2_rows(const CompactBlob *__restrict__
         bad = kCompactRawRange;
       }
     } else {
-      const unsigned n = reinterpret_cast<const unsigned *>(blob + r2_o_cnt(nf, e.rows))[lm];
+      const unsigned n = reinterpret_cast<const unsigned *>(blob + l.o_cnt)[lm];
       if (n > 1024u || p > n_pairs || n > n_pairs - p) {
         bad = kCompactRowBounds;
       } else {
-        const unsigned *list = reinterpret_cast<const unsigned *>(blob + o_pairs) + p;
+        const unsigned *list = reinterpret_cast<const unsigned *>(blob + l.o_pairs) + p;
         unsigned last = 0, wrong = 0;  // `last`: the bin at the end of the stride before
         for (unsigned j0 = 0; j0 < n; j0 += 64) {
           const unsigned j = j0 + lane;
@@ -1623,7 +1583,7 @@ __global__ __launch_bounds__(256) void k_r2_rows(const CompactBlob *__restrict__
         if (__any(wrong)) {
           bad = kCompactNotCanonical;
         } else {
-          begin = (e.addr - base_addr + o_pairs) / 4ull + p;
+          begin = (e.addr - base_addr + l.o_pairs) / 4ull + p;
           cnt = n;
         }
       }
@@ -1925,99 +1885,136 @@ hipError_t launch_decide_raw(const DeviceTables &t, const PcmView &pcm, uint64_t
 }
 
 namespace {
-// P1-P3 of M rows; fmap / dir: the segment-aware form (launch_compact_batch), else nullptr
-hipError_t compact_rows(const uint8_t *records, uint32_t M, uint32_t ch, uint64_t n_frames, uint32_t *loc,
-                        uint64_t *blk, uint64_t *blk_raw, uint64_t *totals, uint8_t *blob, uint64_t o_israw,
-                        uint64_t o_scale, uint64_t o_cnt, uint64_t o_pairs, const uint2 *fmap, unsigned long long *dir,
-                        hipStream_t s) {
-  auto *t = reinterpret_cast<unsigned long long *>(totals);
+inline uint64_t align256(uint64_t v) { return (v + 255ull) & ~255ull; }
+// Consecutive 256-byte aligned arrays of a workspace.  Each workspace has ONE function that takes its arrays
+// from a base: the launcher calls it with the workspace, the *_bytes() function with base 0 and reads `used`.
+struct Carve {
+  uintptr_t base;
+  uint64_t used = 0;
+  template <typename T>
+  T *take(uint64_t n) {
+    T *p = reinterpret_cast<T *>(base + used);
+    used += align256(n * sizeof(T));
+    return p;
+  }
+};
+
+struct CompactScratch {  // of P1-P3 over M rows
+  unsigned *loc;
+  unsigned long long *blk, *blk_raw, *totals;
+  uint64_t bytes;
+};
+CompactScratch compact_scratch(const void *base, uint64_t M) {
+  const uint64_t nblk = (M + 1023) / 1024;
+  Carve c{reinterpret_cast<uintptr_t>(base)};
+  CompactScratch w;
+  w.loc = c.take<unsigned>(M);
+  w.blk = c.take<unsigned long long>(nblk);
+  w.blk_raw = c.take<unsigned long long>(nblk);
+  w.totals = c.take<unsigned long long>(2);
+  w.bytes = c.used;
+  return w;
+}
+}  // namespace
+
+uint64_t compact_scratch_bytes(uint64_t M) { return compact_scratch(nullptr, M).bytes; }
+
+hipError_t launch_compact(const uint8_t *records, uint32_t M, uint32_t ch, uint64_t n_frames, void *scratch, uint8_t *blob,
+                          const CompactLayout &l, const FrameMap *frame_map, uint64_t *clip_dir, hipStream_t s) {
+  static_assert(sizeof(FrameMap) == sizeof(uint2), "FrameMap is read as a uint2");
+  if (!scratch || !blob || (frame_map == nullptr) != (clip_dir == nullptr)) return hipErrorInvalidValue;
+  const CompactScratch w = compact_scratch(scratch, M);
+  const uint2 *fmap = reinterpret_cast<const uint2 *>(frame_map);
+  auto *dir = reinterpret_cast<unsigned long long *>(clip_dir);
   if (M == 0) {  // an empty range: the scans are over nothing, the header says so
-    hipLaunchKernelGGL(k_pack_scan_blocks, dim3(1), dim3(1024), 0, s, reinterpret_cast<unsigned long long *>(blk),
-                       reinterpret_cast<unsigned long long *>(blk_raw), 0u, t, ch, 0ull, static_cast<unsigned long long>(o_pairs), blob);
+    hipLaunchKernelGGL(k_pack_scan_blocks, dim3(1), dim3(1024), 0, s, w.blk, w.blk_raw, 0u, w.totals, ch, 0ull, l, blob);
     return hipGetLastError();
   }
   const unsigned long long hdr = record_header_bytes(ch), rec = record_bytes(ch);
   const unsigned nblk = (M + 1023) / 1024;
-  auto *b = reinterpret_cast<unsigned long long *>(blk);
-  auto *br = reinterpret_cast<unsigned long long *>(blk_raw);
-  float *scales = reinterpret_cast<float *>(blob + o_scale);
-  unsigned *cnt = reinterpret_cast<unsigned *>(blob + o_cnt);
   if (fmap)
-    hipLaunchKernelGGL(k_pack_scan_rows<true>, dim3(nblk), dim3(256), 0, s, records, M, ch, rec, loc, b, br, scales, cnt,
-                       blob + o_israw, fmap);
+    hipLaunchKernelGGL(k_pack_scan_rows<true>, dim3(nblk), dim3(256), 0, s, records, M, ch, rec, w.loc, w.blk, w.blk_raw, l, blob, fmap);
   else
-    hipLaunchKernelGGL(k_pack_scan_rows<false>, dim3(nblk), dim3(256), 0, s, records, M, ch, rec, loc, b, br, scales, cnt,
-                       blob + o_israw, fmap);
-  hipLaunchKernelGGL(k_pack_scan_blocks, dim3(1), dim3(1024), 0, s, b, br, nblk, t, ch, static_cast<unsigned long long>(n_frames),
-                     static_cast<unsigned long long>(o_pairs), blob);
+    hipLaunchKernelGGL(k_pack_scan_rows<false>, dim3(nblk), dim3(256), 0, s, records, M, ch, rec, w.loc, w.blk, w.blk_raw, l, blob, fmap);
+  hipLaunchKernelGGL(k_pack_scan_blocks, dim3(1), dim3(1024), 0, s, w.blk, w.blk_raw, nblk, w.totals, ch,
+                     static_cast<unsigned long long>(n_frames), l, blob);
   if (fmap)
-    hipLaunchKernelGGL(k_pack_rows<true>, dim3((M + 3) / 4), dim3(256), 0, s, records, M, ch, rec, hdr, loc, b, br, t, cnt,
-                       static_cast<unsigned long long>(o_pairs), blob, fmap, dir);
+    hipLaunchKernelGGL(k_pack_rows<true>, dim3((M + 3) / 4), dim3(256), 0, s, records, M, ch, rec, hdr, w.loc, w.blk, w.blk_raw,
+                       w.totals, l, blob, fmap, dir);
   else
-    hipLaunchKernelGGL(k_pack_rows<false>, dim3((M + 3) / 4), dim3(256), 0, s, records, M, ch, rec, hdr, loc, b, br, t, cnt,
-                       static_cast<unsigned long long>(o_pairs), blob, fmap, dir);
+    hipLaunchKernelGGL(k_pack_rows<false>, dim3((M + 3) / 4), dim3(256), 0, s, records, M, ch, rec, hdr, w.loc, w.blk, w.blk_raw,
+                       w.totals, l, blob, fmap, dir);
   return hipGetLastError();
-}
-}  // namespace
-
-hipError_t launch_compact(const uint8_t *records, uint32_t M, uint32_t ch, uint64_t n_frames, uint32_t *loc,
-                          uint64_t *blk, uint64_t *blk_raw, uint64_t *totals, uint8_t *blob, uint64_t o_israw,
-                          uint64_t o_scale, uint64_t o_cnt, uint64_t o_pairs, hipStream_t s) {
-  return compact_rows(records, M, ch, n_frames, loc, blk, blk_raw, totals, blob, o_israw, o_scale, o_cnt, o_pairs, nullptr,
-                      nullptr, s);
-}
-
-hipError_t launch_compact_batch(const uint8_t *records, uint32_t M, uint32_t ch, uint64_t n_frames, const FrameMap *fmap,
-                                uint64_t *dir, uint32_t *loc, uint64_t *blk, uint64_t *blk_raw, uint64_t *totals,
-                                uint8_t *blob, uint64_t o_israw, uint64_t o_scale, uint64_t o_cnt, uint64_t o_pairs,
-                                hipStream_t s) {
-  if (!fmap || !dir) return hipErrorInvalidValue;
-  static_assert(sizeof(FrameMap) == sizeof(uint2), "FrameMap is read as a uint2");
-  return compact_rows(records, M, ch, n_frames, loc, blk, blk_raw, totals, blob, o_israw, o_scale, o_cnt, o_pairs,
-                      reinterpret_cast<const uint2 *>(fmap), reinterpret_cast<unsigned long long *>(dir), s);
 }
 
 namespace {
-inline uint64_t align256(uint64_t v) { return (v + 255ull) & ~255ull; }
+struct RowArrays {  // what DecodeRows points at, per row
+  unsigned long long *row_begin;
+  unsigned *row_cnt;
+  float *row_scale;
+  long long *row_raw;
+  unsigned long long *row_raw_len;
+  void take(Carve &c, uint64_t m) {
+    row_begin = c.take<unsigned long long>(m);
+    row_cnt = c.take<unsigned>(m);
+    row_scale = c.take<float>(m);
+    row_raw = c.take<long long>(m);
+    row_raw_len = c.take<unsigned long long>(m);
+  }
+  DecodeRows rows(const void *pairs, const void *raw_pool) const {
+    // any_raw: the host does not know, so the raw-row kernel is always launched (it returns at once for
+    // the rows of compressed frames)
+    return DecodeRows{static_cast<const uint32_t *>(pairs), reinterpret_cast<const uint64_t *>(row_begin), row_cnt, row_scale,
+                      reinterpret_cast<const int64_t *>(row_raw), reinterpret_cast<const uint64_t *>(row_raw_len),
+                      static_cast<const int16_t *>(raw_pool), 1u};
+  }
+};
+struct R1Tables : RowArrays {  // the fixed-stride lists in front of the row arrays
+  unsigned *pairs;
+  uint64_t bytes;
+};
+R1Tables r1_tables(const void *base, uint32_t M) {
+  const uint64_t m = M ? M : 1;
+  Carve c{reinterpret_cast<uintptr_t>(base)};
+  R1Tables t;
+  t.pairs = c.take<unsigned>(m * kHopI);
+  t.take(c, m);
+  t.bytes = c.used;
+  return t;
+}
+struct R2Tables : RowArrays {  // the row arrays (32 B per row), the block sums behind them
+  unsigned long long *blk, *blk_raw;
+  uint64_t bytes;
+};
+R2Tables r2_tables(const void *base, uint32_t M) {
+  const uint64_t m = M ? M : 1, nblk = (m + 1023) / 1024;
+  Carve c{reinterpret_cast<uintptr_t>(base)};
+  R2Tables t;
+  t.take(c, m);
+  t.blk = c.take<unsigned long long>(nblk);
+  t.blk_raw = c.take<unsigned long long>(nblk);
+  t.bytes = c.used;
+  return t;
+}
 }  // namespace
 
-uint64_t rows_from_records_bytes(uint32_t M) {
-  const uint64_t m = M ? M : 1;
-  // pairs | row_begin | row_cnt | row_scale | row_raw | row_raw_len, each 256-byte aligned
-  return align256(m * kHopI * 4ull) + 3 * align256(m * 8ull) + 2 * align256(m * 4ull);
-}
+uint64_t rows_from_records_bytes(uint32_t M) { return r1_tables(nullptr, M).bytes; }
 
 namespace {
 hipError_t rows_from_records(const uint8_t *records, uint32_t M, uint32_t ch, const FrameMap *fmap, void *workspace,
                              uint64_t *stats, hipStream_t s, DecodeRows *rows) {
   if (!records || !workspace || !rows || ch == 0 || (reinterpret_cast<uintptr_t>(records) & 15u)) return hipErrorInvalidValue;
-  const uint64_t m = M ? M : 1;
-  uint8_t *p = static_cast<uint8_t *>(workspace);
-  auto take = [&](uint64_t bytes) {
-    uint8_t *at = p;
-    p += align256(bytes);
-    return at;
-  };
-  auto *pairs = reinterpret_cast<unsigned *>(take(m * kHopI * 4ull));
-  auto *row_begin = reinterpret_cast<unsigned long long *>(take(m * 8ull));
-  auto *row_cnt = reinterpret_cast<unsigned *>(take(m * 4ull));
-  auto *row_scale = reinterpret_cast<float *>(take(m * 4ull));
-  auto *row_raw = reinterpret_cast<long long *>(take(m * 8ull));
-  auto *row_raw_len = reinterpret_cast<unsigned long long *>(take(m * 8ull));
-  // any_raw: the host does not know, so the raw-row kernel is always launched (it returns at once for
-  // the rows of compressed frames)
-  *rows = DecodeRows{pairs, reinterpret_cast<const uint64_t *>(row_begin), row_cnt, row_scale,
-                     reinterpret_cast<const int64_t *>(row_raw), reinterpret_cast<const uint64_t *>(row_raw_len),
-                     reinterpret_cast<const int16_t *>(records), 1u};
+  const R1Tables t = r1_tables(workspace, M);
+  *rows = t.rows(t.pairs, records);
   if (M == 0) return hipSuccess;
   const unsigned long long rec = record_bytes(ch), hdr = record_header_bytes(ch);
   auto *st = reinterpret_cast<unsigned long long *>(stats);
   if (fmap)
-    hipLaunchKernelGGL(k_rows_from_records<true>, dim3((M + 3) / 4), dim3(256), 0, s, records, M, ch, rec, hdr, pairs, row_begin,
-                       row_cnt, row_scale, row_raw, row_raw_len, st, reinterpret_cast<const uint2 *>(fmap));
+    hipLaunchKernelGGL(k_rows_from_records<true>, dim3((M + 3) / 4), dim3(256), 0, s, records, M, ch, rec, hdr, t.pairs, t.row_begin,
+                       t.row_cnt, t.row_scale, t.row_raw, t.row_raw_len, st, reinterpret_cast<const uint2 *>(fmap));
   else
-    hipLaunchKernelGGL(k_rows_from_records<false>, dim3((M + 3) / 4), dim3(256), 0, s, records, M, ch, rec, hdr, pairs, row_begin,
-                       row_cnt, row_scale, row_raw, row_raw_len, st, static_cast<const uint2 *>(nullptr));
+    hipLaunchKernelGGL(k_rows_from_records<false>, dim3((M + 3) / 4), dim3(256), 0, s, records, M, ch, rec, hdr, t.pairs, t.row_begin,
+                       t.row_cnt, t.row_scale, t.row_raw, t.row_raw_len, st, static_cast<const uint2 *>(nullptr));
   return hipGetLastError();
 }
 }  // namespace
@@ -2033,45 +2030,27 @@ hipError_t launch_rows_from_records_batch(const uint8_t *records, uint32_t M, ui
   return rows_from_records(records, M, ch, fmap, workspace, clip_stats, s, rows);
 }
 
-uint64_t rows_from_compact_bytes(uint32_t M) {
-  const uint64_t m = M ? M : 1;
-  // row_begin | row_cnt | row_scale | row_raw | row_raw_len | blk | blk_raw, each 256-byte aligned
-  return 3 * align256(m * 8ull) + 2 * align256(m * 4ull) + 2 * align256((m + 1023) / 1024 * 8ull);
-}
+uint64_t rows_from_compact_bytes(uint32_t M) { return r2_tables(nullptr, M).bytes; }
 
 hipError_t launch_rows_from_compact(const CompactBlob *dir, const CompactBlob &one, uint32_t n_blobs, uint32_t M, uint32_t ch,
                                     const void *base, void *workspace, CompactStatus *status, hipStream_t s,
                                     DecodeRows *rows) {
   static_assert(sizeof(CompactBlob) == 32 && sizeof(CompactStatus) == 64, "read and written by the kernels as laid out here");
   if (!workspace || !status || !rows || !base || ch == 0 || n_blobs == 0 || (!dir && n_blobs != 1)) return hipErrorInvalidValue;
+  if (M % ch) return hipErrorInvalidValue;  // every blob's rows are whole frames (a directory's entries: the caller's word)
   if (!dir && ((one.addr & 63u) || one.first_row != 0 || one.rows != M || one.addr < reinterpret_cast<uintptr_t>(base)))
     return hipErrorInvalidValue;
   if (reinterpret_cast<uintptr_t>(base) & 63u) return hipErrorInvalidValue;
-  const uint64_t m = M ? M : 1;
-  uint8_t *p = static_cast<uint8_t *>(workspace);
-  auto take = [&](uint64_t bytes) {
-    uint8_t *at = p;
-    p += align256(bytes);
-    return at;
-  };
-  auto *row_begin = reinterpret_cast<unsigned long long *>(take(m * 8ull));
-  auto *row_cnt = reinterpret_cast<unsigned *>(take(m * 4ull));
-  auto *row_scale = reinterpret_cast<float *>(take(m * 4ull));
-  auto *row_raw = reinterpret_cast<long long *>(take(m * 8ull));
-  auto *row_raw_len = reinterpret_cast<unsigned long long *>(take(m * 8ull));
-  const unsigned nblk = static_cast<unsigned>((m + 1023) / 1024);
-  auto *blk = reinterpret_cast<unsigned long long *>(take(nblk * 8ull));
-  auto *blk_raw = reinterpret_cast<unsigned long long *>(take(nblk * 8ull));
-  *rows = DecodeRows{static_cast<const uint32_t *>(base), reinterpret_cast<const uint64_t *>(row_begin), row_cnt, row_scale,
-                     reinterpret_cast<const int64_t *>(row_raw), reinterpret_cast<const uint64_t *>(row_raw_len),
-                     static_cast<const int16_t *>(base), 1u};
+  const R2Tables t = r2_tables(workspace, M);
+  const unsigned nblk = static_cast<unsigned>((static_cast<uint64_t>(M) + 1023) / 1024);
+  *rows = t.rows(base, base);
   hipLaunchKernelGGL(k_r2_headers, dim3((n_blobs + 255) / 256), dim3(256), 0, s, dir, one, n_blobs, ch, status);
   if (M == 0) return hipGetLastError();
-  hipLaunchKernelGGL(k_r2_scan_rows, dim3(nblk), dim3(256), 0, s, dir, one, n_blobs, M, ch, status, row_raw_len, blk, blk_raw);
-  hipLaunchKernelGGL(k_r2_scan_blocks, dim3(1), dim3(1024), 0, s, dir, one, n_blobs, M, blk, blk_raw, nblk, row_raw_len, status);
+  hipLaunchKernelGGL(k_r2_scan_rows, dim3(nblk), dim3(256), 0, s, dir, one, n_blobs, M, ch, status, t.row_raw_len, t.blk, t.blk_raw);
+  hipLaunchKernelGGL(k_r2_scan_blocks, dim3(1), dim3(1024), 0, s, dir, one, n_blobs, M, t.blk, t.blk_raw, nblk, t.row_raw_len, status);
   hipLaunchKernelGGL(k_r2_rows, dim3(static_cast<unsigned>((static_cast<uint64_t>(M) + 3) / 4)), dim3(256), 0, s, dir, one, n_blobs,
-                     M, ch, static_cast<unsigned long long>(reinterpret_cast<uintptr_t>(base)), blk, blk_raw, status, row_begin,
-                     row_cnt, row_scale, row_raw, row_raw_len);
+                     M, ch, static_cast<unsigned long long>(reinterpret_cast<uintptr_t>(base)), t.blk, t.blk_raw, status, t.row_begin,
+                     t.row_cnt, t.row_scale, t.row_raw, t.row_raw_len);
   return hipGetLastError();
 }
 
