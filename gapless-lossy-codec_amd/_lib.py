@@ -68,6 +68,17 @@ class GlcClipLayout(C.Structure):
     ]
 
 
+class GlcStoreEntry(C.Structure):
+    """glc_store_entry (include/glc.h): where the device put a clip's blob in the arena."""
+    _fields_ = [
+        ("offset", C.c_uint64),
+        ("bytes", C.c_uint64),
+        ("n_pairs", C.c_uint64),
+        ("n_raw_rows", C.c_uint32),
+        ("stored", C.c_uint32),
+    ]
+
+
 class GlcFramesView(C.Structure):
     """glc_frames_view (include/glc.h): EncodedAudio as flat arrays."""
     _fields_ = [
@@ -225,6 +236,8 @@ SIGNATURES = {
                                                   C.POINTER(GlcClipLayout)]),
     "glc_decode_compact_last_status": (C.c_int, [_vp, C.POINTER(GlcCompactStatus), C.c_uint64]),
     "glc_frames_to_compact": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(GlcCompactInfo)]),
+    "glc_compact_store_bound": (C.c_uint64, [C.POINTER(GlcClipLayout)]),
+    "glc_encode_batch_device_compact": (C.c_int, [_vp, _vp, C.POINTER(GlcClipLayout), _vp, C.c_uint64, _vp, _vp]),
     "glc_version": (C.c_char_p, []),
 }
 

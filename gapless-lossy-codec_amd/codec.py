@@ -276,6 +276,23 @@ def compact_bound(channels: int, n_frames: int) -> int:
     return int(lib.glc_compact_bound(channels, n_frames))
 
 
+def compact_store_bound(channels: int, lengths) -> int:
+    """Arena bytes that hold the blobs of clips of `lengths` samples per channel whatever their content
+    (glc_compact_store_bound: the sum of compact_bound over the clips)."""
+    lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+    arr = (C.c_uint64 * max(len(lens), 1))(*lens)
+    lay = GlcClipLayout(len(lens), channels, 0, 0, 0, 0, C.cast(arr, C.POINTER(C.c_uint64)))
+    return int(lib.glc_compact_store_bound(C.byref(lay)))
+
+
+def store_blobs(arena, entries) -> list:
+    """The blobs Encoder.encode_compact_batch_tensor left in `arena`, as the list of arena slices that
+    Decoder.decode_compact_batch_tensor takes: one download of `entries` (it waits for the encode), no copy of a
+    blob.  None stands for a clip that did not fit (stored == 0)."""
+    e = entries.cpu().tolist()
+    return [arena[off:off + size] if (raw_stored >> 32) & 1 else None for off, size, _, raw_stored in e]
+
+
 def compact_records(records: np.ndarray, channels: int) -> np.ndarray:
     """Host twin of the device compaction (glc_compact_records): records -> compact blob bytes."""
     records = np.ascontiguousarray(records, np.uint8).reshape(-1)
@@ -532,6 +549,61 @@ class Encoder(_Ctx):
         finally:
             self.set_stream(0)
         return blob[:info.bytes], info
+
+    def encode_compact_batch_tensor(self, x, lengths=None, planar: bool = True, arena=None, cursor=None):
+        """Encode every clip of a padded batch into its own compact blob, the blobs back to back in an arena the
+        DEVICE allocates from (glc_encode_batch_device_compact).  `x`: a float32 CUDA tensor (B, C, T) (planar) or
+        (B, T, C), innermost stride 1, any slice of something bigger; lengths: per clip its true samples per channel
+        (default T) - what lies behind them is not read.  arena: a 1-D uint8 CUDA tensor whose first byte is 64-byte
+        aligned (None: a new one of compact_store_bound bytes); cursor: a one-element int64 CUDA tensor holding the
+        first free byte of the arena (None: a new zero).  Passing the same arena and cursor again appends.
+        Returns (arena, cursor, entries): entries an (B, 4) int64 CUDA tensor, one glc_store_entry per clip as
+        {offset, bytes, n_pairs, n_raw_rows | stored << 32}; blob i is arena[offset : offset + bytes] when stored
+        (store_blobs cuts them).  A clip that does not fit is not stored, and the cursor counts on: its final value
+        is the arena size that would have sufficed.  Queued on torch's current stream as RoundTrip.apply_batch_tensor
+        queues; nothing is copied to the host and the C call does not synchronise (restoring the context's private
+        stream afterwards waits for the queued work, as in every *_tensor method)."""
+        import torch
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 3:
+            raise TypeError("x must be a float32 CUDA tensor of shape (B, C, T) or (B, T, C)")
+        if x.device.index != self.device:
+            raise GlcError(GLC_EINVAL, f"x is on {x.device}, this context on device {self.device}")
+        if x.shape[2] > 1 and x.stride(2) != 1:
+            raise TypeError("x: the innermost stride must be 1")
+        if min(x.stride(0), x.stride(1)) < 0:
+            raise TypeError("x: negative strides")
+        b, ch, n = (x.shape[0], x.shape[1], x.shape[2]) if planar else (x.shape[0], x.shape[2], x.shape[1])
+        if not 0 < ch <= 0xFFFF:
+            raise GlcError(GLC_EINVAL, f"x: {ch} channels")
+        if not planar and b and n > 1 and x.stride(1) != ch:
+            raise TypeError(f"x: an interleaved clip must be dense (stride {ch} between samples)")
+        lay = GlcClipLayout(b, ch, 1 if planar else 0, x.stride(0), x.stride(1) if planar else 0, n, None)
+        if lengths is not None:
+            lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+            if len(lens) != b or any(v < 0 or v > n for v in lens):
+                raise GlcError(GLC_EINVAL, f"lengths must hold {b} values in [0, {n}]")
+            arr = (C.c_uint64 * max(b, 1))(*lens)
+            lay.lengths = C.cast(arr, C.POINTER(C.c_uint64))
+        if arena is None:
+            arena = torch.empty(max(int(lib.glc_compact_store_bound(C.byref(lay))), 64), dtype=torch.uint8, device=x.device)
+        if cursor is None:
+            cursor = torch.zeros(1, dtype=torch.int64, device=x.device)
+        if not isinstance(arena, torch.Tensor) or not arena.is_cuda or arena.dtype != torch.uint8 or arena.dim() != 1 \
+                or not arena.is_contiguous():
+            raise TypeError("arena must be a contiguous 1-D uint8 CUDA tensor")
+        if not isinstance(cursor, torch.Tensor) or not cursor.is_cuda or cursor.dtype != torch.int64 or cursor.numel() != 1:
+            raise TypeError("cursor must be a one-element int64 CUDA tensor")
+        if arena.device != x.device or cursor.device != x.device:
+            raise GlcError(GLC_EINVAL, "x, arena and cursor must be on one device")
+        entries = torch.zeros((b, 4), dtype=torch.int64, device=x.device)
+        self._enter_torch_stream(x.device)
+        try:
+            check(lib.glc_encode_batch_device_compact(self._h, C.c_void_p(x.data_ptr()), C.byref(lay), C.c_void_p(arena.data_ptr()),
+                                                      arena.numel(), C.c_void_p(cursor.data_ptr()),
+                                                      C.c_void_p(entries.data_ptr())), self._h)
+        finally:
+            self.set_stream(0)
+        return arena, cursor, entries
 
     def mdct_forward_device(self, d_pcm: int, t0: int, t_count: int, n_samples: int, channels: int,
                             frame_begin: int, frame_end: int, d_coeffs: int) -> None:

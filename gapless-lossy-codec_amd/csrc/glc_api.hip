@@ -2535,13 +2535,69 @@ struct RtbLayout {
 struct RtbRound {
   uint64_t first = 0, n = 0, V = 0, n_real = 0;
   bool lng = false;
-  size_t o_clips = 0, o_fmap = 0, o_desc = 0;  // in the call's table image
+  size_t o_clips = 0, o_fmap = 0, o_desc = 0, o_span = 0;  // in the call's table image (o_span: the store encode's clip table)
   uint64_t n_desc = 0;
   uint64_t stat_off = 0;  // lng: the clip's kRowStatSlots counter pairs
 };
 
 // Kept hops of a clip: 512 interleaved samples of delay in front (hop 0 is cut), len * ch kept.
 inline uint64_t rtb_hops_kept(uint64_t len, uint32_t ch) { return (glc::kHop / 2 + len * ch - 1) / (uint64_t(glc::kHop) * ch) + 1; }
+
+// Rounds as in encode_batch_impl: whole clips, at most encode_chunk_frames(ch) virtual frames together; a clip of
+// more is a round of its own.
+std::vector<RtbRound> rtb_plan_rounds(const std::vector<glc_plan> &plans, uint32_t ch) {
+  const uint64_t budget = encode_chunk_frames(ch), n = plans.size();
+  std::vector<RtbRound> rounds;
+  RtbRound cur;
+  auto flush = [&](uint64_t next) {
+    if (cur.n) rounds.push_back(cur);
+    cur = RtbRound{};
+    cur.first = next;
+  };
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint64_t v = plans[i].n_frames + 1;
+    if (v > budget) {
+      flush(i);
+      cur.n = 1, cur.lng = true, cur.V = v, cur.n_real = plans[i].n_frames;
+      flush(i + 1);
+      continue;
+    }
+    if (cur.V + v > budget) flush(i);
+    cur.n += 1, cur.V += v, cur.n_real += plans[i].n_frames;
+  }
+  flush(n);
+  return rounds;
+}
+
+// The pinned image of a batch call's tables (rtb_stage -> rtb_tab).  It may still be on its way up for the call
+// before: wait for that copy (not for any kernel of that call - they are queued behind it), then size it.
+int rtb_image_begin(glc_ctx *ctx, size_t tab) {
+  int rc = rt_reserve(ctx, ctx->rtb_tab, tab);
+  if (rc != GLC_OK) return rc;
+  if (!ctx->rtb_ev) GLC_HIP(ctx, hipEventCreateWithFlags(&ctx->rtb_ev, hipEventDisableTiming));
+  if (ctx->rtb_ev_pending) GLC_HIP(ctx, hipEventSynchronize(ctx->rtb_ev));
+  ctx->rtb_ev_pending = false;
+  GLC_HIP(ctx, ctx->rtb_stage.reserve(tab));
+  return GLC_OK;
+}
+int rtb_image_send(glc_ctx *ctx, size_t tab) {
+  GLC_HIP(ctx, hipMemcpyAsync(ctx->rtb_tab.p, ctx->rtb_stage.p, tab, hipMemcpyHostToDevice, ctx->stream));
+  GLC_HIP(ctx, hipEventRecord(ctx->rtb_ev, ctx->stream));
+  ctx->rtb_ev_pending = true;
+  return GLC_OK;
+}
+
+// What every batch call over a glc_clip_layout refuses of clip i (`clip` names the call and the clip).
+int rtb_check_clip(glc_ctx *ctx, const std::string &clip, const RtbLayout &l, uint64_t i) {
+  const uint64_t n = l.l->n_clips, ch = l.l->channels;
+  const glc_plan plan = glc::plan_encode(l.len(i) * ch, l.l->channels);
+  if (plan.n_frames == 0)
+    return fail(ctx, GLC_EINVAL, clip + ": the reference encoder panics on this input (<= 512 samples per channel)");
+  if (plan.n_frames * ch > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, clip + ": stream too long");
+  if (l.planes() && l.l->channel_stride < l.len(i)) return fail(ctx, GLC_EINVAL, clip + ": channel_stride is smaller than a plane");
+  if (n > 1 && l.l->clip_stride < l.occupies(i)) return fail(ctx, GLC_EINVAL, clip + ": clip_stride is smaller than the clip");
+  return GLC_OK;
+}
 
 int rtb_impl(glc_ctx *ctx, const float *d_pcm, const RtbLayout &in, float *d_out, const RtbLayout &out) {
   const uint64_t n = in.l->n_clips;
@@ -2551,29 +2607,7 @@ int rtb_impl(glc_ctx *ctx, const float *d_pcm, const RtbLayout &in, float *d_out
   std::vector<glc_plan> plans(n);
   for (uint64_t i = 0; i < n; ++i) plans[i] = glc::plan_encode(in.len(i) * ch, static_cast<uint16_t>(ch));
 
-  // rounds as in encode_batch_impl: whole clips, at most encode_chunk_frames(ch) virtual frames together
-  const uint64_t budget = encode_chunk_frames(ch);
-  std::vector<RtbRound> rounds;
-  {
-    RtbRound cur;
-    auto flush = [&](uint64_t next) {
-      if (cur.n) rounds.push_back(cur);
-      cur = RtbRound{};
-      cur.first = next;
-    };
-    for (uint64_t i = 0; i < n; ++i) {
-      const uint64_t v = plans[i].n_frames + 1;
-      if (v > budget) {
-        flush(i);
-        cur.n = 1, cur.lng = true, cur.V = v, cur.n_real = plans[i].n_frames;
-        flush(i + 1);
-        continue;
-      }
-      if (cur.V + v > budget) flush(i);
-      cur.n += 1, cur.V += v, cur.n_real += plans[i].n_frames;
-    }
-    flush(n);
-  }
+  std::vector<RtbRound> rounds = rtb_plan_rounds(plans, ch);
   // the call's tables, and what the workspaces have to hold
   size_t tab = 0;
   auto place = [&](size_t bytes) {
@@ -2609,15 +2643,9 @@ int rtb_impl(glc_ctx *ctx, const float *d_pcm, const RtbLayout &in, float *d_out
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rt_rows, glc::rows_from_records_bytes(static_cast<uint32_t>(max_rows)));
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->blocks, max_blocks * slot * sizeof(float));
   if (rc == GLC_OK) rc = reserve_d1_plan(ctx, max_frames, ch);
-  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rtb_tab, tab);
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rtb_stats, stat_words * sizeof(uint64_t));
+  if (rc == GLC_OK) rc = rtb_image_begin(ctx, tab);
   if (rc != GLC_OK) return rc;
-  if (!ctx->rtb_ev) GLC_HIP(ctx, hipEventCreateWithFlags(&ctx->rtb_ev, hipEventDisableTiming));
-  // the pinned image may still be on its way up for the call before: wait for that copy (not for any kernel
-  // of that call - they are queued behind it)
-  if (ctx->rtb_ev_pending) GLC_HIP(ctx, hipEventSynchronize(ctx->rtb_ev));
-  ctx->rtb_ev_pending = false;
-  GLC_HIP(ctx, ctx->rtb_stage.reserve(tab));
   uint8_t *img = static_cast<uint8_t *>(ctx->rtb_stage.p);
   uint8_t *d_tab = static_cast<uint8_t *>(ctx->rtb_tab.p);
   const bool out_planes = out.planes();
@@ -2641,9 +2669,8 @@ int rtb_impl(glc_ctx *ctx, const float *d_pcm, const RtbLayout &in, float *d_out
       return fail(ctx, GLC_EHIP, "glc_roundtrip_batch_device: hop count arithmetic is inconsistent");
   }
   hipStream_t st = ctx->stream;
-  GLC_HIP(ctx, hipMemcpyAsync(d_tab, img, tab, hipMemcpyHostToDevice, st));
-  GLC_HIP(ctx, hipEventRecord(ctx->rtb_ev, st));
-  ctx->rtb_ev_pending = true;
+  rc = rtb_image_send(ctx, tab);
+  if (rc != GLC_OK) return rc;
   uint64_t *d_stats = static_cast<uint64_t *>(ctx->rtb_stats.p);
   GLC_HIP(ctx, hipMemsetAsync(d_stats, 0, stat_words * sizeof(uint64_t), st));
 
@@ -2707,19 +2734,12 @@ int glc_roundtrip_batch_device(glc_ctx *ctx, const float *d_pcm, const glc_clip_
   if ((reinterpret_cast<uintptr_t>(d_pcm) | reinterpret_cast<uintptr_t>(d_out)) & 3u)
     return fail(ctx, GLC_EINVAL, w + ": a pointer is not aligned to its sample size");
   const RtbLayout li{in}, lo{out};
-  const uint64_t n = in->n_clips, ch = in->channels;
+  const uint64_t n = in->n_clips;
   for (uint64_t i = 0; i < n; ++i) {
     const std::string clip = w + ": clip " + std::to_string(i);
     if (li.len(i) != lo.len(i)) return fail(ctx, GLC_EINVAL, clip + ": the two layouts differ in its length");
-    const glc_plan plan = glc::plan_encode(li.len(i) * ch, in->channels);
-    if (plan.n_frames == 0)
-      return fail(ctx, GLC_EINVAL, clip + ": the reference encoder panics on this input (<= 512 samples per channel)");
-    if (plan.n_frames * ch > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, clip + ": stream too long");
-    for (const RtbLayout *l : {&li, &lo}) {
-      if (l->planes() && l->l->channel_stride < l->len(i))
-        return fail(ctx, GLC_EINVAL, clip + ": channel_stride is smaller than a plane");
-      if (n > 1 && l->l->clip_stride < l->occupies(i)) return fail(ctx, GLC_EINVAL, clip + ": clip_stride is smaller than the clip");
-    }
+    for (const RtbLayout *l : {&li, &lo})
+      if (const int rc = rtb_check_clip(ctx, clip, *l, i)) return rc;
   }
   {
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_pcm), a1 = a0 + li.extent() * sizeof(float);
@@ -3004,6 +3024,172 @@ int glc_decode_compact_last_status(glc_ctx *ctx, glc_compact_status *status, uin
     return fail(ctx, GLC_ENOMEM, "glc_decode_compact_last_status: host allocation failed");
   }
   return GLC_OK;
+}
+
+// ------------------------------------------------------------------------------ encode of a batch into per-clip compact blobs
+
+extern "C++" {
+namespace {
+
+// The frame map and the clip table of a round whose clip k has frames[k] frames (A1-A3, glc_kernels.h): every real
+// frame names its record and its clip; with `junk` a record nobody names lies behind every clip.
+void store_round_tables(const uint64_t *frames, uint64_t n, bool junk, glc::FrameMap *fmap, glc::ClipSpan *span) {
+  uint64_t vslot = 0, real = 0;
+  for (uint64_t k = 0; k < n; ++k) {
+    span[k] = glc::ClipSpan{static_cast<uint32_t>(real), static_cast<uint32_t>(frames[k])};
+    for (uint64_t f = 0; f < frames[k]; ++f)
+      fmap[real + f] = glc::FrameMap{static_cast<uint32_t>(vslot + f), static_cast<uint32_t>(k)};
+    vslot += frames[k] + (junk ? 1 : 0);
+    real += frames[k];
+  }
+}
+
+// A1-A3 of one round, as the driver and the hook queue them: the round's tables are on the device already.
+int store_round_launch(glc_ctx *ctx, const void *d_records, uint64_t n_real, uint64_t n_clips, uint32_t ch, const uint8_t *d_tab,
+                       size_t o_fmap, size_t o_span, void *d_arena, uint64_t arena_bytes, uint64_t *d_cursor,
+                       glc_store_entry *d_entries, hipStream_t st) {
+  GLC_HIP(ctx, glc::launch_compact_store(static_cast<const uint8_t *>(d_records), static_cast<uint32_t>(n_real * ch), ch,
+                                         reinterpret_cast<const glc::FrameMap *>(d_tab + o_fmap),
+                                         reinterpret_cast<const glc::ClipSpan *>(d_tab + o_span), static_cast<uint32_t>(n_clips),
+                                         ctx->pack_meta.p, static_cast<uint8_t *>(d_arena), arena_bytes, d_cursor, d_entries, st));
+  return GLC_OK;
+}
+
+int ebc_impl(glc_ctx *ctx, const float *d_pcm, const RtbLayout &in, void *d_arena, uint64_t arena_bytes, uint64_t *d_cursor,
+             glc_store_entry *d_entries) {
+  const uint64_t n = in.l->n_clips;
+  const uint32_t ch = in.l->channels;
+  const uint64_t per_hop = uint64_t(glc::kHop) * ch, rec = glc::record_bytes(ch);
+  std::vector<glc_plan> plans(n);
+  for (uint64_t i = 0; i < n; ++i) plans[i] = glc::plan_encode(in.len(i) * ch, static_cast<uint16_t>(ch));
+  std::vector<RtbRound> rounds = rtb_plan_rounds(plans, ch);
+  size_t tab = 0;
+  auto place = [&](size_t bytes) {
+    const size_t at = tab;
+    tab = align_up(tab + bytes, 256);
+    return at;
+  };
+  uint64_t max_vs = 0, max_recs = 0, max_coef_rows = 0, max_scratch = 0;
+  for (RtbRound &r : rounds) {
+    r.o_clips = place(r.n * sizeof(glc::StageClip));
+    r.o_fmap = place(r.n_real * sizeof(glc::FrameMap));
+    r.o_span = place(r.n * sizeof(glc::ClipSpan));
+    max_vs = std::max(max_vs, r.V * per_hop);
+    // a long clip's records are all held at once (the pack scans the whole clip); its transform goes in chunks
+    max_recs = std::max(max_recs, r.lng ? r.n_real : r.V);
+    max_coef_rows = std::max(max_coef_rows, (r.lng ? std::min(encode_chunk_frames(ch), r.n_real) : r.V) * ch);
+    max_scratch = std::max(max_scratch, glc::compact_store_scratch_bytes(r.n_real * ch, r.n));
+  }
+  rt_forget_streams(ctx);
+  int rc = rt_reserve(ctx, ctx->rtb_vs, max_vs * sizeof(float));
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rt_records, max_recs * rec);
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->coef, max_coef_rows * glc::kHop * sizeof(float));
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->pack_meta, max_scratch);
+  if (rc == GLC_OK) rc = rtb_image_begin(ctx, tab);
+  if (rc != GLC_OK) return rc;
+  uint8_t *img = static_cast<uint8_t *>(ctx->rtb_stage.p);
+  const uint8_t *d_tab = static_cast<const uint8_t *>(ctx->rtb_tab.p);
+  std::vector<uint64_t> frames;
+  for (const RtbRound &r : rounds) {
+    auto *clips = reinterpret_cast<glc::StageClip *>(img + r.o_clips);
+    frames.resize(r.n);
+    uint64_t vslot = 0;
+    for (uint64_t k = 0; k < r.n; ++k) {
+      const uint64_t i = r.first + k;
+      frames[k] = plans[i].n_frames;
+      clips[k] = glc::StageClip{in.at(i), in.len(i), static_cast<uint32_t>(vslot), {0u, 0u, 0u}};
+      vslot += frames[k] + 1;
+    }
+    // a long clip is encoded as a stream of its own: its records are its frames, no junk one among them
+    store_round_tables(frames.data(), r.n, !r.lng, reinterpret_cast<glc::FrameMap *>(img + r.o_fmap),
+                       reinterpret_cast<glc::ClipSpan *>(img + r.o_span));
+  }
+  hipStream_t st = ctx->stream;
+  rc = rtb_image_send(ctx, tab);
+  if (rc != GLC_OK) return rc;
+  float *vs = static_cast<float *>(ctx->rtb_vs.p);
+  for (const RtbRound &r : rounds) {
+    GLC_HIP(ctx, glc::launch_stage_clips(d_pcm, reinterpret_cast<const glc::StageClip *>(d_tab + r.o_clips), static_cast<uint32_t>(r.n), ch,
+                                         in.planes(), in.l->channel_stride, static_cast<uint32_t>(r.V), vs, st));
+    if (r.lng) {
+      const uint64_t len = in.len(r.first);
+      rc = encode_range_on(ctx, st, ctx->coef, vs, 0, len, len * ch, static_cast<uint16_t>(ch), 0, r.n_real, ctx->rt_records.p, nullptr);
+    } else {
+      const uint64_t T = r.V * glc::kHop;
+      rc = encode_range_on(ctx, st, ctx->coef, vs, 0, T, T * ch, static_cast<uint16_t>(ch), 0, r.V, ctx->rt_records.p, nullptr);
+    }
+    if (rc == GLC_OK)
+      rc = store_round_launch(ctx, ctx->rt_records.p, r.n_real, r.n, ch, d_tab, r.o_fmap, r.o_span, d_arena, arena_bytes, d_cursor,
+                              d_entries + r.first, st);
+    if (rc != GLC_OK) return rc;
+  }
+  return GLC_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int glc_encode_batch_device_compact(glc_ctx *ctx, const float *d_pcm, const glc_clip_layout *in, void *d_arena, uint64_t arena_bytes,
+                                    uint64_t *d_cursor, glc_store_entry *d_entries) {
+  const std::string w("glc_encode_batch_device_compact");
+  if (!ctx) return GLC_EINVAL;
+  if (!in) return fail(ctx, GLC_EINVAL, w + ": null argument");
+  if (in->n_clips == 0) return GLC_OK;
+  if (!d_pcm || !d_arena || !d_cursor || !d_entries) return fail(ctx, GLC_EINVAL, w + ": null argument");
+  if (in->channels == 0) return fail(ctx, GLC_EINVAL, w + ": channels == 0");
+  if (reinterpret_cast<uintptr_t>(d_pcm) & 3u) return fail(ctx, GLC_EINVAL, w + ": d_pcm is not aligned to its sample size");
+  if (reinterpret_cast<uintptr_t>(d_arena) & 63u) return fail(ctx, GLC_EINVAL, w + ": d_arena is not 64-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(d_cursor) | reinterpret_cast<uintptr_t>(d_entries)) & 7u)
+    return fail(ctx, GLC_EINVAL, w + ": d_cursor and d_entries must be 8-byte aligned");
+  const RtbLayout li{in};
+  const uint64_t n = in->n_clips;
+  for (uint64_t i = 0; i < n; ++i)
+    if (const int rc = rtb_check_clip(ctx, w + ": clip " + std::to_string(i), li, i)) return rc;
+  {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_pcm), a1 = a0 + li.extent() * sizeof(float);
+    const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_arena), b1 = b0 + arena_bytes;
+    const uintptr_t e0 = reinterpret_cast<uintptr_t>(d_entries), e1 = e0 + n * sizeof(glc_store_entry);
+    if (a0 < b1 && b0 < a1) return fail(ctx, GLC_EINVAL, w + ": the arena overlaps the input");
+    if (a0 < e1 && e0 < a1) return fail(ctx, GLC_EINVAL, w + ": the entries overlap the input");
+  }
+  DeviceGuard guard(ctx->device);
+  try {  // no C++ exception may cross the C ABI
+    return ebc_impl(ctx, d_pcm, li, d_arena, arena_bytes, d_cursor, d_entries);
+  } catch (const std::bad_alloc &) {
+    return fail(ctx, GLC_ENOMEM, w + ": host allocation failed");
+  }
+}
+
+int glc_debug_compact_store_device(glc_ctx *ctx, const void *d_records, const uint64_t *clip_frames, uint64_t n_clips,
+                                   uint16_t channels, void *d_arena, uint64_t arena_bytes, uint64_t *d_cursor,
+                                   glc_store_entry *d_entries) {
+  const std::string w("glc_debug_compact_store_device");
+  if (!ctx || !d_records || !clip_frames || !d_arena || !d_cursor || !d_entries) return fail(ctx, GLC_EINVAL, w + ": null argument");
+  if (channels == 0 || n_clips == 0 || n_clips > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, w + ": no channels, no clips or too many");
+  uint64_t n_real = 0;
+  for (uint64_t i = 0; i < n_clips; ++i) {
+    if (clip_frames[i] == 0 || clip_frames[i] > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, w + ": a clip of no frames, or of too many");
+    n_real += clip_frames[i];
+  }
+  if ((n_real + n_clips) * channels > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, w + ": frame range too long");
+  if ((reinterpret_cast<uintptr_t>(d_records) & 7u) || (reinterpret_cast<uintptr_t>(d_arena) & 63u) ||
+      ((reinterpret_cast<uintptr_t>(d_cursor) | reinterpret_cast<uintptr_t>(d_entries)) & 7u))
+    return fail(ctx, GLC_EINVAL, w + ": a pointer is not aligned");
+  DeviceGuard guard(ctx->device);
+  try {
+    const size_t o_fmap = 0, o_span = align_up(n_real * sizeof(glc::FrameMap), 256), tab = o_span + n_clips * sizeof(glc::ClipSpan);
+    int rc = rt_reserve(ctx, ctx->pack_meta, glc::compact_store_scratch_bytes(n_real * channels, n_clips));
+    if (rc == GLC_OK) rc = rtb_image_begin(ctx, tab);
+    if (rc != GLC_OK) return rc;
+    uint8_t *img = static_cast<uint8_t *>(ctx->rtb_stage.p);
+    store_round_tables(clip_frames, n_clips, true, reinterpret_cast<glc::FrameMap *>(img + o_fmap), reinterpret_cast<glc::ClipSpan *>(img + o_span));
+    rc = rtb_image_send(ctx, tab);
+    if (rc != GLC_OK) return rc;
+    return store_round_launch(ctx, d_records, n_real, n_clips, channels, static_cast<const uint8_t *>(ctx->rtb_tab.p), o_fmap, o_span,
+                              d_arena, arena_bytes, d_cursor, d_entries, ctx->stream);
+  } catch (const std::bad_alloc &) {
+    return fail(ctx, GLC_ENOMEM, w + ": host allocation failed");
+  }
 }
 
 uint64_t glc_ctx_resident_stream(const glc_ctx *ctx) { return ctx ? ctx->dec_uid : 0; }

@@ -239,6 +239,21 @@ uint64_t glc_compact_bound(uint16_t channels, uint64_t n_frames) {
   return glc::compact_layout(channels, n_frames).bound;
 }
 
+uint64_t glc_compact_store_bound(const glc_clip_layout *in) {
+  if (!in || in->channels == 0) return 0;
+  uint64_t sum = 0;
+  for (uint64_t i = 0; i < in->n_clips; ++i) {
+    const uint64_t len = in->lengths ? in->lengths[i] : in->length;
+    if (len > (1ull << 50) / in->channels) return UINT64_MAX;  // a bound of more than 2^63 bytes
+    const glc_plan plan = glc::plan_encode(len * in->channels, in->channels);
+    if (plan.n_frames == 0) return 0;
+    const uint64_t b = glc::compact_layout(in->channels, plan.n_frames).bound;
+    if (b > UINT64_MAX - sum) return UINT64_MAX;
+    sum += b;
+  }
+  return sum;
+}
+
 int glc_compact_records(const void *records, uint64_t n_frames, uint16_t channels, void *blob, uint64_t cap,
                         glc_compact_info *info) {
   if (!blob || !info || channels == 0 || (!records && n_frames)) return GLC_EINVAL;

@@ -79,6 +79,22 @@ uint64_t compact_scratch_bytes(uint64_t M);
 hipError_t launch_compact(const uint8_t *records, uint32_t M, uint32_t ch, uint64_t n_frames, void *scratch, uint8_t *blob,
                           const CompactLayout &l, const FrameMap *frame_map, uint64_t *clip_dir, hipStream_t s);
 
+// A1-A3: the pack of a round of glc_encode_batch_device_compact.  The M real rows of `records` (frame_map as in
+// launch_rows_from_records_batch: EVERY real frame names its record slot and its clip of the round) become one
+// blob per clip - the CompactLayout of the clip's own frames, padding zeroed, no directory - placed back to back
+// in `arena` (64-byte aligned) from *cursor rounded up to 64.  clips[k]: first real frame and frames of clip k;
+// they tile [0, M / ch) in order.  entries[k] (include/glc.h glc_store_entry) is written for every clip; a clip
+// with offset + bytes > arena_bytes is not stored and nothing of it is written; *cursor ends behind the last
+// clip, stored or not.  scratch: compact_store_scratch_bytes(M, n_clips) bytes, 256-byte aligned, nothing in it
+// needs initialising.  Three launches whatever n_clips, no synchronisation, ordinary stores only.
+struct ClipSpan {
+  uint32_t first, frames;
+};
+uint64_t compact_store_scratch_bytes(uint64_t M, uint64_t n_clips);
+hipError_t launch_compact_store(const uint8_t *records, uint32_t M, uint32_t ch, const FrameMap *frame_map, const ClipSpan *clips,
+                                uint32_t n_clips, void *scratch, uint8_t *arena, uint64_t arena_bytes, uint64_t *cursor,
+                                glc_store_entry *entries, hipStream_t s);
+
 // D1: sparse dequant + inverse MDCT + window -> blocks[row][2048].
 //   pairs: packed (u16 idx | i16 q << 16), canonical (ascending, unique, idx < 1024)
 //   row_begin[M] / row_cnt[M]: pair range of a row; row_scale[M]; row_raw[M]: -1 or offset (in

@@ -1262,6 +1262,33 @@ __global__ __launch_bounds__(1024) void k_pack_scan_blocks(unsigned long long *_
   if (threadIdx.x < 64 && pairs_end + threadIdx.x < raw_off) blob[pairs_end + threadIdx.x] = 0;  // deterministic padding
 }
 
+// What one wave does with row `qrow` (the 2048 i16 of channel c behind a record's header) in P3 and A3.  Row of a raw
+// frame: its 2048-sample plane goes to raw_dst (planar order == row order, Q1).  Otherwise ballot + popcount
+// prefix keeps ascending k: the first `room` non-zero bins below 1024 go to dst as (k | u16(q) << 16).  `room` is
+// the count the scan saw: a record whose nnz field disagrees with its row cannot write past its slot.
+__device__ __forceinline__ void pack_row(const short *__restrict__ qrow, bool raw, short4 *__restrict__ raw_dst,
+                                         unsigned *__restrict__ dst, unsigned room, int lane) {
+  if (raw) {
+    const short4 *src = reinterpret_cast<const short4 *>(qrow);
+    for (int i = lane; i < kFrameI / 4; i += 64) raw_dst[i] = src[i];
+    return;
+  }
+  unsigned done = 0;
+  for (int k0 = 0; k0 < kHopI; k0 += 64) {
+    const short q = qrow[k0 + lane];
+    const unsigned long long mask = __ballot(q != 0);
+    if (q != 0) {
+      const unsigned pos = done + __popcll(mask & ((1ull << lane) - 1ull));
+      if (pos < room)
+        dst[pos] = static_cast<unsigned>(k0 + lane) | (static_cast<unsigned>(static_cast<unsigned short>(q)) << 16);
+    }
+    done += __popcll(mask);
+  }
+  // fewer non-zeros than the nnz field claims: fill the rest of the slot (idx 0xFFFF is ignored by
+  // every reader, src/codec.rs:660) so the blob never carries uninitialised bytes
+  for (unsigned pos = done + lane; pos < room; pos += 64) dst[pos] = 0xFFFFu;
+}
+
 template <bool SEG>
 __global__ __launch_bounds__(256) void k_pack_rows(const unsigned char *__restrict__ records, unsigned M,
                                                     unsigned ch, unsigned long long rec_bytes,
@@ -1287,29 +1314,150 @@ __global__ __launch_bounds__(256) void k_pack_rows(const unsigned char *__restri
   }
   const unsigned char *rec = records + static_cast<size_t>(slot) * rec_bytes;
   const short *qrow = reinterpret_cast<const short *>(rec + hdr_bytes) + static_cast<size_t>(c) * kFrameI;
-  if (*reinterpret_cast<const unsigned *>(rec)) {
-    // row of a raw frame: its 2048-sample plane goes to the raw section (planar order == row order, Q1)
-    const short4 *src = reinterpret_cast<const short4 *>(qrow);
-    short4 *dst = reinterpret_cast<short4 *>(blob + compact_raw_offset(l, totals[0]) + at.raw * (kFrameI * 2ull));
-    for (int i = lane; i < kFrameI / 4; i += 64) dst[i] = src[i];
-    return;
-  }
-  unsigned *dst = reinterpret_cast<unsigned *>(blob + l.o_pairs) + at.pairs;
-  const unsigned room = reinterpret_cast<const unsigned *>(blob + l.o_cnt)[m];  // P1's: a record whose nnz field disagrees with its row cannot write past its slot
-  unsigned done = 0;
-  for (int k0 = 0; k0 < kHopI; k0 += 64) {
-    const short q = qrow[k0 + lane];
-    const unsigned long long mask = __ballot(q != 0);
-    if (q != 0) {
-      const unsigned pos = done + __popcll(mask & ((1ull << lane) - 1ull));
-      if (pos < room)
-        dst[pos] = static_cast<unsigned>(k0 + lane) | (static_cast<unsigned>(static_cast<unsigned short>(q)) << 16);
+  const bool raw = *reinterpret_cast<const unsigned *>(rec) != 0;
+  // the raw section starts behind the pairs; the room of a compressed row is the count P1 left in the blob
+  short4 *raw_dst = raw ? reinterpret_cast<short4 *>(blob + compact_raw_offset(l, totals[0]) + at.raw * (kFrameI * 2ull)) : nullptr;
+  const unsigned room = raw ? 0u : reinterpret_cast<const unsigned *>(blob + l.o_cnt)[m];
+  pack_row(qrow, raw, raw_dst, reinterpret_cast<unsigned *>(blob + l.o_pairs) + at.pairs, room, lane);
+}
+
+// ------------------------------------------------------------------------------------------
+// A1-A3: the pack of a round of glc_encode_batch_device_compact - ONE SELF-DESCRIBING BLOB PER CLIP (the single-stream
+// CompactLayout of the clip's own frames, no directory), the blobs back to back in an arena from a cursor the
+// device keeps.  fmap[frame] = {record slot, clip of the round} for EVERY real frame (R1's form), clips[k] =
+// {first real frame, frames} of clip k of the round, entries[k] its glc_store_entry (include/glc.h) as four
+// 64-bit words {offset, bytes, n_pairs, n_raw_rows | stored << 32}.
+//   A1  scan_rows_1024 over the word a row contributes, values only: where a clip's sections lie is not known yet
+//   A2  ONE workgroup: scan_block_sums; per clip its pairs and raw rows as differences of rows_before at its first
+//       row and behind its last, its size from compact_layout / compact_raw_offset; the exclusive scan of the sizes
+//       over the clips from the cursor rounded up to 64, in chunks of 1024 clips with a carry; the fit decision,
+//       every entry, the header of every stored blob, and the cursor behind the last clip - stored or not
+//   A3  one wave per real row: scale, count, raw flag and the row's list or plane (pack_row) at their clip-relative
+//       places; the wave of a clip's first row zeroes the alignment gaps of its sections.  Rows of clips that did
+//       not fit return at once: nothing of such a clip is written.
+// Ordinary stores only; the cursor needs no atomics because rounds run in stream order.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned store_row_word(const unsigned char *__restrict__ rec, unsigned c) {
+  const unsigned nnz = min(*reinterpret_cast<const unsigned *>(rec + 8 + 8 * c + 4), static_cast<unsigned>(kHopI));
+  return *reinterpret_cast<const unsigned *>(rec) ? (1u << kP1RawShift) : nnz;
+}
+
+__global__ __launch_bounds__(256) void k_store_scan_rows(const unsigned char *__restrict__ records, unsigned M, unsigned ch,
+                                                          unsigned long long rec_bytes, unsigned *__restrict__ loc,
+                                                          unsigned long long *__restrict__ blk,
+                                                          unsigned long long *__restrict__ blk_raw,
+                                                          const uint2 *__restrict__ fmap) {
+  scan_rows_1024<unsigned, kP1RawShift>(
+      [&](unsigned m) { return store_row_word(records + static_cast<size_t>(fmap[m / ch].x) * rec_bytes, m % ch); }, M, loc, blk,
+      blk_raw);
+}
+
+__global__ __launch_bounds__(1024) void k_store_place(unsigned long long *blk, unsigned long long *blk_raw, unsigned nblk,
+                                                       const unsigned *__restrict__ loc, unsigned M, unsigned ch,
+                                                       const uint2 *__restrict__ clips, unsigned n_clips,
+                                                       unsigned long long *__restrict__ clip_base,
+                                                       unsigned char *__restrict__ arena, unsigned long long arena_bytes,
+                                                       unsigned long long *cursor, unsigned long long *__restrict__ entries) {
+  __shared__ unsigned long long s[1024];
+  unsigned long long sums[2];
+  scan_block_sums(blk, blk_raw, nblk, s, sums);
+  const unsigned long long all_pairs = sums[0], all_raw = sums[1];
+  auto before = [=](unsigned long long row) {  // rows_before, also of the row behind the last
+    const unsigned long long at = row < M ? row : M - 1;
+    const RowsBefore r = rows_before<kP1RawShift>(loc[at], blk, blk_raw, at);
+    return RowsBefore{row < M ? r.pairs : all_pairs, row < M ? r.raw : all_raw};
+  };
+  unsigned long long carry = align64(*cursor);  // every thread reads it here; thread 0 writes it behind the last barrier
+  for (unsigned k0 = 0; k0 < n_clips; k0 += 1024) {
+    const unsigned k = k0 + threadIdx.x;
+    unsigned long long bytes = 0, n_pairs = 0, n_raw_rows = 0, n_frames = 0;
+    if (k < n_clips) {
+      const uint2 cl = clips[k];
+      n_frames = cl.y;
+      const unsigned long long r0 = static_cast<unsigned long long>(cl.x) * ch;
+      const RowsBefore a = before(r0), b = before(r0 + n_frames * ch);
+      n_pairs = b.pairs - a.pairs;
+      n_raw_rows = b.raw - a.raw;
+      clip_base[2ull * k] = a.pairs;
+      clip_base[2ull * k + 1] = a.raw;
+      bytes = compact_raw_offset(compact_layout(ch, n_frames), n_pairs) + n_raw_rows * (kFrameI * 2ull);
     }
-    done += __popcll(mask);
+    s[threadIdx.x] = bytes;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+      const unsigned long long t = threadIdx.x >= static_cast<unsigned>(off) ? s[threadIdx.x - off] : 0ull;
+      __syncthreads();
+      s[threadIdx.x] += t;
+      __syncthreads();
+    }
+    const unsigned long long offset = carry + s[threadIdx.x] - bytes;  // exclusive: every size is a multiple of 64
+    const unsigned long long chunk_total = s[1023];
+    __syncthreads();
+    carry += chunk_total;
+    if (k < n_clips) {
+      const bool stored = offset <= arena_bytes && bytes <= arena_bytes - offset;
+      unsigned long long *e = entries + 4ull * k;
+      e[0] = offset;
+      e[1] = bytes;
+      e[2] = n_pairs;
+      e[3] = n_raw_rows | (stored ? 1ull << 32 : 0ull);
+      if (stored) {
+        unsigned long long *h = reinterpret_cast<unsigned long long *>(arena + offset);
+        h[0] = kCompactMagic | (static_cast<unsigned long long>(ch) << 32);  // magic, channels
+        h[1] = n_frames;
+        h[2] = n_pairs;
+        h[3] = n_raw_rows;
+        h[4] = bytes;
+        h[5] = h[6] = h[7] = 0ull;
+      }
+    }
   }
-  // fewer non-zeros than the nnz field claims: fill the rest of the slot (idx 0xFFFF is ignored by
-  // every reader, src/codec.rs:660) so the blob never carries uninitialised bytes
-  for (unsigned pos = done + lane; pos < room; pos += 64) dst[pos] = 0xFFFFu;
+  if (threadIdx.x == 0) *cursor = carry;
+}
+
+__global__ __launch_bounds__(256) void k_store_rows(const unsigned char *__restrict__ records, unsigned M, unsigned ch,
+                                                     unsigned long long rec_bytes, unsigned long long hdr_bytes,
+                                                     const unsigned *__restrict__ loc, const unsigned long long *__restrict__ blk,
+                                                     const unsigned long long *__restrict__ blk_raw,
+                                                     const unsigned long long *__restrict__ clip_base,
+                                                     const uint2 *__restrict__ fmap, const uint2 *__restrict__ clips,
+                                                     const unsigned long long *__restrict__ entries,
+                                                     unsigned char *__restrict__ arena) {
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const unsigned m = blockIdx.x * 4 + w;
+  if (m >= M) return;
+  const unsigned frame = m / ch, c = m % ch;
+  const uint2 fm = fmap[frame];
+  const unsigned long long *e = entries + 4ull * fm.y;
+  if ((e[3] >> 32) == 0) return;  // the clip did not fit
+  const uint2 cl = clips[fm.y];
+  const CompactLayout l = compact_layout(ch, cl.y);
+  unsigned char *blob = arena + e[0];
+  const unsigned long long n_pairs = e[2], m_rel = m - static_cast<unsigned long long>(cl.x) * ch;
+  RowsBefore at = rows_before<kP1RawShift>(loc[m], blk, blk_raw, m);
+  at.pairs -= clip_base[2ull * fm.y];
+  at.raw -= clip_base[2ull * fm.y + 1];
+  const unsigned char *rec = records + static_cast<size_t>(fm.x) * rec_bytes;
+  const bool raw = *reinterpret_cast<const unsigned *>(rec) != 0;
+  const unsigned room = raw ? 0u : store_row_word(rec, c);
+  if (lane == 0) {
+    reinterpret_cast<unsigned *>(blob + l.o_scale)[m_rel] = *reinterpret_cast<const unsigned *>(rec + 8 + 8 * c);  // the scale's bits
+    reinterpret_cast<unsigned *>(blob + l.o_cnt)[m_rel] = room;
+    if (c == 0) blob[l.o_israw + (frame - cl.x)] = raw ? 1 : 0;
+  }
+  if (m_rel == 0) {  // the gaps behind the clip's fixed sections and in front of its raw section: < 64 bytes each
+    const unsigned long long rows = static_cast<unsigned long long>(cl.y) * ch;
+    const unsigned long long gap[4][2] = {{l.o_israw + cl.y, l.o_scale},
+                                          {l.o_scale + 4 * rows, l.o_cnt},
+                                          {l.o_cnt + 4 * rows, l.o_pairs},
+                                          {l.o_pairs + 4 * n_pairs, compact_raw_offset(l, n_pairs)}};
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      if (gap[g][0] + lane < gap[g][1]) blob[gap[g][0] + lane] = 0;
+  }
+  const short *qrow = reinterpret_cast<const short *>(rec + hdr_bytes) + static_cast<size_t>(c) * kFrameI;
+  pack_row(qrow, raw, reinterpret_cast<short4 *>(blob + compact_raw_offset(l, n_pairs) + at.raw * (kFrameI * 2ull)),
+           reinterpret_cast<unsigned *>(blob + l.o_pairs) + at.pairs, room, lane);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1944,6 +2092,48 @@ hipError_t launch_compact(const uint8_t *records, uint32_t M, uint32_t ch, uint6
   else
     hipLaunchKernelGGL(k_pack_rows<false>, dim3((M + 3) / 4), dim3(256), 0, s, records, M, ch, rec, hdr, w.loc, w.blk, w.blk_raw,
                        w.totals, l, blob, fmap, dir);
+  return hipGetLastError();
+}
+
+namespace {
+struct StoreScratch {  // of A1-A3 over M rows of n_clips clips
+  unsigned *loc;
+  unsigned long long *blk, *blk_raw, *clip_base;
+  uint64_t bytes;
+};
+StoreScratch store_scratch(const void *base, uint64_t M, uint64_t n_clips) {
+  const uint64_t nblk = (M + 1023) / 1024;
+  Carve c{reinterpret_cast<uintptr_t>(base)};
+  StoreScratch w;
+  w.loc = c.take<unsigned>(M);
+  w.blk = c.take<unsigned long long>(nblk);
+  w.blk_raw = c.take<unsigned long long>(nblk);
+  w.clip_base = c.take<unsigned long long>(2 * n_clips);
+  w.bytes = c.used;
+  return w;
+}
+}  // namespace
+
+uint64_t compact_store_scratch_bytes(uint64_t M, uint64_t n_clips) { return store_scratch(nullptr, M, n_clips).bytes; }
+
+hipError_t launch_compact_store(const uint8_t *records, uint32_t M, uint32_t ch, const FrameMap *frame_map, const ClipSpan *clips,
+                                uint32_t n_clips, void *scratch, uint8_t *arena, uint64_t arena_bytes, uint64_t *cursor,
+                                glc_store_entry *entries, hipStream_t s) {
+  static_assert(sizeof(ClipSpan) == sizeof(uint2) && sizeof(glc_store_entry) == 32, "read and written by the kernels as laid out here");
+  if (!records || !frame_map || !clips || !scratch || !arena || !cursor || !entries || ch == 0 || M == 0 || n_clips == 0 || M % ch)
+    return hipErrorInvalidValue;
+  if ((reinterpret_cast<uintptr_t>(arena) & 63u) || ((reinterpret_cast<uintptr_t>(cursor) | reinterpret_cast<uintptr_t>(entries)) & 7u))
+    return hipErrorInvalidValue;
+  const StoreScratch w = store_scratch(scratch, M, n_clips);
+  const uint2 *fmap = reinterpret_cast<const uint2 *>(frame_map), *cl = reinterpret_cast<const uint2 *>(clips);
+  auto *e = reinterpret_cast<unsigned long long *>(entries);
+  const unsigned long long hdr = record_header_bytes(ch), rec = record_bytes(ch);
+  const unsigned nblk = (M + 1023) / 1024;
+  hipLaunchKernelGGL(k_store_scan_rows, dim3(nblk), dim3(256), 0, s, records, M, ch, rec, w.loc, w.blk, w.blk_raw, fmap);
+  hipLaunchKernelGGL(k_store_place, dim3(1), dim3(1024), 0, s, w.blk, w.blk_raw, nblk, w.loc, M, ch, cl, n_clips, w.clip_base, arena,
+                     static_cast<unsigned long long>(arena_bytes), reinterpret_cast<unsigned long long *>(cursor), e);
+  hipLaunchKernelGGL(k_store_rows, dim3((M + 3) / 4), dim3(256), 0, s, records, M, ch, rec, hdr, w.loc, w.blk, w.blk_raw, w.clip_base,
+                     fmap, cl, e, arena);
   return hipGetLastError();
 }
 

@@ -613,6 +613,48 @@ int glc_decode_compact_last_status(glc_ctx *ctx, glc_compact_status *status, uin
  * that is not strictly ascending below 1024 - and when cap is too small, with info->bytes filled. */
 int glc_frames_to_compact(const glc_frames *f, void *blob, uint64_t cap, glc_compact_info *info);
 
+/* ---- encode of a batch of device-resident clips into per-clip compact blobs: filling the store -- */
+
+/* What the device says about clip i of glc_encode_batch_device_compact. */
+typedef struct glc_store_entry {   /* 32 bytes, written by the device */
+  uint64_t offset;      /* of the clip's blob from d_arena, a multiple of 64 */
+  uint64_t bytes;       /* size of the blob (its header's `bytes`) */
+  uint64_t n_pairs;
+  uint32_t n_raw_rows;
+  uint32_t stored;      /* 1: the blob is in the arena; 0: it did not fit, nothing of it was written */
+} glc_store_entry;
+
+/* Sum of glc_compact_bound over the clips of a layout: an arena of that many bytes holds them all from cursor 0.
+ * Saturates at UINT64_MAX; 0 for a null layout, channels == 0 or a clip the encoder refuses. */
+uint64_t glc_compact_store_bound(const glc_clip_layout *in);
+
+/* glc_encode_range_device + glc_compact_device_records of every clip of a batch (any glc_clip_layout) in one call,
+ * the write side of the store: the blob of clip i holds exactly the bytes those two calls give for clip i alone -
+ * the single-stream compact blob of its frames, padding zeroed, rows of raw frames with the quantiser's scale -
+ * so glc_decode_device_compact, glc_decode_batch_device_compact and glc_frames_from_compact read it as it stands.
+ * Placement is the device's: *d_cursor (a device uint64_t the caller owns, 8-byte aligned) is the first free byte
+ * of the arena.  Every round reads it, rounds it up to 64 and places its clips in clip order, clip i at the
+ * exclusive running sum of the blob sizes (each a multiple of 64), and leaves the cursor at the end of that sum:
+ * offsets ascend with i across rounds and calls, and consecutive calls with the same cursor append with no
+ * synchronisation between them.  A clip is stored when offset + bytes <= arena_bytes.  The cursor keeps
+ * counting whether or not a clip was stored, so the stored clips are a prefix of everything ever appended, the
+ * entry of a clip that was not stored still reports the offset and size it would have had (stored == 0), and the
+ * final cursor is the arena size that would have sufficed.  No byte of the arena outside the stored blobs is
+ * written, no element of d_pcm outside the clips' true samples is read (padding may hold NaN).
+ * d_entries[i] (device, 8-byte aligned, in->n_clips of them) is written for every clip.
+ * Rounds as in glc_roundtrip_batch_device: one gather, one transform and quantiser chain and three pack launches
+ * per ROUND whatever the number of clips; a clip longer than a round is staged whole, encoded into a records
+ * workspace of n_frames * glc_record_bytes and packed as a round of its own.  Queued on glc_ctx_stream(ctx), NOT
+ * synchronised, nothing is copied to the host; the call blocks only where a workspace has to grow and on the
+ * pinned table image of the previous batch call.  Afterwards no stream is resident and an open decode session is
+ * closed.
+ * GLC_EINVAL, before anything is queued: a null pointer, d_arena not 64-byte aligned, d_cursor / d_entries not
+ * 8-byte aligned, what glc_roundtrip_batch_device refuses of a layout (the message names the clip), an arena or
+ * entries range that overlaps the input extent.  n_clips == 0 is GLC_OK and leaves the cursor alone. */
+int glc_encode_batch_device_compact(glc_ctx *ctx, const float *d_pcm, const glc_clip_layout *in,
+                                    void *d_arena, uint64_t arena_bytes,
+                                    uint64_t *d_cursor, glc_store_entry *d_entries);
+
 /* ---- tables (for inspection / parity tests) ---------------------------------------------- */
 
 /* Copies of the host tables of a context: MdctTables.cos_table [1024*2048] (row k), window

@@ -190,6 +190,9 @@ class EncodedAudio {
   glc_frames *h_ = nullptr;
 };
 
+// Arena bytes that hold the blobs of every clip of a layout whatever their content (glc_compact_store_bound).
+inline uint64_t compact_store_bound(const glc_clip_layout &in) { return glc_compact_store_bound(&in); }
+
 class Encoder {
  public:
   // Encoder::new(sample_rate: u32) — src/codec.rs:406
@@ -285,6 +288,12 @@ class Encoder {
     glc_frames *h = nullptr;
     detail::check(glc_frames_from_device_records(ctx_, d_records, n_frames, n_samples, channels, &h), ctx_);
     return EncodedAudio(h);
+  }
+  // glc_encode_batch_device_compact: every clip of a device-resident batch into its own compact blob, placed back to
+  // back in d_arena from *d_cursor by the device; d_entries[i] says where clip i went.  Queued, not synchronised.
+  void encode_batch_device_compact(const float *d_pcm, const glc_clip_layout &in, void *d_arena, uint64_t arena_bytes,
+                                   uint64_t *d_cursor, glc_store_entry *d_entries) {
+    detail::check(glc_encode_batch_device_compact(ctx_, d_pcm, &in, d_arena, arena_bytes, d_cursor, d_entries), ctx_);
   }
   void synchronize() { detail::check(glc_ctx_synchronize(ctx_), ctx_); }
   glc_ctx *ctx() { return ctx_; }

@@ -92,6 +92,16 @@ int glc_debug_overlap_add_device(glc_ctx *ctx, const float *d_blocks, int64_t bl
 int glc_debug_compact_batch_device(glc_ctx *ctx, const void *d_records, const uint64_t *clip_frames, uint64_t n_clips,
                                    uint16_t channels, void *d_blob, uint64_t cap, glc_compact_info *info);
 
+/* The per-clip pack (A1-A3) alone, exactly as a round of glc_encode_batch_device_compact launches it - frame map, clip
+ * table and launch are the driver's own code - on caller-supplied records of a virtual stream laid out as for
+ * glc_debug_compact_batch_device: clip i of clip_frames[i] >= 1 frames, one junk record behind each clip.  d_arena,
+ * arena_bytes, d_cursor and d_entries as in glc_encode_batch_device_compact (include/glc.h).  Queued on the context's
+ * stream behind the table upload; not synchronised.  tests/test_compact_store.py drives the pack through this with
+ * junk records that hold dense rows and raw flags, nnz fields that disagree with their rows and 1100 clips in a round. */
+int glc_debug_compact_store_device(glc_ctx *ctx, const void *d_records, const uint64_t *clip_frames, uint64_t n_clips,
+                                   uint16_t channels, void *d_arena, uint64_t arena_bytes, uint64_t *d_cursor,
+                                   glc_store_entry *d_entries);
+
 /* R2 (launch_rows_from_compact) alone, exactly as glc_decode_device_compact launches it for ONE blob of `n_frames`
  * frames at d_blob (64-byte aligned, blob_bytes >= the fixed sections): the row tables it builds come back to
  * the host - M = n_frames * channels entries each, any pointer may be NULL - with the status words.  row_begin
