@@ -68,6 +68,16 @@ class GlcClipLayout(C.Structure):
     ]
 
 
+class GlcCrop(C.Structure):
+    """glc_crop (include/glc.h): a window of a decoded clip, in samples per channel."""
+    _fields_ = [("start", C.c_uint64), ("length", C.c_uint64)]
+
+
+class GlcCropPlan(C.Structure):
+    """glc_crop_plan (include/glc.h): the frames and hops a crop needs."""
+    _fields_ = [("first_frame", C.c_uint64), ("n_frames", C.c_uint64), ("first_hop", C.c_uint64), ("n_hops", C.c_uint64)]
+
+
 class GlcStoreEntry(C.Structure):
     """glc_store_entry (include/glc.h): where the device put a clip's blob in the arena."""
     _fields_ = [
@@ -234,6 +244,9 @@ SIGNATURES = {
     "glc_decode_device_compact": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint16, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "glc_decode_batch_device_compact": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _vp,
                                                   C.POINTER(GlcClipLayout)]),
+    "glc_plan_crop": (C.c_int, [C.c_uint64, C.c_uint16, C.POINTER(GlcCrop), C.POINTER(GlcCropPlan)]),
+    "glc_decode_crops_device_compact": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                                  C.POINTER(GlcCrop), _vp, C.POINTER(GlcClipLayout)]),
     "glc_decode_compact_last_status": (C.c_int, [_vp, C.POINTER(GlcCompactStatus), C.c_uint64]),
     "glc_frames_to_compact": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(GlcCompactInfo)]),
     "glc_compact_store_bound": (C.c_uint64, [C.POINTER(GlcClipLayout)]),

@@ -21,7 +21,7 @@ from typing import Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import (FRAMES_HOOK, GLC_EINVAL, GLC_PCM_F32, GLC_PCM_S16, GLC_PCM_S32, GlcClipLayout, GlcCompactInfo, GlcCompactStatus, GlcError,
+from ._lib import (FRAMES_HOOK, GLC_EINVAL, GLC_PCM_F32, GLC_PCM_S16, GLC_PCM_S32, GlcClipLayout, GlcCompactInfo, GlcCompactStatus, GlcCrop, GlcCropPlan, GlcError,
                    GlcFramesGather, GlcFramesView, GlcInfo, GlcPlan, GlcRoundtripInfo, check, lib)
 
 FRAME_SIZE = 2048        # src/codec.rs:15
@@ -333,6 +333,17 @@ def plan_encode(n_samples: int, channels: int) -> GlcPlan:
     """Frame count / padding of Encoder::encode (src/codec.rs:433-455); raises where it panics."""
     p = GlcPlan()
     check(lib.glc_plan_encode(n_samples, channels, C.byref(p)))
+    return p
+
+
+def plan_crop(n_samples: int, channels: int, start: int, length: int) -> GlcCropPlan:
+    """The frames [first_frame, first_frame + n_frames) and hops [first_hop, first_hop + n_hops) that the crop
+    [start, start + length) (samples per channel) of a clip of n_samples interleaved samples needs (glc_plan_crop);
+    raises where it refuses: an empty crop, one that ends behind the clip, a clip the encoder refuses."""
+    if start < 0 or length < 0:
+        raise GlcError(GLC_EINVAL, "plan_crop: negative start or length")
+    p = GlcCropPlan()
+    check(lib.glc_plan_crop(n_samples, channels, C.byref(GlcCrop(start, length)), C.byref(p)))
     return p
 
 
@@ -756,23 +767,11 @@ class Decoder(_Ctx):
             self.set_stream(0)
         return out[:n]
 
-    def decode_compact_batch_tensor(self, blobs, n_samples, lengths=None, planar: bool = True, out=None):
-        """Decode one compact blob per clip into ONE padded batch tensor (glc_decode_batch_device_compact).  blobs: B
-        1-D uint8 CUDA tensors (64-byte aligned, anywhere in device memory); n_samples: per clip its interleaved
-        length; lengths: per clip its samples per channel (default n_samples[i] // channels).  out: a float32 CUDA
-        tensor (B, C, T) (planar) or (B, T, C) with innermost stride 1 - a slice of something bigger works - or
-        None: a new zero-filled one with T = max(lengths).  The first lengths[i] samples of clip i are what
-        decode_compact_tensor gives for that blob; no other element is written.  One launch chain per round
-        whatever B.  Queued on torch's current stream; returns the output."""
+    def _batch_out(self, blobs, lens, planar: bool, out):
+        """The output tensor of a decode_compact_* batch call (None: a new zero-filled one of T = max(lens)), checked,
+        and its glc_clip_layout (with the array the layout points into, to be kept alive)."""
         import torch
-        b = len(blobs)
-        ch = self.channels
-        ns = [int(v) for v in (n_samples.tolist() if hasattr(n_samples, "tolist") else n_samples)]
-        lens = [v // ch for v in ns] if lengths is None else \
-            [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-        if len(ns) != b or len(lens) != b:
-            raise GlcError(GLC_EINVAL, f"n_samples and lengths must hold {b} values")
-        blobs = [self._blob_tensor(t, f"blobs[{i}]", self.device) for i, t in enumerate(blobs)]
+        b, ch = len(blobs), self.channels
         if out is None:
             t_max = max(lens, default=0)
             dev = blobs[0].device if b else torch.device("cuda", self.device)
@@ -795,12 +794,63 @@ class Decoder(_Ctx):
         lens_arr = (C.c_uint64 * max(b, 1))(*lens)
         lay = GlcClipLayout(b, ch, 1 if planar else 0, out.stride(0), out.stride(1) if planar else 0, ot,
                             C.cast(lens_arr, C.POINTER(C.c_uint64)))
+        return out, lay, lens_arr
+
+    def decode_compact_batch_tensor(self, blobs, n_samples, lengths=None, planar: bool = True, out=None):
+        """Decode one compact blob per clip into ONE padded batch tensor (glc_decode_batch_device_compact).  blobs: B
+        1-D uint8 CUDA tensors (64-byte aligned, anywhere in device memory); n_samples: per clip its interleaved
+        length; lengths: per clip its samples per channel (default n_samples[i] // channels).  out: a float32 CUDA
+        tensor (B, C, T) (planar) or (B, T, C) with innermost stride 1 - a slice of something bigger works - or
+        None: a new zero-filled one with T = max(lengths).  The first lengths[i] samples of clip i are what
+        decode_compact_tensor gives for that blob; no other element is written.  One launch chain per round
+        whatever B.  Queued on torch's current stream; returns the output."""
+        b = len(blobs)
+        ch = self.channels
+        ns = [int(v) for v in (n_samples.tolist() if hasattr(n_samples, "tolist") else n_samples)]
+        lens = [v // ch for v in ns] if lengths is None else \
+            [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+        if len(ns) != b or len(lens) != b:
+            raise GlcError(GLC_EINVAL, f"n_samples and lengths must hold {b} values")
+        blobs = [self._blob_tensor(t, f"blobs[{i}]", self.device) for i, t in enumerate(blobs)]
+        out, lay, _keep = self._batch_out(blobs, lens, planar, out)
         ptrs = (C.c_void_p * max(b, 1))(*[t.data_ptr() for t in blobs])
         sizes = (C.c_uint64 * max(b, 1))(*[t.numel() for t in blobs])
         ns_arr = (C.c_uint64 * max(b, 1))(*ns)
         self._enter_torch_stream(out.device)
         try:
             check(lib.glc_decode_batch_device_compact(self._h, ptrs, sizes, ns_arr, C.c_void_p(out.data_ptr()), C.byref(lay)),
+                  self._h)
+        finally:
+            self.set_stream(0)
+        self._compact_clips = b
+        return out
+
+    def decode_compact_crops_tensor(self, blobs, n_samples, starts, lengths, planar: bool = True, out=None):
+        """Decode a WINDOW of each of B stored clips into one padded batch tensor (glc_decode_crops_device_compact):
+        entry i is samples [starts[i], starts[i] + lengths[i]) per channel of what decode_compact_tensor gives for
+        blobs[i] (n_samples[i] its interleaved length), bit for bit; only the frames a window needs are decoded.
+        lengths: per crop, or one int for all.  The same blob may appear any number of times.  out: as in
+        decode_compact_batch_tensor ((B, C, L) planar / (B, L, C), a slice of something bigger works), or None: a
+        new zero-filled one with L = max(lengths).  No element outside the crops is written.  One launch chain per
+        round whatever B.  Queued on torch's current stream; returns the output.  last_compact_status() afterwards:
+        one status per crop, bad rows counted inside the window (in the stream's row numbering)."""
+        b = len(blobs)
+        as_ints = lambda v: [int(x) for x in (v.tolist() if hasattr(v, "tolist") else v)]
+        ns, st = as_ints(n_samples), as_ints(starts)
+        lens = [int(lengths)] * b if isinstance(lengths, (int, np.integer)) else as_ints(lengths)
+        if len(ns) != b or len(st) != b or len(lens) != b:
+            raise GlcError(GLC_EINVAL, f"n_samples, starts and lengths must hold {b} values")
+        if any(v < 0 for v in st):
+            raise GlcError(GLC_EINVAL, "starts must not be negative")
+        blobs = [self._blob_tensor(t, f"blobs[{i}]", self.device) for i, t in enumerate(blobs)]
+        out, lay, _keep = self._batch_out(blobs, lens, planar, out)
+        ptrs = (C.c_void_p * max(b, 1))(*[t.data_ptr() for t in blobs])
+        sizes = (C.c_uint64 * max(b, 1))(*[t.numel() for t in blobs])
+        ns_arr = (C.c_uint64 * max(b, 1))(*ns)
+        crops = (GlcCrop * max(b, 1))(*[GlcCrop(a, n) for a, n in zip(st, lens)])
+        self._enter_torch_stream(out.device)
+        try:
+            check(lib.glc_decode_crops_device_compact(self._h, ptrs, sizes, ns_arr, crops, C.c_void_p(out.data_ptr()), C.byref(lay)),
                   self._h)
         finally:
             self.set_stream(0)

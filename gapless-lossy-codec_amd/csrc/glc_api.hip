@@ -1845,12 +1845,17 @@ inline uint64_t count_hop_descs(const glc::Trim &trim, uint64_t per_hop, uint64_
 
 // All descriptors of one clip of a batch round.  `lng` (the one clip of a round of its own, longer than a decode
 // round): round by round, block slots counted in the ring (frame f0 - 1 of a round in slot 0); otherwise flat, the
-// clip's frame 0 in block slot `real`.
+// clip's frame 0 in block slot `real`.  `win` (a crop, `trim` what it keeps): only the window's frames have blocks -
+// its first frame is the one in slot `real`, or the first of the ring rounds - and only its hops are described.
 glc::HopDescStrided *write_clip_descs(glc::HopDescStrided *d, bool lng, uint64_t nf, uint32_t ch, const glc::Trim &trim,
-                                      uint64_t real, uint64_t dst, bool planes, uint64_t cstride) {
-  if (!lng) return write_hop_descs(d, nf, ch, trim, 0, nf + 1, static_cast<int64_t>(real), dst, planes, cstride);
-  for (uint64_t f0 = 0; f0 < nf; f0 += kDecodeChunkFrames) {
-    const uint64_t f1 = std::min(nf, f0 + kDecodeChunkFrames);
+                                      uint64_t real, uint64_t dst, bool planes, uint64_t cstride, const glc_crop_plan *win = nullptr) {
+  const uint64_t fb = win ? win->first_frame : 0, fe = win ? fb + win->n_frames : nf;
+  if (!lng) {
+    const uint64_t h0 = win ? win->first_hop : 0, h1 = win ? h0 + win->n_hops : nf + 1;
+    return write_hop_descs(d, nf, ch, trim, h0, h1, static_cast<int64_t>(real) - static_cast<int64_t>(fb), dst, planes, cstride);
+  }
+  for (uint64_t f0 = fb; f0 < fe; f0 += kDecodeChunkFrames) {
+    const uint64_t f1 = std::min(fe, f0 + kDecodeChunkFrames);
     d = write_hop_descs(d, nf, ch, trim, f0, f1 + (f1 == nf ? 1 : 0), 1 - static_cast<int64_t>(f0), dst, planes, cstride);
   }
   return d;
@@ -2795,25 +2800,32 @@ int cd_check_blob(glc_ctx *ctx, const std::string &who, const void *d_blob, uint
 }
 
 // A blob of `nf` frames through R2 (one pass over all its rows, tables in rt_rows) and the rounds of the family.
+// `win` (a crop, g.trim what it keeps): the windowed R2 over the window's rows, and the rounds of its frames only.
 int cd_decode_one(glc_ctx *ctx, const RtGeom &g, const void *d_blob, uint64_t blob_bytes, glc::CompactStatus *d_status,
-                  float *d_out, const glc::HopDescStrided *desc, bool planar, float *sink_out) {
-  const uint32_t M = static_cast<uint32_t>(g.n_frames * g.ch);
+                  float *d_out, const glc::HopDescStrided *desc, bool planar, float *sink_out, const glc_crop_plan *win = nullptr) {
+  const uint64_t fb = win ? win->first_frame : 0, fe = win ? fb + win->n_frames : g.n_frames;
+  const uint32_t M = static_cast<uint32_t>((fe - fb) * g.ch), M_blob = static_cast<uint32_t>(g.n_frames * g.ch);
   const size_t slot = static_cast<size_t>(g.ch) * glc::kFrame;
   int rc = rt_reserve(ctx, ctx->blocks, (g.round + 1) * slot * sizeof(float));
-  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rt_rows, glc::rows_from_compact_bytes(M));  // 32 B per row of the STREAM
+  // 32 B per row of the STREAM, or of the window
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rt_rows, win ? glc::rows_from_compact_window_bytes(M) : glc::rows_from_compact_bytes(M));
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rt_edge, 2 * g.per_hop * sizeof(float));
   if (rc == GLC_OK) rc = reserve_d1_plan(ctx, g.round, g.ch);
   if (rc != GLC_OK) return rc;
-  const glc::CompactBlob one{reinterpret_cast<uintptr_t>(d_blob), blob_bytes, 0u, M, {0u, 0u}};
+  const uint32_t front = static_cast<uint32_t>(fb * g.ch);
+  const glc::CompactBlob one{reinterpret_cast<uintptr_t>(d_blob), blob_bytes, 0u, M_blob, {win ? front : 0u, win ? M : 0u}};
   glc::DecodeRows rows{};
-  GLC_HIP(ctx, glc::launch_rows_from_compact(nullptr, one, 1, M, g.ch, d_blob, ctx->rt_rows.p, d_status, ctx->stream, &rows));
-  for (uint64_t f0 = 0; f0 < g.n_frames; f0 += g.round) {
-    const uint64_t nf = std::min(g.round, g.n_frames - f0), f1 = f0 + nf;
+  if (win)
+    GLC_HIP(ctx, glc::launch_rows_from_compact_window(nullptr, one, 1, M, g.ch, front, d_blob, ctx->rt_rows.p, d_status, ctx->stream, &rows));
+  else
+    GLC_HIP(ctx, glc::launch_rows_from_compact(nullptr, one, 1, M, g.ch, d_blob, ctx->rt_rows.p, d_status, ctx->stream, &rows));
+  for (uint64_t f0 = fb; f0 < fe; f0 += g.round) {
+    const uint64_t nf = std::min(g.round, fe - f0), f1 = f0 + nf;
     // the round's descriptors: those of hops [f0, f1 (+ 1)) that keep anything (rtb_impl)
     const uint64_t nd = desc ? count_hop_descs(g.trim, g.per_hop, f0, f1 + (f1 == g.n_frames ? 1 : 0)) : 0;
     const RtStridedSink sink{desc, static_cast<uint32_t>(nd), planar, sink_out};
     if (desc) desc += nd;
-    rc = rt_decode_round_rows<float>(ctx, g, rows, static_cast<uint32_t>(f0 * g.ch), f0, nf, d_out, desc ? &sink : nullptr);
+    rc = rt_decode_round_rows<float>(ctx, g, rows, static_cast<uint32_t>((f0 - fb) * g.ch), f0, nf, d_out, desc ? &sink : nullptr);
     if (rc != GLC_OK) return rc;
   }
   return GLC_OK;
@@ -2828,9 +2840,12 @@ struct CdRound {
   uint64_t n_desc = 0;
 };
 
-int cdb_impl(glc_ctx *ctx, const void *const *d_blobs, const uint64_t *blob_bytes, float *d_out, const RtbLayout &out,
-             const std::vector<glc_plan> &plans) {
+// `crops` / `wins` (both or neither; glc_decode_crops_device_compact): entry i is the window wins[i] = plan_crop of
+// crops[i] of its blob - a round counts, tabulates and transforms the windows' frames only.
+int cdb_impl(glc_ctx *ctx, const char *who, const void *const *d_blobs, const uint64_t *blob_bytes, float *d_out, const RtbLayout &out,
+             const std::vector<glc_plan> &plans, const glc_crop *crops = nullptr, const glc_crop_plan *wins = nullptr) {
   const uint64_t n = out.l->n_clips;
+  auto frames_of = [&](uint64_t i) { return wins ? wins[i].n_frames : plans[i].n_frames; };
   const uint32_t ch = out.l->channels;
   const size_t slot = static_cast<size_t>(ch) * glc::kFrame;
   // rounds as glc_decode_batch packs them: whole clips of together at most kDecodeChunkFrames frames (+ a tail hop each)
@@ -2846,15 +2861,15 @@ int cdb_impl(glc_ctx *ctx, const void *const *d_blobs, const uint64_t *blob_byte
       hops = 0;
     };
     for (uint64_t i = 0; i < n; ++i) {
-      const uint64_t v = plans[i].n_frames + 1;
+      const uint64_t v = frames_of(i) + 1;
       if (v > hop_budget) {
         flush(i);
-        cur.n = 1, cur.lng = true, cur.n_real = plans[i].n_frames;
+        cur.n = 1, cur.lng = true, cur.n_real = frames_of(i);
         flush(i + 1);
         continue;
       }
       if (hops + v > hop_budget) flush(i);
-      cur.n += 1, cur.n_real += plans[i].n_frames, hops += v;
+      cur.n += 1, cur.n_real += frames_of(i), hops += v;
     }
     flush(n);
   }
@@ -2867,16 +2882,17 @@ int cdb_impl(glc_ctx *ctx, const void *const *d_blobs, const uint64_t *blob_byte
   uint64_t max_rows = 0, max_blocks = 0, max_frames = 0;
   for (CdRound &r : rounds) {
     if (!r.lng) r.o_dir = place(r.n * sizeof(glc::CompactBlob));
-    for (uint64_t i = r.first; i < r.first + r.n; ++i) r.n_desc += rtb_hops_kept(out.len(i), ch);
+    for (uint64_t i = r.first; i < r.first + r.n; ++i) r.n_desc += wins ? wins[i].n_hops : rtb_hops_kept(out.len(i), ch);
     r.o_desc = place(r.n_desc * sizeof(glc::HopDescStrided));
     const uint64_t rf = r.lng ? std::min<uint64_t>(kDecodeChunkFrames, r.n_real) : r.n_real;
-    max_rows = std::max(max_rows, r.n_real * ch);  // R2 takes a long clip's rows in one pass
+    max_rows = std::max(max_rows, r.n_real * ch);  // R2 takes a long clip's (or window's) rows in one pass
     max_blocks = std::max(max_blocks, rf + (r.lng ? 1 : 0));
     max_frames = std::max(max_frames, rf);
   }
   rt_forget_streams(ctx);
   ctx->cd_status_n = 0;
-  int rc = rt_reserve(ctx, ctx->rt_rows, glc::rows_from_compact_bytes(static_cast<uint32_t>(max_rows)));
+  int rc = rt_reserve(ctx, ctx->rt_rows, wins ? glc::rows_from_compact_window_bytes(static_cast<uint32_t>(max_rows))
+                                              : glc::rows_from_compact_bytes(static_cast<uint32_t>(max_rows)));
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->blocks, max_blocks * slot * sizeof(float));
   if (rc == GLC_OK) rc = reserve_d1_plan(ctx, max_frames, ch);
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rtb_tab, tab);
@@ -2890,21 +2906,26 @@ int cdb_impl(glc_ctx *ctx, const void *const *d_blobs, const uint64_t *blob_byte
   uint8_t *img = static_cast<uint8_t *>(ctx->rtb_stage.p);
   uint8_t *d_tab = static_cast<uint8_t *>(ctx->rtb_tab.p);
   const bool out_planes = out.planes();
+  // what entry i keeps of its un-trimmed stream: the clip, or the crop behind the delay
+  auto trim_of = [&](uint64_t i) {
+    const glc::Trim whole = glc::gapless_trim(plans[i].n_frames, ch, plans[i].encoder_delay, crops ? plans[i].per_channel * ch : out.len(i) * ch);
+    return crops ? glc::Trim{whole.start + crops[i].start * ch, crops[i].length * ch} : whole;
+  };
   for (const CdRound &r : rounds) {
     auto *dir = reinterpret_cast<glc::CompactBlob *>(img + r.o_dir);
     auto *desc = reinterpret_cast<glc::HopDescStrided *>(img + r.o_desc);
     uint64_t real = 0;
     for (uint64_t k = 0; k < r.n; ++k) {
       const uint64_t i = r.first + k, nf = plans[i].n_frames;
-      const glc::Trim trim = glc::gapless_trim(nf, ch, plans[i].encoder_delay, out.len(i) * ch);
+      const uint32_t w0 = wins ? static_cast<uint32_t>(wins[i].first_frame * ch) : 0u, w1 = wins ? static_cast<uint32_t>(wins[i].n_frames * ch) : 0u;
       if (!r.lng)
         dir[k] = glc::CompactBlob{reinterpret_cast<uintptr_t>(d_blobs[i]), blob_bytes[i], static_cast<uint32_t>(real * ch),
-                                  static_cast<uint32_t>(nf * ch), {0u, 0u}};
-      desc = write_clip_descs(desc, r.lng, nf, ch, trim, real, out.at(i), out_planes, out.l->channel_stride);
-      real += nf;
+                                  static_cast<uint32_t>(nf * ch), {w0, w1}};
+      desc = write_clip_descs(desc, r.lng, nf, ch, trim_of(i), real, out.at(i), out_planes, out.l->channel_stride, wins ? &wins[i] : nullptr);
+      real += frames_of(i);
     }
     if (static_cast<uint64_t>(desc - reinterpret_cast<glc::HopDescStrided *>(img + r.o_desc)) != r.n_desc)
-      return fail(ctx, GLC_EHIP, "glc_decode_batch_device_compact: hop count arithmetic is inconsistent");
+      return fail(ctx, GLC_EHIP, std::string(who) + ": hop count arithmetic is inconsistent");
   }
   hipStream_t st = ctx->stream;
   GLC_HIP(ctx, hipMemcpyAsync(d_tab, img, tab, hipMemcpyHostToDevice, st));
@@ -2916,8 +2937,9 @@ int cdb_impl(glc_ctx *ctx, const void *const *d_blobs, const uint64_t *blob_byte
     const auto *desc = reinterpret_cast<const glc::HopDescStrided *>(d_tab + r.o_desc);
     if (r.lng) {
       const uint64_t i = r.first;
-      const RtGeom g = rt_geom(r.n_real, ch, plans[i], out.len(i) * ch);
-      rc = cd_decode_one(ctx, g, d_blobs[i], blob_bytes[i], d_status + i, nullptr, desc, out_planes, d_out);
+      RtGeom g = rt_geom(plans[i].n_frames, ch, plans[i], out.len(i) * ch);
+      g.trim = trim_of(i);
+      rc = cd_decode_one(ctx, g, d_blobs[i], blob_bytes[i], d_status + i, nullptr, desc, out_planes, d_out, wins ? &wins[i] : nullptr);
       if (rc != GLC_OK) return rc;
       continue;
     }
@@ -2927,9 +2949,17 @@ int cdb_impl(glc_ctx *ctx, const void *const *d_blobs, const uint64_t *blob_byte
     for (uint64_t i = r.first; i < r.first + r.n; ++i) base = std::min(base, reinterpret_cast<uintptr_t>(d_blobs[i]));
     const uint32_t M = static_cast<uint32_t>(r.n_real * ch);
     glc::DecodeRows rows{};
-    GLC_HIP(ctx, glc::launch_rows_from_compact(reinterpret_cast<const glc::CompactBlob *>(d_tab + r.o_dir), glc::CompactBlob{},
-                                               static_cast<uint32_t>(r.n), M, ch, reinterpret_cast<const void *>(base),
-                                               ctx->rt_rows.p, d_status + r.first, st, &rows));
+    const auto *d_dir = reinterpret_cast<const glc::CompactBlob *>(d_tab + r.o_dir);
+    if (wins) {
+      uint64_t front = 0;  // the most rows any window of the round has in front
+      for (uint64_t i = r.first; i < r.first + r.n; ++i) front = std::max(front, wins[i].first_frame * ch);
+      GLC_HIP(ctx, glc::launch_rows_from_compact_window(d_dir, glc::CompactBlob{}, static_cast<uint32_t>(r.n), M, ch,
+                                                        static_cast<uint32_t>(front), reinterpret_cast<const void *>(base),
+                                                        ctx->rt_rows.p, d_status + r.first, st, &rows));
+    } else {
+      GLC_HIP(ctx, glc::launch_rows_from_compact(d_dir, glc::CompactBlob{}, static_cast<uint32_t>(r.n), M, ch,
+                                                 reinterpret_cast<const void *>(base), ctx->rt_rows.p, d_status + r.first, st, &rows));
+    }
     // (D1's 8-frame units may span two clips: that only widens a union)
     GLC_HIP(ctx, glc::launch_imdct_rows(ctx->dev, rows, 0, M, ch, blocks, st, ctx->d1_variant, ctx->dec_plan.p,
                                         ctx->dec_plan.p ? ctx->dec_plan_groups : 0, false));
@@ -2971,26 +3001,35 @@ int glc_decode_device_compact(glc_ctx *ctx, const void *d_blob, uint64_t blob_by
   return rc;
 }
 
-int glc_decode_batch_device_compact(glc_ctx *ctx, const void *const *d_blobs, const uint64_t *blob_bytes, const uint64_t *n_samples,
-                                    float *d_out, const glc_clip_layout *out) {
-  const std::string w("glc_decode_batch_device_compact");
+// glc_decode_batch_device_compact and (crops) glc_decode_crops_device_compact: the checks, then cdb_impl.
+static int cd_batch_call(glc_ctx *ctx, const char *who, const void *const *d_blobs, const uint64_t *blob_bytes, const uint64_t *n_samples,
+                         const glc_crop *crops, bool windows, float *d_out, const glc_clip_layout *out) {
+  const std::string w(who);
   if (!ctx) return GLC_EINVAL;
   if (!out) return fail(ctx, GLC_EINVAL, w + ": null argument");
   if (out->n_clips == 0) return GLC_OK;
-  if (!d_blobs || !blob_bytes || !n_samples || !d_out) return fail(ctx, GLC_EINVAL, w + ": null argument");
+  if (!d_blobs || !blob_bytes || !n_samples || !d_out || (windows && !crops)) return fail(ctx, GLC_EINVAL, w + ": null argument");
   if (out->channels == 0) return fail(ctx, GLC_EINVAL, w + ": channels == 0");
   if (reinterpret_cast<uintptr_t>(d_out) & 3u) return fail(ctx, GLC_EINVAL, w + ": output pointer not aligned to its sample size");
   const RtbLayout lo{out};
   const uint64_t n = out->n_clips, ch = out->channels;
   try {  // no C++ exception may cross the C ABI
     std::vector<glc_plan> plans(n);
+    std::vector<glc_crop_plan> wins(windows ? n : 0);
     for (uint64_t i = 0; i < n; ++i) {
       const std::string clip = w + ": clip " + std::to_string(i);
       plans[i] = glc::plan_encode(n_samples[i], out->channels);
       if (plans[i].n_frames == 0)
         return fail(ctx, GLC_EINVAL, clip + ": the reference encoder panics on this input (<= 512 samples per channel, or ragged channels)");
       if (plans[i].n_frames * ch > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, clip + ": stream too long");
-      if (lo.len(i) * ch != n_samples[i]) return fail(ctx, GLC_EINVAL, clip + ": the layout's length is not the decoded length");
+      if (windows) {
+        if (n_samples[i] % ch) return fail(ctx, GLC_EINVAL, clip + ": n_samples is no multiple of the channel count");
+        if (!glc::plan_crop(n_samples[i], out->channels, crops[i], &wins[i]))
+          return fail(ctx, GLC_EINVAL, clip + ": an empty crop, or one that ends behind the clip");
+        if (lo.len(i) != crops[i].length) return fail(ctx, GLC_EINVAL, clip + ": the layout's length is not the crop's");
+      } else if (lo.len(i) * ch != n_samples[i]) {
+        return fail(ctx, GLC_EINVAL, clip + ": the layout's length is not the decoded length");
+      }
       if (lo.planes() && out->channel_stride < lo.len(i)) return fail(ctx, GLC_EINVAL, clip + ": channel_stride is smaller than a plane");
       if (n > 1 && out->clip_stride < lo.occupies(i)) return fail(ctx, GLC_EINVAL, clip + ": clip_stride is smaller than the clip");
       const int rc = cd_check_blob(ctx, clip, d_blobs[i], blob_bytes[i], out->channels, plans[i].n_frames);
@@ -3002,10 +3041,20 @@ int glc_decode_batch_device_compact(glc_ctx *ctx, const void *const *d_blobs, co
       if (a0 < b1 && b0 < a1) return fail(ctx, GLC_EINVAL, w + ": clip " + std::to_string(i) + ": the output extent overlaps the blob");
     }
     DeviceGuard guard(ctx->device);
-    return cdb_impl(ctx, d_blobs, blob_bytes, d_out, lo, plans);
+    return cdb_impl(ctx, who, d_blobs, blob_bytes, d_out, lo, plans, windows ? crops : nullptr, windows ? wins.data() : nullptr);
   } catch (const std::bad_alloc &) {
     return fail(ctx, GLC_ENOMEM, w + ": host allocation failed");
   }
+}
+
+int glc_decode_batch_device_compact(glc_ctx *ctx, const void *const *d_blobs, const uint64_t *blob_bytes, const uint64_t *n_samples,
+                                    float *d_out, const glc_clip_layout *out) {
+  return cd_batch_call(ctx, "glc_decode_batch_device_compact", d_blobs, blob_bytes, n_samples, nullptr, false, d_out, out);
+}
+
+int glc_decode_crops_device_compact(glc_ctx *ctx, const void *const *d_blobs, const uint64_t *blob_bytes, const uint64_t *n_samples,
+                                    const glc_crop *crops, float *d_out, const glc_clip_layout *out) {
+  return cd_batch_call(ctx, "glc_decode_crops_device_compact", d_blobs, blob_bytes, n_samples, crops, true, d_out, out);
 }
 
 int glc_decode_compact_last_status(glc_ctx *ctx, glc_compact_status *status, uint64_t n_clips) {
@@ -3310,6 +3359,36 @@ int glc_debug_rows_from_compact(glc_ctx *ctx, const void *d_blob, uint64_t blob_
   glc::DecodeRows rows{};
   GLC_HIP(ctx, glc::launch_rows_from_compact(nullptr, one, 1, M, channels, d_blob, ctx->rt_rows.p,
                                              static_cast<glc::CompactStatus *>(ctx->cd_status.p), ctx->stream, &rows));
+  GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (row_begin) GLC_HIP(ctx, hipMemcpy(row_begin, rows.row_begin, M * 8ull, hipMemcpyDeviceToHost));
+  if (row_cnt) GLC_HIP(ctx, hipMemcpy(row_cnt, rows.row_cnt, M * 4ull, hipMemcpyDeviceToHost));
+  if (row_scale) GLC_HIP(ctx, hipMemcpy(row_scale, rows.row_scale, M * 4ull, hipMemcpyDeviceToHost));
+  if (row_raw) GLC_HIP(ctx, hipMemcpy(row_raw, rows.row_raw, M * 8ull, hipMemcpyDeviceToHost));
+  if (row_raw_len) GLC_HIP(ctx, hipMemcpy(row_raw_len, rows.row_raw_len, M * 8ull, hipMemcpyDeviceToHost));
+  ctx->cd_status_n = 1;
+  return status ? glc_decode_compact_last_status(ctx, status, 1) : GLC_OK;
+}
+
+int glc_debug_rows_from_compact_window(glc_ctx *ctx, const void *d_blob, uint64_t blob_bytes, uint64_t n_frames, uint16_t channels,
+                                       uint64_t first_frame, uint64_t frames, uint64_t *row_begin, uint32_t *row_cnt,
+                                       float *row_scale, int64_t *row_raw, uint64_t *row_raw_len, glc_compact_status *status) {
+  const std::string w("glc_debug_rows_from_compact_window");
+  if (!ctx) return GLC_EINVAL;
+  if (channels == 0 || n_frames == 0 || n_frames * channels > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, w + ": bad shape");
+  if (frames == 0 || first_frame > n_frames || frames > n_frames - first_frame) return fail(ctx, GLC_EINVAL, w + ": the window leaves the blob");
+  int rc = cd_check_blob(ctx, w, d_blob, blob_bytes, channels, n_frames);
+  if (rc != GLC_OK) return rc;
+  DeviceGuard guard(ctx->device);
+  const uint32_t M = static_cast<uint32_t>(frames * channels), front = static_cast<uint32_t>(first_frame * channels);
+  rt_forget_streams(ctx);
+  ctx->cd_status_n = 0;
+  rc = rt_reserve(ctx, ctx->rt_rows, glc::rows_from_compact_window_bytes(M));
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->cd_status, sizeof(glc::CompactStatus));
+  if (rc != GLC_OK) return rc;
+  const glc::CompactBlob one{reinterpret_cast<uintptr_t>(d_blob), blob_bytes, 0u, static_cast<uint32_t>(n_frames * channels), {front, M}};
+  glc::DecodeRows rows{};
+  GLC_HIP(ctx, glc::launch_rows_from_compact_window(nullptr, one, 1, M, channels, front, d_blob, ctx->rt_rows.p,
+                                                    static_cast<glc::CompactStatus *>(ctx->cd_status.p), ctx->stream, &rows));
   GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (row_begin) GLC_HIP(ctx, hipMemcpy(row_begin, rows.row_begin, M * 8ull, hipMemcpyDeviceToHost));
   if (row_cnt) GLC_HIP(ctx, hipMemcpy(row_cnt, rows.row_cnt, M * 4ull, hipMemcpyDeviceToHost));

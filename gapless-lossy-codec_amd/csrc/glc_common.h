@@ -42,6 +42,10 @@ void build_host_tables(uint32_t sample_rate, HostTables &t);
 // Padding arithmetic of Encoder::encode, src/codec.rs:433-455.
 glc_plan plan_encode(uint64_t n_samples, uint16_t channels);
 
+// What a crop of the decoded clip needs of its stream (include/glc.h glc_plan_crop; DESIGN section 3, "a window of a
+// compact blob"): the ONE statement of that geometry.  false: what glc_plan_crop refuses.
+bool plan_crop(uint64_t n_samples, uint16_t channels, const glc_crop &crop, glc_crop_plan *out);
+
 // Per-channel samples [lo, hi) that frames [f0, f1) read (f1 > f0), clipped to a stream of `per_channel`:
 // [hop*f0 - hop/2, hop*(f1-1) - hop/2 + frame), src/codec.rs:449-474.
 struct SampleWindow {

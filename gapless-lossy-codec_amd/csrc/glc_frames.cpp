@@ -432,6 +432,15 @@ int glc_plan_encode(uint64_t n_samples, uint16_t channels, glc_plan *out) {
   return GLC_OK;
 }
 
+int glc_plan_crop(uint64_t n_samples, uint16_t channels, const glc_crop *crop, glc_crop_plan *out) {
+  if (!crop || !out) return GLC_EINVAL;
+  if (!glc::plan_crop(n_samples, channels, *crop, out)) {
+    glc::set_global_error("glc_plan_crop: a clip the reference encoder panics on, an empty crop, or one that ends behind the clip");
+    return GLC_EINVAL;
+  }
+  return GLC_OK;
+}
+
 int glc_frames_from_records(uint32_t sample_rate, uint64_t n_samples, uint16_t channels,
                             const void *records, uint64_t n_frames, glc_frames **out) {
   if (!records || !out) return GLC_EINVAL;

@@ -154,7 +154,8 @@ hipError_t launch_rows_from_records_batch(const uint8_t *records, uint32_t M, ui
 // is in use.  Four launches whatever n_blobs, no synchronisation; any_raw is set (the host does not know).
 struct CompactBlob {
   uint64_t addr, cap;
-  uint32_t first_row, rows, pad[2];
+  uint32_t first_row, rows;
+  uint32_t win[2];  // launch_rows_from_compact_window: first row and row count of the window inside the blob; else 0
 };
 constexpr uint32_t kCompactBadHeader = 1u, kCompactRowBounds = 2u, kCompactNotCanonical = 4u, kCompactRawRange = 8u,
                    kCompactPairSum = 16u, kCompactRawSum = 32u;
@@ -162,12 +163,38 @@ struct CompactStatus {  // 64 bytes per blob
   uint32_t flags, header_ok;
   uint64_t n_bad_rows, first_bad_row;  // first_bad_row: ~0 while no row has been rejected
   uint64_t n_pairs, n_raw_rows, bytes;  // of a header that passed
-  uint64_t pairs_before, raw_before;    // running sums of the launch at the blob's first row
+  uint64_t pairs_before, raw_before;    // running sums of the launch at the blob's first row (a window: minus its prefix, mod 2^64)
 };
 uint64_t rows_from_compact_bytes(uint32_t M);
 hipError_t launch_rows_from_compact(const CompactBlob *dir, const CompactBlob &one, uint32_t n_blobs, uint32_t M, uint32_t ch,
                                     const void *base, void *workspace, CompactStatus *status, hipStream_t s,
                                     DecodeRows *rows);
+// R2 of WINDOWS of compact blobs (glc_decode_crops_device_compact): entry i of `dir` (or `one`) names a blob as above -
+// address, capacity, `rows` = ALL rows of the blob the host expects (frames * ch) - and the window [win[0], win[0] +
+// win[1]) of its rows (whole frames, inside the blob; win[1] >= 1) whose tables are rows [first_row, first_row +
+// win[1]) of this launch; first_row ascends from 0 and the windows' rows sum to M.  The same blob may be named by any
+// number of entries, in any address order.  The tables of a window's rows are exactly those launch_rows_from_compact
+// builds for these rows of the same bytes (row_begin, row_raw from the common `base`), kept or rejected by the same
+// rules, with one status per ENTRY:
+//   header (k_r2_headers itself): a header that fails rejects the window's rows (n_bad_rows = win[1], first_bad_row =
+//   win[0], written by k_r2w_scan_blocks).
+//   prefix (k_r2w_prefix): the pairs and the rows of raw frames IN FRONT of the window, a reduction over the is_raw
+//   and cnt sections of rows [0, win[0]) - 4096 rows per workgroup, one vector atomic add per workgroup and sum into
+//   the entry's status.  No row in front of a window gets a table entry, none has its list read or is validated.
+//   Not launched when every window starts at its blob's row 0.
+//   scans and rows (k_r2w_scan_rows, k_r2w_scan_blocks, k_r2w_rows): the window's own rows through the scans and
+//   the row check of R2 (the same device functions), the origin of an entry being the prefix of its window.
+//   first_bad_row / n_bad_rows count the window's rows in the blob's row numbering.  kCompactPairSum / kCompactRawSum
+//   are never set: nothing behind a window is read.  No load leaves [address, address + capacity).
+// workspace: rows_from_compact_window_bytes(M) = 5 row arrays of align256(8 M), align256(4 M), align256(4 M),
+// align256(8 M), align256(8 M) bytes (32 B per WINDOW row) + 2 x align256(8 ceil(M / 1024)) bytes of block sums, M
+// counted as 1 when 0, align256 = rounding up to 256: nothing in it is per row of a blob.  Five launches (four
+// without the prefix) whatever n_entries (up to 65535; one more prefix launch per 65535 beyond), no synchronisation, no
+// workgroup waits for another.  max_front: the largest win[0] of the entries (it sizes the prefix launch).
+uint64_t rows_from_compact_window_bytes(uint32_t M);
+hipError_t launch_rows_from_compact_window(const CompactBlob *dir, const CompactBlob &one, uint32_t n_entries, uint32_t M,
+                                           uint32_t ch, uint32_t max_front, const void *base, void *workspace,
+                                           CompactStatus *status, hipStream_t s, DecodeRows *rows);
 // variant (include/glc_debug.h): 0 = shipped (k_imdct_plan + k_imdct_apply, absent row pairs skipped
 // by scalar branches); 1 = one row per workgroup (the cross-check kernel); 2 = plan + apply without
 // the skip; 3 = without the issue-priority schedule; 4 = skipping in row pairs only.  All but 1 need a workspace `plan` of imdct_plan_bytes(plan_groups) bytes,

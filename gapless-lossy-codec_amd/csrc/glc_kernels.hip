@@ -1630,6 +1630,13 @@ __global__ __launch_bounds__(256) void k_r2_headers(const CompactBlob *__restric
   status[b] = st;
 }
 
+// The word row `lm` of blob `e` (whose header passed) gives the scan: its cnt, or one row of a raw frame.
+__device__ __forceinline__ unsigned long long r2_row_word(const CompactBlob e, unsigned ch, unsigned lm) {
+  const CompactLayout l = compact_sections(e.rows / ch, e.rows);
+  const unsigned char *blob = reinterpret_cast<const unsigned char *>(e.addr);
+  return blob[l.o_israw + lm / ch] ? (1ull << kR2RawShift) : reinterpret_cast<const unsigned *>(blob + l.o_cnt)[lm];
+}
+
 __global__ __launch_bounds__(256) void k_r2_scan_rows(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned n_blobs,
                                                        unsigned M, unsigned ch, const CompactStatus *__restrict__ status,
                                                        unsigned long long *__restrict__ loc,
@@ -1640,10 +1647,7 @@ __global__ __launch_bounds__(256) void k_r2_scan_rows(const CompactBlob *__restr
         const unsigned b = dir ? r2_find_blob(dir, n_blobs, m) : 0u;
         const CompactBlob e = dir ? dir[b] : one;
         if (!status[b].header_ok) return 0ull;
-        const unsigned lm = m - e.first_row;
-        const CompactLayout l = compact_sections(e.rows / ch, e.rows);
-        const unsigned char *blob = reinterpret_cast<const unsigned char *>(e.addr);
-        return blob[l.o_israw + lm / ch] ? (1ull << kR2RawShift) : reinterpret_cast<const unsigned *>(blob + l.o_cnt)[lm];
+        return r2_row_word(e, ch, m - e.first_row);
       },
       M, loc, blk, blk_raw);
 }
@@ -1676,32 +1680,23 @@ __global__ __launch_bounds__(1024) void k_r2_scan_blocks(const CompactBlob *__re
   }
 }
 
-__global__ __launch_bounds__(256) void k_r2_rows(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned n_blobs,
-                                                  unsigned M, unsigned ch, unsigned long long base_addr,
-                                                  const unsigned long long *__restrict__ blk,
-                                                  const unsigned long long *__restrict__ blk_raw,
-                                                  CompactStatus *__restrict__ status,
-                                                  unsigned long long *__restrict__ row_begin, unsigned *__restrict__ row_cnt,
-                                                  float *__restrict__ row_scale, long long *__restrict__ row_raw,
-                                                  unsigned long long *__restrict__ row_raw_len) {
-  const int lane = threadIdx.x & 63;
-  const unsigned long long m64 = static_cast<unsigned long long>(blockIdx.x) * 4ull + (threadIdx.x >> 6);
-  if (m64 >= M) return;
-  const unsigned m = static_cast<unsigned>(m64);
-  const unsigned b = dir ? r2_find_blob(dir, n_blobs, m) : 0u;
-  const CompactBlob e = dir ? dir[b] : one;
-  CompactStatus *st = status + b;
+// What one wave of k_r2_rows / k_r2w_rows does with row `lm` of blob `e`, table row `m` of the launch: the checks, the
+// row's five table entries, and what it has to say in the status `st` of its entry.
+__device__ __forceinline__ void r2_row(const CompactBlob &e, CompactStatus *st, unsigned ch, unsigned long long base_addr,
+                                       unsigned lm, unsigned m, const unsigned long long *__restrict__ blk,
+                                       const unsigned long long *__restrict__ blk_raw, unsigned long long *__restrict__ row_begin,
+                                       unsigned *__restrict__ row_cnt, float *__restrict__ row_scale, long long *__restrict__ row_raw,
+                                       unsigned long long *__restrict__ row_raw_len, int lane) {
   unsigned long long begin = 0, raw_len = 0;
   long long raw_at = -1;
   unsigned cnt = 0, bad = 0;
   float scale = 0.0f;
-  const unsigned lm = m - e.first_row;
   if (st->header_ok) {
     const CompactLayout l = compact_sections(e.rows / ch, e.rows);
     const unsigned long long n_pairs = st->n_pairs, n_raw_rows = st->n_raw_rows;
     const unsigned char *blob = reinterpret_cast<const unsigned char *>(e.addr);
     const unsigned c = lm % ch;
-    const RowsBefore at = rows_before<kR2RawShift>(row_raw_len[m], blk, blk_raw, m);  // k_r2_scan_rows left the row's word there
+    const RowsBefore at = rows_before<kR2RawShift>(row_raw_len[m], blk, blk_raw, m);  // the scan left the row's word there
     const unsigned long long p = at.pairs - st->pairs_before, r = at.raw - st->raw_before;
     scale = reinterpret_cast<const float *>(blob + l.o_scale)[lm];
     if (blob[l.o_israw + lm / ch]) {
@@ -1749,6 +1744,124 @@ __global__ __launch_bounds__(256) void k_r2_rows(const CompactBlob *__restrict__
       atomicMin(reinterpret_cast<unsigned long long *>(&st->first_bad_row), static_cast<unsigned long long>(lm));
     }
   }
+}
+
+__global__ __launch_bounds__(256) void k_r2_rows(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned n_blobs,
+                                                  unsigned M, unsigned ch, unsigned long long base_addr,
+                                                  const unsigned long long *__restrict__ blk,
+                                                  const unsigned long long *__restrict__ blk_raw,
+                                                  CompactStatus *__restrict__ status,
+                                                  unsigned long long *__restrict__ row_begin, unsigned *__restrict__ row_cnt,
+                                                  float *__restrict__ row_scale, long long *__restrict__ row_raw,
+                                                  unsigned long long *__restrict__ row_raw_len) {
+  const int lane = threadIdx.x & 63;
+  const unsigned long long m64 = static_cast<unsigned long long>(blockIdx.x) * 4ull + (threadIdx.x >> 6);
+  if (m64 >= M) return;
+  const unsigned m = static_cast<unsigned>(m64);
+  const unsigned b = dir ? r2_find_blob(dir, n_blobs, m) : 0u;
+  const CompactBlob e = dir ? dir[b] : one;
+  r2_row(e, status + b, ch, base_addr, m - e.first_row, m, blk, blk_raw, row_begin, row_cnt, row_scale, row_raw, row_raw_len, lane);
+}
+
+// ------------------------------------------------------------------------------------------
+// R2 of windows (glc_kernels.h launch_rows_from_compact_window has the rules): the tables of rows [win[0], win[0] +
+// win[1]) of each entry's blob, as R2 builds them for those rows, without a table entry for any row in front.
+//   k_r2_headers       as it stands, one thread per entry: the header is the blob's, and the two origin words start at 0
+//   k_r2w_prefix       what lies in front of a window: workgroup (x, entry) sums rows [4096 x, 4096 x + 4096) below
+//                      win[0] - cnt of the rows of compressed frames, one per row of a raw frame, from the cnt and
+//                      is_raw sections alone - in registers, across the wave by shuffles, across the four waves through
+//                      LDS, and adds its two sums to the entry's origin words with one vector atomic each (64-bit
+//                      integer adds: the result does not depend on their order)
+//   k_r2w_scan_rows    scan_rows_1024 over the windows' own rows
+//   k_r2w_scan_blocks  scan_block_sums, then per entry the origin R2 subtracts: the launch's running sums at the
+//                      window's first row MINUS the window's prefix (mod 2^64), so that r2_row finds the row's place in
+//                      its blob with the arithmetic it has; and for a header that failed the rows that rejects: the
+//                      window's, not the blob's
+//   k_r2w_rows         one wave per window row: r2_row
+// ------------------------------------------------------------------------------------------
+constexpr unsigned kR2wPrefixRows = 4096;  // rows in front of a window that one workgroup of k_r2w_prefix sums
+
+__global__ __launch_bounds__(256) void k_r2w_prefix(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned b0, unsigned ch,
+                                                     CompactStatus *__restrict__ status) {
+  __shared__ unsigned long long s_pairs[4], s_raw[4];
+  const unsigned b = b0 + blockIdx.y;
+  const CompactBlob e = dir ? dir[b] : one;
+  const unsigned long long r0 = static_cast<unsigned long long>(blockIdx.x) * kR2wPrefixRows;
+  CompactStatus *st = status + b;
+  if (r0 >= e.win[0] || !st->header_ok) return;  // the whole workgroup
+  const CompactLayout l = compact_sections(e.rows / ch, e.rows);
+  const unsigned char *is_raw = reinterpret_cast<const unsigned char *>(e.addr) + l.o_israw;
+  const unsigned *cnt = reinterpret_cast<const unsigned *>(e.addr + l.o_cnt);
+  const unsigned long long end = min(static_cast<unsigned long long>(e.win[0]), r0 + kR2wPrefixRows);
+  unsigned long long pairs = 0, raw = 0;
+  for (unsigned long long lm = r0 + threadIdx.x; lm < end; lm += 256) {  // below win[0] <= rows: inside the fixed sections
+    if (is_raw[lm / ch]) raw += 1;
+    else pairs += cnt[lm];
+  }
+  for (int off = 32; off; off >>= 1) pairs += __shfl_down(pairs, off), raw += __shfl_down(raw, off);
+  if ((threadIdx.x & 63) == 0) s_pairs[threadIdx.x >> 6] = pairs, s_raw[threadIdx.x >> 6] = raw;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    pairs = s_pairs[0] + s_pairs[1] + s_pairs[2] + s_pairs[3];
+    raw = s_raw[0] + s_raw[1] + s_raw[2] + s_raw[3];
+    if (pairs) atomicAdd(reinterpret_cast<unsigned long long *>(&st->pairs_before), pairs);
+    if (raw) atomicAdd(reinterpret_cast<unsigned long long *>(&st->raw_before), raw);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_r2w_scan_rows(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned n_entries,
+                                                        unsigned M, unsigned ch, const CompactStatus *__restrict__ status,
+                                                        unsigned long long *__restrict__ loc,
+                                                        unsigned long long *__restrict__ blk,
+                                                        unsigned long long *__restrict__ blk_raw) {
+  scan_rows_1024<unsigned long long, kR2RawShift>(
+      [&](unsigned m) -> unsigned long long {
+        const unsigned b = dir ? r2_find_blob(dir, n_entries, m) : 0u;
+        const CompactBlob e = dir ? dir[b] : one;
+        if (!status[b].header_ok) return 0ull;
+        return r2_row_word(e, ch, e.win[0] + (m - e.first_row));
+      },
+      M, loc, blk, blk_raw);
+}
+
+__global__ __launch_bounds__(1024) void k_r2w_scan_blocks(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned n_entries,
+                                                           unsigned long long *__restrict__ blk,
+                                                           unsigned long long *__restrict__ blk_raw, unsigned n,
+                                                           const unsigned long long *__restrict__ loc,
+                                                           CompactStatus *__restrict__ status) {
+  __shared__ unsigned long long s[1024];
+  unsigned long long sums[2];
+  scan_block_sums(blk, blk_raw, n, s, sums);
+  __syncthreads();  // this workgroup's own stores to blk / blk_raw are read below
+  for (unsigned b = threadIdx.x; b < n_entries; b += 1024) {
+    const unsigned r0 = dir ? dir[b].first_row : one.first_row;  // < M: a window has rows
+    const RowsBefore at0 = rows_before<kR2RawShift>(loc[r0], blk, blk_raw, r0);
+    CompactStatus *st = status + b;
+    st->pairs_before = at0.pairs - st->pairs_before;  // k_r2w_prefix left the window's prefix there
+    st->raw_before = at0.raw - st->raw_before;
+    if (!st->header_ok) {  // k_r2_headers reported the blob's rows
+      st->n_bad_rows = dir ? dir[b].win[1] : one.win[1];
+      st->first_bad_row = dir ? dir[b].win[0] : one.win[0];
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_r2w_rows(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned n_entries,
+                                                   unsigned M, unsigned ch, unsigned long long base_addr,
+                                                   const unsigned long long *__restrict__ blk,
+                                                   const unsigned long long *__restrict__ blk_raw,
+                                                   CompactStatus *__restrict__ status,
+                                                   unsigned long long *__restrict__ row_begin, unsigned *__restrict__ row_cnt,
+                                                   float *__restrict__ row_scale, long long *__restrict__ row_raw,
+                                                   unsigned long long *__restrict__ row_raw_len) {
+  const int lane = threadIdx.x & 63;
+  const unsigned long long m64 = static_cast<unsigned long long>(blockIdx.x) * 4ull + (threadIdx.x >> 6);
+  if (m64 >= M) return;
+  const unsigned m = static_cast<unsigned>(m64);
+  const unsigned b = dir ? r2_find_blob(dir, n_entries, m) : 0u;
+  const CompactBlob e = dir ? dir[b] : one;
+  r2_row(e, status + b, ch, base_addr, e.win[0] + (m - e.first_row), m, blk, blk_raw, row_begin, row_cnt, row_scale, row_raw,
+         row_raw_len, lane);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2239,6 +2352,35 @@ hipError_t launch_rows_from_compact(const CompactBlob *dir, const CompactBlob &o
   hipLaunchKernelGGL(k_r2_scan_rows, dim3(nblk), dim3(256), 0, s, dir, one, n_blobs, M, ch, status, t.row_raw_len, t.blk, t.blk_raw);
   hipLaunchKernelGGL(k_r2_scan_blocks, dim3(1), dim3(1024), 0, s, dir, one, n_blobs, M, t.blk, t.blk_raw, nblk, t.row_raw_len, status);
   hipLaunchKernelGGL(k_r2_rows, dim3(static_cast<unsigned>((static_cast<uint64_t>(M) + 3) / 4)), dim3(256), 0, s, dir, one, n_blobs,
+                     M, ch, static_cast<unsigned long long>(reinterpret_cast<uintptr_t>(base)), t.blk, t.blk_raw, status, t.row_begin,
+                     t.row_cnt, t.row_scale, t.row_raw, t.row_raw_len);
+  return hipGetLastError();
+}
+
+uint64_t rows_from_compact_window_bytes(uint32_t M) { return r2_tables(nullptr, M).bytes; }
+
+hipError_t launch_rows_from_compact_window(const CompactBlob *dir, const CompactBlob &one, uint32_t n_entries, uint32_t M,
+                                           uint32_t ch, uint32_t max_front, const void *base, void *workspace,
+                                           CompactStatus *status, hipStream_t s, DecodeRows *rows) {
+  if (!workspace || !status || !rows || !base || ch == 0 || n_entries == 0 || (!dir && n_entries != 1)) return hipErrorInvalidValue;
+  if (M == 0 || M % ch) return hipErrorInvalidValue;  // whole frames, and every window has some (a directory's entries: the caller's word)
+  if (!dir && ((one.addr & 63u) || one.first_row != 0 || one.win[1] != M || one.rows % ch || one.win[0] % ch ||
+               one.win[0] > one.rows || M > one.rows - one.win[0] || one.win[0] > max_front ||
+               one.addr < reinterpret_cast<uintptr_t>(base)))
+    return hipErrorInvalidValue;
+  if (reinterpret_cast<uintptr_t>(base) & 63u) return hipErrorInvalidValue;
+  const R2Tables t = r2_tables(workspace, M);
+  const unsigned nblk = static_cast<unsigned>((static_cast<uint64_t>(M) + 1023) / 1024);
+  *rows = t.rows(base, base);
+  hipLaunchKernelGGL(k_r2_headers, dim3((n_entries + 255) / 256), dim3(256), 0, s, dir, one, n_entries, ch, status);
+  if (max_front) {
+    const unsigned chunks = static_cast<unsigned>((static_cast<uint64_t>(max_front) + kR2wPrefixRows - 1) / kR2wPrefixRows);
+    for (uint32_t b0 = 0; b0 < n_entries; b0 += 65535u)  // blockIdx.y is 16 bits wide
+      hipLaunchKernelGGL(k_r2w_prefix, dim3(chunks, std::min(n_entries - b0, 65535u)), dim3(256), 0, s, dir, one, b0, ch, status);
+  }
+  hipLaunchKernelGGL(k_r2w_scan_rows, dim3(nblk), dim3(256), 0, s, dir, one, n_entries, M, ch, status, t.row_raw_len, t.blk, t.blk_raw);
+  hipLaunchKernelGGL(k_r2w_scan_blocks, dim3(1), dim3(1024), 0, s, dir, one, n_entries, t.blk, t.blk_raw, nblk, t.row_raw_len, status);
+  hipLaunchKernelGGL(k_r2w_rows, dim3(static_cast<unsigned>((static_cast<uint64_t>(M) + 3) / 4)), dim3(256), 0, s, dir, one, n_entries,
                      M, ch, static_cast<unsigned long long>(reinterpret_cast<uintptr_t>(base)), t.blk, t.blk_raw, status, t.row_begin,
                      t.row_cnt, t.row_scale, t.row_raw, t.row_raw_len);
   return hipGetLastError();

@@ -126,4 +126,20 @@ glc_plan plan_encode(uint64_t n_samples, uint16_t channels) {
   return p;
 }
 
+bool plan_crop(uint64_t n_samples, uint16_t channels, const glc_crop &crop, glc_crop_plan *out) {
+  const glc_plan plan = plan_encode(n_samples, channels);
+  if (plan.n_frames == 0) return false;
+  const uint64_t ch = channels, per_hop = static_cast<uint64_t>(kHop) * ch;
+  const Trim trim = gapless_trim(plan.n_frames, channels, plan.encoder_delay, n_samples);
+  const uint64_t len = trim.n / ch;  // the decoded clip, per channel
+  if (crop.length == 0 || crop.length > len || crop.start > len - crop.length) return false;
+  // un-trimmed positions [lo, hi): the delay counts INTERLEAVED samples (Q3)
+  const uint64_t lo = trim.start + crop.start * ch, hi = lo + crop.length * ch;
+  const uint64_t h_lo = lo / per_hop, h_hi = (hi - 1) / per_hop;  // hops of the first and of the last kept sample
+  // hop h = second half of frame h - 1 + first half of frame h: the halo frame in front, none for the bare tail hop
+  const uint64_t f_lo = (h_lo > 1 ? h_lo : 1) - 1, f_hi = h_hi < plan.n_frames - 1 ? h_hi : plan.n_frames - 1;
+  *out = glc_crop_plan{f_lo, f_hi - f_lo + 1, h_lo, h_hi - h_lo + 1};
+  return true;
+}
+
 }  // namespace glc

@@ -590,7 +590,7 @@ int glc_decode_device_compact(glc_ctx *ctx, const void *d_blob, uint64_t blob_by
 int glc_decode_batch_device_compact(glc_ctx *ctx, const void *const *d_blobs, const uint64_t *blob_bytes,
                                     const uint64_t *n_samples, float *d_out, const glc_clip_layout *out);
 
-/* What R2 found in the last of the two calls above: per clip the flag word, the number of rejected rows and
+/* What R2 found in the last of the two calls above (or of glc_decode_crops_device_compact below): per clip the flag word, the number of rejected rows and
  * the first of them (row = frame * channels + channel; 0 when none was rejected).  A bad header rejects every
  * row.  The two SUM flags are reported only: they reject nothing.  Synchronises the context's stream.
  * GLC_EINVAL when no such call has completed on this context or n_clips is not that call's. */
@@ -602,6 +602,48 @@ int glc_decode_batch_device_compact(glc_ctx *ctx, const void *const *d_blobs, co
 #define GLC_COMPACT_RAW_SUM      32u  /* the rows of raw frames are not n_raw_rows */
 typedef struct glc_compact_status { uint32_t flags; uint32_t reserved; uint64_t n_bad_rows; uint64_t first_bad_row; } glc_compact_status;
 int glc_decode_compact_last_status(glc_ctx *ctx, glc_compact_status *status, uint64_t n_clips);
+
+/* ---- windows of stored clips: crops of compact blobs ---------------------------------------- */
+
+/* A window of a decoded clip, in samples PER CHANNEL: [start, start + length). */
+typedef struct glc_crop { uint64_t start, length; } glc_crop;
+
+/* Host only: what a crop of a clip of n_samples interleaved samples needs of the clip's stream - the frames
+ * [first_frame, first_frame + n_frames) (the frame in front of the first kept hop included: its second half
+ * overlaps into that hop; no frame for the bare tail hop) and the hops [first_hop, first_hop + n_hops) of the
+ * un-trimmed stream, from the hop of the first kept sample to the hop of the last one.  The crop lies at the
+ * un-trimmed interleaved positions [512 + start * channels, 512 + (start + length) * channels): the encoder's delay
+ * counts interleaved samples.  glc_decode_crops_device_compact plans with this function.
+ * GLC_EINVAL: a null pointer, an n_samples / channels the encoder refuses, length == 0, start + length beyond the
+ * clip's samples per channel. */
+typedef struct glc_crop_plan { uint64_t first_frame, n_frames, first_hop, n_hops; } glc_crop_plan;
+int glc_plan_crop(uint64_t n_samples, uint16_t channels, const glc_crop *crop, glc_crop_plan *out);
+
+/* A batch of windows of stored clips in one call: entry i is the interleaved samples [crops[i].start * channels,
+ * (crops[i].start + crops[i].length) * channels) of what glc_decode_device_compact gives for d_blobs[i] (blob_bytes[i],
+ * n_samples[i]) - bit for bit, for every content of the blob, damaged ones included - written as clip i of `out`
+ * (any glc_clip_layout; out->lengths[i], or out->length, must be crops[i].length).  No other element of d_out is
+ * written.  The same blob may appear any number of times and the blobs may lie in any address order.
+ * Only the frames glc_plan_crop names go through the inverse transform, and only their rows get a row table (32
+ * bytes per WINDOW row): the pairs and raw planes in front of a window are found by a reduction over the cnt and
+ * is_raw sections of the rows in front, nothing behind a window is read.  Crops are packed into rounds as
+ * glc_decode_batch_device_compact packs clips, each counting its window's frames + 1; one launch chain per ROUND
+ * whatever the number of crops; a window of more frames than a round goes through the rounds of the single call,
+ * restricted to its frames.  Queued on glc_ctx_stream(ctx), NOT synchronised, nothing is copied to the host.
+ * Untrusted blobs: the header check is that of the calls above (a blob that fails gives +0.0); a window's rows are
+ * kept or rejected by the rules above.  Rows outside the window's frames are not validated and cannot affect the
+ * crop, except through their cnt / is_raw in front of the window, which move the origins of its lists and planes
+ * exactly as they do in the whole-blob call.  No load leaves [blob, blob + blob_bytes).
+ * glc_decode_compact_last_status afterwards: one status per CROP; n_bad_rows and first_bad_row count the window's
+ * rows, in the stream's row numbering (a bad header: all rows of the window, and the first of them - which the
+ * status cannot tell from "none" when that row is 0 and the flag is not looked at).  GLC_COMPACT_PAIR_SUM and
+ * GLC_COMPACT_RAW_SUM are NEVER set by this call: it does not read behind the window.
+ * GLC_EINVAL, before anything is queued: everything glc_decode_batch_device_compact refuses (but the layout's lengths
+ * are the crops'), length == 0, start + length beyond the clip's samples per channel, a layout length that is not
+ * the crop's, an output extent that overlaps a blob.  n_clips == 0 is GLC_OK.  The family's rules hold. */
+int glc_decode_crops_device_compact(glc_ctx *ctx, const void *const *d_blobs, const uint64_t *blob_bytes,
+                                    const uint64_t *n_samples, const glc_crop *crops,
+                                    float *d_out, const glc_clip_layout *out);
 
 /* Host only: the compact blob of a whole stream, the inverse of glc_frames_from_compact - the bytes
  * glc_compact_records gives for the records of that stream (padding zeroed), so that a .glc file can be put into

@@ -190,6 +190,13 @@ class EncodedAudio {
   glc_frames *h_ = nullptr;
 };
 
+// The frames and hops a crop of a decoded clip needs (glc_plan_crop); throws where it refuses.
+inline glc_crop_plan plan_crop(uint64_t n_samples, uint16_t channels, const glc_crop &crop) {
+  glc_crop_plan p{};
+  detail::check(glc_plan_crop(n_samples, channels, &crop, &p));
+  return p;
+}
+
 // Arena bytes that hold the blobs of every clip of a layout whatever their content (glc_compact_store_bound).
 inline uint64_t compact_store_bound(const glc_clip_layout &in) { return glc_compact_store_bound(&in); }
 
@@ -423,7 +430,15 @@ class Decoder {
       throw Error(GLC_EINVAL, "decode_batch_device_compact: one blob, size and length per clip of the layout");
     detail::check(glc_decode_batch_device_compact(ctx_, d_blobs.data(), blob_bytes.data(), n_samples.data(), d_out, &out), ctx_);
   }
-  // what the device check found in the blobs of the last of the two calls (synchronises)
+  // ... windows of stored clips: crop i of blob i as clip i of the batch, only the windows' frames decoded
+  void decode_crops_device_compact(const std::vector<const void *> &d_blobs, const std::vector<uint64_t> &blob_bytes,
+                                   const std::vector<uint64_t> &n_samples, const std::vector<glc_crop> &crops, float *d_out,
+                                   const glc_clip_layout &out) {
+    if (d_blobs.size() != out.n_clips || blob_bytes.size() != out.n_clips || n_samples.size() != out.n_clips || crops.size() != out.n_clips)
+      throw Error(GLC_EINVAL, "decode_crops_device_compact: one blob, size, length and crop per clip of the layout");
+    detail::check(glc_decode_crops_device_compact(ctx_, d_blobs.data(), blob_bytes.data(), n_samples.data(), crops.data(), d_out, &out), ctx_);
+  }
+  // what the device check found in the blobs (or windows) of the last of these calls (synchronises)
   std::vector<glc_compact_status> last_compact_status(uint64_t n_clips = 1) {
     std::vector<glc_compact_status> v(n_clips);
     if (n_clips) detail::check(glc_decode_compact_last_status(ctx_, v.data(), n_clips), ctx_);

@@ -112,6 +112,16 @@ int glc_debug_rows_from_compact(glc_ctx *ctx, const void *d_blob, uint64_t blob_
                                 uint64_t *row_begin, uint32_t *row_cnt, float *row_scale, int64_t *row_raw,
                                 uint64_t *row_raw_len, glc_compact_status *status);
 
+/* The windowed R2 (launch_rows_from_compact_window) alone, exactly as glc_decode_crops_device_compact launches it for
+ * ONE window of a long clip: frames [first_frame, first_frame + frames) of the blob of `n_frames` frames at d_blob.
+ * The tables of the window's frames * channels rows come back as above - row_begin and row_raw from d_blob, in the
+ * blob's own terms, so they are the matching slices of glc_debug_rows_from_compact's - with the status words.
+ * Synchronises.  tests/test_compact_crops.py holds windows at the scan's edges, and one behind row 1024 * 1024 of a
+ * blob of that many rows, to the model through this. */
+int glc_debug_rows_from_compact_window(glc_ctx *ctx, const void *d_blob, uint64_t blob_bytes, uint64_t n_frames, uint16_t channels,
+                                       uint64_t first_frame, uint64_t frames, uint64_t *row_begin, uint32_t *row_cnt,
+                                       float *row_scale, int64_t *row_raw, uint64_t *row_raw_len, glc_compact_status *status);
+
 /* The shader clock the device HOLDS under load (measurement only; bench.py's roofline.clock_ghz_held).
  * `begin` starts one sleeping wave on a stream of its own that runs for `window_us` microseconds beside
  * whatever the caller queues meanwhile and reads the shader-cycle counter against the constant 100 MHz
