@@ -251,6 +251,9 @@ SIGNATURES = {
     "glc_frames_to_compact": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(GlcCompactInfo)]),
     "glc_compact_store_bound": (C.c_uint64, [C.POINTER(GlcClipLayout)]),
     "glc_encode_batch_device_compact": (C.c_int, [_vp, _vp, C.POINTER(GlcClipLayout), _vp, C.c_uint64, _vp, _vp]),
+    "glc_store_crop_slots": (C.c_int, [C.c_uint64, C.c_uint16, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "glc_decode_crops_device_store": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint64, _vp,
+                                                C.POINTER(GlcClipLayout)]),
     "glc_version": (C.c_char_p, []),
 }
 

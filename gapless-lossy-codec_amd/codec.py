@@ -293,6 +293,16 @@ def store_blobs(arena, entries) -> list:
     return [arena[off:off + size] if (raw_stored >> 32) & 1 else None for off, size, _, raw_stored in e]
 
 
+def store_crop_slots(length: int, channels: int):
+    """(max_hops, max_frames): the hops and frames a crop of `length` samples per channel needs wherever it starts
+    (glc_store_crop_slots) - the fixed slots a crop of Decoder.decode_store_crops_tensor owns."""
+    if length < 0 or not 0 <= channels <= 0xFFFF:
+        raise GlcError(GLC_EINVAL, "store_crop_slots: negative length or a channel count out of range")
+    hops, frames = C.c_uint64(), C.c_uint64()
+    check(lib.glc_store_crop_slots(length, channels, C.byref(hops), C.byref(frames)))
+    return int(hops.value), int(frames.value)
+
+
 def compact_records(records: np.ndarray, channels: int) -> np.ndarray:
     """Host twin of the device compaction (glc_compact_records): records -> compact blob bytes."""
     records = np.ascontiguousarray(records, np.uint8).reshape(-1)
@@ -852,6 +862,69 @@ class Decoder(_Ctx):
         try:
             check(lib.glc_decode_crops_device_compact(self._h, ptrs, sizes, ns_arr, crops, C.c_void_p(out.data_ptr()), C.byref(lay)),
                   self._h)
+        finally:
+            self.set_stream(0)
+        self._compact_clips = b
+        return out
+
+    def decode_store_crops_tensor(self, arena, entries, lengths, clips, starts, length: int, max_length: int,
+                                  planar: bool = True, out=None):
+        """Draw B crops of `length` samples per channel from the store as Encoder.encode_compact_batch_tensor left it
+        (glc_decode_crops_device_store): crop i is samples [starts[i], starts[i] + length) of stored clip clips[i].
+        arena: the uint8 CUDA tensor; entries: the (N, 4) int64 CUDA tensor the encode returned, or torch.cat of
+        several; lengths: (N,) int64 CUDA, samples per channel of every stored clip; clips, starts: (B,) int64 CUDA
+        (torch.randint on the device, or anything else); max_length: a host upper bound of lengths.  None of the
+        tensors is read on the host and nothing is uploaded: the work of this method does not depend on B.  out: a
+        float32 CUDA tensor (B, C, length) (planar) or (B, length, C) with innermost stride 1 - a slice of something
+        bigger works - or None: a new zero-filled one.  Every usable crop is bit for bit decode_compact_crops_tensor's;
+        a crop whose entry (flag 64) or selection (flag 128) is unusable is +0.0.  No element outside the crops is
+        written.  Queued on torch's current stream; returns the output.  last_compact_status() afterwards: one
+        status per crop."""
+        import torch
+        ch = self.channels
+
+        def index(t, name, shape_tail=()):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int64 or not t.is_contiguous() \
+                    or tuple(t.shape[1:]) != shape_tail:
+                raise TypeError(f"{name} must be a contiguous int64 CUDA tensor of shape (n{''.join(', %d' % v for v in shape_tail)})")
+            if t.device.index != self.device:
+                raise GlcError(GLC_EINVAL, f"{name} is on {t.device}, this context on device {self.device}")
+            return t
+
+        if not isinstance(arena, torch.Tensor) or not arena.is_cuda or arena.dtype != torch.uint8 or arena.dim() != 1 \
+                or not arena.is_contiguous():
+            raise TypeError("arena must be a contiguous 1-D uint8 CUDA tensor")
+        if arena.device.index != self.device:
+            raise GlcError(GLC_EINVAL, f"arena is on {arena.device}, this context on device {self.device}")
+        entries, lengths = index(entries, "entries", (4,)), index(lengths, "lengths")
+        clips, starts = index(clips, "clips"), index(starts, "starts")
+        if lengths.shape[0] != entries.shape[0] or starts.shape[0] != clips.shape[0]:
+            raise GlcError(GLC_EINVAL, "one length per entry and one start per clip index")
+        b, length, max_length = clips.shape[0], int(length), int(max_length)
+        if length < 0 or max_length < 0:
+            raise GlcError(GLC_EINVAL, "length and max_length must not be negative")
+        if out is None:
+            out = torch.zeros((b, ch, length) if planar else (b, length, ch), dtype=torch.float32, device=arena.device)
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32 or out.dim() != 3:
+            raise TypeError("out must be a float32 CUDA tensor of shape (B, C, T) or (B, T, C)")
+        if out.device.index != self.device:
+            raise GlcError(GLC_EINVAL, f"out is on {out.device}, this context on device {self.device}")
+        if out.shape[2] > 1 and out.stride(2) != 1:
+            raise TypeError("out: the innermost stride must be 1")
+        if min(out.stride(0), out.stride(1)) < 0:
+            raise TypeError("out: negative strides")
+        ob, oc, ot = (out.shape[0], out.shape[1], out.shape[2]) if planar else (out.shape[0], out.shape[2], out.shape[1])
+        if ob != b or oc != ch or ot != length:
+            raise GlcError(GLC_EINVAL, f"out has shape {tuple(out.shape)} for {b} crops of {ch} channels and {length} samples")
+        if not planar and ot > 1 and out.stride(1) != ch:
+            raise TypeError(f"out: an interleaved clip must be dense (stride {ch} between samples)")
+        lay = GlcClipLayout(b, ch, 1 if planar else 0, out.stride(0), out.stride(1) if planar else 0, length, None)
+        self._enter_torch_stream(out.device)
+        try:
+            check(lib.glc_decode_crops_device_store(self._h, C.c_void_p(arena.data_ptr()), arena.numel(),
+                                                    C.c_void_p(entries.data_ptr()), C.c_void_p(lengths.data_ptr()), entries.shape[0],
+                                                    max_length, C.c_void_p(clips.data_ptr()), C.c_void_p(starts.data_ptr()), length,
+                                                    C.c_void_p(out.data_ptr()), C.byref(lay)), self._h)
         finally:
             self.set_stream(0)
         self._compact_clips = b

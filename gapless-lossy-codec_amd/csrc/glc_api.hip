@@ -1819,19 +1819,8 @@ int decode_prepared_to_host(glc_ctx *ctx, T *pcm_out, uint64_t cap, uint64_t *n_
 // (planes) in planes `cstride` apart.
 glc::HopDescStrided *write_hop_descs(glc::HopDescStrided *d, uint64_t nf, uint32_t ch, const glc::Trim &trim, uint64_t h0,
                                      uint64_t h1, int64_t base, uint64_t dst, bool planes, uint64_t cstride) {
-  const uint64_t per_hop = uint64_t(glc::kHop) * ch, lo_all = trim.start, hi_all = trim.start + trim.n;
-  for (uint64_t h = h0; h < h1; ++h) {
-    const uint64_t lo = std::max(lo_all, h * per_hop), hi = std::min(hi_all, (h + 1) * per_hop);
-    if (hi <= lo) continue;
-    const uint64_t j0 = lo - trim.start;
-    *d++ = glc::HopDescStrided{h >= 1 ? static_cast<int32_t>(base + static_cast<int64_t>(h) - 1) : -1,
-                               h < nf ? static_cast<int32_t>(base + static_cast<int64_t>(h)) : -1,
-                               static_cast<uint32_t>(lo - h * per_hop),
-                               static_cast<uint32_t>(hi - lo),
-                               planes ? dst : dst + j0,
-                               planes ? cstride : 0ull,
-                               j0};
-  }
+  for (uint64_t h = h0; h < h1; ++h)
+    if (glc::hop_desc(d, nf, ch, trim, h, base, dst, planes, cstride)) ++d;  // glc_kernels.h: the one statement of a descriptor
   return d;
 }
 
@@ -3072,6 +3061,186 @@ int glc_decode_compact_last_status(glc_ctx *ctx, glc_compact_status *status, uin
   } catch (const std::bad_alloc &) {
     return fail(ctx, GLC_ENOMEM, "glc_decode_compact_last_status: host allocation failed");
   }
+  return GLC_OK;
+}
+
+// ------------------------------------------------------------------------------ crops drawn from the store by device-side index
+
+extern "C++" {
+namespace {
+
+// What glc_decode_crops_device_store and its planner hook share: the checks of everything the host can see, and the
+// geometry of the call - the slots of a crop, the crops of a round, and where the planner's three arrays lie in rtb_tab.
+struct SdGeom {
+  glc::CropSlots slots{};
+  uint64_t per_round = 0, max_front = 0;
+  size_t o_dir = 0, o_desc = 0, o_verdict = 0, tab = 0;
+};
+
+int sd_check(glc_ctx *ctx, const std::string &w, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
+             const int64_t *d_lengths, uint64_t n_entries, uint64_t max_length, const int64_t *d_clips, const int64_t *d_starts,
+             uint64_t length, const float *d_out, const glc_clip_layout *out, SdGeom *g) {
+  if (!d_arena || !d_entries || !d_lengths || !d_clips || !d_starts || !d_out) return fail(ctx, GLC_EINVAL, w + ": null argument");
+  if (out->channels == 0) return fail(ctx, GLC_EINVAL, w + ": channels == 0");
+  const uint64_t n = out->n_clips, ch = out->channels;
+  if (reinterpret_cast<uintptr_t>(d_arena) & 63u) return fail(ctx, GLC_EINVAL, w + ": the arena is not 64-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(d_entries) | reinterpret_cast<uintptr_t>(d_lengths) | reinterpret_cast<uintptr_t>(d_clips) |
+       reinterpret_cast<uintptr_t>(d_starts)) & 7u)
+    return fail(ctx, GLC_EINVAL, w + ": entries, lengths, clips and starts must be 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_out) & 3u) return fail(ctx, GLC_EINVAL, w + ": output pointer not aligned to its sample size");
+  if (n_entries == 0) return fail(ctx, GLC_EINVAL, w + ": n_entries == 0");
+  if (length == 0) return fail(ctx, GLC_EINVAL, w + ": length == 0");
+  if (max_length < length) return fail(ctx, GLC_EINVAL, w + ": max_length is smaller than the crop");
+  if (max_length > (UINT64_MAX >> 12) / ch) return fail(ctx, GLC_EINVAL, w + ": max_length: stream too long");
+  const glc_plan longest = glc::plan_encode(max_length * ch, out->channels);
+  if (longest.n_frames == 0)
+    return fail(ctx, GLC_EINVAL, w + ": max_length: the reference encoder panics on this input (<= 512 samples per channel)");
+  if (longest.n_frames * ch > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, w + ": max_length: stream too long");
+  const RtbLayout lo{out};
+  if (out->lengths) {
+    for (uint64_t i = 0; i < n; ++i)
+      if (out->lengths[i] != length) return fail(ctx, GLC_EINVAL, w + ": clip " + std::to_string(i) + ": the layout's length is not the crop's");
+  } else if (out->length != length) {
+    return fail(ctx, GLC_EINVAL, w + ": the layout's length is not the crop's");
+  }
+  const uint64_t occupies = lo.planes() ? (ch - 1) * out->channel_stride + length : length * ch;
+  if (lo.planes() && out->channel_stride < length) return fail(ctx, GLC_EINVAL, w + ": channel_stride is smaller than a plane");
+  if (n > 1 && out->clip_stride < occupies) return fail(ctx, GLC_EINVAL, w + ": clip_stride is smaller than the clip");
+  g->slots = glc::store_crop_slots(length, out->channels);
+  if (g->slots.max_frames + 1 > glc::kStoreRoundBudget)
+    return fail(ctx, GLC_EINVAL, w + ": a crop of this length does not fit a round (glc_decode_crops_device_compact takes such windows)");
+  g->per_round = glc::kStoreRoundBudget / (g->slots.max_frames + 1);
+  g->max_front = longest.n_frames * ch;
+  const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_out), b1 = b0 + ((n - 1) * out->clip_stride + occupies) * sizeof(float);
+  auto overlaps = [&](const void *p, uint64_t bytes) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(p), a1 = a0 + bytes;
+    return a0 < b1 && b0 < a1;
+  };
+  if (overlaps(d_arena, arena_bytes)) return fail(ctx, GLC_EINVAL, w + ": the output extent overlaps the arena");
+  if (overlaps(d_entries, n_entries * sizeof(glc_store_entry)) || overlaps(d_lengths, n_entries * 8) || overlaps(d_clips, n * 8) ||
+      overlaps(d_starts, n * 8))
+    return fail(ctx, GLC_EINVAL, w + ": the output extent overlaps an index array");
+  size_t tab = 0;
+  auto place = [&](size_t bytes) {
+    const size_t at = tab;
+    tab = align_up(tab + bytes, 256);
+    return at;
+  };
+  g->o_dir = place(n * sizeof(glc::CompactBlob));
+  g->o_desc = place(n * g->slots.max_hops * sizeof(glc::HopDescStrided));
+  g->o_verdict = place(n * sizeof(uint32_t));
+  g->tab = tab;
+  return GLC_OK;
+}
+
+// The planner's launch: the call's only word about the selection.  rtb_tab is written by the DEVICE here - the
+// pinned image of the other batch calls is not touched and their upload event not waited for (an upload still on
+// its way is in front of this kernel on the stream).
+int sd_plan(glc_ctx *ctx, const SdGeom &g, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
+            const int64_t *d_lengths, uint64_t n_entries, uint64_t max_length, const int64_t *d_clips, const int64_t *d_starts,
+            uint64_t length, const glc_clip_layout *out) {
+  uint8_t *d_tab = static_cast<uint8_t *>(ctx->rtb_tab.p);
+  const RtbLayout lo{out};
+  glc::StoreDraw a{};
+  a.arena = reinterpret_cast<uintptr_t>(d_arena), a.arena_bytes = arena_bytes;
+  a.entries = d_entries, a.lengths = d_lengths, a.n_entries = n_entries, a.max_length = max_length;
+  a.clips = d_clips, a.starts = d_starts, a.length = length, a.n_crops = out->n_clips;
+  a.ch = out->channels, a.max_hops = static_cast<uint32_t>(g.slots.max_hops), a.max_frames = static_cast<uint32_t>(g.slots.max_frames);
+  a.per_round = static_cast<uint32_t>(g.per_round);
+  a.clip_stride = out->clip_stride, a.channel_stride = out->channel_stride, a.planes = lo.planes() ? 1u : 0u;
+  a.dir = reinterpret_cast<glc::CompactBlob *>(d_tab + g.o_dir);
+  a.desc = reinterpret_cast<glc::HopDescStrided *>(d_tab + g.o_desc);
+  a.verdict = reinterpret_cast<uint32_t *>(d_tab + g.o_verdict);
+  GLC_HIP(ctx, glc::launch_store_plan_crops(a, ctx->stream));
+  return GLC_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int glc_store_crop_slots(uint64_t length, uint16_t channels, uint64_t *max_hops, uint64_t *max_frames) {
+  if (!max_hops || !max_frames || channels == 0 || length == 0 || length > (UINT64_MAX >> 12) / channels) {
+    glc::set_global_error("glc_store_crop_slots: a null pointer, channels == 0, length == 0 or a length whose samples wrap");
+    return GLC_EINVAL;
+  }
+  const glc::CropSlots s = glc::store_crop_slots(length, channels);
+  *max_hops = s.max_hops, *max_frames = s.max_frames;
+  return GLC_OK;
+}
+
+int glc_decode_crops_device_store(glc_ctx *ctx, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
+                                  const int64_t *d_lengths, uint64_t n_entries, uint64_t max_length, const int64_t *d_clips,
+                                  const int64_t *d_starts, uint64_t length, float *d_out, const glc_clip_layout *out) {
+  const std::string w("glc_decode_crops_device_store");
+  if (!ctx) return GLC_EINVAL;
+  if (!out) return fail(ctx, GLC_EINVAL, w + ": null argument");
+  if (out->n_clips == 0) return GLC_OK;
+  SdGeom g;
+  int rc = sd_check(ctx, w, d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips, d_starts, length, d_out, out, &g);
+  if (rc != GLC_OK) return rc;
+  const uint64_t n = out->n_clips;
+  const uint32_t ch = out->channels;
+  const size_t slot = static_cast<size_t>(ch) * glc::kFrame;
+  const uint64_t widest = std::min(n, g.per_round) * g.slots.max_frames;  // frames (block slots) of the fullest round
+  DeviceGuard guard(ctx->device);
+  rt_forget_streams(ctx);
+  ctx->cd_status_n = 0;
+  rc = rt_reserve(ctx, ctx->rt_rows, glc::rows_from_compact_window_bytes(static_cast<uint32_t>(widest * ch)));
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->blocks, widest * slot * sizeof(float));
+  if (rc == GLC_OK) rc = reserve_d1_plan(ctx, widest, ch);
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rtb_tab, g.tab);
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->cd_status, n * sizeof(glc::CompactStatus));
+  if (rc == GLC_OK) rc = sd_plan(ctx, g, d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips, d_starts, length, out);
+  if (rc != GLC_OK) return rc;
+  const uint8_t *d_tab = static_cast<const uint8_t *>(ctx->rtb_tab.p);
+  const auto *d_dir = reinterpret_cast<const glc::CompactBlob *>(d_tab + g.o_dir);
+  const auto *d_desc = reinterpret_cast<const glc::HopDescStrided *>(d_tab + g.o_desc);
+  const auto *d_verdict = reinterpret_cast<const uint32_t *>(d_tab + g.o_verdict);
+  auto *d_status = static_cast<glc::CompactStatus *>(ctx->cd_status.p);
+  float *blocks = static_cast<float *>(ctx->blocks.p);
+  const bool out_planes = RtbLayout{out}.planes();
+  hipStream_t st = ctx->stream;
+  // one chain per round, each the same launches whatever the selection holds: the rounds differ only in their first crop
+  for (uint64_t first = 0; first < n; first += g.per_round) {
+    const uint64_t nr = std::min(g.per_round, n - first);
+    const uint32_t M = static_cast<uint32_t>(nr * g.slots.max_frames * ch);
+    glc::DecodeRows rows{};
+    // pairs and raw planes are addressed from the arena: every usable blob lies inside it, 64-byte aligned
+    GLC_HIP(ctx, glc::launch_rows_from_compact_window(d_dir + first, glc::CompactBlob{}, static_cast<uint32_t>(nr), M, ch,
+                                                      static_cast<uint32_t>(g.max_front), d_arena, ctx->rt_rows.p, d_status + first, st,
+                                                      &rows, d_verdict + first));
+    GLC_HIP(ctx, glc::launch_imdct_rows(ctx->dev, rows, 0, M, ch, blocks, st, ctx->d1_variant, ctx->dec_plan.p,
+                                        ctx->dec_plan.p ? ctx->dec_plan_groups : 0, false));
+    GLC_HIP(ctx, glc::launch_overlap_add_strided(blocks, d_desc + first * g.slots.max_hops, static_cast<uint32_t>(nr * g.slots.max_hops), ch,
+                                                 out_planes, d_out, st));
+  }
+  ctx->cd_status_n = n;
+  return GLC_OK;
+}
+
+int glc_debug_store_plan_device(glc_ctx *ctx, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
+                                const int64_t *d_lengths, uint64_t n_entries, uint64_t max_length, const int64_t *d_clips,
+                                const int64_t *d_starts, uint64_t length, const float *d_out, const glc_clip_layout *out, void *dir,
+                                void *desc, uint32_t *verdict) {
+  const std::string w("glc_debug_store_plan_device");
+  if (!ctx) return GLC_EINVAL;
+  if (!out || !dir || !desc || !verdict) return fail(ctx, GLC_EINVAL, w + ": null argument");
+  if (out->n_clips == 0) return GLC_OK;
+  SdGeom g;
+  int rc = sd_check(ctx, w, d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips, d_starts, length, d_out, out, &g);
+  if (rc != GLC_OK) return rc;
+  DeviceGuard guard(ctx->device);
+  rt_forget_streams(ctx);
+  ctx->cd_status_n = 0;
+  rc = rt_reserve(ctx, ctx->rtb_tab, g.tab);
+  if (rc == GLC_OK) rc = sd_plan(ctx, g, d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips, d_starts, length, out);
+  if (rc != GLC_OK) return rc;
+  const uint64_t n = out->n_clips;
+  const uint8_t *d_tab = static_cast<const uint8_t *>(ctx->rtb_tab.p);
+  GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  GLC_HIP(ctx, hipMemcpy(dir, d_tab + g.o_dir, n * sizeof(glc::CompactBlob), hipMemcpyDeviceToHost));
+  GLC_HIP(ctx, hipMemcpy(desc, d_tab + g.o_desc, n * g.slots.max_hops * sizeof(glc::HopDescStrided), hipMemcpyDeviceToHost));
+  GLC_HIP(ctx, hipMemcpy(verdict, d_tab + g.o_verdict, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return GLC_OK;
 }
 

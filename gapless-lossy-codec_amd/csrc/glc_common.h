@@ -8,6 +8,13 @@
 
 #include "../../include/glc.h"
 
+// GLC_HD: stated once for the host drivers and the device kernels, which call the same function.
+#if defined(__HIP__) || defined(__HIPCC__)
+#define GLC_HD __host__ __device__
+#else
+#define GLC_HD
+#endif
+
 namespace glc {
 
 constexpr uint32_t kFrame = GLC_FRAME_SIZE;  // FRAME_SIZE, src/codec.rs:15
@@ -40,11 +47,25 @@ struct HostTables {
 void build_host_tables(uint32_t sample_rate, HostTables &t);
 
 // Padding arithmetic of Encoder::encode, src/codec.rs:433-455.
-glc_plan plan_encode(uint64_t n_samples, uint16_t channels);
-
-// What a crop of the decoded clip needs of its stream (include/glc.h glc_plan_crop; DESIGN section 3, "a window of a
-// compact blob"): the ONE statement of that geometry.  false: what glc_plan_crop refuses.
-bool plan_crop(uint64_t n_samples, uint16_t channels, const glc_crop &crop, glc_crop_plan *out);
+GLC_HD inline glc_plan plan_encode(uint64_t n_samples, uint16_t channels) {
+  glc_plan p{};
+  if (channels == 0) return p;  // `i % ch` panics, src/codec.rs:430
+  const uint64_t ch = channels;
+  auto per_channel = [&](uint64_t c) { return n_samples > c ? (n_samples - c + ch - 1) / ch : 0; };
+  auto padded = [](uint64_t len) { return ((kHop / 2 + len + kHop - 1) / kHop) * kHop + kHop / 2; };
+  const uint64_t l0 = per_channel(0);
+  const uint64_t p0 = padded(l0);
+  const uint64_t nf = p0 < kFrame ? 1 : (p0 - kFrame) / kHop + 1;  // :449-455
+  const uint64_t last_end = (nf - 1) * kHop + kFrame;              // slice end, :474
+  // per_channel(c) descends with c: the last channel is the shortest (a ragged tail leaves it one sample short)
+  if (padded(per_channel(ch - 1)) < last_end) return p;  // reference panics: slice out of range
+  p.n_frames = nf;
+  p.padded_len = p0;
+  p.per_channel = l0;
+  p.encoder_delay = kHop / 2;                                  // :547
+  p.padding = static_cast<uint32_t>(p0 - l0 - kHop / 2);       // :546
+  return p;
+}
 
 // Per-channel samples [lo, hi) that frames [f0, f1) read (f1 > f0), clipped to a stream of `per_channel`:
 // [hop*f0 - hop/2, hop*(f1-1) - hop/2 + frame), src/codec.rs:449-474.
@@ -62,7 +83,7 @@ inline SampleWindow frame_sample_window(uint64_t f0, uint64_t f1, uint64_t per_c
 struct Trim {
   uint64_t start, n;
 };
-inline Trim gapless_trim(uint64_t n_frames, uint32_t ch, uint64_t encoder_delay, uint64_t original_length) {
+GLC_HD inline Trim gapless_trim(uint64_t n_frames, uint32_t ch, uint64_t encoder_delay, uint64_t original_length) {
   Trim t{0, (n_frames + 1) * static_cast<uint64_t>(kHop) * ch};
   if (t.n > encoder_delay) {
     t.start = encoder_delay;
@@ -71,6 +92,40 @@ inline Trim gapless_trim(uint64_t n_frames, uint32_t ch, uint64_t encoder_delay,
   if (t.n > original_length) t.n = original_length;
   return t;
 }
+
+// What a crop of the decoded clip needs of its stream (include/glc.h glc_plan_crop; DESIGN section 3, "a window of a
+// compact blob"): the ONE statement of that geometry.  false: what glc_plan_crop refuses.
+GLC_HD inline bool plan_crop(uint64_t n_samples, uint16_t channels, const glc_crop &crop, glc_crop_plan *out) {
+  const glc_plan plan = plan_encode(n_samples, channels);
+  if (plan.n_frames == 0) return false;
+  const uint64_t ch = channels, per_hop = static_cast<uint64_t>(kHop) * ch;
+  const Trim trim = gapless_trim(plan.n_frames, channels, plan.encoder_delay, n_samples);
+  const uint64_t len = trim.n / ch;  // the decoded clip, per channel
+  if (crop.length == 0 || crop.length > len || crop.start > len - crop.length) return false;
+  // un-trimmed positions [lo, hi): the delay counts INTERLEAVED samples (Q3)
+  const uint64_t lo = trim.start + crop.start * ch, hi = lo + crop.length * ch;
+  const uint64_t h_lo = lo / per_hop, h_hi = (hi - 1) / per_hop;  // hops of the first and of the last kept sample
+  // hop h = second half of frame h - 1 + first half of frame h: the halo frame in front, none for the bare tail hop
+  const uint64_t f_lo = (h_lo > 1 ? h_lo : 1) - 1, f_hi = h_hi < plan.n_frames - 1 ? h_hi : plan.n_frames - 1;
+  *out = glc_crop_plan{f_lo, f_hi - f_lo + 1, h_lo, h_hi - h_lo + 1};
+  return true;
+}
+
+// The slots a crop of `length` samples per channel needs wherever it starts (include/glc.h glc_store_crop_slots): it
+// lies at the un-trimmed interleaved positions [lo, lo + length * ch), lo = 512 + start * ch, and spans the most
+// hops when lo lies as late in its hop as a start can put it - at 1024 ch - ch + 512 % ch, the largest value below
+// 1024 ch that is 512 modulo ch.  One frame more than hops: the halo frame.  length >= 1, length * ch must not wrap.
+struct CropSlots {
+  uint64_t max_hops, max_frames;
+};
+GLC_HD inline CropSlots store_crop_slots(uint64_t length, uint32_t ch) {
+  const uint64_t per_hop = static_cast<uint64_t>(kHop) * ch;
+  const uint64_t hops = (per_hop - ch + (kHop / 2) % ch + length * ch - 1) / per_hop + 1;
+  return {hops, hops + 1};
+}
+// Crops of a round of glc_decode_crops_device_store: each counts its slot's frames + 1, as the crops of the pointer
+// call count their windows', against the 4096 frames + 1 of a decode round.
+constexpr uint64_t kStoreRoundBudget = 4097;
 
 // Fixed-size device record (see include/glc.h glc_record_bytes).
 inline uint64_t record_header_bytes(uint32_t ch) { return ((8ull + 8ull * ch) + 15ull) & ~15ull; }
@@ -98,11 +153,6 @@ struct CompactHeader {
 static_assert(sizeof(CompactHeader) == 64, "compact header is 64 bytes");
 // The layout and the header rule below are the only statement of either: the host drivers and the device
 // kernels (P1-P3 write a blob, R2 reads one) call the same functions.
-#if defined(__HIP__) || defined(__HIPCC__)
-#define GLC_HD __host__ __device__
-#else
-#define GLC_HD
-#endif
 GLC_HD inline uint64_t align64(uint64_t v) { return (v + 63ull) & ~63ull; }
 struct CompactLayout {
   uint64_t o_israw, o_scale, o_cnt, o_pairs;  // byte offsets of the fixed sections

@@ -190,11 +190,18 @@ hipError_t launch_rows_from_compact(const CompactBlob *dir, const CompactBlob &o
 // align256(8 M), align256(8 M) bytes (32 B per WINDOW row) + 2 x align256(8 ceil(M / 1024)) bytes of block sums, M
 // counted as 1 when 0, align256 = rounding up to 256: nothing in it is per row of a blob.  Five launches (four
 // without the prefix) whatever n_entries (up to 65535; one more prefix launch per 65535 beyond), no synchronisation, no
-// workgroup waits for another.  max_front: the largest win[0] of the entries (it sizes the prefix launch).
+// workgroup waits for another.  max_front: the largest win[0] of the entries, or a bound of it (it sizes the prefix
+// launch).
+// Fixed slots (glc_decode_crops_device_store): an entry may own MORE table rows than its window has - first_row of
+// the next entry lies further on, and M counts the slots.  The rows of a slot behind the window are empty rows
+// (count 0, scale 0.0f, no raw plane) that report nothing; win[1] may then be 0.  verdict (null, or n_entries device
+// words): bits that join kCompactBadHeader in the status of an entry whose header check fails - the draw planner's
+// word about an entry it emptied (cap 0: the capacity pre-check fails it and nothing is read).
 uint64_t rows_from_compact_window_bytes(uint32_t M);
 hipError_t launch_rows_from_compact_window(const CompactBlob *dir, const CompactBlob &one, uint32_t n_entries, uint32_t M,
                                            uint32_t ch, uint32_t max_front, const void *base, void *workspace,
-                                           CompactStatus *status, hipStream_t s, DecodeRows *rows);
+                                           CompactStatus *status, hipStream_t s, DecodeRows *rows,
+                                           const uint32_t *verdict = nullptr);
 // variant (include/glc_debug.h): 0 = shipped (k_imdct_plan + k_imdct_apply, absent row pairs skipped
 // by scalar branches); 1 = one row per workgroup (the cross-check kernel); 2 = plan + apply without
 // the skip; 3 = without the issue-priority schedule; 4 = skipping in row pairs only.  All but 1 need a workspace `plan` of imdct_plan_bytes(plan_groups) bytes,
@@ -243,6 +250,57 @@ struct HopDescStrided {
 };
 hipError_t launch_overlap_add_strided(const float *blocks, const HopDescStrided *desc, uint32_t n_desc, uint32_t ch, bool planar,
                                       float *out, hipStream_t s);
+// The descriptor of hop h of a clip of `nf` frames whose frame f is block slot base + f, the ONE statement of it for
+// the host drivers (write_hop_descs) and the draw planner: the span of the hop that `trim` keeps lands from element
+// `dst` on, interleaved, or (planes) in planes `cstride` apart.  false: the trim keeps nothing of the hop.
+GLC_HD inline bool hop_desc(HopDescStrided *d, uint64_t nf, uint32_t ch, const Trim &trim, uint64_t h, int64_t base, uint64_t dst,
+                            bool planes, uint64_t cstride) {
+  const uint64_t per_hop = uint64_t(kHop) * ch, lo_all = trim.start, hi_all = trim.start + trim.n;
+  const uint64_t lo = lo_all > h * per_hop ? lo_all : h * per_hop, hi = hi_all < (h + 1) * per_hop ? hi_all : (h + 1) * per_hop;
+  if (hi <= lo) return false;
+  const uint64_t j0 = lo - trim.start;
+  *d = HopDescStrided{h >= 1 ? static_cast<int32_t>(base + static_cast<int64_t>(h) - 1) : -1,
+                      h < nf ? static_cast<int32_t>(base + static_cast<int64_t>(h)) : -1,
+                      static_cast<uint32_t>(lo - h * per_hop),
+                      static_cast<uint32_t>(hi - lo),
+                      planes ? dst : dst + j0,
+                      planes ? cstride : 0ull,
+                      j0};
+  return true;
+}
+
+// The draw planner (glc_decode_crops_device_store; DESIGN section 3, "drawing from the store"): crop i of n_crops is
+// samples [starts[i], starts[i] + length) per channel of stored clip clips[i] - device data, as are the store's index
+// entries[n_entries] and the clips' lengths[n_entries] (samples per channel).  Crop i is number k = i % per_round of
+// round i / per_round and owns there table rows [k * max_frames * ch, (k + 1) * max_frames * ch), block slots
+// [k * max_frames, (k + 1) * max_frames) and descriptors [k * max_hops, (k + 1) * max_hops) (glc_common.h
+// store_crop_slots).  Written, one launch for all rounds:
+//   dir[i]      usable: {arena + offset, bytes, k * max_frames * ch, frames(len) * ch, {first_frame * ch, n_frames * ch}}
+//               (glc_common.h plan_crop); unusable: {arena, 0, k * max_frames * ch, 0, {0, 0}}
+//   desc[i * max_hops + s]   usable: hop_desc of hop first_hop + s with base = k * max_frames - first_frame and the
+//               destination of clip i of the output layout, null ({-1, -1, 0, 0, 0, 0, 0}) from n_hops on; unusable:
+//               both slots absent over interleaved samples [s * 1024 ch, (s + 1) * 1024 ch) of the span (+0.0)
+//   verdict[i]  0, kCompactBadCrop (clip index outside [0, n_entries), a length below 0, above max_length or one the
+//               encoder refuses, start < 0, start + length beyond the clip: the entry is then not read) or
+//               kCompactNoBlob (stored == 0, offset no multiple of 64, [offset, offset + bytes) not inside the arena)
+// max_length * ch must not wrap and frames(max_length) * ch must fit 32 bits (the caller's check).  No load leaves
+// the four index arrays; `arena` is a number here, nothing of the arena is read.
+constexpr uint32_t kCompactNoBlob = 64u, kCompactBadCrop = 128u;
+struct StoreDraw {
+  uint64_t arena, arena_bytes;
+  const glc_store_entry *entries;
+  const int64_t *lengths;
+  uint64_t n_entries, max_length;
+  const int64_t *clips, *starts;
+  uint64_t length, n_crops;
+  uint32_t ch, max_hops, max_frames, per_round;
+  uint64_t clip_stride, channel_stride;  // of the output layout, in elements
+  uint32_t planes, pad;                  // planes: planar output of more than one channel
+  CompactBlob *dir;
+  HopDescStrided *desc;
+  uint32_t *verdict;
+};
+hipError_t launch_store_plan_crops(const StoreDraw &a, hipStream_t s);
 // The interleaved descriptor with a 32-bit destination, 24 bytes instead of 40: what glc_decode_batch uploads per
 // kept hop (its rounds address their output in 31 bits).  Same kernel, same chunks; kept beside HopDescStrided
 // because that driver measured slower, per launch and per call, with the wide form.

@@ -1606,8 +1606,11 @@ __device__ __forceinline__ unsigned r2_find_blob(const CompactBlob *__restrict__
   return lo;
 }
 
+// verdict (null, or one word per entry: the draw planner's, k_store_plan_crops): the bits it gave an entry it emptied
+// join kCompactBadHeader in the status this kernel writes wholesale.
 __global__ __launch_bounds__(256) void k_r2_headers(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned n_blobs,
-                                                     unsigned ch, CompactStatus *__restrict__ status) {
+                                                     unsigned ch, CompactStatus *__restrict__ status,
+                                                     const unsigned *__restrict__ verdict) {
   const unsigned b = blockIdx.x * 256u + threadIdx.x;
   if (b >= n_blobs) return;
   const CompactBlob e = dir ? dir[b] : one;
@@ -1623,7 +1626,7 @@ __global__ __launch_bounds__(256) void k_r2_headers(const CompactBlob *__restric
   }
   st.header_ok = ok ? 1u : 0u;
   if (!ok) {  // every row is rejected
-    st.flags = kCompactBadHeader;
+    st.flags = kCompactBadHeader | (verdict ? verdict[b] : 0u);
     st.n_bad_rows = e.rows;
     st.first_bad_row = 0;
   }
@@ -1778,6 +1781,9 @@ __global__ __launch_bounds__(256) void k_r2_rows(const CompactBlob *__restrict__
 //                      its blob with the arithmetic it has; and for a header that failed the rows that rejects: the
 //                      window's, not the blob's
 //   k_r2w_rows         one wave per window row: r2_row
+// An entry may own more table rows than its window has (the next entry's first_row lies further on: the fixed slots
+// of glc_decode_crops_device_store, or an entry whose window is empty).  Row first_row + j with j >= win[1] is an
+// empty row: the scans see the word 0, k_r2w_rows writes {0, 0, 0.0f, -1, 0} and reports nothing.
 // ------------------------------------------------------------------------------------------
 constexpr unsigned kR2wPrefixRows = 4096;  // rows in front of a window that one workgroup of k_r2w_prefix sums
 
@@ -1818,7 +1824,8 @@ __global__ __launch_bounds__(256) void k_r2w_scan_rows(const CompactBlob *__rest
       [&](unsigned m) -> unsigned long long {
         const unsigned b = dir ? r2_find_blob(dir, n_entries, m) : 0u;
         const CompactBlob e = dir ? dir[b] : one;
-        if (!status[b].header_ok) return 0ull;
+        // a row of the entry's slot behind its window (the fixed slots of the store draw): an empty row
+        if (m - e.first_row >= e.win[1] || !status[b].header_ok) return 0ull;
         return r2_row_word(e, ch, e.win[0] + (m - e.first_row));
       },
       M, loc, blk, blk_raw);
@@ -1860,8 +1867,86 @@ __global__ __launch_bounds__(256) void k_r2w_rows(const CompactBlob *__restrict_
   const unsigned m = static_cast<unsigned>(m64);
   const unsigned b = dir ? r2_find_blob(dir, n_entries, m) : 0u;
   const CompactBlob e = dir ? dir[b] : one;
+  if (m - e.first_row >= e.win[1]) {  // behind the window: the empty row, and nothing to report
+    if (lane == 0) row_begin[m] = 0ull, row_cnt[m] = 0u, row_scale[m] = 0.0f, row_raw[m] = -1ll, row_raw_len[m] = 0ull;
+    return;
+  }
   r2_row(e, status + b, ch, base_addr, e.win[0] + (m - e.first_row), m, blk, blk_raw, row_begin, row_cnt, row_scale, row_raw,
          row_raw_len, lane);
+}
+
+// ------------------------------------------------------------------------------------------
+// The draw planner of glc_decode_crops_device_store (glc_kernels.h launch_store_plan_crops has the rules): what the
+// host drivers of the pointer calls work out per crop - plan_encode, plan_crop, the directory entry, the hop
+// descriptors, all from glc_common.h / glc_kernels.h, the same functions - for selections that are device data.
+// One thread per (crop, hop slot): the kernel is a chain of three dependent loads (clip index -> length and entry)
+// and some 64-bit integer arithmetic, so it is latency-bound whatever the split; with a thread per slot the
+// descriptors of a crop go out as one store each from neighbouring lanes instead of max_hops stores one after the
+// other from one lane, and the plan every thread of a crop repeats costs nothing that matters beside the loads
+// (which the crop's threads share in cache).  Slot 0 of a crop also writes its directory entry and its verdict.
+// Ordinary vector loads and stores, no atomics; nothing of the arena is dereferenced.
+// Descriptors behind a crop's hops are null ({-1, -1, 0, 0, 0, 0, 0}): k_overlap_add_strided gives a span of cnt == 0
+// at most one chunk whose four `keep` are all false - d2_store then stores element by element and keeps none, and
+// d2_sample reads no block when both slots are absent - and k_overlap_add_planar returns at t_hi <= t_lo.  Neither
+// writes anything.  An unusable crop gets descriptors with both slots absent over its whole span: +0.0.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_store_plan_crops(StoreDraw a) {
+  const unsigned long long t = static_cast<unsigned long long>(blockIdx.x) * 256ull + threadIdx.x;
+  if (t >= a.n_crops * a.max_hops) return;
+  const unsigned long long i = t / a.max_hops;
+  const unsigned s = static_cast<unsigned>(t - i * a.max_hops);
+  const unsigned k = static_cast<unsigned>(i % a.per_round);  // the crop's place in its round
+  const unsigned long long ch = a.ch, per_hop = static_cast<unsigned long long>(kHop) * ch;
+  const long long clip = a.clips[i], start = a.starts[i];
+  unsigned verdict = 0;
+  glc_plan plan{};
+  glc_crop_plan win{};
+  unsigned long long addr = a.arena, cap = 0;
+  if (clip < 0 || static_cast<unsigned long long>(clip) >= a.n_entries) {
+    verdict = kCompactBadCrop;  // and the entry is not read
+  } else {
+    const long long len = a.lengths[clip];
+    // len <= max_length bounds len * ch (the host checked max_length), start <= len - length bounds start * ch
+    if (len < 0 || static_cast<unsigned long long>(len) > a.max_length || start < 0) {
+      verdict = kCompactBadCrop;
+    } else {
+      const unsigned long long n_samples = static_cast<unsigned long long>(len) * ch;
+      plan = plan_encode(n_samples, static_cast<uint16_t>(a.ch));
+      if (plan.n_frames == 0 ||
+          !plan_crop(n_samples, static_cast<uint16_t>(a.ch), glc_crop{static_cast<unsigned long long>(start), a.length}, &win))
+        verdict = kCompactBadCrop;
+    }
+    if (!verdict) {
+      const glc_store_entry e = a.entries[clip];
+      // each term is bounded before the difference is formed: nothing wraps (compact_header_fault's way)
+      if (e.stored == 0 || (e.offset & 63ull) || e.offset > a.arena_bytes || e.bytes > a.arena_bytes - e.offset)
+        verdict = kCompactNoBlob;
+      else
+        addr = a.arena + e.offset, cap = e.bytes;
+    }
+  }
+  const unsigned slot0 = k * a.max_frames;  // the crop's first block slot; its first table row is slot0 * ch
+  if (s == 0) {
+    a.dir[i] = verdict ? CompactBlob{a.arena, 0ull, slot0 * a.ch, 0u, {0u, 0u}}
+                       : CompactBlob{addr, cap, slot0 * a.ch, static_cast<unsigned>(plan.n_frames * ch),
+                                     {static_cast<unsigned>(win.first_frame * ch), static_cast<unsigned>(win.n_frames * ch)}};
+    a.verdict[i] = verdict;
+  }
+  const unsigned long long dst = i * a.clip_stride, span = a.length * ch;
+  HopDescStrided d{-1, -1, 0u, 0u, 0ull, 0ull, 0ull};
+  if (verdict) {  // silence over the whole span, a hop's worth per slot
+    const unsigned long long j0 = s * per_hop;
+    if (j0 < span) {
+      const unsigned long long cnt = span - j0 < per_hop ? span - j0 : per_hop;
+      d = HopDescStrided{-1, -1, 0u, static_cast<unsigned>(cnt), a.planes ? dst : dst + j0, a.planes ? a.channel_stride : 0ull, j0};
+    }
+  } else if (s < win.n_hops) {
+    const Trim whole = gapless_trim(plan.n_frames, a.ch, plan.encoder_delay, plan.per_channel * ch);
+    const Trim trim{whole.start + static_cast<unsigned long long>(start) * ch, span};  // what the crop keeps of its un-trimmed stream
+    hop_desc(&d, plan.n_frames, a.ch, trim, win.first_hop + s, static_cast<long long>(slot0) - static_cast<long long>(win.first_frame),
+             dst, a.planes != 0, a.channel_stride);
+  }
+  a.desc[t] = d;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2347,7 +2432,8 @@ hipError_t launch_rows_from_compact(const CompactBlob *dir, const CompactBlob &o
   const R2Tables t = r2_tables(workspace, M);
   const unsigned nblk = static_cast<unsigned>((static_cast<uint64_t>(M) + 1023) / 1024);
   *rows = t.rows(base, base);
-  hipLaunchKernelGGL(k_r2_headers, dim3((n_blobs + 255) / 256), dim3(256), 0, s, dir, one, n_blobs, ch, status);
+  hipLaunchKernelGGL(k_r2_headers, dim3((n_blobs + 255) / 256), dim3(256), 0, s, dir, one, n_blobs, ch, status,
+                     static_cast<const unsigned *>(nullptr));
   if (M == 0) return hipGetLastError();
   hipLaunchKernelGGL(k_r2_scan_rows, dim3(nblk), dim3(256), 0, s, dir, one, n_blobs, M, ch, status, t.row_raw_len, t.blk, t.blk_raw);
   hipLaunchKernelGGL(k_r2_scan_blocks, dim3(1), dim3(1024), 0, s, dir, one, n_blobs, M, t.blk, t.blk_raw, nblk, t.row_raw_len, status);
@@ -2361,7 +2447,7 @@ uint64_t rows_from_compact_window_bytes(uint32_t M) { return r2_tables(nullptr, 
 
 hipError_t launch_rows_from_compact_window(const CompactBlob *dir, const CompactBlob &one, uint32_t n_entries, uint32_t M,
                                            uint32_t ch, uint32_t max_front, const void *base, void *workspace,
-                                           CompactStatus *status, hipStream_t s, DecodeRows *rows) {
+                                           CompactStatus *status, hipStream_t s, DecodeRows *rows, const uint32_t *verdict) {
   if (!workspace || !status || !rows || !base || ch == 0 || n_entries == 0 || (!dir && n_entries != 1)) return hipErrorInvalidValue;
   if (M == 0 || M % ch) return hipErrorInvalidValue;  // whole frames, and every window has some (a directory's entries: the caller's word)
   if (!dir && ((one.addr & 63u) || one.first_row != 0 || one.win[1] != M || one.rows % ch || one.win[0] % ch ||
@@ -2372,7 +2458,7 @@ hipError_t launch_rows_from_compact_window(const CompactBlob *dir, const Compact
   const R2Tables t = r2_tables(workspace, M);
   const unsigned nblk = static_cast<unsigned>((static_cast<uint64_t>(M) + 1023) / 1024);
   *rows = t.rows(base, base);
-  hipLaunchKernelGGL(k_r2_headers, dim3((n_entries + 255) / 256), dim3(256), 0, s, dir, one, n_entries, ch, status);
+  hipLaunchKernelGGL(k_r2_headers, dim3((n_entries + 255) / 256), dim3(256), 0, s, dir, one, n_entries, ch, status, verdict);
   if (max_front) {
     const unsigned chunks = static_cast<unsigned>((static_cast<uint64_t>(max_front) + kR2wPrefixRows - 1) / kR2wPrefixRows);
     for (uint32_t b0 = 0; b0 < n_entries; b0 += 65535u)  // blockIdx.y is 16 bits wide
@@ -2383,6 +2469,18 @@ hipError_t launch_rows_from_compact_window(const CompactBlob *dir, const Compact
   hipLaunchKernelGGL(k_r2w_rows, dim3(static_cast<unsigned>((static_cast<uint64_t>(M) + 3) / 4)), dim3(256), 0, s, dir, one, n_entries,
                      M, ch, static_cast<unsigned long long>(reinterpret_cast<uintptr_t>(base)), t.blk, t.blk_raw, status, t.row_begin,
                      t.row_cnt, t.row_scale, t.row_raw, t.row_raw_len);
+  return hipGetLastError();
+}
+
+hipError_t launch_store_plan_crops(const StoreDraw &a, hipStream_t s) {
+  static_assert(sizeof(glc_store_entry) == 32 && sizeof(HopDescStrided) == 40, "read and written by the planner as laid out here");
+  if (a.n_crops == 0) return hipSuccess;
+  if (!a.entries || !a.lengths || !a.clips || !a.starts || !a.dir || !a.desc || !a.verdict || a.ch == 0 || a.ch > 65535u ||
+      a.max_hops == 0 || a.max_frames != a.max_hops + 1 || a.per_round == 0 || a.length == 0 || a.n_entries == 0)
+    return hipErrorInvalidValue;
+  const uint64_t threads = a.n_crops * a.max_hops, blocks = (threads + 255) / 256;
+  if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_store_plan_crops, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

@@ -106,40 +106,4 @@ void build_host_tables(uint32_t sample_rate, HostTables &t) {
   t.noise_floor = powf(10.0f, kNoiseFloorDb / 20.0f);  // src/codec.rs:277
 }
 
-glc_plan plan_encode(uint64_t n_samples, uint16_t channels) {
-  glc_plan p{};
-  if (channels == 0) return p;  // `i % ch` panics, src/codec.rs:430
-  const uint64_t ch = channels;
-  auto per_channel = [&](uint64_t c) { return n_samples > c ? (n_samples - c + ch - 1) / ch : 0; };
-  auto padded = [](uint64_t len) { return ((kHop / 2 + len + kHop - 1) / kHop) * kHop + kHop / 2; };
-  const uint64_t l0 = per_channel(0);
-  const uint64_t p0 = padded(l0);
-  const uint64_t nf = p0 < kFrame ? 1 : (p0 - kFrame) / kHop + 1;  // :449-455
-  const uint64_t last_end = (nf - 1) * kHop + kFrame;              // slice end, :474
-  for (uint64_t c = 0; c < ch; ++c)
-    if (padded(per_channel(c)) < last_end) return p;  // reference panics: slice out of range
-  p.n_frames = nf;
-  p.padded_len = p0;
-  p.per_channel = l0;
-  p.encoder_delay = kHop / 2;                                  // :547
-  p.padding = static_cast<uint32_t>(p0 - l0 - kHop / 2);       // :546
-  return p;
-}
-
-bool plan_crop(uint64_t n_samples, uint16_t channels, const glc_crop &crop, glc_crop_plan *out) {
-  const glc_plan plan = plan_encode(n_samples, channels);
-  if (plan.n_frames == 0) return false;
-  const uint64_t ch = channels, per_hop = static_cast<uint64_t>(kHop) * ch;
-  const Trim trim = gapless_trim(plan.n_frames, channels, plan.encoder_delay, n_samples);
-  const uint64_t len = trim.n / ch;  // the decoded clip, per channel
-  if (crop.length == 0 || crop.length > len || crop.start > len - crop.length) return false;
-  // un-trimmed positions [lo, hi): the delay counts INTERLEAVED samples (Q3)
-  const uint64_t lo = trim.start + crop.start * ch, hi = lo + crop.length * ch;
-  const uint64_t h_lo = lo / per_hop, h_hi = (hi - 1) / per_hop;  // hops of the first and of the last kept sample
-  // hop h = second half of frame h - 1 + first half of frame h: the halo frame in front, none for the bare tail hop
-  const uint64_t f_lo = (h_lo > 1 ? h_lo : 1) - 1, f_hi = h_hi < plan.n_frames - 1 ? h_hi : plan.n_frames - 1;
-  *out = glc_crop_plan{f_lo, f_hi - f_lo + 1, h_lo, h_hi - h_lo + 1};
-  return true;
-}
-
 }  // namespace glc

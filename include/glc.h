@@ -590,7 +590,7 @@ int glc_decode_device_compact(glc_ctx *ctx, const void *d_blob, uint64_t blob_by
 int glc_decode_batch_device_compact(glc_ctx *ctx, const void *const *d_blobs, const uint64_t *blob_bytes,
                                     const uint64_t *n_samples, float *d_out, const glc_clip_layout *out);
 
-/* What R2 found in the last of the two calls above (or of glc_decode_crops_device_compact below): per clip the flag word, the number of rejected rows and
+/* What R2 found in the last of the two calls above (or of glc_decode_crops_device_compact / glc_decode_crops_device_store below): per clip the flag word, the number of rejected rows and
  * the first of them (row = frame * channels + channel; 0 when none was rejected).  A bad header rejects every
  * row.  The two SUM flags are reported only: they reject nothing.  Synchronises the context's stream.
  * GLC_EINVAL when no such call has completed on this context or n_clips is not that call's. */
@@ -696,6 +696,56 @@ uint64_t glc_compact_store_bound(const glc_clip_layout *in);
 int glc_encode_batch_device_compact(glc_ctx *ctx, const float *d_pcm, const glc_clip_layout *in,
                                     void *d_arena, uint64_t arena_bytes,
                                     uint64_t *d_cursor, glc_store_entry *d_entries);
+
+/* ---- drawing crops from the store by device-side index and start ---------------------------- */
+
+/* Two more status flags, set only by glc_decode_crops_device_store, always together with GLC_COMPACT_BAD_HEADER. */
+#define GLC_COMPACT_NO_BLOB   64u   /* the entry holds no usable blob: stored == 0, offset not a multiple of 64,
+                                       or [offset, offset + bytes) not inside the arena */
+#define GLC_COMPACT_BAD_CROP 128u   /* the selection is unusable: clip index outside [0, n_entries), a stored length
+                                       the encoder refuses or above max_length, start < 0, start + length beyond the clip */
+
+/* Host only: the slots a crop of `length` samples per channel needs wherever it starts - the most hops
+ * (glc_plan_crop's n_hops) and frames (n_frames) any start gives in any clip:
+ *   max_hops = floor((1024 ch - ch + 512 % ch + length ch - 1) / (1024 ch)) + 1,  max_frames = max_hops + 1.
+ * A crop begins at the un-trimmed interleaved position 512 + start * ch, which is 512 modulo ch: 1024 ch - ch + 512 % ch
+ * is the latest place in a hop it can have.  Both bounds are reached by some start of every clip long enough.
+ * GLC_EINVAL: a null pointer, channels == 0, length == 0, a length * channels that wraps. */
+int glc_store_crop_slots(uint64_t length, uint16_t channels, uint64_t *max_hops, uint64_t *max_frames);
+
+/* Crops of ONE length drawn from a store as its write side left it, selected by DEVICE data: crop i of out->n_clips
+ * is samples [d_starts[i], d_starts[i] + length) per channel of stored clip d_clips[i].  d_arena / arena_bytes: the
+ * arena; d_entries[n_entries]: its index - what glc_encode_batch_device_compact wrote, concatenated over any number
+ * of calls, or entries a host built for blobs it uploaded itself; d_lengths[e]: samples per channel of stored clip e
+ * (the blob does not hold it); max_length: a host upper bound of those lengths.  All four index arrays are int64_t
+ * / 32-byte entries on the device, 8-byte aligned, and none is read by the host.
+ * For every crop whose entry and selection are usable, clip i of `out` is bit for bit what
+ * glc_decode_crops_device_compact writes for d_blobs[i] = d_arena + entry.offset, blob_bytes[i] = entry.bytes,
+ * n_samples[i] = d_lengths[clip] * channels, crops[i] = {start, length} - damaged blobs included - and
+ * glc_decode_compact_last_status gives the same words.  A crop whose entry (GLC_COMPACT_NO_BLOB) or selection
+ * (GLC_COMPACT_BAD_CROP; it wins when both apply, the entry of an index out of range is not read) is unusable is
+ * +0.0 over its length * channels samples, with status flags = that bit | GLC_COMPACT_BAD_HEADER, n_bad_rows = 0,
+ * first_bad_row = 0; its neighbours are not affected.  No element of d_out outside the crops is written.  No load
+ * leaves the arena, d_entries[0 .. n_entries), d_lengths[0 .. n_entries) or the two selection arrays, whatever they
+ * hold.
+ * Every crop owns a fixed block of glc_store_crop_slots(length) table rows, block slots and hop descriptors, so the
+ * rounds - floor(4097 / (max_frames + 1)) crops each - and every launch depend on n_clips, length and channels alone.
+ * One planner kernel per call resolves the selection on the device; then one windowed R2, inverse-transform and
+ * overlap-add chain per round.  Queued on glc_ctx_stream(ctx), NOT synchronised.  The call makes NO host-to-device
+ * copy, does not wait for the pinned table image of earlier batch calls, and its host work does not depend on
+ * n_clips apart from the launches of ceil(n_clips / crops per round) chains; it blocks only where a workspace has
+ * to grow.  Afterwards no stream is resident and an open decode session is closed.
+ * GLC_EINVAL, before anything is queued: a null pointer, channels == 0, d_arena not 64-byte aligned, an index array
+ * not 8-byte aligned, length == 0, max_length < length, a max_length the encoder refuses or whose frames * channels
+ * exceed 32 bits, out->lengths given and not all `length` (out->length != length without them), strides too small,
+ * n_entries == 0, max_frames + 1 > 4097 (such windows stay with glc_decode_crops_device_compact), an output extent
+ * that overlaps the arena or an index array.  n_clips == 0 is GLC_OK. */
+int glc_decode_crops_device_store(glc_ctx *ctx,
+                                  const void *d_arena, uint64_t arena_bytes,
+                                  const glc_store_entry *d_entries, const int64_t *d_lengths, uint64_t n_entries,
+                                  uint64_t max_length,
+                                  const int64_t *d_clips, const int64_t *d_starts, uint64_t length,
+                                  float *d_out, const glc_clip_layout *out);
 
 /* ---- tables (for inspection / parity tests) ---------------------------------------------- */
 

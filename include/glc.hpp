@@ -197,6 +197,16 @@ inline glc_crop_plan plan_crop(uint64_t n_samples, uint16_t channels, const glc_
   return p;
 }
 
+// The hops and frames a crop of `length` samples per channel needs wherever it starts (glc_store_crop_slots).
+struct CropSlots {
+  uint64_t max_hops, max_frames;
+};
+inline CropSlots store_crop_slots(uint64_t length, uint16_t channels) {
+  CropSlots s{};
+  detail::check(glc_store_crop_slots(length, channels, &s.max_hops, &s.max_frames));
+  return s;
+}
+
 // Arena bytes that hold the blobs of every clip of a layout whatever their content (glc_compact_store_bound).
 inline uint64_t compact_store_bound(const glc_clip_layout &in) { return glc_compact_store_bound(&in); }
 
@@ -437,6 +447,15 @@ class Decoder {
     if (d_blobs.size() != out.n_clips || blob_bytes.size() != out.n_clips || n_samples.size() != out.n_clips || crops.size() != out.n_clips)
       throw Error(GLC_EINVAL, "decode_crops_device_compact: one blob, size, length and crop per clip of the layout");
     detail::check(glc_decode_crops_device_compact(ctx_, d_blobs.data(), blob_bytes.data(), n_samples.data(), crops.data(), d_out, &out), ctx_);
+  }
+  // ... crops of one length drawn from the store as its write side left it, selected by device arrays: crop i is
+  // samples [d_starts[i], d_starts[i] + length) of stored clip d_clips[i]; nothing is uploaded (glc.h
+  // glc_decode_crops_device_store)
+  void decode_crops_device_store(const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries, const int64_t *d_lengths,
+                                 uint64_t n_entries, uint64_t max_length, const int64_t *d_clips, const int64_t *d_starts,
+                                 uint64_t length, float *d_out, const glc_clip_layout &out) {
+    detail::check(glc_decode_crops_device_store(ctx_, d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips,
+                                                d_starts, length, d_out, &out), ctx_);
   }
   // what the device check found in the blobs (or windows) of the last of these calls (synchronises)
   std::vector<glc_compact_status> last_compact_status(uint64_t n_clips = 1) {

@@ -122,6 +122,18 @@ int glc_debug_rows_from_compact_window(glc_ctx *ctx, const void *d_blob, uint64_
                                        uint64_t first_frame, uint64_t frames, uint64_t *row_begin, uint32_t *row_cnt,
                                        float *row_scale, int64_t *row_raw, uint64_t *row_raw_len, glc_compact_status *status);
 
+/* The draw planner (k_store_plan_crops) alone, exactly as glc_decode_crops_device_store launches it - the checks and
+ * the geometry are the call's own code - with what it wrote copied back: dir, out->n_clips records of 32 bytes {u64
+ * address, u64 capacity, u32 first_row, u32 rows, u32 win[2]}; desc, out->n_clips * max_hops records of 40 bytes {i32
+ * prev, i32 cur, u32 first, u32 cnt, u64 dst, u64 cstride, u64 j0}; verdict, out->n_clips words (0, GLC_COMPACT_NO_BLOB
+ * or GLC_COMPACT_BAD_CROP).  The planner never dereferences the arena and nothing is written to d_out, so d_arena may
+ * be any 64-byte aligned number and arena_bytes 2^40: offsets beyond 4 GiB and lengths near the 32-bit row limit are
+ * reached without the memory.  Synchronises.  tests/test_store_draw.py holds the planner to a model through this. */
+int glc_debug_store_plan_device(glc_ctx *ctx, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
+                                const int64_t *d_lengths, uint64_t n_entries, uint64_t max_length, const int64_t *d_clips,
+                                const int64_t *d_starts, uint64_t length, const float *d_out, const glc_clip_layout *out,
+                                void *dir, void *desc, uint32_t *verdict);
+
 /* The shader clock the device HOLDS under load (measurement only; bench.py's roofline.clock_ghz_held).
  * `begin` starts one sleeping wave on a stream of its own that runs for `window_us` microseconds beside
  * whatever the caller queues meanwhile and reads the shader-cycle counter against the constant 100 MHz
