@@ -219,7 +219,12 @@ int glc_imdct_device(glc_ctx *ctx, const glc_frames *in, uint64_t frame_begin, u
 /* Decoder::decode_streaming src/codec.rs:595-741: un-trimmed output delivered in chunks of at
  * least FRAMES_PER_CHUNK*1024*channels samples (AudioChunk, :81-85).  `begin` decodes on the
  * device; `next` copies the next chunk (returns its size through n_out, sets *is_last on the
- * final chunk, which carries the overlap tail :722-732). */
+ * final chunk, which carries the overlap tail :722-732).
+ * An open session survives every encode entry point, glc_ctx_set_stream and the debug switches.  Every decode-side
+ * call closes it - glc_decode*, glc_decode_batch*, the round-trip, compact, crop and store families - and so does a
+ * glc_decode / glc_decode_device / glc_decode_range_device / glc_imdct_device that is refused for its capacity or range
+ * (not one refused for a null argument); `next` is then GLC_EINVAL.  A `next` refused for the other sample format
+ * leaves the session open. */
 int glc_decode_stream_begin(glc_ctx *ctx, const glc_frames *in);
 int glc_decode_stream_next(glc_ctx *ctx, float *chunk, uint64_t cap, uint64_t *n_out,
                            int *is_last);
@@ -501,7 +506,9 @@ int glc_roundtrip(glc_ctx *ctx, const void *pcm, glc_pcm_format fmt, uint32_t bi
 /* What the last glc_roundtrip_device / glc_roundtrip on this context encoded, from a device reduction
  * over the record headers: the counts glc_frames_info gives for glc_encode of the same samples, and
  * serialized_bytes == glc_serialized_size of it - the bitrate without the stream.  Synchronises the
- * context's stream.  GLC_EINVAL when no round trip has completed on this context. */
+ * context's stream.  GLC_EINVAL when no round trip has completed on this context.  The record is that of the last
+ * COMPLETED call of the two: calls of every other family, glc_decode_device_records (it encodes nothing) and calls
+ * refused by an argument check leave it as it is ("What a call leaves on its context"). */
 typedef struct glc_roundtrip_info {
   uint64_t n_frames;
   uint64_t n_raw_frames;
@@ -549,7 +556,8 @@ int glc_roundtrip_batch_device(glc_ctx *ctx, const float *d_pcm, const glc_clip_
 /* glc_roundtrip_last_info for every clip of the last glc_roundtrip_batch_device on this context:
  * infos[i] is what glc_roundtrip_last_info gives after glc_roundtrip_device of clip i alone, from per-clip
  * device counters.  Synchronises the context's stream.  GLC_EINVAL when no batch round trip has completed
- * on this context or n_clips is not that call's. */
+ * on this context or n_clips is not that call's.  Calls of other families, refused calls and a call with n_clips == 0
+ * leave the record of the last completed batch call as it is. */
 int glc_roundtrip_batch_last_info(glc_ctx *ctx, glc_roundtrip_info *infos, uint64_t n_clips);
 
 /* ---- decode of compact blobs that are in device memory: a compressed clip store in HBM ------ */
@@ -593,7 +601,9 @@ int glc_decode_batch_device_compact(glc_ctx *ctx, const void *const *d_blobs, co
 /* What R2 found in the last of the two calls above (or of glc_decode_crops_device_compact / glc_decode_crops_device_store below): per clip the flag word, the number of rejected rows and
  * the first of them (row = frame * channels + channel; 0 when none was rejected).  A bad header rejects every
  * row.  The two SUM flags are reported only: they reject nothing.  Synchronises the context's stream.
- * GLC_EINVAL when no such call has completed on this context or n_clips is not that call's. */
+ * GLC_EINVAL when no such call has completed on this context or n_clips is not that call's.  The words are those of the
+ * last completed call ALONE (every call starts its counters from zero); calls of other families, refused calls and
+ * calls with n_clips == 0 leave them as they are. */
 #define GLC_COMPACT_BAD_HEADER    1u  /* the header check failed: the clip is silence */
 #define GLC_COMPACT_ROW_BOUNDS    2u  /* a row longer than 1024 or reaching behind n_pairs */
 #define GLC_COMPACT_NOT_CANONICAL 4u  /* a list that is not strictly ascending below 1024 */
