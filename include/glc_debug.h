@@ -3,7 +3,8 @@
  * include/glc.h): these entry points exist so that soak tools and tests can run one stream through
  * two independent implementations of the same arithmetic and demand identical bits, or drive one kernel
  * stage on inputs built for the purpose (tests/test_quantizer_edges.py, tests/test_decode_edges.py,
- * tests/test_compact_edges.py).
+ * tests/test_compact_edges.py).  tests/test_channel_axis.py drives the store pack, the windowed R2 and the draw
+ * planner through their hooks at 4, 5, 7, 9, 16, 17, 257 and 513 channels.
  */
 #ifndef GLC_DEBUG_H
 #define GLC_DEBUG_H
@@ -97,7 +98,8 @@ int glc_debug_compact_batch_device(glc_ctx *ctx, const void *d_records, const ui
  * glc_debug_compact_batch_device: clip i of clip_frames[i] >= 1 frames, one junk record behind each clip.  d_arena,
  * arena_bytes, d_cursor and d_entries as in glc_encode_batch_device_compact (include/glc.h).  Queued on the context's
  * stream behind the table upload; not synchronised.  tests/test_compact_store.py drives the pack through this with
- * junk records that hold dense rows and raw flags, nnz fields that disagree with their rows and 1100 clips in a round. */
+ * junk records that hold dense rows and raw flags, nnz fields that disagree with their rows and 1100 clips in a round;
+ * tests/test_channel_axis.py with rows per clip that are no multiple of 4, up to 513 channels. */
 int glc_debug_compact_store_device(glc_ctx *ctx, const void *d_records, const uint64_t *clip_frames, uint64_t n_clips,
                                    uint16_t channels, void *d_arena, uint64_t arena_bytes, uint64_t *d_cursor,
                                    glc_store_entry *d_entries);
@@ -117,7 +119,8 @@ int glc_debug_rows_from_compact(glc_ctx *ctx, const void *d_blob, uint64_t blob_
  * The tables of the window's frames * channels rows come back as above - row_begin and row_raw from d_blob, in the
  * blob's own terms, so they are the matching slices of glc_debug_rows_from_compact's - with the status words.
  * Synchronises.  tests/test_compact_crops.py holds windows at the scan's edges, and one behind row 1024 * 1024 of a
- * blob of that many rows, to the model through this. */
+ * blob of that many rows, to the model through this; tests/test_channel_axis.py the windows of the oracle's streams of
+ * 4 to 513 channels. */
 int glc_debug_rows_from_compact_window(glc_ctx *ctx, const void *d_blob, uint64_t blob_bytes, uint64_t n_frames, uint16_t channels,
                                        uint64_t first_frame, uint64_t frames, uint64_t *row_begin, uint32_t *row_cnt,
                                        float *row_scale, int64_t *row_raw, uint64_t *row_raw_len, glc_compact_status *status);
@@ -128,7 +131,9 @@ int glc_debug_rows_from_compact_window(glc_ctx *ctx, const void *d_blob, uint64_
  * prev, i32 cur, u32 first, u32 cnt, u64 dst, u64 cstride, u64 j0}; verdict, out->n_clips words (0, GLC_COMPACT_NO_BLOB
  * or GLC_COMPACT_BAD_CROP).  The planner never dereferences the arena and nothing is written to d_out, so d_arena may
  * be any 64-byte aligned number and arena_bytes 2^40: offsets beyond 4 GiB and lengths near the 32-bit row limit are
- * reached without the memory.  Synchronises.  tests/test_store_draw.py holds the planner to a model through this. */
+ * reached without the memory.  Synchronises.  tests/test_store_draw.py holds the planner to a model through this, and
+ * tests/test_channel_axis.py does at the channel counts whose sample frames begin 1, 8, 255 and 512 positions into a
+ * hop's grid (512 % channels). */
 int glc_debug_store_plan_device(glc_ctx *ctx, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
                                 const int64_t *d_lengths, uint64_t n_entries, uint64_t max_length, const int64_t *d_clips,
                                 const int64_t *d_starts, uint64_t length, const float *d_out, const glc_clip_layout *out,

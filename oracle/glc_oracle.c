@@ -65,15 +65,21 @@ void glo_mdct_block(const float *table, float norm, const float *block, float *o
 }
 
 void glo_imdct_block(const float *table, float norm, const float *coeffs, float *out) {
-  /* src/codec.rs:380-389 */
-  for (uint32_t i = 0; i < N_FRAME; ++i) {
-    float s = 0.0f;
-    for (uint32_t k = 0; k < N_HOP; ++k) {
-      float p = coeffs[k] * table[(size_t)k * N_FRAME + i];
-      s = s + p;
+  /* src/codec.rs:380-389: out[i] = (sum over k, in ascending k, of coeffs[k] * table[k][i]) * norm, multiply then
+     add.  The loops are interchanged - the table is walked row by row, the 2048 running sums live in `out` - which
+     leaves every sum its own terms in their own order: the same bits, a tenth of the time (the column walk of
+     the 8 MiB table missed the cache on every term; a clip of several hundred channels took seconds). */
+  float acc[N_FRAME]; /* local: nothing aliases it, so the inner loop vectorises (lane by lane the same arithmetic) */
+  for (uint32_t i = 0; i < N_FRAME; ++i) acc[i] = 0.0f;
+  for (uint32_t k = 0; k < N_HOP; ++k) {
+    const float *tb = table + (size_t)k * N_FRAME;
+    const float c = coeffs[k];
+    for (uint32_t i = 0; i < N_FRAME; ++i) {
+      float p = c * tb[i];
+      acc[i] = acc[i] + p;
     }
-    out[i] = s * norm;
   }
+  for (uint32_t i = 0; i < N_FRAME; ++i) out[i] = acc[i] * norm;
 }
 
 /* ---------------------------------------------------------------- perceptual model */

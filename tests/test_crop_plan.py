@@ -6,12 +6,15 @@
   f and f + 1, its 2048-sample support is the positions [1024 ch f, 1024 ch (f + 2)); the stream has n_frames
   frames and n_frames + 1 hops.
 
-The model marks every position of the crop and asks each hop and each frame's support whether it meets one.  Host
-only: no GPU is needed."""
+The model marks every position of the crop and asks each hop and each frame's support whether it meets one (a stream
+of more than 2^20 positions is not marked: each hop is asked whether it meets the crop's interval - the same question,
+hop by hop, and still no division).  Host only: no GPU is needed."""
 import ctypes as C
 
 import numpy as np
 import pytest
+
+from channel_axis_cases import CHANNELS
 
 HOP = 1024
 DELAY = 512
@@ -25,13 +28,27 @@ def glc_amd():
     return g
 
 
-def model(nf, ch, start, length):
+MARKED = 1 << 20                 # positions up to which a stream is marked one by one
+
+
+def hops_marked(nf, per_hop, lo, hi):
+    kept = np.zeros((nf + 2) * per_hop, bool)
+    kept[lo:hi] = True
+    assert not kept[(nf + 1) * per_hop:].any()                 # the crop lies inside the n_frames + 1 hops
+    return kept.reshape(nf + 2, per_hop).any(axis=1)
+
+
+def hops_by_interval(nf, per_hop, lo, hi):
+    assert hi <= (nf + 1) * per_hop
+    return np.array([max(lo, h * per_hop) < min(hi, (h + 1) * per_hop) for h in range(nf + 2)])
+
+
+def model(nf, ch, start, length, by_hop_of=None):
     """(first_frame, n_frames, first_hop, n_hops) by marking positions."""
     per_hop = HOP * ch
-    kept = np.zeros((nf + 2) * per_hop, bool)
-    kept[DELAY + start * ch:DELAY + (start + length) * ch] = True
-    assert not kept[(nf + 1) * per_hop:].any()                 # the crop lies inside the n_frames + 1 hops
-    by_hop = kept.reshape(nf + 2, per_hop).any(axis=1)
+    if by_hop_of is None:
+        by_hop_of = hops_marked if (nf + 2) * per_hop <= MARKED else hops_by_interval
+    by_hop = by_hop_of(nf, per_hop, DELAY + start * ch, DELAY + (start + length) * ch)
     hops = np.flatnonzero(by_hop)
     assert np.array_equal(hops, np.arange(hops[0], hops[-1] + 1))
     frames = [f for f in range(nf) if by_hop[f] or by_hop[f + 1]]   # support = hops f and f + 1
@@ -42,24 +59,42 @@ def model(nf, ch, start, length):
 LENGTHS = (513, 514, 1023, 1024, 1025, 2047, 2048, 2049, 3 * HOP - 1, 3 * HOP, 3 * HOP + 1, 5 * HOP + 300)
 
 
-def grid(n):
-    """Starts / lengths worth trying in a clip of n samples per channel: the ends, and the hop boundaries of the
-    un-trimmed stream (for every ch a boundary falls near a multiple of 512 / ch ... 1024) and their neighbours."""
+def grid(n, ch):
+    """Starts / lengths worth trying in a clip of n samples per channel: the ends, multiples of 512, and the hop
+    boundaries of the un-trimmed stream for this channel count - the sample whose frame holds position 1024 ch h, for
+    every hop h of the clip - with their neighbours."""
     pts = {0, 1, 2, n - 2, n - 1, n}
     for k in range(0, n + HOP, 512):
         for d in (-2, -1, 0, 1, 2):
             pts.add(k + d)
-    for k in (171, 341, 342, 853, 854, 1195, 1196):            # boundaries of 3 and 6 channels
+    for h in range(1, (DELAY + n * ch) // (HOP * ch) + 2):
+        k = (HOP * ch * h - DELAY) // ch
+        pts.update((k - 1, k, k + 1))
+    for k in (171, 341, 342, 853, 854, 1195, 1196):            # inside a hop for most counts: the shortest clips have no boundary
         pts.update((k - 1, k, k + 1))
     return sorted(p for p in pts if 0 <= p <= n)
 
 
-@pytest.mark.parametrize("ch", (1, 2, 3, 6))
+def test_the_interval_model_is_the_marking_model():
+    """Where both forms of the model can run they agree: the wide channel counts are held to the same thing."""
+    checked = 0
+    for ch, n in ((3, 2049), (7, 1537), (17, 3 * HOP + 1)):
+        nf = -(-(DELAY + n) // HOP) - 1
+        pts = grid(n, ch)
+        for start in pts[::2]:
+            for end in pts[1::2]:
+                if end > start:
+                    assert model(nf, ch, start, end - start, hops_marked) == model(nf, ch, start, end - start, hops_by_interval)
+                    checked += 1
+    assert checked > 300
+
+
+@pytest.mark.parametrize("ch", (1, 2, 3, 6) + CHANNELS + (1023, 1024, 1025))
 @pytest.mark.parametrize("n", LENGTHS)
 def test_plan_equals_the_brute_force_model(glc_amd, ch, n):
     g = glc_amd
     nf = g.plan_encode(n * ch, ch).n_frames
-    pts = grid(n)
+    pts = grid(n, ch)
     checked = 0
     for start in pts:
         for end in pts:

@@ -13,6 +13,8 @@ import ctypes as C
 
 import pytest
 
+from channel_axis_cases import CHANNELS
+
 HOP = 1024
 EINVAL = -1
 CLIPS = (513, 1024, 1025, 1536, 2049, 3000, 4097, 5 * HOP + 300)
@@ -32,7 +34,7 @@ def model(length, ch):
     return hops, hops + 1
 
 
-@pytest.mark.parametrize("ch", (1, 2, 3, 6))
+@pytest.mark.parametrize("ch", (1, 2, 3, 6) + CHANNELS + (1023, 1024, 1025))
 @pytest.mark.parametrize("length", LENGTHS)
 def test_slots_against_every_start(glc_amd, ch, length):
     g = glc_amd
