@@ -257,6 +257,13 @@ SIGNATURES = {
     "glc_version": (C.c_char_p, []),
 }
 
+# the hooks of include/glc_debug.h that choose and count the repair of the screened encode (tests bind the others
+# themselves, beside the cases that drive them)
+DEBUG_SIGNATURES = {
+    "glc_debug_set_encode_repair": (C.c_int, [_vp, C.c_int]),
+    "glc_debug_encode_repair_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+}
+
 if not os.path.exists(LIB_PATH):
     raise ImportError(
         f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -276,7 +283,7 @@ except Exception:  # pragma: no cover - torch absent: the system ROCm runtime al
     _torch = None
 
 lib = C.CDLL(LIB_PATH)
-for _name, (_res, _args) in SIGNATURES.items():
+for _name, (_res, _args) in list(SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()):
     _fn = getattr(lib, _name)  # AttributeError if the ABI is incomplete
     _fn.restype = _res
     _fn.argtypes = _args

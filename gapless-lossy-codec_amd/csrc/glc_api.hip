@@ -201,6 +201,9 @@ struct glc_ctx {
   uint32_t screen_backoff = 0;  // launches the guard still sends down today's path
   bool screen_held = false;     // the last count read was a bad one: one probe at a time
   bool screen_judged_any = false;  // a count has been read since the context was created (or the mode set)
+  uint32_t screen_last_failed = 0;  // ... and the failed rows of the last one read: picks the repair's transform
+  int repair_kind = 0;             // include/glc_debug.h glc_debug_set_encode_repair
+  uint64_t repair_launches[2] = {0, 0};  // screened launches that took k_mdct_fwd_small_cols / k_mdct_fwd_small_rows
   uint64_t rows_screened = 0;
   hipStream_t probe_stream = nullptr;  // include/glc_debug.h clock probe
   HostBuf probe_out;
@@ -536,10 +539,11 @@ static bool screen_may(const glc_ctx *ctx, uint32_t M, uint32_t ch) {
 // stores in no order, and this reads them without synchronising - it may see a launch's seq beside the counts
 // of the one before, or judge a launch late.  Either only moves the decision by a launch; the records are the
 // same whichever path a launch takes.
+// The same count picks the repair's transform (glc_kernels.h launch_encode_screened), in the forced mode 2 as well:
+// screen_latency_repair below.
 constexpr uint32_t kScreenGuardDen = 8, kScreenGuardBackoff = 32;
 static bool screen_takes(glc_ctx *ctx, uint32_t M, uint32_t ch) {
   if (!screen_may(ctx, M, ch)) return false;
-  if (ctx->screen_mode == 2) return true;
   bool pending = false;  // a screened launch whose count has not come back
   for (int s = 0; s < 2; ++s) {
     const volatile uint32_t *hs = static_cast<const volatile uint32_t *>(ctx->screen_stat.p) + 8 * s;
@@ -550,14 +554,29 @@ static bool screen_takes(glc_ctx *ctx, uint32_t M, uint32_t ch) {
       if (bad) ctx->screen_backoff = kScreenGuardBackoff;
       ctx->screen_held = bad;
       ctx->screen_judged_any = true;
+      ctx->screen_last_failed = failed;
     }
     pending = pending || seq != ctx->screen_seq[s];
   }
+  if (ctx->screen_mode == 2) return true;
   if (ctx->screen_backoff) {
     --ctx->screen_backoff;
     return false;
   }
   return !((ctx->screen_held || !ctx->screen_judged_any) && pending);
+}
+
+// Which transform repairs a screened launch: the latency kernel when the last count the device left (read by
+// screen_takes just before) is small, today's when it is large - and when no count has been read yet, so that a
+// fresh context on noise pays what it paid.  A heuristic like the guard: the records are the same either way.
+// kScreenRepairLatencyRows is the measured crossover (profiles/encode_repair_bench.txt section 5, 8192-row launches):
+// with the failed frames spread over the launch the latency kernel wins at every count measured, 2 .. 1024 rows; with
+// them in one run - the tile kernel's best case, a tile of 32 rows is all failed rows - it still wins at 132 failed
+// rows (by 5.8 us) and loses at 516 (by 119 us).  128 is the largest count of the sweep at which it wins either way.
+constexpr uint32_t kScreenRepairLatencyRows = 128;
+static bool screen_latency_repair(const glc_ctx *ctx) {
+  if (ctx->repair_kind) return ctx->repair_kind == 2;
+  return ctx->screen_judged_any && ctx->screen_last_failed <= kScreenRepairLatencyRows;
 }
 
 // The screened path's workspace of a coefficient workspace (slot 0 with `coef`, 1 with `coef_b`), reserved where
@@ -624,9 +643,11 @@ static int encode_range_on(glc_ctx *ctx, hipStream_t stream, DevBuf &coef_ws, co
       if (ctx->screen_ws[slot].cap < glc::encode_screen_bytes(M, ctx->screen_shape))
         return fail(ctx, GLC_EINVAL, "glc_encode_range_device: the screen's workspace was not reserved for this launch");
       bool decided = false;
+      const bool latency = screen_latency_repair(ctx);
       GLC_HIP(ctx, glc::launch_encode_screened(ctx->dev, ctx->screen_shape, view, f, M, coef, ctx->screen_ws[slot].p,
                                                static_cast<uint32_t *>(ctx->screen_stat.p) + 8 * slot, ++ctx->screen_seq[slot],
-                                               r, st, &decided));
+                                               r, st, &decided, latency));
+      ++ctx->repair_launches[latency ? 1 : 0];
       if (!decided) GLC_HIP(ctx, glc::launch_decide_raw(ctx->dev, view, f, static_cast<uint32_t>(nf), r, st));
       ctx->rows_screened += M;
       continue;
@@ -3587,6 +3608,19 @@ int glc_debug_set_encode_screen(glc_ctx *ctx, int mode) {
   ctx->screen_backoff = 0;
   ctx->screen_held = false;
   ctx->screen_judged_any = false;
+  return GLC_OK;
+}
+
+int glc_debug_set_encode_repair(glc_ctx *ctx, int kind) {
+  if (!ctx || kind < 0 || kind > 2) return fail(ctx, GLC_EINVAL, "glc_debug_set_encode_repair: kind must be 0..2");
+  ctx->repair_kind = kind;
+  return GLC_OK;
+}
+
+int glc_debug_encode_repair_stats(glc_ctx *ctx, uint64_t *launches_tiles, uint64_t *launches_latency) {
+  if (!ctx || !launches_tiles || !launches_latency) return fail(ctx, GLC_EINVAL, "glc_debug_encode_repair_stats: null argument");
+  *launches_tiles = ctx->repair_launches[0];
+  *launches_latency = ctx->repair_launches[1];
   return GLC_OK;
 }
 

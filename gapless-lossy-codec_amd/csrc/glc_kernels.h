@@ -43,6 +43,15 @@ hipError_t launch_quantize(const DeviceTables &t, const float *coef, uint32_t M,
 // section 2): the mixed-role transform (exact below C0, a fused-multiply-add bound above), the quantiser on the
 // rows that pass, then the repair - exact columns C0.. and today's quantiser for the rows that failed.  Same
 // record bytes as launch_mdct_forward + launch_quantize for every input; *decided as launch_quantize.
+// The repair's transform is one of two kernels, chosen by the caller per launch (`latency_repair`); both write the
+// same coefficients for every input, so the records never depend on the choice:
+//   false  k_mdct_fwd_small_cols: the 2 x 2 short-clip kernel over the columns C0.., one workgroup per (tile of 32
+//          rows, 32 columns) that leaves unless the tile holds a failed row - a throughput kernel: many failed rows
+//          share its table tiles, and a launch costs its LDS-staged chain (55 us) however few rows failed
+//   true   k_mdct_fwd_small_rows: one wave per (two failed rows, 64 columns), found from the quantiser's per-wave fail
+//          counts on a fixed grid; the rows in LDS, the table streamed 112 i-steps ahead - a latency kernel: a
+//          handful of failed rows cost one wave's chain of 2048 dependent adds, a long list costs a chain per
+//          kRowsGrid items
 struct ScreenShape {
   uint32_t l0, c0, ne, n_oct;  // start of the last band, l0 rounded up to 64, c0 / 64, octets of columns >= c0
 };
@@ -55,7 +64,7 @@ uint64_t encode_screen_bytes(uint32_t M, const ScreenShape &sh);
 // device-visible host words {failed rows, rows, seq, -, u64 failed rows so far, ...} the last launch writes.
 hipError_t launch_encode_screened(const DeviceTables &t, const ScreenShape &sh, const PcmView &pcm, uint64_t frame_begin,
                                   uint32_t M, float *coef, void *workspace, uint32_t *host_stat, uint32_t seq,
-                                  uint8_t *records, hipStream_t s, bool *decided);
+                                  uint8_t *records, hipStream_t s, bool *decided, bool latency_repair = false);
 // K3: per-frame raw-vs-compressed decision and raw fallback plane (channel counts K2 does not decide).
 hipError_t launch_decide_raw(const DeviceTables &t, const PcmView &pcm, uint64_t frame_begin,
                              uint32_t n_frames, uint8_t *records, hipStream_t s);

@@ -2171,7 +2171,7 @@ uint64_t encode_screen_bytes(uint32_t M, const ScreenShape &sh) {
 
 hipError_t launch_encode_screened(const DeviceTables &t, const ScreenShape &sh, const PcmView &pcm, uint64_t frame_begin,
                                   uint32_t M, float *coef, void *workspace, uint32_t *host_stat, uint32_t seq,
-                                  uint8_t *records, hipStream_t s, bool *decided) {
+                                  uint8_t *records, hipStream_t s, bool *decided, bool latency_repair) {
   *decided = pcm.ch == 1 || pcm.ch == 2 || pcm.ch == 4;
   if (M == 0) return hipSuccess;
   const uint64_t stride = screen_stride(M);
@@ -2196,9 +2196,12 @@ hipError_t launch_encode_screened(const DeviceTables &t, const ScreenShape &sh, 
   else
     hipLaunchKernelGGL((k_quantize_screen<false, 1>), grid, dim3(256), 0, s, t, coef, M, pcm.ch, rec, hdr, pcm, fb, records, sa);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  // the repair: exact columns C0.. of the row tiles that hold a failed row, then those rows' records from all
-  // 1024 exact coefficients.  Both launches leave at once where nothing failed.
-  if ((e = k1::launch_small_cols<2>(t, pcm, frame_begin, M, coef, row_flag, sh.c0, s)) != hipSuccess) return e;
+  // the repair: exact columns C0.. of the failed rows - one wave per (two failed rows, 64 columns) found through the
+  // fail counts where few rows fail, the row tiles that hold a failed row where many do - then those rows' records
+  // from all 1024 exact coefficients.  Every launch leaves at once where nothing failed.
+  e = latency_repair ? k1::launch_small_rows<GLC_SMALL_ROWS_R>(t, pcm, frame_begin, M, coef, row_flag, wave_fail, sh.c0, s)
+                     : k1::launch_small_cols<2>(t, pcm, frame_begin, M, coef, row_flag, sh.c0, s);
+  if (e != hipSuccess) return e;
   if (*decided)
     hipLaunchKernelGGL((k_quantize_screen<true, 2>), grid, dim3(256), 0, s, t, coef, M, pcm.ch, rec, hdr, pcm, fb, records, sa);
   else

@@ -23,6 +23,9 @@
 //                      multiply-add, no coefficients stored) on the rest - the screen of DESIGN section 2.  With
 //                      k_mdct_fwd_small_cols, the 2 x 2 short-clip kernel over a column range and only the row tiles
 //                      that hold a flagged row: the exact columns of the rows that failed the screen.
+//   k_mdct_fwd_small_rows  the same repair built for latency, for launches in which few rows failed: one wave per
+//                      (two failed rows, 64 columns) found from the quantiser's fail counts on a fixed grid, the rows in
+//                      LDS, the table streamed by dwordx4 loads 112 i-steps ahead.
 //   k_mdct_fwd_dma     the kernel of rounds 2 / 3 for the same launches, now behind
 //                      glc_debug_set_mdct_variant(ctx, 1): 128x128 tile, 512 threads, 4x8 outputs per lane
 //                      with lanes <-> columns, both operands from LDS (table tile by LDS-DMA two stages
@@ -1572,6 +1575,297 @@ inline hipError_t launch_small(const DeviceTables &t, const PcmView &pcm, uint64
   const unsigned m_tiles = (M + 31) / 32;
   hipLaunchKernelGGL((k_mdct_fwd_small<TN>), dim3(m_tiles * (kHopI / (16 * TN))), dim3(256), 0, s, t, pcm,
                      static_cast<long long>(frame_begin), M, coef);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// k_mdct_fwd_small_rows: the repair of a launch in which FEW rows failed the screen (launch_encode_screened), built
+// for latency.  What such a launch costs is one wave's chain of 2048 dependent adds per accumulator, so everything
+// else is kept off that chain:
+//   work item   R consecutive entries of the list of failed rows x one slab of 64 columns >= col0; one wave (a
+//               workgroup of its own: the slabs of a row group run on different CUs, each pulling only its own
+//               512 KiB of the table through its L1).  A lane owns ONE column and carries R accumulators, two to a
+//               packed register: an i-step is R / 2 v_pk_mul_f32 and R / 2 v_pk_add_f32, separately rounded.
+//   rows        the group's windowed rows, fl(x w), staged once in LDS ([pair][i][2]); the wave reads them as
+//               broadcasts, 16 i-steps ahead.
+//   table       tb.cos ([k][i], the values of cos_t bit for bit): a lane streams its own row with dwordx4 loads,
+//               four i-steps each, 28 loads (112 i-steps) in flight - more than an Infinity-Cache round trip at the
+//               step length reached; no LDS tile, no transposition, no address arithmetic inside the loop.
+//   finding it  the grid is fixed.  Every wave sums the per-wave fail counts the screened quantiser left (lane l owns
+//               a contiguous run of them), leaves if the sum is 0, and otherwise finds entry j of the list where the
+//               running sum passes j: no atomics, no workspace of its own, nothing to clear.  Workgroups stride over
+//               the items, so any number of failed rows is handled; every barrier is workgroup-uniform.
+// Same products, same ascending-i adds, one accumulator per output: the bytes small_body writes.
+// ------------------------------------------------------------------------------------------
+constexpr int kRowsGrid = 1024;  // workgroups of a launch, whatever M: one wave per SIMD of the chip
+#ifndef GLC_SMALL_ROWS_R
+#define GLC_SMALL_ROWS_R 2  // failed rows of a work item: 2 or 4 (measured equal at four failed rows, profiles/encode_repair_bench.txt section 6; 2 is a stereo frame)
+#endif
+constexpr unsigned kRowsSlab = 64;  // columns of a work item: one per lane
+
+// four table loads (16 i-steps) of this lane's row, `byte_off` from tp
+__device__ __forceinline__ void rows_issue_t(f32x4 (&t)[4], const float *tp, int byte_off) {
+  asm volatile(
+      "global_load_dwordx4 %0, %4, off offset:%c5\n\t"
+      "global_load_dwordx4 %1, %4, off offset:%c6\n\t"
+      "global_load_dwordx4 %2, %4, off offset:%c7\n\t"
+      "global_load_dwordx4 %3, %4, off offset:%c8"
+      : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3])
+      : "v"(tp), "i"(byte_off), "i"(byte_off + 16), "i"(byte_off + 32), "i"(byte_off + 48)
+      : "memory");
+}
+
+// wait until at most PENDING of this wave's table loads are outstanding (they return in order): `t` has landed
+template <int PENDING>
+__device__ __forceinline__ void rows_wait_t(f32x4 (&t)[4]) {
+  asm volatile("s_waitcnt vmcnt(%c4)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]) : "i"(PENDING) : "memory");
+}
+
+template <int NP>
+struct RowsX {  // the windowed samples of 16 i-steps: per pair of rows, 8 x {a_i, b_i, a_i+1, b_i+1}
+  f32x4 v[NP][8];
+};
+
+template <int NP>
+__device__ __forceinline__ void rows_issue_x(RowsX<NP> &x, unsigned xa, int byte_off) {
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const int o = byte_off + p * kFrameI * 8;
+    asm volatile(
+        "ds_read_b128 %0, %8 offset:%c9\n\t"
+        "ds_read_b128 %1, %8 offset:%c10\n\t"
+        "ds_read_b128 %2, %8 offset:%c11\n\t"
+        "ds_read_b128 %3, %8 offset:%c12\n\t"
+        "ds_read_b128 %4, %8 offset:%c13\n\t"
+        "ds_read_b128 %5, %8 offset:%c14\n\t"
+        "ds_read_b128 %6, %8 offset:%c15\n\t"
+        "ds_read_b128 %7, %8 offset:%c16"
+        : "=&v"(x.v[p][0]), "=&v"(x.v[p][1]), "=&v"(x.v[p][2]), "=&v"(x.v[p][3]), "=&v"(x.v[p][4]), "=&v"(x.v[p][5]),
+          "=&v"(x.v[p][6]), "=&v"(x.v[p][7])
+        : "v"(xa), "i"(o), "i"(o + 16), "i"(o + 32), "i"(o + 48), "i"(o + 64), "i"(o + 80), "i"(o + 96), "i"(o + 112)
+        : "memory");
+  }
+}
+
+template <int NP>
+__device__ __forceinline__ void rows_wait_x(RowsX<NP> &x) {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+  for (int p = 0; p < NP; ++p)
+    asm volatile(""
+                 : "+v"(x.v[p][0]), "+v"(x.v[p][1]), "+v"(x.v[p][2]), "+v"(x.v[p][3]), "+v"(x.v[p][4]), "+v"(x.v[p][5]),
+                   "+v"(x.v[p][6]), "+v"(x.v[p][7])::"memory");
+}
+
+// four i-steps of one pair of rows: acc = {s_a, s_b}; xa = {a_i, b_i, a_i+1, b_i+1}, xb the next two; t = T[k][i .. i+3].
+// Each product is rounded, then added: the multiply of a step is issued ahead of the add of the step before it.
+__device__ __forceinline__ void rows_mac4(f32x2 &acc, f32x4 xa, f32x4 xb, f32x4 t) {
+  const f32x2 x0 = __builtin_shufflevector(xa, xa, 0, 1), x1 = __builtin_shufflevector(xa, xa, 2, 3);
+  const f32x2 x2 = __builtin_shufflevector(xb, xb, 0, 1), x3 = __builtin_shufflevector(xb, xb, 2, 3);
+  const f32x2 t01 = __builtin_shufflevector(t, t, 0, 1), t23 = __builtin_shufflevector(t, t, 2, 3);
+  f32x2 p0, p1, p2, p3;
+  asm volatile(
+      "v_pk_mul_f32 %1, %5, %9 op_sel_hi:[1,0]\n\t"
+      "v_pk_mul_f32 %2, %6, %9 op_sel:[0,1]\n\t"
+      "v_pk_add_f32 %0, %0, %1\n\t"
+      "v_pk_mul_f32 %3, %7, %10 op_sel_hi:[1,0]\n\t"
+      "v_pk_add_f32 %0, %0, %2\n\t"
+      "v_pk_mul_f32 %4, %8, %10 op_sel:[0,1]\n\t"
+      "v_pk_add_f32 %0, %0, %3\n\t"
+      "v_pk_add_f32 %0, %0, %4"
+      : "+v"(acc), "=&v"(p0), "=&v"(p1), "=&v"(p2), "=&v"(p3)
+      : "v"(x0), "v"(x1), "v"(x2), "v"(x3), "v"(t01), "v"(t23));
+}
+
+template <int R>
+__global__ __launch_bounds__(64) void k_mdct_fwd_small_rows(DeviceTables tb, PcmView pcm, long long frame_begin, unsigned M,
+                                                             float *__restrict__ coef, const unsigned *__restrict__ row_flag,
+                                                             const unsigned *__restrict__ wave_fail, unsigned col0) {
+  static_assert(R == 2 || R == 4, "rows of a group: whole packed pairs");
+  constexpr int NP = R / 2;
+  constexpr unsigned kNone = 0xFFFFFFFFu;
+  __shared__ __attribute__((aligned(16))) float xs[NP * kFrameI * 2];  // [pair][i][2]
+  __shared__ unsigned s_row[R], s_total;
+  const unsigned lane = threadIdx.x;
+
+  // the list of failed rows, implicitly: lane l owns the counts of quantiser waves [l per, (l + 1) per), 4 rows each
+  const unsigned n_w = (M + 15u) / 16u * 4u;  // the counts k_quantize_screen<*, 1> wrote: a multiple of 4
+  const unsigned per = ((n_w + 63u) / 64u + 3u) & ~3u;
+  const unsigned w0 = lane * per;
+  const uint4 *wf4 = reinterpret_cast<const uint4 *>(wave_fail);
+  // the four counts at word w of this lane's run, 0 beyond the run or the launch: an unconditional load, so that a
+  // trip's eight are in flight together (a wave that waited for each would spend a memory round trip per load)
+  auto counts = [&](unsigned w) -> uint4 {
+    const bool in = w < per && w0 + w < n_w;
+    const uint4 c = wf4[in ? (w0 + w) >> 2 : 0u];
+    return in ? c : uint4{0u, 0u, 0u, 0u};
+  };
+  unsigned cnt = 0;
+  for (unsigned w = 0; w < per; w += 32) {
+    uint4 c[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) c[k] = counts(w + 4 * k);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) cnt += c[k].x + c[k].y + c[k].z + c[k].w;
+  }
+  unsigned incl = cnt;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const unsigned v = __shfl_up(incl, off);
+    if (lane >= static_cast<unsigned>(off)) incl += v;
+  }
+  if (lane == 63) s_total = incl;
+  __syncthreads();
+  const unsigned n_fail = __builtin_amdgcn_readfirstlane(s_total);
+  if (n_fail == 0) return;  // nothing failed: the whole launch leaves here
+  const unsigned base = incl - cnt;
+
+  const unsigned n_slabs = (static_cast<unsigned>(kHopI) - col0) / kRowsSlab;
+  const unsigned n_items = (n_fail + R - 1) / R * n_slabs;
+  long long e_end = static_cast<long long>(pcm.t_count) * pcm.ch;  // shard end (elements from pcm.p)
+  const long long n_rel = static_cast<long long>(pcm.n_samples) - static_cast<long long>(pcm.t0) * pcm.ch;
+  if (e_end > n_rel) e_end = n_rel;  // stream end
+  const unsigned xs0 = static_cast<unsigned>(reinterpret_cast<uintptr_t>(&xs[0]));
+
+#pragma unroll 1
+  for (unsigned item = blockIdx.x; item < n_items; item += gridDim.x) {
+    const unsigned g = item / n_slabs, slab = item - g * n_slabs;
+    // entries g R .. g R + R - 1 of the list: the lane whose run of counts holds entry j walks it to the wave, then
+    // that wave's four flags to the row
+    if (lane < R) s_row[lane] = kNone;
+    __syncthreads();
+    if (cnt != 0 && g * R + R > base && g * R < base + cnt) {
+      unsigned run = base, word[R], rank[R];
+#pragma unroll
+      for (int q = 0; q < R; ++q) word[q] = kNone, rank[q] = 0;
+      for (unsigned w = 0; w < per; w += 32) {
+        uint4 c[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) c[k] = counts(w + 4 * k);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const unsigned ce[4] = {c[k].x, c[k].y, c[k].z, c[k].w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+#pragma unroll
+            for (int q = 0; q < R; ++q) {
+              const unsigned j = g * R + q;
+              if (j >= run && j < run + ce[e]) word[q] = w0 + w + 4 * k + e, rank[q] = j - run;
+            }
+            run += ce[e];
+          }
+        }
+      }
+      // the four flags of each wave found: one aligned load (row_flag holds a multiple of 256 entries), all in flight
+      uint4 f4[R];
+#pragma unroll
+      for (int q = 0; q < R; ++q) f4[q] = *reinterpret_cast<const uint4 *>(row_flag + (word[q] != kNone ? word[q] * 4u : 0u));
+#pragma unroll
+      for (int q = 0; q < R; ++q)
+        if (word[q] != kNone) {
+          const unsigned fl[4] = {f4[q].x, f4[q].y, f4[q].z, f4[q].w};
+          unsigned seen = 0;
+#pragma unroll
+          for (unsigned e = 0; e < 4; ++e)
+            if (word[q] * 4u + e < M && fl[e] != 0u) {
+              if (seen == rank[q]) s_row[q] = word[q] * 4u + e;
+              ++seen;
+            }
+        }
+    }
+    __syncthreads();
+    unsigned m[R];
+#pragma unroll
+    for (int q = 0; q < R; ++q) m[q] = __builtin_amdgcn_readfirstlane(s_row[q]);
+
+    // fl(x w) of the group's rows -> LDS.  Each row is read through a buffer descriptor of its own whose range check
+    // is the encoder's zero padding, as in small_body (an element before the base wraps to a huge offset, one past the
+    // shard or the stream is beyond the record count: both load 0.0) - so every load is unconditional and all of them
+    // are issued before the first LDS write: one memory round trip for the whole group, not one per sample
+    constexpr int kPer = kFrameI / 64;
+    float wv[kPer], xv[R][kPer];
+#pragma unroll
+    for (int t = 0; t < kPer; ++t) wv[t] = tb.window[lane + 64 * t];
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+      const bool live = m[q] != kNone;
+      const long long f = frame_begin + (live ? m[q] / pcm.ch : 0u);
+      const long long e_row =
+          (f * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * static_cast<long long>(pcm.ch) + (live ? m[q] % pcm.ch : 0u);
+      const long long e_base = e_row < 0 ? 0 : e_row;
+      long long e_cnt = live ? e_end - e_base : 0;  // (a row the list does not have: nothing in range, all zeros)
+      if (e_cnt < 0) e_cnt = 0;
+      if (e_cnt > (1ll << 28)) e_cnt = 1ll << 28;
+      const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(pcm.p + e_base), 0,
+                                                                           static_cast<int>(e_cnt * 4), 0x00020000);
+      const unsigned off0 = static_cast<unsigned>((e_row - e_base) * 4);  // 0, or negative: wraps, that IS the padding
+#pragma unroll
+      for (int t = 0; t < kPer; ++t)
+        xv[q][t] = __builtin_bit_cast(
+            float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, off0 + (lane + 64u * t) * (pcm.ch * 4u), 0, 0));
+    }
+#pragma unroll
+    for (int q = 0; q < R; ++q)
+#pragma unroll
+      for (int t = 0; t < kPer; ++t)
+        xs[((q >> 1) * kFrameI + static_cast<int>(lane) + 64 * t) * 2 + (q & 1)] = mul_rn(xv[q][t], wv[t]);  // block[i] = slice[i]*window[i], :480
+    __syncthreads();
+
+    // the chain: 16 rounds of 8 blocks of 16 i-steps; 7 blocks of table loads in flight, the rows a block ahead
+    const unsigned col = col0 + slab * kRowsSlab + lane;
+    const float *row_t = tb.cos + static_cast<size_t>(col) * kFrameI;
+    const float *tp = row_t;
+    unsigned xa = xs0;
+    f32x2 acc[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) acc[p] = f32x2{0.0f, 0.0f};  // `let mut s = 0.0f32`, :365
+    f32x4 T[8][4];
+    RowsX<NP> X[2];
+#pragma unroll
+    for (int b = 0; b < 7; ++b) rows_issue_t(T[b], tp, b * 64);
+    rows_issue_x<NP>(X[0], xa, 0);
+    rows_wait_x<NP>(X[0]);
+    constexpr int kRounds = kFrameI / 128;
+#pragma unroll 1
+    for (int round = 0; round < kRounds; ++round) {
+      // (the last round's look-ahead wraps to i = 0: in bounds, never used)
+      const float *tp_next = round + 1 < kRounds ? tp + 128 : row_t;
+      const unsigned xa_next = round + 1 < kRounds ? xa + 128 * 8 : xs0;
+#pragma unroll
+      for (int b = 0; b < 8; ++b) {
+        rows_wait_t<24>(T[b]);
+        if (b == 0) rows_issue_t(T[7], tp, 7 * 64);
+        else rows_issue_t(T[b - 1], tp_next, (b - 1) * 64);
+        if (b < 7) rows_issue_x<NP>(X[(b + 1) & 1], xa, (b + 1) * 128);
+        else rows_issue_x<NP>(X[0], xa_next, 0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int p = 0; p < NP; ++p) rows_mac4(acc[p], X[b & 1].v[p][2 * j], X[b & 1].v[p][2 * j + 1], T[b][j]);
+        rows_wait_x<NP>(X[(b + 1) & 1]);
+      }
+      tp = tp_next;
+      xa = xa_next;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the wrap-around look-ahead
+
+    // epilogue: out[k] = s * norm, :372
+#pragma unroll
+    for (int q = 0; q < R; ++q)
+      if (m[q] != kNone) coef[static_cast<size_t>(m[q]) * kHopI + col] = mul_rn(q & 1 ? acc[q >> 1].y : acc[q >> 1].x, tb.norm);
+  }
+}
+
+// columns [col0, 1024) (col0 a multiple of 64) of the rows flagged in row_flag[M], found through wave_fail (the fail
+// count of every quantiser wave of 4 rows, ceil(M / 16) * 4 words, 16-byte aligned): both as k_quantize_screen<*, 1>
+// leaves them
+template <int R>
+inline hipError_t launch_small_rows(const DeviceTables &t, const PcmView &pcm, uint64_t frame_begin, uint32_t M, float *coef,
+                                    const unsigned *row_flag, const unsigned *wave_fail, uint32_t col0, hipStream_t s) {
+  if (M == 0 || col0 >= static_cast<uint32_t>(kHopI)) return hipSuccess;
+  if (col0 % 64u || !row_flag || !wave_fail) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((k_mdct_fwd_small_rows<R>), dim3(kRowsGrid), dim3(64), 0, s, t, pcm, static_cast<long long>(frame_begin), M,
+                     coef, row_flag, wave_fail, col0);
   return hipGetLastError();
 }
 

@@ -58,6 +58,20 @@ int glc_debug_set_encode_screen(glc_ctx *ctx, int mode);
  * and were repaired.  Waits for the context's encode streams. */
 int glc_debug_encode_screen_stats(glc_ctx *ctx, uint64_t *rows_screened, uint64_t *rows_repaired);
 
+/* Which transform repairs the rows of a screened launch that failed the screen (csrc/glc_kernels.h
+ * launch_encode_screened):
+ *   0  automatic: k_mdct_fwd_small_rows (one wave per two failed rows and 64 columns: a handful of failed rows cost
+ *      one wave's chain) when the last failed-row count the device reported is small, k_mdct_fwd_small_cols (the
+ *      row tiles that hold a failed row) when it is large or none has been read yet
+ *   1  k_mdct_fwd_small_cols for every screened launch
+ *   2  k_mdct_fwd_small_rows for every screened launch
+ * The setting survives glc_debug_set_encode_screen.  All kinds produce the same record bytes
+ * (tests/test_encode_repair.py). */
+int glc_debug_set_encode_repair(glc_ctx *ctx, int kind);
+/* Screened launches of `ctx` so far whose repair took k_mdct_fwd_small_cols / k_mdct_fwd_small_rows.  Host counters:
+ * nothing is waited for. */
+int glc_debug_encode_repair_stats(glc_ctx *ctx, uint64_t *launches_tiles, uint64_t *launches_latency);
+
 /* K2 (+ K3 where the channel count needs it) exactly as glc_encode_range_device runs them, on caller-supplied
  * coefficients: d_coeffs holds (frame_end - frame_begin) * channels rows of 1024 floats, laid out as
  * glc_mdct_forward_device writes them; d_pcm / t0 / t_count / n_samples are read only for raw planes.
