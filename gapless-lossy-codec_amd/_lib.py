@@ -254,14 +254,16 @@ SIGNATURES = {
     "glc_store_crop_slots": (C.c_int, [C.c_uint64, C.c_uint16, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "glc_decode_crops_device_store": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint64, _vp,
                                                 C.POINTER(GlcClipLayout)]),
+    "glc_store_compact_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "glc_version": (C.c_char_p, []),
 }
 
-# the hooks of include/glc_debug.h that choose and count the repair of the screened encode (tests bind the others
-# themselves, beside the cases that drive them)
+# the hooks of include/glc_debug.h that choose and count the repair of the screened encode and set the round of an
+# in-place eviction (tests bind the others themselves, beside the cases that drive them)
 DEBUG_SIGNATURES = {
     "glc_debug_set_encode_repair": (C.c_int, [_vp, C.c_int]),
     "glc_debug_encode_repair_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "glc_debug_set_store_compact_round": (C.c_int, [_vp, C.c_uint64]),
 }
 
 if not os.path.exists(LIB_PATH):

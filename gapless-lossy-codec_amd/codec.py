@@ -436,6 +436,66 @@ class _Ctx:
             s.synchronize()
         self.set_stream(s.cuda_stream)
 
+    def compact_store_tensor(self, arena, entries, lengths, keep, out_arena=None, used_bytes=None):
+        """Evict clips from a store and close the gaps (glc_store_compact_device).  arena: the 1-D uint8 CUDA tensor;
+        entries: its (N, 4) int64 CUDA index; lengths: (N,) int64 CUDA, or None; keep: (N,) torch.bool / uint8 CUDA,
+        non-zero = keep.  out_arena: None compacts in place, else a 1-D uint8 CUDA tensor that does not overlap
+        `arena` receives the kept blobs.  used_bytes: a host bound on the bytes of `arena` in use (default: all of
+        it); fewer rounds are queued in place, and an entry that reaches behind it is unusable.
+        Returns (entries_out, lengths_out, new_index, n_out, cursor), all new CUDA tensors: (N, 4) int64 with the
+        kept entries in front and zeros behind them, (N,) int64 or None, (N,) int64 - the new number of every old
+        entry or -1 (dropped) / -2 (unusable) / -3 (out of order) -, and two one-element int64 tensors; `cursor` is
+        what Encoder.encode_compact_batch_tensor takes to append.  Nothing is read on the host and nothing is copied
+        to or from it; queued on torch's current stream.  The context's resident stream, decode session and
+        last-info records are untouched."""
+        import torch
+        if not isinstance(arena, torch.Tensor) or not arena.is_cuda or arena.dtype != torch.uint8 or arena.dim() != 1 \
+                or not arena.is_contiguous():
+            raise TypeError("arena must be a contiguous 1-D uint8 CUDA tensor")
+        if arena.device.index != self.device:
+            raise GlcError(GLC_EINVAL, f"arena is on {arena.device}, this context on device {self.device}")
+        if not isinstance(entries, torch.Tensor) or not entries.is_cuda or entries.dtype != torch.int64 or entries.dim() != 2 \
+                or entries.shape[1] != 4 or not entries.is_contiguous():
+            raise TypeError("entries must be a contiguous int64 CUDA tensor of shape (n, 4)")
+        n = entries.shape[0]
+        if lengths is not None and (not isinstance(lengths, torch.Tensor) or not lengths.is_cuda or lengths.dtype != torch.int64
+                                    or tuple(lengths.shape) != (n,) or not lengths.is_contiguous()):
+            raise TypeError("lengths must be a contiguous int64 CUDA tensor of shape (n) or None")
+        if not isinstance(keep, torch.Tensor) or not keep.is_cuda or keep.dtype not in (torch.bool, torch.uint8) \
+                or tuple(keep.shape) != (n,) or not keep.is_contiguous():
+            raise TypeError("keep must be a contiguous bool or uint8 CUDA tensor of shape (n)")
+        others = [entries, keep] + ([lengths] if lengths is not None else [])
+        if out_arena is not None:
+            if not isinstance(out_arena, torch.Tensor) or not out_arena.is_cuda or out_arena.dtype != torch.uint8 \
+                    or out_arena.dim() != 1 or not out_arena.is_contiguous():
+                raise TypeError("out_arena must be a contiguous 1-D uint8 CUDA tensor")
+            others.append(out_arena)
+        if any(t.device != arena.device for t in others):
+            raise GlcError(GLC_EINVAL, "arena, entries, lengths, keep and out_arena must be on one device")
+        src_bytes = arena.numel()
+        if used_bytes is not None:
+            used_bytes = int(used_bytes)
+            if not 0 <= used_bytes <= src_bytes:
+                raise GlcError(GLC_EINVAL, f"used_bytes must lie in [0, {src_bytes}]")
+            src_bytes = used_bytes
+        dst, dst_bytes = (arena, src_bytes) if out_arena is None else (out_arena, out_arena.numel())
+        dev = arena.device
+        entries_out = torch.empty((n, 4), dtype=torch.int64, device=dev)
+        lengths_out = torch.empty(n, dtype=torch.int64, device=dev) if lengths is not None else None
+        new_index = torch.empty(n, dtype=torch.int64, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        self._enter_torch_stream(dev)
+        try:
+            check(lib.glc_store_compact_device(
+                self._h, C.c_void_p(arena.data_ptr()), src_bytes, C.c_void_p(entries.data_ptr()),
+                C.c_void_p(lengths.data_ptr()) if lengths is not None else None, n, C.c_void_p(keep.data_ptr()),
+                C.c_void_p(dst.data_ptr()), dst_bytes, C.c_void_p(entries_out.data_ptr()),
+                C.c_void_p(lengths_out.data_ptr()) if lengths is not None else None, C.c_void_p(new_index.data_ptr()),
+                C.c_void_p(counts.data_ptr()), C.c_void_p(counts.data_ptr() + 8)), self._h)
+        finally:
+            self.set_stream(0)
+        return entries_out, lengths_out, new_index, counts[0:1], counts[1:2]
+
     def timer_begin(self) -> None:
         """Record a HIP event on the context's stream (device-side stopwatch)."""
         check(lib.glc_ctx_timer_begin(self._h), self._h)

@@ -179,6 +179,10 @@ struct glc_ctx {
   // glc_decode_device_compact / glc_decode_batch_device_compact
   DevBuf cd_status;         // one glc::CompactStatus per blob of the last call: what R2 found
   uint64_t cd_status_n = 0; // blobs of that call (0: none has completed)
+  // glc_store_compact_device: buffers of its own, so that the call leaves every other family's state alone
+  DevBuf sc_ws;             // the scan's move table (glc_kernels.h store_evict_ws_bytes)
+  DevBuf sc_stage;          // in place: two staging buffers of one round each
+  uint64_t sc_round = 0;    // include/glc_debug.h glc_debug_set_store_compact_round (0: kStoreCompactRound)
   HostBuf batch_stage;  // pinned: a round of glc_encode_batch's short clips going up, then its payload coming down / of glc_decode_batch's rows going up
   std::string err;
   // decode session (decode_prepare / round_launch): device-resident sparse rows + position
@@ -423,6 +427,8 @@ void glc_ctx_destroy(glc_ctx *ctx) {
   ctx->rtb_tab.release();
   ctx->rtb_stats.release();
   ctx->cd_status.release();
+  ctx->sc_ws.release();
+  ctx->sc_stage.release();
   ctx->rtb_stage.release();
   if (ctx->rtb_ev) (void)hipEventDestroy(ctx->rtb_ev);
   ctx->pack_blob.release();
@@ -3262,6 +3268,86 @@ int glc_debug_store_plan_device(glc_ctx *ctx, const void *d_arena, uint64_t aren
   GLC_HIP(ctx, hipMemcpy(dir, d_tab + g.o_dir, n * sizeof(glc::CompactBlob), hipMemcpyDeviceToHost));
   GLC_HIP(ctx, hipMemcpy(desc, d_tab + g.o_desc, n * g.slots.max_hops * sizeof(glc::HopDescStrided), hipMemcpyDeviceToHost));
   GLC_HIP(ctx, hipMemcpy(verdict, d_tab + g.o_verdict, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return GLC_OK;
+}
+
+// ------------------------------------------------------------------------------ eviction from the store
+
+namespace {
+// Packed bytes of an in-place round ("the round of an eviction"): two staging buffers of this size.
+constexpr uint64_t kStoreCompactRound = 64ull << 20;
+}  // namespace
+
+int glc_store_compact_device(glc_ctx *ctx, void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
+                             const int64_t *d_lengths, uint64_t n_entries, const uint8_t *d_keep, void *d_dst, uint64_t dst_bytes,
+                             glc_store_entry *d_entries_out, int64_t *d_lengths_out, int64_t *d_new_index, uint64_t *d_n_out,
+                             uint64_t *d_cursor) {
+  const std::string w("glc_store_compact_device");
+  if (!ctx) return GLC_EINVAL;
+  if (!d_arena || !d_entries || !d_keep || !d_dst || !d_entries_out || !d_new_index || !d_n_out || !d_cursor)
+    return fail(ctx, GLC_EINVAL, w + ": null argument");
+  if ((d_lengths == nullptr) != (d_lengths_out == nullptr))
+    return fail(ctx, GLC_EINVAL, w + ": d_lengths and d_lengths_out are given together or not at all");
+  if ((reinterpret_cast<uintptr_t>(d_arena) | reinterpret_cast<uintptr_t>(d_dst)) & 63u)
+    return fail(ctx, GLC_EINVAL, w + ": the arenas must be 64-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(d_entries) | reinterpret_cast<uintptr_t>(d_lengths) | reinterpret_cast<uintptr_t>(d_entries_out) |
+       reinterpret_cast<uintptr_t>(d_lengths_out) | reinterpret_cast<uintptr_t>(d_new_index) | reinterpret_cast<uintptr_t>(d_n_out) |
+       reinterpret_cast<uintptr_t>(d_cursor)) & 7u)
+    return fail(ctx, GLC_EINVAL, w + ": entries, lengths, new_index, n_out and cursor must be 8-byte aligned");
+  if (n_entries == 0) return fail(ctx, GLC_EINVAL, w + ": n_entries == 0");
+  if (n_entries > (1ull << 40)) return fail(ctx, GLC_EINVAL, w + ": too many entries");
+  const bool in_place = d_dst == d_arena;
+  if (in_place && dst_bytes != arena_bytes) return fail(ctx, GLC_EINVAL, w + ": in place, dst_bytes must be arena_bytes");
+  struct Span {
+    uintptr_t lo, hi;
+    const char *name;
+  };
+  std::vector<Span> spans;
+  auto span = [&](const void *p, uint64_t bytes, const char *name) {
+    if (p && bytes) spans.push_back(Span{reinterpret_cast<uintptr_t>(p), reinterpret_cast<uintptr_t>(p) + bytes, name});
+  };
+  span(d_arena, arena_bytes, "the arena");
+  if (!in_place) span(d_dst, dst_bytes, "the destination arena");
+  span(d_entries, n_entries * sizeof(glc_store_entry), "d_entries");
+  span(d_lengths, n_entries * 8, "d_lengths");
+  span(d_keep, n_entries, "d_keep");
+  if (d_entries_out != d_entries) span(d_entries_out, n_entries * sizeof(glc_store_entry), "d_entries_out");
+  if (d_lengths_out != d_lengths) span(d_lengths_out, n_entries * 8, "d_lengths_out");
+  span(d_new_index, n_entries * 8, "d_new_index");
+  span(d_n_out, 8, "d_n_out");
+  span(d_cursor, 8, "d_cursor");
+  for (size_t i = 0; i < spans.size(); ++i)
+    for (size_t j = i + 1; j < spans.size(); ++j)
+      if (spans[i].lo < spans[j].hi && spans[j].lo < spans[i].hi)
+        return fail(ctx, GLC_EINVAL, w + ": " + spans[i].name + " overlaps " + spans[j].name);
+  const uint64_t round = ctx->sc_round ? ctx->sc_round : kStoreCompactRound;
+  DeviceGuard guard(ctx->device);
+  // not a decode and not an encode: the resident stream, an open session, the kept plan and the last-info records stay
+  int rc = rt_reserve(ctx, ctx->sc_ws, glc::store_evict_ws_bytes(n_entries));
+  if (rc == GLC_OK && in_place && arena_bytes) rc = rt_reserve(ctx, ctx->sc_stage, 2 * std::min(round, (arena_bytes + 63) / 64 * 64));
+  if (rc != GLC_OK) return rc;
+  glc::StoreEvict a{};
+  a.arena_bytes = arena_bytes, a.dst_bytes = dst_bytes;
+  a.entries = d_entries, a.lengths = d_lengths, a.keep = d_keep, a.n_entries = n_entries;
+  a.entries_out = d_entries_out, a.lengths_out = d_lengths_out, a.new_index = d_new_index;
+  a.n_out = d_n_out, a.cursor = d_cursor, a.ws = static_cast<uint64_t *>(ctx->sc_ws.p);
+  GLC_HIP(ctx, glc::launch_store_evict_scan(a, ctx->stream));
+  if (!in_place) {
+    GLC_HIP(ctx, glc::launch_store_evict_gather(a.ws, d_arena, arena_bytes, d_dst, ctx->stream));
+    return GLC_OK;
+  }
+  if (arena_bytes == 0) return GLC_OK;
+  // the host does not know the packed total: every round the arena could need is queued, and one at or behind the total
+  // returns at once.  An arena of less than a round is one round of its own size (rounded up to 64).
+  const uint64_t rs = std::min(round, (arena_bytes + 63) / 64 * 64), rounds = (arena_bytes + rs - 1) / rs;
+  for (uint64_t r = 0; r <= rounds; ++r) GLC_HIP(ctx, glc::launch_store_evict_round(a.ws, d_arena, ctx->sc_stage.p, rs, r, ctx->stream));
+  return GLC_OK;
+}
+
+int glc_debug_set_store_compact_round(glc_ctx *ctx, uint64_t bytes) {
+  if (!ctx || (bytes & 63ull) || bytes > (1ull << 40))
+    return fail(ctx, GLC_EINVAL, "glc_debug_set_store_compact_round: the round must be a multiple of 64 (0: the default)");
+  ctx->sc_round = bytes;
   return GLC_OK;
 }
 

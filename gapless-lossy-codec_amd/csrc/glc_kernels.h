@@ -310,6 +310,49 @@ struct StoreDraw {
   uint32_t *verdict;
 };
 hipError_t launch_store_plan_crops(const StoreDraw &a, hipStream_t s);
+
+// Eviction (glc_store_compact_device; DESIGN section 3, "evicting from the store").  include/glc.h states the rules;
+// the two launchers below are all of the call.
+//   E1  k_store_evict_scan, ONE workgroup of 1024 threads over chunks of 1024 entries with a carry (k_store_place's
+//       form): usability, the exclusive prefix maximum of the candidates' ends, the kept flag, the exclusive scans of
+//       the kept sizes and counts; new_index for every entry, entries_out / lengths_out for the kept ones, the move
+//       table in the workspace, *n_out and *cursor.  A chunk is read whole before anything of it is written and a
+//       kept entry's number never exceeds its index, so entries_out may be entries (and lengths_out lengths).
+//   E2  k_store_evict_tail: the all-zero words of entries_out / lengths_out [n_out, n_entries).
+//   M   k_store_evict_gather (out of place) / k_store_evict_round (in place): tiles of kStoreMoveTile packed bytes; the
+//       kept entries a tile meets by binary search over the ascending new offsets of the move table, 16-byte loads
+//       and stores.
+// The workspace (store_evict_ws_bytes(n_entries), 8-byte aligned): u64 head[8] = {n_out, total, limit, first_moved, n_entries + 1},
+// u64 new_off[n_entries + 1] (new_off[n_out] = total), u64 src_off[n_entries].  limit: the end of the last stored
+// kept blob - the stored ones are a prefix, every size being positive -; first_moved: the new offset of the first
+// kept blob that is not where it was (total when none moves): in place nothing below it is touched.
+constexpr uint32_t kStoreMoveTile = 16384;   // packed bytes per workgroup pass: 256 threads x 4 x 16 bytes
+constexpr uint32_t kStoreMoveGrid = 2048;    // workgroups of a move launch at most (grid-stride behind them)
+constexpr int64_t kStoreDropped = -1, kStoreUnusable = -2, kStoreOutOfOrder = -3;
+struct StoreEvict {
+  uint64_t arena_bytes, dst_bytes;
+  const glc_store_entry *entries;
+  const int64_t *lengths;        // or null (then lengths_out is null too)
+  const uint8_t *keep;
+  uint64_t n_entries;
+  glc_store_entry *entries_out;
+  int64_t *lengths_out;
+  int64_t *new_index;
+  uint64_t *n_out, *cursor;
+  uint64_t *ws;
+};
+inline uint64_t store_evict_ws_bytes(uint64_t n_entries) { return (8ull + 2ull * n_entries + 1ull) * 8ull; }
+hipError_t launch_store_evict_scan(const StoreEvict &a, hipStream_t s);
+// Out of place: packed bytes [0, limit) from their sources in `arena` to `dst`, one launch whose shape depends on
+// arena_bytes alone.
+hipError_t launch_store_evict_gather(const uint64_t *ws, const void *arena, uint64_t arena_bytes, void *dst, hipStream_t s);
+// In place, launch r of ceil(arena_bytes / round) + 1: staging[(r - 1) & 1] goes back to packed bytes
+// [(r - 1) round, r round) of the arena and packed bytes [r round, (r + 1) round) are gathered into staging[r & 1]
+// (stage: two buffers of `round` bytes, the second at stage + round; round a multiple of 64).  The two halves
+// touch disjoint bytes: every source of round r lies at or behind r * round.  Bytes below first_moved and at or
+// above total are neither staged nor written.
+hipError_t launch_store_evict_round(const uint64_t *ws, void *arena, void *stage, uint64_t round, uint64_t r, hipStream_t s);
+
 // The interleaved descriptor with a 32-bit destination, 24 bytes instead of 40: what glc_decode_batch uploads per
 // kept hop (its rounds address their output in 31 bits).  Same kernel, same chunks; kept beside HopDescStrided
 // because that driver measured slower, per launch and per call, with the wide form.

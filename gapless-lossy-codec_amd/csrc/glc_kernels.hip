@@ -1950,6 +1950,178 @@ __global__ __launch_bounds__(256) void k_store_plan_crops(StoreDraw a) {
 }
 
 // ------------------------------------------------------------------------------------------
+// Eviction: glc_store_compact_device (glc_kernels.h StoreEvict has the plan, include/glc.h the rules).
+// E1 is k_store_place's shape: one workgroup, chunks of 1024 entries, three Hillis-Steele scans per chunk (the
+// maximum of the candidates' ends, the kept bytes, the kept count) with their carries in registers.  Every thread
+// loads its entry, keep byte and length at the top of a chunk and stores behind the scans' barriers, and the number
+// of a kept entry is at most its index: an output word is never written before the input word at the same place
+// has been read, which is what lets the output arrays be the input arrays.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void k_store_evict_scan(StoreEvict a) {
+  __shared__ unsigned long long s_max[1024], s_sum[1024];
+  __shared__ unsigned s_cnt[1024];
+  __shared__ unsigned long long s_limit, s_first;
+  const unsigned t = threadIdx.x;
+  if (t == 0) s_limit = 0ull, s_first = ~0ull;
+  const unsigned long long n = a.n_entries;
+  const unsigned long long *in = reinterpret_cast<const unsigned long long *>(a.entries);
+  unsigned long long *out = reinterpret_cast<unsigned long long *>(a.entries_out);
+  uint64_t *new_off = a.ws + 8, *src_off = a.ws + 8 + n + 1;
+  unsigned long long carry_max = 0, carry_sum = 0, carry_cnt = 0;
+  for (unsigned long long k0 = 0; k0 < n; k0 += 1024) {
+    const unsigned long long i = k0 + t;
+    unsigned long long offset = 0, bytes = 0, n_pairs = 0, word3 = 0;
+    long long len = 0;
+    bool keep = false;
+    if (i < n) {
+      offset = in[4 * i], bytes = in[4 * i + 1], n_pairs = in[4 * i + 2], word3 = in[4 * i + 3];
+      keep = a.keep[i] != 0;
+      if (a.lengths) len = a.lengths[i];
+    }
+    // each term is bounded before the difference is formed: nothing wraps (k_store_plan_crops' way)
+    const bool usable = i < n && (word3 >> 32) != 0 && (offset & 63ull) == 0 && (bytes & 63ull) == 0 && bytes != 0 &&
+                        offset <= a.arena_bytes && bytes <= a.arena_bytes - offset;
+    const bool cand = keep && usable;
+    s_max[t] = cand ? offset + bytes : 0ull;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+      const unsigned long long v = t >= static_cast<unsigned>(off) ? s_max[t - off] : 0ull;
+      __syncthreads();
+      if (v > s_max[t]) s_max[t] = v;
+      __syncthreads();
+    }
+    const unsigned long long before = t ? s_max[t - 1] : 0ull;
+    const unsigned long long ends_before = before > carry_max ? before : carry_max;  // E_i
+    if (s_max[1023] > carry_max) carry_max = s_max[1023];
+    const bool kept = cand && offset >= ends_before;
+    s_sum[t] = kept ? bytes : 0ull;
+    s_cnt[t] = kept ? 1u : 0u;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+      const unsigned long long v = t >= static_cast<unsigned>(off) ? s_sum[t - off] : 0ull;
+      const unsigned c = t >= static_cast<unsigned>(off) ? s_cnt[t - off] : 0u;
+      __syncthreads();
+      s_sum[t] += v;
+      s_cnt[t] += c;
+      __syncthreads();
+    }
+    const unsigned long long place = carry_sum + s_sum[t] - (kept ? bytes : 0ull);  // exclusive: the kept sources are disjoint
+    const unsigned long long k = carry_cnt + s_cnt[t] - (kept ? 1u : 0u);           // inside the arena, the sum cannot wrap
+    carry_sum += s_sum[1023];
+    carry_cnt += s_cnt[1023];
+    if (i < n) a.new_index[i] = kept ? static_cast<long long>(k) : !keep ? kStoreDropped : !usable ? kStoreUnusable : kStoreOutOfOrder;
+    if (kept) {
+      const bool stored = place <= a.dst_bytes && bytes <= a.dst_bytes - place;  // the encoder's rule (k_store_place)
+      out[4 * k] = place;
+      out[4 * k + 1] = bytes;
+      out[4 * k + 2] = n_pairs;
+      out[4 * k + 3] = (word3 & 0xFFFFFFFFull) | (stored ? 1ull << 32 : 0ull);
+      if (a.lengths_out) a.lengths_out[k] = len;
+      new_off[k] = place;
+      src_off[k] = offset;
+      if (stored) atomicMax(&s_limit, place + bytes);
+      if (offset != place) atomicMin(&s_first, place);
+    }
+    __syncthreads();  // the scan arrays are rewritten by the next chunk
+  }
+  if (t == 0) {
+    new_off[carry_cnt] = carry_sum;
+    a.ws[0] = carry_cnt;
+    a.ws[1] = carry_sum;
+    a.ws[2] = s_limit;
+    a.ws[3] = s_first < carry_sum ? s_first : carry_sum;
+    a.ws[4] = n + 1;  // words from new_off to src_off
+    *a.n_out = carry_cnt;
+    *a.cursor = carry_sum;
+  }
+}
+
+// E2: behind E1 on the stream, so behind every read of the input arrays.
+__global__ __launch_bounds__(256) void k_store_evict_tail(StoreEvict a) {
+  const unsigned long long n_out = a.ws[0];
+  unsigned long long *out = reinterpret_cast<unsigned long long *>(a.entries_out);
+  const unsigned long long step = static_cast<unsigned long long>(gridDim.x) * 256ull;
+  for (unsigned long long k = n_out + static_cast<unsigned long long>(blockIdx.x) * 256ull + threadIdx.x; k < a.n_entries; k += step) {
+    out[4 * k] = out[4 * k + 1] = out[4 * k + 2] = out[4 * k + 3] = 0ull;
+    if (a.lengths_out) a.lengths_out[k] = 0;
+  }
+}
+
+// Packed bytes [lo, hi) - multiples of 64, hi - lo <= kStoreMoveTile, hi <= new_off[n_out] - from their sources to
+// dst[p - origin].  The tile's first and last kept entry are found once (the same search in every lane: uniform),
+// each 16-byte unit then searches between the two: no step for a blob that covers the tile, 8 for 64-byte blobs.
+// A unit lies inside one blob (every offset and size is a multiple of 64), so no load leaves the blob: the arena.
+__device__ __forceinline__ void store_evict_gather_tile(const unsigned long long *__restrict__ new_off,
+                                                        const unsigned long long *__restrict__ src_off, unsigned long long n_out,
+                                                        const unsigned char *arena, unsigned char *dst, unsigned long long origin,
+                                                        unsigned long long lo, unsigned long long hi) {
+  auto last_at_or_below = [&](unsigned long long p, unsigned long long a, unsigned long long b) {  // new_off[a] <= p, a <= b
+    while (a < b) {
+      const unsigned long long mid = a + (b - a + 1) / 2;
+      if (new_off[mid] <= p) a = mid; else b = mid - 1;
+    }
+    return a;
+  };
+  const unsigned long long k_lo = last_at_or_below(lo, 0, n_out - 1), k_hi = last_at_or_below(hi - 16, k_lo, n_out - 1);
+  // four units per thread, all loads in front of all stores.  Named scalars, not arrays: an array here is promoted to
+  // LDS, and the index of that promotion reads the dispatch packet in every wave - measured: an empty round launch
+  // took 16 us with the arrays and takes 2.5 us without them
+  auto unit = [&](unsigned long long p) {
+    uint4 v{};
+    if (p < hi) {
+      const unsigned long long k = last_at_or_below(p, k_lo, k_hi);
+      v = *reinterpret_cast<const uint4 *>(arena + src_off[k] + (p - new_off[k]));
+    }
+    return v;
+  };
+  const unsigned long long p0 = lo + threadIdx.x * 16ull, p1 = p0 + 4096ull, p2 = p0 + 8192ull, p3 = p0 + 12288ull;
+  const uint4 v0 = unit(p0), v1 = unit(p1), v2 = unit(p2), v3 = unit(p3);
+  if (p0 < hi) *reinterpret_cast<uint4 *>(dst + (p0 - origin)) = v0;
+  if (p1 < hi) *reinterpret_cast<uint4 *>(dst + (p1 - origin)) = v1;
+  if (p2 < hi) *reinterpret_cast<uint4 *>(dst + (p2 - origin)) = v2;
+  if (p3 < hi) *reinterpret_cast<uint4 *>(dst + (p3 - origin)) = v3;
+}
+
+__global__ __launch_bounds__(256) void k_store_evict_gather(const unsigned long long *__restrict__ ws, const unsigned char *arena,
+                                                            unsigned char *dst) {
+  const unsigned long long n_out = ws[0], limit = ws[2];
+  const unsigned long long *new_off = ws + 8, *src_off = new_off + ws[4];
+  for (unsigned long long lo = static_cast<unsigned long long>(blockIdx.x) * kStoreMoveTile; lo < limit;
+       lo += static_cast<unsigned long long>(gridDim.x) * kStoreMoveTile) {
+    const unsigned long long hi = lo + kStoreMoveTile < limit ? lo + kStoreMoveTile : limit;
+    store_evict_gather_tile(new_off, src_off, n_out, arena, dst, 0ull, lo, hi);
+  }
+}
+
+// One launch of the in-place rounds (glc_kernels.h launch_store_evict_round): job j < tiles is tile j of the write-back
+// of round r - 1, job tiles + j tile j of the gather of round r.  A round at or behind the total returns at once.
+__global__ __launch_bounds__(256) void k_store_evict_round(const unsigned long long *__restrict__ ws, unsigned char *arena,
+                                                           unsigned char *stage, unsigned long long round, unsigned long long r,
+                                                           unsigned tiles) {
+  const unsigned long long n_out = ws[0], total = ws[1], first = ws[3];
+  const unsigned long long *new_off = ws + 8, *src_off = new_off + ws[4];
+  for (unsigned j = blockIdx.x; j < 2u * tiles; j += gridDim.x) {
+    const bool back = j < tiles;
+    if (back && r == 0) continue;
+    const unsigned long long rr = back ? r - 1 : r, base = rr * round;
+    if (base >= total) continue;
+    const unsigned long long at = static_cast<unsigned long long>(back ? j : j - tiles) * kStoreMoveTile;
+    const unsigned long long in_round = at + kStoreMoveTile < round ? at + kStoreMoveTile : round;
+    unsigned long long lo = base + at, hi = base + in_round;
+    if (lo < first) lo = first;
+    if (hi > total) hi = total;
+    if (lo >= hi) continue;
+    unsigned char *buf = stage + (rr & 1ull) * round;
+    if (back) {
+      for (unsigned long long p = lo + threadIdx.x * 16ull; p < hi; p += 256ull * 16ull)
+        *reinterpret_cast<uint4 *>(arena + p) = *reinterpret_cast<const uint4 *>(buf + (p - base));
+    } else {
+      store_evict_gather_tile(new_off, src_off, n_out, arena, buf, base, lo, hi);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // S1: the virtual stream of a round of glc_roundtrip_batch_device, gathered from clips that lie strided
 // (and, `planar`, one plane per channel) in the caller's memory.  Workgroup row blockIdx.x is virtual frame
 // slot v: the 1024 * ch interleaved samples [1024 v, 1024 v + 1024) of the stream.  Its clip is the last one
@@ -2484,6 +2656,36 @@ hipError_t launch_store_plan_crops(const StoreDraw &a, hipStream_t s) {
   const uint64_t threads = a.n_crops * a.max_hops, blocks = (threads + 255) / 256;
   if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_store_plan_crops, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_store_evict_scan(const StoreEvict &a, hipStream_t s) {
+  if (!a.entries || !a.keep || !a.entries_out || !a.new_index || !a.n_out || !a.cursor || !a.ws || a.n_entries == 0 ||
+      (a.lengths == nullptr) != (a.lengths_out == nullptr))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_store_evict_scan, dim3(1), dim3(1024), 0, s, a);
+  const uint64_t blocks = (a.n_entries + 255) / 256;
+  hipLaunchKernelGGL(k_store_evict_tail, dim3(static_cast<unsigned>(blocks < 1024 ? blocks : 1024)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_store_evict_gather(const uint64_t *ws, const void *arena, uint64_t arena_bytes, void *dst, hipStream_t s) {
+  if (!ws || !arena || !dst) return hipErrorInvalidValue;
+  if (arena_bytes == 0) return hipSuccess;  // nothing is usable in an empty arena
+  const uint64_t tiles = (arena_bytes + kStoreMoveTile - 1) / kStoreMoveTile;
+  hipLaunchKernelGGL(k_store_evict_gather, dim3(static_cast<unsigned>(tiles < kStoreMoveGrid ? tiles : kStoreMoveGrid)), dim3(256), 0, s,
+                     reinterpret_cast<const unsigned long long *>(ws), static_cast<const unsigned char *>(arena),
+                     static_cast<unsigned char *>(dst));
+  return hipGetLastError();
+}
+
+hipError_t launch_store_evict_round(const uint64_t *ws, void *arena, void *stage, uint64_t round, uint64_t r, hipStream_t s) {
+  if (!ws || !arena || !stage || round == 0 || (round & 63ull) || round > (1ull << 40)) return hipErrorInvalidValue;
+  const uint64_t tiles = (round + kStoreMoveTile - 1) / kStoreMoveTile;
+  hipLaunchKernelGGL(k_store_evict_round, dim3(static_cast<unsigned>(2 * tiles < kStoreMoveGrid ? 2 * tiles : kStoreMoveGrid)), dim3(256),
+                     0, s, reinterpret_cast<const unsigned long long *>(ws), static_cast<unsigned char *>(arena),
+                     static_cast<unsigned char *>(stage), static_cast<unsigned long long>(round), static_cast<unsigned long long>(r),
+                     static_cast<unsigned>(tiles));
   return hipGetLastError();
 }
 

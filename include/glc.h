@@ -757,6 +757,61 @@ int glc_decode_crops_device_store(glc_ctx *ctx,
                                   const int64_t *d_clips, const int64_t *d_starts, uint64_t length,
                                   float *d_out, const glc_clip_layout *out);
 
+/* ---- evicting clips from the store: compact arena and index on the device ------------------- */
+
+/* What d_new_index holds for an entry that was not kept. */
+#define GLC_STORE_DROPPED      (-1)  /* keep[i] == 0 */
+#define GLC_STORE_UNUSABLE     (-2)  /* stored == 0, offset or bytes not a multiple of 64, bytes == 0,
+                                        or [offset, offset + bytes) not inside the source arena */
+#define GLC_STORE_OUT_OF_ORDER (-3)  /* begins below the end of an earlier candidate */
+
+/* Drops clips from a store and closes the gaps: the kept blobs move to the front of d_dst in index order, the index
+ * is rewritten to match, and *d_cursor is left where the next glc_encode_batch_device_compact appends.  The
+ * selection d_keep[n_entries] (non-zero = keep) is device data, and everything is decided on the device.
+ * Candidates: entry i is a candidate when keep[i] != 0 and it is usable: stored != 0, offset % 64 == 0,
+ *   bytes % 64 == 0, bytes != 0, offset <= arena_bytes and bytes <= arena_bytes - offset.
+ * Kept: a candidate is kept when its offset is not below E_i, the maximum of offset + bytes over ALL candidates
+ *   j < i (0 when there is none).  Every store the encoder wrote passes (its offsets ascend with i across rounds
+ *   and calls), and so does every host-made store laid out in index order.
+ * Placement: the kept entries, in index order, are numbered 0 .. n_out - 1; number k goes to the destination offset
+ *   that is the sum of `bytes` of the kept entries in front of it, from 0, every one a multiple of 64.
+ *   d_entries_out[k] = {new offset, bytes, n_pairs, n_raw_rows, stored}, stored = (new offset <= dst_bytes && bytes <=
+ *   dst_bytes - new offset): in place always 1; out of place a blob that does not fit is not written, and the sum
+ *   and the cursor count on - the encoder's rule.  d_lengths_out[k] = d_lengths[i].  d_new_index[i] = k, or
+ *   GLC_STORE_DROPPED, which wins over GLC_STORE_UNUSABLE, which wins over GLC_STORE_OUT_OF_ORDER.  *d_n_out = n_out.
+ *   *d_cursor = the sum over all kept entries: written, never read.  Entries and lengths [n_out, n_entries) of the
+ *   output arrays are written as all-zero words: a stale index gives GLC_COMPACT_NO_BLOB or GLC_COMPACT_BAD_CROP in a
+ *   draw, it does not read old bytes.
+ * Bytes: for every kept, stored entry the `bytes` bytes at its new offset in d_dst are the bytes that were at its old
+ *   offset in d_arena, verbatim; the call does not look into a blob (a damaged one stays exactly as damaged).  In
+ *   place no byte of the arena at or above *d_cursor is written.  Out of place no byte of d_dst outside the stored
+ *   blobs is written and the source arena is not written at all.  No load leaves [d_arena, d_arena + arena_bytes),
+ *   d_entries[0 .. n_entries), d_lengths[0 .. n_entries) or d_keep[0 .. n_entries), whatever they hold.
+ * Aliasing: d_dst is d_arena with dst_bytes == arena_bytes (in place) or an arena disjoint from it.  d_entries_out may
+ *   be d_entries and d_lengths_out may be d_lengths: the results are as if every input had been read before any output
+ *   was written.  Any other overlap among the arenas and arrays is GLC_EINVAL.
+ * In place the bytes move in rounds through a staging buffer the context owns (64 MiB packed bytes per round, two
+ *   buffers); the host does not know the packed total and queues ceil(arena_bytes / round) + 1 launches, of which those
+ *   behind the total return at once.  A caller who knows a bound on the bytes in use (a cursor it has read before)
+ *   may pass it as arena_bytes and gets fewer launches - entries that reach behind the bound are then UNUSABLE.
+ *   Out of place one gather goes straight into d_dst.
+ * Family rules: queued on glc_ctx_stream(ctx) and NOT synchronised; no host-to-device or device-to-host copy; the
+ *   call blocks only where its workspace (16 bytes per entry, the staging) has to grow; the number and shape of its
+ *   launches depend on n_entries, arena_bytes and the round size alone.  It is not a decode and not an encode: the
+ *   resident stream, an open decode session, the kept plan and every "last info / last status" record of the context
+ *   stay exactly as they were.
+ * GLC_EINVAL, checked before anything is queued: a null pointer (d_lengths and d_lengths_out are both NULL or both
+ *   given), an arena not 64-byte aligned, an array not 8-byte aligned (d_keep needs no alignment), n_entries == 0,
+ *   the overlaps above, in place with dst_bytes != arena_bytes. */
+int glc_store_compact_device(glc_ctx *ctx,
+                             void *d_arena, uint64_t arena_bytes,
+                             const glc_store_entry *d_entries, const int64_t *d_lengths, uint64_t n_entries,
+                             const uint8_t *d_keep,
+                             void *d_dst, uint64_t dst_bytes,
+                             glc_store_entry *d_entries_out, int64_t *d_lengths_out,
+                             int64_t *d_new_index,
+                             uint64_t *d_n_out, uint64_t *d_cursor);
+
 /* ---- tables (for inspection / parity tests) ---------------------------------------------- */
 
 /* Copies of the host tables of a context: MdctTables.cos_table [1024*2048] (row k), window

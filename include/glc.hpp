@@ -210,6 +210,19 @@ inline CropSlots store_crop_slots(uint64_t length, uint16_t channels) {
 // Arena bytes that hold the blobs of every clip of a layout whatever their content (glc_compact_store_bound).
 inline uint64_t compact_store_bound(const glc_clip_layout &in) { return glc_compact_store_bound(&in); }
 
+// Evict clips from a store and close the gaps (glc.h glc_store_compact_device), on any context: the kept blobs of
+// d_arena go to the front of d_dst (d_arena itself: in place) in index order, the index is rewritten, *d_cursor is where
+// the next encode_batch_device_compact appends.  d_keep[n_entries]: device bytes, non-zero = keep.  d_lengths and
+// d_lengths_out: both or neither.  Queued on the context's stream, not synchronised; nothing is copied to the host.
+// Encoder::compact_store_device and Decoder::compact_store_device forward here.
+inline void compact_store_device(glc_ctx *ctx, void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
+                                 const int64_t *d_lengths, uint64_t n_entries, const uint8_t *d_keep, void *d_dst, uint64_t dst_bytes,
+                                 glc_store_entry *d_entries_out, int64_t *d_lengths_out, int64_t *d_new_index, uint64_t *d_n_out,
+                                 uint64_t *d_cursor) {
+  detail::check(glc_store_compact_device(ctx, d_arena, arena_bytes, d_entries, d_lengths, n_entries, d_keep, d_dst, dst_bytes,
+                                         d_entries_out, d_lengths_out, d_new_index, d_n_out, d_cursor), ctx);
+}
+
 class Encoder {
  public:
   // Encoder::new(sample_rate: u32) — src/codec.rs:406
@@ -311,6 +324,13 @@ class Encoder {
   void encode_batch_device_compact(const float *d_pcm, const glc_clip_layout &in, void *d_arena, uint64_t arena_bytes,
                                    uint64_t *d_cursor, glc_store_entry *d_entries) {
     detail::check(glc_encode_batch_device_compact(ctx_, d_pcm, &in, d_arena, arena_bytes, d_cursor, d_entries), ctx_);
+  }
+  // glc::compact_store_device on this context
+  void compact_store_device(void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries, const int64_t *d_lengths,
+                            uint64_t n_entries, const uint8_t *d_keep, void *d_dst, uint64_t dst_bytes, glc_store_entry *d_entries_out,
+                            int64_t *d_lengths_out, int64_t *d_new_index, uint64_t *d_n_out, uint64_t *d_cursor) {
+    glc::compact_store_device(ctx_, d_arena, arena_bytes, d_entries, d_lengths, n_entries, d_keep, d_dst, dst_bytes, d_entries_out,
+                              d_lengths_out, d_new_index, d_n_out, d_cursor);
   }
   void synchronize() { detail::check(glc_ctx_synchronize(ctx_), ctx_); }
   glc_ctx *ctx() { return ctx_; }
@@ -456,6 +476,13 @@ class Decoder {
                                  uint64_t length, float *d_out, const glc_clip_layout &out) {
     detail::check(glc_decode_crops_device_store(ctx_, d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips,
                                                 d_starts, length, d_out, &out), ctx_);
+  }
+  // glc::compact_store_device on this context
+  void compact_store_device(void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries, const int64_t *d_lengths,
+                            uint64_t n_entries, const uint8_t *d_keep, void *d_dst, uint64_t dst_bytes, glc_store_entry *d_entries_out,
+                            int64_t *d_lengths_out, int64_t *d_new_index, uint64_t *d_n_out, uint64_t *d_cursor) {
+    glc::compact_store_device(ctx_, d_arena, arena_bytes, d_entries, d_lengths, n_entries, d_keep, d_dst, dst_bytes, d_entries_out,
+                              d_lengths_out, d_new_index, d_n_out, d_cursor);
   }
   // what the device check found in the blobs (or windows) of the last of these calls (synchronises)
   std::vector<glc_compact_status> last_compact_status(uint64_t n_clips = 1) {

@@ -153,6 +153,11 @@ int glc_debug_store_plan_device(glc_ctx *ctx, const void *d_arena, uint64_t aren
                                 const int64_t *d_starts, uint64_t length, const float *d_out, const glc_clip_layout *out,
                                 void *dir, void *desc, uint32_t *verdict);
 
+/* The packed bytes an in-place glc_store_compact_device of `ctx` moves per round (include/glc.h): a multiple of 64, 0
+ * restores the default.  tests/test_store_compact.py puts blobs of a few hundred bytes across round boundaries with
+ * rounds of 1 KiB and 4 KiB; tools/store_compact_bench.cpp measures the rounds the default was chosen from. */
+int glc_debug_set_store_compact_round(glc_ctx *ctx, uint64_t bytes);
+
 /* The shader clock the device HOLDS under load (measurement only; bench.py's roofline.clock_ghz_held).
  * `begin` starts one sleeping wave on a stream of its own that runs for `window_us` microseconds beside
  * whatever the caller queues meanwhile and reads the shader-cycle counter against the constant 100 MHz
