@@ -3724,6 +3724,18 @@ int glc_debug_encode_screen_stats(glc_ctx *ctx, uint64_t *rows_screened, uint64_
   return GLC_OK;
 }
 
+int glc_debug_encode_screen_layout(uint32_t ne, uint32_t rows, uint32_t *hybrid_pairs, uint32_t *planes,
+                                   uint64_t *workspace_bytes) {
+  if (!hybrid_pairs || !planes || !workspace_bytes) return GLC_EINVAL;
+  const uint32_t edge = 64u * ne;  // a last band that starts at column 64 ne
+  glc::ScreenShape sh{};
+  if (ne > 16 || !glc::encode_screen_shape(&edge, 1, &sh)) return GLC_EINVAL;
+  *hybrid_pairs = sh.hp;
+  *planes = sh.n_planes;
+  *workspace_bytes = glc::encode_screen_bytes(rows, sh);
+  return GLC_OK;
+}
+
 int glc_debug_clock_probe_begin(glc_ctx *ctx, uint32_t window_us) {
   if (!ctx || window_us == 0) return fail(ctx, GLC_EINVAL, "glc_debug_clock_probe_begin: bad argument");
   DeviceGuard guard(ctx->device);

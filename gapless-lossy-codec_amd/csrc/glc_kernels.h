@@ -53,7 +53,9 @@ hipError_t launch_quantize(const DeviceTables &t, const float *coef, uint32_t M,
 //          handful of failed rows cost one wave's chain of 2048 dependent adds, a long list costs a chain per
 //          kRowsGrid items
 struct ScreenShape {
-  uint32_t l0, c0, ne, n_oct;  // start of the last band, l0 rounded up to 64, c0 / 64, octets of columns >= c0
+  uint32_t l0, c0, ne;  // start of the last band, l0 rounded up to 64, c0 / 64
+  uint32_t hp;          // exact column pairs of the transform's hybrid waves (0: none - waves [0, ne) are exact)
+  uint32_t n_planes;    // hf planes of a launch: one per wave that carries bound columns (the A plane follows them)
 };
 bool encode_screen_shape(const uint32_t *edges, uint32_t n_bands, ScreenShape *sh);  // false: c0 / 64 outside 1..15
 // true where launch_mdct_forward gives the launch to the 16-wave k_mdct_fwd_st, the form the mixed-role kernel has

@@ -6,8 +6,9 @@
 // never lets the compiler contract a*b+c: the file is compiled with -ffp-contract=off and the
 // accumulation is additionally written with __fmul_rn/__fadd_rn.  No v_fma/v_fmac/v_pk_fma may
 // appear in the MDCT kernels (checked at build time by tools/check_isa.py) - with one exception that
-// never produces a value of the stream: the bound waves of k_mdct_mix_st accumulate an UPPER BOUND of
-// last-band magnitudes with v_pk_fma_f32 (the screen, above k_quantize).
+// never produces a value of the stream: the bound waves of k_mdct_mix_st, and the bound column pairs of its hybrid
+// waves, accumulate an UPPER BOUND of last-band magnitudes with v_pk_fma_f32 (the screen, above k_quantize; DESIGN
+// section 2).
 //
 // Reference loops replaced (file:line into /root/reference):
 //   K1 k_mdct_fwd      src/codec.rs:476-481 (window) + :359-374 (mdct_block)
@@ -70,11 +71,13 @@ constexpr int kQRows = 4;  // rows per wave
 
 // The screen.  With L = edges[n_bands - 1] the start of the last band and C0 = L rounded up to
 // 64, the mixed-role K1 leaves exact coefficients only below C0; of a column k >= C0 it leaves e_k, the same sum
-// with fused multiply-adds, as max |e| per octet of columns, and A = sum_i |fl(x_i w_i)|.  The stream's value is
+// with fused multiply-adds, as max |e| per PLANE - the bound columns of one wave of the transform: 8 of them, or
+// the 2 / 4 / 6 of a hybrid wave; the screen only ever takes the maximum over all planes, so which columns a plane
+// holds is the transform's business - and A = sum_i |fl(x_i w_i)|, the ascending f32 sum.  The stream's value is
 // c_k = fl(s_k norm) with s_k the ascending f32 sum of the rounded products.  Both s_k and e_k differ from the
 // real sum of xw_i T_ki by at most gamma_2048 sum_i |xw_i| |T_ki| (2048 roundings each at most: product and add
 // per term there, one fused rounding per term here; gamma_n = n u / (1 - n u), u = 2^-24), and |T| <= 1, so
-//     |c_k| <= (max_octets |e| + 2 gamma_2048 A) norm (1 + u),          2 gamma_2048 = 2.4417e-4 < kScreenCErr.
+//     |c_k| <= (max_planes |e| + 2 gamma_2048 A) norm (1 + u),          2 gamma_2048 = 2.4417e-4 < kScreenCErr.
 // kScreenSlack covers that (1 + u), the roundings of the bound's own five operations and those of the 2048 adds
 // behind A (relative gamma_2048 = 1.3e-4, on a term that only adds); kScreenTiny the products that underflow
 // (4096 operations, each off by less than 2^-126 even where subnormals are flushed: < 5e-35).
@@ -86,12 +89,12 @@ constexpr int kQRows = 4;  // rows per wave
 constexpr float kScreenCErr = 2.45e-4f, kScreenSlack = 1.001f, kScreenTiny = 1e-33f;
 
 struct ScreenArgs {
-  const float *hf;        // [n_oct + 1][stride]: per octet of columns >= C0 max |e|, then A
+  const float *hf;        // [n_planes + 1][stride]: per bound-carrying wave of the transform max |e| of its columns >= C0, then A
   unsigned *row_flag;     // [M] 1 = the row's frame failed the screen (MODE 1 writes every entry, MODE 2 reads)
   unsigned *wave_fail;    // [waves of the MODE 1 launch] failed rows of each wave (every entry written)
   unsigned *host_stat;    // host-mapped {failed rows, rows, seq, -, u64 failed rows so far}: MODE 2 leaves the count
   unsigned long long stride;
-  unsigned c0, l0, n_oct, seq;
+  unsigned c0, l0, n_planes, seq;
 };
 
 // MODE 0: every row of the launch from exact coefficients.  1: the screened form - rows that pass, from the
@@ -181,11 +184,11 @@ __device__ __forceinline__ void quantize_body(const DeviceTables &tb, const floa
   if constexpr (MODE == 1) {
     // the screen: rows m0 .. m0 + 3 are one float4 of every hf plane
     float hfm[4] = {0.f, 0.f, 0.f, 0.f};
-    for (unsigned o = lane; o < sa.n_oct; o += 64) {
+    for (unsigned o = lane; o < sa.n_planes; o += 64) {
       const float4 h = *reinterpret_cast<const float4 *>(sa.hf + o * sa.stride + m0);
       hfm[0] = fmaxf(hfm[0], h.x); hfm[1] = fmaxf(hfm[1], h.y); hfm[2] = fmaxf(hfm[2], h.z); hfm[3] = fmaxf(hfm[3], h.w);
     }
-    const float4 a4 = *reinterpret_cast<const float4 *>(sa.hf + sa.n_oct * sa.stride + m0);
+    const float4 a4 = *reinterpret_cast<const float4 *>(sa.hf + sa.n_planes * sa.stride + m0);
     const float asum[4] = {a4.x, a4.y, a4.z, a4.w};
     unsigned fail = 0;
 #pragma unroll
@@ -2328,7 +2331,10 @@ bool encode_screen_shape(const uint32_t *edges, uint32_t n_bands, ScreenShape *s
   sh->c0 = (sh->l0 + 63u) / 64u * 64u;
   sh->ne = sh->c0 / 64u;
   if (sh->ne < 1 || sh->ne > 15) return false;
-  sh->n_oct = 8u * (16u - sh->ne);
+  // The balanced wave layout of k_mdct_mix_st (glc_mdct_fwd.hpp mix_wave) wherever it exists.  The plane count
+  // follows from the choice, and the workspace size, its carving and the quantiser's loop read it from here alone.
+  sh->hp = static_cast<uint32_t>(k1::mix_hybrid_pairs(static_cast<int>(sh->ne)));
+  sh->n_planes = static_cast<uint32_t>(k1::mix_planes(static_cast<int>(sh->ne), static_cast<int>(sh->hp)));
   return true;
 }
 
@@ -2338,7 +2344,7 @@ inline uint64_t screen_stride(uint32_t M) { return (static_cast<uint64_t>(M) + 2
 
 uint64_t encode_screen_bytes(uint32_t M, const ScreenShape &sh) {
   // hf planes | row flags | failed rows per quantiser wave (a quarter of a plane is more than it needs)
-  return ((sh.n_oct + 1ull) * screen_stride(M) + screen_stride(M) + screen_stride(M) / 4) * 4ull;
+  return ((sh.n_planes + 1ull) * screen_stride(M) + screen_stride(M) + screen_stride(M) / 4) * 4ull;
 }
 
 hipError_t launch_encode_screened(const DeviceTables &t, const ScreenShape &sh, const PcmView &pcm, uint64_t frame_begin,
@@ -2348,18 +2354,18 @@ hipError_t launch_encode_screened(const DeviceTables &t, const ScreenShape &sh, 
   if (M == 0) return hipSuccess;
   const uint64_t stride = screen_stride(M);
   float *hf = static_cast<float *>(workspace);
-  unsigned *row_flag = reinterpret_cast<unsigned *>(hf + (sh.n_oct + 1ull) * stride);
+  unsigned *row_flag = reinterpret_cast<unsigned *>(hf + (sh.n_planes + 1ull) * stride);
   unsigned *wave_fail = row_flag + stride;
   hipError_t e;
   switch (pcm.ch) {
-    case 1: e = k1::launch_mix_st<1>(t, pcm, frame_begin, M, coef, sh.ne, hf, stride, s); break;
-    case 2: e = k1::launch_mix_st<2>(t, pcm, frame_begin, M, coef, sh.ne, hf, stride, s); break;
-    case 4: e = k1::launch_mix_st<4>(t, pcm, frame_begin, M, coef, sh.ne, hf, stride, s); break;
-    case 8: e = k1::launch_mix_st<8>(t, pcm, frame_begin, M, coef, sh.ne, hf, stride, s); break;
-    default: e = k1::launch_mix_st<0>(t, pcm, frame_begin, M, coef, sh.ne, hf, stride, s); break;
+    case 1: e = k1::launch_mix_st<1>(t, pcm, frame_begin, M, coef, sh.ne, sh.hp, hf, stride, s); break;
+    case 2: e = k1::launch_mix_st<2>(t, pcm, frame_begin, M, coef, sh.ne, sh.hp, hf, stride, s); break;
+    case 4: e = k1::launch_mix_st<4>(t, pcm, frame_begin, M, coef, sh.ne, sh.hp, hf, stride, s); break;
+    case 8: e = k1::launch_mix_st<8>(t, pcm, frame_begin, M, coef, sh.ne, sh.hp, hf, stride, s); break;
+    default: e = k1::launch_mix_st<0>(t, pcm, frame_begin, M, coef, sh.ne, sh.hp, hf, stride, s); break;
   }
   if (e != hipSuccess) return e;
-  const ScreenArgs sa{hf, row_flag, wave_fail, host_stat, stride, sh.c0, sh.l0, sh.n_oct, seq};
+  const ScreenArgs sa{hf, row_flag, wave_fail, host_stat, stride, sh.c0, sh.l0, sh.n_planes, seq};
   const unsigned long long hdr = record_header_bytes(pcm.ch), rec = record_bytes(pcm.ch);
   const dim3 grid((M + 4 * kQRows - 1) / (4 * kQRows));
   const long long fb = static_cast<long long>(frame_begin);

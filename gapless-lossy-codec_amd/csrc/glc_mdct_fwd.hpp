@@ -20,7 +20,9 @@
 //                      1 / 2 / 4 / 8 channels (CH), one dword per (row, sample) otherwise (CH = 0).
 //   k_mdct_mix_st      the 16-wave k_mdct_fwd_st in mixed-role form, for glc_encode_range_device without a coefficient
 //                      tap: exact waves on the columns below the last band, bound waves (one v_pk_fma_f32 per packed
-//                      multiply-add, no coefficients stored) on the rest - the screen of DESIGN section 2.  With
+//                      multiply-add, no coefficients stored) on the rest - the screen of DESIGN section 2 - and, where
+//                      the exact columns are no whole number of waves per SIMD, hybrid waves that hold column pairs of
+//                      both kinds, so that the four SIMDs issue the same number of packed operations.  With
 //                      k_mdct_fwd_small_cols, the 2 x 2 short-clip kernel over a column range and only the row tiles
 //                      that hold a flagged row: the exact columns of the rows that failed the screen.
 //   k_mdct_fwd_small_rows  the same repair built for latency, for launches in which few rows failed: one wave per
@@ -44,6 +46,8 @@
 //   mac2rows           the 2-row x 8-column multiply/add block; also the entry step of D1 (k_imdct_chan).
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "glc_kernels.h"
 
@@ -805,6 +809,7 @@ inline hipError_t launch_dma(const DeviceTables &t, const PcmView &pcm, uint64_t
 // i-steps at a time, a whole pair ahead (as k_imdct_apply does with its records).
 // ------------------------------------------------------------------------------------------
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x8 __attribute__((ext_vector_type(8)));
 
 template <int D>
@@ -906,10 +911,167 @@ __device__ __forceinline__ void mac2rows_fma(f32x2 (&c0)[4], f32x2 (&c1)[4], f32
       : "v"(a), "s"(b0), "s"(b1), "s"(b2), "s"(b3));
 }
 
-// ROLE of a wave: 0 = exact (st_mac: the stream's arithmetic), 1 = bound (fused), 2 = bound, and the wave
-// also sums |x w| of its lanes' 4 rows over the whole i loop (asum: the A of the screen's error term)
+// Hybrid waves of the mixed-role kernel: of the wave's four column pairs the first two are exact - mac2rows_st's
+// separately rounded multiply, then add, per pair - and the other two are bound pairs (mac2rows_fma's fused op).
+// The multiplies lead and the adds trail, so a product is as far from its add as in mac2rows_st.
+__device__ __forceinline__ void mac2rows_hy(f32x2 (&c0)[4], f32x2 (&c1)[4], f32x2 a, u32x2 b0, u32x2 b1, u32x2 b2,
+                                            u32x2 b3) {
+  f32x2 t0, t1, t2, t3;
+  asm volatile(
+      "v_pk_mul_f32 %8, %12, %13 op_sel_hi:[0,1]\n\t"
+      "v_pk_mul_f32 %9, %12, %14 op_sel_hi:[0,1]\n\t"
+      "v_pk_mul_f32 %10, %12, %13 op_sel:[1,0]\n\t"
+      "v_pk_mul_f32 %11, %12, %14 op_sel:[1,0]\n\t"
+      "v_pk_fma_f32 %2, %12, %15, %2 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %3, %12, %16, %3 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %6, %12, %15, %6 op_sel:[1,0,0]\n\t"
+      "v_pk_fma_f32 %7, %12, %16, %7 op_sel:[1,0,0]\n\t"
+      "v_pk_add_f32 %0, %0, %8\n\t"
+      "v_pk_add_f32 %1, %1, %9\n\t"
+      "v_pk_add_f32 %4, %4, %10\n\t"
+      "v_pk_add_f32 %5, %5, %11"
+      : "+v"(c0[0]), "+v"(c0[1]), "+v"(c0[2]), "+v"(c0[3]), "+v"(c1[0]), "+v"(c1[1]), "+v"(c1[2]), "+v"(c1[3]),
+        "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3)
+      : "v"(a), "s"(b0), "s"(b1), "s"(b2), "s"(b3));
+}
+
+// Which columns a wave of the mixed-role kernel owns and what it does with them.
+//
+// hp = 0 (ne > 11, and wherever the balanced form is not built: mix_hybrid_pairs): waves
+// [0, ne) are exact, [ne, 16) bound.  Waves sit on SIMD wave % 4, so the four SIMDs carry unequal numbers of exact
+// waves unless ne is a multiple of 4 (2, 2, 1, 1 for ne = 6), and the fullest sets the pace between two barriers.
+// hp = ne % 4 > 0 (ne <= 11): the BALANCED form.  With q = ne / 4, the wave with index k = wave / 4 on its SIMD
+// is exact for k < q, HYBRID for k == q - hp of its four column pairs exact, 4 - hp bound - and bound above: every
+// SIMD carries ne exact and 16 - ne bound pairs.  (Above ne = 11 a SIMD would be left without a pure bound wave,
+// which the A sum needs.)
+// Workgroup n_tile owns exact columns [8 ne n_tile, 8 ne (n_tile + 1)) and bound columns C0 + 8 (16 - ne) n_tile ...,
+// C0 = 64 ne, in both forms; inside each range the waves take consecutive runs: 8 columns per exact wave, then
+// 2 hp per hybrid wave; 8 - 2 hp per hybrid wave, then 8 per bound wave.  A run is what one scalar load fetches:
+//   hp = 2   run 0 = the exact 4, run 1 = the bound 4 (the form the kernel is built for: mix_hybrid_pairs)
+//   hp = 3   runs 0, 1 = an x4 and an x2 part of the exact 6 (the x4 on a multiple of 4 columns), run 2 = the bound 2
+//   hp = 1   runs 0, 1 = an x4 and an x2 part of the bound 6, run 2 = the exact 2
+// (the map is stated, and checked below, for every hp; the kernel holds loop copies for hp = 0 and 2 only).
+// Every bound-carrying wave, hybrid ones included, owns one hf plane.
+constexpr int kMixHybridMax = 11;  // largest ne the balanced form takes
+struct MixWave {
+  int kind;    // 0 exact, 1 bound, 2 hybrid
+  int plane;   // hf plane of the wave's bound columns (none: -1)
+  int col[3];  // first column of each run
+  int len[3];  // columns of each run
+  int exact;   // bit r: run r holds exact columns
+};
+// The exact pairs per hybrid wave a launch takes.  Only 2 is built: at ne = 6 (44.1 / 48 kHz) it measured faster than
+// whole waves, at ne = 3 (96 kHz, 3 pairs) the balanced form measured no faster - the chip holds less clock under the
+// fuller SIMDs (profiles/encode_balance_bench.txt) - and no rate has ne % 4 == 1; those keep whole waves.
+__host__ __device__ constexpr int mix_hybrid_pairs(int ne) { return ne <= kMixHybridMax && ne % 4 == 2 ? 2 : 0; }
+// first wave that carries bound columns; every wave from there on owns an hf plane
+__host__ __device__ constexpr int mix_first_bound(int ne, int hp) { return hp ? ne / 4 * 4 : ne; }
+// first wave with bound columns only: it also carries the A sum in workgroups n_tile < 4
+__host__ __device__ constexpr int mix_a_wave(int ne, int hp) { return hp ? ne / 4 * 4 + 4 : ne; }
+// hf planes of a launch (the A plane follows them)
+__host__ __device__ constexpr int mix_planes(int ne, int hp) { return 8 * (16 - mix_first_bound(ne, hp)); }
+__host__ __device__ constexpr MixWave mix_wave(int ne, int hp, int n_tile, int wave) {
+  const int xb = 8 * ne * n_tile;                        // the workgroup's exact columns
+  const int bb = 64 * ne + 8 * (16 - ne) * n_tile;       // ... and its bound columns
+  const int fb = mix_first_bound(ne, hp);
+  const int plane = (16 - fb) * n_tile + wave - fb;
+  if (hp == 0) {
+    if (wave < ne) return MixWave{0, -1, {xb + 8 * wave, 0, 0}, {8, 0, 0}, 1};
+    return MixWave{1, plane, {bb + 8 * (wave - ne), 0, 0}, {8, 0, 0}, 0};
+  }
+  const int q = ne / 4, k = wave / 4, sd = wave % 4, odd = sd & 1;
+  if (k < q) return MixWave{0, -1, {xb + 8 * wave, 0, 0}, {8, 0, 0}, 1};
+  if (k > q) return MixWave{1, plane, {bb + 4 * (8 - 2 * hp) + 8 * (wave - 4 * q - 4), 0, 0}, {8, 0, 0}, 0};
+  const int xr = xb + 32 * q + 2 * hp * sd;              // the hybrid wave's exact run
+  const int br = bb + (8 - 2 * hp) * sd;                 // ... and its bound run
+  if (hp == 2) return MixWave{2, plane, {xr, br, 0}, {4, 4, 0}, 1};
+  // the 6 column run starts on 2 mod 4 columns on the odd SIMDs: x2 first there, x4 first on the even ones
+  if (hp == 3) return MixWave{2, plane, {xr + (odd ? 2 : 0), xr + (odd ? 0 : 4), br}, {4, 2, 2}, 3};
+  return MixWave{2, plane, {br + (odd ? 2 : 0), br + (odd ? 0 : 4), xr}, {4, 2, 2}, 4};
+}
+// no column left out, none covered twice, exact columns exactly [0, 64 ne), ne exact pairs per SIMD, one wave per plane
+__host__ __device__ constexpr bool mix_map_ok(int ne, int hp) {
+  int own[kHopI] = {};
+  int plane_used[8 * 16] = {};
+  int exact_pairs[4] = {};
+  for (int j = 0; j < 8; ++j)
+    for (int w = 0; w < 16; ++w) {
+      const MixWave m = mix_wave(ne, hp, j, w);
+      int cols = 0;
+      for (int r = 0; r < 3; ++r) {
+        const bool ex = (m.exact >> r) & 1;
+        if (m.len[r] && (m.col[r] % (m.len[r] == 8 ? 8 : m.len[r]) || m.col[r] < 0 || m.col[r] + m.len[r] > kHopI)) return false;
+        for (int c = m.col[r]; c < m.col[r] + m.len[r]; ++c) {
+          if (own[c]++ || ex != (c < 64 * ne)) return false;
+        }
+        cols += m.len[r];
+        if (ex && j == 0) exact_pairs[w % 4] += m.len[r] / 2;
+      }
+      if (cols != 8) return false;
+      if ((m.kind == 0) != (m.plane < 0)) return false;
+      if (m.plane >= 0 && (m.plane >= mix_planes(ne, hp) || plane_used[m.plane]++)) return false;
+      if (m.kind == 2 && (m.exact & 1 ? m.len[0] + (hp == 3 ? m.len[1] : 0) : m.len[2]) != 2 * hp) return false;
+    }
+  for (int c = 0; c < kHopI; ++c)
+    if (own[c] != 1) return false;
+  for (int p = 0; p < mix_planes(ne, hp); ++p)
+    if (plane_used[p] != 1) return false;
+  if (hp)
+    for (int sd = 0; sd < 4; ++sd)
+      if (exact_pairs[sd] != ne) return false;
+  return mix_a_wave(ne, hp) < 16 && mix_wave(ne, hp, 0, mix_a_wave(ne, hp)).kind == 1;
+}
+template <int NE>
+constexpr bool mix_maps_ok() {  // whole waves for every ne, the balanced map wherever it exists (built or not)
+  if constexpr (NE == 0) return true;
+  else return mix_map_ok(NE, 0) && mix_map_ok(NE, NE <= kMixHybridMax ? NE % 4 : 0) && mix_maps_ok<NE - 1>();
+}
+static_assert(mix_maps_ok<15>(), "column and plane map of the mixed-role kernel");
+
+// operands of 4 i-steps of a hybrid wave: the same 8 table values per i-step as StOps, as its two runs of 4 columns
+struct HyOps {
+  f32x4 a[4];
+  u32x4 x[4], b[4];  // the exact run, the bound run
+};
+// trow: column 0 of the table row of the stage's first i-step; ox, ob: byte offsets of the wave's two runs in a row.
+// One pointer and two offsets, not two pointers (and two more for the next stage): the 64 table values in flight
+// leave little room in the scalar file.
+template <int II>
+__device__ __forceinline__ void hy_fetch_b(u32x4 &x, u32x4 &b, const unsigned *trow, unsigned ox, unsigned ob) {
+  asm volatile("s_load_dwordx4 %0, %1, %2 offset:%c3" : "=&s"(x) : "s"(trow), "s"(ox), "i"(II * kHopI * 4) : "memory");
+  asm volatile("s_load_dwordx4 %0, %1, %2 offset:%c3" : "=&s"(b) : "s"(trow), "s"(ob), "i"(II * kHopI * 4) : "memory");
+}
+template <int II, int AS>
+__device__ __forceinline__ void hy_fetch(HyOps &o, unsigned a_addr, const unsigned *trow, unsigned ox, unsigned ob) {
+  hy_fetch_b<II>(o.x[0], o.b[0], trow, ox, ob);
+  hy_fetch_b<II + 1>(o.x[1], o.b[1], trow, ox, ob);
+  hy_fetch_b<II + 2>(o.x[2], o.b[2], trow, ox, ob);
+  hy_fetch_b<II + 3>(o.x[3], o.b[3], trow, ox, ob);
+  st_fetch_a<II, AS>(o.a[0], a_addr);
+  st_fetch_a<II + 1, AS>(o.a[1], a_addr);
+  st_fetch_a<II + 2, AS>(o.a[2], a_addr);
+  st_fetch_a<II + 3, AS>(o.a[3], a_addr);
+}
+__device__ __forceinline__ void hy_wait(HyOps &o) {
+  asm volatile("s_waitcnt lgkmcnt(0)"
+               : "+s"(o.x[0]), "+s"(o.x[1]), "+s"(o.x[2]), "+s"(o.x[3]), "+s"(o.b[0]), "+s"(o.b[1]), "+s"(o.b[2]),
+                 "+s"(o.b[3])::"memory");
+  asm volatile("" : "+v"(o.a[0]), "+v"(o.a[1]), "+v"(o.a[2]), "+v"(o.a[3])::"memory");
+}
+__device__ __forceinline__ void hy_mac(f32x2 (&acc)[4][4], const HyOps &o) {
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    mac2rows_hy(acc[0], acc[1], o.a[d].xy, o.x[d].xy, o.x[d].zw, o.b[d].xy, o.b[d].zw);
+    mac2rows_hy(acc[2], acc[3], o.a[d].zw, o.x[d].xy, o.x[d].zw, o.b[d].xy, o.b[d].zw);
+  }
+}
+
+// ROLE of a wave's copy of the i loop: 0 = exact (st_mac: the stream's arithmetic), 1 = bound (fused), 2 + j = bound,
+// and the wave also sums |x w| of row j of each lane's 4 over the whole i loop (asum: the A of the screen's error
+// term), kRoleHybrid = hybrid (hy_mac)
+constexpr int kRoleHybrid = 6;
 template <int ROLE, int D>
-__device__ __forceinline__ void st_mac_role(f32x2 (&acc)[4][4], float (&asum)[4], const StOps<D> &o) {
+__device__ __forceinline__ void st_mac_role(f32x2 (&acc)[4][4], float &asum, const StOps<D> &o) {
   if constexpr (ROLE == 0) {
     st_mac(acc, o);
   } else {
@@ -917,12 +1079,7 @@ __device__ __forceinline__ void st_mac_role(f32x2 (&acc)[4][4], float (&asum)[4]
     for (int d = 0; d < D; ++d) {
       mac2rows_fma(acc[0], acc[1], o.a[d].xy, o.b[d].s01, o.b[d].s23, o.b[d].s45, o.b[d].s67);
       mac2rows_fma(acc[2], acc[3], o.a[d].zw, o.b[d].s01, o.b[d].s23, o.b[d].s45, o.b[d].s67);
-      if constexpr (ROLE == 2) {
-        asum[0] = add_rn(asum[0], __builtin_fabsf(o.a[d].x));
-        asum[1] = add_rn(asum[1], __builtin_fabsf(o.a[d].y));
-        asum[2] = add_rn(asum[2], __builtin_fabsf(o.a[d].z));
-        asum[3] = add_rn(asum[3], __builtin_fabsf(o.a[d].w));
-      }
+      if constexpr (ROLE >= 2) asum = add_rn(asum, __builtin_fabsf(o.a[d][ROLE - 2]));
     }
   }
 }
@@ -940,19 +1097,25 @@ struct RoleTag {
 //
 // MIX (k_mdct_mix_st, 16 waves): the mixed-role form for launches whose records can only depend on the columns
 // below C0 = 64 ne when a row passes the screen.  Tile, staging, ring and barriers are the
-// same; what changes is which columns a wave owns and what it does with them.  Waves [0, ne) are EXACT: workgroup
-// n_tile = j owns columns [8 ne j, 8 ne (j + 1)), its exact waves run st_mac and store coefficients.  Waves
-// [ne, 16) are BOUND waves on columns C0 + 8 (16 - ne) j ...: fused multiply-adds (half the issue slots), no
-// coefficients; per row the largest |sum| of the wave's 8 columns goes to hf[octet][row] (octet = (16 - ne) j +
-// wave - ne; plain coalesced stores, every slot of the launch is written), and wave ne of workgroup j = 0 - the sum
-// does not depend on the columns - adds the row's sum of |x w| at hf[8 (16 - ne)][row].  Waves sit on SIMD wave % 4, so `wave < ne` spreads the exact ones as evenly
-// as ne allows (2, 2, 1, 1 for ne = 6) and wave ne, which has 4 more adds per i-step, never joins a fullest SIMD.
+// same; what changes is which columns a wave owns and what it does with them (mix_wave, above).  Workgroup
+// n_tile = j owns exact columns [8 ne j, 8 ne (j + 1)) and bound columns C0 + 8 (16 - ne) j ....  EXACT waves run
+// st_mac on 8 of the former and store coefficients.  BOUND waves run fused multiply-adds (half the issue slots) on 8
+// of the latter and store none; per row the largest |sum| of the wave's columns goes to its plane hf[plane][row]
+// (plain coalesced stores, every slot of the launch is written).  HYBRID waves (E > 0: E exact column pairs, 4 - E
+// bound ones) do both with their two kinds of columns, so that every SIMD - waves sit on SIMD wave % 4 - carries ne
+// exact and 16 - ne bound pairs and issues the same 2 ne + (16 - ne) packed operations per i-step; E = 0 is the
+// layout with whole waves only (2, 2, 1, 1 exact waves per SIMD for ne = 6: 96, 96, 80, 80).  The sum of |x w| of a
+// row - it does not depend on the columns - is formed by the first bound-only wave of workgroups j = 0 .. 3, workgroup
+// j adding row j of each lane's four (one add per i-step; four in one workgroup would put that workgroup behind the
+// other seven of the launch's single round) and storing it at hf[planes][m0 + 4 lane + j]: per row the same
+// ascending f32 sum wherever it is formed.
 // The role branch is wave-uniform and outside the i loop; every role runs the same barriers.
-template <int CH, int PRIO, int D, int NW, int BK, int ABL, bool STAMP, bool MIX>
+template <int CH, int PRIO, int D, int NW, int BK, int ABL, bool STAMP, bool MIX, int E = 0>
 __device__ __forceinline__ void st_body(const DeviceTables &tb, const PcmView &pcm, long long frame_begin, unsigned M,
                                         float *__restrict__ coef, unsigned long long *__restrict__ stamps, unsigned ne,
                                         float *__restrict__ hf, unsigned long long hf_stride) {
-  static_assert(!MIX || NW == 16, "the mixed-role form is the 16-wave one");
+  static_assert(!MIX || (NW == 16 && D == 4), "the mixed-role form is the 16-wave one");
+  static_assert((E == 0 || E == 2) && (MIX || E == 0), "exact pairs of the hybrid waves: the forms that are built");
   if constexpr (STAMP) {
     if (threadIdx.x == 0) stamps[static_cast<size_t>(blockIdx.x) * 8] = __builtin_amdgcn_s_memrealtime();
   }
@@ -1107,22 +1270,24 @@ __device__ __forceinline__ void st_body(const DeviceTables &tb, const PcmView &p
   const unsigned a_lds0 = static_cast<unsigned>(reinterpret_cast<uintptr_t>(&As[0][lane * 4]));
   // this wave's 8 columns of table row 0 (wave-uniform: the scalar loads' base)
   int col0 = n0 + 8 * wave, role = 0;
+  MixWave mw{};
   if constexpr (MIX) {
-    const int nb = 16 - static_cast<int>(ne);  // bound waves per workgroup
-    if (wave < static_cast<int>(ne)) {
-      col0 = 8 * static_cast<int>(ne) * n_tile + 8 * wave;
-    } else {
-      col0 = 64 * static_cast<int>(ne) + 8 * nb * n_tile + 8 * (wave - static_cast<int>(ne));
-      role = wave == static_cast<int>(ne) && n_tile == 0 ? 2 : 1;  // A does not depend on the columns: one workgroup of a row tile forms it
-    }
+    mw = mix_wave(static_cast<int>(ne), E, n_tile, wave);
+    col0 = mw.col[0];
+    role = mw.kind == 2 ? kRoleHybrid : mw.kind;
+    // A does not depend on the columns: the first four workgroups of a row tile form it, workgroup j row j of each
+    // lane's four - one add per i-step - so that no workgroup falls behind the others by more than that
+    if (wave == mix_a_wave(static_cast<int>(ne), E) && n_tile < 4) role = 2 + n_tile;
   }
-  const unsigned *b_base = reinterpret_cast<const unsigned *>(tb.cos_t) + col0;
+  // a hybrid wave's loads start from column 0 and add the byte offset of each of its runs
+  const unsigned *b_base = reinterpret_cast<const unsigned *>(tb.cos_t) + (role == kRoleHybrid ? 0 : col0);
+  const unsigned hy_ox = static_cast<unsigned>(mw.col[0]) * 4u, hy_ob = static_cast<unsigned>(mw.col[1]) * 4u;
 
   // Stage hand-off in the middle of a stage, as in k_mdct_fwd_dma: the samples of stage s+1 are
   // published by a barrier after the first BK / 2 i-steps, the stage's last fetch takes the first operands
   // of stage s+1, and the PCM loads of stage s+2 are issued behind the barrier.  Slot use: stage s reads
   // slot s % 3; As[(s+1) % 3] is written before the barrier of stage s (last read in stage s-2).
-  float asum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  float asum = 0.0f;
   // The i loop, once per role of the mixed form (one of them runs).  Every load an asm statement issues and a
   // LATER one waits for - PCM registers, operands - is issued and retired INSIDE it: the compiler does not know such
   // a load is in flight, and where the roles branch or join it may copy the destination registers, or reuse them,
@@ -1132,9 +1297,21 @@ __device__ __forceinline__ void st_body(const DeviceTables &tb, const PcmView &p
   issue_a(BK);  // PCM of stage 1 into registers
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __syncthreads();
-  StOps<D> X, Y;
-  st_fetch<0, kAS>(X, a_lds0, b_base);
-  st_wait(X);
+  constexpr bool kHy = ROLE == kRoleHybrid;
+  std::conditional_t<kHy, HyOps, StOps<D>> X, Y;
+  // one spelling of fetch / wait / multiply-add for both operand forms
+  // (always inlined: the loads they issue are in flight when they return)
+  auto fetch = [&](auto ii, auto &o, unsigned a_at, const unsigned *trow) __attribute__((always_inline)) {
+    constexpr int II = decltype(ii)::value;
+    if constexpr (kHy) hy_fetch<II, kAS>(o, a_at, trow, hy_ox, hy_ob);
+    else st_fetch<II, kAS>(o, a_at, trow);
+  };
+  auto wait = [&](auto &o) __attribute__((always_inline)) {
+    if constexpr (kHy) hy_wait(o);
+    else st_wait(o);
+  };
+  fetch(RoleTag<0>{}, X, a_lds0, b_base);
+  wait(X);
   if constexpr (STAMP) {
     if (tid == 0) stamps[static_cast<size_t>(blockIdx.x) * 8 + 1] = __builtin_amdgcn_s_memrealtime();
   }
@@ -1166,7 +1343,7 @@ __device__ __forceinline__ void st_body(const DeviceTables &tb, const PcmView &p
   do {                                                            \
     wait_staged();                                                \
     store_a(((s + 1) & (kStages - 1)) * BK, nslot);               \
-    st_wait(NEXT);                                                \
+    wait(NEXT);                                                   \
     __builtin_amdgcn_s_barrier();                                 \
     if constexpr (PRIO == 2) __builtin_amdgcn_s_setprio(1);       \
     issue_a(((s + 2) & (kStages - 1)) * BK);                      \
@@ -1174,11 +1351,12 @@ __device__ __forceinline__ void st_body(const DeviceTables &tb, const PcmView &p
     // X holds the operands of i-steps [0, D) of the stage; groups alternate X, Y
 #define GLC_ST_GROUP(CUR, NXT, II)                                                        \
   do {                                                                                    \
-    if constexpr ((II) + D < BK) st_fetch<((II) + D) % BK, kAS>(NXT, a_addr, brow);        \
-    else st_fetch<0, kAS>(NXT, a_next, brow_next);                                        \
-    st_mac_role<ROLE>(acc, asum, CUR);                                                    \
+    if constexpr ((II) + D < BK) fetch(RoleTag<((II) + D) % BK>{}, NXT, a_addr, brow);   \
+    else fetch(RoleTag<0>{}, NXT, a_next, brow_next);                                     \
+    if constexpr (kHy) hy_mac(acc, CUR);                                                  \
+    else st_mac_role<ROLE>(acc, asum, CUR);                                               \
     if constexpr ((II) + D == BK / 2 && !(ABL & 2)) GLC_ST_HANDOFF(NXT);                  \
-    else st_wait(NXT);                                                                    \
+    else wait(NXT);                                                                       \
   } while (0)
     GLC_ST_GROUP(X, Y, 0);
     GLC_ST_GROUP(Y, X, D);
@@ -1210,7 +1388,11 @@ __device__ __forceinline__ void st_body(const DeviceTables &tb, const PcmView &p
   if constexpr (MIX) {
     if (role == 0) i_loop(RoleTag<0>{});
     else if (role == 1) i_loop(RoleTag<1>{});
-    else i_loop(RoleTag<2>{});
+    else if (role == 2) i_loop(RoleTag<2>{});
+    else if (role == 3) i_loop(RoleTag<3>{});
+    else if (role == 4) i_loop(RoleTag<4>{});
+    else if (role == 5) i_loop(RoleTag<5>{});
+    else if constexpr (E != 0) i_loop(RoleTag<kRoleHybrid>{});
   } else {
     i_loop(RoleTag<0>{});
   }
@@ -1222,21 +1404,32 @@ __device__ __forceinline__ void st_body(const DeviceTables &tb, const PcmView &p
     if (role != 0) {
       // rows m0 + 4 lane .. + 3 of the launch's padded row range (hf_stride = rows rounded up to whole tiles:
       // rows >= M were staged as zeros and store 0)
-      const unsigned nb = 16u - ne;
+      const int c_lo = role == kRoleHybrid ? E : 0;  // a hybrid wave's first E pairs are coefficients
       f32x4 mx;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float m = 0.0f;
 #pragma unroll
-        for (int c = 0; c < 4; ++c) m = fmaxf(m, fmaxf(__builtin_fabsf(acc[r][c].x), __builtin_fabsf(acc[r][c].y)));
+        for (int c = 0; c < 4; ++c)
+          if (c >= c_lo) m = fmaxf(m, fmaxf(__builtin_fabsf(acc[r][c].x), __builtin_fabsf(acc[r][c].y)));
         mx[r] = m;
       }
       const size_t at = static_cast<size_t>(m0) + static_cast<size_t>(lane) * 4;
-      const unsigned octet = nb * static_cast<unsigned>(n_tile) + static_cast<unsigned>(wave) - ne;
-      *reinterpret_cast<f32x4 *>(hf + octet * hf_stride + at) = mx;
-      if (role == 2) {
-        const f32x4 av = {asum[0], asum[1], asum[2], asum[3]};
-        *reinterpret_cast<f32x4 *>(hf + 8u * nb * hf_stride + at) = av;
+      *reinterpret_cast<f32x4 *>(hf + static_cast<unsigned>(mw.plane) * hf_stride + at) = mx;
+      if (role >= 2 && role < kRoleHybrid)  // row role - 2 of the lane's four
+        hf[static_cast<unsigned>(mix_planes(static_cast<int>(ne), E)) * hf_stride + at + static_cast<unsigned>(role - 2)] = asum;
+      if (role != kRoleHybrid) return;
+      if constexpr (E != 0) {
+        // the coefficients of the exact run: 4 columns, on a multiple of 4
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const unsigned row = m0 + lane * 4 + r;
+          if (row >= M) continue;
+          float4 o;
+          o.x = mul_rn(acc[r][0].x, tb.norm); o.y = mul_rn(acc[r][0].y, tb.norm);
+          o.z = mul_rn(acc[r][1].x, tb.norm); o.w = mul_rn(acc[r][1].y, tb.norm);
+          *reinterpret_cast<float4 *>(coef + static_cast<size_t>(row) * kHopI + mw.col[0]) = o;
+        }
       }
       return;
     }
@@ -1267,23 +1460,28 @@ void k_mdct_fwd_st(DeviceTables tb, PcmView pcm, long long frame_begin, unsigned
   st_body<CH, PRIO, D, NW, BK, ABL, STAMP, false>(tb, pcm, frame_begin, M, coef, stamps, 0u, nullptr, 0ull);
 }
 
-// the mixed-role form (see st_body): ne exact waves, hf = [8 (16 - ne) + 1][hf_stride] floats
-template <int MINW, int CH = 0>
+// the mixed-role form (see st_body and mix_wave): E = exact pairs of the hybrid waves (0: none, waves [0, ne) exact),
+// hf = [mix_planes(ne, E) + 1][hf_stride] floats
+template <int MINW, int CH = 0, int E = 0>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(MINW, MINW)))
 void k_mdct_mix_st(DeviceTables tb, PcmView pcm, long long frame_begin, unsigned M, float *__restrict__ coef,
                    unsigned ne, float *__restrict__ hf, unsigned long long hf_stride) {
-  st_body<CH, 2, 4, 16, 16, 0, false, true>(tb, pcm, frame_begin, M, coef, nullptr, ne, hf, hf_stride);
+  st_body<CH, 2, 4, 16, 16, 0, false, true, E>(tb, pcm, frame_begin, M, coef, nullptr, ne, hf, hf_stride);
 }
 
+// hp: exact pairs of the hybrid waves, 0 or mix_hybrid_pairs(ne) (ScreenShape::hp: the workspace was sized for it)
 template <int CH>
 inline hipError_t launch_mix_st(const DeviceTables &t, const PcmView &pcm, uint64_t frame_begin, uint32_t M, float *coef,
-                                uint32_t ne, float *hf, uint64_t hf_stride, hipStream_t s) {
+                                uint32_t ne, uint32_t hp, float *hf, uint64_t hf_stride, hipStream_t s) {
   if (M == 0) return hipSuccess;
   if (CH != 0 && pcm.ch != static_cast<uint32_t>(CH)) return hipErrorInvalidValue;
   if (ne < 1 || ne > 15 || hf_stride < M || hf_stride % 256) return hipErrorInvalidValue;
-  const unsigned m_tiles = (M + 255) / 256;
-  hipLaunchKernelGGL((k_mdct_mix_st<4, CH>), dim3(m_tiles * 8), dim3(1024), 0, s, t, pcm,
-                     static_cast<long long>(frame_begin), M, coef, ne, hf, static_cast<unsigned long long>(hf_stride));
+  if (hp != 0 && hp != static_cast<uint32_t>(mix_hybrid_pairs(static_cast<int>(ne)))) return hipErrorInvalidValue;
+  const dim3 grid((M + 255) / 256 * 8), block(1024);
+  const long long fb = static_cast<long long>(frame_begin);
+  const unsigned long long st = hf_stride;
+  if (hp == 2) hipLaunchKernelGGL((k_mdct_mix_st<4, CH, 2>), grid, block, 0, s, t, pcm, fb, M, coef, ne, hf, st);
+  else hipLaunchKernelGGL((k_mdct_mix_st<4, CH, 0>), grid, block, 0, s, t, pcm, fb, M, coef, ne, hf, st);
   return hipGetLastError();
 }
 

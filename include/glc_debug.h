@@ -57,6 +57,13 @@ int glc_debug_set_encode_screen(glc_ctx *ctx, int mode);
 /* Rows the screened path has transformed since the context was created, and how many of them failed the screen
  * and were repaired.  Waits for the context's encode streams. */
 int glc_debug_encode_screen_stats(glc_ctx *ctx, uint64_t *rows_screened, uint64_t *rows_repaired);
+/* The layout a screened launch has at a rate whose last band starts in (64 (ne - 1), 64 ne], ne in 1..15: the exact
+ * column pairs of the transform's hybrid waves (0: none, waves [0, ne) are exact - csrc/glc_mdct_fwd.hpp mix_wave), the
+ * hf planes the transform writes and the quantiser reads (the A plane follows them), and the bytes of the workspace
+ * of a launch of `rows` rows: (planes + 1) planes of rows rounded up to 256 floats, one of row flags, a quarter of
+ * one of fail counts.  Host arithmetic only: no context, no device. */
+int glc_debug_encode_screen_layout(uint32_t ne, uint32_t rows, uint32_t *hybrid_pairs, uint32_t *planes,
+                                   uint64_t *workspace_bytes);
 
 /* Which transform repairs the rows of a screened launch that failed the screen (csrc/glc_kernels.h
  * launch_encode_screened):

@@ -7,11 +7,13 @@ reference accumulates with a separately rounded multiply and add.
                 (v_div_scale ... v_div_fixup), which the raw-frame path `i16 / 32767.0` needs
   k_mdct_mix_st (the mixed-role form of k_mdct_fwd_st)   v_pk_fma_f32 alone is allowed: its bound waves
                 accumulate an upper bound with it, never a coefficient; its exact waves run k_mdct_fwd_st's own multiply /
-                add block.  The i loop exists once per role (exact, bound, bound + A), each copy BK = 16 i-steps of
-                16 packed multiply-adds (a lane's 4 rows x 8 columns / 2): every instantiation may hold at most
-                2 x 256 v_pk_fma_f32 - the two bound copies - and must hold the exact copy's 256 v_pk_mul_f32 and
-                256 v_pk_add_f32, so a fused op in the exact role shows here as well as in the bit-exact parity of
-                tests/test_encode_screen.py
+                add block.  The i loop exists once per role - exact, bound, bound + A of row 0 / 1 / 2 / 3 and, in the
+                instantiations with E > 0 exact pairs per hybrid wave (the third template argument), hybrid - each copy
+                BK = 16 i-steps of 16 packed multiply-adds (a lane's 4 rows x 4 column pairs).  A hybrid copy holds
+                64 (4 - E) v_pk_fma_f32 and 64 E each of v_pk_mul_f32 and v_pk_add_f32.  Every instantiation may hold at
+                most 5 x 256 + 64 (4 - E) v_pk_fma_f32 (E = 0: 5 x 256) and must hold 256 + 64 E v_pk_mul_f32 and as many
+                v_pk_add_f32, so a fused op in an exact pair shows here as well as in the bit-exact parity of
+                tests/test_encode_screen.py and tests/test_encode_balance.py
 The quantiser / decision / overlap-add kernels are not scanned: their IEEE divide, sqrt and
 64-bit index division expand to FMA-based sequences by design.  The arithmetic of the quantiser and the
 raw-or-compressed decision is pinned instead by tests/test_quantizer_edges.py, which drives them with
@@ -30,6 +32,15 @@ KERNELS = ("k_mdct_fwd_sched", "k_mdct_fwd_dma", "k_mdct_fwd_st", "k_mdct_mix_st
 DIV_WINDOW = {"k_imdct_rows", "k_imdct_plan"}
 BOUND_FMA = re.compile(r"^\s+v_pk_fma_f32\b")  # the one fused op of k_mdct_mix_st's bound waves
 MIX_LOOP_MACS = 16 * 16  # packed multiply-adds in one copy of k_mdct_mix_st's i loop: BK i-steps x (4 rows x 8 columns / 2)
+MIX_BOUND_COPIES = 5     # bound, bound + A of row 0 .. 3
+MIX_NAME = re.compile(r"k_mdct_mix_stILi\d+ELi\d+ELi([0-3])EE")  # <MINW, CH, E>
+
+
+def mix_bounds(name):
+    """(v_pk_fma_f32 at most, v_pk_mul_f32 / v_pk_add_f32 at least) of an instantiation, from the E in its name."""
+    e = int(MIX_NAME.search(name).group(1))
+    per_pair = MIX_LOOP_MACS // 4      # one column pair of a copy: 16 i-steps x 4 rows
+    return MIX_BOUND_COPIES * MIX_LOOP_MACS + (per_pair * (4 - e) if e else 0), MIX_LOOP_MACS + per_pair * e
 
 
 def main() -> int:
@@ -71,16 +82,20 @@ def main() -> int:
             pk = re.match(r"^\s+v_pk_(fma|mul|add)_f32\b", line)
             if pk:
                 cur_mix[("fma", "mul", "add").index(pk.group(1))] += 1
-        if "s_endpgm" in line:
+        if line.startswith(".Lfunc_end"):  # (not s_endpgm: a kernel with an early return has blocks behind its first one)
             cur = None
     missing = set(KERNELS) - seen
     if missing:
         print("check_isa: kernels not found in ISA:", sorted(missing))
         return 1
     for name, (n_fma, n_mul, n_add) in mix.items():
-        if n_fma > 2 * MIX_LOOP_MACS or n_mul < MIX_LOOP_MACS or n_add < MIX_LOOP_MACS:
-            bad.append(("k_mdct_mix_st", f"{name}: {n_fma} v_pk_fma_f32 (at most {2 * MIX_LOOP_MACS}: the two bound copies), "
-                                         f"{n_mul} v_pk_mul_f32 / {n_add} v_pk_add_f32 (at least {MIX_LOOP_MACS} each: the exact copy)"))
+        if not MIX_NAME.search(name):
+            bad.append(("k_mdct_mix_st", f"{name}: no <MINW, CH, E> in the name"))
+            continue
+        fma_max, mul_min = mix_bounds(name)
+        if n_fma > fma_max or n_mul < mul_min or n_add < mul_min:
+            bad.append(("k_mdct_mix_st", f"{name}: {n_fma} v_pk_fma_f32 (at most {fma_max}: the bound copies and the hybrid copy's bound pairs), "
+                                         f"{n_mul} v_pk_mul_f32 / {n_add} v_pk_add_f32 (at least {mul_min} each: the exact copy and the hybrid copy's exact pairs)"))
     if bad:
         for k, l in bad:
             print(f"check_isa: fused op in {k}: {l}")
