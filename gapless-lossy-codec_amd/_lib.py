@@ -255,6 +255,15 @@ SIGNATURES = {
     "glc_decode_crops_device_store": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint64, _vp,
                                                 C.POINTER(GlcClipLayout)]),
     "glc_store_compact_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
+    "glc_encode_batch_device_compact_int": (C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.POINTER(GlcClipLayout), _vp, C.c_uint64, _vp, _vp]),
+    "glc_roundtrip_batch_device_pcm": (C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.POINTER(GlcClipLayout), _vp, C.c_int,
+                                                 C.POINTER(GlcClipLayout)]),
+    "glc_decode_batch_device_compact_i16": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _vp,
+                                                      C.POINTER(GlcClipLayout)]),
+    "glc_decode_crops_device_compact_i16": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                                      C.POINTER(GlcCrop), _vp, C.POINTER(GlcClipLayout)]),
+    "glc_decode_crops_device_store_i16": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint64, _vp,
+                                                    C.POINTER(GlcClipLayout)]),
     "glc_version": (C.c_char_p, []),
 }
 

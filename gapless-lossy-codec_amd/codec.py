@@ -382,6 +382,38 @@ def pcm_format(samples, bits: Optional[int] = None):
     return np.ascontiguousarray(samples).reshape(-1), fmt, bits or 32
 
 
+def _tensor_pcm_format(t, bits: Optional[int], what: str = "x"):
+    """(glc_pcm_format, bits) of a torch tensor handed to a device batch call: float32, or int16 / int32 holding
+    `bits`-bit values - the defaults and the checks pcm_format applies to integer arrays."""
+    import torch
+    formats = {torch.float32: (GLC_PCM_F32, 32), torch.int16: (GLC_PCM_S16, 16), torch.int32: (GLC_PCM_S32, 32)}
+    if getattr(t, "dtype", None) not in formats:
+        raise TypeError(f"{what} must be a float32, int16 or int32 CUDA tensor")
+    fmt, width = formats[t.dtype]
+    if fmt == GLC_PCM_F32:
+        if bits is not None:
+            raise TypeError("bits applies to integer samples only")
+        return fmt, 32
+    bits = width if bits is None else int(bits)
+    if not 1 <= bits <= width:
+        raise GlcError(GLC_EINVAL, f"bits must be 1..{width} for {t.dtype} samples")
+    return fmt, bits
+
+
+def _tensor_out_dtype(dtype, out):
+    """torch.float32 or torch.int16 for the output of a device batch decode: an `out` tensor of int16 selects the
+    format by itself; `dtype` (torch or numpy spelling) names it for a fresh output."""
+    import torch
+    if isinstance(out, torch.Tensor) and out.dtype == torch.int16:
+        return torch.int16
+    if dtype is None:
+        return torch.float32
+    name = str(dtype).replace("torch.", "") if isinstance(dtype, torch.dtype) else np.dtype(dtype).name
+    if name not in ("float32", "int16"):
+        raise TypeError(f"dtype must be float32 or int16, not {dtype}")
+    return getattr(torch, name)
+
+
 class _Ctx:
     def __init__(self, sample_rate: int, device: int):
         h = C.c_void_p()
@@ -631,7 +663,7 @@ class Encoder(_Ctx):
             self.set_stream(0)
         return blob[:info.bytes], info
 
-    def encode_compact_batch_tensor(self, x, lengths=None, planar: bool = True, arena=None, cursor=None):
+    def encode_compact_batch_tensor(self, x, lengths=None, planar: bool = True, arena=None, cursor=None, bits: Optional[int] = None):
         """Encode every clip of a padded batch into its own compact blob, the blobs back to back in an arena the
         DEVICE allocates from (glc_encode_batch_device_compact).  `x`: a float32 CUDA tensor (B, C, T) (planar) or
         (B, T, C), innermost stride 1, any slice of something bigger; lengths: per clip its true samples per channel
@@ -643,10 +675,14 @@ class Encoder(_Ctx):
         (store_blobs cuts them).  A clip that does not fit is not stored, and the cursor counts on: its final value
         is the arena size that would have sufficed.  Queued on torch's current stream as RoundTrip.apply_batch_tensor
         queues; nothing is copied to the host and the C call does not synchronise (restoring the context's private
-        stream afterwards waits for the queued work, as in every *_tensor method)."""
+        stream afterwards waits for the queued work, as in every *_tensor method).
+        An int16 / int32 tensor holds `bits`-bit integer PCM (default: the container's width; the checks of
+        Encoder.encode): glc_encode_batch_device_compact_int widens it in the gather, and the blobs are those of the
+        widened clips, byte for byte."""
         import torch
-        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 3:
-            raise TypeError("x must be a float32 CUDA tensor of shape (B, C, T) or (B, T, C)")
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in (torch.float32, torch.int16, torch.int32) or x.dim() != 3:
+            raise TypeError("x must be a float32 (or int16 / int32) CUDA tensor of shape (B, C, T) or (B, T, C)")
+        fmt, bits = _tensor_pcm_format(x, bits)
         if x.device.index != self.device:
             raise GlcError(GLC_EINVAL, f"x is on {x.device}, this context on device {self.device}")
         if x.shape[2] > 1 and x.stride(2) != 1:
@@ -679,9 +715,14 @@ class Encoder(_Ctx):
         entries = torch.zeros((b, 4), dtype=torch.int64, device=x.device)
         self._enter_torch_stream(x.device)
         try:
-            check(lib.glc_encode_batch_device_compact(self._h, C.c_void_p(x.data_ptr()), C.byref(lay), C.c_void_p(arena.data_ptr()),
-                                                      arena.numel(), C.c_void_p(cursor.data_ptr()),
-                                                      C.c_void_p(entries.data_ptr())), self._h)
+            if fmt == GLC_PCM_F32:
+                check(lib.glc_encode_batch_device_compact(self._h, C.c_void_p(x.data_ptr()), C.byref(lay), C.c_void_p(arena.data_ptr()),
+                                                          arena.numel(), C.c_void_p(cursor.data_ptr()),
+                                                          C.c_void_p(entries.data_ptr())), self._h)
+            else:
+                check(lib.glc_encode_batch_device_compact_int(self._h, C.c_void_p(x.data_ptr()), fmt, bits, C.byref(lay),
+                                                              C.c_void_p(arena.data_ptr()), arena.numel(),
+                                                              C.c_void_p(cursor.data_ptr()), C.c_void_p(entries.data_ptr())), self._h)
         finally:
             self.set_stream(0)
         return arena, cursor, entries
@@ -837,17 +878,18 @@ class Decoder(_Ctx):
             self.set_stream(0)
         return out[:n]
 
-    def _batch_out(self, blobs, lens, planar: bool, out):
+    def _batch_out(self, blobs, lens, planar: bool, out, dtype=None):
         """The output tensor of a decode_compact_* batch call (None: a new zero-filled one of T = max(lens)), checked,
         and its glc_clip_layout (with the array the layout points into, to be kept alive)."""
         import torch
         b, ch = len(blobs), self.channels
+        dtype = _tensor_out_dtype(dtype, out)
         if out is None:
             t_max = max(lens, default=0)
             dev = blobs[0].device if b else torch.device("cuda", self.device)
-            out = torch.zeros((b, ch, t_max) if planar else (b, t_max, ch), dtype=torch.float32, device=dev)
-        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32 or out.dim() != 3:
-            raise TypeError("out must be a float32 CUDA tensor of shape (B, C, T) or (B, T, C)")
+            out = torch.zeros((b, ch, t_max) if planar else (b, t_max, ch), dtype=dtype, device=dev)
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != dtype or out.dim() != 3:
+            raise TypeError("out must be a float32 (or, dtype=torch.int16, an int16) CUDA tensor of shape (B, C, T) or (B, T, C)")
         if out.device.index != self.device:
             raise GlcError(GLC_EINVAL, f"out is on {out.device}, this context on device {self.device}")
         if out.shape[2] > 1 and out.stride(2) != 1:
@@ -866,14 +908,16 @@ class Decoder(_Ctx):
                             C.cast(lens_arr, C.POINTER(C.c_uint64)))
         return out, lay, lens_arr
 
-    def decode_compact_batch_tensor(self, blobs, n_samples, lengths=None, planar: bool = True, out=None):
+    def decode_compact_batch_tensor(self, blobs, n_samples, lengths=None, planar: bool = True, out=None, dtype=None):
         """Decode one compact blob per clip into ONE padded batch tensor (glc_decode_batch_device_compact).  blobs: B
         1-D uint8 CUDA tensors (64-byte aligned, anywhere in device memory); n_samples: per clip its interleaved
         length; lengths: per clip its samples per channel (default n_samples[i] // channels).  out: a float32 CUDA
         tensor (B, C, T) (planar) or (B, T, C) with innermost stride 1 - a slice of something bigger works - or
         None: a new zero-filled one with T = max(lengths).  The first lengths[i] samples of clip i are what
         decode_compact_tensor gives for that blob; no other element is written.  One launch chain per round
-        whatever B.  Queued on torch's current stream; returns the output."""
+        whatever B.  Queued on torch's current stream; returns the output.
+        dtype=torch.int16 (or an int16 `out`, which selects the format by itself): 16-bit PCM narrowed on the device as
+        decode(dtype=np.int16) narrows (glc_decode_batch_device_compact_i16)."""
         b = len(blobs)
         ch = self.channels
         ns = [int(v) for v in (n_samples.tolist() if hasattr(n_samples, "tolist") else n_samples)]
@@ -882,20 +926,21 @@ class Decoder(_Ctx):
         if len(ns) != b or len(lens) != b:
             raise GlcError(GLC_EINVAL, f"n_samples and lengths must hold {b} values")
         blobs = [self._blob_tensor(t, f"blobs[{i}]", self.device) for i, t in enumerate(blobs)]
-        out, lay, _keep = self._batch_out(blobs, lens, planar, out)
+        out, lay, _keep = self._batch_out(blobs, lens, planar, out, dtype)
         ptrs = (C.c_void_p * max(b, 1))(*[t.data_ptr() for t in blobs])
         sizes = (C.c_uint64 * max(b, 1))(*[t.numel() for t in blobs])
         ns_arr = (C.c_uint64 * max(b, 1))(*ns)
+        call = lib.glc_decode_batch_device_compact_i16 if out.dtype.itemsize == 2 else lib.glc_decode_batch_device_compact
         self._enter_torch_stream(out.device)
         try:
-            check(lib.glc_decode_batch_device_compact(self._h, ptrs, sizes, ns_arr, C.c_void_p(out.data_ptr()), C.byref(lay)),
+            check(call(self._h, ptrs, sizes, ns_arr, C.c_void_p(out.data_ptr()), C.byref(lay)),
                   self._h)
         finally:
             self.set_stream(0)
         self._compact_clips = b
         return out
 
-    def decode_compact_crops_tensor(self, blobs, n_samples, starts, lengths, planar: bool = True, out=None):
+    def decode_compact_crops_tensor(self, blobs, n_samples, starts, lengths, planar: bool = True, out=None, dtype=None):
         """Decode a WINDOW of each of B stored clips into one padded batch tensor (glc_decode_crops_device_compact):
         entry i is samples [starts[i], starts[i] + lengths[i]) per channel of what decode_compact_tensor gives for
         blobs[i] (n_samples[i] its interleaved length), bit for bit; only the frames a window needs are decoded.
@@ -903,7 +948,8 @@ class Decoder(_Ctx):
         decode_compact_batch_tensor ((B, C, L) planar / (B, L, C), a slice of something bigger works), or None: a
         new zero-filled one with L = max(lengths).  No element outside the crops is written.  One launch chain per
         round whatever B.  Queued on torch's current stream; returns the output.  last_compact_status() afterwards:
-        one status per crop, bad rows counted inside the window (in the stream's row numbering)."""
+        one status per crop, bad rows counted inside the window (in the stream's row numbering).
+        dtype=torch.int16 (or an int16 `out`): the crops as 16-bit PCM (glc_decode_crops_device_compact_i16)."""
         b = len(blobs)
         as_ints = lambda v: [int(x) for x in (v.tolist() if hasattr(v, "tolist") else v)]
         ns, st = as_ints(n_samples), as_ints(starts)
@@ -913,14 +959,15 @@ class Decoder(_Ctx):
         if any(v < 0 for v in st):
             raise GlcError(GLC_EINVAL, "starts must not be negative")
         blobs = [self._blob_tensor(t, f"blobs[{i}]", self.device) for i, t in enumerate(blobs)]
-        out, lay, _keep = self._batch_out(blobs, lens, planar, out)
+        out, lay, _keep = self._batch_out(blobs, lens, planar, out, dtype)
         ptrs = (C.c_void_p * max(b, 1))(*[t.data_ptr() for t in blobs])
         sizes = (C.c_uint64 * max(b, 1))(*[t.numel() for t in blobs])
         ns_arr = (C.c_uint64 * max(b, 1))(*ns)
+        call = lib.glc_decode_crops_device_compact_i16 if out.dtype.itemsize == 2 else lib.glc_decode_crops_device_compact
         crops = (GlcCrop * max(b, 1))(*[GlcCrop(a, n) for a, n in zip(st, lens)])
         self._enter_torch_stream(out.device)
         try:
-            check(lib.glc_decode_crops_device_compact(self._h, ptrs, sizes, ns_arr, crops, C.c_void_p(out.data_ptr()), C.byref(lay)),
+            check(call(self._h, ptrs, sizes, ns_arr, crops, C.c_void_p(out.data_ptr()), C.byref(lay)),
                   self._h)
         finally:
             self.set_stream(0)
@@ -928,7 +975,7 @@ class Decoder(_Ctx):
         return out
 
     def decode_store_crops_tensor(self, arena, entries, lengths, clips, starts, length: int, max_length: int,
-                                  planar: bool = True, out=None):
+                                  planar: bool = True, out=None, dtype=None):
         """Draw B crops of `length` samples per channel from the store as Encoder.encode_compact_batch_tensor left it
         (glc_decode_crops_device_store): crop i is samples [starts[i], starts[i] + length) of stored clip clips[i].
         arena: the uint8 CUDA tensor; entries: the (N, 4) int64 CUDA tensor the encode returned, or torch.cat of
@@ -939,9 +986,11 @@ class Decoder(_Ctx):
         bigger works - or None: a new zero-filled one.  Every usable crop is bit for bit decode_compact_crops_tensor's;
         a crop whose entry (flag 64) or selection (flag 128) is unusable is +0.0.  No element outside the crops is
         written.  Queued on torch's current stream; returns the output.  last_compact_status() afterwards: one
-        status per crop."""
+        status per crop.  dtype=torch.int16 (or an int16 `out`): the crops as 16-bit PCM, an unusable one 0
+        (glc_decode_crops_device_store_i16)."""
         import torch
         ch = self.channels
+        dtype = _tensor_out_dtype(dtype, out)
 
         def index(t, name, shape_tail=()):
             if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int64 or not t.is_contiguous() \
@@ -964,9 +1013,9 @@ class Decoder(_Ctx):
         if length < 0 or max_length < 0:
             raise GlcError(GLC_EINVAL, "length and max_length must not be negative")
         if out is None:
-            out = torch.zeros((b, ch, length) if planar else (b, length, ch), dtype=torch.float32, device=arena.device)
-        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32 or out.dim() != 3:
-            raise TypeError("out must be a float32 CUDA tensor of shape (B, C, T) or (B, T, C)")
+            out = torch.zeros((b, ch, length) if planar else (b, length, ch), dtype=dtype, device=arena.device)
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != dtype or out.dim() != 3:
+            raise TypeError("out must be a float32 (or, dtype=torch.int16, an int16) CUDA tensor of shape (B, C, T) or (B, T, C)")
         if out.device.index != self.device:
             raise GlcError(GLC_EINVAL, f"out is on {out.device}, this context on device {self.device}")
         if out.shape[2] > 1 and out.stride(2) != 1:
@@ -979,12 +1028,13 @@ class Decoder(_Ctx):
         if not planar and ot > 1 and out.stride(1) != ch:
             raise TypeError(f"out: an interleaved clip must be dense (stride {ch} between samples)")
         lay = GlcClipLayout(b, ch, 1 if planar else 0, out.stride(0), out.stride(1) if planar else 0, length, None)
+        call = lib.glc_decode_crops_device_store_i16 if dtype == torch.int16 else lib.glc_decode_crops_device_store
         self._enter_torch_stream(out.device)
         try:
-            check(lib.glc_decode_crops_device_store(self._h, C.c_void_p(arena.data_ptr()), arena.numel(),
-                                                    C.c_void_p(entries.data_ptr()), C.c_void_p(lengths.data_ptr()), entries.shape[0],
-                                                    max_length, C.c_void_p(clips.data_ptr()), C.c_void_p(starts.data_ptr()), length,
-                                                    C.c_void_p(out.data_ptr()), C.byref(lay)), self._h)
+            check(call(self._h, C.c_void_p(arena.data_ptr()), arena.numel(),
+                       C.c_void_p(entries.data_ptr()), C.c_void_p(lengths.data_ptr()), entries.shape[0],
+                       max_length, C.c_void_p(clips.data_ptr()), C.c_void_p(starts.data_ptr()), length,
+                       C.c_void_p(out.data_ptr()), C.byref(lay)), self._h)
         finally:
             self.set_stream(0)
         self._compact_clips = b
@@ -1102,7 +1152,8 @@ class RoundTrip(_Ctx):
         assert n == x.numel()
         return out
 
-    def apply_batch_tensor(self, x, lengths=None, planar: bool = True, out=None, out_planar: Optional[bool] = None):
+    def apply_batch_tensor(self, x, lengths=None, planar: bool = True, out=None, out_planar: Optional[bool] = None,
+                           bits: Optional[int] = None, out_dtype=None):
         """The round trip of every clip of a padded batch in one call (glc_roundtrip_batch_device).  `x`: a float32
         CUDA tensor of shape (B, C, T) (planar) or (B, T, C), innermost stride 1; the other strides are taken from
         the tensor, so a slice of something bigger works without a copy.  lengths: per clip its true number of
@@ -1111,13 +1162,19 @@ class RoundTrip(_Ctx):
         for that clip alone; no other element of it is written.
         out: None - a new tensor like x, zero-filled, so the padding behind short clips is zero; x itself - in
         place; or a float32 CUDA tensor of its own, whose layout is out_planar (default: as `planar`) and which
-        must not overlap x.  Queued on torch's current stream as apply_tensor queues; returns the output."""
+        must not overlap x.  Queued on torch's current stream as apply_tensor queues; returns the output.
+        An int16 / int32 `x` holds `bits`-bit integer PCM (default: the container's width), widened on the device as
+        Encoder.encode widens it; out_dtype (torch.float32, the default, or torch.int16; an int16 `out` selects it by
+        itself) is the output's format, int16 narrowed as Decoder.decode(dtype=np.int16) narrows
+        (glc_roundtrip_batch_device_pcm).  In place needs the same format on both sides."""
         import torch
         out_planar = planar if out_planar is None else bool(out_planar)
+        fmt, bits = _tensor_pcm_format(x, bits)
+        out_dtype = _tensor_out_dtype(out_dtype, out)
 
         def layout(t, is_planar, what):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-                raise TypeError(f"{what} must be a float32 CUDA tensor")
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != (out_dtype if what == "out" else x.dtype):
+                raise TypeError(f"{what} must be a {'float32 or int16' if what == 'out' else 'float32, int16 or int32'} CUDA tensor")
             if t.dim() != 3:
                 raise TypeError(f"{what} must have shape (B, C, T) or (B, T, C)")
             if t.shape[2] > 1 and t.stride(2) != 1:
@@ -1143,7 +1200,8 @@ class RoundTrip(_Ctx):
             arr = (C.c_uint64 * max(b, 1))(*lens)
             lin.lengths = C.cast(arr, C.POINTER(C.c_uint64))
         if out is None:
-            out = torch.zeros_like(x) if planar == out_planar else torch.zeros_like(x.transpose(1, 2), memory_format=torch.contiguous_format)
+            out = torch.zeros_like(x, dtype=out_dtype) if planar == out_planar else \
+                torch.zeros_like(x.transpose(1, 2), dtype=out_dtype, memory_format=torch.contiguous_format)
         want = tuple(x.shape) if planar == out_planar else (x.shape[0], x.shape[2], x.shape[1])
         lout, _ = layout(out, out_planar, "out")
         if tuple(out.shape) != want:
@@ -1151,8 +1209,13 @@ class RoundTrip(_Ctx):
         lout.lengths = lin.lengths
         self.set_stream(torch.cuda.current_stream(x.device).cuda_stream)
         try:
-            check(lib.glc_roundtrip_batch_device(self._h, C.c_void_p(x.data_ptr()), C.byref(lin), C.c_void_p(out.data_ptr()),
-                                                 C.byref(lout)), self._h)
+            if fmt == GLC_PCM_F32 and out_dtype == torch.float32:
+                check(lib.glc_roundtrip_batch_device(self._h, C.c_void_p(x.data_ptr()), C.byref(lin), C.c_void_p(out.data_ptr()),
+                                                     C.byref(lout)), self._h)
+            else:
+                check(lib.glc_roundtrip_batch_device_pcm(self._h, C.c_void_p(x.data_ptr()), fmt, bits, C.byref(lin),
+                                                         C.c_void_p(out.data_ptr()),
+                                                         GLC_PCM_S16 if out_dtype == torch.int16 else GLC_PCM_F32, C.byref(lout)), self._h)
         finally:
             self.set_stream(0)
         self._batch_clips = b

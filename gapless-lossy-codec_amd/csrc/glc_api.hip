@@ -2220,16 +2220,17 @@ int rt_emit_hops(glc_ctx *ctx, const RtGeom &g, uint64_t h0, uint64_t h1, T *d_o
 // slot 0 for the next round.  `stats`: device counters of glc_roundtrip_last_info, or null.
 // `sink` (glc_roundtrip_batch_device, a clip longer than a round): the round's hops go through the strided
 // overlap-add by these descriptors (block slots counted in the ring) instead of into a contiguous d_out.
+template <typename T>
 struct RtStridedSink {
   const glc::HopDescStrided *desc;
   uint32_t n_desc;
   bool planar;
-  float *out;
+  T *out;  // float, or int16_t: the strided overlap-add narrows on the way out
 };
 // ... from row `row0` on of row tables that are on the device (R1 of the round's records, or R2 of a whole blob)
 template <typename T>
 int rt_decode_round_rows(glc_ctx *ctx, const RtGeom &g, const glc::DecodeRows &rows, uint32_t row0, uint64_t f0, uint64_t nf,
-                         T *d_out, const RtStridedSink *sink) {
+                         T *d_out, const RtStridedSink<T> *sink) {
   const size_t slot = static_cast<size_t>(g.ch) * glc::kFrame;
   float *blocks = static_cast<float *>(ctx->blocks.p);
   const uint32_t M = static_cast<uint32_t>(nf * g.ch);
@@ -2248,7 +2249,7 @@ int rt_decode_round_rows(glc_ctx *ctx, const RtGeom &g, const glc::DecodeRows &r
 }
 template <typename T>
 int rt_decode_round(glc_ctx *ctx, const RtGeom &g, const uint8_t *recs, uint64_t f0, uint64_t nf, uint64_t *stats, T *d_out,
-                    const RtStridedSink *sink = nullptr) {
+                    const RtStridedSink<T> *sink = nullptr) {
   glc::DecodeRows rows{};
   GLC_HIP(ctx, glc::launch_rows_from_records(recs, static_cast<uint32_t>(nf * g.ch), g.ch, ctx->rt_rows.p, stats, ctx->stream, &rows));
   return rt_decode_round_rows(ctx, g, rows, 0, f0, nf, d_out, sink);
@@ -2285,7 +2286,7 @@ int rt_check(glc_ctx *ctx, const char *who, uint64_t n_samples, uint16_t channel
 // buffer, then rt_decode_round of it.
 template <typename T>
 int rt_roundtrip_round(glc_ctx *ctx, const RtGeom &g, const float *d_pcm, uint64_t n_samples, uint64_t f0, uint64_t nf, T *d_out,
-                       uint64_t *stats, const RtStridedSink *sink = nullptr) {
+                       uint64_t *stats, const RtStridedSink<T> *sink = nullptr) {
   const uint64_t t_count = (n_samples + g.ch - 1) / g.ch;
   int rc = encode_range_on(ctx, ctx->stream, ctx->coef, d_pcm, 0, t_count, n_samples, static_cast<uint16_t>(g.ch), f0, f0 + nf,
                            ctx->rt_records.p, nullptr);
@@ -2549,7 +2550,38 @@ struct RtbLayout {
     return planes() == o.planes() && (l->n_clips <= 1 || l->clip_stride == o.l->clip_stride) &&
            (!planes() || l->channel_stride == o.l->channel_stride);
   }
+  // The bytes [p, p + extent() * elem) of the batch at `p`, whose elements are `elem` bytes wide: overlap is judged on
+  // BYTES, the layouts of a call may count elements of different widths.
+  uintptr_t end_of(const void *p, size_t elem) const { return reinterpret_cast<uintptr_t>(p) + extent() * elem; }
 };
+
+// The input of a batch call: device samples of `fmt` (`bits` wide for the integer formats), the layout counting
+// elements of that type.  S1 widens the integers in its gather (glc::launch_stage_clips_int).
+struct RtbPcm {
+  const void *p;
+  glc_pcm_format fmt;
+  uint32_t bits;
+  size_t elem() const { return fmt == GLC_PCM_S16 ? 2 : 4; }
+};
+
+int rtb_stage(glc_ctx *ctx, const RtbPcm &pcm, const glc::StageClip *clips, uint64_t n_clips, uint32_t ch, const RtbLayout &in, uint64_t V,
+              float *vs, hipStream_t st) {
+  if (pcm.fmt == GLC_PCM_F32)
+    GLC_HIP(ctx, glc::launch_stage_clips(static_cast<const float *>(pcm.p), clips, static_cast<uint32_t>(n_clips), ch, in.planes(),
+                                         in.l->channel_stride, static_cast<uint32_t>(V), vs, st));
+  else
+    GLC_HIP(ctx, glc::launch_stage_clips_int(pcm.p, pcm.fmt == GLC_PCM_S32, pcm.bits, clips, static_cast<uint32_t>(n_clips), ch, in.planes(),
+                                             in.l->channel_stride, static_cast<uint32_t>(V), vs, st));
+  return GLC_OK;
+}
+
+// What the integer twins check of `fmt` and `bits`, as glc_encode_int does.
+int rtb_check_fmt(glc_ctx *ctx, const std::string &w, glc_pcm_format fmt, uint32_t bits) {
+  if (fmt != GLC_PCM_S16 && fmt != GLC_PCM_S32 && fmt != GLC_PCM_F32) return fail(ctx, GLC_EINVAL, w + ": unknown sample format");
+  if (fmt != GLC_PCM_F32 && (bits == 0 || bits > (fmt == GLC_PCM_S16 ? 16u : 32u)))
+    return fail(ctx, GLC_EINVAL, w + ": bits must be 1..16 for 16-bit samples, 1..32 for 32-bit ones");
+  return GLC_OK;
+}
 
 // A round of the batch round trip: clips [first, first + n) packed into one virtual stream, or (lng) ONE clip
 // longer than a round, staged whole and sent through rounds with the carried overlap.
@@ -2620,7 +2652,8 @@ int rtb_check_clip(glc_ctx *ctx, const std::string &clip, const RtbLayout &l, ui
   return GLC_OK;
 }
 
-int rtb_impl(glc_ctx *ctx, const float *d_pcm, const RtbLayout &in, float *d_out, const RtbLayout &out) {
+template <typename Out>  // float, or int16_t: D2 narrows
+int rtb_impl(glc_ctx *ctx, const RtbPcm &pcm, const RtbLayout &in, Out *d_out, const RtbLayout &out) {
   const uint64_t n = in.l->n_clips;
   const uint32_t ch = in.l->channels;
   const uint64_t per_hop = uint64_t(glc::kHop) * ch, rec = glc::record_bytes(ch);
@@ -2701,8 +2734,8 @@ int rtb_impl(glc_ctx *ctx, const float *d_pcm, const RtbLayout &in, float *d_out
   for (const RtbRound &r : rounds) {
     const auto *clips = reinterpret_cast<const glc::StageClip *>(d_tab + r.o_clips);
     const auto *desc = reinterpret_cast<const glc::HopDescStrided *>(d_tab + r.o_desc);
-    GLC_HIP(ctx, glc::launch_stage_clips(d_pcm, clips, static_cast<uint32_t>(r.n), ch, in.planes(), in.l->channel_stride,
-                                         static_cast<uint32_t>(r.V), vs, st));
+    rc = rtb_stage(ctx, pcm, clips, r.n, ch, in, r.V, vs, st);
+    if (rc != GLC_OK) return rc;
     if (r.lng) {
       const uint64_t i = r.first, n_samples = in.len(i) * ch;
       const RtGeom g = rt_geom(r.n_real, ch, plans[i], n_samples);
@@ -2711,8 +2744,8 @@ int rtb_impl(glc_ctx *ctx, const float *d_pcm, const RtbLayout &in, float *d_out
         // the round's descriptors: those of hops [f0, f1 (+ 1)) that keep anything - all but none, since only the
         // tail hop can lie wholly behind the kept samples
         const uint64_t nd = count_hop_descs(g.trim, per_hop, f0, f1 + (f1 == g.n_frames ? 1 : 0));
-        const RtStridedSink sink{desc, static_cast<uint32_t>(nd), out_planes, d_out};
-        rc = rt_roundtrip_round<float>(ctx, g, vs, n_samples, f0, nf, nullptr, d_stats + r.stat_off, &sink);
+        const RtStridedSink<Out> sink{desc, static_cast<uint32_t>(nd), out_planes, d_out};
+        rc = rt_roundtrip_round<Out>(ctx, g, vs, n_samples, f0, nf, nullptr, d_stats + r.stat_off, &sink);
         if (rc != GLC_OK) return rc;
         desc += nd;
       }
@@ -2741,18 +2774,22 @@ int rtb_impl(glc_ctx *ctx, const float *d_pcm, const RtbLayout &in, float *d_out
 }  // namespace
 }  // extern "C++"
 
-int glc_roundtrip_batch_device(glc_ctx *ctx, const float *d_pcm, const glc_clip_layout *in, float *d_out,
-                               const glc_clip_layout *out) {
-  const char *who = "glc_roundtrip_batch_device";
+// glc_roundtrip_batch_device and glc_roundtrip_batch_device_pcm: the checks, then rtb_impl.
+static int rtb_call(glc_ctx *ctx, const char *who, const void *d_pcm, glc_pcm_format fmt, uint32_t bits, const glc_clip_layout *in,
+                    void *d_out, glc_pcm_format out_fmt, const glc_clip_layout *out) {
   const std::string w(who);
   if (!ctx) return GLC_EINVAL;
   if (!in || !out) return fail(ctx, GLC_EINVAL, w + ": null argument");
+  if (const int rc = rtb_check_fmt(ctx, w, fmt, bits)) return rc;
+  if (out_fmt != GLC_PCM_F32 && out_fmt != GLC_PCM_S16) return fail(ctx, GLC_EINVAL, w + ": the output is GLC_PCM_F32 or GLC_PCM_S16");
   if (in->n_clips != out->n_clips || in->channels != out->channels)
     return fail(ctx, GLC_EINVAL, w + ": the two layouts differ in the number of clips or channels");
   if (in->n_clips == 0) return GLC_OK;
   if (!d_pcm || !d_out) return fail(ctx, GLC_EINVAL, w + ": null argument");
   if (in->channels == 0) return fail(ctx, GLC_EINVAL, w + ": channels == 0");
-  if ((reinterpret_cast<uintptr_t>(d_pcm) | reinterpret_cast<uintptr_t>(d_out)) & 3u)
+  const RtbPcm pcm{d_pcm, fmt, bits};
+  const size_t in_elem = pcm.elem(), out_elem = out_fmt == GLC_PCM_S16 ? 2 : 4;
+  if ((reinterpret_cast<uintptr_t>(d_pcm) & (in_elem - 1u)) | (reinterpret_cast<uintptr_t>(d_out) & (out_elem - 1u)))
     return fail(ctx, GLC_EINVAL, w + ": a pointer is not aligned to its sample size");
   const RtbLayout li{in}, lo{out};
   const uint64_t n = in->n_clips;
@@ -2763,17 +2800,28 @@ int glc_roundtrip_batch_device(glc_ctx *ctx, const float *d_pcm, const glc_clip_
       if (const int rc = rtb_check_clip(ctx, clip, *l, i)) return rc;
   }
   {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_pcm), a1 = a0 + li.extent() * sizeof(float);
-    const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_out), b1 = b0 + lo.extent() * sizeof(float);
-    if (a0 < b1 && b0 < a1 && !(a0 == b0 && li.same_as(lo)))
-      return fail(ctx, GLC_EINVAL, w + ": input and output overlap (in place needs the same pointer and the same layout)");
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_pcm), a1 = li.end_of(d_pcm, in_elem);
+    const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_out), b1 = lo.end_of(d_out, out_elem);
+    if (a0 < b1 && b0 < a1 && !(a0 == b0 && li.same_as(lo) && fmt == out_fmt))
+      return fail(ctx, GLC_EINVAL, w + ": input and output overlap (in place needs the same pointer, the same layout and the same format)");
   }
   DeviceGuard guard(ctx->device);
   try {  // no C++ exception may cross the C ABI
-    return rtb_impl(ctx, d_pcm, li, d_out, lo);
+    return out_fmt == GLC_PCM_S16 ? rtb_impl(ctx, pcm, li, static_cast<int16_t *>(d_out), lo)
+                                  : rtb_impl(ctx, pcm, li, static_cast<float *>(d_out), lo);
   } catch (const std::bad_alloc &) {
     return fail(ctx, GLC_ENOMEM, w + ": host allocation failed");
   }
+}
+
+int glc_roundtrip_batch_device(glc_ctx *ctx, const float *d_pcm, const glc_clip_layout *in, float *d_out,
+                               const glc_clip_layout *out) {
+  return rtb_call(ctx, "glc_roundtrip_batch_device", d_pcm, GLC_PCM_F32, 32, in, d_out, GLC_PCM_F32, out);
+}
+
+int glc_roundtrip_batch_device_pcm(glc_ctx *ctx, const void *d_pcm, glc_pcm_format fmt, uint32_t bits, const glc_clip_layout *in,
+                                   void *d_out, glc_pcm_format out_fmt, const glc_clip_layout *out) {
+  return rtb_call(ctx, "glc_roundtrip_batch_device_pcm", d_pcm, fmt, bits, in, d_out, out_fmt, out);
 }
 
 int glc_roundtrip_batch_last_info(glc_ctx *ctx, glc_roundtrip_info *infos, uint64_t n_clips) {
@@ -2817,8 +2865,9 @@ int cd_check_blob(glc_ctx *ctx, const std::string &who, const void *d_blob, uint
 
 // A blob of `nf` frames through R2 (one pass over all its rows, tables in rt_rows) and the rounds of the family.
 // `win` (a crop, g.trim what it keeps): the windowed R2 over the window's rows, and the rounds of its frames only.
+template <typename T>
 int cd_decode_one(glc_ctx *ctx, const RtGeom &g, const void *d_blob, uint64_t blob_bytes, glc::CompactStatus *d_status,
-                  float *d_out, const glc::HopDescStrided *desc, bool planar, float *sink_out, const glc_crop_plan *win = nullptr) {
+                  T *d_out, const glc::HopDescStrided *desc, bool planar, T *sink_out, const glc_crop_plan *win = nullptr) {
   const uint64_t fb = win ? win->first_frame : 0, fe = win ? fb + win->n_frames : g.n_frames;
   const uint32_t M = static_cast<uint32_t>((fe - fb) * g.ch), M_blob = static_cast<uint32_t>(g.n_frames * g.ch);
   const size_t slot = static_cast<size_t>(g.ch) * glc::kFrame;
@@ -2839,9 +2888,9 @@ int cd_decode_one(glc_ctx *ctx, const RtGeom &g, const void *d_blob, uint64_t bl
     const uint64_t nf = std::min(g.round, fe - f0), f1 = f0 + nf;
     // the round's descriptors: those of hops [f0, f1 (+ 1)) that keep anything (rtb_impl)
     const uint64_t nd = desc ? count_hop_descs(g.trim, g.per_hop, f0, f1 + (f1 == g.n_frames ? 1 : 0)) : 0;
-    const RtStridedSink sink{desc, static_cast<uint32_t>(nd), planar, sink_out};
+    const RtStridedSink<T> sink{desc, static_cast<uint32_t>(nd), planar, sink_out};
     if (desc) desc += nd;
-    rc = rt_decode_round_rows<float>(ctx, g, rows, static_cast<uint32_t>((f0 - fb) * g.ch), f0, nf, d_out, desc ? &sink : nullptr);
+    rc = rt_decode_round_rows<T>(ctx, g, rows, static_cast<uint32_t>((f0 - fb) * g.ch), f0, nf, d_out, desc ? &sink : nullptr);
     if (rc != GLC_OK) return rc;
   }
   return GLC_OK;
@@ -2858,7 +2907,8 @@ struct CdRound {
 
 // `crops` / `wins` (both or neither; glc_decode_crops_device_compact): entry i is the window wins[i] = plan_crop of
 // crops[i] of its blob - a round counts, tabulates and transforms the windows' frames only.
-int cdb_impl(glc_ctx *ctx, const char *who, const void *const *d_blobs, const uint64_t *blob_bytes, float *d_out, const RtbLayout &out,
+template <typename T>
+int cdb_impl(glc_ctx *ctx, const char *who, const void *const *d_blobs, const uint64_t *blob_bytes, T *d_out, const RtbLayout &out,
              const std::vector<glc_plan> &plans, const glc_crop *crops = nullptr, const glc_crop_plan *wins = nullptr) {
   const uint64_t n = out.l->n_clips;
   auto frames_of = [&](uint64_t i) { return wins ? wins[i].n_frames : plans[i].n_frames; };
@@ -2955,7 +3005,7 @@ int cdb_impl(glc_ctx *ctx, const char *who, const void *const *d_blobs, const ui
       const uint64_t i = r.first;
       RtGeom g = rt_geom(plans[i].n_frames, ch, plans[i], out.len(i) * ch);
       g.trim = trim_of(i);
-      rc = cd_decode_one(ctx, g, d_blobs[i], blob_bytes[i], d_status + i, nullptr, desc, out_planes, d_out, wins ? &wins[i] : nullptr);
+      rc = cd_decode_one<T>(ctx, g, d_blobs[i], blob_bytes[i], d_status + i, nullptr, desc, out_planes, d_out, wins ? &wins[i] : nullptr);
       if (rc != GLC_OK) return rc;
       continue;
     }
@@ -3012,21 +3062,24 @@ int glc_decode_device_compact(glc_ctx *ctx, const void *d_blob, uint64_t blob_by
   ctx->cd_status_n = 0;
   rc = rt_reserve(ctx, ctx->cd_status, sizeof(glc::CompactStatus));
   if (rc == GLC_OK)
-    rc = cd_decode_one(ctx, g, d_blob, blob_bytes, static_cast<glc::CompactStatus *>(ctx->cd_status.p), d_out, nullptr, false, nullptr);
+    rc = cd_decode_one<float>(ctx, g, d_blob, blob_bytes, static_cast<glc::CompactStatus *>(ctx->cd_status.p), d_out, nullptr, false, nullptr);
   if (rc == GLC_OK) ctx->cd_status_n = 1;
   return rc;
 }
 
-// glc_decode_batch_device_compact and (crops) glc_decode_crops_device_compact: the checks, then cdb_impl.
+// glc_decode_batch_device_compact and (crops) glc_decode_crops_device_compact, and their _i16 twins (T = int16_t): the
+// checks, then cdb_impl.
+extern "C++" {
+template <typename T>
 static int cd_batch_call(glc_ctx *ctx, const char *who, const void *const *d_blobs, const uint64_t *blob_bytes, const uint64_t *n_samples,
-                         const glc_crop *crops, bool windows, float *d_out, const glc_clip_layout *out) {
+                         const glc_crop *crops, bool windows, T *d_out, const glc_clip_layout *out) {
   const std::string w(who);
   if (!ctx) return GLC_EINVAL;
   if (!out) return fail(ctx, GLC_EINVAL, w + ": null argument");
   if (out->n_clips == 0) return GLC_OK;
   if (!d_blobs || !blob_bytes || !n_samples || !d_out || (windows && !crops)) return fail(ctx, GLC_EINVAL, w + ": null argument");
   if (out->channels == 0) return fail(ctx, GLC_EINVAL, w + ": channels == 0");
-  if (reinterpret_cast<uintptr_t>(d_out) & 3u) return fail(ctx, GLC_EINVAL, w + ": output pointer not aligned to its sample size");
+  if (reinterpret_cast<uintptr_t>(d_out) & (sizeof(T) - 1u)) return fail(ctx, GLC_EINVAL, w + ": output pointer not aligned to its sample size");
   const RtbLayout lo{out};
   const uint64_t n = out->n_clips, ch = out->channels;
   try {  // no C++ exception may cross the C ABI
@@ -3051,7 +3104,7 @@ static int cd_batch_call(glc_ctx *ctx, const char *who, const void *const *d_blo
       const int rc = cd_check_blob(ctx, clip, d_blobs[i], blob_bytes[i], out->channels, plans[i].n_frames);
       if (rc != GLC_OK) return rc;
     }
-    const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_out), b1 = b0 + lo.extent() * sizeof(float);
+    const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_out), b1 = lo.end_of(d_out, sizeof(T));
     for (uint64_t i = 0; i < n; ++i) {
       const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_blobs[i]), a1 = a0 + blob_bytes[i];
       if (a0 < b1 && b0 < a1) return fail(ctx, GLC_EINVAL, w + ": clip " + std::to_string(i) + ": the output extent overlaps the blob");
@@ -3062,6 +3115,7 @@ static int cd_batch_call(glc_ctx *ctx, const char *who, const void *const *d_blo
     return fail(ctx, GLC_ENOMEM, w + ": host allocation failed");
   }
 }
+}  // extern "C++"
 
 int glc_decode_batch_device_compact(glc_ctx *ctx, const void *const *d_blobs, const uint64_t *blob_bytes, const uint64_t *n_samples,
                                     float *d_out, const glc_clip_layout *out) {
@@ -3071,6 +3125,16 @@ int glc_decode_batch_device_compact(glc_ctx *ctx, const void *const *d_blobs, co
 int glc_decode_crops_device_compact(glc_ctx *ctx, const void *const *d_blobs, const uint64_t *blob_bytes, const uint64_t *n_samples,
                                     const glc_crop *crops, float *d_out, const glc_clip_layout *out) {
   return cd_batch_call(ctx, "glc_decode_crops_device_compact", d_blobs, blob_bytes, n_samples, crops, true, d_out, out);
+}
+
+int glc_decode_batch_device_compact_i16(glc_ctx *ctx, const void *const *d_blobs, const uint64_t *blob_bytes, const uint64_t *n_samples,
+                                        int16_t *d_out, const glc_clip_layout *out) {
+  return cd_batch_call(ctx, "glc_decode_batch_device_compact_i16", d_blobs, blob_bytes, n_samples, nullptr, false, d_out, out);
+}
+
+int glc_decode_crops_device_compact_i16(glc_ctx *ctx, const void *const *d_blobs, const uint64_t *blob_bytes, const uint64_t *n_samples,
+                                        const glc_crop *crops, int16_t *d_out, const glc_clip_layout *out) {
+  return cd_batch_call(ctx, "glc_decode_crops_device_compact_i16", d_blobs, blob_bytes, n_samples, crops, true, d_out, out);
 }
 
 int glc_decode_compact_last_status(glc_ctx *ctx, glc_compact_status *status, uint64_t n_clips) {
@@ -3106,7 +3170,7 @@ struct SdGeom {
 
 int sd_check(glc_ctx *ctx, const std::string &w, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
              const int64_t *d_lengths, uint64_t n_entries, uint64_t max_length, const int64_t *d_clips, const int64_t *d_starts,
-             uint64_t length, const float *d_out, const glc_clip_layout *out, SdGeom *g) {
+             uint64_t length, const void *d_out, size_t out_elem, const glc_clip_layout *out, SdGeom *g) {
   if (!d_arena || !d_entries || !d_lengths || !d_clips || !d_starts || !d_out) return fail(ctx, GLC_EINVAL, w + ": null argument");
   if (out->channels == 0) return fail(ctx, GLC_EINVAL, w + ": channels == 0");
   const uint64_t n = out->n_clips, ch = out->channels;
@@ -3114,7 +3178,7 @@ int sd_check(glc_ctx *ctx, const std::string &w, const void *d_arena, uint64_t a
   if ((reinterpret_cast<uintptr_t>(d_entries) | reinterpret_cast<uintptr_t>(d_lengths) | reinterpret_cast<uintptr_t>(d_clips) |
        reinterpret_cast<uintptr_t>(d_starts)) & 7u)
     return fail(ctx, GLC_EINVAL, w + ": entries, lengths, clips and starts must be 8-byte aligned");
-  if (reinterpret_cast<uintptr_t>(d_out) & 3u) return fail(ctx, GLC_EINVAL, w + ": output pointer not aligned to its sample size");
+  if (reinterpret_cast<uintptr_t>(d_out) & (out_elem - 1u)) return fail(ctx, GLC_EINVAL, w + ": output pointer not aligned to its sample size");
   if (n_entries == 0) return fail(ctx, GLC_EINVAL, w + ": n_entries == 0");
   if (length == 0) return fail(ctx, GLC_EINVAL, w + ": length == 0");
   if (max_length < length) return fail(ctx, GLC_EINVAL, w + ": max_length is smaller than the crop");
@@ -3138,7 +3202,7 @@ int sd_check(glc_ctx *ctx, const std::string &w, const void *d_arena, uint64_t a
     return fail(ctx, GLC_EINVAL, w + ": a crop of this length does not fit a round (glc_decode_crops_device_compact takes such windows)");
   g->per_round = glc::kStoreRoundBudget / (g->slots.max_frames + 1);
   g->max_front = longest.n_frames * ch;
-  const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_out), b1 = b0 + ((n - 1) * out->clip_stride + occupies) * sizeof(float);
+  const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_out), b1 = b0 + ((n - 1) * out->clip_stride + occupies) * out_elem;
   auto overlaps = [&](const void *p, uint64_t bytes) {
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(p), a1 = a0 + bytes;
     return a0 < b1 && b0 < a1;
@@ -3195,15 +3259,19 @@ int glc_store_crop_slots(uint64_t length, uint16_t channels, uint64_t *max_hops,
   return GLC_OK;
 }
 
-int glc_decode_crops_device_store(glc_ctx *ctx, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
-                                  const int64_t *d_lengths, uint64_t n_entries, uint64_t max_length, const int64_t *d_clips,
-                                  const int64_t *d_starts, uint64_t length, float *d_out, const glc_clip_layout *out) {
-  const std::string w("glc_decode_crops_device_store");
+// glc_decode_crops_device_store and its _i16 twin (T = int16_t): the same plan, the same launches, D2 narrowing.
+extern "C++" {
+template <typename T>
+static int sd_call(glc_ctx *ctx, const char *who, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
+                   const int64_t *d_lengths, uint64_t n_entries, uint64_t max_length, const int64_t *d_clips, const int64_t *d_starts,
+                   uint64_t length, T *d_out, const glc_clip_layout *out) {
+  const std::string w(who);
   if (!ctx) return GLC_EINVAL;
   if (!out) return fail(ctx, GLC_EINVAL, w + ": null argument");
   if (out->n_clips == 0) return GLC_OK;
   SdGeom g;
-  int rc = sd_check(ctx, w, d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips, d_starts, length, d_out, out, &g);
+  int rc = sd_check(ctx, w, d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips, d_starts, length, d_out, sizeof(T),
+                    out, &g);
   if (rc != GLC_OK) return rc;
   const uint64_t n = out->n_clips;
   const uint32_t ch = out->channels;
@@ -3244,6 +3312,21 @@ int glc_decode_crops_device_store(glc_ctx *ctx, const void *d_arena, uint64_t ar
   ctx->cd_status_n = n;
   return GLC_OK;
 }
+}  // extern "C++"
+
+int glc_decode_crops_device_store(glc_ctx *ctx, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
+                                  const int64_t *d_lengths, uint64_t n_entries, uint64_t max_length, const int64_t *d_clips,
+                                  const int64_t *d_starts, uint64_t length, float *d_out, const glc_clip_layout *out) {
+  return sd_call(ctx, "glc_decode_crops_device_store", d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips, d_starts,
+                 length, d_out, out);
+}
+
+int glc_decode_crops_device_store_i16(glc_ctx *ctx, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
+                                      const int64_t *d_lengths, uint64_t n_entries, uint64_t max_length, const int64_t *d_clips,
+                                      const int64_t *d_starts, uint64_t length, int16_t *d_out, const glc_clip_layout *out) {
+  return sd_call(ctx, "glc_decode_crops_device_store_i16", d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips,
+                 d_starts, length, d_out, out);
+}
 
 int glc_debug_store_plan_device(glc_ctx *ctx, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
                                 const int64_t *d_lengths, uint64_t n_entries, uint64_t max_length, const int64_t *d_clips,
@@ -3254,7 +3337,8 @@ int glc_debug_store_plan_device(glc_ctx *ctx, const void *d_arena, uint64_t aren
   if (!out || !dir || !desc || !verdict) return fail(ctx, GLC_EINVAL, w + ": null argument");
   if (out->n_clips == 0) return GLC_OK;
   SdGeom g;
-  int rc = sd_check(ctx, w, d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips, d_starts, length, d_out, out, &g);
+  int rc = sd_check(ctx, w, d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips, d_starts, length, d_out, sizeof(float),
+                    out, &g);
   if (rc != GLC_OK) return rc;
   DeviceGuard guard(ctx->device);
   rt_forget_streams(ctx);
@@ -3380,7 +3464,7 @@ int store_round_launch(glc_ctx *ctx, const void *d_records, uint64_t n_real, uin
   return GLC_OK;
 }
 
-int ebc_impl(glc_ctx *ctx, const float *d_pcm, const RtbLayout &in, void *d_arena, uint64_t arena_bytes, uint64_t *d_cursor,
+int ebc_impl(glc_ctx *ctx, const RtbPcm &pcm, const RtbLayout &in, void *d_arena, uint64_t arena_bytes, uint64_t *d_cursor,
              glc_store_entry *d_entries) {
   const uint64_t n = in.l->n_clips;
   const uint32_t ch = in.l->channels;
@@ -3434,8 +3518,8 @@ int ebc_impl(glc_ctx *ctx, const float *d_pcm, const RtbLayout &in, void *d_aren
   if (rc != GLC_OK) return rc;
   float *vs = static_cast<float *>(ctx->rtb_vs.p);
   for (const RtbRound &r : rounds) {
-    GLC_HIP(ctx, glc::launch_stage_clips(d_pcm, reinterpret_cast<const glc::StageClip *>(d_tab + r.o_clips), static_cast<uint32_t>(r.n), ch,
-                                         in.planes(), in.l->channel_stride, static_cast<uint32_t>(r.V), vs, st));
+    rc = rtb_stage(ctx, pcm, reinterpret_cast<const glc::StageClip *>(d_tab + r.o_clips), r.n, ch, in, r.V, vs, st);
+    if (rc != GLC_OK) return rc;
     if (r.lng) {
       const uint64_t len = in.len(r.first);
       rc = encode_range_on(ctx, st, ctx->coef, vs, 0, len, len * ch, static_cast<uint16_t>(ch), 0, r.n_real, ctx->rt_records.p, nullptr);
@@ -3454,15 +3538,18 @@ int ebc_impl(glc_ctx *ctx, const float *d_pcm, const RtbLayout &in, void *d_aren
 }  // namespace
 }  // extern "C++"
 
-int glc_encode_batch_device_compact(glc_ctx *ctx, const float *d_pcm, const glc_clip_layout *in, void *d_arena, uint64_t arena_bytes,
-                                    uint64_t *d_cursor, glc_store_entry *d_entries) {
-  const std::string w("glc_encode_batch_device_compact");
+// glc_encode_batch_device_compact and glc_encode_batch_device_compact_int: the checks, then ebc_impl.
+static int ebc_call(glc_ctx *ctx, const char *who, const void *d_pcm, glc_pcm_format fmt, uint32_t bits, const glc_clip_layout *in,
+                    void *d_arena, uint64_t arena_bytes, uint64_t *d_cursor, glc_store_entry *d_entries) {
+  const std::string w(who);
   if (!ctx) return GLC_EINVAL;
   if (!in) return fail(ctx, GLC_EINVAL, w + ": null argument");
+  if (const int rc = rtb_check_fmt(ctx, w, fmt, bits)) return rc;
   if (in->n_clips == 0) return GLC_OK;
   if (!d_pcm || !d_arena || !d_cursor || !d_entries) return fail(ctx, GLC_EINVAL, w + ": null argument");
   if (in->channels == 0) return fail(ctx, GLC_EINVAL, w + ": channels == 0");
-  if (reinterpret_cast<uintptr_t>(d_pcm) & 3u) return fail(ctx, GLC_EINVAL, w + ": d_pcm is not aligned to its sample size");
+  const RtbPcm pcm{d_pcm, fmt, bits};
+  if (reinterpret_cast<uintptr_t>(d_pcm) & (pcm.elem() - 1u)) return fail(ctx, GLC_EINVAL, w + ": d_pcm is not aligned to its sample size");
   if (reinterpret_cast<uintptr_t>(d_arena) & 63u) return fail(ctx, GLC_EINVAL, w + ": d_arena is not 64-byte aligned");
   if ((reinterpret_cast<uintptr_t>(d_cursor) | reinterpret_cast<uintptr_t>(d_entries)) & 7u)
     return fail(ctx, GLC_EINVAL, w + ": d_cursor and d_entries must be 8-byte aligned");
@@ -3471,7 +3558,7 @@ int glc_encode_batch_device_compact(glc_ctx *ctx, const float *d_pcm, const glc_
   for (uint64_t i = 0; i < n; ++i)
     if (const int rc = rtb_check_clip(ctx, w + ": clip " + std::to_string(i), li, i)) return rc;
   {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_pcm), a1 = a0 + li.extent() * sizeof(float);
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_pcm), a1 = li.end_of(d_pcm, pcm.elem());
     const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_arena), b1 = b0 + arena_bytes;
     const uintptr_t e0 = reinterpret_cast<uintptr_t>(d_entries), e1 = e0 + n * sizeof(glc_store_entry);
     if (a0 < b1 && b0 < a1) return fail(ctx, GLC_EINVAL, w + ": the arena overlaps the input");
@@ -3479,10 +3566,20 @@ int glc_encode_batch_device_compact(glc_ctx *ctx, const float *d_pcm, const glc_
   }
   DeviceGuard guard(ctx->device);
   try {  // no C++ exception may cross the C ABI
-    return ebc_impl(ctx, d_pcm, li, d_arena, arena_bytes, d_cursor, d_entries);
+    return ebc_impl(ctx, pcm, li, d_arena, arena_bytes, d_cursor, d_entries);
   } catch (const std::bad_alloc &) {
     return fail(ctx, GLC_ENOMEM, w + ": host allocation failed");
   }
+}
+
+int glc_encode_batch_device_compact(glc_ctx *ctx, const float *d_pcm, const glc_clip_layout *in, void *d_arena, uint64_t arena_bytes,
+                                    uint64_t *d_cursor, glc_store_entry *d_entries) {
+  return ebc_call(ctx, "glc_encode_batch_device_compact", d_pcm, GLC_PCM_F32, 32, in, d_arena, arena_bytes, d_cursor, d_entries);
+}
+
+int glc_encode_batch_device_compact_int(glc_ctx *ctx, const void *d_pcm, glc_pcm_format fmt, uint32_t bits, const glc_clip_layout *in,
+                                        void *d_arena, uint64_t arena_bytes, uint64_t *d_cursor, glc_store_entry *d_entries) {
+  return ebc_call(ctx, "glc_encode_batch_device_compact_int", d_pcm, fmt, bits, in, d_arena, arena_bytes, d_cursor, d_entries);
 }
 
 int glc_debug_compact_store_device(glc_ctx *ctx, const void *d_records, const uint64_t *clip_frames, uint64_t n_clips,

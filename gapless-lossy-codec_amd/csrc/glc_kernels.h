@@ -247,6 +247,12 @@ struct StageClip {
 };
 hipError_t launch_stage_clips(const float *src, const StageClip *clips, uint32_t n_clips, uint32_t ch, bool planar,
                               uint64_t channel_stride, uint32_t n_virtual_frames, float *vstream, hipStream_t s);
+// ... from integer clips (`wide`: int32_t samples of 1..32 bits, else int16_t of 1..16), widened in the SAME pass
+// by W1's rule (launch_pcm_widen below: one device function serves both): `src`, StageClip::src and channel_stride
+// count elements of the sample type, the source is aligned to its sample and to nothing more.  The zeros behind
+// a clip are +0.0, not widened integer zeros.
+hipError_t launch_stage_clips_int(const void *src, bool wide, uint32_t bits, const StageClip *clips, uint32_t n_clips, uint32_t ch,
+                                  bool planar, uint64_t channel_stride, uint32_t n_virtual_frames, float *vstream, hipStream_t s);
 
 // D2 by descriptor, one per kept output hop (the batch drivers): the hop is made of the second half of block slot
 // `prev` (-1: +0.0, a stream's first hop) and the first half of slot `cur` (-1: none, the bare tail).  The
@@ -261,6 +267,10 @@ struct HopDescStrided {
 };
 hipError_t launch_overlap_add_strided(const float *blocks, const HopDescStrided *desc, uint32_t n_desc, uint32_t ch, bool planar,
                                       float *out, hipStream_t s);
+// ... narrowed to 16-bit PCM as launch_overlap_add narrows: dst and cstride count 2-byte elements, `out` is any
+// 2-byte aligned pointer, chunks are short4 at 8-byte boundaries.  A null descriptor writes nothing here either.
+hipError_t launch_overlap_add_strided(const float *blocks, const HopDescStrided *desc, uint32_t n_desc, uint32_t ch, bool planar,
+                                      int16_t *out, hipStream_t s);
 // The descriptor of hop h of a clip of `nf` frames whose frame f is block slot base + f, the ONE statement of it for
 // the host drivers (write_hop_descs) and the draw planner: the span of the hop that `trim` keeps lands from element
 // `dst` on, interleaved, or (planes) in planes `cstride` apart.  false: the trim keeps nothing of the hop.

@@ -1046,10 +1046,12 @@ __global__ __launch_bounds__(256) void k_overlap_add_strided(const float *__rest
 // j0 <= t * ch + c < j0 + cnt, at most 1025 of them, consecutive in memory.  A thread owns an aligned float4 of
 // the plane: four consecutive times, whose samples are four consecutive entries of ONE block plane - position
 // i0 + (t - t_lo) of block channel cc, one division per thread.  Only the first and the last chunk of a span
-// can be partial; they store float by float.
+// can be partial; they store float by float.  T = short: the same over aligned short4 of the plane (8-byte
+// boundaries), narrowed as d2_store narrows.
+template <typename T>
 __global__ __launch_bounds__(256) void k_overlap_add_planar(const float *__restrict__ blocks,
                                                              const HopDescStrided *__restrict__ desc, unsigned ch,
-                                                             float *__restrict__ out) {
+                                                             T *__restrict__ out) {
   const HopDescStrided d = desc[blockIdx.y];
   const unsigned c = blockIdx.x;
   const unsigned long long j1 = d.j0 + d.cnt;
@@ -1061,10 +1063,10 @@ __global__ __launch_bounds__(256) void k_overlap_add_planar(const float *__restr
   const bool has_prev = d.prev >= 0, has_cur = d.cur >= 0;
   const float *prev = blocks + (static_cast<size_t>(has_prev ? d.prev : 0) * ch + cc) * kFrameI + kHopI + i0;
   const float *cur = blocks + (static_cast<size_t>(has_cur ? d.cur : 0) * ch + cc) * kFrameI + i0;
-  float *span = out + d.dst + c * d.cstride + t_lo;
-  const unsigned lead = static_cast<unsigned>(reinterpret_cast<uintptr_t>(span) >> 2) & 3u;
+  T *span = out + d.dst + c * d.cstride + t_lo;
+  const unsigned lead = static_cast<unsigned>(reinterpret_cast<uintptr_t>(span) / sizeof(T)) & 3u;
   const unsigned n_chunks = (lead + n + 3u) >> 2;
-  float *base = span - lead;
+  T *base = span - lead;
   for (unsigned k = threadIdx.x; k < n_chunks; k += 256u) {
     const int j0 = static_cast<int>(4u * k) - static_cast<int>(lead);
     float v[4];
@@ -1089,6 +1091,13 @@ __global__ __launch_bounds__(256) void k_overlap_add_planar(const float *__restr
 // when the source is aligned there too (VEC), else one by one.  The at most 3 + 3 samples in front
 // of and behind the body are converted by the threads after the body's.
 // ------------------------------------------------------------------------------------------
+// The ONE conversion of an integer sample, for W1 and for the widening gather S1 (k_stage_clips*): the host
+// boundary and the store cannot drift apart.
+template <typename S>
+__device__ __forceinline__ float pcm_widen1(S s, float inv) {
+  return mul_rn(static_cast<float>(s), inv);
+}
+
 template <typename S, bool VEC>
 __global__ __launch_bounds__(256) void k_pcm_widen(const S *__restrict__ in, float *__restrict__ out,
                                                     unsigned long long n, unsigned head, float inv) {
@@ -1099,21 +1108,19 @@ __global__ __launch_bounds__(256) void k_pcm_widen(const S *__restrict__ in, flo
     float4 v;
     if constexpr (VEC && sizeof(S) == 2) {
       const short4 s = *reinterpret_cast<const short4 *>(in + at);
-      v = float4{static_cast<float>(s.x), static_cast<float>(s.y), static_cast<float>(s.z), static_cast<float>(s.w)};
+      v = float4{pcm_widen1(s.x, inv), pcm_widen1(s.y, inv), pcm_widen1(s.z, inv), pcm_widen1(s.w, inv)};
     } else if constexpr (VEC) {
       const int4 s = *reinterpret_cast<const int4 *>(in + at);
-      v = float4{static_cast<float>(s.x), static_cast<float>(s.y), static_cast<float>(s.z), static_cast<float>(s.w)};
+      v = float4{pcm_widen1(s.x, inv), pcm_widen1(s.y, inv), pcm_widen1(s.z, inv), pcm_widen1(s.w, inv)};
     } else {
-      v = float4{static_cast<float>(in[at]), static_cast<float>(in[at + 1]), static_cast<float>(in[at + 2]),
-                 static_cast<float>(in[at + 3])};
+      v = float4{pcm_widen1(in[at], inv), pcm_widen1(in[at + 1], inv), pcm_widen1(in[at + 2], inv), pcm_widen1(in[at + 3], inv)};
     }
-    v.x = mul_rn(v.x, inv), v.y = mul_rn(v.y, inv), v.z = mul_rn(v.z, inv), v.w = mul_rn(v.w, inv);
     *reinterpret_cast<float4 *>(out + at) = v;
     return;
   }
   const unsigned long long e = g - n4;  // 0 .. head-1: the head; then the tail behind the body
   const unsigned long long at = e < head ? e : 4u * n4 + e;
-  if (at < n) out[at] = mul_rn(static_cast<float>(in[at]), inv);
+  if (at < n) out[at] = pcm_widen1(in[at], inv);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2142,46 +2149,70 @@ __device__ __forceinline__ StageClip stage_find_clip(const StageClip *__restrict
   return clips[lo];
 }
 
-// Elements [t, t + 4) of a run of `len` floats (+0.0 past its end).  A run that starts off a 16-byte
-// boundary is read as the two aligned float4 around the four - both inside the run, so nothing outside
-// the caller's samples is touched; only where one of them would cross the run's first or last element
-// (its edges) do the four come one by one.  t advances by 4 per thread, so the case is wave-uniform.
-__device__ __forceinline__ float4 stage_load4(const float *__restrict__ run, unsigned long long t, unsigned long long len) {
-  const float *p = run + t;
-  const unsigned mis = static_cast<unsigned>(reinterpret_cast<uintptr_t>(p) >> 2) & 3u;
-  if (mis == 0 && t + 4 <= len) return *reinterpret_cast<const float4 *>(p);
+// Elements [t, t + 4) of a run of `len` samples of S (float, or int16_t / int32_t widened by pcm_widen1 with
+// `inv`; +0.0 past the run's end - the reference's padding, never a widened integer zero).  A run that starts off
+// the boundary of a vector of four S (16 bytes of float4 / int4, 8 of short4) is read as the two aligned
+// vectors around the four - both inside the run, so nothing outside the caller's samples is touched; only where
+// one of them would cross the run's first or last element (its edges) do the four come one by one.  `mis`
+// counts ELEMENTS from the vector boundary: an int16 run may start at any 2-byte address.  t advances by 4 per
+// thread, so the case is wave-uniform.
+template <typename S>
+struct StageVec4;
+template <>
+struct StageVec4<float> { using type = float4; };
+template <>
+struct StageVec4<short> { using type = short4; };
+template <>
+struct StageVec4<int> { using type = int4; };
+
+template <typename S>
+__device__ __forceinline__ float stage_widen(S s, float inv) {
+  if constexpr (std::is_same<S, float>::value) return s;
+  else return pcm_widen1(s, inv);
+}
+
+template <typename S>
+__device__ __forceinline__ float4 stage_load4(const S *__restrict__ run, unsigned long long t, unsigned long long len, float inv) {
+  using S4 = typename StageVec4<S>::type;
+  const S *p = run + t;
+  const unsigned mis = static_cast<unsigned>(reinterpret_cast<uintptr_t>(p) / sizeof(S)) & 3u;
+  if (mis == 0 && t + 4 <= len) {
+    const S4 a = *reinterpret_cast<const S4 *>(p);
+    return float4{stage_widen(a.x, inv), stage_widen(a.y, inv), stage_widen(a.z, inv), stage_widen(a.w, inv)};
+  }
   if (mis != 0 && t >= mis && t - mis + 8 <= len) {
-    const float4 a = *reinterpret_cast<const float4 *>(p - mis), b = *reinterpret_cast<const float4 *>(p - mis + 4);
-    if (mis == 1) return float4{a.y, a.z, a.w, b.x};
-    if (mis == 2) return float4{a.z, a.w, b.x, b.y};
-    return float4{a.w, b.x, b.y, b.z};
+    const S4 a = *reinterpret_cast<const S4 *>(p - mis), b = *reinterpret_cast<const S4 *>(p - mis + 4);
+    if (mis == 1) return float4{stage_widen(a.y, inv), stage_widen(a.z, inv), stage_widen(a.w, inv), stage_widen(b.x, inv)};
+    if (mis == 2) return float4{stage_widen(a.z, inv), stage_widen(a.w, inv), stage_widen(b.x, inv), stage_widen(b.y, inv)};
+    return float4{stage_widen(a.w, inv), stage_widen(b.x, inv), stage_widen(b.y, inv), stage_widen(b.z, inv)};
   }
   float4 r;
-  r.x = t < len ? p[0] : 0.0f;
-  r.y = t + 1 < len ? p[1] : 0.0f;
-  r.z = t + 2 < len ? p[2] : 0.0f;
-  r.w = t + 3 < len ? p[3] : 0.0f;
+  r.x = t < len ? stage_widen(p[0], inv) : 0.0f;
+  r.y = t + 1 < len ? stage_widen(p[1], inv) : 0.0f;
+  r.z = t + 2 < len ? stage_widen(p[2], inv) : 0.0f;
+  r.w = t + 3 < len ? stage_widen(p[3], inv) : 0.0f;
   return r;
 }
 
-// Interleaved clips (and mono planar ones, which are the same thing): a clip is ONE run of len * ch floats,
-// a thread copies a float4 of it.  grid (V, ch).
-__global__ __launch_bounds__(256) void k_stage_clips(const float *__restrict__ src, const StageClip *__restrict__ clips,
-                                                      unsigned n_clips, unsigned ch, float *__restrict__ vs) {
+// Interleaved clips (and mono planar ones, which are the same thing): a clip is ONE run of len * ch samples,
+// a thread converts four of them into a float4.  grid (V, ch).
+template <typename S>
+__global__ __launch_bounds__(256) void k_stage_clips(const S *__restrict__ src, const StageClip *__restrict__ clips,
+                                                      unsigned n_clips, unsigned ch, float inv, float *__restrict__ vs) {
   const unsigned v = blockIdx.x;
   const StageClip cl = stage_find_clip(clips, n_clips, v);
   const unsigned per_hop = static_cast<unsigned>(kHopI) * ch;
   const unsigned o = (blockIdx.y * 256u + threadIdx.x) * 4u;
   if (o >= per_hop) return;
   const unsigned long long t = static_cast<unsigned long long>(v - cl.slot) * per_hop + o;
-  *reinterpret_cast<float4 *>(vs + static_cast<size_t>(v) * per_hop + o) = stage_load4(src + cl.src, t, cl.len * ch);
+  *reinterpret_cast<float4 *>(vs + static_cast<size_t>(v) * per_hop + o) = stage_load4(src + cl.src, t, cl.len * ch, inv);
 }
 
 // Planar clips of 2 / 4 / 8 channels: a thread takes the same four samples of every plane (CH coalesced
-// 16-byte loads, one plane each) and stores them interleaved as CH float4.  grid (V).
-template <int CH>
-__global__ __launch_bounds__(256) void k_stage_clips_planar(const float *__restrict__ src, const StageClip *__restrict__ clips,
-                                                             unsigned n_clips, unsigned long long cstride,
+// vector loads, one plane each) and stores them interleaved as CH float4.  grid (V).
+template <int CH, typename S>
+__global__ __launch_bounds__(256) void k_stage_clips_planar(const S *__restrict__ src, const StageClip *__restrict__ clips,
+                                                             unsigned n_clips, unsigned long long cstride, float inv,
                                                              float *__restrict__ vs) {
   const unsigned v = blockIdx.x;
   const StageClip cl = stage_find_clip(clips, n_clips, v);
@@ -2190,7 +2221,7 @@ __global__ __launch_bounds__(256) void k_stage_clips_planar(const float *__restr
   float q[4 * CH];  // [sample][channel]
 #pragma unroll
   for (int c = 0; c < CH; ++c) {
-    const float4 p = stage_load4(src + cl.src + c * cstride, t, cl.len);
+    const float4 p = stage_load4(src + cl.src + c * cstride, t, cl.len, inv);
     q[c] = p.x, q[CH + c] = p.y, q[2 * CH + c] = p.z, q[3 * CH + c] = p.w;
   }
   float4 *dst = reinterpret_cast<float4 *>(vs + (static_cast<size_t>(v) * kHopI + i0) * CH);
@@ -2200,9 +2231,10 @@ __global__ __launch_bounds__(256) void k_stage_clips_planar(const float *__restr
 
 // Planar clips of any other channel count: a thread owns a float4 of the interleaved OUTPUT and fetches its
 // four samples one by one (a division each).  grid (V, ch).
-__global__ __launch_bounds__(256) void k_stage_clips_planar_any(const float *__restrict__ src,
+template <typename S>
+__global__ __launch_bounds__(256) void k_stage_clips_planar_any(const S *__restrict__ src,
                                                                  const StageClip *__restrict__ clips, unsigned n_clips,
-                                                                 unsigned ch, unsigned long long cstride,
+                                                                 unsigned ch, unsigned long long cstride, float inv,
                                                                  float *__restrict__ vs) {
   const unsigned v = blockIdx.x;
   const StageClip cl = stage_find_clip(clips, n_clips, v);
@@ -2214,7 +2246,7 @@ __global__ __launch_bounds__(256) void k_stage_clips_planar_any(const float *__r
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const unsigned i = (o + e) / ch, c = (o + e) - i * ch;
-    q[e] = t0 + i < cl.len ? src[cl.src + c * cstride + t0 + i] : 0.0f;
+    q[e] = t0 + i < cl.len ? stage_widen(src[cl.src + c * cstride + t0 + i], inv) : 0.0f;
   }
   *reinterpret_cast<float4 *>(vs + static_cast<size_t>(v) * per_hop + o) = float4{q[0], q[1], q[2], q[3]};
 }
@@ -2798,24 +2830,49 @@ hipError_t launch_overlap_add(const float *blocks, int64_t blk_frame0, uint64_t 
   return overlap_add_typed(blocks, blk_frame0, n_frames, ch, hop_begin, hop_end, reinterpret_cast<short *>(out), s);
 }
 
-hipError_t launch_stage_clips(const float *src, const StageClip *clips, uint32_t n_clips, uint32_t ch, bool planar,
-                              uint64_t channel_stride, uint32_t n_virtual_frames, float *vstream, hipStream_t s) {
-  if (!src || !clips || !vstream || n_clips == 0 || ch == 0 || (reinterpret_cast<uintptr_t>(vstream) & 15u)) return hipErrorInvalidValue;
+namespace {
+template <typename S>
+hipError_t stage_clips_typed(const S *src, const StageClip *clips, uint32_t n_clips, uint32_t ch, bool planar, uint64_t channel_stride,
+                             uint32_t n_virtual_frames, float inv, float *vstream, hipStream_t s) {
+  if (!src || !clips || !vstream || n_clips == 0 || ch == 0 || (reinterpret_cast<uintptr_t>(vstream) & 15u) ||
+      (reinterpret_cast<uintptr_t>(src) & (sizeof(S) - 1u)))
+    return hipErrorInvalidValue;
   if (n_virtual_frames == 0) return hipSuccess;
   const unsigned long long cs = channel_stride;
   const dim3 wide(n_virtual_frames, ch), one(n_virtual_frames);  // 1024 * ch / 4 float4 over 256 threads: ch workgroups per slot
   if (ch > 65535u) return hipErrorInvalidValue;
   if (!planar || ch == 1) {
-    hipLaunchKernelGGL(k_stage_clips, wide, dim3(256), 0, s, src, clips, n_clips, ch, vstream);
+    hipLaunchKernelGGL(k_stage_clips<S>, wide, dim3(256), 0, s, src, clips, n_clips, ch, inv, vstream);
   } else {
     switch (ch) {
-      case 2: hipLaunchKernelGGL(k_stage_clips_planar<2>, one, dim3(256), 0, s, src, clips, n_clips, cs, vstream); break;
-      case 4: hipLaunchKernelGGL(k_stage_clips_planar<4>, one, dim3(256), 0, s, src, clips, n_clips, cs, vstream); break;
-      case 8: hipLaunchKernelGGL(k_stage_clips_planar<8>, one, dim3(256), 0, s, src, clips, n_clips, cs, vstream); break;
-      default: hipLaunchKernelGGL(k_stage_clips_planar_any, wide, dim3(256), 0, s, src, clips, n_clips, ch, cs, vstream); break;
+      case 2: hipLaunchKernelGGL((k_stage_clips_planar<2, S>), one, dim3(256), 0, s, src, clips, n_clips, cs, inv, vstream); break;
+      case 4: hipLaunchKernelGGL((k_stage_clips_planar<4, S>), one, dim3(256), 0, s, src, clips, n_clips, cs, inv, vstream); break;
+      case 8: hipLaunchKernelGGL((k_stage_clips_planar<8, S>), one, dim3(256), 0, s, src, clips, n_clips, cs, inv, vstream); break;
+      default: hipLaunchKernelGGL(k_stage_clips_planar_any<S>, wide, dim3(256), 0, s, src, clips, n_clips, ch, cs, inv, vstream); break;
     }
   }
   return hipGetLastError();
+}
+
+// `(1 << (bits - 1)) as f32` on an i32 literal: 32 bits shift into the sign (quirk Q11, glc_wav.cpp).  A power of
+// two, so its reciprocal is exact.
+float pcm_widen_inv(uint32_t bits) {
+  const float max = bits == 32 ? -2147483648.0f : static_cast<float>(1u << (bits - 1));
+  return 1.0f / max;
+}
+}  // namespace
+
+hipError_t launch_stage_clips(const float *src, const StageClip *clips, uint32_t n_clips, uint32_t ch, bool planar,
+                              uint64_t channel_stride, uint32_t n_virtual_frames, float *vstream, hipStream_t s) {
+  return stage_clips_typed(src, clips, n_clips, ch, planar, channel_stride, n_virtual_frames, 1.0f, vstream, s);
+}
+
+hipError_t launch_stage_clips_int(const void *src, bool wide, uint32_t bits, const StageClip *clips, uint32_t n_clips, uint32_t ch,
+                                  bool planar, uint64_t channel_stride, uint32_t n_virtual_frames, float *vstream, hipStream_t s) {
+  if (bits == 0 || bits > (wide ? 32u : 16u)) return hipErrorInvalidValue;
+  const float inv = pcm_widen_inv(bits);
+  return wide ? stage_clips_typed(static_cast<const int *>(src), clips, n_clips, ch, planar, channel_stride, n_virtual_frames, inv, vstream, s)
+              : stage_clips_typed(static_cast<const short *>(src), clips, n_clips, ch, planar, channel_stride, n_virtual_frames, inv, vstream, s);
 }
 
 namespace {
@@ -2828,7 +2885,7 @@ hipError_t overlap_add_strided_typed(const float *blocks, const D *desc, uint32_
     const D *d = desc + d0;
     if constexpr (std::is_same<D, HopDescStrided>::value) {  // (a HopDesc has no planes)
       if (planar && ch > 1) {
-        hipLaunchKernelGGL(k_overlap_add_planar, dim3(ch, nd), dim3(256), 0, s, blocks, d, ch, out);
+        hipLaunchKernelGGL(k_overlap_add_planar<T>, dim3(ch, nd), dim3(256), 0, s, blocks, d, ch, out);
         return;
       }
     }
@@ -2845,6 +2902,11 @@ hipError_t overlap_add_strided_typed(const float *blocks, const D *desc, uint32_
 hipError_t launch_overlap_add_strided(const float *blocks, const HopDescStrided *desc, uint32_t n_desc, uint32_t ch, bool planar,
                                       float *out, hipStream_t s) {
   return overlap_add_strided_typed(blocks, desc, n_desc, ch, planar, out, s);
+}
+
+hipError_t launch_overlap_add_strided(const float *blocks, const HopDescStrided *desc, uint32_t n_desc, uint32_t ch, bool planar,
+                                      int16_t *out, hipStream_t s) {
+  return overlap_add_strided_typed(blocks, desc, n_desc, ch, planar, reinterpret_cast<short *>(out), s);
 }
 
 hipError_t launch_overlap_add_strided(const float *blocks, const HopDesc *desc, uint32_t n_desc, uint32_t ch, float *out,
@@ -2874,9 +2936,7 @@ hipError_t widen_typed(const S *in, uint64_t n, float inv, float *out, hipStream
 
 hipError_t launch_pcm_widen(const void *in, bool wide, uint32_t bits, uint64_t n, float *out, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  // `(1 << (bits - 1)) as f32` on an i32 literal: 32 bits shift into the sign (quirk Q11, glc_wav.cpp)
-  const float max = bits == 32 ? -2147483648.0f : static_cast<float>(1u << (bits - 1));
-  const float inv = 1.0f / max;  // a power of two: exact
+  const float inv = pcm_widen_inv(bits);
   constexpr uint64_t kPiece = uint64_t{1} << 30;  // samples per launch: the grid stays far below its limit
   for (uint64_t at = 0; at < n; at += kPiece) {
     const uint64_t m = std::min(kPiece, n - at);

@@ -812,6 +812,52 @@ int glc_store_compact_device(glc_ctx *ctx,
                              int64_t *d_new_index,
                              uint64_t *d_n_out, uint64_t *d_cursor);
 
+/* ---- integer PCM on the device batch and store paths: S16 / S32 in, S16 out ------------------ */
+
+/* The integer twins of the five device-resident batch calls.  Each follows its float twin's contract word for word -
+ * rounds, launches per round independent of the number of clips, no copy to or from the host, no synchronisation
+ * except for workspace growth, the pinned-table rule, what the call leaves on its context - except where stated here.
+ *
+ * Input side (glc_encode_batch_device_compact_int, glc_roundtrip_batch_device_pcm): `fmt` is GLC_PCM_S16 (int16_t
+ * samples of `bits` = 1..16 bits), GLC_PCM_S32 (int32_t, 1..32) or GLC_PCM_F32 (`bits` ignored: the call forwards
+ * to its float twin), validated as glc_encode_int validates them.  The strides and lengths of the glc_clip_layout
+ * count ELEMENTS of the sample type; d_pcm is aligned to its sample size and to nothing more - odd strides and slices
+ * that start on any element are legal.  Every sample is widened in the gather itself by the rule of
+ * glc_pcm_widen_device (one device function serves both: `(float)s / 2^(bits-1)`, -2^31 for bits == 32), so the blob
+ * of clip i is byte for byte what glc_encode_batch_device_compact stores for the same clip widened by
+ * glc_pcm_widen_device; entries, cursor arithmetic and the round-trip output are identical likewise.  Nothing
+ * outside the clips' true samples is read.  The zeros behind a clip are +0.0, the reference's padding, not widened
+ * integer zeros (no output can tell the two apart).
+ *
+ * Output side (out_fmt == GLC_PCM_S16 and the three _i16 calls): what the float call writes, narrowed as the
+ * reference's 16-bit writers narrow (`(s * 32767.0).clamp(-32768.0, 32767.0) as i16`, NaN -> 0).  The layout counts
+ * int16_t elements, d_out is any 2-byte aligned pointer, no element outside the clips or crops is written.  An
+ * unusable crop of the store draw is 0 over its samples.  glc_decode_compact_last_status and
+ * glc_roundtrip_batch_last_info return exactly the words of the float call.  out_fmt is GLC_PCM_F32 or GLC_PCM_S16;
+ * anything else is GLC_EINVAL.
+ *
+ * Overlap is judged on BYTE extents.  The round trip in place is accepted only when pointer, layout and format are
+ * all the same (S16 -> S16 too); every other overlap, an input and an output of different widths on one buffer
+ * included, is GLC_EINVAL, as are an extent that overlaps the arena, a blob or an index array where the float
+ * twin refuses it. */
+int glc_encode_batch_device_compact_int(glc_ctx *ctx, const void *d_pcm, glc_pcm_format fmt, uint32_t bits,
+                                        const glc_clip_layout *in, void *d_arena, uint64_t arena_bytes,
+                                        uint64_t *d_cursor, glc_store_entry *d_entries);
+int glc_roundtrip_batch_device_pcm(glc_ctx *ctx, const void *d_pcm, glc_pcm_format fmt, uint32_t bits,
+                                   const glc_clip_layout *in, void *d_out, glc_pcm_format out_fmt,
+                                   const glc_clip_layout *out);
+int glc_decode_batch_device_compact_i16(glc_ctx *ctx, const void *const *d_blobs, const uint64_t *blob_bytes,
+                                        const uint64_t *n_samples, int16_t *d_out, const glc_clip_layout *out);
+int glc_decode_crops_device_compact_i16(glc_ctx *ctx, const void *const *d_blobs, const uint64_t *blob_bytes,
+                                        const uint64_t *n_samples, const glc_crop *crops, int16_t *d_out,
+                                        const glc_clip_layout *out);
+int glc_decode_crops_device_store_i16(glc_ctx *ctx,
+                                      const void *d_arena, uint64_t arena_bytes,
+                                      const glc_store_entry *d_entries, const int64_t *d_lengths, uint64_t n_entries,
+                                      uint64_t max_length,
+                                      const int64_t *d_clips, const int64_t *d_starts, uint64_t length,
+                                      int16_t *d_out, const glc_clip_layout *out);
+
 /* ---- tables (for inspection / parity tests) ---------------------------------------------- */
 
 /* Copies of the host tables of a context: MdctTables.cos_table [1024*2048] (row k), window

@@ -325,6 +325,16 @@ class Encoder {
                                    uint64_t *d_cursor, glc_store_entry *d_entries) {
     detail::check(glc_encode_batch_device_compact(ctx_, d_pcm, &in, d_arena, arena_bytes, d_cursor, d_entries), ctx_);
   }
+  // ... from int16_t / int32_t clips holding `bits`-bit PCM (glc_encode_batch_device_compact_int): widened in the
+  // gather, the blobs those of the widened clips byte for byte; the layout counts elements of the sample type
+  void encode_batch_device_compact(const int16_t *d_pcm, uint32_t bits, const glc_clip_layout &in, void *d_arena, uint64_t arena_bytes,
+                                   uint64_t *d_cursor, glc_store_entry *d_entries) {
+    detail::check(glc_encode_batch_device_compact_int(ctx_, d_pcm, GLC_PCM_S16, bits, &in, d_arena, arena_bytes, d_cursor, d_entries), ctx_);
+  }
+  void encode_batch_device_compact(const int32_t *d_pcm, uint32_t bits, const glc_clip_layout &in, void *d_arena, uint64_t arena_bytes,
+                                   uint64_t *d_cursor, glc_store_entry *d_entries) {
+    detail::check(glc_encode_batch_device_compact_int(ctx_, d_pcm, GLC_PCM_S32, bits, &in, d_arena, arena_bytes, d_cursor, d_entries), ctx_);
+  }
   // glc::compact_store_device on this context
   void compact_store_device(void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries, const int64_t *d_lengths,
                             uint64_t n_entries, const uint8_t *d_keep, void *d_dst, uint64_t dst_bytes, glc_store_entry *d_entries_out,
@@ -477,6 +487,28 @@ class Decoder {
     detail::check(glc_decode_crops_device_store(ctx_, d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips,
                                                 d_starts, length, d_out, &out), ctx_);
   }
+  // ... the three calls above as 16-bit PCM, narrowed on the device as decode_i16 narrows (the layout counts int16_t
+  // elements, d_out is any 2-byte aligned pointer; an unusable crop of the store draw is 0)
+  void decode_batch_device_compact_i16(const std::vector<const void *> &d_blobs, const std::vector<uint64_t> &blob_bytes,
+                                       const std::vector<uint64_t> &n_samples, int16_t *d_out, const glc_clip_layout &out) {
+    if (d_blobs.size() != out.n_clips || blob_bytes.size() != out.n_clips || n_samples.size() != out.n_clips)
+      throw Error(GLC_EINVAL, "decode_batch_device_compact_i16: one blob, size and length per clip of the layout");
+    detail::check(glc_decode_batch_device_compact_i16(ctx_, d_blobs.data(), blob_bytes.data(), n_samples.data(), d_out, &out), ctx_);
+  }
+  void decode_crops_device_compact_i16(const std::vector<const void *> &d_blobs, const std::vector<uint64_t> &blob_bytes,
+                                       const std::vector<uint64_t> &n_samples, const std::vector<glc_crop> &crops, int16_t *d_out,
+                                       const glc_clip_layout &out) {
+    if (d_blobs.size() != out.n_clips || blob_bytes.size() != out.n_clips || n_samples.size() != out.n_clips || crops.size() != out.n_clips)
+      throw Error(GLC_EINVAL, "decode_crops_device_compact_i16: one blob, size, length and crop per clip of the layout");
+    detail::check(glc_decode_crops_device_compact_i16(ctx_, d_blobs.data(), blob_bytes.data(), n_samples.data(), crops.data(), d_out, &out),
+                  ctx_);
+  }
+  void decode_crops_device_store_i16(const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries, const int64_t *d_lengths,
+                                     uint64_t n_entries, uint64_t max_length, const int64_t *d_clips, const int64_t *d_starts,
+                                     uint64_t length, int16_t *d_out, const glc_clip_layout &out) {
+    detail::check(glc_decode_crops_device_store_i16(ctx_, d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips,
+                                                    d_starts, length, d_out, &out), ctx_);
+  }
   // glc::compact_store_device on this context
   void compact_store_device(void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries, const int64_t *d_lengths,
                             uint64_t n_entries, const uint8_t *d_keep, void *d_dst, uint64_t dst_bytes, glc_store_entry *d_entries_out,
@@ -552,6 +584,23 @@ class RoundTrip {
   // when d_out == d_pcm and the layouts agree; queued, not synchronised
   void apply_batch_device(const float *d_pcm, const glc_clip_layout &in, float *d_out, const glc_clip_layout &out) {
     detail::check(glc_roundtrip_batch_device(ctx_, d_pcm, &in, d_out, &out), ctx_);
+  }
+  // ... from and to integer PCM (glc_roundtrip_batch_device_pcm): int16_t / int32_t clips of `bits` bits widened in the
+  // gather, float or int16_t out; in place needs the same pointer, layout and format
+  void apply_batch_device(const int16_t *d_pcm, uint32_t bits, const glc_clip_layout &in, float *d_out, const glc_clip_layout &out) {
+    detail::check(glc_roundtrip_batch_device_pcm(ctx_, d_pcm, GLC_PCM_S16, bits, &in, d_out, GLC_PCM_F32, &out), ctx_);
+  }
+  void apply_batch_device(const int16_t *d_pcm, uint32_t bits, const glc_clip_layout &in, int16_t *d_out, const glc_clip_layout &out) {
+    detail::check(glc_roundtrip_batch_device_pcm(ctx_, d_pcm, GLC_PCM_S16, bits, &in, d_out, GLC_PCM_S16, &out), ctx_);
+  }
+  void apply_batch_device(const int32_t *d_pcm, uint32_t bits, const glc_clip_layout &in, float *d_out, const glc_clip_layout &out) {
+    detail::check(glc_roundtrip_batch_device_pcm(ctx_, d_pcm, GLC_PCM_S32, bits, &in, d_out, GLC_PCM_F32, &out), ctx_);
+  }
+  void apply_batch_device(const int32_t *d_pcm, uint32_t bits, const glc_clip_layout &in, int16_t *d_out, const glc_clip_layout &out) {
+    detail::check(glc_roundtrip_batch_device_pcm(ctx_, d_pcm, GLC_PCM_S32, bits, &in, d_out, GLC_PCM_S16, &out), ctx_);
+  }
+  void apply_batch_device(const float *d_pcm, const glc_clip_layout &in, int16_t *d_out, const glc_clip_layout &out) {
+    detail::check(glc_roundtrip_batch_device_pcm(ctx_, d_pcm, GLC_PCM_F32, 32, &in, d_out, GLC_PCM_S16, &out), ctx_);
   }
   // per clip of the last apply_batch_device what last_info gives for that clip alone (synchronises)
   std::vector<glc_roundtrip_info> last_batch_info(uint64_t n_clips) {
