@@ -207,6 +207,9 @@ struct glc_ctx {
   bool screen_judged_any = false;  // a count has been read since the context was created (or the mode set)
   uint32_t screen_last_failed = 0;  // ... and the failed rows of the last one read: picks the repair's transform
   int repair_kind = 0;             // include/glc_debug.h glc_debug_set_encode_repair
+  int bound_kind = 0;              // include/glc_debug.h glc_debug_set_encode_bound
+  uint32_t tap_rows = 0, tap_planes = 0;  // the last screened launch on slot 0: its rows and hf planes (glc_debug_encode_bound_tap)
+  DevBuf bound_tables;             // the matrix form's table image (glc_kernels.h MatrixBound), where the form is built
   uint64_t repair_launches[2] = {0, 0};  // screened launches that took k_mdct_fwd_small_cols / k_mdct_fwd_small_rows
   uint64_t rows_screened = 0;
   hipStream_t probe_stream = nullptr;  // include/glc_debug.h clock probe
@@ -379,6 +382,21 @@ int glc_ctx_create(int device, uint32_t sample_rate, glc_ctx **out) {
   d.cf = h.cf;
   d.noise_floor = h.noise_floor;
   ctx->screen_usable = glc::encode_screen_shape(h.edges.data(), static_cast<uint32_t>(nb), &ctx->screen_shape);
+  d.cos_bf = nullptr;
+  if (ctx->screen_usable && ctx->screen_shape.ne == static_cast<uint32_t>(glc::MatrixBound::kNe)) {
+    // the bf16 pieces of the bound columns depend on the rate's C0 alone: built and uploaded once per context
+    std::vector<uint16_t> img;
+    glc::build_bound_table_image(h, ctx->screen_shape.c0, img);
+    e = ctx->bound_tables.reserve(img.size() * 2);
+    if (e == hipSuccess) e = hipMemcpy(ctx->bound_tables.p, img.data(), img.size() * 2, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      ctx->bound_tables.release();
+      ctx->tables.release();
+      (void)hipStreamDestroy(ctx->own_stream);
+      return hip_fail(nullptr, e, "hipMemcpy(bound tables)");
+    }
+    d.cos_bf = static_cast<const uint16_t *>(ctx->bound_tables.p);
+  }
   *out = ctx.release();
   return GLC_OK;
 }
@@ -410,6 +428,7 @@ void glc_ctx_destroy(glc_ctx *ctx) {
   if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   ctx->tables.release();
+  ctx->bound_tables.release();
   ctx->coef.release();
   ctx->pcm.release();
   ctx->pcm_int.release();
@@ -527,7 +546,9 @@ static hipError_t launch_quantize_decide(glc_ctx *ctx, const float *coef, const 
 // Whether a launch of M rows may take the screened path at all (the mode and the launch's shape; the guard aside).
 static bool screen_may(const glc_ctx *ctx, uint32_t M, uint32_t ch) {
   if (!ctx->screen_usable || ctx->screen_mode == 1) return false;
-  if (ctx->screen_mode == 2) return M >= 256;
+  // (forced on: from one row tile of the form the launch takes - 256 rows, 128 where the matrix form is forced too)
+  if (ctx->screen_mode == 2)
+    return M >= (ctx->bound_kind == 2 && glc::encode_matrix_bound_built(ctx->dev, ctx->screen_shape, ch) ? 128u : 256u);
   return glc::mdct_forward_is_st16(M, ch, ctx->k1_variant);
 }
 
@@ -583,6 +604,15 @@ constexpr uint32_t kScreenRepairLatencyRows = 128;
 static bool screen_latency_repair(const glc_ctx *ctx) {
   if (ctx->repair_kind) return ctx->repair_kind == 2;
   return ctx->screen_judged_any && ctx->screen_last_failed <= kScreenRepairLatencyRows;
+}
+
+// Which form of the transform a screened launch of M rows takes (glc_kernels.h MatrixBound): the matrix form where
+// it is built - the rate's ne, a channel count with a segment loader - and, in the automatic mode, where the launch
+// is one the automatic screen takes at all (mdct_forward_is_st16: 3584 rows and up); the forced kind 2 takes it
+// wherever it is built, kind 1 never.
+static bool screen_matrix_bound(const glc_ctx *ctx, uint32_t M, uint32_t ch) {
+  if (ctx->bound_kind == 1 || !glc::encode_matrix_bound_built(ctx->dev, ctx->screen_shape, ch)) return false;
+  return ctx->bound_kind == 2 || M >= 3584u;
 }
 
 // The screened path's workspace of a coefficient workspace (slot 0 with `coef`, 1 with `coef_b`), reserved where
@@ -650,9 +680,11 @@ static int encode_range_on(glc_ctx *ctx, hipStream_t stream, DevBuf &coef_ws, co
         return fail(ctx, GLC_EINVAL, "glc_encode_range_device: the screen's workspace was not reserved for this launch");
       bool decided = false;
       const bool latency = screen_latency_repair(ctx);
+      const bool matrix = screen_matrix_bound(ctx, M, ch);
+      if (slot == 0) ctx->tap_rows = M, ctx->tap_planes = matrix ? glc::MatrixBound::kGroups : ctx->screen_shape.n_planes;
       GLC_HIP(ctx, glc::launch_encode_screened(ctx->dev, ctx->screen_shape, view, f, M, coef, ctx->screen_ws[slot].p,
                                                static_cast<uint32_t *>(ctx->screen_stat.p) + 8 * slot, ++ctx->screen_seq[slot],
-                                               r, st, &decided, latency));
+                                               r, st, &decided, latency, matrix));
       ++ctx->repair_launches[latency ? 1 : 0];
       if (!decided) GLC_HIP(ctx, glc::launch_decide_raw(ctx->dev, view, f, static_cast<uint32_t>(nf), r, st));
       ctx->rows_screened += M;
@@ -3797,6 +3829,57 @@ int glc_debug_set_encode_screen(glc_ctx *ctx, int mode) {
 int glc_debug_set_encode_repair(glc_ctx *ctx, int kind) {
   if (!ctx || kind < 0 || kind > 2) return fail(ctx, GLC_EINVAL, "glc_debug_set_encode_repair: kind must be 0..2");
   ctx->repair_kind = kind;
+  return GLC_OK;
+}
+
+int glc_debug_set_encode_bound(glc_ctx *ctx, int kind) {
+  if (!ctx || kind < 0 || kind > 2) return fail(ctx, GLC_EINVAL, "glc_debug_set_encode_bound: kind must be 0..2");
+  ctx->bound_kind = kind;
+  return GLC_OK;
+}
+
+int glc_debug_encode_matrix_bound(uint32_t *ne, uint32_t *pieces, uint32_t *products, uint32_t *k_block, uint32_t *seg_blocks,
+                                  uint32_t *planes, double *kappa, double *split_eps, double *budget) {
+  if (!ne || !pieces || !products || !k_block || !seg_blocks || !planes || !kappa || !split_eps || !budget) return GLC_EINVAL;
+  using MB = glc::MatrixBound;
+  *ne = MB::kNe, *pieces = MB::kPieces, *products = MB::kProducts, *k_block = MB::kKBlock, *seg_blocks = MB::kSegBlocks;
+  *planes = MB::kGroups, *kappa = MB::kKappa, *split_eps = MB::kSplitEps, *budget = MB::kBudget;
+  return GLC_OK;
+}
+
+int glc_debug_encode_bound_tap(glc_ctx *ctx, uint32_t rows, float *h, float *a) {
+  if (!ctx || !h || !a || rows == 0 || rows != ctx->tap_rows || !ctx->screen_ws[0].p)
+    return fail(ctx, GLC_EINVAL, "glc_debug_encode_bound_tap: no screened launch of that many rows on this context");
+  DeviceGuard guard(ctx->device);
+  GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const uint64_t stride = (static_cast<uint64_t>(rows) + 255ull) / 256ull * 256ull;
+  std::vector<float> planes((ctx->tap_planes + 1ull) * stride);
+  GLC_HIP(ctx, hipMemcpy(planes.data(), ctx->screen_ws[0].p, planes.size() * 4, hipMemcpyDeviceToHost));
+  for (uint32_t m = 0; m < rows; ++m) {
+    float mx = 0.0f;
+    for (uint32_t p = 0; p < ctx->tap_planes; ++p) mx = std::fmax(mx, planes[p * stride + m]);
+    h[m] = mx;
+    a[m] = planes[ctx->tap_planes * stride + m];
+  }
+  return GLC_OK;
+}
+
+int glc_debug_mfma_bf16(glc_ctx *ctx, const uint16_t *a, const uint16_t *b, const float *c, float *d) {
+  if (!ctx || !a || !b || !c || !d) return fail(ctx, GLC_EINVAL, "glc_debug_mfma_bf16: null argument");
+  DeviceGuard guard(ctx->device);
+  DevBuf buf;
+  GLC_HIP(ctx, buf.reserve(2 * 1024 + 2 * 4096));
+  uint8_t *p = static_cast<uint8_t *>(buf.p);
+  hipError_t e = hipMemcpy(p, a, 1024, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(p + 1024, b, 1024, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(p + 2048, c, 4096, hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+    e = glc::launch_debug_mfma_bf16(reinterpret_cast<const uint16_t *>(p), reinterpret_cast<const uint16_t *>(p + 1024),
+                                    reinterpret_cast<const float *>(p + 2048), reinterpret_cast<float *>(p + 2048 + 4096), ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = hipMemcpy(d, p + 2048 + 4096, 4096, hipMemcpyDeviceToHost);
+  buf.release();
+  GLC_HIP(ctx, e);
   return GLC_OK;
 }
 

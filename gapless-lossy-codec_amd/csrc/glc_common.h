@@ -45,6 +45,12 @@ struct HostTables {
 };
 
 void build_host_tables(uint32_t sample_rate, HostTables &t);
+// The table operand of the matrix form of the screened transform (glc_kernels.h MatrixBound): the two bf16 pieces
+// t1 = bf16_rn(T), t2 = bf16_rn(T - t1) of T[k][i] for k >= c0 (a multiple of 32), from t.cos_table, in the order
+// the instruction's fragments are loaded: [K-block of 16 i][tile of 32 columns][piece][lane 0..63][8 values],
+// lane l of a fragment holding column tile * 32 + l % 32 at i = 16 block + 8 (l / 32) .. + 7.
+void build_bound_table_image(const HostTables &t, uint32_t c0, std::vector<uint16_t> &out);
+uint16_t bf16_round_nearest_even(float x);  // finite x; a value that rounds past the largest bf16 gives infinity
 
 // Padding arithmetic of Encoder::encode, src/codec.rs:433-455.
 GLC_HD inline glc_plan plan_encode(uint64_t n_samples, uint16_t channels) {

@@ -20,7 +20,37 @@ struct DeviceTables {
   const uint32_t *edges;   // [n_bands+1]
   uint32_t n_bands;
   float norm, cf, noise_floor;
+  const uint16_t *cos_bf;  // bf16 pieces of T[k][i], k >= C0, in fragment order (MatrixBound below); null where not built
 };
+
+// The matrix form of the screened transform (glc_mdct_fwd.hpp k_mdct_mx_st): the bound sums e_k of
+// the columns k >= C0 on the bf16 matrix pipe.  Each f32 operand is split a = a1 + a2 + r, a1 = bf16_rn(a), a2 =
+// bf16_rn(a - a1); e_k sums the kProducts piece products a1 t1 + a1 t2 + a2 t1 with one v_mfma_f32_32x32x16_bf16 per
+// product and K-block of kKBlock i-steps.  A chain of accumulating instructions is cut every kSegBlocks K-blocks: the
+// segment's accumulator is added to a per-output f32 total and cleared.  The error budget, per unit of A = sum |xw|:
+//   split         kSplitEps = 3 * 2^-16 (+ O(2^-24)): the dropped a2 t2 + r_a t + a r_t, |T| <= 1
+//   accumulation  kSegBlocks * kProducts instructions per chain, each within kKappa (|C| + sum |p|), kKappa = 17 * 2^-23
+//                 (any f32 summation of 16 products and C, rounding or truncating, in any order)
+//   totals        kSegments f32 adds, 2^-24 each
+// and the sum must stay within gamma_2048 = 2048 u / (1 - 2048 u), the half of kScreenCErr that belongs to e_k.
+struct MatrixBound {
+  static constexpr int kNe = 6;                    // the form is built for C0 = 384 (44.1 and 48 kHz)
+  static constexpr int kPieces = 2;                // bf16 pieces kept per operand
+  static constexpr int kProducts = 3;              // piece products summed
+  static constexpr int kKBlock = 16;               // i-steps per instruction
+  static constexpr int kSegBlocks = 8;             // K-blocks per accumulation segment
+  static constexpr int kSegments = 2048 / (kKBlock * kSegBlocks);
+  static constexpr int kRows = 128;                // rows per workgroup
+  static constexpr int kGroups = 4;                // workgroups per row tile = hf planes of a launch
+  static constexpr int kTile = 32;                 // bound columns per fragment
+  static constexpr double kKappa = 17.0 / 8388608.0;
+  static constexpr double kSplitEps = 3.0 / 65536.0;
+  static constexpr double kGamma = 2048.0 / 16777216.0 / (1.0 - 2048.0 / 16777216.0);
+  static constexpr double kBudget = kSplitEps + kSegBlocks * kProducts * kKappa + kSegments / 16777216.0;
+  static_assert(kBudget <= kGamma, "the matrix form's e_k must stay within gamma_2048 A of the real sum");
+};
+// bytes of the fragment-ordered table image for a last band that starts at column c0 (a multiple of 64)
+inline uint64_t matrix_bound_table_bytes(uint32_t c0) { return 128ull * ((1024u - c0) / 32u) * 2ull * 64ull * 16ull; }
 
 // View of interleaved PCM on the device (whole stream or a shard with halo).
 struct PcmView {
@@ -66,7 +96,14 @@ uint64_t encode_screen_bytes(uint32_t M, const ScreenShape &sh);
 // device-visible host words {failed rows, rows, seq, -, u64 failed rows so far, ...} the last launch writes.
 hipError_t launch_encode_screened(const DeviceTables &t, const ScreenShape &sh, const PcmView &pcm, uint64_t frame_begin,
                                   uint32_t M, float *coef, void *workspace, uint32_t *host_stat, uint32_t seq,
-                                  uint8_t *records, hipStream_t s, bool *decided, bool latency_repair = false);
+                                  uint8_t *records, hipStream_t s, bool *decided, bool latency_repair = false,
+                                  bool matrix_bound = false);
+// true where the matrix form (MatrixBound) exists for a launch: the rate's ne, a channel count with a segment
+// loader, and the table image uploaded
+bool encode_matrix_bound_built(const DeviceTables &t, const ScreenShape &sh, uint32_t ch);
+// One v_mfma_f32_32x32x16_bf16 of one wave on given operands (the instruction the matrix form accumulates with):
+// a, b = 64 lanes x 8 bf16 (lane l: index l % 32, K slots 8 (l / 32) .. + 7), c, d = 64 lanes x 16 f32.  Device pointers.
+hipError_t launch_debug_mfma_bf16(const uint16_t *a, const uint16_t *b, const float *c, float *d, hipStream_t s);
 // K3: per-frame raw-vs-compressed decision and raw fallback plane (channel counts K2 does not decide).
 hipError_t launch_decide_raw(const DeviceTables &t, const PcmView &pcm, uint64_t frame_begin,
                              uint32_t n_frames, uint8_t *records, hipStream_t s);

@@ -8,7 +8,7 @@
 // appear in the MDCT kernels (checked at build time by tools/check_isa.py) - with one exception that
 // never produces a value of the stream: the bound waves of k_mdct_mix_st, and the bound column pairs of its hybrid
 // waves, accumulate an UPPER BOUND of last-band magnitudes with v_pk_fma_f32 (the screen, above k_quantize; DESIGN
-// section 2).
+// section 2), and the matrix waves of k_mdct_mx_st the same bound with v_mfma_f32_32x32x16_bf16.
 //
 // Reference loops replaced (file:line into /root/reference):
 //   K1 k_mdct_fwd      src/codec.rs:476-481 (window) + :359-374 (mdct_block)
@@ -72,7 +72,9 @@ constexpr int kQRows = 4;  // rows per wave
 // The screen.  With L = edges[n_bands - 1] the start of the last band and C0 = L rounded up to
 // 64, the mixed-role K1 leaves exact coefficients only below C0; of a column k >= C0 it leaves e_k, the same sum
 // with fused multiply-adds, as max |e| per PLANE - the bound columns of one wave of the transform: 8 of them, or
-// the 2 / 4 / 6 of a hybrid wave; the screen only ever takes the maximum over all planes, so which columns a plane
+// the 2 / 4 / 6 of a hybrid wave, or the 160 of a workgroup of the matrix form (k_mdct_mx_st, whose e_k is a sum of
+// bf16 piece products within the same gamma_2048 sum |xw| of the real sum: glc_kernels.h MatrixBound); the screen only
+// ever takes the maximum over all planes, so which columns a plane
 // holds is the transform's business - and A = sum_i |fl(x_i w_i)|, the ascending f32 sum.  The stream's value is
 // c_k = fl(s_k norm) with s_k the ascending f32 sum of the rounded products.  Both s_k and e_k differ from the
 // real sum of xw_i T_ki by at most gamma_2048 sum_i |xw_i| |T_ki| (2048 roundings each at most: product and add
@@ -2371,6 +2373,30 @@ bool encode_screen_shape(const uint32_t *edges, uint32_t n_bands, ScreenShape *s
 }
 
 namespace {
+__global__ __launch_bounds__(64) void k_debug_mfma_bf16(const uint16_t *__restrict__ a, const uint16_t *__restrict__ b,
+                                                        const float *__restrict__ c, float *__restrict__ d) {
+  const int lane = threadIdx.x;
+  const k1::bf16x8 av = __builtin_bit_cast(k1::bf16x8, reinterpret_cast<const uint4 *>(a)[lane]);
+  const k1::bf16x8 bv = __builtin_bit_cast(k1::bf16x8, reinterpret_cast<const uint4 *>(b)[lane]);
+  k1::f32x16 acc;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) acc[e] = c[lane * 16 + e];
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc, 0, 0, 0);
+#pragma unroll
+  for (int e = 0; e < 16; ++e) d[lane * 16 + e] = acc[e];
+}
+}  // namespace
+
+hipError_t launch_debug_mfma_bf16(const uint16_t *a, const uint16_t *b, const float *c, float *d, hipStream_t s) {
+  hipLaunchKernelGGL(k_debug_mfma_bf16, dim3(1), dim3(64), 0, s, a, b, c, d);
+  return hipGetLastError();
+}
+
+bool encode_matrix_bound_built(const DeviceTables &t, const ScreenShape &sh, uint32_t ch) {
+  return t.cos_bf && sh.ne == static_cast<uint32_t>(MatrixBound::kNe) && (ch == 1 || ch == 2 || ch == 4 || ch == 8);
+}
+
+namespace {
 inline uint64_t screen_stride(uint32_t M) { return (static_cast<uint64_t>(M) + 255ull) / 256ull * 256ull; }
 }  // namespace
 
@@ -2381,15 +2407,26 @@ uint64_t encode_screen_bytes(uint32_t M, const ScreenShape &sh) {
 
 hipError_t launch_encode_screened(const DeviceTables &t, const ScreenShape &sh, const PcmView &pcm, uint64_t frame_begin,
                                   uint32_t M, float *coef, void *workspace, uint32_t *host_stat, uint32_t seq,
-                                  uint8_t *records, hipStream_t s, bool *decided, bool latency_repair) {
+                                  uint8_t *records, hipStream_t s, bool *decided, bool latency_repair, bool matrix_bound) {
   *decided = pcm.ch == 1 || pcm.ch == 2 || pcm.ch == 4;
   if (M == 0) return hipSuccess;
   const uint64_t stride = screen_stride(M);
   float *hf = static_cast<float *>(workspace);
+  // the workspace is carved for the FMA form, the larger of the two: the matrix form's 4 planes and its A plane lie
+  // at the front of the FMA form's, the flags and counts where they always are
   unsigned *row_flag = reinterpret_cast<unsigned *>(hf + (sh.n_planes + 1ull) * stride);
   unsigned *wave_fail = row_flag + stride;
+  static_assert(MatrixBound::kGroups <= 8, "the matrix form's planes fit in those of any FMA form (8 at the least)");
+  if (matrix_bound && !encode_matrix_bound_built(t, sh, pcm.ch)) return hipErrorInvalidValue;
+  const unsigned n_planes = matrix_bound ? static_cast<unsigned>(MatrixBound::kGroups) : sh.n_planes;
   hipError_t e;
-  switch (pcm.ch) {
+  if (matrix_bound) switch (pcm.ch) {
+    case 1: e = k1::launch_mx_st<1>(t, pcm, frame_begin, M, coef, hf, stride, s); break;
+    case 2: e = k1::launch_mx_st<2>(t, pcm, frame_begin, M, coef, hf, stride, s); break;
+    case 4: e = k1::launch_mx_st<4>(t, pcm, frame_begin, M, coef, hf, stride, s); break;
+    default: e = k1::launch_mx_st<8>(t, pcm, frame_begin, M, coef, hf, stride, s); break;
+  }
+  else switch (pcm.ch) {
     case 1: e = k1::launch_mix_st<1>(t, pcm, frame_begin, M, coef, sh.ne, sh.hp, hf, stride, s); break;
     case 2: e = k1::launch_mix_st<2>(t, pcm, frame_begin, M, coef, sh.ne, sh.hp, hf, stride, s); break;
     case 4: e = k1::launch_mix_st<4>(t, pcm, frame_begin, M, coef, sh.ne, sh.hp, hf, stride, s); break;
@@ -2397,7 +2434,7 @@ hipError_t launch_encode_screened(const DeviceTables &t, const ScreenShape &sh, 
     default: e = k1::launch_mix_st<0>(t, pcm, frame_begin, M, coef, sh.ne, sh.hp, hf, stride, s); break;
   }
   if (e != hipSuccess) return e;
-  const ScreenArgs sa{hf, row_flag, wave_fail, host_stat, stride, sh.c0, sh.l0, sh.n_planes, seq};
+  const ScreenArgs sa{hf, row_flag, wave_fail, host_stat, stride, sh.c0, sh.l0, n_planes, seq};
   const unsigned long long hdr = record_header_bytes(pcm.ch), rec = record_bytes(pcm.ch);
   const dim3 grid((M + 4 * kQRows - 1) / (4 * kQRows));
   const long long fb = static_cast<long long>(frame_begin);

@@ -25,6 +25,9 @@
 //                      both kinds, so that the four SIMDs issue the same number of packed operations.  With
 //                      k_mdct_fwd_small_cols, the 2 x 2 short-clip kernel over a column range and only the row tiles
 //                      that hold a flagged row: the exact columns of the rows that failed the screen.
+//   k_mdct_mx_st       the mixed-role form with the bound on the bf16 matrix pipe, for C0 = 384 (44.1 / 48 kHz) and 1 / 2 /
+//                      4 / 8 channels: 128 x 256 tile, twelve exact waves with 2 rows x 8 columns per lane (the exact
+//                      kernel's chain per column), four matrix waves with 32 rows x 160 bound columns each.
 //   k_mdct_fwd_small_rows  the same repair built for latency, for launches in which few rows failed: one wave per
 //                      (two failed rows, 64 columns) found from the quantiser's fail counts on a fixed grid, the rows in
 //                      LDS, the table streamed by dwordx4 loads 112 i-steps ahead.
@@ -1494,6 +1497,318 @@ inline hipError_t launch_st(const DeviceTables &t, const PcmView &pcm, uint64_t 
   const unsigned m_tiles = (M + 255) / 256;
   hipLaunchKernelGGL((k_mdct_fwd_st<MINW, CH, PRIO, D, NW, BK, ABL, STAMP>), dim3(m_tiles * (kHopI / (8 * NW))), dim3(NW * 64), 0,
                      s, t, pcm, static_cast<long long>(frame_begin), M, coef, stamps);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// k_mdct_mx_st: the MATRIX form of the mixed-role transform, for C0 = 384 (ne = 6: 44.1 and 48 kHz) and the channel
+// counts of the segment loader.  The exact columns keep k_mdct_fwd_st's arithmetic - the same per-column chain of
+// separately rounded multiplies and adds, the table values by scalar loads, mac2rows_st - and the bound columns
+// leave the vector ALU: their sums e_k run on the bf16 matrix pipe, which executes beside it (DESIGN section 2,
+// glc_kernels.h MatrixBound for the split, the segments and the error budget).
+//   tile      128 rows x (96 exact + 160 bound) columns, 1024 threads, one workgroup per CU; workgroup j = 0 .. 3 of
+//             a row tile owns exact columns [96 j, 96 j + 96) and bound columns [384 + 160 j, 384 + 160 j + 160)
+//   waves     0 .. 11 exact: 8 columns each, the lane's 2 rows (2 lane, 2 lane + 1) - 16 packed operations per i-step,
+//             three such waves on every SIMD;  12 .. 15 matrix, one per SIMD: 32 rows x the 160 bound columns as five
+//             32 x 32 tiles, 15 v_mfma_f32_32x32x16_bf16 per K-block of 16 i-steps
+//   operands  the windowed samples go through the 3-slot LDS ring of k_mdct_fwd_st (a stage = a K-block = 16 i-steps,
+//             published by one barrier in the middle of the stage before).  The matrix waves read their rows' 8
+//             samples per lane from the same stage, split them into two bf16 pieces (B operand: lane = row), and take
+//             the table pieces - A operand, lane = column - from the fragment-ordered image DeviceTables::cos_bf:
+//             10 KiB per workgroup and K-block, copied global -> LDS by the matrix waves (global_load_lds_dwordx4, one
+//             instruction per fragment) two stages ahead into a 3-slot ring of its own
+//   totals    80 accumulators per lane leave no registers for the segment totals at four waves per SIMD: they live in
+//             LDS (80 KiB, each matrix wave its own 20 KiB, read-add-written every 8 K-blocks)
+//   out       coefficients of the exact columns; hf[j][row] = max |total| over the workgroup's 160 bound columns
+//             (+inf where a total is not finite: fmaxf in the quantiser would drop a NaN) - 4 planes - and, from
+//             workgroup j = 0, A = sum |x w| at hf[4][row]: 16 partial sums per row (the lane's 8 i of every K-block,
+//             then the two lane halves), any order being covered by the screen's slack
+// LDS: 24.75 KiB samples + 8 KiB window + 30 KiB table pieces + 80 KiB totals = 142.75 KiB of 160.
+// ------------------------------------------------------------------------------------------
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+struct MxOps {  // operands of 4 i-steps of an exact wave: 2 rows of this lane, 8 columns of this wave
+  f32x2 a[4];
+  u32x8 b[4];
+};
+template <int II, int AS>
+__device__ __forceinline__ void mx_fetch_a(f32x2 &a, unsigned a_addr) {
+  asm volatile("ds_read_b64 %0, %1 offset:%c2" : "=&v"(a) : "v"(a_addr), "i"(II * AS * 4) : "memory");
+}
+template <int II, int AS>
+__device__ __forceinline__ void mx_fetch(MxOps &o, unsigned a_addr, const unsigned *brow) {
+  st_fetch_b<II>(o.b[0], brow);
+  st_fetch_b<II + 1>(o.b[1], brow);
+  st_fetch_b<II + 2>(o.b[2], brow);
+  st_fetch_b<II + 3>(o.b[3], brow);
+  mx_fetch_a<II, AS>(o.a[0], a_addr);
+  mx_fetch_a<II + 1, AS>(o.a[1], a_addr);
+  mx_fetch_a<II + 2, AS>(o.a[2], a_addr);
+  mx_fetch_a<II + 3, AS>(o.a[3], a_addr);
+}
+__device__ __forceinline__ void mx_wait(MxOps &o) {
+  asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(o.b[0]), "+s"(o.b[1]), "+s"(o.b[2]), "+s"(o.b[3])::"memory");
+  asm volatile("" : "+v"(o.a[0]), "+v"(o.a[1]), "+v"(o.a[2]), "+v"(o.a[3])::"memory");
+}
+__device__ __forceinline__ void mx_mac(f32x2 (&acc)[2][4], const MxOps &o) {
+#pragma unroll
+  for (int d = 0; d < 4; ++d) mac2rows_st(acc[0], acc[1], o.a[d], o.b[d].s01, o.b[d].s23, o.b[d].s45, o.b[d].s67);
+}
+// two f32 -> their bf16 roundings to nearest even, packed (lo in bits 0..15)
+__device__ __forceinline__ unsigned mx_cvt_pk_bf16(float lo, float hi) {
+  unsigned r;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+  return r;
+}
+
+template <int CH>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void k_mdct_mx_st(DeviceTables tb, PcmView pcm, long long frame_begin, unsigned M, float *__restrict__ coef,
+                  float *__restrict__ hf, unsigned long long hf_stride) {
+  using MB = MatrixBound;
+  static_assert(CH == 1 || CH == 2 || CH == 4 || CH == 8, "segment loader shapes");
+  constexpr int BM = MB::kRows, BK = MB::kKBlock, RING = 3, NE = MB::kNe;
+  constexpr int kAS = BM + 4;                           // the bank spread of k_mdct_fwd_st's A tile (132 = 4 mod 64)
+  constexpr int kExactWaves = 12, kExactCols = 8 * kExactWaves;
+  constexpr int kTiles = (kHopI - 64 * NE) / MB::kTile / MB::kGroups;  // 32-column tiles per workgroup: 5
+  constexpr int kTilesAll = kTiles * MB::kGroups;
+  constexpr int kFrags = kTiles * MB::kPieces;          // 1 KiB fragments per workgroup and K-block: 10
+  constexpr int kStages = kFrameI / BK;
+  constexpr int kLoaders = BM * BK / 4;                 // lanes of the segment loader: one dwordx4 each
+  static_assert(kExactCols * MB::kGroups == 64 * NE && kTiles * MB::kGroups * MB::kTile == kHopI - 64 * NE, "column map");
+  static_assert(kLoaders == 512 && kStages % MB::kSegBlocks == 0, "staging shape");
+  __shared__ __attribute__((aligned(16))) float As[RING][BK * kAS];
+  __shared__ __attribute__((aligned(16))) float Ws[kFrameI];
+  __shared__ __attribute__((aligned(16))) uint4 Bt[RING][kFrags * 64];
+  __shared__ __attribute__((aligned(16))) f32x4 Tot[4][kTiles * 4][64];
+
+  const int tid = threadIdx.x;
+  // XCD-aware tile map (speed only): the workgroups of a row tile on one XCD, where the grid divides by 8
+  const unsigned g = gridDim.x % 8u ? blockIdx.x : (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  const int j = g % MB::kGroups;
+  const int m0 = (g / MB::kGroups) * BM;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = tid & 63;
+
+  for (int i = tid; i < kFrameI; i += 1024) Ws[i] = tb.window[i];
+
+  const long long f0 = frame_begin + m0 / CH;
+  const long long e_first = (f0 * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * CH;
+  long long e_end = static_cast<long long>(pcm.t_count) * CH;
+  const long long n_rel = static_cast<long long>(pcm.n_samples) - static_cast<long long>(pcm.t0) * CH;
+  if (e_end > n_rel) e_end = n_rel;
+  const long long e_base = e_first < 0 ? 0 : e_first;
+  long long e_cnt = e_end - e_base;
+  if (e_cnt < 0) e_cnt = 0;
+  if (e_cnt > (1ll << 28)) e_cnt = 1ll << 28;
+  const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float *>(pcm.p + e_base), 0, static_cast<int>(e_cnt * 4), 0x00020000);
+
+  // segment loader (waves 0 .. 7): lane -> (frame seg_fl of the tile, 4 consecutive floats of its BK x CH segment)
+  constexpr int kSegLanes = BK / 4 * CH;
+  const bool loader = wave < kLoaders / 64;
+  const int seg_fl = tid / kSegLanes;
+  const int seg_o = (tid % kSegLanes) * 4;
+  unsigned a_off = 0x80000000u;  // out-of-range row: every load returns 0
+  {
+    const unsigned row0 = m0 + seg_fl * CH;
+    if (loader && row0 < M) {
+      const long long f = frame_begin + row0 / CH;
+      const long long e_row = (f * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * CH;
+      a_off = static_cast<unsigned>((e_row - e_base + seg_o) * 4);
+    }
+  }
+  f32x4 a_seg = {0.f, 0.f, 0.f, 0.f};
+  auto issue_a = [&](int i0) {  // asm: hipcc must not count these loads (see lds_fetch4)
+    if (!loader) return;
+    const unsigned o = a_off + static_cast<unsigned>(i0) * static_cast<unsigned>(CH * 4);
+    asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=&v"(a_seg) : "v"(o), "s"(a_rsrc) : "memory");
+  };
+  auto store_a = [&](int i0, int slot) {
+    if (!loader) return;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int e = seg_o + q;  // float e of the segment: sample i = e / CH of channel e % CH
+      const int ii = e / CH;
+      As[slot][ii * kAS + seg_fl * CH + e % CH] = mul_rn(a_seg[q], Ws[i0 + ii]);  // block[i] = slice[i]*window[i], :480
+    }
+  };
+  auto wait_staged = [&]() { asm volatile("s_waitcnt vmcnt(0)" : "+v"(a_seg)::"memory"); };
+
+  if (wave < kExactWaves) {
+    // ---------------------------------------------------------------- exact waves
+    f32x2 acc[2][4];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc[r][c] = f32x2{0.0f, 0.0f};
+    __syncthreads();  // Ws
+    issue_a(0);
+    wait_staged();
+    store_a(0, 0);
+    const unsigned a_lds0 = static_cast<unsigned>(reinterpret_cast<uintptr_t>(&As[0][lane * 2]));
+    const int col0 = kExactCols * j + 8 * wave;
+    const unsigned *b_base = reinterpret_cast<const unsigned *>(tb.cos_t) + col0;
+    issue_a(BK);  // PCM of stage 1 into registers
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __syncthreads();
+    MxOps X, Y;
+    mx_fetch<0, kAS>(X, a_lds0, b_base);
+    mx_wait(X);
+#pragma unroll 1
+    for (int s = 0; s < kStages; ++s) {
+      __builtin_amdgcn_s_setprio(0);  // half-way between two barriers
+      const int slot = s % 3, nslot = (s + 1) % 3;
+      const unsigned a_addr = a_lds0 + slot * (BK * kAS * 4);
+      const unsigned a_next = a_lds0 + nslot * (BK * kAS * 4);
+      const unsigned *brow = b_base + static_cast<size_t>(s) * (BK * kHopI);
+      const unsigned *brow_next = b_base + static_cast<size_t>((s + 1) & (kStages - 1)) * (BK * kHopI);
+      mx_fetch<4, kAS>(Y, a_addr, brow);
+      mx_mac(acc, X);
+      mx_wait(Y);
+      mx_fetch<8, kAS>(X, a_addr, brow);
+      mx_mac(acc, Y);
+      // the hand-off, as in st_body: the PCM registers of stage s+1 -> LDS, barrier, PCM loads of stage s+2
+      wait_staged();
+      store_a(((s + 1) & (kStages - 1)) * BK, nslot);
+      mx_wait(X);
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_s_setprio(1);
+      issue_a(((s + 2) & (kStages - 1)) * BK);
+      mx_fetch<12, kAS>(Y, a_addr, brow);
+      mx_mac(acc, X);
+      mx_wait(Y);
+      mx_fetch<0, kAS>(X, a_next, brow_next);
+      mx_mac(acc, Y);
+      mx_wait(X);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the wrap-around prefetch
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const unsigned row = m0 + lane * 2 + r;
+      if (row >= M) continue;
+      float *dst = coef + static_cast<size_t>(row) * kHopI + col0;
+      float4 o;
+      o.x = mul_rn(acc[r][0].x, tb.norm); o.y = mul_rn(acc[r][0].y, tb.norm);
+      o.z = mul_rn(acc[r][1].x, tb.norm); o.w = mul_rn(acc[r][1].y, tb.norm);
+      *reinterpret_cast<float4 *>(dst) = o;
+      o.x = mul_rn(acc[r][2].x, tb.norm); o.y = mul_rn(acc[r][2].y, tb.norm);
+      o.z = mul_rn(acc[r][3].x, tb.norm); o.w = mul_rn(acc[r][3].y, tb.norm);
+      *reinterpret_cast<float4 *>(dst + 4) = o;
+    }
+    return;
+  }
+
+  // ------------------------------------------------------------------ matrix waves
+  __builtin_amdgcn_s_setprio(3);  // little to issue, and the other twelve waves wait for it at every barrier
+  const int mw = wave - kExactWaves, half = lane >> 5, idx = lane & 31;
+  f32x16 acc[kTiles];
+#pragma unroll
+  for (int c = 0; c < kTiles; ++c)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[c][e] = 0.0f;
+#pragma unroll
+  for (int q = 0; q < kTiles * 4; ++q) Tot[mw][q][lane] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // the workgroup's fragments of K-block kb are 10 consecutive KiB of the image; this wave copies mw, mw + 4, mw + 8
+  const uint4 *img = reinterpret_cast<const uint4 *>(tb.cos_bf) + static_cast<size_t>(kTiles * j * MB::kPieces) * 64 + lane;
+  auto issue_t = [&](int kb, int slot) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      const int fr = mw + 4 * q;
+      if (fr < kFrags)
+        __builtin_amdgcn_global_load_lds(img + (static_cast<size_t>(kb) * (kTilesAll * MB::kPieces) + fr) * 64, &Bt[slot][fr * 64],
+                                         16, 0, 0);
+    }
+  };
+  __syncthreads();  // Ws
+  issue_t(0, 0);
+  issue_t(1, 1);
+  issue_a(BK);  // (no loader among the matrix waves: the calls keep the two roles' hand-offs alike)
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  __syncthreads();
+  float asum = 0.0f;
+#pragma unroll 1
+  for (int s = 0; s < kStages; ++s) {
+    const int slot = s % 3;
+    // this lane's row 32 mw + idx, i-steps 8 half .. 8 half + 7 of the K-block
+    const float *ax = &As[slot][(8 * half) * kAS + 32 * mw + idx];
+    float x[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[e] = ax[e * kAS];
+    u32x4 hi, lo;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      asum = add_rn(asum, add_rn(__builtin_fabsf(x[2 * p]), __builtin_fabsf(x[2 * p + 1])));
+      const unsigned h = mx_cvt_pk_bf16(x[2 * p], x[2 * p + 1]);
+      hi[p] = h;
+      // a - a1 is exact in f32 (a1 holds the leading 8 bits of a, rounded)
+      const float r0 = add_rn(x[2 * p], -__builtin_bit_cast(float, h << 16));
+      const float r1 = add_rn(x[2 * p + 1], -__builtin_bit_cast(float, h & 0xFFFF0000u));
+      lo[p] = mx_cvt_pk_bf16(r0, r1);
+    }
+    const bf16x8 x1 = __builtin_bit_cast(bf16x8, hi), x2 = __builtin_bit_cast(bf16x8, lo);
+#pragma unroll
+    for (int c = 0; c < kTiles; ++c) {
+      const bf16x8 t1 = __builtin_bit_cast(bf16x8, Bt[slot][(2 * c) * 64 + lane]);
+      const bf16x8 t2 = __builtin_bit_cast(bf16x8, Bt[slot][(2 * c + 1) * 64 + lane]);
+      acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t1, x1, acc[c], 0, 0, 0);
+      acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t2, x1, acc[c], 0, 0, 0);
+      acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t1, x2, acc[c], 0, 0, 0);
+    }
+    if (s % MB::kSegBlocks == MB::kSegBlocks - 1) {  // the segment ends: total += accumulator, accumulator = 0
+#pragma unroll
+      for (int c = 0; c < kTiles; ++c)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          f32x4 t = Tot[mw][c * 4 + v][lane];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            t[e] = add_rn(t[e], acc[c][v * 4 + e]);
+            acc[c][v * 4 + e] = 0.0f;
+          }
+          Tot[mw][c * 4 + v][lane] = t;
+        }
+    }
+    // the hand-off (the exact waves' is in the middle of their stage s): stage s+1's samples were staged by waves
+    // 0 .. 7; this wave's table pieces of stage s+1 have landed; behind the barrier the pieces of stage s+2 set out
+    // into the slot stage s-1 was read from
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    issue_t((s + 2) & (kStages - 1), (s + 2) % 3);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the wrap-around prefetch
+  float h = 0.0f;
+  bool bad = false;
+#pragma unroll
+  for (int q = 0; q < kTiles * 4; ++q) {
+    const f32x4 t = Tot[mw][q][lane];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float a = __builtin_fabsf(t[e]);
+      bad = bad || !(a <= 3.4028234663852886e38f);  // an infinity or a NaN: the row must fail
+      h = fmaxf(h, a);
+    }
+  }
+  if (bad) h = __builtin_inff();
+  h = fmaxf(h, __shfl_xor(h, 32));
+  asum = add_rn(asum, __shfl_xor(asum, 32));
+  if (half == 0) {
+    const size_t at = static_cast<size_t>(m0) + 32 * mw + idx;
+    hf[static_cast<unsigned>(j) * hf_stride + at] = h;
+    if (j == 0) hf[static_cast<unsigned>(MB::kGroups) * hf_stride + at] = asum;
+  }
+}
+
+template <int CH>
+inline hipError_t launch_mx_st(const DeviceTables &t, const PcmView &pcm, uint64_t frame_begin, uint32_t M, float *coef,
+                               float *hf, uint64_t hf_stride, hipStream_t s) {
+  if (M == 0) return hipSuccess;
+  if (pcm.ch != static_cast<uint32_t>(CH) || !t.cos_bf) return hipErrorInvalidValue;
+  if (hf_stride < (M + MatrixBound::kRows - 1) / MatrixBound::kRows * MatrixBound::kRows) return hipErrorInvalidValue;
+  const dim3 grid((M + MatrixBound::kRows - 1) / MatrixBound::kRows * MatrixBound::kGroups), block(1024);
+  const unsigned long long st = hf_stride;
+  hipLaunchKernelGGL((k_mdct_mx_st<CH>), grid, block, 0, s, t, pcm, static_cast<long long>(frame_begin), M, coef, hf, st);
   return hipGetLastError();
 }
 

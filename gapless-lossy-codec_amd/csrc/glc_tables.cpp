@@ -7,6 +7,7 @@
 // would define a different transform.  They are therefore built once on the
 // host, in binary32 with contraction off, and uploaded.
 #include <cmath>
+#include <cstring>
 
 #include "glc_common.h"
 
@@ -104,6 +105,32 @@ void build_host_tables(uint32_t sample_rate, HostTables &t) {
   for (uint32_t k = 0; k < kHop; ++k) t.indiv[k] = 1.0f / std::fmax(t.weights[k], 0.1f);
   t.cf = std::fmax(1.0f - kQuality, 0.01f);
   t.noise_floor = powf(10.0f, kNoiseFloorDb / 20.0f);  // src/codec.rs:277
+}
+
+uint16_t bf16_round_nearest_even(float x) {
+  uint32_t u;
+  std::memcpy(&u, &x, 4);
+  u += 0x7FFFu + ((u >> 16) & 1u);
+  return static_cast<uint16_t>(u >> 16);
+}
+
+void build_bound_table_image(const HostTables &t, uint32_t c0, std::vector<uint16_t> &out) {
+  const uint32_t tiles = (kHop - c0) / 32;
+  out.assign(static_cast<size_t>(kFrame / 16) * tiles * 2 * 64 * 8, 0);
+  size_t at = 0;
+  for (uint32_t kb = 0; kb < kFrame / 16; ++kb)
+    for (uint32_t tile = 0; tile < tiles; ++tile)
+      for (uint32_t piece = 0; piece < 2; ++piece)
+        for (uint32_t lane = 0; lane < 64; ++lane)
+          for (uint32_t e = 0; e < 8; ++e) {
+            const uint32_t k = c0 + tile * 32 + lane % 32, i = kb * 16 + 8 * (lane / 32) + e;
+            const float v = t.cos_table[static_cast<size_t>(k) * kFrame + i];
+            const uint16_t h1 = bf16_round_nearest_even(v);
+            uint32_t hb = static_cast<uint32_t>(h1) << 16;
+            float t1;
+            std::memcpy(&t1, &hb, 4);
+            out[at++] = piece == 0 ? h1 : bf16_round_nearest_even(v - t1);  // v - t1 is exact in f32
+          }
 }
 
 }  // namespace glc

@@ -79,6 +79,29 @@ int glc_debug_set_encode_repair(glc_ctx *ctx, int kind);
  * nothing is waited for. */
 int glc_debug_encode_repair_stats(glc_ctx *ctx, uint64_t *launches_tiles, uint64_t *launches_latency);
 
+/* Which form of the mixed-role transform a screened launch takes (csrc/glc_kernels.h MatrixBound):
+ *   0  automatic: the matrix form (k_mdct_mx_st: the bound sums on the bf16 matrix pipe) where it is built - 44.1 and
+ *      48 kHz, 1 / 2 / 4 / 8 channels - for launches of 3584 rows and up, the FMA form (k_mdct_mix_st) everywhere else
+ *   1  the FMA form for every screened launch
+ *   2  the matrix form wherever it is built, whatever the row count (and with the screen forced on as well, mode 2 of
+ *      glc_debug_set_encode_screen, from 128 rows - one row tile of the form - instead of 256)
+ * The setting survives glc_debug_set_encode_screen.  All kinds produce the same record bytes
+ * (tests/test_encode_matrix.py). */
+int glc_debug_set_encode_bound(glc_ctx *ctx, int kind);
+/* H and A of the last screened launch of `ctx` on its own coefficient workspace, which must have had `rows` rows: per
+ * row the maximum over the launch's hf planes and the A plane, as the quantiser reads them.  Waits for the stream. */
+int glc_debug_encode_bound_tap(glc_ctx *ctx, uint32_t rows, float *h, float *a);
+/* One v_mfma_f32_32x32x16_bf16 of one wave on host operands: a, b = 64 lanes x 8 bf16 (lane l: row / column l % 32, K
+ * slots 8 (l / 32) .. + 7), c, d = 64 lanes x 16 f32 (lane l, element e: row 8 (e / 4) + 4 (l / 32) + e % 4, column
+ * l % 32).  The instruction the matrix form accumulates with, for checking its error model on the device. */
+int glc_debug_mfma_bf16(glc_ctx *ctx, const uint16_t *a, const uint16_t *b, const float *c, float *d);
+/* The constants of the matrix form (host only; no context, no device): the ne it is built for, bf16 pieces kept per
+ * operand, piece products summed, i-steps per instruction, K-blocks per accumulation segment, hf planes of a launch,
+ * the per-instruction error model kappa, the split's error and the whole budget per unit of A = sum |x w|, which the
+ * library asserts to be within gamma_2048. */
+int glc_debug_encode_matrix_bound(uint32_t *ne, uint32_t *pieces, uint32_t *products, uint32_t *k_block, uint32_t *seg_blocks,
+                                  uint32_t *planes, double *kappa, double *split_eps, double *budget);
+
 /* K2 (+ K3 where the channel count needs it) exactly as glc_encode_range_device runs them, on caller-supplied
  * coefficients: d_coeffs holds (frame_end - frame_begin) * channels rows of 1024 floats, laid out as
  * glc_mdct_forward_device writes them; d_pcm / t0 / t_count / n_samples are read only for raw planes.

@@ -14,6 +14,11 @@ reference accumulates with a separately rounded multiply and add.
                 most 5 x 256 + 64 (4 - E) v_pk_fma_f32 (E = 0: 5 x 256) and must hold 256 + 64 E v_pk_mul_f32 and as many
                 v_pk_add_f32, so a fused op in an exact pair shows here as well as in the bit-exact parity of
                 tests/test_encode_screen.py and tests/test_encode_balance.py
+  k_mdct_mx_st (the matrix form of the mixed-role transform)   v_mfma_f32_*_bf16 alone is allowed: its
+                matrix waves accumulate the upper bound with it, never a coefficient.  No v_pk_fma_f32 at all: the bound has
+                left the vector ALU.  Its exact waves run k_mdct_fwd_st's multiply / add block on a lane's 2 rows x 8
+                columns: the one copy of their i loop holds BK = 16 i-steps of 8 packed multiplies and 8 packed adds, so
+                every instantiation must hold at least 128 v_pk_mul_f32 and as many v_pk_add_f32.
 The quantiser / decision / overlap-add kernels are not scanned: their IEEE divide, sqrt and
 64-bit index division expand to FMA-based sequences by design.  The arithmetic of the quantiser and the
 raw-or-compressed decision is pinned instead by tests/test_quantizer_edges.py, which drives them with
@@ -28,11 +33,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gapless-lossy-codec_amd", "csrc")
 ISA = os.path.join(ROOT, "build", "isa", "glc_kernels-hip-amdgcn-amd-amdhsa-gfx950.s")
 FORBIDDEN = re.compile(r"^\s+(v_fma\w*|v_fmac\w*|v_pk_fma\w*|v_mad_\w*f32|v_mac\w*|v_dot\w*|v_mfma\w*)\b")
-KERNELS = ("k_mdct_fwd_sched", "k_mdct_fwd_dma", "k_mdct_fwd_st", "k_mdct_mix_st", "k_mdct_fwd_small_rows", "k_mdct_fwd_small", "k_imdct_rows", "k_imdct_plan", "k_imdct_apply")
+KERNELS = ("k_mdct_fwd_sched", "k_mdct_fwd_dma", "k_mdct_fwd_st", "k_mdct_mix_st", "k_mdct_mx_st", "k_mdct_fwd_small_rows", "k_mdct_fwd_small", "k_imdct_rows", "k_imdct_plan", "k_imdct_apply")
 DIV_WINDOW = {"k_imdct_rows", "k_imdct_plan"}
 BOUND_FMA = re.compile(r"^\s+v_pk_fma_f32\b")  # the one fused op of k_mdct_mix_st's bound waves
 MIX_LOOP_MACS = 16 * 16  # packed multiply-adds in one copy of k_mdct_mix_st's i loop: BK i-steps x (4 rows x 8 columns / 2)
 MIX_BOUND_COPIES = 5     # bound, bound + A of row 0 .. 3
+MX_MFMA = re.compile(r"^\s+v_mfma_f32_\w+_bf16\b")  # the one matrix op of k_mdct_mx_st's matrix waves
+MX_LOOP_MACS = 16 * 8  # packed multiplies (and adds) in the exact waves' i loop: BK i-steps x (2 rows x 8 columns / 2)
 MIX_NAME = re.compile(r"k_mdct_mix_stILi\d+ELi\d+ELi([0-3])EE")  # <MINW, CH, E>
 
 
@@ -47,12 +54,14 @@ def main() -> int:
     subprocess.check_call(["make", "-C", CSRC, "-s", "isa"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     cur, bad, seen, in_div = None, [], set(), False
     first_ds = {}   # kernel -> True once its first ds_read has been seen
+    mx = {}         # instantiation of k_mdct_mx_st -> [v_mfma_f32_*_bf16, v_pk_mul_f32, v_pk_add_f32] counts
     mix = {}        # instantiation of k_mdct_mix_st -> [v_pk_fma_f32, v_pk_mul_f32, v_pk_add_f32] counts
     for line in open(ISA):
         m = re.match(r"^(_Z\w+):", line)
         if m:
             cur = next((k for k in KERNELS if k in m.group(1)), None)
             cur_mix = mix.setdefault(m.group(1), [0, 0, 0]) if cur == "k_mdct_mix_st" else None
+            cur_mx = mx.setdefault(m.group(1), [0, 0, 0]) if cur == "k_mdct_mx_st" else None
             in_div = False
             first_ds = {}
             if cur:
@@ -61,7 +70,8 @@ def main() -> int:
             in_div = True
         elif cur and "v_div_fixup_f32" in line:
             in_div = False
-        elif cur and FORBIDDEN.match(line) and not in_div and not (cur == "k_mdct_mix_st" and BOUND_FMA.match(line)):
+        elif cur and FORBIDDEN.match(line) and not in_div and not (cur == "k_mdct_mix_st" and BOUND_FMA.match(line)) \
+                and not (cur == "k_mdct_mx_st" and MX_MFMA.match(line)):
             bad.append((cur, line.strip()))
         # k_mdct_fwd_small waits for its LDS operands with COUNTED lgkmcnt (LDS returns in order): a scalar
         # load in flight at the same time would make those counts meaningless (SMEM returns out of order)
@@ -82,6 +92,12 @@ def main() -> int:
             pk = re.match(r"^\s+v_pk_(fma|mul|add)_f32\b", line)
             if pk:
                 cur_mix[("fma", "mul", "add").index(pk.group(1))] += 1
+        if cur == "k_mdct_mx_st":
+            if MX_MFMA.match(line):
+                cur_mx[0] += 1
+            pk = re.match(r"^\s+v_pk_(mul|add)_f32\b", line)
+            if pk:
+                cur_mx[1 + ("mul", "add").index(pk.group(1))] += 1
         if line.startswith(".Lfunc_end"):  # (not s_endpgm: a kernel with an early return has blocks behind its first one)
             cur = None
     missing = set(KERNELS) - seen
@@ -96,6 +112,10 @@ def main() -> int:
         if n_fma > fma_max or n_mul < mul_min or n_add < mul_min:
             bad.append(("k_mdct_mix_st", f"{name}: {n_fma} v_pk_fma_f32 (at most {fma_max}: the bound copies and the hybrid copy's bound pairs), "
                                          f"{n_mul} v_pk_mul_f32 / {n_add} v_pk_add_f32 (at least {mul_min} each: the exact copy and the hybrid copy's exact pairs)"))
+    for name, (n_mfma, n_mul, n_add) in mx.items():
+        if not n_mfma or n_mul < MX_LOOP_MACS or n_add < MX_LOOP_MACS:
+            bad.append(("k_mdct_mx_st", f"{name}: {n_mfma} v_mfma_f32_*_bf16 (the bound must be on the matrix pipe), {n_mul} v_pk_mul_f32 / "
+                                        f"{n_add} v_pk_add_f32 (at least {MX_LOOP_MACS} each: the exact waves' i loop)"))
     if bad:
         for k, l in bad:
             print(f"check_isa: fused op in {k}: {l}")
