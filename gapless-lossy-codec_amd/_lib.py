@@ -89,6 +89,16 @@ class GlcStoreEntry(C.Structure):
     ]
 
 
+class GlcStreamPushPlan(C.Structure):
+    """glc_stream_push_plan (include/glc.h): what a push completes on a lane of a streaming encode."""
+    _fields_ = [("first_frame", C.c_uint64), ("n_frames", C.c_uint64), ("carry", C.c_uint64)]
+
+
+class GlcStreamSeg(C.Structure):
+    """glc_stream_seg (include/glc.h): the lane and the frame range of a segment a push completed."""
+    _fields_ = [("stream", C.c_uint64), ("first_frame", C.c_uint64), ("n_frames", C.c_uint64)]
+
+
 class GlcFramesView(C.Structure):
     """glc_frames_view (include/glc.h): EncodedAudio as flat arrays."""
     _fields_ = [
@@ -264,6 +274,18 @@ SIGNATURES = {
                                                       C.POINTER(GlcCrop), _vp, C.POINTER(GlcClipLayout)]),
     "glc_decode_crops_device_store_i16": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint64, _vp,
                                                     C.POINTER(GlcClipLayout)]),
+    "glc_plan_stream_push": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int, C.POINTER(GlcStreamPushPlan)]),
+    "glc_stream_enc_open": (C.c_int, [_vp, C.c_uint16, C.c_uint64, C.POINTER(_vp)]),
+    "glc_stream_enc_close": (None, [_vp]),
+    "glc_stream_enc_reset": (C.c_int, [_vp, C.c_uint64]),
+    "glc_stream_enc_max_push": (C.c_uint64, [C.c_uint16]),
+    "glc_stream_enc_push_device": (C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.POINTER(GlcClipLayout), _vp, _vp, C.c_uint64, _vp, _vp,
+                                             C.POINTER(GlcStreamSeg), C.POINTER(C.c_uint64)]),
+    "glc_stream_enc_push": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.c_uint32, C.POINTER(C.c_uint64), _vp]),
+    "glc_stream_enc_segments": (C.c_int, [_vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "glc_stream_enc_segment": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint64)]),
+    "glc_stream_enc_frames": (C.c_int, [_vp, C.c_uint64, C.POINTER(_vp)]),
     "glc_version": (C.c_char_p, []),
 }
 

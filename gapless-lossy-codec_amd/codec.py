@@ -22,7 +22,7 @@ from typing import Iterator, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ._lib import (FRAMES_HOOK, GLC_EINVAL, GLC_PCM_F32, GLC_PCM_S16, GLC_PCM_S32, GlcClipLayout, GlcCompactInfo, GlcCompactStatus, GlcCrop, GlcCropPlan, GlcError,
-                   GlcFramesGather, GlcFramesView, GlcInfo, GlcPlan, GlcRoundtripInfo, check, lib)
+                   GlcFramesGather, GlcFramesView, GlcInfo, GlcPlan, GlcRoundtripInfo, GlcStreamPushPlan, GlcStreamSeg, check, lib)
 
 FRAME_SIZE = 2048        # src/codec.rs:15
 HOP_SIZE = 1024          # src/codec.rs:16
@@ -1246,6 +1246,145 @@ class RoundTrip(_Ctx):
         i = GlcRoundtripInfo()
         check(lib.glc_roundtrip_last_info(self._h, C.byref(i)), self._h)
         return RoundTripInfo(i.n_frames, i.n_raw_frames, i.total_nnz, i.serialized_bytes)
+
+
+def plan_stream_push(received: int, n_new: int, finish: bool = False) -> GlcStreamPushPlan:
+    """What a push of n_new samples per channel completes on a lane of a streaming encode that has `received` so
+    far (glc_plan_stream_push): first_frame, n_frames and the samples held back afterwards; raises where a finish
+    ends a stream the encoder refuses (<= 512 samples per channel)."""
+    if received < 0 or n_new < 0:
+        raise GlcError(GLC_EINVAL, "plan_stream_push: negative count")
+    p = GlcStreamPushPlan()
+    check(lib.glc_plan_stream_push(received, n_new, 1 if finish else 0, C.byref(p)))
+    return p
+
+
+class StreamEncoder(_Ctx):
+    """Encoder::encode fed in chunks: n_streams independent lanes of `channels` channels on one context
+    (glc_stream_enc_*).  A lane pushed in any chunking serialises to the bytes Encoder.encode gives for the
+    concatenation.  Use .push / .segments / .encoded (host samples) or .push_tensor (device samples), not both."""
+
+    def __init__(self, sample_rate: int, channels: int, n_streams: int = 1, device: int = 0):
+        super().__init__(sample_rate, device)
+        self.channels, self.n_streams = int(channels), int(n_streams)
+        self._s = None
+        if not 0 < self.channels <= 0xFFFF or self.n_streams <= 0:
+            raise GlcError(GLC_EINVAL, "StreamEncoder: channels must be 1..65535 and n_streams positive")
+        s = C.c_void_p()
+        check(lib.glc_stream_enc_open(self._h, self.channels, self.n_streams, C.byref(s)), self._h)
+        self._s = s
+
+    def __del__(self):
+        s, self._s = getattr(self, "_s", None), None
+        if s:
+            lib.glc_stream_enc_close(s)  # before its context
+        super().__del__()
+
+    @property
+    def max_push(self) -> int:
+        """Samples per channel one lane may take in one device push."""
+        return int(lib.glc_stream_enc_max_push(self.channels))
+
+    def _finish_flags(self, finish):
+        if finish is None:
+            return None, None
+        flags = np.ascontiguousarray(np.asarray(finish).astype(bool).astype(np.uint8).reshape(-1))
+        if flags.size != self.n_streams:
+            raise GlcError(GLC_EINVAL, f"finish must hold {self.n_streams} flags")
+        return flags, flags.ctypes.data_as(C.c_void_p)
+
+    def push(self, chunks, finish=None, bits: Optional[int] = None) -> None:
+        """chunks: per lane the interleaved samples it receives (None or empty: nothing), all float32 or all int16 /
+        int32 of `bits` bits; finish: per lane whether this chunk ends its stream (None: no lane).  Synchronises."""
+        if self.n_streams == 1 and (chunks is None or hasattr(chunks, "dtype")):
+            chunks = [chunks]
+        if len(chunks) != self.n_streams:
+            raise GlcError(GLC_EINVAL, f"chunks must hold {self.n_streams} arrays")
+        if self.n_streams == 1 and isinstance(finish, (bool, int)):
+            finish = [finish]
+        arrs, fmt = [], None
+        for c in chunks:
+            if c is None or len(c) == 0:
+                arrs.append(None)
+                continue
+            a, f, b = pcm_format(c, bits)
+            if fmt is not None and (f, b) != fmt:
+                raise TypeError("the chunks of one push must share one sample format")
+            fmt = (f, b)
+            arrs.append(a)
+        fmt = fmt or (GLC_PCM_F32, 32)
+        ptrs = (C.c_void_p * self.n_streams)(*[a.ctypes.data if a is not None else None for a in arrs])
+        ns = (C.c_uint64 * self.n_streams)(*[a.size if a is not None else 0 for a in arrs])
+        flags, fp = self._finish_flags(finish)
+        check(lib.glc_stream_enc_push(self._s, ptrs, fmt[0], fmt[1], ns, fp), self._h)
+
+    def segments(self, i: int = 0) -> list:
+        """[(first_frame, n_frames, blob bytes)] of lane i: the segments host pushes have completed and .encoded has
+        not taken - what a sender ships; glc_frames_from_compact assembles them."""
+        n = C.c_uint64()
+        check(lib.glc_stream_enc_segments(self._s, i, C.byref(n)), self._h)
+        out = []
+        for k in range(n.value):
+            p, nb, f0, nf = C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+            check(lib.glc_stream_enc_segment(self._s, i, k, C.byref(p), C.byref(nb), C.byref(f0), C.byref(nf)), self._h)
+            out.append((f0.value, nf.value, C.string_at(p.value, nb.value)))
+        return out
+
+    def encoded(self, i: int = 0) -> EncodedAudio:
+        """The finished stream of lane i as EncodedAudio; the lane is fresh afterwards."""
+        out = C.c_void_p()
+        check(lib.glc_stream_enc_frames(self._s, i, C.byref(out)), self._h)
+        return EncodedAudio(out.value)
+
+    def reset(self, i: int = 0) -> None:
+        """Lane i back to "nothing received"."""
+        check(lib.glc_stream_enc_reset(self._s, i), self._h)
+
+    def push_tensor(self, x, lengths, finish, arena, cursor, planar: bool = True, bits: Optional[int] = None):
+        """glc_stream_enc_push_device on torch's current stream.  x: a float32 / int16 / int32 CUDA tensor (B, C, T)
+        (planar) or (B, T, C) with B == n_streams, innermost stride 1; lengths: per lane the samples per channel it
+        receives (None: T); finish: per lane flags or None; arena / cursor as Encoder.encode_compact_batch_tensor takes
+        them.  Returns (entries, segs): an (n_segs, 4) int64 CUDA tensor of glc_store_entry words and the host list
+        [(lane, first_frame, n_frames)] in the same order.  Nothing is copied to the host."""
+        import torch
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 3:
+            raise TypeError("x must be a float32 (or int16 / int32) CUDA tensor of shape (B, C, T) or (B, T, C)")
+        fmt, bits = _tensor_pcm_format(x, bits)
+        if x.device.index != self.device:
+            raise GlcError(GLC_EINVAL, f"x is on {x.device}, this context on device {self.device}")
+        if x.shape[2] > 1 and x.stride(2) != 1:
+            raise TypeError("x: the innermost stride must be 1")
+        if min(x.stride(0), x.stride(1)) < 0:
+            raise TypeError("x: negative strides")
+        b, ch, n = (x.shape[0], x.shape[1], x.shape[2]) if planar else (x.shape[0], x.shape[2], x.shape[1])
+        if b != self.n_streams or ch != self.channels:
+            raise GlcError(GLC_EINVAL, f"x must hold {self.n_streams} lanes of {self.channels} channels")
+        if not planar and n > 1 and x.stride(1) != ch:
+            raise TypeError(f"x: an interleaved chunk must be dense (stride {ch} between samples)")
+        lens = [n] * b if lengths is None else [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+        if len(lens) != b or any(v < 0 or v > n for v in lens):
+            raise GlcError(GLC_EINVAL, f"lengths must hold {b} values in [0, {n}]")
+        arr = (C.c_uint64 * b)(*lens)
+        lay = GlcClipLayout(b, ch, 1 if planar else 0, x.stride(0), x.stride(1) if planar else 0, n, C.cast(arr, C.POINTER(C.c_uint64)))
+        if not isinstance(arena, torch.Tensor) or not arena.is_cuda or arena.dtype != torch.uint8 or arena.dim() != 1 \
+                or not arena.is_contiguous():
+            raise TypeError("arena must be a contiguous 1-D uint8 CUDA tensor")
+        if not isinstance(cursor, torch.Tensor) or not cursor.is_cuda or cursor.dtype != torch.int64 or cursor.numel() != 1:
+            raise TypeError("cursor must be a one-element int64 CUDA tensor")
+        if arena.device != x.device or cursor.device != x.device:
+            raise GlcError(GLC_EINVAL, "x, arena and cursor must be on one device")
+        flags, fp = self._finish_flags(finish)
+        entries = torch.zeros((b, 4), dtype=torch.int64, device=x.device)
+        segs = (GlcStreamSeg * b)()
+        n_segs = C.c_uint64()
+        self._enter_torch_stream(x.device)
+        try:
+            check(lib.glc_stream_enc_push_device(self._s, C.c_void_p(x.data_ptr()), fmt, bits, C.byref(lay), fp,
+                                                 C.c_void_p(arena.data_ptr()), arena.numel(), C.c_void_p(cursor.data_ptr()),
+                                                 C.c_void_p(entries.data_ptr()), segs, C.byref(n_segs)), self._h)
+        finally:
+            self.set_stream(0)
+        return entries[:n_segs.value], [(g.stream, g.first_frame, g.n_frames) for g in segs[:n_segs.value]]
 
 
 def save_encoded(encoded: EncodedAudio, path) -> None:

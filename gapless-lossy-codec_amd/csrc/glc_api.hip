@@ -3646,6 +3646,454 @@ int glc_debug_compact_store_device(glc_ctx *ctx, const void *d_records, const ui
   }
 }
 
+// ------------------------------------------------------------------------------ streaming encode
+
+extern "C++" {
+
+// A host segment of a lane: the compact blob of frames [first_frame, first_frame + n_frames).
+struct StreamBlob {
+  uint64_t first_frame, n_frames;
+  std::vector<uint64_t> words;  // the blob, 8-byte aligned
+  uint64_t bytes;
+};
+
+struct StreamLane {
+  uint64_t received = 0, done = 0;  // samples per channel so far, frames completed
+  uint32_t parity = 0;              // which of the lane's two held-back buffers is current
+  bool finished = false;            // host pushes: ended and not taken yet
+  uint64_t total = 0;               // ... its samples per channel
+  std::vector<StreamBlob> blobs;    // host pushes: the segments so far
+};
+
+}  // extern "C++"
+
+struct glc_stream_enc {
+  glc_ctx *ctx = nullptr;
+  uint32_t ch = 0;
+  uint64_t n = 0;
+  int mode = 0;       // 0: no push yet, 1: host pushes, 2: device pushes
+  DevBuf held;        // [lane][2][2048 * ch] floats
+  std::vector<StreamLane> lanes;
+  // host pushes
+  HostBuf up, down;   // pinned: the chunks going up, the entries and blobs coming down
+  DevBuf d_pcm, arena, d_meta;  // d_meta: the cursor (8 bytes, padded to 64) and the entries
+  uint64_t held_at(uint64_t lane, uint32_t parity) const { return (lane * 2 + parity) * uint64_t(glc::kFrame) * ch; }
+};
+
+extern "C++" {
+namespace {
+
+// What a device push does with lane `lane`: its plan, and the chunk.
+struct StreamLanePush {
+  uint64_t lane, n_new;
+  bool finish;
+  glc_stream_push_plan plan;
+};
+
+// The core of both pushes: everything is validated.  Queues the rounds; fills segs / n_segs; updates the lanes.
+int stream_push_core(glc_stream_enc *s, const RtbPcm &pcm, const RtbLayout &in, const std::vector<StreamLanePush> &act,
+                     void *d_arena, uint64_t arena_bytes, uint64_t *d_cursor, glc_store_entry *d_entries, glc_stream_seg *segs,
+                     uint64_t *n_segs) {
+  glc_ctx *ctx = s->ctx;
+  const uint32_t ch = s->ch;
+  const uint64_t per_hop = uint64_t(glc::kHop) * ch, rec = glc::record_bytes(ch), budget = encode_chunk_frames(ch);
+  // the segments, in lane order, and the lanes whose held-back samples change (a finished lane holds nothing back)
+  std::vector<const StreamLanePush *> seg, keep;
+  for (const StreamLanePush &a : act) {
+    if (a.plan.n_frames) seg.push_back(&a);
+    if (!a.finish && a.n_new) keep.push_back(&a);
+  }
+  // rounds: a virtual slot in front (its second half is the first segment's lookback), frames + 1 slots per segment
+  struct Round {
+    uint64_t first, n, V, n_real;
+    size_t o_spans, o_fmap, o_span;
+    uint64_t n_spans;
+  };
+  std::vector<Round> rounds;
+  for (uint64_t k = 0; k < seg.size(); ++k) {
+    const uint64_t v = seg[k]->plan.n_frames + 1;
+    if (rounds.empty() || rounds.back().V + v > budget) rounds.push_back(Round{k, 0, 1, 0, 0, 0, 0, 0});
+    rounds.back().n += 1, rounds.back().V += v, rounds.back().n_real += seg[k]->plan.n_frames;
+  }
+  if (rounds.empty() && !keep.empty()) rounds.push_back(Round{0, 0, 0, 0, 0, 0, 0, 0});  // the stager alone
+  *n_segs = seg.size();
+  for (uint64_t k = 0; k < seg.size(); ++k) segs[k] = glc_stream_seg{seg[k]->lane, seg[k]->plan.first_frame, seg[k]->plan.n_frames};
+  rt_forget_streams(ctx);
+  // what the lanes are after the push: a finished lane is fresh, the others have flipped to their other buffer
+  auto commit = [&] {
+    for (const StreamLanePush &a : act) {
+      StreamLane &L = s->lanes[a.lane];
+      if (a.finish) {
+        L.received = 0, L.done = 0;
+      } else {
+        L.received += a.n_new, L.done += a.plan.n_frames;
+        if (a.n_new) L.parity ^= 1u;
+      }
+    }
+  };
+  if (rounds.empty()) {  // only finishes that complete no frame: nothing to queue
+    commit();
+    return GLC_OK;
+  }
+  size_t tab = 0;
+  auto place = [&](size_t bytes) {
+    const size_t at = tab;
+    tab = align_up(tab + bytes, 256);
+    return at;
+  };
+  uint64_t max_V = 0, max_scratch = 0;
+  for (size_t r = 0; r < rounds.size(); ++r) {
+    Round &R = rounds[r];
+    R.n_spans = R.n + (r == 0 ? keep.size() : 0);
+    R.o_spans = place(R.n_spans * sizeof(glc::StreamSpan));
+    R.o_fmap = place(R.n_real * sizeof(glc::FrameMap));
+    R.o_span = place(R.n * sizeof(glc::ClipSpan));
+    max_V = std::max(max_V, R.V);
+    if (R.n) max_scratch = std::max(max_scratch, glc::compact_store_scratch_bytes(R.n_real * ch, R.n));
+  }
+  int rc = rt_reserve(ctx, ctx->rtb_vs, max_V * per_hop * sizeof(float));
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rt_records, max_V * rec);
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->coef, max_V * ch * glc::kHop * sizeof(float));
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->pack_meta, max_scratch);
+  if (rc == GLC_OK) rc = rtb_image_begin(ctx, tab);
+  if (rc != GLC_OK) return rc;
+  uint8_t *img = static_cast<uint8_t *>(ctx->rtb_stage.p);
+  const uint8_t *d_tab = static_cast<const uint8_t *>(ctx->rtb_tab.p);
+  auto span_of = [&](const StreamLanePush &a) {
+    const StreamLane &L = s->lanes[a.lane];
+    glc::StreamSpan sp{};
+    sp.src = in.at(a.lane), sp.received = L.received, sp.n_new = a.n_new;
+    sp.held_x = glc::stream_held_from(L.done);
+    sp.held_old = s->held_at(a.lane, L.parity), sp.held_new = s->held_at(a.lane, L.parity ^ 1u);
+    return sp;
+  };
+  std::vector<uint64_t> frames;
+  for (size_t r = 0; r < rounds.size(); ++r) {
+    const Round &R = rounds[r];
+    auto *spans = reinterpret_cast<glc::StreamSpan *>(img + R.o_spans);
+    frames.resize(R.n);
+    uint64_t slot = 1;
+    for (uint64_t k = 0; k < R.n; ++k) {
+      const StreamLanePush &a = *seg[R.first + k];
+      glc::StreamSpan sp = span_of(a);
+      sp.x0 = static_cast<int64_t>(a.plan.first_frame * glc::kHop) - static_cast<int64_t>(glc::kHop / 2);
+      sp.unit = static_cast<uint32_t>(2 * slot - 1);
+      spans[k] = sp;
+      frames[k] = a.plan.n_frames;
+      slot += a.plan.n_frames + 1;
+    }
+    if (r == 0)
+      for (size_t q = 0; q < keep.size(); ++q) {
+        const StreamLanePush &a = *keep[q];
+        glc::StreamSpan sp = span_of(a);
+        sp.x0 = static_cast<int64_t>(glc::stream_held_from(a.plan.first_frame + a.plan.n_frames));
+        sp.unit = static_cast<uint32_t>(2 * R.V + 4 * q);
+        spans[R.n + q] = sp;
+      }
+    if (R.n)
+      store_round_tables(frames.data(), R.n, true, reinterpret_cast<glc::FrameMap *>(img + R.o_fmap),
+                         reinterpret_cast<glc::ClipSpan *>(img + R.o_span));
+  }
+  hipStream_t st = ctx->stream;
+  rc = rtb_image_send(ctx, tab);
+  if (rc != GLC_OK) return rc;
+  float *vs = static_cast<float *>(ctx->rtb_vs.p);
+  for (size_t r = 0; r < rounds.size(); ++r) {
+    const Round &R = rounds[r];
+    GLC_HIP(ctx, glc::launch_stage_segments(pcm.p, pcm.fmt, pcm.bits, reinterpret_cast<const glc::StreamSpan *>(d_tab + R.o_spans),
+                                            static_cast<uint32_t>(R.n_spans), static_cast<uint32_t>(2 * R.V),
+                                            static_cast<uint32_t>(r == 0 ? 4 * keep.size() : 0), ch, in.planes(), in.l->channel_stride,
+                                            static_cast<float *>(s->held.p), vs, st));
+    if (!R.n) continue;
+    // the virtual stream's frames [1, V - 1): frame 0 is the slot in front, frame V - 1 the last segment's junk one;
+    // record j is virtual frame j + 1, which is how store_round_tables numbers them
+    const uint64_t T = R.V * glc::kHop;
+    rc = encode_range_on(ctx, st, ctx->coef, vs, 0, T, T * ch, static_cast<uint16_t>(ch), 1, R.V - 1, ctx->rt_records.p, nullptr);
+    if (rc == GLC_OK)
+      rc = store_round_launch(ctx, ctx->rt_records.p, R.n_real, R.n, ch, d_tab, R.o_fmap, R.o_span, d_arena, arena_bytes, d_cursor,
+                              d_entries + R.first, st);
+    if (rc != GLC_OK) return rc;
+  }
+  commit();
+  return GLC_OK;
+}
+
+// What both pushes check of the lanes and build for the core.  `lens`: samples per channel per lane.
+int stream_plan_lanes(glc_stream_enc *s, const std::string &w, const uint64_t *lens, uint64_t len_all, const uint8_t *finish,
+                      std::vector<StreamLanePush> *act) {
+  const uint64_t max_push = glc_stream_enc_max_push(static_cast<uint16_t>(s->ch));
+  for (uint64_t i = 0; i < s->n; ++i) {
+    const uint64_t n_new = lens ? lens[i] : len_all;
+    const bool fin = finish && finish[i];
+    if (n_new > max_push)
+      return fail(s->ctx, GLC_EINVAL, w + ": lane " + std::to_string(i) + ": the chunk is larger than glc_stream_enc_max_push");
+    if (!n_new && !fin) continue;
+    StreamLanePush a{i, n_new, fin, {}};
+    if (!glc::plan_stream_push(s->lanes[i].received, n_new, fin, &a.plan))
+      return fail(s->ctx, GLC_EINVAL, w + ": lane " + std::to_string(i) +
+                                          ": the reference encoder panics on a stream of <= 512 samples per channel");
+    act->push_back(a);
+  }
+  return GLC_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int glc_plan_stream_push(uint64_t received, uint64_t n_new, int finish, glc_stream_push_plan *out) {
+  if (!out) return GLC_EINVAL;
+  *out = glc_stream_push_plan{0, 0, 0};
+  if (!glc::plan_stream_push(received, n_new, finish != 0, out)) {
+    glc::set_global_error("glc_plan_stream_push: a sum that wraps, or a finish at <= 512 samples per channel (the reference encoder panics)");
+    return GLC_EINVAL;
+  }
+  return GLC_OK;
+}
+
+uint64_t glc_stream_enc_max_push(uint16_t channels) {
+  // a push of n samples completes at most ceil(n / 1024) + 1 frames; with its junk slot and the round's slot in front
+  // that is ceil(n / 1024) + 3 virtual frames of the encode_chunk_frames a round holds
+  return channels ? (encode_chunk_frames(channels) - 4) * glc::kHop : 0;
+}
+
+int glc_stream_enc_open(glc_ctx *ctx, uint16_t channels, uint64_t n_streams, glc_stream_enc **out) {
+  if (!ctx) return GLC_EINVAL;
+  if (!out) return fail(ctx, GLC_EINVAL, "glc_stream_enc_open: null argument");
+  *out = nullptr;
+  if (channels == 0 || n_streams == 0) return fail(ctx, GLC_EINVAL, "glc_stream_enc_open: no channels or no streams");
+  const uint64_t per_lane = 2ull * glc::kFrame * channels * sizeof(float);
+  if (n_streams > (1ull << 46) / per_lane) return fail(ctx, GLC_EINVAL, "glc_stream_enc_open: too many streams");
+  DeviceGuard guard(ctx->device);
+  try {
+    std::unique_ptr<glc_stream_enc> s(new glc_stream_enc);
+    s->ctx = ctx, s->ch = channels, s->n = n_streams;
+    s->lanes.resize(n_streams);
+    const hipError_t e = s->held.reserve(n_streams * per_lane);
+    if (e != hipSuccess) return hip_fail(ctx, e, "glc_stream_enc_open: hipMalloc");
+    *out = s.release();
+    return GLC_OK;
+  } catch (const std::bad_alloc &) {
+    return fail(ctx, GLC_ENOMEM, "glc_stream_enc_open: host allocation failed");
+  }
+}
+
+void glc_stream_enc_close(glc_stream_enc *s) {
+  if (!s) return;
+  DeviceGuard guard(s->ctx->device);
+  (void)hipStreamSynchronize(s->ctx->stream);  // queued pushes may still read and write the session's buffers
+  s->held.release(), s->d_pcm.release(), s->arena.release(), s->d_meta.release();
+  s->up.release(), s->down.release();
+  delete s;
+}
+
+int glc_stream_enc_reset(glc_stream_enc *s, uint64_t stream) {
+  if (!s) return GLC_EINVAL;
+  if (stream >= s->n) return fail(s->ctx, GLC_EINVAL, "glc_stream_enc_reset: no such stream");
+  StreamLane &L = s->lanes[stream];
+  L.received = 0, L.done = 0, L.finished = false, L.total = 0;
+  L.blobs.clear();
+  return GLC_OK;
+}
+
+// The checks of a device push, then the core.
+static int stream_push_device_checked(glc_stream_enc *s, const char *who, const void *d_pcm, glc_pcm_format fmt, uint32_t bits,
+                                      const glc_clip_layout *in, const uint8_t *finish, void *d_arena, uint64_t arena_bytes,
+                                      uint64_t *d_cursor, glc_store_entry *d_entries, glc_stream_seg *segs, uint64_t *n_segs) {
+  glc_ctx *ctx = s->ctx;
+  const std::string w(who);
+  if (!in || !d_pcm || !d_arena || !d_cursor || !d_entries || !segs || !n_segs) return fail(ctx, GLC_EINVAL, w + ": null argument");
+  if (const int rc = rtb_check_fmt(ctx, w, fmt, bits)) return rc;
+  if (in->n_clips != s->n || in->channels != s->ch)
+    return fail(ctx, GLC_EINVAL, w + ": the layout's n_clips and channels must be the session's");
+  const RtbPcm pcm{d_pcm, fmt, bits};
+  if (reinterpret_cast<uintptr_t>(d_pcm) & (pcm.elem() - 1u)) return fail(ctx, GLC_EINVAL, w + ": d_pcm is not aligned to its sample size");
+  if (reinterpret_cast<uintptr_t>(d_arena) & 63u) return fail(ctx, GLC_EINVAL, w + ": d_arena is not 64-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(d_cursor) | reinterpret_cast<uintptr_t>(d_entries)) & 7u)
+    return fail(ctx, GLC_EINVAL, w + ": d_cursor and d_entries must be 8-byte aligned");
+  const RtbLayout li{in};
+  DeviceGuard guard(ctx->device);
+  try {  // no C++ exception may cross the C ABI
+    std::vector<StreamLanePush> act;
+    if (const int rc = stream_plan_lanes(s, w, in->lengths, in->length, finish, &act)) return rc;
+    for (uint64_t i = 0; i < s->n; ++i) {
+      if (li.len(i) == 0) continue;
+      const std::string lane = w + ": lane " + std::to_string(i);
+      if (li.planes() && in->channel_stride < li.len(i)) return fail(ctx, GLC_EINVAL, lane + ": channel_stride is smaller than a plane");
+      if (s->n > 1 && in->clip_stride < li.occupies(i)) return fail(ctx, GLC_EINVAL, lane + ": clip_stride is smaller than the chunk");
+    }
+    {
+      const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_pcm), a1 = li.end_of(d_pcm, pcm.elem());
+      const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_arena), b1 = b0 + arena_bytes;
+      const uintptr_t e0 = reinterpret_cast<uintptr_t>(d_entries), e1 = e0 + s->n * sizeof(glc_store_entry);
+      if (a0 < b1 && b0 < a1) return fail(ctx, GLC_EINVAL, w + ": the arena overlaps the input");
+      if (a0 < e1 && e0 < a1) return fail(ctx, GLC_EINVAL, w + ": the entries overlap the input");
+    }
+    return stream_push_core(s, pcm, li, act, d_arena, arena_bytes, d_cursor, d_entries, segs, n_segs);
+  } catch (const std::bad_alloc &) {
+    return fail(ctx, GLC_ENOMEM, w + ": host allocation failed");
+  }
+}
+
+int glc_stream_enc_push_device(glc_stream_enc *s, const void *d_pcm, glc_pcm_format fmt, uint32_t bits, const glc_clip_layout *in,
+                               const uint8_t *finish, void *d_arena, uint64_t arena_bytes, uint64_t *d_cursor,
+                               glc_store_entry *d_entries, glc_stream_seg *segs, uint64_t *n_segs) {
+  if (!s) return GLC_EINVAL;
+  if (s->mode == 1) return fail(s->ctx, GLC_EINVAL, "glc_stream_enc_push_device: this session takes host pushes");
+  const int rc = stream_push_device_checked(s, "glc_stream_enc_push_device", d_pcm, fmt, bits, in, finish, d_arena, arena_bytes, d_cursor,
+                                            d_entries, segs, n_segs);
+  if (rc == GLC_OK) s->mode = 2;
+  return rc;
+}
+
+int glc_stream_enc_push(glc_stream_enc *s, const void *const *pcm, glc_pcm_format fmt, uint32_t bits, const uint64_t *n_samples,
+                        const uint8_t *finish) {
+  if (!s) return GLC_EINVAL;
+  glc_ctx *ctx = s->ctx;
+  const std::string w("glc_stream_enc_push");
+  if (s->mode == 2) return fail(ctx, GLC_EINVAL, w + ": this session takes device pushes");
+  if (!pcm || !n_samples) return fail(ctx, GLC_EINVAL, w + ": null argument");
+  if (const int rc = rtb_check_fmt(ctx, w, fmt, bits)) return rc;
+  const uint32_t ch = s->ch;
+  const size_t elem = fmt == GLC_PCM_S16 ? 2 : 4;
+  const uint64_t max_push = glc_stream_enc_max_push(static_cast<uint16_t>(ch));
+  DeviceGuard guard(ctx->device);
+  try {
+    std::vector<uint64_t> left(s->n), lens(s->n);
+    bool any = false;
+    for (uint64_t i = 0; i < s->n; ++i) {
+      const std::string lane = w + ": lane " + std::to_string(i);
+      const StreamLane &L = s->lanes[i];
+      const bool fin = finish && finish[i];
+      if (n_samples[i] % ch) return fail(ctx, GLC_EINVAL, lane + ": n_samples is not a multiple of channels");
+      if (n_samples[i] && !pcm[i]) return fail(ctx, GLC_EINVAL, lane + ": null samples");
+      if (n_samples[i] && (reinterpret_cast<uintptr_t>(pcm[i]) & (elem - 1u))) return fail(ctx, GLC_EINVAL, lane + ": samples are not aligned");
+      if ((n_samples[i] || fin) && L.finished) return fail(ctx, GLC_EINVAL, lane + ": the stream is finished and has not been taken");
+      left[i] = n_samples[i] / ch;
+      glc_stream_push_plan plan;
+      if ((left[i] || fin) && !glc::plan_stream_push(L.received, left[i], fin, &plan))
+        return fail(ctx, GLC_EINVAL, lane + ": the reference encoder panics on a stream of <= 512 samples per channel");
+      any = any || left[i] || fin;
+    }
+    if (!any) {
+      rt_forget_streams(ctx);
+      s->mode = 1;
+      return GLC_OK;
+    }
+    std::vector<uint8_t> fin_now(s->n);
+    std::vector<uint64_t> at(s->n, 0);  // samples per channel of pcm[i] already pushed
+    std::vector<glc_stream_seg> segs(s->n);
+    std::vector<glc_store_entry> ents(s->n);
+    for (bool more = true; more;) {
+      more = false;
+      uint64_t longest = 0, arena_need = 64;
+      for (uint64_t i = 0; i < s->n; ++i) {
+        lens[i] = std::min(left[i], max_push);
+        fin_now[i] = finish && finish[i] && left[i] == lens[i] && !s->lanes[i].finished;
+        if (left[i] > lens[i]) more = true;
+        longest = std::max(longest, lens[i]);
+        glc_stream_push_plan plan{};
+        if ((lens[i] || fin_now[i]) && glc::plan_stream_push(s->lanes[i].received, lens[i], fin_now[i], &plan) && plan.n_frames)
+          arena_need += glc::align64(glc::compact_layout(ch, plan.n_frames).bound);
+      }
+      const uint64_t stride = std::max<uint64_t>(longest * ch, 1);
+      const size_t up_bytes = static_cast<size_t>(s->n * stride * elem);
+      GLC_HIP(ctx, s->up.reserve(up_bytes));
+      int rc = rt_reserve(ctx, s->d_pcm, up_bytes);
+      if (rc == GLC_OK) rc = rt_reserve(ctx, s->arena, arena_need);
+      if (rc == GLC_OK) rc = rt_reserve(ctx, s->d_meta, 64 + s->n * sizeof(glc_store_entry));
+      if (rc != GLC_OK) return rc;
+      for (uint64_t i = 0; i < s->n; ++i)
+        if (lens[i])
+          std::memcpy(static_cast<uint8_t *>(s->up.p) + i * stride * elem, static_cast<const uint8_t *>(pcm[i]) + at[i] * ch * elem,
+                      lens[i] * ch * elem);
+      uint64_t *d_cursor = static_cast<uint64_t *>(s->d_meta.p);
+      glc_store_entry *d_entries = reinterpret_cast<glc_store_entry *>(static_cast<uint8_t *>(s->d_meta.p) + 64);
+      GLC_HIP(ctx, hipMemcpyAsync(s->d_pcm.p, s->up.p, up_bytes, hipMemcpyHostToDevice, ctx->stream));
+      GLC_HIP(ctx, hipMemsetAsync(d_cursor, 0, 8, ctx->stream));
+      glc_clip_layout lay{s->n, static_cast<uint16_t>(ch), 0, stride, 0, 0, lens.data()};
+      const RtbLayout li{&lay};
+      const RtbPcm dp{s->d_pcm.p, fmt, bits};
+      std::vector<StreamLanePush> act;
+      rc = stream_plan_lanes(s, w, lens.data(), 0, fin_now.data(), &act);
+      uint64_t n_segs = 0;
+      std::vector<uint64_t> totals(s->n);
+      for (uint64_t i = 0; i < s->n; ++i) totals[i] = s->lanes[i].received + lens[i];
+      if (rc == GLC_OK) rc = stream_push_core(s, dp, li, act, s->arena.p, s->arena.cap, d_cursor, d_entries, segs.data(), &n_segs);
+      if (rc != GLC_OK) return rc;
+      s->mode = 1;
+      for (uint64_t i = 0; i < s->n; ++i) {
+        at[i] += lens[i], left[i] -= lens[i];
+        if (fin_now[i]) s->lanes[i].finished = true, s->lanes[i].total = totals[i];
+      }
+      if (n_segs) {
+        GLC_HIP(ctx, hipMemcpyAsync(ents.data(), d_entries, n_segs * sizeof(glc_store_entry), hipMemcpyDeviceToHost, ctx->stream));
+        GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        uint64_t down_bytes = 0;
+        for (uint64_t j = 0; j < n_segs; ++j) {
+          if (!ents[j].stored || ents[j].offset + ents[j].bytes > s->arena.cap)
+            return fail(ctx, GLC_EHIP, w + ": a segment did not fit the session's arena");
+          down_bytes = std::max(down_bytes, ents[j].offset + ents[j].bytes);
+        }
+        GLC_HIP(ctx, s->down.reserve(down_bytes));
+        GLC_HIP(ctx, hipMemcpyAsync(s->down.p, s->arena.p, down_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (uint64_t j = 0; j < n_segs; ++j) {
+          StreamBlob b{segs[j].first_frame, segs[j].n_frames, std::vector<uint64_t>((ents[j].bytes + 7) / 8), ents[j].bytes};
+          std::memcpy(b.words.data(), static_cast<const uint8_t *>(s->down.p) + ents[j].offset, ents[j].bytes);
+          s->lanes[segs[j].stream].blobs.push_back(std::move(b));
+        }
+      } else {
+        // the pinned chunks must have left before the next round of this loop, or the caller's next push, rewrites them
+        GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      }
+    }
+    return GLC_OK;
+  } catch (const std::bad_alloc &) {
+    return fail(ctx, GLC_ENOMEM, w + ": host allocation failed");
+  }
+}
+
+int glc_stream_enc_segments(const glc_stream_enc *s, uint64_t stream, uint64_t *n_blobs) {
+  if (!s) return GLC_EINVAL;
+  if (!n_blobs || stream >= s->n) return fail(s->ctx, GLC_EINVAL, "glc_stream_enc_segments: null argument or no such stream");
+  *n_blobs = s->lanes[stream].blobs.size();
+  return GLC_OK;
+}
+
+int glc_stream_enc_segment(const glc_stream_enc *s, uint64_t stream, uint64_t k, const void **blob, uint64_t *bytes,
+                           uint64_t *first_frame, uint64_t *n_frames) {
+  if (!s) return GLC_EINVAL;
+  if (stream >= s->n || k >= s->lanes[stream].blobs.size()) return fail(s->ctx, GLC_EINVAL, "glc_stream_enc_segment: no such segment");
+  const StreamBlob &b = s->lanes[stream].blobs[k];
+  if (blob) *blob = b.words.data();
+  if (bytes) *bytes = b.bytes;
+  if (first_frame) *first_frame = b.first_frame;
+  if (n_frames) *n_frames = b.n_frames;
+  return GLC_OK;
+}
+
+int glc_stream_enc_frames(glc_stream_enc *s, uint64_t stream, glc_frames **out) {
+  if (!s) return GLC_EINVAL;
+  if (!out || stream >= s->n) return fail(s->ctx, GLC_EINVAL, "glc_stream_enc_frames: null argument or no such stream");
+  *out = nullptr;
+  StreamLane &L = s->lanes[stream];
+  if (!L.finished) return fail(s->ctx, GLC_EINVAL, "glc_stream_enc_frames: the stream is not finished");
+  if (L.blobs.size() > 0xFFFFFFFFull) return fail(s->ctx, GLC_EINVAL, "glc_stream_enc_frames: too many segments");
+  try {
+    std::vector<const void *> blobs(L.blobs.size());
+    std::vector<uint64_t> bytes(L.blobs.size());
+    for (size_t k = 0; k < L.blobs.size(); ++k) blobs[k] = L.blobs[k].words.data(), bytes[k] = L.blobs[k].bytes;
+    const int rc = glc::frames_from_compact(s->ctx->sample_rate, L.total * s->ch, static_cast<uint16_t>(s->ch), blobs.data(), bytes.data(),
+                                            static_cast<uint32_t>(blobs.size()), /*trusted=*/true, out);
+    if (rc != GLC_OK) return fail(s->ctx, rc, std::string("glc_stream_enc_frames: ") + glc_last_error(nullptr));
+  } catch (const std::bad_alloc &) {
+    return fail(s->ctx, GLC_ENOMEM, "glc_stream_enc_frames: host allocation failed");
+  }
+  L.finished = false, L.total = 0;
+  L.blobs.clear();
+  return GLC_OK;
+}
+
 uint64_t glc_ctx_resident_stream(const glc_ctx *ctx) { return ctx ? ctx->dec_uid : 0; }
 
 int glc_decode_resident(glc_ctx *ctx, uint64_t stream_id, float *pcm_out, uint64_t cap, uint64_t *n_out) {

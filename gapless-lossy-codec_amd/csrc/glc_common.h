@@ -84,6 +84,29 @@ inline SampleWindow frame_sample_window(uint64_t f0, uint64_t f1, uint64_t per_c
   return {lo, hi < per_channel ? hi : per_channel};
 }
 
+// What a push of n_new samples per channel completes on a lane of a streaming encode that has `received` so far
+// (include/glc.h glc_plan_stream_push), the ONE statement of it.  Frame f reads [hop f - hop/2, hop f - hop/2 + frame):
+// it is final once hop f + frame - hop/2 samples are there.  false: a wrapping sum, or a finish the encoder refuses.
+inline uint64_t stream_frames_done(uint64_t received) {
+  const uint64_t a = (received + kHop / 2) / kHop;
+  return (a > 1 ? a : 1) - 1;
+}
+// the lane's first sample that is still held back after `done` frames
+inline uint64_t stream_held_from(uint64_t done) { return done ? done * kHop - kHop / 2 : 0; }
+inline bool plan_stream_push(uint64_t received, uint64_t n_new, bool finish, glc_stream_push_plan *out) {
+  if (n_new > UINT64_MAX - received || received + n_new > UINT64_MAX - 2 * kFrame) return false;
+  const uint64_t total = received + n_new, done0 = stream_frames_done(received);
+  if (finish) {
+    const glc_plan plan = plan_encode(total, 1);
+    if (plan.n_frames == 0) return false;
+    *out = glc_stream_push_plan{done0, plan.n_frames - done0, 0};
+    return true;
+  }
+  const uint64_t done1 = stream_frames_done(total);
+  *out = glc_stream_push_plan{done0, done1 - done0, total - stream_held_from(done1)};
+  return true;
+}
+
 // Gapless trim of a decoded stream, src/codec.rs:756-765: the interleaved samples [start, start + n) of
 // the (n_frames + 1) hops.  The delay counts INTERLEAVED samples (quirk Q3).
 struct Trim {

@@ -291,6 +291,33 @@ hipError_t launch_stage_clips(const float *src, const StageClip *clips, uint32_t
 hipError_t launch_stage_clips_int(const void *src, bool wide, uint32_t bits, const StageClip *clips, uint32_t n_clips, uint32_t ch,
                                   bool planar, uint64_t channel_stride, uint32_t n_virtual_frames, float *vstream, hipStream_t s);
 
+// S2: the segment stager of a streaming push (glc_stream_enc_push_device; DESIGN section 3, "a round of segments").
+// A lane's stream is numbered in samples per channel from 0; of the `received` samples it has had so far the session
+// holds back [held_x, received) as floats, interleaved, at element held_old of `held`; the push brings n_new more at
+// element `src` of the source (laid out as S1's clips are).  A span is a run of 512-sample UNITS whose first one shows
+// the lane's sample x0 (negative in front of the stream: +0.0) and which lasts until the next span's `unit`:
+//   units [0, vs_units)   half hops of the round's virtual stream, vstream[unit * 512 * ch ..): the span of a segment
+//                         of frames [F, F + n) starts at unit 2 slot - 1 with x0 = 1024 F - 512 and owns 2 n + 2 units,
+//                         so that the frame in virtual slot `slot` + k is the lane's frame F + k.  Units 0 and
+//                         vs_units - 1 belong to no span and are written +0.0.
+//   units from vs_units   the new held-back samples of a lane, 4 units from element held_new of `held`, x0 = the new
+//                         held_x; what lies at or behind received + n_new is written +0.0.
+// Spans ascend in `unit`; spans[0].unit is 1 (0 when vs_units == 0).  Every element of the virtual stream and of the
+// named held-back buffers is written; held_old and held_new of a lane are different buffers.  Samples at or behind
+// received + n_new are +0.0: the padding behind a finished stream.  Integer sources are widened by W1's rule.
+struct StreamSpan {
+  uint64_t src;       // element of the lane's new chunk in the source
+  uint64_t received;  // samples per channel the lane had before this push
+  uint64_t n_new;     // ... and what the push adds
+  uint64_t held_x;    // the lane's sample at held_old
+  uint64_t held_old, held_new;  // elements of `held`, multiples of 4
+  int64_t x0;
+  uint32_t unit, pad;
+};
+hipError_t launch_stage_segments(const void *src, glc_pcm_format fmt, uint32_t bits, const StreamSpan *spans, uint32_t n_spans,
+                                 uint32_t vs_units, uint32_t held_units, uint32_t ch, bool planar, uint64_t channel_stride,
+                                 float *held, float *vstream, hipStream_t s);
+
 // D2 by descriptor, one per kept output hop (the batch drivers): the hop is made of the second half of block slot
 // `prev` (-1: +0.0, a stream's first hop) and the first half of slot `cur` (-1: none, the bare tail).  The
 // destination is a 64-bit element index bound to no alignment beyond that of `out`, which is aligned to its

@@ -2254,6 +2254,57 @@ __global__ __launch_bounds__(256) void k_stage_clips_planar_any(const S *__restr
 }
 
 // ------------------------------------------------------------------------------------------
+// S2: the segment stager of a streaming push (glc_kernels.h StreamSpan).  Workgroup row blockIdx.x is a UNIT of 512
+// samples per channel: units [0, vs_units) are the half hops of the round's virtual stream, the ones behind them the
+// quarters of the lanes' new held-back buffers.  A unit's span is the last one whose `unit` is <= it (a binary search
+// per workgroup, as S1); unit 0 and unit vs_units - 1 belong to no lane and are +0.0.  Sample x of a lane comes from
+// what it held back (x < received), from the new chunk (x < received + n_new), and is +0.0 in front of sample 0 and
+// behind the chunk.  A thread owns a float4 of the interleaved destination and fetches its four samples one by one.
+// The held-back samples are read from one buffer and written to the other, so no order among the workgroups matters.
+// grid (units, ch).
+// ------------------------------------------------------------------------------------------
+template <typename S>
+__global__ __launch_bounds__(256) void k_stage_segments(const S *__restrict__ src, const StreamSpan *__restrict__ spans,
+                                                         unsigned n_spans, unsigned vs_units, unsigned ch, unsigned planar,
+                                                         unsigned long long cstride, float inv, float *__restrict__ held,
+                                                         float *__restrict__ vs) {
+  const unsigned u = blockIdx.x;
+  const unsigned per_unit = 512u * ch;
+  const unsigned o = (blockIdx.y * 256u + threadIdx.x) * 4u;
+  if (o >= per_unit) return;
+  if (u < vs_units && (u == 0 || u + 1 == vs_units)) {
+    *reinterpret_cast<float4 *>(vs + static_cast<size_t>(u) * per_unit + o) = float4{0.0f, 0.0f, 0.0f, 0.0f};
+    return;
+  }
+  unsigned lo = 0, hi = n_spans;  // spans[lo].unit <= u < spans[hi].unit
+  while (hi - lo > 1) {
+    const unsigned mid = (lo + hi) >> 1;
+    if (spans[mid].unit <= u) lo = mid;
+    else hi = mid;
+  }
+  const StreamSpan sp = spans[lo];
+  const long long x_unit = sp.x0 + 512ll * static_cast<long long>(u - sp.unit);
+  const long long received = static_cast<long long>(sp.received), end = static_cast<long long>(sp.received + sp.n_new);
+  const long long held_x = static_cast<long long>(sp.held_x);
+  float q[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const unsigned i = (o + e) / ch, c = (o + e) - i * ch;
+    const long long x = x_unit + i;
+    float v = 0.0f;
+    if (x >= held_x && x < received) {
+      v = held[sp.held_old + static_cast<unsigned long long>(x - held_x) * ch + c];
+    } else if (x >= received && x < end) {
+      const unsigned long long t = static_cast<unsigned long long>(x - received);
+      v = stage_widen(src[sp.src + (planar ? c * cstride + t : t * ch + c)], inv);
+    }
+    q[e] = v;
+  }
+  float *dst = u < vs_units ? vs + static_cast<size_t>(u) * per_unit : held + sp.held_new + static_cast<size_t>(u - sp.unit) * per_unit;
+  *reinterpret_cast<float4 *>(dst + o) = float4{q[0], q[1], q[2], q[3]};
+}
+
+// ------------------------------------------------------------------------------------------
 // Clock probe (include/glc_debug.h, measurement only): ONE wave that sleeps beside whatever else runs
 // on the device and reads the shader-clock counter (s_memtime) against the constant 100 MHz counter
 // (s_memrealtime) over `ticks_100mhz`: shader cycles / reference ticks x 100 MHz = the clock the chip
@@ -2910,6 +2961,37 @@ hipError_t launch_stage_clips_int(const void *src, bool wide, uint32_t bits, con
   const float inv = pcm_widen_inv(bits);
   return wide ? stage_clips_typed(static_cast<const int *>(src), clips, n_clips, ch, planar, channel_stride, n_virtual_frames, inv, vstream, s)
               : stage_clips_typed(static_cast<const short *>(src), clips, n_clips, ch, planar, channel_stride, n_virtual_frames, inv, vstream, s);
+}
+
+namespace {
+template <typename S>
+hipError_t stage_segments_typed(const S *src, const StreamSpan *spans, uint32_t n_spans, uint32_t vs_units, uint32_t held_units,
+                                uint32_t ch, bool planar, uint64_t channel_stride, float inv, float *held, float *vstream, hipStream_t s) {
+  if (!spans || !held || n_spans == 0 || ch == 0 || ch > 65535u || (vs_units && !vstream) || vs_units == 1 ||
+      ((reinterpret_cast<uintptr_t>(vstream) | reinterpret_cast<uintptr_t>(held)) & 15u) ||
+      (reinterpret_cast<uintptr_t>(src) & (sizeof(S) - 1u)))
+    return hipErrorInvalidValue;
+  if (vs_units + held_units == 0) return hipSuccess;
+  // 512 * ch / 4 float4 over 256 threads: ceil(ch / 2) workgroups per unit
+  hipLaunchKernelGGL(k_stage_segments<S>, dim3(vs_units + held_units, (ch + 1u) / 2u), dim3(256), 0, s, src, spans, n_spans, vs_units,
+                     ch, planar && ch > 1 ? 1u : 0u, static_cast<unsigned long long>(channel_stride), inv, held, vstream);
+  return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_stage_segments(const void *src, glc_pcm_format fmt, uint32_t bits, const StreamSpan *spans, uint32_t n_spans,
+                                 uint32_t vs_units, uint32_t held_units, uint32_t ch, bool planar, uint64_t channel_stride,
+                                 float *held, float *vstream, hipStream_t s) {
+  if (fmt == GLC_PCM_F32)
+    return stage_segments_typed(static_cast<const float *>(src), spans, n_spans, vs_units, held_units, ch, planar, channel_stride, 1.0f,
+                                held, vstream, s);
+  const bool wide = fmt == GLC_PCM_S32;
+  if ((!wide && fmt != GLC_PCM_S16) || bits == 0 || bits > (wide ? 32u : 16u)) return hipErrorInvalidValue;
+  const float inv = pcm_widen_inv(bits);
+  return wide ? stage_segments_typed(static_cast<const int *>(src), spans, n_spans, vs_units, held_units, ch, planar, channel_stride, inv,
+                                     held, vstream, s)
+              : stage_segments_typed(static_cast<const short *>(src), spans, n_spans, vs_units, held_units, ch, planar, channel_stride, inv,
+                                     held, vstream, s);
 }
 
 namespace {

@@ -858,6 +858,85 @@ int glc_decode_crops_device_store_i16(glc_ctx *ctx,
                                       const int64_t *d_clips, const int64_t *d_starts, uint64_t length,
                                       int16_t *d_out, const glc_clip_layout *out);
 
+/* ---- streaming encode: PCM in chunks, many live streams per launch chain ------------------- */
+
+/* Frame f of a stream reads the per-channel samples [1024 f - 512, 1024 f + 1536), so it is final once
+ * 1024 f + 1536 samples have arrived, whatever follows; only the last frames depend on the total length.  A stream
+ * pushed in ANY chunking serialises to exactly the bytes glc_encode gives for the concatenation.
+ *
+ * Host only: what a push of n_new samples per channel completes on a lane that has received `received` so far.
+ * Without `finish`: the frames done after R samples are max(1, (R + 512) / 1024) - 1; held back afterwards is
+ * everything from sample 1024 done - 512 on (everything while done == 0), never more than 2047 samples per channel.
+ * With `finish` the total L = received + n_new ends the stream: all remaining frames of the encode plan of L samples
+ * of one channel are completed, with the reference's zero padding behind L, and carry is 0.
+ * GLC_EINVAL: a null pointer, a sum that wraps, a finish at L <= 512 (the reference panics there). */
+typedef struct glc_stream_push_plan {
+  uint64_t first_frame;  /* frames completed before this push */
+  uint64_t n_frames;     /* frames this push completes */
+  uint64_t carry;        /* samples per channel held back afterwards; 0 after a finish */
+} glc_stream_push_plan;
+int glc_plan_stream_push(uint64_t received, uint64_t n_new, int finish, glc_stream_push_plan *out);
+
+/* A session of n_streams independent lanes of `channels` channels on one context.  The session owns the lanes'
+ * held-back samples in device memory of its own (widened floats, two buffers of 2048 * channels per lane); the host
+ * keeps the samples received and the frames done per lane.  No workspace of the context holds lane state: any other
+ * call on the context may run between two pushes.  Close a session before its context is destroyed.  open, close,
+ * reset and the getters leave the context as it was.  A session is not thread-safe, like its context.
+ * GLC_EINVAL: a null pointer, channels == 0, n_streams == 0 or so many that the buffers' size wraps. */
+typedef struct glc_stream_enc glc_stream_enc;
+int glc_stream_enc_open(glc_ctx *ctx, uint16_t channels, uint64_t n_streams, glc_stream_enc **out);
+void glc_stream_enc_close(glc_stream_enc *s);
+/* Lane `stream` back to "nothing received": what it held back and its host segments are dropped. */
+int glc_stream_enc_reset(glc_stream_enc *s, uint64_t stream);
+/* Samples per channel one lane may take in one device push: the frames it completes then fit one round. */
+uint64_t glc_stream_enc_max_push(uint16_t channels);
+
+/* Device push.  Lane i receives the in->lengths[i] (or in->length) samples per channel of clip i of the layout
+ * (in->n_clips == n_streams, in->channels == the session's; a length may be 0); layout, sample types, strides and
+ * alignment are those of glc_encode_batch_device_compact_int, and nothing outside those samples is read.  finish[i]
+ * != 0 (host array, or NULL for none) ends lane i with this chunk, which may be empty; the lane is fresh afterwards.
+ * Every lane that completes at least one frame yields one SEGMENT, in ascending lane order: segs[j] (host, room for
+ * n_streams, filled before the call returns, *n_segs of them) names the lane and the frame range, d_entries[j]
+ * (device, room for n_streams) is written by the device, and the blob is byte for byte what glc_encode_range_device
+ * of those frames of the whole stream followed by glc_compact_device_records gives.  Placement, the 64-byte
+ * alignment, the `stored` rule and the cursor that counts on are exactly those of glc_encode_batch_device_compact.
+ * A lane that completes nothing writes no entry; only what it holds back changes.
+ * Segments are packed into rounds as clips are, each counting its frames + 1 (one more per round in front); per round
+ * one stager launch - it replaces the gather: the virtual stream from what was held back and what arrived, and (first
+ * round) every lane's new held-back samples -, the transform and quantiser chain and the three pack launches, whatever
+ * the number of lanes.  Queued on glc_ctx_stream of the session's context, NOT synchronised; no copy to the host and
+ * none from it but the pinned table image; the call blocks only where a workspace has to grow and on the table image
+ * of the previous batch call.  Afterwards the context is as glc_encode_batch_device_compact leaves it: no stream
+ * resident, an open decode session closed; this holds for every accepted push, whether or not it completes a frame.
+ * GLC_EINVAL, before anything is queued and changing nothing: a null or misaligned pointer, a layout that does not
+ * match the session or whose strides are too small, a chunk above glc_stream_enc_max_push or a finish that
+ * glc_plan_stream_push refuses (the message names the lane), an arena or entries range that overlaps the input,
+ * a session that has taken a host push. */
+typedef struct glc_stream_seg { uint64_t stream, first_frame, n_frames; } glc_stream_seg;
+int glc_stream_enc_push_device(glc_stream_enc *s, const void *d_pcm, glc_pcm_format fmt, uint32_t bits,
+                               const glc_clip_layout *in, const uint8_t *finish,
+                               void *d_arena, uint64_t arena_bytes, uint64_t *d_cursor,
+                               glc_store_entry *d_entries, glc_stream_seg *segs, uint64_t *n_segs);
+
+/* Host push.  pcm[i]: the n_samples[i] interleaved samples lane i receives (a multiple of channels, may be 0 and
+ * pcm[i] then NULL); finish as above.  The chunks are staged in pinned memory and uploaded, the device push runs into
+ * an arena the session owns (sized so that every blob fits), and the new blobs come down - which synchronises - and
+ * are appended to the lane's list.  A chunk above glc_stream_enc_max_push is split into several pushes, so it may
+ * give several segments.  The segments are what a sender ships as they appear; glc_frames_from_compact assembles them.
+ * A finished lane refuses further samples (GLC_EINVAL) until glc_stream_enc_frames or glc_stream_enc_reset.
+ * A session is used through host pushes or through device pushes, never both: the first push decides.
+ * Totals that are no multiple of `channels` stay with glc_encode.  A refused push changes nothing. */
+int glc_stream_enc_push(glc_stream_enc *s, const void *const *pcm, glc_pcm_format fmt, uint32_t bits,
+                        const uint64_t *n_samples, const uint8_t *finish);
+/* The segments lane `stream` has completed through host pushes and not handed over yet. */
+int glc_stream_enc_segments(const glc_stream_enc *s, uint64_t stream, uint64_t *n_blobs);
+/* Segment k of them: borrowed, valid until the lane is taken, reset or the session closed.  Any output may be NULL. */
+int glc_stream_enc_segment(const glc_stream_enc *s, uint64_t stream, uint64_t k, const void **blob, uint64_t *bytes,
+                           uint64_t *first_frame, uint64_t *n_frames);
+/* After the finish: the lane's stream assembled from its segments (the context's sample rate, L * channels samples),
+ * then the lane is cleared.  GLC_EINVAL while the lane is not finished. */
+int glc_stream_enc_frames(glc_stream_enc *s, uint64_t stream, glc_frames **out);
+
 /* ---- tables (for inspection / parity tests) ---------------------------------------------- */
 
 /* Copies of the host tables of a context: MdctTables.cos_table [1024*2048] (row k), window

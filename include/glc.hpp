@@ -624,6 +624,100 @@ class RoundTrip {
   glc_ctx *ctx_ = nullptr;
 };
 
+// What a push of n_new samples per channel completes on a lane that has `received` so far (glc_plan_stream_push);
+// throws where a finish ends a stream the encoder refuses.
+inline glc_stream_push_plan plan_stream_push(uint64_t received, uint64_t n_new, bool finish = false) {
+  glc_stream_push_plan p{};
+  detail::check(glc_plan_stream_push(received, n_new, finish ? 1 : 0, &p));
+  return p;
+}
+
+// Encoder::encode fed in chunks (glc.h glc_stream_enc_*): n_streams independent lanes of `channels` channels on a
+// context of its own.  A lane pushed in any chunking serialises to the bytes Encoder::encode gives for the
+// concatenation.  Host pushes (push / segments / encoded) or device pushes (push_device), not both on one object.
+class StreamEncoder {
+ public:
+  struct Segment {
+    uint64_t first_frame, n_frames;
+    const void *blob;  // borrowed: valid until the lane is taken, reset or the object destroyed
+    uint64_t bytes;
+  };
+  StreamEncoder(uint32_t sample_rate, uint16_t channels, uint64_t n_streams = 1, int device = 0) : channels_(channels), n_(n_streams) {
+    detail::check(glc_ctx_create(device, sample_rate, &ctx_));
+    const int rc = glc_stream_enc_open(ctx_, channels, n_streams, &s_);
+    if (rc != GLC_OK) {
+      const Error e(rc, glc_last_error(ctx_));
+      glc_ctx_destroy(ctx_);
+      throw e;
+    }
+  }
+  ~StreamEncoder() {
+    glc_stream_enc_close(s_);  // before its context
+    glc_ctx_destroy(ctx_);
+  }
+  StreamEncoder(const StreamEncoder &) = delete;
+  StreamEncoder &operator=(const StreamEncoder &) = delete;
+  uint64_t n_streams() const { return n_; }
+  uint64_t max_push() const { return glc_stream_enc_max_push(channels_); }
+  // every lane at once: pcm[i] / n_samples[i] interleaved samples for lane i, finish[i] != 0 ends it (or nullptr)
+  void push(const void *const *pcm, glc_pcm_format fmt, uint32_t bits, const uint64_t *n_samples, const uint8_t *finish) {
+    detail::check(glc_stream_enc_push(s_, pcm, fmt, bits, n_samples, finish), ctx_);
+  }
+  // one lane, the others receive nothing
+  void push(uint64_t stream, const float *samples, uint64_t n_samples, bool finish = false) {
+    push_one(stream, samples, GLC_PCM_F32, 32, n_samples, finish);
+  }
+  void push(uint64_t stream, const int16_t *samples, uint64_t n_samples, bool finish = false, uint32_t bits = 16) {
+    push_one(stream, samples, GLC_PCM_S16, bits, n_samples, finish);
+  }
+  void push(uint64_t stream, const int32_t *samples, uint32_t bits, uint64_t n_samples, bool finish = false) {
+    push_one(stream, samples, GLC_PCM_S32, bits, n_samples, finish);
+  }
+  std::vector<Segment> segments(uint64_t stream = 0) const {
+    uint64_t n = 0;
+    detail::check(glc_stream_enc_segments(s_, stream, &n), ctx_);
+    std::vector<Segment> v(n);
+    for (uint64_t k = 0; k < n; ++k)
+      detail::check(glc_stream_enc_segment(s_, stream, k, &v[k].blob, &v[k].bytes, &v[k].first_frame, &v[k].n_frames), ctx_);
+    return v;
+  }
+  // after the finish: the lane's stream; the lane is fresh afterwards
+  EncodedAudio encoded(uint64_t stream = 0) {
+    glc_frames *h = nullptr;
+    detail::check(glc_stream_enc_frames(s_, stream, &h), ctx_);
+    return EncodedAudio(h);
+  }
+  void reset(uint64_t stream = 0) { detail::check(glc_stream_enc_reset(s_, stream), ctx_); }
+  // glc_stream_enc_push_device: queued on the context's stream, not synchronised; returns the segments (host)
+  std::vector<glc_stream_seg> push_device(const void *d_pcm, glc_pcm_format fmt, uint32_t bits, const glc_clip_layout &in,
+                                          const uint8_t *finish, void *d_arena, uint64_t arena_bytes, uint64_t *d_cursor,
+                                          glc_store_entry *d_entries) {
+    std::vector<glc_stream_seg> segs(n_);
+    uint64_t n = 0;
+    detail::check(glc_stream_enc_push_device(s_, d_pcm, fmt, bits, &in, finish, d_arena, arena_bytes, d_cursor, d_entries, segs.data(), &n),
+                  ctx_);
+    segs.resize(n);
+    return segs;
+  }
+  void synchronize() { detail::check(glc_ctx_synchronize(ctx_), ctx_); }
+  glc_ctx *ctx() { return ctx_; }
+  glc_stream_enc *handle() { return s_; }
+
+ private:
+  void push_one(uint64_t stream, const void *samples, glc_pcm_format fmt, uint32_t bits, uint64_t n_samples, bool finish) {
+    if (stream >= n_) throw Error(GLC_EINVAL, "StreamEncoder::push: no such stream");
+    std::vector<const void *> pcm(n_, nullptr);
+    std::vector<uint64_t> ns(n_, 0);
+    std::vector<uint8_t> fin(n_, 0);
+    pcm[stream] = samples, ns[stream] = n_samples, fin[stream] = finish ? 1 : 0;
+    push(pcm.data(), fmt, bits, ns.data(), fin.data());
+  }
+  glc_ctx *ctx_ = nullptr;
+  glc_stream_enc *s_ = nullptr;
+  uint16_t channels_ = 0;
+  uint64_t n_ = 0;
+};
+
 // save_encoded / load_encoded — src/codec.rs:774-786
 inline void save_encoded(const EncodedAudio &e, const std::string &path) { detail::check(glc_save(e.handle(), path.c_str())); }
 inline EncodedAudio load_encoded(const std::string &path) {

@@ -3,6 +3,7 @@
 // save, load, decode both ways, and leave the artefacts on disk for the caller to compare.
 //   glc_cpp_roundtrip <in.f32> <sample_rate> <channels> <out.glc> <out.f32>
 // Build: g++ -O2 -std=c++17 -Iinclude tools/glc_cpp_roundtrip.cpp -Lgapless-lossy-codec_amd -lglc_hip
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -12,11 +13,44 @@
 #include "glc.hpp"
 
 int main(int argc, char **argv) {
-  if (argc != 6) {
-    std::fprintf(stderr, "usage: %s in.f32 sample_rate channels out.glc out.f32\n", argv[0]);
+  if (argc != 6 && argc != 8) {
+    std::fprintf(stderr, "usage: %s in.f32 sample_rate channels out.glc out.f32 [chunk_sample_frames stream_out.glc]\n", argv[0]);
     return 2;
   }
   try {
+    if (argc == 8) {
+      // the streaming encoder through the C++ mirror: the file in chunks of argv[6] sample frames, the finish as an
+      // empty push; the segments' frame ranges tile the stream; the bytes go to argv[7] for the caller to compare
+      std::ifstream in(argv[1], std::ios::binary);
+      std::vector<char> raw((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+      std::vector<float> pcm(raw.size() / sizeof(float));
+      std::memcpy(pcm.data(), raw.data(), pcm.size() * sizeof(float));
+      const uint32_t sr = static_cast<uint32_t>(std::atoi(argv[2]));
+      const uint16_t ch = static_cast<uint16_t>(std::atoi(argv[3]));
+      const uint64_t chunk = static_cast<uint64_t>(std::atoll(argv[6])) * ch;
+      if (chunk == 0) return std::fprintf(stderr, "chunk_sample_frames must be positive\n"), 2;
+      glc::StreamEncoder se(sr, ch, 2);  // lane 1 is the one in use, lane 0 stays idle
+      uint64_t received = 0;
+      for (uint64_t at = 0; at < pcm.size(); at += chunk) {
+        const uint64_t n = std::min<uint64_t>(chunk, pcm.size() - at);
+        const glc_stream_push_plan plan = glc::plan_stream_push(received, n / ch);
+        const size_t before = se.segments(1).size();
+        se.push(1, pcm.data() + at, n);
+        if (se.segments(1).size() != before + (plan.n_frames ? 1 : 0)) return std::fprintf(stderr, "segments do not follow the plan\n"), 1;
+        received += n / ch;
+      }
+      se.push(1, static_cast<const float *>(nullptr), 0, true);
+      uint64_t next = 0;
+      for (const glc::StreamEncoder::Segment &g : se.segments(1)) {
+        if (g.first_frame != next) return std::fprintf(stderr, "segments do not tile the stream\n"), 1;
+        next += g.n_frames;
+      }
+      if (!se.segments(0).empty()) return std::fprintf(stderr, "the idle lane has segments\n"), 1;
+      const glc::EncodedAudio e = se.encoded(1);
+      if (e.n_frames() != next || !se.segments(1).empty()) return std::fprintf(stderr, "encoded(): wrong frame count\n"), 1;
+      glc::save_encoded(e, argv[7]);
+      return 0;
+    }
     std::ifstream in(argv[1], std::ios::binary);
     std::vector<char> raw((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
     std::vector<float> pcm(raw.size() / sizeof(float));
