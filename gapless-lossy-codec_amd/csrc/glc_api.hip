@@ -212,6 +212,14 @@ struct glc_ctx {
   DevBuf bound_tables;             // the matrix form's table image (glc_kernels.h MatrixBound), where the form is built
   uint64_t repair_launches[2] = {0, 0};  // screened launches that took k_mdct_fwd_small_cols / k_mdct_fwd_small_rows
   uint64_t rows_screened = 0;
+  // The edge path of a screened launch (glc_kernels.h EdgeLaunch): a side stream of the context's own - not stream_b,
+  // which the chunk alternation uses - and per slot the three events of a launch's fork and join.
+  int edge_kind = 0;               // include/glc_debug.h glc_debug_set_encode_edge
+  hipStream_t edge_stream = nullptr;
+  hipEvent_t ev_edge[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // {fork, edge rows done}
+  DevBuf edge_coef[2];             // the edge rows' coefficients, [kEdgeRowsMax][1024]
+  DevBuf edge_failed;              // [2] uint64_t, zeroed once: per slot the edge rows that failed the screen so far
+  uint64_t edge_launches = 0, edge_rows = 0;  // screened launches that took the edge path, and their edge rows
   hipStream_t probe_stream = nullptr;  // include/glc_debug.h clock probe
   HostBuf probe_out;
   uint32_t dec_ch = 0;
@@ -418,12 +426,18 @@ void glc_ctx_destroy(glc_ctx *ctx) {
   for (hipEvent_t e : ctx->ev_round)
     if (e) (void)hipEventDestroy(e);
   if (ctx->stream_b) (void)hipStreamDestroy(ctx->stream_b);
+  if (ctx->edge_stream) (void)hipStreamDestroy(ctx->edge_stream);
+  for (auto &slot : ctx->ev_edge)
+    for (hipEvent_t ev : slot)
+      if (ev) (void)hipEventDestroy(ev);
   if (ctx->probe_stream) (void)hipStreamDestroy(ctx->probe_stream);
   ctx->probe_out.release();
   ctx->coef_b.release();
   ctx->screen_ws[0].release();
   ctx->screen_ws[1].release();
   ctx->screen_stat.release();
+  for (DevBuf &b : ctx->edge_coef) b.release();
+  ctx->edge_failed.release();
   if (ctx->down_stream) (void)hipStreamDestroy(ctx->down_stream);
   if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -601,6 +615,11 @@ static bool screen_takes(glc_ctx *ctx, uint32_t M, uint32_t ch) {
 // them in one run - the tile kernel's best case, a tile of 32 rows is all failed rows - it still wins at 132 failed
 // rows (by 5.8 us) and loses at 516 (by 119 us).  128 is the largest count of the sweep at which it wins either way.
 constexpr uint32_t kScreenRepairLatencyRows = 128;
+// Which edge transform a launch that takes the edge path gets (include/glc_debug.h glc_debug_set_encode_edge): the
+// capped one unless the latency form is forced.  Measured (profiles/encode_edge_bench.txt): the latency form's waves
+// do not fit beside two resident workgroups of K2 and cost K2 its single round; the capped form's do.
+static bool edge_capped(const glc_ctx *ctx) { return ctx->edge_kind != 2; }
+
 static bool screen_latency_repair(const glc_ctx *ctx) {
   if (ctx->repair_kind) return ctx->repair_kind == 2;
   return ctx->screen_judged_any && ctx->screen_last_failed <= kScreenRepairLatencyRows;
@@ -629,6 +648,14 @@ static hipError_t screen_reserve(glc_ctx *ctx, int slot, uint32_t ch, uint64_t f
     if (e != hipSuccess) return e;
     std::memset(ctx->screen_stat.p, 0, 2 * 8 * sizeof(uint32_t));
   }
+  if (!ctx->edge_failed.p) {
+    // the edge path's running total, cleared where it is allocated - beside the workspaces, before any launch is
+    // queued - and waited for here, since the streams that will use it do not order themselves behind this one
+    hipError_t e = ctx->edge_failed.reserve(2 * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipMemset(ctx->edge_failed.p, 0, 2 * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) return e;
+  }
   return ctx->screen_ws[slot].reserve(need);
 }
 
@@ -636,7 +663,8 @@ static hipError_t screen_reserve(glc_ctx *ctx, int slot, uint32_t ch, uint64_t f
 // alternate rounds on two streams)
 static int encode_range_on(glc_ctx *ctx, hipStream_t stream, DevBuf &coef_ws, const float *d_pcm, uint64_t t0, uint64_t t_count,
                            uint64_t n_samples, uint16_t channels, uint64_t frame_begin, uint64_t frame_end,
-                           void *d_records, float *d_coeffs, bool alternate_ok = false, bool beside = false) {
+                           void *d_records, float *d_coeffs, bool alternate_ok = false, bool beside = false,
+                           bool edge_ok = false) {
   const int rc = check_encode_range(ctx, "glc_encode_range_device", d_pcm, t0, t_count, n_samples, channels,
                                     frame_begin, frame_end, d_records, d_coeffs != nullptr);
   if (rc != GLC_OK) return rc;
@@ -666,6 +694,10 @@ static int encode_range_on(glc_ctx *ctx, hipStream_t stream, DevBuf &coef_ws, co
     GLC_HIP(ctx, hipEventRecord(ctx->ev_fork, stream));
     GLC_HIP(ctx, hipStreamWaitEvent(ctx->stream_b, ctx->ev_fork, 0));
   }
+  // The stream's edge frames (glc_kernels.h edge_frames): a screened chunk that holds some hands them to the side
+  // stream.  Only the call that owns its stream's order does (edge_ok): the drivers pass no edge range.
+  const glc_plan plan = glc::plan_encode(n_samples, channels);
+  const glc::EdgeFrames ef = glc::edge_frames(plan.per_channel, plan.n_frames);
   uint64_t c_idx = 0;
   for (uint64_t f = frame_begin; f < frame_end; f += chunk, ++c_idx) {
     const uint64_t nf = std::min<uint64_t>(chunk, frame_end - f);
@@ -682,9 +714,25 @@ static int encode_range_on(glc_ctx *ctx, hipStream_t stream, DevBuf &coef_ws, co
       const bool latency = screen_latency_repair(ctx);
       const bool matrix = screen_matrix_bound(ctx, M, ch);
       if (slot == 0) ctx->tap_rows = M, ctx->tap_planes = matrix ? glc::MatrixBound::kGroups : ctx->screen_shape.n_planes;
+      glc::EdgeLaunch edge{ef.a, ef.b, nullptr, nullptr, nullptr, nullptr, false, nullptr};
+      const uint32_t n_edge = glc::edge_rows(ef.a, ef.b, f, M, ch).n;
+      const bool take_edge = edge_ok && ctx->edge_kind != 1 && n_edge >= 1 && n_edge <= glc::kEdgeRowsMax && ctx->edge_failed.p;
+      if (take_edge) {
+        if (!ctx->edge_stream) GLC_HIP(ctx, hipStreamCreateWithFlags(&ctx->edge_stream, hipStreamNonBlocking));
+        for (hipEvent_t &ev : ctx->ev_edge[slot])
+          if (!ev) GLC_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        GLC_HIP(ctx, ctx->edge_coef[slot].reserve(static_cast<size_t>(glc::kEdgeRowsMax) * glc::kHop * sizeof(float)));
+        edge.side = ctx->edge_stream;
+        edge.ev_fork = ctx->ev_edge[slot][0], edge.ev_edge = ctx->ev_edge[slot][1];
+        edge.coef = static_cast<float *>(ctx->edge_coef[slot].p);
+        edge.capped = edge_capped(ctx);
+        edge.failed_total = static_cast<unsigned long long *>(ctx->edge_failed.p) + slot;
+        ++ctx->edge_launches;
+        ctx->edge_rows += n_edge;
+      }
       GLC_HIP(ctx, glc::launch_encode_screened(ctx->dev, ctx->screen_shape, view, f, M, coef, ctx->screen_ws[slot].p,
                                                static_cast<uint32_t *>(ctx->screen_stat.p) + 8 * slot, ++ctx->screen_seq[slot],
-                                               r, st, &decided, latency, matrix));
+                                               r, st, &decided, latency, matrix, take_edge ? &edge : nullptr));
       ++ctx->repair_launches[latency ? 1 : 0];
       if (!decided) GLC_HIP(ctx, glc::launch_decide_raw(ctx->dev, view, f, static_cast<uint32_t>(nf), r, st));
       ctx->rows_screened += M;
@@ -705,7 +753,7 @@ int glc_encode_range_device(glc_ctx *ctx, const float *d_pcm, uint64_t t0, uint6
                             uint64_t frame_end, void *d_records, float *d_coeffs) {
   if (!ctx) return GLC_EINVAL;
   return encode_range_on(ctx, ctx->stream, ctx->coef, d_pcm, t0, t_count, n_samples, channels, frame_begin, frame_end,
-                         d_records, d_coeffs, /*alternate_ok=*/true);
+                         d_records, d_coeffs, /*alternate_ok=*/true, /*beside=*/false, /*edge_ok=*/true);
 }
 
 int glc_debug_quantize_device(glc_ctx *ctx, const float *d_coeffs, const float *d_pcm, uint64_t t0, uint64_t t_count,
@@ -4280,6 +4328,19 @@ int glc_debug_set_encode_repair(glc_ctx *ctx, int kind) {
   return GLC_OK;
 }
 
+int glc_debug_set_encode_edge(glc_ctx *ctx, int kind) {
+  if (!ctx || kind < 0 || kind > 3) return fail(ctx, GLC_EINVAL, "glc_debug_set_encode_edge: kind must be 0..3");
+  ctx->edge_kind = kind;
+  return GLC_OK;
+}
+
+int glc_debug_encode_edge_stats(glc_ctx *ctx, uint64_t *launches, uint64_t *rows) {
+  if (!ctx || !launches || !rows) return fail(ctx, GLC_EINVAL, "glc_debug_encode_edge_stats: null argument");
+  *launches = ctx->edge_launches;
+  *rows = ctx->edge_rows;
+  return GLC_OK;
+}
+
 int glc_debug_set_encode_bound(glc_ctx *ctx, int kind) {
   if (!ctx || kind < 0 || kind > 2) return fail(ctx, GLC_EINVAL, "glc_debug_set_encode_bound: kind must be 0..2");
   ctx->bound_kind = kind;
@@ -4347,7 +4408,13 @@ int glc_debug_encode_screen_stats(glc_ctx *ctx, uint64_t *rows_screened, uint64_
   *rows_repaired = 0;
   if (ctx->screen_stat.p) {
     const volatile uint64_t *hs = static_cast<const volatile uint64_t *>(ctx->screen_stat.p);
-    *rows_repaired = hs[2] + hs[4 + 2];
+    *rows_repaired = hs[2] + hs[4 + 2];  // per slot: the rows the serial repair took
+  }
+  if (ctx->edge_failed.p) {  // ... and the edge rows that failed, which the side stream took
+    uint64_t e[2] = {0, 0};  // (the streams that write it have been waited for above)
+    GLC_HIP(ctx, hipMemcpyAsync(e, ctx->edge_failed.p, sizeof e, hipMemcpyDeviceToHost, ctx->stream));
+    GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *rows_repaired += e[0] + e[1];
   }
   return GLC_OK;
 }

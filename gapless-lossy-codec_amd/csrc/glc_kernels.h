@@ -93,11 +93,61 @@ bool mdct_forward_is_st16(uint32_t M, uint32_t ch, int variant);
 bool mdct_forward_has_segment_loader(uint32_t ch);
 uint64_t encode_screen_bytes(uint32_t M, const ScreenShape &sh);
 // workspace: encode_screen_bytes(M) bytes, 16-byte aligned, nothing in it needs initialising.  host_stat: 8
-// device-visible host words {failed rows, rows, seq, -, u64 failed rows so far, ...} the last launch writes.
+// device-visible host words {failed rows, rows, seq, -, u64 failed rows so far, ...} the last launch writes; they count
+// the serial repair's rows, the edge rows that failed go to EdgeLaunch::failed_total alone.
+// The edge path: the frames whose window reaches into the stream's zero padding (edge_frames below) fail the screen
+// on any content that is not silent there, and which they are is known before anything is launched.  With `edge`
+// given, their exact coefficients (k_mdct_edge_rows, the repair's chain with the row list taken from the kernel
+// arguments, all 1024 columns into edge->coef) and their records (k_quantize_screen<*, 3>) are queued on edge->side
+// beside K1 and K2, depending on nothing either writes; K2 evaluates their screen but neither writes nor lists them,
+// the serial repair is left the rows nobody could predict, and the caller's stream continues only behind the side
+// stream's last launch.  Same record bytes with or without it.
+struct EdgeLaunch {
+  uint64_t a, b;                // edge_frames of the stream, absolute frame numbers
+  hipStream_t side;             // not the launch's stream
+  hipEvent_t ev_fork, ev_edge;  // this launch's own until its stream has passed the join
+  float *coef;                  // [kEdgeRowsMax][1024], this launch's own for as long
+  bool capped;                  // the transform with the short table ring and a register cap (k_mdct_edge_rows_capped: fits beside
+                                // two resident workgroups of K2 on a CU) instead of the latency form; same bytes
+  unsigned long long *failed_total;  // device: the edge rows that failed the screen so far; the repair quantiser adds this launch's
+};
 hipError_t launch_encode_screened(const DeviceTables &t, const ScreenShape &sh, const PcmView &pcm, uint64_t frame_begin,
                                   uint32_t M, float *coef, void *workspace, uint32_t *host_stat, uint32_t seq,
                                   uint8_t *records, hipStream_t s, bool *decided, bool latency_repair = false,
-                                  bool matrix_bound = false);
+                                  bool matrix_bound = false, const EdgeLaunch *edge = nullptr);
+
+// The ONE definition of an edge frame: frame f reads per-channel samples [hop f - hop/2, hop f - hop/2 + frame); it
+// is an edge frame if that window is not wholly inside the stream [0, per_channel) of plan_encode.  Edge frames are
+// the prefix [0, a) and the suffix [b, n_frames) of the stream's frames (a <= b; a shard's halo is not padding).
+struct EdgeFrames {
+  uint64_t a, b;
+};
+GLC_HD inline EdgeFrames edge_frames(uint64_t per_channel, uint64_t n_frames) {
+  const uint64_t tail = kFrame - kHop / 2;  // a frame's window ends at hop f + tail
+  uint64_t a = n_frames < 1 ? n_frames : 1;  // frame 0 starts hop / 2 before the stream, frame 1 inside it
+  uint64_t b = per_channel >= tail ? (per_channel - tail) / kHop + 1 : 0;  // the first f with hop f + tail > per_channel
+  if (b > n_frames) b = n_frames;
+  if (b < a) b = a;
+  return {a, b};
+}
+// The edge rows of a launch of M rows (row = (frame - frame_begin) * ch + c) of a stream whose edge frames are
+// f < a || f >= b: rows [0, n_pre) and [suf0, M), n of them (suf0 >= n_pre).
+struct EdgeRows {
+  unsigned n_pre, suf0, n;
+};
+GLC_HD inline EdgeRows edge_rows(unsigned long long a, unsigned long long b, unsigned long long frame_begin, unsigned M,
+                                 unsigned ch) {
+  const unsigned long long nf = M / ch, fe = frame_begin + nf;
+  const unsigned long long pre = a > frame_begin ? (a < fe ? a : fe) - frame_begin : 0;
+  const unsigned long long s = b > frame_begin ? (b < fe ? b : fe) - frame_begin : 0;  // first suffix frame of the launch
+  const unsigned n_pre = static_cast<unsigned>(pre) * ch;
+  unsigned suf0 = static_cast<unsigned>(s) * ch;
+  if (suf0 < n_pre) suf0 = n_pre;
+  if (suf0 > M) suf0 = M;
+  return {n_pre, suf0, n_pre + (M - suf0)};
+}
+constexpr unsigned kEdgeRowsMax = 32;  // edge rows a launch may hand to the side stream: 4 frames x 8 channels
+constexpr unsigned long long kNoEdge = ~0ull;  // b of a launch that takes no edge path (with a = 0): no frame is an edge frame
 // true where the matrix form (MatrixBound) exists for a launch: the rate's ne, a channel count with a segment
 // loader, and the table image uploaded
 bool encode_matrix_bound_built(const DeviceTables &t, const ScreenShape &sh, uint32_t ch);

@@ -16,6 +16,7 @@
 //   K3 k_decide_raw    :496-502 (raw plane) + :505-540 (size estimate, decision)
 //   D1 k_imdct_rows    :626-644 (raw frames), :651-665 (dequant), :377-390 (imdct), :672-675
 //   D2 k_overlap_add   :688-705 (overlap-add + interleave), :722-729 (tail)
+#include <algorithm>
 #include <type_traits>
 
 #include "glc_common.h"
@@ -92,15 +93,23 @@ constexpr float kScreenCErr = 2.45e-4f, kScreenSlack = 1.001f, kScreenTiny = 1e-
 
 struct ScreenArgs {
   const float *hf;        // [n_planes + 1][stride]: per bound-carrying wave of the transform max |e| of its columns >= C0, then A
-  unsigned *row_flag;     // [M] 1 = the row's frame failed the screen (MODE 1 writes every entry, MODE 2 reads)
-  unsigned *wave_fail;    // [waves of the MODE 1 launch] failed rows of each wave (every entry written)
-  unsigned *host_stat;    // host-mapped {failed rows, rows, seq, -, u64 failed rows so far}: MODE 2 leaves the count
+  unsigned *row_flag;     // [M] 1 = the row's frame failed the screen and is the serial repair's, 2 = it failed and is an
+                          // edge row (the side stream's), 0 = it passed (MODE 1 writes every entry, MODE 2 reads)
+  unsigned *wave_fail;    // [waves of the MODE 1 launch] rows flagged 1 of each wave (every entry written)
+  unsigned *host_stat;    // host-mapped {failed rows, rows, seq, -, u64 failed rows so far}: MODE 2 leaves the counts;
+                          // the edge rows that failed are in none of them
   unsigned long long stride;
   unsigned c0, l0, n_planes, seq;
+  unsigned long long edge_a, edge_b;  // frame f is an edge frame iff f < edge_a || f >= edge_b (glc_kernels.h edge_frames;
+                                      // 0 and kNoEdge: none is)
+  unsigned long long *edge_total;     // device: failed edge rows so far (read and written only by a launch that has edge rows)
 };
 
 // MODE 0: every row of the launch from exact coefficients.  1: the screened form - rows that pass, from the
-// columns below C0; rows that fail are flagged and left alone.  2: the repair - MODE 0 on the flagged rows only.
+// columns below C0; rows that fail are flagged and left alone, and so are the edge rows, whose screen is evaluated
+// for the statistics only.  2: the repair - MODE 0 on the rows flagged 1 only.  3: MODE 0 on the edge rows only, one
+// workgroup per group of 16 rows that holds one; `coef` is then the edge rows' own buffer, row j of it the j-th edge
+// row (beside K1 and K2 on another stream: it reads nothing they write, and writes records they leave alone).
 template <bool FUSED, int MODE>
 __device__ __forceinline__ void quantize_body(const DeviceTables &tb, const float *__restrict__ coef, unsigned M,
                                               unsigned ch, unsigned long long rec_bytes, unsigned long long hdr_bytes,
@@ -109,29 +118,48 @@ __device__ __forceinline__ void quantize_body(const DeviceTables &tb, const floa
   __shared__ __attribute__((aligned(16))) float ssq[4][kQRows][kHopI];  // 64 KiB
   __shared__ float sbase[4][kQRows][64];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const unsigned m0 = (blockIdx.x * 4 + w) * kQRows;
-  unsigned on = 0;  // MODE 1 / 2: bit r = row m0 + r is this launch's to write
-  if constexpr (MODE == 2) {
-    if (blockIdx.x == 0 && w == 0) {  // the count of the screened launch, for the host's guard and statistics
-      const unsigned n_w = (M + 15) / 16 * 4;
-      unsigned cnt = 0;
-      for (unsigned i = lane; i < n_w; i += 64) cnt += sa.wave_fail[i];
+  unsigned blk = blockIdx.x;  // the group of 16 rows this workgroup quantises
+  EdgeRows er{0u, M, 0u};     // the launch's edge rows: [0, n_pre) and [suf0, M)
+  if constexpr (MODE != 0) er = edge_rows(sa.edge_a, sa.edge_b, static_cast<unsigned long long>(frame_begin), M, ch);
+  if constexpr (MODE == 3) {
+    const unsigned g_pre = (er.n_pre + 15u) / 16u, g_suf = er.suf0 / 16u > g_pre ? er.suf0 / 16u : g_pre;
+    if (blk >= g_pre) blk = g_suf + (blk - g_pre);
+  }
+  const unsigned m0 = (blk * 4 + w) * kQRows;
+  unsigned on = 0;  // MODE 1 / 2 / 3: bit r = row m0 + r is this launch's to write
+  auto edge_row = [&](unsigned m) -> bool { return m < er.n_pre || m >= er.suf0; };
+  if constexpr (MODE == 3) {
 #pragma unroll
-      for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
+    for (int r = 0; r < kQRows; ++r)
+      if (m0 + r < M && edge_row(m0 + r)) on |= 1u << r;
+  }
+  if constexpr (MODE == 2) {
+    if (blk == 0 && w == 0) {  // the counts of the screened launch, for the host's guard and statistics
+      const unsigned n_w = (M + 15) / 16 * 4;
+      unsigned cnt = 0, ecnt = 0;
+      // the edge rows that failed: not the serial repair's, so not in wave_fail; they count in the statistics alone,
+      // in device memory (a launch without edge rows touches none of this)
+      unsigned long long etot = 0;
+      if (er.n) etot = *sa.edge_total;
+      for (unsigned i = lane; i < n_w; i += 64) cnt += sa.wave_fail[i];
+      for (unsigned i = lane; i < er.n; i += 64) ecnt += sa.row_flag[i < er.n_pre ? i : er.suf0 + (i - er.n_pre)] == 2u;
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off), ecnt += __shfl_xor(ecnt, off);
       if (lane == 0) {
         // plain stores, in no order the host can rely on: it reads them unsynchronised, for a heuristic (the guard,
         // glc_api.hip screen_takes); the statistics call reads them after the stream has been waited for
         volatile unsigned *hs = sa.host_stat;
         volatile unsigned long long *tot = reinterpret_cast<volatile unsigned long long *>(sa.host_stat + 4);
         *tot = *tot + cnt;
+        if (er.n) *sa.edge_total = etot + ecnt;
         hs[0] = cnt;
         hs[1] = M;
         hs[2] = sa.seq;
       }
     }
     // every wave reads the 16 flags of the workgroup's rows: the whole workgroup leaves, or none of it
-    const unsigned fr = blockIdx.x * 16 + lane;
-    const bool flagged = lane < 16 && fr < M && sa.row_flag[fr] != 0u;
+    const unsigned fr = blk * 16 + lane;
+    const bool flagged = lane < 16 && fr < M && sa.row_flag[fr] == 1u;
     const unsigned blk_on = static_cast<unsigned>(__ballot(flagged));
     if (blk_on == 0u) return;
     on = (blk_on >> (4 * w)) & 0xFu;
@@ -159,7 +187,8 @@ __device__ __forceinline__ void quantize_body(const DeviceTables &tb, const floa
     const unsigned m = m0 + r;
     float amax = 0.0f;
     if (MODE == 1 ? m < M : row_on(r)) {
-      const float4 *src = reinterpret_cast<const float4 *>(coef + static_cast<size_t>(m) * kHopI);
+      const unsigned src_row = MODE == 3 ? (m < er.n_pre ? m : er.n_pre + (m - er.suf0)) : m;
+      const float4 *src = reinterpret_cast<const float4 *>(coef + static_cast<size_t>(src_row) * kHopI);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if constexpr (MODE == 1) {  // columns >= C0 (a multiple of 64) were not computed: they count as 0
@@ -227,9 +256,13 @@ __device__ __forceinline__ void quantize_body(const DeviceTables &tb, const floa
           if (static_cast<unsigned>(q) / ch == static_cast<unsigned>(r) / ch && ((fail >> q) & 1u)) ff |= 1u << r;
       fail = ff & valid;
     }
-    on = valid & ~fail;
-    if (lane < kQRows && m0 + lane < M) sa.row_flag[m0 + lane] = (fail >> lane) & 1u;
-    if (lane == 0) sa.wave_fail[blockIdx.x * 4 + w] = __builtin_popcount(fail);
+    unsigned edge = 0;  // (FUSED: a frame's rows are all edge rows or none is)
+#pragma unroll
+    for (int r = 0; r < kQRows; ++r)
+      if (((valid >> r) & 1u) && edge_row(m0 + r)) edge |= 1u << r;
+    on = valid & ~fail & ~edge;
+    if (lane < kQRows && m0 + lane < M) sa.row_flag[m0 + lane] = ((fail >> lane) & 1u) << ((edge >> lane) & 1u);
+    if (lane == 0) sa.wave_fail[blk * 4 + w] = __builtin_popcount(fail & ~edge);
   }
   __syncthreads();
 
@@ -2458,9 +2491,15 @@ uint64_t encode_screen_bytes(uint32_t M, const ScreenShape &sh) {
 
 hipError_t launch_encode_screened(const DeviceTables &t, const ScreenShape &sh, const PcmView &pcm, uint64_t frame_begin,
                                   uint32_t M, float *coef, void *workspace, uint32_t *host_stat, uint32_t seq,
-                                  uint8_t *records, hipStream_t s, bool *decided, bool latency_repair, bool matrix_bound) {
+                                  uint8_t *records, hipStream_t s, bool *decided, bool latency_repair, bool matrix_bound,
+                                  const EdgeLaunch *edge) {
   *decided = pcm.ch == 1 || pcm.ch == 2 || pcm.ch == 4;
   if (M == 0) return hipSuccess;
+  // the edge rows the side stream takes: none without `edge`, and then every kernel below is what it always was
+  const unsigned long long edge_a = edge ? edge->a : 0ull, edge_b = edge ? edge->b : kNoEdge;
+  const EdgeRows er = edge_rows(edge_a, edge_b, frame_begin, M, pcm.ch);
+  if (edge && (er.n == 0 || er.n > kEdgeRowsMax || !edge->side || edge->side == s || !edge->coef || !edge->failed_total))
+    return hipErrorInvalidValue;
   const uint64_t stride = screen_stride(M);
   float *hf = static_cast<float *>(workspace);
   // the workspace is carved for the FMA form, the larger of the two: the matrix form's 4 planes and its A plane lie
@@ -2471,6 +2510,7 @@ hipError_t launch_encode_screened(const DeviceTables &t, const ScreenShape &sh, 
   if (matrix_bound && !encode_matrix_bound_built(t, sh, pcm.ch)) return hipErrorInvalidValue;
   const unsigned n_planes = matrix_bound ? static_cast<unsigned>(MatrixBound::kGroups) : sh.n_planes;
   hipError_t e;
+  if (edge && (e = hipEventRecord(edge->ev_fork, s)) != hipSuccess) return e;
   if (matrix_bound) switch (pcm.ch) {
     case 1: e = k1::launch_mx_st<1>(t, pcm, frame_begin, M, coef, hf, stride, s); break;
     case 2: e = k1::launch_mx_st<2>(t, pcm, frame_begin, M, coef, hf, stride, s); break;
@@ -2485,26 +2525,54 @@ hipError_t launch_encode_screened(const DeviceTables &t, const ScreenShape &sh, 
     default: e = k1::launch_mix_st<0>(t, pcm, frame_begin, M, coef, sh.ne, sh.hp, hf, stride, s); break;
   }
   if (e != hipSuccess) return e;
-  const ScreenArgs sa{hf, row_flag, wave_fail, host_stat, stride, sh.c0, sh.l0, n_planes, seq};
+  const ScreenArgs sa{hf, row_flag, wave_fail, host_stat, stride, sh.c0, sh.l0, n_planes, seq, edge_a, edge_b,
+                      edge ? edge->failed_total : nullptr};
   const unsigned long long hdr = record_header_bytes(pcm.ch), rec = record_bytes(pcm.ch);
   const dim3 grid((M + 4 * kQRows - 1) / (4 * kQRows));
   const long long fb = static_cast<long long>(frame_begin);
+  // from the side stream's first command on, every way out joins it: the caller's stream never goes on beside it
+  bool forked = false;
+  auto leave = [&](hipError_t err) -> hipError_t {
+    if (!forked) return err;
+    hipError_t j = hipEventRecord(edge->ev_edge, edge->side);
+    if (j == hipSuccess) j = hipStreamWaitEvent(s, edge->ev_edge, 0);
+    return err != hipSuccess ? err : j;
+  };
+  if (edge) {
+    // The side stream needs only what was on the stream before K1 (the PCM): the edge transform forms all 1024
+    // columns of its rows in a buffer of their own, so neither it nor the edge quantiser waits for a kernel of this
+    // launch, and no event stands between K1 and K2.  It is queued behind K1 so that K1's single round of workgroups
+    // is on the chip first; its waves take the CUs K1 leaves.
+    if ((e = hipStreamWaitEvent(edge->side, edge->ev_fork, 0)) != hipSuccess) return e;
+    forked = true;
+    e = edge->capped ? k1::launch_edge_rows<GLC_SMALL_ROWS_R, true>(t, pcm, frame_begin, M, edge->coef, er, 0u, edge->side)
+                     : k1::launch_edge_rows<GLC_SMALL_ROWS_R, false>(t, pcm, frame_begin, M, edge->coef, er, 0u, edge->side);
+    if (e != hipSuccess) return leave(e);
+    const unsigned g_pre = (er.n_pre + 15u) / 16u, g_suf = std::max(er.suf0 / 16u, g_pre), g_end = (M + 15u) / 16u;
+    const dim3 egrid(g_pre + (er.suf0 < M && g_suf < g_end ? g_end - g_suf : 0u));
+    if (*decided)
+      hipLaunchKernelGGL((k_quantize_screen<true, 3>), egrid, dim3(256), 0, edge->side, t, edge->coef, M, pcm.ch, rec, hdr, pcm, fb, records, sa);
+    else
+      hipLaunchKernelGGL((k_quantize_screen<false, 3>), egrid, dim3(256), 0, edge->side, t, edge->coef, M, pcm.ch, rec, hdr, pcm, fb, records, sa);
+    if ((e = hipGetLastError()) != hipSuccess) return leave(e);
+  }
   if (*decided)
     hipLaunchKernelGGL((k_quantize_screen<true, 1>), grid, dim3(256), 0, s, t, coef, M, pcm.ch, rec, hdr, pcm, fb, records, sa);
   else
     hipLaunchKernelGGL((k_quantize_screen<false, 1>), grid, dim3(256), 0, s, t, coef, M, pcm.ch, rec, hdr, pcm, fb, records, sa);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if ((e = hipGetLastError()) != hipSuccess) return leave(e);
   // the repair: exact columns C0.. of the failed rows - one wave per (two failed rows, 64 columns) found through the
   // fail counts where few rows fail, the row tiles that hold a failed row where many do - then those rows' records
   // from all 1024 exact coefficients.  Every launch leaves at once where nothing failed.
   e = latency_repair ? k1::launch_small_rows<GLC_SMALL_ROWS_R>(t, pcm, frame_begin, M, coef, row_flag, wave_fail, sh.c0, s)
                      : k1::launch_small_cols<2>(t, pcm, frame_begin, M, coef, row_flag, sh.c0, s);
-  if (e != hipSuccess) return e;
+  if (e != hipSuccess) return leave(e);
   if (*decided)
     hipLaunchKernelGGL((k_quantize_screen<true, 2>), grid, dim3(256), 0, s, t, coef, M, pcm.ch, rec, hdr, pcm, fb, records, sa);
   else
     hipLaunchKernelGGL((k_quantize_screen<false, 2>), grid, dim3(256), 0, s, t, coef, M, pcm.ch, rec, hdr, pcm, fb, records, sa);
-  return hipGetLastError();
+  // the join: the stream goes on (K3, the caller's own work) only behind the edge rows' records
+  return leave(hipGetLastError());
 }
 
 hipError_t launch_quantize(const DeviceTables &t, const float *coef, uint32_t M, uint32_t ch, const PcmView &pcm,

@@ -1950,7 +1950,7 @@ __device__ __forceinline__ void small_body(const DeviceTables &tb, const PcmView
   const int tx = tid % 16, ty = tid / 16;
   if constexpr (REPAIR) {
     const unsigned fr = static_cast<unsigned>(m0) + (tid & 31);
-    const bool flagged = fr < M && row_flag[fr] != 0u;
+    const bool flagged = fr < M && row_flag[fr] == 1u;  // (2: an edge row, the side stream's)
     if (__ballot(flagged) == 0ull) return;
   }
 
@@ -2190,10 +2190,18 @@ __device__ __forceinline__ void rows_mac4(f32x2 &acc, f32x4 xa, f32x4 xb, f32x4 
       : "v"(x0), "v"(x1), "v"(x2), "v"(x3), "v"(t01), "v"(t23));
 }
 
-template <int R>
-__global__ __launch_bounds__(64) void k_mdct_fwd_small_rows(DeviceTables tb, PcmView pcm, long long frame_begin, unsigned M,
-                                                             float *__restrict__ coef, const unsigned *__restrict__ row_flag,
-                                                             const unsigned *__restrict__ wave_fail, unsigned col0) {
+// FROM_ARGS: the list is not found but given - `er`, the launch's edge rows [0, n_pre) and [suf0, M) (glc_kernels.h
+// edge_rows), entry j being row j or suf0 + (j - n_pre).  No scan, no walk, no flag load: row_flag and wave_fail are
+// not read, and the grid is exactly the items.  `coef` is then not the launch's workspace but a buffer of the list's
+// own, [er.n][1024]: entry j's coefficients go to its row j (with col0 = 0 all 1024 of them, so that nothing of the
+// launch's transform is needed to quantise the row).
+// NB: blocks of 16 i-steps in the ring of table registers (NB - 1 of them, 4 loads each, in flight): 8 is the latency
+// form (28 loads, 128 registers of table values); 4 is the capped form of the edge transform (12 loads, 64 registers),
+// which has to fit on a SIMD beside two resident waves of the screened quantiser.
+template <int R, bool FROM_ARGS, int NB = 8>
+__device__ __forceinline__ void small_rows_body(const DeviceTables &tb, const PcmView &pcm, long long frame_begin, unsigned M,
+                                                float *__restrict__ coef, const unsigned *__restrict__ row_flag,
+                                                const unsigned *__restrict__ wave_fail, unsigned col0, const EdgeRows er) {
   static_assert(R == 2 || R == 4, "rows of a group: whole packed pairs");
   constexpr int NP = R / 2;
   constexpr unsigned kNone = 0xFFFFFFFFu;
@@ -2213,25 +2221,27 @@ __global__ __launch_bounds__(64) void k_mdct_fwd_small_rows(DeviceTables tb, Pcm
     const uint4 c = wf4[in ? (w0 + w) >> 2 : 0u];
     return in ? c : uint4{0u, 0u, 0u, 0u};
   };
-  unsigned cnt = 0;
-  for (unsigned w = 0; w < per; w += 32) {
-    uint4 c[8];
+  unsigned cnt = 0, base = 0, n_fail = er.n;
+  if constexpr (!FROM_ARGS) {
+    for (unsigned w = 0; w < per; w += 32) {
+      uint4 c[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) c[k] = counts(w + 4 * k);
+      for (int k = 0; k < 8; ++k) c[k] = counts(w + 4 * k);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) cnt += c[k].x + c[k].y + c[k].z + c[k].w;
+      for (int k = 0; k < 8; ++k) cnt += c[k].x + c[k].y + c[k].z + c[k].w;
+    }
+    unsigned incl = cnt;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const unsigned v = __shfl_up(incl, off);
+      if (lane >= static_cast<unsigned>(off)) incl += v;
+    }
+    if (lane == 63) s_total = incl;
+    __syncthreads();
+    n_fail = __builtin_amdgcn_readfirstlane(s_total);
+    base = incl - cnt;
   }
-  unsigned incl = cnt;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned v = __shfl_up(incl, off);
-    if (lane >= static_cast<unsigned>(off)) incl += v;
-  }
-  if (lane == 63) s_total = incl;
-  __syncthreads();
-  const unsigned n_fail = __builtin_amdgcn_readfirstlane(s_total);
   if (n_fail == 0) return;  // nothing failed: the whole launch leaves here
-  const unsigned base = incl - cnt;
 
   const unsigned n_slabs = (static_cast<unsigned>(kHopI) - col0) / kRowsSlab;
   const unsigned n_items = (n_fail + R - 1) / R * n_slabs;
@@ -2245,6 +2255,15 @@ __global__ __launch_bounds__(64) void k_mdct_fwd_small_rows(DeviceTables tb, Pcm
     const unsigned g = item / n_slabs, slab = item - g * n_slabs;
     // entries g R .. g R + R - 1 of the list: the lane whose run of counts holds entry j walks it to the wave, then
     // that wave's four flags to the row
+    unsigned m[R];
+    if constexpr (FROM_ARGS) {
+#pragma unroll
+      for (int q = 0; q < R; ++q) {
+        const unsigned j = g * R + q;
+        m[q] = j >= er.n ? kNone : j < er.n_pre ? j : er.suf0 + (j - er.n_pre);
+      }
+      __syncthreads();  // the item before this one has read its rows out of xs
+    } else {
     if (lane < R) s_row[lane] = kNone;
     __syncthreads();
     if (cnt != 0 && g * R + R > base && g * R < base + cnt) {
@@ -2280,16 +2299,16 @@ __global__ __launch_bounds__(64) void k_mdct_fwd_small_rows(DeviceTables tb, Pcm
           unsigned seen = 0;
 #pragma unroll
           for (unsigned e = 0; e < 4; ++e)
-            if (word[q] * 4u + e < M && fl[e] != 0u) {
+            if (word[q] * 4u + e < M && fl[e] == 1u) {  // (2: an edge row, the side stream's)
               if (seen == rank[q]) s_row[q] = word[q] * 4u + e;
               ++seen;
             }
         }
     }
     __syncthreads();
-    unsigned m[R];
 #pragma unroll
     for (int q = 0; q < R; ++q) m[q] = __builtin_amdgcn_readfirstlane(s_row[q]);
+    }
 
     // fl(x w) of the group's rows -> LDS.  Each row is read through a buffer descriptor of its own whose range check
     // is the encoder's zero padding, as in small_body (an element before the base wraps to a huge offset, one past the
@@ -2332,24 +2351,25 @@ __global__ __launch_bounds__(64) void k_mdct_fwd_small_rows(DeviceTables tb, Pcm
     f32x2 acc[NP];
 #pragma unroll
     for (int p = 0; p < NP; ++p) acc[p] = f32x2{0.0f, 0.0f};  // `let mut s = 0.0f32`, :365
-    f32x4 T[8][4];
+    static_assert(NB == 4 || NB == 8, "an even ring that divides the 128 blocks of a row");
+    f32x4 T[NB][4];
     RowsX<NP> X[2];
 #pragma unroll
-    for (int b = 0; b < 7; ++b) rows_issue_t(T[b], tp, b * 64);
+    for (int b = 0; b < NB - 1; ++b) rows_issue_t(T[b], tp, b * 64);
     rows_issue_x<NP>(X[0], xa, 0);
     rows_wait_x<NP>(X[0]);
-    constexpr int kRounds = kFrameI / 128;
+    constexpr int kRounds = kFrameI / (16 * NB);
 #pragma unroll 1
     for (int round = 0; round < kRounds; ++round) {
       // (the last round's look-ahead wraps to i = 0: in bounds, never used)
-      const float *tp_next = round + 1 < kRounds ? tp + 128 : row_t;
-      const unsigned xa_next = round + 1 < kRounds ? xa + 128 * 8 : xs0;
+      const float *tp_next = round + 1 < kRounds ? tp + 16 * NB : row_t;
+      const unsigned xa_next = round + 1 < kRounds ? xa + 16 * NB * 8 : xs0;
 #pragma unroll
-      for (int b = 0; b < 8; ++b) {
-        rows_wait_t<24>(T[b]);
-        if (b == 0) rows_issue_t(T[7], tp, 7 * 64);
+      for (int b = 0; b < NB; ++b) {
+        rows_wait_t<4 * (NB - 2)>(T[b]);
+        if (b == 0) rows_issue_t(T[NB - 1], tp, (NB - 1) * 64);
         else rows_issue_t(T[b - 1], tp_next, (b - 1) * 64);
-        if (b < 7) rows_issue_x<NP>(X[(b + 1) & 1], xa, (b + 1) * 128);
+        if (b < NB - 1) rows_issue_x<NP>(X[(b + 1) & 1], xa, (b + 1) * 128);
         else rows_issue_x<NP>(X[0], xa_next, 0);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -2365,8 +2385,38 @@ __global__ __launch_bounds__(64) void k_mdct_fwd_small_rows(DeviceTables tb, Pcm
     // epilogue: out[k] = s * norm, :372
 #pragma unroll
     for (int q = 0; q < R; ++q)
-      if (m[q] != kNone) coef[static_cast<size_t>(m[q]) * kHopI + col] = mul_rn(q & 1 ? acc[q >> 1].y : acc[q >> 1].x, tb.norm);
+      if (m[q] != kNone)
+        coef[static_cast<size_t>(FROM_ARGS ? g * R + q : m[q]) * kHopI + col] = mul_rn(q & 1 ? acc[q >> 1].y : acc[q >> 1].x, tb.norm);
+    // (the argument form's grid is exactly its items: one pass, so that nothing of the staging - 32 offsets, 32 window
+    // values - is kept in registers through the chain for a next item)
+    if constexpr (FROM_ARGS) break;
   }
+}
+
+template <int R>
+__global__ __launch_bounds__(64) void k_mdct_fwd_small_rows(DeviceTables tb, PcmView pcm, long long frame_begin, unsigned M,
+                                                             float *__restrict__ coef, const unsigned *__restrict__ row_flag,
+                                                             const unsigned *__restrict__ wave_fail, unsigned col0) {
+  small_rows_body<R, false>(tb, pcm, frame_begin, M, coef, row_flag, wave_fail, col0, EdgeRows{0u, M, 0u});
+}
+
+// The edge transform: columns [col0, 1024) of the launch's edge rows into their own buffer `coef` ([er.n][1024]), on
+// the side stream: it reads the PCM and the tables and nothing a kernel of the launch writes.
+template <int R>
+__global__ __launch_bounds__(64) void k_mdct_edge_rows(DeviceTables tb, PcmView pcm, long long frame_begin, unsigned M,
+                                                        float *__restrict__ coef, unsigned col0, EdgeRows er) {
+  small_rows_body<R, true, 8>(tb, pcm, frame_begin, M, coef, nullptr, nullptr, col0, er);
+}
+
+// ... and its capped form: the short table ring, and no more than kEdgeCapVgprs registers - what a SIMD has left beside
+// two resident waves of k_quantize_screen<*, 1> (2 x 160 of 512), whose 512 workgroups are one round of the chip at two
+// per CU; its 16 KiB of LDS fit beside their 2 x 68 KiB.  The cap that would fit beside a resident K1 workgroup (32
+// registers) is out of reach of this chain: the table ring alone is 64.
+constexpr int kEdgeCapVgprs = 192;
+template <int R>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(kEdgeCapVgprs))) void k_mdct_edge_rows_capped(
+    DeviceTables tb, PcmView pcm, long long frame_begin, unsigned M, float *__restrict__ coef, unsigned col0, EdgeRows er) {
+  small_rows_body<R, true, 4>(tb, pcm, frame_begin, M, coef, nullptr, nullptr, col0, er);
 }
 
 // columns [col0, 1024) (col0 a multiple of 64) of the rows flagged in row_flag[M], found through wave_fail (the fail
@@ -2379,6 +2429,23 @@ inline hipError_t launch_small_rows(const DeviceTables &t, const PcmView &pcm, u
   if (col0 % 64u || !row_flag || !wave_fail) return hipErrorInvalidValue;
   hipLaunchKernelGGL((k_mdct_fwd_small_rows<R>), dim3(kRowsGrid), dim3(64), 0, s, t, pcm, static_cast<long long>(frame_begin), M,
                      coef, row_flag, wave_fail, col0);
+  return hipGetLastError();
+}
+
+// columns [col0, 1024) of the edge rows `er` of a launch of M rows -> coef[er.n][1024]: one workgroup per item, nothing
+// else in the grid
+template <int R, bool CAPPED>
+inline hipError_t launch_edge_rows(const DeviceTables &t, const PcmView &pcm, uint64_t frame_begin, uint32_t M, float *coef,
+                                   const EdgeRows &er, uint32_t col0, hipStream_t s) {
+  if (M == 0 || er.n == 0 || col0 >= static_cast<uint32_t>(kHopI)) return hipSuccess;
+  if (col0 % 64u || er.n_pre > er.suf0 || er.suf0 > M || er.n != er.n_pre + (M - er.suf0)) return hipErrorInvalidValue;
+  const unsigned n_items = (er.n + R - 1) / R * ((static_cast<unsigned>(kHopI) - col0) / kRowsSlab);
+  if (CAPPED)
+    hipLaunchKernelGGL((k_mdct_edge_rows_capped<R>), dim3(n_items), dim3(64), 0, s, t, pcm, static_cast<long long>(frame_begin), M,
+                       coef, col0, er);
+  else
+    hipLaunchKernelGGL((k_mdct_edge_rows<R>), dim3(n_items), dim3(64), 0, s, t, pcm, static_cast<long long>(frame_begin), M, coef,
+                       col0, er);
   return hipGetLastError();
 }
 

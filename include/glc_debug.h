@@ -79,6 +79,26 @@ int glc_debug_set_encode_repair(glc_ctx *ctx, int kind);
  * nothing is waited for. */
 int glc_debug_encode_repair_stats(glc_ctx *ctx, uint64_t *launches_tiles, uint64_t *launches_latency);
 
+/* Whether a screened launch of glc_encode_range_device hands its edge frames - the frames whose 2048-sample window
+ * reaches into the stream's zero padding: frame 0 and, unless the stream ends exactly where its window does, the last
+ * frame - to a side stream of the
+ * context (csrc/glc_kernels.h EdgeLaunch): all their exact coefficients, in a buffer of their own, and their records
+ * are then produced beside K1 and K2 instead of by the serial repair behind them, and the caller's stream continues
+ * behind both.
+ *   0  automatic: every screened launch that holds 1..32 edge rows takes it, with the transform of kind 3
+ *   1  off: bit for bit the launches of a library without the path
+ *   2  on, with k_mdct_edge_rows: the latency repair's chain as it is, 28 table loads in flight (211 VGPRs: its waves
+ *      do not fit beside two resident workgroups of K2 on a CU, and K2 then needs a second round)
+ *   3  on, with k_mdct_edge_rows_capped: the same chain with 12 table loads in flight, at most 192 VGPRs and 16 KiB of
+ *      LDS, which fits beside them.  (Neither fits beside a resident K1 workgroup, which leaves 32 VGPRs per SIMD.)
+ * The setting survives glc_debug_set_encode_screen.  All kinds produce the same record bytes, and
+ * glc_debug_encode_screen_stats' rows_repaired counts the edge rows that failed the screen whichever path took them
+ * (tests/test_encode_edge.py). */
+int glc_debug_set_encode_edge(glc_ctx *ctx, int kind);
+/* Screened launches of `ctx` so far that took the edge path, and the edge rows they handed to the side stream.  Host
+ * counters: nothing is waited for. */
+int glc_debug_encode_edge_stats(glc_ctx *ctx, uint64_t *launches, uint64_t *rows);
+
 /* Which form of the mixed-role transform a screened launch takes (csrc/glc_kernels.h MatrixBound):
  *   0  automatic: the matrix form (k_mdct_mx_st: the bound sums on the bf16 matrix pipe) where it is built - 44.1 and
  *      48 kHz, 1 / 2 / 4 / 8 channels - for launches of 3584 rows and up, the FMA form (k_mdct_mix_st) everywhere else
