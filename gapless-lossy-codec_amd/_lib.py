@@ -301,6 +301,7 @@ DEBUG_SIGNATURES = {
     "glc_debug_encode_matrix_bound": (C.c_int, [C.POINTER(C.c_uint32)] * 6 + [C.POINTER(C.c_double)] * 3),
     "glc_debug_set_encode_edge": (C.c_int, [_vp, C.c_int]),
     "glc_debug_encode_edge_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "glc_debug_live_resources": (C.c_int, [C.POINTER(C.c_uint64)]),
 }
 
 if not os.path.exists(LIB_PATH):

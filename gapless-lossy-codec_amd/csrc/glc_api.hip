@@ -23,6 +23,7 @@
 #include "../../include/glc_debug.h"
 #include "glc_common.h"
 #include "glc_kernels.h"
+#include "glc_resources.hpp"
 
 namespace glc {
 
@@ -35,47 +36,6 @@ void set_global_error(const std::string &msg) {
 }
 
 }  // namespace glc
-
-// Device buffer that grows on demand (never shrinks while the context lives).
-struct DevBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-  hipError_t reserve(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e == hipSuccess) cap = bytes;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
-// Pinned host staging buffer (grows on demand): device <-> host copies through it run at PCIe
-// speed and truly asynchronously, which pageable memory does not give.
-struct HostBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-  hipError_t reserve(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
-    if (e == hipSuccess) cap = bytes;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
 
 // A parked host thread that runs one job at a time (glc_encode's uploader and launcher): started on
 // first use and kept for the life of the context, because a fresh std::thread costs ~50 us before its
@@ -123,24 +83,21 @@ struct Worker {
   }
 };
 
+// Everything a context owns releases itself (glc_resources.hpp), and `delete ctx` is all glc_ctx_destroy does about
+// it.  Members are destroyed in reverse order of declaration, so THE ORDER BELOW IS THE ORDER OF RELEASE, backwards:
+// the helper threads stand last and are joined first, the events before them are destroyed next, then the streams,
+// and the buffers are freed last - the encode slots stand among them, so a slot's two edge events go with its buffers,
+// behind the side stream as they always did.  A new member goes into the group of its kind; state that owns nothing
+// may stand anywhere in front of the streams.
 struct glc_ctx {
   int device = 0;
   uint32_t sample_rate = 0;
-  hipStream_t stream = nullptr;      // stream in use
-  hipStream_t own_stream = nullptr;  // the context's private stream
-  hipEvent_t ev_begin = nullptr, ev_end = nullptr;  // glc_ctx_timer_*
-  hipStream_t copy_stream = nullptr;  // glc_encode: uploads run ahead of the kernels on this one
-  hipEvent_t ev_copy = nullptr;
-  hipStream_t stream_b = nullptr;     // odd rounds / chunks of an encode are transformed here, beside the even ones on `stream`
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;  // glc_encode_range_device: second stream after the caller's work, caller's stream after both
-  DevBuf coef_b;                      // ... with a coefficient workspace of their own
-  hipStream_t down_stream = nullptr;  // glc_encode: round i is compacted and its blob comes down while round i+1 is transformed
-  std::vector<hipEvent_t> ev_round;   // one per round: records written
-  std::unique_ptr<Worker> enc_up, enc_launch;  // glc_encode's helper threads (multi-round streams only)
   glc::HostTables host;
   glc::DeviceTables dev{};
   DevBuf tables;     // all constant tables in one allocation
-  DevBuf coef;       // MDCT coefficient workspace [rows][1024]
+  // The two encode launch chains: slot 0 goes with the caller's stream, slot 1 with `stream_b` (odd rounds / chunks).
+  EncodeSlot slot[2];
+  DevBuf &coef = slot[0].coef;  // slot 0's coefficient workspace, as the round trip, store, stream and batch drivers name it
   DevBuf pcm;        // staging for host-boundary encode / decode output
   DevBuf pcm_int;    // glc_encode_int / glc_encode_batch_int: the integer samples as uploaded, widened into `pcm` on the device
   DevBuf records;    // staging for host-boundary encode
@@ -167,8 +124,7 @@ struct glc_ctx {
   DevBuf rtb_vs;       // the virtual stream of a round / a clip longer than a round, staged whole
   DevBuf rtb_tab;      // the call's tables: per round the clip table, the frame map and the hop descriptors
   DevBuf rtb_stats;    // per-clip counters of the last batch call
-  HostBuf rtb_stage;   // pinned image of rtb_tab on its way up ...
-  hipEvent_t rtb_ev = nullptr;  // ... recorded behind that copy: the next call waits for it before it rewrites the image
+  HostBuf rtb_stage;   // pinned image of rtb_tab on its way up; rtb_ev is recorded behind that copy
   bool rtb_ev_pending = false;
   struct RtbClipInfo {
     uint64_t n_frames, stat_off;  // stat_off: the clip's first counter pair in rtb_stats, in uint64_t
@@ -193,45 +149,39 @@ struct glc_ctx {
   uint32_t dec_delay = 0;
   uint64_t dec_orig_len = 0, dec_n_pairs = 0, dec_n_raw = 0;
   int d1_variant = 0;    // include/glc_debug.h: which inverse-transform kernel / path to launch
-  int k1_variant = 0;    // include/glc_debug.h: which forward-transform kernel takes launches of >= 4096 rows
-  // The screened encode (glc_kernels.h launch_encode_screened).  Slot 0 goes with `coef`, slot 1 with `coef_b`:
-  // a workspace of hf planes and flags, and 8 host-mapped words the repair launch leaves its count in.
-  int screen_mode = 0;          // include/glc_debug.h glc_debug_set_encode_screen
-  bool screen_usable = false;   // the rate's last band starts where a screen pays (encode_screen_shape)
-  glc::ScreenShape screen_shape{};
-  DevBuf screen_ws[2];
-  HostBuf screen_stat;          // [2][8] uint32_t
-  uint32_t screen_seq[2] = {0, 0}, screen_judged[2] = {0, 0};  // launches queued / whose count the guard has read
-  uint32_t screen_backoff = 0;  // launches the guard still sends down today's path
-  bool screen_held = false;     // the last count read was a bad one: one probe at a time
-  bool screen_judged_any = false;  // a count has been read since the context was created (or the mode set)
-  uint32_t screen_last_failed = 0;  // ... and the failed rows of the last one read: picks the repair's transform
-  int repair_kind = 0;             // include/glc_debug.h glc_debug_set_encode_repair
-  int bound_kind = 0;              // include/glc_debug.h glc_debug_set_encode_bound
-  uint32_t tap_rows = 0, tap_planes = 0;  // the last screened launch on slot 0: its rows and hf planes (glc_debug_encode_bound_tap)
-  DevBuf bound_tables;             // the matrix form's table image (glc_kernels.h MatrixBound), where the form is built
-  uint64_t repair_launches[2] = {0, 0};  // screened launches that took k_mdct_fwd_small_cols / k_mdct_fwd_small_rows
-  uint64_t rows_screened = 0;
-  // The edge path of a screened launch (glc_kernels.h EdgeLaunch): a side stream of the context's own - not stream_b,
-  // which the chunk alternation uses - and per slot the three events of a launch's fork and join.
-  int edge_kind = 0;               // include/glc_debug.h glc_debug_set_encode_edge
-  hipStream_t edge_stream = nullptr;
-  hipEvent_t ev_edge[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // {fork, edge rows done}
-  DevBuf edge_coef[2];             // the edge rows' coefficients, [kEdgeRowsMax][1024]
+  // The screened encode (glc_kernels.h launch_encode_screened): its policy, and what the two slots share - the words
+  // their launches report through, allocated and cleared once (ensure_screen_shared).
+  ScreenPolicy policy;
+  HostBuf screen_stat;             // [2][8] uint32_t, host-mapped: slot i's repair launch leaves its count in words 8 i ..
   DevBuf edge_failed;              // [2] uint64_t, zeroed once: per slot the edge rows that failed the screen so far
-  uint64_t edge_launches = 0, edge_rows = 0;  // screened launches that took the edge path, and their edge rows
-  hipStream_t probe_stream = nullptr;  // include/glc_debug.h clock probe
-  HostBuf probe_out;
+  DevBuf bound_tables;             // the matrix form's table image (glc_kernels.h MatrixBound), where the form is built
+  HostBuf probe_out;               // include/glc_debug.h clock probe
   uint32_t dec_ch = 0;
   uint64_t dec_frames = 0, dec_next = 0;
   bool stream_open = false;  // glc_decode_stream_begin called, last chunk not yet delivered
   int stream_elem = 0;       // bytes per sample of the chunks handed out so far (4: float, 2: int16_t; 0: none yet)
   // streaming session: chunk i is copied to the host while chunk i+1 is already being decoded
-  DevBuf stream_out;                           // two chunk-sized output buffers
-  hipEvent_t ev_dec[2] = {nullptr, nullptr};   // "kernels of the chunk in buffer b are done"
+  DevBuf stream_out;                           // two chunk-sized output buffers; ev_dec[b]: "kernels of the chunk in buffer b are done"
   int stream_buf = 0;                          // buffer holding the chunk the next call delivers
   uint64_t stream_frames = 0;                  // its frame count
   bool stream_last = false;                    // ... and whether it is the last one (carries the tail)
+  // ---- streams: each but own_stream is opened where a call first needs it ----
+  Stream own_stream;   // the context's private stream
+  Stream stream;       // stream in use: own_stream's handle, or the caller's (glc_ctx_set_stream) - borrowed either way
+  Stream copy_stream;  // glc_encode: uploads run ahead of the kernels on this one
+  Stream stream_b;     // odd rounds / chunks of an encode are transformed here, beside the even ones on `stream`
+  Stream down_stream;  // glc_encode: round i is compacted and its blob comes down while round i+1 is transformed
+  Stream edge_stream;  // the edge path of a screened launch (glc_kernels.h EdgeLaunch): a side stream of the context's own - not
+                       // stream_b, which the chunk alternation uses; the slot holds the events of a launch's fork and join
+  Stream probe_stream; // include/glc_debug.h clock probe
+  // ---- events ----
+  Event ev_begin, ev_end;        // glc_ctx_timer_* (the two that keep time)
+  Event ev_fork, ev_join;        // glc_encode_range_device: second stream after the caller's work, caller's stream after both
+  std::vector<Event> ev_round;   // glc_encode, one per round: records written
+  Event ev_dec[2];               // decode: "kernels of the chunk in buffer b are done"
+  Event rtb_ev;                  // recorded behind the upload of rtb_stage: the next call waits for it before it rewrites the image
+  // ---- threads ----
+  std::unique_ptr<Worker> enc_up, enc_launch;  // glc_encode's helper threads (multi-round streams only)
 };
 
 namespace {
@@ -321,15 +271,18 @@ int glc_ctx_create(int device, uint32_t sample_rate, glc_ctx **out) {
                 std::string("glc_ctx_create: device is ") + prop.gcnArchName +
                     ", kernels are built for gfx950 only");
 
+  DeviceGuard guard(device);  // in front of `ctx`: a context that fails below is released with its device current
   std::unique_ptr<glc_ctx> ctx(new (std::nothrow) glc_ctx);
   if (!ctx) return GLC_ENOMEM;
   ctx->device = device;
   ctx->sample_rate = sample_rate;
   glc::build_host_tables(sample_rate, ctx->host);
 
-  DeviceGuard guard(device);
-  GLC_HIP(nullptr, hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
-  ctx->stream = ctx->own_stream;
+  ctx->slot[1].index = 1;
+  ctx->policy.dev = &ctx->dev;
+
+  GLC_HIP(nullptr, ctx->own_stream.ensure());
+  ctx->stream.borrow(ctx->own_stream);
 
   // one allocation, 256-B aligned sub-buffers
   const glc::HostTables &h = ctx->host;
@@ -349,10 +302,7 @@ int glc_ctx_create(int device, uint32_t sample_rate, glc_ctx **out) {
   const size_t o_bof = place(h.band_of.size() * 2);
   const size_t o_edges = place(65 * 4);
   e = ctx->tables.reserve(off);
-  if (e != hipSuccess) {
-    (void)hipStreamDestroy(ctx->own_stream);
-    return hip_fail(nullptr, e, "hipMalloc(tables)");
-  }
+  if (e != hipSuccess) return hip_fail(nullptr, e, "hipMalloc(tables)");
   uint8_t *base = static_cast<uint8_t *>(ctx->tables.p);
   auto up = [&](size_t o, const void *src, size_t bytes) {
     return hipMemcpy(base + o, src, bytes, hipMemcpyHostToDevice);
@@ -371,11 +321,7 @@ int glc_ctx_create(int device, uint32_t sample_rate, glc_ctx **out) {
                       up(o_bof, h.band_of.data(), h.band_of.size() * 2),
                       up(o_edges, edges.data(), 65 * 4)};
   for (hipError_t x : es)
-    if (x != hipSuccess) {
-      ctx->tables.release();
-      (void)hipStreamDestroy(ctx->own_stream);
-      return hip_fail(nullptr, x, "hipMemcpy(tables)");
-    }
+    if (x != hipSuccess) return hip_fail(nullptr, x, "hipMemcpy(tables)");
   glc::DeviceTables &d = ctx->dev;
   d.cos_t = reinterpret_cast<const float *>(base + o_cos_t);
   d.cos = reinterpret_cast<const float *>(base + o_cos);
@@ -389,20 +335,16 @@ int glc_ctx_create(int device, uint32_t sample_rate, glc_ctx **out) {
   d.norm = h.norm;
   d.cf = h.cf;
   d.noise_floor = h.noise_floor;
-  ctx->screen_usable = glc::encode_screen_shape(h.edges.data(), static_cast<uint32_t>(nb), &ctx->screen_shape);
+  ScreenPolicy &pol = ctx->policy;
+  pol.usable = glc::encode_screen_shape(h.edges.data(), static_cast<uint32_t>(nb), &pol.shape);
   d.cos_bf = nullptr;
-  if (ctx->screen_usable && ctx->screen_shape.ne == static_cast<uint32_t>(glc::MatrixBound::kNe)) {
+  if (pol.usable && pol.shape.ne == static_cast<uint32_t>(glc::MatrixBound::kNe)) {
     // the bf16 pieces of the bound columns depend on the rate's C0 alone: built and uploaded once per context
     std::vector<uint16_t> img;
-    glc::build_bound_table_image(h, ctx->screen_shape.c0, img);
+    glc::build_bound_table_image(h, pol.shape.c0, img);
     e = ctx->bound_tables.reserve(img.size() * 2);
     if (e == hipSuccess) e = hipMemcpy(ctx->bound_tables.p, img.data(), img.size() * 2, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      ctx->bound_tables.release();
-      ctx->tables.release();
-      (void)hipStreamDestroy(ctx->own_stream);
-      return hip_fail(nullptr, e, "hipMemcpy(bound tables)");
-    }
+    if (e != hipSuccess) return hip_fail(nullptr, e, "hipMemcpy(bound tables)");
     d.cos_bf = static_cast<const uint16_t *>(ctx->bound_tables.p);
   }
   *out = ctx.release();
@@ -412,72 +354,18 @@ int glc_ctx_create(int device, uint32_t sample_rate, glc_ctx **out) {
 void glc_ctx_destroy(glc_ctx *ctx) {
   if (!ctx) return;
   DeviceGuard guard(ctx->device);
-  ctx->enc_up.reset();      // joins the helper threads (idle: glc_encode waits for them before it returns)
-  ctx->enc_launch.reset();
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
-  if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
-  if (ctx->ev_copy) (void)hipEventDestroy(ctx->ev_copy);
-  if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
-  if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
-  for (hipEvent_t e : ctx->ev_dec)
-    if (e) (void)hipEventDestroy(e);
-  ctx->stream_out.release();
-  for (hipEvent_t e : ctx->ev_round)
-    if (e) (void)hipEventDestroy(e);
-  if (ctx->stream_b) (void)hipStreamDestroy(ctx->stream_b);
-  if (ctx->edge_stream) (void)hipStreamDestroy(ctx->edge_stream);
-  for (auto &slot : ctx->ev_edge)
-    for (hipEvent_t ev : slot)
-      if (ev) (void)hipEventDestroy(ev);
-  if (ctx->probe_stream) (void)hipStreamDestroy(ctx->probe_stream);
-  ctx->probe_out.release();
-  ctx->coef_b.release();
-  ctx->screen_ws[0].release();
-  ctx->screen_ws[1].release();
-  ctx->screen_stat.release();
-  for (DevBuf &b : ctx->edge_coef) b.release();
-  ctx->edge_failed.release();
-  if (ctx->down_stream) (void)hipStreamDestroy(ctx->down_stream);
-  if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
-  if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-  ctx->tables.release();
-  ctx->bound_tables.release();
-  ctx->coef.release();
-  ctx->pcm.release();
-  ctx->pcm_int.release();
-  ctx->records.release();
-  ctx->blocks.release();
-  ctx->dec_meta.release();
-  ctx->dec_plan.release();
-  ctx->pack_meta.release();
-  ctx->rt_records.release();
-  ctx->rt_rows.release();
-  ctx->rt_edge.release();
-  ctx->rt_stats.release();
-  ctx->rt_out.release();
-  ctx->rtb_vs.release();
-  ctx->rtb_tab.release();
-  ctx->rtb_stats.release();
-  ctx->cd_status.release();
-  ctx->sc_ws.release();
-  ctx->sc_stage.release();
-  ctx->rtb_stage.release();
-  if (ctx->rtb_ev) (void)hipEventDestroy(ctx->rtb_ev);
-  ctx->pack_blob.release();
-  ctx->host_stage.release();
-  ctx->batch_stage.release();
-  delete ctx;
+  delete ctx;  // the helper threads are idle (glc_encode waits for them before it returns); the members' order does the rest
 }
 
-void *glc_ctx_stream(glc_ctx *ctx) { return ctx ? ctx->stream : nullptr; }
+void *glc_ctx_stream(glc_ctx *ctx) { return ctx ? static_cast<hipStream_t>(ctx->stream) : nullptr; }
 int glc_ctx_device(const glc_ctx *ctx) { return ctx ? ctx->device : -1; }
 
 int glc_ctx_set_stream(glc_ctx *ctx, void *hip_stream) {
   if (!ctx) return GLC_EINVAL;
   DeviceGuard guard(ctx->device);
   GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->own_stream;
+  ctx->stream.borrow(hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->own_stream);
   return GLC_OK;
 }
 
@@ -491,8 +379,8 @@ int glc_ctx_synchronize(glc_ctx *ctx) {
 int glc_ctx_timer_begin(glc_ctx *ctx) {
   if (!ctx) return GLC_EINVAL;
   DeviceGuard guard(ctx->device);
-  if (!ctx->ev_begin) GLC_HIP(ctx, hipEventCreate(&ctx->ev_begin));
-  if (!ctx->ev_end) GLC_HIP(ctx, hipEventCreate(&ctx->ev_end));
+  GLC_HIP(ctx, ctx->ev_begin.ensure(hipEventDefault));
+  GLC_HIP(ctx, ctx->ev_end.ensure(hipEventDefault));
   GLC_HIP(ctx, hipEventRecord(ctx->ev_begin, ctx->stream));
   return GLC_OK;
 }
@@ -521,15 +409,31 @@ int glc_ctx_tables(const glc_ctx *ctx, float *cos_table, float *window, float *n
 
 // ------------------------------------------------------------------------------ encode
 
+// A frame-range encode: frames [frame_begin, frame_end) of the stream `view` shows (whole, or a shard with halo) ->
+// their records.
+struct EncodeRange {
+  glc::PcmView view;
+  uint64_t frame_begin, frame_end;
+  void *records;
+  float *coef_tap;   // optional: the range's coefficients go here, in one launch, instead of into the slot's workspace
+  EncodeSlot *slot;  // the launch chain the range is queued on (null where nothing is transformed)
+};
+// What a caller of encode_range_on allows the range:
+enum : unsigned {
+  kEncodeAlternate = 1u,  // a range of several chunks may alternate between the given stream and stream_b (slot 1)
+  kEncodeBeside = 2u,     // the launch runs beside others: launch_mdct_forward deals its rows accordingly
+  kEncodeEdge = 4u,       // the caller owns its stream's order: a screened chunk may hand its edge frames to the side stream
+};
+
 // Arguments of a frame-range encode (glc_encode_range_device, glc_debug_quantize_device): `fn` names the
 // entry point in the error message.  `whole_tap`: the range's rows go into one caller-supplied coefficient
 // buffer, so their count must fit one launch.
-static int check_encode_range(glc_ctx *ctx, const char *fn, const float *d_pcm, uint64_t t0, uint64_t t_count,
-                              uint64_t n_samples, uint16_t channels, uint64_t frame_begin, uint64_t frame_end,
-                              const void *d_records, bool whole_tap) {
+static int check_encode_range(glc_ctx *ctx, const char *fn, const EncodeRange &r, bool whole_tap) {
   const std::string f(fn);
-  if (!ctx || !d_pcm || !d_records) return fail(ctx, GLC_EINVAL, f + ": null argument");
-  const glc_plan plan = glc::plan_encode(n_samples, channels);
+  const uint64_t t0 = r.view.t0, t_count = r.view.t_count, frame_begin = r.frame_begin, frame_end = r.frame_end;
+  const uint16_t channels = static_cast<uint16_t>(r.view.ch);
+  if (!ctx || !r.view.p || !r.records) return fail(ctx, GLC_EINVAL, f + ": null argument");
+  const glc_plan plan = glc::plan_encode(r.view.n_samples, channels);
   if (plan.n_frames == 0)
     return fail(ctx, GLC_EINVAL, f + ": the reference encoder panics on this input");
   if (frame_begin > frame_end || frame_end > plan.n_frames)
@@ -557,92 +461,9 @@ static hipError_t launch_quantize_decide(glc_ctx *ctx, const float *coef, const 
   return e;
 }
 
-// Whether a launch of M rows may take the screened path at all (the mode and the launch's shape; the guard aside).
-static bool screen_may(const glc_ctx *ctx, uint32_t M, uint32_t ch) {
-  if (!ctx->screen_usable || ctx->screen_mode == 1) return false;
-  // (forced on: from one row tile of the form the launch takes - 256 rows, 128 where the matrix form is forced too)
-  if (ctx->screen_mode == 2)
-    return M >= (ctx->bound_kind == 2 && glc::encode_matrix_bound_built(ctx->dev, ctx->screen_shape, ch) ? 128u : 256u);
-  return glc::mdct_forward_is_st16(M, ch, ctx->k1_variant);
-}
-
-// Whether a launch of M rows takes the screened path.  Automatic mode: where launch_mdct_forward would pick the
-// 16-wave kernel, unless the guard holds it off.  The guard: content that fails the screen everywhere (noise)
-// pays the fast pass AND a slow repair, so when a count a repair launch left shows more than 1 row in
-// kScreenGuardDen failed, the path is held off: the next kScreenGuardBackoff launches take today's kernels, then
-// ONE launch probes again, and until its count has come back - the host may be many launches ahead of the
-// device - nothing else is screened.  A launch that passes opens the path again.  A context that has read no count
-// yet is treated the same way: its first screened launch is its probe, and the launches queued behind it before
-// its count is back take today's kernels (a burst of noise on a fresh context pays the repair once).  What the
-// guard cannot shorten: when content turns from passing to failing, the launches queued before the first bad
-// count is back are screened and repaired - as many as the caller queues without waiting.
-// The count is a heuristic's input and nothing more: the device leaves {failed, rows, seq} as three plain
-// stores in no order, and this reads them without synchronising - it may see a launch's seq beside the counts
-// of the one before, or judge a launch late.  Either only moves the decision by a launch; the records are the
-// same whichever path a launch takes.
-// The same count picks the repair's transform (glc_kernels.h launch_encode_screened), in the forced mode 2 as well:
-// screen_latency_repair below.
-constexpr uint32_t kScreenGuardDen = 8, kScreenGuardBackoff = 32;
-static bool screen_takes(glc_ctx *ctx, uint32_t M, uint32_t ch) {
-  if (!screen_may(ctx, M, ch)) return false;
-  bool pending = false;  // a screened launch whose count has not come back
-  for (int s = 0; s < 2; ++s) {
-    const volatile uint32_t *hs = static_cast<const volatile uint32_t *>(ctx->screen_stat.p) + 8 * s;
-    const uint32_t seq = hs[2], failed = hs[0], rows = hs[1];
-    if (seq != ctx->screen_judged[s]) {
-      ctx->screen_judged[s] = seq;
-      const bool bad = rows && static_cast<uint64_t>(failed) * kScreenGuardDen > rows;
-      if (bad) ctx->screen_backoff = kScreenGuardBackoff;
-      ctx->screen_held = bad;
-      ctx->screen_judged_any = true;
-      ctx->screen_last_failed = failed;
-    }
-    pending = pending || seq != ctx->screen_seq[s];
-  }
-  if (ctx->screen_mode == 2) return true;
-  if (ctx->screen_backoff) {
-    --ctx->screen_backoff;
-    return false;
-  }
-  return !((ctx->screen_held || !ctx->screen_judged_any) && pending);
-}
-
-// Which transform repairs a screened launch: the latency kernel when the last count the device left (read by
-// screen_takes just before) is small, today's when it is large - and when no count has been read yet, so that a
-// fresh context on noise pays what it paid.  A heuristic like the guard: the records are the same either way.
-// kScreenRepairLatencyRows is the measured crossover (profiles/encode_repair_bench.txt section 5, 8192-row launches):
-// with the failed frames spread over the launch the latency kernel wins at every count measured, 2 .. 1024 rows; with
-// them in one run - the tile kernel's best case, a tile of 32 rows is all failed rows - it still wins at 132 failed
-// rows (by 5.8 us) and loses at 516 (by 119 us).  128 is the largest count of the sweep at which it wins either way.
-constexpr uint32_t kScreenRepairLatencyRows = 128;
-// Which edge transform a launch that takes the edge path gets (include/glc_debug.h glc_debug_set_encode_edge): the
-// capped one unless the latency form is forced.  Measured (profiles/encode_edge_bench.txt): the latency form's waves
-// do not fit beside two resident workgroups of K2 and cost K2 its single round; the capped form's do.
-static bool edge_capped(const glc_ctx *ctx) { return ctx->edge_kind != 2; }
-
-static bool screen_latency_repair(const glc_ctx *ctx) {
-  if (ctx->repair_kind) return ctx->repair_kind == 2;
-  return ctx->screen_judged_any && ctx->screen_last_failed <= kScreenRepairLatencyRows;
-}
-
-// Which form of the transform a screened launch of M rows takes (glc_kernels.h MatrixBound): the matrix form where
-// it is built - the rate's ne, a channel count with a segment loader - and, in the automatic mode, where the launch
-// is one the automatic screen takes at all (mdct_forward_is_st16: 3584 rows and up); the forced kind 2 takes it
-// wherever it is built, kind 1 never.
-static bool screen_matrix_bound(const glc_ctx *ctx, uint32_t M, uint32_t ch) {
-  if (ctx->bound_kind == 1 || !glc::encode_matrix_bound_built(ctx->dev, ctx->screen_shape, ch)) return false;
-  return ctx->bound_kind == 2 || M >= 3584u;
-}
-
-// The screened path's workspace of a coefficient workspace (slot 0 with `coef`, 1 with `coef_b`), reserved where
-// that one is: for the largest launch of a range of `frames` frames in chunks of `chunk` that may take the path.
-static hipError_t screen_reserve(glc_ctx *ctx, int slot, uint32_t ch, uint64_t frames, uint64_t chunk) {
-  const uint32_t m_full = static_cast<uint32_t>(std::min(chunk, frames) * ch);
-  const uint32_t m_last = frames > chunk ? static_cast<uint32_t>(frames % chunk * ch) : 0u;
-  uint64_t need = 0;
-  if (screen_may(ctx, m_full, ch)) need = glc::encode_screen_bytes(m_full, ctx->screen_shape);
-  if (m_last && screen_may(ctx, m_last, ch)) need = std::max(need, glc::encode_screen_bytes(m_last, ctx->screen_shape));
-  if (!need) return hipSuccess;
+// What the two slots' screened launches share, allocated and cleared once per context, in front of the first
+// workspace a slot reserves: the host-mapped words and the edge path's running totals.
+static hipError_t ensure_screen_shared(glc_ctx *ctx) {
   if (!ctx->screen_stat.p) {
     const hipError_t e = ctx->screen_stat.reserve(2 * 8 * sizeof(uint32_t));
     if (e != hipSuccess) return e;
@@ -656,47 +477,70 @@ static hipError_t screen_reserve(glc_ctx *ctx, int slot, uint32_t ch, uint64_t f
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) return e;
   }
-  return ctx->screen_ws[slot].reserve(need);
+  for (EncodeSlot &s : ctx->slot) {
+    s.stat = static_cast<uint32_t *>(ctx->screen_stat.p) + 8 * s.index;
+    s.failed_total = static_cast<unsigned long long *>(ctx->edge_failed.p) + s.index;
+  }
+  return hipSuccess;
 }
 
-// glc_encode_range_device on a given stream with a given coefficient workspace (glc_encode runs
-// alternate rounds on two streams)
-static int encode_range_on(glc_ctx *ctx, hipStream_t stream, DevBuf &coef_ws, const float *d_pcm, uint64_t t0, uint64_t t_count,
-                           uint64_t n_samples, uint16_t channels, uint64_t frame_begin, uint64_t frame_end,
-                           void *d_records, float *d_coeffs, bool alternate_ok = false, bool beside = false,
-                           bool edge_ok = false) {
-  const int rc = check_encode_range(ctx, "glc_encode_range_device", d_pcm, t0, t_count, n_samples, channels,
-                                    frame_begin, frame_end, d_records, d_coeffs != nullptr);
+// A slot's workspaces for a range of `frames` frames in chunks of `chunk`: the coefficients of its largest launch
+// and, where one of its launches may take the screened path, that path's workspace and the shared words.  The one
+// place that reserves for a launch: screen_takes below decides from the same policy and the same launch shapes.
+static hipError_t reserve_slot(glc_ctx *ctx, EncodeSlot &slot, uint32_t ch, uint64_t frames, uint64_t chunk) {
+  const uint64_t rows = std::min<uint64_t>(chunk, frames) * ch;
+  hipError_t e = slot.coef.reserve(std::max<size_t>(rows, 1) * glc::kHop * sizeof(float));
+  if (e == hipSuccess && ctx->policy.workspace_bytes(ch, frames, chunk)) e = ensure_screen_shared(ctx);
+  if (e == hipSuccess) e = slot.reserve_screen(ctx->policy, ch, frames, chunk);
+  return e;
+}
+
+// Whether a launch of M rows takes the screened path (ScreenPolicy): the guard's step, fed the words the slots'
+// repair launches left - plain loads of host-mapped memory, not synchronised.
+static bool screen_takes(glc_ctx *ctx, uint32_t M, uint32_t ch) {
+  ScreenPolicy &pol = ctx->policy;
+  if (!pol.may(M, ch)) return false;
+  bool pending = false;  // a screened launch whose count has not come back
+  for (EncodeSlot &s : ctx->slot) {
+    const volatile uint32_t *hs = s.stat;
+    const uint32_t seq = hs[2], failed = hs[0], rows = hs[1];
+    pol.observe(s.judged, seq, failed, rows);
+    pending = pending || seq != s.seq;
+  }
+  return pol.admit(pending);
+}
+
+// glc_encode_range_device on a given stream and slot (glc_encode runs alternate rounds on two streams)
+static int encode_range_on(glc_ctx *ctx, hipStream_t stream, const EncodeRange &r, unsigned flags = 0) {
+  const int rc = check_encode_range(ctx, "glc_encode_range_device", r, r.coef_tap != nullptr);
   if (rc != GLC_OK) return rc;
-  const uint32_t ch = channels;
+  const glc::PcmView &view = r.view;
+  const uint32_t ch = view.ch;
+  const uint64_t frame_begin = r.frame_begin, frame_end = r.frame_end;
+  float *const d_coeffs = r.coef_tap;
+  ScreenPolicy &pol = ctx->policy;
   DeviceGuard guard(ctx->device);
   const uint64_t rec = glc::record_bytes(ch);
-  glc::PcmView view{d_pcm, t0, t_count, n_samples, ch};
-  uint8_t *recs = static_cast<uint8_t *>(d_records);
+  uint8_t *recs = static_cast<uint8_t *>(r.records);
   const uint64_t chunk = d_coeffs ? (frame_end - frame_begin ? frame_end - frame_begin : 1) : encode_chunk_frames(ch);
-  if (!d_coeffs) {
-    const uint64_t rows = std::min<uint64_t>(chunk, frame_end - frame_begin) * ch;
-    GLC_HIP(ctx, coef_ws.reserve(std::max<size_t>(rows, 1) * glc::kHop * sizeof(float)));
-    GLC_HIP(ctx, screen_reserve(ctx, &coef_ws == &ctx->coef_b ? 1 : 0, ch, frame_end - frame_begin, chunk));
-  }
+  if (!d_coeffs) GLC_HIP(ctx, reserve_slot(ctx, *r.slot, ch, frame_end - frame_begin, chunk));
   // A range of several chunks alternates between the caller's stream and a second one (its own
   // coefficient workspace): chunk c's quantiser then runs beside chunk c+1's transform instead of in
   // front of it (six 4096-frame chunks: 3.78 -> 3.68 ms).  Fork and join by events, so the caller sees
   // plain stream order: everything queued before the call is finished before the second stream
   // starts, and the caller's stream continues only when both are done.
-  const bool alternate = alternate_ok && !d_coeffs && frame_end - frame_begin > chunk;
+  const bool alternate = (flags & kEncodeAlternate) && !d_coeffs && frame_end - frame_begin > chunk;
   if (alternate) {
-    if (!ctx->stream_b) GLC_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream_b, hipStreamNonBlocking));
-    if (!ctx->ev_fork) GLC_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-    if (!ctx->ev_join) GLC_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-    GLC_HIP(ctx, ctx->coef_b.reserve(static_cast<size_t>(chunk) * ch * glc::kHop * sizeof(float)));
-    GLC_HIP(ctx, screen_reserve(ctx, 1, ch, frame_end - frame_begin, chunk));
+    GLC_HIP(ctx, ctx->stream_b.ensure());
+    GLC_HIP(ctx, ctx->ev_fork.ensure());
+    GLC_HIP(ctx, ctx->ev_join.ensure());
+    GLC_HIP(ctx, reserve_slot(ctx, ctx->slot[1], ch, frame_end - frame_begin, chunk));
     GLC_HIP(ctx, hipEventRecord(ctx->ev_fork, stream));
     GLC_HIP(ctx, hipStreamWaitEvent(ctx->stream_b, ctx->ev_fork, 0));
   }
   // The stream's edge frames (glc_kernels.h edge_frames): a screened chunk that holds some hands them to the side
-  // stream.  Only the call that owns its stream's order does (edge_ok): the drivers pass no edge range.
-  const glc_plan plan = glc::plan_encode(n_samples, channels);
+  // stream.  Only the call that owns its stream's order does (kEncodeEdge): the drivers pass no edge range.
+  const glc_plan plan = glc::plan_encode(view.n_samples, static_cast<uint16_t>(ch));
   const glc::EdgeFrames ef = glc::edge_frames(plan.per_channel, plan.n_frames);
   uint64_t c_idx = 0;
   for (uint64_t f = frame_begin; f < frame_end; f += chunk, ++c_idx) {
@@ -704,42 +548,39 @@ static int encode_range_on(glc_ctx *ctx, hipStream_t stream, DevBuf &coef_ws, co
     const uint32_t M = static_cast<uint32_t>(nf * ch);
     const bool odd = alternate && (c_idx & 1);
     hipStream_t st = odd ? ctx->stream_b : stream;
-    float *coef = d_coeffs ? d_coeffs + (f - frame_begin) * ch * glc::kHop : static_cast<float *>(odd ? ctx->coef_b.p : coef_ws.p);
-    uint8_t *r = recs + (f - frame_begin) * rec;
-    const int slot = (odd || &coef_ws == &ctx->coef_b) ? 1 : 0;
+    uint8_t *rp = recs + (f - frame_begin) * rec;
+    EncodeSlot &slot = odd ? ctx->slot[1] : *r.slot;
+    float *coef = d_coeffs ? d_coeffs + (f - frame_begin) * ch * glc::kHop : static_cast<float *>(slot.coef.p);
     if (!d_coeffs && screen_takes(ctx, M, ch)) {
-      if (ctx->screen_ws[slot].cap < glc::encode_screen_bytes(M, ctx->screen_shape))
+      if (slot.screen_ws.cap < glc::encode_screen_bytes(M, pol.shape))
         return fail(ctx, GLC_EINVAL, "glc_encode_range_device: the screen's workspace was not reserved for this launch");
       bool decided = false;
-      const bool latency = screen_latency_repair(ctx);
-      const bool matrix = screen_matrix_bound(ctx, M, ch);
-      if (slot == 0) ctx->tap_rows = M, ctx->tap_planes = matrix ? glc::MatrixBound::kGroups : ctx->screen_shape.n_planes;
+      glc::ScreenLaunch sl{slot.screen_ws.p, slot.stat, 0, rp, st, pol.latency_repair(), pol.matrix_bound(M, ch), nullptr};
+      if (slot.index == 0) pol.tap_rows = M, pol.tap_planes = sl.matrix_bound ? glc::MatrixBound::kGroups : pol.shape.n_planes;
       glc::EdgeLaunch edge{ef.a, ef.b, nullptr, nullptr, nullptr, nullptr, false, nullptr};
       const uint32_t n_edge = glc::edge_rows(ef.a, ef.b, f, M, ch).n;
-      const bool take_edge = edge_ok && ctx->edge_kind != 1 && n_edge >= 1 && n_edge <= glc::kEdgeRowsMax && ctx->edge_failed.p;
-      if (take_edge) {
-        if (!ctx->edge_stream) GLC_HIP(ctx, hipStreamCreateWithFlags(&ctx->edge_stream, hipStreamNonBlocking));
-        for (hipEvent_t &ev : ctx->ev_edge[slot])
-          if (!ev) GLC_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        GLC_HIP(ctx, ctx->edge_coef[slot].reserve(static_cast<size_t>(glc::kEdgeRowsMax) * glc::kHop * sizeof(float)));
+      if ((flags & kEncodeEdge) && pol.edge_kind != 1 && n_edge >= 1 && n_edge <= glc::kEdgeRowsMax) {
+        GLC_HIP(ctx, ctx->edge_stream.ensure());
+        for (Event &ev : slot.ev_edge) GLC_HIP(ctx, ev.ensure());
+        GLC_HIP(ctx, slot.edge_coef.reserve(static_cast<size_t>(glc::kEdgeRowsMax) * glc::kHop * sizeof(float)));
         edge.side = ctx->edge_stream;
-        edge.ev_fork = ctx->ev_edge[slot][0], edge.ev_edge = ctx->ev_edge[slot][1];
-        edge.coef = static_cast<float *>(ctx->edge_coef[slot].p);
-        edge.capped = edge_capped(ctx);
-        edge.failed_total = static_cast<unsigned long long *>(ctx->edge_failed.p) + slot;
-        ++ctx->edge_launches;
-        ctx->edge_rows += n_edge;
+        edge.ev_fork = slot.ev_edge[0], edge.ev_edge = slot.ev_edge[1];
+        edge.coef = static_cast<float *>(slot.edge_coef.p);
+        edge.capped = pol.edge_capped();
+        edge.failed_total = slot.failed_total;
+        ++pol.edge_launches;
+        pol.edge_rows += n_edge;
+        sl.edge = &edge;
       }
-      GLC_HIP(ctx, glc::launch_encode_screened(ctx->dev, ctx->screen_shape, view, f, M, coef, ctx->screen_ws[slot].p,
-                                               static_cast<uint32_t *>(ctx->screen_stat.p) + 8 * slot, ++ctx->screen_seq[slot],
-                                               r, st, &decided, latency, matrix, take_edge ? &edge : nullptr));
-      ++ctx->repair_launches[latency ? 1 : 0];
-      if (!decided) GLC_HIP(ctx, glc::launch_decide_raw(ctx->dev, view, f, static_cast<uint32_t>(nf), r, st));
-      ctx->rows_screened += M;
+      sl.seq = ++slot.seq;
+      GLC_HIP(ctx, glc::launch_encode_screened(ctx->dev, pol.shape, view, f, M, coef, sl, &decided));
+      ++pol.repair_launches[sl.latency_repair ? 1 : 0];
+      if (!decided) GLC_HIP(ctx, glc::launch_decide_raw(ctx->dev, view, f, static_cast<uint32_t>(nf), rp, st));
+      pol.rows_screened += M;
       continue;
     }
-    GLC_HIP(ctx, glc::launch_mdct_forward(ctx->dev, view, f, M, coef, st, ctx->k1_variant, beside));
-    GLC_HIP(ctx, launch_quantize_decide(ctx, coef, view, f, nf, r, st));
+    GLC_HIP(ctx, glc::launch_mdct_forward(ctx->dev, view, f, M, coef, st, pol.k1_variant, (flags & kEncodeBeside) != 0));
+    GLC_HIP(ctx, launch_quantize_decide(ctx, coef, view, f, nf, rp, st));
   }
   if (alternate) {
     GLC_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->stream_b));
@@ -752,8 +593,8 @@ int glc_encode_range_device(glc_ctx *ctx, const float *d_pcm, uint64_t t0, uint6
                             uint64_t n_samples, uint16_t channels, uint64_t frame_begin,
                             uint64_t frame_end, void *d_records, float *d_coeffs) {
   if (!ctx) return GLC_EINVAL;
-  return encode_range_on(ctx, ctx->stream, ctx->coef, d_pcm, t0, t_count, n_samples, channels, frame_begin, frame_end,
-                         d_records, d_coeffs, /*alternate_ok=*/true, /*beside=*/false, /*edge_ok=*/true);
+  const EncodeRange r{{d_pcm, t0, t_count, n_samples, channels}, frame_begin, frame_end, d_records, d_coeffs, &ctx->slot[0]};
+  return encode_range_on(ctx, ctx->stream, r, kEncodeAlternate | kEncodeEdge);
 }
 
 int glc_debug_quantize_device(glc_ctx *ctx, const float *d_coeffs, const float *d_pcm, uint64_t t0, uint64_t t_count,
@@ -761,11 +602,11 @@ int glc_debug_quantize_device(glc_ctx *ctx, const float *d_coeffs, const float *
                               void *d_records) {
   if (!ctx) return GLC_EINVAL;
   if (!d_coeffs) return fail(ctx, GLC_EINVAL, "glc_debug_quantize_device: null argument");
-  const int rc = check_encode_range(ctx, "glc_debug_quantize_device", d_pcm, t0, t_count, n_samples, channels,
-                                    frame_begin, frame_end, d_records, /*whole_tap=*/true);
+  const glc::PcmView view{d_pcm, t0, t_count, n_samples, channels};
+  const int rc = check_encode_range(ctx, "glc_debug_quantize_device", EncodeRange{view, frame_begin, frame_end, d_records, nullptr, nullptr},
+                                    /*whole_tap=*/true);
   if (rc != GLC_OK) return rc;
   DeviceGuard guard(ctx->device);
-  const glc::PcmView view{d_pcm, t0, t_count, n_samples, channels};
   GLC_HIP(ctx, launch_quantize_decide(ctx, d_coeffs, view, frame_begin, frame_end - frame_begin,
                                       static_cast<uint8_t *>(d_records), ctx->stream));
   return GLC_OK;
@@ -783,7 +624,7 @@ int glc_mdct_forward_device(glc_ctx *ctx, const float *d_pcm, uint64_t t0, uint6
   DeviceGuard guard(ctx->device);
   glc::PcmView view{d_pcm, t0, t_count, n_samples, channels};
   GLC_HIP(ctx, glc::launch_mdct_forward(ctx->dev, view, frame_begin, static_cast<uint32_t>(rows), d_coeffs,
-                                        ctx->stream, ctx->k1_variant));
+                                        ctx->stream, ctx->policy.k1_variant));
   return GLC_OK;
 }
 
@@ -1047,25 +888,24 @@ static int encode_pipeline(glc_ctx *ctx, const void *pcm_any, glc_pcm_format fmt
   GLC_HIP(ctx, ctx->host_stage.reserve(stage_cap));
   // the per-round workspaces at their largest now: growing one mid-pipeline would free it under queued work
   GLC_HIP(ctx, ctx->coef.reserve(static_cast<size_t>(max_nf) * ch * glc::kHop * sizeof(float)));
-  if (n_rounds > 1) GLC_HIP(ctx, ctx->coef_b.reserve(static_cast<size_t>(max_nf) * ch * glc::kHop * sizeof(float)));
+  if (n_rounds > 1) GLC_HIP(ctx, ctx->slot[1].coef.reserve(static_cast<size_t>(max_nf) * ch * glc::kHop * sizeof(float)));
   GLC_HIP(ctx, ctx->pack_meta.reserve(glc::compact_scratch_bytes(max_nf * ch)));
-  if (!ctx->stream_b) GLC_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream_b, hipStreamNonBlocking));
-  if (!ctx->copy_stream) GLC_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-  if (!ctx->down_stream) GLC_HIP(ctx, hipStreamCreateWithFlags(&ctx->down_stream, hipStreamNonBlocking));
+  GLC_HIP(ctx, ctx->stream_b.ensure());
+  GLC_HIP(ctx, ctx->copy_stream.ensure());
+  GLC_HIP(ctx, ctx->down_stream.ensure());
   while (ctx->ev_round.size() < n_rounds) {
-    hipEvent_t e = nullptr;
-    GLC_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    Event e;
+    GLC_HIP(ctx, e.ensure());
     try {
-      ctx->ev_round.push_back(e);
+      ctx->ev_round.push_back(std::move(e));
     } catch (const std::bad_alloc &) {
-      (void)hipEventDestroy(e);
       return fail(ctx, GLC_ENOMEM, "glc_encode: host allocation failed");
     }
   }
   GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // earlier work may still read the staging buffers
   float *d_pcm = static_cast<float *>(ctx->pcm.p);
   uint8_t *d_blob = static_cast<uint8_t *>(ctx->pack_blob.p);
-  hipEvent_t *ev_rec = ctx->ev_round.data();
+  const Event *ev_rec = ctx->ev_round.data();
 
   // progress shared by the three threads; an error anywhere stops all of them
   struct Progress {
@@ -1132,8 +972,8 @@ static int encode_pipeline(glc_ctx *ctx, const void *pcm_any, glc_pcm_format fmt
       hipStream_t cs = (i & 1) ? ctx->stream_b : ctx->stream;
       hipError_t e = hipSuccess;
       uint8_t *recs = static_cast<uint8_t *>(ctx->records.p) + r.f0 * rec;
-      int rc = encode_range_on(ctx, cs, (i & 1) ? ctx->coef_b : ctx->coef, d_pcm, 0, t_count, n_samples, channels, r.f0,
-                               r.f0 + r.nf, recs, nullptr, /*alternate_ok=*/false, /*beside=*/true);
+      int rc = encode_range_on(ctx, cs, EncodeRange{{d_pcm, 0, t_count, n_samples, ch}, r.f0, r.f0 + r.nf, recs, nullptr, &ctx->slot[i & 1]},
+                               kEncodeBeside);
       if (rc != GLC_OK) return prog.set_error(rc, my_err);
       e = hipEventRecord(ev_rec[i], cs);
       if (e != hipSuccess) return prog.set_error(GLC_EHIP, hip_msg("glc_encode: queueing a round", e));
@@ -1417,7 +1257,7 @@ int encode_batch_round(glc_ctx *ctx, const std::vector<BatchClip> &clips, const 
   // and +0.0 + -0.0 = +0.0, the raw planes narrow both to 0.
   if (is_int) GLC_HIP(ctx, glc::launch_pcm_widen(d_up, fmt == GLC_PCM_S32, bits, n_virtual, d_pcm, st));
 
-  int rc = encode_range_on(ctx, st, ctx->coef, d_pcm, 0, T, n_virtual, channels, 0, V, ctx->records.p, nullptr);
+  int rc = encode_range_on(ctx, st, EncodeRange{{d_pcm, 0, T, n_virtual, ch}, 0, V, ctx->records.p, nullptr, &ctx->slot[0]});
   if (rc != GLC_OK) return rc;
 
   rc = compact_batch_launch(ctx, ctx->records.p, clip_frames.data(), n, ch, bl, d_blob, st);
@@ -1829,9 +1669,8 @@ int round_launch(glc_ctx *ctx, uint64_t round_frames, bool flush_at_full, T *dou
 
 int ensure_copy_objects(glc_ctx *ctx) {
   DeviceGuard guard(ctx->device);
-  if (!ctx->copy_stream) GLC_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-  for (hipEvent_t &e : ctx->ev_dec)
-    if (!e) GLC_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  GLC_HIP(ctx, ctx->copy_stream.ensure());
+  for (Event &e : ctx->ev_dec) GLC_HIP(ctx, e.ensure());
   return GLC_OK;
 }
 
@@ -2368,8 +2207,8 @@ template <typename T>
 int rt_roundtrip_round(glc_ctx *ctx, const RtGeom &g, const float *d_pcm, uint64_t n_samples, uint64_t f0, uint64_t nf, T *d_out,
                        uint64_t *stats, const RtStridedSink<T> *sink = nullptr) {
   const uint64_t t_count = (n_samples + g.ch - 1) / g.ch;
-  int rc = encode_range_on(ctx, ctx->stream, ctx->coef, d_pcm, 0, t_count, n_samples, static_cast<uint16_t>(g.ch), f0, f0 + nf,
-                           ctx->rt_records.p, nullptr);
+  int rc = encode_range_on(ctx, ctx->stream,
+                           EncodeRange{{d_pcm, 0, t_count, n_samples, g.ch}, f0, f0 + nf, ctx->rt_records.p, nullptr, &ctx->slot[0]});
   if (rc != GLC_OK) return rc;
   return rt_decode_round(ctx, g, static_cast<const uint8_t *>(ctx->rt_records.p), f0, nf, stats, d_out, sink);
 }
@@ -2405,7 +2244,7 @@ int rt_roundtrip_host(glc_ctx *ctx, const void *pcm, glc_pcm_format fmt, uint32_
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rt_out, std::max<size_t>(g.trim.n, 1) * sizeof(T));
   if (rc == GLC_OK) rc = ensure_copy_objects(ctx);
   if (rc != GLC_OK) return rc;
-  if (!ctx->down_stream) GLC_HIP(ctx, hipStreamCreateWithFlags(&ctx->down_stream, hipStreamNonBlocking));
+  GLC_HIP(ctx, ctx->down_stream.ensure());
   // the staging buffers are shared with the other host-boundary calls, some of which work on streams of their own
   GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   float *d_pcm = static_cast<float *>(ctx->pcm.p);
@@ -2707,7 +2546,7 @@ std::vector<RtbRound> rtb_plan_rounds(const std::vector<glc_plan> &plans, uint32
 int rtb_image_begin(glc_ctx *ctx, size_t tab) {
   int rc = rt_reserve(ctx, ctx->rtb_tab, tab);
   if (rc != GLC_OK) return rc;
-  if (!ctx->rtb_ev) GLC_HIP(ctx, hipEventCreateWithFlags(&ctx->rtb_ev, hipEventDisableTiming));
+  GLC_HIP(ctx, ctx->rtb_ev.ensure());
   if (ctx->rtb_ev_pending) GLC_HIP(ctx, hipEventSynchronize(ctx->rtb_ev));
   ctx->rtb_ev_pending = false;
   GLC_HIP(ctx, ctx->rtb_stage.reserve(tab));
@@ -2832,7 +2671,7 @@ int rtb_impl(glc_ctx *ctx, const RtbPcm &pcm, const RtbLayout &in, Out *d_out, c
       continue;
     }
     const uint64_t T = r.V * glc::kHop;
-    rc = encode_range_on(ctx, st, ctx->coef, vs, 0, T, T * ch, static_cast<uint16_t>(ch), 0, r.V, ctx->rt_records.p, nullptr);
+    rc = encode_range_on(ctx, st, EncodeRange{{vs, 0, T, T * ch, static_cast<uint32_t>(ch)}, 0, r.V, ctx->rt_records.p, nullptr, &ctx->slot[0]});
     if (rc != GLC_OK) return rc;
     const uint32_t M = static_cast<uint32_t>(r.n_real * ch);
     glc::DecodeRows rows{};
@@ -3044,7 +2883,7 @@ int cdb_impl(glc_ctx *ctx, const char *who, const void *const *d_blobs, const ui
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rtb_tab, tab);
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->cd_status, n * sizeof(glc::CompactStatus));
   if (rc != GLC_OK) return rc;
-  if (!ctx->rtb_ev) GLC_HIP(ctx, hipEventCreateWithFlags(&ctx->rtb_ev, hipEventDisableTiming));
+  GLC_HIP(ctx, ctx->rtb_ev.ensure());
   // the pinned image is shared with glc_roundtrip_batch_device: wait until the last upload has left it
   if (ctx->rtb_ev_pending) GLC_HIP(ctx, hipEventSynchronize(ctx->rtb_ev));
   ctx->rtb_ev_pending = false;
@@ -3602,10 +3441,10 @@ int ebc_impl(glc_ctx *ctx, const RtbPcm &pcm, const RtbLayout &in, void *d_arena
     if (rc != GLC_OK) return rc;
     if (r.lng) {
       const uint64_t len = in.len(r.first);
-      rc = encode_range_on(ctx, st, ctx->coef, vs, 0, len, len * ch, static_cast<uint16_t>(ch), 0, r.n_real, ctx->rt_records.p, nullptr);
+      rc = encode_range_on(ctx, st, EncodeRange{{vs, 0, len, len * ch, static_cast<uint32_t>(ch)}, 0, r.n_real, ctx->rt_records.p, nullptr, &ctx->slot[0]});
     } else {
       const uint64_t T = r.V * glc::kHop;
-      rc = encode_range_on(ctx, st, ctx->coef, vs, 0, T, T * ch, static_cast<uint16_t>(ch), 0, r.V, ctx->rt_records.p, nullptr);
+      rc = encode_range_on(ctx, st, EncodeRange{{vs, 0, T, T * ch, static_cast<uint32_t>(ch)}, 0, r.V, ctx->rt_records.p, nullptr, &ctx->slot[0]});
     }
     if (rc == GLC_OK)
       rc = store_round_launch(ctx, ctx->rt_records.p, r.n_real, r.n, ch, d_tab, r.o_fmap, r.o_span, d_arena, arena_bytes, d_cursor,
@@ -3856,7 +3695,7 @@ int stream_push_core(glc_stream_enc *s, const RtbPcm &pcm, const RtbLayout &in, 
     // the virtual stream's frames [1, V - 1): frame 0 is the slot in front, frame V - 1 the last segment's junk one;
     // record j is virtual frame j + 1, which is how store_round_tables numbers them
     const uint64_t T = R.V * glc::kHop;
-    rc = encode_range_on(ctx, st, ctx->coef, vs, 0, T, T * ch, static_cast<uint16_t>(ch), 1, R.V - 1, ctx->rt_records.p, nullptr);
+    rc = encode_range_on(ctx, st, EncodeRange{{vs, 0, T, T * ch, static_cast<uint32_t>(ch)}, 1, R.V - 1, ctx->rt_records.p, nullptr, &ctx->slot[0]});
     if (rc == GLC_OK)
       rc = store_round_launch(ctx, ctx->rt_records.p, R.n_real, R.n, ch, d_tab, R.o_fmap, R.o_span, d_arena, arena_bytes, d_cursor,
                               d_entries + R.first, st);
@@ -3929,8 +3768,6 @@ void glc_stream_enc_close(glc_stream_enc *s) {
   if (!s) return;
   DeviceGuard guard(s->ctx->device);
   (void)hipStreamSynchronize(s->ctx->stream);  // queued pushes may still read and write the session's buffers
-  s->held.release(), s->d_pcm.release(), s->arena.release(), s->d_meta.release();
-  s->up.release(), s->down.release();
   delete s;
 }
 
@@ -4309,41 +4146,44 @@ int glc_debug_set_imdct_variant(glc_ctx *ctx, int variant) {
 
 int glc_debug_set_mdct_variant(glc_ctx *ctx, int variant) {
   if (!ctx || variant < 0 || variant > 4) return fail(ctx, GLC_EINVAL, "glc_debug_set_mdct_variant: variant must be 0..4");
-  ctx->k1_variant = variant;
+  ctx->policy.k1_variant = variant;
+  return GLC_OK;
+}
+
+int glc_debug_live_resources(uint64_t counts[4]) {
+  if (!counts) return GLC_EINVAL;
+  for (int k = 0; k < glc::kLiveKinds; ++k) counts[k] = glc::g_live[k].load(std::memory_order_relaxed);
   return GLC_OK;
 }
 
 int glc_debug_set_encode_screen(glc_ctx *ctx, int mode) {
   if (!ctx || mode < 0 || mode > 2) return fail(ctx, GLC_EINVAL, "glc_debug_set_encode_screen: mode must be 0..2");
-  ctx->screen_mode = mode;
-  ctx->screen_backoff = 0;
-  ctx->screen_held = false;
-  ctx->screen_judged_any = false;
+  ctx->policy.set_mode(mode);
   return GLC_OK;
 }
 
 int glc_debug_set_encode_repair(glc_ctx *ctx, int kind) {
   if (!ctx || kind < 0 || kind > 2) return fail(ctx, GLC_EINVAL, "glc_debug_set_encode_repair: kind must be 0..2");
-  ctx->repair_kind = kind;
+  ctx->policy.repair_kind = kind;
   return GLC_OK;
 }
 
 int glc_debug_set_encode_edge(glc_ctx *ctx, int kind) {
   if (!ctx || kind < 0 || kind > 3) return fail(ctx, GLC_EINVAL, "glc_debug_set_encode_edge: kind must be 0..3");
-  ctx->edge_kind = kind;
+  ctx->policy.edge_kind = kind;
   return GLC_OK;
 }
 
 int glc_debug_encode_edge_stats(glc_ctx *ctx, uint64_t *launches, uint64_t *rows) {
   if (!ctx || !launches || !rows) return fail(ctx, GLC_EINVAL, "glc_debug_encode_edge_stats: null argument");
-  *launches = ctx->edge_launches;
-  *rows = ctx->edge_rows;
+  *launches = ctx->policy.edge_launches;
+  *rows = ctx->policy.edge_rows;
   return GLC_OK;
 }
 
 int glc_debug_set_encode_bound(glc_ctx *ctx, int kind) {
   if (!ctx || kind < 0 || kind > 2) return fail(ctx, GLC_EINVAL, "glc_debug_set_encode_bound: kind must be 0..2");
-  ctx->bound_kind = kind;
+  ctx->policy.bound_kind = kind;
   return GLC_OK;
 }
 
@@ -4357,18 +4197,19 @@ int glc_debug_encode_matrix_bound(uint32_t *ne, uint32_t *pieces, uint32_t *prod
 }
 
 int glc_debug_encode_bound_tap(glc_ctx *ctx, uint32_t rows, float *h, float *a) {
-  if (!ctx || !h || !a || rows == 0 || rows != ctx->tap_rows || !ctx->screen_ws[0].p)
+  if (!ctx || !h || !a || rows == 0 || rows != ctx->policy.tap_rows || !ctx->slot[0].screen_ws.p)
     return fail(ctx, GLC_EINVAL, "glc_debug_encode_bound_tap: no screened launch of that many rows on this context");
   DeviceGuard guard(ctx->device);
   GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const uint64_t stride = (static_cast<uint64_t>(rows) + 255ull) / 256ull * 256ull;
-  std::vector<float> planes((ctx->tap_planes + 1ull) * stride);
-  GLC_HIP(ctx, hipMemcpy(planes.data(), ctx->screen_ws[0].p, planes.size() * 4, hipMemcpyDeviceToHost));
+  const uint32_t tap_planes = ctx->policy.tap_planes;
+  std::vector<float> planes((tap_planes + 1ull) * stride);
+  GLC_HIP(ctx, hipMemcpy(planes.data(), ctx->slot[0].screen_ws.p, planes.size() * 4, hipMemcpyDeviceToHost));
   for (uint32_t m = 0; m < rows; ++m) {
     float mx = 0.0f;
-    for (uint32_t p = 0; p < ctx->tap_planes; ++p) mx = std::fmax(mx, planes[p * stride + m]);
+    for (uint32_t p = 0; p < tap_planes; ++p) mx = std::fmax(mx, planes[p * stride + m]);
     h[m] = mx;
-    a[m] = planes[ctx->tap_planes * stride + m];
+    a[m] = planes[tap_planes * stride + m];
   }
   return GLC_OK;
 }
@@ -4387,15 +4228,14 @@ int glc_debug_mfma_bf16(glc_ctx *ctx, const uint16_t *a, const uint16_t *b, cons
                                     reinterpret_cast<const float *>(p + 2048), reinterpret_cast<float *>(p + 2048 + 4096), ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e == hipSuccess) e = hipMemcpy(d, p + 2048 + 4096, 4096, hipMemcpyDeviceToHost);
-  buf.release();
   GLC_HIP(ctx, e);
   return GLC_OK;
 }
 
 int glc_debug_encode_repair_stats(glc_ctx *ctx, uint64_t *launches_tiles, uint64_t *launches_latency) {
   if (!ctx || !launches_tiles || !launches_latency) return fail(ctx, GLC_EINVAL, "glc_debug_encode_repair_stats: null argument");
-  *launches_tiles = ctx->repair_launches[0];
-  *launches_latency = ctx->repair_launches[1];
+  *launches_tiles = ctx->policy.repair_launches[0];
+  *launches_latency = ctx->policy.repair_launches[1];
   return GLC_OK;
 }
 
@@ -4404,7 +4244,7 @@ int glc_debug_encode_screen_stats(glc_ctx *ctx, uint64_t *rows_screened, uint64_
   DeviceGuard guard(ctx->device);
   GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (ctx->stream_b) GLC_HIP(ctx, hipStreamSynchronize(ctx->stream_b));
-  *rows_screened = ctx->rows_screened;
+  *rows_screened = ctx->policy.rows_screened;
   *rows_repaired = 0;
   if (ctx->screen_stat.p) {
     const volatile uint64_t *hs = static_cast<const volatile uint64_t *>(ctx->screen_stat.p);
@@ -4434,7 +4274,7 @@ int glc_debug_encode_screen_layout(uint32_t ne, uint32_t rows, uint32_t *hybrid_
 int glc_debug_clock_probe_begin(glc_ctx *ctx, uint32_t window_us) {
   if (!ctx || window_us == 0) return fail(ctx, GLC_EINVAL, "glc_debug_clock_probe_begin: bad argument");
   DeviceGuard guard(ctx->device);
-  if (!ctx->probe_stream) GLC_HIP(ctx, hipStreamCreateWithFlags(&ctx->probe_stream, hipStreamNonBlocking));
+  GLC_HIP(ctx, ctx->probe_stream.ensure());
   GLC_HIP(ctx, ctx->probe_out.reserve(64));  // pinned: the wave writes its two counters straight to the host
   std::memset(ctx->probe_out.p, 0, 16);
   GLC_HIP(ctx, glc::launch_clock_probe(static_cast<uint64_t>(window_us) * 100ull, static_cast<uint64_t *>(ctx->probe_out.p),

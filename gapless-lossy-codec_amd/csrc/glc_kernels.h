@@ -111,10 +111,18 @@ struct EdgeLaunch {
                                 // two resident workgroups of K2 on a CU) instead of the latency form; same bytes
   unsigned long long *failed_total;  // device: the edge rows that failed the screen so far; the repair quantiser adds this launch's
 };
+// What a screened launch is given besides its rows (the comments above say what each is).
+struct ScreenLaunch {
+  void *workspace;
+  uint32_t *host_stat;
+  uint32_t seq;
+  uint8_t *records;
+  hipStream_t s;
+  bool latency_repair, matrix_bound;
+  const EdgeLaunch *edge;  // null: no edge path
+};
 hipError_t launch_encode_screened(const DeviceTables &t, const ScreenShape &sh, const PcmView &pcm, uint64_t frame_begin,
-                                  uint32_t M, float *coef, void *workspace, uint32_t *host_stat, uint32_t seq,
-                                  uint8_t *records, hipStream_t s, bool *decided, bool latency_repair = false,
-                                  bool matrix_bound = false, const EdgeLaunch *edge = nullptr);
+                                  uint32_t M, float *coef, const ScreenLaunch &launch, bool *decided);
 
 // The ONE definition of an edge frame: frame f reads per-channel samples [hop f - hop/2, hop f - hop/2 + frame); it
 // is an edge frame if that window is not wholly inside the stream [0, per_channel) of plan_encode.  Edge frames are

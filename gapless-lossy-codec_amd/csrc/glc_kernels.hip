@@ -2490,9 +2490,14 @@ uint64_t encode_screen_bytes(uint32_t M, const ScreenShape &sh) {
 }
 
 hipError_t launch_encode_screened(const DeviceTables &t, const ScreenShape &sh, const PcmView &pcm, uint64_t frame_begin,
-                                  uint32_t M, float *coef, void *workspace, uint32_t *host_stat, uint32_t seq,
-                                  uint8_t *records, hipStream_t s, bool *decided, bool latency_repair, bool matrix_bound,
-                                  const EdgeLaunch *edge) {
+                                  uint32_t M, float *coef, const ScreenLaunch &launch, bool *decided) {
+  void *const workspace = launch.workspace;
+  uint32_t *const host_stat = launch.host_stat;
+  const uint32_t seq = launch.seq;
+  uint8_t *const records = launch.records;
+  const hipStream_t s = launch.s;
+  const bool latency_repair = launch.latency_repair, matrix_bound = launch.matrix_bound;
+  const EdgeLaunch *const edge = launch.edge;
   *decided = pcm.ch == 1 || pcm.ch == 2 || pcm.ch == 4;
   if (M == 0) return hipSuccess;
   // the edge rows the side stream takes: none without `edge`, and then every kernel below is what it always was

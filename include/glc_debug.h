@@ -208,6 +208,14 @@ int glc_debug_store_plan_device(glc_ctx *ctx, const void *d_arena, uint64_t aren
  * rounds of 1 KiB and 4 KiB; tools/store_compact_bench.cpp measures the rounds the default was chosen from. */
 int glc_debug_set_store_compact_round(glc_ctx *ctx, uint64_t bytes);
 
+/* What the library holds of the device at this moment, over all contexts and stream encoders of the process: counts[0]
+ * device buffers, [1] pinned host buffers, [2] streams of its own (a caller's stream, glc_ctx_set_stream, is not one),
+ * [3] events.  Every one of them belongs to a context or a stream encoder (or lives for the length of one call) and is
+ * released with it, so the counts after glc_ctx_destroy / glc_stream_enc_close are the counts before the matching
+ * create / open, whatever ran in between and however it ended (tests/test_ctx_resources.py).  Relaxed atomic counters:
+ * no context, no device, nothing is waited for; meaningful when no other thread is inside the library. */
+int glc_debug_live_resources(uint64_t counts[4]);
+
 /* The shader clock the device HOLDS under load (measurement only; bench.py's roofline.clock_ghz_held).
  * `begin` starts one sleeping wave on a stream of its own that runs for `window_us` microseconds beside
  * whatever the caller queues meanwhile and reads the shader-cycle counter against the constant 100 MHz
