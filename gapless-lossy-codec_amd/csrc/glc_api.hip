@@ -24,6 +24,7 @@
 #include "glc_common.h"
 #include "glc_kernels.h"
 #include "glc_resources.hpp"
+#include "glc_rounds.hpp"
 
 namespace glc {
 
@@ -83,6 +84,23 @@ struct Worker {
   }
 };
 
+// The tables of a batch call: written into the context's pinned image (rtb_stage), sent up to rtb_tab in ONE copy with
+// rtb_ev recorded behind it.  The image is shared by every such call of the context and may still be on its way up for
+// the call before, so begin() waits for that copy - not for any kernel of that call, they are queued behind it - before
+// the caller may write host<T>(); send() queues the copy, after which the launches may read dev<T>().  Owns nothing:
+// buffers and event are the context's.
+struct TableImage {
+  bool pending = false;  // an upload has been queued and its event not waited for
+  uint8_t *img = nullptr;
+  const uint8_t *tab = nullptr;  // of the call that last began
+  int begin(glc_ctx *ctx, size_t bytes);
+  int send(glc_ctx *ctx, size_t bytes);
+  template <typename T>
+  T *host(size_t off) const { return reinterpret_cast<T *>(img + off); }
+  template <typename T>
+  const T *dev(size_t off) const { return reinterpret_cast<const T *>(tab + off); }
+};
+
 // Everything a context owns releases itself (glc_resources.hpp), and `delete ctx` is all glc_ctx_destroy does about
 // it.  Members are destroyed in reverse order of declaration, so THE ORDER BELOW IS THE ORDER OF RELEASE, backwards:
 // the helper threads stand last and are joined first, the events before them are destroyed next, then the streams,
@@ -125,7 +143,7 @@ struct glc_ctx {
   DevBuf rtb_tab;      // the call's tables: per round the clip table, the frame map and the hop descriptors
   DevBuf rtb_stats;    // per-clip counters of the last batch call
   HostBuf rtb_stage;   // pinned image of rtb_tab on its way up; rtb_ev is recorded behind that copy
-  bool rtb_ev_pending = false;
+  TableImage rtb_image;  // the upload protocol of the two: every call that writes rtb_stage goes through it
   struct RtbClipInfo {
     uint64_t n_frames, stat_off;  // stat_off: the clip's first counter pair in rtb_stats, in uint64_t
     uint32_t stat_slots;
@@ -287,21 +305,16 @@ int glc_ctx_create(int device, uint32_t sample_rate, glc_ctx **out) {
   // one allocation, 256-B aligned sub-buffers
   const glc::HostTables &h = ctx->host;
   const size_t nb = h.edges.size() - 1;
-  size_t off = 0;
-  auto place = [&](size_t bytes) {
-    size_t at = off;
-    off = align_up(off + bytes, 256);
-    return at;
-  };
-  const size_t o_cos_t = place(h.cos_table_t.size() * 4);
-  const size_t o_cos = place(h.cos_table.size() * 4);
-  const size_t o_win = place(h.window.size() * 4);
-  const size_t o_indiv = place(h.indiv.size() * 4);
-  const size_t o_pf = place(64 * 4);
-  const size_t o_len = place(64 * 4);
-  const size_t o_bof = place(h.band_of.size() * 2);
-  const size_t o_edges = place(65 * 4);
-  e = ctx->tables.reserve(off);
+  TableOffsets offs;
+  const size_t o_cos_t = offs.take(h.cos_table_t.size() * 4);
+  const size_t o_cos = offs.take(h.cos_table.size() * 4);
+  const size_t o_win = offs.take(h.window.size() * 4);
+  const size_t o_indiv = offs.take(h.indiv.size() * 4);
+  const size_t o_pf = offs.take(64 * 4);
+  const size_t o_len = offs.take(64 * 4);
+  const size_t o_bof = offs.take(h.band_of.size() * 2);
+  const size_t o_edges = offs.take(65 * 4);
+  e = ctx->tables.reserve(offs.size());
   if (e != hipSuccess) return hip_fail(nullptr, e, "hipMalloc(tables)");
   uint8_t *base = static_cast<uint8_t *>(ctx->tables.p);
   auto up = [&](size_t o, const void *src, size_t bytes) {
@@ -1331,35 +1344,22 @@ int encode_batch_impl(glc_ctx *ctx, const char *who, const void *const *pcm, glc
   }
   DeviceGuard guard(ctx->device);
   std::vector<std::unique_ptr<glc_frames>> result(n_clips);
-  const uint64_t budget = encode_chunk_frames(channels);  // virtual frames per round: the workspaces stay round-sized
-  std::vector<BatchClip> round;
-  uint64_t used = 0;
+  // the budget: virtual frames per round, so that the workspaces stay round-sized
+  const auto rounds = pack_rounds(n_clips, [&](uint64_t i) { return all[i].plan.n_frames; }, encode_chunk_frames(channels), 0);
   int rc = GLC_OK;
-  auto alone = [&](uint64_t i) {  // the single-stream pipeline (uploads, kernels and downloads of one stream overlapped)
-    glc_frames *f = nullptr;
-    rc = encode_pipeline(ctx, pcm[i], fmt, bits, n_samples[i], channels, nullptr, nullptr, &f);
-    result[i].reset(f);
-  };
-  auto flush = [&] {
-    if (round.size() == 1 && rc == GLC_OK)  // a clip with a round to itself shares nothing
-      alone(round[0].index);
-    else if (!round.empty() && rc == GLC_OK)
+  for (size_t k = 0; k < rounds.size() && rc == GLC_OK; ++k) {
+    const RoundSpan &r = rounds[k];
+    // longer than a round, or a round to itself: it shares nothing, and the single-stream pipeline overlaps the uploads,
+    // kernels and downloads of one stream
+    if (r.lng || r.n == 1) {
+      glc_frames *f = nullptr;
+      rc = encode_pipeline(ctx, pcm[r.first], fmt, bits, n_samples[r.first], channels, nullptr, nullptr, &f);
+      result[r.first].reset(f);
+    } else {
+      const std::vector<BatchClip> round(all.begin() + r.first, all.begin() + r.first + r.n);
       rc = encode_batch_round(ctx, round, pcm, fmt, bits, n_samples, channels, result);
-    round.clear();
-    used = 0;
-  };
-  for (uint64_t i = 0; i < n_clips && rc == GLC_OK; ++i) {
-    const uint64_t v = all[i].plan.n_frames + 1;
-    if (v > budget) {  // longer than a round: nothing to gain from packing
-      flush();
-      if (rc == GLC_OK) alone(i);
-      continue;
     }
-    if (used + v > budget) flush();
-    round.push_back(all[i]);
-    used += v;
   }
-  flush();
   if (rc != GLC_OK) {
     (void)hipStreamSynchronize(ctx->stream);  // nothing may still be in flight out of the caller's memory
     return rc;
@@ -1566,17 +1566,12 @@ int decode_prepare_impl(glc_ctx *ctx, const glc_frames *in) {
   if (rc != GLC_OK) return rc;
 
   DeviceGuard guard(ctx->device);
-  size_t off = 0;
-  auto place = [&](size_t bytes) {
-    size_t at = off;
-    off = align_up(off + bytes, 256);
-    return at;
-  };
-  const size_t o_pairs = place(std::max<size_t>(t.n_stored + t.extra.size(), 1) * 4);
-  const size_t o_rows = place(t.h_end);  // the row block, as it is
-  const size_t o_pool = place(std::max<size_t>(in->raw.size(), 1) * 2);
+  TableOffsets offs;
+  const size_t o_pairs = offs.take(std::max<size_t>(t.n_stored + t.extra.size(), 1) * 4);
+  const size_t o_rows = offs.take(t.h_end);  // the row block, as it is
+  const size_t o_pool = offs.take(std::max<size_t>(in->raw.size(), 1) * 2);
   GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // a previous session may still read dec_meta
-  GLC_HIP(ctx, ctx->dec_meta.reserve(off));
+  GLC_HIP(ctx, ctx->dec_meta.reserve(offs.size()));
   uint8_t *mb = static_cast<uint8_t *>(ctx->dec_meta.p);
   auto up = [&](size_t o, const void *src, size_t bytes) -> hipError_t {
     if (!bytes) return hipSuccess;
@@ -1830,21 +1825,16 @@ int decode_batch_round(glc_ctx *ctx, const glc_frames *const *streams, uint64_t 
   }
   // everything D1 and D2 read, as ONE image in pinned memory and one copy: the pairs of all streams, the
   // canonicalised lists, the row arrays, the raw pool, the hop descriptors
-  size_t off = 0;
-  auto place = [&](size_t bytes) {
-    size_t at = off;
-    off = align_up(off + bytes, 256);
-    return at;
-  };
-  const size_t o_pairs = place(std::max<size_t>(t.n_stored + t.extra.size(), 1) * 4);
-  const size_t o_rows = place(t.h_end);
-  const size_t o_pool = place(std::max<size_t>(t.n_raw, 1) * 2);
-  const size_t o_desc = place(std::max<size_t>(desc.size(), 1) * sizeof(glc::HopDesc));
+  TableOffsets offs;
+  const size_t o_pairs = offs.take(std::max<size_t>(t.n_stored + t.extra.size(), 1) * 4);
+  const size_t o_rows = offs.take(t.h_end);
+  const size_t o_pool = offs.take(std::max<size_t>(t.n_raw, 1) * 2);
+  const size_t o_desc = offs.take(std::max<size_t>(desc.size(), 1) * sizeof(glc::HopDesc));
   DeviceGuard guard(ctx->device);
   const size_t slot = static_cast<size_t>(ch) * glc::kFrame;
   GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // a previous session may still read dec_meta
-  GLC_HIP(ctx, ctx->dec_meta.reserve(off));
-  GLC_HIP(ctx, ctx->batch_stage.reserve(off));
+  GLC_HIP(ctx, ctx->dec_meta.reserve(offs.size()));
+  GLC_HIP(ctx, ctx->batch_stage.reserve(offs.size()));
   GLC_HIP(ctx, ctx->blocks.reserve(std::max<size_t>(frames, 1) * slot * sizeof(float)));
   GLC_HIP(ctx, ctx->pcm.reserve(std::max<size_t>(n_out, 1) * sizeof(T)));
   uint8_t *img = static_cast<uint8_t *>(ctx->batch_stage.p);
@@ -1863,7 +1853,7 @@ int decode_batch_round(glc_ctx *ctx, const glc_frames *const *streams, uint64_t 
     if (!desc.empty()) std::memcpy(img + o_desc, desc.data(), desc.size() * sizeof(glc::HopDesc));
   }
   uint8_t *mb = static_cast<uint8_t *>(ctx->dec_meta.p);
-  GLC_HIP(ctx, hipMemcpyAsync(mb, img, off, hipMemcpyHostToDevice, ctx->stream));
+  GLC_HIP(ctx, hipMemcpyAsync(mb, img, offs.size(), hipMemcpyHostToDevice, ctx->stream));
   const glc::DecodeRows rows{reinterpret_cast<const uint32_t *>(mb + o_pairs),
                              reinterpret_cast<const uint64_t *>(mb + o_rows + t.h_begin),
                              reinterpret_cast<const uint32_t *>(mb + o_rows + t.h_cnt),
@@ -1891,38 +1881,22 @@ int decode_batch_impl(glc_ctx *ctx, const char *who, const glc_frames *const *in
   // a round: whole streams of together at most kDecodeChunkFrames frames (+ one tail hop each), its output
   // addressed in 32 bits
   const uint64_t hop_budget = std::min<uint64_t>(kDecodeChunkFrames + 1, 0x7FFFFFFFull / per_hop);
-  uint64_t first = 0, hops = 0;
+  const auto rounds = pack_rounds(n_streams, [&](uint64_t i) { return in[i]->n_frames; }, hop_budget, 0);
   int rc = GLC_OK;
-  auto alone = [&](uint64_t i) {  // the single-stream driver, straight into the stream's span
-    rc = decode_prepare(ctx, in[i]);
-    if (rc == GLC_OK)
-      rc = decode_prepared_to_host(ctx, pcm_out + offsets[i], offsets[i + 1] - offsets[i], nullptr, who);
-    ctx->dec_uid = 0;  // a batch decode leaves no stream resident
-    ctx->plan_uid = 0;
-  };
-  auto flush = [&](uint64_t end) {
-    if (end == first + 1 && rc == GLC_OK) {  // a stream with a round to itself shares nothing
-      alone(first);
-    } else if (end > first && rc == GLC_OK) {
+  for (size_t k = 0; k < rounds.size() && rc == GLC_OK; ++k) {
+    const uint64_t first = rounds[k].first, end = first + rounds[k].n;
+    if (end == first + 1) {  // longer than a round, or a round to itself: the single-stream driver, straight into the stream's span
+      rc = decode_prepare(ctx, in[first]);
+      if (rc == GLC_OK)
+        rc = decode_prepared_to_host(ctx, pcm_out + offsets[first], offsets[end] - offsets[first], nullptr, who);
+      ctx->dec_uid = 0;  // a batch decode leaves no stream resident
+      ctx->plan_uid = 0;
+    } else {
       std::vector<uint64_t> lens(end - first);
       for (uint64_t i = first; i < end; ++i) lens[i - first] = offsets[i + 1] - offsets[i];
       rc = decode_batch_round(ctx, in + first, end - first, ch, lens.data(), pcm_out + offsets[first]);
     }
-    first = end;
-    hops = 0;
-  };
-  for (uint64_t i = 0; i < n_streams && rc == GLC_OK; ++i) {
-    const uint64_t v = in[i]->n_frames + 1;
-    if (v > hop_budget) {  // longer than a round
-      flush(i);
-      if (rc == GLC_OK) alone(i);
-      first = i + 1;
-      continue;
-    }
-    if (hops + v > hop_budget) flush(i);
-    hops += v;
   }
-  flush(n_streams);
   return rc;
 }
 
@@ -2445,6 +2419,23 @@ int glc_roundtrip_last_info(glc_ctx *ctx, glc_roundtrip_info *out) {
 
 // ------------------------------------------------------------------------------ round trip, many clips
 
+int TableImage::begin(glc_ctx *ctx, size_t bytes) {
+  int rc = rt_reserve(ctx, ctx->rtb_tab, bytes);
+  if (rc != GLC_OK) return rc;
+  GLC_HIP(ctx, ctx->rtb_ev.ensure());
+  if (pending) GLC_HIP(ctx, hipEventSynchronize(ctx->rtb_ev));
+  pending = false;
+  GLC_HIP(ctx, ctx->rtb_stage.reserve(bytes));
+  img = static_cast<uint8_t *>(ctx->rtb_stage.p), tab = static_cast<const uint8_t *>(ctx->rtb_tab.p);
+  return GLC_OK;
+}
+int TableImage::send(glc_ctx *ctx, size_t bytes) {
+  GLC_HIP(ctx, hipMemcpyAsync(ctx->rtb_tab.p, ctx->rtb_stage.p, bytes, hipMemcpyHostToDevice, ctx->stream));
+  GLC_HIP(ctx, hipEventRecord(ctx->rtb_ev, ctx->stream));
+  pending = true;
+  return GLC_OK;
+}
+
 extern "C++" {
 namespace {
 
@@ -2504,9 +2495,7 @@ int rtb_check_fmt(glc_ctx *ctx, const std::string &w, glc_pcm_format fmt, uint32
 
 // A round of the batch round trip: clips [first, first + n) packed into one virtual stream, or (lng) ONE clip
 // longer than a round, staged whole and sent through rounds with the carried overlap.
-struct RtbRound {
-  uint64_t first = 0, n = 0, V = 0, n_real = 0;
-  bool lng = false;
+struct RtbRound : RoundSpan {
   size_t o_clips = 0, o_fmap = 0, o_desc = 0, o_span = 0;  // in the call's table image (o_span: the store encode's clip table)
   uint64_t n_desc = 0;
   uint64_t stat_off = 0;  // lng: the clip's kRowStatSlots counter pairs
@@ -2515,48 +2504,12 @@ struct RtbRound {
 // Kept hops of a clip: 512 interleaved samples of delay in front (hop 0 is cut), len * ch kept.
 inline uint64_t rtb_hops_kept(uint64_t len, uint32_t ch) { return (glc::kHop / 2 + len * ch - 1) / (uint64_t(glc::kHop) * ch) + 1; }
 
-// Rounds as in encode_batch_impl: whole clips, at most encode_chunk_frames(ch) virtual frames together; a clip of
-// more is a round of its own.
-std::vector<RtbRound> rtb_plan_rounds(const std::vector<glc_plan> &plans, uint32_t ch) {
-  const uint64_t budget = encode_chunk_frames(ch), n = plans.size();
-  std::vector<RtbRound> rounds;
-  RtbRound cur;
-  auto flush = [&](uint64_t next) {
-    if (cur.n) rounds.push_back(cur);
-    cur = RtbRound{};
-    cur.first = next;
-  };
-  for (uint64_t i = 0; i < n; ++i) {
-    const uint64_t v = plans[i].n_frames + 1;
-    if (v > budget) {
-      flush(i);
-      cur.n = 1, cur.lng = true, cur.V = v, cur.n_real = plans[i].n_frames;
-      flush(i + 1);
-      continue;
-    }
-    if (cur.V + v > budget) flush(i);
-    cur.n += 1, cur.V += v, cur.n_real += plans[i].n_frames;
-  }
-  flush(n);
+// pack_rounds (glc_rounds.hpp) into the rounds a driver keeps: R is a RoundSpan and the driver's own offsets.
+template <typename R, typename FramesOf>
+std::vector<R> plan_rounds(uint64_t n, FramesOf frames_of, uint64_t budget, uint64_t front) {
+  std::vector<R> rounds;
+  for (const RoundSpan &s : pack_rounds(n, frames_of, budget, front)) static_cast<RoundSpan &>(rounds.emplace_back()) = s;
   return rounds;
-}
-
-// The pinned image of a batch call's tables (rtb_stage -> rtb_tab).  It may still be on its way up for the call
-// before: wait for that copy (not for any kernel of that call - they are queued behind it), then size it.
-int rtb_image_begin(glc_ctx *ctx, size_t tab) {
-  int rc = rt_reserve(ctx, ctx->rtb_tab, tab);
-  if (rc != GLC_OK) return rc;
-  GLC_HIP(ctx, ctx->rtb_ev.ensure());
-  if (ctx->rtb_ev_pending) GLC_HIP(ctx, hipEventSynchronize(ctx->rtb_ev));
-  ctx->rtb_ev_pending = false;
-  GLC_HIP(ctx, ctx->rtb_stage.reserve(tab));
-  return GLC_OK;
-}
-int rtb_image_send(glc_ctx *ctx, size_t tab) {
-  GLC_HIP(ctx, hipMemcpyAsync(ctx->rtb_tab.p, ctx->rtb_stage.p, tab, hipMemcpyHostToDevice, ctx->stream));
-  GLC_HIP(ctx, hipEventRecord(ctx->rtb_ev, ctx->stream));
-  ctx->rtb_ev_pending = true;
-  return GLC_OK;
 }
 
 // What every batch call over a glc_clip_layout refuses of clip i (`clip` names the call and the clip).
@@ -2580,21 +2533,16 @@ int rtb_impl(glc_ctx *ctx, const RtbPcm &pcm, const RtbLayout &in, Out *d_out, c
   std::vector<glc_plan> plans(n);
   for (uint64_t i = 0; i < n; ++i) plans[i] = glc::plan_encode(in.len(i) * ch, static_cast<uint16_t>(ch));
 
-  std::vector<RtbRound> rounds = rtb_plan_rounds(plans, ch);
+  auto rounds = plan_rounds<RtbRound>(n, [&](uint64_t i) { return plans[i].n_frames; }, encode_chunk_frames(ch), 0);
   // the call's tables, and what the workspaces have to hold
-  size_t tab = 0;
-  auto place = [&](size_t bytes) {
-    const size_t at = tab;
-    tab = align_up(tab + bytes, 256);
-    return at;
-  };
+  TableOffsets offs;
   const uint64_t clip_stat = uint64_t(glc::kClipStatSlots) * glc::kRowStatStride;  // uint64_t per clip
   uint64_t stat_words = n * clip_stat;
   uint64_t max_vs = 0, max_recs = 0, max_rows = 0, max_blocks = 0, max_frames = 0, max_coef_rows = 0;
   for (RtbRound &r : rounds) {
-    r.o_clips = place(r.n * sizeof(glc::StageClip));
+    r.o_clips = offs.take(r.n * sizeof(glc::StageClip));
     for (uint64_t i = r.first; i < r.first + r.n; ++i) r.n_desc += rtb_hops_kept(in.len(i), ch);
-    r.o_desc = place(r.n_desc * sizeof(glc::HopDescStrided));
+    r.o_desc = offs.take(r.n_desc * sizeof(glc::HopDescStrided));
     max_vs = std::max(max_vs, r.V * per_hop);
     if (r.lng) {
       const uint64_t rf = std::min<uint64_t>(kDecodeChunkFrames, r.n_real);
@@ -2603,7 +2551,7 @@ int rtb_impl(glc_ctx *ctx, const RtbPcm &pcm, const RtbLayout &in, Out *d_out, c
       max_recs = std::max(max_recs, rf), max_rows = std::max(max_rows, rf * ch), max_blocks = std::max(max_blocks, rf + 1);
       max_frames = std::max(max_frames, rf), max_coef_rows = std::max(max_coef_rows, rf * ch);
     } else {
-      r.o_fmap = place(r.n_real * sizeof(glc::FrameMap));
+      r.o_fmap = offs.take(r.n_real * sizeof(glc::FrameMap));
       max_recs = std::max(max_recs, r.V), max_rows = std::max(max_rows, r.n_real * ch), max_blocks = std::max(max_blocks, r.n_real);
       max_frames = std::max(max_frames, r.n_real), max_coef_rows = std::max(max_coef_rows, r.V * ch);
     }
@@ -2617,15 +2565,14 @@ int rtb_impl(glc_ctx *ctx, const RtbPcm &pcm, const RtbLayout &in, Out *d_out, c
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->blocks, max_blocks * slot * sizeof(float));
   if (rc == GLC_OK) rc = reserve_d1_plan(ctx, max_frames, ch);
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rtb_stats, stat_words * sizeof(uint64_t));
-  if (rc == GLC_OK) rc = rtb_image_begin(ctx, tab);
+  TableImage &image = ctx->rtb_image;
+  if (rc == GLC_OK) rc = image.begin(ctx, offs.size());
   if (rc != GLC_OK) return rc;
-  uint8_t *img = static_cast<uint8_t *>(ctx->rtb_stage.p);
-  uint8_t *d_tab = static_cast<uint8_t *>(ctx->rtb_tab.p);
   const bool out_planes = out.planes();
   for (const RtbRound &r : rounds) {
-    auto *clips = reinterpret_cast<glc::StageClip *>(img + r.o_clips);
-    auto *desc = reinterpret_cast<glc::HopDescStrided *>(img + r.o_desc);
-    auto *fmap = reinterpret_cast<glc::FrameMap *>(img + r.o_fmap);
+    auto *clips = image.host<glc::StageClip>(r.o_clips);
+    auto *desc = image.host<glc::HopDescStrided>(r.o_desc);
+    auto *fmap = image.host<glc::FrameMap>(r.o_fmap);
     uint64_t vslot = 0, real = 0;
     for (uint64_t k = 0; k < r.n; ++k) {
       const uint64_t i = r.first + k, nf = plans[i].n_frames;
@@ -2638,11 +2585,11 @@ int rtb_impl(glc_ctx *ctx, const RtbPcm &pcm, const RtbLayout &in, Out *d_out, c
       vslot += nf + 1;
       real += nf;
     }
-    if (static_cast<uint64_t>(desc - reinterpret_cast<glc::HopDescStrided *>(img + r.o_desc)) != r.n_desc)
+    if (static_cast<uint64_t>(desc - image.host<glc::HopDescStrided>(r.o_desc)) != r.n_desc)
       return fail(ctx, GLC_EHIP, "glc_roundtrip_batch_device: hop count arithmetic is inconsistent");
   }
   hipStream_t st = ctx->stream;
-  rc = rtb_image_send(ctx, tab);
+  rc = image.send(ctx, offs.size());
   if (rc != GLC_OK) return rc;
   uint64_t *d_stats = static_cast<uint64_t *>(ctx->rtb_stats.p);
   GLC_HIP(ctx, hipMemsetAsync(d_stats, 0, stat_words * sizeof(uint64_t), st));
@@ -2651,9 +2598,8 @@ int rtb_impl(glc_ctx *ctx, const RtbPcm &pcm, const RtbLayout &in, Out *d_out, c
   float *blocks = static_cast<float *>(ctx->blocks.p);
   const uint8_t *recs = static_cast<const uint8_t *>(ctx->rt_records.p);
   for (const RtbRound &r : rounds) {
-    const auto *clips = reinterpret_cast<const glc::StageClip *>(d_tab + r.o_clips);
-    const auto *desc = reinterpret_cast<const glc::HopDescStrided *>(d_tab + r.o_desc);
-    rc = rtb_stage(ctx, pcm, clips, r.n, ch, in, r.V, vs, st);
+    const auto *desc = image.dev<glc::HopDescStrided>(r.o_desc);
+    rc = rtb_stage(ctx, pcm, image.dev<glc::StageClip>(r.o_clips), r.n, ch, in, r.V, vs, st);
     if (rc != GLC_OK) return rc;
     if (r.lng) {
       const uint64_t i = r.first, n_samples = in.len(i) * ch;
@@ -2675,8 +2621,7 @@ int rtb_impl(glc_ctx *ctx, const RtbPcm &pcm, const RtbLayout &in, Out *d_out, c
     if (rc != GLC_OK) return rc;
     const uint32_t M = static_cast<uint32_t>(r.n_real * ch);
     glc::DecodeRows rows{};
-    GLC_HIP(ctx, glc::launch_rows_from_records_batch(recs, M, ch, reinterpret_cast<const glc::FrameMap *>(d_tab + r.o_fmap),
-                                                     ctx->rt_rows.p, d_stats, st, &rows));
+    GLC_HIP(ctx, glc::launch_rows_from_records_batch(recs, M, ch, image.dev<glc::FrameMap>(r.o_fmap), ctx->rt_rows.p, d_stats, st, &rows));
     // (D1's 8-frame units may span two clips: that only widens a union)
     GLC_HIP(ctx, glc::launch_imdct_rows(ctx->dev, rows, 0, M, ch, blocks, st, ctx->d1_variant, ctx->dec_plan.p,
                                         ctx->dec_plan.p ? ctx->dec_plan_groups : 0, false));
@@ -2817,9 +2762,7 @@ int cd_decode_one(glc_ctx *ctx, const RtGeom &g, const void *d_blob, uint64_t bl
 
 // A round of glc_decode_batch_device_compact: blobs [first, first + n) with together n_real frames, or (lng) ONE
 // blob of more frames than a round.
-struct CdRound {
-  uint64_t first = 0, n = 0, n_real = 0;
-  bool lng = false;
+struct CdRound : RoundSpan {
   size_t o_dir = 0, o_desc = 0;  // in the call's table image
   uint64_t n_desc = 0;
 };
@@ -2833,42 +2776,14 @@ int cdb_impl(glc_ctx *ctx, const char *who, const void *const *d_blobs, const ui
   auto frames_of = [&](uint64_t i) { return wins ? wins[i].n_frames : plans[i].n_frames; };
   const uint32_t ch = out.l->channels;
   const size_t slot = static_cast<size_t>(ch) * glc::kFrame;
-  // rounds as glc_decode_batch packs them: whole clips of together at most kDecodeChunkFrames frames (+ a tail hop each)
-  const uint64_t hop_budget = kDecodeChunkFrames + 1;
-  std::vector<CdRound> rounds;
-  {
-    CdRound cur;
-    uint64_t hops = 0;
-    auto flush = [&](uint64_t next) {
-      if (cur.n) rounds.push_back(cur);
-      cur = CdRound{};
-      cur.first = next;
-      hops = 0;
-    };
-    for (uint64_t i = 0; i < n; ++i) {
-      const uint64_t v = frames_of(i) + 1;
-      if (v > hop_budget) {
-        flush(i);
-        cur.n = 1, cur.lng = true, cur.n_real = frames_of(i);
-        flush(i + 1);
-        continue;
-      }
-      if (hops + v > hop_budget) flush(i);
-      cur.n += 1, cur.n_real += frames_of(i), hops += v;
-    }
-    flush(n);
-  }
-  size_t tab = 0;
-  auto place = [&](size_t bytes) {
-    const size_t at = tab;
-    tab = align_up(tab + bytes, 256);
-    return at;
-  };
+  // whole clips of together at most kDecodeChunkFrames frames (+ a tail hop each)
+  auto rounds = plan_rounds<CdRound>(n, frames_of, kDecodeChunkFrames + 1, 0);
+  TableOffsets offs;
   uint64_t max_rows = 0, max_blocks = 0, max_frames = 0;
   for (CdRound &r : rounds) {
-    if (!r.lng) r.o_dir = place(r.n * sizeof(glc::CompactBlob));
+    if (!r.lng) r.o_dir = offs.take(r.n * sizeof(glc::CompactBlob));
     for (uint64_t i = r.first; i < r.first + r.n; ++i) r.n_desc += wins ? wins[i].n_hops : rtb_hops_kept(out.len(i), ch);
-    r.o_desc = place(r.n_desc * sizeof(glc::HopDescStrided));
+    r.o_desc = offs.take(r.n_desc * sizeof(glc::HopDescStrided));
     const uint64_t rf = r.lng ? std::min<uint64_t>(kDecodeChunkFrames, r.n_real) : r.n_real;
     max_rows = std::max(max_rows, r.n_real * ch);  // R2 takes a long clip's (or window's) rows in one pass
     max_blocks = std::max(max_blocks, rf + (r.lng ? 1 : 0));
@@ -2880,16 +2795,10 @@ int cdb_impl(glc_ctx *ctx, const char *who, const void *const *d_blobs, const ui
                                               : glc::rows_from_compact_bytes(static_cast<uint32_t>(max_rows)));
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->blocks, max_blocks * slot * sizeof(float));
   if (rc == GLC_OK) rc = reserve_d1_plan(ctx, max_frames, ch);
-  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rtb_tab, tab);
+  TableImage &image = ctx->rtb_image;
+  if (rc == GLC_OK) rc = image.begin(ctx, offs.size());
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->cd_status, n * sizeof(glc::CompactStatus));
   if (rc != GLC_OK) return rc;
-  GLC_HIP(ctx, ctx->rtb_ev.ensure());
-  // the pinned image is shared with glc_roundtrip_batch_device: wait until the last upload has left it
-  if (ctx->rtb_ev_pending) GLC_HIP(ctx, hipEventSynchronize(ctx->rtb_ev));
-  ctx->rtb_ev_pending = false;
-  GLC_HIP(ctx, ctx->rtb_stage.reserve(tab));
-  uint8_t *img = static_cast<uint8_t *>(ctx->rtb_stage.p);
-  uint8_t *d_tab = static_cast<uint8_t *>(ctx->rtb_tab.p);
   const bool out_planes = out.planes();
   // what entry i keeps of its un-trimmed stream: the clip, or the crop behind the delay
   auto trim_of = [&](uint64_t i) {
@@ -2897,8 +2806,8 @@ int cdb_impl(glc_ctx *ctx, const char *who, const void *const *d_blobs, const ui
     return crops ? glc::Trim{whole.start + crops[i].start * ch, crops[i].length * ch} : whole;
   };
   for (const CdRound &r : rounds) {
-    auto *dir = reinterpret_cast<glc::CompactBlob *>(img + r.o_dir);
-    auto *desc = reinterpret_cast<glc::HopDescStrided *>(img + r.o_desc);
+    auto *dir = image.host<glc::CompactBlob>(r.o_dir);
+    auto *desc = image.host<glc::HopDescStrided>(r.o_desc);
     uint64_t real = 0;
     for (uint64_t k = 0; k < r.n; ++k) {
       const uint64_t i = r.first + k, nf = plans[i].n_frames;
@@ -2909,17 +2818,16 @@ int cdb_impl(glc_ctx *ctx, const char *who, const void *const *d_blobs, const ui
       desc = write_clip_descs(desc, r.lng, nf, ch, trim_of(i), real, out.at(i), out_planes, out.l->channel_stride, wins ? &wins[i] : nullptr);
       real += frames_of(i);
     }
-    if (static_cast<uint64_t>(desc - reinterpret_cast<glc::HopDescStrided *>(img + r.o_desc)) != r.n_desc)
+    if (static_cast<uint64_t>(desc - image.host<glc::HopDescStrided>(r.o_desc)) != r.n_desc)
       return fail(ctx, GLC_EHIP, std::string(who) + ": hop count arithmetic is inconsistent");
   }
   hipStream_t st = ctx->stream;
-  GLC_HIP(ctx, hipMemcpyAsync(d_tab, img, tab, hipMemcpyHostToDevice, st));
-  GLC_HIP(ctx, hipEventRecord(ctx->rtb_ev, st));
-  ctx->rtb_ev_pending = true;
+  rc = image.send(ctx, offs.size());
+  if (rc != GLC_OK) return rc;
   auto *d_status = static_cast<glc::CompactStatus *>(ctx->cd_status.p);
   float *blocks = static_cast<float *>(ctx->blocks.p);
   for (const CdRound &r : rounds) {
-    const auto *desc = reinterpret_cast<const glc::HopDescStrided *>(d_tab + r.o_desc);
+    const auto *desc = image.dev<glc::HopDescStrided>(r.o_desc);
     if (r.lng) {
       const uint64_t i = r.first;
       RtGeom g = rt_geom(plans[i].n_frames, ch, plans[i], out.len(i) * ch);
@@ -2934,7 +2842,7 @@ int cdb_impl(glc_ctx *ctx, const char *who, const void *const *d_blobs, const ui
     for (uint64_t i = r.first; i < r.first + r.n; ++i) base = std::min(base, reinterpret_cast<uintptr_t>(d_blobs[i]));
     const uint32_t M = static_cast<uint32_t>(r.n_real * ch);
     glc::DecodeRows rows{};
-    const auto *d_dir = reinterpret_cast<const glc::CompactBlob *>(d_tab + r.o_dir);
+    const auto *d_dir = image.dev<glc::CompactBlob>(r.o_dir);
     if (wins) {
       uint64_t front = 0;  // the most rows any window of the round has in front
       for (uint64_t i = r.first; i < r.first + r.n; ++i) front = std::max(front, wins[i].first_frame * ch);
@@ -3130,16 +3038,11 @@ int sd_check(glc_ctx *ctx, const std::string &w, const void *d_arena, uint64_t a
   if (overlaps(d_entries, n_entries * sizeof(glc_store_entry)) || overlaps(d_lengths, n_entries * 8) || overlaps(d_clips, n * 8) ||
       overlaps(d_starts, n * 8))
     return fail(ctx, GLC_EINVAL, w + ": the output extent overlaps an index array");
-  size_t tab = 0;
-  auto place = [&](size_t bytes) {
-    const size_t at = tab;
-    tab = align_up(tab + bytes, 256);
-    return at;
-  };
-  g->o_dir = place(n * sizeof(glc::CompactBlob));
-  g->o_desc = place(n * g->slots.max_hops * sizeof(glc::HopDescStrided));
-  g->o_verdict = place(n * sizeof(uint32_t));
-  g->tab = tab;
+  TableOffsets offs;
+  g->o_dir = offs.take(n * sizeof(glc::CompactBlob));
+  g->o_desc = offs.take(n * g->slots.max_hops * sizeof(glc::HopDescStrided));
+  g->o_verdict = offs.take(n * sizeof(uint32_t));
+  g->tab = offs.size();
   return GLC_OK;
 }
 
@@ -3373,12 +3276,11 @@ void store_round_tables(const uint64_t *frames, uint64_t n, bool junk, glc::Fram
 }
 
 // A1-A3 of one round, as the driver and the hook queue them: the round's tables are on the device already.
-int store_round_launch(glc_ctx *ctx, const void *d_records, uint64_t n_real, uint64_t n_clips, uint32_t ch, const uint8_t *d_tab,
+int store_round_launch(glc_ctx *ctx, const void *d_records, uint64_t n_real, uint64_t n_clips, uint32_t ch, const TableImage &image,
                        size_t o_fmap, size_t o_span, void *d_arena, uint64_t arena_bytes, uint64_t *d_cursor,
                        glc_store_entry *d_entries, hipStream_t st) {
   GLC_HIP(ctx, glc::launch_compact_store(static_cast<const uint8_t *>(d_records), static_cast<uint32_t>(n_real * ch), ch,
-                                         reinterpret_cast<const glc::FrameMap *>(d_tab + o_fmap),
-                                         reinterpret_cast<const glc::ClipSpan *>(d_tab + o_span), static_cast<uint32_t>(n_clips),
+                                         image.dev<glc::FrameMap>(o_fmap), image.dev<glc::ClipSpan>(o_span), static_cast<uint32_t>(n_clips),
                                          ctx->pack_meta.p, static_cast<uint8_t *>(d_arena), arena_bytes, d_cursor, d_entries, st));
   return GLC_OK;
 }
@@ -3390,18 +3292,13 @@ int ebc_impl(glc_ctx *ctx, const RtbPcm &pcm, const RtbLayout &in, void *d_arena
   const uint64_t per_hop = uint64_t(glc::kHop) * ch, rec = glc::record_bytes(ch);
   std::vector<glc_plan> plans(n);
   for (uint64_t i = 0; i < n; ++i) plans[i] = glc::plan_encode(in.len(i) * ch, static_cast<uint16_t>(ch));
-  std::vector<RtbRound> rounds = rtb_plan_rounds(plans, ch);
-  size_t tab = 0;
-  auto place = [&](size_t bytes) {
-    const size_t at = tab;
-    tab = align_up(tab + bytes, 256);
-    return at;
-  };
+  auto rounds = plan_rounds<RtbRound>(n, [&](uint64_t i) { return plans[i].n_frames; }, encode_chunk_frames(ch), 0);
+  TableOffsets offs;
   uint64_t max_vs = 0, max_recs = 0, max_coef_rows = 0, max_scratch = 0;
   for (RtbRound &r : rounds) {
-    r.o_clips = place(r.n * sizeof(glc::StageClip));
-    r.o_fmap = place(r.n_real * sizeof(glc::FrameMap));
-    r.o_span = place(r.n * sizeof(glc::ClipSpan));
+    r.o_clips = offs.take(r.n * sizeof(glc::StageClip));
+    r.o_fmap = offs.take(r.n_real * sizeof(glc::FrameMap));
+    r.o_span = offs.take(r.n * sizeof(glc::ClipSpan));
     max_vs = std::max(max_vs, r.V * per_hop);
     // a long clip's records are all held at once (the pack scans the whole clip); its transform goes in chunks
     max_recs = std::max(max_recs, r.lng ? r.n_real : r.V);
@@ -3413,13 +3310,12 @@ int ebc_impl(glc_ctx *ctx, const RtbPcm &pcm, const RtbLayout &in, void *d_arena
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rt_records, max_recs * rec);
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->coef, max_coef_rows * glc::kHop * sizeof(float));
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->pack_meta, max_scratch);
-  if (rc == GLC_OK) rc = rtb_image_begin(ctx, tab);
+  TableImage &image = ctx->rtb_image;
+  if (rc == GLC_OK) rc = image.begin(ctx, offs.size());
   if (rc != GLC_OK) return rc;
-  uint8_t *img = static_cast<uint8_t *>(ctx->rtb_stage.p);
-  const uint8_t *d_tab = static_cast<const uint8_t *>(ctx->rtb_tab.p);
   std::vector<uint64_t> frames;
   for (const RtbRound &r : rounds) {
-    auto *clips = reinterpret_cast<glc::StageClip *>(img + r.o_clips);
+    auto *clips = image.host<glc::StageClip>(r.o_clips);
     frames.resize(r.n);
     uint64_t vslot = 0;
     for (uint64_t k = 0; k < r.n; ++k) {
@@ -3429,15 +3325,14 @@ int ebc_impl(glc_ctx *ctx, const RtbPcm &pcm, const RtbLayout &in, void *d_arena
       vslot += frames[k] + 1;
     }
     // a long clip is encoded as a stream of its own: its records are its frames, no junk one among them
-    store_round_tables(frames.data(), r.n, !r.lng, reinterpret_cast<glc::FrameMap *>(img + r.o_fmap),
-                       reinterpret_cast<glc::ClipSpan *>(img + r.o_span));
+    store_round_tables(frames.data(), r.n, !r.lng, image.host<glc::FrameMap>(r.o_fmap), image.host<glc::ClipSpan>(r.o_span));
   }
   hipStream_t st = ctx->stream;
-  rc = rtb_image_send(ctx, tab);
+  rc = image.send(ctx, offs.size());
   if (rc != GLC_OK) return rc;
   float *vs = static_cast<float *>(ctx->rtb_vs.p);
   for (const RtbRound &r : rounds) {
-    rc = rtb_stage(ctx, pcm, reinterpret_cast<const glc::StageClip *>(d_tab + r.o_clips), r.n, ch, in, r.V, vs, st);
+    rc = rtb_stage(ctx, pcm, image.dev<glc::StageClip>(r.o_clips), r.n, ch, in, r.V, vs, st);
     if (rc != GLC_OK) return rc;
     if (r.lng) {
       const uint64_t len = in.len(r.first);
@@ -3447,7 +3342,7 @@ int ebc_impl(glc_ctx *ctx, const RtbPcm &pcm, const RtbLayout &in, void *d_arena
       rc = encode_range_on(ctx, st, EncodeRange{{vs, 0, T, T * ch, static_cast<uint32_t>(ch)}, 0, r.V, ctx->rt_records.p, nullptr, &ctx->slot[0]});
     }
     if (rc == GLC_OK)
-      rc = store_round_launch(ctx, ctx->rt_records.p, r.n_real, r.n, ch, d_tab, r.o_fmap, r.o_span, d_arena, arena_bytes, d_cursor,
+      rc = store_round_launch(ctx, ctx->rt_records.p, r.n_real, r.n, ch, image, r.o_fmap, r.o_span, d_arena, arena_bytes, d_cursor,
                               d_entries + r.first, st);
     if (rc != GLC_OK) return rc;
   }
@@ -3519,15 +3414,15 @@ int glc_debug_compact_store_device(glc_ctx *ctx, const void *d_records, const ui
   DeviceGuard guard(ctx->device);
   try {
     const size_t o_fmap = 0, o_span = align_up(n_real * sizeof(glc::FrameMap), 256), tab = o_span + n_clips * sizeof(glc::ClipSpan);
+    TableImage &image = ctx->rtb_image;
     int rc = rt_reserve(ctx, ctx->pack_meta, glc::compact_store_scratch_bytes(n_real * channels, n_clips));
-    if (rc == GLC_OK) rc = rtb_image_begin(ctx, tab);
+    if (rc == GLC_OK) rc = image.begin(ctx, tab);
     if (rc != GLC_OK) return rc;
-    uint8_t *img = static_cast<uint8_t *>(ctx->rtb_stage.p);
-    store_round_tables(clip_frames, n_clips, true, reinterpret_cast<glc::FrameMap *>(img + o_fmap), reinterpret_cast<glc::ClipSpan *>(img + o_span));
-    rc = rtb_image_send(ctx, tab);
+    store_round_tables(clip_frames, n_clips, true, image.host<glc::FrameMap>(o_fmap), image.host<glc::ClipSpan>(o_span));
+    rc = image.send(ctx, tab);
     if (rc != GLC_OK) return rc;
-    return store_round_launch(ctx, d_records, n_real, n_clips, channels, static_cast<const uint8_t *>(ctx->rtb_tab.p), o_fmap, o_span,
-                              d_arena, arena_bytes, d_cursor, d_entries, ctx->stream);
+    return store_round_launch(ctx, d_records, n_real, n_clips, channels, image, o_fmap, o_span, d_arena, arena_bytes, d_cursor, d_entries,
+                              ctx->stream);
   } catch (const std::bad_alloc &) {
     return fail(ctx, GLC_ENOMEM, w + ": host allocation failed");
   }
@@ -3591,18 +3486,16 @@ int stream_push_core(glc_stream_enc *s, const RtbPcm &pcm, const RtbLayout &in, 
     if (!a.finish && a.n_new) keep.push_back(&a);
   }
   // rounds: a virtual slot in front (its second half is the first segment's lookback), frames + 1 slots per segment
-  struct Round {
-    uint64_t first, n, V, n_real;
-    size_t o_spans, o_fmap, o_span;
-    uint64_t n_spans;
+  struct Round : RoundSpan {
+    size_t o_spans = 0, o_fmap = 0, o_span = 0;
+    uint64_t n_spans = 0;
   };
-  std::vector<Round> rounds;
-  for (uint64_t k = 0; k < seg.size(); ++k) {
-    const uint64_t v = seg[k]->plan.n_frames + 1;
-    if (rounds.empty() || rounds.back().V + v > budget) rounds.push_back(Round{k, 0, 1, 0, 0, 0, 0, 0});
-    rounds.back().n += 1, rounds.back().V += v, rounds.back().n_real += seg[k]->plan.n_frames;
-  }
-  if (rounds.empty() && !keep.empty()) rounds.push_back(Round{0, 0, 0, 0, 0, 0, 0, 0});  // the stager alone
+  auto rounds = plan_rounds<Round>(seg.size(), [&](uint64_t k) { return seg[k]->plan.n_frames; }, budget, 1);
+  // no segment is a round of its own: glc_stream_enc_max_push bounds a chunk so that the frames it completes, their
+  // junk slot and the slot in front fit a round
+  for (const Round &R : rounds)
+    if (R.lng) return fail(ctx, GLC_EHIP, "glc_stream_enc_push: internal: a segment does not fit a round");
+  if (rounds.empty() && !keep.empty()) rounds.emplace_back();  // the stager alone: no slot at all
   *n_segs = seg.size();
   for (uint64_t k = 0; k < seg.size(); ++k) segs[k] = glc_stream_seg{seg[k]->lane, seg[k]->plan.first_frame, seg[k]->plan.n_frames};
   rt_forget_streams(ctx);
@@ -3622,19 +3515,14 @@ int stream_push_core(glc_stream_enc *s, const RtbPcm &pcm, const RtbLayout &in, 
     commit();
     return GLC_OK;
   }
-  size_t tab = 0;
-  auto place = [&](size_t bytes) {
-    const size_t at = tab;
-    tab = align_up(tab + bytes, 256);
-    return at;
-  };
+  TableOffsets offs;
   uint64_t max_V = 0, max_scratch = 0;
   for (size_t r = 0; r < rounds.size(); ++r) {
     Round &R = rounds[r];
     R.n_spans = R.n + (r == 0 ? keep.size() : 0);
-    R.o_spans = place(R.n_spans * sizeof(glc::StreamSpan));
-    R.o_fmap = place(R.n_real * sizeof(glc::FrameMap));
-    R.o_span = place(R.n * sizeof(glc::ClipSpan));
+    R.o_spans = offs.take(R.n_spans * sizeof(glc::StreamSpan));
+    R.o_fmap = offs.take(R.n_real * sizeof(glc::FrameMap));
+    R.o_span = offs.take(R.n * sizeof(glc::ClipSpan));
     max_V = std::max(max_V, R.V);
     if (R.n) max_scratch = std::max(max_scratch, glc::compact_store_scratch_bytes(R.n_real * ch, R.n));
   }
@@ -3642,10 +3530,9 @@ int stream_push_core(glc_stream_enc *s, const RtbPcm &pcm, const RtbLayout &in, 
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rt_records, max_V * rec);
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->coef, max_V * ch * glc::kHop * sizeof(float));
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->pack_meta, max_scratch);
-  if (rc == GLC_OK) rc = rtb_image_begin(ctx, tab);
+  TableImage &image = ctx->rtb_image;
+  if (rc == GLC_OK) rc = image.begin(ctx, offs.size());
   if (rc != GLC_OK) return rc;
-  uint8_t *img = static_cast<uint8_t *>(ctx->rtb_stage.p);
-  const uint8_t *d_tab = static_cast<const uint8_t *>(ctx->rtb_tab.p);
   auto span_of = [&](const StreamLanePush &a) {
     const StreamLane &L = s->lanes[a.lane];
     glc::StreamSpan sp{};
@@ -3657,7 +3544,7 @@ int stream_push_core(glc_stream_enc *s, const RtbPcm &pcm, const RtbLayout &in, 
   std::vector<uint64_t> frames;
   for (size_t r = 0; r < rounds.size(); ++r) {
     const Round &R = rounds[r];
-    auto *spans = reinterpret_cast<glc::StreamSpan *>(img + R.o_spans);
+    auto *spans = image.host<glc::StreamSpan>(R.o_spans);
     frames.resize(R.n);
     uint64_t slot = 1;
     for (uint64_t k = 0; k < R.n; ++k) {
@@ -3677,18 +3564,15 @@ int stream_push_core(glc_stream_enc *s, const RtbPcm &pcm, const RtbLayout &in, 
         sp.unit = static_cast<uint32_t>(2 * R.V + 4 * q);
         spans[R.n + q] = sp;
       }
-    if (R.n)
-      store_round_tables(frames.data(), R.n, true, reinterpret_cast<glc::FrameMap *>(img + R.o_fmap),
-                         reinterpret_cast<glc::ClipSpan *>(img + R.o_span));
+    if (R.n) store_round_tables(frames.data(), R.n, true, image.host<glc::FrameMap>(R.o_fmap), image.host<glc::ClipSpan>(R.o_span));
   }
   hipStream_t st = ctx->stream;
-  rc = rtb_image_send(ctx, tab);
+  rc = image.send(ctx, offs.size());
   if (rc != GLC_OK) return rc;
   float *vs = static_cast<float *>(ctx->rtb_vs.p);
   for (size_t r = 0; r < rounds.size(); ++r) {
     const Round &R = rounds[r];
-    GLC_HIP(ctx, glc::launch_stage_segments(pcm.p, pcm.fmt, pcm.bits, reinterpret_cast<const glc::StreamSpan *>(d_tab + R.o_spans),
-                                            static_cast<uint32_t>(R.n_spans), static_cast<uint32_t>(2 * R.V),
+    GLC_HIP(ctx, glc::launch_stage_segments(pcm.p, pcm.fmt, pcm.bits, image.dev<glc::StreamSpan>(R.o_spans), static_cast<uint32_t>(R.n_spans), static_cast<uint32_t>(2 * R.V),
                                             static_cast<uint32_t>(r == 0 ? 4 * keep.size() : 0), ch, in.planes(), in.l->channel_stride,
                                             static_cast<float *>(s->held.p), vs, st));
     if (!R.n) continue;
@@ -3697,7 +3581,7 @@ int stream_push_core(glc_stream_enc *s, const RtbPcm &pcm, const RtbLayout &in, 
     const uint64_t T = R.V * glc::kHop;
     rc = encode_range_on(ctx, st, EncodeRange{{vs, 0, T, T * ch, static_cast<uint32_t>(ch)}, 1, R.V - 1, ctx->rt_records.p, nullptr, &ctx->slot[0]});
     if (rc == GLC_OK)
-      rc = store_round_launch(ctx, ctx->rt_records.p, R.n_real, R.n, ch, d_tab, R.o_fmap, R.o_span, d_arena, arena_bytes, d_cursor,
+      rc = store_round_launch(ctx, ctx->rt_records.p, R.n_real, R.n, ch, image, R.o_fmap, R.o_span, d_arena, arena_bytes, d_cursor,
                               d_entries + R.first, st);
     if (rc != GLC_OK) return rc;
   }

@@ -1,0 +1,52 @@
+// glc_rounds.hpp — how the batch, store and stream drivers of glc_api.hip cut a call into rounds, and where the tables
+// of a call lie in its image.  Plain C++17 without a HIP type: a host program can include it alone
+// (tools/round_plan_check.cpp).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+// Items [first, first + n) of a call, sent through one launch chain.  n_real: their frames.  V: the slots of the
+// round's virtual stream - `front` + frames + 1 per item - or, of a long round, the item's frames + 1.
+struct RoundSpan {
+  uint64_t first = 0, n = 0, n_real = 0, V = 0;
+  bool lng = false;  // ONE item that is more than a round: its driver sends it down the single-stream path
+};
+
+// THE round rule.  Whole items in order, frames_of(i) + 1 slots each - the one more is the junk
+// frame that straddles two clips, or the tail hop of a decode - behind `front` slots that every round spends before its
+// first item, at most `budget` slots together.  Greedy: an item joins the open round unless that would pass the budget,
+// which closes the round first.  An item that does not fit a round of its own closes the open round and is a round to
+// itself, flagged `lng`: the items around it are never merged across it.  No round is empty.
+template <typename FramesOf>
+std::vector<RoundSpan> pack_rounds(uint64_t n, FramesOf frames_of, uint64_t budget, uint64_t front) {
+  std::vector<RoundSpan> rounds;
+  RoundSpan cur{0, 0, 0, front, false};
+  auto close = [&](uint64_t next) {
+    if (cur.n) rounds.push_back(cur);
+    cur = RoundSpan{next, 0, 0, front, false};
+  };
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint64_t frames = frames_of(i), cost = frames + 1;
+    if (front + cost > budget) {
+      close(i + 1);
+      rounds.push_back(RoundSpan{i, 1, frames, cost, true});
+      continue;
+    }
+    if (cur.V + cost > budget) close(i);
+    cur.n += 1, cur.n_real += frames, cur.V += cost;
+  }
+  close(n);
+  return rounds;
+}
+
+// Where the tables of an image lie: every table starts on a multiple of 256 bytes, in the order it was taken.
+struct TableOffsets {
+  size_t end = 0;
+  size_t take(size_t bytes) {
+    const size_t at = end;
+    end = (end + bytes + 255) / 256 * 256;
+    return at;
+  }
+  size_t size() const { return end; }  // of the image: the aligned end of the last table
+};

@@ -1,0 +1,156 @@
+// round_plan_check.cpp - the round rule and the table offsets of the batch, store and stream drivers
+// (csrc/glc_rounds.hpp) on the host alone.  The greedy rule makes the rounds of a list unique, so the properties below
+// pin pack_rounds without a second copy of its loop; tests/test_round_boundaries.py pins on the device that every
+// driver sizes and addresses what it returns.  Plain C++, no HIP header: built by tests/test_round_plan.py with
+//   g++ -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -Wall -Werror tools/round_plan_check.cpp
+// Exit status 0 and the line "round plan ok": every check held.
+#include <cstdio>
+#include <initializer_list>
+
+#include "../gapless-lossy-codec_amd/csrc/glc_rounds.hpp"
+
+static int g_failed = 0;
+#define CHECK(cond)                                                                                       \
+  do {                                                                                                    \
+    if (!(cond)) {                                                                                        \
+      if (++g_failed <= 20) std::printf("line %d (%s): %s does not hold\n", __LINE__, g_what, #cond);      \
+    }                                                                                                     \
+  } while (0)
+static char g_what[96] = "";
+
+using Frames = std::vector<uint64_t>;
+
+static std::vector<RoundSpan> pack(const Frames &f, uint64_t budget, uint64_t front) {
+  return pack_rounds(f.size(), [&](uint64_t i) { return f[i]; }, budget, front);
+}
+
+// Every property the drivers rely on, of the rounds of one list.
+static void check_rounds(const Frames &f, uint64_t budget, uint64_t front) {
+  const std::vector<RoundSpan> rounds = pack(f, budget, front);
+  uint64_t next = 0;  // every item in exactly one round: the rounds are contiguous, in item order, and end at n
+  for (size_t j = 0; j < rounds.size(); ++j) {
+    const RoundSpan &r = rounds[j];
+    CHECK(r.first == next);
+    CHECK(r.n >= 1);
+    CHECK(r.first + r.n <= f.size());
+    if (r.n < 1 || r.first + r.n > f.size()) return;
+    next = r.first + r.n;
+    uint64_t real = 0, slots = 0;
+    for (uint64_t i = r.first; i < next; ++i) real += f[i], slots += f[i] + 1;
+    CHECK(r.n_real == real);
+    const bool alone_too_long = r.n == 1 && front + f[r.first] + 1 > budget;
+    CHECK(r.lng == alone_too_long);
+    if (r.lng) {
+      CHECK(r.V == slots);
+    } else {
+      CHECK(r.V == front + slots);
+      CHECK(front + slots <= budget);
+      // greedy: the round before, where it is a packed one, had no room for this round's first item
+      if (j > 0 && !rounds[j - 1].lng) CHECK(rounds[j - 1].V + f[r.first] + 1 > budget);
+    }
+  }
+  CHECK(next == f.size());
+}
+
+static uint64_t g_rng = 0x9E3779B97F4A7C15ull;  // fixed seed: the same lists in every run
+static uint64_t rnd(uint64_t below) {
+  g_rng = g_rng * 6364136223846793005ull + 1442695040888963407ull;
+  return below ? (g_rng >> 33) % below : 0;
+}
+
+static size_t count_lng(const std::vector<RoundSpan> &rounds) {
+  size_t n = 0;
+  for (const RoundSpan &r : rounds) n += r.lng ? 1 : 0;
+  return n;
+}
+
+int main() {
+  const struct {
+    uint64_t budget, front;
+  } cases[] = {{4096, 0}, {8192, 0}, {4097, 0}, {4096, 1}, {5, 0}, {5, 1}, {2, 0}};
+  for (const auto &c : cases) {
+    const uint64_t B = c.budget, F = c.front;
+    std::snprintf(g_what, sizeof g_what, "budget %llu, front %llu", (unsigned long long)B, (unsigned long long)F);
+    const uint64_t fits = B - F - 1;  // the most frames of an item that is not a round of its own
+    // hand-written lists
+    CHECK(pack({}, B, F).empty());
+    {
+      const auto r = pack({fits}, B, F);
+      CHECK(r.size() == 1 && !r[0].lng && r[0].V == B && r[0].n_real == fits);
+      check_rounds({fits}, B, F);
+    }
+    {
+      const auto r = pack({fits + 1}, B, F);
+      CHECK(r.size() == 1 && r[0].lng && r[0].n == 1 && r[0].V == fits + 2 && r[0].n_real == fits + 1);
+      check_rounds({fits + 1}, B, F);
+    }
+    // a long item first, last, and between two small ones, which are not merged across it
+    for (const Frames &f : {Frames{B, 0, 0}, Frames{0, 0, B}, Frames{0, B + 7, 0}}) {
+      const auto r = pack(f, B, F);
+      check_rounds(f, B, F);
+      CHECK(count_lng(r) == 1);
+      const bool two_small_fit = F + 2 <= B;  // two items of no frames in one round
+      const bool between = f[1] != 0;
+      CHECK(r.size() == (between || !two_small_fit ? 3u : 2u));
+    }
+    // items that fill a round to exactly the budget, then one more frame
+    if (fits >= 1) {
+      Frames f;  // `fits + 1` slots behind the front: items of 1 frame (2 slots) and, where that is odd, one of none
+      for (uint64_t s = fits + 1; s >= 2 && f.size() < 4096; s -= 2) f.push_back(1);
+      if ((fits + 1) % 2) f.push_back(0);
+      uint64_t slots = 0;
+      for (uint64_t v : f) slots += v + 1;
+      if (F + slots == B) {  // (the largest budgets are filled with longer items below)
+        CHECK(pack(f, B, F).size() == 1);
+        check_rounds(f, B, F);
+        f.back() += 1;  // (a lone item grown past the budget is one long round)
+        CHECK(pack(f, B, F).size() == (f.size() == 1 ? 1u : 2u));
+        check_rounds(f, B, F);
+      }
+    }
+    if (B >= 4096) {  // 64 items of 63 frames fill 4096 slots; the other budgets get their remainder as a last item
+      Frames f(64, 63);
+      f.back() = 63 + B - F - 4096;
+      CHECK(pack(f, B, F).size() == 1 && pack(f, B, F)[0].V == B);
+      check_rounds(f, B, F);
+      f.back() += 1;
+      CHECK(pack(f, B, F).size() == 2 && pack(f, B, F)[1].n == 1);
+      check_rounds(f, B, F);
+    }
+    // items of no frames: refused by the drivers, but the packer must neither divide nor wrap on them
+    check_rounds(Frames(1000, 0), B, F);
+    CHECK(pack(Frames(1000, 0), B, F).size() == (1000 + (B - F) - 1) / (B - F));
+    // pseudo-random lists: short items, items about a round long, items far beyond one
+    for (int t = 0; t < 3000; ++t) {
+      Frames f(rnd(48));
+      const uint64_t kind = rnd(4);
+      for (uint64_t &v : f) {
+        const uint64_t k = kind == 3 ? rnd(3) : kind;
+        v = k == 0 ? rnd(B / 8 + 2) : k == 1 ? rnd(B + 2) : fits - (fits ? rnd(2) : 0) + rnd(3) * rnd(B);
+      }
+      check_rounds(f, B, F);
+    }
+  }
+
+  // TableOffsets: tables on multiples of 256 that do not overlap; an empty table takes nothing
+  std::snprintf(g_what, sizeof g_what, "TableOffsets");
+  for (int t = 0; t < 2000; ++t) {
+    TableOffsets offs;
+    CHECK(offs.size() == 0 && offs.take(0) == 0 && offs.size() == 0);
+    size_t end = 0;  // of the last table
+    for (uint64_t k = rnd(12); k > 0; --k) {
+      const size_t bytes = rnd(4) ? rnd(5000) : 256 * rnd(4), at = offs.take(bytes);
+      CHECK(at % 256 == 0 && at >= end && at < end + 256);
+      end = at + bytes;
+      CHECK(offs.size() % 256 == 0 && offs.size() >= end && offs.size() < end + 256);
+      const size_t here = offs.size();
+      CHECK(offs.take(0) == here && offs.size() == here);
+    }
+  }
+  if (g_failed) {
+    std::printf("round plan: %d checks failed\n", g_failed);
+    return 1;
+  }
+  std::printf("round plan ok\n");
+  return 0;
+}
