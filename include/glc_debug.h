@@ -4,7 +4,12 @@
  * two independent implementations of the same arithmetic and demand identical bits, or drive one kernel
  * stage on inputs built for the purpose (tests/test_quantizer_edges.py, tests/test_decode_edges.py,
  * tests/test_compact_edges.py).  tests/test_channel_axis.py drives the store pack, the windowed R2 and the draw
- * planner through their hooks at 4, 5, 7, 9, 16, 17, 257 and 513 channels.
+ * planner through their hooks at 4, 5, 7, 9, 16, 17, 257 and 513 channels.  tests/test_encode_screen_drivers.py holds
+ * the screened encode under the store encode (glc_encode_batch_device_compact and _int), the stream push (device and
+ * host) and glc_roundtrip_batch_device_pcm to the oracle with glc_debug_set_encode_screen / _bound / _repair / _edge
+ * and their stats: forced on under the FMA and the matrix form with either repair, and, for a clip longer than a round,
+ * in the automatic mode; tests/test_encode_screen_edges.py does for glc_encode, glc_encode_batch and the float round
+ * trips, under the automatic bound kind and the forced matrix form.
  */
 #ifndef GLC_DEBUG_H
 #define GLC_DEBUG_H

@@ -10,7 +10,8 @@ GPU: every case through glc_encode_range_device with the screen forced on and of
 oracle, guard pages, the counts exactly the model's; sequences on one context (a smaller launch after a larger, the
 channel count changing, the same launch twice, 255 and 256 rows); and the other four drivers of encode_range_on -
 glc_encode (both workspace slots), glc_encode_batch (junk frames), the single and the batch round trip - against
-oracle.encode / oracle.decode."""
+oracle.encode / oracle.decode, under the automatic bound kind and with the matrix form forced.  (The store encode, the
+stream push and the PCM round trip: tests/test_encode_screen_drivers.py.)"""
 import os
 import sys
 
@@ -380,6 +381,13 @@ def _delta(glc_amd, ctx, s0):
     return s1[0] - s0[0], s1[1] - s0[1]
 
 
+BOUND_KINDS = (0, 2)      # automatic - the FMA form at these row counts - and the matrix form forced wherever it is built
+
+
+def _set_bound(glc_amd, ctx, kind):
+    assert glc_amd.lib.glc_debug_set_encode_bound(ctx._h, kind) == 0
+
+
 _oracle = {}
 
 
@@ -396,9 +404,11 @@ def _bounds(name):
 
 
 @pytest.mark.gpu
-def test_gpu_glc_encode_screens_every_round_on_both_workspace_slots(gpu):
+@pytest.mark.parametrize("bound", BOUND_KINDS)
+def test_gpu_glc_encode_screens_every_round_on_both_workspace_slots(gpu, bound):
     """Encoder.encode of 690 frames of 8 channels: three rounds, the middle one - on the second stream, workspace
-    slot 1 - with 40 frames of noise; float32, and the same clip as int16."""
+    slot 1 - with 40 frames of noise; float32, and the same clip as int16.  Bound kind 2: the rounds take the matrix
+    form's 8-channel segment loader (the kind outlives the screen's setter)."""
     torch, glc_amd, _ = gpu
     c = driver("encode")[0]
     x = E.encode_clip().reshape(-1)
@@ -409,6 +419,7 @@ def test_gpu_glc_encode_screens_every_round_on_both_workspace_slots(gpu):
     lo16, hi16 = _bounds("encode16")
     enc = glc_amd.Encoder(SR)
     try:
+        _set_bound(glc_amd, enc, bound)
         _set(glc_amd, enc, 2)
         s0 = E.S.stats(glc_amd, enc)
         on = enc.encode(x, c.ch).to_bytes()
@@ -428,11 +439,13 @@ def test_gpu_glc_encode_screens_every_round_on_both_workspace_slots(gpu):
         assert _delta(glc_amd, enc, s0) == (0, 0)
         assert off == ref, "mode 1: the stream differs from the oracle's"
     finally:
+        _set_bound(glc_amd, enc, 0)
         enc.close()
 
 
 @pytest.mark.gpu
-def test_gpu_encode_batch_screens_the_virtual_stream_junk_frames_included(gpu):
+@pytest.mark.parametrize("bound", BOUND_KINDS)
+def test_gpu_encode_batch_screens_the_virtual_stream_junk_frames_included(gpu, bound):
     """20 stereo clips of 5..9 frames in one round: 160 virtual frames, 320 rows, the 20 junk frames among them.
     They count as screened - they are rows of the launch - and the repaired bound treats them like every row: the
     model, run on the virtual stream of DESIGN section 3, decides them."""
@@ -443,6 +456,7 @@ def test_gpu_encode_batch_screens_the_virtual_stream_junk_frames_included(gpu):
     lo, hi = _bounds("batch")
     enc = glc_amd.Encoder(SR)
     try:
+        _set_bound(glc_amd, enc, bound)
         _set(glc_amd, enc, 2)
         s0 = E.S.stats(glc_amd, enc)
         on = [e.to_bytes() for e in enc.encode_batch(clips, 2)]
@@ -457,18 +471,22 @@ def test_gpu_encode_batch_screens_the_virtual_stream_junk_frames_included(gpu):
         assert _delta(glc_amd, enc, s0) == (0, 0)
         assert off == on
     finally:
+        _set_bound(glc_amd, enc, 0)
         enc.close()
 
 
 @pytest.mark.gpu
-def test_gpu_round_trips_decode_the_records_the_screen_and_the_repair_left(gpu):
+@pytest.mark.parametrize("bound", BOUND_KINDS)
+def test_gpu_round_trips_decode_the_records_the_screen_and_the_repair_left(gpu, bound):
     """RoundTrip on one clip (298 rows, a clicked frame repaired in front of the decode of the same round) and
     apply_batch_tensor on a planar stereo and an interleaved 3-channel batch (278 / 285 rows of virtual stream):
-    the output words are the oracle's decode of its own encode per clip, the NaN pattern everywhere else."""
+    the output words are the oracle's decode of its own encode per clip, the NaN pattern everywhere else.  Bound kind 2:
+    the stereo launches take the matrix form; the 3-channel batch, which the form is not built for, keeps the FMA one."""
     import test_roundtrip_batch as RB
     torch, glc_amd, _ = gpu
     rt = glc_amd.RoundTrip(SR)
     try:
+        _set_bound(glc_amd, rt, bound)
         for mode in (2, 1):
             _set(glc_amd, rt, mode)
             x = E.roundtrip_clip()
@@ -492,4 +510,5 @@ def test_gpu_round_trips_decode_the_records_the_screen_and_the_repair_left(gpu):
                 print(f"{name}, mode {mode}: screened {screened} of {c.M}, repaired {repaired}, model {lo}..{hi}")
                 assert (screened, repaired) == (0, 0) if mode == 1 else (screened == c.M and lo <= repaired <= hi), (name, mode, screened, repaired)
     finally:
+        _set_bound(glc_amd, rt, 0)
         rt.close()
