@@ -99,6 +99,11 @@ class GlcStreamSeg(C.Structure):
     _fields_ = [("stream", C.c_uint64), ("first_frame", C.c_uint64), ("n_frames", C.c_uint64)]
 
 
+class GlcStreamDecPlan(C.Structure):
+    """glc_stream_dec_plan (include/glc.h): the samples per channel a push emits on a lane of a streaming decode."""
+    _fields_ = [("first_sample", C.c_uint64), ("n_samples", C.c_uint64)]
+
+
 class GlcFramesView(C.Structure):
     """glc_frames_view (include/glc.h): EncodedAudio as flat arrays."""
     _fields_ = [
@@ -286,6 +291,16 @@ SIGNATURES = {
     "glc_stream_enc_segment": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_uint64)]),
     "glc_stream_enc_frames": (C.c_int, [_vp, C.c_uint64, C.POINTER(_vp)]),
+    "glc_plan_stream_dec_push": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(GlcStreamDecPlan)]),
+    "glc_stream_dec_open": (C.c_int, [_vp, C.c_uint16, C.c_uint64, C.POINTER(_vp)]),
+    "glc_stream_dec_close": (None, [_vp]),
+    "glc_stream_dec_reset": (C.c_int, [_vp, C.c_uint64]),
+    "glc_stream_dec_max_push": (C.c_uint64, [C.c_uint16]),
+    "glc_stream_dec_frames_done": (C.c_int, [_vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "glc_stream_dec_push_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.POINTER(GlcStreamSeg), C.c_uint64, _vp, C.POINTER(C.c_uint64),
+                                             _vp, C.c_int, C.POINTER(GlcClipLayout)]),
+    "glc_stream_dec_push": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(GlcStreamSeg), C.c_uint64, _vp,
+                                      C.POINTER(C.c_uint64), C.POINTER(_vp), C.c_int, C.POINTER(C.c_uint64)]),
     "glc_version": (C.c_char_p, []),
 }
 

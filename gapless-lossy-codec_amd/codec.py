@@ -22,7 +22,7 @@ from typing import Iterator, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ._lib import (FRAMES_HOOK, GLC_EINVAL, GLC_PCM_F32, GLC_PCM_S16, GLC_PCM_S32, GlcClipLayout, GlcCompactInfo, GlcCompactStatus, GlcCrop, GlcCropPlan, GlcError,
-                   GlcFramesGather, GlcFramesView, GlcInfo, GlcPlan, GlcRoundtripInfo, GlcStreamPushPlan, GlcStreamSeg, check, lib)
+                   GlcFramesGather, GlcFramesView, GlcInfo, GlcPlan, GlcRoundtripInfo, GlcStreamDecPlan, GlcStreamPushPlan, GlcStreamSeg, check, lib)
 
 FRAME_SIZE = 2048        # src/codec.rs:15
 HOP_SIZE = 1024          # src/codec.rs:16
@@ -1385,6 +1385,159 @@ class StreamEncoder(_Ctx):
         finally:
             self.set_stream(0)
         return entries[:n_segs.value], [(g.stream, g.first_frame, g.n_frames) for g in segs[:n_segs.value]]
+
+
+def plan_stream_dec_push(frames_done: int, n_frames: int, finish: bool = False, total_len: int = 0) -> GlcStreamDecPlan:
+    """What a push of n_frames frames emits on a lane of a streaming decode that has taken frames_done so far
+    (glc_plan_stream_dec_push): first_sample and n_samples, per channel; raises where a finish's total_len does not
+    plan to exactly frames_done + n_frames frames."""
+    if frames_done < 0 or n_frames < 0 or total_len < 0:
+        raise GlcError(GLC_EINVAL, "plan_stream_dec_push: negative count")
+    p = GlcStreamDecPlan()
+    check(lib.glc_plan_stream_dec_push(frames_done, n_frames, 1 if finish else 0, total_len, C.byref(p)))
+    return p
+
+
+class StreamDecoder(_Ctx):
+    """Decoder::decode fed in segments: n_streams independent lanes of `channels` channels on one context
+    (glc_stream_dec_*).  The concatenation of a lane's outputs over any chunking is bit for bit Decoder.decode of the
+    stream its segments assemble to.  Use .push (host blobs) or .push_tensor (a device arena), not both."""
+
+    def __init__(self, sample_rate: int, channels: int, n_streams: int = 1, device: int = 0):
+        super().__init__(sample_rate, device)
+        self.channels, self.n_streams = int(channels), int(n_streams)
+        self._s = None
+        self._n_segs = 0
+        if not 0 < self.channels <= 0xFFFF or self.n_streams <= 0:
+            raise GlcError(GLC_EINVAL, "StreamDecoder: channels must be 1..65535 and n_streams positive")
+        s = C.c_void_p()
+        check(lib.glc_stream_dec_open(self._h, self.channels, self.n_streams, C.byref(s)), self._h)
+        self._s = s
+
+    def __del__(self):
+        s, self._s = getattr(self, "_s", None), None
+        if s:
+            lib.glc_stream_dec_close(s)  # before its context
+        super().__del__()
+
+    @property
+    def max_push(self) -> int:
+        """Frames one lane may take in one push."""
+        return int(lib.glc_stream_dec_max_push(self.channels))
+
+    def frames_done(self, i: int = 0) -> int:
+        n = C.c_uint64()
+        check(lib.glc_stream_dec_frames_done(self._s, i, C.byref(n)), self._h)
+        return n.value
+
+    def reset(self, i: int = 0) -> None:
+        """Lane i back to "no frame taken"."""
+        check(lib.glc_stream_dec_reset(self._s, i), self._h)
+
+    def _lane_args(self, finish, total_len):
+        b = self.n_streams
+        if b == 1 and isinstance(finish, (bool, int)):
+            finish = [finish]
+        if b == 1 and isinstance(total_len, int):
+            total_len = [total_len]
+        fin = [False] * b if finish is None else [bool(v) for v in finish]
+        tot = [0] * b if total_len is None else [int(v) for v in total_len]
+        if len(fin) != b or len(tot) != b:
+            raise GlcError(GLC_EINVAL, f"finish and total_len must hold {b} values")
+        return fin, tot
+
+    def _plans(self, frames, fin, tot):
+        return [plan_stream_dec_push(self.frames_done(i), frames[i], fin[i], tot[i]) if frames[i] or fin[i] else None
+                for i in range(self.n_streams)]
+
+    def push(self, segments_per_lane, finish=None, total_len=None, dtype=np.float32) -> list:
+        """segments_per_lane: per lane a list of (first_frame, n_frames, blob bytes) - what StreamEncoder.segments
+        gives - in frame order (None or empty: nothing); finish / total_len: per lane whether this push ends its stream
+        and the stream's samples per channel.  Returns per lane the interleaved samples the push emits (float32, or
+        int16 narrowed as Decoder.decode(dtype=np.int16) narrows).  Synchronises."""
+        b, ch = self.n_streams, self.channels
+        if b == 1 and (segments_per_lane is None or (len(segments_per_lane) and isinstance(segments_per_lane[0], tuple))):
+            segments_per_lane = [segments_per_lane]
+        if len(segments_per_lane) != b:
+            raise GlcError(GLC_EINVAL, f"segments_per_lane must hold {b} lists")
+        dt = Decoder._out_dtype(dtype)
+        fin, tot = self._lane_args(finish, total_len)
+        flat = [(i, f0, nf, bytes(blob)) for i, lane in enumerate(segments_per_lane) for (f0, nf, blob) in (lane or [])]
+        frames = [sum(nf for (_, nf, _) in (lane or [])) for lane in segments_per_lane]
+        plans = self._plans(frames, fin, tot)
+        outs = [np.empty((p.n_samples if p else 0) * ch, dtype=dt) for p in plans]
+        n = len(flat)
+        keep = [np.frombuffer(bytearray(blob) + bytearray(8), dtype=np.uint8) for (_, _, _, blob) in flat]
+        ptrs = (C.c_void_p * max(n, 1))(*[k.ctypes.data for k in keep])
+        nbytes = (C.c_uint64 * max(n, 1))(*[len(blob) for (_, _, _, blob) in flat])
+        segs = (GlcStreamSeg * max(n, 1))(*[GlcStreamSeg(i, f0, nf) for (i, f0, nf, _) in flat])
+        flags = (C.c_uint8 * b)(*[1 if v else 0 for v in fin])
+        totals = (C.c_uint64 * b)(*tot)
+        optrs = (C.c_void_p * b)(*[o.ctypes.data if o.size else None for o in outs])
+        n_out = (C.c_uint64 * b)()
+        check(lib.glc_stream_dec_push(self._s, ptrs, nbytes, segs, n, C.cast(flags, C.c_void_p), totals, optrs,
+                                      GLC_PCM_S16 if dt == np.int16 else GLC_PCM_F32, n_out), self._h)
+        self._n_segs = n
+        return outs
+
+    def push_tensor(self, arena, entries, segs, finish=None, total_len=None, planar: bool = True, out=None, dtype=None):
+        """glc_stream_dec_push_device on torch's current stream.  arena: the contiguous 1-D uint8 CUDA tensor the
+        segments lie in; entries: the (n_segs, 4) int64 CUDA tensor of glc_store_entry words and segs: the host list
+        [(lane, first_frame, n_frames)] StreamEncoder.push_tensor returned (concatenated over pushes, ascending by lane
+        and frame).  Returns (out, lengths): a (B, C, T) (planar) or (B, T, C) CUDA tensor, float32 or int16 (`dtype`
+        or `out`'s), T the longest span of the push - `out` is filled when given, a fresh tensor is zero outside the
+        spans - and per lane the samples per channel the push emitted.  Nothing is copied to the host."""
+        import torch
+        b, ch = self.n_streams, self.channels
+        if not isinstance(arena, torch.Tensor) or not arena.is_cuda or arena.dtype != torch.uint8 or arena.dim() != 1 \
+                or not arena.is_contiguous():
+            raise TypeError("arena must be a contiguous 1-D uint8 CUDA tensor")
+        segs = [(int(a), int(f0), int(nf)) for (a, f0, nf) in segs]
+        n = len(segs)
+        if n and (not isinstance(entries, torch.Tensor) or not entries.is_cuda or entries.dtype != torch.int64
+                  or entries.dim() != 2 or entries.shape != (n, 4) or not entries.is_contiguous()):
+            raise TypeError("entries must be a contiguous (n_segs, 4) int64 CUDA tensor")
+        if arena.device.index != self.device or (n and entries.device != arena.device):
+            raise GlcError(GLC_EINVAL, "arena and entries must be on this context's device")
+        fin, tot = self._lane_args(finish, total_len)
+        frames = [0] * b
+        for (a, _, nf) in segs:
+            if not 0 <= a < b:
+                raise GlcError(GLC_EINVAL, "segs: no such lane")
+            frames[a] += nf
+        lens = [p.n_samples if p else 0 for p in self._plans(frames, fin, tot)]
+        t = max(max(lens), 1)
+        tdt = _tensor_out_dtype(dtype, out)
+        shape = (b, ch, t) if planar else (b, t, ch)
+        if out is None:
+            out = torch.zeros(shape, dtype=tdt, device=arena.device)
+        elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != arena.device or out.dim() != 3 \
+                or out.shape[0] != b or (out.shape[1] if planar else out.shape[2]) != ch \
+                or (out.shape[2] if planar else out.shape[1]) < max(lens) or not out.is_contiguous():
+            raise TypeError(f"out must be a contiguous CUDA tensor of shape {shape} or longer in time")
+        arr = (C.c_uint64 * b)(*lens)
+        lay = GlcClipLayout(b, ch, 1 if planar else 0, out.stride(0), out.stride(1) if planar else 0, 0, C.cast(arr, C.POINTER(C.c_uint64)))
+        c_segs = (GlcStreamSeg * max(n, 1))(*[GlcStreamSeg(a, f0, nf) for (a, f0, nf) in segs])
+        flags = (C.c_uint8 * b)(*[1 if v else 0 for v in fin])
+        totals = (C.c_uint64 * b)(*tot)
+        self._enter_torch_stream(arena.device)
+        try:
+            check(lib.glc_stream_dec_push_device(self._s, C.c_void_p(arena.data_ptr()), arena.numel(),
+                                                 C.c_void_p(entries.data_ptr()) if n else None, c_segs, n,
+                                                 C.cast(flags, C.c_void_p), totals, C.c_void_p(out.data_ptr()),
+                                                 GLC_PCM_S16 if out.dtype == torch.int16 else GLC_PCM_F32, C.byref(lay)), self._h)
+        finally:
+            self.set_stream(0)
+        self._n_segs = n
+        return out, lens
+
+    def last_compact_status(self):
+        """glc_decode_compact_last_status: one CompactStatus per SEGMENT of the last push.  Synchronises."""
+        n = self._n_segs
+        arr = (GlcCompactStatus * max(n, 1))()
+        if n:
+            check(lib.glc_decode_compact_last_status(self._h, arr, n), self._h)
+        return [CompactStatus(int(a.flags), int(a.n_bad_rows), int(a.first_bad_row)) for a in arr[:n]]
 
 
 def save_encoded(encoded: EncodedAudio, path) -> None:

@@ -3863,6 +3863,426 @@ int glc_stream_enc_frames(glc_stream_enc *s, uint64_t stream, glc_frames **out) 
   return GLC_OK;
 }
 
+// ------------------------------------------------------------------------------ streaming decode
+
+struct glc_stream_dec {
+  glc_ctx *ctx = nullptr;
+  uint32_t ch = 0;
+  uint64_t n = 0;
+  int mode = 0;       // 0: no push yet, 1: host pushes, 2: device pushes
+  DevBuf carry;       // [lane][2][ch][1024] floats: (a) the last hop's finished sums, (b) the last frame's second half
+  std::vector<uint64_t> done;  // frames taken per lane
+  // host pushes
+  HostBuf up, down;   // pinned: the blobs and entries going up, the samples coming down
+  DevBuf arena, d_entries, d_out;
+  uint64_t carry_at(uint64_t lane) const { return lane * 2ull * glc::kHop * ch; }
+};
+
+extern "C++" {
+namespace {
+
+// What a push does with lane `lane`: frames [D, D + n) from segments [seg0, seg0 + nseg), and what that emits.
+struct DecLanePush {
+  uint64_t lane, D, n;
+  bool fin;
+  uint64_t seg0, nseg;
+  glc_stream_dec_plan plan;
+};
+
+// The part of a lane's push that one round decodes: frames [D, D + n) in block slots [slot0, slot0 + n), the lane's
+// two pseudo-slots at `pseudo` (D > 0), its samples from `before` samples per channel behind the lane's output start.
+struct DecPiece {
+  uint64_t lane, D, n, slot0, pseudo, before;
+  bool fin;
+  glc_stream_dec_plan plan;
+};
+
+// The core of both pushes: everything is validated.  Queues the planner and the rounds; updates the lanes.
+template <typename T>
+int stream_dec_core(glc_stream_dec *s, const std::vector<DecLanePush> &act, const glc_stream_seg *segs, uint64_t n_segs,
+                    const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries, const uint64_t *total_len, T *d_out,
+                    const RtbLayout &out) {
+  glc_ctx *ctx = s->ctx;
+  const uint32_t ch = s->ch;
+  const uint64_t per_hop = uint64_t(glc::kHop) * ch;
+  const size_t slot = static_cast<size_t>(ch) * glc::kFrame;
+  // the items of the round packer, in lane order: a lane's segments, or ONE item of no frames for a finish that brings none
+  struct Item {
+    size_t a;      // index into act
+    int64_t seg;   // index into segs, -1: none
+    uint64_t frames;
+  };
+  std::vector<Item> items;
+  for (size_t a = 0; a < act.size(); ++a) {
+    for (uint64_t j = 0; j < act[a].nseg; ++j) items.push_back(Item{a, static_cast<int64_t>(act[a].seg0 + j), segs[act[a].seg0 + j].n_frames});
+    if (!act[a].nseg) items.push_back(Item{a, -1, 0});
+  }
+  struct Round : RoundSpan {
+    size_t o_desc = 0, o_load = 0, o_save = 0;
+    uint64_t n_desc = 0, n_load = 0, n_save = 0, seg_first = 0, seg_n = 0;
+    std::vector<DecPiece> pieces;
+  };
+  auto rounds = plan_rounds<Round>(items.size(), [&](uint64_t k) { return items[k].frames; }, kDecodeChunkFrames + 1, 0);
+  for (const Round &R : rounds)
+    if (R.lng) return fail(ctx, GLC_EHIP, "glc_stream_dec_push: internal: a segment does not fit a round");
+  rt_forget_streams(ctx);
+  ctx->cd_status_n = 0;
+  auto commit = [&] {
+    for (const DecLanePush &a : act) s->done[a.lane] = a.fin ? 0 : a.D + a.n;
+  };
+  if (rounds.empty()) return GLC_OK;  // nothing arrives and nothing finishes
+  // the pieces: a lane that straddles two rounds is two consecutive pushes of it, the carry handed on through the
+  // session's buffer by the first round's save and the second round's load
+  std::vector<uint64_t> taken(act.size(), 0);
+  TableOffsets offs;
+  const size_t o_segs = offs.take(std::max<uint64_t>(n_segs, 1) * sizeof(glc::StreamDecSeg));
+  uint64_t max_M = 0, max_slots = 0, max_frames = 0, seg_at = 0;
+  for (Round &R : rounds) {
+    uint64_t real = 0;
+    R.seg_first = seg_at;
+    for (uint64_t k = R.first; k < R.first + R.n; ++k) {
+      const Item &it = items[k];
+      const DecLanePush &a = act[it.a];
+      if (R.pieces.empty() || R.pieces.back().lane != a.lane)
+        R.pieces.push_back(DecPiece{a.lane, a.D + taken[it.a], 0, real, 0, glc::stream_dec_emitted(a.D + taken[it.a]) - a.plan.first_sample, false, {}});
+      DecPiece &p = R.pieces.back();
+      p.n += it.frames, taken[it.a] += it.frames, real += it.frames;
+      if (it.seg >= 0) ++R.seg_n, ++seg_at;
+      p.fin = a.fin && taken[it.a] == a.n && (k + 1 == items.size() || items[k + 1].a != it.a);
+    }
+    for (size_t q = 0; q < R.pieces.size(); ++q) {
+      DecPiece &p = R.pieces[q];
+      p.pseudo = R.n_real + 2 * q;
+      glc::plan_stream_dec_push(p.D, p.n, p.fin, p.fin ? total_len[p.lane] : 0, &p.plan);  // cannot fail: the lane's plan passed
+      const glc::Trim trim{glc::kHop / 2 + ch * p.plan.first_sample, ch * p.plan.n_samples};
+      R.n_desc += count_hop_descs(trim, per_hop, 0, p.D + p.n + 1);
+      if (p.D) ++R.n_load;
+      if (!p.fin) ++R.n_save;
+    }
+    R.o_desc = offs.take(R.n_desc * sizeof(glc::HopDescStrided));
+    R.o_load = offs.take(R.n_load * sizeof(glc::StreamCarry));
+    R.o_save = offs.take(R.n_save * sizeof(glc::StreamCarry));
+    max_M = std::max(max_M, R.n_real * ch);
+    max_slots = std::max<uint64_t>(max_slots, R.n_real + 2 * R.pieces.size());
+    max_frames = std::max(max_frames, R.n_real);
+  }
+  const size_t img_bytes = offs.size();
+  // behind the image, written by the planner kernel: the directory and the verdicts
+  const size_t o_dir = offs.take(std::max<uint64_t>(n_segs, 1) * sizeof(glc::CompactBlob));
+  const size_t o_verdict = offs.take(std::max<uint64_t>(n_segs, 1) * sizeof(uint32_t));
+  int rc = rt_reserve(ctx, ctx->rt_rows, glc::rows_from_compact_window_bytes(static_cast<uint32_t>(max_M)));
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->blocks, max_slots * slot * sizeof(float));
+  if (rc == GLC_OK && max_frames) rc = reserve_d1_plan(ctx, max_frames, ch);
+  TableImage &image = ctx->rtb_image;
+  if (rc == GLC_OK) rc = image.begin(ctx, offs.size());
+  if (rc == GLC_OK && n_segs) rc = rt_reserve(ctx, ctx->cd_status, n_segs * sizeof(glc::CompactStatus));
+  if (rc != GLC_OK) return rc;
+  const bool out_planes = out.planes();
+  auto *seg_tab = image.host<glc::StreamDecSeg>(o_segs);
+  for (const Round &R : rounds) {
+    uint64_t row = 0, j = R.seg_first;
+    for (uint64_t k = R.first; k < R.first + R.n; ++k) {
+      if (items[k].seg < 0) continue;
+      seg_tab[j++] = glc::StreamDecSeg{static_cast<uint32_t>(row), static_cast<uint32_t>(items[k].frames * ch)};
+      row += items[k].frames * ch;
+    }
+    auto *desc = image.host<glc::HopDescStrided>(R.o_desc);
+    auto *load = image.host<glc::StreamCarry>(R.o_load);
+    auto *save = image.host<glc::StreamCarry>(R.o_save);
+    for (const DecPiece &p : R.pieces) {
+      const uint64_t nf = p.D + p.n;
+      const glc::Trim trim{glc::kHop / 2 + ch * p.plan.first_sample, ch * p.plan.n_samples};
+      const uint64_t dst = out.at(p.lane) + (out_planes ? p.before : p.before * ch);
+      const int32_t slot_a = static_cast<int32_t>(p.pseudo), slot_b = slot_a + 1;
+      if (trim.n) {
+        const uint64_t h0 = trim.start / per_hop, h1 = (trim.start + trim.n - 1) / per_hop + 1;
+        for (uint64_t h = h0; h < h1; ++h) {
+          if (!glc::hop_desc(desc, nf, ch, trim, h, static_cast<int64_t>(p.slot0) - static_cast<int64_t>(p.D), dst, out_planes,
+                             out.l->channel_stride))
+            continue;
+          // the hops that reach back behind the push: hop D - 1 is the carried sums alone - the second half of a slot
+          // with no `cur`, so that D2 adds nothing to them -, hop D takes frame D - 1's second half from the carry
+          if (p.D && h + 1 == p.D) desc->prev = slot_a, desc->cur = -1;
+          if (p.D && h == p.D) desc->prev = slot_b;
+          ++desc;
+        }
+      }
+      if (p.D) *load++ = glc::StreamCarry{slot_a, -1, s->carry_at(p.lane)};
+      if (!p.fin)  // n >= 1: a push that does not finish brings frames
+        *save++ = glc::StreamCarry{p.n >= 2 ? static_cast<int32_t>(p.slot0 + p.n - 2) : (p.D ? slot_b : -1),
+                                   static_cast<int32_t>(p.slot0 + p.n - 1), s->carry_at(p.lane)};
+    }
+    if (static_cast<uint64_t>(desc - image.host<glc::HopDescStrided>(R.o_desc)) != R.n_desc)
+      return fail(ctx, GLC_EHIP, "glc_stream_dec_push: hop count arithmetic is inconsistent");
+  }
+  hipStream_t st = ctx->stream;
+  rc = image.send(ctx, img_bytes);
+  if (rc != GLC_OK) return rc;
+  uint8_t *d_tab = static_cast<uint8_t *>(ctx->rtb_tab.p);
+  auto *d_dir = reinterpret_cast<glc::CompactBlob *>(d_tab + o_dir);
+  auto *d_verdict = reinterpret_cast<uint32_t *>(d_tab + o_verdict);
+  if (n_segs)
+    GLC_HIP(ctx, glc::launch_stream_dec_plan(reinterpret_cast<uintptr_t>(d_arena), arena_bytes, d_entries, image.dev<glc::StreamDecSeg>(o_segs),
+                                             static_cast<uint32_t>(n_segs), d_dir, d_verdict, st));
+  auto *d_status = static_cast<glc::CompactStatus *>(ctx->cd_status.p);
+  float *blocks = static_cast<float *>(ctx->blocks.p);
+  float *carry = static_cast<float *>(s->carry.p);
+  for (const Round &R : rounds) {
+    const uint32_t M = static_cast<uint32_t>(R.n_real * ch);
+    if (M) {
+      glc::DecodeRows rows{};
+      // pairs and raw planes are addressed from the arena: every usable blob lies inside it, 64-byte aligned
+      GLC_HIP(ctx, glc::launch_rows_from_compact_window(d_dir + R.seg_first, glc::CompactBlob{}, static_cast<uint32_t>(R.seg_n), M, ch, 0u,
+                                                        d_arena, ctx->rt_rows.p, d_status + R.seg_first, st, &rows, d_verdict + R.seg_first));
+      GLC_HIP(ctx, glc::launch_imdct_rows(ctx->dev, rows, 0, M, ch, blocks, st, ctx->d1_variant, ctx->dec_plan.p,
+                                          ctx->dec_plan.p ? ctx->dec_plan_groups : 0, false));
+    }
+    GLC_HIP(ctx, glc::launch_stream_dec_carry(false, image.dev<glc::StreamCarry>(R.o_load), static_cast<uint32_t>(R.n_load), ch, blocks, carry, st));
+    if (R.n_desc)
+      GLC_HIP(ctx, glc::launch_overlap_add_strided(blocks, image.dev<glc::HopDescStrided>(R.o_desc), static_cast<uint32_t>(R.n_desc), ch,
+                                                   out_planes, d_out, st));
+    GLC_HIP(ctx, glc::launch_stream_dec_carry(true, image.dev<glc::StreamCarry>(R.o_save), static_cast<uint32_t>(R.n_save), ch, blocks, carry, st));
+  }
+  ctx->cd_status_n = n_segs;
+  commit();
+  return GLC_OK;
+}
+
+// What both pushes check of the segments and the lanes, and build for the core.  lens: the layout's, or null (the
+// host push sizes its own output).
+int stream_dec_plan_lanes(glc_stream_dec *s, const std::string &w, const glc_stream_seg *segs, uint64_t n_segs, const uint8_t *finish,
+                          const uint64_t *total_len, std::vector<DecLanePush> *act) {
+  glc_ctx *ctx = s->ctx;
+  const uint64_t max_push = glc_stream_dec_max_push(static_cast<uint16_t>(s->ch));
+  std::vector<DecLanePush> by_lane;
+  uint64_t j = 0;
+  for (uint64_t j0 = 0; j0 < n_segs; j0 = j) {
+    const uint64_t lane = segs[j0].stream;
+    const std::string name = w + ": segment " + std::to_string(j0);
+    if (lane >= s->n) return fail(ctx, GLC_EINVAL, name + ": no such stream");
+    if (!by_lane.empty() && lane <= by_lane.back().lane) return fail(ctx, GLC_EINVAL, name + ": the segments do not ascend by stream and frame");
+    DecLanePush a{lane, s->done[lane], 0, false, j0, 0, {}};
+    for (j = j0; j < n_segs && segs[j].stream == lane; ++j) {
+      if (segs[j].n_frames == 0) return fail(ctx, GLC_EINVAL, w + ": segment " + std::to_string(j) + ": no frames");
+      if (segs[j].first_frame != a.D + a.n)
+        return fail(ctx, GLC_EINVAL, w + ": segment " + std::to_string(j) + ": it does not start where its lane's frames end");
+      if (segs[j].n_frames > max_push - a.n)
+        return fail(ctx, GLC_EINVAL, w + ": lane " + std::to_string(lane) + ": more frames than glc_stream_dec_max_push");
+      a.n += segs[j].n_frames, ++a.nseg;
+    }
+    by_lane.push_back(a);
+  }
+  size_t at = 0;
+  for (uint64_t i = 0; i < s->n; ++i) {
+    const bool fin = finish && finish[i];
+    DecLanePush a{i, s->done[i], 0, fin, 0, 0, {}};
+    if (at < by_lane.size() && by_lane[at].lane == i) a = by_lane[at++], a.fin = fin;
+    if (!a.n && !fin) continue;
+    if (fin && !total_len) return fail(ctx, GLC_EINVAL, w + ": a finish without total_len");
+    if (!glc::plan_stream_dec_push(a.D, a.n, fin, fin ? total_len[i] : 0, &a.plan))
+      return fail(ctx, GLC_EINVAL, w + ": lane " + std::to_string(i) + ": total_len does not plan to the frames the lane has taken");
+    act->push_back(a);
+  }
+  return GLC_OK;
+}
+
+template <typename T>
+int stream_dec_push_device_checked(glc_stream_dec *s, const std::string &w, const void *d_arena, uint64_t arena_bytes,
+                                   const glc_store_entry *d_entries, const glc_stream_seg *segs, uint64_t n_segs, const uint8_t *finish,
+                                   const uint64_t *total_len, T *d_out, const glc_clip_layout *out) {
+  glc_ctx *ctx = s->ctx;
+  if (!out || !d_out || (n_segs && (!d_arena || !d_entries || !segs))) return fail(ctx, GLC_EINVAL, w + ": null argument");
+  if (out->n_clips != s->n || out->channels != s->ch) return fail(ctx, GLC_EINVAL, w + ": the layout's n_clips and channels must be the session's");
+  if (reinterpret_cast<uintptr_t>(d_arena) & 63u) return fail(ctx, GLC_EINVAL, w + ": d_arena is not 64-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_entries) & 7u) return fail(ctx, GLC_EINVAL, w + ": d_entries must be 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_out) & (sizeof(T) - 1u)) return fail(ctx, GLC_EINVAL, w + ": output pointer not aligned to its sample size");
+  if (n_segs > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, w + ": too many segments");
+  const RtbLayout lo{out};
+  DeviceGuard guard(ctx->device);
+  try {  // no C++ exception may cross the C ABI
+    std::vector<DecLanePush> act;
+    if (const int rc = stream_dec_plan_lanes(s, w, segs, n_segs, finish, total_len, &act)) return rc;
+    size_t at = 0;
+    for (uint64_t i = 0; i < s->n; ++i) {
+      const std::string lane = w + ": lane " + std::to_string(i);
+      uint64_t emits = 0;
+      if (at < act.size() && act[at].lane == i) emits = act[at++].plan.n_samples;
+      if (lo.len(i) != emits) return fail(ctx, GLC_EINVAL, lane + ": the layout's length is not what the push emits (glc_plan_stream_dec_push)");
+      if (!emits) continue;
+      if (lo.planes() && out->channel_stride < emits) return fail(ctx, GLC_EINVAL, lane + ": channel_stride is smaller than a plane");
+      if (s->n > 1 && out->clip_stride < lo.occupies(i)) return fail(ctx, GLC_EINVAL, lane + ": clip_stride is smaller than the clip");
+    }
+    {
+      const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_out), b1 = lo.end_of(d_out, sizeof(T));
+      const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_arena), a1 = a0 + arena_bytes;
+      const uintptr_t e0 = reinterpret_cast<uintptr_t>(d_entries), e1 = e0 + n_segs * sizeof(glc_store_entry);
+      if (n_segs && a0 < b1 && b0 < a1) return fail(ctx, GLC_EINVAL, w + ": the output extent overlaps the arena");
+      if (n_segs && e0 < b1 && b0 < e1) return fail(ctx, GLC_EINVAL, w + ": the output extent overlaps the entries");
+    }
+    return stream_dec_core<T>(s, act, segs, n_segs, d_arena, arena_bytes, d_entries, total_len, d_out, lo);
+  } catch (const std::bad_alloc &) {
+    return fail(ctx, GLC_ENOMEM, w + ": host allocation failed");
+  }
+}
+
+}  // namespace
+}  // extern "C++"
+
+int glc_plan_stream_dec_push(uint64_t frames_done, uint64_t n_frames, int finish, uint64_t total_len, glc_stream_dec_plan *out) {
+  if (!out) return GLC_EINVAL;
+  *out = glc_stream_dec_plan{0, 0};
+  if (!glc::plan_stream_dec_push(frames_done, n_frames, finish != 0, total_len, out)) {
+    glc::set_global_error("glc_plan_stream_dec_push: a sum that wraps, or a finish whose total_len does not plan to frames_done + n_frames frames");
+    return GLC_EINVAL;
+  }
+  return GLC_OK;
+}
+
+uint64_t glc_stream_dec_max_push(uint16_t channels) {
+  // every segment of a lane's push, with the slot the round packer counts for it, fits a decode round
+  return channels ? kDecodeChunkFrames : 0;
+}
+
+int glc_stream_dec_open(glc_ctx *ctx, uint16_t channels, uint64_t n_streams, glc_stream_dec **out) {
+  if (!ctx) return GLC_EINVAL;
+  if (!out) return fail(ctx, GLC_EINVAL, "glc_stream_dec_open: null argument");
+  *out = nullptr;
+  if (channels == 0 || n_streams == 0) return fail(ctx, GLC_EINVAL, "glc_stream_dec_open: no channels or no streams");
+  const uint64_t per_lane = 2ull * glc::kHop * channels * sizeof(float);
+  if (n_streams > (1ull << 46) / per_lane) return fail(ctx, GLC_EINVAL, "glc_stream_dec_open: too many streams");
+  DeviceGuard guard(ctx->device);
+  try {
+    std::unique_ptr<glc_stream_dec> s(new glc_stream_dec);
+    s->ctx = ctx, s->ch = channels, s->n = n_streams;
+    s->done.assign(n_streams, 0);
+    const hipError_t e = s->carry.reserve(n_streams * per_lane);
+    if (e != hipSuccess) return hip_fail(ctx, e, "glc_stream_dec_open: hipMalloc");
+    *out = s.release();
+    return GLC_OK;
+  } catch (const std::bad_alloc &) {
+    return fail(ctx, GLC_ENOMEM, "glc_stream_dec_open: host allocation failed");
+  }
+}
+
+void glc_stream_dec_close(glc_stream_dec *s) {
+  if (!s) return;
+  DeviceGuard guard(s->ctx->device);
+  (void)hipStreamSynchronize(s->ctx->stream);  // queued pushes may still read and write the session's buffers
+  delete s;
+}
+
+int glc_stream_dec_reset(glc_stream_dec *s, uint64_t stream) {
+  if (!s) return GLC_EINVAL;
+  if (stream >= s->n) return fail(s->ctx, GLC_EINVAL, "glc_stream_dec_reset: no such stream");
+  s->done[stream] = 0;
+  return GLC_OK;
+}
+
+int glc_stream_dec_frames_done(const glc_stream_dec *s, uint64_t stream, uint64_t *n) {
+  if (!s) return GLC_EINVAL;
+  if (!n || stream >= s->n) return fail(s->ctx, GLC_EINVAL, "glc_stream_dec_frames_done: null argument or no such stream");
+  *n = s->done[stream];
+  return GLC_OK;
+}
+
+int glc_stream_dec_push_device(glc_stream_dec *s, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
+                               const glc_stream_seg *segs, uint64_t n_segs, const uint8_t *finish, const uint64_t *total_len, void *d_out,
+                               glc_pcm_format out_fmt, const glc_clip_layout *out) {
+  if (!s) return GLC_EINVAL;
+  const std::string w("glc_stream_dec_push_device");
+  if (s->mode == 1) return fail(s->ctx, GLC_EINVAL, w + ": this session takes host pushes");
+  if (out_fmt != GLC_PCM_F32 && out_fmt != GLC_PCM_S16) return fail(s->ctx, GLC_EINVAL, w + ": out_fmt must be GLC_PCM_F32 or GLC_PCM_S16");
+  const int rc = out_fmt == GLC_PCM_F32 ? stream_dec_push_device_checked(s, w, d_arena, arena_bytes, d_entries, segs, n_segs, finish, total_len,
+                                                                         static_cast<float *>(d_out), out)
+                                        : stream_dec_push_device_checked(s, w, d_arena, arena_bytes, d_entries, segs, n_segs, finish, total_len,
+                                                                         static_cast<int16_t *>(d_out), out);
+  if (rc == GLC_OK) s->mode = 2;
+  return rc;
+}
+
+int glc_stream_dec_push(glc_stream_dec *s, const void *const *blobs, const uint64_t *blob_bytes, const glc_stream_seg *segs, uint64_t n_segs,
+                        const uint8_t *finish, const uint64_t *total_len, void *const *pcm_out, glc_pcm_format out_fmt, uint64_t *n_out) {
+  if (!s) return GLC_EINVAL;
+  glc_ctx *ctx = s->ctx;
+  const std::string w("glc_stream_dec_push");
+  if (s->mode == 2) return fail(ctx, GLC_EINVAL, w + ": this session takes device pushes");
+  if (out_fmt != GLC_PCM_F32 && out_fmt != GLC_PCM_S16) return fail(ctx, GLC_EINVAL, w + ": out_fmt must be GLC_PCM_F32 or GLC_PCM_S16");
+  if (!pcm_out || !n_out || (n_segs && (!blobs || !blob_bytes || !segs))) return fail(ctx, GLC_EINVAL, w + ": null argument");
+  if (n_segs > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, w + ": too many segments");
+  const uint32_t ch = s->ch;
+  const size_t elem = out_fmt == GLC_PCM_S16 ? 2 : 4;
+  DeviceGuard guard(ctx->device);
+  try {
+    std::vector<DecLanePush> act;
+    if (const int rc = stream_dec_plan_lanes(s, w, segs, n_segs, finish, total_len, &act)) return rc;
+    // the session's arena: the blobs back to back at multiples of 64, the entries behind them in the same pinned image
+    std::vector<glc_store_entry> ents(n_segs);
+    uint64_t arena_need = 64;
+    for (uint64_t j = 0; j < n_segs; ++j) {
+      if (!blobs[j]) return fail(ctx, GLC_EINVAL, w + ": segment " + std::to_string(j) + ": null blob");
+      if (blob_bytes[j] > (1ull << 46)) return fail(ctx, GLC_EINVAL, w + ": segment " + std::to_string(j) + ": blob_bytes too large");
+      ents[j] = glc_store_entry{arena_need - 64, blob_bytes[j], 0, 0, 1u};
+      arena_need += glc::align64(blob_bytes[j]);
+    }
+    std::vector<uint64_t> lens(s->n, 0);
+    uint64_t longest = 0;
+    for (const DecLanePush &a : act) {
+      if (a.plan.n_samples && !pcm_out[a.lane]) return fail(ctx, GLC_EINVAL, w + ": lane " + std::to_string(a.lane) + ": null output");
+      lens[a.lane] = a.plan.n_samples, longest = std::max(longest, a.plan.n_samples);
+    }
+    for (uint64_t i = 0; i < s->n; ++i) n_out[i] = lens[i] * ch;
+    const uint64_t stride = (std::max<uint64_t>(longest * ch, 1) + 3) / 4 * 4;
+    const size_t ents_at = static_cast<size_t>(arena_need - 64), up_bytes = ents_at + n_segs * sizeof(glc_store_entry);
+    const size_t out_bytes = static_cast<size_t>(s->n * stride * elem);
+    GLC_HIP(ctx, s->up.reserve(std::max<size_t>(up_bytes, 64)));
+    GLC_HIP(ctx, s->down.reserve(out_bytes));
+    int rc = rt_reserve(ctx, s->arena, std::max<size_t>(up_bytes, 64));
+    if (rc == GLC_OK) rc = rt_reserve(ctx, s->d_out, out_bytes);
+    if (rc != GLC_OK) return rc;
+    uint8_t *up = static_cast<uint8_t *>(s->up.p);
+    for (uint64_t j = 0; j < n_segs; ++j) std::memcpy(up + ents[j].offset, blobs[j], blob_bytes[j]);
+    if (n_segs) std::memcpy(up + ents_at, ents.data(), n_segs * sizeof(glc_store_entry));
+    if (up_bytes) GLC_HIP(ctx, hipMemcpyAsync(s->arena.p, up, up_bytes, hipMemcpyHostToDevice, ctx->stream));
+    const auto *d_entries = reinterpret_cast<const glc_store_entry *>(static_cast<const uint8_t *>(s->arena.p) + ents_at);
+    glc_clip_layout lay{s->n, static_cast<uint16_t>(ch), 0, stride, 0, 0, lens.data()};
+    const RtbLayout lo{&lay};
+    rc = out_fmt == GLC_PCM_F32 ? stream_dec_core<float>(s, act, segs, n_segs, s->arena.p, ents_at, d_entries, total_len,
+                                                         static_cast<float *>(s->d_out.p), lo)
+                                : stream_dec_core<int16_t>(s, act, segs, n_segs, s->arena.p, ents_at, d_entries, total_len,
+                                                           static_cast<int16_t *>(s->d_out.p), lo);
+    if (rc != GLC_OK) return rc;
+    s->mode = 1;
+    GLC_HIP(ctx, hipMemcpyAsync(s->down.p, s->d_out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint64_t i = 0; i < s->n; ++i)
+      if (lens[i]) std::memcpy(pcm_out[i], static_cast<const uint8_t *>(s->down.p) + i * stride * elem, lens[i] * ch * elem);
+    return GLC_OK;
+  } catch (const std::bad_alloc &) {
+    return fail(ctx, GLC_ENOMEM, w + ": host allocation failed");
+  }
+}
+
+int glc_debug_stream_dec_carry_device(glc_ctx *ctx, int save, int32_t prev, int32_t cur, uint16_t channels, float *d_blocks,
+                                      uint64_t n_slots, float *d_carry) {
+  const std::string w("glc_debug_stream_dec_carry_device");
+  if (!ctx) return GLC_EINVAL;
+  if (!d_blocks || !d_carry || channels == 0) return fail(ctx, GLC_EINVAL, w + ": null argument or channels == 0");
+  if ((reinterpret_cast<uintptr_t>(d_blocks) | reinterpret_cast<uintptr_t>(d_carry)) & 15u)
+    return fail(ctx, GLC_EINVAL, w + ": blocks and carry must be 16-byte aligned");
+  const int64_t n = static_cast<int64_t>(std::min<uint64_t>(n_slots, 0x7FFFFFFFull));
+  const bool ok = save ? (prev >= -1 && prev < n && cur >= 0 && cur < n) : (prev >= 0 && int64_t(prev) + 1 < n);
+  if (!ok) return fail(ctx, GLC_EINVAL, w + ": a slot outside the blocks");
+  DeviceGuard guard(ctx->device);
+  DevBuf d_desc;
+  GLC_HIP(ctx, d_desc.reserve(sizeof(glc::StreamCarry)));
+  const glc::StreamCarry desc{prev, save ? cur : -1, 0ull};
+  GLC_HIP(ctx, hipMemcpyAsync(d_desc.p, &desc, sizeof(desc), hipMemcpyHostToDevice, ctx->stream));
+  GLC_HIP(ctx, glc::launch_stream_dec_carry(save != 0, static_cast<const glc::StreamCarry *>(d_desc.p), 1, channels, d_blocks, d_carry,
+                                            ctx->stream));
+  GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return GLC_OK;
+}
+
 uint64_t glc_ctx_resident_stream(const glc_ctx *ctx) { return ctx ? ctx->dec_uid : 0; }
 
 int glc_decode_resident(glc_ctx *ctx, uint64_t stream_id, float *pcm_out, uint64_t cap, uint64_t *n_out) {

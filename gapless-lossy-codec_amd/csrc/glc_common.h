@@ -107,6 +107,26 @@ inline bool plan_stream_push(uint64_t received, uint64_t n_new, bool finish, glc
   return true;
 }
 
+// What a push of frames [done, done + n) emits on a lane of a streaming decode (include/glc.h
+// glc_plan_stream_dec_push), the ONE statement of it.  A stream of L samples per channel has nf = plan_encode(L, 1)
+// frames; decoded sample t of channel c lies at the un-trimmed interleaved position 512 + t ch + c (the delay counts
+// interleaved samples, Q3), and the receiver learns L only at the finish.  After D frames a lane has emitted
+// emitted(D) = 1024 D - 512 samples per channel (0 at D = 0): everything up to there is final whatever follows and
+// emitted(D) < L for every D <= nf, so nothing emitted is trimmed later.  A finish with the total L must plan to
+// exactly done + n frames and emits [emitted(done), L).  false: a wrapping sum, or such a finish.
+inline uint64_t stream_dec_emitted(uint64_t done) { return done ? done * kHop - kHop / 2 : 0; }
+inline bool plan_stream_dec_push(uint64_t done, uint64_t n, bool finish, uint64_t total_len, glc_stream_dec_plan *out) {
+  if (n > UINT64_MAX - done || done + n > (UINT64_MAX >> 12)) return false;
+  const uint64_t first = stream_dec_emitted(done);
+  if (finish) {
+    if (total_len > (UINT64_MAX >> 12) || plan_encode(total_len, 1).n_frames != done + n || done + n == 0) return false;
+    *out = glc_stream_dec_plan{first, total_len - first};
+    return true;
+  }
+  *out = glc_stream_dec_plan{first, stream_dec_emitted(done + n) - first};
+  return true;
+}
+
 // Gapless trim of a decoded stream, src/codec.rs:756-765: the interleaved samples [start, start + n) of
 // the (n_frames + 1) hops.  The delay counts INTERLEAVED samples (quirk Q3).
 struct Trim {

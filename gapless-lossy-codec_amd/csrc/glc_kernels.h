@@ -445,6 +445,37 @@ struct StoreDraw {
 };
 hipError_t launch_store_plan_crops(const StoreDraw &a, hipStream_t s);
 
+// The segment planner of a streaming decode push (glc_stream_dec_push_device; DESIGN section 3, "a lane's carry"):
+// segment j of n_segs is the blob entries[j] names - device data - and owns table rows [segs[j].first_row,
+// segs[j].first_row + segs[j].rows) of its round (the host's word, from the table image).  Written, one launch per push:
+//   dir[j]      usable: {arena + offset, bytes, first_row, rows, {0, rows}}: the whole blob is the window, and its header
+//               must carry exactly rows / ch frames; unusable: {arena, 0, first_row, 0, {0, 0}} - the slot's rows are
+//               empty rows and nothing is read
+//   verdict[j]  0, or kCompactNoBlob (stored == 0, offset no multiple of 64, [offset, offset + bytes) not inside the arena)
+// No load leaves entries[0 .. n_segs); `arena` is a number here, nothing of the arena is read.
+struct StreamDecSeg {
+  uint32_t first_row, rows;
+};
+hipError_t launch_stream_dec_plan(uint64_t arena, uint64_t arena_bytes, const glc_store_entry *entries, const StreamDecSeg *segs,
+                                  uint32_t n_segs, CompactBlob *dir, uint32_t *verdict, hipStream_t s);
+
+// The carry of a streaming decode ("a lane's carry"): per lane 2 x [ch][1024] floats at element
+// `carry` of the session's buffer (a multiple of 4) - (a) the finished sums of the lane's last hop, (b) the second half
+// of its last frame's windowed block.  Two roles, one descriptor per lane of the round that takes part:
+//   load (in front of D2)  (a) -> the second half of block slot `prev`, (b) -> the second half of slot prev + 1: the
+//                          pseudo-slots of the lane, behind the round's real frames.  `cur` is not used.  The sums
+//                          re-enter D2 as the second half of a slot whose hop has no `cur`, so D2 adds nothing to them.
+//   save (behind D1)       (a) <- d2_sum(second half of slot `prev` (-1: absent, +0.0), first half of slot `cur`) - the
+//                          sum D2 would form, by D2's own function and in its order; (b) <- the second half of slot `cur`.
+// blocks: [slot][ch][2048] floats, 16-byte aligned.  Memory-bound: 16-byte loads and stores, a grid of (units of 256
+// float4, lanes), the lane's descriptor read once per workgroup; ordinary vector stores, no flags, no atomics.
+struct StreamCarry {
+  int32_t prev, cur;
+  uint64_t carry;
+};
+hipError_t launch_stream_dec_carry(bool save, const StreamCarry *desc, uint32_t n_desc, uint32_t ch, float *blocks, float *carry,
+                                   hipStream_t s);
+
 // Eviction (glc_store_compact_device; DESIGN section 3, "evicting from the store").  include/glc.h states the rules;
 // the two launchers below are all of the call.
 //   E1  k_store_evict_scan, ONE workgroup of 1024 threads over chunks of 1024 entries with a carry (k_store_place's

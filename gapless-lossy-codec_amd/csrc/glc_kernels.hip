@@ -1995,6 +1995,60 @@ __global__ __launch_bounds__(256) void k_store_plan_crops(StoreDraw a) {
 }
 
 // ------------------------------------------------------------------------------------------
+// The segment planner of glc_stream_dec_push_device (glc_kernels.h launch_stream_dec_plan has the rules): one thread
+// per segment, one 32-byte entry in, one 32-byte directory entry and one verdict word out - k_store_plan_crops' rules
+// for an entry, without a selection.  Latency-bound (one load per thread); ordinary vector loads and stores.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_stream_dec_plan(unsigned long long arena, unsigned long long arena_bytes,
+                                                          const glc_store_entry *__restrict__ entries,
+                                                          const StreamDecSeg *__restrict__ segs, unsigned n_segs,
+                                                          CompactBlob *__restrict__ dir, unsigned *__restrict__ verdict) {
+  const unsigned j = blockIdx.x * 256u + threadIdx.x;
+  if (j >= n_segs) return;
+  const glc_store_entry e = entries[j];
+  const StreamDecSeg sg = segs[j];
+  // each term is bounded before the difference is formed: nothing wraps (k_store_plan_crops' way)
+  const bool usable = e.stored != 0 && (e.offset & 63ull) == 0 && e.offset <= arena_bytes && e.bytes <= arena_bytes - e.offset;
+  dir[j] = usable ? CompactBlob{arena + e.offset, e.bytes, sg.first_row, sg.rows, {0u, sg.rows}}
+                  : CompactBlob{arena, 0ull, sg.first_row, 0u, {0u, 0u}};
+  verdict[j] = usable ? 0u : kCompactNoBlob;
+}
+
+// ------------------------------------------------------------------------------------------
+// The carry of a streaming decode (glc_kernels.h launch_stream_dec_carry has the two roles).  Workgroup (u, lane): unit
+// u = half * ch + c is the 1024 floats of channel c of carry part `half` (0: the hop's sums, 1: the block's second
+// half), one float4 per thread; the lane's descriptor is one block-uniform load.  The save role forms the sums with
+// d2_sum on the operands and in the order D2 uses, so a carried sum has the bits D2 would have written.
+// ------------------------------------------------------------------------------------------
+template <bool SAVE>
+__global__ __launch_bounds__(256) void k_stream_dec_carry(const StreamCarry *__restrict__ desc, unsigned ch,
+                                                           float *__restrict__ blocks, float *__restrict__ carry) {
+  const StreamCarry d = desc[blockIdx.y];
+  const unsigned half = blockIdx.x / ch, c = blockIdx.x - half * ch;
+  const unsigned i = threadIdx.x * 4u;
+  float *held = carry + d.carry + (static_cast<size_t>(half) * ch + c) * kHopI + i;
+  if constexpr (!SAVE) {
+    float *dst = blocks + ((static_cast<size_t>(d.prev) + half) * ch + c) * kFrameI + kHopI + i;
+    *reinterpret_cast<float4 *>(dst) = *reinterpret_cast<const float4 *>(held);
+  } else {
+    const float *cur = blocks + (static_cast<size_t>(d.cur) * ch + c) * kFrameI + i;
+    float4 out;
+    if (half) {
+      out = *reinterpret_cast<const float4 *>(cur + kHopI);
+    } else {
+      const bool has_prev = d.prev >= 0;
+      const float4 q = *reinterpret_cast<const float4 *>(cur);
+      float4 p = float4{0.0f, 0.0f, 0.0f, 0.0f};
+      if (has_prev) p = *reinterpret_cast<const float4 *>(blocks + (static_cast<size_t>(d.prev) * ch + c) * kFrameI + kHopI + i);
+      const float pv[4] = {p.x, p.y, p.z, p.w}, cv[4] = {q.x, q.y, q.z, q.w};
+      out = float4{d2_sum(pv, cv, has_prev, true, 0), d2_sum(pv, cv, has_prev, true, 1), d2_sum(pv, cv, has_prev, true, 2),
+                   d2_sum(pv, cv, has_prev, true, 3)};
+    }
+    *reinterpret_cast<float4 *>(held) = out;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // Eviction: glc_store_compact_device (glc_kernels.h StoreEvict has the plan, include/glc.h the rules).
 // E1 is k_store_place's shape: one workgroup, chunks of 1024 entries, three Hillis-Steele scans per chunk (the
 // maximum of the candidates' ends, the kept bytes, the kept count) with their carries in registers.  Every thread
@@ -2855,6 +2909,27 @@ hipError_t launch_store_plan_crops(const StoreDraw &a, hipStream_t s) {
   const uint64_t threads = a.n_crops * a.max_hops, blocks = (threads + 255) / 256;
   if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_store_plan_crops, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_stream_dec_plan(uint64_t arena, uint64_t arena_bytes, const glc_store_entry *entries, const StreamDecSeg *segs,
+                                  uint32_t n_segs, CompactBlob *dir, uint32_t *verdict, hipStream_t s) {
+  if (n_segs == 0) return hipSuccess;
+  if (!entries || !segs || !dir || !verdict || (arena & 63u)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_stream_dec_plan, dim3((n_segs + 255u) / 256u), dim3(256), 0, s, arena, arena_bytes, entries, segs, n_segs, dir,
+                     verdict);
+  return hipGetLastError();
+}
+
+hipError_t launch_stream_dec_carry(bool save, const StreamCarry *desc, uint32_t n_desc, uint32_t ch, float *blocks, float *carry,
+                                   hipStream_t s) {
+  if (n_desc == 0) return hipSuccess;
+  if (!desc || !blocks || !carry || ch == 0 || ch > 32767u) return hipErrorInvalidValue;
+  for (uint32_t d0 = 0; d0 < n_desc; d0 += 65535u) {  // blockIdx.y is 16 bits wide
+    const dim3 grid(2u * ch, std::min(n_desc - d0, 65535u));
+    if (save) hipLaunchKernelGGL(k_stream_dec_carry<true>, grid, dim3(256), 0, s, desc + d0, ch, blocks, carry);
+    else hipLaunchKernelGGL(k_stream_dec_carry<false>, grid, dim3(256), 0, s, desc + d0, ch, blocks, carry);
+  }
   return hipGetLastError();
 }
 

@@ -937,6 +937,84 @@ int glc_stream_enc_segment(const glc_stream_enc *s, uint64_t stream, uint64_t k,
  * then the lane is cleared.  GLC_EINVAL while the lane is not finished. */
 int glc_stream_enc_frames(glc_stream_enc *s, uint64_t stream, glc_frames **out);
 
+/* ---- streaming decode: segment blobs in, PCM out, many live streams per launch chain ------- */
+
+/* The receiving half of a stream: the segments glc_stream_enc_* emits are decoded as they arrive, and the
+ * concatenation of a lane's outputs over ANY chunking is bit for bit glc_decode(glc_frames_from_compact(segments)).
+ *
+ * Host only: what a push of n_frames frames emits on a lane that has taken frames_done so far.  A stream of L samples
+ * per channel has nf = glc_plan_encode(L, 1).n_frames frames, and decoded sample t of channel c lies at the un-trimmed
+ * interleaved position 512 + t * channels + c; the receiver learns L only at the finish.  After D frames a lane has
+ * emitted emitted(D) = 1024 D - 512 samples per channel (0 at D = 0) - whole hops cannot be emitted: with two or more
+ * channels the reference's trim cuts into the last ones.  Without `finish` the push emits [emitted(D), emitted(D + n));
+ * with `finish` and the total length total_len = L, which must plan to exactly frames_done + n_frames frames, it
+ * emits [emitted(D), L): at most 512 samples and a hop per channel more.  emitted(D) < L for every D <= nf.
+ * GLC_EINVAL: a null pointer, a sum that wraps, a finish whose total_len does not plan to frames_done + n_frames. */
+typedef struct glc_stream_dec_plan {
+  uint64_t first_sample;  /* per channel: samples emitted before this push */
+  uint64_t n_samples;     /* per channel: samples this push emits */
+} glc_stream_dec_plan;
+int glc_plan_stream_dec_push(uint64_t frames_done, uint64_t n_frames, int finish, uint64_t total_len,
+                             glc_stream_dec_plan *out);
+
+/* A session of n_streams independent lanes of `channels` channels on one context.  The session owns the lanes' carry
+ * in device memory of its own (2 * 1024 * channels floats per lane: the finished, not yet emitted sums of the last
+ * hop, and the second half of the last frame's windowed block); the host keeps the frames done per lane.  No workspace
+ * of the context holds lane state: any other call on the context may run between two pushes, and several sessions may
+ * live on one context.  Close a session before its context is destroyed.  open, close, reset and the getters leave
+ * the context as it was.  A session is not thread-safe, like its context.
+ * GLC_EINVAL: a null pointer, channels == 0, n_streams == 0 or so many that the buffer's size wraps. */
+typedef struct glc_stream_dec glc_stream_dec;
+int glc_stream_dec_open(glc_ctx *ctx, uint16_t channels, uint64_t n_streams, glc_stream_dec **out);
+void glc_stream_dec_close(glc_stream_dec *s);
+/* Lane `stream` back to "no frame taken". */
+int glc_stream_dec_reset(glc_stream_dec *s, uint64_t stream);
+/* Frames one lane may take in one push (over all its segments of the push). */
+uint64_t glc_stream_dec_max_push(uint16_t channels);
+int glc_stream_dec_frames_done(const glc_stream_dec *s, uint64_t stream, uint64_t *n);
+
+/* Device push.  segs[n_segs] (host) and d_entries[n_segs] (device, 8-byte aligned, never read by the host) are what
+ * glc_stream_enc_push_device returned, possibly concatenated over several encoder pushes: ascending by (stream,
+ * first_frame), a lane's segments consecutive and starting at its frames done - so a clip stored as k segments
+ * decodes in one call.  d_arena / arena_bytes: the arena the entries point into (64-byte aligned).  finish[i] != 0
+ * (host array per lane, or NULL for none) ends lane i with this push at total_len[i] samples per channel (total_len
+ * may be NULL when nothing finishes); a finish may bring no frames.  A finished lane is fresh afterwards.
+ * `out` describes n_streams clips in d_out (out->n_clips == n_streams, out->channels == the session's): lane i's
+ * emitted samples - glc_plan_stream_dec_push of its frames - are clip i, and out->lengths[i] (or out->length) must be
+ * exactly that plan's n_samples, 0 included.  out_fmt: GLC_PCM_F32 (d_out holds floats) or GLC_PCM_S16 (int16_t,
+ * narrowed in the overlap-add as the _i16 calls narrow); the layout counts elements of that type.  No element of
+ * d_out outside the lanes' spans is written.
+ * A segment is a whole blob whose header must carry exactly the segment's frame count.  Untrusted: a segment whose
+ * entry is unusable (stored == 0, an offset that is no multiple of 64, [offset, offset + bytes) not inside the arena:
+ * GLC_COMPACT_NO_BLOB | GLC_COMPACT_BAD_HEADER, nothing of it is read) or whose header fails the check
+ * (GLC_COMPACT_BAD_HEADER) contributes +0.0 blocks for all its frames; rows are kept or rejected by the rules of the
+ * compact decode family; neighbouring segments and lanes are not affected; no load leaves the arena or
+ * d_entries[0 .. n_segs).  glc_decode_compact_last_status afterwards gives one status per SEGMENT.
+ * Segments are packed into rounds as the batch decode packs clips; per round one row-table pass, at most two carry
+ * launches, one inverse transform and one overlap-add, whatever the number of lanes, behind one planner launch per
+ * push.  Queued on glc_ctx_stream of the session's context, NOT synchronised; nothing is copied to the host and
+ * nothing from it but the pinned table image; the call blocks only where a workspace has to grow and on the table
+ * image of the previous batch call.  Afterwards the context is as the compact decode family leaves it: no stream
+ * resident, an open decode session closed, the kept plan dropped.
+ * GLC_EINVAL, before anything is queued and changing nothing (the lanes included): a null or misaligned pointer, a
+ * segment out of order, not at its lane's frames done or of no frames, a lane above glc_stream_dec_max_push, a finish
+ * glc_plan_stream_dec_push refuses, a layout that does not match, an output extent that overlaps the arena or the
+ * entries, an out_fmt other than the two, a session that has taken a host push. */
+int glc_stream_dec_push_device(glc_stream_dec *s, const void *d_arena, uint64_t arena_bytes,
+                               const glc_store_entry *d_entries, const glc_stream_seg *segs, uint64_t n_segs,
+                               const uint8_t *finish, const uint64_t *total_len,
+                               void *d_out, glc_pcm_format out_fmt, const glc_clip_layout *out);
+
+/* Host push.  blobs[j] / blob_bytes[j]: segment segs[j] in host memory (what glc_stream_enc_segment hands out), in
+ * the order above.  The blobs go through pinned staging into an arena the session owns, the entries are made by the
+ * host, the device push runs and lane i's samples come down to pcm_out[i] (interleaved, of out_fmt; may be NULL where
+ * the lane emits nothing), n_out[i] of them (per lane, all channels counted; the caller sizes pcm_out[i] with
+ * glc_plan_stream_dec_push).  Synchronises.  A session is used through host pushes or through device pushes, never
+ * both: the first push decides.  A refused push changes nothing. */
+int glc_stream_dec_push(glc_stream_dec *s, const void *const *blobs, const uint64_t *blob_bytes,
+                        const glc_stream_seg *segs, uint64_t n_segs, const uint8_t *finish, const uint64_t *total_len,
+                        void *const *pcm_out, glc_pcm_format out_fmt, uint64_t *n_out);
+
 /* ---- tables (for inspection / parity tests) ---------------------------------------------- */
 
 /* Copies of the host tables of a context: MdctTables.cos_table [1024*2048] (row k), window

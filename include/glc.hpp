@@ -718,6 +718,98 @@ class StreamEncoder {
   uint64_t n_ = 0;
 };
 
+// What a push of n_frames frames emits on a lane that has taken frames_done so far (glc_plan_stream_dec_push);
+// throws where a finish's total_len does not plan to exactly frames_done + n_frames frames.
+inline glc_stream_dec_plan plan_stream_dec_push(uint64_t frames_done, uint64_t n_frames, bool finish = false, uint64_t total_len = 0) {
+  glc_stream_dec_plan p{};
+  detail::check(glc_plan_stream_dec_push(frames_done, n_frames, finish ? 1 : 0, total_len, &p));
+  return p;
+}
+
+// Decoder::decode fed in segments (glc.h glc_stream_dec_*): n_streams independent lanes of `channels` channels on a
+// context of its own.  The concatenation of a lane's outputs over any chunking is bit for bit Decoder::decode of the
+// stream its segments assemble to.  Host pushes (push) or device pushes (push_device), not both on one object.
+class StreamDecoder {
+ public:
+  struct Segment {
+    uint64_t first_frame, n_frames;
+    const void *blob;
+    uint64_t bytes;
+  };
+  StreamDecoder(uint32_t sample_rate, uint16_t channels, uint64_t n_streams = 1, int device = 0) : channels_(channels), n_(n_streams) {
+    detail::check(glc_ctx_create(device, sample_rate, &ctx_));
+    const int rc = glc_stream_dec_open(ctx_, channels, n_streams, &s_);
+    if (rc != GLC_OK) {
+      const Error e(rc, glc_last_error(ctx_));
+      glc_ctx_destroy(ctx_);
+      throw e;
+    }
+  }
+  ~StreamDecoder() {
+    glc_stream_dec_close(s_);  // before its context
+    glc_ctx_destroy(ctx_);
+  }
+  StreamDecoder(const StreamDecoder &) = delete;
+  StreamDecoder &operator=(const StreamDecoder &) = delete;
+  uint64_t n_streams() const { return n_; }
+  uint64_t max_push() const { return glc_stream_dec_max_push(channels_); }
+  uint64_t frames_done(uint64_t stream = 0) const {
+    uint64_t n = 0;
+    detail::check(glc_stream_dec_frames_done(s_, stream, &n), ctx_);
+    return n;
+  }
+  void reset(uint64_t stream = 0) { detail::check(glc_stream_dec_reset(s_, stream), ctx_); }
+  // every lane at once (glc_stream_dec_push): pcm_out[i] receives n_out[i] samples of out_fmt
+  void push(const void *const *blobs, const uint64_t *blob_bytes, const glc_stream_seg *segs, uint64_t n_segs, const uint8_t *finish,
+            const uint64_t *total_len, void *const *pcm_out, glc_pcm_format out_fmt, uint64_t *n_out) {
+    detail::check(glc_stream_dec_push(s_, blobs, blob_bytes, segs, n_segs, finish, total_len, pcm_out, out_fmt, n_out), ctx_);
+  }
+  // one lane, the others receive nothing: the samples its consecutive segments emit; finish with the stream's
+  // samples per channel ends it
+  std::vector<float> push(uint64_t stream, const std::vector<Segment> &segments, bool finish = false, uint64_t total_len = 0) {
+    return push_one<float>(stream, segments, finish, total_len, GLC_PCM_F32);
+  }
+  std::vector<int16_t> push_i16(uint64_t stream, const std::vector<Segment> &segments, bool finish = false, uint64_t total_len = 0) {
+    return push_one<int16_t>(stream, segments, finish, total_len, GLC_PCM_S16);
+  }
+  // glc_stream_dec_push_device: queued on the context's stream, not synchronised
+  void push_device(const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries, const glc_stream_seg *segs, uint64_t n_segs,
+                   const uint8_t *finish, const uint64_t *total_len, void *d_out, glc_pcm_format out_fmt, const glc_clip_layout &out) {
+    detail::check(glc_stream_dec_push_device(s_, d_arena, arena_bytes, d_entries, segs, n_segs, finish, total_len, d_out, out_fmt, &out),
+                  ctx_);
+  }
+  void synchronize() { detail::check(glc_ctx_synchronize(ctx_), ctx_); }
+  glc_ctx *ctx() { return ctx_; }
+  glc_stream_dec *handle() { return s_; }
+
+ private:
+  template <typename T>
+  std::vector<T> push_one(uint64_t stream, const std::vector<Segment> &segments, bool finish, uint64_t total_len, glc_pcm_format fmt) {
+    if (stream >= n_) throw Error(GLC_EINVAL, "StreamDecoder::push: no such stream");
+    uint64_t frames = 0;
+    std::vector<const void *> blobs;
+    std::vector<uint64_t> bytes;
+    std::vector<glc_stream_seg> segs;
+    for (const Segment &g : segments) {
+      blobs.push_back(g.blob), bytes.push_back(g.bytes), segs.push_back(glc_stream_seg{stream, g.first_frame, g.n_frames});
+      frames += g.n_frames;
+    }
+    std::vector<T> out;
+    if (!frames && !finish) return out;
+    out.resize(plan_stream_dec_push(frames_done(stream), frames, finish, total_len).n_samples * channels_);
+    std::vector<uint8_t> fin(n_, 0);
+    std::vector<uint64_t> total(n_, 0), n_out(n_, 0);
+    std::vector<void *> outs(n_, nullptr);
+    fin[stream] = finish ? 1 : 0, total[stream] = total_len, outs[stream] = out.data();
+    push(blobs.data(), bytes.data(), segs.data(), segs.size(), fin.data(), total.data(), outs.data(), fmt, n_out.data());
+    return out;
+  }
+  glc_ctx *ctx_ = nullptr;
+  glc_stream_dec *s_ = nullptr;
+  uint16_t channels_ = 0;
+  uint64_t n_ = 0;
+};
+
 // save_encoded / load_encoded — src/codec.rs:774-786
 inline void save_encoded(const EncodedAudio &e, const std::string &path) { detail::check(glc_save(e.handle(), path.c_str())); }
 inline EncodedAudio load_encoded(const std::string &path) {

@@ -208,16 +208,25 @@ int glc_debug_store_plan_device(glc_ctx *ctx, const void *d_arena, uint64_t aren
                                 const int64_t *d_starts, uint64_t length, const float *d_out, const glc_clip_layout *out,
                                 void *dir, void *desc, uint32_t *verdict);
 
+/* The carry kernel of the streaming decode (k_stream_dec_carry) alone, for ONE lane whose carry lies at d_carry[0 ..
+ * 2 * 1024 * channels): save == 0 copies the two carried halves into the second halves of block slots `prev` and prev + 1
+ * of d_blocks ([n_slots][channels][2048] floats); save != 0 writes the carry from slots `prev` (-1: absent) and `cur` as a
+ * push that ends with the frame in `cur` does.  Slots outside [0, n_slots) are GLC_EINVAL.  Synchronises.
+ * tests/test_stream_decode.py drives it with halves of -0.0, which no decode produces, and checks the sign bit. */
+int glc_debug_stream_dec_carry_device(glc_ctx *ctx, int save, int32_t prev, int32_t cur, uint16_t channels, float *d_blocks,
+                                      uint64_t n_slots, float *d_carry);
+
 /* The packed bytes an in-place glc_store_compact_device of `ctx` moves per round (include/glc.h): a multiple of 64, 0
  * restores the default.  tests/test_store_compact.py puts blobs of a few hundred bytes across round boundaries with
  * rounds of 1 KiB and 4 KiB; tools/store_compact_bench.cpp measures the rounds the default was chosen from. */
 int glc_debug_set_store_compact_round(glc_ctx *ctx, uint64_t bytes);
 
-/* What the library holds of the device at this moment, over all contexts and stream encoders of the process: counts[0]
- * device buffers, [1] pinned host buffers, [2] streams of its own (a caller's stream, glc_ctx_set_stream, is not one),
- * [3] events.  Every one of them belongs to a context or a stream encoder (or lives for the length of one call) and is
- * released with it, so the counts after glc_ctx_destroy / glc_stream_enc_close are the counts before the matching
- * create / open, whatever ran in between and however it ended (tests/test_ctx_resources.py).  Relaxed atomic counters:
+/* What the library holds of the device at this moment, over all contexts, stream encoders and stream decoders of the
+ * process: counts[0] device buffers, [1] pinned host buffers, [2] streams of its own (a caller's stream,
+ * glc_ctx_set_stream, is not one), [3] events.  Every one of them belongs to a context, a stream encoder or a stream
+ * decoder (or lives for the length of one call) and is released with it, so the counts after glc_ctx_destroy /
+ * glc_stream_enc_close / glc_stream_dec_close are the counts before the matching create / open, whatever ran in between
+ * and however it ended (tests/test_ctx_resources.py, tests/test_stream_decode.py).  Relaxed atomic counters:
  * no context, no device, nothing is waited for; meaningful when no other thread is inside the library. */
 int glc_debug_live_resources(uint64_t counts[4]);
 

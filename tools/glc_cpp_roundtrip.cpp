@@ -2,6 +2,7 @@
 // Decoder API) the way tests/integration_tests.rs drives the Rust API: encode interleaved f32 PCM,
 // save, load, decode both ways, and leave the artefacts on disk for the caller to compare.
 //   glc_cpp_roundtrip <in.f32> <sample_rate> <channels> <out.glc> <out.f32>
+//   ... <chunk_sample_frames> <stream_out.glc> [<stream_out.f32>]   the stream encoder (and decoder) instead
 // Build: g++ -O2 -std=c++17 -Iinclude tools/glc_cpp_roundtrip.cpp -Lgapless-lossy-codec_amd -lglc_hip
 #include <algorithm>
 #include <cstdio>
@@ -13,12 +14,12 @@
 #include "glc.hpp"
 
 int main(int argc, char **argv) {
-  if (argc != 6 && argc != 8) {
-    std::fprintf(stderr, "usage: %s in.f32 sample_rate channels out.glc out.f32 [chunk_sample_frames stream_out.glc]\n", argv[0]);
+  if (argc != 6 && argc != 8 && argc != 9) {
+    std::fprintf(stderr, "usage: %s in.f32 sample_rate channels out.glc out.f32 [chunk_sample_frames stream_out.glc [stream_out.f32]]\n", argv[0]);
     return 2;
   }
   try {
-    if (argc == 8) {
+    if (argc >= 8) {
       // the streaming encoder through the C++ mirror: the file in chunks of argv[6] sample frames, the finish as an
       // empty push; the segments' frame ranges tile the stream; the bytes go to argv[7] for the caller to compare
       std::ifstream in(argv[1], std::ios::binary);
@@ -46,6 +47,25 @@ int main(int argc, char **argv) {
         next += g.n_frames;
       }
       if (!se.segments(0).empty()) return std::fprintf(stderr, "the idle lane has segments\n"), 1;
+      if (argc == 9) {
+        // the streaming decoder through the C++ mirror: the segments one push each as they were emitted, the finish with
+        // the last one; every push emits what glc::plan_stream_dec_push says; the samples go to argv[8]
+        glc::StreamDecoder sd(sr, ch, 2);  // lane 1 again
+        const std::vector<glc::StreamEncoder::Segment> segs = se.segments(1);
+        std::vector<float> played;
+        for (size_t k = 0; k < segs.size(); ++k) {
+          const bool last = k + 1 == segs.size();
+          const glc_stream_dec_plan plan = glc::plan_stream_dec_push(sd.frames_done(1), segs[k].n_frames, last, received);
+          const std::vector<float> got =
+              sd.push(1, {glc::StreamDecoder::Segment{segs[k].first_frame, segs[k].n_frames, segs[k].blob, segs[k].bytes}}, last, received);
+          if (got.size() != plan.n_samples * ch || plan.first_sample * ch != played.size())
+            return std::fprintf(stderr, "a push does not emit what the plan says\n"), 1;
+          played.insert(played.end(), got.begin(), got.end());
+        }
+        if (sd.frames_done(1) != 0 || sd.frames_done(0) != 0) return std::fprintf(stderr, "a finished lane is not fresh\n"), 1;
+        std::ofstream out(argv[8], std::ios::binary);
+        out.write(reinterpret_cast<const char *>(played.data()), static_cast<std::streamsize>(played.size() * sizeof(float)));
+      }
       const glc::EncodedAudio e = se.encoded(1);
       if (e.n_frames() != next || !se.segments(1).empty()) return std::fprintf(stderr, "encoded(): wrong frame count\n"), 1;
       glc::save_encoded(e, argv[7]);
