@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/glc_debug.h"
+#include "glc_args.hpp"
 #include "glc_common.h"
 #include "glc_kernels.h"
 #include "glc_resources.hpp"
@@ -253,6 +254,18 @@ struct DeviceGuard {
     if (prev >= 0) (void)hipSetDevice(prev);
   }
 };
+
+// The body of a device batch, store or stream call behind its argument checks: the context's device is current while
+// it runs, and no C++ exception crosses the C ABI.  `w` names the call.
+template <typename Body>
+int on_device(glc_ctx *ctx, const std::string &w, Body body) {
+  DeviceGuard guard(ctx->device);
+  try {
+    return body();
+  } catch (const std::bad_alloc &) {
+    return fail(ctx, GLC_ENOMEM, w + ": host allocation failed");
+  }
+}
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -661,7 +674,7 @@ int glc_compact_device_records(glc_ctx *ctx, const void *d_records, uint64_t n_f
   if (!ctx || !d_blob || !info || (!d_records && n_frames)) return fail(ctx, GLC_EINVAL, "glc_compact_device_records: null argument");
   if (channels == 0) return fail(ctx, GLC_EINVAL, "glc_compact_device_records: channels == 0");
   // the kernels read rows as short4 and write the header as 64-bit words (include/glc.h)
-  if (reinterpret_cast<uintptr_t>(d_records) % 8 != 0 || reinterpret_cast<uintptr_t>(d_blob) % 8 != 0)
+  if (!all_aligned(8, d_records, d_blob))
     return fail(ctx, GLC_EINVAL, "glc_compact_device_records: d_records and d_blob must be 8-byte aligned");
   const glc::CompactLayout l = glc::compact_layout(channels, n_frames);
   if (cap < l.bound) return fail(ctx, GLC_EINVAL, "glc_compact_device_records: blob buffer smaller than glc_compact_bound()");
@@ -803,12 +816,9 @@ int glc_encode_int(glc_ctx *ctx, const void *pcm, glc_pcm_format fmt, uint32_t b
 
 int glc_pcm_widen_device(glc_ctx *ctx, const void *d_in, glc_pcm_format fmt, uint32_t bits, uint64_t n, float *d_out) {
   if (!ctx || ((!d_in || !d_out) && n)) return fail(ctx, GLC_EINVAL, "glc_pcm_widen_device: null argument");
-  if (fmt != GLC_PCM_S16 && fmt != GLC_PCM_S32 && fmt != GLC_PCM_F32)
-    return fail(ctx, GLC_EINVAL, "glc_pcm_widen_device: unknown sample format");
-  if (fmt != GLC_PCM_F32 && (bits == 0 || bits > (fmt == GLC_PCM_S16 ? 16u : 32u)))
-    return fail(ctx, GLC_EINVAL, "glc_pcm_widen_device: bits must be 1..16 for 16-bit samples, 1..32 for 32-bit ones");
-  const uintptr_t mis = (reinterpret_cast<uintptr_t>(d_in) & (fmt == GLC_PCM_S16 ? 1u : 3u)) | (reinterpret_cast<uintptr_t>(d_out) & 3u);
-  if (n && mis) return fail(ctx, GLC_EINVAL, "glc_pcm_widen_device: a pointer is not aligned to its sample size");
+  if (const char *bad = fmt_fault(fmt, bits)) return fail(ctx, GLC_EINVAL, std::string("glc_pcm_widen_device: ") + bad);
+  if (n && (!aligned(d_in, pcm_elem(fmt)) || !aligned(d_out, sizeof(float))))
+    return fail(ctx, GLC_EINVAL, "glc_pcm_widen_device: a pointer is not aligned to its sample size");
   if (n == 0) return GLC_OK;
   DeviceGuard guard(ctx->device);
   if (fmt == GLC_PCM_F32) {
@@ -825,7 +835,7 @@ static int encode_pipeline(glc_ctx *ctx, const void *pcm_any, glc_pcm_format fmt
   const float *pcm = static_cast<const float *>(pcm_any);          // GLC_PCM_F32
   const uint8_t *pcm_int = static_cast<const uint8_t *>(pcm_any);  // the integer formats
   const bool is_int = fmt != GLC_PCM_F32;
-  const size_t elem = fmt == GLC_PCM_S16 ? 2 : 4;
+  const size_t elem = pcm_elem(fmt);
   if (out) *out = nullptr;
   const glc_plan plan = glc::plan_encode(n_samples, channels);
   if (plan.n_frames == 0)
@@ -1203,7 +1213,7 @@ int encode_batch_round(glc_ctx *ctx, const std::vector<BatchClip> &clips, const 
                        std::vector<std::unique_ptr<glc_frames>> &result) {
   const uint32_t ch = channels;
   const bool is_int = fmt != GLC_PCM_F32;
-  const uint64_t elem = fmt == GLC_PCM_S16 ? 2 : 4;  // bytes per sample as uploaded
+  const uint64_t elem = pcm_elem(fmt);  // bytes per sample as uploaded
   const uint64_t n = clips.size();
   std::vector<uint64_t> clip_frames(n);
   for (uint64_t i = 0; i < n; ++i) clip_frames[i] = clips[i].plan.n_frames;
@@ -1600,6 +1610,14 @@ int decode_prepare_impl(glc_ctx *ctx, const glc_frames *in) {
   return GLC_OK;
 }
 
+// D1 of rows [row0, row0 + M) of `rows` on `st`, by the context's variant and through its plan workspace.  `reuse`:
+// the workspace still holds the plan of this very launch (launch_d1).
+hipError_t launch_d1_rows(glc_ctx *ctx, const glc::DecodeRows &rows, uint32_t row0, uint32_t M, uint32_t ch, float *blocks, hipStream_t st,
+                          bool reuse = false) {
+  return glc::launch_imdct_rows(ctx->dev, rows, row0, M, ch, blocks, st, ctx->d1_variant, ctx->dec_plan.p,
+                                ctx->dec_plan.p ? ctx->dec_plan_groups : 0, reuse);
+}
+
 // D1 for rows [row_begin, row_begin + M) of the prepared stream.  A launch that fits one batch of the
 // plan workspace leaves its plan records (and the unit order) behind; the same launch of the same
 // stream again - a repeated decode - skips k_imdct_plan.
@@ -1609,8 +1627,7 @@ int launch_d1(glc_ctx *ctx, uint32_t row_begin, uint32_t M, float *blocks) {
   const bool one_batch = planned && ((M / ch + 7) / 8) * ch <= ctx->dec_plan_groups;
   const bool reuse = one_batch && ctx->plan_uid == ctx->dec_uid && ctx->plan_uid != 0 && ctx->plan_row_begin == row_begin &&
                      ctx->plan_M == M;
-  GLC_HIP(ctx, glc::launch_imdct_rows(ctx->dev, ctx->dec_rows, row_begin, M, ch, blocks, ctx->stream, ctx->d1_variant,
-                                      ctx->dec_plan.p, ctx->dec_plan.p ? ctx->dec_plan_groups : 0, reuse));
+  GLC_HIP(ctx, launch_d1_rows(ctx, ctx->dec_rows, row_begin, M, ch, blocks, ctx->stream, reuse));
   if (planned) {
     ctx->plan_uid = one_batch ? ctx->dec_uid : 0;
     ctx->plan_row_begin = row_begin;
@@ -1864,8 +1881,7 @@ int decode_batch_round(glc_ctx *ctx, const glc_frames *const *streams, uint64_t 
   float *blocks = static_cast<float *>(ctx->blocks.p);
   T *stage = static_cast<T *>(ctx->pcm.p);
   // (D1's 8-frame units may span two streams: that only widens a union)
-  GLC_HIP(ctx, glc::launch_imdct_rows(ctx->dev, rows, 0, static_cast<uint32_t>(M), ch, blocks, ctx->stream, ctx->d1_variant,
-                                      ctx->dec_plan.p, ctx->dec_plan.p ? ctx->dec_plan_groups : 0, false));
+  GLC_HIP(ctx, launch_d1_rows(ctx, rows, 0, static_cast<uint32_t>(M), ch, blocks, ctx->stream));
   GLC_HIP(ctx, glc::launch_overlap_add_strided(blocks, reinterpret_cast<const glc::HopDesc *>(mb + o_desc),
                                                static_cast<uint32_t>(desc.size()), ch, stage, ctx->stream));
   if (n_out) GLC_HIP(ctx, hipMemcpyAsync(pcm_out, stage, n_out * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
@@ -1922,7 +1938,7 @@ int decode_range_device(glc_ctx *ctx, const glc_frames *in, uint64_t hop_begin, 
     return fail(ctx, GLC_EINVAL, std::string(who) + ": hop range out of bounds");
   if (cap < (hop_end - hop_begin) * glc::kHop * in->channels)
     return fail(ctx, GLC_EINVAL, std::string(who) + ": output buffer too small");
-  if (reinterpret_cast<uintptr_t>(d_out) % sizeof(T))
+  if (!aligned(d_out, sizeof(T)))
     return fail(ctx, GLC_EINVAL, std::string(who) + ": output pointer not aligned to its sample size");
   int rc = decode_prepare(ctx, in);
   if (rc != GLC_OK) return rc;
@@ -2127,8 +2143,7 @@ int rt_decode_round_rows(glc_ctx *ctx, const RtGeom &g, const glc::DecodeRows &r
   const size_t slot = static_cast<size_t>(g.ch) * glc::kFrame;
   float *blocks = static_cast<float *>(ctx->blocks.p);
   const uint32_t M = static_cast<uint32_t>(nf * g.ch);
-  GLC_HIP(ctx, glc::launch_imdct_rows(ctx->dev, rows, row0, M, g.ch, blocks + slot, ctx->stream, ctx->d1_variant, ctx->dec_plan.p,
-                                      ctx->dec_plan.p ? ctx->dec_plan_groups : 0, false));
+  GLC_HIP(ctx, launch_d1_rows(ctx, rows, row0, M, g.ch, blocks + slot, ctx->stream));
   const bool last = f0 + nf == g.n_frames;
   if (sink) {
     GLC_HIP(ctx, glc::launch_overlap_add_strided(blocks, sink->desc, sink->n_desc, g.ch, sink->planar, sink->out, ctx->stream));
@@ -2163,15 +2178,12 @@ int rt_check(glc_ctx *ctx, const char *who, uint64_t n_samples, uint16_t channel
              uint64_t cap, uint64_t *n_out, glc_plan *plan, RtGeom *g) {
   const std::string w(who);
   if (channels == 0) return fail(ctx, GLC_EINVAL, w + ": channels == 0");
-  *plan = glc::plan_encode(n_samples, channels);
-  if (plan->n_frames == 0)
-    return fail(ctx, GLC_EINVAL, w + ": the reference encoder panics on this input (<= 512 samples per channel, or ragged channels)");
-  if (plan->n_frames * channels > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, w + ": stream too long");
+  if (const char *bad = frames_fault(n_samples, channels, plan)) return fail(ctx, GLC_EINVAL, w + ": " + bad);
   *g = rt_geom(plan->n_frames, channels, *plan, n_samples);
   if (n_out) *n_out = g->trim.n;
   if (cap < g->trim.n) return fail(ctx, GLC_EINVAL, w + ": output buffer too small");
   if (!out) return fail(ctx, GLC_EINVAL, w + ": null argument");
-  if (reinterpret_cast<uintptr_t>(out) % out_align) return fail(ctx, GLC_EINVAL, w + ": output pointer not aligned to its sample size");
+  if (!aligned(out, out_align)) return fail(ctx, GLC_EINVAL, w + ": output pointer not aligned to its sample size");
   return GLC_OK;
 }
 
@@ -2211,7 +2223,7 @@ template <typename T>
 int rt_roundtrip_host(glc_ctx *ctx, const void *pcm, glc_pcm_format fmt, uint32_t bits, uint64_t n_samples, const RtGeom &g,
                       const glc_plan &plan, T *pcm_out) {
   const bool is_int = fmt != GLC_PCM_F32;
-  const size_t elem = fmt == GLC_PCM_S16 ? 2 : 4;
+  const size_t elem = pcm_elem(fmt);
   int rc = rt_roundtrip_begin(ctx, g);
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->pcm, static_cast<size_t>(n_samples) * sizeof(float));
   if (rc == GLC_OK && is_int) rc = rt_reserve(ctx, ctx->pcm_int, static_cast<size_t>(n_samples) * elem);
@@ -2333,8 +2345,7 @@ int glc_decode_device_records(glc_ctx *ctx, const void *d_records, uint64_t n_fr
   if (!ctx) return GLC_EINVAL;
   if (n_out) *n_out = 0;
   if (!d_records) return fail(ctx, GLC_EINVAL, "glc_decode_device_records: null argument");
-  if (reinterpret_cast<uintptr_t>(d_records) & 15u)
-    return fail(ctx, GLC_EINVAL, "glc_decode_device_records: the records are not 16-byte aligned");
+  if (!aligned(d_records, 16)) return fail(ctx, GLC_EINVAL, "glc_decode_device_records: the records are not 16-byte aligned");
   glc_plan plan;
   RtGeom g;
   int rc = rt_check(ctx, "glc_decode_device_records", n_samples, channels, d_out, sizeof(float), cap, n_out, &plan, &g);
@@ -2377,15 +2388,11 @@ int glc_roundtrip(glc_ctx *ctx, const void *pcm, glc_pcm_format fmt, uint32_t bi
   if (!ctx) return GLC_EINVAL;
   if (n_out) *n_out = 0;
   if (!pcm) return fail(ctx, GLC_EINVAL, "glc_roundtrip: null argument");
-  if (fmt != GLC_PCM_S16 && fmt != GLC_PCM_S32 && fmt != GLC_PCM_F32) return fail(ctx, GLC_EINVAL, "glc_roundtrip: unknown sample format");
-  if (fmt != GLC_PCM_F32 && (bits == 0 || bits > (fmt == GLC_PCM_S16 ? 16u : 32u)))
-    return fail(ctx, GLC_EINVAL, "glc_roundtrip: bits must be 1..16 for 16-bit samples, 1..32 for 32-bit ones");
-  if (out_fmt != GLC_PCM_F32 && out_fmt != GLC_PCM_S16)
-    return fail(ctx, GLC_EINVAL, "glc_roundtrip: the output is GLC_PCM_F32 or GLC_PCM_S16");
+  if (const char *bad = fmt_fault(fmt, bits)) return fail(ctx, GLC_EINVAL, std::string("glc_roundtrip: ") + bad);
+  if (const char *bad = out_fmt_fault(out_fmt)) return fail(ctx, GLC_EINVAL, std::string("glc_roundtrip: ") + bad);
   glc_plan plan;
   RtGeom g;
-  const size_t out_elem = out_fmt == GLC_PCM_S16 ? 2 : 4;
-  int rc = rt_check(ctx, "glc_roundtrip", n_samples, channels, pcm_out, out_elem, cap, n_out, &plan, &g);
+  int rc = rt_check(ctx, "glc_roundtrip", n_samples, channels, pcm_out, pcm_elem(out_fmt), cap, n_out, &plan, &g);
   if (rc != GLC_OK) return rc;
   // At the host boundary a round is what the copies are cut into, and the first upload and the last download
   // are hidden by nothing: rounds of 4096 ROWS - the smallest launch the large transform kernel takes
@@ -2439,40 +2446,7 @@ int TableImage::send(glc_ctx *ctx, size_t bytes) {
 extern "C++" {
 namespace {
 
-// Where clip i of a glc_clip_layout starts, what it occupies, and the extent of the whole layout, in elements.
-struct RtbLayout {
-  const glc_clip_layout *l;
-  uint64_t len(uint64_t i) const { return l->lengths ? l->lengths[i] : l->length; }
-  uint64_t at(uint64_t i) const { return i * l->clip_stride; }
-  bool planes() const { return l->planar && l->channels > 1; }
-  uint64_t occupies(uint64_t i) const {
-    return planes() ? (l->channels - 1ull) * l->channel_stride + len(i) : len(i) * l->channels;
-  }
-  // The extent is that of the padded batch: every clip slot counts with the length of the LONGEST clip, so the padding
-  // behind a short last clip belongs to the batch too and no second buffer may begin inside it.
-  uint64_t extent() const {
-    uint64_t longest = 0;
-    for (uint64_t i = 0; i < l->n_clips; ++i) longest = std::max(longest, len(i));
-    const uint64_t occ = planes() ? (l->channels - 1ull) * l->channel_stride + longest : longest * l->channels;
-    return at(l->n_clips - 1) + occ;
-  }
-  bool same_as(const RtbLayout &o) const {
-    return planes() == o.planes() && (l->n_clips <= 1 || l->clip_stride == o.l->clip_stride) &&
-           (!planes() || l->channel_stride == o.l->channel_stride);
-  }
-  // The bytes [p, p + extent() * elem) of the batch at `p`, whose elements are `elem` bytes wide: overlap is judged on
-  // BYTES, the layouts of a call may count elements of different widths.
-  uintptr_t end_of(const void *p, size_t elem) const { return reinterpret_cast<uintptr_t>(p) + extent() * elem; }
-};
-
-// The input of a batch call: device samples of `fmt` (`bits` wide for the integer formats), the layout counting
-// elements of that type.  S1 widens the integers in its gather (glc::launch_stage_clips_int).
-struct RtbPcm {
-  const void *p;
-  glc_pcm_format fmt;
-  uint32_t bits;
-  size_t elem() const { return fmt == GLC_PCM_S16 ? 2 : 4; }
-};
+// (RtbLayout, the view of a glc_clip_layout, and RtbPcm, the input of a batch call: glc_args.hpp)
 
 int rtb_stage(glc_ctx *ctx, const RtbPcm &pcm, const glc::StageClip *clips, uint64_t n_clips, uint32_t ch, const RtbLayout &in, uint64_t V,
               float *vs, hipStream_t st) {
@@ -2482,14 +2456,6 @@ int rtb_stage(glc_ctx *ctx, const RtbPcm &pcm, const glc::StageClip *clips, uint
   else
     GLC_HIP(ctx, glc::launch_stage_clips_int(pcm.p, pcm.fmt == GLC_PCM_S32, pcm.bits, clips, static_cast<uint32_t>(n_clips), ch, in.planes(),
                                              in.l->channel_stride, static_cast<uint32_t>(V), vs, st));
-  return GLC_OK;
-}
-
-// What the integer twins check of `fmt` and `bits`, as glc_encode_int does.
-int rtb_check_fmt(glc_ctx *ctx, const std::string &w, glc_pcm_format fmt, uint32_t bits) {
-  if (fmt != GLC_PCM_S16 && fmt != GLC_PCM_S32 && fmt != GLC_PCM_F32) return fail(ctx, GLC_EINVAL, w + ": unknown sample format");
-  if (fmt != GLC_PCM_F32 && (bits == 0 || bits > (fmt == GLC_PCM_S16 ? 16u : 32u)))
-    return fail(ctx, GLC_EINVAL, w + ": bits must be 1..16 for 16-bit samples, 1..32 for 32-bit ones");
   return GLC_OK;
 }
 
@@ -2510,18 +2476,6 @@ std::vector<R> plan_rounds(uint64_t n, FramesOf frames_of, uint64_t budget, uint
   std::vector<R> rounds;
   for (const RoundSpan &s : pack_rounds(n, frames_of, budget, front)) static_cast<RoundSpan &>(rounds.emplace_back()) = s;
   return rounds;
-}
-
-// What every batch call over a glc_clip_layout refuses of clip i (`clip` names the call and the clip).
-int rtb_check_clip(glc_ctx *ctx, const std::string &clip, const RtbLayout &l, uint64_t i) {
-  const uint64_t n = l.l->n_clips, ch = l.l->channels;
-  const glc_plan plan = glc::plan_encode(l.len(i) * ch, l.l->channels);
-  if (plan.n_frames == 0)
-    return fail(ctx, GLC_EINVAL, clip + ": the reference encoder panics on this input (<= 512 samples per channel)");
-  if (plan.n_frames * ch > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, clip + ": stream too long");
-  if (l.planes() && l.l->channel_stride < l.len(i)) return fail(ctx, GLC_EINVAL, clip + ": channel_stride is smaller than a plane");
-  if (n > 1 && l.l->clip_stride < l.occupies(i)) return fail(ctx, GLC_EINVAL, clip + ": clip_stride is smaller than the clip");
-  return GLC_OK;
 }
 
 template <typename Out>  // float, or int16_t: D2 narrows
@@ -2623,8 +2577,7 @@ int rtb_impl(glc_ctx *ctx, const RtbPcm &pcm, const RtbLayout &in, Out *d_out, c
     glc::DecodeRows rows{};
     GLC_HIP(ctx, glc::launch_rows_from_records_batch(recs, M, ch, image.dev<glc::FrameMap>(r.o_fmap), ctx->rt_rows.p, d_stats, st, &rows));
     // (D1's 8-frame units may span two clips: that only widens a union)
-    GLC_HIP(ctx, glc::launch_imdct_rows(ctx->dev, rows, 0, M, ch, blocks, st, ctx->d1_variant, ctx->dec_plan.p,
-                                        ctx->dec_plan.p ? ctx->dec_plan_groups : 0, false));
+    GLC_HIP(ctx, launch_d1_rows(ctx, rows, 0, M, ch, blocks, st));
     GLC_HIP(ctx, glc::launch_overlap_add_strided(blocks, desc, static_cast<uint32_t>(r.n_desc), ch, out_planes, d_out, st));
   }
   ctx->rtb_info.resize(n);
@@ -2644,38 +2597,29 @@ static int rtb_call(glc_ctx *ctx, const char *who, const void *d_pcm, glc_pcm_fo
   const std::string w(who);
   if (!ctx) return GLC_EINVAL;
   if (!in || !out) return fail(ctx, GLC_EINVAL, w + ": null argument");
-  if (const int rc = rtb_check_fmt(ctx, w, fmt, bits)) return rc;
-  if (out_fmt != GLC_PCM_F32 && out_fmt != GLC_PCM_S16) return fail(ctx, GLC_EINVAL, w + ": the output is GLC_PCM_F32 or GLC_PCM_S16");
+  if (const char *bad = fmt_fault(fmt, bits)) return fail(ctx, GLC_EINVAL, w + ": " + bad);
+  if (const char *bad = out_fmt_fault(out_fmt)) return fail(ctx, GLC_EINVAL, w + ": " + bad);
   if (in->n_clips != out->n_clips || in->channels != out->channels)
     return fail(ctx, GLC_EINVAL, w + ": the two layouts differ in the number of clips or channels");
   if (in->n_clips == 0) return GLC_OK;
   if (!d_pcm || !d_out) return fail(ctx, GLC_EINVAL, w + ": null argument");
   if (in->channels == 0) return fail(ctx, GLC_EINVAL, w + ": channels == 0");
   const RtbPcm pcm{d_pcm, fmt, bits};
-  const size_t in_elem = pcm.elem(), out_elem = out_fmt == GLC_PCM_S16 ? 2 : 4;
-  if ((reinterpret_cast<uintptr_t>(d_pcm) & (in_elem - 1u)) | (reinterpret_cast<uintptr_t>(d_out) & (out_elem - 1u)))
+  if (!aligned(d_pcm, pcm.elem()) || !aligned(d_out, pcm_elem(out_fmt)))
     return fail(ctx, GLC_EINVAL, w + ": a pointer is not aligned to its sample size");
   const RtbLayout li{in}, lo{out};
   const uint64_t n = in->n_clips;
   for (uint64_t i = 0; i < n; ++i) {
-    const std::string clip = w + ": clip " + std::to_string(i);
-    if (li.len(i) != lo.len(i)) return fail(ctx, GLC_EINVAL, clip + ": the two layouts differ in its length");
+    if (li.len(i) != lo.len(i)) return fail(ctx, GLC_EINVAL, clip_name(w, i) + ": the two layouts differ in its length");
     for (const RtbLayout *l : {&li, &lo})
-      if (const int rc = rtb_check_clip(ctx, clip, *l, i)) return rc;
+      if (const char *bad = clip_fault(*l, i)) return fail(ctx, GLC_EINVAL, clip_name(w, i) + ": " + bad);
   }
-  {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_pcm), a1 = li.end_of(d_pcm, in_elem);
-    const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_out), b1 = lo.end_of(d_out, out_elem);
-    if (a0 < b1 && b0 < a1 && !(a0 == b0 && li.same_as(lo) && fmt == out_fmt))
-      return fail(ctx, GLC_EINVAL, w + ": input and output overlap (in place needs the same pointer, the same layout and the same format)");
-  }
-  DeviceGuard guard(ctx->device);
-  try {  // no C++ exception may cross the C ABI
+  if (overlaps(span_of(d_pcm, li, pcm.elem()), span_of(d_out, lo, pcm_elem(out_fmt))) && !in_place(d_pcm, li, fmt, d_out, lo, out_fmt))
+    return fail(ctx, GLC_EINVAL, w + ": input and output overlap (in place needs the same pointer, the same layout and the same format)");
+  return on_device(ctx, w, [&] {
     return out_fmt == GLC_PCM_S16 ? rtb_impl(ctx, pcm, li, static_cast<int16_t *>(d_out), lo)
                                   : rtb_impl(ctx, pcm, li, static_cast<float *>(d_out), lo);
-  } catch (const std::bad_alloc &) {
-    return fail(ctx, GLC_ENOMEM, w + ": host allocation failed");
-  }
+  });
 }
 
 int glc_roundtrip_batch_device(glc_ctx *ctx, const float *d_pcm, const glc_clip_layout *in, float *d_out,
@@ -2694,10 +2638,9 @@ int glc_roundtrip_batch_last_info(glc_ctx *ctx, glc_roundtrip_info *infos, uint6
     return fail(ctx, GLC_EINVAL, "glc_roundtrip_batch_last_info: no batch round trip has completed on this context");
   if (n_clips != ctx->rtb_info.size())
     return fail(ctx, GLC_EINVAL, "glc_roundtrip_batch_last_info: the last batch had another number of clips");
-  DeviceGuard guard(ctx->device);
   uint64_t words = 0;
   for (const glc_ctx::RtbClipInfo &c : ctx->rtb_info) words = std::max(words, c.stat_off + uint64_t(c.stat_slots) * glc::kRowStatStride);
-  try {
+  return on_device(ctx, "glc_roundtrip_batch_last_info", [&]() -> int {
     std::vector<uint64_t> h(words);
     GLC_HIP(ctx, hipMemcpyAsync(h.data(), ctx->rtb_stats.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -2707,10 +2650,8 @@ int glc_roundtrip_batch_last_info(glc_ctx *ctx, glc_roundtrip_info *infos, uint6
       for (uint32_t k = 0; k < c.stat_slots; ++k) s0 += h[c.stat_off + k * glc::kRowStatStride], s1 += h[c.stat_off + k * glc::kRowStatStride + 1];
       rt_fill_info(&infos[i], c.n_frames, ctx->rtb_info_ch, s0, s1);
     }
-  } catch (const std::bad_alloc &) {
-    return fail(ctx, GLC_ENOMEM, "glc_roundtrip_batch_last_info: host allocation failed");
-  }
-  return GLC_OK;
+    return GLC_OK;
+  });
 }
 
 // ------------------------------------------------------------------------------ decode of compact blobs in HBM
@@ -2718,13 +2659,12 @@ int glc_roundtrip_batch_last_info(glc_ctx *ctx, glc_roundtrip_info *infos, uint6
 extern "C++" {
 namespace {
 
-// What both calls check of one blob before anything is queued.  `who` already names the clip.
-int cd_check_blob(glc_ctx *ctx, const std::string &who, const void *d_blob, uint64_t blob_bytes, uint32_t ch, uint64_t n_frames) {
-  if (!d_blob) return fail(ctx, GLC_EINVAL, who + ": null argument");
-  if (reinterpret_cast<uintptr_t>(d_blob) & 63u) return fail(ctx, GLC_EINVAL, who + ": the blob is not 64-byte aligned");
-  if (blob_bytes < glc::compact_layout(ch, n_frames).o_pairs)
-    return fail(ctx, GLC_EINVAL, who + ": blob_bytes is smaller than the fixed sections of a blob of that many frames");
-  return GLC_OK;
+// What both calls check of one blob before anything is queued: the fault, or null (as the rules of glc_args.hpp).
+const char *cd_blob_fault(const void *d_blob, uint64_t blob_bytes, uint32_t ch, uint64_t n_frames) {
+  if (!d_blob) return "null argument";
+  if (!aligned(d_blob, 64)) return "the blob is not 64-byte aligned";
+  if (blob_bytes < glc::compact_layout(ch, n_frames).o_pairs) return "blob_bytes is smaller than the fixed sections of a blob of that many frames";
+  return nullptr;
 }
 
 // A blob of `nf` frames through R2 (one pass over all its rows, tables in rt_rows) and the rounds of the family.
@@ -2854,8 +2794,7 @@ int cdb_impl(glc_ctx *ctx, const char *who, const void *const *d_blobs, const ui
                                                  reinterpret_cast<const void *>(base), ctx->rt_rows.p, d_status + r.first, st, &rows));
     }
     // (D1's 8-frame units may span two clips: that only widens a union)
-    GLC_HIP(ctx, glc::launch_imdct_rows(ctx->dev, rows, 0, M, ch, blocks, st, ctx->d1_variant, ctx->dec_plan.p,
-                                        ctx->dec_plan.p ? ctx->dec_plan_groups : 0, false));
+    GLC_HIP(ctx, launch_d1_rows(ctx, rows, 0, M, ch, blocks, st));
     GLC_HIP(ctx, glc::launch_overlap_add_strided(blocks, desc, static_cast<uint32_t>(r.n_desc), ch, out_planes, d_out, st));
   }
   ctx->cd_status_n = n;
@@ -2874,12 +2813,9 @@ int glc_decode_device_compact(glc_ctx *ctx, const void *d_blob, uint64_t blob_by
   RtGeom g;
   int rc = rt_check(ctx, w.c_str(), n_samples, channels, d_out, sizeof(float), cap, n_out, &plan, &g);
   if (rc != GLC_OK) return rc;
-  rc = cd_check_blob(ctx, w, d_blob, blob_bytes, channels, plan.n_frames);
-  if (rc == GLC_OK) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_blob), a1 = a0 + blob_bytes;
-    const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_out), b1 = b0 + g.trim.n * sizeof(float);
-    if (a0 < b1 && b0 < a1) rc = fail(ctx, GLC_EINVAL, w + ": the output overlaps the blob");
-  }
+  if (const char *bad = cd_blob_fault(d_blob, blob_bytes, channels, plan.n_frames)) rc = fail(ctx, GLC_EINVAL, w + ": " + bad);
+  if (rc == GLC_OK && overlaps(span_of(d_blob, blob_bytes), span_of(d_out, g.trim.n * sizeof(float))))
+    rc = fail(ctx, GLC_EINVAL, w + ": the output overlaps the blob");
   if (rc != GLC_OK) {
     if (n_out) *n_out = 0;
     return rc;
@@ -2906,36 +2842,28 @@ static int cd_batch_call(glc_ctx *ctx, const char *who, const void *const *d_blo
   if (out->n_clips == 0) return GLC_OK;
   if (!d_blobs || !blob_bytes || !n_samples || !d_out || (windows && !crops)) return fail(ctx, GLC_EINVAL, w + ": null argument");
   if (out->channels == 0) return fail(ctx, GLC_EINVAL, w + ": channels == 0");
-  if (reinterpret_cast<uintptr_t>(d_out) & (sizeof(T) - 1u)) return fail(ctx, GLC_EINVAL, w + ": output pointer not aligned to its sample size");
+  if (!aligned(d_out, sizeof(T))) return fail(ctx, GLC_EINVAL, w + ": output pointer not aligned to its sample size");
   const RtbLayout lo{out};
   const uint64_t n = out->n_clips, ch = out->channels;
-  try {  // no C++ exception may cross the C ABI
+  try {  // no C++ exception may cross the C ABI; the device is set only once nothing is left to refuse
     std::vector<glc_plan> plans(n);
     std::vector<glc_crop_plan> wins(windows ? n : 0);
     for (uint64_t i = 0; i < n; ++i) {
-      const std::string clip = w + ": clip " + std::to_string(i);
-      plans[i] = glc::plan_encode(n_samples[i], out->channels);
-      if (plans[i].n_frames == 0)
-        return fail(ctx, GLC_EINVAL, clip + ": the reference encoder panics on this input (<= 512 samples per channel, or ragged channels)");
-      if (plans[i].n_frames * ch > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, clip + ": stream too long");
+      auto refuse = [&](const char *what) { return fail(ctx, GLC_EINVAL, clip_name(w, i) + ": " + what); };
+      if (const char *bad = frames_fault(n_samples[i], out->channels, &plans[i])) return refuse(bad);
       if (windows) {
-        if (n_samples[i] % ch) return fail(ctx, GLC_EINVAL, clip + ": n_samples is no multiple of the channel count");
-        if (!glc::plan_crop(n_samples[i], out->channels, crops[i], &wins[i]))
-          return fail(ctx, GLC_EINVAL, clip + ": an empty crop, or one that ends behind the clip");
-        if (lo.len(i) != crops[i].length) return fail(ctx, GLC_EINVAL, clip + ": the layout's length is not the crop's");
+        if (n_samples[i] % ch) return refuse("n_samples is no multiple of the channel count");
+        if (!glc::plan_crop(n_samples[i], out->channels, crops[i], &wins[i])) return refuse("an empty crop, or one that ends behind the clip");
+        if (lo.len(i) != crops[i].length) return refuse("the layout's length is not the crop's");
       } else if (lo.len(i) * ch != n_samples[i]) {
-        return fail(ctx, GLC_EINVAL, clip + ": the layout's length is not the decoded length");
+        return refuse("the layout's length is not the decoded length");
       }
-      if (lo.planes() && out->channel_stride < lo.len(i)) return fail(ctx, GLC_EINVAL, clip + ": channel_stride is smaller than a plane");
-      if (n > 1 && out->clip_stride < lo.occupies(i)) return fail(ctx, GLC_EINVAL, clip + ": clip_stride is smaller than the clip");
-      const int rc = cd_check_blob(ctx, clip, d_blobs[i], blob_bytes[i], out->channels, plans[i].n_frames);
-      if (rc != GLC_OK) return rc;
+      if (const char *bad = stride_fault(lo, i)) return refuse(bad);
+      if (const char *bad = cd_blob_fault(d_blobs[i], blob_bytes[i], out->channels, plans[i].n_frames)) return refuse(bad);
     }
-    const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_out), b1 = lo.end_of(d_out, sizeof(T));
-    for (uint64_t i = 0; i < n; ++i) {
-      const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_blobs[i]), a1 = a0 + blob_bytes[i];
-      if (a0 < b1 && b0 < a1) return fail(ctx, GLC_EINVAL, w + ": clip " + std::to_string(i) + ": the output extent overlaps the blob");
-    }
+    const ByteSpan all = span_of(d_out, lo, sizeof(T));
+    for (uint64_t i = 0; i < n; ++i)
+      if (overlaps(span_of(d_blobs[i], blob_bytes[i]), all)) return fail(ctx, GLC_EINVAL, clip_name(w, i) + ": the output extent overlaps the blob");
     DeviceGuard guard(ctx->device);
     return cdb_impl(ctx, who, d_blobs, blob_bytes, d_out, lo, plans, windows ? crops : nullptr, windows ? wins.data() : nullptr);
   } catch (const std::bad_alloc &) {
@@ -2969,17 +2897,14 @@ int glc_decode_compact_last_status(glc_ctx *ctx, glc_compact_status *status, uin
   if (ctx->cd_status_n == 0 || !ctx->cd_status.p)
     return fail(ctx, GLC_EINVAL, "glc_decode_compact_last_status: no compact decode has completed on this context");
   if (n_clips != ctx->cd_status_n) return fail(ctx, GLC_EINVAL, "glc_decode_compact_last_status: the last call had another number of clips");
-  DeviceGuard guard(ctx->device);
-  try {
+  return on_device(ctx, "glc_decode_compact_last_status", [&]() -> int {
     std::vector<glc::CompactStatus> h(n_clips);
     GLC_HIP(ctx, hipMemcpyAsync(h.data(), ctx->cd_status.p, n_clips * sizeof(glc::CompactStatus), hipMemcpyDeviceToHost, ctx->stream));
     GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (uint64_t i = 0; i < n_clips; ++i)
       status[i] = glc_compact_status{h[i].flags, 0u, h[i].n_bad_rows, h[i].n_bad_rows ? h[i].first_bad_row : 0ull};
-  } catch (const std::bad_alloc &) {
-    return fail(ctx, GLC_ENOMEM, "glc_decode_compact_last_status: host allocation failed");
-  }
-  return GLC_OK;
+    return GLC_OK;
+  });
 }
 
 // ------------------------------------------------------------------------------ crops drawn from the store by device-side index
@@ -3001,43 +2926,35 @@ int sd_check(glc_ctx *ctx, const std::string &w, const void *d_arena, uint64_t a
   if (!d_arena || !d_entries || !d_lengths || !d_clips || !d_starts || !d_out) return fail(ctx, GLC_EINVAL, w + ": null argument");
   if (out->channels == 0) return fail(ctx, GLC_EINVAL, w + ": channels == 0");
   const uint64_t n = out->n_clips, ch = out->channels;
-  if (reinterpret_cast<uintptr_t>(d_arena) & 63u) return fail(ctx, GLC_EINVAL, w + ": the arena is not 64-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(d_entries) | reinterpret_cast<uintptr_t>(d_lengths) | reinterpret_cast<uintptr_t>(d_clips) |
-       reinterpret_cast<uintptr_t>(d_starts)) & 7u)
+  if (!aligned(d_arena, 64)) return fail(ctx, GLC_EINVAL, w + ": the arena is not 64-byte aligned");
+  if (!all_aligned(8, d_entries, d_lengths, d_clips, d_starts))
     return fail(ctx, GLC_EINVAL, w + ": entries, lengths, clips and starts must be 8-byte aligned");
-  if (reinterpret_cast<uintptr_t>(d_out) & (out_elem - 1u)) return fail(ctx, GLC_EINVAL, w + ": output pointer not aligned to its sample size");
+  if (!aligned(d_out, out_elem)) return fail(ctx, GLC_EINVAL, w + ": output pointer not aligned to its sample size");
   if (n_entries == 0) return fail(ctx, GLC_EINVAL, w + ": n_entries == 0");
   if (length == 0) return fail(ctx, GLC_EINVAL, w + ": length == 0");
   if (max_length < length) return fail(ctx, GLC_EINVAL, w + ": max_length is smaller than the crop");
   if (max_length > (UINT64_MAX >> 12) / ch) return fail(ctx, GLC_EINVAL, w + ": max_length: stream too long");
-  const glc_plan longest = glc::plan_encode(max_length * ch, out->channels);
-  if (longest.n_frames == 0)
-    return fail(ctx, GLC_EINVAL, w + ": max_length: the reference encoder panics on this input (<= 512 samples per channel)");
-  if (longest.n_frames * ch > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, w + ": max_length: stream too long");
+  glc_plan longest;
+  if (const char *bad = frames_fault(max_length * ch, out->channels, &longest)) return fail(ctx, GLC_EINVAL, w + ": max_length: " + bad);
   const RtbLayout lo{out};
   if (out->lengths) {
     for (uint64_t i = 0; i < n; ++i)
-      if (out->lengths[i] != length) return fail(ctx, GLC_EINVAL, w + ": clip " + std::to_string(i) + ": the layout's length is not the crop's");
+      if (out->lengths[i] != length) return fail(ctx, GLC_EINVAL, clip_name(w, i) + ": the layout's length is not the crop's");
   } else if (out->length != length) {
     return fail(ctx, GLC_EINVAL, w + ": the layout's length is not the crop's");
   }
-  const uint64_t occupies = lo.planes() ? (ch - 1) * out->channel_stride + length : length * ch;
-  if (lo.planes() && out->channel_stride < length) return fail(ctx, GLC_EINVAL, w + ": channel_stride is smaller than a plane");
-  if (n > 1 && out->clip_stride < occupies) return fail(ctx, GLC_EINVAL, w + ": clip_stride is smaller than the clip");
+  // every clip is `length` long: what the stride rule finds of clip 0 it finds of all
+  if (const char *bad = stride_fault(lo, 0)) return fail(ctx, GLC_EINVAL, w + ": " + bad);
   g->slots = glc::store_crop_slots(length, out->channels);
   if (g->slots.max_frames + 1 > glc::kStoreRoundBudget)
     return fail(ctx, GLC_EINVAL, w + ": a crop of this length does not fit a round (glc_decode_crops_device_compact takes such windows)");
   g->per_round = glc::kStoreRoundBudget / (g->slots.max_frames + 1);
   g->max_front = longest.n_frames * ch;
-  const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_out), b1 = b0 + ((n - 1) * out->clip_stride + occupies) * out_elem;
-  auto overlaps = [&](const void *p, uint64_t bytes) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(p), a1 = a0 + bytes;
-    return a0 < b1 && b0 < a1;
-  };
-  if (overlaps(d_arena, arena_bytes)) return fail(ctx, GLC_EINVAL, w + ": the output extent overlaps the arena");
-  if (overlaps(d_entries, n_entries * sizeof(glc_store_entry)) || overlaps(d_lengths, n_entries * 8) || overlaps(d_clips, n * 8) ||
-      overlaps(d_starts, n * 8))
-    return fail(ctx, GLC_EINVAL, w + ": the output extent overlaps an index array");
+  const ByteSpan all = span_of(d_out, lo, out_elem);
+  if (overlaps(span_of(d_arena, arena_bytes), all)) return fail(ctx, GLC_EINVAL, w + ": the output extent overlaps the arena");
+  for (const ByteSpan &index : {span_of(d_entries, n_entries * sizeof(glc_store_entry)), span_of(d_lengths, n_entries * 8),
+                                span_of(d_clips, n * 8), span_of(d_starts, n * 8)})
+    if (overlaps(index, all)) return fail(ctx, GLC_EINVAL, w + ": the output extent overlaps an index array");
   TableOffsets offs;
   g->o_dir = offs.take(n * sizeof(glc::CompactBlob));
   g->o_desc = offs.take(n * g->slots.max_hops * sizeof(glc::HopDescStrided));
@@ -3126,8 +3043,7 @@ static int sd_call(glc_ctx *ctx, const char *who, const void *d_arena, uint64_t 
     GLC_HIP(ctx, glc::launch_rows_from_compact_window(d_dir + first, glc::CompactBlob{}, static_cast<uint32_t>(nr), M, ch,
                                                       static_cast<uint32_t>(g.max_front), d_arena, ctx->rt_rows.p, d_status + first, st,
                                                       &rows, d_verdict + first));
-    GLC_HIP(ctx, glc::launch_imdct_rows(ctx->dev, rows, 0, M, ch, blocks, st, ctx->d1_variant, ctx->dec_plan.p,
-                                        ctx->dec_plan.p ? ctx->dec_plan_groups : 0, false));
+    GLC_HIP(ctx, launch_d1_rows(ctx, rows, 0, M, ch, blocks, st));
     GLC_HIP(ctx, glc::launch_overlap_add_strided(blocks, d_desc + first * g.slots.max_hops, static_cast<uint32_t>(nr * g.slots.max_hops), ch,
                                                  out_planes, d_out, st));
   }
@@ -3194,38 +3110,27 @@ int glc_store_compact_device(glc_ctx *ctx, void *d_arena, uint64_t arena_bytes, 
     return fail(ctx, GLC_EINVAL, w + ": null argument");
   if ((d_lengths == nullptr) != (d_lengths_out == nullptr))
     return fail(ctx, GLC_EINVAL, w + ": d_lengths and d_lengths_out are given together or not at all");
-  if ((reinterpret_cast<uintptr_t>(d_arena) | reinterpret_cast<uintptr_t>(d_dst)) & 63u)
-    return fail(ctx, GLC_EINVAL, w + ": the arenas must be 64-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(d_entries) | reinterpret_cast<uintptr_t>(d_lengths) | reinterpret_cast<uintptr_t>(d_entries_out) |
-       reinterpret_cast<uintptr_t>(d_lengths_out) | reinterpret_cast<uintptr_t>(d_new_index) | reinterpret_cast<uintptr_t>(d_n_out) |
-       reinterpret_cast<uintptr_t>(d_cursor)) & 7u)
+  if (!all_aligned(64, d_arena, d_dst)) return fail(ctx, GLC_EINVAL, w + ": the arenas must be 64-byte aligned");
+  if (!all_aligned(8, d_entries, d_lengths, d_entries_out, d_lengths_out, d_new_index, d_n_out, d_cursor))
     return fail(ctx, GLC_EINVAL, w + ": entries, lengths, new_index, n_out and cursor must be 8-byte aligned");
   if (n_entries == 0) return fail(ctx, GLC_EINVAL, w + ": n_entries == 0");
   if (n_entries > (1ull << 40)) return fail(ctx, GLC_EINVAL, w + ": too many entries");
   const bool in_place = d_dst == d_arena;
   if (in_place && dst_bytes != arena_bytes) return fail(ctx, GLC_EINVAL, w + ": in place, dst_bytes must be arena_bytes");
-  struct Span {
-    uintptr_t lo, hi;
-    const char *name;
-  };
-  std::vector<Span> spans;
-  auto span = [&](const void *p, uint64_t bytes, const char *name) {
-    if (p && bytes) spans.push_back(Span{reinterpret_cast<uintptr_t>(p), reinterpret_cast<uintptr_t>(p) + bytes, name});
-  };
-  span(d_arena, arena_bytes, "the arena");
-  if (!in_place) span(d_dst, dst_bytes, "the destination arena");
-  span(d_entries, n_entries * sizeof(glc_store_entry), "d_entries");
-  span(d_lengths, n_entries * 8, "d_lengths");
-  span(d_keep, n_entries, "d_keep");
-  if (d_entries_out != d_entries) span(d_entries_out, n_entries * sizeof(glc_store_entry), "d_entries_out");
-  if (d_lengths_out != d_lengths) span(d_lengths_out, n_entries * 8, "d_lengths_out");
-  span(d_new_index, n_entries * 8, "d_new_index");
-  span(d_n_out, 8, "d_n_out");
-  span(d_cursor, 8, "d_cursor");
-  for (size_t i = 0; i < spans.size(); ++i)
-    for (size_t j = i + 1; j < spans.size(); ++j)
-      if (spans[i].lo < spans[j].hi && spans[j].lo < spans[i].hi)
-        return fail(ctx, GLC_EINVAL, w + ": " + spans[i].name + " overlaps " + spans[j].name);
+  // (an arena or an index array that is updated in place is ONE span: its twin takes no part)
+  const char *one, *other;
+  if (first_overlap({span_of(d_arena, arena_bytes, "the arena"),
+                     in_place ? ByteSpan{} : span_of(d_dst, dst_bytes, "the destination arena"),
+                     span_of(d_entries, n_entries * sizeof(glc_store_entry), "d_entries"),
+                     span_of(d_lengths, n_entries * 8, "d_lengths"),
+                     span_of(d_keep, n_entries, "d_keep"),
+                     d_entries_out != d_entries ? span_of(d_entries_out, n_entries * sizeof(glc_store_entry), "d_entries_out") : ByteSpan{},
+                     d_lengths_out != d_lengths ? span_of(d_lengths_out, n_entries * 8, "d_lengths_out") : ByteSpan{},
+                     span_of(d_new_index, n_entries * 8, "d_new_index"),
+                     span_of(d_n_out, 8, "d_n_out"),
+                     span_of(d_cursor, 8, "d_cursor")},
+                    &one, &other))
+    return fail(ctx, GLC_EINVAL, w + ": " + one + " overlaps " + other);
   const uint64_t round = ctx->sc_round ? ctx->sc_round : kStoreCompactRound;
   DeviceGuard guard(ctx->device);
   // not a decode and not an encode: the resident stream, an open session, the kept plan and the last-info records stay
@@ -3358,32 +3263,18 @@ static int ebc_call(glc_ctx *ctx, const char *who, const void *d_pcm, glc_pcm_fo
   const std::string w(who);
   if (!ctx) return GLC_EINVAL;
   if (!in) return fail(ctx, GLC_EINVAL, w + ": null argument");
-  if (const int rc = rtb_check_fmt(ctx, w, fmt, bits)) return rc;
+  if (const char *bad = fmt_fault(fmt, bits)) return fail(ctx, GLC_EINVAL, w + ": " + bad);
   if (in->n_clips == 0) return GLC_OK;
   if (!d_pcm || !d_arena || !d_cursor || !d_entries) return fail(ctx, GLC_EINVAL, w + ": null argument");
   if (in->channels == 0) return fail(ctx, GLC_EINVAL, w + ": channels == 0");
   const RtbPcm pcm{d_pcm, fmt, bits};
-  if (reinterpret_cast<uintptr_t>(d_pcm) & (pcm.elem() - 1u)) return fail(ctx, GLC_EINVAL, w + ": d_pcm is not aligned to its sample size");
-  if (reinterpret_cast<uintptr_t>(d_arena) & 63u) return fail(ctx, GLC_EINVAL, w + ": d_arena is not 64-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(d_cursor) | reinterpret_cast<uintptr_t>(d_entries)) & 7u)
-    return fail(ctx, GLC_EINVAL, w + ": d_cursor and d_entries must be 8-byte aligned");
+  if (const char *bad = store_fill_misaligned(pcm, d_arena, d_cursor, d_entries)) return fail(ctx, GLC_EINVAL, w + ": " + bad);
   const RtbLayout li{in};
   const uint64_t n = in->n_clips;
   for (uint64_t i = 0; i < n; ++i)
-    if (const int rc = rtb_check_clip(ctx, w + ": clip " + std::to_string(i), li, i)) return rc;
-  {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_pcm), a1 = li.end_of(d_pcm, pcm.elem());
-    const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_arena), b1 = b0 + arena_bytes;
-    const uintptr_t e0 = reinterpret_cast<uintptr_t>(d_entries), e1 = e0 + n * sizeof(glc_store_entry);
-    if (a0 < b1 && b0 < a1) return fail(ctx, GLC_EINVAL, w + ": the arena overlaps the input");
-    if (a0 < e1 && e0 < a1) return fail(ctx, GLC_EINVAL, w + ": the entries overlap the input");
-  }
-  DeviceGuard guard(ctx->device);
-  try {  // no C++ exception may cross the C ABI
-    return ebc_impl(ctx, pcm, li, d_arena, arena_bytes, d_cursor, d_entries);
-  } catch (const std::bad_alloc &) {
-    return fail(ctx, GLC_ENOMEM, w + ": host allocation failed");
-  }
+    if (const char *bad = clip_fault(li, i)) return fail(ctx, GLC_EINVAL, clip_name(w, i) + ": " + bad);
+  if (const char *bad = store_fill_overlap(pcm, li, d_arena, arena_bytes, d_entries)) return fail(ctx, GLC_EINVAL, w + ": " + bad);
+  return on_device(ctx, w, [&] { return ebc_impl(ctx, pcm, li, d_arena, arena_bytes, d_cursor, d_entries); });
 }
 
 int glc_encode_batch_device_compact(glc_ctx *ctx, const float *d_pcm, const glc_clip_layout *in, void *d_arena, uint64_t arena_bytes,
@@ -3408,11 +3299,8 @@ int glc_debug_compact_store_device(glc_ctx *ctx, const void *d_records, const ui
     n_real += clip_frames[i];
   }
   if ((n_real + n_clips) * channels > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, w + ": frame range too long");
-  if ((reinterpret_cast<uintptr_t>(d_records) & 7u) || (reinterpret_cast<uintptr_t>(d_arena) & 63u) ||
-      ((reinterpret_cast<uintptr_t>(d_cursor) | reinterpret_cast<uintptr_t>(d_entries)) & 7u))
-    return fail(ctx, GLC_EINVAL, w + ": a pointer is not aligned");
-  DeviceGuard guard(ctx->device);
-  try {
+  if (!aligned(d_arena, 64) || !all_aligned(8, d_records, d_cursor, d_entries)) return fail(ctx, GLC_EINVAL, w + ": a pointer is not aligned");
+  return on_device(ctx, w, [&]() -> int {
     const size_t o_fmap = 0, o_span = align_up(n_real * sizeof(glc::FrameMap), 256), tab = o_span + n_clips * sizeof(glc::ClipSpan);
     TableImage &image = ctx->rtb_image;
     int rc = rt_reserve(ctx, ctx->pack_meta, glc::compact_store_scratch_bytes(n_real * channels, n_clips));
@@ -3423,9 +3311,7 @@ int glc_debug_compact_store_device(glc_ctx *ctx, const void *d_records, const ui
     if (rc != GLC_OK) return rc;
     return store_round_launch(ctx, d_records, n_real, n_clips, channels, image, o_fmap, o_span, d_arena, arena_bytes, d_cursor, d_entries,
                               ctx->stream);
-  } catch (const std::bad_alloc &) {
-    return fail(ctx, GLC_ENOMEM, w + ": host allocation failed");
-  }
+  });
 }
 
 // ------------------------------------------------------------------------------ streaming encode
@@ -3447,18 +3333,56 @@ struct StreamLane {
   std::vector<StreamBlob> blobs;    // host pushes: the segments so far
 };
 
-}  // extern "C++"
-
-struct glc_stream_enc {
+// What a streaming session of either direction is: `n` lanes of `ch` channels on a context, what each lane carries
+// from push to push in device memory, and the pinned buffers of its host pushes.
+struct StreamSession {
   glc_ctx *ctx = nullptr;
   uint32_t ch = 0;
   uint64_t n = 0;
   int mode = 0;       // 0: no push yet, 1: host pushes, 2: device pushes
-  DevBuf held;        // [lane][2][2048 * ch] floats
-  std::vector<StreamLane> lanes;
-  // host pushes
-  HostBuf up, down;   // pinned: the chunks going up, the entries and blobs coming down
-  DevBuf d_pcm, arena, d_meta;  // d_meta: the cursor (8 bytes, padded to 64) and the entries
+  DevBuf lane_buf;    // what the lanes carry, a fixed number of bytes each (stream_open)
+  HostBuf up, down;   // pinned, host pushes: what goes up, what comes down
+};
+
+// glc_stream_enc_open / glc_stream_dec_open (`who`): a session S of n_streams lanes that carry `per_lane` bytes each.
+template <typename S>
+int stream_open(glc_ctx *ctx, const std::string &who, uint16_t channels, uint64_t n_streams, uint64_t per_lane, S **out) {
+  if (!ctx) return GLC_EINVAL;
+  if (!out) return fail(ctx, GLC_EINVAL, who + ": null argument");
+  *out = nullptr;
+  if (channels == 0 || n_streams == 0) return fail(ctx, GLC_EINVAL, who + ": no channels or no streams");
+  if (n_streams > (1ull << 46) / per_lane) return fail(ctx, GLC_EINVAL, who + ": too many streams");
+  return on_device(ctx, who, [&]() -> int {
+    std::unique_ptr<S> s(new S);
+    s->ctx = ctx, s->ch = channels, s->n = n_streams;
+    s->size_lanes(n_streams);
+    const hipError_t e = s->lane_buf.reserve(n_streams * per_lane);
+    if (e != hipSuccess) return hip_fail(ctx, e, (who + ": hipMalloc").c_str());
+    *out = s.release();
+    return GLC_OK;
+  });
+}
+
+template <typename S>
+void stream_close(S *s) {
+  if (!s) return;
+  DeviceGuard guard(s->ctx->device);
+  (void)hipStreamSynchronize(s->ctx->stream);  // queued pushes may still read and write the session's buffers
+  delete s;
+}
+
+// A session takes host pushes (1) or device pushes (2), whichever came first: the gate of a push of kind `pushing`.
+static int stream_mode_gate(const StreamSession *s, const std::string &w, int pushing) {
+  if (s->mode == 0 || s->mode == pushing) return GLC_OK;
+  return fail(s->ctx, GLC_EINVAL, w + (pushing == 1 ? ": this session takes device pushes" : ": this session takes host pushes"));
+}
+
+}  // extern "C++"
+
+struct glc_stream_enc : StreamSession {
+  std::vector<StreamLane> lanes;  // lane_buf holds what they keep back: [lane][2][2048 * ch] floats
+  void size_lanes(uint64_t k) { lanes.resize(k); }
+  DevBuf d_pcm, arena, d_meta;  // host pushes; d_meta: the cursor (8 bytes, padded to 64) and the entries
   uint64_t held_at(uint64_t lane, uint32_t parity) const { return (lane * 2 + parity) * uint64_t(glc::kFrame) * ch; }
 };
 
@@ -3574,7 +3498,7 @@ int stream_push_core(glc_stream_enc *s, const RtbPcm &pcm, const RtbLayout &in, 
     const Round &R = rounds[r];
     GLC_HIP(ctx, glc::launch_stage_segments(pcm.p, pcm.fmt, pcm.bits, image.dev<glc::StreamSpan>(R.o_spans), static_cast<uint32_t>(R.n_spans), static_cast<uint32_t>(2 * R.V),
                                             static_cast<uint32_t>(r == 0 ? 4 * keep.size() : 0), ch, in.planes(), in.l->channel_stride,
-                                            static_cast<float *>(s->held.p), vs, st));
+                                            static_cast<float *>(s->lane_buf.p), vs, st));
     if (!R.n) continue;
     // the virtual stream's frames [1, V - 1): frame 0 is the slot in front, frame V - 1 the last segment's junk one;
     // record j is virtual frame j + 1, which is how store_round_tables numbers them
@@ -3628,32 +3552,10 @@ uint64_t glc_stream_enc_max_push(uint16_t channels) {
 }
 
 int glc_stream_enc_open(glc_ctx *ctx, uint16_t channels, uint64_t n_streams, glc_stream_enc **out) {
-  if (!ctx) return GLC_EINVAL;
-  if (!out) return fail(ctx, GLC_EINVAL, "glc_stream_enc_open: null argument");
-  *out = nullptr;
-  if (channels == 0 || n_streams == 0) return fail(ctx, GLC_EINVAL, "glc_stream_enc_open: no channels or no streams");
-  const uint64_t per_lane = 2ull * glc::kFrame * channels * sizeof(float);
-  if (n_streams > (1ull << 46) / per_lane) return fail(ctx, GLC_EINVAL, "glc_stream_enc_open: too many streams");
-  DeviceGuard guard(ctx->device);
-  try {
-    std::unique_ptr<glc_stream_enc> s(new glc_stream_enc);
-    s->ctx = ctx, s->ch = channels, s->n = n_streams;
-    s->lanes.resize(n_streams);
-    const hipError_t e = s->held.reserve(n_streams * per_lane);
-    if (e != hipSuccess) return hip_fail(ctx, e, "glc_stream_enc_open: hipMalloc");
-    *out = s.release();
-    return GLC_OK;
-  } catch (const std::bad_alloc &) {
-    return fail(ctx, GLC_ENOMEM, "glc_stream_enc_open: host allocation failed");
-  }
+  return stream_open(ctx, "glc_stream_enc_open", channels, n_streams, 2ull * glc::kFrame * channels * sizeof(float), out);
 }
 
-void glc_stream_enc_close(glc_stream_enc *s) {
-  if (!s) return;
-  DeviceGuard guard(s->ctx->device);
-  (void)hipStreamSynchronize(s->ctx->stream);  // queued pushes may still read and write the session's buffers
-  delete s;
-}
+void glc_stream_enc_close(glc_stream_enc *s) { stream_close(s); }
 
 int glc_stream_enc_reset(glc_stream_enc *s, uint64_t stream) {
   if (!s) return GLC_EINVAL;
@@ -3671,43 +3573,29 @@ static int stream_push_device_checked(glc_stream_enc *s, const char *who, const 
   glc_ctx *ctx = s->ctx;
   const std::string w(who);
   if (!in || !d_pcm || !d_arena || !d_cursor || !d_entries || !segs || !n_segs) return fail(ctx, GLC_EINVAL, w + ": null argument");
-  if (const int rc = rtb_check_fmt(ctx, w, fmt, bits)) return rc;
+  if (const char *bad = fmt_fault(fmt, bits)) return fail(ctx, GLC_EINVAL, w + ": " + bad);
   if (in->n_clips != s->n || in->channels != s->ch)
     return fail(ctx, GLC_EINVAL, w + ": the layout's n_clips and channels must be the session's");
   const RtbPcm pcm{d_pcm, fmt, bits};
-  if (reinterpret_cast<uintptr_t>(d_pcm) & (pcm.elem() - 1u)) return fail(ctx, GLC_EINVAL, w + ": d_pcm is not aligned to its sample size");
-  if (reinterpret_cast<uintptr_t>(d_arena) & 63u) return fail(ctx, GLC_EINVAL, w + ": d_arena is not 64-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(d_cursor) | reinterpret_cast<uintptr_t>(d_entries)) & 7u)
-    return fail(ctx, GLC_EINVAL, w + ": d_cursor and d_entries must be 8-byte aligned");
+  if (const char *bad = store_fill_misaligned(pcm, d_arena, d_cursor, d_entries)) return fail(ctx, GLC_EINVAL, w + ": " + bad);
   const RtbLayout li{in};
-  DeviceGuard guard(ctx->device);
-  try {  // no C++ exception may cross the C ABI
+  return on_device(ctx, w, [&]() -> int {
     std::vector<StreamLanePush> act;
     if (const int rc = stream_plan_lanes(s, w, in->lengths, in->length, finish, &act)) return rc;
     for (uint64_t i = 0; i < s->n; ++i) {
-      if (li.len(i) == 0) continue;
-      const std::string lane = w + ": lane " + std::to_string(i);
-      if (li.planes() && in->channel_stride < li.len(i)) return fail(ctx, GLC_EINVAL, lane + ": channel_stride is smaller than a plane");
-      if (s->n > 1 && in->clip_stride < li.occupies(i)) return fail(ctx, GLC_EINVAL, lane + ": clip_stride is smaller than the chunk");
+      if (li.len(i) == 0) continue;  // a lane that brings nothing has no chunk to place
+      if (const char *bad = stride_fault(li, i)) return fail(ctx, GLC_EINVAL, w + ": lane " + std::to_string(i) + ": " + bad);
     }
-    {
-      const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_pcm), a1 = li.end_of(d_pcm, pcm.elem());
-      const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_arena), b1 = b0 + arena_bytes;
-      const uintptr_t e0 = reinterpret_cast<uintptr_t>(d_entries), e1 = e0 + s->n * sizeof(glc_store_entry);
-      if (a0 < b1 && b0 < a1) return fail(ctx, GLC_EINVAL, w + ": the arena overlaps the input");
-      if (a0 < e1 && e0 < a1) return fail(ctx, GLC_EINVAL, w + ": the entries overlap the input");
-    }
+    if (const char *bad = store_fill_overlap(pcm, li, d_arena, arena_bytes, d_entries)) return fail(ctx, GLC_EINVAL, w + ": " + bad);
     return stream_push_core(s, pcm, li, act, d_arena, arena_bytes, d_cursor, d_entries, segs, n_segs);
-  } catch (const std::bad_alloc &) {
-    return fail(ctx, GLC_ENOMEM, w + ": host allocation failed");
-  }
+  });
 }
 
 int glc_stream_enc_push_device(glc_stream_enc *s, const void *d_pcm, glc_pcm_format fmt, uint32_t bits, const glc_clip_layout *in,
                                const uint8_t *finish, void *d_arena, uint64_t arena_bytes, uint64_t *d_cursor,
                                glc_store_entry *d_entries, glc_stream_seg *segs, uint64_t *n_segs) {
   if (!s) return GLC_EINVAL;
-  if (s->mode == 1) return fail(s->ctx, GLC_EINVAL, "glc_stream_enc_push_device: this session takes host pushes");
+  if (const int rc = stream_mode_gate(s, "glc_stream_enc_push_device", 2)) return rc;
   const int rc = stream_push_device_checked(s, "glc_stream_enc_push_device", d_pcm, fmt, bits, in, finish, d_arena, arena_bytes, d_cursor,
                                             d_entries, segs, n_segs);
   if (rc == GLC_OK) s->mode = 2;
@@ -3719,14 +3607,13 @@ int glc_stream_enc_push(glc_stream_enc *s, const void *const *pcm, glc_pcm_forma
   if (!s) return GLC_EINVAL;
   glc_ctx *ctx = s->ctx;
   const std::string w("glc_stream_enc_push");
-  if (s->mode == 2) return fail(ctx, GLC_EINVAL, w + ": this session takes device pushes");
+  if (const int rc = stream_mode_gate(s, w, 1)) return rc;
   if (!pcm || !n_samples) return fail(ctx, GLC_EINVAL, w + ": null argument");
-  if (const int rc = rtb_check_fmt(ctx, w, fmt, bits)) return rc;
+  if (const char *bad = fmt_fault(fmt, bits)) return fail(ctx, GLC_EINVAL, w + ": " + bad);
   const uint32_t ch = s->ch;
-  const size_t elem = fmt == GLC_PCM_S16 ? 2 : 4;
+  const size_t elem = pcm_elem(fmt);
   const uint64_t max_push = glc_stream_enc_max_push(static_cast<uint16_t>(ch));
-  DeviceGuard guard(ctx->device);
-  try {
+  return on_device(ctx, w, [&]() -> int {
     std::vector<uint64_t> left(s->n), lens(s->n);
     bool any = false;
     for (uint64_t i = 0; i < s->n; ++i) {
@@ -3735,7 +3622,7 @@ int glc_stream_enc_push(glc_stream_enc *s, const void *const *pcm, glc_pcm_forma
       const bool fin = finish && finish[i];
       if (n_samples[i] % ch) return fail(ctx, GLC_EINVAL, lane + ": n_samples is not a multiple of channels");
       if (n_samples[i] && !pcm[i]) return fail(ctx, GLC_EINVAL, lane + ": null samples");
-      if (n_samples[i] && (reinterpret_cast<uintptr_t>(pcm[i]) & (elem - 1u))) return fail(ctx, GLC_EINVAL, lane + ": samples are not aligned");
+      if (n_samples[i] && !aligned(pcm[i], elem)) return fail(ctx, GLC_EINVAL, lane + ": samples are not aligned");
       if ((n_samples[i] || fin) && L.finished) return fail(ctx, GLC_EINVAL, lane + ": the stream is finished and has not been taken");
       left[i] = n_samples[i] / ch;
       glc_stream_push_plan plan;
@@ -3817,9 +3704,7 @@ int glc_stream_enc_push(glc_stream_enc *s, const void *const *pcm, glc_pcm_forma
       }
     }
     return GLC_OK;
-  } catch (const std::bad_alloc &) {
-    return fail(ctx, GLC_ENOMEM, w + ": host allocation failed");
-  }
+  });
 }
 
 int glc_stream_enc_segments(const glc_stream_enc *s, uint64_t stream, uint64_t *n_blobs) {
@@ -3865,16 +3750,11 @@ int glc_stream_enc_frames(glc_stream_enc *s, uint64_t stream, glc_frames **out) 
 
 // ------------------------------------------------------------------------------ streaming decode
 
-struct glc_stream_dec {
-  glc_ctx *ctx = nullptr;
-  uint32_t ch = 0;
-  uint64_t n = 0;
-  int mode = 0;       // 0: no push yet, 1: host pushes, 2: device pushes
-  DevBuf carry;       // [lane][2][ch][1024] floats: (a) the last hop's finished sums, (b) the last frame's second half
+struct glc_stream_dec : StreamSession {
+  // lane_buf is the carry, [lane][2][ch][1024] floats: (a) the last hop's finished sums, (b) the last frame's second half
   std::vector<uint64_t> done;  // frames taken per lane
-  // host pushes
-  HostBuf up, down;   // pinned: the blobs and entries going up, the samples coming down
-  DevBuf arena, d_entries, d_out;
+  void size_lanes(uint64_t k) { done.assign(k, 0); }
+  DevBuf arena, d_entries, d_out;  // host pushes
   uint64_t carry_at(uint64_t lane) const { return lane * 2ull * glc::kHop * ch; }
 };
 
@@ -4026,7 +3906,7 @@ int stream_dec_core(glc_stream_dec *s, const std::vector<DecLanePush> &act, cons
                                              static_cast<uint32_t>(n_segs), d_dir, d_verdict, st));
   auto *d_status = static_cast<glc::CompactStatus *>(ctx->cd_status.p);
   float *blocks = static_cast<float *>(ctx->blocks.p);
-  float *carry = static_cast<float *>(s->carry.p);
+  float *carry = static_cast<float *>(s->lane_buf.p);
   for (const Round &R : rounds) {
     const uint32_t M = static_cast<uint32_t>(R.n_real * ch);
     if (M) {
@@ -4034,8 +3914,7 @@ int stream_dec_core(glc_stream_dec *s, const std::vector<DecLanePush> &act, cons
       // pairs and raw planes are addressed from the arena: every usable blob lies inside it, 64-byte aligned
       GLC_HIP(ctx, glc::launch_rows_from_compact_window(d_dir + R.seg_first, glc::CompactBlob{}, static_cast<uint32_t>(R.seg_n), M, ch, 0u,
                                                         d_arena, ctx->rt_rows.p, d_status + R.seg_first, st, &rows, d_verdict + R.seg_first));
-      GLC_HIP(ctx, glc::launch_imdct_rows(ctx->dev, rows, 0, M, ch, blocks, st, ctx->d1_variant, ctx->dec_plan.p,
-                                          ctx->dec_plan.p ? ctx->dec_plan_groups : 0, false));
+      GLC_HIP(ctx, launch_d1_rows(ctx, rows, 0, M, ch, blocks, st));
     }
     GLC_HIP(ctx, glc::launch_stream_dec_carry(false, image.dev<glc::StreamCarry>(R.o_load), static_cast<uint32_t>(R.n_load), ch, blocks, carry, st));
     if (R.n_desc)
@@ -4093,36 +3972,30 @@ int stream_dec_push_device_checked(glc_stream_dec *s, const std::string &w, cons
   glc_ctx *ctx = s->ctx;
   if (!out || !d_out || (n_segs && (!d_arena || !d_entries || !segs))) return fail(ctx, GLC_EINVAL, w + ": null argument");
   if (out->n_clips != s->n || out->channels != s->ch) return fail(ctx, GLC_EINVAL, w + ": the layout's n_clips and channels must be the session's");
-  if (reinterpret_cast<uintptr_t>(d_arena) & 63u) return fail(ctx, GLC_EINVAL, w + ": d_arena is not 64-byte aligned");
-  if (reinterpret_cast<uintptr_t>(d_entries) & 7u) return fail(ctx, GLC_EINVAL, w + ": d_entries must be 8-byte aligned");
-  if (reinterpret_cast<uintptr_t>(d_out) & (sizeof(T) - 1u)) return fail(ctx, GLC_EINVAL, w + ": output pointer not aligned to its sample size");
+  if (!aligned(d_arena, 64)) return fail(ctx, GLC_EINVAL, w + ": d_arena is not 64-byte aligned");
+  if (!aligned(d_entries, 8)) return fail(ctx, GLC_EINVAL, w + ": d_entries must be 8-byte aligned");
+  if (!aligned(d_out, sizeof(T))) return fail(ctx, GLC_EINVAL, w + ": output pointer not aligned to its sample size");
   if (n_segs > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, w + ": too many segments");
   const RtbLayout lo{out};
-  DeviceGuard guard(ctx->device);
-  try {  // no C++ exception may cross the C ABI
+  return on_device(ctx, w, [&]() -> int {
     std::vector<DecLanePush> act;
     if (const int rc = stream_dec_plan_lanes(s, w, segs, n_segs, finish, total_len, &act)) return rc;
     size_t at = 0;
     for (uint64_t i = 0; i < s->n; ++i) {
-      const std::string lane = w + ": lane " + std::to_string(i);
+      auto refuse = [&](const char *what) { return fail(ctx, GLC_EINVAL, w + ": lane " + std::to_string(i) + ": " + what); };
       uint64_t emits = 0;
       if (at < act.size() && act[at].lane == i) emits = act[at++].plan.n_samples;
-      if (lo.len(i) != emits) return fail(ctx, GLC_EINVAL, lane + ": the layout's length is not what the push emits (glc_plan_stream_dec_push)");
-      if (!emits) continue;
-      if (lo.planes() && out->channel_stride < emits) return fail(ctx, GLC_EINVAL, lane + ": channel_stride is smaller than a plane");
-      if (s->n > 1 && out->clip_stride < lo.occupies(i)) return fail(ctx, GLC_EINVAL, lane + ": clip_stride is smaller than the clip");
+      if (lo.len(i) != emits) return refuse("the layout's length is not what the push emits (glc_plan_stream_dec_push)");
+      if (!emits) continue;  // a lane that emits nothing has no samples to place
+      if (const char *bad = stride_fault(lo, i)) return refuse(bad);
     }
-    {
-      const uintptr_t b0 = reinterpret_cast<uintptr_t>(d_out), b1 = lo.end_of(d_out, sizeof(T));
-      const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_arena), a1 = a0 + arena_bytes;
-      const uintptr_t e0 = reinterpret_cast<uintptr_t>(d_entries), e1 = e0 + n_segs * sizeof(glc_store_entry);
-      if (n_segs && a0 < b1 && b0 < a1) return fail(ctx, GLC_EINVAL, w + ": the output extent overlaps the arena");
-      if (n_segs && e0 < b1 && b0 < e1) return fail(ctx, GLC_EINVAL, w + ": the output extent overlaps the entries");
+    if (n_segs) {  // a push without segments reads neither the arena nor the entries
+      const ByteSpan all = span_of(d_out, lo, sizeof(T));
+      if (overlaps(span_of(d_arena, arena_bytes), all)) return fail(ctx, GLC_EINVAL, w + ": the output extent overlaps the arena");
+      if (overlaps(span_of(d_entries, n_segs * sizeof(glc_store_entry)), all)) return fail(ctx, GLC_EINVAL, w + ": the output extent overlaps the entries");
     }
     return stream_dec_core<T>(s, act, segs, n_segs, d_arena, arena_bytes, d_entries, total_len, d_out, lo);
-  } catch (const std::bad_alloc &) {
-    return fail(ctx, GLC_ENOMEM, w + ": host allocation failed");
-  }
+  });
 }
 
 }  // namespace
@@ -4144,32 +4017,10 @@ uint64_t glc_stream_dec_max_push(uint16_t channels) {
 }
 
 int glc_stream_dec_open(glc_ctx *ctx, uint16_t channels, uint64_t n_streams, glc_stream_dec **out) {
-  if (!ctx) return GLC_EINVAL;
-  if (!out) return fail(ctx, GLC_EINVAL, "glc_stream_dec_open: null argument");
-  *out = nullptr;
-  if (channels == 0 || n_streams == 0) return fail(ctx, GLC_EINVAL, "glc_stream_dec_open: no channels or no streams");
-  const uint64_t per_lane = 2ull * glc::kHop * channels * sizeof(float);
-  if (n_streams > (1ull << 46) / per_lane) return fail(ctx, GLC_EINVAL, "glc_stream_dec_open: too many streams");
-  DeviceGuard guard(ctx->device);
-  try {
-    std::unique_ptr<glc_stream_dec> s(new glc_stream_dec);
-    s->ctx = ctx, s->ch = channels, s->n = n_streams;
-    s->done.assign(n_streams, 0);
-    const hipError_t e = s->carry.reserve(n_streams * per_lane);
-    if (e != hipSuccess) return hip_fail(ctx, e, "glc_stream_dec_open: hipMalloc");
-    *out = s.release();
-    return GLC_OK;
-  } catch (const std::bad_alloc &) {
-    return fail(ctx, GLC_ENOMEM, "glc_stream_dec_open: host allocation failed");
-  }
+  return stream_open(ctx, "glc_stream_dec_open", channels, n_streams, 2ull * glc::kHop * channels * sizeof(float), out);
 }
 
-void glc_stream_dec_close(glc_stream_dec *s) {
-  if (!s) return;
-  DeviceGuard guard(s->ctx->device);
-  (void)hipStreamSynchronize(s->ctx->stream);  // queued pushes may still read and write the session's buffers
-  delete s;
-}
+void glc_stream_dec_close(glc_stream_dec *s) { stream_close(s); }
 
 int glc_stream_dec_reset(glc_stream_dec *s, uint64_t stream) {
   if (!s) return GLC_EINVAL;
@@ -4190,8 +4041,8 @@ int glc_stream_dec_push_device(glc_stream_dec *s, const void *d_arena, uint64_t 
                                glc_pcm_format out_fmt, const glc_clip_layout *out) {
   if (!s) return GLC_EINVAL;
   const std::string w("glc_stream_dec_push_device");
-  if (s->mode == 1) return fail(s->ctx, GLC_EINVAL, w + ": this session takes host pushes");
-  if (out_fmt != GLC_PCM_F32 && out_fmt != GLC_PCM_S16) return fail(s->ctx, GLC_EINVAL, w + ": out_fmt must be GLC_PCM_F32 or GLC_PCM_S16");
+  if (const int rc = stream_mode_gate(s, w, 2)) return rc;
+  if (const char *bad = out_fmt_fault(out_fmt)) return fail(s->ctx, GLC_EINVAL, w + ": " + bad);
   const int rc = out_fmt == GLC_PCM_F32 ? stream_dec_push_device_checked(s, w, d_arena, arena_bytes, d_entries, segs, n_segs, finish, total_len,
                                                                          static_cast<float *>(d_out), out)
                                         : stream_dec_push_device_checked(s, w, d_arena, arena_bytes, d_entries, segs, n_segs, finish, total_len,
@@ -4205,14 +4056,13 @@ int glc_stream_dec_push(glc_stream_dec *s, const void *const *blobs, const uint6
   if (!s) return GLC_EINVAL;
   glc_ctx *ctx = s->ctx;
   const std::string w("glc_stream_dec_push");
-  if (s->mode == 2) return fail(ctx, GLC_EINVAL, w + ": this session takes device pushes");
-  if (out_fmt != GLC_PCM_F32 && out_fmt != GLC_PCM_S16) return fail(ctx, GLC_EINVAL, w + ": out_fmt must be GLC_PCM_F32 or GLC_PCM_S16");
+  if (const int rc = stream_mode_gate(s, w, 1)) return rc;
+  if (const char *bad = out_fmt_fault(out_fmt)) return fail(ctx, GLC_EINVAL, w + ": " + bad);
   if (!pcm_out || !n_out || (n_segs && (!blobs || !blob_bytes || !segs))) return fail(ctx, GLC_EINVAL, w + ": null argument");
   if (n_segs > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, w + ": too many segments");
   const uint32_t ch = s->ch;
-  const size_t elem = out_fmt == GLC_PCM_S16 ? 2 : 4;
-  DeviceGuard guard(ctx->device);
-  try {
+  const size_t elem = pcm_elem(out_fmt);
+  return on_device(ctx, w, [&]() -> int {
     std::vector<DecLanePush> act;
     if (const int rc = stream_dec_plan_lanes(s, w, segs, n_segs, finish, total_len, &act)) return rc;
     // the session's arena: the blobs back to back at multiples of 64, the entries behind them in the same pinned image
@@ -4257,9 +4107,7 @@ int glc_stream_dec_push(glc_stream_dec *s, const void *const *blobs, const uint6
     for (uint64_t i = 0; i < s->n; ++i)
       if (lens[i]) std::memcpy(pcm_out[i], static_cast<const uint8_t *>(s->down.p) + i * stride * elem, lens[i] * ch * elem);
     return GLC_OK;
-  } catch (const std::bad_alloc &) {
-    return fail(ctx, GLC_ENOMEM, w + ": host allocation failed");
-  }
+  });
 }
 
 int glc_debug_stream_dec_carry_device(glc_ctx *ctx, int save, int32_t prev, int32_t cur, uint16_t channels, float *d_blocks,
@@ -4267,8 +4115,7 @@ int glc_debug_stream_dec_carry_device(glc_ctx *ctx, int save, int32_t prev, int3
   const std::string w("glc_debug_stream_dec_carry_device");
   if (!ctx) return GLC_EINVAL;
   if (!d_blocks || !d_carry || channels == 0) return fail(ctx, GLC_EINVAL, w + ": null argument or channels == 0");
-  if ((reinterpret_cast<uintptr_t>(d_blocks) | reinterpret_cast<uintptr_t>(d_carry)) & 15u)
-    return fail(ctx, GLC_EINVAL, w + ": blocks and carry must be 16-byte aligned");
+  if (!all_aligned(16, d_blocks, d_carry)) return fail(ctx, GLC_EINVAL, w + ": blocks and carry must be 16-byte aligned");
   const int64_t n = static_cast<int64_t>(std::min<uint64_t>(n_slots, 0x7FFFFFFFull));
   const bool ok = save ? (prev >= -1 && prev < n && cur >= 0 && cur < n) : (prev >= 0 && int64_t(prev) + 1 < n);
   if (!ok) return fail(ctx, GLC_EINVAL, w + ": a slot outside the blocks");
@@ -4364,7 +4211,7 @@ int glc_debug_compact_batch_device(glc_ctx *ctx, const void *d_records, const ui
     if (clip_frames[i] == 0 || clip_frames[i] > 0xFFFFFFFFull)
       return fail(ctx, GLC_EINVAL, "glc_debug_compact_batch_device: a clip of no frames, or of too many");
   if (n_clips > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, "glc_debug_compact_batch_device: too many clips");
-  if (reinterpret_cast<uintptr_t>(d_records) % 8 != 0 || reinterpret_cast<uintptr_t>(d_blob) % 8 != 0)
+  if (!all_aligned(8, d_records, d_blob))
     return fail(ctx, GLC_EINVAL, "glc_debug_compact_batch_device: d_records and d_blob must be 8-byte aligned");
   const BatchBlobLayout l = batch_blob_layout(channels, clip_frames, n_clips);
   if (cap < l.at.bound) return fail(ctx, GLC_EINVAL, "glc_debug_compact_batch_device: blob buffer too small");
@@ -4388,13 +4235,12 @@ int glc_debug_rows_from_compact(glc_ctx *ctx, const void *d_blob, uint64_t blob_
   const std::string w("glc_debug_rows_from_compact");
   if (!ctx) return GLC_EINVAL;
   if (channels == 0 || n_frames == 0 || n_frames * channels > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, w + ": bad shape");
-  int rc = cd_check_blob(ctx, w, d_blob, blob_bytes, channels, n_frames);
-  if (rc != GLC_OK) return rc;
+  if (const char *bad = cd_blob_fault(d_blob, blob_bytes, channels, n_frames)) return fail(ctx, GLC_EINVAL, w + ": " + bad);
   DeviceGuard guard(ctx->device);
   const uint32_t M = static_cast<uint32_t>(n_frames * channels);
   rt_forget_streams(ctx);
   ctx->cd_status_n = 0;
-  rc = rt_reserve(ctx, ctx->rt_rows, glc::rows_from_compact_bytes(M));
+  int rc = rt_reserve(ctx, ctx->rt_rows, glc::rows_from_compact_bytes(M));
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->cd_status, sizeof(glc::CompactStatus));
   if (rc != GLC_OK) return rc;
   const glc::CompactBlob one{reinterpret_cast<uintptr_t>(d_blob), blob_bytes, 0u, M, {0u, 0u}};
@@ -4418,13 +4264,12 @@ int glc_debug_rows_from_compact_window(glc_ctx *ctx, const void *d_blob, uint64_
   if (!ctx) return GLC_EINVAL;
   if (channels == 0 || n_frames == 0 || n_frames * channels > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, w + ": bad shape");
   if (frames == 0 || first_frame > n_frames || frames > n_frames - first_frame) return fail(ctx, GLC_EINVAL, w + ": the window leaves the blob");
-  int rc = cd_check_blob(ctx, w, d_blob, blob_bytes, channels, n_frames);
-  if (rc != GLC_OK) return rc;
+  if (const char *bad = cd_blob_fault(d_blob, blob_bytes, channels, n_frames)) return fail(ctx, GLC_EINVAL, w + ": " + bad);
   DeviceGuard guard(ctx->device);
   const uint32_t M = static_cast<uint32_t>(frames * channels), front = static_cast<uint32_t>(first_frame * channels);
   rt_forget_streams(ctx);
   ctx->cd_status_n = 0;
-  rc = rt_reserve(ctx, ctx->rt_rows, glc::rows_from_compact_window_bytes(M));
+  int rc = rt_reserve(ctx, ctx->rt_rows, glc::rows_from_compact_window_bytes(M));
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->cd_status, sizeof(glc::CompactStatus));
   if (rc != GLC_OK) return rc;
   const glc::CompactBlob one{reinterpret_cast<uintptr_t>(d_blob), blob_bytes, 0u, static_cast<uint32_t>(n_frames * channels), {front, M}};

@@ -288,6 +288,17 @@ def test_arguments_refused_before_anything_is_queued(glc_amd, torch):
     assert call(d.data_ptr(), nbytes, n, 2, out.data_ptr() + 2, n) == EINVAL
     assert call(d.data_ptr(), nbytes, n, 2, out.data_ptr(), n - 1) == EINVAL and got.value == n
     assert call(d.data_ptr(), nbytes, n, 2, d.data_ptr() + 64, n) == EINVAL                 # the output overlaps the blob
+    hook = g.lib.glc_debug_rows_from_compact                                                # the R2 hook checks a blob as the call does
+    hook.restype, hook.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint16] + [C.c_void_p] * 6
+    st = (C.c_uint64 * 3)()
+    for blob_at, nb in ((d.data_ptr() + 32, nbytes - 32), (d.data_ptr(), o_pairs - 1), (None, nbytes)):
+        assert hook(dec._h, blob_at, nb, 5, 2, None, None, None, None, None, C.addressof(st)) == EINVAL
+        assert b"glc_debug_rows_from_compact" in g.lib.glc_last_error(dec._h)
+    window = g.lib.glc_debug_rows_from_compact_window                                       # ... and so does its window twin
+    window.restype, window.argtypes = C.c_int, hook.argtypes[:5] + [C.c_uint64, C.c_uint64] + [C.c_void_p] * 6
+    for blob_at, nb in ((d.data_ptr() + 32, nbytes - 32), (d.data_ptr(), o_pairs - 1), (None, nbytes)):
+        assert window(dec._h, blob_at, nb, 5, 2, 1, 3, None, None, None, None, None, C.addressof(st)) == EINVAL
+        assert b"glc_debug_rows_from_compact_window" in g.lib.glc_last_error(dec._h)
     torch.cuda.synchronize()
     assert np.all(out.cpu().numpy().view(np.uint32) == NAN_BITS)
     assert call(d.data_ptr(), o_pairs, n, 2, out.data_ptr(), n) == 0                        # the minimum passes the host

@@ -469,6 +469,16 @@ def test_arguments_refused_before_anything_is_queued(gpu):
         if what in ("a clip the encoder refuses", "channel_stride smaller than a plane", "clip_stride smaller than the clip"):
             assert "clip 1" in msg, (what, msg)
     assert f(None, None, None, None, 0, None, None) == EINVAL
+    # the A1-A3 hook holds the same four pointers to the same alignments: the arena to 64 bytes (32 is not enough), the
+    # records, the cursor and the entries to 8
+    one_each = (C.c_uint64 * 2)(1, 1)
+    hook = lambda rec=0, a=0, cu=0, e=0: g.lib.glc_debug_compact_store_device(
+        enc._h, x.data_ptr() + rec, one_each, 2, 2, arena.data_ptr() + a, image.size - a, cursor.data_ptr() + cu, ent.data_ptr() + e)
+    for what, fn in {"arena": lambda: hook(a=32), "records": lambda: hook(rec=4), "cursor": lambda: hook(cu=4),
+                     "entries": lambda: hook(e=4)}.items():
+        assert fn() == EINVAL, what
+        msg = g.lib.glc_last_error(enc._h).decode()
+        assert "glc_debug_compact_store_device" in msg and "aligned" in msg, (what, msg)
     # nothing was queued: the arena, the cursor and the entries are what they were
     enc.synchronize()
     assert np.array_equal(arena.cpu().numpy(), image) and int(cursor.item()) == 128 and bool((ent == -1).all())

@@ -581,6 +581,16 @@ def test_arguments_refused_before_anything_is_queued(glc_amd, torch):
         call(d_out=Ln), call(d_out=Cl), call(d_out=St - 4 * 2399),
     ]
     assert refused == [EINVAL] * len(refused)
+    # the planner hook checks what the call checks: a clip that overlaps the next, an arena that is not aligned
+    hook = g.lib.glc_debug_store_plan_device
+    hook.restype = C.c_int
+    hook.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                     C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    plan = np.zeros(4096, np.uint8)
+    for arena_at, layout, what in ((A, lay(cs=1199), b"clip_stride"), (A + 32, lay(), b"64-byte")):
+        assert hook(dec._h, arena_at, store.arena.numel(), E, Ln, n_e, ml, Cl, St, length, o, C.addressof(layout), plan.ctypes.data,
+                    plan.ctypes.data, plan.ctypes.data) == EINVAL
+        assert b"glc_debug_store_plan_device" in g.lib.glc_last_error(dec._h) and what in g.lib.glc_last_error(dec._h)
     torch.cuda.synchronize()
     assert np.all(out.cpu().numpy().view(np.uint32) == NAN_BITS)
     assert g.lib.glc_decode_compact_last_status(dec._h, (L.GlcCompactStatus * 2)(), 2) == EINVAL      # nothing has completed

@@ -792,6 +792,9 @@ def test_the_carry_keeps_the_sign_of_zero(E, ch):
     assert np.array_equal(bits(first), bits((F32(0.0) + blocks[1, :, :1024]).astype(F32))) and not np.signbit(first[:, :600]).any()
     for bad in ((1, 0, 4), (1, -2, 1), (0, 3, -1), (0, -1, -1)):
         assert f(h, bad[0], bad[1], bad[2], ch, d_blocks.data_ptr(), 4, d_carry.data_ptr()) == EINVAL
+    for blocks_at, carry_at in ((8, 0), (0, 4)):                                               # float4 accesses: 16-byte pointers
+        assert f(h, 1, 0, 1, ch, d_blocks.data_ptr() + blocks_at, 4, d_carry.data_ptr() + carry_at) == EINVAL
+        assert b"glc_debug_stream_dec_carry_device" in lib.glc_last_error(h) and b"16-byte" in lib.glc_last_error(h)
 
 
 # ------------------------------------------------------------------------------------------ 8. the C++ mirror

@@ -616,6 +616,12 @@ def test_device_refusals_change_nothing(E):
         as_arena = lay.d.view(torch.uint8)
         assert S.push_device(lay, None, as_arena, cursor, entries, arena_bytes=256)[0] == EINVAL        # an arena that overlaps the input
         assert b"overlaps" in S.err()
+        as_entries = lay.d.view(torch.uint8)[64:]
+        assert S.push_device(lay, None, arena, cursor, as_entries)[0] == EINVAL                         # entries inside the input
+        assert b"glc_stream_enc_push_device" in S.err() and b"entries overlap" in S.err()
+        lay.fmt = 7
+        assert S.push_device(lay, None, arena, cursor, entries)[0] == EINVAL and b"sample format" in S.err()
+        lay.fmt = PF32
         assert S.push_device(lay, None, arena, cursor, entries, bits=0)[0] == 0                         # (bits is ignored for floats)
         E.enc.synchronize()
         assert int(cursor.item()) == state[1]                                                           # 2500 samples: still one frame
