@@ -279,8 +279,8 @@ def compact_bound(channels: int, n_frames: int) -> int:
 def compact_store_bound(channels: int, lengths) -> int:
     """Arena bytes that hold the blobs of clips of `lengths` samples per channel whatever their content
     (glc_compact_store_bound: the sum of compact_bound over the clips)."""
-    lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-    arr = (C.c_uint64 * max(len(lens), 1))(*lens)
+    lens = _ints(lengths)
+    arr = _c_array(C.c_uint64, lens)
     lay = GlcClipLayout(len(lens), channels, 0, 0, 0, 0, C.cast(arr, C.POINTER(C.c_uint64)))
     return int(lib.glc_compact_store_bound(C.byref(lay)))
 
@@ -362,6 +362,19 @@ _PCM_FORMATS = {np.dtype(np.int16): (GLC_PCM_S16, 16), np.dtype(np.int32): (GLC_
 _PCM_DTYPES = {GLC_PCM_S16: np.int16, GLC_PCM_S32: np.int32, GLC_PCM_F32: np.float32}
 
 
+def _pcm_bits(fmt: int, width: int, bits: Optional[int], dtype) -> int:
+    """The `bits` rule of every call that takes PCM: none for float32 samples (TypeError), 1..width for integer
+    ones (GlcError), default the container's width."""
+    if fmt == GLC_PCM_F32:
+        if bits is not None:
+            raise TypeError("bits applies to integer samples only")
+        return 32
+    bits = width if bits is None else int(bits)
+    if not 1 <= bits <= width:
+        raise GlcError(GLC_EINVAL, f"bits must be 1..{width} for {dtype} samples")
+    return bits
+
+
 def pcm_format(samples, bits: Optional[int] = None):
     """(flat C-contiguous array, glc_pcm_format, bits) of samples handed to an encoder: float32, or
     int16 / int32 holding `bits`-bit values (default: the container's width).  An array of any other
@@ -372,32 +385,22 @@ def pcm_format(samples, bits: Optional[int] = None):
     if np.dtype(dt) not in _PCM_FORMATS:
         raise TypeError(f"samples must be float32, int16 or int32, not {dt}")
     fmt, width = _PCM_FORMATS[np.dtype(dt)]
-    if fmt == GLC_PCM_F32:
-        if bits is not None:
-            raise TypeError("bits applies to integer samples only")
-    else:
-        bits = width if bits is None else int(bits)
-        if not 1 <= bits <= width:
-            raise GlcError(GLC_EINVAL, f"bits must be 1..{width} for {np.dtype(dt)} samples")
-    return np.ascontiguousarray(samples).reshape(-1), fmt, bits or 32
+    return np.ascontiguousarray(samples).reshape(-1), fmt, _pcm_bits(fmt, width, bits, np.dtype(dt))
+
+
+_TORCH_PCM_FORMATS = {}   # torch dtype -> (glc_pcm_format, container bits); filled by the first tensor call, torch is imported lazily
 
 
 def _tensor_pcm_format(t, bits: Optional[int], what: str = "x"):
     """(glc_pcm_format, bits) of a torch tensor handed to a device batch call: float32, or int16 / int32 holding
     `bits`-bit values - the defaults and the checks pcm_format applies to integer arrays."""
-    import torch
-    formats = {torch.float32: (GLC_PCM_F32, 32), torch.int16: (GLC_PCM_S16, 16), torch.int32: (GLC_PCM_S32, 32)}
-    if getattr(t, "dtype", None) not in formats:
+    if not _TORCH_PCM_FORMATS:
+        import torch
+        _TORCH_PCM_FORMATS.update({getattr(torch, np.dtype(dt).name): f for dt, f in _PCM_FORMATS.items()})
+    if getattr(t, "dtype", None) not in _TORCH_PCM_FORMATS:
         raise TypeError(f"{what} must be a float32, int16 or int32 CUDA tensor")
-    fmt, width = formats[t.dtype]
-    if fmt == GLC_PCM_F32:
-        if bits is not None:
-            raise TypeError("bits applies to integer samples only")
-        return fmt, 32
-    bits = width if bits is None else int(bits)
-    if not 1 <= bits <= width:
-        raise GlcError(GLC_EINVAL, f"bits must be 1..{width} for {t.dtype} samples")
-    return fmt, bits
+    fmt, width = _TORCH_PCM_FORMATS[t.dtype]
+    return fmt, _pcm_bits(fmt, width, bits, t.dtype)
 
 
 def _tensor_out_dtype(dtype, out):
@@ -412,6 +415,83 @@ def _tensor_out_dtype(dtype, out):
     if name not in ("float32", "int16"):
         raise TypeError(f"dtype must be float32 or int16, not {dtype}")
     return getattr(torch, name)
+
+
+def _out_format(out) -> int:
+    """glc_pcm_format of an output tensor that _tensor_out_dtype passed: int16 or float32."""
+    return GLC_PCM_S16 if out.dtype.itemsize == 2 else GLC_PCM_F32
+
+
+def _entry_in(name: str, fmt: int, bits: int):
+    """Where the samples' format chooses the entry point: (`name`, ()) for float32 input, (`name`_int, (fmt, bits)) -
+    the arguments that follow the samples - for integer PCM."""
+    return (getattr(lib, name), ()) if fmt == GLC_PCM_F32 else (getattr(lib, name + "_int"), (fmt, bits))
+
+
+def _entry_out(name: str, out):
+    """Where the output's format chooses the entry point: `name` gives float32, `name`_i16 int16."""
+    return getattr(lib, name + "_i16" if _out_format(out) == GLC_PCM_S16 else name)
+
+
+def _ints(values) -> list:
+    """A sequence or a tensor of integers as a list of int."""
+    return [int(v) for v in (values.tolist() if hasattr(values, "tolist") else values)]
+
+
+def _c_array(ctype, values):
+    """A ctypes array of `values`, never of length 0: an empty batch still hands the C side a pointer."""
+    return (ctype * max(len(values), 1))(*values)
+
+
+def _clip_layout(t, planar: bool, what: str):
+    """(GlcClipLayout, B, C, T) of a padded batch tensor (B, C, T) (planar) or (B, T, C): the strides between clips and
+    planes are the tensor's own, so a slice of something bigger is described where it lies.  The samples of a plane,
+    or the channels of an interleaved sample, are adjacent; an interleaved clip is dense.  Reads shape and strides
+    only; that `t` is a CUDA tensor of the right dtype on the right device is _Ctx._tensor's rule."""
+    if t.dim() != 3:
+        raise TypeError(f"{what} must have shape (B, C, T) or (B, T, C)")
+    if t.shape[2] > 1 and t.stride(2) != 1:
+        raise TypeError(f"{what}: the innermost stride must be 1")
+    if min(t.stride(0), t.stride(1)) < 0:
+        raise TypeError(f"{what}: negative strides")
+    b, c, n = (t.shape[0], t.shape[1], t.shape[2]) if planar else (t.shape[0], t.shape[2], t.shape[1])
+    if not planar and b and c and n > 1 and t.stride(1) != c:
+        raise TypeError(f"{what}: an interleaved clip must be dense (stride {c} between samples)")
+    return GlcClipLayout(b, c, 1 if planar else 0, t.stride(0), t.stride(1) if planar else 0, n, None), b, c, n
+
+
+def _set_lengths(lay: GlcClipLayout, lengths, b: int, t: int) -> list:
+    """Give `lay` the true lengths of its clips: `b` integers in [0, t], a sequence or a tensor.  The array the
+    layout points into is the layout's own attribute and lives as long as it; returns the lengths as a list."""
+    lens = _ints(lengths)
+    if len(lens) != b or any(v < 0 or v > t for v in lens):
+        raise GlcError(GLC_EINVAL, f"lengths must hold {b} values in [0, {t}]")
+    lay.lengths_array = _c_array(C.c_uint64, lens)
+    lay.lengths = C.cast(lay.lengths_array, C.POINTER(C.c_uint64))
+    return lens
+
+
+class _on_torch_stream:
+    """`with _on_torch_stream(ctx, device):` - the scope in which a context queues on torch's current stream of `device`,
+    the one way the tensor methods reach the stream (any context class, a stub in a test).  Entered, it hands that stream to
+    the context (set_stream); left, also by an exception, it restores the private stream (set_stream(0), which waits
+    for what was queued).  The legacy default stream has no handle to hand over (0 means the private stream, which
+    does not order itself against it): what torch has queued there - the fill of a fresh output, whatever produced
+    the input - is waited for instead."""
+    __slots__ = ("ctx", "device")
+
+    def __init__(self, ctx: "_Ctx", device):
+        self.ctx, self.device = ctx, device
+
+    def __enter__(self):
+        import torch
+        s = torch.cuda.current_stream(self.device)
+        if s.cuda_stream == 0:
+            s.synchronize()
+        self.ctx.set_stream(s.cuda_stream)
+
+    def __exit__(self, *exc):
+        self.ctx.set_stream(0)
 
 
 class _Ctx:
@@ -458,15 +538,53 @@ class _Ctx:
     def synchronize(self) -> None:
         check(lib.glc_ctx_synchronize(self._h), self._h)
 
-    def _enter_torch_stream(self, device) -> None:
-        """Queue on torch's current stream of `device`.  The legacy default stream has no handle to hand over (0
-        means the private stream, which does not order itself against it): what torch has queued there - the fill
-        of a fresh output, whatever produced the input - is waited for instead."""
+    def _tensor(self, t, what: str, dtypes, shape=None, contiguous: bool = True):
+        """`t` as it is, or the refusal: `what` must be a (contiguous) CUDA tensor of one of `dtypes` (one torch dtype
+        or a tuple) and, where `shape` is given, of its rank and sizes - None stands for any size - (TypeError), on
+        this context's device (GlcError)."""
         import torch
-        s = torch.cuda.current_stream(device)
-        if s.cuda_stream == 0:
-            s.synchronize()
-        self.set_stream(s.cuda_stream)
+        ok = isinstance(t, torch.Tensor) and t.is_cuda and (t.dtype in dtypes if isinstance(dtypes, tuple) else t.dtype == dtypes) \
+            and (not contiguous or t.is_contiguous()) and (shape is None or t.dim() == len(shape))
+        if ok and shape is not None:
+            for want, got in zip(shape, t.shape):
+                if want is not None and want != got:
+                    ok = False
+        if not ok:
+            names = " or ".join(str(d).replace("torch.", "") for d in (dtypes if isinstance(dtypes, tuple) else (dtypes,)))
+            of = "" if shape is None else f" of shape ({', '.join('n' if w is None else str(w) for w in shape)})"
+            raise TypeError(f"{what} must be a {'contiguous ' if contiguous else ''}{names} CUDA tensor{of}")
+        if t.get_device() != self.device:
+            raise GlcError(GLC_EINVAL, f"{what} is on {t.device}, this context on device {self.device}")
+        return t
+
+    def _pcm_tensor(self, x, bits: Optional[int]):
+        """(glc_pcm_format, bits) of the samples of a device batch call: `x` a 3-D CUDA tensor of a PCM dtype, any strides."""
+        import torch
+        return _tensor_pcm_format(self._tensor(x, "x", (torch.float32, torch.int16, torch.int32), (None, None, None), contiguous=False), bits)
+
+    def _append_tensors(self, arena, cursor):
+        """The arena and the cursor of the two calls that append to a store, checked."""
+        import torch
+        self._tensor(arena, "arena", torch.uint8, (None,))
+        if self._tensor(cursor, "cursor", torch.int64, contiguous=False).numel() != 1:
+            raise TypeError("cursor must be a one-element int64 CUDA tensor")
+
+    def _out_tensor(self, out, shape, dtype, planar: bool, contiguous: bool = False):
+        """(out, its GlcClipLayout, B, C, T) of a call that fills a padded batch: `out` None is a new zero-filled
+        tensor of `shape` and `dtype` (what _tensor_out_dtype gave) on this context's device, a given one is held
+        to _tensor and _clip_layout."""
+        import torch
+        if out is None:
+            out = torch.zeros(shape, dtype=dtype, device=torch.device("cuda", self.device))
+        self._tensor(out, "out", dtype, (None, None, None), contiguous)
+        return (out,) + _clip_layout(out, planar, "out")
+
+    def _compact_status(self, n: int) -> list:
+        """One CompactStatus per blob of the last call that decoded `n` compact blobs on this context."""
+        arr = (GlcCompactStatus * max(n, 1))()
+        if n:
+            check(lib.glc_decode_compact_last_status(self._h, arr, n), self._h)
+        return [CompactStatus(int(a.flags), int(a.n_bad_rows), int(a.first_bad_row)) for a in arr[:n]]
 
     def compact_store_tensor(self, arena, entries, lengths, keep, out_arena=None, used_bytes=None):
         """Evict clips from a store and close the gaps (glc_store_compact_device).  arena: the 1-D uint8 CUDA tensor;
@@ -481,29 +599,13 @@ class _Ctx:
         to or from it; queued on torch's current stream.  The context's resident stream, decode session and
         last-info records are untouched."""
         import torch
-        if not isinstance(arena, torch.Tensor) or not arena.is_cuda or arena.dtype != torch.uint8 or arena.dim() != 1 \
-                or not arena.is_contiguous():
-            raise TypeError("arena must be a contiguous 1-D uint8 CUDA tensor")
-        if arena.device.index != self.device:
-            raise GlcError(GLC_EINVAL, f"arena is on {arena.device}, this context on device {self.device}")
-        if not isinstance(entries, torch.Tensor) or not entries.is_cuda or entries.dtype != torch.int64 or entries.dim() != 2 \
-                or entries.shape[1] != 4 or not entries.is_contiguous():
-            raise TypeError("entries must be a contiguous int64 CUDA tensor of shape (n, 4)")
-        n = entries.shape[0]
-        if lengths is not None and (not isinstance(lengths, torch.Tensor) or not lengths.is_cuda or lengths.dtype != torch.int64
-                                    or tuple(lengths.shape) != (n,) or not lengths.is_contiguous()):
-            raise TypeError("lengths must be a contiguous int64 CUDA tensor of shape (n) or None")
-        if not isinstance(keep, torch.Tensor) or not keep.is_cuda or keep.dtype not in (torch.bool, torch.uint8) \
-                or tuple(keep.shape) != (n,) or not keep.is_contiguous():
-            raise TypeError("keep must be a contiguous bool or uint8 CUDA tensor of shape (n)")
-        others = [entries, keep] + ([lengths] if lengths is not None else [])
+        self._tensor(arena, "arena", torch.uint8, (None,))
+        n = self._tensor(entries, "entries", torch.int64, (None, 4)).shape[0]
+        if lengths is not None:
+            self._tensor(lengths, "lengths", torch.int64, (n,))
+        self._tensor(keep, "keep", (torch.bool, torch.uint8), (n,))
         if out_arena is not None:
-            if not isinstance(out_arena, torch.Tensor) or not out_arena.is_cuda or out_arena.dtype != torch.uint8 \
-                    or out_arena.dim() != 1 or not out_arena.is_contiguous():
-                raise TypeError("out_arena must be a contiguous 1-D uint8 CUDA tensor")
-            others.append(out_arena)
-        if any(t.device != arena.device for t in others):
-            raise GlcError(GLC_EINVAL, "arena, entries, lengths, keep and out_arena must be on one device")
+            self._tensor(out_arena, "out_arena", torch.uint8, (None,))
         src_bytes = arena.numel()
         if used_bytes is not None:
             used_bytes = int(used_bytes)
@@ -516,16 +618,13 @@ class _Ctx:
         lengths_out = torch.empty(n, dtype=torch.int64, device=dev) if lengths is not None else None
         new_index = torch.empty(n, dtype=torch.int64, device=dev)
         counts = torch.empty(2, dtype=torch.int64, device=dev)
-        self._enter_torch_stream(dev)
-        try:
+        with _on_torch_stream(self, dev):
             check(lib.glc_store_compact_device(
                 self._h, C.c_void_p(arena.data_ptr()), src_bytes, C.c_void_p(entries.data_ptr()),
                 C.c_void_p(lengths.data_ptr()) if lengths is not None else None, n, C.c_void_p(keep.data_ptr()),
                 C.c_void_p(dst.data_ptr()), dst_bytes, C.c_void_p(entries_out.data_ptr()),
                 C.c_void_p(lengths_out.data_ptr()) if lengths is not None else None, C.c_void_p(new_index.data_ptr()),
                 C.c_void_p(counts.data_ptr()), C.c_void_p(counts.data_ptr() + 8)), self._h)
-        finally:
-            self.set_stream(0)
         return entries_out, lengths_out, new_index, counts[0:1], counts[1:2]
 
     def timer_begin(self) -> None:
@@ -646,21 +745,14 @@ class Encoder(_Ctx):
         decode wants it) together with the GlcCompactInfo.  Runs on torch's current stream; synchronises (the
         sizes come back)."""
         import torch
-        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous():
-            raise TypeError("encode_compact_tensor takes a contiguous float32 CUDA tensor")
-        if x.device.index != self.device:
-            raise GlcError(GLC_EINVAL, f"the tensor is on {x.device}, this context on device {self.device}")
-        n = x.numel()
+        n = self._tensor(x, "x", torch.float32).numel()
         plan = plan_encode(n, channels)
         nf = plan.n_frames
         records = torch.empty(nf * int(lib.glc_record_bytes(channels)), dtype=torch.uint8, device=x.device)
         blob = torch.empty(compact_bound(channels, nf), dtype=torch.uint8, device=x.device)
-        self._enter_torch_stream(x.device)
-        try:
+        with _on_torch_stream(self, x.device):
             self.encode_range_device(x.data_ptr(), 0, plan.per_channel, n, channels, 0, nf, records.data_ptr())
             info = self.compact_device_records(records.data_ptr(), nf, channels, blob.data_ptr(), blob.numel())
-        finally:
-            self.set_stream(0)
         return blob[:info.bytes], info
 
     def encode_compact_batch_tensor(self, x, lengths=None, planar: bool = True, arena=None, cursor=None, bits: Optional[int] = None):
@@ -680,51 +772,23 @@ class Encoder(_Ctx):
         Encoder.encode): glc_encode_batch_device_compact_int widens it in the gather, and the blobs are those of the
         widened clips, byte for byte."""
         import torch
-        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in (torch.float32, torch.int16, torch.int32) or x.dim() != 3:
-            raise TypeError("x must be a float32 (or int16 / int32) CUDA tensor of shape (B, C, T) or (B, T, C)")
-        fmt, bits = _tensor_pcm_format(x, bits)
-        if x.device.index != self.device:
-            raise GlcError(GLC_EINVAL, f"x is on {x.device}, this context on device {self.device}")
-        if x.shape[2] > 1 and x.stride(2) != 1:
-            raise TypeError("x: the innermost stride must be 1")
-        if min(x.stride(0), x.stride(1)) < 0:
-            raise TypeError("x: negative strides")
-        b, ch, n = (x.shape[0], x.shape[1], x.shape[2]) if planar else (x.shape[0], x.shape[2], x.shape[1])
+        fmt, bits = self._pcm_tensor(x, bits)
+        lay, b, ch, n = _clip_layout(x, planar, "x")
         if not 0 < ch <= 0xFFFF:
             raise GlcError(GLC_EINVAL, f"x: {ch} channels")
-        if not planar and b and n > 1 and x.stride(1) != ch:
-            raise TypeError(f"x: an interleaved clip must be dense (stride {ch} between samples)")
-        lay = GlcClipLayout(b, ch, 1 if planar else 0, x.stride(0), x.stride(1) if planar else 0, n, None)
         if lengths is not None:
-            lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-            if len(lens) != b or any(v < 0 or v > n for v in lens):
-                raise GlcError(GLC_EINVAL, f"lengths must hold {b} values in [0, {n}]")
-            arr = (C.c_uint64 * max(b, 1))(*lens)
-            lay.lengths = C.cast(arr, C.POINTER(C.c_uint64))
+            _set_lengths(lay, lengths, b, n)
         if arena is None:
             arena = torch.empty(max(int(lib.glc_compact_store_bound(C.byref(lay))), 64), dtype=torch.uint8, device=x.device)
         if cursor is None:
             cursor = torch.zeros(1, dtype=torch.int64, device=x.device)
-        if not isinstance(arena, torch.Tensor) or not arena.is_cuda or arena.dtype != torch.uint8 or arena.dim() != 1 \
-                or not arena.is_contiguous():
-            raise TypeError("arena must be a contiguous 1-D uint8 CUDA tensor")
-        if not isinstance(cursor, torch.Tensor) or not cursor.is_cuda or cursor.dtype != torch.int64 or cursor.numel() != 1:
-            raise TypeError("cursor must be a one-element int64 CUDA tensor")
-        if arena.device != x.device or cursor.device != x.device:
-            raise GlcError(GLC_EINVAL, "x, arena and cursor must be on one device")
+        self._append_tensors(arena, cursor)
         entries = torch.zeros((b, 4), dtype=torch.int64, device=x.device)
-        self._enter_torch_stream(x.device)
-        try:
-            if fmt == GLC_PCM_F32:
-                check(lib.glc_encode_batch_device_compact(self._h, C.c_void_p(x.data_ptr()), C.byref(lay), C.c_void_p(arena.data_ptr()),
-                                                          arena.numel(), C.c_void_p(cursor.data_ptr()),
-                                                          C.c_void_p(entries.data_ptr())), self._h)
-            else:
-                check(lib.glc_encode_batch_device_compact_int(self._h, C.c_void_p(x.data_ptr()), fmt, bits, C.byref(lay),
-                                                              C.c_void_p(arena.data_ptr()), arena.numel(),
-                                                              C.c_void_p(cursor.data_ptr()), C.c_void_p(entries.data_ptr())), self._h)
-        finally:
-            self.set_stream(0)
+        call, ints = _entry_in("glc_encode_batch_device_compact", fmt, bits)
+        with _on_torch_stream(self, x.device):
+            check(call(
+                self._h, C.c_void_p(x.data_ptr()), *ints, C.byref(lay), C.c_void_p(arena.data_ptr()), arena.numel(),
+                C.c_void_p(cursor.data_ptr()), C.c_void_p(entries.data_ptr())), self._h)
         return arena, cursor, entries
 
     def mdct_forward_device(self, d_pcm: int, t0: int, t_count: int, n_samples: int, channels: int,
@@ -840,15 +904,6 @@ class Decoder(_Ctx):
                                             C.c_void_p(d_out), cap, C.byref(n)), self._h)
         return n.value
 
-    @staticmethod
-    def _blob_tensor(t, what: str, device: int):
-        import torch
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
-            raise TypeError(f"{what} must be a contiguous 1-D uint8 CUDA tensor")
-        if t.device.index != device:
-            raise GlcError(GLC_EINVAL, f"{what} is on {t.device}, this context on device {device}")
-        return t
-
     def decode_device_compact(self, d_blob: int, blob_bytes: int, n_samples: int, channels: int, d_out: int, cap: int) -> int:
         """glc_decode_device_compact on raw device addresses; returns the number of samples written.  Queued on the
         context's stream, not synchronised."""
@@ -865,48 +920,27 @@ class Decoder(_Ctx):
         when given: 1-D contiguous float32, at least n_samples long; its first n_samples elements are returned).
         Queued on torch's current stream as RoundTrip.apply_tensor queues; nothing touches the host."""
         import torch
-        blob = self._blob_tensor(blob, "blob", self.device)
+        self._tensor(blob, "blob", torch.uint8, (None,))
         if out is None:
             out = torch.empty(n_samples, dtype=torch.float32, device=blob.device)
-        elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32 or out.dim() != 1 \
-                or not out.is_contiguous():
-            raise TypeError("out must be a contiguous 1-D float32 CUDA tensor")
-        self._enter_torch_stream(blob.device)
-        try:
+        self._tensor(out, "out", torch.float32, (None,))
+        with _on_torch_stream(self, blob.device):
             n = self.decode_device_compact(blob.data_ptr(), blob.numel(), n_samples, self.channels, out.data_ptr(), out.numel())
-        finally:
-            self.set_stream(0)
         return out[:n]
 
     def _batch_out(self, blobs, lens, planar: bool, out, dtype=None):
-        """The output tensor of a decode_compact_* batch call (None: a new zero-filled one of T = max(lens)), checked,
-        and its glc_clip_layout (with the array the layout points into, to be kept alive)."""
+        """The checked blobs of a decode_compact_* batch call, their addresses and sizes as the C call takes them, the
+        output tensor (None: a new zero-filled one of T = max(lens)) and its glc_clip_layout with `lens` set."""
         import torch
         b, ch = len(blobs), self.channels
-        dtype = _tensor_out_dtype(dtype, out)
-        if out is None:
-            t_max = max(lens, default=0)
-            dev = blobs[0].device if b else torch.device("cuda", self.device)
-            out = torch.zeros((b, ch, t_max) if planar else (b, t_max, ch), dtype=dtype, device=dev)
-        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != dtype or out.dim() != 3:
-            raise TypeError("out must be a float32 (or, dtype=torch.int16, an int16) CUDA tensor of shape (B, C, T) or (B, T, C)")
-        if out.device.index != self.device:
-            raise GlcError(GLC_EINVAL, f"out is on {out.device}, this context on device {self.device}")
-        if out.shape[2] > 1 and out.stride(2) != 1:
-            raise TypeError("out: the innermost stride must be 1")
-        if min(out.stride(0), out.stride(1)) < 0:
-            raise TypeError("out: negative strides")
-        ob, oc, ot = (out.shape[0], out.shape[1], out.shape[2]) if planar else (out.shape[0], out.shape[2], out.shape[1])
+        for i, t in enumerate(blobs):
+            self._tensor(t, f"blobs[{i}]", torch.uint8, (None,))
+        t_max = max(lens, default=0)
+        out, lay, ob, oc, ot = self._out_tensor(out, (b, ch, t_max) if planar else (b, t_max, ch), _tensor_out_dtype(dtype, out), planar)
         if ob != b or oc != ch:
             raise GlcError(GLC_EINVAL, f"out has shape {tuple(out.shape)} for {b} clips of {ch} channels")
-        if not planar and ot > 1 and out.stride(1) != ch:
-            raise TypeError(f"out: an interleaved clip must be dense (stride {ch} between samples)")
-        if any(v < 0 or v > ot for v in lens):
-            raise GlcError(GLC_EINVAL, f"lengths must lie in [0, {ot}]")
-        lens_arr = (C.c_uint64 * max(b, 1))(*lens)
-        lay = GlcClipLayout(b, ch, 1 if planar else 0, out.stride(0), out.stride(1) if planar else 0, ot,
-                            C.cast(lens_arr, C.POINTER(C.c_uint64)))
-        return out, lay, lens_arr
+        _set_lengths(lay, lens, b, ot)
+        return _c_array(C.c_void_p, [t.data_ptr() for t in blobs]), _c_array(C.c_uint64, [t.numel() for t in blobs]), out, lay
 
     def decode_compact_batch_tensor(self, blobs, n_samples, lengths=None, planar: bool = True, out=None, dtype=None):
         """Decode one compact blob per clip into ONE padded batch tensor (glc_decode_batch_device_compact).  blobs: B
@@ -919,24 +953,14 @@ class Decoder(_Ctx):
         dtype=torch.int16 (or an int16 `out`, which selects the format by itself): 16-bit PCM narrowed on the device as
         decode(dtype=np.int16) narrows (glc_decode_batch_device_compact_i16)."""
         b = len(blobs)
-        ch = self.channels
-        ns = [int(v) for v in (n_samples.tolist() if hasattr(n_samples, "tolist") else n_samples)]
-        lens = [v // ch for v in ns] if lengths is None else \
-            [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+        ns = _ints(n_samples)
+        lens = [v // self.channels for v in ns] if lengths is None else _ints(lengths)
         if len(ns) != b or len(lens) != b:
             raise GlcError(GLC_EINVAL, f"n_samples and lengths must hold {b} values")
-        blobs = [self._blob_tensor(t, f"blobs[{i}]", self.device) for i, t in enumerate(blobs)]
-        out, lay, _keep = self._batch_out(blobs, lens, planar, out, dtype)
-        ptrs = (C.c_void_p * max(b, 1))(*[t.data_ptr() for t in blobs])
-        sizes = (C.c_uint64 * max(b, 1))(*[t.numel() for t in blobs])
-        ns_arr = (C.c_uint64 * max(b, 1))(*ns)
-        call = lib.glc_decode_batch_device_compact_i16 if out.dtype.itemsize == 2 else lib.glc_decode_batch_device_compact
-        self._enter_torch_stream(out.device)
-        try:
-            check(call(self._h, ptrs, sizes, ns_arr, C.c_void_p(out.data_ptr()), C.byref(lay)),
-                  self._h)
-        finally:
-            self.set_stream(0)
+        ptrs, sizes, out, lay = self._batch_out(blobs, lens, planar, out, dtype)
+        with _on_torch_stream(self, out.device):
+            check(_entry_out("glc_decode_batch_device_compact", out)(
+                self._h, ptrs, sizes, _c_array(C.c_uint64, ns), C.c_void_p(out.data_ptr()), C.byref(lay)), self._h)
         self._compact_clips = b
         return out
 
@@ -951,26 +975,17 @@ class Decoder(_Ctx):
         one status per crop, bad rows counted inside the window (in the stream's row numbering).
         dtype=torch.int16 (or an int16 `out`): the crops as 16-bit PCM (glc_decode_crops_device_compact_i16)."""
         b = len(blobs)
-        as_ints = lambda v: [int(x) for x in (v.tolist() if hasattr(v, "tolist") else v)]
-        ns, st = as_ints(n_samples), as_ints(starts)
-        lens = [int(lengths)] * b if isinstance(lengths, (int, np.integer)) else as_ints(lengths)
+        ns, st = _ints(n_samples), _ints(starts)
+        lens = [int(lengths)] * b if isinstance(lengths, (int, np.integer)) else _ints(lengths)
         if len(ns) != b or len(st) != b or len(lens) != b:
             raise GlcError(GLC_EINVAL, f"n_samples, starts and lengths must hold {b} values")
         if any(v < 0 for v in st):
             raise GlcError(GLC_EINVAL, "starts must not be negative")
-        blobs = [self._blob_tensor(t, f"blobs[{i}]", self.device) for i, t in enumerate(blobs)]
-        out, lay, _keep = self._batch_out(blobs, lens, planar, out, dtype)
-        ptrs = (C.c_void_p * max(b, 1))(*[t.data_ptr() for t in blobs])
-        sizes = (C.c_uint64 * max(b, 1))(*[t.numel() for t in blobs])
-        ns_arr = (C.c_uint64 * max(b, 1))(*ns)
-        call = lib.glc_decode_crops_device_compact_i16 if out.dtype.itemsize == 2 else lib.glc_decode_crops_device_compact
-        crops = (GlcCrop * max(b, 1))(*[GlcCrop(a, n) for a, n in zip(st, lens)])
-        self._enter_torch_stream(out.device)
-        try:
-            check(call(self._h, ptrs, sizes, ns_arr, crops, C.c_void_p(out.data_ptr()), C.byref(lay)),
-                  self._h)
-        finally:
-            self.set_stream(0)
+        ptrs, sizes, out, lay = self._batch_out(blobs, lens, planar, out, dtype)
+        crops = _c_array(GlcCrop, [GlcCrop(a, n) for a, n in zip(st, lens)])
+        with _on_torch_stream(self, out.device):
+            check(_entry_out("glc_decode_crops_device_compact", out)(
+                self._h, ptrs, sizes, _c_array(C.c_uint64, ns), crops, C.c_void_p(out.data_ptr()), C.byref(lay)), self._h)
         self._compact_clips = b
         return out
 
@@ -991,63 +1006,30 @@ class Decoder(_Ctx):
         import torch
         ch = self.channels
         dtype = _tensor_out_dtype(dtype, out)
-
-        def index(t, name, shape_tail=()):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int64 or not t.is_contiguous() \
-                    or tuple(t.shape[1:]) != shape_tail:
-                raise TypeError(f"{name} must be a contiguous int64 CUDA tensor of shape (n{''.join(', %d' % v for v in shape_tail)})")
-            if t.device.index != self.device:
-                raise GlcError(GLC_EINVAL, f"{name} is on {t.device}, this context on device {self.device}")
-            return t
-
-        if not isinstance(arena, torch.Tensor) or not arena.is_cuda or arena.dtype != torch.uint8 or arena.dim() != 1 \
-                or not arena.is_contiguous():
-            raise TypeError("arena must be a contiguous 1-D uint8 CUDA tensor")
-        if arena.device.index != self.device:
-            raise GlcError(GLC_EINVAL, f"arena is on {arena.device}, this context on device {self.device}")
-        entries, lengths = index(entries, "entries", (4,)), index(lengths, "lengths")
-        clips, starts = index(clips, "clips"), index(starts, "starts")
+        self._tensor(arena, "arena", torch.uint8, (None,))
+        self._tensor(entries, "entries", torch.int64, (None, 4))
+        for t, name in ((lengths, "lengths"), (clips, "clips"), (starts, "starts")):
+            self._tensor(t, name, torch.int64, (None,))
         if lengths.shape[0] != entries.shape[0] or starts.shape[0] != clips.shape[0]:
             raise GlcError(GLC_EINVAL, "one length per entry and one start per clip index")
         b, length, max_length = clips.shape[0], int(length), int(max_length)
         if length < 0 or max_length < 0:
             raise GlcError(GLC_EINVAL, "length and max_length must not be negative")
-        if out is None:
-            out = torch.zeros((b, ch, length) if planar else (b, length, ch), dtype=dtype, device=arena.device)
-        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != dtype or out.dim() != 3:
-            raise TypeError("out must be a float32 (or, dtype=torch.int16, an int16) CUDA tensor of shape (B, C, T) or (B, T, C)")
-        if out.device.index != self.device:
-            raise GlcError(GLC_EINVAL, f"out is on {out.device}, this context on device {self.device}")
-        if out.shape[2] > 1 and out.stride(2) != 1:
-            raise TypeError("out: the innermost stride must be 1")
-        if min(out.stride(0), out.stride(1)) < 0:
-            raise TypeError("out: negative strides")
-        ob, oc, ot = (out.shape[0], out.shape[1], out.shape[2]) if planar else (out.shape[0], out.shape[2], out.shape[1])
+        out, lay, ob, oc, ot = self._out_tensor(out, (b, ch, length) if planar else (b, length, ch), dtype, planar)
         if ob != b or oc != ch or ot != length:
             raise GlcError(GLC_EINVAL, f"out has shape {tuple(out.shape)} for {b} crops of {ch} channels and {length} samples")
-        if not planar and ot > 1 and out.stride(1) != ch:
-            raise TypeError(f"out: an interleaved clip must be dense (stride {ch} between samples)")
-        lay = GlcClipLayout(b, ch, 1 if planar else 0, out.stride(0), out.stride(1) if planar else 0, length, None)
-        call = lib.glc_decode_crops_device_store_i16 if dtype == torch.int16 else lib.glc_decode_crops_device_store
-        self._enter_torch_stream(out.device)
-        try:
-            check(call(self._h, C.c_void_p(arena.data_ptr()), arena.numel(),
-                       C.c_void_p(entries.data_ptr()), C.c_void_p(lengths.data_ptr()), entries.shape[0],
-                       max_length, C.c_void_p(clips.data_ptr()), C.c_void_p(starts.data_ptr()), length,
-                       C.c_void_p(out.data_ptr()), C.byref(lay)), self._h)
-        finally:
-            self.set_stream(0)
+        with _on_torch_stream(self, out.device):
+            check(_entry_out("glc_decode_crops_device_store", out)(
+                self._h, C.c_void_p(arena.data_ptr()), arena.numel(), C.c_void_p(entries.data_ptr()),
+                C.c_void_p(lengths.data_ptr()), entries.shape[0], max_length, C.c_void_p(clips.data_ptr()),
+                C.c_void_p(starts.data_ptr()), length, C.c_void_p(out.data_ptr()), C.byref(lay)), self._h)
         self._compact_clips = b
         return out
 
     def last_compact_status(self):
         """glc_decode_compact_last_status: per blob of the last decode_compact_* call a CompactStatus (flags 0 and
         no bad rows for a blob that passed every check).  Synchronises."""
-        n = getattr(self, "_compact_clips", 0)
-        arr = (GlcCompactStatus * max(n, 1))()
-        if n:
-            check(lib.glc_decode_compact_last_status(self._h, arr, n), self._h)
-        return [CompactStatus(int(a.flags), int(a.n_bad_rows), int(a.first_bad_row)) for a in arr[:n]]
+        return self._compact_status(getattr(self, "_compact_clips", 0))
 
     def imdct_device(self, encoded: EncodedAudio, frame_begin: int, frame_end: int, d_blocks: int) -> None:
         """Dequant + imdct_block + window (src/codec.rs:651-675) alone for a frame range:
@@ -1134,21 +1116,15 @@ class RoundTrip(_Ctx):
         restored before the call returns, which waits for the queued work (glc_ctx_set_stream).  Raises
         GlcError where set_stream does (two HIP runtimes mapped)."""
         import torch
-        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous():
-            raise TypeError("apply_tensor takes a contiguous float32 CUDA tensor")
-        if x.device.index != self.device:
-            raise GlcError(GLC_EINVAL, f"the tensor is on {x.device}, this context on device {self.device}")
+        self._tensor(x, "x", torch.float32)
         if x.dim() == 2:
             if x.shape[1] != channels:
                 raise GlcError(GLC_EINVAL, f"a 2-D tensor is (frames, channels): got {tuple(x.shape)} for {channels} channels")
         elif x.dim() != 1:
             raise GlcError(GLC_EINVAL, "the tensor is interleaved 1-D or of shape (frames, channels)")
         out = torch.empty_like(x)
-        self.set_stream(torch.cuda.current_stream(x.device).cuda_stream)
-        try:
+        with _on_torch_stream(self, x.device):
             n = self.apply_device(x.data_ptr(), x.numel(), channels, out.data_ptr(), out.numel())
-        finally:
-            self.set_stream(0)
         assert n == x.numel()
         return out
 
@@ -1169,55 +1145,28 @@ class RoundTrip(_Ctx):
         (glc_roundtrip_batch_device_pcm).  In place needs the same format on both sides."""
         import torch
         out_planar = planar if out_planar is None else bool(out_planar)
-        fmt, bits = _tensor_pcm_format(x, bits)
+        fmt, bits = self._pcm_tensor(x, bits)
         out_dtype = _tensor_out_dtype(out_dtype, out)
-
-        def layout(t, is_planar, what):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != (out_dtype if what == "out" else x.dtype):
-                raise TypeError(f"{what} must be a {'float32 or int16' if what == 'out' else 'float32, int16 or int32'} CUDA tensor")
-            if t.dim() != 3:
-                raise TypeError(f"{what} must have shape (B, C, T) or (B, T, C)")
-            if t.shape[2] > 1 and t.stride(2) != 1:
-                raise TypeError(f"{what}: the innermost stride must be 1")
-            if t.device.index != self.device:
-                raise GlcError(GLC_EINVAL, f"{what} is on {t.device}, this context on device {self.device}")
-            b, c, n = (t.shape[0], t.shape[1], t.shape[2]) if is_planar else (t.shape[0], t.shape[2], t.shape[1])
-            if not 0 < c <= 0xFFFF:
-                raise GlcError(GLC_EINVAL, f"{what}: {c} channels")
-            if min(t.stride(0), t.stride(1)) < 0:
-                raise TypeError(f"{what}: negative strides")
-            lay = GlcClipLayout(b, c, 1 if is_planar else 0, t.stride(0), t.stride(1) if is_planar else 0, n, None)
-            if not is_planar and b and n > 1 and t.stride(1) != c:
-                raise TypeError(f"{what}: an interleaved clip must be dense (stride {c} between samples)")
-            return lay, n
-
-        lin, n = layout(x, planar, "x")
-        b = x.shape[0]
+        lin, b, ch, n = _clip_layout(x, planar, "x")
+        if not 0 < ch <= 0xFFFF:
+            raise GlcError(GLC_EINVAL, f"x: {ch} channels")
         if lengths is not None:
-            lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-            if len(lens) != b or any(v < 0 or v > n for v in lens):
-                raise GlcError(GLC_EINVAL, f"lengths must hold {b} values in [0, {n}]")
-            arr = (C.c_uint64 * max(b, 1))(*lens)
-            lin.lengths = C.cast(arr, C.POINTER(C.c_uint64))
-        if out is None:
+            _set_lengths(lin, lengths, b, n)
+        if out is None:   # like x: its strides where it is dense, and no shape to build
             out = torch.zeros_like(x, dtype=out_dtype) if planar == out_planar else \
                 torch.zeros_like(x.transpose(1, 2), dtype=out_dtype, memory_format=torch.contiguous_format)
         want = tuple(x.shape) if planar == out_planar else (x.shape[0], x.shape[2], x.shape[1])
-        lout, _ = layout(out, out_planar, "out")
+        out, lout = self._out_tensor(out, want, out_dtype, out_planar)[:2]
         if tuple(out.shape) != want:
             raise GlcError(GLC_EINVAL, f"out has shape {tuple(out.shape)}, expected {want}")
-        lout.lengths = lin.lengths
-        self.set_stream(torch.cuda.current_stream(x.device).cuda_stream)
-        try:
-            if fmt == GLC_PCM_F32 and out_dtype == torch.float32:
+        lout.lengths, lout.lengths_array = lin.lengths, getattr(lin, "lengths_array", None)   # one array, held by both
+        with _on_torch_stream(self, x.device):
+            if fmt == GLC_PCM_F32 and _out_format(out) == GLC_PCM_F32:
                 check(lib.glc_roundtrip_batch_device(self._h, C.c_void_p(x.data_ptr()), C.byref(lin), C.c_void_p(out.data_ptr()),
                                                      C.byref(lout)), self._h)
-            else:
+            else:   # the one entry point that takes both formats as arguments
                 check(lib.glc_roundtrip_batch_device_pcm(self._h, C.c_void_p(x.data_ptr()), fmt, bits, C.byref(lin),
-                                                         C.c_void_p(out.data_ptr()),
-                                                         GLC_PCM_S16 if out_dtype == torch.int16 else GLC_PCM_F32, C.byref(lout)), self._h)
-        finally:
-            self.set_stream(0)
+                                                         C.c_void_p(out.data_ptr()), _out_format(out), C.byref(lout)), self._h)
         self._batch_clips = b
         return out
 
@@ -1347,43 +1296,20 @@ class StreamEncoder(_Ctx):
         them.  Returns (entries, segs): an (n_segs, 4) int64 CUDA tensor of glc_store_entry words and the host list
         [(lane, first_frame, n_frames)] in the same order.  Nothing is copied to the host."""
         import torch
-        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 3:
-            raise TypeError("x must be a float32 (or int16 / int32) CUDA tensor of shape (B, C, T) or (B, T, C)")
-        fmt, bits = _tensor_pcm_format(x, bits)
-        if x.device.index != self.device:
-            raise GlcError(GLC_EINVAL, f"x is on {x.device}, this context on device {self.device}")
-        if x.shape[2] > 1 and x.stride(2) != 1:
-            raise TypeError("x: the innermost stride must be 1")
-        if min(x.stride(0), x.stride(1)) < 0:
-            raise TypeError("x: negative strides")
-        b, ch, n = (x.shape[0], x.shape[1], x.shape[2]) if planar else (x.shape[0], x.shape[2], x.shape[1])
+        fmt, bits = self._pcm_tensor(x, bits)
+        lay, b, ch, n = _clip_layout(x, planar, "x")
         if b != self.n_streams or ch != self.channels:
             raise GlcError(GLC_EINVAL, f"x must hold {self.n_streams} lanes of {self.channels} channels")
-        if not planar and n > 1 and x.stride(1) != ch:
-            raise TypeError(f"x: an interleaved chunk must be dense (stride {ch} between samples)")
-        lens = [n] * b if lengths is None else [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-        if len(lens) != b or any(v < 0 or v > n for v in lens):
-            raise GlcError(GLC_EINVAL, f"lengths must hold {b} values in [0, {n}]")
-        arr = (C.c_uint64 * b)(*lens)
-        lay = GlcClipLayout(b, ch, 1 if planar else 0, x.stride(0), x.stride(1) if planar else 0, n, C.cast(arr, C.POINTER(C.c_uint64)))
-        if not isinstance(arena, torch.Tensor) or not arena.is_cuda or arena.dtype != torch.uint8 or arena.dim() != 1 \
-                or not arena.is_contiguous():
-            raise TypeError("arena must be a contiguous 1-D uint8 CUDA tensor")
-        if not isinstance(cursor, torch.Tensor) or not cursor.is_cuda or cursor.dtype != torch.int64 or cursor.numel() != 1:
-            raise TypeError("cursor must be a one-element int64 CUDA tensor")
-        if arena.device != x.device or cursor.device != x.device:
-            raise GlcError(GLC_EINVAL, "x, arena and cursor must be on one device")
+        _set_lengths(lay, [n] * b if lengths is None else lengths, b, n)
+        self._append_tensors(arena, cursor)
         flags, fp = self._finish_flags(finish)
         entries = torch.zeros((b, 4), dtype=torch.int64, device=x.device)
         segs = (GlcStreamSeg * b)()
         n_segs = C.c_uint64()
-        self._enter_torch_stream(x.device)
-        try:
+        with _on_torch_stream(self, x.device):
             check(lib.glc_stream_enc_push_device(self._s, C.c_void_p(x.data_ptr()), fmt, bits, C.byref(lay), fp,
                                                  C.c_void_p(arena.data_ptr()), arena.numel(), C.c_void_p(cursor.data_ptr()),
                                                  C.c_void_p(entries.data_ptr()), segs, C.byref(n_segs)), self._h)
-        finally:
-            self.set_stream(0)
         return entries[:n_segs.value], [(g.stream, g.first_frame, g.n_frames) for g in segs[:n_segs.value]]
 
 
@@ -1489,16 +1415,11 @@ class StreamDecoder(_Ctx):
         spans - and per lane the samples per channel the push emitted.  Nothing is copied to the host."""
         import torch
         b, ch = self.n_streams, self.channels
-        if not isinstance(arena, torch.Tensor) or not arena.is_cuda or arena.dtype != torch.uint8 or arena.dim() != 1 \
-                or not arena.is_contiguous():
-            raise TypeError("arena must be a contiguous 1-D uint8 CUDA tensor")
+        self._tensor(arena, "arena", torch.uint8, (None,))
         segs = [(int(a), int(f0), int(nf)) for (a, f0, nf) in segs]
         n = len(segs)
-        if n and (not isinstance(entries, torch.Tensor) or not entries.is_cuda or entries.dtype != torch.int64
-                  or entries.dim() != 2 or entries.shape != (n, 4) or not entries.is_contiguous()):
-            raise TypeError("entries must be a contiguous (n_segs, 4) int64 CUDA tensor")
-        if arena.device.index != self.device or (n and entries.device != arena.device):
-            raise GlcError(GLC_EINVAL, "arena and entries must be on this context's device")
+        if n:
+            self._tensor(entries, "entries", torch.int64, (n, 4))
         fin, tot = self._lane_args(finish, total_len)
         frames = [0] * b
         for (a, _, nf) in segs:
@@ -1507,37 +1428,26 @@ class StreamDecoder(_Ctx):
             frames[a] += nf
         lens = [p.n_samples if p else 0 for p in self._plans(frames, fin, tot)]
         t = max(max(lens), 1)
-        tdt = _tensor_out_dtype(dtype, out)
         shape = (b, ch, t) if planar else (b, t, ch)
-        if out is None:
-            out = torch.zeros(shape, dtype=tdt, device=arena.device)
-        elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != arena.device or out.dim() != 3 \
-                or out.shape[0] != b or (out.shape[1] if planar else out.shape[2]) != ch \
-                or (out.shape[2] if planar else out.shape[1]) < max(lens) or not out.is_contiguous():
+        out, lay, ob, oc, ot = self._out_tensor(out, shape, _tensor_out_dtype(dtype, out), planar, contiguous=True)
+        if ob != b or oc != ch or ot < max(lens):
             raise TypeError(f"out must be a contiguous CUDA tensor of shape {shape} or longer in time")
-        arr = (C.c_uint64 * b)(*lens)
-        lay = GlcClipLayout(b, ch, 1 if planar else 0, out.stride(0), out.stride(1) if planar else 0, 0, C.cast(arr, C.POINTER(C.c_uint64)))
-        c_segs = (GlcStreamSeg * max(n, 1))(*[GlcStreamSeg(a, f0, nf) for (a, f0, nf) in segs])
+        _set_lengths(lay, lens, b, ot)
+        lay.length = 0   # a push has no common length: every lane's span is in `lengths`
+        c_segs = _c_array(GlcStreamSeg, [GlcStreamSeg(a, f0, nf) for (a, f0, nf) in segs])
         flags = (C.c_uint8 * b)(*[1 if v else 0 for v in fin])
         totals = (C.c_uint64 * b)(*tot)
-        self._enter_torch_stream(arena.device)
-        try:
+        with _on_torch_stream(self, arena.device):
             check(lib.glc_stream_dec_push_device(self._s, C.c_void_p(arena.data_ptr()), arena.numel(),
                                                  C.c_void_p(entries.data_ptr()) if n else None, c_segs, n,
                                                  C.cast(flags, C.c_void_p), totals, C.c_void_p(out.data_ptr()),
-                                                 GLC_PCM_S16 if out.dtype == torch.int16 else GLC_PCM_F32, C.byref(lay)), self._h)
-        finally:
-            self.set_stream(0)
+                                                 _out_format(out), C.byref(lay)), self._h)
         self._n_segs = n
         return out, lens
 
     def last_compact_status(self):
         """glc_decode_compact_last_status: one CompactStatus per SEGMENT of the last push.  Synchronises."""
-        n = self._n_segs
-        arr = (GlcCompactStatus * max(n, 1))()
-        if n:
-            check(lib.glc_decode_compact_last_status(self._h, arr, n), self._h)
-        return [CompactStatus(int(a.flags), int(a.n_bad_rows), int(a.first_bad_row)) for a in arr[:n]]
+        return self._compact_status(self._n_segs)
 
 
 def save_encoded(encoded: EncodedAudio, path) -> None:
