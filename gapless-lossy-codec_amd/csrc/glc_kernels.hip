@@ -29,6 +29,20 @@ namespace glc {
 
 namespace {
 
+// What the K1 and D2 launchers share: the instantiation by channel count, f(CH) with CH = ch for 1 / 2 / 4 / 8 -
+// the counts with a segment loader in K1 and a whole-chunk form in D2 - and CH = FALLBACK otherwise: 0, the form
+// for any count, or 8 where the caller has already refused every other count.
+template <int FALLBACK = 0, typename F>
+auto by_channels(uint32_t ch, F &&f) {
+  switch (ch) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: return f(std::integral_constant<int, FALLBACK>{});
+  }
+}
+
 constexpr int kHopI = 1024;
 constexpr int kFrameI = 2048;
 
@@ -2440,23 +2454,15 @@ hipError_t launch_st_ch(const DeviceTables &t, const PcmView &pcm, uint64_t fram
   // dword per (row, sample).  PRIO: 8 waves - by quarter of the i loop (between a CU's two workgroups);
   // 16 waves - by distance from the last barrier (inside the workgroup).
   constexpr int P = NW == 8 ? 1 : 2;
-  switch (pcm.ch) {
-    case 1: return k1::launch_st<4, 1, P, 4, NW>(t, pcm, frame_begin, M, coef, s);
-    case 2: return k1::launch_st<4, 2, P, 4, NW>(t, pcm, frame_begin, M, coef, s);
-    case 4: return k1::launch_st<4, 4, P, 4, NW>(t, pcm, frame_begin, M, coef, s);
-    case 8: return k1::launch_st<4, 8, P, 4, NW>(t, pcm, frame_begin, M, coef, s);
-    default: return k1::launch_st<4, 0, P, 4, NW>(t, pcm, frame_begin, M, coef, s);
-  }
+  return by_channels(pcm.ch, [&](auto CH) {
+    return k1::launch_st<4, decltype(CH)::value, P, 4, NW>(t, pcm, frame_begin, M, coef, s);
+  });
 }
 hipError_t launch_dma_ch(const DeviceTables &t, const PcmView &pcm, uint64_t frame_begin, uint32_t M, float *coef,
                          hipStream_t s) {
-  switch (pcm.ch) {
-    case 1: return k1::launch_dma<4, 1, 1>(t, pcm, frame_begin, M, coef, s);
-    case 2: return k1::launch_dma<4, 2, 1>(t, pcm, frame_begin, M, coef, s);
-    case 4: return k1::launch_dma<4, 4, 1>(t, pcm, frame_begin, M, coef, s);
-    case 8: return k1::launch_dma<4, 8, 1>(t, pcm, frame_begin, M, coef, s);
-    default: return k1::launch_dma<4, 0, 1>(t, pcm, frame_begin, M, coef, s);
-  }
+  return by_channels(pcm.ch, [&](auto CH) {
+    return k1::launch_dma<4, decltype(CH)::value, 1>(t, pcm, frame_begin, M, coef, s);
+  });
 }
 }  // namespace
 
@@ -2570,19 +2576,14 @@ hipError_t launch_encode_screened(const DeviceTables &t, const ScreenShape &sh, 
   const unsigned n_planes = matrix_bound ? static_cast<unsigned>(MatrixBound::kGroups) : sh.n_planes;
   hipError_t e;
   if (edge && (e = hipEventRecord(edge->ev_fork, s)) != hipSuccess) return e;
-  if (matrix_bound) switch (pcm.ch) {
-    case 1: e = k1::launch_mx_st<1>(t, pcm, frame_begin, M, coef, hf, stride, s); break;
-    case 2: e = k1::launch_mx_st<2>(t, pcm, frame_begin, M, coef, hf, stride, s); break;
-    case 4: e = k1::launch_mx_st<4>(t, pcm, frame_begin, M, coef, hf, stride, s); break;
-    default: e = k1::launch_mx_st<8>(t, pcm, frame_begin, M, coef, hf, stride, s); break;
-  }
-  else switch (pcm.ch) {
-    case 1: e = k1::launch_mix_st<1>(t, pcm, frame_begin, M, coef, sh.ne, sh.hp, hf, stride, s); break;
-    case 2: e = k1::launch_mix_st<2>(t, pcm, frame_begin, M, coef, sh.ne, sh.hp, hf, stride, s); break;
-    case 4: e = k1::launch_mix_st<4>(t, pcm, frame_begin, M, coef, sh.ne, sh.hp, hf, stride, s); break;
-    case 8: e = k1::launch_mix_st<8>(t, pcm, frame_begin, M, coef, sh.ne, sh.hp, hf, stride, s); break;
-    default: e = k1::launch_mix_st<0>(t, pcm, frame_begin, M, coef, sh.ne, sh.hp, hf, stride, s); break;
-  }
+  if (matrix_bound)  // (encode_matrix_bound_built has refused every count but 1 / 2 / 4 / 8: no form for any count is built)
+    e = by_channels<8>(pcm.ch, [&](auto CH) {
+      return k1::launch_mx_st<decltype(CH)::value>(t, pcm, frame_begin, M, coef, hf, stride, s);
+    });
+  else
+    e = by_channels(pcm.ch, [&](auto CH) {
+      return k1::launch_mix_st<decltype(CH)::value>(t, pcm, frame_begin, M, coef, sh.ne, sh.hp, hf, stride, s);
+    });
   if (e != hipSuccess) return e;
   const ScreenArgs sa{hf, row_flag, wave_fail, host_stat, stride, sh.c0, sh.l0, n_planes, seq, edge_a, edge_b,
                       edge ? edge->failed_total : nullptr};
@@ -3021,17 +3022,7 @@ template <typename F>
 void d2_slabs(uint64_t n, F &&launch) {
   for (uint64_t r0 = 0; r0 < n; r0 += 32768) launch(r0, static_cast<unsigned>(std::min<uint64_t>(n - r0, 32768)));
 }
-// ... and the instantiation by channel count: launch(CH) with CH = ch for 1 / 2 / 4 / 8, else 0 (any count)
-template <typename F>
-void d2_by_channels(uint32_t ch, F &&launch) {
-  switch (ch) {
-    case 1: launch(std::integral_constant<int, 1>{}); break;
-    case 2: launch(std::integral_constant<int, 2>{}); break;
-    case 4: launch(std::integral_constant<int, 4>{}); break;
-    case 8: launch(std::integral_constant<int, 8>{}); break;
-    default: launch(std::integral_constant<int, 0>{}); break;
-  }
-}
+// (... and by_channels, at the top of the file, for the instantiation by channel count)
 inline unsigned d2_blocks_x(uint32_t ch) { return (1024u * ch / 4u + 255u) / 256u; }  // 4-sample chunks of a hop over 256 threads
 
 template <typename T>
@@ -3048,7 +3039,7 @@ hipError_t overlap_add_typed(const float *blocks, int64_t blk_frame0, uint64_t n
       hipLaunchKernelGGL((k_overlap_add<0, false, T>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o);
       return;
     }
-    d2_by_channels(ch, [&](auto CH) {
+    by_channels(ch, [&](auto CH) {
       hipLaunchKernelGGL((k_overlap_add<decltype(CH)::value, true, T>), grid, dim3(256), 0, s, blocks, f0, nf, ch, hb, o);
     });
   });
@@ -3158,7 +3149,7 @@ hipError_t overlap_add_strided_typed(const float *blocks, const D *desc, uint32_
     }
     // (a span that starts off a chunk boundary has one chunk more: the kernel's stride loop takes it)
     const dim3 grid(d2_blocks_x(ch), nd);
-    d2_by_channels(ch, [&](auto CH) {
+    by_channels(ch, [&](auto CH) {
       hipLaunchKernelGGL((k_overlap_add_strided<decltype(CH)::value, T, D>), grid, dim3(256), 0, s, blocks, d, ch, out);
     });
   });

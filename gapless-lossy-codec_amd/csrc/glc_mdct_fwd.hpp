@@ -47,6 +47,9 @@
 //                      (round 2 used <32,64,32,4,4,4,2> for <= 512 rows); kept as the plainest statement
 //                      of the loop and for tools/k1_tune.hip.
 //   mac2rows           the 2-row x 8-column multiply/add block; also the entry step of D1 (k_imdct_chan).
+// How every body reads its PCM tile - descriptor, row origin, loaders, tile map - is stated once, ahead of the
+// kernels ("The PCM tile loader"); DESIGN section 4 has a subsection of that name: what each helper owns, which kernel
+// uses which form, and what is deliberately not shared.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -62,6 +65,155 @@ constexpr int kFrameI = 2048;
 
 __device__ __forceinline__ float mul_rn(float a, float b) { return __fmul_rn(a, b); }
 __device__ __forceinline__ float add_rn(float a, float b) { return __fadd_rn(a, b); }
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// ------------------------------------------------------------------------------------------
+// The PCM tile loader: how every kernel of this file turns a PcmView into its A operand, stated once (DESIGN
+// section 4, "The PCM tile loader", says which kernel uses which form).  `ch` is passed in the type the caller
+// divides by - pcm.ch, or the kernel's compile-time channel count - so that a helper costs what its copy did.
+// ------------------------------------------------------------------------------------------
+// element, from pcm.p, of (frame of `row`, i = 0, channel 0): a frame's 2048 samples start half a hop before it
+template <typename Row, typename Ch>
+__device__ __forceinline__ long long pcm_frame_first(const PcmView &pcm, long long frame_begin, Row row, Ch ch) {
+  const long long f = frame_begin + row / ch;
+  return (f * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * ch;
+}
+// one past the last element present, from pcm.p: the shard's end or the stream's
+template <typename Ch>
+__device__ __forceinline__ long long pcm_end(const PcmView &pcm, Ch ch) {
+  long long e_end = static_cast<long long>(pcm.t_count) * ch;  // shard end (elements)
+  const long long n_rel = static_cast<long long>(pcm.n_samples) - static_cast<long long>(pcm.t0) * ch;
+  if (e_end > n_rel) e_end = n_rel;  // stream end
+  return e_end;
+}
+// e_cnt elements from element e_base >= 0 as a raw buffer (2^28 elements is the most a byte offset reaches)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t pcm_rsrc(const PcmView &pcm, long long e_base, long long e_cnt) {
+  if (e_cnt < 0) e_cnt = 0;
+  if (e_cnt > (1ll << 28)) e_cnt = 1ll << 28;
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(pcm.p + e_base), 0, static_cast<int>(e_cnt * 4), 0x00020000);
+}
+
+// The interleaved PCM of a row tile is read through ONE buffer descriptor whose hardware range check supplies the
+// encoder's zero padding (512 leading zeros, tail, shard edges).  Its base is the tile's first element, or pcm.p
+// where that lies before the stream; its records end with the shard or the stream.  An element before the base
+// wraps to a huge unsigned byte offset, one past the end is >= the record count: both load 0.0, so every load is
+// unconditional - and so is a row >= M, which loads from kPcmNoRow.  All inputs are blockIdx / kernarg scalars.
+struct PcmTile {
+  __amdgpu_buffer_rsrc_t rsrc;
+  long long e_base;  // the base, in elements from pcm.p
+};
+constexpr unsigned kPcmNoRow = 0x80000000u;  // byte offset beyond every descriptor: what a row >= M loads from
+template <typename Ch>
+__device__ __forceinline__ PcmTile pcm_tile(const PcmView &pcm, long long frame_begin, int m0, Ch ch) {
+  const long long e_first = pcm_frame_first(pcm, frame_begin, m0, ch);  // first frame of the tile
+  const long long e_end = pcm_end(pcm, ch);
+  const long long e_base = e_first < 0 ? 0 : e_first;
+  return PcmTile{pcm_rsrc(pcm, e_base, e_end - e_base), e_base};
+}
+// off = byte offset from the tile's base of (row, i = a_i), where row < M (else it stays what it was: kPcmNoRow):
+// the per-row loaders, any channel count.  (The segment form is one statement on pcm_frame_first: see SegLoader.)
+template <typename Ch>
+__device__ __forceinline__ void pcm_row_origin(unsigned &off, const PcmView &pcm, const PcmTile &t, long long frame_begin,
+                                               unsigned row, unsigned M, Ch ch, int a_i) {
+  if (row < M) {
+    const long long c = row % ch;
+    const long long e_row = pcm_frame_first(pcm, frame_begin, row, ch) + c;
+    off = static_cast<unsigned>((e_row - t.e_base + a_i * static_cast<long long>(ch)) * 4);  // may wrap: that IS the padding
+  }
+}
+
+// Workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8 says which blocks share an L2).  Give XCD x the
+// contiguous tile range [x T / 8, (x + 1) T / 8) in (m_tile, n_tile) order: the PCM rows of an m-tile are then
+// fetched by ONE XCD instead of all eight, and the table rows of a stage are shared in that XCD's L2 by all
+// resident m-tiles, which sweep i together (measured: 4x less L2 fill traffic).  Speed only, never results.
+// ANY: the grid need not divide by 8 (the map is then the identity); the other launchers' grids always do.
+template <bool ANY = false>
+__device__ __forceinline__ unsigned xcd_tile() {
+  if (ANY && gridDim.x % 8u) return blockIdx.x;
+  return (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+}
+
+// The per-row loaders: N dwords of one row, `step` bytes apart from byte offset `off`.
+// Builtin form (k_mdct_fwd, k_mdct_fwd_sched, small_body): hipcc places the loads and counts them.
+template <int N>
+__device__ __forceinline__ void pcm_load_rows(float (&x)[N], __amdgpu_buffer_rsrc_t rsrc, unsigned off, unsigned step) {
+#pragma unroll
+  for (int j = 0; j < N; ++j)
+    x[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, off + j * step, 0, 0));
+}
+// Asm form (k_mdct_fwd_dma, st_body): hipcc must not count these loads or move their first use (see lds_fetch4);
+// pcm_wait_rows retires them, and everything else the wave has in flight, and ties every register of x
+template <int N, int R>
+__device__ __forceinline__ void pcm_issue_rows(float (&x)[R], __amdgpu_buffer_rsrc_t rsrc, unsigned o, unsigned a_step) {
+  static_assert((N == 4 || N == 8) && N <= R, "per-row loader shapes");
+  asm volatile(
+      "buffer_load_dword %0, %4, %8, 0 offen\n\t"
+      "buffer_load_dword %1, %5, %8, 0 offen\n\t"
+      "buffer_load_dword %2, %6, %8, 0 offen\n\t"
+      "buffer_load_dword %3, %7, %8, 0 offen"
+      : "=&v"(x[0]), "=&v"(x[1]), "=&v"(x[2]), "=&v"(x[3])
+      : "v"(o), "v"(o + a_step), "v"(o + 2 * a_step), "v"(o + 3 * a_step), "s"(rsrc)
+      : "memory");
+  if constexpr (N == 8)
+    asm volatile(
+        "buffer_load_dword %0, %4, %8, 0 offen\n\t"
+        "buffer_load_dword %1, %5, %8, 0 offen\n\t"
+        "buffer_load_dword %2, %6, %8, 0 offen\n\t"
+        "buffer_load_dword %3, %7, %8, 0 offen"
+        : "=&v"(x[4]), "=&v"(x[5]), "=&v"(x[6]), "=&v"(x[7])
+        : "v"(o + 4 * a_step), "v"(o + 5 * a_step), "v"(o + 6 * a_step), "v"(o + 7 * a_step), "s"(rsrc)
+        : "memory");
+}
+__device__ __forceinline__ void pcm_wait_rows(float (&x)[4]) {
+  asm volatile("s_waitcnt vmcnt(0)" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3])::"memory");
+}
+__device__ __forceinline__ void pcm_wait_rows(float (&x)[8]) {
+  asm volatile("s_waitcnt vmcnt(0)"
+               : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7])::"memory");
+}
+
+// The segment loader, for streams of CH = 1 / 2 / 4 / 8 channels (CH then divides every tile height): a stage's BK
+// samples x CH channels of one frame are 4 BK CH contiguous bytes, fetched by BK / 4 * CH lanes with one dwordx4
+// each - 16x fewer cache-line touches in the texture addresser than the per-row loaders - and scattered, windowed,
+// into the A tile As[slot][i][row], whose rows of i are AS floats apart.  One piece per lane: k_mdct_fwd_dma and
+// k_mdct_mx_st.  The kernel states `off` itself, in one statement (pcm_frame_first of the frame's first row - the
+// tile's base + o, where that row is < M): behind a call here k_mdct_fwd_dma took one more SGPR and the loops of
+// k_mdct_mx_st other scalar registers.  st_body (one or two pieces) keeps these rules in its own statements, for the
+// reason given there.
+// SOME: only the lanes constructed with `loads` load and store (wave-uniform); every lane waits.
+template <int CH, int BK, int AS, bool SOME = false>
+struct SegLoader {
+  static_assert(CH == 1 || CH == 2 || CH == 4 || CH == 8, "segment loader shapes");
+  static constexpr int kLanes = BK / 4 * CH;  // lanes per frame segment
+  int fl, o;     // lane -> (frame fl of the tile, floats o .. o + 3 of its BK x CH segment)
+  bool on;       // this lane loads
+  unsigned off;  // byte offset of the segment's float o at i = 0, from the tile's base
+  f32x4 v;
+
+  __device__ __forceinline__ SegLoader(int tid, bool loads)
+      : fl(tid / kLanes), o((tid % kLanes) * 4), on(loads), off(kPcmNoRow), v{0.f, 0.f, 0.f, 0.f} {}
+  // i0_bytes: i0 x the bytes between two samples of a channel, in the form the kernel has them (asm: as pcm_issue_rows)
+  __device__ __forceinline__ void issue(__amdgpu_buffer_rsrc_t rsrc, unsigned i0_bytes) {
+    if (SOME && !on) return;
+    const unsigned o0 = off + i0_bytes;
+    asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=&v"(v) : "v"(o0), "s"(rsrc) : "memory");
+  }
+  __device__ __forceinline__ void wait() {  // everything this wave has in flight
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(v)::"memory");
+  }
+  template <typename ATile, typename Window>
+  __device__ __forceinline__ void store(int i0, int slot, ATile &As, const Window &Ws) {
+    if (SOME && !on) return;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int e = o + j;  // float e of the segment: sample i = e / CH of channel e % CH
+      const int ii = e / CH;
+      As[slot][ii * AS + fl * CH + e % CH] = mul_rn(v[j], Ws[i0 + ii]);  // block[i] = slice[i]*window[i], :480
+    }
+  }
+};
 
 // BM x BN output tile per workgroup, BK table rows per LDS stage, TM x TN outputs per lane
 // (TM, TN in {4, 8}: one or two conflict-free ds_read_b128 per operand and i-step),
@@ -101,34 +253,15 @@ __global__ __launch_bounds__((BM / TM) * (BN / TN), MINW) void k_mdct_fwd(Device
   const int n0 = n_tile * BN;
   const int tx = tid % C::kNtx, ty = tid / C::kNtx;
 
-  // --- A operand: interleaved PCM read through a buffer descriptor whose hardware range check
-  // supplies the encoder's zero padding (512 leading zeros, tail, shard edges): an element
-  // before the descriptor base wraps to a huge unsigned offset, one past the end is >= the
-  // record count; both load 0.0.  All descriptor inputs are blockIdx/kernarg scalars.
+  // --- A operand (the PCM tile loader, above)
   const long long ch = pcm.ch;
-  const long long f0 = frame_begin + m0 / pcm.ch;  // first frame of the tile
-  const long long e_first = (f0 * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * ch;
-  long long e_end = static_cast<long long>(pcm.t_count) * ch;  // shard end (elements)
-  const long long n_rel = static_cast<long long>(pcm.n_samples) - static_cast<long long>(pcm.t0) * ch;
-  if (e_end > n_rel) e_end = n_rel;  // stream end
-  const long long e_base = e_first < 0 ? 0 : e_first;
-  long long e_cnt = e_end - e_base;
-  if (e_cnt < 0) e_cnt = 0;
-  if (e_cnt > (1ll << 28)) e_cnt = 1ll << 28;
-  const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(pcm.p + e_base), 0, static_cast<int>(e_cnt * 4), 0x00020000);
-
+  const PcmTile a_tile = pcm_tile(pcm, frame_begin, m0, pcm.ch);
+  const __amdgpu_buffer_rsrc_t a_rsrc = a_tile.rsrc;  // (what the stage lambdas take: a_tile stays out of their captures)
   // this thread stages ONE row (r = tid % BM) and kAPer of the BK i of a stage
   const int a_r = tid % BM;
   const int a_i = tid / BM;
-  const unsigned a_row = m0 + a_r;
-  unsigned a_off = 0x80000000u;  // out-of-range row: every load returns 0
-  if (a_row < M) {
-    const long long f = frame_begin + a_row / pcm.ch;
-    const long long c = a_row % pcm.ch;
-    const long long e_row = (f * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * ch + c;
-    a_off = static_cast<unsigned>((e_row - e_base + a_i * ch) * 4);  // may wrap: that IS the padding
-  }
+  unsigned a_off = kPcmNoRow;
+  pcm_row_origin(a_off, pcm, a_tile, frame_begin, m0 + a_r, M, pcm.ch, a_i);
   const unsigned a_step = static_cast<unsigned>(C::kAStride * ch * 4);  // bytes between this thread's i's
   const float *w_ptr = tb.window + a_i;
   // B operand: float4 (row = idx / (BN/4), col4 = idx % (BN/4)), idx = tid + kThreads j
@@ -139,13 +272,9 @@ __global__ __launch_bounds__((BM / TM) * (BN / TN), MINW) void k_mdct_fwd(Device
   float4 b_stage[C::kBPer];
 
   auto load_stage = [&](int i0) {
-    const unsigned off0 = a_off + static_cast<unsigned>(i0) * static_cast<unsigned>(ch * 4);
+    pcm_load_rows(a_stage, a_rsrc, a_off + static_cast<unsigned>(i0) * static_cast<unsigned>(ch * 4), a_step);
 #pragma unroll
-    for (int j = 0; j < C::kAPer; ++j) {
-      const float x = __builtin_bit_cast(
-          float, __builtin_amdgcn_raw_buffer_load_b32(a_rsrc, off0 + j * a_step, 0, 0));
-      a_stage[j] = mul_rn(x, w_ptr[i0 + C::kAStride * j]);  // block[i] = slice[i]*window[i], :480
-    }
+    for (int j = 0; j < C::kAPer; ++j) a_stage[j] = mul_rn(a_stage[j], w_ptr[i0 + C::kAStride * j]);  // block[i] = slice[i]*window[i], :480
 #pragma unroll
     for (int j = 0; j < C::kBPer; ++j)
       b_stage[j] = *reinterpret_cast<const float4 *>(b_ptr + static_cast<size_t>(i0 + C::kBRowsPer * j) * kHopI);
@@ -233,9 +362,6 @@ __global__ __launch_bounds__((BM / TM) * (BN / TN), MINW) void k_mdct_fwd(Device
 // step first, then 2 groups of {8 v_pk_mul, 8 v_pk_add} (dependent instructions 8 apart), then
 // one s_waitcnt: register set X feeds even steps, set Y odd steps (ping-pong, no copies).
 // ------------------------------------------------------------------------------------------
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 struct Operands {  // one i-step's A (4 rows) and B (8 columns) values of this lane
   f32x2 a0, a1, b0, b1, b2, b3;
 };
@@ -405,13 +531,8 @@ void k_mdct_fwd_sched(DeviceTables tb, PcmView pcm, long long frame_begin, unsig
   __shared__ __attribute__((aligned(16))) float Bs[2][BK * BN];
 
   const int tid = threadIdx.x;
-  // Workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8 says which blocks share an
-  // L2).  Give XCD x the contiguous tile range [x*T/8, (x+1)*T/8) in (m_tile, n_tile) order: the
-  // PCM rows of an m-tile are then fetched by ONE XCD instead of all eight, and the table rows of
-  // a stage are shared in that XCD's L2 by all resident m-tiles, which sweep i together
-  // (measured: 4x less L2 fill traffic).  Placement affects speed only, never results.
   static_assert(C::kNTiles == 8, "tile map assumes 8 coefficient tiles");
-  const unsigned g = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  const unsigned g = xcd_tile();
   const int n_tile = g % C::kNTiles;
   const int m_tile = g / C::kNTiles;
   const int m0 = m_tile * BM;
@@ -419,28 +540,12 @@ void k_mdct_fwd_sched(DeviceTables tb, PcmView pcm, long long frame_begin, unsig
   const int tx = tid % C::kNtx, ty = tid / C::kNtx;
 
   const long long ch = pcm.ch;
-  const long long f0 = frame_begin + m0 / pcm.ch;
-  const long long e_first = (f0 * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * ch;
-  long long e_end = static_cast<long long>(pcm.t_count) * ch;
-  const long long n_rel = static_cast<long long>(pcm.n_samples) - static_cast<long long>(pcm.t0) * ch;
-  if (e_end > n_rel) e_end = n_rel;
-  const long long e_base = e_first < 0 ? 0 : e_first;
-  long long e_cnt = e_end - e_base;
-  if (e_cnt < 0) e_cnt = 0;
-  if (e_cnt > (1ll << 28)) e_cnt = 1ll << 28;
-  const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(pcm.p + e_base), 0, static_cast<int>(e_cnt * 4), 0x00020000);
-
+  const PcmTile a_tile = pcm_tile(pcm, frame_begin, m0, pcm.ch);
+  const __amdgpu_buffer_rsrc_t a_rsrc = a_tile.rsrc;  // (what the stage lambdas take: a_tile stays out of their captures)
   const int a_r = tid % BM;
   const int a_i = tid / BM;
-  const unsigned a_row = m0 + a_r;
-  unsigned a_off = 0x80000000u;
-  if (a_row < M) {
-    const long long f = frame_begin + a_row / pcm.ch;
-    const long long c = a_row % pcm.ch;
-    const long long e_row = (f * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * ch + c;
-    a_off = static_cast<unsigned>((e_row - e_base + a_i * ch) * 4);
-  }
+  unsigned a_off = kPcmNoRow;
+  pcm_row_origin(a_off, pcm, a_tile, frame_begin, m0 + a_r, M, pcm.ch, a_i);
   const unsigned a_step = static_cast<unsigned>(C::kAStride * ch * 4);
   const float *w_ptr = tb.window + a_i;
   const int b_r = tid / (BN / 4), b_c4 = tid % (BN / 4);
@@ -451,12 +556,9 @@ void k_mdct_fwd_sched(DeviceTables tb, PcmView pcm, long long frame_begin, unsig
   float a_raw[C::kAPer], a_win[C::kAPer];
   f32x4 b_stage[C::kBPer];
   auto load_stage = [&](int i0) {
-    const unsigned off0 = a_off + static_cast<unsigned>(i0) * static_cast<unsigned>(ch * 4);
+    pcm_load_rows(a_raw, a_rsrc, a_off + static_cast<unsigned>(i0) * static_cast<unsigned>(ch * 4), a_step);
 #pragma unroll
-    for (int j = 0; j < C::kAPer; ++j) {
-      a_raw[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(a_rsrc, off0 + j * a_step, 0, 0));
-      a_win[j] = w_ptr[i0 + C::kAStride * j];
-    }
+    for (int j = 0; j < C::kAPer; ++j) a_win[j] = w_ptr[i0 + C::kAStride * j];
 #pragma unroll
     for (int j = 0; j < C::kBPer; ++j)
       b_stage[j] = *reinterpret_cast<const f32x4 *>(b_ptr + static_cast<size_t>(i0 + C::kBRowsPer * j) * kHopI);
@@ -562,10 +664,8 @@ template <int MINW, int CH = 0, int PRIO = 0, bool STAMP = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MINW, MINW)))
 void k_mdct_fwd_dma(DeviceTables tb, PcmView pcm, long long frame_begin, unsigned M, float *__restrict__ coef,
                     unsigned long long *__restrict__ stamps) {
-  // CH = 0: one PCM dword per (row, i) and lane - any channel count.  CH = 1 / 2 / 4 / 8 (the
-  // stream's channel count, which then divides the tile height): a stage's 16 samples x CH channels
-  // of one frame are 64 * CH contiguous bytes, fetched by 4 * CH lanes with one dwordx4 each - 16x
-  // fewer cache-line touches in the texture addresser than the per-row loader.
+  // CH = 0: the per-row loader, one PCM dword per (row, i) and lane - any channel count.  CH = 1 / 2 / 4 / 8 (the
+  // stream's channel count): the segment loader, one piece.
   // 512 threads, 2 workgroups per CU (56 KiB LDS each).
   constexpr int BM = 128, BN = 128, BK = 16, TM = 4, RING = 3;
   // A rows are kAS floats apart in LDS, 4 more than the tile is wide: the segment loader's four ds_write_b32
@@ -584,7 +684,7 @@ void k_mdct_fwd_dma(DeviceTables tb, PcmView pcm, long long frame_begin, unsigne
   __shared__ __attribute__((aligned(16))) float Ws[kFrameI];
 
   const int tid = threadIdx.x;
-  const unsigned g = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);  // XCD-aware tile map
+  const unsigned g = xcd_tile();
   const int n_tile = g % 8;
   const int m_tile = g / 8;
   const int m0 = m_tile * BM;
@@ -596,76 +696,34 @@ void k_mdct_fwd_dma(DeviceTables tb, PcmView pcm, long long frame_begin, unsigne
   for (int i = tid; i < kFrameI; i += kThreads) Ws[i] = tb.window[i];
 
   const long long ch = pcm.ch;
-  const long long f0 = frame_begin + m0 / pcm.ch;
-  const long long e_first = (f0 * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * ch;
-  long long e_end = static_cast<long long>(pcm.t_count) * ch;
-  const long long n_rel = static_cast<long long>(pcm.n_samples) - static_cast<long long>(pcm.t0) * ch;
-  if (e_end > n_rel) e_end = n_rel;
-  const long long e_base = e_first < 0 ? 0 : e_first;
-  long long e_cnt = e_end - e_base;
-  if (e_cnt < 0) e_cnt = 0;
-  if (e_cnt > (1ll << 28)) e_cnt = 1ll << 28;
-  const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(pcm.p + e_base), 0, static_cast<int>(e_cnt * 4), 0x00020000);
-
+  const PcmTile a_tile = pcm_tile(pcm, frame_begin, m0, pcm.ch);
+  const __amdgpu_buffer_rsrc_t a_rsrc = a_tile.rsrc;  // (what the stage lambdas take: a_tile stays out of their captures)
+  // per-row loader: lane -> (row a_r of the tile, i = a_i + 4 j; a_i is the same for every lane of a wave)
   const int a_r = tid % BM;
-  const int a_i = tid / BM;  // 0..3: i = a_i + 4 j  (the same for every lane of a wave)
-  const unsigned a_row = m0 + a_r;
-  unsigned a_off = 0x80000000u;
-  if (a_row < M) {
-    const long long f = frame_begin + a_row / pcm.ch;
-    const long long c = a_row % pcm.ch;
-    const long long e_row = (f * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * ch + c;
-    a_off = static_cast<unsigned>((e_row - e_base + a_i * ch) * 4);
-  }
+  const int a_i = tid / BM;
+  unsigned a_off = kPcmNoRow;
   const unsigned a_step = static_cast<unsigned>(kAStride * ch * 4);
   const unsigned i_bytes = static_cast<unsigned>(ch * 4);
-  // segment loader: lane -> (frame of the tile, 4 consecutive floats of its 16 x CH segment)
-  constexpr int kSegCh = kSeg ? CH : 1;
-  const int seg_fl = tid / (4 * kSegCh);       // frame within the tile
-  const int seg_o = (tid % (4 * kSegCh)) * 4;  // first float of this lane inside the segment
+  float a_raw[kAPer];
+  SegLoader<kSeg ? CH : 1, BK, kAS> seg(tid, true);
   if constexpr (kSeg) {
-    const unsigned row0 = m0 + seg_fl * CH;
-    a_off = 0x80000000u;
-    if (row0 < M) {
-      const long long f = frame_begin + row0 / CH;
-      const long long e_row = (f * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * CH;
-      a_off = static_cast<unsigned>((e_row - e_base + seg_o) * 4);
-    }
+    const unsigned row0 = m0 + seg.fl * CH;
+    if (row0 < M) seg.off = static_cast<unsigned>((pcm_frame_first(pcm, frame_begin, row0, CH) - a_tile.e_base + seg.o) * 4);
+  } else {
+    pcm_row_origin(a_off, pcm, a_tile, frame_begin, m0 + a_r, M, pcm.ch, a_i);
   }
   // table DMA: wave w copies rows 2 w, 2 w + 1 of the stage's 16 x 128 tile (1 KiB, lane-linear)
   const float *b_src = tb.cos_t + n0 + static_cast<size_t>(2 * wave + (lane >> 5)) * kHopI + (lane & 31) * 4;
 
-  float a_raw[kAPer];
-  f32x4 a_seg = {0.f, 0.f, 0.f, 0.f};
-  auto issue_a = [&](int i0) {  // asm: hipcc must not count these loads (see lds_fetch4)
-    const unsigned o = a_off + static_cast<unsigned>(i0) * i_bytes;
-    if constexpr (kSeg) {
-      asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=&v"(a_seg) : "v"(o), "s"(a_rsrc) : "memory");
-      return;
-    }
-    asm volatile(
-        "buffer_load_dword %0, %4, %8, 0 offen\n\t"
-        "buffer_load_dword %1, %5, %8, 0 offen\n\t"
-        "buffer_load_dword %2, %6, %8, 0 offen\n\t"
-        "buffer_load_dword %3, %7, %8, 0 offen"
-        : "=&v"(a_raw[0]), "=&v"(a_raw[1]), "=&v"(a_raw[2]), "=&v"(a_raw[3])
-        : "v"(o), "v"(o + a_step), "v"(o + 2 * a_step), "v"(o + 3 * a_step), "s"(a_rsrc)
-        : "memory");
+  auto issue_a = [&](int i0) {
+    if constexpr (kSeg) return seg.issue(a_rsrc, static_cast<unsigned>(i0) * i_bytes);
+    pcm_issue_rows<kAPer>(a_raw, a_rsrc, a_off + static_cast<unsigned>(i0) * i_bytes, a_step);
   };
   auto issue_b = [&](int i0, int slot) {
     __builtin_amdgcn_global_load_lds(b_src + static_cast<size_t>(i0) * kHopI, &Bs[slot][2 * wave * BN], 16, 0, 0);
   };
   auto store_a = [&](int i0, int slot) {
-    if constexpr (kSeg) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int e = seg_o + j;  // float e of the segment: sample i = e / CH of channel e % CH
-        const int ii = e / CH;
-        As[slot][ii * kAS + seg_fl * CH + e % CH] = mul_rn(a_seg[j], Ws[i0 + ii]);  // :480
-      }
-      return;
-    }
+    if constexpr (kSeg) return seg.store(i0, slot, As, Ws);
 #pragma unroll
     for (int j = 0; j < kAPer; ++j) {
       const int ii = a_i + kAStride * j;
@@ -673,10 +731,8 @@ void k_mdct_fwd_dma(DeviceTables tb, PcmView pcm, long long frame_begin, unsigne
     }
   };
   auto wait_staged = [&]() {  // everything this wave has in flight: PCM registers + table DMA of the next stage
-    if constexpr (kSeg)
-      asm volatile("s_waitcnt vmcnt(0)" : "+v"(a_seg)::"memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" : "+v"(a_raw[0]), "+v"(a_raw[1]), "+v"(a_raw[2]), "+v"(a_raw[3])::"memory");
+    if constexpr (kSeg) return seg.wait();
+    pcm_wait_rows(a_raw);
   };
 
   f32x2 acc[TM][4];
@@ -691,7 +747,7 @@ void k_mdct_fwd_dma(DeviceTables tb, PcmView pcm, long long frame_begin, unsigne
   issue_a(0);
   issue_b(0, 0);
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)"
-               : "+v"(a_raw[0]), "+v"(a_raw[1]), "+v"(a_raw[2]), "+v"(a_raw[3]), "+v"(a_seg)::"memory");
+               : "+v"(a_raw[0]), "+v"(a_raw[1]), "+v"(a_raw[2]), "+v"(a_raw[3]), "+v"(seg.v)::"memory");
   store_a(0, 0);
   issue_a(BK);
   issue_b(BK, 1);
@@ -1140,7 +1196,7 @@ __device__ __forceinline__ void st_body(const DeviceTables &tb, const PcmView &p
   __shared__ __attribute__((aligned(16))) float Ws[kFrameI];
 
   const int tid = threadIdx.x;
-  const unsigned g = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);  // XCD-aware tile map
+  const unsigned g = xcd_tile();
   const int n_tile = g % kNTiles;
   const int m_tile = g / kNTiles;
   const int m0 = m_tile * BM;
@@ -1151,25 +1207,18 @@ __device__ __forceinline__ void st_body(const DeviceTables &tb, const PcmView &p
   for (int i = tid; i < kFrameI; i += kThreads) Ws[i] = tb.window[i];
 
   const long long ch = pcm.ch;
-  const long long f0 = frame_begin + m0 / pcm.ch;
-  const long long e_first = (f0 * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * ch;
-  long long e_end = static_cast<long long>(pcm.t_count) * ch;
-  const long long n_rel = static_cast<long long>(pcm.n_samples) - static_cast<long long>(pcm.t0) * ch;
-  if (e_end > n_rel) e_end = n_rel;
-  const long long e_base = e_first < 0 ? 0 : e_first;
-  long long e_cnt = e_end - e_base;
-  if (e_cnt < 0) e_cnt = 0;
-  if (e_cnt > (1ll << 28)) e_cnt = 1ll << 28;
-  const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(pcm.p + e_base), 0, static_cast<int>(e_cnt * 4), 0x00020000);
-
+  const PcmTile a_tile = pcm_tile(pcm, frame_begin, m0, pcm.ch);
+  const __amdgpu_buffer_rsrc_t a_rsrc = a_tile.rsrc;  // (what the stage lambdas take: a_tile stays out of their captures)
   // per-row loader: lane -> (row a_r of the tile, i = a_i + kIGroups * j)
   const int a_r = tid % BM;
   const int a_i = tid / BM;
-  unsigned a_off[2] = {0x80000000u, 0x80000000u};
+  unsigned a_off[2] = {kPcmNoRow, kPcmNoRow};
   const unsigned a_step = static_cast<unsigned>(kIGroups * ch * 4);
   const unsigned i_bytes = static_cast<unsigned>(ch * 4);
-  // segment loader: (lane, p) -> (frame seg_fl + p * kSegHalf of the tile, 4 consecutive floats of its BK x CH segment)
+  // segment loader: SegLoader's rules - (lane, p) -> (frame seg_fl + p * kSegHalf of the tile, 4 consecutive floats of
+  // its BK x CH segment) - for one or two pieces, in this body's own statements: on SegLoader, in every form tried,
+  // the i loops of the 16-wave instantiations came out with other registers and another instruction order
+  // (profiles/k1_loader_isa.txt), and these are the kernels every large launch runs
   constexpr int kSegCh = kSeg ? CH : 1;
   constexpr int kSegLanes = BK / 4 * kSegCh;  // lanes per frame segment
   constexpr int kSegHalf = kThreads / kSegLanes;
@@ -1179,20 +1228,10 @@ __device__ __forceinline__ void st_body(const DeviceTables &tb, const PcmView &p
 #pragma unroll
     for (int p = 0; p < kPieces; ++p) {
       const unsigned row0 = m0 + (seg_fl + p * kSegHalf) * CH;
-      if (row0 < M) {
-        const long long f = frame_begin + row0 / CH;
-        const long long e_row = (f * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * CH;
-        a_off[p] = static_cast<unsigned>((e_row - e_base + seg_o) * 4);
-      }
+      if (row0 < M) a_off[p] = static_cast<unsigned>((pcm_frame_first(pcm, frame_begin, row0, CH) - a_tile.e_base + seg_o) * 4);
     }
   } else {
-    const unsigned a_row = m0 + a_r;
-    if (a_row < M) {
-      const long long f = frame_begin + a_row / pcm.ch;
-      const long long c = a_row % pcm.ch;
-      const long long e_row = (f * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * ch + c;
-      a_off[0] = static_cast<unsigned>((e_row - e_base + a_i * ch) * 4);
-    }
+    pcm_row_origin(a_off[0], pcm, a_tile, frame_begin, m0 + a_r, M, pcm.ch, a_i);
   }
 
   float a_raw[8];
@@ -1211,24 +1250,7 @@ __device__ __forceinline__ void st_body(const DeviceTables &tb, const PcmView &p
       }
       return;
     }
-    const unsigned o = a_off[0] + static_cast<unsigned>(i0) * i_bytes;
-    asm volatile(
-        "buffer_load_dword %0, %4, %8, 0 offen\n\t"
-        "buffer_load_dword %1, %5, %8, 0 offen\n\t"
-        "buffer_load_dword %2, %6, %8, 0 offen\n\t"
-        "buffer_load_dword %3, %7, %8, 0 offen"
-        : "=&v"(a_raw[0]), "=&v"(a_raw[1]), "=&v"(a_raw[2]), "=&v"(a_raw[3])
-        : "v"(o), "v"(o + a_step), "v"(o + 2 * a_step), "v"(o + 3 * a_step), "s"(a_rsrc)
-        : "memory");
-    if constexpr (kAPer == 8)
-      asm volatile(
-          "buffer_load_dword %0, %4, %8, 0 offen\n\t"
-          "buffer_load_dword %1, %5, %8, 0 offen\n\t"
-          "buffer_load_dword %2, %6, %8, 0 offen\n\t"
-          "buffer_load_dword %3, %7, %8, 0 offen"
-          : "=&v"(a_raw[4]), "=&v"(a_raw[5]), "=&v"(a_raw[6]), "=&v"(a_raw[7])
-          : "v"(o + 4 * a_step), "v"(o + 5 * a_step), "v"(o + 6 * a_step), "v"(o + 7 * a_step), "s"(a_rsrc)
-          : "memory");
+    pcm_issue_rows<kAPer>(a_raw, a_rsrc, a_off[0] + static_cast<unsigned>(i0) * i_bytes, a_step);
   };
   auto store_a = [&](int i0, int slot) {
     if constexpr (kSeg) {
@@ -1249,12 +1271,11 @@ __device__ __forceinline__ void st_body(const DeviceTables &tb, const PcmView &p
     }
   };
   auto wait_staged = [&]() {
-    if constexpr (kSeg)
+    if constexpr (kSeg) {
       asm volatile("s_waitcnt vmcnt(0)" : "+v"(a_seg[0]), "+v"(a_seg[1])::"memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)"
-                   : "+v"(a_raw[0]), "+v"(a_raw[1]), "+v"(a_raw[2]), "+v"(a_raw[3]), "+v"(a_raw[4]), "+v"(a_raw[5]),
-                     "+v"(a_raw[6]), "+v"(a_raw[7])::"memory");
+      return;
+    }
+    pcm_wait_rows(a_raw);
   };
 
   f32x2 acc[4][4];
@@ -1584,8 +1605,7 @@ void k_mdct_mx_st(DeviceTables tb, PcmView pcm, long long frame_begin, unsigned 
   __shared__ __attribute__((aligned(16))) f32x4 Tot[4][kTiles * 4][64];
 
   const int tid = threadIdx.x;
-  // XCD-aware tile map (speed only): the workgroups of a row tile on one XCD, where the grid divides by 8
-  const unsigned g = gridDim.x % 8u ? blockIdx.x : (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  const unsigned g = xcd_tile<true>();  // 4 workgroups per row tile: any grid
   const int j = g % MB::kGroups;
   const int m0 = (g / MB::kGroups) * BM;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1593,48 +1613,18 @@ void k_mdct_mx_st(DeviceTables tb, PcmView pcm, long long frame_begin, unsigned 
 
   for (int i = tid; i < kFrameI; i += 1024) Ws[i] = tb.window[i];
 
-  const long long f0 = frame_begin + m0 / CH;
-  const long long e_first = (f0 * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * CH;
-  long long e_end = static_cast<long long>(pcm.t_count) * CH;
-  const long long n_rel = static_cast<long long>(pcm.n_samples) - static_cast<long long>(pcm.t0) * CH;
-  if (e_end > n_rel) e_end = n_rel;
-  const long long e_base = e_first < 0 ? 0 : e_first;
-  long long e_cnt = e_end - e_base;
-  if (e_cnt < 0) e_cnt = 0;
-  if (e_cnt > (1ll << 28)) e_cnt = 1ll << 28;
-  const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(pcm.p + e_base), 0, static_cast<int>(e_cnt * 4), 0x00020000);
-
-  // segment loader (waves 0 .. 7): lane -> (frame seg_fl of the tile, 4 consecutive floats of its BK x CH segment)
-  constexpr int kSegLanes = BK / 4 * CH;
-  const bool loader = wave < kLoaders / 64;
-  const int seg_fl = tid / kSegLanes;
-  const int seg_o = (tid % kSegLanes) * 4;
-  unsigned a_off = 0x80000000u;  // out-of-range row: every load returns 0
+  const PcmTile a_tile = pcm_tile(pcm, frame_begin, m0, CH);
+  const __amdgpu_buffer_rsrc_t a_rsrc = a_tile.rsrc;
+  // the segment loader's lanes are waves 0 .. 7, one piece each
+  SegLoader<CH, BK, kAS, true> seg(tid, wave < kLoaders / 64);
   {
-    const unsigned row0 = m0 + seg_fl * CH;
-    if (loader && row0 < M) {
-      const long long f = frame_begin + row0 / CH;
-      const long long e_row = (f * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * CH;
-      a_off = static_cast<unsigned>((e_row - e_base + seg_o) * 4);
-    }
+    const unsigned row0 = m0 + seg.fl * CH;
+    if (seg.on && row0 < M)
+      seg.off = static_cast<unsigned>((pcm_frame_first(pcm, frame_begin, row0, CH) - a_tile.e_base + seg.o) * 4);
   }
-  f32x4 a_seg = {0.f, 0.f, 0.f, 0.f};
-  auto issue_a = [&](int i0) {  // asm: hipcc must not count these loads (see lds_fetch4)
-    if (!loader) return;
-    const unsigned o = a_off + static_cast<unsigned>(i0) * static_cast<unsigned>(CH * 4);
-    asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=&v"(a_seg) : "v"(o), "s"(a_rsrc) : "memory");
-  };
-  auto store_a = [&](int i0, int slot) {
-    if (!loader) return;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int e = seg_o + q;  // float e of the segment: sample i = e / CH of channel e % CH
-      const int ii = e / CH;
-      As[slot][ii * kAS + seg_fl * CH + e % CH] = mul_rn(a_seg[q], Ws[i0 + ii]);  // block[i] = slice[i]*window[i], :480
-    }
-  };
-  auto wait_staged = [&]() { asm volatile("s_waitcnt vmcnt(0)" : "+v"(a_seg)::"memory"); };
+  auto issue_a = [&](int i0) { seg.issue(a_rsrc, static_cast<unsigned>(i0) * static_cast<unsigned>(CH * 4)); };
+  auto store_a = [&](int i0, int slot) { seg.store(i0, slot, As, Ws); };
+  auto wait_staged = [&]() { seg.wait(); };
 
   if (wave < kExactWaves) {
     // ---------------------------------------------------------------- exact waves
@@ -1954,28 +1944,13 @@ __device__ __forceinline__ void small_body(const DeviceTables &tb, const PcmView
     if (__ballot(flagged) == 0ull) return;
   }
 
-  // A operand through a buffer descriptor whose range check is the encoder's zero padding (see k_mdct_fwd)
+  // A operand: the per-row loader, builtin form
   const long long ch = pcm.ch;
-  const long long f0 = frame_begin + m0 / pcm.ch;
-  const long long e_first = (f0 * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * ch;
-  long long e_end = static_cast<long long>(pcm.t_count) * ch;
-  const long long n_rel = static_cast<long long>(pcm.n_samples) - static_cast<long long>(pcm.t0) * ch;
-  if (e_end > n_rel) e_end = n_rel;
-  const long long e_base = e_first < 0 ? 0 : e_first;
-  long long e_cnt = e_end - e_base;
-  if (e_cnt < 0) e_cnt = 0;
-  if (e_cnt > (1ll << 28)) e_cnt = 1ll << 28;
-  const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(pcm.p + e_base), 0, static_cast<int>(e_cnt * 4), 0x00020000);
+  const PcmTile a_tile = pcm_tile(pcm, frame_begin, m0, pcm.ch);
+  const __amdgpu_buffer_rsrc_t a_rsrc = a_tile.rsrc;  // (what the stage lambdas take: a_tile stays out of their captures)
   const int a_r = tid % BM, a_i = tid / BM;
-  const unsigned a_row = m0 + a_r;
-  unsigned a_off = 0x80000000u;  // out-of-range row: every load returns 0
-  if (a_row < M) {
-    const long long f = frame_begin + a_row / pcm.ch;
-    const long long c = a_row % pcm.ch;
-    const long long e_row = (f * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * ch + c;
-    a_off = static_cast<unsigned>((e_row - e_base + a_i * ch) * 4);  // may wrap: that IS the padding
-  }
+  unsigned a_off = kPcmNoRow;
+  pcm_row_origin(a_off, pcm, a_tile, frame_begin, m0 + a_r, M, pcm.ch, a_i);
   const unsigned a_step = static_cast<unsigned>(kAStride * ch * 4);
   const float *w_ptr = tb.window + a_i;
   const int b_r = tid / (BN / 4), b_c4 = tid % (BN / 4);
@@ -1984,12 +1959,9 @@ __device__ __forceinline__ void small_body(const DeviceTables &tb, const PcmView
   float a_raw[kAPer], a_win[kAPer];
   f32x4 b_stage[kBPer];
   auto load_stage = [&](int i0) {
-    const unsigned off0 = a_off + static_cast<unsigned>(i0) * static_cast<unsigned>(ch * 4);
+    pcm_load_rows(a_raw, a_rsrc, a_off + static_cast<unsigned>(i0) * static_cast<unsigned>(ch * 4), a_step);
 #pragma unroll
-    for (int j = 0; j < kAPer; ++j) {
-      a_raw[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(a_rsrc, off0 + j * a_step, 0, 0));
-      a_win[j] = w_ptr[i0 + kAStride * j];
-    }
+    for (int j = 0; j < kAPer; ++j) a_win[j] = w_ptr[i0 + kAStride * j];
 #pragma unroll
     for (int j = 0; j < kBPer; ++j)
       b_stage[j] = *reinterpret_cast<const f32x4 *>(b_ptr + static_cast<size_t>(i0 + kBRowsPer * j) * kHopI);
@@ -2245,9 +2217,7 @@ __device__ __forceinline__ void small_rows_body(const DeviceTables &tb, const Pc
 
   const unsigned n_slabs = (static_cast<unsigned>(kHopI) - col0) / kRowsSlab;
   const unsigned n_items = (n_fail + R - 1) / R * n_slabs;
-  long long e_end = static_cast<long long>(pcm.t_count) * pcm.ch;  // shard end (elements from pcm.p)
-  const long long n_rel = static_cast<long long>(pcm.n_samples) - static_cast<long long>(pcm.t0) * pcm.ch;
-  if (e_end > n_rel) e_end = n_rel;  // stream end
+  const long long e_end = pcm_end(pcm, pcm.ch);
   const unsigned xs0 = static_cast<unsigned>(reinterpret_cast<uintptr_t>(&xs[0]));
 
 #pragma unroll 1
@@ -2310,10 +2280,9 @@ __device__ __forceinline__ void small_rows_body(const DeviceTables &tb, const Pc
     for (int q = 0; q < R; ++q) m[q] = __builtin_amdgcn_readfirstlane(s_row[q]);
     }
 
-    // fl(x w) of the group's rows -> LDS.  Each row is read through a buffer descriptor of its own whose range check
-    // is the encoder's zero padding, as in small_body (an element before the base wraps to a huge offset, one past the
-    // shard or the stream is beyond the record count: both load 0.0) - so every load is unconditional and all of them
-    // are issued before the first LDS write: one memory round trip for the whole group, not one per sample
+    // fl(x w) of the group's rows -> LDS.  Each row is read through a buffer descriptor of its own, based at the row's
+    // first element, whose range check is the encoder's zero padding as PcmTile's is - so every load is unconditional
+    // and all of them are issued before the first LDS write: one memory round trip for the whole group, not one per sample
     constexpr int kPer = kFrameI / 64;
     float wv[kPer], xv[R][kPer];
 #pragma unroll
@@ -2325,11 +2294,8 @@ __device__ __forceinline__ void small_rows_body(const DeviceTables &tb, const Pc
       const long long e_row =
           (f * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * static_cast<long long>(pcm.ch) + (live ? m[q] % pcm.ch : 0u);
       const long long e_base = e_row < 0 ? 0 : e_row;
-      long long e_cnt = live ? e_end - e_base : 0;  // (a row the list does not have: nothing in range, all zeros)
-      if (e_cnt < 0) e_cnt = 0;
-      if (e_cnt > (1ll << 28)) e_cnt = 1ll << 28;
-      const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(pcm.p + e_base), 0,
-                                                                           static_cast<int>(e_cnt * 4), 0x00020000);
+      // (a row the list does not have: nothing in range, all zeros)
+      const __amdgpu_buffer_rsrc_t rsrc = pcm_rsrc(pcm, e_base, live ? e_end - e_base : 0);
       const unsigned off0 = static_cast<unsigned>((e_row - e_base) * 4);  // 0, or negative: wraps, that IS the padding
 #pragma unroll
       for (int t = 0; t < kPer; ++t)

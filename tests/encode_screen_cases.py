@@ -266,11 +266,14 @@ def stats(glc_amd, ctx):
     return a.value, b.value
 
 
-def records(torch, glc_amd, enc, c, mode):
+def records(torch, glc_amd, enc, c, mode, nan_pad=0):
     """One glc_encode_range_device of the case with the screen in `mode` (None: as the context stands, which is the
-    automatic mode) -> (record bytes, rows screened, rows repaired)."""
+    automatic mode) -> (record bytes, rows screened, rows repaired).  nan_pad: that many NaN words in front of and
+    behind the shard on the device."""
     sh, t0, tc = c.shard()
-    d_pcm = torch.from_numpy(sh.view(np.int32).copy()).cuda()     # as words: NaN payloads travel untouched
+    host = np.full(sh.size + 2 * nan_pad, 0x7FC00000, np.uint32)
+    host[nan_pad:nan_pad + sh.size] = sh.view(np.uint32)          # as words: NaN payloads travel untouched
+    d_pcm = torch.from_numpy(host.view(np.int32)).cuda()
     rb = glc_amd.lib.glc_record_bytes(c.ch) * (c.f1 - c.f0)
     d_rec = torch.full((rb + 8192,), 0xA5, dtype=torch.uint8, device="cuda")
     d_rec[4096:4096 + rb] = 0     # zeroed, as the oracle's are: header padding and the upper half of a compressed row are nobody's
@@ -279,7 +282,7 @@ def records(torch, glc_amd, enc, c, mode):
     if mode is not None:      # (setting a mode, the automatic one too, clears the guard's state: None leaves it alone)
         assert glc_amd.lib.glc_debug_set_encode_screen(enc._h, mode) == 0
     try:
-        enc.encode_range_device(d_pcm.data_ptr(), t0, tc, c.n_samples, c.ch, c.f0, c.f1, d_rec.data_ptr() + 4096)
+        enc.encode_range_device(d_pcm.data_ptr() + 4 * nan_pad, t0, tc, c.n_samples, c.ch, c.f0, c.f1, d_rec.data_ptr() + 4096)
         enc.synchronize()
     finally:
         if mode is not None:

@@ -38,6 +38,19 @@ def stream(sr, ch, frames):
     return tones(sr, ch, frames * HOP, *LOW)
 
 
+def guarded_shard_case(ch=2):
+    """258 rows from frame 5 of a longer stream - one 256-row tile of the FMA form of the transform and one frame
+    more, two 128-row tiles of the matrix form and one frame more - with a click in one frame, so that a few rows fail
+    and the repair runs.  Its tight shard starts inside the stream (t0 > 0) and ends inside it; the GPU test puts NaN
+    on both sides of it, so a descriptor that reached one sample too far on either side would show in the records.
+    ch = 2: the segment loader; ch = 3: one dword per (row, sample), tiles that start inside a frame."""
+    assert 258 % ch == 0
+    f0, nf = 5, 258 // ch
+    x = stream(SR, ch, f0 + nf + 4)
+    _click(x, f0 + nf // 2)
+    return Case(f"guarded-shard-ch{ch}", "guarded", SR, ch, x, f0, f0 + nf)
+
+
 # ---------------------------------------------------------------------------------------------------- 1: channels
 
 def channel_cases():

@@ -362,7 +362,8 @@ def _channels_family():
 def _guards_family():
     cases = []
     f0 = 7
-    for ch, todo in ((2, (("small2", 66), ("large", 4098))), (3, (("small4", 645), ("large", 4101)))):
+    # (sched: 28 of its 64-row tiles and two rows, the fewest rows the dispatch gives it that end inside a tile)
+    for ch, todo in ((2, (("small2", 66), ("sched", 1794), ("large", 4098))), (3, (("small4", 645), ("large", 4101)))):
         frames = max(M for _, M in todo) // ch
         src = _whole_stream(f"guards-ch{ch}", ch, f0 + frames + 9, 600 + ch)
         for cls, M in todo:

@@ -372,6 +372,32 @@ def test_gpu_one_workspace_reused_by_a_sequence_of_launches(gpu, seq):
         _launch_and_check(gpu, enc, CASES[name], f"{seq}[{i}] ")
 
 
+@pytest.mark.gpu
+# the FMA form (k_mdct_mix_st) with either PCM loader, the matrix form (k_mdct_mx_st: built for 1 / 2 / 4 / 8 channels)
+@pytest.mark.parametrize("ch, bound", ((2, 1), (2, 2), (3, 1)))
+def test_gpu_tight_shard_with_nan_on_both_sides_under_both_forms_and_both_repairs(gpu, ch, bound):
+    """The mixed-role transforms and the latency repair (k_mdct_fwd_small_rows) read their PCM through the same
+    descriptor rules as the exact kernels, whose guards cases tests/test_k1_edges.py holds: a shard with t0 > 0 that
+    ends inside the stream, NaN in front of it and behind it, a last tile that is not full.  Records byte for byte."""
+    torch, glc_amd, encoder = gpu
+    c = E.guarded_shard_case(ch)
+    exp, taps = E.expected(c)
+    v = E.model(c, taps)
+    _, t0, tc = c.shard()
+    assert t0 > 0 and (t0 + tc) * c.ch < c.n_samples and c.M % 256 and c.M % 128 and 0 < int((v == -1).sum())
+    enc = encoder("guarded")
+    lib = glc_amd.lib
+    try:
+        assert lib.glc_debug_set_encode_bound(enc._h, bound) == 0
+        for repair in (2, 1):                   # k_mdct_fwd_small_rows, k_mdct_fwd_small_cols
+            assert lib.glc_debug_set_encode_repair(enc._h, repair) == 0
+            got, screened, repaired = E.S.records(torch, glc_amd, enc, c, 2, nan_pad=16384)
+            assert np.array_equal(got, exp), f"bound {bound}, repair {repair}: {E.S.explain(got, exp, c.ch)}"
+            assert screened == c.M and int((v == -1).sum()) <= repaired <= int((v != 1).sum()), (bound, repair, screened, repaired)
+    finally:
+        assert lib.glc_debug_set_encode_bound(enc._h, 0) == 0 and lib.glc_debug_set_encode_repair(enc._h, 0) == 0
+
+
 def _set(glc_amd, ctx, mode):
     assert glc_amd.lib.glc_debug_set_encode_screen(ctx._h, mode) == 0
 

@@ -186,24 +186,15 @@ __global__ __launch_bounds__(256) void k_mdct_fwd_row(DeviceTables tb, PcmView p
   const int lane = tid & 63;
 
   const long long ch = pcm.ch;
-  const long long f0 = frame_begin + m0 / pcm.ch;
-  const long long e_first = (f0 * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * ch;
-  long long e_end = static_cast<long long>(pcm.t_count) * ch;
-  const long long n_rel = static_cast<long long>(pcm.n_samples) - static_cast<long long>(pcm.t0) * ch;
-  if (e_end > n_rel) e_end = n_rel;
-  const long long e_base = e_first < 0 ? 0 : e_first;
-  long long e_cnt = e_end - e_base;
-  if (e_cnt < 0) e_cnt = 0;
-  if (e_cnt > (1ll << 28)) e_cnt = 1ll << 28;
-  const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(pcm.p + e_base), 0, static_cast<int>(e_cnt * 4), 0x00020000);
+  const PcmTile a_tile = pcm_tile(pcm, frame_begin, m0, pcm.ch);
+  const __amdgpu_buffer_rsrc_t a_rsrc = a_tile.rsrc;
 
   // per-row loader: lane -> (row a_r of the tile, i = a_i + 4 j)
   const int a_r = tid % BM;
   const int a_i = tid / BM;
   unsigned a_off[kSeg ? kPieces : 1];
 #pragma unroll
-  for (int p = 0; p < (kSeg ? kPieces : 1); ++p) a_off[p] = 0x80000000u;
+  for (int p = 0; p < (kSeg ? kPieces : 1); ++p) a_off[p] = kPcmNoRow;
   const unsigned a_step = static_cast<unsigned>(kIGroups * ch * 4);
   const unsigned i_bytes = static_cast<unsigned>(ch * 4);
   // segment loader: (lane, p) -> (frame seg_fl + p * kSegStep of the tile, 4 consecutive floats of its BK x CH segment)
@@ -219,7 +210,7 @@ __global__ __launch_bounds__(256) void k_mdct_fwd_row(DeviceTables tb, PcmView p
       if (row0 < M) {
         const long long f = frame_begin + row0 / CH;
         const long long e_row = (f * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * CH;
-        a_off[p] = static_cast<unsigned>((e_row - e_base + seg_o) * 4);
+        a_off[p] = static_cast<unsigned>((e_row - a_tile.e_base + seg_o) * 4);
       }
     }
   } else {
@@ -228,7 +219,7 @@ __global__ __launch_bounds__(256) void k_mdct_fwd_row(DeviceTables tb, PcmView p
       const long long f = frame_begin + a_row / pcm.ch;
       const long long c = a_row % pcm.ch;
       const long long e_row = (f * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * ch + c;
-      a_off[0] = static_cast<unsigned>((e_row - e_base + a_i * ch) * 4);
+      a_off[0] = static_cast<unsigned>((e_row - a_tile.e_base + a_i * ch) * 4);
     }
   }
 
@@ -404,17 +395,8 @@ __global__ __launch_bounds__(256) void k_mdct_fwd_row8(DeviceTables tb, PcmView 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63;
   const long long ch = pcm.ch;
-  const long long f0 = frame_begin + m0 / pcm.ch;
-  const long long e_first = (f0 * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * ch;
-  long long e_end = static_cast<long long>(pcm.t_count) * ch;
-  const long long n_rel = static_cast<long long>(pcm.n_samples) - static_cast<long long>(pcm.t0) * ch;
-  if (e_end > n_rel) e_end = n_rel;
-  const long long e_base = e_first < 0 ? 0 : e_first;
-  long long e_cnt = e_end - e_base;
-  if (e_cnt < 0) e_cnt = 0;
-  if (e_cnt > (1ll << 28)) e_cnt = 1ll << 28;
-  const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(pcm.p + e_base), 0, static_cast<int>(e_cnt * 4), 0x00020000);
+  const PcmTile a_tile = pcm_tile(pcm, frame_begin, m0, pcm.ch);
+  const __amdgpu_buffer_rsrc_t a_rsrc = a_tile.rsrc;
   unsigned a_off[kPieces];
   const unsigned i_bytes = static_cast<unsigned>(ch * 4);
   constexpr int kSegLanes = BK / 4 * CH;
@@ -423,12 +405,12 @@ __global__ __launch_bounds__(256) void k_mdct_fwd_row8(DeviceTables tb, PcmView 
   const int seg_o = (tid % kSegLanes) * 4;
 #pragma unroll
   for (int p = 0; p < kPieces; ++p) {
-    a_off[p] = 0x80000000u;
+    a_off[p] = kPcmNoRow;
     const unsigned row0 = m0 + (seg_fl + p * kSegStep) * CH;
     if (row0 < M) {
       const long long f = frame_begin + row0 / CH;
       const long long e_row = (f * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * CH;
-      a_off[p] = static_cast<unsigned>((e_row - e_base + seg_o) * 4);
+      a_off[p] = static_cast<unsigned>((e_row - a_tile.e_base + seg_o) * 4);
     }
   }
   constexpr int kWin = CH == 1 ? 4 : CH == 2 ? 2 : 1;

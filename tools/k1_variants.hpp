@@ -34,9 +34,16 @@
 #include <hip/hip_runtime.h>
 
 #include "glc_kernels.h"
+#include "glc_mdct_fwd.hpp"  // the PCM tile helpers the variants share with the shipped kernels
 
 namespace glc {
 namespace k1x {
+
+using k1::PcmTile;
+using k1::kPcmNoRow;
+using k1::pcm_row_origin;
+using k1::pcm_tile;
+using k1::xcd_tile;
 
 constexpr int kHopI = 1024;
 constexpr int kFrameI = 2048;
@@ -82,34 +89,16 @@ __global__ __launch_bounds__((BM / TM) * (BN / TN), MINW) void k_mdct_fwd(Device
   const int n0 = n_tile * BN;
   const int tx = tid % C::kNtx, ty = tid / C::kNtx;
 
-  // --- A operand: interleaved PCM read through a buffer descriptor whose hardware range check
-  // supplies the encoder's zero padding (512 leading zeros, tail, shard edges): an element
-  // before the descriptor base wraps to a huge unsigned offset, one past the end is >= the
-  // record count; both load 0.0.  All descriptor inputs are blockIdx/kernarg scalars.
+  // --- A operand (glc_mdct_fwd.hpp pcm_tile: the descriptor whose range check is the zero padding)
   const long long ch = pcm.ch;
-  const long long f0 = frame_begin + m0 / pcm.ch;  // first frame of the tile
-  const long long e_first = (f0 * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * ch;
-  long long e_end = static_cast<long long>(pcm.t_count) * ch;  // shard end (elements)
-  const long long n_rel = static_cast<long long>(pcm.n_samples) - static_cast<long long>(pcm.t0) * ch;
-  if (e_end > n_rel) e_end = n_rel;  // stream end
-  const long long e_base = e_first < 0 ? 0 : e_first;
-  long long e_cnt = e_end - e_base;
-  if (e_cnt < 0) e_cnt = 0;
-  if (e_cnt > (1ll << 28)) e_cnt = 1ll << 28;
-  const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(pcm.p + e_base), 0, static_cast<int>(e_cnt * 4), 0x00020000);
+  const PcmTile a_tile = pcm_tile(pcm, frame_begin, m0, pcm.ch);
+  const __amdgpu_buffer_rsrc_t a_rsrc = a_tile.rsrc;
 
   // this thread stages ONE row (r = tid % BM) and kAPer of the BK i of a stage
   const int a_r = tid % BM;
   const int a_i = tid / BM;
-  const unsigned a_row = m0 + a_r;
-  unsigned a_off = 0x80000000u;  // out-of-range row: every load returns 0
-  if (a_row < M) {
-    const long long f = frame_begin + a_row / pcm.ch;
-    const long long c = a_row % pcm.ch;
-    const long long e_row = (f * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * ch + c;
-    a_off = static_cast<unsigned>((e_row - e_base + a_i * ch) * 4);  // may wrap: that IS the padding
-  }
+  unsigned a_off = kPcmNoRow;
+  pcm_row_origin(a_off, pcm, a_tile, frame_begin, m0 + a_r, M, pcm.ch, a_i);
   const unsigned a_step = static_cast<unsigned>(C::kAStride * ch * 4);  // bytes between this thread's i's
   const float *w_ptr = tb.window + a_i;
   // B operand: float4 (row = idx / (BN/4), col4 = idx % (BN/4)), idx = tid + kThreads j
@@ -441,13 +430,8 @@ void k_mdct_fwd_sched(DeviceTables tb, PcmView pcm, long long frame_begin, unsig
   const int tid = threadIdx.x;
   if (WLDS)
     for (int i = tid; i < kFrameI; i += C::kThreads) Ws[i] = tb.window[i];
-  // Workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8 says which blocks share an
-  // L2).  Give XCD x the contiguous tile range [x*T/8, (x+1)*T/8) in (m_tile, n_tile) order: the
-  // PCM rows of an m-tile are then fetched by ONE XCD instead of all eight, and the table rows of
-  // a stage are shared in that XCD's L2 by all resident m-tiles, which sweep i together
-  // (measured: 4x less L2 fill traffic).  Placement affects speed only, never results.
   static_assert(C::kNTiles == 8, "tile map assumes 8 coefficient tiles");
-  const unsigned g = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  const unsigned g = xcd_tile();  // XCD-aware tile map (glc_mdct_fwd.hpp)
   const int n_tile = g % C::kNTiles;
   const int m_tile = g / C::kNTiles;
   const int m0 = m_tile * BM;
@@ -455,28 +439,13 @@ void k_mdct_fwd_sched(DeviceTables tb, PcmView pcm, long long frame_begin, unsig
   const int tx = tid % C::kNtx, ty = tid / C::kNtx;
 
   const long long ch = pcm.ch;
-  const long long f0 = frame_begin + m0 / pcm.ch;
-  const long long e_first = (f0 * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * ch;
-  long long e_end = static_cast<long long>(pcm.t_count) * ch;
-  const long long n_rel = static_cast<long long>(pcm.n_samples) - static_cast<long long>(pcm.t0) * ch;
-  if (e_end > n_rel) e_end = n_rel;
-  const long long e_base = e_first < 0 ? 0 : e_first;
-  long long e_cnt = e_end - e_base;
-  if (e_cnt < 0) e_cnt = 0;
-  if (e_cnt > (1ll << 28)) e_cnt = 1ll << 28;
-  const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(pcm.p + e_base), 0, static_cast<int>(e_cnt * 4), 0x00020000);
+  const PcmTile a_tile = pcm_tile(pcm, frame_begin, m0, pcm.ch);
+  const __amdgpu_buffer_rsrc_t a_rsrc = a_tile.rsrc;
 
   const int a_r = tid % BM;
   const int a_i = tid / BM;
-  const unsigned a_row = m0 + a_r;
-  unsigned a_off = 0x80000000u;
-  if (a_row < M) {
-    const long long f = frame_begin + a_row / pcm.ch;
-    const long long c = a_row % pcm.ch;
-    const long long e_row = (f * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * ch + c;
-    a_off = static_cast<unsigned>((e_row - e_base + a_i * ch) * 4);
-  }
+  unsigned a_off = kPcmNoRow;
+  pcm_row_origin(a_off, pcm, a_tile, frame_begin, m0 + a_r, M, pcm.ch, a_i);
   const unsigned a_step = static_cast<unsigned>(C::kAStride * ch * 4);
   const float *w_ptr = tb.window + a_i;
   const int b_r = tid / (BN / 4), b_c4 = tid % (BN / 4);
@@ -664,7 +633,7 @@ void k_mdct_fwd_dma(DeviceTables tb, PcmView pcm, long long frame_begin, unsigne
   __shared__ __attribute__((aligned(16))) float Ws[kWinLds ? kFrameI : 4];
 
   const int tid = threadIdx.x;
-  const unsigned g = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);  // XCD-aware tile map
+  const unsigned g = xcd_tile();  // XCD-aware tile map
   const int n_tile = g % 8;
   const int m_tile = g / 8;
   const int m0 = m_tile * BM;
@@ -682,29 +651,14 @@ void k_mdct_fwd_dma(DeviceTables tb, PcmView pcm, long long frame_begin, unsigne
     for (int i = tid; i < kFrameI; i += kThreads) Ws[i] = tb.window[i];
 
   const long long ch = pcm.ch;
-  const long long f0 = frame_begin + m0 / pcm.ch;
-  const long long e_first = (f0 * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * ch;
-  long long e_end = static_cast<long long>(pcm.t_count) * ch;
-  const long long n_rel = static_cast<long long>(pcm.n_samples) - static_cast<long long>(pcm.t0) * ch;
-  if (e_end > n_rel) e_end = n_rel;
-  const long long e_base = e_first < 0 ? 0 : e_first;
-  long long e_cnt = e_end - e_base;
-  if (e_cnt < 0) e_cnt = 0;
-  if (e_cnt > (1ll << 28)) e_cnt = 1ll << 28;
-  const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(pcm.p + e_base), 0, static_cast<int>(e_cnt * 4), 0x00020000);
+  const PcmTile a_tile = pcm_tile(pcm, frame_begin, m0, pcm.ch);
+  const __amdgpu_buffer_rsrc_t a_rsrc = a_tile.rsrc;
 
   const int a_r = tid % BM;
   const int a_i = tid / BM;  // 0..3: i = a_i + 4 j  (the same for every lane of a wave)
   const int a_i_s = __builtin_amdgcn_readfirstlane(a_i);
-  const unsigned a_row = m0 + a_r;
-  unsigned a_off = 0x80000000u;
-  if (a_row < M) {
-    const long long f = frame_begin + a_row / pcm.ch;
-    const long long c = a_row % pcm.ch;
-    const long long e_row = (f * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * ch + c;
-    a_off = static_cast<unsigned>((e_row - e_base + a_i * ch) * 4);
-  }
+  unsigned a_off = kPcmNoRow;
+  pcm_row_origin(a_off, pcm, a_tile, frame_begin, m0 + a_r, M, pcm.ch, a_i);
   const unsigned a_step = static_cast<unsigned>(kAStride * ch * 4);
   const unsigned i_bytes = static_cast<unsigned>(ch * 4);
   // segment loader: lane -> (frame of the tile, 4 consecutive floats of its 16 x CH segment)
@@ -713,11 +667,11 @@ void k_mdct_fwd_dma(DeviceTables tb, PcmView pcm, long long frame_begin, unsigne
   const int seg_o = (tid % (4 * kSegCh)) * 4;  // first float of this lane inside the segment
   if constexpr (kSeg) {
     const unsigned row0 = m0 + seg_fl * CH;
-    a_off = 0x80000000u;
+    a_off = kPcmNoRow;
     if (row0 < M) {
       const long long f = frame_begin + row0 / CH;
       const long long e_row = (f * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * CH;
-      a_off = static_cast<unsigned>((e_row - e_base + seg_o) * 4);
+      a_off = static_cast<unsigned>((e_row - a_tile.e_base + seg_o) * 4);
     }
   }
   // table DMA: instruction d of wave w copies rows 2(d*kWaves + w), +1 of the stage's 16 x 128
@@ -909,33 +863,18 @@ __global__ __launch_bounds__(256, MINW) void k_mdct_fwd_mx(DeviceTables tb, PcmV
   __shared__ __attribute__((aligned(16))) float Bs[2][BK * BN];
 
   const int tid = threadIdx.x;
-  const unsigned g = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);  // XCD-aware tile map
+  const unsigned g = xcd_tile();  // XCD-aware tile map
   const int n_tile = g % 8, m_tile = g / 8;
   const int m0 = m_tile * BM, n0 = n_tile * BN;
   const int wave = tid >> 6, lane = tid & 63;
   const int r0 = (wave >> 1) * 64, c0 = (wave & 1) * 64;
 
   const long long ch = pcm.ch;
-  const long long f0 = frame_begin + m0 / pcm.ch;
-  const long long e_first = (f0 * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * ch;
-  long long e_end = static_cast<long long>(pcm.t_count) * ch;
-  const long long n_rel = static_cast<long long>(pcm.n_samples) - static_cast<long long>(pcm.t0) * ch;
-  if (e_end > n_rel) e_end = n_rel;
-  const long long e_base = e_first < 0 ? 0 : e_first;
-  long long e_cnt = e_end - e_base;
-  if (e_cnt < 0) e_cnt = 0;
-  if (e_cnt > (1ll << 28)) e_cnt = 1ll << 28;
-  const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(pcm.p + e_base), 0, static_cast<int>(e_cnt * 4), 0x00020000);
+  const PcmTile a_tile = pcm_tile(pcm, frame_begin, m0, pcm.ch);
+  const __amdgpu_buffer_rsrc_t a_rsrc = a_tile.rsrc;
   const int a_r = tid % BM, a_i = tid / BM;
-  const unsigned a_row = m0 + a_r;
-  unsigned a_off = 0x80000000u;
-  if (a_row < M) {
-    const long long f = frame_begin + a_row / pcm.ch;
-    const long long c = a_row % pcm.ch;
-    const long long e_row = (f * kHopI - kHopI / 2 - static_cast<long long>(pcm.t0)) * ch + c;
-    a_off = static_cast<unsigned>((e_row - e_base + a_i * ch) * 4);
-  }
+  unsigned a_off = kPcmNoRow;
+  pcm_row_origin(a_off, pcm, a_tile, frame_begin, m0 + a_r, M, pcm.ch, a_i);
   const unsigned a_step = static_cast<unsigned>(kAStride * ch * 4);
   const float *w_ptr = tb.window + a_i;
   const int b_r = tid / (BN / 4), b_c4 = tid % (BN / 4);
