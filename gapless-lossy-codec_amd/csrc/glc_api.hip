@@ -7,16 +7,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
-#include <condition_variable>
 #include <functional>
 #include <cstdio>
 #include <memory>
 #include <mutex>
 #include <new>
 #include <string>
-#include <system_error>
-#include <thread>
 #include <cstdlib>
 #include <vector>
 
@@ -26,6 +22,7 @@
 #include "glc_kernels.h"
 #include "glc_resources.hpp"
 #include "glc_rounds.hpp"
+#include "glc_stages.hpp"
 
 namespace glc {
 
@@ -38,52 +35,6 @@ void set_global_error(const std::string &msg) {
 }
 
 }  // namespace glc
-
-// A parked host thread that runs one job at a time (glc_encode's uploader and launcher): started on
-// first use and kept for the life of the context, because a fresh std::thread costs ~50 us before its
-// first HIP call returns (thread start + the runtime's per-thread state) - 5 % of a config-2 call.
-struct Worker {
-  std::thread th;
-  std::mutex mu;
-  std::condition_variable cv;
-  std::function<void()> job;
-  bool has_job = false, idle = true, quit = false;
-  void submit(std::function<void()> j) {  // may throw std::system_error / std::bad_alloc on first use
-    if (!th.joinable())
-      th = std::thread([this] {
-        std::unique_lock<std::mutex> lk(mu);
-        for (;;) {
-          cv.wait(lk, [&] { return has_job || quit; });
-          if (quit) return;
-          std::function<void()> j2 = std::move(job);
-          has_job = false;
-          lk.unlock();
-          j2();  // jobs do not throw (glc_encode wraps them)
-          lk.lock();
-          idle = true;
-          cv.notify_all();
-        }
-      });
-    std::lock_guard<std::mutex> lk(mu);
-    job = std::move(j);
-    has_job = true;
-    idle = false;
-    cv.notify_all();
-  }
-  void wait() {
-    std::unique_lock<std::mutex> lk(mu);
-    cv.wait(lk, [&] { return idle; });
-  }
-  ~Worker() {
-    if (!th.joinable()) return;
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      quit = true;
-      cv.notify_all();
-    }
-    th.join();
-  }
-};
 
 // The tables of a batch call: written into the context's pinned image (rtb_stage), sent up to rtb_tab in ONE copy with
 // rtb_ev recorded behind it.  The image is shared by every such call of the context and may still be on its way up for
@@ -200,7 +151,7 @@ struct glc_ctx {
   Event ev_dec[2];               // decode: "kernels of the chunk in buffer b are done"
   Event rtb_ev;                  // recorded behind the upload of rtb_stage: the next call waits for it before it rewrites the image
   // ---- threads ----
-  std::unique_ptr<Worker> enc_up, enc_launch;  // glc_encode's helper threads (multi-round streams only)
+  Worker enc_up, enc_launch;     // the helper threads of glc_encode* and glc_roundtrip: started by the first multi-round stream
 };
 
 namespace {
@@ -268,6 +219,43 @@ int on_device(glc_ctx *ctx, const std::string &w, Body body) {
 }
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// The counters of a StageGate (glc_stages.hpp): rounds whose samples are on the device / whose records event has been recorded.
+enum { kUploaded, kQueued };
+
+// THE uploader stage of glc_encode* and glc_roundtrip: for every round i of n_rounds, what of the stream `pcm` lies
+// between the mark of the round before and its own, mark_of(i) (glc::upload_mark), goes up on `st`, back to back, and
+// the round is reported to the gate as `counter`.  Floats (GLC_PCM_F32) go straight into d_pcm.  Integer samples go
+// up as they are, 2 or 4 bytes each, into d_int, and the round's increment is widened into d_pcm behind its copy: the
+// next stage finds the same floats as after a float upload.
+// host_wait: the stage waits for `st` before it reports - a copy from pageable memory has completed when the call
+// returns; should the runtime ever queue it instead, this is where it is waited for (the next stage queues nothing
+// behind it).  Without it the caller's kernels follow on `st` itself.  Ends early once another stage has failed or the
+// consumer has stopped; a failure of its own is "<who>: upload: <hip error string>" in the gate.
+template <typename MarkOf>
+void upload_rounds(glc_ctx *ctx, const char *who, StageGate &gate, int counter, size_t n_rounds, MarkOf mark_of,
+                   const void *pcm, glc_pcm_format fmt, uint32_t bits, float *d_pcm, uint8_t *d_int, hipStream_t st, bool host_wait) {
+  DeviceGuard g(ctx->device);
+  const uint8_t *h = static_cast<const uint8_t *>(pcm);
+  const bool is_int = fmt != GLC_PCM_F32;
+  const size_t elem = pcm_elem(fmt);
+  uint64_t copied = 0;
+  for (size_t i = 0; i < n_rounds; ++i) {
+    const uint64_t hi = mark_of(i);
+    hipError_t e = hipSuccess;
+    if (hi > copied) {
+      void *dst = is_int ? static_cast<void *>(d_int + copied * elem) : d_pcm + copied;
+      e = hipMemcpyAsync(dst, h + copied * elem, (hi - copied) * elem, hipMemcpyHostToDevice, st);
+      if (e == hipSuccess && is_int)
+        e = glc::launch_pcm_widen(dst, fmt == GLC_PCM_S32, bits, hi - copied, d_pcm + copied, st);
+      copied = hi;
+    }
+    if (e == hipSuccess && host_wait) e = hipStreamSynchronize(st);
+    if (e != hipSuccess)
+      return gate.set_error(e == hipErrorOutOfMemory ? GLC_ENOMEM : GLC_EHIP, std::string(who) + ": upload: " + hipGetErrorString(e));
+    if (!gate.advance(counter)) return;
+  }
+}
 
 }  // namespace
 
@@ -832,10 +820,7 @@ int glc_pcm_widen_device(glc_ctx *ctx, const void *d_in, glc_pcm_format fmt, uin
 static int encode_pipeline(glc_ctx *ctx, const void *pcm_any, glc_pcm_format fmt, uint32_t bits, uint64_t n_samples,
                            uint16_t channels, glc_frames_hook hook, void *hook_user, glc_frames **out) {
   if (!ctx || !pcm_any || (!out && !hook)) return fail(ctx, GLC_EINVAL, "glc_encode: null argument");
-  const float *pcm = static_cast<const float *>(pcm_any);          // GLC_PCM_F32
-  const uint8_t *pcm_int = static_cast<const uint8_t *>(pcm_any);  // the integer formats
   const bool is_int = fmt != GLC_PCM_F32;
-  const size_t elem = pcm_elem(fmt);
   if (out) *out = nullptr;
   const glc_plan plan = glc::plan_encode(n_samples, channels);
   if (plan.n_frames == 0)
@@ -846,35 +831,9 @@ static int encode_pipeline(glc_ctx *ctx, const void *pcm_any, glc_pcm_format fmt
   const uint32_t ch = channels;
   const uint64_t rec = glc::record_bytes(ch);
   const uint64_t t_count = (n_samples + ch - 1) / ch;
-  // A pipeline over rounds of at most kEncodeChunkFrames frames.  Every stage has its own stream AND
-  // its own host thread, because two of the stages block their caller: a copy from or to pageable
-  // memory returns when it is done.
-  //   uploader thread   round i+1's samples go up, back to back                      (copy_stream)
-  //   launcher thread   round i is transformed and quantised as soon as it is up     (stream / stream_b)
-  //   this thread       round i-1 is compacted, its blob comes down - metadata, then the payload
-  //                     straight into the EncodedAudio's pools - and is indexed       (down_stream)
-  // PCIe is full duplex and the compaction kernels are small, so a call costs
-  // max(upload, kernels) + the first upload + the last round's compaction and download instead of
-  // their sum.  One rule keeps the stages from blocking each other: NOTHING IS QUEUED BEHIND AN
-  // UNFINISHED DEPENDENCY.  A process has a handful of hardware queues for all its streams, and a
-  // queue is in order: a `hipStreamWaitEvent` that has to wait parks every stream that shares its
-  // queue (seen in the trace: the compaction's wait for the quantiser held the NEXT upload's event
-  // back, and with it the next transform), and the copy engines execute in submission order.  So a
-  // stage waits on the host (thread hand-off, hipEventSynchronize) and only then queues its work.
-  // Rounds: the upload nothing hides is the first round's, and the kernels nothing hides are the last
-  // round's, so a stream opens with four rounds of 2048 rows (0.15 ms of PCIe each for stereo) before
-  // it goes on in rounds of kEncodeChunkFrames.  A 2048-row launch alone leaves the chip half empty
-  // (its time is one workgroup's 2048-step chain, 0.22 ms whatever the row count), so consecutive
-  // rounds run on TWO streams with a coefficient workspace each: the next round's transform fills in
-  // beside this one's, and a round's quantiser runs beside the next transform (four 1024-frame stereo
-  // launches: 0.87 ms on one stream, 0.67 ms alternating, 0.59 ms as one launch; two 2048-frame ones
-  // 0.66 / 0.60).  BASELINE config 2 (4096 stereo frames) is the four opening rounds; a stream of
-  // one round runs on this thread alone.
-  // (at most 2048 rows: the size the round kernel of launch_mdct_forward - `beside` - is dealt one workgroup per CU for)
-  const uint64_t piece = std::max<uint64_t>(1, 2048 / ch);  // frames of an opening round
-  const uint64_t opening = 4 * piece;
+  // the rounds of the stream (glc_rounds.hpp), where each round's blob lands and what must be up before it runs
   struct Round {
-    uint64_t f0, nf, blob_off, hi;  // hi: interleaved samples that must be on the device before its kernels run
+    uint64_t f0, nf, blob_off, hi;  // hi: its upload mark
     glc::CompactLayout l;
   };
   std::vector<Round> rounds;
@@ -882,17 +841,10 @@ static int encode_pipeline(glc_ctx *ctx, const void *pcm_any, glc_pcm_format fmt
   uint64_t max_nf = 0;
   try {
     uint64_t blob_off = 0;
-    for (uint64_t f = 0, nf = 0; f < plan.n_frames; f += nf) {
-      const uint64_t left = plan.n_frames - f;
-      nf = std::min<uint64_t>(f < opening ? piece : encode_chunk_frames(ch), left);
-      if (left - nf < piece / 2) nf = left;  // no round for a remainder of less than half a piece
-      // (Measured and dropped, round 3: cutting the END of a stream in halves - .. 2048, 1024, 512, 512 frames -
-      // so that the last, unhidden transform is a short one: 1.045 ms against 1.02 at config 2; a round
-      // costs the launcher and the collector more than the shorter tail returns.)
-      const uint64_t hi_t = glc::frame_sample_window(f, f + nf, plan.per_channel).hi;
-      Round r{f, nf, blob_off, std::min<uint64_t>(n_samples, hi_t * ch), glc::compact_layout(ch, nf)};
+    for (const StreamRound &sr : encode_stream_rounds(plan.n_frames, ch, encode_chunk_frames(ch))) {
+      Round r{sr.f0, sr.nf, blob_off, glc::upload_mark(sr.f0, sr.nf, plan.per_channel, ch, n_samples), glc::compact_layout(ch, sr.nf)};
       blob_off += align_up(r.l.bound, 256);
-      max_nf = std::max(max_nf, nf);
+      max_nf = std::max(max_nf, sr.nf);
       rounds.push_back(r);
     }
     F.reset(new glc_frames);
@@ -905,7 +857,7 @@ static int encode_pipeline(glc_ctx *ctx, const void *pcm_any, glc_pcm_format fmt
   const size_t stage_cap = std::max<size_t>(std::min<size_t>(align_up(glc::compact_layout(ch, max_nf).bound, 256), size_t(64) << 20),
                                             align_up(glc::compact_layout(ch, max_nf).o_pairs, 256));
   GLC_HIP(ctx, ctx->pcm.reserve(static_cast<size_t>(t_count) * ch * sizeof(float)));
-  if (is_int) GLC_HIP(ctx, ctx->pcm_int.reserve(static_cast<size_t>(t_count) * ch * elem));
+  if (is_int) GLC_HIP(ctx, ctx->pcm_int.reserve(static_cast<size_t>(t_count) * ch * pcm_elem(fmt)));
   GLC_HIP(ctx, ctx->records.reserve(static_cast<size_t>(plan.n_frames) * rec));
   GLC_HIP(ctx, ctx->pack_blob.reserve(rounds.back().blob_off + align_up(rounds.back().l.bound, 256)));
   GLC_HIP(ctx, ctx->host_stage.reserve(stage_cap));
@@ -930,60 +882,17 @@ static int encode_pipeline(glc_ctx *ctx, const void *pcm_any, glc_pcm_format fmt
   uint8_t *d_blob = static_cast<uint8_t *>(ctx->pack_blob.p);
   const Event *ev_rec = ctx->ev_round.data();
 
-  // progress shared by the three threads; an error anywhere stops all of them
-  struct Progress {
-    std::mutex mu;
-    std::condition_variable cv;
-    size_t uploaded = 0, queued = 0;  // rounds whose samples are on the device / whose records event has been recorded
-    int rc = GLC_OK;
-    std::string msg;
-    void set_error(int code, const std::string &m) {
-      std::lock_guard<std::mutex> lk(mu);
-      if (rc == GLC_OK) rc = code, msg = m;
-      cv.notify_all();
-    }
-    // wait until *counter > i; false when another stage has failed
-    bool wait_for(const size_t &counter, size_t i) {
-      std::unique_lock<std::mutex> lk(mu);
-      cv.wait(lk, [&] { return counter > i || rc != GLC_OK; });
-      return rc == GLC_OK;
-    }
-    void advance(size_t &counter) {
-      std::lock_guard<std::mutex> lk(mu);
-      ++counter;
-      cv.notify_all();
-    }
-  } prog;
+  // what the three threads meet at (kUploaded, kQueued)
+  StageGate prog;
   auto hip_msg = [](const char *what, hipError_t e) { return std::string(what) + ": " + hipGetErrorString(e); };
   double pairs_per_frame = 0.0;  // stored pairs per frame so far, + 25 % (sizes the next round's first copy)
 
-  // Integer samples go up as they are, 2 or 4 bytes each, and the round's increment is widened into
-  // d_pcm behind its copy: the launcher finds the same floats as after a float upload.  A stream of a
-  // single round has nothing to run ahead of: its copy and its widening are queued on the stream the
-  // round's kernels follow on, and nobody waits for them on the host.
-  uint8_t *d_int = static_cast<uint8_t *>(ctx->pcm_int.p);
-  hipStream_t up_stream = is_int && n_rounds == 1 ? ctx->stream : ctx->copy_stream;
+  // A stream of a single round has nothing to run ahead of: integer samples have their copy and their widening
+  // queued on the stream the round's kernels follow on, and nobody waits for them on the host.
+  const bool up_in_order = is_int && n_rounds == 1;
   auto upload = [&] {  // stage 1
-    DeviceGuard g(ctx->device);
-    uint64_t copied = 0;
-    for (size_t i = 0; i < n_rounds; ++i) {
-      const Round &r = rounds[i];
-      hipError_t e = hipSuccess;
-      if (r.hi > copied && !is_int)
-        e = hipMemcpyAsync(d_pcm + copied, pcm + copied, (r.hi - copied) * sizeof(float), hipMemcpyHostToDevice, ctx->copy_stream);
-      if (r.hi > copied && is_int) {
-        e = hipMemcpyAsync(d_int + copied * elem, pcm_int + copied * elem, (r.hi - copied) * elem, hipMemcpyHostToDevice, up_stream);
-        if (e == hipSuccess)
-          e = glc::launch_pcm_widen(d_int + copied * elem, fmt == GLC_PCM_S32, bits, r.hi - copied, d_pcm + copied, up_stream);
-      }
-      copied = std::max(copied, r.hi);
-      // a copy from pageable memory has completed when the call returns; should the runtime ever
-      // queue it instead, this is where it is waited for (the launcher queues nothing behind it)
-      if (e == hipSuccess && up_stream == ctx->copy_stream) e = hipStreamSynchronize(ctx->copy_stream);
-      if (e != hipSuccess) return prog.set_error(e == hipErrorOutOfMemory ? GLC_ENOMEM : GLC_EHIP, hip_msg("glc_encode: upload", e));
-      prog.advance(prog.uploaded);
-      { std::lock_guard<std::mutex> lk(prog.mu); if (prog.rc != GLC_OK) return; }
-    }
+    upload_rounds(ctx, "glc_encode", prog, kUploaded, n_rounds, [&](size_t i) { return rounds[i].hi; }, pcm_any, fmt, bits, d_pcm,
+                  static_cast<uint8_t *>(ctx->pcm_int.p), up_in_order ? ctx->stream : ctx->copy_stream, !up_in_order);
   };
   auto launch = [&] {  // stage 2
     std::string my_err;  // failures of this stage land here, not in ctx->err (another thread's to write)
@@ -991,7 +900,7 @@ static int encode_pipeline(glc_ctx *ctx, const void *pcm_any, glc_pcm_format fmt
     DeviceGuard g(ctx->device);
     for (size_t i = 0; i < n_rounds; ++i) {
       const Round &r = rounds[i];
-      if (!prog.wait_for(prog.uploaded, i)) return;
+      if (!prog.wait_for(kUploaded, i)) return;
       hipStream_t cs = (i & 1) ? ctx->stream_b : ctx->stream;
       hipError_t e = hipSuccess;
       uint8_t *recs = static_cast<uint8_t *>(ctx->records.p) + r.f0 * rec;
@@ -1000,7 +909,7 @@ static int encode_pipeline(glc_ctx *ctx, const void *pcm_any, glc_pcm_format fmt
       if (rc != GLC_OK) return prog.set_error(rc, my_err);
       e = hipEventRecord(ev_rec[i], cs);
       if (e != hipSuccess) return prog.set_error(GLC_EHIP, hip_msg("glc_encode: queueing a round", e));
-      prog.advance(prog.queued);
+      prog.advance(kQueued);
     }
   };
   uint64_t p_used = 0, r_used = 0;  // the pools are grown ahead of need (below): what of them is filled
@@ -1047,17 +956,12 @@ static int encode_pipeline(glc_ctx *ctx, const void *pcm_any, glc_pcm_format fmt
       }
       if (hook) {  // hand out finished frames while this round's records are not ready
         while (delivered < complete) {
-          bool ready;
-          {
-            std::lock_guard<std::mutex> lk(prog.mu);
-            if (prog.rc != GLC_OK) return;
-            ready = prog.queued > i;
-          }
-          if (ready && hipEventQuery(ev_rec[i]) == hipSuccess) break;
+          if (prog.failed()) return;
+          if (prog.passed(kQueued, i) && hipEventQuery(ev_rec[i]) == hipSuccess) break;
           if (!deliver(std::min(complete, delivered + kHookSlice))) return;
         }
       }
-      if (!prog.wait_for(prog.queued, i)) return;
+      if (!prog.wait_for(kQueued, i)) return;
       hipError_t e = hipEventSynchronize(ev_rec[i]);  // the round's records are written: compact them now
       if (e != hipSuccess) return prog.set_error(GLC_EHIP, hip_msg("glc_encode: waiting for a round", e));
       // pairs the round is expected to hold, from the density of the stream so far (+ 25 %)
@@ -1078,63 +982,38 @@ static int encode_pipeline(glc_ctx *ctx, const void *pcm_any, glc_pcm_format fmt
     if (hook && delivered < complete) (void)deliver(complete);
   };
 
-  int rc = GLC_OK;
-  std::string msg;
-  try {
-    if (n_rounds == 1) {
-      upload();
-      launch();
-      collect();
-    } else {
-      if (!ctx->enc_up) ctx->enc_up.reset(new Worker);
-      if (!ctx->enc_launch) ctx->enc_launch.reset(new Worker);
-      auto guarded = [&prog](const std::function<void()> &f) {
-        return [&prog, f] {
-          try {
-            f();
-          } catch (...) {
-            try {
-              prog.set_error(GLC_ENOMEM, "glc_encode: host allocation failed");
-            } catch (...) {
-            }
-          }
-        };
-      };
-      int started = 0;
-      try {
-        ctx->enc_up->submit(guarded(upload));
-        started = 1;
-        ctx->enc_launch->submit(guarded(launch));
-        started = 2;
-      } catch (...) {  // a helper could not be started: stop the others, report
-        prog.set_error(GLC_ENOMEM, "glc_encode: cannot start a helper thread");
-        if (started >= 1) ctx->enc_up->wait();
-        if (started >= 2) ctx->enc_launch->wait();
-        throw;
-      }
-      try {
-        collect();
-      } catch (...) {
-        prog.set_error(GLC_ENOMEM, "glc_encode: host allocation failed");
-      }
-      ctx->enc_up->wait();
-      ctx->enc_launch->wait();
-    }
-    std::lock_guard<std::mutex> lk(prog.mu);
-    rc = prog.rc;
-    msg = prog.msg;
-  } catch (const std::bad_alloc &) {
-    rc = GLC_ENOMEM, msg = "glc_encode: host allocation failed";
-  } catch (...) {  // std::system_error from starting a helper thread; nothing may cross the C ABI
-    rc = GLC_ENOMEM, msg = "glc_encode: cannot start a helper thread";
-  }
-  if (rc != GLC_OK) {
+  // A pipeline over rounds of at most kEncodeChunkFrames frames.  Every stage has its own stream AND
+  // its own host thread, because two of the stages block their caller: a copy from or to pageable
+  // memory returns when it is done.
+  //   uploader thread   round i+1's samples go up, back to back                      (copy_stream)
+  //   launcher thread   round i is transformed and quantised as soon as it is up     (stream / stream_b)
+  //   this thread       round i-1 is compacted, its blob comes down - metadata, then the payload
+  //                     straight into the EncodedAudio's pools - and is indexed       (down_stream)
+  // PCIe is full duplex and the compaction kernels are small, so a call costs
+  // max(upload, kernels) + the first upload + the last round's compaction and download instead of
+  // their sum.  One rule keeps the stages from blocking each other: NOTHING IS QUEUED BEHIND AN
+  // UNFINISHED DEPENDENCY.  A process has a handful of hardware queues for all its streams, and a
+  // queue is in order: a `hipStreamWaitEvent` that has to wait parks every stream that shares its
+  // queue (seen in the trace: the compaction's wait for the quantiser held the NEXT upload's event
+  // back, and with it the next transform), and the copy engines execute in submission order.  So a
+  // stage waits on the host (the gate, hipEventSynchronize) and only then queues its work.
+  // An opening round's 2048-row launch alone leaves the chip half empty (its time is one workgroup's
+  // 2048-step chain, 0.22 ms whatever the row count), so consecutive rounds run on TWO streams with
+  // a coefficient workspace each: the next round's transform fills in beside this one's, and a
+  // round's quantiser runs beside the next transform (four 1024-frame stereo launches: 0.87 ms on
+  // one stream, 0.67 ms alternating, 0.59 ms as one launch; two 2048-frame ones 0.66 / 0.60).
+  // A stream of one round runs on this thread alone.
+  if (n_rounds == 1)
+    run_stages(prog, "glc_encode", {}, [&] { upload(), launch(), collect(); });
+  else
+    run_stages(prog, "glc_encode", {{ctx->enc_up, std::ref(upload)}, {ctx->enc_launch, std::ref(launch)}}, collect);
+  if (prog.failed()) {
     // nothing may still be in flight into the caller's or the result's memory when this returns
     (void)hipStreamSynchronize(ctx->copy_stream);
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipStreamSynchronize(ctx->stream_b);
     (void)hipStreamSynchronize(ctx->down_stream);
-    return fail(ctx, rc, msg);
+    return fail(ctx, prog.code(), prog.message());
   }
   try {
     F->pairs.resize(p_used);  // shrinks: the pools were grown ahead of need
@@ -1717,15 +1596,24 @@ int decode_hops_prepared(glc_ctx *ctx, uint64_t hop_begin, uint64_t hop_end, T *
   return GLC_OK;
 }
 
+// Copies a finished device buffer out behind the event its kernels recorded: `cs` waits for the event, takes the
+// `n` samples and is drained.  On ctx->stream itself - what follows the kernels in stream order - there is no wait.
+template <typename T>
+int copy_out_behind(glc_ctx *ctx, const Event &done, hipStream_t cs, T *dst, const T *src, uint64_t n) {
+  if (cs != ctx->stream) GLC_HIP(ctx, hipStreamWaitEvent(cs, done, 0));
+  if (n) GLC_HIP(ctx, hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, cs));
+  GLC_HIP(ctx, hipStreamSynchronize(cs));
+  return GLC_OK;
+}
+
 // Decoder::decode of the prepared session into host memory (src/codec.rs:744-768).
 template <typename T>
 int decode_prepared_to_host(glc_ctx *ctx, T *pcm_out, uint64_t cap, uint64_t *n_out, const char *who) {
   const uint64_t n_frames = ctx->dec_frames;
   const uint32_t channels = ctx->dec_ch;
   const glc::Trim trim = glc::gapless_trim(n_frames, channels, ctx->dec_delay, ctx->dec_orig_len);
-  const uint64_t start = trim.start, n = trim.n;
-  if (n_out) *n_out = n;
-  if (cap < n) return fail(ctx, GLC_EINVAL, std::string(who) + ": output buffer too small");
+  if (n_out) *n_out = trim.n;
+  if (cap < trim.n) return fail(ctx, GLC_EINVAL, std::string(who) + ": output buffer too small");
   ctx->dec_next = 0;
   // Rounds of 4096 frames through two device output buffers: the kernels of round r+1 are queued
   // before round r is copied out (on the copy stream, behind that round's event), so the D2H of
@@ -1755,15 +1643,12 @@ int decode_prepared_to_host(glc_ctx *ctx, T *pcm_out, uint64_t cap, uint64_t *n_
       rc = round_launch(ctx, round, false, stage + static_cast<size_t>(buf ^ 1) * bufcap, ctx->ev_dec[buf ^ 1], &frames, &last);
       if (rc != GLC_OK) return rc;
     }
-    const uint64_t c_lo = cur_f0 * per_hop, c_hi = (cur_f0 + cur_frames + (cur_last ? 1 : 0)) * per_hop;
-    const uint64_t lo = std::max(c_lo, start), hi = std::min(c_hi, start + n);
+    const glc::OutSpan out = glc::decode_round_span(trim, per_hop, cur_f0, cur_frames, cur_last);
     // a stream of a single round (short clips) has nothing to overlap: copy in stream order
     hipStream_t cs = (cur_last && cur_f0 == 0) ? ctx->stream : ctx->copy_stream;
-    if (cs != ctx->stream) GLC_HIP(ctx, hipStreamWaitEvent(cs, ctx->ev_dec[buf], 0));
-    if (hi > lo)
-      GLC_HIP(ctx, hipMemcpyAsync(pcm_out + (lo - start), stage + static_cast<size_t>(buf) * bufcap + (lo - c_lo),
-                                  (hi - lo) * sizeof(T), hipMemcpyDeviceToHost, cs));
-    GLC_HIP(ctx, hipStreamSynchronize(cs));
+    const T *from = stage + static_cast<size_t>(buf) * bufcap + (out.hi > out.lo ? out.lo - cur_f0 * per_hop : 0);
+    rc = copy_out_behind(ctx, ctx->ev_dec[buf], cs, pcm_out + (out.lo - trim.start), from, out.hi - out.lo);
+    if (rc != GLC_OK) return rc;
     if (cur_last) break;
     buf ^= 1;
   }
@@ -1981,11 +1866,8 @@ int decode_stream_next(glc_ctx *ctx, T *chunk, uint64_t cap, uint64_t *n_out, in
                                 ctx->ev_dec[buf ^ 1], &ctx->stream_frames, &ctx->stream_last);
     if (rc != GLC_OK) return rc;
   }
-  GLC_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_dec[buf], 0));
-  if (n)
-    GLC_HIP(ctx, hipMemcpyAsync(chunk, stage + static_cast<size_t>(buf) * bufcap, n * sizeof(T), hipMemcpyDeviceToHost,
-                                ctx->copy_stream));
-  GLC_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
+  const int rc = copy_out_behind(ctx, ctx->ev_dec[buf], ctx->copy_stream, chunk, stage + static_cast<size_t>(buf) * bufcap, n);
+  if (rc != GLC_OK) return rc;
   ctx->stream_buf = buf ^ 1;
   if (last) ctx->stream_open = false;
   return GLC_OK;
@@ -2222,11 +2104,9 @@ void rt_roundtrip_end(glc_ctx *ctx, const RtGeom &g) {
 template <typename T>
 int rt_roundtrip_host(glc_ctx *ctx, const void *pcm, glc_pcm_format fmt, uint32_t bits, uint64_t n_samples, const RtGeom &g,
                       const glc_plan &plan, T *pcm_out) {
-  const bool is_int = fmt != GLC_PCM_F32;
-  const size_t elem = pcm_elem(fmt);
   int rc = rt_roundtrip_begin(ctx, g);
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->pcm, static_cast<size_t>(n_samples) * sizeof(float));
-  if (rc == GLC_OK && is_int) rc = rt_reserve(ctx, ctx->pcm_int, static_cast<size_t>(n_samples) * elem);
+  if (rc == GLC_OK && fmt != GLC_PCM_F32) rc = rt_reserve(ctx, ctx->pcm_int, static_cast<size_t>(n_samples) * pcm_elem(fmt));
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rt_out, std::max<size_t>(g.trim.n, 1) * sizeof(T));
   if (rc == GLC_OK) rc = ensure_copy_objects(ctx);
   if (rc != GLC_OK) return rc;
@@ -2234,68 +2114,37 @@ int rt_roundtrip_host(glc_ctx *ctx, const void *pcm, glc_pcm_format fmt, uint32_
   // the staging buffers are shared with the other host-boundary calls, some of which work on streams of their own
   GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   float *d_pcm = static_cast<float *>(ctx->pcm.p);
-  uint8_t *d_int = static_cast<uint8_t *>(ctx->pcm_int.p);
   T *d_out = static_cast<T *>(ctx->rt_out.p);
-  const uint8_t *src = static_cast<const uint8_t *>(pcm);
-  const uint64_t n_rounds = (g.n_frames + g.round - 1) / g.round;
+  const uint64_t n_rounds = fixed_round_count(g.n_frames, g.round);
+  auto mark_of = [&](size_t i) {
+    const StreamRound r = fixed_round(g.n_frames, g.round, i);
+    return glc::upload_mark(r.f0, r.nf, plan.per_channel, g.ch, n_samples);
+  };
   // Three stages, as in glc_encode: round i + 1's samples go up (copy stream; a helper thread when there is more
   // than one round, because a copy from pageable memory blocks its caller), round i's kernels run, round i - 1's
   // output comes down (download stream, this thread) - PCIe carries both directions at once.  A stage waits on
   // the HOST for what it depends on and only then queues (nothing is queued behind an unfinished dependency);
   // copies from and to pageable memory have completed when they return.
-  struct Progress {
-    std::mutex mu;
-    std::condition_variable cv;
-    uint64_t uploaded = 0;
-    hipError_t err = hipSuccess;
-    bool stop = false;
-  } prog;
-  auto upload_all = [&] {
-    DeviceGuard dg(ctx->device);
-    uint64_t copied = 0;
-    for (uint64_t i = 0; i < n_rounds; ++i) {
-      const uint64_t f0 = i * g.round, nf = std::min(g.round, g.n_frames - f0);
-      const uint64_t hi = std::min<uint64_t>(n_samples, glc::frame_sample_window(f0, f0 + nf, plan.per_channel).hi * g.ch);
-      hipError_t e = hipSuccess;
-      if (hi > copied) {
-        if (!is_int) {
-          e = hipMemcpyAsync(d_pcm + copied, src + copied * 4, (hi - copied) * 4, hipMemcpyHostToDevice, ctx->copy_stream);
-        } else {
-          e = hipMemcpyAsync(d_int + copied * elem, src + copied * elem, (hi - copied) * elem, hipMemcpyHostToDevice, ctx->copy_stream);
-          if (e == hipSuccess)
-            e = glc::launch_pcm_widen(d_int + copied * elem, fmt == GLC_PCM_S32, bits, hi - copied, d_pcm + copied, ctx->copy_stream);
-        }
-        copied = hi;
-      }
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->copy_stream);
-      std::lock_guard<std::mutex> lk(prog.mu);
-      if (e != hipSuccess) prog.err = e;
-      else ++prog.uploaded;
-      prog.cv.notify_all();
-      if (e != hipSuccess || prog.stop) return;
-    }
+  StageGate gate;
+  auto upload = [&] {
+    upload_rounds(ctx, "glc_roundtrip", gate, kUploaded, n_rounds, mark_of, pcm, fmt, bits, d_pcm, static_cast<uint8_t *>(ctx->pcm_int.p),
+                  ctx->copy_stream, true);
   };
   auto download = [&](uint64_t i) -> hipError_t {  // the trimmed samples round i wrote
-    const uint64_t f0 = i * g.round, nf = std::min(g.round, g.n_frames - f0);
-    const bool last = f0 + nf == g.n_frames;
-    const uint64_t lo = std::max(g.trim.start, f0 * g.per_hop);
-    const uint64_t hi = std::min(g.trim.start + g.trim.n, (f0 + nf + (last ? 1 : 0)) * g.per_hop);
+    const StreamRound r = fixed_round(g.n_frames, g.round, i);
+    const glc::OutSpan out = glc::decode_round_span(g.trim, g.per_hop, r.f0, r.nf, r.f0 + r.nf == g.n_frames);
     hipError_t e = hipEventSynchronize(ctx->ev_dec[i & 1]);
-    if (e == hipSuccess && hi > lo)
-      e = hipMemcpyAsync(pcm_out + (lo - g.trim.start), d_out + (lo - g.trim.start), (hi - lo) * sizeof(T), hipMemcpyDeviceToHost,
-                         ctx->down_stream);
+    if (e == hipSuccess && out.hi > out.lo)
+      e = hipMemcpyAsync(pcm_out + (out.lo - g.trim.start), d_out + (out.lo - g.trim.start), (out.hi - out.lo) * sizeof(T),
+                         hipMemcpyDeviceToHost, ctx->down_stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->down_stream);
     return e;
   };
   auto rounds = [&]() -> int {
     for (uint64_t i = 0; i < n_rounds; ++i) {
-      {
-        std::unique_lock<std::mutex> lk(prog.mu);
-        prog.cv.wait(lk, [&] { return prog.uploaded > i || prog.err != hipSuccess; });
-        if (prog.err != hipSuccess) return hip_fail(ctx, prog.err, "glc_roundtrip: upload");
-      }
-      const uint64_t f0 = i * g.round, nf = std::min(g.round, g.n_frames - f0);
-      const int rrc = rt_roundtrip_round(ctx, g, d_pcm, n_samples, f0, nf, d_out, static_cast<uint64_t *>(ctx->rt_stats.p));
+      if (!gate.wait_for(kUploaded, i)) return fail(ctx, gate.code(), gate.message());
+      const StreamRound r = fixed_round(g.n_frames, g.round, i);
+      const int rrc = rt_roundtrip_round(ctx, g, d_pcm, n_samples, r.f0, r.nf, d_out, static_cast<uint64_t *>(ctx->rt_stats.p));
       if (rrc != GLC_OK) return rrc;
       GLC_HIP(ctx, hipEventRecord(ctx->ev_dec[i & 1], ctx->stream));
       if (i > 0) GLC_HIP(ctx, download(i - 1));
@@ -2303,23 +2152,11 @@ int rt_roundtrip_host(glc_ctx *ctx, const void *pcm, glc_pcm_format fmt, uint32_
     GLC_HIP(ctx, download(n_rounds - 1));
     return GLC_OK;
   };
-  if (n_rounds == 1) {
-    upload_all();
-    rc = rounds();
-  } else {
-    try {
-      if (!ctx->enc_up) ctx->enc_up.reset(new Worker);
-      ctx->enc_up->submit(upload_all);
-    } catch (...) {  // std::system_error / std::bad_alloc from starting the helper: nothing has been started
-      return fail(ctx, GLC_ENOMEM, "glc_roundtrip: cannot start a helper thread");
-    }
-    rc = rounds();
-    {
-      std::lock_guard<std::mutex> lk(prog.mu);
-      prog.stop = true;
-    }
-    ctx->enc_up->wait();  // it reads this frame's variables
-  }
+  if (n_rounds == 1)
+    run_stages(gate, "glc_roundtrip", {}, [&] { upload(), rc = rounds(); });
+  else
+    run_stages(gate, "glc_roundtrip", {{ctx->enc_up, std::ref(upload)}}, [&] { rc = rounds(); });
+  if (rc == GLC_OK && gate.failed()) rc = fail(ctx, gate.code(), gate.message());  // no helper thread, or an exception in the body
   if (rc != GLC_OK) return rc;
   rt_roundtrip_end(ctx, g);
   return GLC_OK;

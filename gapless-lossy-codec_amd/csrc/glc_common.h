@@ -83,6 +83,12 @@ inline SampleWindow frame_sample_window(uint64_t f0, uint64_t f1, uint64_t per_c
   const uint64_t hi = (f1 - 1) * kHop + kFrame - kHop / 2;
   return {lo, hi < per_channel ? hi : per_channel};
 }
+// The upload mark of a round of frames [f0, f0 + nf): the INTERLEAVED samples of the stream's n_samples that must be on
+// the device before its kernels run - everything up to the end of its window, halo included.
+inline uint64_t upload_mark(uint64_t f0, uint64_t nf, uint64_t per_channel, uint32_t ch, uint64_t n_samples) {
+  const uint64_t hi = frame_sample_window(f0, f0 + nf, per_channel).hi * ch;
+  return hi < n_samples ? hi : n_samples;
+}
 
 // What a push of n_new samples per channel completes on a lane of a streaming encode that has `received` so far
 // (include/glc.h glc_plan_stream_push), the ONE statement of it.  Frame f reads [hop f - hop/2, hop f - hop/2 + frame):
@@ -140,6 +146,17 @@ GLC_HD inline Trim gapless_trim(uint64_t n_frames, uint32_t ch, uint64_t encoder
   }
   if (t.n > original_length) t.n = original_length;
   return t;
+}
+// What a decode round of frames [f0, f0 + nf) contributes to the trimmed output: the un-trimmed interleaved positions
+// [lo, hi) of its hops - with the bare tail hop where it is the stream's `last` round, whose nf may be 0 - that the
+// trim keeps.  hi >= lo; the spans of a stream's rounds tile [trim.start, trim.start + trim.n).
+struct OutSpan {
+  uint64_t lo, hi;
+};
+inline OutSpan decode_round_span(const Trim &trim, uint64_t per_hop, uint64_t f0, uint64_t nf, bool last) {
+  const uint64_t c_lo = f0 * per_hop, c_hi = (f0 + nf + (last ? 1 : 0)) * per_hop, end = trim.start + trim.n;
+  const uint64_t lo = c_lo > trim.start ? (c_lo < end ? c_lo : end) : trim.start, hi = c_hi < end ? c_hi : end;
+  return {lo, hi > lo ? hi : lo};
 }
 
 // What a crop of the decoded clip needs of its stream (include/glc.h glc_plan_crop; DESIGN section 3, "a window of a

@@ -1,5 +1,5 @@
-// glc_rounds.hpp — how the batch, store and stream drivers of glc_api.hip cut a call into rounds, and where the tables
-// of a call lie in its image.  Plain C++17 without a HIP type: a host program can include it alone
+// glc_rounds.hpp — how the drivers of glc_api.hip cut a call into rounds (the batch, store and stream drivers their
+// items, the host encode, round trip and decode their one stream), and where the tables of a call lie in its image.  Plain C++17 without a HIP type: a host program can include it alone
 // (tools/round_plan_check.cpp).
 #pragma once
 #include <cstddef>
@@ -38,6 +38,40 @@ std::vector<RoundSpan> pack_rounds(uint64_t n, FramesOf frames_of, uint64_t budg
   }
   close(n);
   return rounds;
+}
+
+// Frames [f0, f0 + nf) of ONE stream, sent through one launch chain.
+struct StreamRound {
+  uint64_t f0 = 0, nf = 0;
+};
+
+// THE rounds of a host encode (glc_encode*).  The upload nothing hides is the first round's, and
+// the kernels nothing hide are the last round's, so a stream opens with four rounds of `piece` frames - 2048 rows,
+// 0.15 ms of PCIe each for stereo; at most 2048 rows because that is the size the round kernel of
+// launch_mdct_forward (`beside`) is dealt one workgroup per CU for - before it goes on in rounds of `chunk`
+// (encode_chunk_frames(ch)).  No round for a remainder of less than half a piece: the round before takes it.
+// BASELINE config 2 (4096 stereo frames) is the four opening rounds.
+// (Measured and dropped, round 3: cutting the END of a stream in halves - .. 2048, 1024, 512, 512 frames - so that
+// the last, unhidden transform is a short one: 1.045 ms against 1.02 at config 2; a round costs the launcher and
+// the collector more than the shorter tail returns.)
+inline std::vector<StreamRound> encode_stream_rounds(uint64_t n_frames, uint32_t ch, uint64_t chunk) {
+  const uint64_t piece = ch < 2048 ? 2048 / ch : 1, opening = 4 * piece;
+  std::vector<StreamRound> rounds;
+  for (uint64_t f = 0, nf = 0; f < n_frames; f += nf) {
+    const uint64_t left = n_frames - f;
+    nf = f < opening ? piece : chunk;
+    if (nf > left) nf = left;
+    if (left - nf < piece / 2) nf = left;
+    rounds.push_back(StreamRound{f, nf});
+  }
+  return rounds;
+}
+
+// The fixed rounds of the round trip and the decode: `round` frames each (>= 1), a ragged last one.
+inline uint64_t fixed_round_count(uint64_t n_frames, uint64_t round) { return (n_frames + round - 1) / round; }
+inline StreamRound fixed_round(uint64_t n_frames, uint64_t round, uint64_t i) {
+  const uint64_t f0 = i * round;
+  return StreamRound{f0, n_frames - f0 < round ? n_frames - f0 : round};
 }
 
 // Where the tables of an image lie: every table starts on a multiple of 256 bytes, in the order it was taken.

@@ -1,7 +1,10 @@
 """The round rule of the batch, store and stream drivers without a device: tools/round_plan_check.cpp includes
 csrc/glc_rounds.hpp alone and holds pack_rounds to the properties DESIGN.md section 3 states (every item in one round,
 in order, none empty, the sums, `lng` exactly for an item that fits no round, the budget, greediness) over the budgets
-and fronts the drivers use and a few tiny ones, and TableOffsets to 256-byte tables that do not overlap.  Built here
+and fronts the drivers use and a few tiny ones, and TableOffsets to 256-byte tables that do not overlap.  With
+csrc/glc_common.h it holds the rounds of ONE stream to theirs: encode_stream_rounds tiles the stream with four opening
+rounds, whole chunks and no short last round; the upload marks of its rounds never decrease, cover each round's halo and
+end at the stream's length; the output spans of the decode rounds tile what the trim keeps.  Built here
 with AddressSanitizer and UBSan and run: it is plain host code."""
 import os
 import shutil

@@ -157,6 +157,23 @@ def test_integer_input_equals_encode_int_then_decode(glc_amd, dtype, nbits, out_
     assert np.array_equal(y.view(np.uint32 if out_dtype == F32 else np.int16), ref.view(np.uint32 if out_dtype == F32 else np.int16))
 
 
+# (two rounds, the last of a single frame: the integer samples of the second go up, and are widened, on the helper thread)
+@pytest.mark.parametrize("ch,n_frames,dtype,nbits,out_dtype", [(1, 4097, np.int16, 16, F32), (2, 2049, np.int32, 24, np.int16)])
+def test_integer_input_over_two_rounds_equals_encode_int_then_decode(glc_amd, ch, n_frames, dtype, nbits, out_dtype):
+    sr = 44100
+    per_channel = n_frames * HOP - 100
+    assert RC.frames_of(per_channel) == n_frames
+    seg = np.concatenate([cf.gen_chord(sr, ch, 3 * HOP, seed=9), RC.lcg_noise(2 * HOP * ch)])
+    x = np.resize(seg, per_channel * ch).astype(F32)
+    lim = float(2 ** (nbits - 1))
+    xi = np.clip(np.round(x.astype(np.float64) * lim), -lim, lim - 1).astype(dtype)
+    _, ref = two_step(glc_amd, sr, xi, ch, bits_=nbits, dtype=out_dtype)
+    y = ctx(glc_amd, "rt", sr).apply(xi, ch, bits=nbits, dtype=out_dtype)
+    view = np.uint32 if out_dtype == F32 else np.int16
+    assert y.dtype == out_dtype and y.size == ref.size == xi.size
+    assert np.array_equal(y.view(view), ref.view(view))
+
+
 def test_ten_minutes_of_stereo_cross_several_rounds(glc_amd, torch):
     sr, ch = 48000, 2
     seg = cf.gen_chord(sr, ch, 480000)
