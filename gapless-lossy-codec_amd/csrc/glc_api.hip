@@ -2514,17 +2514,15 @@ int cd_decode_one(glc_ctx *ctx, const RtGeom &g, const void *d_blob, uint64_t bl
   const size_t slot = static_cast<size_t>(g.ch) * glc::kFrame;
   int rc = rt_reserve(ctx, ctx->blocks, (g.round + 1) * slot * sizeof(float));
   // 32 B per row of the STREAM, or of the window
-  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rt_rows, win ? glc::rows_from_compact_window_bytes(M) : glc::rows_from_compact_bytes(M));
+  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rt_rows, glc::rows_from_compact_bytes(M));
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rt_edge, 2 * g.per_hop * sizeof(float));
   if (rc == GLC_OK) rc = reserve_d1_plan(ctx, g.round, g.ch);
   if (rc != GLC_OK) return rc;
   const uint32_t front = static_cast<uint32_t>(fb * g.ch);
-  const glc::CompactBlob one{reinterpret_cast<uintptr_t>(d_blob), blob_bytes, 0u, M_blob, {win ? front : 0u, win ? M : 0u}};
+  const glc::CompactBlob one{reinterpret_cast<uintptr_t>(d_blob), blob_bytes, 0u, M_blob, {front, M}};  // whole: {0, M_blob}
   glc::DecodeRows rows{};
-  if (win)
-    GLC_HIP(ctx, glc::launch_rows_from_compact_window(nullptr, one, 1, M, g.ch, front, d_blob, ctx->rt_rows.p, d_status, ctx->stream, &rows));
-  else
-    GLC_HIP(ctx, glc::launch_rows_from_compact(nullptr, one, 1, M, g.ch, d_blob, ctx->rt_rows.p, d_status, ctx->stream, &rows));
+  GLC_HIP(ctx, glc::launch_rows_from_compact(nullptr, one, 1, M, g.ch, glc::R2Mode{!win, front, nullptr}, d_blob, ctx->rt_rows.p, d_status,
+                                             ctx->stream, &rows));
   for (uint64_t f0 = fb; f0 < fe; f0 += g.round) {
     const uint64_t nf = std::min(g.round, fe - f0), f1 = f0 + nf;
     // the round's descriptors: those of hops [f0, f1 (+ 1)) that keep anything (rtb_impl)
@@ -2568,8 +2566,7 @@ int cdb_impl(glc_ctx *ctx, const char *who, const void *const *d_blobs, const ui
   }
   rt_forget_streams(ctx);
   ctx->cd_status_n = 0;
-  int rc = rt_reserve(ctx, ctx->rt_rows, wins ? glc::rows_from_compact_window_bytes(static_cast<uint32_t>(max_rows))
-                                              : glc::rows_from_compact_bytes(static_cast<uint32_t>(max_rows)));
+  int rc = rt_reserve(ctx, ctx->rt_rows, glc::rows_from_compact_bytes(static_cast<uint32_t>(max_rows)));
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->blocks, max_blocks * slot * sizeof(float));
   if (rc == GLC_OK) rc = reserve_d1_plan(ctx, max_frames, ch);
   TableImage &image = ctx->rtb_image;
@@ -2588,7 +2585,7 @@ int cdb_impl(glc_ctx *ctx, const char *who, const void *const *d_blobs, const ui
     uint64_t real = 0;
     for (uint64_t k = 0; k < r.n; ++k) {
       const uint64_t i = r.first + k, nf = plans[i].n_frames;
-      const uint32_t w0 = wins ? static_cast<uint32_t>(wins[i].first_frame * ch) : 0u, w1 = wins ? static_cast<uint32_t>(wins[i].n_frames * ch) : 0u;
+      const uint32_t w0 = wins ? static_cast<uint32_t>(wins[i].first_frame * ch) : 0u, w1 = static_cast<uint32_t>(frames_of(i) * ch);
       if (!r.lng)
         dir[k] = glc::CompactBlob{reinterpret_cast<uintptr_t>(d_blobs[i]), blob_bytes[i], static_cast<uint32_t>(real * ch),
                                   static_cast<uint32_t>(nf * ch), {w0, w1}};
@@ -2620,16 +2617,11 @@ int cdb_impl(glc_ctx *ctx, const char *who, const void *const *d_blobs, const ui
     const uint32_t M = static_cast<uint32_t>(r.n_real * ch);
     glc::DecodeRows rows{};
     const auto *d_dir = image.dev<glc::CompactBlob>(r.o_dir);
-    if (wins) {
-      uint64_t front = 0;  // the most rows any window of the round has in front
-      for (uint64_t i = r.first; i < r.first + r.n; ++i) front = std::max(front, wins[i].first_frame * ch);
-      GLC_HIP(ctx, glc::launch_rows_from_compact_window(d_dir, glc::CompactBlob{}, static_cast<uint32_t>(r.n), M, ch,
-                                                        static_cast<uint32_t>(front), reinterpret_cast<const void *>(base),
-                                                        ctx->rt_rows.p, d_status + r.first, st, &rows));
-    } else {
-      GLC_HIP(ctx, glc::launch_rows_from_compact(d_dir, glc::CompactBlob{}, static_cast<uint32_t>(r.n), M, ch,
-                                                 reinterpret_cast<const void *>(base), ctx->rt_rows.p, d_status + r.first, st, &rows));
-    }
+    uint64_t front = 0;  // the most rows any window of the round has in front
+    for (uint64_t i = r.first; wins && i < r.first + r.n; ++i) front = std::max(front, wins[i].first_frame * ch);
+    GLC_HIP(ctx, glc::launch_rows_from_compact(d_dir, glc::CompactBlob{}, static_cast<uint32_t>(r.n), M, ch,
+                                               glc::R2Mode{!wins, static_cast<uint32_t>(front), nullptr},
+                                               reinterpret_cast<const void *>(base), ctx->rt_rows.p, d_status + r.first, st, &rows));
     // (D1's 8-frame units may span two clips: that only widens a union)
     GLC_HIP(ctx, launch_d1_rows(ctx, rows, 0, M, ch, blocks, st));
     GLC_HIP(ctx, glc::launch_overlap_add_strided(blocks, desc, static_cast<uint32_t>(r.n_desc), ch, out_planes, d_out, st));
@@ -2856,7 +2848,7 @@ static int sd_call(glc_ctx *ctx, const char *who, const void *d_arena, uint64_t 
   DeviceGuard guard(ctx->device);
   rt_forget_streams(ctx);
   ctx->cd_status_n = 0;
-  rc = rt_reserve(ctx, ctx->rt_rows, glc::rows_from_compact_window_bytes(static_cast<uint32_t>(widest * ch)));
+  rc = rt_reserve(ctx, ctx->rt_rows, glc::rows_from_compact_bytes(static_cast<uint32_t>(widest * ch)));
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->blocks, widest * slot * sizeof(float));
   if (rc == GLC_OK) rc = reserve_d1_plan(ctx, widest, ch);
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rtb_tab, g.tab);
@@ -2877,9 +2869,9 @@ static int sd_call(glc_ctx *ctx, const char *who, const void *d_arena, uint64_t 
     const uint32_t M = static_cast<uint32_t>(nr * g.slots.max_frames * ch);
     glc::DecodeRows rows{};
     // pairs and raw planes are addressed from the arena: every usable blob lies inside it, 64-byte aligned
-    GLC_HIP(ctx, glc::launch_rows_from_compact_window(d_dir + first, glc::CompactBlob{}, static_cast<uint32_t>(nr), M, ch,
-                                                      static_cast<uint32_t>(g.max_front), d_arena, ctx->rt_rows.p, d_status + first, st,
-                                                      &rows, d_verdict + first));
+    GLC_HIP(ctx, glc::launch_rows_from_compact(d_dir + first, glc::CompactBlob{}, static_cast<uint32_t>(nr), M, ch,
+                                               glc::R2Mode{false, static_cast<uint32_t>(g.max_front), d_verdict + first}, d_arena,
+                                               ctx->rt_rows.p, d_status + first, st, &rows));
     GLC_HIP(ctx, launch_d1_rows(ctx, rows, 0, M, ch, blocks, st));
     GLC_HIP(ctx, glc::launch_overlap_add_strided(blocks, d_desc + first * g.slots.max_hops, static_cast<uint32_t>(nr * g.slots.max_hops), ch,
                                                  out_planes, d_out, st));
@@ -3687,7 +3679,7 @@ int stream_dec_core(glc_stream_dec *s, const std::vector<DecLanePush> &act, cons
   // behind the image, written by the planner kernel: the directory and the verdicts
   const size_t o_dir = offs.take(std::max<uint64_t>(n_segs, 1) * sizeof(glc::CompactBlob));
   const size_t o_verdict = offs.take(std::max<uint64_t>(n_segs, 1) * sizeof(uint32_t));
-  int rc = rt_reserve(ctx, ctx->rt_rows, glc::rows_from_compact_window_bytes(static_cast<uint32_t>(max_M)));
+  int rc = rt_reserve(ctx, ctx->rt_rows, glc::rows_from_compact_bytes(static_cast<uint32_t>(max_M)));
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->blocks, max_slots * slot * sizeof(float));
   if (rc == GLC_OK && max_frames) rc = reserve_d1_plan(ctx, max_frames, ch);
   TableImage &image = ctx->rtb_image;
@@ -3749,8 +3741,9 @@ int stream_dec_core(glc_stream_dec *s, const std::vector<DecLanePush> &act, cons
     if (M) {
       glc::DecodeRows rows{};
       // pairs and raw planes are addressed from the arena: every usable blob lies inside it, 64-byte aligned
-      GLC_HIP(ctx, glc::launch_rows_from_compact_window(d_dir + R.seg_first, glc::CompactBlob{}, static_cast<uint32_t>(R.seg_n), M, ch, 0u,
-                                                        d_arena, ctx->rt_rows.p, d_status + R.seg_first, st, &rows, d_verdict + R.seg_first));
+      GLC_HIP(ctx, glc::launch_rows_from_compact(d_dir + R.seg_first, glc::CompactBlob{}, static_cast<uint32_t>(R.seg_n), M, ch,
+                                                 glc::R2Mode{false, 0u, d_verdict + R.seg_first}, d_arena, ctx->rt_rows.p,
+                                                 d_status + R.seg_first, st, &rows));
       GLC_HIP(ctx, launch_d1_rows(ctx, rows, 0, M, ch, blocks, st));
     }
     GLC_HIP(ctx, glc::launch_stream_dec_carry(false, image.dev<glc::StreamCarry>(R.o_load), static_cast<uint32_t>(R.n_load), ch, blocks, carry, st));
@@ -4066,23 +4059,27 @@ int glc_debug_compact_batch_device(glc_ctx *ctx, const void *d_records, const ui
   return GLC_OK;
 }
 
-int glc_debug_rows_from_compact(glc_ctx *ctx, const void *d_blob, uint64_t blob_bytes, uint64_t n_frames, uint16_t channels,
-                                uint64_t *row_begin, uint32_t *row_cnt, float *row_scale, int64_t *row_raw,
-                                uint64_t *row_raw_len, glc_compact_status *status) {
-  const std::string w("glc_debug_rows_from_compact");
+extern "C++" {
+namespace {
+// The two R2 hooks: the window [first_frame, first_frame + frames) of one blob through R2 alone, its tables and status
+// to the host.  `whole`: the window is the blob, and the launch compares the sums with the header's totals.
+int debug_rows_from_compact(glc_ctx *ctx, const std::string &w, bool whole, const void *d_blob, uint64_t blob_bytes, uint64_t n_frames,
+                            uint16_t channels, uint64_t first_frame, uint64_t frames, uint64_t *row_begin, uint32_t *row_cnt,
+                            float *row_scale, int64_t *row_raw, uint64_t *row_raw_len, glc_compact_status *status) {
   if (!ctx) return GLC_EINVAL;
   if (channels == 0 || n_frames == 0 || n_frames * channels > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, w + ": bad shape");
+  if (frames == 0 || first_frame > n_frames || frames > n_frames - first_frame) return fail(ctx, GLC_EINVAL, w + ": the window leaves the blob");
   if (const char *bad = cd_blob_fault(d_blob, blob_bytes, channels, n_frames)) return fail(ctx, GLC_EINVAL, w + ": " + bad);
   DeviceGuard guard(ctx->device);
-  const uint32_t M = static_cast<uint32_t>(n_frames * channels);
+  const uint32_t M = static_cast<uint32_t>(frames * channels), front = static_cast<uint32_t>(first_frame * channels);
   rt_forget_streams(ctx);
   ctx->cd_status_n = 0;
   int rc = rt_reserve(ctx, ctx->rt_rows, glc::rows_from_compact_bytes(M));
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->cd_status, sizeof(glc::CompactStatus));
   if (rc != GLC_OK) return rc;
-  const glc::CompactBlob one{reinterpret_cast<uintptr_t>(d_blob), blob_bytes, 0u, M, {0u, 0u}};
+  const glc::CompactBlob one{reinterpret_cast<uintptr_t>(d_blob), blob_bytes, 0u, static_cast<uint32_t>(n_frames * channels), {front, M}};
   glc::DecodeRows rows{};
-  GLC_HIP(ctx, glc::launch_rows_from_compact(nullptr, one, 1, M, channels, d_blob, ctx->rt_rows.p,
+  GLC_HIP(ctx, glc::launch_rows_from_compact(nullptr, one, 1, M, channels, glc::R2Mode{whole, front, nullptr}, d_blob, ctx->rt_rows.p,
                                              static_cast<glc::CompactStatus *>(ctx->cd_status.p), ctx->stream, &rows));
   GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (row_begin) GLC_HIP(ctx, hipMemcpy(row_begin, rows.row_begin, M * 8ull, hipMemcpyDeviceToHost));
@@ -4093,34 +4090,21 @@ int glc_debug_rows_from_compact(glc_ctx *ctx, const void *d_blob, uint64_t blob_
   ctx->cd_status_n = 1;
   return status ? glc_decode_compact_last_status(ctx, status, 1) : GLC_OK;
 }
+}  // namespace
+}  // extern "C++"
+
+int glc_debug_rows_from_compact(glc_ctx *ctx, const void *d_blob, uint64_t blob_bytes, uint64_t n_frames, uint16_t channels,
+                                uint64_t *row_begin, uint32_t *row_cnt, float *row_scale, int64_t *row_raw,
+                                uint64_t *row_raw_len, glc_compact_status *status) {
+  return debug_rows_from_compact(ctx, "glc_debug_rows_from_compact", true, d_blob, blob_bytes, n_frames, channels, 0, n_frames, row_begin,
+                                 row_cnt, row_scale, row_raw, row_raw_len, status);
+}
 
 int glc_debug_rows_from_compact_window(glc_ctx *ctx, const void *d_blob, uint64_t blob_bytes, uint64_t n_frames, uint16_t channels,
                                        uint64_t first_frame, uint64_t frames, uint64_t *row_begin, uint32_t *row_cnt,
                                        float *row_scale, int64_t *row_raw, uint64_t *row_raw_len, glc_compact_status *status) {
-  const std::string w("glc_debug_rows_from_compact_window");
-  if (!ctx) return GLC_EINVAL;
-  if (channels == 0 || n_frames == 0 || n_frames * channels > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, w + ": bad shape");
-  if (frames == 0 || first_frame > n_frames || frames > n_frames - first_frame) return fail(ctx, GLC_EINVAL, w + ": the window leaves the blob");
-  if (const char *bad = cd_blob_fault(d_blob, blob_bytes, channels, n_frames)) return fail(ctx, GLC_EINVAL, w + ": " + bad);
-  DeviceGuard guard(ctx->device);
-  const uint32_t M = static_cast<uint32_t>(frames * channels), front = static_cast<uint32_t>(first_frame * channels);
-  rt_forget_streams(ctx);
-  ctx->cd_status_n = 0;
-  int rc = rt_reserve(ctx, ctx->rt_rows, glc::rows_from_compact_window_bytes(M));
-  if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->cd_status, sizeof(glc::CompactStatus));
-  if (rc != GLC_OK) return rc;
-  const glc::CompactBlob one{reinterpret_cast<uintptr_t>(d_blob), blob_bytes, 0u, static_cast<uint32_t>(n_frames * channels), {front, M}};
-  glc::DecodeRows rows{};
-  GLC_HIP(ctx, glc::launch_rows_from_compact_window(nullptr, one, 1, M, channels, front, d_blob, ctx->rt_rows.p,
-                                                    static_cast<glc::CompactStatus *>(ctx->cd_status.p), ctx->stream, &rows));
-  GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (row_begin) GLC_HIP(ctx, hipMemcpy(row_begin, rows.row_begin, M * 8ull, hipMemcpyDeviceToHost));
-  if (row_cnt) GLC_HIP(ctx, hipMemcpy(row_cnt, rows.row_cnt, M * 4ull, hipMemcpyDeviceToHost));
-  if (row_scale) GLC_HIP(ctx, hipMemcpy(row_scale, rows.row_scale, M * 4ull, hipMemcpyDeviceToHost));
-  if (row_raw) GLC_HIP(ctx, hipMemcpy(row_raw, rows.row_raw, M * 8ull, hipMemcpyDeviceToHost));
-  if (row_raw_len) GLC_HIP(ctx, hipMemcpy(row_raw_len, rows.row_raw_len, M * 8ull, hipMemcpyDeviceToHost));
-  ctx->cd_status_n = 1;
-  return status ? glc_decode_compact_last_status(ctx, status, 1) : GLC_OK;
+  return debug_rows_from_compact(ctx, "glc_debug_rows_from_compact_window", false, d_blob, blob_bytes, n_frames, channels, first_frame,
+                                 frames, row_begin, row_cnt, row_scale, row_raw, row_raw_len, status);
 }
 
 int glc_debug_set_imdct_variant(glc_ctx *ctx, int variant) {

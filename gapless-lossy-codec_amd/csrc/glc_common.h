@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/glc.h"
@@ -198,6 +199,18 @@ inline uint64_t record_header_bytes(uint32_t ch) { return ((8ull + 8ull * ch) + 
 inline uint64_t record_bytes(uint32_t ch) {
   return record_header_bytes(ch) + 2ull * kFrame * ch;
 }
+// The header's fields: {u32 raw flag, u32 0}, then per channel {f32 scale, u32 nnz}.  `rec` (16-byte aligned bytes) may
+// be const or not, and so is the field.
+template <typename T, typename B>
+GLC_HD inline auto &record_field(B *at) {
+  return *reinterpret_cast<typename std::conditional<std::is_const<B>::value, const T, T>::type *>(at);
+}
+template <typename B>
+GLC_HD inline auto &record_raw(B *rec) { return record_field<uint32_t>(rec); }
+template <typename B>
+GLC_HD inline auto &record_scale(B *rec, uint32_t c) { return record_field<float>(rec + 8 + 8 * c); }
+template <typename B>
+GLC_HD inline auto &record_nnz(B *rec, uint32_t c) { return record_field<uint32_t>(rec + 8 + 8 * c + 4); }
 
 // Compact ("bitstream payload") form of a contiguous frame range, one self-describing blob:
 //   header (64 B) | is_raw u8[n_frames] | scale f32[M] | cnt u32[M] | pairs u32[n_pairs] |
@@ -217,6 +230,9 @@ struct CompactHeader {
   uint64_t reserved[3];
 };
 static_assert(sizeof(CompactHeader) == 64, "compact header is 64 bytes");
+GLC_HD inline CompactHeader compact_header(uint32_t ch, uint64_t n_frames, uint64_t n_pairs, uint64_t n_raw_rows, uint64_t bytes) {
+  return CompactHeader{kCompactMagic, ch, n_frames, n_pairs, n_raw_rows, bytes, {0, 0, 0}};
+}
 // The layout and the header rule below are the only statement of either: the host drivers and the device
 // kernels (P1-P3 write a blob, R2 reads one) call the same functions.
 GLC_HD inline uint64_t align64(uint64_t v) { return (v + 63ull) & ~63ull; }

@@ -304,13 +304,7 @@ int glc_compact_records(const void *records, uint64_t n_frames, uint16_t channel
     std::memcpy(rawp + rr * glc::kFrame, base + f * rec + hdr, sizeof(int16_t) * glc::kFrame * ch);
     rr += ch;
   }
-  glc::CompactHeader h{};
-  h.magic = glc::kCompactMagic;
-  h.channels = ch;
-  h.n_frames = n_frames;
-  h.n_pairs = n_pairs;
-  h.n_raw_rows = n_raw_rows;
-  h.bytes = raw_off + n_raw_rows * glc::kFrame * 2;
+  const glc::CompactHeader h = glc::compact_header(ch, n_frames, n_pairs, n_raw_rows, raw_off + n_raw_rows * glc::kFrame * 2);
   std::memcpy(out, &h, sizeof h);
   info->n_frames = n_frames;
   info->n_pairs = n_pairs;
@@ -408,13 +402,7 @@ int glc_frames_to_compact(const glc_frames *f, void *blob, uint64_t cap, glc_com
       p_at += b - a;
     }
   }
-  glc::CompactHeader h{};
-  h.magic = glc::kCompactMagic;
-  h.channels = ch;
-  h.n_frames = nf;
-  h.n_pairs = n_pairs;
-  h.n_raw_rows = n_raw_rows;
-  h.bytes = info->bytes;
+  const glc::CompactHeader h = glc::compact_header(ch, nf, n_pairs, n_raw_rows, info->bytes);
   std::memcpy(out, &h, sizeof h);
   return GLC_OK;
 }

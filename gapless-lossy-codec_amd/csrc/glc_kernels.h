@@ -236,78 +236,72 @@ hipError_t launch_rows_from_records(const uint8_t *records, uint32_t M, uint32_t
 constexpr uint32_t kClipStatSlots = 4;
 hipError_t launch_rows_from_records_batch(const uint8_t *records, uint32_t M, uint32_t ch, const FrameMap *fmap, void *workspace,
                                           uint64_t *clip_stats, hipStream_t s, DecodeRows *rows);
-// R2: the DecodeRows of the M rows of one or several COMPACT BLOBS (glc_common.h CompactLayout) that are on the
-// device, built there.  Nothing of the payload is copied: rows->pairs and rows->raw_pool are ONE common base (the
-// lowest blob address, every blob 64-byte aligned) from which row_begin counts in u32 and row_raw in i16, so
-// the lists and raw planes are read where they lie inside the blobs.  Blob i of `n_blobs` is described by
-// CompactBlob {address, capacity in bytes the caller vouches for, first row, rows}; first_row ascends from 0, rows
-// = frames * ch of the stream the host expects (whole frames: an M that is no multiple of ch is refused), and their
-// sum is M.  `dir` is that table on the device, or
-// null with n_blobs == 1, when `one` travels as a kernel argument.  status[n_blobs] (device, kept by the caller
-// for as long as it wants to read it; written here, no need to zero it): what the checks found.
-//   header (k_r2_headers, one thread per blob): glc_common.h compact_header_fault - magic, ch, exactly rows / ch frames,
+// R2: the DecodeRows of WINDOWS of COMPACT BLOBS (glc_common.h CompactLayout) that are on the device, built there.
+// Nothing of the payload is copied: rows->pairs and rows->raw_pool are ONE common `base` (at or below every blob
+// address, 64-byte aligned like every blob) from which row_begin counts in u32 and row_raw in i16, so the lists and
+// raw planes are read where they lie inside the blobs.  Entry i of `n_entries` names a blob - address, capacity in
+// bytes the caller vouches for, `rows` = ALL rows of the blob the host expects (frames * ch) - and the window [win[0],
+// win[0] + win[1]) of its rows (whole frames, inside the blob; win[1] >= 1) whose tables are rows [first_row,
+// first_row + win[1]) of this launch; first_row ascends from 0 and the windows' rows sum to M (whole frames: an M that
+// is no multiple of ch is refused).  A WHOLE BLOB is the window {0, rows}.  The same blob may be named by any number
+// of entries, in any address order.  `dir` is the table of entries on the device, or null with n_entries == 1, when
+// `one` travels as a kernel argument.  status[n_entries] (device, kept by the caller for as long as it wants to read
+// it; written here, no need to zero it): what the checks found, per ENTRY.
+//   header (k_r2_headers, one thread per entry): glc_common.h compact_header_fault - magic, ch, exactly rows / ch frames,
 //   n_pairs <= 1024 rows, n_raw_rows <= rows and a multiple of ch, bytes == the sum of the sections <= capacity.
-//   A blob that fails is read no further: its rows are empty lists of scale 0.0f with no raw plane.
-//   scans (k_r2_scan_rows, k_r2_scan_blocks): row_begin = exclusive 64-bit sum of cnt over the blob's rows in
-//   front (rows of raw frames count 0 whatever their cnt says), raw plane = rows of raw frames in front: sums
-//   inside blocks of 1024 rows, one workgroup scans the block sums in chunks of 1024 and takes each blob's
-//   own origin out of the running sums.  No workgroup waits for another.
-//   rows (k_r2_rows, one wave per row): a compressed row is kept when cnt <= 1024, row_begin + cnt <= n_pairs and
-//   its bins ascend strictly below 1024; the rows of a raw frame when the frame's planes lie below n_raw_rows
-//   and inside `bytes`.  A row that is not kept becomes the empty list with its stored scale and no raw plane.
-//   No load leaves [address, address + capacity).
-// workspace: rows_from_compact_bytes(M) bytes (32 B per row + the block sums) that stay untouched while *rows
-// is in use.  Four launches whatever n_blobs, no synchronisation; any_raw is set (the host does not know).
-struct CompactBlob {
-  uint64_t addr, cap;
-  uint32_t first_row, rows;
-  uint32_t win[2];  // launch_rows_from_compact_window: first row and row count of the window inside the blob; else 0
-};
-constexpr uint32_t kCompactBadHeader = 1u, kCompactRowBounds = 2u, kCompactNotCanonical = 4u, kCompactRawRange = 8u,
-                   kCompactPairSum = 16u, kCompactRawSum = 32u;
-struct CompactStatus {  // 64 bytes per blob
-  uint32_t flags, header_ok;
-  uint64_t n_bad_rows, first_bad_row;  // first_bad_row: ~0 while no row has been rejected
-  uint64_t n_pairs, n_raw_rows, bytes;  // of a header that passed
-  uint64_t pairs_before, raw_before;    // running sums of the launch at the blob's first row (a window: minus its prefix, mod 2^64)
-};
-uint64_t rows_from_compact_bytes(uint32_t M);
-hipError_t launch_rows_from_compact(const CompactBlob *dir, const CompactBlob &one, uint32_t n_blobs, uint32_t M, uint32_t ch,
-                                    const void *base, void *workspace, CompactStatus *status, hipStream_t s,
-                                    DecodeRows *rows);
-// R2 of WINDOWS of compact blobs (glc_decode_crops_device_compact): entry i of `dir` (or `one`) names a blob as above -
-// address, capacity, `rows` = ALL rows of the blob the host expects (frames * ch) - and the window [win[0], win[0] +
-// win[1]) of its rows (whole frames, inside the blob; win[1] >= 1) whose tables are rows [first_row, first_row +
-// win[1]) of this launch; first_row ascends from 0 and the windows' rows sum to M.  The same blob may be named by any
-// number of entries, in any address order.  The tables of a window's rows are exactly those launch_rows_from_compact
-// builds for these rows of the same bytes (row_begin, row_raw from the common `base`), kept or rejected by the same
-// rules, with one status per ENTRY:
-//   header (k_r2_headers itself): a header that fails rejects the window's rows (n_bad_rows = win[1], first_bad_row =
-//   win[0], written by k_r2w_scan_blocks).
+//   A blob that fails is read no further: its window's rows are empty lists of scale 0.0f with no raw plane, and
+//   all rejected (n_bad_rows = win[1], first_bad_row = win[0]).
 //   prefix (k_r2w_prefix): the pairs and the rows of raw frames IN FRONT of the window, a reduction over the is_raw
 //   and cnt sections of rows [0, win[0]) - 4096 rows per workgroup, one vector atomic add per workgroup and sum into
 //   the entry's status.  No row in front of a window gets a table entry, none has its list read or is validated.
-//   Not launched when every window starts at its blob's row 0.
-//   scans and rows (k_r2w_scan_rows, k_r2w_scan_blocks, k_r2w_rows): the window's own rows through the scans and
-//   the row check of R2 (the same device functions), the origin of an entry being the prefix of its window.
-//   first_bad_row / n_bad_rows count the window's rows in the blob's row numbering.  kCompactPairSum / kCompactRawSum
-//   are never set: nothing behind a window is read.  No load leaves [address, address + capacity).
-// workspace: rows_from_compact_window_bytes(M) = 5 row arrays of align256(8 M), align256(4 M), align256(4 M),
-// align256(8 M), align256(8 M) bytes (32 B per WINDOW row) + 2 x align256(8 ceil(M / 1024)) bytes of block sums, M
-// counted as 1 when 0, align256 = rounding up to 256: nothing in it is per row of a blob.  Five launches (four
-// without the prefix) whatever n_entries (up to 65535; one more prefix launch per 65535 beyond), no synchronisation, no
-// workgroup waits for another.  max_front: the largest win[0] of the entries, or a bound of it (it sizes the prefix
-// launch).
-// Fixed slots (glc_decode_crops_device_store): an entry may own MORE table rows than its window has - first_row of
-// the next entry lies further on, and M counts the slots.  The rows of a slot behind the window are empty rows
-// (count 0, scale 0.0f, no raw plane) that report nothing; win[1] may then be 0.  verdict (null, or n_entries device
-// words): bits that join kCompactBadHeader in the status of an entry whose header check fails - the draw planner's
-// word about an entry it emptied (cap 0: the capacity pre-check fails it and nothing is read).
-uint64_t rows_from_compact_window_bytes(uint32_t M);
-hipError_t launch_rows_from_compact_window(const CompactBlob *dir, const CompactBlob &one, uint32_t n_entries, uint32_t M,
-                                           uint32_t ch, uint32_t max_front, const void *base, void *workspace,
-                                           CompactStatus *status, hipStream_t s, DecodeRows *rows,
-                                           const uint32_t *verdict = nullptr);
+//   Not launched when every window starts at its blob's row 0 (mode.max_front == 0).
+//   scans (k_r2_scan_rows, k_r2_scan_blocks): row_begin = exclusive 64-bit sum of cnt over the blob's rows in
+//   front (rows of raw frames count 0 whatever their cnt says), raw plane = rows of raw frames in front: sums
+//   inside blocks of 1024 table rows, one workgroup scans the block sums in chunks of 1024 and takes each entry's
+//   own origin - the running sums at its first row minus its window's prefix - out of them.
+//   rows (k_r2_rows, one wave per row): a compressed row is kept when cnt <= 1024, row_begin + cnt <= n_pairs and
+//   its bins ascend strictly below 1024; the rows of a raw frame when the frame's planes lie below n_raw_rows
+//   and inside `bytes`.  A row that is not kept becomes the empty list with its stored scale and no raw plane.
+//   first_bad_row / n_bad_rows count the window's rows in the blob's row numbering.
+//   No load leaves [address, address + capacity), and nothing behind a window is read.
+// mode {totals, max_front, verdict}.  totals: a launch of WHOLE blobs, every win = {0, rows} and max_front 0.  Each
+// entry's two sums are compared with the totals its header promised (kCompactPairSum / kCompactRawSum: reported, they
+// reject nothing), and M == 0 queues the header kernel alone.  Without it - a launch of windows - the sums say nothing
+// about the totals, so the two flags are never set, also where a window covers its blob; M == 0 is refused.
+// max_front: the largest win[0] of the entries, or a bound of it (it sizes the prefix launch).  verdict (null, or
+// n_entries device words): bits that
+// join kCompactBadHeader in the status of an entry whose header check fails - the draw planner's word about an entry
+// it emptied (cap 0: the capacity pre-check fails it and nothing is read).
+// Fixed slots (glc_decode_crops_device_store): an entry of a window launch may own MORE table rows than its window
+// has - first_row of the next entry lies further on, and M counts the slots.  The rows of a slot behind the window
+// are empty rows (count 0, scale 0.0f, no raw plane) that report nothing; win[1] may then be 0.
+// workspace: rows_from_compact_bytes(M) = 5 row arrays of align256(8 M), align256(4 M), align256(4 M), align256(8 M),
+// align256(8 M) bytes (32 B per TABLE row) + 2 x align256(8 ceil(M / 1024)) bytes of block sums, M counted as 1 when
+// 0, align256 = rounding up to 256: nothing in it is per row of a blob.  It stays untouched while *rows is in use.
+// Four launches, five with the prefix, whatever n_entries (up to 65535; one more prefix launch per 65535 beyond), no
+// synchronisation, no workgroup waits for another; any_raw is set (the host does not know).
+struct CompactBlob {
+  uint64_t addr, cap;
+  uint32_t first_row, rows;
+  uint32_t win[2];  // first row and row count of the window inside the blob; a whole blob: {0, rows}
+};
+constexpr uint32_t kCompactBadHeader = 1u, kCompactRowBounds = 2u, kCompactNotCanonical = 4u, kCompactRawRange = 8u,
+                   kCompactPairSum = 16u, kCompactRawSum = 32u;
+struct CompactStatus {  // 64 bytes per entry
+  uint32_t flags, header_ok;
+  uint64_t n_bad_rows, first_bad_row;  // first_bad_row: ~0 while no row has been rejected
+  uint64_t n_pairs, n_raw_rows, bytes;  // of a header that passed
+  uint64_t pairs_before, raw_before;    // running sums of the launch at the entry's first row minus its window's prefix, mod 2^64
+};
+struct R2Mode {
+  bool totals;
+  uint32_t max_front;
+  const uint32_t *verdict;
+};
+uint64_t rows_from_compact_bytes(uint32_t M);
+hipError_t launch_rows_from_compact(const CompactBlob *dir, const CompactBlob &one, uint32_t n_entries, uint32_t M, uint32_t ch,
+                                    const R2Mode &mode, const void *base, void *workspace, CompactStatus *status, hipStream_t s,
+                                    DecodeRows *rows);
 // variant (include/glc_debug.h): 0 = shipped (k_imdct_plan + k_imdct_apply, absent row pairs skipped
 // by scalar branches); 1 = one row per workgroup (the cross-check kernel); 2 = plan + apply without
 // the skip; 3 = without the issue-priority schedule; 4 = skipping in row pairs only.  All but 1 need a workspace `plan` of imdct_plan_bytes(plan_groups) bytes,

@@ -378,8 +378,8 @@ __device__ __forceinline__ void quantize_body(const DeviceTables &tb, const floa
     if (lane == 0) {
       const unsigned frame = m / ch, c = m % ch;
       unsigned char *rec = records + static_cast<size_t>(frame) * rec_bytes;
-      *reinterpret_cast<float *>(rec + 8 + 8 * c) = sc;
-      *reinterpret_cast<unsigned *>(rec + 8 + 8 * c + 4) = cnt;
+      record_scale(rec, c) = sc;
+      record_nnz(rec, c) = cnt;
     }
   }
 
@@ -402,7 +402,7 @@ __device__ __forceinline__ void quantize_body(const DeviceTables &tb, const floa
       const unsigned long long raw_size = 2ull * kFrameI * ch;    // :518
       use_raw = static_cast<float>(compressed) >= mul_rn(static_cast<float>(raw_size), 0.85f);  // :521
       if (c == 0 && lane == 0) {
-        *reinterpret_cast<unsigned *>(rec) = use_raw ? 1u : 0u;
+        record_raw(rec) = use_raw ? 1u : 0u;
         *reinterpret_cast<unsigned *>(rec + 4) = 0u;
       }
     }
@@ -451,14 +451,14 @@ __global__ __launch_bounds__(256) void k_decide_raw(DeviceTables tb, PcmView pcm
   const unsigned ch = pcm.ch;
   unsigned long long compressed = 0;
   for (unsigned c = 0; c < ch; ++c)
-    compressed += 8ull + 4ull * *reinterpret_cast<const unsigned *>(rec + 8 + 8 * c + 4);  // :507-511
+    compressed += 8ull + 4ull * record_nnz(rec, c);  // :507-511
   compressed += 8ull + 4ull * ch;  // :513
   compressed += 64ull;             // :515
   const unsigned long long raw_size = 2ull * kFrameI * ch;  // :518
   const bool use_raw =
       static_cast<float>(compressed) >= mul_rn(static_cast<float>(raw_size), 0.85f);  // :521
   if (threadIdx.x == 0) {
-    *reinterpret_cast<unsigned *>(rec) = use_raw ? 1u : 0u;
+    record_raw(rec) = use_raw ? 1u : 0u;
     *reinterpret_cast<unsigned *>(rec + 4) = 0u;
   }
   if (!use_raw) return;
@@ -1220,6 +1220,18 @@ __device__ __forceinline__ void scan_rows_1024(F count, unsigned M, W *__restric
   }
 }
 
+// A workgroup of 1024 threads: s[t] becomes the sum of the `mine` of threads 0 .. t (Hillis-Steele, inclusive).
+__device__ __forceinline__ void scan_sum_1024(unsigned long long *s /* LDS, [1024] */, unsigned long long mine) {
+  s[threadIdx.x] = mine;
+  __syncthreads();
+  for (int off = 1; off < 1024; off <<= 1) {
+    const unsigned long long t = threadIdx.x >= static_cast<unsigned>(off) ? s[threadIdx.x - off] : 0ull;
+    __syncthreads();
+    s[threadIdx.x] += t;
+    __syncthreads();
+  }
+}
+
 __device__ __forceinline__ void scan_block_sums(unsigned long long *__restrict__ blk, unsigned long long *__restrict__ blk_raw,
                                                 unsigned n, unsigned long long *s /* LDS, [1024] */,
                                                 unsigned long long sums[2]) {
@@ -1230,14 +1242,7 @@ __device__ __forceinline__ void scan_block_sums(unsigned long long *__restrict__
     for (unsigned b0 = 0; b0 < n; b0 += 1024) {
       const unsigned i = b0 + threadIdx.x;
       const unsigned long long mine = i < n ? v[i] : 0ull;
-      s[threadIdx.x] = mine;
-      __syncthreads();
-      for (int off = 1; off < 1024; off <<= 1) {
-        const unsigned long long t = threadIdx.x >= static_cast<unsigned>(off) ? s[threadIdx.x - off] : 0ull;
-        __syncthreads();
-        s[threadIdx.x] += t;
-        __syncthreads();
-      }
+      scan_sum_1024(s, mine);
       if (i < n) v[i] = carry + s[threadIdx.x] - mine;  // exclusive
       const unsigned long long chunk_total = s[1023];
       __syncthreads();
@@ -1287,9 +1292,9 @@ __global__ __launch_bounds__(256) void k_pack_scan_rows(const unsigned char *__r
         const unsigned frame = m / ch, c = m % ch;
         const unsigned slot = SEG ? fmap[frame].x : frame;
         const unsigned char *rec = records + static_cast<size_t>(slot) * rec_bytes;
-        const unsigned raw = *reinterpret_cast<const unsigned *>(rec);
-        const unsigned nnz = min(*reinterpret_cast<const unsigned *>(rec + 8 + 8 * c + 4), static_cast<unsigned>(kHopI));
-        scales[m] = *reinterpret_cast<const float *>(rec + 8 + 8 * c);
+        const unsigned raw = record_raw(rec);
+        const unsigned nnz = min(record_nnz(rec, c), static_cast<unsigned>(kHopI));
+        scales[m] = record_scale(rec, c);
         cnt[m] = raw ? 0u : nnz;
         if (c == 0) is_raw[frame] = raw ? 1 : 0;
         return raw ? (1u << kP1RawShift) : nnz;
@@ -1310,13 +1315,7 @@ __global__ __launch_bounds__(1024) void k_pack_scan_blocks(unsigned long long *_
   if (threadIdx.x == 0) {
     totals[0] = n_pairs;
     totals[1] = n_raw_rows;
-    unsigned long long *h = reinterpret_cast<unsigned long long *>(blob);
-    h[0] = kCompactMagic | (static_cast<unsigned long long>(ch) << 32);  // magic, channels
-    h[1] = n_frames;
-    h[2] = n_pairs;
-    h[3] = n_raw_rows;
-    h[4] = raw_off + n_raw_rows * 4096ull;
-    h[5] = h[6] = h[7] = 0ull;
+    *reinterpret_cast<CompactHeader *>(blob) = compact_header(ch, n_frames, n_pairs, n_raw_rows, raw_off + n_raw_rows * 4096ull);
   }
   if (threadIdx.x < 64 && pairs_end + threadIdx.x < raw_off) blob[pairs_end + threadIdx.x] = 0;  // deterministic padding
 }
@@ -1373,7 +1372,7 @@ __global__ __launch_bounds__(256) void k_pack_rows(const unsigned char *__restri
   }
   const unsigned char *rec = records + static_cast<size_t>(slot) * rec_bytes;
   const short *qrow = reinterpret_cast<const short *>(rec + hdr_bytes) + static_cast<size_t>(c) * kFrameI;
-  const bool raw = *reinterpret_cast<const unsigned *>(rec) != 0;
+  const bool raw = record_raw(rec) != 0;
   // the raw section starts behind the pairs; the room of a compressed row is the count P1 left in the blob
   short4 *raw_dst = raw ? reinterpret_cast<short4 *>(blob + compact_raw_offset(l, totals[0]) + at.raw * (kFrameI * 2ull)) : nullptr;
   const unsigned room = raw ? 0u : reinterpret_cast<const unsigned *>(blob + l.o_cnt)[m];
@@ -1397,8 +1396,8 @@ __global__ __launch_bounds__(256) void k_pack_rows(const unsigned char *__restri
 // Ordinary stores only; the cursor needs no atomics because rounds run in stream order.
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ unsigned store_row_word(const unsigned char *__restrict__ rec, unsigned c) {
-  const unsigned nnz = min(*reinterpret_cast<const unsigned *>(rec + 8 + 8 * c + 4), static_cast<unsigned>(kHopI));
-  return *reinterpret_cast<const unsigned *>(rec) ? (1u << kP1RawShift) : nnz;
+  const unsigned nnz = min(record_nnz(rec, c), static_cast<unsigned>(kHopI));
+  return record_raw(rec) ? (1u << kP1RawShift) : nnz;
 }
 
 __global__ __launch_bounds__(256) void k_store_scan_rows(const unsigned char *__restrict__ records, unsigned M, unsigned ch,
@@ -1441,14 +1440,7 @@ __global__ __launch_bounds__(1024) void k_store_place(unsigned long long *blk, u
       clip_base[2ull * k + 1] = a.raw;
       bytes = compact_raw_offset(compact_layout(ch, n_frames), n_pairs) + n_raw_rows * (kFrameI * 2ull);
     }
-    s[threadIdx.x] = bytes;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-      const unsigned long long t = threadIdx.x >= static_cast<unsigned>(off) ? s[threadIdx.x - off] : 0ull;
-      __syncthreads();
-      s[threadIdx.x] += t;
-      __syncthreads();
-    }
+    scan_sum_1024(s, bytes);
     const unsigned long long offset = carry + s[threadIdx.x] - bytes;  // exclusive: every size is a multiple of 64
     const unsigned long long chunk_total = s[1023];
     __syncthreads();
@@ -1460,15 +1452,7 @@ __global__ __launch_bounds__(1024) void k_store_place(unsigned long long *blk, u
       e[1] = bytes;
       e[2] = n_pairs;
       e[3] = n_raw_rows | (stored ? 1ull << 32 : 0ull);
-      if (stored) {
-        unsigned long long *h = reinterpret_cast<unsigned long long *>(arena + offset);
-        h[0] = kCompactMagic | (static_cast<unsigned long long>(ch) << 32);  // magic, channels
-        h[1] = n_frames;
-        h[2] = n_pairs;
-        h[3] = n_raw_rows;
-        h[4] = bytes;
-        h[5] = h[6] = h[7] = 0ull;
-      }
+      if (stored) *reinterpret_cast<CompactHeader *>(arena + offset) = compact_header(ch, n_frames, n_pairs, n_raw_rows, bytes);
     }
   }
   if (threadIdx.x == 0) *cursor = carry;
@@ -1497,10 +1481,10 @@ __global__ __launch_bounds__(256) void k_store_rows(const unsigned char *__restr
   at.pairs -= clip_base[2ull * fm.y];
   at.raw -= clip_base[2ull * fm.y + 1];
   const unsigned char *rec = records + static_cast<size_t>(fm.x) * rec_bytes;
-  const bool raw = *reinterpret_cast<const unsigned *>(rec) != 0;
+  const bool raw = record_raw(rec) != 0;
   const unsigned room = raw ? 0u : store_row_word(rec, c);
   if (lane == 0) {
-    reinterpret_cast<unsigned *>(blob + l.o_scale)[m_rel] = *reinterpret_cast<const unsigned *>(rec + 8 + 8 * c);  // the scale's bits
+    reinterpret_cast<unsigned *>(blob + l.o_scale)[m_rel] = __float_as_uint(record_scale(rec, c));
     reinterpret_cast<unsigned *>(blob + l.o_cnt)[m_rel] = room;
     if (c == 0) blob[l.o_israw + (frame - cl.x)] = raw ? 1 : 0;
   }
@@ -1565,9 +1549,9 @@ __global__ __launch_bounds__(256) void k_rows_from_records(const unsigned char *
       stat_clip = fm.y;
     }
     const unsigned char *rec = records + static_cast<size_t>(frame) * rec_bytes;
-    const unsigned raw = *reinterpret_cast<const unsigned *>(rec);
-    const float scale = *reinterpret_cast<const float *>(rec + 8 + 8 * c);
-    const unsigned room = min(*reinterpret_cast<const unsigned *>(rec + 8 + 8 * c + 4), static_cast<unsigned>(kHopI));
+    const unsigned raw = record_raw(rec);
+    const float scale = record_scale(rec, c);
+    const unsigned room = min(record_nnz(rec, c), static_cast<unsigned>(kHopI));
     unsigned n_row = 0;
     if (raw) {
       stat_raw = c == 0 ? 1u : 0u;
@@ -1639,24 +1623,38 @@ __global__ __launch_bounds__(256) void k_rows_from_records(const unsigned char *
 
 // ------------------------------------------------------------------------------------------
 // R2: compact blobs -> the row tables D1 reads, without the host and without moving the payload (glc_kernels.h
-// launch_rows_from_compact has the rules).  The blob is almost the table already: cnt is row_cnt, scale is
-// row_scale, the pairs are the rows' lists back to back - what is missing are the two exclusive scans (pairs and
-// raw rows in front of a row; the shared scan above P1) and the checks build_row_table makes on the host, because
-// D1 trusts its rows.  Sections are found with glc_common.h compact_sections, as the host finds them.
-//   k_r2_headers      one thread per blob: glc_common.h compact_header_fault behind a capacity pre-check; fills
-//                     the blob's CompactStatus
-//   k_r2_scan_rows    scan_rows_1024 over the blob's own cnt (nothing for a blob whose header failed).  The
+// launch_rows_from_compact has the rules): the tables of rows [win[0], win[0] + win[1]) of each entry's blob, without
+// a table entry for any row in front; a whole blob is the window {0, rows}.  The blob is almost the table already:
+// cnt is row_cnt, scale is row_scale, the pairs are the rows' lists back to back - what is missing are the two
+// exclusive scans (pairs and raw rows in front of a row; the shared scan above P1) and the checks build_row_table
+// makes on the host, because D1 trusts its rows.  Sections are found with glc_common.h compact_sections, as the host
+// finds them.
+//   k_r2_headers      one thread per entry: glc_common.h compact_header_fault behind a capacity pre-check; fills
+//                     the entry's CompactStatus, the two origin words with 0
+//   k_r2w_prefix      (only when a window has rows in front) workgroup (x, entry) sums rows [4096 x, 4096 x + 4096)
+//                     below win[0] - cnt of the rows of compressed frames, one per row of a raw frame, from the cnt
+//                     and is_raw sections alone - in registers, across the wave by shuffles, across the four waves
+//                     through LDS, and adds its two sums to the entry's origin words with one vector atomic each
+//                     (64-bit integer adds: the result does not depend on their order)
+//   k_r2_scan_rows    scan_rows_1024 over the windows' own cnt (nothing for a blob whose header failed).  The
 //                     row's word waits in its row_raw_len slot for k_r2_rows.
-//   k_r2_scan_blocks  scan_block_sums, then per blob the running sums at its first row (its rows' origin) and
-//                     the two totals the header promised (reported, they reject nothing)
-//   k_r2_rows         one wave per row: bounds, then the list in strides of 64 - lane l compares its bin with
-//                     lane l - 1's (shuffle; lane 0 takes the previous stride's last) - and the row's arrays
-// Rows of several blobs follow each other (glc_decode_batch_device_compact): a row finds its blob by a binary
-// search over the directory's first rows, and the scans simply run across the blobs - a blob's origin is
+//   k_r2_scan_blocks  scan_block_sums, then per entry the origin r2_row subtracts - the launch's running sums at
+//                     the entry's first row MINUS the window's prefix (mod 2^64), so that r2_row finds the row's
+//                     place in its blob - and for a header that failed the rows that rejects: the window's.  TOTALS
+//                     (the launch's word, a launch of whole blobs): the entry's two sums against the totals its
+//                     header promised (reported, they reject nothing)
+//   k_r2_rows         one wave per row (r2_row): bounds, then the list in strides of 64 - lane l compares its bin
+//                     with lane l - 1's (shuffle; lane 0 takes the previous stride's last) - and the row's arrays
+// Rows of several entries follow each other (glc_decode_batch_device_compact): a row finds its entry by a binary
+// search over the directory's first rows, and the scans simply run across the entries - an entry's origin is
 // subtracted again.  The sums of a blob whose header failed are taken over nothing.
+// An entry may own more table rows than its window has (the next entry's first_row lies further on: the fixed slots
+// of glc_decode_crops_device_store, or an entry whose window is empty).  Row first_row + j with j >= win[1] is an
+// empty row: the scans see the word 0, k_r2_rows writes {0, 0, 0.0f, -1, 0} and reports nothing.  WINDOW false (the
+// scan-rows and rows kernels of a launch of whole blobs): win is {0, rows}, so that test and the offset are left out.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned r2_find_blob(const CompactBlob *__restrict__ dir, unsigned n_blobs, unsigned m) {
-  unsigned lo = 0, hi = n_blobs;  // the last blob whose first_row <= m (first_row ascends from 0)
+__device__ __forceinline__ unsigned r2_find_blob(const CompactBlob *__restrict__ dir, unsigned n_entries, unsigned m) {
+  unsigned lo = 0, hi = n_entries;  // the last entry whose first_row <= m (first_row ascends from 0)
   while (hi - lo > 1) {
     const unsigned mid = (lo + hi) >> 1;
     if (dir[mid].first_row <= m) lo = mid;
@@ -1699,22 +1697,25 @@ __device__ __forceinline__ unsigned long long r2_row_word(const CompactBlob e, u
   return blob[l.o_israw + lm / ch] ? (1ull << kR2RawShift) : reinterpret_cast<const unsigned *>(blob + l.o_cnt)[lm];
 }
 
-__global__ __launch_bounds__(256) void k_r2_scan_rows(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned n_blobs,
+template <bool WINDOW>
+__global__ __launch_bounds__(256) void k_r2_scan_rows(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned n_entries,
                                                        unsigned M, unsigned ch, const CompactStatus *__restrict__ status,
                                                        unsigned long long *__restrict__ loc,
                                                        unsigned long long *__restrict__ blk,
                                                        unsigned long long *__restrict__ blk_raw) {
   scan_rows_1024<unsigned long long, kR2RawShift>(
       [&](unsigned m) -> unsigned long long {
-        const unsigned b = dir ? r2_find_blob(dir, n_blobs, m) : 0u;
+        const unsigned b = dir ? r2_find_blob(dir, n_entries, m) : 0u;
         const CompactBlob e = dir ? dir[b] : one;
-        if (!status[b].header_ok) return 0ull;
-        return r2_row_word(e, ch, m - e.first_row);
+        const unsigned j = m - e.first_row;  // row j of the entry's slot; behind the window: an empty row
+        if ((WINDOW && j >= e.win[1]) || !status[b].header_ok) return 0ull;
+        return r2_row_word(e, ch, WINDOW ? e.win[0] + j : j);
       },
       M, loc, blk, blk_raw);
 }
 
-__global__ __launch_bounds__(1024) void k_r2_scan_blocks(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned n_blobs,
+template <bool TOTALS>
+__global__ __launch_bounds__(1024) void k_r2_scan_blocks(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned n_entries,
                                                           unsigned M, unsigned long long *__restrict__ blk,
                                                           unsigned long long *__restrict__ blk_raw, unsigned n,
                                                           const unsigned long long *__restrict__ loc,
@@ -1723,17 +1724,20 @@ __global__ __launch_bounds__(1024) void k_r2_scan_blocks(const CompactBlob *__re
   unsigned long long sums[2];
   scan_block_sums(blk, blk_raw, n, s, sums);
   __syncthreads();  // this workgroup's own stores to blk / blk_raw are read below
-  // per blob: the running sums at its first row and behind its last one
-  for (unsigned b = threadIdx.x; b < n_blobs; b += 1024) {
+  // per entry: the running sums at its first row and (TOTALS) behind its window's last one
+  for (unsigned b = threadIdx.x; b < n_entries; b += 1024) {
     const CompactBlob e = dir ? dir[b] : one;
-    const unsigned long long r0 = e.first_row, r1 = r0 + e.rows;
+    const unsigned long long r0 = e.first_row, r1 = r0 + e.win[1];
     RowsBefore at0{sums[0], sums[1]}, at1 = at0;
     if (r0 < M) at0 = rows_before<kR2RawShift>(loc[r0], blk, blk_raw, r0);
-    if (r1 < M) at1 = rows_before<kR2RawShift>(loc[r1], blk, blk_raw, r1);
+    if (TOTALS && r1 < M) at1 = rows_before<kR2RawShift>(loc[r1], blk, blk_raw, r1);
     CompactStatus *st = status + b;
-    st->pairs_before = at0.pairs;
-    st->raw_before = at0.raw;
-    if (st->header_ok) {
+    st->pairs_before = at0.pairs - st->pairs_before;  // the window's prefix is there: k_r2w_prefix's sums, or k_r2_headers' 0
+    st->raw_before = at0.raw - st->raw_before;
+    if (!st->header_ok) {  // k_r2_headers reported the blob's rows
+      st->n_bad_rows = e.win[1];
+      st->first_bad_row = e.win[0];
+    } else if constexpr (TOTALS) {
       unsigned f = st->flags;
       if (at1.pairs - at0.pairs != st->n_pairs) f |= kCompactPairSum;
       if (at1.raw - at0.raw != st->n_raw_rows) f |= kCompactRawSum;
@@ -1742,8 +1746,8 @@ __global__ __launch_bounds__(1024) void k_r2_scan_blocks(const CompactBlob *__re
   }
 }
 
-// What one wave of k_r2_rows / k_r2w_rows does with row `lm` of blob `e`, table row `m` of the launch: the checks, the
-// row's five table entries, and what it has to say in the status `st` of its entry.
+// What one wave of k_r2_rows does with row `lm` of blob `e`, table row `m` of the launch: the checks, the row's five
+// table entries, and what it has to say in the status `st` of its entry.
 __device__ __forceinline__ void r2_row(const CompactBlob &e, CompactStatus *st, unsigned ch, unsigned long long base_addr,
                                        unsigned lm, unsigned m, const unsigned long long *__restrict__ blk,
                                        const unsigned long long *__restrict__ blk_raw, unsigned long long *__restrict__ row_begin,
@@ -1808,7 +1812,8 @@ __device__ __forceinline__ void r2_row(const CompactBlob &e, CompactStatus *st, 
   }
 }
 
-__global__ __launch_bounds__(256) void k_r2_rows(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned n_blobs,
+template <bool WINDOW>
+__global__ __launch_bounds__(256) void k_r2_rows(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned n_entries,
                                                   unsigned M, unsigned ch, unsigned long long base_addr,
                                                   const unsigned long long *__restrict__ blk,
                                                   const unsigned long long *__restrict__ blk_raw,
@@ -1820,30 +1825,17 @@ __global__ __launch_bounds__(256) void k_r2_rows(const CompactBlob *__restrict__
   const unsigned long long m64 = static_cast<unsigned long long>(blockIdx.x) * 4ull + (threadIdx.x >> 6);
   if (m64 >= M) return;
   const unsigned m = static_cast<unsigned>(m64);
-  const unsigned b = dir ? r2_find_blob(dir, n_blobs, m) : 0u;
+  const unsigned b = dir ? r2_find_blob(dir, n_entries, m) : 0u;
   const CompactBlob e = dir ? dir[b] : one;
-  r2_row(e, status + b, ch, base_addr, m - e.first_row, m, blk, blk_raw, row_begin, row_cnt, row_scale, row_raw, row_raw_len, lane);
+  const unsigned j = m - e.first_row;
+  if (WINDOW && j >= e.win[1]) {  // behind the window: the empty row, and nothing to report
+    if (lane == 0) row_begin[m] = 0ull, row_cnt[m] = 0u, row_scale[m] = 0.0f, row_raw[m] = -1ll, row_raw_len[m] = 0ull;
+    return;
+  }
+  r2_row(e, status + b, ch, base_addr, WINDOW ? e.win[0] + j : j, m, blk, blk_raw, row_begin, row_cnt, row_scale, row_raw, row_raw_len,
+         lane);
 }
 
-// ------------------------------------------------------------------------------------------
-// R2 of windows (glc_kernels.h launch_rows_from_compact_window has the rules): the tables of rows [win[0], win[0] +
-// win[1]) of each entry's blob, as R2 builds them for those rows, without a table entry for any row in front.
-//   k_r2_headers       as it stands, one thread per entry: the header is the blob's, and the two origin words start at 0
-//   k_r2w_prefix       what lies in front of a window: workgroup (x, entry) sums rows [4096 x, 4096 x + 4096) below
-//                      win[0] - cnt of the rows of compressed frames, one per row of a raw frame, from the cnt and
-//                      is_raw sections alone - in registers, across the wave by shuffles, across the four waves through
-//                      LDS, and adds its two sums to the entry's origin words with one vector atomic each (64-bit
-//                      integer adds: the result does not depend on their order)
-//   k_r2w_scan_rows    scan_rows_1024 over the windows' own rows
-//   k_r2w_scan_blocks  scan_block_sums, then per entry the origin R2 subtracts: the launch's running sums at the
-//                      window's first row MINUS the window's prefix (mod 2^64), so that r2_row finds the row's place in
-//                      its blob with the arithmetic it has; and for a header that failed the rows that rejects: the
-//                      window's, not the blob's
-//   k_r2w_rows         one wave per window row: r2_row
-// An entry may own more table rows than its window has (the next entry's first_row lies further on: the fixed slots
-// of glc_decode_crops_device_store, or an entry whose window is empty).  Row first_row + j with j >= win[1] is an
-// empty row: the scans see the word 0, k_r2w_rows writes {0, 0, 0.0f, -1, 0} and reports nothing.
-// ------------------------------------------------------------------------------------------
 constexpr unsigned kR2wPrefixRows = 4096;  // rows in front of a window that one workgroup of k_r2w_prefix sums
 
 __global__ __launch_bounds__(256) void k_r2w_prefix(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned b0, unsigned ch,
@@ -1872,66 +1864,6 @@ __global__ __launch_bounds__(256) void k_r2w_prefix(const CompactBlob *__restric
     if (pairs) atomicAdd(reinterpret_cast<unsigned long long *>(&st->pairs_before), pairs);
     if (raw) atomicAdd(reinterpret_cast<unsigned long long *>(&st->raw_before), raw);
   }
-}
-
-__global__ __launch_bounds__(256) void k_r2w_scan_rows(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned n_entries,
-                                                        unsigned M, unsigned ch, const CompactStatus *__restrict__ status,
-                                                        unsigned long long *__restrict__ loc,
-                                                        unsigned long long *__restrict__ blk,
-                                                        unsigned long long *__restrict__ blk_raw) {
-  scan_rows_1024<unsigned long long, kR2RawShift>(
-      [&](unsigned m) -> unsigned long long {
-        const unsigned b = dir ? r2_find_blob(dir, n_entries, m) : 0u;
-        const CompactBlob e = dir ? dir[b] : one;
-        // a row of the entry's slot behind its window (the fixed slots of the store draw): an empty row
-        if (m - e.first_row >= e.win[1] || !status[b].header_ok) return 0ull;
-        return r2_row_word(e, ch, e.win[0] + (m - e.first_row));
-      },
-      M, loc, blk, blk_raw);
-}
-
-__global__ __launch_bounds__(1024) void k_r2w_scan_blocks(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned n_entries,
-                                                           unsigned long long *__restrict__ blk,
-                                                           unsigned long long *__restrict__ blk_raw, unsigned n,
-                                                           const unsigned long long *__restrict__ loc,
-                                                           CompactStatus *__restrict__ status) {
-  __shared__ unsigned long long s[1024];
-  unsigned long long sums[2];
-  scan_block_sums(blk, blk_raw, n, s, sums);
-  __syncthreads();  // this workgroup's own stores to blk / blk_raw are read below
-  for (unsigned b = threadIdx.x; b < n_entries; b += 1024) {
-    const unsigned r0 = dir ? dir[b].first_row : one.first_row;  // < M: a window has rows
-    const RowsBefore at0 = rows_before<kR2RawShift>(loc[r0], blk, blk_raw, r0);
-    CompactStatus *st = status + b;
-    st->pairs_before = at0.pairs - st->pairs_before;  // k_r2w_prefix left the window's prefix there
-    st->raw_before = at0.raw - st->raw_before;
-    if (!st->header_ok) {  // k_r2_headers reported the blob's rows
-      st->n_bad_rows = dir ? dir[b].win[1] : one.win[1];
-      st->first_bad_row = dir ? dir[b].win[0] : one.win[0];
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void k_r2w_rows(const CompactBlob *__restrict__ dir, CompactBlob one, unsigned n_entries,
-                                                   unsigned M, unsigned ch, unsigned long long base_addr,
-                                                   const unsigned long long *__restrict__ blk,
-                                                   const unsigned long long *__restrict__ blk_raw,
-                                                   CompactStatus *__restrict__ status,
-                                                   unsigned long long *__restrict__ row_begin, unsigned *__restrict__ row_cnt,
-                                                   float *__restrict__ row_scale, long long *__restrict__ row_raw,
-                                                   unsigned long long *__restrict__ row_raw_len) {
-  const int lane = threadIdx.x & 63;
-  const unsigned long long m64 = static_cast<unsigned long long>(blockIdx.x) * 4ull + (threadIdx.x >> 6);
-  if (m64 >= M) return;
-  const unsigned m = static_cast<unsigned>(m64);
-  const unsigned b = dir ? r2_find_blob(dir, n_entries, m) : 0u;
-  const CompactBlob e = dir ? dir[b] : one;
-  if (m - e.first_row >= e.win[1]) {  // behind the window: the empty row, and nothing to report
-    if (lane == 0) row_begin[m] = 0ull, row_cnt[m] = 0u, row_scale[m] = 0.0f, row_raw[m] = -1ll, row_raw_len[m] = 0ull;
-    return;
-  }
-  r2_row(e, status + b, ch, base_addr, e.win[0] + (m - e.first_row), m, blk, blk_raw, row_begin, row_cnt, row_scale, row_raw,
-         row_raw_len, lane);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2849,53 +2781,34 @@ hipError_t launch_rows_from_records_batch(const uint8_t *records, uint32_t M, ui
 
 uint64_t rows_from_compact_bytes(uint32_t M) { return r2_tables(nullptr, M).bytes; }
 
-hipError_t launch_rows_from_compact(const CompactBlob *dir, const CompactBlob &one, uint32_t n_blobs, uint32_t M, uint32_t ch,
-                                    const void *base, void *workspace, CompactStatus *status, hipStream_t s,
+hipError_t launch_rows_from_compact(const CompactBlob *dir, const CompactBlob &one, uint32_t n_entries, uint32_t M, uint32_t ch,
+                                    const R2Mode &mode, const void *base, void *workspace, CompactStatus *status, hipStream_t s,
                                     DecodeRows *rows) {
   static_assert(sizeof(CompactBlob) == 32 && sizeof(CompactStatus) == 64, "read and written by the kernels as laid out here");
-  if (!workspace || !status || !rows || !base || ch == 0 || n_blobs == 0 || (!dir && n_blobs != 1)) return hipErrorInvalidValue;
-  if (M % ch) return hipErrorInvalidValue;  // every blob's rows are whole frames (a directory's entries: the caller's word)
-  if (!dir && ((one.addr & 63u) || one.first_row != 0 || one.rows != M || one.addr < reinterpret_cast<uintptr_t>(base)))
-    return hipErrorInvalidValue;
-  if (reinterpret_cast<uintptr_t>(base) & 63u) return hipErrorInvalidValue;
-  const R2Tables t = r2_tables(workspace, M);
-  const unsigned nblk = static_cast<unsigned>((static_cast<uint64_t>(M) + 1023) / 1024);
-  *rows = t.rows(base, base);
-  hipLaunchKernelGGL(k_r2_headers, dim3((n_blobs + 255) / 256), dim3(256), 0, s, dir, one, n_blobs, ch, status,
-                     static_cast<const unsigned *>(nullptr));
-  if (M == 0) return hipGetLastError();
-  hipLaunchKernelGGL(k_r2_scan_rows, dim3(nblk), dim3(256), 0, s, dir, one, n_blobs, M, ch, status, t.row_raw_len, t.blk, t.blk_raw);
-  hipLaunchKernelGGL(k_r2_scan_blocks, dim3(1), dim3(1024), 0, s, dir, one, n_blobs, M, t.blk, t.blk_raw, nblk, t.row_raw_len, status);
-  hipLaunchKernelGGL(k_r2_rows, dim3(static_cast<unsigned>((static_cast<uint64_t>(M) + 3) / 4)), dim3(256), 0, s, dir, one, n_blobs,
-                     M, ch, static_cast<unsigned long long>(reinterpret_cast<uintptr_t>(base)), t.blk, t.blk_raw, status, t.row_begin,
-                     t.row_cnt, t.row_scale, t.row_raw, t.row_raw_len);
-  return hipGetLastError();
-}
-
-uint64_t rows_from_compact_window_bytes(uint32_t M) { return r2_tables(nullptr, M).bytes; }
-
-hipError_t launch_rows_from_compact_window(const CompactBlob *dir, const CompactBlob &one, uint32_t n_entries, uint32_t M,
-                                           uint32_t ch, uint32_t max_front, const void *base, void *workspace,
-                                           CompactStatus *status, hipStream_t s, DecodeRows *rows, const uint32_t *verdict) {
   if (!workspace || !status || !rows || !base || ch == 0 || n_entries == 0 || (!dir && n_entries != 1)) return hipErrorInvalidValue;
-  if (M == 0 || M % ch) return hipErrorInvalidValue;  // whole frames, and every window has some (a directory's entries: the caller's word)
+  // whole frames; every window has some; whole blobs have nothing in front (a directory's entries: the caller's word)
+  if (M % ch || (M == 0 && !mode.totals) || (mode.totals && mode.max_front)) return hipErrorInvalidValue;
   if (!dir && ((one.addr & 63u) || one.first_row != 0 || one.win[1] != M || one.rows % ch || one.win[0] % ch ||
-               one.win[0] > one.rows || M > one.rows - one.win[0] || one.win[0] > max_front ||
-               one.addr < reinterpret_cast<uintptr_t>(base)))
+               one.win[0] > one.rows || M > one.rows - one.win[0] || one.win[0] > mode.max_front ||
+               (mode.totals && one.rows != M) || one.addr < reinterpret_cast<uintptr_t>(base)))
     return hipErrorInvalidValue;
   if (reinterpret_cast<uintptr_t>(base) & 63u) return hipErrorInvalidValue;
   const R2Tables t = r2_tables(workspace, M);
   const unsigned nblk = static_cast<unsigned>((static_cast<uint64_t>(M) + 1023) / 1024);
   *rows = t.rows(base, base);
-  hipLaunchKernelGGL(k_r2_headers, dim3((n_entries + 255) / 256), dim3(256), 0, s, dir, one, n_entries, ch, status, verdict);
-  if (max_front) {
-    const unsigned chunks = static_cast<unsigned>((static_cast<uint64_t>(max_front) + kR2wPrefixRows - 1) / kR2wPrefixRows);
+  hipLaunchKernelGGL(k_r2_headers, dim3((n_entries + 255) / 256), dim3(256), 0, s, dir, one, n_entries, ch, status, mode.verdict);
+  if (M == 0) return hipGetLastError();
+  if (mode.max_front) {
+    const unsigned chunks = static_cast<unsigned>((static_cast<uint64_t>(mode.max_front) + kR2wPrefixRows - 1) / kR2wPrefixRows);
     for (uint32_t b0 = 0; b0 < n_entries; b0 += 65535u)  // blockIdx.y is 16 bits wide
       hipLaunchKernelGGL(k_r2w_prefix, dim3(chunks, std::min(n_entries - b0, 65535u)), dim3(256), 0, s, dir, one, b0, ch, status);
   }
-  hipLaunchKernelGGL(k_r2w_scan_rows, dim3(nblk), dim3(256), 0, s, dir, one, n_entries, M, ch, status, t.row_raw_len, t.blk, t.blk_raw);
-  hipLaunchKernelGGL(k_r2w_scan_blocks, dim3(1), dim3(1024), 0, s, dir, one, n_entries, t.blk, t.blk_raw, nblk, t.row_raw_len, status);
-  hipLaunchKernelGGL(k_r2w_rows, dim3(static_cast<unsigned>((static_cast<uint64_t>(M) + 3) / 4)), dim3(256), 0, s, dir, one, n_entries,
+  const auto scan_rows = mode.totals ? k_r2_scan_rows<false> : k_r2_scan_rows<true>;
+  const auto scan_blocks = mode.totals ? k_r2_scan_blocks<true> : k_r2_scan_blocks<false>;
+  const auto table_rows = mode.totals ? k_r2_rows<false> : k_r2_rows<true>;
+  hipLaunchKernelGGL(scan_rows, dim3(nblk), dim3(256), 0, s, dir, one, n_entries, M, ch, status, t.row_raw_len, t.blk, t.blk_raw);
+  hipLaunchKernelGGL(scan_blocks, dim3(1), dim3(1024), 0, s, dir, one, n_entries, M, t.blk, t.blk_raw, nblk, t.row_raw_len, status);
+  hipLaunchKernelGGL(table_rows, dim3(static_cast<unsigned>((static_cast<uint64_t>(M) + 3) / 4)), dim3(256), 0, s, dir, one, n_entries,
                      M, ch, static_cast<unsigned long long>(reinterpret_cast<uintptr_t>(base)), t.blk, t.blk_raw, status, t.row_begin,
                      t.row_cnt, t.row_scale, t.row_raw, t.row_raw_len);
   return hipGetLastError();

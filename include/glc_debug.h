@@ -173,7 +173,7 @@ int glc_debug_compact_store_device(glc_ctx *ctx, const void *d_records, const ui
                                    uint16_t channels, void *d_arena, uint64_t arena_bytes, uint64_t *d_cursor,
                                    glc_store_entry *d_entries);
 
-/* R2 (launch_rows_from_compact) alone, exactly as glc_decode_device_compact launches it for ONE blob of `n_frames`
+/* R2 (launch_rows_from_compact, totals compared) alone, exactly as glc_decode_device_compact launches it for ONE blob of `n_frames`
  * frames at d_blob (64-byte aligned, blob_bytes >= the fixed sections): the row tables it builds come back to
  * the host - M = n_frames * channels entries each, any pointer may be NULL - with the status words.  row_begin
  * counts u32 and row_raw i16 from d_blob (-1: no raw plane).  Synchronises.  tests/test_compact_decode.py holds
@@ -183,11 +183,12 @@ int glc_debug_rows_from_compact(glc_ctx *ctx, const void *d_blob, uint64_t blob_
                                 uint64_t *row_begin, uint32_t *row_cnt, float *row_scale, int64_t *row_raw,
                                 uint64_t *row_raw_len, glc_compact_status *status);
 
-/* The windowed R2 (launch_rows_from_compact_window) alone, exactly as glc_decode_crops_device_compact launches it for
- * ONE window of a long clip: frames [first_frame, first_frame + frames) of the blob of `n_frames` frames at d_blob.
- * The tables of the window's frames * channels rows come back as above - row_begin and row_raw from d_blob, in the
- * blob's own terms, so they are the matching slices of glc_debug_rows_from_compact's - with the status words.
- * Synchronises.  tests/test_compact_crops.py holds windows at the scan's edges, and one behind row 1024 * 1024 of a
+/* R2 of a window (the same launch_rows_from_compact, totals not compared) alone, exactly as
+ * glc_decode_crops_device_compact launches it for ONE window of a long clip: frames [first_frame, first_frame + frames)
+ * of the blob of `n_frames` frames at d_blob.  The tables of the window's frames * channels rows come back as above -
+ * row_begin and row_raw from d_blob, in the blob's own terms, so they are the matching slices of
+ * glc_debug_rows_from_compact's, and for the window of all frames the same tables - with the status words.  Both hooks
+ * are one body.  Synchronises.  tests/test_compact_crops.py holds windows at the scan's edges, and one behind row 1024 * 1024 of a
  * blob of that many rows, to the model through this; tests/test_channel_axis.py the windows of the oracle's streams of
  * 4 to 513 channels. */
 int glc_debug_rows_from_compact_window(glc_ctx *ctx, const void *d_blob, uint64_t blob_bytes, uint64_t n_frames, uint16_t channels,

@@ -1,5 +1,6 @@
-"""Windows of stored clips: glc_decode_crops_device_compact, the windowed R2 behind it (launch_rows_from_compact_window
-through glc_debug_rows_from_compact_window) and Decoder.decode_compact_crops_tensor (DESIGN.md sections 3 and 4).
+"""Windows of stored clips: glc_decode_crops_device_compact, R2 of windows behind it (launch_rows_from_compact through
+glc_debug_rows_from_compact_window; the whole blob, glc_debug_rows_from_compact, is the window of all frames plus the
+totals check) and Decoder.decode_compact_crops_tensor (DESIGN.md sections 3 and 4).
 
 Every sample comparison is bit for bit - float32 viewed as uint32, tolerance 0.  The expectation is always the slice
 of a path that existed before: Decoder.decode_compact_tensor (glc_decode_device_compact) of the same bytes, which
@@ -9,6 +10,7 @@ computes and every element outside the crops must keep it.  Damaged blobs sit in
 with every count inside the buffer (compact_decode_cases.pack): the tests pin the defined result, they provoke
 nothing."""
 import ctypes as C
+import struct
 
 import numpy as np
 import pytest
@@ -262,6 +264,90 @@ def test_window_tables_behind_a_million_rows(glc_amd, torch):
     nf = edge + K.SCAN_BLOCK + 7
     buf, nbytes, want = K.big_mono(nf, (0, 5, edge - 1, edge, edge + 1, edge + 3, nf - 1))
     check_table_windows(glc_amd, torch, buf, nbytes, nf, 1, want, [(edge + 1, 5), (edge - 2, 9), (nf - 1, 1), (3, edge + 1025)])
+
+
+def all_tables(g, d_blob, cap_bytes, nf, ch, window):
+    """The five row tables (the scales as bits) and (flags, n_bad_rows, first_bad_row) of a blob through
+    glc_debug_rows_from_compact (window None), or of the window (first_frame, frames) through its window twin."""
+    tail = [C.c_void_p] * 6
+    if window is None:
+        f, mid, frames = g.lib.glc_debug_rows_from_compact, (), nf
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint16] + tail
+    else:
+        f, mid, frames = g.lib.glc_debug_rows_from_compact_window, tuple(window), window[1]
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint16, C.c_uint64, C.c_uint64] + tail
+    f.restype = C.c_int
+    m = frames * ch
+    arrays = [np.empty(m, t) for t in (np.uint64, np.uint32, np.uint32, np.int64, np.uint64)]   # begin, cnt, scale, raw, raw_len
+    st = (C.c_uint64 * 3)()
+    rc = f(ctx(g, "dec", ch)._h, d_blob.data_ptr(), cap_bytes, nf, ch, *mid, *[a.ctypes.data for a in arrays], C.addressof(st))
+    assert rc == 0
+    return arrays, (st[0] & 0xFFFFFFFF, st[1], st[2])
+
+
+def whole_and_window(g, torch, buf, cap_bytes, nf, ch):
+    """Both hooks over all frames of one blob: the tables must be bit-equal.  -> (tables, whole status, window status)."""
+    d_blob = upload(torch, buf)
+    torch.cuda.synchronize()
+    whole, st_whole = all_tables(g, d_blob, cap_bytes, nf, ch, None)
+    win, st_win = all_tables(g, d_blob, cap_bytes, nf, ch, (0, nf))
+    for name, a, b in zip(("row_begin", "row_cnt", "row_scale", "row_raw", "row_raw_len"), whole, win):
+        assert np.array_equal(a, b), name
+    return whole, st_whole, st_win
+
+
+@pytest.mark.parametrize("rows,ch", SCAN_SHAPES, ids=[f"rows-{r}-{c}ch" for r, c in SCAN_SHAPES])
+def test_whole_blob_is_the_window_of_all_frames_at_the_scan_edges(glc_amd, torch, rows, ch):
+    """The whole-blob R2 is the window {0, rows} plus the totals check: same five tables, same status, both K.tables."""
+    frames = CC.scan_blob(rows, ch)
+    buf, nbytes = K.pack(ch, frames)
+    (begin, cnt, _, raw, raw_len), st_whole, st_win = whole_and_window(glc_amd, torch, buf[:nbytes], nbytes, rows // ch, ch)
+    assert st_whole == st_win == (0, 0, 0)
+    want = K.tables(ch, frames)
+    assert np.array_equal(begin, want[0]) and np.array_equal(cnt, want[1]) and np.array_equal(raw, want[2])
+    assert np.array_equal(raw_len, np.where(want[2] >= 0, FRAME * ch, 0).astype(np.uint64))
+
+
+def header_fields(buf):
+    """(magic, channels, n_frames, n_pairs, n_raw_rows, bytes) of a packed blob."""
+    return struct.unpack("<IIQQQQ", buf[:40].tobytes())
+
+
+def test_whole_blob_and_window_agree_on_damaged_blobs(glc_amd, torch):
+    g = glc_amd
+    base, ch, nf = CC.stereo_stream(), 2, 8
+    clean_buf, clean_bytes = K.pack(ch, base)
+    want = K.tables(ch, base)
+    n_true = int(want[1].sum())
+
+    # a non-canonical list at row 7: one row rejected, by both, and every other row as in the clean blob
+    frames = CC.with_bad_list(base, 7)
+    assert all(frames[i // ch][1][i % ch] is base[i // ch][1][i % ch] for i in range(nf * ch) if i != 7)
+    assert list(frames[3][1][1].idx) == [3, 40, 40, 900]
+    buf, nbytes = K.pack(ch, frames)
+    (begin, cnt, _, raw, _), st_whole, st_win = whole_and_window(g, torch, buf, nbytes, nf, ch)
+    assert st_whole == st_win == (K.NOT_CANONICAL, 1, 7)
+    others = np.arange(nf * ch) != 7                      # the lists in the blob are those of `frames`: row 7 holds 4 pairs
+    assert (begin[7], cnt[7]) == (0, 0) and np.all(raw == -1)
+    assert np.array_equal(begin[others], K.tables(ch, frames)[0][others]) and np.array_equal(cnt[others], want[1][others])
+
+    # n_pairs one too large with a consistent `bytes`: the totals are the whole-blob launch's business alone
+    o_pairs = K.layout(ch, nf)[3]
+    buf, nbytes = K.pack(ch, base, n_pairs=n_true + 1, bytes_field=K.align64(o_pairs + 4 * (n_true + 1)))
+    hc, hd = header_fields(clean_buf), header_fields(buf)
+    assert hd[3] == hc[3] + 1 and hd[5] == K.align64(o_pairs + 4 * hd[3]) and (hd[:3], hd[4]) == (hc[:3], hc[4])
+    assert np.array_equal(buf[64:], clean_buf[64:])
+    (begin, cnt, _, raw, _), st_whole, st_win = whole_and_window(g, torch, buf, buf.size, nf, ch)
+    assert st_whole == (K.PAIR_SUM, 0, 0) and st_win == (0, 0, 0)
+    assert np.array_equal(begin, want[0]) and np.array_equal(cnt, want[1]) and np.array_equal(raw, want[2])
+
+    # a bad magic: every row rejected and empty, by both
+    buf, nbytes = K.pack(ch, base, magic=K.MAGIC ^ 0x100)
+    assert header_fields(buf)[0] != K.MAGIC and header_fields(buf)[1:] == hc[1:] and np.array_equal(buf[64:], clean_buf[64:])
+    tables, st_whole, st_win = whole_and_window(g, torch, buf, nbytes, nf, ch)
+    assert st_whole == st_win == (K.BAD_HEADER, nf * ch, 0)
+    begin, cnt, scale, raw, raw_len = tables
+    assert not begin.any() and not cnt.any() and not scale.any() and np.all(raw == -1) and not raw_len.any()
 
 
 # ------------------------------------------------------------------------------------------ 4: batches
