@@ -301,6 +301,10 @@ SIGNATURES = {
                                              _vp, C.c_int, C.POINTER(GlcClipLayout)]),
     "glc_stream_dec_push": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_uint64), C.POINTER(GlcStreamSeg), C.c_uint64, _vp,
                                       C.POINTER(C.c_uint64), C.POINTER(_vp), C.c_int, C.POINTER(C.c_uint64)]),
+    "glc_store_join_segments_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.POINTER(GlcStreamSeg), C.c_uint64, C.POINTER(C.c_uint64),
+                                                 C.c_uint16, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "glc_compact_join": (C.c_int, [C.POINTER(_vp), C.POINTER(C.c_uint64), C.c_uint32, C.c_uint16, _vp, C.c_uint64,
+                                   C.POINTER(GlcCompactInfo)]),
     "glc_version": (C.c_char_p, []),
 }
 

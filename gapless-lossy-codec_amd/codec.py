@@ -331,6 +331,30 @@ def frames_to_compact(encoded: "EncodedAudio") -> bytes:
     return blob[:info.bytes].tobytes()
 
 
+def compact_join(blobs, channels: Optional[int] = None) -> bytes:
+    """The blob of a whole clip from its segment blobs in frame order (glc_compact_join): what a receiver of
+    StreamEncoder.segments calls, and the host twin of join_segments_tensor - the header of the sums, then each of the
+    five sections the segments' sections back to back.  channels: the clip's channel count; None takes it from the first
+    blob's header (every segment must then agree with it, as with a given one).  GlcError (GLC_EINVAL) names the first
+    unusable segment; an empty list is refused too."""
+    arrs = [np.frombuffer(bytes(b), np.uint8) if not isinstance(b, np.ndarray) else np.ascontiguousarray(b, np.uint8).reshape(-1)
+            for b in blobs]
+    held = [np.concatenate([a, np.zeros(-a.size % 8, np.uint8)]).view(np.uint64) for a in arrs]  # 8-byte aligned copies
+    ptrs = _c_array(C.c_void_p, [h.ctypes.data for h in held])
+    sizes = _c_array(C.c_uint64, [a.size for a in arrs])
+    if channels is None:
+        channels = int(arrs[0][4:8].copy().view(np.uint32)[0]) if arrs and arrs[0].size >= 8 else 0
+    if not 0 < channels <= 0xFFFF:
+        raise GlcError(GLC_EINVAL, "compact_join: no channel count (an empty list, a blob without a header, or channels out of range)")
+    info = GlcCompactInfo()
+    rc = lib.glc_compact_join(ptrs, sizes, len(arrs), channels, None, 0, C.byref(info))  # sizes the blob, or says why there is none
+    if rc != GLC_EINVAL or info.bytes == 0:
+        check(rc)
+    out = np.empty(info.bytes // 8 + 1, np.uint64)
+    check(lib.glc_compact_join(ptrs, sizes, len(arrs), channels, out.ctypes.data_as(C.c_void_p), info.bytes, C.byref(info)))
+    return out.view(np.uint8)[:info.bytes].tobytes()
+
+
 @dataclass
 class CompactStatus:
     """glc_compact_status: what the device check of one compact blob found (include/glc.h GLC_COMPACT_*)."""
@@ -626,6 +650,44 @@ class _Ctx:
                 C.c_void_p(lengths_out.data_ptr()) if lengths is not None else None, C.c_void_p(new_index.data_ptr()),
                 C.c_void_p(counts.data_ptr()), C.c_void_p(counts.data_ptr() + 8)), self._h)
         return entries_out, lengths_out, new_index, counts[0:1], counts[1:2]
+
+    def join_segments_tensor(self, arena, entries, segs, out_arena, cursor, lengths=None, channels: Optional[int] = None):
+        """Join the segments StreamEncoder.push_tensor stored into one blob per clip (glc_store_join_segments_device).
+        arena: the 1-D uint8 CUDA tensor the segments lie in; entries: its (n_segs, 4) int64 CUDA index; segs: the host
+        list [(stream, first_frame, n_frames)] in the same order, ascending by (stream, first_frame) - the segments of
+        one stream value are one clip; out_arena / cursor: the destination store, as
+        Encoder.encode_compact_batch_tensor takes them (the call appends at the cursor); lengths: per clip the samples
+        per channel (host integers), or None; channels: the clips' channel count (default: this object's).
+        Returns (entries_out, lengths_out, seg_status), new CUDA tensors: (n_clips, 4) int64 - all zero for a clip
+        with an unusable segment -, (n_clips,) int64 or None, (n_segs,) int32 of GLC_COMPACT_* bits.  Nothing is read
+        on the host and nothing but the table image is copied; queued on torch's current stream.  The context's
+        resident stream, decode session and last-info records are untouched."""
+        import torch
+        channels = int(getattr(self, "channels", 0) if channels is None else channels)
+        if not 0 < channels <= 0xFFFF:
+            raise GlcError(GLC_EINVAL, "join_segments_tensor: channels must be 1..65535")
+        segs = [tuple(int(v) for v in g) for g in segs]
+        n = self._tensor(entries, "entries", torch.int64, (len(segs), 4)).shape[0]
+        self._tensor(arena, "arena", torch.uint8, (None,))
+        self._append_tensors(out_arena, cursor)
+        n_clips = len({g[0] for g in segs})
+        if lengths is not None:
+            lengths = _ints(lengths)
+            if len(lengths) != n_clips:
+                raise GlcError(GLC_EINVAL, f"lengths must hold {n_clips} values, one per clip")
+        dev = arena.device
+        entries_out = torch.zeros((n_clips, 4), dtype=torch.int64, device=dev)
+        lengths_out = torch.zeros(n_clips, dtype=torch.int64, device=dev) if lengths is not None else None
+        seg_status = torch.zeros(n, dtype=torch.int32, device=dev)
+        c_segs = _c_array(GlcStreamSeg, [GlcStreamSeg(*g) for g in segs])
+        c_lens = _c_array(C.c_uint64, lengths) if lengths is not None else None
+        with _on_torch_stream(self, dev):
+            check(lib.glc_store_join_segments_device(
+                self._h, C.c_void_p(arena.data_ptr()), arena.numel(), C.c_void_p(entries.data_ptr()), c_segs, n, c_lens,
+                channels, C.c_void_p(out_arena.data_ptr()), out_arena.numel(), C.c_void_p(cursor.data_ptr()),
+                C.c_void_p(entries_out.data_ptr()), C.c_void_p(lengths_out.data_ptr()) if lengths is not None else None,
+                C.c_void_p(seg_status.data_ptr())), self._h)
+        return entries_out, lengths_out, seg_status
 
     def timer_begin(self) -> None:
         """Record a HIP event on the context's stream (device-side stopwatch)."""

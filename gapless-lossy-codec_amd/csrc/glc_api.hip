@@ -2991,6 +2991,74 @@ int glc_debug_set_store_compact_round(glc_ctx *ctx, uint64_t bytes) {
   return GLC_OK;
 }
 
+// ------------------------------------------------------------------------------ joining a clip's segments in the store
+
+int glc_store_join_segments_device(glc_ctx *ctx, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
+                                   const glc_stream_seg *segs, uint64_t n_segs, const uint64_t *lengths, uint16_t channels, void *d_dst,
+                                   uint64_t dst_bytes, uint64_t *d_cursor, glc_store_entry *d_entries_out, int64_t *d_lengths_out,
+                                   uint32_t *d_seg_status) {
+  const std::string w("glc_store_join_segments_device");
+  if (!ctx) return GLC_EINVAL;
+  if (n_segs == 0) return GLC_OK;  // nothing to join: the cursor stays
+  if (!d_arena || !d_entries || !segs || !d_dst || !d_cursor || !d_entries_out || !d_seg_status)
+    return fail(ctx, GLC_EINVAL, w + ": null argument");
+  if (channels == 0) return fail(ctx, GLC_EINVAL, w + ": channels == 0");
+  if ((lengths == nullptr) != (d_lengths_out == nullptr))
+    return fail(ctx, GLC_EINVAL, w + ": lengths and d_lengths_out are given together or not at all");
+  if (!all_aligned(64, d_arena, d_dst)) return fail(ctx, GLC_EINVAL, w + ": the arenas must be 64-byte aligned");
+  if (!all_aligned(8, d_entries, d_cursor, d_entries_out, d_lengths_out))
+    return fail(ctx, GLC_EINVAL, w + ": entries, lengths_out and cursor must be 8-byte aligned");
+  if (!aligned(d_seg_status, 4)) return fail(ctx, GLC_EINVAL, w + ": d_seg_status must be 4-byte aligned");
+  if (n_segs > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, w + ": too many segments");
+  return on_device(ctx, w, [&]() -> int {
+    std::vector<JoinClipSpan> clips;
+    uint64_t at = 0;
+    bool of_clip = false;
+    if (const char *bad = join_segs_fault(segs, n_segs, lengths, channels, &clips, &at, &of_clip))
+      return fail(ctx, GLC_EINVAL, w + (of_clip ? ": clip " : ": segment ") + std::to_string(at) + ": " + bad);
+    const uint64_t n_clips = clips.size();
+    const char *one, *other;
+    if (first_overlap({span_of(d_arena, arena_bytes, "the arena"), span_of(d_dst, dst_bytes, "the destination arena"),
+                       span_of(d_entries, n_segs * sizeof(glc_store_entry), "d_entries"),
+                       span_of(d_entries_out, n_clips * sizeof(glc_store_entry), "d_entries_out"),
+                       span_of(d_lengths_out, n_clips * 8, "d_lengths_out"), span_of(d_seg_status, n_segs * 4, "d_seg_status"),
+                       span_of(d_cursor, 8, "d_cursor")},
+                      &one, &other))
+      return fail(ctx, GLC_EINVAL, w + ": " + one + " overlaps " + other);
+    // a host bound on the joined bytes, for the shape of the move: what the clips' rows can hold, and the destination
+    uint64_t bound = 0;
+    for (const JoinClipSpan &c : clips) bound = std::min(dst_bytes, bound + glc::compact_layout(channels, c.n_frames).bound);
+    // not a decode and not an encode: the resident stream, an open session, the kept plan and the last-info records stay.
+    // The image (the two tables) and, behind it, the workspace the kernels write share the batch calls' table buffer.
+    TableOffsets offs;
+    const size_t o_segs = offs.take(n_segs * sizeof(glc::StoreJoinSeg));
+    const size_t o_clips = offs.take(n_clips * sizeof(glc::StoreJoinClip));
+    const size_t img_bytes = offs.size();
+    const size_t o_ws = offs.take(glc::store_join_ws_bytes(n_segs, n_clips));
+    TableImage &image = ctx->rtb_image;
+    if (const int rc = image.begin(ctx, offs.size())) return rc;
+    auto *seg_tab = image.host<glc::StoreJoinSeg>(o_segs);
+    auto *clip_tab = image.host<glc::StoreJoinClip>(o_clips);
+    for (uint64_t c = 0; c < n_clips; ++c) {
+      clip_tab[c] = glc::StoreJoinClip{clips[c].seg_first, clips[c].n_segs, clips[c].n_frames, lengths ? static_cast<int64_t>(lengths[c]) : 0};
+      for (uint64_t j = clips[c].seg_first; j < clips[c].seg_first + clips[c].n_segs; ++j)
+        seg_tab[j] = glc::StoreJoinSeg{static_cast<uint32_t>(c), 0u, segs[j].first_frame, segs[j].n_frames};
+    }
+    if (const int rc = image.send(ctx, img_bytes)) return rc;
+    glc::StoreJoin a{};
+    a.arena = static_cast<const unsigned char *>(d_arena), a.arena_bytes = arena_bytes, a.entries = d_entries;
+    a.segs = image.dev<glc::StoreJoinSeg>(o_segs), a.n_segs = n_segs;
+    a.clips = image.dev<glc::StoreJoinClip>(o_clips), a.n_clips = n_clips;
+    a.ch = channels, a.has_lengths = lengths ? 1u : 0u;
+    a.dst = static_cast<unsigned char *>(d_dst), a.dst_bytes = dst_bytes, a.cursor = d_cursor;
+    a.entries_out = d_entries_out, a.lengths_out = d_lengths_out, a.seg_status = d_seg_status;
+    a.ws = reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(ctx->rtb_tab.p) + o_ws);
+    GLC_HIP(ctx, glc::launch_store_join_plan(a, ctx->stream));
+    GLC_HIP(ctx, glc::launch_store_join_move(a, bound, ctx->stream));
+    return GLC_OK;
+  });
+}
+
 // ------------------------------------------------------------------------------ encode of a batch into per-clip compact blobs
 
 extern "C++" {

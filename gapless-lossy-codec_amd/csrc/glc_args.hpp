@@ -146,6 +146,44 @@ static inline const char *store_fill_overlap(const RtbPcm &pcm, const RtbLayout 
   return nullptr;
 }
 
+// THE segment rule of the join (glc_store_join_segments_device): segs ascends by (stream, first_frame); the segments of
+// one stream value are one clip - consecutive, the first at frame 0, each with frames, each starting where the one
+// before ends -, the clips numbered in order of appearance; a clip's frames pass the 32-bit row limit of frames_fault
+// and, where lengths are given, are exactly plan_encode(lengths[c], 1).n_frames.  *clips: per clip {first segment,
+// segments, frames}, fault or not; *at: the segment or (*of_clip, the last two rules) the clip the fault names.
+struct JoinClipSpan {
+  uint64_t seg_first, n_segs, n_frames;
+};
+static inline const char *join_segs_fault(const glc_stream_seg *segs, uint64_t n_segs, const uint64_t *lengths, uint16_t channels,
+                                          std::vector<JoinClipSpan> *clips, uint64_t *at, bool *of_clip) {
+  clips->clear();
+  *of_clip = false;
+  for (uint64_t j = 0; j < n_segs; ++j) {
+    *at = j;
+    if (segs[j].n_frames == 0) return "no frames";
+    const bool fresh = j == 0 || segs[j].stream != segs[j - 1].stream;
+    if (fresh) {
+      if (j && segs[j].stream < segs[j - 1].stream) return "the segments do not ascend by stream and frame";
+      if (segs[j].first_frame != 0) return "a clip's first segment must start at frame 0";
+      clips->push_back(JoinClipSpan{j, 0, 0});
+    } else if (segs[j].first_frame != clips->back().n_frames) {
+      return segs[j].first_frame < clips->back().n_frames ? "the segments do not ascend by stream and frame"
+                                                          : "it does not start where its clip's frames end";
+    }
+    JoinClipSpan &c = clips->back();
+    if (segs[j].n_frames > 0xFFFFFFFFull - c.n_frames) return "stream too long";
+    c.n_frames += segs[j].n_frames, c.n_segs += 1;
+  }
+  *of_clip = true;
+  for (uint64_t c = 0; c < clips->size(); ++c) {
+    *at = c;
+    if ((*clips)[c].n_frames * channels > 0xFFFFFFFFull) return "stream too long";
+    if (lengths && glc::plan_encode(lengths[c], 1).n_frames != (*clips)[c].n_frames)
+      return "the segments' frames are not those of a clip of lengths[c] samples (glc_plan_encode)";
+  }
+  return nullptr;
+}
+
 // The one overlap of input and output the batch round trip allows: in place - the same pointer, the same layout and the
 // same format, so that every sample is read before the slot it lies in is written.
 static inline bool in_place(const void *in, const RtbLayout &li, glc_pcm_format fmt, const void *out, const RtbLayout &lo,

@@ -407,6 +407,84 @@ int glc_frames_to_compact(const glc_frames *f, void *blob, uint64_t cap, glc_com
   return GLC_OK;
 }
 
+// The host twin of glc_store_join_segments_device (include/glc.h): the C-side statement of the join.
+int glc_compact_join(const void *const *blobs, const uint64_t *blob_bytes, uint32_t n_blobs, uint16_t channels, void *out,
+                     uint64_t cap, glc_compact_info *info) {
+  const std::string who("glc_compact_join: ");
+  if (!info || channels == 0 || (n_blobs && (!blobs || !blob_bytes)) || (!out && cap)) return GLC_EINVAL;
+  *info = glc_compact_info{0, 0, 0, 0};
+  const uint32_t ch = channels;
+  if (n_blobs == 0) {  // every segment has frames and a clip has a segment: there is no blob of nothing
+    glc::set_global_error(who + "no segments");
+    return GLC_EINVAL;
+  }
+  auto refuse = [&](uint32_t b, const char *what) {
+    glc::set_global_error(who + "segment " + std::to_string(b) + ": " + what);
+    return GLC_EINVAL;
+  };
+  if (reinterpret_cast<uintptr_t>(out) % 8 != 0) {
+    glc::set_global_error(who + "out must be 8-byte aligned");
+    return GLC_EINVAL;
+  }
+  // pass 1: the usability rule, per segment, and the sums
+  std::vector<glc::CompactHeader> hdrs;
+  try {
+    hdrs.resize(n_blobs);
+  } catch (const std::bad_alloc &) {
+    return GLC_ENOMEM;
+  }
+  uint64_t F = 0, P = 0, R = 0;
+  for (uint32_t b = 0; b < n_blobs; ++b) {
+    if (!blobs[b] || blob_bytes[b] < sizeof(glc::CompactHeader)) return refuse(b, "blob shorter than its header");
+    if (reinterpret_cast<uintptr_t>(blobs[b]) % 8 != 0) return refuse(b, "blob must be 8-byte aligned");
+    glc::CompactHeader &h = hdrs[b];
+    std::memcpy(&h, blobs[b], sizeof h);
+    if (h.n_frames == 0) return refuse(b, "no frames");
+    // compact_header_fault leaves the bound on n_frames to its caller (the sizes it forms from the count must not wrap):
+    // the 32-bit row limit of every clip, and a frame is at least its is_raw byte, so a blob cannot hold more than its size
+    if (h.n_frames > 0xFFFFFFFFull / ch || h.n_frames > blob_bytes[b] - sizeof(glc::CompactHeader))
+      return refuse(b, "bad magic, channel count or frame count");
+    if (const char *bad = glc::compact_header_error(h, ch, h.n_frames, /*exact=*/true, blob_bytes[b])) return refuse(b, bad);
+    const glc::CompactLayout l = glc::compact_layout(ch, h.n_frames);
+    const uint8_t *base = static_cast<const uint8_t *>(blobs[b]);
+    const uint32_t *cnt = reinterpret_cast<const uint32_t *>(base + l.o_cnt);
+    uint64_t pairs = 0, raws = 0;
+    for (uint64_t m = 0; m < h.n_frames * ch; ++m) pairs += cnt[m];
+    for (uint64_t f = 0; f < h.n_frames; ++f) raws += base[l.o_israw + f] ? ch : 0;
+    if (pairs != h.n_pairs) return refuse(b, "the rows' counts do not add up to n_pairs");
+    if (raws != h.n_raw_rows) return refuse(b, "the rows of raw frames are not n_raw_rows");
+    F += h.n_frames, P += h.n_pairs, R += h.n_raw_rows;
+    if (F * ch > 0xFFFFFFFFull) return refuse(b, "stream too long");
+  }
+  const glc::CompactLayout l = glc::compact_layout(ch, F);
+  const uint64_t raw_off = glc::compact_raw_offset(l, P);
+  *info = glc_compact_info{F, P, R, raw_off + R * glc::kFrame * 2};
+  if (cap < info->bytes) {
+    glc::set_global_error(who + "out is smaller than the joined blob (info->bytes)");
+    return GLC_EINVAL;
+  }
+  // pass 2: the header, then the five sections, each the segments' sections back to back; every gap is zero
+  uint8_t *o = static_cast<uint8_t *>(out);
+  std::memset(o, 0, l.o_pairs);
+  std::memset(o + l.o_pairs + 4 * P, 0, raw_off - (l.o_pairs + 4 * P));
+  const glc::CompactHeader h = glc::compact_header(ch, F, P, R, info->bytes);
+  std::memcpy(o, &h, sizeof h);
+  uint64_t f_at = 0, p_at = 0, r_at = 0;
+  for (uint32_t b = 0; b < n_blobs; ++b) {
+    const glc::CompactHeader &s = hdrs[b];
+    const glc::CompactLayout ls = glc::compact_layout(ch, s.n_frames);
+    const uint8_t *base = static_cast<const uint8_t *>(blobs[b]);
+    const uint64_t rows = s.n_frames * ch;
+    std::memcpy(o + l.o_israw + f_at, base + ls.o_israw, s.n_frames);
+    std::memcpy(o + l.o_scale + 4 * f_at * ch, base + ls.o_scale, 4 * rows);
+    std::memcpy(o + l.o_cnt + 4 * f_at * ch, base + ls.o_cnt, 4 * rows);
+    if (s.n_pairs) std::memcpy(o + l.o_pairs + 4 * p_at, base + ls.o_pairs, 4 * s.n_pairs);
+    if (s.n_raw_rows) std::memcpy(o + raw_off + r_at * glc::kFrame * 2, base + glc::compact_raw_offset(ls, s.n_pairs), s.n_raw_rows * glc::kFrame * 2);
+    f_at += s.n_frames, p_at += s.n_pairs, r_at += s.n_raw_rows;
+  }
+  return GLC_OK;
+}
+
 uint64_t glc_record_bytes(uint16_t channels) { return glc::record_bytes(channels); }
 
 int glc_plan_encode(uint64_t n_samples, uint16_t channels, glc_plan *out) {

@@ -512,6 +512,56 @@ hipError_t launch_store_evict_gather(const uint64_t *ws, const void *arena, uint
 // above total are neither staged nor written.
 hipError_t launch_store_evict_round(const uint64_t *ws, void *arena, void *stage, uint64_t round, uint64_t r, hipStream_t s);
 
+// The segment join (glc_store_join_segments_device; DESIGN section 3, "joining a clip's segments").  include/glc.h
+// states the rules; the two launchers below are all of the call.
+//   J1  k_store_join_plan, one workgroup of 256 threads per segment: the entry rule of the draw, the header rule with
+//       the segment's frames exact and the entry's bytes available, then - only behind a header that passed - the sum of
+//       the cnt section and the count of set is_raw bytes, 16-byte loads over the 64-byte aligned sections, the words
+//       behind the rows masked.  seg_status[j] and found[j] = {arena offset, n_pairs, n_raw_rows, bad}; a bad segment
+//       counts no pairs and no raw rows.
+//   J2  k_store_join_scan, ONE workgroup of 1024 threads (k_store_evict_scan's form, chunks of 1024 with a carry): the
+//       exclusive scans of found[].n_pairs / n_raw_rows / bad over ALL segments - a clip's totals and a segment's place
+//       in its clip are differences of them -, then over the clips the sizes, the exclusive scan of the sizes from the
+//       rounded-up cursor, entries_out, lengths_out, the headers of the stored clips, the cursor and the move table.
+//   M   k_store_join_move: tiles of kStoreMoveTile bytes of the packed destination space [0, limit); a 16-byte unit
+//       finds its clip by search over clip_off, its section from the clip's layout and its segment by search over the
+//       segments' starts in that section's run.
+// The workspace (store_join_ws_bytes(n_segs, n_clips), 8-byte aligned), in uint64_t words: head[8] = {base, total,
+// limit} (base: the rounded-up cursor; total, limit: packed - relative to base - ends of all and of the stored clips),
+// found[n_segs] of 4 words, ex_pairs / ex_raw / ex_bad of n_segs + 1 words each, clip_off[n_clips + 1] (packed),
+// clip_sum[n_clips] of 2 words {n_pairs, n_raw_rows}.
+struct StoreJoinSeg {   // host, in the table image
+  uint32_t clip, pad;
+  uint64_t first_frame, n_frames;
+};
+struct StoreJoinClip {  // host, in the table image
+  uint64_t seg_first, n_segs, n_frames;
+  int64_t length;
+};
+struct StoreJoin {
+  const unsigned char *arena;
+  uint64_t arena_bytes;
+  const glc_store_entry *entries;
+  const StoreJoinSeg *segs;
+  uint64_t n_segs;
+  const StoreJoinClip *clips;
+  uint64_t n_clips;
+  uint32_t ch, has_lengths;
+  unsigned char *dst;
+  uint64_t dst_bytes;
+  uint64_t *cursor;
+  glc_store_entry *entries_out;
+  int64_t *lengths_out;  // or null
+  uint32_t *seg_status;
+  uint64_t *ws;
+};
+inline uint64_t store_join_ws_bytes(uint64_t n_segs, uint64_t n_clips) {
+  return (8ull + 4ull * n_segs + 3ull * (n_segs + 1ull) + (n_clips + 1ull) + 2ull * n_clips) * 8ull;
+}
+hipError_t launch_store_join_plan(const StoreJoin &a, hipStream_t s);
+// max_bytes: a host bound on the packed bytes of the stored clips; the launch's shape depends on it alone.
+hipError_t launch_store_join_move(const StoreJoin &a, uint64_t max_bytes, hipStream_t s);
+
 // The interleaved descriptor with a 32-bit destination, 24 bytes instead of 40: what glc_decode_batch uploads per
 // kept hop (its rounds address their output in 31 bits).  Same kernel, same chunks; kept beside HopDescStrided
 // because that driver measured slower, per launch and per call, with the wide form.

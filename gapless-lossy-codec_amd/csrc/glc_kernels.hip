@@ -2167,6 +2167,324 @@ __global__ __launch_bounds__(256) void k_store_evict_round(const unsigned long l
 }
 
 // ------------------------------------------------------------------------------------------
+// The segment join: glc_store_join_segments_device (glc_kernels.h StoreJoin has the plan, include/glc.h the rules).
+// ------------------------------------------------------------------------------------------
+struct StoreJoinWs {  // the workspace's arrays (glc_kernels.h)
+  unsigned long long *head, *found, *ex_pairs, *ex_raw, *ex_bad, *clip_off, *clip_sum;
+};
+__device__ __forceinline__ StoreJoinWs store_join_ws(const StoreJoin &a) {
+  StoreJoinWs w;
+  w.head = reinterpret_cast<unsigned long long *>(a.ws);
+  w.found = w.head + 8;
+  w.ex_pairs = w.found + 4ull * a.n_segs;
+  w.ex_raw = w.ex_pairs + a.n_segs + 1;
+  w.ex_bad = w.ex_raw + a.n_segs + 1;
+  w.clip_off = w.ex_bad + a.n_segs + 1;
+  w.clip_sum = w.clip_off + a.n_clips + 1;
+  return w;
+}
+
+// J1.  Thread 0 judges the entry and the header; nothing of a segment with an unusable entry is read, and nothing
+// behind a failing header.  The two reductions run over whole 16-byte units of the sections, which end on multiples of
+// 64 inside the blob (the header rule: `bytes` is exactly the sections and fits the entry), and mask what lies behind
+// the rows: the padding is as untrusted as the rest.
+__global__ __launch_bounds__(256) void k_store_join_plan(StoreJoin a) {
+  __shared__ CompactHeader s_h;
+  __shared__ unsigned s_bits;
+  __shared__ unsigned long long s_part[2][4];
+  const StoreJoinWs w = store_join_ws(a);
+  const unsigned t = threadIdx.x;
+  for (unsigned long long j = blockIdx.x; j < a.n_segs; j += gridDim.x) {
+    const glc_store_entry e = a.entries[j];
+    const StoreJoinSeg sg = a.segs[j];
+    if (t == 0) {
+      unsigned bits = 0;
+      // each term is bounded before the difference is formed: nothing wraps (k_store_plan_crops' way)
+      if (e.stored == 0 || (e.offset & 63ull) || e.offset > a.arena_bytes || e.bytes > a.arena_bytes - e.offset) {
+        bits = kCompactNoBlob | kCompactBadHeader;
+      } else if (e.bytes < sizeof(CompactHeader)) {
+        bits = kCompactBadHeader;  // not even a header
+      } else {
+        const uint4 *hp = reinterpret_cast<const uint4 *>(a.arena + e.offset);
+        uint4 *hs = reinterpret_cast<uint4 *>(&s_h);
+        hs[0] = hp[0], hs[1] = hp[1], hs[2] = hp[2], hs[3] = hp[3];
+        if (compact_header_fault(s_h, a.ch, sg.n_frames, 0, true, e.bytes) != HeaderFault::kNone) bits = kCompactBadHeader;
+      }
+      s_bits = bits;
+    }
+    __syncthreads();
+    unsigned long long pairs = 0, raws = 0;
+    if (s_bits == 0) {
+      const unsigned long long F = sg.n_frames, M = F * a.ch;
+      const CompactLayout l = compact_layout(a.ch, F);
+      const unsigned char *blob = a.arena + e.offset;
+      for (unsigned long long u = t; u * 4ull < M; u += 256ull) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(blob + l.o_cnt + 16ull * u);
+        const unsigned long long m = 4ull * u;
+        pairs += v.x;
+        if (m + 1 < M) pairs += v.y;
+        if (m + 2 < M) pairs += v.z;
+        if (m + 3 < M) pairs += v.w;
+      }
+      for (unsigned long long u = t; u * 16ull < F; u += 256ull) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(blob + l.o_israw + 16ull * u);
+        const unsigned words[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+          if (16ull * u + i < F && ((words[i >> 2] >> (8 * (i & 3))) & 0xFFu)) ++raws;
+      }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+      pairs += __shfl_down(pairs, off, 64);
+      raws += __shfl_down(raws, off, 64);
+    }
+    if ((t & 63u) == 0) s_part[0][t >> 6] = pairs, s_part[1][t >> 6] = raws;
+    __syncthreads();
+    if (t == 0) {
+      unsigned bits = s_bits;
+      const unsigned long long n_pairs = s_part[0][0] + s_part[0][1] + s_part[0][2] + s_part[0][3];
+      const unsigned long long n_raw = (s_part[1][0] + s_part[1][1] + s_part[1][2] + s_part[1][3]) * a.ch;
+      if (bits == 0) {
+        if (n_pairs != s_h.n_pairs) bits |= kCompactPairSum;
+        if (n_raw != s_h.n_raw_rows) bits |= kCompactRawSum;
+      }
+      a.seg_status[j] = bits;
+      w.found[4 * j] = e.offset;
+      w.found[4 * j + 1] = bits ? 0ull : n_pairs;
+      w.found[4 * j + 2] = bits ? 0ull : n_raw;
+      w.found[4 * j + 3] = bits ? 1ull : 0ull;
+    }
+    __syncthreads();  // s_h, s_bits and s_part are rewritten by the next segment
+  }
+}
+
+// J2.  The three scans over the segments first, their exclusive values in the workspace (the sums may wrap: only
+// differences inside one clip are used, and those are bounded by the clip's rows); then the clips, k_store_place's
+// placement rule word for word, a refused clip counting 0.
+__global__ __launch_bounds__(1024) void k_store_join_scan(StoreJoin a) {
+  __shared__ unsigned long long s[1024];
+  __shared__ unsigned long long s_limit;
+  const StoreJoinWs w = store_join_ws(a);
+  const unsigned t = threadIdx.x;
+  if (t == 0) s_limit = 0ull;
+#pragma unroll 1
+  for (int which = 0; which < 3; ++which) {
+    unsigned long long *ex = which == 0 ? w.ex_pairs : which == 1 ? w.ex_raw : w.ex_bad;
+    unsigned long long carry = 0;
+    for (unsigned long long j0 = 0; j0 < a.n_segs; j0 += 1024) {
+      const unsigned long long j = j0 + t;
+      const unsigned long long mine = j < a.n_segs ? w.found[4 * j + 1 + which] : 0ull;
+      scan_sum_1024(s, mine);
+      if (j < a.n_segs) ex[j] = carry + s[t] - mine;
+      const unsigned long long chunk_total = s[1023];
+      __syncthreads();
+      carry += chunk_total;
+    }
+    if (t == 0) ex[a.n_segs] = carry;
+  }
+  __threadfence_block();
+  __syncthreads();  // the exclusive values are read below by other threads than wrote them
+  const unsigned long long base = align64(*a.cursor);  // every thread reads it here; thread 0 writes it behind the last barrier
+  unsigned long long carry = base;
+  unsigned long long *out = reinterpret_cast<unsigned long long *>(a.entries_out);
+  for (unsigned long long c0 = 0; c0 < a.n_clips; c0 += 1024) {
+    const unsigned long long c = c0 + t;
+    unsigned long long bytes = 0, n_pairs = 0, n_raw = 0, F = 0;
+    long long len = 0;
+    bool ok = false;
+    if (c < a.n_clips) {
+      const StoreJoinClip cl = a.clips[c];
+      const unsigned long long j0 = cl.seg_first, j1 = cl.seg_first + cl.n_segs;
+      F = cl.n_frames, len = cl.length;
+      ok = w.ex_bad[j1] == w.ex_bad[j0];
+      if (ok) {
+        n_pairs = w.ex_pairs[j1] - w.ex_pairs[j0];
+        n_raw = w.ex_raw[j1] - w.ex_raw[j0];
+        bytes = compact_raw_offset(compact_layout(a.ch, F), n_pairs) + n_raw * (kFrameI * 2ull);
+      }
+    }
+    scan_sum_1024(s, bytes);
+    const unsigned long long offset = carry + s[t] - bytes;  // exclusive: every size is a multiple of 64
+    const unsigned long long chunk_total = s[1023];
+    __syncthreads();
+    carry += chunk_total;
+    if (c < a.n_clips) {
+      const bool stored = ok && offset <= a.dst_bytes && bytes <= a.dst_bytes - offset;  // the encoder's rule (k_store_place)
+      out[4 * c] = ok ? offset : 0ull;
+      out[4 * c + 1] = bytes;
+      out[4 * c + 2] = n_pairs;
+      out[4 * c + 3] = n_raw | (stored ? 1ull << 32 : 0ull);
+      if (a.lengths_out) a.lengths_out[c] = ok ? len : 0;
+      w.clip_off[c] = offset - base;
+      w.clip_sum[2 * c] = n_pairs;
+      w.clip_sum[2 * c + 1] = n_raw;
+      if (stored) {
+        *reinterpret_cast<CompactHeader *>(a.dst + offset) = compact_header(a.ch, F, n_pairs, n_raw, bytes);
+        atomicMax(&s_limit, offset + bytes - base);
+      }
+    }
+  }
+  __syncthreads();
+  if (t == 0) {
+    w.clip_off[a.n_clips] = carry - base;
+    w.head[0] = base;
+    w.head[1] = carry - base;
+    w.head[2] = s_limit;
+    *a.cursor = carry;
+  }
+}
+
+// M.  Where a byte of the packed destination space comes from.  A clip's blob is its header (J2 wrote it) and five
+// runs - is_raw, scale, cnt, pairs, raw -, each the segments' runs back to back, each followed by zeros up to the next
+// multiple of 64.  Segment j of a clip starts in a run at key(j): its first frame (is_raw), its first row's dword
+// (scale, cnt), the pairs / raw rows of the clip's segments in front of it (pairs, raw).  Empty runs share a start:
+// the search takes the LAST segment that starts at or below the byte, which is the one that holds it.
+enum : unsigned { kJoinHeader = 0, kJoinIsRaw, kJoinScale, kJoinCnt, kJoinPairs, kJoinRaw };
+struct JoinRun {  // one run of one clip
+  unsigned long long clip, sec, at, len;  // at: the run's packed offset; len: its bytes without the padding
+  unsigned long long j0, j1;              // the clip's segments
+};
+__device__ __forceinline__ unsigned long long join_key(const StoreJoin &a, const StoreJoinWs &w, const JoinRun &r, unsigned long long j) {
+  if (j >= r.j1) return r.len;
+  switch (r.sec) {
+    case kJoinIsRaw: return a.segs[j].first_frame;
+    case kJoinScale:
+    case kJoinCnt: return a.segs[j].first_frame * a.ch * 4ull;
+    case kJoinPairs: return (w.ex_pairs[j] - w.ex_pairs[r.j0]) * 4ull;
+    default: return (w.ex_raw[j] - w.ex_raw[r.j0]) * (kFrameI * 2ull);
+  }
+}
+// where segment j's part of the run lies in the arena
+__device__ __forceinline__ unsigned long long join_source(const StoreJoin &a, const StoreJoinWs &w, const JoinRun &r, unsigned long long j) {
+  const CompactLayout l = compact_layout(a.ch, a.segs[j].n_frames);
+  const unsigned long long at = r.sec == kJoinIsRaw  ? l.o_israw
+                                : r.sec == kJoinScale ? l.o_scale
+                                : r.sec == kJoinCnt   ? l.o_cnt
+                                : r.sec == kJoinPairs ? l.o_pairs
+                                                      : compact_raw_offset(l, w.found[4 * j + 1]);
+  return w.found[4 * j] + at;
+}
+// the run that holds packed byte p, the clip sought in [c_lo, c_hi]
+__device__ __forceinline__ JoinRun join_run(const StoreJoin &a, const StoreJoinWs &w, unsigned long long p, unsigned long long c_lo,
+                                            unsigned long long c_hi) {
+  while (c_lo < c_hi) {
+    const unsigned long long mid = c_lo + (c_hi - c_lo + 1) / 2;
+    if (w.clip_off[mid] <= p) c_lo = mid; else c_hi = mid - 1;
+  }
+  const StoreJoinClip cl = a.clips[c_lo];
+  const unsigned long long base = w.clip_off[c_lo], rel = p - base, n_pairs = w.clip_sum[2 * c_lo], n_raw = w.clip_sum[2 * c_lo + 1];
+  const unsigned long long M = cl.n_frames * a.ch;
+  const CompactLayout l = compact_layout(a.ch, cl.n_frames);
+  const unsigned long long o_raw = compact_raw_offset(l, n_pairs);
+  JoinRun r;
+  r.clip = c_lo, r.j0 = cl.seg_first, r.j1 = cl.seg_first + cl.n_segs;
+  if (rel < l.o_israw) r.sec = kJoinHeader, r.at = base, r.len = l.o_israw;
+  else if (rel < l.o_scale) r.sec = kJoinIsRaw, r.at = base + l.o_israw, r.len = cl.n_frames;
+  else if (rel < l.o_cnt) r.sec = kJoinScale, r.at = base + l.o_scale, r.len = 4ull * M;
+  else if (rel < l.o_pairs) r.sec = kJoinCnt, r.at = base + l.o_cnt, r.len = 4ull * M;
+  else if (rel < o_raw) r.sec = kJoinPairs, r.at = base + l.o_pairs, r.len = 4ull * n_pairs;
+  else r.sec = kJoinRaw, r.at = base + o_raw, r.len = n_raw * (kFrameI * 2ull);
+  return r;
+}
+// the segment of run r that holds byte u of the run (u < r.len), sought in [j_lo, j_hi]
+__device__ __forceinline__ unsigned long long join_segment(const StoreJoin &a, const StoreJoinWs &w, const JoinRun &r, unsigned long long u,
+                                                           unsigned long long j_lo, unsigned long long j_hi) {
+  while (j_lo < j_hi) {
+    const unsigned long long mid = j_lo + (j_hi - j_lo + 1) / 2;
+    if (join_key(a, w, r, mid) <= u) j_lo = mid; else j_hi = mid - 1;
+  }
+  return j_lo;
+}
+
+// The 16 bytes at arena address `at` (any alignment) from the one or two aligned units that hold them: a dword select
+// and a byte funnel, no byte loads.  Both units hold a byte of the run, so both lie inside the segment's blob, whose
+// offset and size are multiples of 64.
+__device__ __forceinline__ uint4 join_load16(const unsigned char *arena, unsigned long long at) {
+  const unsigned sh = static_cast<unsigned>(at & 15ull);
+  const unsigned char *p = arena + (at - sh);
+  const uint4 lo = *reinterpret_cast<const uint4 *>(p);
+  if (sh == 0) return lo;
+  const uint4 hi = *reinterpret_cast<const uint4 *>(p + 16);
+  const unsigned k = sh >> 2, b = (sh & 3u) * 8u;
+  const unsigned w0 = k == 0 ? lo.x : k == 1 ? lo.y : k == 2 ? lo.z : lo.w;
+  const unsigned w1 = k == 0 ? lo.y : k == 1 ? lo.z : k == 2 ? lo.w : hi.x;
+  const unsigned w2 = k == 0 ? lo.z : k == 1 ? lo.w : k == 2 ? hi.x : hi.y;
+  const unsigned w3 = k == 0 ? lo.w : k == 1 ? hi.x : k == 2 ? hi.y : hi.z;
+  const unsigned w4 = k == 0 ? hi.x : k == 1 ? hi.y : k == 2 ? hi.z : hi.w;
+  auto funnel = [b](unsigned l, unsigned h) { return static_cast<unsigned>(((static_cast<unsigned long long>(h) << 32) | l) >> b); };
+  return uint4{funnel(w0, w1), funnel(w1, w2), funnel(w2, w3), funnel(w3, w4)};
+}
+
+// The slow path of a boundary unit: `n` elements of `width` bytes (1: is_raw, 4: the dword runs) from byte u of the
+// run on, each from the segment that holds it, zero behind the run's end.  The segment only moves forward.
+__device__ __forceinline__ unsigned join_gather4(const StoreJoin &a, const StoreJoinWs &w, const JoinRun &r, unsigned long long u,
+                                                 unsigned long long &j) {
+  unsigned word = 0;
+  const unsigned width = r.sec == kJoinIsRaw ? 1u : 4u;
+  for (unsigned i = 0; i < 4u; i += width) {
+    const unsigned long long v = u + i;
+    if (v >= r.len) break;
+    j = join_segment(a, w, r, v, j, r.j1 - 1);
+    const unsigned long long at = join_source(a, w, r, j) + (v - join_key(a, w, r, j));
+    if (width == 4u) word = *reinterpret_cast<const unsigned *>(a.arena + at);
+    else word |= static_cast<unsigned>(a.arena[at]) << (8u * i);
+  }
+  return word;
+}
+
+// Packed bytes [lo, hi) - multiples of 16, hi - lo <= kStoreMoveTile, hi <= limit - to dst + base.  The runs of the
+// tile's first and last unit are found once (the same search in every lane: uniform); where they are one run, a unit
+// that lies in it searches its segment between theirs.  Four units per thread, all loads in front of all stores, named
+// scalars (the comment at store_evict_gather_tile).
+__device__ __forceinline__ void store_join_move_tile(const StoreJoin &a, const StoreJoinWs &w, unsigned long long base,
+                                                     unsigned long long lo, unsigned long long hi) {
+  const JoinRun r_lo = join_run(a, w, lo, 0, a.n_clips - 1), r_hi = join_run(a, w, hi - 16, r_lo.clip, a.n_clips - 1);
+  const bool one_run = r_lo.clip == r_hi.clip && r_lo.sec == r_hi.sec && r_lo.sec != kJoinHeader && lo - r_lo.at < r_lo.len;
+  unsigned long long t_lo = 0, t_hi = 0;
+  if (one_run) {
+    const unsigned long long last = hi - 16 - r_lo.at < r_lo.len ? hi - 16 - r_lo.at : r_lo.len - 1;
+    t_lo = join_segment(a, w, r_lo, lo - r_lo.at, r_lo.j0, r_lo.j1 - 1);
+    t_hi = join_segment(a, w, r_lo, last, t_lo, r_lo.j1 - 1);
+  }
+  auto unit = [&](unsigned long long p, bool &live) {
+    uint4 v{};
+    live = false;
+    if (p >= hi) return v;
+    const JoinRun r = join_run(a, w, p, r_lo.clip, r_hi.clip);
+    if (r.sec == kJoinHeader) return v;  // J2 wrote it
+    live = true;
+    const unsigned long long u = p - r.at;
+    if (u >= r.len) return v;  // the zeros behind a run
+    const bool narrow = one_run && r.clip == r_lo.clip && r.sec == r_lo.sec;
+    unsigned long long j = join_segment(a, w, r, u, narrow ? t_lo : r.j0, narrow ? t_hi : r.j1 - 1);
+    if (u + 16 <= join_key(a, w, r, j + 1)) return join_load16(a.arena, join_source(a, w, r, j) + (u - join_key(a, w, r, j)));
+    v.x = join_gather4(a, w, r, u, j);
+    v.y = join_gather4(a, w, r, u + 4, j);
+    v.z = join_gather4(a, w, r, u + 8, j);
+    v.w = join_gather4(a, w, r, u + 12, j);
+    return v;
+  };
+  const unsigned long long p0 = lo + threadIdx.x * 16ull, p1 = p0 + 4096ull, p2 = p0 + 8192ull, p3 = p0 + 12288ull;
+  bool s0, s1, s2, s3;
+  const uint4 v0 = unit(p0, s0), v1 = unit(p1, s1), v2 = unit(p2, s2), v3 = unit(p3, s3);
+  unsigned char *dst = a.dst + base;
+  if (s0) *reinterpret_cast<uint4 *>(dst + p0) = v0;
+  if (s1) *reinterpret_cast<uint4 *>(dst + p1) = v1;
+  if (s2) *reinterpret_cast<uint4 *>(dst + p2) = v2;
+  if (s3) *reinterpret_cast<uint4 *>(dst + p3) = v3;
+}
+
+__global__ __launch_bounds__(256) void k_store_join_move(StoreJoin a) {
+  const StoreJoinWs w = store_join_ws(a);
+  const unsigned long long base = w.head[0], limit = w.head[2];
+  for (unsigned long long lo = static_cast<unsigned long long>(blockIdx.x) * kStoreMoveTile; lo < limit;
+       lo += static_cast<unsigned long long>(gridDim.x) * kStoreMoveTile) {
+    const unsigned long long hi = lo + kStoreMoveTile < limit ? lo + kStoreMoveTile : limit;
+    store_join_move_tile(a, w, base, lo, hi);
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // S1: the virtual stream of a round of glc_roundtrip_batch_device, gathered from clips that lie strided
 // (and, `planar`, one plane per channel) in the caller's memory.  Workgroup row blockIdx.x is virtual frame
 // slot v: the 1024 * ch interleaved samples [1024 v, 1024 v + 1024) of the stream.  Its clip is the last one
@@ -2864,6 +3182,23 @@ hipError_t launch_store_evict_gather(const uint64_t *ws, const void *arena, uint
   hipLaunchKernelGGL(k_store_evict_gather, dim3(static_cast<unsigned>(tiles < kStoreMoveGrid ? tiles : kStoreMoveGrid)), dim3(256), 0, s,
                      reinterpret_cast<const unsigned long long *>(ws), static_cast<const unsigned char *>(arena),
                      static_cast<unsigned char *>(dst));
+  return hipGetLastError();
+}
+
+hipError_t launch_store_join_plan(const StoreJoin &a, hipStream_t s) {
+  if (a.n_segs == 0 || a.n_clips == 0) return hipSuccess;
+  (void)hipGetLastError();
+  constexpr uint64_t kMaxGrid = 1ull << 20;  // segments behind it are taken by the grid stride
+  hipLaunchKernelGGL(k_store_join_plan, dim3(static_cast<unsigned>(a.n_segs < kMaxGrid ? a.n_segs : kMaxGrid)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_store_join_scan, dim3(1), dim3(1024), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_store_join_move(const StoreJoin &a, uint64_t max_bytes, hipStream_t s) {
+  const uint64_t tiles = (max_bytes + kStoreMoveTile - 1) / kStoreMoveTile;
+  if (a.n_segs == 0 || a.n_clips == 0 || tiles == 0) return hipSuccess;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_store_join_move, dim3(static_cast<unsigned>(tiles < kStoreMoveGrid ? tiles : kStoreMoveGrid)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

@@ -937,6 +937,61 @@ int glc_stream_enc_segment(const glc_stream_enc *s, uint64_t stream, uint64_t k,
  * then the lane is cleared.  GLC_EINVAL while the lane is not finished. */
 int glc_stream_enc_frames(glc_stream_enc *s, uint64_t stream, glc_frames **out);
 
+/* ---- joining a streamed clip's segments into one store blob ---------------------------------- */
+
+/* A clip that glc_stream_enc_push_device stored in k chunks lies in the arena as k segment blobs; every other consumer
+ * of the store (batch decode, windowed decode, the draw, eviction) takes ONE blob per clip.  This call writes, for
+ * every clip, the blob of the whole clip into a destination store.  A segment holds byte for byte the rows the
+ * whole-stream encode gives for its frames, so the clip's blob is compact_header(ch, F, P, R, bytes) - F, P, R the
+ * sums over its segments - followed by the five sections, each the segments' sections concatenated in frame order,
+ * all padding zero: nothing is recomputed, nothing is lossy, and the result is byte for byte what
+ * glc_encode_batch_device_compact stores for the whole clip.
+ * segs[n_segs] (host, as the encoder pushes returned them) ascends by (stream, first_frame).  The segments of one
+ *   `stream` value form one clip: they are consecutive, the first has first_frame == 0, each has n_frames > 0 and starts
+ *   where the one before ends.  The clips are numbered 0, 1, .. in order of appearance.  d_entries[j] (device, never
+ *   read by the host) names segment j's blob in d_arena.  lengths[c] (host, or NULL): samples per channel of clip c;
+ *   the clip's frames must then be glc_plan_encode(lengths[c], 1).n_frames.
+ * Usable segment (decided on the device; blobs and entries are untrusted): its entry passes the GLC_COMPACT_NO_BLOB
+ *   rule of the draw (stored != 0, offset a multiple of 64, [offset, offset + bytes) inside the arena); its header
+ *   passes the compact header rule with exactly the segment's n_frames and entry.bytes available; the sum over its cnt
+ *   section is n_pairs; channels times the number of non-zero is_raw bytes is n_raw_rows.  d_seg_status[j] = 0 for a
+ *   usable segment, else GLC_COMPACT_NO_BLOB | GLC_COMPACT_BAD_HEADER (entry; nothing of the segment is read),
+ *   GLC_COMPACT_BAD_HEADER (header; nothing behind it is read), GLC_COMPACT_PAIR_SUM and / or GLC_COMPACT_RAW_SUM.
+ *   Lists are not checked for canonical form: the decode does that, as always.
+ * A clip is joined only when all its segments are usable.  A refused clip writes nothing to the destination, its
+ *   entry is all zero words (a draw sees GLC_COMPACT_NO_BLOB) and it counts 0 bytes in the placement.
+ * Placement is the encoder's: *d_cursor is read and rounded up to 64; the clips are placed in clip order at the
+ *   exclusive running sum of their sizes; stored = 1 when the clip fits dst_bytes; the cursor counts on for clips that
+ *   do not fit; no byte of d_dst outside the stored blobs is written.  d_entries_out[c] = {offset, bytes, P, R, stored};
+ *   d_lengths_out[c] = lengths[c], 0 for a refused clip.
+ * No load leaves [d_arena, d_arena + arena_bytes) or d_entries[0 .. n_segs), whatever they hold.
+ * Family rules: queued on glc_ctx_stream(ctx), NOT synchronised; no copy to the host and none from it but the pinned
+ *   table image (the segment and clip tables); the call blocks only where its workspace has to grow and on the table
+ *   image of the previous batch call; three launches whose shape depends on n_segs, the clip count and a host bound on
+ *   the joined bytes, never on content.  Like eviction it is neither a decode nor an encode: the resident stream, an
+ *   open decode session, the kept plan and every "last info / last status" record stay as they were.
+ * GLC_EINVAL, before anything is queued and changing nothing: a null pointer (lengths and d_lengths_out both or
+ *   neither), channels == 0, an arena not 64-byte aligned, d_entries / d_cursor / d_entries_out / d_lengths_out not
+ *   8-byte aligned, d_seg_status not 4-byte aligned, a segment list that breaks the rules above, a clip of more than
+ *   2^32 - 1 rows, any overlap among the two arenas, d_entries and the output arrays.  n_segs == 0 is GLC_OK and
+ *   leaves the cursor alone. */
+int glc_store_join_segments_device(glc_ctx *ctx,
+                                   const void *d_arena, uint64_t arena_bytes,
+                                   const glc_store_entry *d_entries,
+                                   const glc_stream_seg *segs, uint64_t n_segs,
+                                   const uint64_t *lengths, uint16_t channels,
+                                   void *d_dst, uint64_t dst_bytes, uint64_t *d_cursor,
+                                   glc_store_entry *d_entries_out, int64_t *d_lengths_out,
+                                   uint32_t *d_seg_status);
+
+/* Host only, the same join over blobs in host memory (what glc_stream_enc_segment hands out, in frame order): the same
+ * bytes under the same usability rule, each blob judged against its own header's frame count (not 0, not more than
+ * blob_bytes - 64, not more than 2^32 - 1 rows: a count that could make the section sizes wrap is refused before any
+ * size is formed) and its blob_bytes.  n_blobs == 0 is GLC_EINVAL: there is no clip without a segment.  info (never NULL) receives the joined counts; GLC_EINVAL with glc_last_error(NULL) naming the
+ * segment for an unusable one, and for a cap below info->bytes (info is then filled).  blobs and out 8-byte aligned. */
+int glc_compact_join(const void *const *blobs, const uint64_t *blob_bytes, uint32_t n_blobs, uint16_t channels,
+                     void *out, uint64_t cap, glc_compact_info *info);
+
 /* ---- streaming decode: segment blobs in, PCM out, many live streams per launch chain ------- */
 
 /* The receiving half of a stream: the segments glc_stream_enc_* emits are decoded as they arrive, and the

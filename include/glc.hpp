@@ -223,6 +223,33 @@ inline void compact_store_device(glc_ctx *ctx, void *d_arena, uint64_t arena_byt
                                          d_entries_out, d_lengths_out, d_new_index, d_n_out, d_cursor), ctx);
 }
 
+// Join the segments a StreamEncoder's device pushes stored into one blob per clip (glc.h glc_store_join_segments_device),
+// on any context: segs (host) ascending by (stream, first_frame), d_entries (device) in the same order; the clips' blobs
+// are appended to the store d_dst at *d_cursor by the encoder's placement rule.  lengths (host) and d_lengths_out: both
+// or neither.  Queued on the context's stream, not synchronised; nothing is copied to the host.
+// StreamEncoder::join_segments_device forwards here.
+inline void join_segments_device(glc_ctx *ctx, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
+                                 const std::vector<glc_stream_seg> &segs, const uint64_t *lengths, uint16_t channels, void *d_dst,
+                                 uint64_t dst_bytes, uint64_t *d_cursor, glc_store_entry *d_entries_out, int64_t *d_lengths_out,
+                                 uint32_t *d_seg_status) {
+  detail::check(glc_store_join_segments_device(ctx, d_arena, arena_bytes, d_entries, segs.data(), segs.size(), lengths, channels, d_dst,
+                                               dst_bytes, d_cursor, d_entries_out, d_lengths_out, d_seg_status), ctx);
+}
+
+// The blob of a whole clip from its segment blobs in frame order, on the host (glc_compact_join): the same bytes.
+// An empty list is refused, as an unusable segment is.
+inline std::vector<uint8_t> compact_join(const std::vector<const void *> &blobs, const std::vector<uint64_t> &blob_bytes, uint16_t channels) {
+  if (blobs.size() != blob_bytes.size()) throw Error(GLC_EINVAL, "compact_join: one size per blob");
+  glc_compact_info info{};
+  const uint32_t n = static_cast<uint32_t>(blobs.size());
+  const int rc = glc_compact_join(blobs.data(), blob_bytes.data(), n, channels, nullptr, 0, &info);  // sizes the blob, or says why there is none
+  if (rc != GLC_EINVAL || info.bytes == 0) detail::check(rc);
+  std::vector<uint64_t> words(info.bytes / 8 + 1);  // 8-byte aligned
+  detail::check(glc_compact_join(blobs.data(), blob_bytes.data(), n, channels, words.data(), info.bytes, &info));
+  const uint8_t *p = reinterpret_cast<const uint8_t *>(words.data());
+  return std::vector<uint8_t>(p, p + info.bytes);
+}
+
 class Encoder {
  public:
   // Encoder::new(sample_rate: u32) — src/codec.rs:406
@@ -698,6 +725,13 @@ class StreamEncoder {
                   ctx_);
     segs.resize(n);
     return segs;
+  }
+  // glc::join_segments_device on this context, with this encoder's channel count
+  void join_segments_device(const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries, const std::vector<glc_stream_seg> &segs,
+                            const uint64_t *lengths, void *d_dst, uint64_t dst_bytes, uint64_t *d_cursor, glc_store_entry *d_entries_out,
+                            int64_t *d_lengths_out, uint32_t *d_seg_status) {
+    glc::join_segments_device(ctx_, d_arena, arena_bytes, d_entries, segs, lengths, channels_, d_dst, dst_bytes, d_cursor, d_entries_out,
+                              d_lengths_out, d_seg_status);
   }
   void synchronize() { detail::check(glc_ctx_synchronize(ctx_), ctx_); }
   glc_ctx *ctx() { return ctx_; }

@@ -1,5 +1,5 @@
 // host_fuzz.cpp — AddressSanitizer + UBSan harness for the host-side parsers and writers of the
-// library (no device code): the .glc container, the structured bridge and the compact-blob writer (glc_frames.cpp), the WAV twin
+// library (no device code): the .glc container, the structured bridge, the compact-blob writer and the segment join (glc_frames.cpp), the WAV twin
 // (glc_wav.cpp) and the FLAC twin (glc_flac.cpp).  GPU sanitizers are not available on the pool, host ones are, and
 // these are the functions that read files a user did not write.
 //
@@ -198,6 +198,99 @@ static void fuzz_to_compact() {
     if (glc_deserialize(bad.data(), bad.size(), &fr) != GLC_OK) continue;
     to_compact_checked(fr, false, nullptr);
     glc_frames_free(fr);
+  }
+}
+
+// ---- glc_compact_join: segment blobs into the blob of the whole clip -------------------------------
+// Every blob lies in a heap block of exactly its size and the output in one of exactly the size the function asked
+// for: a byte read or written behind either is a finding.
+static bool blob_of(const std::vector<uint8_t> &glc, std::vector<uint64_t> *blob, uint64_t *bytes) {
+  glc_frames *fr = nullptr;
+  REQUIRE(glc_deserialize(glc.data(), glc.size(), &fr) == GLC_OK);
+  glc_compact_info info;
+  const int sized = glc_frames_to_compact(fr, nullptr, 0, &info);
+  const bool ok = sized == GLC_EINVAL && info.bytes != 0;
+  if (ok) {
+    blob->assign(info.bytes / 8, 0);
+    REQUIRE(glc_frames_to_compact(fr, blob->data(), info.bytes, &info) == GLC_OK);
+    *bytes = info.bytes;
+  }
+  glc_frames_free(fr);
+  return ok;
+}
+
+static void fuzz_compact_join() {
+  const unsigned ch = 1 + static_cast<unsigned>(below(3));
+  const uint32_t n = 1 + static_cast<uint32_t>(below(3));
+  std::vector<std::vector<uint64_t>> blobs(n);
+  std::vector<uint64_t> sizes(n);
+  std::vector<const void *> ptrs(n);
+  uint64_t frames = 0;
+  for (uint32_t b = 0; b < n; ++b) {
+    const unsigned nf = 1 + static_cast<unsigned>(below(5));
+    const std::vector<uint8_t> glc = make_glc(ch, nf);
+    if (glc.empty() || !blob_of(glc, &blobs[b], &sizes[b])) return;
+    ptrs[b] = blobs[b].data(), frames += nf;
+  }
+  glc_compact_info info;
+  REQUIRE(glc_compact_join(ptrs.data(), sizes.data(), n, static_cast<uint16_t>(ch), nullptr, 0, &info) == GLC_EINVAL);
+  const uint64_t want = info.bytes;
+  REQUIRE(want >= 64 && want % 64 == 0 && info.n_frames == frames);
+  std::vector<uint64_t> out(want / 8, 0xABABABABABABABABull);
+  REQUIRE(glc_compact_join(ptrs.data(), sizes.data(), n, static_cast<uint16_t>(ch), out.data(), want - 1, &info) == GLC_EINVAL && info.bytes == want);
+  REQUIRE(glc_compact_join(ptrs.data(), sizes.data(), n, static_cast<uint16_t>(ch), out.data(), want, &info) == GLC_OK && info.bytes == want);
+  if (n == 1) REQUIRE(out == blobs[0]);  // one segment: the join is the segment
+  // the stream of the joined blob is the stream of the segments
+  const uint64_t n_samples = 1024ull * frames * ch;
+  const void *one[1] = {out.data()};
+  glc_frames *a = nullptr, *b = nullptr;
+  REQUIRE(glc_frames_from_compact(44100, n_samples, static_cast<uint16_t>(ch), one, &want, 1, &a) == GLC_OK);
+  REQUIRE(glc_frames_from_compact(44100, n_samples, static_cast<uint16_t>(ch), ptrs.data(), sizes.data(), n, &b) == GLC_OK);
+  std::vector<uint8_t> sa(glc_serialized_size(a)), sb(glc_serialized_size(b));
+  uint64_t w = 0;
+  REQUIRE(glc_serialize(a, sa.data(), sa.size(), &w) == GLC_OK && glc_serialize(b, sb.data(), sb.size(), &w) == GLC_OK && sa == sb);
+  glc_frames_free(a), glc_frames_free(b);
+  // no segments: refused, nothing sized
+  REQUIRE(glc_compact_join(ptrs.data(), sizes.data(), 0, static_cast<uint16_t>(ch), nullptr, 0, &info) == GLC_EINVAL && info.bytes == 0);
+  // a header whose frame count wraps every size formed from it (n_frames = 2^64 - 64, mono: the offsets wrap to 0, -256,
+  // -512 and the size comes out as 64): a blob of exactly 64 heap bytes, refused before anything behind them is read
+  {
+    const uint64_t counts[4] = {0xFFFFFFFFFFFFFFC0ull, 0xFFFFFFFFFFFFFFFFull, 1ull << 32, 1ull << 63};
+    for (uint64_t nf : counts) {
+      uint64_t *crafted = static_cast<uint64_t *>(std::malloc(64));
+      REQUIRE(crafted != nullptr);
+      const uint32_t magic = 0x42434C47u, one = 1;
+      std::memset(crafted, 0, 64);
+      std::memcpy(crafted, &magic, 4), std::memcpy(reinterpret_cast<uint8_t *>(crafted) + 4, &one, 4);
+      crafted[1] = nf, crafted[2] = nf == counts[0] ? 144 : 0, crafted[3] = 0, crafted[4] = 64;
+      const void *cp[1] = {crafted};
+      const uint64_t cs[1] = {64};
+      std::vector<uint64_t> o(1 << 10);
+      REQUIRE(glc_compact_join(cp, cs, 1, 1, o.data(), o.size() * 8, &info) == GLC_EINVAL && info.bytes == 0);
+      std::free(crafted);
+    }
+  }
+  // a damaged segment is joined or refused, never trusted: whatever its header and sections say
+  for (int round = 0; round < 40; ++round) {
+    const uint32_t which = static_cast<uint32_t>(below(n));
+    std::vector<uint8_t> bad(sizes[which]);
+    std::memcpy(bad.data(), blobs[which].data(), bad.size());
+    for (uint64_t m = 1 + below(3); m; --m) mutate(bad);
+    if (bad.empty()) continue;
+    uint8_t *exact = static_cast<uint8_t *>(std::malloc(bad.size()));  // malloc: 16-byte aligned, exactly bad.size() bytes
+    REQUIRE(exact != nullptr);
+    std::memcpy(exact, bad.data(), bad.size());
+    std::vector<const void *> p2 = ptrs;
+    std::vector<uint64_t> s2 = sizes;
+    p2[which] = exact, s2[which] = bad.size();
+    const int sized = glc_compact_join(p2.data(), s2.data(), n, static_cast<uint16_t>(ch), nullptr, 0, &info);
+    REQUIRE(sized == GLC_EINVAL);
+    if (info.bytes) {
+      std::vector<uint64_t> o2(info.bytes / 8 + 1);
+      const uint64_t cap = info.bytes;
+      REQUIRE(glc_compact_join(p2.data(), s2.data(), n, static_cast<uint16_t>(ch), o2.data(), cap, &info) == GLC_OK && info.bytes == cap);
+    }
+    std::free(exact);
   }
 }
 
@@ -429,6 +522,7 @@ int main(int argc, char **argv) {
     fuzz_glc(tmp);
     fuzz_bridge();
     fuzz_to_compact();
+    fuzz_compact_join();
     fuzz_wav(tmp);
     fuzz_flac();
     ++rounds;
