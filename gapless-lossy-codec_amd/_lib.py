@@ -269,6 +269,11 @@ SIGNATURES = {
     "glc_store_crop_slots": (C.c_int, [C.c_uint64, C.c_uint16, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "glc_decode_crops_device_store": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint64, _vp,
                                                 C.POINTER(GlcClipLayout)]),
+    "glc_store_ragged_slots": (C.c_int, [C.c_uint64, C.c_uint16, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "glc_decode_ragged_crops_device_store": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp, C.c_uint64,
+                                                       _vp, C.POINTER(GlcClipLayout), _vp]),
+    "glc_decode_ragged_crops_device_store_i16": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp,
+                                                           C.c_uint64, _vp, C.POINTER(GlcClipLayout), _vp]),
     "glc_store_compact_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "glc_encode_batch_device_compact_int": (C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.POINTER(GlcClipLayout), _vp, C.c_uint64, _vp, _vp]),
     "glc_roundtrip_batch_device_pcm": (C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.POINTER(GlcClipLayout), _vp, C.c_int,

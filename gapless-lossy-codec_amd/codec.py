@@ -303,6 +303,17 @@ def store_crop_slots(length: int, channels: int):
     return int(hops.value), int(frames.value)
 
 
+def store_ragged_slots(length: int, channels: int):
+    """(max_descs, max_frames): the hop descriptors and frames a ragged crop of `length` samples per channel needs
+    whatever its start and valid length (glc_store_ragged_slots) - the fixed slots a crop of
+    Decoder.decode_store_ragged_crops_tensor owns."""
+    if length < 0 or not 0 <= channels <= 0xFFFF:
+        raise GlcError(GLC_EINVAL, "store_ragged_slots: negative length or a channel count out of range")
+    descs, frames = C.c_uint64(), C.c_uint64()
+    check(lib.glc_store_ragged_slots(length, channels, C.byref(descs), C.byref(frames)))
+    return int(descs.value), int(frames.value)
+
+
 def compact_records(records: np.ndarray, channels: int) -> np.ndarray:
     """Host twin of the device compaction (glc_compact_records): records -> compact blob bytes."""
     records = np.ascontiguousarray(records, np.uint8).reshape(-1)
@@ -1065,6 +1076,18 @@ class Decoder(_Ctx):
         written.  Queued on torch's current stream; returns the output.  last_compact_status() afterwards: one
         status per crop.  dtype=torch.int16 (or an int16 `out`): the crops as 16-bit PCM, an unusable one 0
         (glc_decode_crops_device_store_i16)."""
+        b, length, max_length, out, lay = self._store_draw_tensors(arena, entries, lengths, clips, starts, length, max_length, planar, out, dtype)
+        with _on_torch_stream(self, out.device):
+            check(_entry_out("glc_decode_crops_device_store", out)(
+                self._h, C.c_void_p(arena.data_ptr()), arena.numel(), C.c_void_p(entries.data_ptr()),
+                C.c_void_p(lengths.data_ptr()), entries.shape[0], max_length, C.c_void_p(clips.data_ptr()),
+                C.c_void_p(starts.data_ptr()), length, C.c_void_p(out.data_ptr()), C.byref(lay)), self._h)
+        self._compact_clips = b
+        return out
+
+    def _store_draw_tensors(self, arena, entries, lengths, clips, starts, length, max_length, planar: bool, out, dtype):
+        """The checked tensors of a draw from the store -> (B, length, max_length, out, its GlcClipLayout); `out` None
+        is a new zero-filled tensor of B crops of `length` samples."""
         import torch
         ch = self.channels
         dtype = _tensor_out_dtype(dtype, out)
@@ -1080,13 +1103,35 @@ class Decoder(_Ctx):
         out, lay, ob, oc, ot = self._out_tensor(out, (b, ch, length) if planar else (b, length, ch), dtype, planar)
         if ob != b or oc != ch or ot != length:
             raise GlcError(GLC_EINVAL, f"out has shape {tuple(out.shape)} for {b} crops of {ch} channels and {length} samples")
+        return b, length, max_length, out, lay
+
+    def decode_store_ragged_crops_tensor(self, arena, entries, lengths, clips, starts, length: int, max_length: int, want=None,
+                                         planar: bool = True, out=None, dtype=None, valid=None):
+        """decode_store_crops_tensor for a ragged corpus (glc_decode_ragged_crops_device_store): every crop owns a row of
+        `length` samples per channel, takes v = min(want[i], lengths[clips[i]] - starts[i]) of them from its clip -
+        bit for bit decode_compact_crops_tensor's crop {starts[i], v} - and the rest of the row is +0.0; valid[i] = v.
+        A selection is usable when 0 <= starts[i] < the clip's length and 1 <= want[i] <= length: clips shorter than
+        `length`, starts near a clip's end and max_length < length are all fine.  want: (B,) int64 CUDA, or None: every
+        crop wants `length`.  valid: (B,) int64 CUDA, or None: a new one.  The other arguments, the flags of an
+        unusable crop (which is +0.0, valid 0) and last_compact_status() are decode_store_crops_tensor's; nothing is
+        read on the host and nothing is uploaded.  Queued on torch's current stream; returns (out, valid).
+        dtype=torch.int16 (or an int16 `out`): 16-bit PCM, padding and unusable crops 0
+        (glc_decode_ragged_crops_device_store_i16)."""
+        import torch
+        b, length, max_length, out, lay = self._store_draw_tensors(arena, entries, lengths, clips, starts, length, max_length, planar, out, dtype)
+        if want is not None:
+            self._tensor(want, "want", torch.int64, (b,))
+        if valid is None:
+            valid = torch.zeros(b, dtype=torch.int64, device=out.device)
+        self._tensor(valid, "valid", torch.int64, (b,))
         with _on_torch_stream(self, out.device):
-            check(_entry_out("glc_decode_crops_device_store", out)(
+            check(_entry_out("glc_decode_ragged_crops_device_store", out)(
                 self._h, C.c_void_p(arena.data_ptr()), arena.numel(), C.c_void_p(entries.data_ptr()),
                 C.c_void_p(lengths.data_ptr()), entries.shape[0], max_length, C.c_void_p(clips.data_ptr()),
-                C.c_void_p(starts.data_ptr()), length, C.c_void_p(out.data_ptr()), C.byref(lay)), self._h)
+                C.c_void_p(starts.data_ptr()), C.c_void_p(want.data_ptr()) if want is not None else None, length,
+                C.c_void_p(out.data_ptr()), C.byref(lay), C.c_void_p(valid.data_ptr())), self._h)
         self._compact_clips = b
-        return out
+        return out, valid
 
     def last_compact_status(self):
         """glc_decode_compact_last_status: per blob of the last decode_compact_* call a CompactStatus (flags 0 and

@@ -2741,27 +2741,39 @@ int glc_decode_compact_last_status(glc_ctx *ctx, glc_compact_status *status, uin
 extern "C++" {
 namespace {
 
-// What glc_decode_crops_device_store and its planner hook share: the checks of everything the host can see, and the
-// geometry of the call - the slots of a crop, the crops of a round, and where the planner's three arrays lie in rtb_tab.
+// What glc_decode_crops_device_store, its ragged sibling and their planner hooks share: the checks of everything the
+// host can see, and the geometry of the call - the slots of a crop, the crops of a round, and where the planner's three
+// arrays lie in rtb_tab.
 struct SdGeom {
   glc::CropSlots slots{};
+  uint64_t descs = 0;  // descriptors of a crop: its hops, or what a ragged crop needs (glc_common.h store_ragged_slots)
   uint64_t per_round = 0, max_front = 0;
   size_t o_dir = 0, o_desc = 0, o_verdict = 0, tab = 0;
 };
 
+// What the ragged draw has beyond the fixed one: per crop the length it wants and the length it got, device arrays
+// that may both be absent.  A null SdRagged is the fixed draw.
+struct SdRagged {
+  const int64_t *d_want;
+  int64_t *d_valid;
+};
+
 int sd_check(glc_ctx *ctx, const std::string &w, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
              const int64_t *d_lengths, uint64_t n_entries, uint64_t max_length, const int64_t *d_clips, const int64_t *d_starts,
-             uint64_t length, const void *d_out, size_t out_elem, const glc_clip_layout *out, SdGeom *g) {
+             uint64_t length, const void *d_out, size_t out_elem, const glc_clip_layout *out, const SdRagged *rg, SdGeom *g) {
   if (!d_arena || !d_entries || !d_lengths || !d_clips || !d_starts || !d_out) return fail(ctx, GLC_EINVAL, w + ": null argument");
   if (out->channels == 0) return fail(ctx, GLC_EINVAL, w + ": channels == 0");
   const uint64_t n = out->n_clips, ch = out->channels;
   if (!aligned(d_arena, 64)) return fail(ctx, GLC_EINVAL, w + ": the arena is not 64-byte aligned");
   if (!all_aligned(8, d_entries, d_lengths, d_clips, d_starts))
     return fail(ctx, GLC_EINVAL, w + ": entries, lengths, clips and starts must be 8-byte aligned");
+  if (rg && !all_aligned(8, rg->d_want, rg->d_valid)) return fail(ctx, GLC_EINVAL, w + ": want and valid must be 8-byte aligned");
   if (!aligned(d_out, out_elem)) return fail(ctx, GLC_EINVAL, w + ": output pointer not aligned to its sample size");
   if (n_entries == 0) return fail(ctx, GLC_EINVAL, w + ": n_entries == 0");
   if (length == 0) return fail(ctx, GLC_EINVAL, w + ": length == 0");
-  if (max_length < length) return fail(ctx, GLC_EINVAL, w + ": max_length is smaller than the crop");
+  // a ragged crop may be longer than every clip; its own samples must still not wrap (max_length bounds the fixed crop's)
+  if (!rg && max_length < length) return fail(ctx, GLC_EINVAL, w + ": max_length is smaller than the crop");
+  if (rg && length > (UINT64_MAX >> 12) / ch) return fail(ctx, GLC_EINVAL, w + ": length: stream too long");
   if (max_length > (UINT64_MAX >> 12) / ch) return fail(ctx, GLC_EINVAL, w + ": max_length: stream too long");
   glc_plan longest;
   if (const char *bad = frames_fault(max_length * ch, out->channels, &longest)) return fail(ctx, GLC_EINVAL, w + ": max_length: " + bad);
@@ -2775,18 +2787,27 @@ int sd_check(glc_ctx *ctx, const std::string &w, const void *d_arena, uint64_t a
   // every clip is `length` long: what the stride rule finds of clip 0 it finds of all
   if (const char *bad = stride_fault(lo, 0)) return fail(ctx, GLC_EINVAL, w + ": " + bad);
   g->slots = glc::store_crop_slots(length, out->channels);
+  g->descs = rg ? glc::store_ragged_slots(length, out->channels).max_descs : g->slots.max_hops;
   if (g->slots.max_frames + 1 > glc::kStoreRoundBudget)
     return fail(ctx, GLC_EINVAL, w + ": a crop of this length does not fit a round (glc_decode_crops_device_compact takes such windows)");
   g->per_round = glc::kStoreRoundBudget / (g->slots.max_frames + 1);
   g->max_front = longest.n_frames * ch;
   const ByteSpan all = span_of(d_out, lo, out_elem);
   if (overlaps(span_of(d_arena, arena_bytes), all)) return fail(ctx, GLC_EINVAL, w + ": the output extent overlaps the arena");
-  for (const ByteSpan &index : {span_of(d_entries, n_entries * sizeof(glc_store_entry)), span_of(d_lengths, n_entries * 8),
-                                span_of(d_clips, n * 8), span_of(d_starts, n * 8)})
-    if (overlaps(index, all)) return fail(ctx, GLC_EINVAL, w + ": the output extent overlaps an index array");
+  const ByteSpan index[] = {span_of(d_entries, n_entries * sizeof(glc_store_entry)), span_of(d_lengths, n_entries * 8),
+                            span_of(d_clips, n * 8), span_of(d_starts, n * 8), span_of(rg ? rg->d_want : nullptr, n * 8)};
+  for (const ByteSpan &in : index)
+    if (in.lo && overlaps(in, all)) return fail(ctx, GLC_EINVAL, w + ": the output extent overlaps an index array");
+  if (rg && rg->d_valid) {  // the one array beside the output that the call writes
+    const ByteSpan valid = span_of(rg->d_valid, n * 8);
+    if (overlaps(valid, all)) return fail(ctx, GLC_EINVAL, w + ": the output extent overlaps valid");
+    if (overlaps(valid, span_of(d_arena, arena_bytes))) return fail(ctx, GLC_EINVAL, w + ": valid overlaps the arena");
+    for (const ByteSpan &in : index)
+      if (in.lo && overlaps(in, valid)) return fail(ctx, GLC_EINVAL, w + ": valid overlaps an index array");
+  }
   TableOffsets offs;
   g->o_dir = offs.take(n * sizeof(glc::CompactBlob));
-  g->o_desc = offs.take(n * g->slots.max_hops * sizeof(glc::HopDescStrided));
+  g->o_desc = offs.take(n * g->descs * sizeof(glc::HopDescStrided));
   g->o_verdict = offs.take(n * sizeof(uint32_t));
   g->tab = offs.size();
   return GLC_OK;
@@ -2797,19 +2818,20 @@ int sd_check(glc_ctx *ctx, const std::string &w, const void *d_arena, uint64_t a
 // its way is in front of this kernel on the stream).
 int sd_plan(glc_ctx *ctx, const SdGeom &g, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
             const int64_t *d_lengths, uint64_t n_entries, uint64_t max_length, const int64_t *d_clips, const int64_t *d_starts,
-            uint64_t length, const glc_clip_layout *out) {
+            uint64_t length, const glc_clip_layout *out, const SdRagged *rg) {
   uint8_t *d_tab = static_cast<uint8_t *>(ctx->rtb_tab.p);
   const RtbLayout lo{out};
   glc::StoreDraw a{};
   a.arena = reinterpret_cast<uintptr_t>(d_arena), a.arena_bytes = arena_bytes;
   a.entries = d_entries, a.lengths = d_lengths, a.n_entries = n_entries, a.max_length = max_length;
   a.clips = d_clips, a.starts = d_starts, a.length = length, a.n_crops = out->n_clips;
-  a.ch = out->channels, a.max_hops = static_cast<uint32_t>(g.slots.max_hops), a.max_frames = static_cast<uint32_t>(g.slots.max_frames);
+  a.ch = out->channels, a.max_hops = static_cast<uint32_t>(g.descs), a.max_frames = static_cast<uint32_t>(g.slots.max_frames);
   a.per_round = static_cast<uint32_t>(g.per_round);
   a.clip_stride = out->clip_stride, a.channel_stride = out->channel_stride, a.planes = lo.planes() ? 1u : 0u;
   a.dir = reinterpret_cast<glc::CompactBlob *>(d_tab + g.o_dir);
   a.desc = reinterpret_cast<glc::HopDescStrided *>(d_tab + g.o_desc);
   a.verdict = reinterpret_cast<uint32_t *>(d_tab + g.o_verdict);
+  if (rg) a.ragged = 1u, a.want = rg->d_want, a.valid = rg->d_valid;
   GLC_HIP(ctx, glc::launch_store_plan_crops(a, ctx->stream));
   return GLC_OK;
 }
@@ -2827,19 +2849,30 @@ int glc_store_crop_slots(uint64_t length, uint16_t channels, uint64_t *max_hops,
   return GLC_OK;
 }
 
-// glc_decode_crops_device_store and its _i16 twin (T = int16_t): the same plan, the same launches, D2 narrowing.
+int glc_store_ragged_slots(uint64_t length, uint16_t channels, uint64_t *max_descs, uint64_t *max_frames) {
+  if (!max_descs || !max_frames || channels == 0 || length == 0 || length > (UINT64_MAX >> 12) / channels) {
+    glc::set_global_error("glc_store_ragged_slots: a null pointer, channels == 0, length == 0 or a length whose samples wrap");
+    return GLC_EINVAL;
+  }
+  const glc::RaggedSlots s = glc::store_ragged_slots(length, channels);
+  *max_descs = s.max_descs, *max_frames = s.max_frames;
+  return GLC_OK;
+}
+
+// glc_decode_crops_device_store, its _i16 twin (T = int16_t) and the ragged pair (rg given): the same plan, the same
+// launches - but for the descriptors of a crop, of which a ragged one may have one more - D2 narrowing.
 extern "C++" {
 template <typename T>
 static int sd_call(glc_ctx *ctx, const char *who, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
                    const int64_t *d_lengths, uint64_t n_entries, uint64_t max_length, const int64_t *d_clips, const int64_t *d_starts,
-                   uint64_t length, T *d_out, const glc_clip_layout *out) {
+                   uint64_t length, T *d_out, const glc_clip_layout *out, const SdRagged *rg = nullptr) {
   const std::string w(who);
   if (!ctx) return GLC_EINVAL;
   if (!out) return fail(ctx, GLC_EINVAL, w + ": null argument");
   if (out->n_clips == 0) return GLC_OK;
   SdGeom g;
   int rc = sd_check(ctx, w, d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips, d_starts, length, d_out, sizeof(T),
-                    out, &g);
+                    out, rg, &g);
   if (rc != GLC_OK) return rc;
   const uint64_t n = out->n_clips;
   const uint32_t ch = out->channels;
@@ -2853,7 +2886,8 @@ static int sd_call(glc_ctx *ctx, const char *who, const void *d_arena, uint64_t 
   if (rc == GLC_OK) rc = reserve_d1_plan(ctx, widest, ch);
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->rtb_tab, g.tab);
   if (rc == GLC_OK) rc = rt_reserve(ctx, ctx->cd_status, n * sizeof(glc::CompactStatus));
-  if (rc == GLC_OK) rc = sd_plan(ctx, g, d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips, d_starts, length, out);
+  if (rc == GLC_OK)
+    rc = sd_plan(ctx, g, d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips, d_starts, length, out, rg);
   if (rc != GLC_OK) return rc;
   const uint8_t *d_tab = static_cast<const uint8_t *>(ctx->rtb_tab.p);
   const auto *d_dir = reinterpret_cast<const glc::CompactBlob *>(d_tab + g.o_dir);
@@ -2873,10 +2907,46 @@ static int sd_call(glc_ctx *ctx, const char *who, const void *d_arena, uint64_t 
                                                glc::R2Mode{false, static_cast<uint32_t>(g.max_front), d_verdict + first}, d_arena,
                                                ctx->rt_rows.p, d_status + first, st, &rows));
     GLC_HIP(ctx, launch_d1_rows(ctx, rows, 0, M, ch, blocks, st));
-    GLC_HIP(ctx, glc::launch_overlap_add_strided(blocks, d_desc + first * g.slots.max_hops, static_cast<uint32_t>(nr * g.slots.max_hops), ch,
-                                                 out_planes, d_out, st));
+    GLC_HIP(ctx, glc::launch_overlap_add_strided(blocks, d_desc + first * g.descs, static_cast<uint32_t>(nr * g.descs), ch, out_planes,
+                                                 d_out, st));
   }
   ctx->cd_status_n = n;
+  return GLC_OK;
+}
+
+// The two planner hooks (include/glc_debug.h): the checks and the planner's launch as the calls make them, then what it
+// wrote copied back - `valid` (ragged only) from a table behind the planner's own in rtb_tab.
+static int sd_plan_hook(glc_ctx *ctx, const char *who, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
+                        const int64_t *d_lengths, uint64_t n_entries, uint64_t max_length, const int64_t *d_clips,
+                        const int64_t *d_starts, const int64_t *d_want, bool ragged, uint64_t length, const float *d_out,
+                        const glc_clip_layout *out, void *dir, void *desc, uint32_t *verdict, int64_t *valid) {
+  const std::string w(who);
+  if (!ctx) return GLC_EINVAL;
+  if (!out || !dir || !desc || !verdict || (ragged && !valid)) return fail(ctx, GLC_EINVAL, w + ": null argument");
+  if (out->n_clips == 0) return GLC_OK;
+  SdGeom g;
+  SdRagged rg{d_want, nullptr};
+  int rc = sd_check(ctx, w, d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips, d_starts, length, d_out, sizeof(float),
+                    out, ragged ? &rg : nullptr, &g);
+  if (rc != GLC_OK) return rc;
+  const uint64_t n = out->n_clips;
+  DeviceGuard guard(ctx->device);
+  rt_forget_streams(ctx);
+  ctx->cd_status_n = 0;
+  rc = rt_reserve(ctx, ctx->rtb_tab, g.tab + (ragged ? n * 8 : 0));
+  if (rc != GLC_OK) return rc;
+  uint8_t *d_tab = static_cast<uint8_t *>(ctx->rtb_tab.p);
+  rg.d_valid = reinterpret_cast<int64_t *>(d_tab + g.tab);
+  rc = sd_plan(ctx, g, d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips, d_starts, length, out,
+               ragged ? &rg : nullptr);
+  if (rc != GLC_OK) return rc;
+  GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  GLC_HIP(ctx, hipMemcpy(dir, d_tab + g.o_dir, n * sizeof(glc::CompactBlob), hipMemcpyDeviceToHost));
+  GLC_HIP(ctx, hipMemcpy(desc, d_tab + g.o_desc, n * g.descs * sizeof(glc::HopDescStrided), hipMemcpyDeviceToHost));
+  GLC_HIP(ctx, hipMemcpy(verdict, d_tab + g.o_verdict, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (ragged) {
+    GLC_HIP(ctx, hipMemcpy(valid, rg.d_valid, n * 8, hipMemcpyDeviceToHost));
+  }
   return GLC_OK;
 }
 }  // extern "C++"
@@ -2895,31 +2965,38 @@ int glc_decode_crops_device_store_i16(glc_ctx *ctx, const void *d_arena, uint64_
                  d_starts, length, d_out, out);
 }
 
+int glc_decode_ragged_crops_device_store(glc_ctx *ctx, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
+                                         const int64_t *d_lengths, uint64_t n_entries, uint64_t max_length, const int64_t *d_clips,
+                                         const int64_t *d_starts, const int64_t *d_want, uint64_t length, float *d_out,
+                                         const glc_clip_layout *out, int64_t *d_valid) {
+  const SdRagged rg{d_want, d_valid};
+  return sd_call(ctx, "glc_decode_ragged_crops_device_store", d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips,
+                 d_starts, length, d_out, out, &rg);
+}
+
+int glc_decode_ragged_crops_device_store_i16(glc_ctx *ctx, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
+                                             const int64_t *d_lengths, uint64_t n_entries, uint64_t max_length, const int64_t *d_clips,
+                                             const int64_t *d_starts, const int64_t *d_want, uint64_t length, int16_t *d_out,
+                                             const glc_clip_layout *out, int64_t *d_valid) {
+  const SdRagged rg{d_want, d_valid};
+  return sd_call(ctx, "glc_decode_ragged_crops_device_store_i16", d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length,
+                 d_clips, d_starts, length, d_out, out, &rg);
+}
+
 int glc_debug_store_plan_device(glc_ctx *ctx, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
                                 const int64_t *d_lengths, uint64_t n_entries, uint64_t max_length, const int64_t *d_clips,
                                 const int64_t *d_starts, uint64_t length, const float *d_out, const glc_clip_layout *out, void *dir,
                                 void *desc, uint32_t *verdict) {
-  const std::string w("glc_debug_store_plan_device");
-  if (!ctx) return GLC_EINVAL;
-  if (!out || !dir || !desc || !verdict) return fail(ctx, GLC_EINVAL, w + ": null argument");
-  if (out->n_clips == 0) return GLC_OK;
-  SdGeom g;
-  int rc = sd_check(ctx, w, d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips, d_starts, length, d_out, sizeof(float),
-                    out, &g);
-  if (rc != GLC_OK) return rc;
-  DeviceGuard guard(ctx->device);
-  rt_forget_streams(ctx);
-  ctx->cd_status_n = 0;
-  rc = rt_reserve(ctx, ctx->rtb_tab, g.tab);
-  if (rc == GLC_OK) rc = sd_plan(ctx, g, d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips, d_starts, length, out);
-  if (rc != GLC_OK) return rc;
-  const uint64_t n = out->n_clips;
-  const uint8_t *d_tab = static_cast<const uint8_t *>(ctx->rtb_tab.p);
-  GLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  GLC_HIP(ctx, hipMemcpy(dir, d_tab + g.o_dir, n * sizeof(glc::CompactBlob), hipMemcpyDeviceToHost));
-  GLC_HIP(ctx, hipMemcpy(desc, d_tab + g.o_desc, n * g.slots.max_hops * sizeof(glc::HopDescStrided), hipMemcpyDeviceToHost));
-  GLC_HIP(ctx, hipMemcpy(verdict, d_tab + g.o_verdict, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return GLC_OK;
+  return sd_plan_hook(ctx, "glc_debug_store_plan_device", d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips,
+                      d_starts, nullptr, false, length, d_out, out, dir, desc, verdict, nullptr);
+}
+
+int glc_debug_store_plan_ragged_device(glc_ctx *ctx, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
+                                       const int64_t *d_lengths, uint64_t n_entries, uint64_t max_length, const int64_t *d_clips,
+                                       const int64_t *d_starts, const int64_t *d_want, uint64_t length, const float *d_out,
+                                       const glc_clip_layout *out, void *dir, void *desc, uint32_t *verdict, int64_t *valid) {
+  return sd_plan_hook(ctx, "glc_debug_store_plan_ragged_device", d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips,
+                      d_starts, d_want, true, length, d_out, out, dir, desc, verdict, valid);
 }
 
 // ------------------------------------------------------------------------------ eviction from the store

@@ -190,6 +190,28 @@ GLC_HD inline CropSlots store_crop_slots(uint64_t length, uint32_t ch) {
   const uint64_t hops = (per_hop - ch + (kHop / 2) % ch + length * ch - 1) / per_hop + 1;
   return {hops, hops + 1};
 }
+// The slots of a RAGGED crop (include/glc.h glc_store_ragged_slots): of the `length` samples of its output row the
+// first v are the clip's - 1 <= v <= length, v = min(wanted, clip length - start) - and the rest +0.0.  Frames: a
+// valid part of v <= length samples needs no more than a crop of `length` does.  Descriptors: one per hop of the
+// valid part and one per 1024 ch positions of the padding [v ch, length ch).  With P = 1024 ch, L = length ch,
+// x = v ch and the valid part `a` positions into its first hop that is hops(a, x) + pads(x), hops = floor((a + x -
+// 1) / P) + 1, pads = ceil((L - x) / P) = floor((L - x + P - 1) / P).  The two numerators add up to S = a + L + P -
+// 2 whatever x is, so the sum is floor(S / P) + 1 where the remainders of the two add up to less than P - that is,
+// where (a + x - 1) % P <= S % P - and floor(S / P) elsewhere.  It grows with a, so a is the latest place of
+// store_crop_slots; there a + x - 1 = P + (512 % ch - 1) + (x - ch), whose remainder is least at x = ch, or, where
+// ch divides 512, at x = 2 ch (x = ch then ends exactly on the hop's last position).  If any x reaches the larger
+// value, that one does: the most descriptors are those of a valid part of ONE sample per channel, or of two, which
+// starts as late in its hop as a start can put it.  x = L is the fixed draw's crop: max_descs >= max_hops, and at
+// most one more.  length >= 1, length * ch must not wrap.
+struct RaggedSlots {
+  uint64_t max_descs, max_frames;
+};
+GLC_HD inline RaggedSlots store_ragged_slots(uint64_t length, uint32_t ch) {
+  const uint64_t per_hop = static_cast<uint64_t>(kHop) * ch, span = length * ch, a = per_hop - ch + (kHop / 2) % ch;
+  auto descs = [&](uint64_t x) { return (a + x - 1) / per_hop + 1 + (span - x + per_hop - 1) / per_hop; };
+  const uint64_t one = descs(ch), two = descs(length >= 2 ? 2ull * ch : ch);
+  return {one > two ? one : two, store_crop_slots(length, ch).max_frames};
+}
 // Crops of a round of glc_decode_crops_device_store: each counts its slot's frames + 1, as the crops of the pointer
 // call count their windows', against the 4096 frames + 1 of a decode round.
 constexpr uint64_t kStoreRoundBudget = 4097;

@@ -422,6 +422,17 @@ GLC_HD inline bool hop_desc(HopDescStrided *d, uint64_t nf, uint32_t ch, const T
 //               kCompactNoBlob (stored == 0, offset no multiple of 64, [offset, offset + bytes) not inside the arena)
 // max_length * ch must not wrap and frames(max_length) * ch must fit 32 bits (the caller's check).  No load leaves
 // the four index arrays; `arena` is a number here, nothing of the arena is read.
+// The RAGGED form (glc_decode_ragged_crops_device_store; `ragged` set, max_hops = store_ragged_slots' max_descs): crop
+// i wants w = want ? want[i] : length samples from starts[i] on and gets v = min(w, len - start) of them, the rest of
+// its `length` is +0.0.  The selection is usable when the index is in range, the length is the encoder's and at most
+// max_length, 0 <= start < len and 1 <= w <= length - start + length may lie beyond the clip, and max_length below
+// length.  Of a usable crop:
+//   dir[i]      as above, with the window plan_crop gives for {start, v}
+//   desc[i * max_hops + s]   s < n_hops: hop_desc of hop first_hop + s with the trim {whole.start + start * ch, v * ch};
+//               then the padding, a hop's worth per slot, both slots absent over interleaved samples [v * ch + k * 1024
+//               ch, min(v * ch + (k + 1) * 1024 ch, length * ch)) of the span, k = s - n_hops; null behind that
+//   valid[i]    v (where `valid` is not null); 0 for an unusable crop, which is otherwise as above
+// No load leaves the four index arrays and `want`.
 constexpr uint32_t kCompactNoBlob = 64u, kCompactBadCrop = 128u;
 struct StoreDraw {
   uint64_t arena, arena_bytes;
@@ -432,10 +443,12 @@ struct StoreDraw {
   uint64_t length, n_crops;
   uint32_t ch, max_hops, max_frames, per_round;
   uint64_t clip_stride, channel_stride;  // of the output layout, in elements
-  uint32_t planes, pad;                  // planes: planar output of more than one channel
+  uint32_t planes, ragged;               // planes: planar output of more than one channel
   CompactBlob *dir;
   HopDescStrided *desc;
   uint32_t *verdict;
+  const int64_t *want;  // the ragged form's two: either may be null
+  int64_t *valid;
 };
 hipError_t launch_store_plan_crops(const StoreDraw &a, hipStream_t s);
 

@@ -1880,7 +1880,13 @@ __global__ __launch_bounds__(256) void k_r2w_prefix(const CompactBlob *__restric
 // at most one chunk whose four `keep` are all false - d2_store then stores element by element and keeps none, and
 // d2_sample reads no block when both slots are absent - and k_overlap_add_planar returns at t_hi <= t_lo.  Neither
 // writes anything.  An unusable crop gets descriptors with both slots absent over its whole span: +0.0.
+// RAGGED (glc_decode_ragged_crops_device_store): the crop keeps v = min(wanted, len - start) samples and its descriptor
+// slots are the hops of that valid part, then the padding [v * ch, length * ch) of the span a hop's worth per slot,
+// both block slots absent, then null ones; slot 0 also writes v (0 for an unusable crop) where the caller asked.  A
+// valid descriptor and the pad descriptor behind it meet at span position v * ch, which need not be a chunk
+// boundary of the destination: DESIGN section 4, "a ragged crop's seam", has why neither writes the other's elements.
 // ------------------------------------------------------------------------------------------
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void k_store_plan_crops(StoreDraw a) {
   const unsigned long long t = static_cast<unsigned long long>(blockIdx.x) * 256ull + threadIdx.x;
   if (t >= a.n_crops * a.max_hops) return;
@@ -1889,6 +1895,7 @@ __global__ __launch_bounds__(256) void k_store_plan_crops(StoreDraw a) {
   const unsigned k = static_cast<unsigned>(i % a.per_round);  // the crop's place in its round
   const unsigned long long ch = a.ch, per_hop = static_cast<unsigned long long>(kHop) * ch;
   const long long clip = a.clips[i], start = a.starts[i];
+  unsigned long long keep = a.length;  // samples per channel the crop takes from its clip
   unsigned verdict = 0;
   glc_plan plan{};
   glc_crop_plan win{};
@@ -1900,11 +1907,20 @@ __global__ __launch_bounds__(256) void k_store_plan_crops(StoreDraw a) {
     // len <= max_length bounds len * ch (the host checked max_length), start <= len - length bounds start * ch
     if (len < 0 || static_cast<unsigned long long>(len) > a.max_length || start < 0) {
       verdict = kCompactBadCrop;
-    } else {
+    } else if (RAGGED) {
+      const long long want = a.want ? a.want[i] : static_cast<long long>(a.length);
+      if (start >= len || want < 1 || static_cast<unsigned long long>(want) > a.length) {
+        verdict = kCompactBadCrop;
+      } else {  // start < len bounds start * ch, keep <= length bounds keep * ch (the host checked length)
+        const unsigned long long left = static_cast<unsigned long long>(len - start);
+        keep = static_cast<unsigned long long>(want) < left ? static_cast<unsigned long long>(want) : left;
+      }
+    }
+    if (!verdict) {
       const unsigned long long n_samples = static_cast<unsigned long long>(len) * ch;
       plan = plan_encode(n_samples, static_cast<uint16_t>(a.ch));
       if (plan.n_frames == 0 ||
-          !plan_crop(n_samples, static_cast<uint16_t>(a.ch), glc_crop{static_cast<unsigned long long>(start), a.length}, &win))
+          !plan_crop(n_samples, static_cast<uint16_t>(a.ch), glc_crop{static_cast<unsigned long long>(start), keep}, &win))
         verdict = kCompactBadCrop;
     }
     if (!verdict) {
@@ -1922,20 +1938,25 @@ __global__ __launch_bounds__(256) void k_store_plan_crops(StoreDraw a) {
                        : CompactBlob{addr, cap, slot0 * a.ch, static_cast<unsigned>(plan.n_frames * ch),
                                      {static_cast<unsigned>(win.first_frame * ch), static_cast<unsigned>(win.n_frames * ch)}};
     a.verdict[i] = verdict;
+    if (RAGGED && a.valid) a.valid[i] = verdict ? 0ll : static_cast<long long>(keep);
   }
   const unsigned long long dst = i * a.clip_stride, span = a.length * ch;
   HopDescStrided d{-1, -1, 0u, 0u, 0ull, 0ull, 0ull};
-  if (verdict) {  // silence over the whole span, a hop's worth per slot
-    const unsigned long long j0 = s * per_hop;
-    if (j0 < span) {
-      const unsigned long long cnt = span - j0 < per_hop ? span - j0 : per_hop;
-      d = HopDescStrided{-1, -1, 0u, static_cast<unsigned>(cnt), a.planes ? dst : dst + j0, a.planes ? a.channel_stride : 0ull, j0};
-    }
+  // silence a hop's worth per slot: over the whole span of an unusable crop, behind the valid part of a ragged one
+  auto silence = [&](unsigned long long j0) {
+    if (j0 >= span) return;
+    const unsigned long long cnt = span - j0 < per_hop ? span - j0 : per_hop;
+    d = HopDescStrided{-1, -1, 0u, static_cast<unsigned>(cnt), a.planes ? dst : dst + j0, a.planes ? a.channel_stride : 0ull, j0};
+  };
+  if (verdict) {
+    silence(s * per_hop);
   } else if (s < win.n_hops) {
     const Trim whole = gapless_trim(plan.n_frames, a.ch, plan.encoder_delay, plan.per_channel * ch);
-    const Trim trim{whole.start + static_cast<unsigned long long>(start) * ch, span};  // what the crop keeps of its un-trimmed stream
+    const Trim trim{whole.start + static_cast<unsigned long long>(start) * ch, keep * ch};  // what the crop keeps of its un-trimmed stream
     hop_desc(&d, plan.n_frames, a.ch, trim, win.first_hop + s, static_cast<long long>(slot0) - static_cast<long long>(win.first_frame),
              dst, a.planes != 0, a.channel_stride);
+  } else if (RAGGED) {
+    silence(keep * ch + (s - win.n_hops) * per_hop);
   }
   a.desc[t] = d;
 }
@@ -3136,11 +3157,14 @@ hipError_t launch_store_plan_crops(const StoreDraw &a, hipStream_t s) {
   static_assert(sizeof(glc_store_entry) == 32 && sizeof(HopDescStrided) == 40, "read and written by the planner as laid out here");
   if (a.n_crops == 0) return hipSuccess;
   if (!a.entries || !a.lengths || !a.clips || !a.starts || !a.dir || !a.desc || !a.verdict || a.ch == 0 || a.ch > 65535u ||
-      a.max_hops == 0 || a.max_frames != a.max_hops + 1 || a.per_round == 0 || a.length == 0 || a.n_entries == 0)
+      a.max_hops == 0 || a.per_round == 0 || a.length == 0 || a.n_entries == 0)
     return hipErrorInvalidValue;
+  // descriptors per crop: the fixed draw's are its hops, one fewer than its frames; a ragged crop may need one more
+  if (a.max_frames != a.max_hops + 1 && !(a.ragged && a.max_frames == a.max_hops)) return hipErrorInvalidValue;
   const uint64_t threads = a.n_crops * a.max_hops, blocks = (threads + 255) / 256;
   if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_store_plan_crops, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
+  const auto planner = a.ragged ? k_store_plan_crops<true> : k_store_plan_crops<false>;
+  hipLaunchKernelGGL(planner, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

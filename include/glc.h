@@ -709,7 +709,8 @@ int glc_encode_batch_device_compact(glc_ctx *ctx, const float *d_pcm, const glc_
 
 /* ---- drawing crops from the store by device-side index and start ---------------------------- */
 
-/* Two more status flags, set only by glc_decode_crops_device_store, always together with GLC_COMPACT_BAD_HEADER. */
+/* Two more status flags, set only by glc_decode_crops_device_store and glc_decode_ragged_crops_device_store (which
+ * has its own rule for a usable selection), always together with GLC_COMPACT_BAD_HEADER. */
 #define GLC_COMPACT_NO_BLOB   64u   /* the entry holds no usable blob: stored == 0, offset not a multiple of 64,
                                        or [offset, offset + bytes) not inside the arena */
 #define GLC_COMPACT_BAD_CROP 128u   /* the selection is unusable: clip index outside [0, n_entries), a stored length
@@ -756,6 +757,61 @@ int glc_decode_crops_device_store(glc_ctx *ctx,
                                   uint64_t max_length,
                                   const int64_t *d_clips, const int64_t *d_starts, uint64_t length,
                                   float *d_out, const glc_clip_layout *out);
+
+/* ---- ragged crops from the store: short clips zero-padded on the device --------------------- */
+
+/* Host only: the slots a RAGGED crop of `length` samples per channel needs (below): the descriptors of its valid
+ * part - one per hop - plus those of its padding - one per 1024 ch interleaved positions - at their most over every
+ * valid length 1 .. length and every start, and the frames, which are glc_store_crop_slots' (a valid part is no longer
+ * than the row).  With f(v) = floor((1024 ch - ch + 512 % ch + v ch - 1) / (1024 ch)) + 1 + ceil((length - v) ch /
+ * (1024 ch)),  max_descs = max(f(1), f(min(2, length))): the most are needed by a valid part of one sample per
+ * channel, or of two, that starts as late in its hop as a start can put it; it is glc_store_crop_slots' max_hops or
+ * one more.  GLC_EINVAL: a null pointer, channels == 0, length == 0, a length * channels that wraps. */
+int glc_store_ragged_slots(uint64_t length, uint16_t channels, uint64_t *max_descs, uint64_t *max_frames);
+
+/* glc_decode_crops_device_store for a ragged corpus: every crop owns an output row of `length` samples per channel,
+ * takes as many of them from its clip as the clip has, and the rest of the row is zeros.  The arguments are that
+ * call's, plus d_want (device int64_t[n_clips], 8-byte aligned, or NULL: every crop wants `length`) and d_valid
+ * (device int64_t[n_clips], 8-byte aligned, or NULL).  With n = d_lengths[d_clips[i]], s = d_starts[i] and w = d_want ?
+ * d_want[i] : length, the selection of crop i is usable when the clip index is inside [0, n_entries), n is a length the
+ * encoder accepts and at most max_length, 0 <= s < n and 1 <= w <= length; otherwise its verdict is
+ * GLC_COMPACT_BAD_CROP and the entry is not read.  A usable selection whose entry is unusable is GLC_COMPACT_NO_BLOB, by
+ * that call's rule.  The valid length of a usable crop is v = min(w, n - s) >= 1:
+ *   samples [0, v) per channel of clip i of `out` are bit for bit what glc_decode_crops_device_compact writes for
+ *     d_blobs[i] = d_arena + entry.offset, blob_bytes[i] = entry.bytes, n_samples[i] = n * channels, crops[i] = {s, v} -
+ *     damaged blobs included - and glc_decode_compact_last_status gives that call's words, one per crop;
+ *   samples [v, length) of every channel are +0.0;
+ *   d_valid[i] = v.
+ * An unusable crop is +0.0 over its length * channels samples, with status flags = its verdict | GLC_COMPACT_BAD_HEADER,
+ * n_bad_rows = first_bad_row = 0, and d_valid[i] = 0.  Exactly the length * channels elements of every crop are
+ * written and no other element of d_out; out->lengths[i], or out->length, must be `length`.  max_length < length is
+ * legal: every clip is then short.  No load leaves the arena, d_entries[0 .. n_entries), d_lengths[0 .. n_entries), the
+ * two selection arrays or d_want[0 .. n_clips), whatever they hold; d_valid is only written, by ordinary stores.
+ * A crop owns the table rows and block slots of glc_store_crop_slots(length) - its valid part is no longer than that -
+ * and glc_store_ragged_slots(length)'s max_descs descriptors; the rounds are floor(4097 / (max_frames + 1)) crops.  The
+ * family's rules are glc_decode_crops_device_store's word for word: queued on glc_ctx_stream(ctx), NOT synchronised; no
+ * host-to-device copy, no wait for the pinned table image; the number and shape of the launches depend on n_clips,
+ * length and channels alone - not on the selection, the wanted lengths or how many clips are short; the call blocks
+ * only where a workspace has to grow; afterwards no stream is resident and an open decode session is closed.
+ * GLC_EINVAL, before anything is queued: everything glc_decode_crops_device_store refuses except max_length < length
+ * (a length * channels that wraps is refused by name), d_want or d_valid not 8-byte aligned, d_want or d_valid
+ * overlapping the output extent, d_valid overlapping the arena or an input array.  n_clips == 0 is GLC_OK.
+ * The _i16 twin writes 16-bit PCM narrowed as glc_decode_crops_device_store_i16 narrows: padding and unusable crops
+ * are 0, the layout counts int16_t elements, everything else is the same. */
+int glc_decode_ragged_crops_device_store(glc_ctx *ctx,
+                                         const void *d_arena, uint64_t arena_bytes,
+                                         const glc_store_entry *d_entries, const int64_t *d_lengths, uint64_t n_entries,
+                                         uint64_t max_length,
+                                         const int64_t *d_clips, const int64_t *d_starts, const int64_t *d_want,
+                                         uint64_t length,
+                                         float *d_out, const glc_clip_layout *out, int64_t *d_valid);
+int glc_decode_ragged_crops_device_store_i16(glc_ctx *ctx,
+                                             const void *d_arena, uint64_t arena_bytes,
+                                             const glc_store_entry *d_entries, const int64_t *d_lengths, uint64_t n_entries,
+                                             uint64_t max_length,
+                                             const int64_t *d_clips, const int64_t *d_starts, const int64_t *d_want,
+                                             uint64_t length,
+                                             int16_t *d_out, const glc_clip_layout *out, int64_t *d_valid);
 
 /* ---- evicting clips from the store: compact arena and index on the device ------------------- */
 

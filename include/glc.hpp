@@ -207,6 +207,16 @@ inline CropSlots store_crop_slots(uint64_t length, uint16_t channels) {
   return s;
 }
 
+// The descriptors and frames a ragged crop of `length` samples per channel needs (glc_store_ragged_slots).
+struct RaggedSlots {
+  uint64_t max_descs, max_frames;
+};
+inline RaggedSlots store_ragged_slots(uint64_t length, uint16_t channels) {
+  RaggedSlots s{};
+  detail::check(glc_store_ragged_slots(length, channels, &s.max_descs, &s.max_frames));
+  return s;
+}
+
 // Arena bytes that hold the blobs of every clip of a layout whatever their content (glc_compact_store_bound).
 inline uint64_t compact_store_bound(const glc_clip_layout &in) { return glc_compact_store_bound(&in); }
 
@@ -535,6 +545,23 @@ class Decoder {
                                      uint64_t length, int16_t *d_out, const glc_clip_layout &out) {
     detail::check(glc_decode_crops_device_store_i16(ctx_, d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips,
                                                     d_starts, length, d_out, &out), ctx_);
+  }
+  // ... ragged crops from the store: crop i takes min(d_want[i] or length, what its clip has from d_starts[i] on)
+  // samples, the rest of its `length` is zeros and d_valid[i] the count; d_want and d_valid may be null (glc.h
+  // glc_decode_ragged_crops_device_store)
+  void decode_ragged_crops_device_store(const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
+                                        const int64_t *d_lengths, uint64_t n_entries, uint64_t max_length, const int64_t *d_clips,
+                                        const int64_t *d_starts, const int64_t *d_want, uint64_t length, float *d_out,
+                                        const glc_clip_layout &out, int64_t *d_valid) {
+    detail::check(glc_decode_ragged_crops_device_store(ctx_, d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length, d_clips,
+                                                       d_starts, d_want, length, d_out, &out, d_valid), ctx_);
+  }
+  void decode_ragged_crops_device_store_i16(const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
+                                            const int64_t *d_lengths, uint64_t n_entries, uint64_t max_length, const int64_t *d_clips,
+                                            const int64_t *d_starts, const int64_t *d_want, uint64_t length, int16_t *d_out,
+                                            const glc_clip_layout &out, int64_t *d_valid) {
+    detail::check(glc_decode_ragged_crops_device_store_i16(ctx_, d_arena, arena_bytes, d_entries, d_lengths, n_entries, max_length,
+                                                           d_clips, d_starts, d_want, length, d_out, &out, d_valid), ctx_);
   }
   // glc::compact_store_device on this context
   void compact_store_device(void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries, const int64_t *d_lengths,

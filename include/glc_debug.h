@@ -209,6 +209,15 @@ int glc_debug_store_plan_device(glc_ctx *ctx, const void *d_arena, uint64_t aren
                                 const int64_t *d_starts, uint64_t length, const float *d_out, const glc_clip_layout *out,
                                 void *dir, void *desc, uint32_t *verdict);
 
+/* ... in its ragged form, exactly as glc_decode_ragged_crops_device_store launches it: d_want as that call takes it
+ * (device, or NULL), desc out->n_clips * max_descs records (glc_store_ragged_slots), and `valid`, out->n_clips host
+ * int64_t: what the planner wrote as d_valid, into a table of the context's.  The arena is only a number here too.
+ * Synchronises.  tests/test_store_ragged.py holds the ragged planner to its model through this. */
+int glc_debug_store_plan_ragged_device(glc_ctx *ctx, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries,
+                                       const int64_t *d_lengths, uint64_t n_entries, uint64_t max_length, const int64_t *d_clips,
+                                       const int64_t *d_starts, const int64_t *d_want, uint64_t length, const float *d_out,
+                                       const glc_clip_layout *out, void *dir, void *desc, uint32_t *verdict, int64_t *valid);
+
 /* The carry kernel of the streaming decode (k_stream_dec_carry) alone, for ONE lane whose carry lies at d_carry[0 ..
  * 2 * 1024 * channels): save == 0 copies the two carried halves into the second halves of block slots `prev` and prev + 1
  * of d_blocks ([n_slots][channels][2048] floats); save != 0 writes the carry from slots `prev` (-1: absent) and `cur` as a
