@@ -99,6 +99,11 @@ class GlcStreamSeg(C.Structure):
     _fields_ = [("stream", C.c_uint64), ("first_frame", C.c_uint64), ("n_frames", C.c_uint64)]
 
 
+class GlcStoreCut(C.Structure):
+    """glc_store_cut (include/glc.h): the clip and the frame range of one piece of glc_store_cut_device."""
+    _fields_ = [("clip", C.c_uint64), ("first_frame", C.c_uint64), ("n_frames", C.c_uint64)]
+
+
 class GlcStreamDecPlan(C.Structure):
     """glc_stream_dec_plan (include/glc.h): the samples per channel a push emits on a lane of a streaming decode."""
     _fields_ = [("first_sample", C.c_uint64), ("n_samples", C.c_uint64)]
@@ -310,6 +315,9 @@ SIGNATURES = {
                                                  C.c_uint16, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
     "glc_compact_join": (C.c_int, [C.POINTER(_vp), C.POINTER(C.c_uint64), C.c_uint32, C.c_uint16, _vp, C.c_uint64,
                                    C.POINTER(GlcCompactInfo)]),
+    "glc_store_cut_device": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(GlcStoreCut), C.c_uint64, C.POINTER(C.c_uint64),
+                                       C.c_uint16, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "glc_compact_cut": (C.c_int, [_vp, C.c_uint64, C.c_uint16, C.c_uint64, C.c_uint64, _vp, C.c_uint64, C.POINTER(GlcCompactInfo)]),
     "glc_version": (C.c_char_p, []),
 }
 

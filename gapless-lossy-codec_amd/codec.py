@@ -22,7 +22,7 @@ from typing import Iterator, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ._lib import (FRAMES_HOOK, GLC_EINVAL, GLC_PCM_F32, GLC_PCM_S16, GLC_PCM_S32, GlcClipLayout, GlcCompactInfo, GlcCompactStatus, GlcCrop, GlcCropPlan, GlcError,
-                   GlcFramesGather, GlcFramesView, GlcInfo, GlcPlan, GlcRoundtripInfo, GlcStreamDecPlan, GlcStreamPushPlan, GlcStreamSeg, check, lib)
+                   GlcFramesGather, GlcFramesView, GlcInfo, GlcPlan, GlcRoundtripInfo, GlcStreamDecPlan, GlcStoreCut, GlcStreamPushPlan, GlcStreamSeg, check, lib)
 
 FRAME_SIZE = 2048        # src/codec.rs:15
 HOP_SIZE = 1024          # src/codec.rs:16
@@ -366,6 +366,30 @@ def compact_join(blobs, channels: Optional[int] = None) -> bytes:
     return out.view(np.uint8)[:info.bytes].tobytes()
 
 
+def compact_cut(blob, first_frame: int, n_frames: int, channels: Optional[int] = None) -> bytes:
+    """The blob of frames [first_frame, first_frame + n_frames) of a clip's blob (glc_compact_cut): the host twin of
+    cut_clips_tensor and the inverse of compact_join - a fresh header, then the window's slice of each of the five
+    sections.  channels: the clip's channel count; None takes it from the blob's header.  GlcError (GLC_EINVAL) says
+    what is wrong with an unusable blob or window."""
+    arr = np.frombuffer(bytes(blob), np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, np.uint8).reshape(-1)
+    held = np.concatenate([arr, np.zeros(-arr.size % 8, np.uint8)]).view(np.uint64)  # an 8-byte aligned copy
+    if channels is None:
+        channels = int(arr[4:8].copy().view(np.uint32)[0]) if arr.size >= 8 else 0
+    if not 0 < channels <= 0xFFFF:
+        raise GlcError(GLC_EINVAL, "compact_cut: no channel count (a blob without a header, or channels out of range)")
+    first_frame, n_frames = int(first_frame), int(n_frames)
+    if first_frame < 0 or n_frames < 0:
+        raise GlcError(GLC_EINVAL, "compact_cut: first_frame and n_frames must not be negative")
+    info = GlcCompactInfo()
+    src = held.ctypes.data_as(C.c_void_p)
+    rc = lib.glc_compact_cut(src, arr.size, channels, first_frame, n_frames, None, 0, C.byref(info))  # sizes the piece, or says why there is none
+    if rc != GLC_EINVAL or info.bytes == 0:
+        check(rc)
+    out = np.empty(info.bytes // 8 + 1, np.uint64)
+    check(lib.glc_compact_cut(src, arr.size, channels, first_frame, n_frames, out.ctypes.data_as(C.c_void_p), info.bytes, C.byref(info)))
+    return out.view(np.uint8)[:info.bytes].tobytes()
+
+
 @dataclass
 class CompactStatus:
     """glc_compact_status: what the device check of one compact blob found (include/glc.h GLC_COMPACT_*)."""
@@ -699,6 +723,46 @@ class _Ctx:
                 C.c_void_p(entries_out.data_ptr()), C.c_void_p(lengths_out.data_ptr()) if lengths is not None else None,
                 C.c_void_p(seg_status.data_ptr())), self._h)
         return entries_out, lengths_out, seg_status
+
+    def cut_clips_tensor(self, arena, entries, cuts, out_arena, cursor, lengths=None, channels: Optional[int] = None):
+        """Cut stored clips into frame ranges (glc_store_cut_device): split, trim, resend - the inverse of
+        join_segments_tensor.  arena: the 1-D uint8 CUDA tensor the clips lie in; entries: its (N, 4) int64 CUDA index;
+        cuts: an (n, 3) host integer array or a list of triples (clip, first_frame, n_frames), in any order, a clip any
+        number of times, ranges may overlap; out_arena / cursor: the destination store, as
+        Encoder.encode_compact_batch_tensor takes them (the call appends at the cursor); lengths: per piece the samples
+        per channel (host integers, each planning to the piece's n_frames), or None for 1024 * n_frames; channels: the
+        clips' channel count (default: this object's).
+        Returns (entries_out, lengths_out, status), new CUDA tensors: (n, 4) int64 - all zero for a refused cut -,
+        (n,) int64 - 0 for a refused cut -, (n,) int32 of GLC_COMPACT_* bits.  Nothing is read on the host and nothing
+        but the table image is copied; queued on torch's current stream.  The context's resident stream, decode session
+        and last-info records are untouched."""
+        import torch
+        channels = int(getattr(self, "channels", 0) if channels is None else channels)
+        if not 0 < channels <= 0xFFFF:
+            raise GlcError(GLC_EINVAL, "cut_clips_tensor: channels must be 1..65535")
+        cuts = [tuple(int(v) for v in c) for c in (cuts.tolist() if isinstance(cuts, np.ndarray) else cuts)]
+        if any(len(c) != 3 or min(c) < 0 for c in cuts):
+            raise GlcError(GLC_EINVAL, "cut_clips_tensor: a cut is (clip, first_frame, n_frames), none of them negative")
+        n = len(cuts)
+        n_entries = self._tensor(entries, "entries", torch.int64, (None, 4)).shape[0]
+        self._tensor(arena, "arena", torch.uint8, (None,))
+        self._append_tensors(out_arena, cursor)
+        if lengths is not None:
+            lengths = _ints(lengths)
+            if len(lengths) != n:
+                raise GlcError(GLC_EINVAL, f"lengths must hold {n} values, one per cut")
+        dev = arena.device
+        entries_out = torch.zeros((n, 4), dtype=torch.int64, device=dev)
+        lengths_out = torch.zeros(n, dtype=torch.int64, device=dev)
+        status = torch.zeros(n, dtype=torch.int32, device=dev)
+        c_cuts = _c_array(GlcStoreCut, [GlcStoreCut(*c) for c in cuts])
+        c_lens = _c_array(C.c_uint64, lengths) if lengths is not None else None
+        with _on_torch_stream(self, dev):
+            check(lib.glc_store_cut_device(
+                self._h, C.c_void_p(arena.data_ptr()), arena.numel(), C.c_void_p(entries.data_ptr()), n_entries, c_cuts, n, c_lens,
+                channels, C.c_void_p(out_arena.data_ptr()), out_arena.numel(), C.c_void_p(cursor.data_ptr()),
+                C.c_void_p(entries_out.data_ptr()), C.c_void_p(lengths_out.data_ptr()), C.c_void_p(status.data_ptr())), self._h)
+        return entries_out, lengths_out, status
 
     def timer_begin(self) -> None:
         """Record a HIP event on the context's stream (device-side stopwatch)."""

@@ -3136,6 +3136,65 @@ int glc_store_join_segments_device(glc_ctx *ctx, const void *d_arena, uint64_t a
   });
 }
 
+// ------------------------------------------------------------------------------ cutting stored clips into frame ranges
+
+int glc_store_cut_device(glc_ctx *ctx, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries, uint64_t n_entries,
+                         const glc_store_cut *cuts, uint64_t n_cuts, const uint64_t *lengths, uint16_t channels, void *d_dst,
+                         uint64_t dst_bytes, uint64_t *d_cursor, glc_store_entry *d_entries_out, int64_t *d_lengths_out,
+                         uint32_t *d_cut_status) {
+  const std::string w("glc_store_cut_device");
+  if (!ctx) return GLC_EINVAL;
+  if (n_cuts == 0) return GLC_OK;  // nothing to cut: the cursor stays
+  if (!d_arena || !d_entries || !cuts || !d_dst || !d_cursor || !d_entries_out || !d_lengths_out || !d_cut_status)
+    return fail(ctx, GLC_EINVAL, w + ": null argument");
+  if (channels == 0) return fail(ctx, GLC_EINVAL, w + ": channels == 0");
+  if (!all_aligned(64, d_arena, d_dst)) return fail(ctx, GLC_EINVAL, w + ": the arenas must be 64-byte aligned");
+  if (!all_aligned(8, d_entries, d_cursor, d_entries_out, d_lengths_out))
+    return fail(ctx, GLC_EINVAL, w + ": entries, lengths_out and cursor must be 8-byte aligned");
+  if (!aligned(d_cut_status, 4)) return fail(ctx, GLC_EINVAL, w + ": d_cut_status must be 4-byte aligned");
+  if (n_cuts > 0xFFFFFFFFull) return fail(ctx, GLC_EINVAL, w + ": too many cuts");
+  if (n_entries > (1ull << 40)) return fail(ctx, GLC_EINVAL, w + ": too many entries");
+  return on_device(ctx, w, [&]() -> int {
+    uint64_t at = 0;
+    if (const char *bad = cuts_fault(cuts, n_cuts, lengths, channels, &at))
+      return fail(ctx, GLC_EINVAL, w + ": cut " + std::to_string(at) + ": " + bad);
+    const char *one, *other;
+    if (first_overlap({span_of(d_arena, arena_bytes, "the arena"), span_of(d_dst, dst_bytes, "the destination arena"),
+                       span_of(d_entries, n_entries * sizeof(glc_store_entry), "d_entries"),
+                       span_of(d_entries_out, n_cuts * sizeof(glc_store_entry), "d_entries_out"),
+                       span_of(d_lengths_out, n_cuts * 8, "d_lengths_out"), span_of(d_cut_status, n_cuts * 4, "d_cut_status"),
+                       span_of(d_cursor, 8, "d_cursor")},
+                      &one, &other))
+      return fail(ctx, GLC_EINVAL, w + ": " + one + " overlaps " + other);
+    // a host bound on the pieces' bytes, for the shape of the move: what the pieces' rows can hold, and the destination
+    uint64_t bound = 0;
+    for (uint64_t i = 0; i < n_cuts; ++i) bound = std::min(dst_bytes, bound + glc::compact_layout(channels, cuts[i].n_frames).bound);
+    // not a decode and not an encode: the resident stream, an open session, the kept plan and the last-info records stay.
+    // The image (the cut table) and, behind it, the workspace the kernels write share the batch calls' table buffer.
+    TableOffsets offs;
+    const size_t o_cuts = offs.take(n_cuts * sizeof(glc::StoreCutItem));
+    const size_t img_bytes = offs.size();
+    const size_t o_ws = offs.take(glc::store_cut_ws_bytes(n_cuts));
+    TableImage &image = ctx->rtb_image;
+    if (const int rc = image.begin(ctx, offs.size())) return rc;
+    auto *cut_tab = image.host<glc::StoreCutItem>(o_cuts);
+    for (uint64_t i = 0; i < n_cuts; ++i)
+      cut_tab[i] = glc::StoreCutItem{cuts[i].clip, cuts[i].first_frame, cuts[i].n_frames,
+                                     static_cast<int64_t>(lengths ? lengths[i] : glc::kHop * cuts[i].n_frames)};
+    if (const int rc = image.send(ctx, img_bytes)) return rc;
+    glc::StoreCut a{};
+    a.arena = static_cast<const unsigned char *>(d_arena), a.arena_bytes = arena_bytes, a.entries = d_entries, a.n_entries = n_entries;
+    a.cuts = image.dev<glc::StoreCutItem>(o_cuts), a.n_cuts = n_cuts;
+    a.ch = channels;
+    a.dst = static_cast<unsigned char *>(d_dst), a.dst_bytes = dst_bytes, a.cursor = d_cursor;
+    a.entries_out = d_entries_out, a.lengths_out = d_lengths_out, a.cut_status = d_cut_status;
+    a.ws = reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(ctx->rtb_tab.p) + o_ws);
+    GLC_HIP(ctx, glc::launch_store_cut_plan(a, ctx->stream));
+    GLC_HIP(ctx, glc::launch_store_cut_move(a, bound, ctx->stream));
+    return GLC_OK;
+  });
+}
+
 // ------------------------------------------------------------------------------ encode of a batch into per-clip compact blobs
 
 extern "C++" {

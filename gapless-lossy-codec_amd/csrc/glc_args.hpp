@@ -184,6 +184,20 @@ static inline const char *join_segs_fault(const glc_stream_seg *segs, uint64_t n
   return nullptr;
 }
 
+// THE cut rule (glc_store_cut_device): every cut has frames, its piece's rows pass the 32-bit row limit of frames_fault
+// and, where lengths are given, its frames are exactly plan_encode(lengths[i], 1).n_frames.  Which clip a cut names and
+// where its window lies are judged on the device, against an index and headers the host never reads.  *at: the cut.
+static inline const char *cuts_fault(const glc_store_cut *cuts, uint64_t n_cuts, const uint64_t *lengths, uint16_t channels, uint64_t *at) {
+  for (uint64_t i = 0; i < n_cuts; ++i) {
+    *at = i;
+    if (cuts[i].n_frames == 0) return "no frames";
+    if (cuts[i].n_frames > 0xFFFFFFFFull / channels) return "stream too long";
+    if (lengths && glc::plan_encode(lengths[i], 1).n_frames != cuts[i].n_frames)
+      return "n_frames is not the frame count of a clip of lengths[i] samples (glc_plan_encode)";
+  }
+  return nullptr;
+}
+
 // The one overlap of input and output the batch round trip allows: in place - the same pointer, the same layout and the
 // same format, so that every sample is read before the slot it lies in is written.
 static inline bool in_place(const void *in, const RtbLayout &li, glc_pcm_format fmt, const void *out, const RtbLayout &lo,

@@ -485,6 +485,59 @@ int glc_compact_join(const void *const *blobs, const uint64_t *blob_bytes, uint3
   return GLC_OK;
 }
 
+// The host twin of glc_store_cut_device (include/glc.h): the C-side statement of the cut.
+int glc_compact_cut(const void *blob, uint64_t blob_bytes, uint16_t channels, uint64_t first_frame, uint64_t n_frames, void *out,
+                    uint64_t cap, glc_compact_info *info) {
+  const std::string who("glc_compact_cut: ");
+  if (!info || channels == 0 || !blob || (!out && cap)) return GLC_EINVAL;
+  *info = glc_compact_info{0, 0, 0, 0};
+  const uint32_t ch = channels;
+  auto refuse = [&](const char *what) {
+    glc::set_global_error(who + what);
+    return GLC_EINVAL;
+  };
+  if (reinterpret_cast<uintptr_t>(blob) % 8 != 0 || reinterpret_cast<uintptr_t>(out) % 8 != 0) return refuse("blob and out must be 8-byte aligned");
+  if (n_frames == 0) return refuse("no frames");
+  if (blob_bytes < sizeof(glc::CompactHeader)) return refuse("blob shorter than its header");
+  glc::CompactHeader h;
+  std::memcpy(&h, blob, sizeof h);
+  // the bound of glc_compact_join on the header's own frame count, before any size is formed from it
+  if (h.n_frames == 0 || h.n_frames > 0xFFFFFFFFull / ch || h.n_frames > blob_bytes - sizeof(glc::CompactHeader))
+    return refuse("bad magic, channel count or frame count");
+  if (const char *bad = glc::compact_header_error(h, ch, h.n_frames, /*exact=*/true, blob_bytes)) return refuse(bad);
+  if (first_frame > h.n_frames || n_frames > h.n_frames - first_frame) return refuse("the window reaches behind the blob's frames");
+  // the rows in front of the window and in it; nothing behind the window is read
+  const glc::CompactLayout ls = glc::compact_layout(ch, h.n_frames);
+  const uint8_t *base = static_cast<const uint8_t *>(blob);
+  const uint32_t *cnt = reinterpret_cast<const uint32_t *>(base + ls.o_cnt);
+  const uint64_t m0 = first_frame * ch, m1 = (first_frame + n_frames) * ch;
+  uint64_t P0 = 0, P = 0, R0 = 0, R = 0;
+  for (uint64_t m = 0; m < m1; ++m) {
+    if (cnt[m] > glc::kHop) return refuse("a row longer than 1024 pairs in front of the window or in it");
+    (m < m0 ? P0 : P) += cnt[m];
+  }
+  for (uint64_t f = 0; f < first_frame + n_frames; ++f)
+    if (base[ls.o_israw + f]) (f < first_frame ? R0 : R) += ch;
+  if (P0 + P > h.n_pairs) return refuse("the window's rows reach behind n_pairs");
+  if (R0 + R > h.n_raw_rows) return refuse("the window's raw frames reach behind n_raw_rows");
+  const glc::CompactLayout l = glc::compact_layout(ch, n_frames);
+  const uint64_t raw_off = glc::compact_raw_offset(l, P);
+  *info = glc_compact_info{n_frames, P, R, raw_off + R * glc::kFrame * 2};
+  if (cap < info->bytes) return refuse("out is smaller than the piece (info->bytes)");
+  // the header, then the five sections, each the window's slice of the source's section; every gap is zero
+  uint8_t *o = static_cast<uint8_t *>(out);
+  std::memset(o, 0, l.o_pairs);
+  std::memset(o + l.o_pairs + 4 * P, 0, raw_off - (l.o_pairs + 4 * P));
+  const glc::CompactHeader ho = glc::compact_header(ch, n_frames, P, R, info->bytes);
+  std::memcpy(o, &ho, sizeof ho);
+  std::memcpy(o + l.o_israw, base + ls.o_israw + first_frame, n_frames);
+  std::memcpy(o + l.o_scale, base + ls.o_scale + 4 * m0, 4 * (m1 - m0));
+  std::memcpy(o + l.o_cnt, base + ls.o_cnt + 4 * m0, 4 * (m1 - m0));
+  if (P) std::memcpy(o + l.o_pairs, base + ls.o_pairs + 4 * P0, 4 * P);
+  if (R) std::memcpy(o + raw_off, base + glc::compact_raw_offset(ls, h.n_pairs) + R0 * glc::kFrame * 2, R * glc::kFrame * 2);
+  return GLC_OK;
+}
+
 uint64_t glc_record_bytes(uint16_t channels) { return glc::record_bytes(channels); }
 
 int glc_plan_encode(uint64_t n_samples, uint16_t channels, glc_plan *out) {

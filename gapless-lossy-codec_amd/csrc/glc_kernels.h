@@ -575,6 +575,50 @@ hipError_t launch_store_join_plan(const StoreJoin &a, hipStream_t s);
 // max_bytes: a host bound on the packed bytes of the stored clips; the launch's shape depends on it alone.
 hipError_t launch_store_join_move(const StoreJoin &a, uint64_t max_bytes, hipStream_t s);
 
+// The cut (glc_store_cut_device; DESIGN section 3, "cutting a stored clip").  include/glc.h states the rules; the two
+// launchers below are all of the call.
+//   C1  k_store_cut_plan, one workgroup of 256 threads per cut: thread 0 judges the selection (clip < n_entries), the
+//       entry (the draw's rule), the header (its own frame count, bounded as glc_compact_join bounds it before any size
+//       is formed, entry.bytes available) and the window (inside the header's frames).  Behind a header and a window
+//       that passed, all threads reduce the cnt words of the rows in front of the window (P0) and in it (P), every
+//       word held to 1024, and the non-zero is_raw bytes in front (R0 / ch) and in it (R / ch): 16-byte loads over
+//       the 64-byte aligned sections, the edges masked.  Nothing behind the window's last row / frame is read.
+//       cut_status[i] and found[i] = {arena offset, P0, P, R0, R, bad, the source's n_frames, the source's n_pairs}.
+//   C2  k_store_cut_scan, ONE workgroup of 1024 threads (k_store_join_scan's form, chunks of 1024 with a carry): the
+//       sizes, their exclusive scan from the rounded-up cursor, entries_out, lengths_out, the headers of the stored
+//       pieces, the cursor and the move table.
+//   M   k_store_cut_move: tiles of kStoreMoveTile bytes of the packed destination space [0, limit).  Every run of a
+//       piece - is_raw, scale, cnt, pairs, raw - is ONE contiguous range of the source blob, so a tile whose first and
+//       last unit lie in one run of one cut has one source base for all its units; a tile that spans runs or pieces
+//       finds each unit's cut by search over cut_off and its run from the piece's layout.
+// The workspace (store_cut_ws_bytes(n_cuts), 8-byte aligned), in uint64_t words: head[8] = {base, total, limit} (as
+// the join's), found[n_cuts] of 8 words, cut_off[n_cuts + 1] (packed), runs[n_cuts] of 10 words: per run the arena
+// offset of its first byte and its bytes without the padding.
+struct StoreCutItem {  // host, in the table image
+  uint64_t clip, first_frame, n_frames;
+  int64_t length;      // what lengths_out receives for a piece that is cut
+};
+struct StoreCut {
+  const unsigned char *arena;
+  uint64_t arena_bytes;
+  const glc_store_entry *entries;
+  uint64_t n_entries;
+  const StoreCutItem *cuts;
+  uint64_t n_cuts;
+  uint32_t ch, pad;
+  unsigned char *dst;
+  uint64_t dst_bytes;
+  uint64_t *cursor;
+  glc_store_entry *entries_out;
+  int64_t *lengths_out;
+  uint32_t *cut_status;
+  uint64_t *ws;
+};
+inline uint64_t store_cut_ws_bytes(uint64_t n_cuts) { return (8ull + 8ull * n_cuts + (n_cuts + 1ull) + 10ull * n_cuts) * 8ull; }
+hipError_t launch_store_cut_plan(const StoreCut &a, hipStream_t s);
+// max_bytes: a host bound on the packed bytes of the stored pieces; the launch's shape depends on it alone.
+hipError_t launch_store_cut_move(const StoreCut &a, uint64_t max_bytes, hipStream_t s);
+
 // The interleaved descriptor with a 32-bit destination, 24 bytes instead of 40: what glc_decode_batch uploads per
 // kept hop (its rounds address their output in 31 bits).  Same kernel, same chunks; kept beside HopDescStrided
 // because that driver measured slower, per launch and per call, with the wide form.

@@ -2506,6 +2506,292 @@ __global__ __launch_bounds__(256) void k_store_join_move(StoreJoin a) {
 }
 
 // ------------------------------------------------------------------------------------------
+// The cut: glc_store_cut_device (glc_kernels.h StoreCut has the plan, include/glc.h the rules).
+// ------------------------------------------------------------------------------------------
+struct StoreCutWs {  // the workspace's arrays (glc_kernels.h)
+  unsigned long long *head, *found, *cut_off, *runs;
+};
+__device__ __forceinline__ StoreCutWs store_cut_ws(const StoreCut &a) {
+  StoreCutWs w;
+  w.head = reinterpret_cast<unsigned long long *>(a.ws);
+  w.found = w.head + 8;
+  w.cut_off = w.found + 8ull * a.n_cuts;
+  w.runs = w.cut_off + a.n_cuts + 1;
+  return w;
+}
+
+// C1.  Thread 0 judges the selection, the entry, the header and the window, in that order: the entry of a clip index
+// outside the index is not read, nothing of a blob with an unusable entry, nothing behind a failing header.  The
+// header's own frame count is bounded as glc_compact_join bounds it before a size is formed from it.  The reductions
+// run over whole 16-byte units of the cnt and is_raw sections from their starts to the window's end and mask what lies
+// behind it inside the last unit; a unit that holds a row of the window lies inside the section, which ends on a
+// multiple of 64 inside the blob (the header rule), and no unit behind the window's last one is loaded.
+__global__ __launch_bounds__(256) void k_store_cut_plan(StoreCut a) {
+  __shared__ CompactHeader s_h;
+  __shared__ unsigned s_bits;
+  __shared__ unsigned long long s_off;
+  __shared__ unsigned long long s_part[5][4];
+  const StoreCutWs w = store_cut_ws(a);
+  const unsigned t = threadIdx.x;
+  for (unsigned long long i = blockIdx.x; i < a.n_cuts; i += gridDim.x) {
+    const StoreCutItem c = a.cuts[i];
+    if (t == 0) {
+      unsigned bits = 0;
+      unsigned long long off = 0;
+      if (c.clip >= a.n_entries) {
+        bits = kCompactBadCrop;  // and the entry is not read
+      } else {
+        const glc_store_entry e = a.entries[c.clip];
+        // each term is bounded before the difference is formed: nothing wraps (k_store_plan_crops' way)
+        if (e.stored == 0 || (e.offset & 63ull) || e.offset > a.arena_bytes || e.bytes > a.arena_bytes - e.offset) {
+          bits = kCompactNoBlob | kCompactBadHeader;
+        } else if (e.bytes < sizeof(CompactHeader)) {
+          bits = kCompactBadHeader;  // not even a header
+        } else {
+          const uint4 *hp = reinterpret_cast<const uint4 *>(a.arena + e.offset);
+          uint4 *hs = reinterpret_cast<uint4 *>(&s_h);
+          hs[0] = hp[0], hs[1] = hp[1], hs[2] = hp[2], hs[3] = hp[3];
+          off = e.offset;
+          const unsigned long long F = s_h.n_frames;
+          // the 32-bit row limit of every clip, and a frame is at least its is_raw byte (glc_compact_join's bound)
+          if (F == 0 || F > 0xFFFFFFFFull / a.ch || F > e.bytes - sizeof(CompactHeader) ||
+              compact_header_fault(s_h, a.ch, F, 0, true, e.bytes) != HeaderFault::kNone)
+            bits = kCompactBadHeader;
+          else if (c.first_frame > F || c.n_frames > F - c.first_frame)
+            bits = kCompactBadCrop;
+        }
+      }
+      s_bits = bits;
+      s_off = off;
+    }
+    __syncthreads();
+    unsigned long long p0 = 0, p = 0, r0 = 0, r = 0, over = 0;
+    if (s_bits == 0) {
+      const unsigned long long f0 = c.first_frame, f1 = f0 + c.n_frames, m0 = f0 * a.ch, m1 = f1 * a.ch;
+      const CompactLayout l = compact_layout(a.ch, s_h.n_frames);
+      const unsigned char *blob = a.arena + s_off;
+      auto row = [&](unsigned long long m, unsigned n) {
+        if (m >= m1) return;
+        if (n > static_cast<unsigned>(kHop)) over = 1;
+        if (m < m0) p0 += n; else p += n;
+      };
+      for (unsigned long long u = t; u * 4ull < m1; u += 256ull) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(blob + l.o_cnt + 16ull * u);
+        const unsigned long long m = 4ull * u;
+        row(m, v.x), row(m + 1, v.y), row(m + 2, v.z), row(m + 3, v.w);
+      }
+      auto flags = [&](unsigned long long f, unsigned word) {
+#pragma unroll
+        for (unsigned k = 0; k < 4u; ++k)
+          if (f + k < f1 && ((word >> (8u * k)) & 0xFFu)) {
+            if (f + k < f0) ++r0; else ++r;
+          }
+      };
+      for (unsigned long long u = t; u * 16ull < f1; u += 256ull) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(blob + l.o_israw + 16ull * u);
+        const unsigned long long f = 16ull * u;
+        flags(f, v.x), flags(f + 4, v.y), flags(f + 8, v.z), flags(f + 12, v.w);
+      }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+      p0 += __shfl_down(p0, off, 64);
+      p += __shfl_down(p, off, 64);
+      r0 += __shfl_down(r0, off, 64);
+      r += __shfl_down(r, off, 64);
+      over += __shfl_down(over, off, 64);
+    }
+    if ((t & 63u) == 0) s_part[0][t >> 6] = p0, s_part[1][t >> 6] = p, s_part[2][t >> 6] = r0, s_part[3][t >> 6] = r, s_part[4][t >> 6] = over;
+    __syncthreads();
+    if (t == 0) {
+      unsigned bits = s_bits;
+      auto sum = [&](int k) { return s_part[k][0] + s_part[k][1] + s_part[k][2] + s_part[k][3]; };
+      const unsigned long long P0 = sum(0), P = sum(1), R0 = sum(2) * a.ch, R = sum(3) * a.ch;
+      if (bits == 0) {
+        if (sum(4) != 0 || P0 + P > s_h.n_pairs) bits |= kCompactRowBounds;
+        if (R0 + R > s_h.n_raw_rows) bits |= kCompactRawRange;
+      }
+      a.cut_status[i] = bits;
+      unsigned long long *f = w.found + 8ull * i;
+      f[0] = bits ? 0ull : s_off;
+      f[1] = bits ? 0ull : P0;
+      f[2] = bits ? 0ull : P;
+      f[3] = bits ? 0ull : R0;
+      f[4] = bits ? 0ull : R;
+      f[5] = bits ? 1ull : 0ull;
+      f[6] = bits ? 0ull : s_h.n_frames;
+      f[7] = bits ? 0ull : s_h.n_pairs;
+    }
+    __syncthreads();  // s_h, s_bits, s_off and s_part are rewritten by the next cut
+  }
+}
+
+// C2.  k_store_place's placement rule word for word, a refused cut counting 0; then, per cut, where its five runs lie
+// in the arena: the window's slice of each of the source's sections (the source's layout from ITS frame and pair
+// counts, the pairs behind the P0 in front, the planes behind the R0 in front).
+__global__ __launch_bounds__(1024) void k_store_cut_scan(StoreCut a) {
+  __shared__ unsigned long long s[1024];
+  __shared__ unsigned long long s_limit;
+  const StoreCutWs w = store_cut_ws(a);
+  const unsigned t = threadIdx.x;
+  if (t == 0) s_limit = 0ull;
+  const unsigned long long base = align64(*a.cursor);  // every thread reads it here; thread 0 writes it behind the last barrier
+  unsigned long long carry = base;
+  unsigned long long *out = reinterpret_cast<unsigned long long *>(a.entries_out);
+  for (unsigned long long c0 = 0; c0 < a.n_cuts; c0 += 1024) {
+    const unsigned long long i = c0 + t;
+    unsigned long long bytes = 0, P = 0, R = 0;
+    StoreCutItem c{};
+    bool ok = false;
+    if (i < a.n_cuts) {
+      c = a.cuts[i];
+      ok = w.found[8 * i + 5] == 0;
+      if (ok) {
+        P = w.found[8 * i + 2], R = w.found[8 * i + 4];
+        bytes = compact_raw_offset(compact_layout(a.ch, c.n_frames), P) + R * (kFrameI * 2ull);
+      }
+    }
+    scan_sum_1024(s, bytes);
+    const unsigned long long offset = carry + s[t] - bytes;  // exclusive: every size is a multiple of 64
+    const unsigned long long chunk_total = s[1023];
+    __syncthreads();
+    carry += chunk_total;
+    if (i < a.n_cuts) {
+      const bool stored = ok && offset <= a.dst_bytes && bytes <= a.dst_bytes - offset;  // the encoder's rule (k_store_place)
+      out[4 * i] = ok ? offset : 0ull;
+      out[4 * i + 1] = bytes;
+      out[4 * i + 2] = P;
+      out[4 * i + 3] = R | (stored ? 1ull << 32 : 0ull);
+      a.lengths_out[i] = ok ? c.length : 0;
+      w.cut_off[i] = offset - base;
+      unsigned long long *run = w.runs + 10ull * i;
+      const unsigned long long *f = w.found + 8ull * i;
+      const CompactLayout ls = compact_layout(a.ch, f[6]);
+      const unsigned long long rows0 = c.first_frame * a.ch, rows = c.n_frames * a.ch;
+      run[0] = ok ? f[0] + ls.o_israw + c.first_frame : 0ull, run[1] = ok ? c.n_frames : 0ull;
+      run[2] = ok ? f[0] + ls.o_scale + 4ull * rows0 : 0ull, run[3] = ok ? 4ull * rows : 0ull;
+      run[4] = ok ? f[0] + ls.o_cnt + 4ull * rows0 : 0ull, run[5] = ok ? 4ull * rows : 0ull;
+      run[6] = ok ? f[0] + ls.o_pairs + 4ull * f[1] : 0ull, run[7] = ok ? 4ull * P : 0ull;
+      run[8] = ok ? f[0] + compact_raw_offset(ls, f[7]) + f[3] * (kFrameI * 2ull) : 0ull, run[9] = ok ? R * (kFrameI * 2ull) : 0ull;
+      if (stored) {
+        *reinterpret_cast<CompactHeader *>(a.dst + offset) = compact_header(a.ch, c.n_frames, P, R, bytes);
+        atomicMax(&s_limit, offset + bytes - base);
+      }
+    }
+  }
+  __syncthreads();
+  if (t == 0) {
+    w.cut_off[a.n_cuts] = carry - base;
+    w.head[0] = base;
+    w.head[1] = carry - base;
+    w.head[2] = s_limit;
+    *a.cursor = carry;
+  }
+}
+
+// M.  Where a byte of the packed destination space comes from.  A piece's blob is its header (C2 wrote it) and five
+// runs - is_raw, scale, cnt, pairs, raw -, each ONE contiguous range of the arena (C2's table), each followed by zeros
+// up to the next multiple of 64.  A refused cut has no bytes and shares its start with the next one: the search takes
+// the LAST cut that starts at or below the byte, which is the one that holds it (below `limit` that is a stored one).
+enum : unsigned { kCutHeader = 0, kCutIsRaw, kCutScale, kCutCnt, kCutPairs, kCutRaw };
+struct CutRun {  // one run of one cut
+  unsigned long long cut, at, len, src;  // at: the run's packed offset; len: its bytes without the padding; src: in the arena
+  unsigned sec;
+};
+// the run that holds packed byte p, the cut sought in [c_lo, c_hi]
+__device__ __forceinline__ CutRun cut_run(const StoreCut &a, const StoreCutWs &w, unsigned long long p, unsigned long long c_lo,
+                                          unsigned long long c_hi) {
+  while (c_lo < c_hi) {
+    const unsigned long long mid = c_lo + (c_hi - c_lo + 1) / 2;
+    if (w.cut_off[mid] <= p) c_lo = mid; else c_hi = mid - 1;
+  }
+  const unsigned long long base = w.cut_off[c_lo], rel = p - base;
+  const CompactLayout l = compact_layout(a.ch, a.cuts[c_lo].n_frames);
+  const unsigned long long *run = w.runs + 10ull * c_lo;
+  const unsigned long long o_raw = align64(l.o_pairs + run[7]);
+  CutRun r;
+  r.cut = c_lo;
+  if (rel < l.o_israw) {
+    r.sec = kCutHeader, r.at = base, r.len = l.o_israw, r.src = 0ull;
+    return r;
+  }
+  if (rel < l.o_scale) r.sec = kCutIsRaw, r.at = base + l.o_israw;
+  else if (rel < l.o_cnt) r.sec = kCutScale, r.at = base + l.o_scale;
+  else if (rel < l.o_pairs) r.sec = kCutCnt, r.at = base + l.o_cnt;
+  else if (rel < o_raw) r.sec = kCutPairs, r.at = base + l.o_pairs;
+  else r.sec = kCutRaw, r.at = base + o_raw;
+  r.src = run[2u * (r.sec - 1u)], r.len = run[2u * (r.sec - 1u) + 1u];
+  return r;
+}
+
+// The 16 bytes of run r from its byte u on.  A unit inside the run is join_load16 of src + u: both aligned units it
+// loads hold a byte of the run, so both lie inside the source blob, whose offset and size are multiples of 64.  The
+// run's last unit where the run does not end on 16 takes dword loads (byte loads in is_raw; the dword runs start and
+// end on dwords) of what the run holds and is zero behind it, as is every unit of the padding.
+__device__ __forceinline__ uint4 cut_unit(const unsigned char *arena, const CutRun &r, unsigned long long u) {
+  uint4 v{};
+  if (u >= r.len) return v;
+  const unsigned long long at = r.src + u;
+  if (u + 16ull <= r.len) return join_load16(arena, at);
+  const unsigned left = static_cast<unsigned>(r.len - u);  // 1 .. 15
+  if (r.sec == kCutIsRaw) {
+    auto word = [&](unsigned k) {
+      unsigned x = 0;
+#pragma unroll
+      for (unsigned b = 0; b < 4u; ++b)
+        if (k + b < left) x |= static_cast<unsigned>(arena[at + k + b]) << (8u * b);
+      return x;
+    };
+    v.x = word(0), v.y = word(4), v.z = word(8), v.w = word(12);
+  } else {
+    auto word = [&](unsigned k) { return k < left ? *reinterpret_cast<const unsigned *>(arena + at + k) : 0u; };
+    v.x = word(0), v.y = word(4), v.z = word(8), v.w = word(12);
+  }
+  return v;
+}
+
+// Packed bytes [lo, hi) - multiples of 16, hi - lo <= kStoreMoveTile, hi <= limit - to dst + base.  The runs of the
+// tile's first and last unit are found once (the same search in every lane: uniform).  Where they are one run of one
+// cut every unit of the tile lies in it or in its padding, and its source is the tile's one base plus p: no search and
+// no table load per unit.  Otherwise a unit finds its cut between the two and its run from that cut's layout.  Four
+// units per thread, all loads in front of all stores, named scalars (the comment at store_evict_gather_tile).
+__device__ __forceinline__ void store_cut_move_tile(const StoreCut &a, const StoreCutWs &w, unsigned long long base,
+                                                    unsigned long long lo, unsigned long long hi) {
+  const CutRun r_lo = cut_run(a, w, lo, 0, a.n_cuts - 1), r_hi = cut_run(a, w, hi - 16, r_lo.cut, a.n_cuts - 1);
+  const bool one_run = r_lo.cut == r_hi.cut && r_lo.sec == r_hi.sec && r_lo.sec != kCutHeader;
+  auto unit = [&](unsigned long long p, bool &live) {
+    uint4 v{};
+    live = false;
+    if (p >= hi) return v;
+    if (one_run) {
+      live = true;
+      return cut_unit(a.arena, r_lo, p - r_lo.at);
+    }
+    const CutRun r = cut_run(a, w, p, r_lo.cut, r_hi.cut);
+    if (r.sec == kCutHeader) return v;  // C2 wrote it
+    live = true;
+    return cut_unit(a.arena, r, p - r.at);
+  };
+  const unsigned long long p0 = lo + threadIdx.x * 16ull, p1 = p0 + 4096ull, p2 = p0 + 8192ull, p3 = p0 + 12288ull;
+  bool s0, s1, s2, s3;
+  const uint4 v0 = unit(p0, s0), v1 = unit(p1, s1), v2 = unit(p2, s2), v3 = unit(p3, s3);
+  unsigned char *dst = a.dst + base;
+  if (s0) *reinterpret_cast<uint4 *>(dst + p0) = v0;
+  if (s1) *reinterpret_cast<uint4 *>(dst + p1) = v1;
+  if (s2) *reinterpret_cast<uint4 *>(dst + p2) = v2;
+  if (s3) *reinterpret_cast<uint4 *>(dst + p3) = v3;
+}
+
+__global__ __launch_bounds__(256) void k_store_cut_move(StoreCut a) {
+  const StoreCutWs w = store_cut_ws(a);
+  const unsigned long long base = w.head[0], limit = w.head[2];
+  for (unsigned long long lo = static_cast<unsigned long long>(blockIdx.x) * kStoreMoveTile; lo < limit;
+       lo += static_cast<unsigned long long>(gridDim.x) * kStoreMoveTile) {
+    const unsigned long long hi = lo + kStoreMoveTile < limit ? lo + kStoreMoveTile : limit;
+    store_cut_move_tile(a, w, base, lo, hi);
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // S1: the virtual stream of a round of glc_roundtrip_batch_device, gathered from clips that lie strided
 // (and, `planar`, one plane per channel) in the caller's memory.  Workgroup row blockIdx.x is virtual frame
 // slot v: the 1024 * ch interleaved samples [1024 v, 1024 v + 1024) of the stream.  Its clip is the last one
@@ -3223,6 +3509,23 @@ hipError_t launch_store_join_move(const StoreJoin &a, uint64_t max_bytes, hipStr
   if (a.n_segs == 0 || a.n_clips == 0 || tiles == 0) return hipSuccess;
   (void)hipGetLastError();
   hipLaunchKernelGGL(k_store_join_move, dim3(static_cast<unsigned>(tiles < kStoreMoveGrid ? tiles : kStoreMoveGrid)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_store_cut_plan(const StoreCut &a, hipStream_t s) {
+  if (a.n_cuts == 0) return hipSuccess;
+  (void)hipGetLastError();
+  constexpr uint64_t kMaxGrid = 1ull << 20;  // cuts behind it are taken by the grid stride
+  hipLaunchKernelGGL(k_store_cut_plan, dim3(static_cast<unsigned>(a.n_cuts < kMaxGrid ? a.n_cuts : kMaxGrid)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_store_cut_scan, dim3(1), dim3(1024), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_store_cut_move(const StoreCut &a, uint64_t max_bytes, hipStream_t s) {
+  const uint64_t tiles = (max_bytes + kStoreMoveTile - 1) / kStoreMoveTile;
+  if (a.n_cuts == 0 || tiles == 0) return hipSuccess;
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(k_store_cut_move, dim3(static_cast<unsigned>(tiles < kStoreMoveGrid ? tiles : kStoreMoveGrid)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

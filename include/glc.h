@@ -1048,6 +1048,71 @@ int glc_store_join_segments_device(glc_ctx *ctx,
 int glc_compact_join(const void *const *blobs, const uint64_t *blob_bytes, uint32_t n_blobs, uint16_t channels,
                      void *out, uint64_t cap, glc_compact_info *info);
 
+/* ---- cutting stored clips into frame ranges: split, trim, resend ------------------------------ */
+
+/* The inverse of the join: the blob of frames [first_frame, first_frame + n_frames) of a stored clip, as a store entry of
+ * its own.  A blob's five sections are indexed by frame, by row or by the rows in front, so the piece is
+ * compact_header(ch, nf, P, R, bytes) followed by five contiguous windows of the source's sections, all padding zero:
+ * is_raw[f0 .. f0 + nf), the scale and cnt rows [ch f0, ch (f0 + nf)), the P pairs behind the P0 pairs of the rows in
+ * front, the R raw planes behind the R0 in front - P the sum of the window's cnt words, R channels times its non-zero
+ * is_raw bytes.  Nothing is recomputed and nothing is lossy: the pieces of a partition are byte for byte the segment
+ * blobs glc_stream_enc_push_device stores for those frames, they pass the header rule and the join's segment rule, and
+ * glc_store_join_segments_device over them gives the source back.  A piece is a clip to every consumer of the store
+ * (decode, crops, the draw, eviction) and a segment to glc_stream_dec_push_device.
+ * cuts[n_cuts] (host): any order, a clip any number of times, ranges may overlap; n_frames > 0; output i belongs to cut
+ *   i.  d_entries[n_entries] (device, never read by the host) is the source store's index.  lengths[i] (host, or NULL):
+ *   samples per channel of piece i, which must plan to n_frames frames (glc_plan_encode(lengths[i], 1)); NULL stands
+ *   for 1024 * n_frames, which does.  d_lengths_out[i] receives it, 0 for a refused cut.
+ * Usable cut (decided on the device; entries and blobs are untrusted), the first rule that fails:
+ *   GLC_COMPACT_BAD_CROP: clip >= n_entries (the entry is not read).
+ *   GLC_COMPACT_NO_BLOB | GLC_COMPACT_BAD_HEADER: the entry fails the draw's rule (stored != 0, offset a multiple of 64,
+ *     [offset, offset + bytes) inside the arena); nothing of the blob is read.
+ *   GLC_COMPACT_BAD_HEADER: the header fails the compact header rule with its OWN frame count - not 0, not more than
+ *     2^32 - 1 rows, not more than entry.bytes - 64, bounded before any size is formed as glc_compact_join bounds it -
+ *     and entry.bytes available; nothing behind the header is read.
+ *   GLC_COMPACT_BAD_CROP: first_frame + n_frames beyond the header's n_frames.
+ *   GLC_COMPACT_ROW_BOUNDS: a cnt word above 1024 in front of the window or in it, or P0 + P above the header's n_pairs;
+ *   GLC_COMPACT_RAW_RANGE: R0 + R above the header's n_raw_rows (the two may be set together).
+ *   Nothing behind the window's last row and frame is read, as in the crop calls: GLC_COMPACT_PAIR_SUM and
+ *   GLC_COMPACT_RAW_SUM are NEVER set, and damage behind the window does not refuse a cut.  Lists are not checked for
+ *   canonical form: the decode does that, as always.  d_cut_status[i] = 0 for a usable cut.
+ * A refused cut writes nothing to the destination, its entry is all zero words (a draw sees GLC_COMPACT_NO_BLOB) and it
+ *   counts 0 bytes in the placement.
+ * Placement is the encoder's, word for word the join's: *d_cursor is read and rounded up to 64; the pieces are placed in
+ *   cut order at the exclusive running sum of their sizes; stored = 1 when the piece fits dst_bytes; the cursor counts
+ *   on for pieces that do not fit; no byte of d_dst outside the stored blobs is written.  d_entries_out[i] = {offset,
+ *   bytes, P, R, stored}.
+ * No load leaves d_entries[0 .. n_entries) or [d_arena, d_arena + arena_bytes), whatever they hold, and for a usable
+ *   entry none leaves that entry's own [offset, offset + bytes).
+ * Family rules: queued on glc_ctx_stream(ctx), NOT synchronised; no copy to the host and none from it but the pinned
+ *   table image (the cut table); the call blocks only where its workspace has to grow and on the table image of the
+ *   previous batch call; three launches whose shape depends on n_cuts and a host bound on the pieces' bytes (the sum of
+ *   the worst-case sizes of n_frames frames, capped by dst_bytes), never on content.  Like the join it is neither a
+ *   decode nor an encode: the resident stream, an open decode session, the kept plan and every "last info / last
+ *   status" record stay as they were.
+ * GLC_EINVAL, before anything is queued and changing nothing: a null pointer (only lengths may be NULL), channels == 0,
+ *   an arena not 64-byte aligned, d_entries / d_cursor / d_entries_out / d_lengths_out not 8-byte aligned, d_cut_status
+ *   not 4-byte aligned, a cut with n_frames == 0, a piece of more than 2^32 - 1 rows, a lengths[i] that does not plan
+ *   to n_frames, any overlap among the two arenas, d_entries and the output arrays.  n_cuts == 0 is GLC_OK and leaves
+ *   the cursor alone. */
+typedef struct glc_store_cut { uint64_t clip, first_frame, n_frames; } glc_store_cut;
+int glc_store_cut_device(glc_ctx *ctx,
+                         const void *d_arena, uint64_t arena_bytes,
+                         const glc_store_entry *d_entries, uint64_t n_entries,
+                         const glc_store_cut *cuts, uint64_t n_cuts,
+                         const uint64_t *lengths, uint16_t channels,
+                         void *d_dst, uint64_t dst_bytes, uint64_t *d_cursor,
+                         glc_store_entry *d_entries_out, int64_t *d_lengths_out,
+                         uint32_t *d_cut_status);
+
+/* Host only, the same cut of a blob in host memory: the same bytes under the same rules, blob_bytes in the place of
+ * entry.bytes.  info (never NULL) receives the piece's counts; GLC_EINVAL with glc_last_error(NULL) naming what was
+ * wrong for an unusable blob or window, for n_frames == 0, and for a cap below info->bytes (info is then filled).
+ * blob and out 8-byte aligned. */
+int glc_compact_cut(const void *blob, uint64_t blob_bytes, uint16_t channels,
+                    uint64_t first_frame, uint64_t n_frames,
+                    void *out, uint64_t cap, glc_compact_info *info);
+
 /* ---- streaming decode: segment blobs in, PCM out, many live streams per launch chain ------- */
 
 /* The receiving half of a stream: the segments glc_stream_enc_* emits are decoded as they arrive, and the

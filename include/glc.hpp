@@ -260,6 +260,30 @@ inline std::vector<uint8_t> compact_join(const std::vector<const void *> &blobs,
   return std::vector<uint8_t>(p, p + info.bytes);
 }
 
+// Cut stored clips into frame ranges (glc.h glc_store_cut_device), on any context: the inverse of join_segments_device.
+// cuts (host): any order, a clip any number of times, ranges may overlap; piece i is appended to the store d_dst at
+// *d_cursor by the encoder's placement rule.  lengths (host, or null for 1024 * n_frames): one per cut.  Queued on the
+// context's stream, not synchronised; nothing is copied to the host.  Encoder::cut_clips_device,
+// Decoder::cut_clips_device and StreamEncoder::cut_clips_device forward here.
+inline void cut_clips_device(glc_ctx *ctx, const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries, uint64_t n_entries,
+                             const std::vector<glc_store_cut> &cuts, const uint64_t *lengths, uint16_t channels, void *d_dst,
+                             uint64_t dst_bytes, uint64_t *d_cursor, glc_store_entry *d_entries_out, int64_t *d_lengths_out,
+                             uint32_t *d_cut_status) {
+  detail::check(glc_store_cut_device(ctx, d_arena, arena_bytes, d_entries, n_entries, cuts.data(), cuts.size(), lengths, channels, d_dst,
+                                     dst_bytes, d_cursor, d_entries_out, d_lengths_out, d_cut_status), ctx);
+}
+
+// The blob of frames [first_frame, first_frame + n_frames) of a clip's blob, on the host (glc_compact_cut): the same bytes.
+inline std::vector<uint8_t> compact_cut(const void *blob, uint64_t blob_bytes, uint16_t channels, uint64_t first_frame, uint64_t n_frames) {
+  glc_compact_info info{};
+  const int rc = glc_compact_cut(blob, blob_bytes, channels, first_frame, n_frames, nullptr, 0, &info);  // sizes the piece, or says why there is none
+  if (rc != GLC_EINVAL || info.bytes == 0) detail::check(rc);
+  std::vector<uint64_t> words(info.bytes / 8 + 1);  // 8-byte aligned
+  detail::check(glc_compact_cut(blob, blob_bytes, channels, first_frame, n_frames, words.data(), info.bytes, &info));
+  const uint8_t *p = reinterpret_cast<const uint8_t *>(words.data());
+  return std::vector<uint8_t>(p, p + info.bytes);
+}
+
 class Encoder {
  public:
   // Encoder::new(sample_rate: u32) — src/codec.rs:406
@@ -378,6 +402,13 @@ class Encoder {
                             int64_t *d_lengths_out, int64_t *d_new_index, uint64_t *d_n_out, uint64_t *d_cursor) {
     glc::compact_store_device(ctx_, d_arena, arena_bytes, d_entries, d_lengths, n_entries, d_keep, d_dst, dst_bytes, d_entries_out,
                               d_lengths_out, d_new_index, d_n_out, d_cursor);
+  }
+  // glc::cut_clips_device on this context
+  void cut_clips_device(const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries, uint64_t n_entries,
+                        const std::vector<glc_store_cut> &cuts, const uint64_t *lengths, uint16_t channels, void *d_dst, uint64_t dst_bytes,
+                        uint64_t *d_cursor, glc_store_entry *d_entries_out, int64_t *d_lengths_out, uint32_t *d_cut_status) {
+    glc::cut_clips_device(ctx_, d_arena, arena_bytes, d_entries, n_entries, cuts, lengths, channels, d_dst, dst_bytes, d_cursor, d_entries_out,
+                          d_lengths_out, d_cut_status);
   }
   void synchronize() { detail::check(glc_ctx_synchronize(ctx_), ctx_); }
   glc_ctx *ctx() { return ctx_; }
@@ -570,6 +601,13 @@ class Decoder {
     glc::compact_store_device(ctx_, d_arena, arena_bytes, d_entries, d_lengths, n_entries, d_keep, d_dst, dst_bytes, d_entries_out,
                               d_lengths_out, d_new_index, d_n_out, d_cursor);
   }
+  // glc::cut_clips_device on this context
+  void cut_clips_device(const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries, uint64_t n_entries,
+                        const std::vector<glc_store_cut> &cuts, const uint64_t *lengths, uint16_t channels, void *d_dst, uint64_t dst_bytes,
+                        uint64_t *d_cursor, glc_store_entry *d_entries_out, int64_t *d_lengths_out, uint32_t *d_cut_status) {
+    glc::cut_clips_device(ctx_, d_arena, arena_bytes, d_entries, n_entries, cuts, lengths, channels, d_dst, dst_bytes, d_cursor, d_entries_out,
+                          d_lengths_out, d_cut_status);
+  }
   // what the device check found in the blobs (or windows) of the last of these calls (synchronises)
   std::vector<glc_compact_status> last_compact_status(uint64_t n_clips = 1) {
     std::vector<glc_compact_status> v(n_clips);
@@ -759,6 +797,13 @@ class StreamEncoder {
                             int64_t *d_lengths_out, uint32_t *d_seg_status) {
     glc::join_segments_device(ctx_, d_arena, arena_bytes, d_entries, segs, lengths, channels_, d_dst, dst_bytes, d_cursor, d_entries_out,
                               d_lengths_out, d_seg_status);
+  }
+  // glc::cut_clips_device on this context, with this encoder's channel count
+  void cut_clips_device(const void *d_arena, uint64_t arena_bytes, const glc_store_entry *d_entries, uint64_t n_entries,
+                        const std::vector<glc_store_cut> &cuts, const uint64_t *lengths, void *d_dst, uint64_t dst_bytes, uint64_t *d_cursor,
+                        glc_store_entry *d_entries_out, int64_t *d_lengths_out, uint32_t *d_cut_status) {
+    glc::cut_clips_device(ctx_, d_arena, arena_bytes, d_entries, n_entries, cuts, lengths, channels_, d_dst, dst_bytes, d_cursor, d_entries_out,
+                          d_lengths_out, d_cut_status);
   }
   void synchronize() { detail::check(glc_ctx_synchronize(ctx_), ctx_); }
   glc_ctx *ctx() { return ctx_; }

@@ -1,5 +1,5 @@
 // host_fuzz.cpp — AddressSanitizer + UBSan harness for the host-side parsers and writers of the
-// library (no device code): the .glc container, the structured bridge, the compact-blob writer and the segment join (glc_frames.cpp), the WAV twin
+// library (no device code): the .glc container, the structured bridge, the compact-blob writer, the segment join and the cut (glc_frames.cpp), the WAV twin
 // (glc_wav.cpp) and the FLAC twin (glc_flac.cpp).  GPU sanitizers are not available on the pool, host ones are, and
 // these are the functions that read files a user did not write.
 //
@@ -294,6 +294,62 @@ static void fuzz_compact_join() {
   }
 }
 
+// ---- glc_compact_cut: a frame range of a blob as a blob of its own ---------------------------------
+// The source lies in a heap block of exactly its size and the piece in one of exactly the size the function asked for.
+static void fuzz_compact_cut() {
+  const unsigned ch = 1 + static_cast<unsigned>(below(3));
+  const unsigned nf = 1 + static_cast<unsigned>(below(9));
+  std::vector<uint64_t> blob;
+  uint64_t bytes = 0;
+  const std::vector<uint8_t> glc = make_glc(ch, nf);
+  if (glc.empty() || !blob_of(glc, &blob, &bytes)) return;
+  glc_compact_info info;
+  // a partition: the pieces are sized, cut, and join back to the blob
+  std::vector<std::vector<uint64_t>> pieces;
+  std::vector<const void *> ptrs;
+  std::vector<uint64_t> sizes;
+  for (uint64_t f0 = 0; f0 < nf;) {
+    const uint64_t n = 1 + below(nf - f0);
+    REQUIRE(glc_compact_cut(blob.data(), bytes, static_cast<uint16_t>(ch), f0, n, nullptr, 0, &info) == GLC_EINVAL);
+    const uint64_t want = info.bytes;
+    REQUIRE(want >= 64 && want % 64 == 0 && info.n_frames == n);
+    pieces.emplace_back(want / 8, 0xABABABABABABABABull);
+    REQUIRE(glc_compact_cut(blob.data(), bytes, static_cast<uint16_t>(ch), f0, n, pieces.back().data(), want - 1, &info) == GLC_EINVAL && info.bytes == want);
+    REQUIRE(glc_compact_cut(blob.data(), bytes, static_cast<uint16_t>(ch), f0, n, pieces.back().data(), want, &info) == GLC_OK && info.bytes == want);
+    sizes.push_back(want);
+    f0 += n;
+  }
+  for (const auto &p : pieces) ptrs.push_back(p.data());
+  REQUIRE(glc_compact_join(ptrs.data(), sizes.data(), static_cast<uint32_t>(ptrs.size()), static_cast<uint16_t>(ch), nullptr, 0, &info) == GLC_EINVAL &&
+          info.bytes == bytes);
+  std::vector<uint64_t> back(bytes / 8);
+  REQUIRE(glc_compact_join(ptrs.data(), sizes.data(), static_cast<uint32_t>(ptrs.size()), static_cast<uint16_t>(ch), back.data(), bytes, &info) == GLC_OK);
+  REQUIRE(back == blob);
+  // no frames, a window beyond the frames, sums that wrap: refused, nothing sized
+  REQUIRE(glc_compact_cut(blob.data(), bytes, static_cast<uint16_t>(ch), 0, 0, nullptr, 0, &info) == GLC_EINVAL && info.bytes == 0);
+  REQUIRE(glc_compact_cut(blob.data(), bytes, static_cast<uint16_t>(ch), nf, 1, nullptr, 0, &info) == GLC_EINVAL && info.bytes == 0);
+  REQUIRE(glc_compact_cut(blob.data(), bytes, static_cast<uint16_t>(ch), 1, ~0ull, nullptr, 0, &info) == GLC_EINVAL && info.bytes == 0);
+  // a damaged blob is cut or refused, never trusted: whatever its header and sections say
+  for (int round = 0; round < 40; ++round) {
+    std::vector<uint8_t> bad(bytes);
+    std::memcpy(bad.data(), blob.data(), bad.size());
+    for (uint64_t m = 1 + below(3); m; --m) mutate(bad);
+    if (bad.empty()) continue;
+    uint8_t *exact = static_cast<uint8_t *>(std::malloc(bad.size()));  // malloc: 16-byte aligned, exactly bad.size() bytes
+    REQUIRE(exact != nullptr);
+    std::memcpy(exact, bad.data(), bad.size());
+    const uint64_t f0 = below(nf + 1), n = below(nf + 2);
+    const int sized = glc_compact_cut(exact, bad.size(), static_cast<uint16_t>(ch), f0, n, nullptr, 0, &info);
+    REQUIRE(sized == GLC_EINVAL);
+    if (info.bytes) {
+      std::vector<uint64_t> o2(info.bytes / 8 + 1);
+      const uint64_t cap = info.bytes;
+      REQUIRE(glc_compact_cut(exact, bad.size(), static_cast<uint16_t>(ch), f0, n, o2.data(), cap, &info) == GLC_OK && info.bytes == cap);
+    }
+    std::free(exact);
+  }
+}
+
 // ---- the structured bridge: flat view, from_parts / from_gather on hostile arrays ------------------
 static void fuzz_bridge() {
   std::vector<uint8_t> good = make_glc(1 + static_cast<unsigned>(below(3)), 1 + static_cast<unsigned>(below(6)));
@@ -523,6 +579,7 @@ int main(int argc, char **argv) {
     fuzz_bridge();
     fuzz_to_compact();
     fuzz_compact_join();
+    fuzz_compact_cut();
     fuzz_wav(tmp);
     fuzz_flac();
     ++rounds;
