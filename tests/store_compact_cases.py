@@ -5,7 +5,8 @@ An entry is [offset, bytes, n_pairs, n_raw_rows | stored << 32] in Python ints (
 never wraps.  A case is a dict:
   name, arena_bytes, entries, lengths (a list, one per entry), keep (bytes 0..255),
   dst_bytes (None: in place; else the capacity of a disjoint destination arena),
-  round (None: any round size; else the in-place round, in bytes, the case was laid out for)."""
+  round (None: any round size; else the in-place round, in bytes, the case was laid out for),
+  big (only the grid-stride cases: the arena's bytes are drawn as bytes)."""
 import numpy as np
 
 DROPPED, UNUSABLE, OUT_OF_ORDER = -1, -2, -3
@@ -13,6 +14,9 @@ U64 = 1 << 64
 PATTERN = 0xA5                        # what the GPU tests fill every byte with that must not be written
 TILE = 16384                          # bytes one workgroup moves at a time (csrc/glc_kernels.h kStoreMoveTile)
 CHUNK = 1024                          # entries of one chunk of the scan
+GRID = 2048                           # workgroups of a move launch at most (kStoreMoveGrid): tile GRID is a second pass
+TAIL_CAP = 1024 * 256                 # entries one pass of k_store_evict_tail zeroes
+DEFAULT_ROUND = 64 << 20              # the in-place round where none is set (csrc/glc_api.hip kStoreCompactRound)
 
 
 def entry(offset, size, n_pairs=0, n_raw_rows=0, stored=1):
@@ -25,16 +29,9 @@ def usable(e, arena_bytes):
         and size <= arena_bytes - offset
 
 
-def compact(arena, arena_bytes, entries, lengths, keep, dst=None, dst_bytes=None):
-    """-> dict(arena: the destination afterwards (the source arena itself in place), entries (n, 4) of Python ints,
-    lengths (or None), new_index, n_out, cursor).  `arena` / `dst` are uint8 arrays at least arena_bytes / dst_bytes
-    long; neither is modified."""
-    n = len(entries)
-    in_place = dst is None
-    if in_place:
-        dst_bytes = arena_bytes
-    out = np.array(arena if in_place else dst, np.uint8, copy=True)
-    new_index, kept = [0] * n, []
+def verdicts(arena_bytes, entries, keep):
+    """(new_index, the indices of the kept entries in order): the keep byte, the entry rule and the order rule."""
+    new_index, kept = [0] * len(entries), []
     ends = 0                                                  # E_i: the maximum of offset + bytes over the candidates in front
     for i, e in enumerate(entries):
         if not keep[i]:
@@ -49,6 +46,19 @@ def compact(arena, arena_bytes, entries, lengths, keep, dst=None, dst_bytes=None
             new_index[i] = len(kept)
             kept.append(i)
         ends = max(ends, e[0] + e[1])
+    return new_index, kept
+
+
+def compact(arena, arena_bytes, entries, lengths, keep, dst=None, dst_bytes=None):
+    """-> dict(arena: the destination afterwards (the source arena itself in place), entries (n, 4) of Python ints,
+    lengths (or None), new_index, n_out, cursor).  `arena` / `dst` are uint8 arrays at least arena_bytes / dst_bytes
+    long; neither is modified."""
+    n = len(entries)
+    in_place = dst is None
+    if in_place:
+        dst_bytes = arena_bytes
+    out = np.array(arena if in_place else dst, np.uint8, copy=True)
+    new_index, kept = verdicts(arena_bytes, entries, keep)
     entries_out = [[0, 0, 0, 0] for _ in range(n)]
     lengths_out = None if lengths is None else [0] * n
     place = 0
@@ -66,6 +76,8 @@ def compact(arena, arena_bytes, entries, lengths, keep, dst=None, dst_bytes=None
 
 def arena_of(case, seed=0):
     """The seeded random bytes of a case's source arena (arena_bytes of them)."""
+    if case.get("big"):               # tens of MiB: bytes drawn as bytes
+        return np.random.default_rng(0x5eed + seed + case["arena_bytes"] % 9973).integers(0, 256, case["arena_bytes"], dtype=np.uint8)
     rng = np.random.RandomState(0x5eed + seed + case["arena_bytes"] % 9973)
     return rng.randint(0, 256, case["arena_bytes"]).astype(np.uint8)
 
@@ -210,3 +222,61 @@ ROUNDS = (1024, 4096)
 
 def all_cases():
     return small_cases() + [c for r in ROUNDS for c in round_edges(r)]
+
+
+# ------------------------------------------------------------------------------------------ grid-stride edges
+# Arenas of tens of MiB: more than GRID tiles, so that the movers' grid-stride loops run a second pass (tests/
+# store_mover_paths.py names what a case reaches).  Cheap to describe - the bytes are drawn when a test asks for them.
+
+MIB = 1 << 20
+BIG_ROUNDS = (17 * MIB + 64, 3 * TILE + 64, None)         # 2 * tiles above GRID and no multiple of the tile; a few tiles; one round
+
+
+def big(c):
+    c["big"] = True
+    return c
+
+
+def grid_out_of_place():
+    """36 MiB of kept blobs out of an arena of 38: large and small ones on both sides of tile GRID, which a large one spans."""
+    sizes = [64, 20 * MIB + 320, 128, 9 * MIB + 64, 4096, 64, 5 * MIB + 192, 3 * TILE, 64, 2 * MIB + 64, 192, 64, 320]
+    keep = [0, 1, 1, 1, 0, 1, 1, 1, 0, 1, 1, 0, 1]
+    ent, end = laid(sizes, gaps=[0, 64, 0, 0, 128, 0, 0, 0, 0, 64, 0, 0, 0])
+    total = sum(s for s, k in zip(sizes, keep) if k)
+    assert total > (GRID + 64) * TILE
+    return big(case("grid_out_of_place", ent, keep, end + 64, dst_bytes=total + 128))
+
+
+def grid_in_place():
+    """40 MiB in place: a dropped 64 bytes in front, so every blob shifts by 64 and overlaps its own source; blobs that span
+    the boundaries of a 17 MiB + 64 round; a second dropped blob far behind; the last kept blob ends the arena."""
+    sizes = [64, 12 * MIB + 320, 9 * MIB + 192, 64, 11 * MIB + 64, 6 * MIB + 128, 4096, 2 * MIB - 4096 - 64 * 9, 64]
+    keep = [0, 1, 1, 1, 1, 1, 0, 1, 1]
+    ent, end = laid(sizes)
+    assert end > 2 * BIG_ROUNDS[0] and end > (GRID + 64) * TILE
+    return big(case("grid_in_place", ent, keep, end))
+
+
+def long_tail():
+    """TAIL_CAP + 300 entries of 64 bytes, most dropped, some of the last 300 kept: the zeroed tail of the output arrays is
+    longer than one pass of k_store_evict_tail."""
+    n = TAIL_CAP + 300
+    ent, end = laid([64] * n)
+    keep = [1 if i in (3, 1024, 70000, TAIL_CAP - 1, TAIL_CAP, TAIL_CAP + 7, n - 2, n - 1) or i % 50021 == 11 else 0 for i in range(n)]
+    return big(case("long_tail", ent, keep, end))
+
+
+GRID_RUNS = {"grid_out_of_place": (grid_out_of_place, None), "grid_in_place_round_17_mib_64": (grid_in_place, BIG_ROUNDS[0]),
+             "grid_in_place_round_3_tiles_64": (grid_in_place, BIG_ROUNDS[1]), "grid_in_place_one_round": (grid_in_place, BIG_ROUNDS[2]),
+             "long_tail": (long_tail, None)}
+
+
+def grid_runs():
+    """(case, in-place round) of every run of the grid-stride cases."""
+    return [(make(), rnd) for make, rnd in GRID_RUNS.values()]
+
+
+def small_runs():
+    """(case, in-place round) of every run tests/test_store_compact.py makes of the small cases."""
+    runs = [(c, None) for c in all_cases()] + [(c, r) for r in ROUNDS for c in round_edges(r)]
+    return runs + [(c, 1024) for c in own_source_overlap() + keep_patterns()] + [(c, 1024 + 64) for c in round_edges(4096)]

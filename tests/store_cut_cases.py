@@ -5,6 +5,7 @@ placement rule over the pieces.
 
 The blobs are made by the builder of tests/store_join_cases.py: the cut is structural, like the join, and never looks at
 what a list or a plane means."""
+import functools
 import struct
 
 import numpy as np
@@ -13,6 +14,7 @@ import store_join_cases as J
 
 PATTERN = J.PATTERN
 HOP, FRAME = J.HOP, J.FRAME
+TILE, GRID = J.TILE, J.GRID
 BAD_HEADER, ROW_BOUNDS, RAW_RANGE, NO_BLOB, BAD_CROP = 1, 2, 8, 64, 128
 
 
@@ -213,3 +215,94 @@ def store_of(c, rng, gap=True):
         at += len(b)
     chunks.append(np.full(192, PATTERN, np.uint8))
     return np.concatenate(chunks), entries
+
+
+# ------------------------------------------------------------------------------------------ tile, section and grid edges
+# Cases laid out against the mover's 16 KiB tiles of the packed destination space (tests/store_mover_paths.py names
+# what each reaches, tests/test_store_mover_paths.py holds the union of all case lists to it).  Built on first use and
+# kept, not at import.
+
+def aligned_case(name, ch, clips, filler_clip, targets):
+    """A case whose pieces lie where the tiles are.  targets: ((clip, f0, nf), anchor, want): one-frame pieces of
+    `filler_clip` - whose frame k has 16 k pairs in its first row and none else, a piece of 256 + 64 k bytes - in front
+    of the piece put its byte `anchor` on a packed offset that is `want` mod TILE (anchor None: no fillers).  Packed
+    offsets count from the rounded-up cursor."""
+    cuts, at = [], 0
+    for (clip, f0, nf), anchor, want in targets:
+        if anchor is not None:
+            for k in J.fill((want - at - anchor) % TILE):
+                cuts.append((filler_clip, k, 1))
+                at += 256 + 64 * k
+            assert (at + anchor) % TILE == want % TILE
+        cuts.append((clip, f0, nf))
+        at += len(cut(clips[clip], ch, f0, nf)[1])
+    return case(name, ch, clips, cuts)
+
+
+def _tiles_mono(rng):
+    """A mono clip of 32800 frames: frames 32744..32759 hold one pair each, 32760..32770 are full rows (44 KiB of pairs),
+    32790..32799 are raw (40 KiB of planes), everything in front is empty, so that long windows stay small."""
+    F = 32800
+    clip = J.make_blob(rng, 1, F, range(32790, 32800), J._rows(F, full=range(32760, 32771), some=[(f, 1) for f in range(32744, 32760)]))
+    fill_clip = J.make_blob(rng, 1, 65, cnt=[16 * k for k in range(65)])
+    # the whole clip with its is_raw run on a tile boundary: tiles inside one run in every section, source and
+    # destination co-aligned
+    targets = [((0, 0, F), 64, 0)]
+    # the piece on a tile boundary and 32640 + e frames: tile 1 begins in the is_raw run and its last unit in the padding,
+    # e bytes in the run's last unit; f0 = e gives the source phase
+    for e in (1, 7, 15):
+        targets.append(((0, e, 32640 + e), 0, 0))
+    # the same with the run on the boundary and 16320 + e frames
+    for e in (2, 3, 4, 5, 6, 8, 9, 10, 11, 12, 13, 14):
+        targets.append(((0, e, 16320 + e), 64, 0))
+    # the scale run, then the cnt run, ends TILE - 64 + 4 q in a tile (4112 + q frames: 16 KiB and more)
+    for which in (0, 1):
+        for q in (1, 2, 3):
+            n = 4112 + q
+            targets.append(((0, 4 * which + q, n), 64 + J.a64(n) + which * J.a64(4 * n) + 4 * n - 4 * q, TILE - 64))
+    # the pairs run: P0 = 12..15 pairs in front, 11264 + 4..1 in the window; where that is no multiple of 4, the run ends
+    # TILE - 64 + 4 q in a tile
+    for j in (12, 13, 14, 15):
+        q = (16 - j) % 4
+        targets.append(((0, 32744 + j, 30), J.layout(1, 30)[3] + 4 * (11 * HOP + 16 - j - q) if q else None, TILE - 64))
+    # the planes
+    targets.append(((0, 32780, 20), None, 0))
+    return aligned_case("tiles_mono", 1, [clip, fill_clip], 1, targets)
+
+
+def _tiles_three(rng):
+    """Three channels: the dword windows start on dword 3 f0."""
+    F = 14001
+    clip = J.make_blob(rng, 3, F, (5, 6, 7000, 14000), J._rows(F, 3, full=(20, 21, 9000), some=[(f, 1 + f % 3) for f in range(16)]))
+    cuts = [(0, f0, nf) for f0, nf in ((0, F), (1, 5500), (2, 9001), (3, 13998), (7, 6990), (6999, 7002), (9000, 1), (13990, 11))]
+    return case("tiles_three_channels", 3, [clip], cuts)
+
+
+def _small_phases(rng):
+    """Small pieces, whose tiles hold many runs: every source phase f0 = 0..15 against every count of bytes in the last
+    unit of the is_raw run, and the dword phases and counts that go with them."""
+    clip = J.make_blob(rng, 1, 48, raw=(5, 20, 21), cnt=rng.integers(0, 4, 48))
+    return case("small_phases", 1, [clip], [(0, i, 17 + i) for i in range(16)] + [(0, 15 - i, 1 + i) for i in range(15)])
+
+
+def _grid_stride(rng):
+    """The joined clips of the join's grid-stride case as the store: the 40 MiB of planes in the three pieces of its
+    seams (2550 tiles, the grid is 2048), then pieces of the two small clips, one of them on a tile boundary: headers, run
+    ends of every section and the call's short last tile all behind tile 2048."""
+    c = J.heavy_case(J.GRID_CASE)
+    clips = [J.join(blobs, 2) for blobs in c["clips"] if len(blobs) > 1]
+    clips.append(J.make_blob(rng, 2, 65, cnt=[n for k in range(65) for n in (16 * k, 0)]))
+    cuts = [(0, 0, 2000), (0, 2000, 2200), (0, 4200, 900), (1, 0, 51), (1, 3, 5), (2, 8, 1), (2, 0, 20), (2, 20, 31), (1, 40, 11), (2, 5, 3), (1, 17, 30)]
+    return aligned_case("grid_stride", 2, clips, 3, [(c, 0 if c == (2, 0, 20) else None, 0) for c in cuts])
+
+
+_HEAVY = {"tiles_mono": (_tiles_mono, 41), "tiles_three_channels": (_tiles_three, 42), "small_phases": (_small_phases, 43)}
+TILE_CASES = tuple(_HEAVY)             # names: heavy_case(name) builds
+GRID_CASE = "grid_stride"
+_HEAVY[GRID_CASE] = (_grid_stride, 44)
+
+
+@functools.lru_cache(maxsize=None)
+def heavy_case(name):
+    make, seed = _HEAVY[name]
+    return make(np.random.default_rng(20250300 + seed))

@@ -4,6 +4,7 @@ sections, write the header of the sums and zero padding; then the encoder's plac
 
 A blob here is made by the builder below, not by the codec: the join is structural and never looks at what a list or a
 plane means.  The builder makes raw frames too (stream_decode_cases.compact_blob makes none)."""
+import functools
 import struct
 
 import numpy as np
@@ -12,6 +13,8 @@ MAGIC = 0x42434C47
 FRAME = 2048
 HOP = 1024
 PATTERN = 0xA5
+TILE = 16384                          # bytes one workgroup moves at a time (csrc/glc_kernels.h kStoreMoveTile)
+GRID = 2048                           # workgroups of a move launch at most (kStoreMoveGrid): tile GRID is a second pass
 BAD_HEADER, PAIR_SUM, RAW_SUM, NO_BLOB = 1, 16, 32, 64
 
 
@@ -60,6 +63,8 @@ def make_blob(rng, ch: int, nf: int, raw=(), cnt=None) -> bytes:
         scale[f * ch:(f + 1) * ch] = 0
     pairs = []
     for n in cnt:
+        if n == 0:                    # an empty row draws nothing from the generator: skipped, the bytes stay the same
+            continue
         idx = np.sort(rng.choice(HOP, int(n), replace=False)).astype(np.uint32)
         q = rng.integers(0, 2 ** 16, int(n), dtype=np.uint32)
         pairs.append(idx | (q << 16))
@@ -277,3 +282,139 @@ def store_of(c, rng, gap=True):
         lengths.append(clip_length(f0))
     chunks.append(rng.integers(0, 256, 192, dtype=np.uint8))
     return np.concatenate(chunks), entries, segs, lengths
+
+
+# ------------------------------------------------------------------------------------------ tile, section and grid edges
+# Cases laid out against the mover's 16 KiB tiles of the packed destination space (tests/store_mover_paths.py names
+# what each reaches, tests/test_store_mover_paths.py holds the union of all case lists to it).  They are heavy - tens of
+# thousands of rows, tens of MiB - so they are built on first use and kept, not at import.
+
+def filler(ch: int, k: int) -> bytes:
+    """A one-frame blob of 256 + 64 k bytes (k in 0..64; ch <= 16): what stands between two clips to move the next."""
+    assert 0 <= k <= 64 and ch <= 16
+    return _filler(ch, k)
+
+
+@functools.lru_cache(maxsize=None)
+def _filler(ch, k):
+    return make_blob(np.random.default_rng(7000 + 100 * ch + k), ch, 1, cnt=[16 * k] + [0] * (ch - 1))
+
+
+def fill(gap: int):
+    """The k of fillers whose sizes sum to `gap` bytes (a multiple of 64) or, where gap < 256, to gap + TILE."""
+    assert gap % 64 == 0 and 0 <= gap < TILE
+    if gap == 0:
+        return []
+    if gap < 256:
+        gap += TILE
+    out = []
+    while gap:
+        size = gap if gap <= 4352 else min(4352, gap - 256)
+        out.append((size - 256) // 64)
+        gap -= size
+    return out
+
+
+def joined_bytes(blobs, ch: int) -> int:
+    F, P, R = (sum(parse_header(b)[k] for b in blobs) for k in (2, 3, 4))
+    return blob_bytes(ch, F, P, R)
+
+
+def aligned_case(name, ch, targets):
+    """A case whose clips lie where the tiles are.  targets: (segment blobs, anchor, want): one-frame filler clips in
+    front of the clip put byte `anchor` of its joined blob on a packed offset that is `want` mod TILE (anchor None: no
+    fillers).  Packed offsets count from the rounded-up cursor."""
+    clips, at = [], 0
+    for blobs, anchor, want in targets:
+        if anchor is not None:
+            for k in fill((want - at - anchor) % TILE):
+                clips.append([filler(ch, k)])
+                at += 256 + 64 * k
+            assert (at + anchor) % TILE == want % TILE
+        clips.append(blobs)
+        at += joined_bytes(blobs, ch)
+    return case(name, ch, clips)
+
+
+def _rows(nf, ch=1, full=(), some=()):
+    """List lengths of nf frames: 1024 in the frames `full` (every channel), n pairs in frame f for (f, n) of `some`;
+    frames at or behind nf are passed over."""
+    cnt = np.zeros(nf * ch, np.uint32)
+    for f in full:
+        cnt[f * ch:(f + 1) * ch] = HOP
+    for f, n in some:
+        cnt[f * ch:f * ch + 1] = n
+    return cnt
+
+
+def _tiles_mono(rng):
+    """One long mono clip for the one-run tiles with and without seams, then clips whose runs end 16 to 63 bytes in
+    front of a tile boundary, in every section and with every count of bytes in the run's last unit."""
+    # 15 segments of 1025 frames and one of 25000: the is_raw run starts on a tile; its seams lie at 1025 k, on every
+    # residue 1..15, all inside the first tile, and the next tile has none; the dword runs have seams at 4100 k.  Every
+    # segment but the 8th has two full rows and k mod 4 pairs more (the pairs seams take every dword residue, the 8th
+    # is an empty part between two seams); the last has nine full rows: 36 KiB of pairs without a seam.  Raw frames:
+    # the last six of segment 3, none in segment 4, the first six of segment 5 (an empty part between two seams inside
+    # 48 KiB of planes), and nine in the last segment.
+    segs, f0 = [], 0
+    for k in range(15):
+        raw = range(1019, 1025) if k == 3 else range(6) if k == 5 else ()
+        cnt = _rows(1025) if k == 7 else _rows(1025, full=(10, 11), some=((12, k % 4),))
+        segs.append(make_blob(rng, 1, 1025, raw, cnt))
+    segs.append(make_blob(rng, 1, 25000, range(14625, 14634), _rows(25000, full=range(100, 109))))
+    targets = [(segs, 64, 0)]
+    # the is_raw run ends 16320 + e bytes behind a tile boundary, e = 1..15: the tile begins in the run and its last unit
+    # in the padding; a seam nine frames in front of the end
+    for e in range(1, 16):
+        F = 16320 + e
+        targets.append(([make_blob(rng, 1, F - 9, cnt=_rows(F - 9)), make_blob(rng, 1, 9, cnt=_rows(9, some=((0, 3),)))], 64, 0))
+    # the scale run, then the cnt run, ends TILE - 64 + e in a tile, e = 4, 8, 12 (4113 .. 4115 frames: 16 KiB and more)
+    for which in (0, 1):
+        for q in (1, 2, 3):
+            F = 4112 + q
+            end = 64 + a64(F) + which * a64(4 * F) + 4 * F
+            targets.append(([make_blob(rng, 1, 4000, cnt=_rows(4000)), make_blob(rng, 1, F - 4000, (5,), _rows(F - 4000))], end - 4 * q, TILE - 64))
+    # the pairs run likewise: five full rows and q pairs
+    for q in (1, 2, 3):
+        blobs = [make_blob(rng, 1, 5, cnt=_rows(5, full=(0, 1, 2))), make_blob(rng, 1, 3, cnt=_rows(3, full=(0, 2), some=((1, q),)))]
+        targets.append((blobs, layout(1, 8)[3] + 4 * 5 * HOP, TILE - 64))
+    return aligned_case("tiles_mono", 1, targets)
+
+
+def _tiles_three(rng):
+    """Three channels, odd frame counts, one segment of one frame: the dword runs' seams at 12 first_frame."""
+    frames = [4673, 4661, 1, 4666]
+    segs = clip_of(rng, 3, frames, raw=(4672, 4673, 9000, 9335), cnt=lambda f0, nf: _rows(nf, 3, full=(7, 8), some=((9, 1 + f0 % 3),)))
+    small = clip_of(rng, 3, [2, 1, 5, 3], raw=(3,))
+    return aligned_case("tiles_three_channels", 3, [(segs, None, 0), (small, None, 0), (small[::-1], 64, 0)])
+
+
+def _small_phases(rng):
+    """Small clips, whose tiles hold many runs: sixteen segments of 33 frames (seams and source phases on every residue),
+    and a clip of 16 + e frames for every e = 1..15 (every count of bytes in a run's last unit)."""
+    clips = [clip_of(rng, 1, [33] * 16, raw=(32, 33, 70), cnt=lambda f0, nf: rng.integers(0, 4, nf))]
+    clips += [clip_of(rng, 1, [16, e], cnt=lambda f0, nf: rng.integers(0, 4, nf)) for e in range(1, 16)]
+    clips += [clip_of(rng, 1, [3, 2, 4], cnt=lambda f0, nf: [q] + [0] * (nf - 1)) for q in (1, 2, 3)]
+    return case("small_phases", 1, clips)
+
+
+def _grid_stride(rng):
+    """Stereo, 5100 raw frames in three segments - 40 MiB of planes, 2550 tiles, the grid is 2048 -, the second seam of
+    the planes behind tile 2048; then two small clips of twelve segments each, the second on a tile boundary: headers, seams
+    of every section and the call's short last tile all behind tile 2048."""
+    big = [make_blob(rng, 2, nf, range(nf), _rows(nf, 2)) for nf in (2000, 2200, 900)]
+    frames = [3, 5, 1, 7, 2, 9, 4, 1, 6, 2, 8, 3]
+    small = [clip_of(rng, 2, frames[k:] + frames[:k], raw=(4, 5, 20, 21, 40), cnt=lambda f0, nf: rng.integers(100, 700, 2 * nf)) for k in (0, 5)]
+    return aligned_case("grid_stride", 2, [(big, None, 0), (small[0], None, 0), (small[1], 0, 0)])
+
+
+_HEAVY = {"tiles_mono": (_tiles_mono, 31), "tiles_three_channels": (_tiles_three, 32), "small_phases": (_small_phases, 33)}
+TILE_CASES = tuple(_HEAVY)             # names: heavy_case(name) builds
+GRID_CASE = "grid_stride"
+_HEAVY[GRID_CASE] = (_grid_stride, 34)
+
+
+@functools.lru_cache(maxsize=None)
+def heavy_case(name):
+    make, seed = _HEAVY[name]
+    return make(np.random.default_rng(20250300 + seed))

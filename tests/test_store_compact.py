@@ -152,6 +152,98 @@ def test_round_edges_in_place(glc_amd, torch, rnd):
             run_case(g, torch, case, rnd=1024 + 64)
 
 
+@pytest.mark.parametrize("name", tuple(M.GRID_RUNS))
+def test_grid_stride_edges(glc_amd, torch, name):
+    """Arenas of tens of MiB (tests/store_compact_cases.py "grid-stride edges"): more tiles than the movers' grid, out of
+    place and in place; in place with a round whose 2 * tiles jobs exceed the grid and which is no multiple of the tile,
+    with a round of three tiles and 64 bytes, and as one round; and a tail of the output arrays longer than one pass."""
+    make, rnd = M.GRID_RUNS[name]
+    want = run_case(glc_amd, torch, make(), alias=name.endswith("64"), rnd=rnd)
+    assert want["n_out"] >= 7
+
+
+MIB, FAR = 1 << 20, 1 << 32
+
+
+def far_call(g, torch, mover, arena, ab, entries, lengths, keep, dst, dst_bytes):
+    """glc_store_compact_device on arenas the caller holds: (entries_out, lengths_out, new_index, n_out, cursor), every
+    array checked for its pattern margin."""
+    n = len(entries)
+    ent_in, len_in = dev(torch, entries_np(entries)), dev(torch, np.array(lengths, np.int64))
+    keep_d = dev(torch, np.array(keep, np.uint8))
+    outs = [dev(torch, np.full(k * n + MARGIN, M.PATTERN, np.uint8)) for k in (32, 8, 8)] + [dev(torch, np.full(16 + MARGIN, M.PATTERN, np.uint8))]
+    torch.cuda.synchronize()
+    assert g.lib.glc_debug_set_store_compact_round(mover._h, 0) == 0
+    rc = g.lib.glc_store_compact_device(mover._h, arena.data_ptr(), ab, ent_in.data_ptr(), len_in.data_ptr(), n, keep_d.data_ptr(), dst.data_ptr(),
+                                        dst_bytes, outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), outs[3].data_ptr(),
+                                        outs[3].data_ptr() + 8)
+    assert rc == 0, g.lib.glc_last_error(mover._h)
+    mover.synchronize()
+    got = [o.cpu().numpy() for o in outs]
+    for o, k in zip(got, (32 * n, 8 * n, 8 * n, 16)):
+        assert np.all(o[k:] == M.PATTERN)
+    counts = got[3][:16].view(np.uint64).tolist()
+    return (got[0][:32 * n].view(np.uint64).reshape(n, 4).tolist(), got[1][:8 * n].view(np.int64).tolist(),
+            got[2][:8 * n].view(np.int64).tolist(), counts[0], counts[1])
+
+
+def far_case():
+    ent, end = M.laid([64, 5 * M.TILE + 320, 64, 2 * M.TILE, 192, 64])
+    return M.case("far", ent, [0, 1, 0, 1, 1, 0], end)
+
+
+def test_in_place_beyond_4_gib(glc_amd, torch):
+    """A kept first blob of exactly 4 GiB at offset 0, which does not move; 64 dropped bytes behind it; kept blobs behind
+    those, whose new offsets lie above 2^32 and shift by 64.  Only the window behind 2^32 is written and compared (the
+    model runs on that window, its offsets shifted); the arena's first MiB, where an offset cut to 32 bits would land,
+    keeps its pattern."""
+    g = glc_amd
+    case = far_case()
+    small_h = M.arena_of(case)
+    want = M.compact(small_h, case["arena_bytes"], case["entries"], case["lengths"], case["keep"])
+    arena = torch.empty(FAR + 4 * MIB, dtype=torch.uint8, device="cuda")
+    arena[:MIB] = M.PATTERN
+    arena[FAR:FAR + 2 * MIB] = M.PATTERN
+    arena[FAR:FAR + small_h.size] = dev(torch, small_h)
+    ab = FAR + case["arena_bytes"]
+    entries = [M.entry(0, FAR, n_pairs=5)] + [M.entry(e[0] + FAR, e[1], e[2], e[3] & 0xFFFFFFFF) for e in case["entries"]]
+    got = far_call(g, torch, ctx(g, "mover"), arena, ab, entries, [77] + case["lengths"], [1] + case["keep"], arena, ab)
+    n_out = want["n_out"]
+    shifted = [[e[0] + FAR] + e[1:] for e in want["entries"][:n_out]]
+    assert got[0] == [M.entry(0, FAR, n_pairs=5)] + shifted + [[0] * 4] * (len(entries) - 1 - n_out)
+    assert got[1] == [77] + want["lengths"]
+    assert got[2] == [0] + [v + 1 if v >= 0 else v for v in want["new_index"]]
+    assert got[3:] == (n_out + 1, want["cursor"] + FAR) and want["cursor"] + 64 < case["arena_bytes"]
+    assert all(e[0] > FAR for e in shifted[1:]) and shifted[0][0] == FAR
+    assert np.array_equal(arena[FAR:FAR + small_h.size].cpu().numpy(), want["arena"])
+    assert bool((arena[FAR + small_h.size:FAR + 2 * MIB] == M.PATTERN).all()) and bool((arena[:MIB] == M.PATTERN).all())
+    del arena
+    torch.cuda.empty_cache()
+
+
+def test_out_of_place_from_beyond_4_gib(glc_amd, torch):
+    """The same store with every source above 2^32, gathered into a small destination: a source offset cut to 32 bits
+    would read the pattern of the arena's first MiBs."""
+    g = glc_amd
+    case = far_case()
+    small_h = M.arena_of(case)
+    total = sum(e[1] for e, k in zip(case["entries"], case["keep"]) if k)
+    dst_h = np.full(total + 64, M.PATTERN, np.uint8)
+    want = M.compact(small_h, case["arena_bytes"], case["entries"], case["lengths"], case["keep"], dst_h, total)
+    arena = torch.empty(FAR + 4 * MIB, dtype=torch.uint8, device="cuda")
+    arena[:3 * MIB] = M.PATTERN
+    base = FAR + MIB
+    arena[base:base + small_h.size] = dev(torch, small_h)
+    dst = dev(torch, padded(dst_h))
+    entries = [M.entry(e[0] + base, e[1], e[2], e[3] & 0xFFFFFFFF) for e in case["entries"]]
+    got = far_call(g, torch, ctx(g, "mover"), arena, FAR + 4 * MIB, entries, case["lengths"], case["keep"], dst, total)
+    assert got == (want["entries"], want["lengths"], want["new_index"], want["n_out"], want["cursor"]) and want["cursor"] == total
+    assert np.array_equal(dst.cpu().numpy(), padded(want["arena"]))
+    assert np.array_equal(arena[base:base + small_h.size].cpu().numpy(), small_h) and bool((arena[:3 * MIB] == M.PATTERN).all())
+    del arena
+    torch.cuda.empty_cache()
+
+
 def test_scan_edges(glc_amd, torch):
     for i, case in enumerate(M.scan_edges()):
         run_case(glc_amd, torch, case, alias=bool(i % 2), with_lengths=i % 3 != 2)

@@ -111,6 +111,19 @@ CASES = K.edge_cases()
 
 @pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
 def test_synthetic_against_the_model(glc_amd, torch, case):
+    synthetic(glc_amd, torch, case)
+
+
+@pytest.mark.parametrize("name", K.TILE_CASES + (K.GRID_CASE,))
+def test_tile_section_and_grid_edges(glc_amd, torch, name):
+    """The cases laid out against the mover's tiles (tests/store_cut_cases.py "tile, section and grid edges"): tiles
+    inside one run and tiles that end in its padding, in every section, every source phase and every count of bytes in
+    a run's last unit on both kinds of tile, and 40 MiB whose tiles outnumber the grid.  tests/test_store_mover_paths.py
+    names what they reach."""
+    synthetic(glc_amd, torch, K.heavy_case(name))
+
+
+def synthetic(glc_amd, torch, case):
     rng = np.random.default_rng(11)
     arena_h, entries = K.store_of(case, rng)
     ch, cuts = case["ch"], case["cuts"]
@@ -140,6 +153,61 @@ def test_without_lengths_and_python_binding(glc_amd, torch):
         assert np.array_equal(ent.cpu().numpy(), J.entry_words(want["entries"])) and lens.cpu().tolist() == want["lengths"]
         assert status.cpu().tolist() == want["status"] and int(cursor.cpu()[0]) == want["cursor"]
         assert np.array_equal(out_arena.cpu().numpy(), want["dst"])
+
+
+MIB, FAR = 1 << 20, 1 << 32
+
+
+def test_offsets_beyond_4_gib(glc_amd, torch):
+    """Source and destination arenas of 2^32 + 4 MiB bytes, allocated and never filled: both clips lie above 2^32, the
+    cursor just below it, so that the first piece lands below 2^32, the second across it and the others above.  Only the
+    two windows are written and compared (the model runs on them, its offsets shifted); the first MiB of either arena,
+    where an offset cut to 32 bits would land, keeps its pattern."""
+    g = glc_amd
+    case = next(c for c in CASES if c["name"] == "runs_longer_than_a_tile")
+    ch, cuts = case["ch"], [(0, 1, 8), (1, 1, 8), (0, 0, 10), (1, 0, 10), (0, 3, 5), (1, 9, 1)]
+    arena_h, entries = K.store_of(case, np.random.default_rng(31))
+    sizes = [len(K.cut(case["clips"][c], ch, f0, nf)[1]) for c, f0, nf in cuts]
+    size, base, win = FAR + 4 * MIB, FAR + MIB, FAR - MIB
+    cursor = FAR - sizes[0] - 100
+    dst_h = np.full(2 * MIB, K.PATTERN, np.uint8)
+    lengths = [HOP * nf - 1 for _, _, nf in cuts]
+    want = K.cut_store(arena_h, arena_h.size, entries, cuts, lengths, ch, dst_h, size - win, cursor - win)
+    assert want["entries"][1][0] + win < FAR < want["entries"][1][0] + win + sizes[1] and want["cursor"] < 2 * MIB
+    arena = torch.empty(size, dtype=torch.uint8, device="cuda")
+    dst = torch.empty(size, dtype=torch.uint8, device="cuda")
+    arena[:3 * MIB] = K.PATTERN
+    arena[base:base + arena_h.size] = dev(torch, arena_h)
+    dst[:MIB] = K.PATTERN
+    dst[win:win + 2 * MIB] = K.PATTERN
+    n = len(cuts)
+    ent_in = dev(torch, J.entry_words([[e[0] + base] + e[1:] for e in entries]))
+    ent_out = dev(torch, np.full(32 * n + MARGIN, K.PATTERN, np.uint8))
+    len_out = dev(torch, np.full(8 * n + MARGIN, K.PATTERN, np.uint8))
+    status = dev(torch, np.full(4 * n + MARGIN, K.PATTERN, np.uint8))
+    cur = dev(torch, np.array([cursor], np.uint64))
+    torch.cuda.synchronize()
+    mover = ctx(g, "mover")
+    rc = g.lib.glc_store_cut_device(mover._h, arena.data_ptr(), size, ent_in.data_ptr(), len(entries), cut_array(g, cuts), n,
+                                    (C.c_uint64 * n)(*lengths), ch, dst.data_ptr(), size, cur.data_ptr(), ent_out.data_ptr(),
+                                    len_out.data_ptr(), status.data_ptr())
+    assert rc == 0, g.lib.glc_last_error(mover._h)
+    mover.synchronize()
+    got = status.cpu().numpy()
+    assert got[:4 * n].view(np.uint32).tolist() == want["status"] == [0] * n and np.all(got[4 * n:] == K.PATTERN)
+    assert int(cur.cpu()[0]) == want["cursor"] + win
+    got = ent_out.cpu().numpy()
+    assert np.array_equal(got[:32 * n].view(np.int64).reshape(n, 4), J.entry_words([[e[0] + win] + e[1:] for e in want["entries"]]))
+    assert np.all(got[32 * n:] == K.PATTERN)
+    got = len_out.cpu().numpy()
+    assert got[:8 * n].view(np.int64).tolist() == want["lengths"] == lengths and np.all(got[8 * n:] == K.PATTERN)
+    got = dst[win:win + 2 * MIB].cpu().numpy()
+    diff = np.nonzero(got != want["dst"])[0]
+    assert diff.size == 0, ("first differing byte", int(diff[0]), "entries", want["entries"])
+    assert bool((dst[:MIB] == K.PATTERN).all()) and bool((arena[:3 * MIB] == K.PATTERN).all())
+    assert np.array_equal(arena[base:base + arena_h.size].cpu().numpy(), arena_h)
+    del arena, dst
+    torch.cuda.empty_cache()
 
 
 # ------------------------------------------------------------------------------------------ 2: real blobs

@@ -108,9 +108,21 @@ CASES = J.edge_cases()
 
 @pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
 def test_synthetic_against_the_model(glc_amd, torch, case):
+    synthetic(glc_amd, torch, case)
+
+
+@pytest.mark.parametrize("name", J.TILE_CASES + (J.GRID_CASE,))
+def test_tile_section_and_grid_edges(glc_amd, torch, name):
+    """The cases laid out against the mover's tiles (tests/store_join_cases.py "tile, section and grid edges"): tiles
+    inside one run with and without seams, tiles that end in a run's padding, every source phase and seam position on
+    both kinds of tile, and 40 MiB whose tiles outnumber the grid.  tests/test_store_mover_paths.py names what they reach."""
+    synthetic(glc_amd, torch, J.heavy_case(name))
+
+
+def synthetic(glc_amd, torch, case):
     rng = np.random.default_rng(11)
     arena_h, entries, segs, lengths = J.store_of(case, rng)
-    total = sum(len(J.join(blobs, case["ch"])) for blobs in case["clips"])
+    total = sum(J.joined_bytes(blobs, case["ch"]) for blobs in case["clips"])
     dst_h = np.full(128 + total + 512, J.PATTERN, np.uint8)
     want = run_join(glc_amd, torch, arena_h, arena_h.size, entries, segs, lengths, case["ch"], dst_h, dst_h.size, 100, case["name"])
     assert all(e[4] == 1 for e in want["entries"]) and want["entries"][0][0] == 128 and want["cursor"] == 128 + total
@@ -133,6 +145,62 @@ def test_without_lengths_and_python_binding(glc_amd, torch):
         assert np.array_equal(ent.cpu().numpy(), J.entry_words(want["entries"])) and lens.cpu().tolist() == want["lengths"]
         assert status.cpu().tolist() == want["status"] and int(cursor.cpu()[0]) == want["cursor"]
         assert np.array_equal(out_arena.cpu().numpy(), want["dst"])
+
+
+MIB, FAR = 1 << 20, 1 << 32
+
+
+def test_offsets_beyond_4_gib(glc_amd, torch):
+    """Source and destination arenas of 2^32 + 4 MiB bytes, allocated and never filled: every segment lies above 2^32,
+    the cursor just below it, so that the first clip lands below 2^32, the second across it and the others above.  Only
+    the two windows are written and compared (the model runs on them, its offsets shifted); the first MiB of either
+    arena, where an offset cut to 32 bits would land, keeps its pattern."""
+    g = glc_amd
+    rng = np.random.default_rng(31)
+    ch = 2
+    case = J.case("far", ch, next(c for c in CASES if c["name"] == "long_rows")["clips"] + three_clips(rng)["clips"])
+    arena_h, entries, segs, lengths = J.store_of(case, rng)
+    sizes = [J.joined_bytes(blobs, ch) for blobs in case["clips"]]
+    size, base, win = FAR + 4 * MIB, FAR + MIB, FAR - MIB
+    cursor = FAR - sizes[0] - 100
+    dst_h = np.full(2 * MIB, J.PATTERN, np.uint8)
+    want = J.join_store(arena_h, arena_h.size, entries, segs, lengths, ch, dst_h, size - win, cursor - win)
+    assert want["entries"][1][0] + win < FAR < want["entries"][1][0] + win + sizes[1] and want["cursor"] < 2 * MIB
+    arena = torch.empty(size, dtype=torch.uint8, device="cuda")
+    dst = torch.empty(size, dtype=torch.uint8, device="cuda")
+    arena[:3 * MIB] = J.PATTERN
+    arena[base:base + arena_h.size] = dev(torch, arena_h)
+    dst[:MIB] = J.PATTERN
+    dst[win:win + 2 * MIB] = J.PATTERN
+    n, n_clips = len(segs), len(sizes)
+    far = [[e[0] + base] + e[1:] for e in entries]
+    ent_in = dev(torch, J.entry_words(far))
+    ent_out = dev(torch, np.full(32 * n_clips + MARGIN, J.PATTERN, np.uint8))
+    len_out = dev(torch, np.full(8 * n_clips + MARGIN, J.PATTERN, np.uint8))
+    status = dev(torch, np.full(4 * n + MARGIN, J.PATTERN, np.uint8))
+    cur = dev(torch, np.array([cursor], np.uint64))
+    torch.cuda.synchronize()
+    mover = ctx(g, "mover")
+    rc = g.lib.glc_store_join_segments_device(mover._h, arena.data_ptr(), size, ent_in.data_ptr(), seg_array(g, segs), n,
+                                              (C.c_uint64 * n_clips)(*lengths), ch, dst.data_ptr(), size, cur.data_ptr(),
+                                              ent_out.data_ptr(), len_out.data_ptr(), status.data_ptr())
+    assert rc == 0, g.lib.glc_last_error(mover._h)
+    mover.synchronize()
+    got = status.cpu().numpy()
+    assert got[:4 * n].view(np.uint32).tolist() == want["status"] == [0] * n and np.all(got[4 * n:] == J.PATTERN)
+    assert int(cur.cpu()[0]) == want["cursor"] + win
+    got = ent_out.cpu().numpy()
+    assert np.array_equal(got[:32 * n_clips].view(np.int64).reshape(n_clips, 4), J.entry_words([[e[0] + win] + e[1:] for e in want["entries"]]))
+    assert np.all(got[32 * n_clips:] == J.PATTERN)
+    got = len_out.cpu().numpy()
+    assert got[:8 * n_clips].view(np.int64).tolist() == want["lengths"] and np.all(got[8 * n_clips:] == J.PATTERN)
+    got = dst[win:win + 2 * MIB].cpu().numpy()
+    diff = np.nonzero(got != want["dst"])[0]
+    assert diff.size == 0, ("first differing byte", int(diff[0]), "entries", want["entries"])
+    assert bool((dst[:MIB] == J.PATTERN).all()) and bool((arena[:3 * MIB] == J.PATTERN).all())
+    assert np.array_equal(arena[base:base + arena_h.size].cpu().numpy(), arena_h)
+    del arena, dst
+    torch.cuda.empty_cache()
 
 
 # ------------------------------------------------------------------------------------------ 2: end to end
